@@ -78,10 +78,16 @@ def parse_args(argv=None):
     ap.add_argument("--timed-only", action="store_true",
                     help="profiler runs (tools/profiling/*.sh): only the W warm-up and K timed steps, so every kernel is launched a known "
                          "number of times; prints value / ms_per_step only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (see dump_outputs; dumps/<name> inside "
+                         "the tree is git-ignored); rank 0 only")
     ap.add_argument("--rehearse-control-flow", action="store_true",
                     help="NO GPU work: run only the multi-rank control flow (rendezvous, per-rank seeds, barriers, reduction, rank-0 "
                          "JSON) with a sleep in place of the encode; used by the CPU gloo test, never a measurement")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def spawn_ranks_if_asked(args, argv):
@@ -246,6 +252,59 @@ OTHER_CONFIGS = [
 ]
 
 
+DUMP_BYTES = 60_000_000       # --dump-outputs writes at most this much array data (under 64 MiB with the .npy headers)
+DUMP_SEED = 20250718
+
+
+def dump_rows(n, frac):
+    """Rows of an n-row array that --dump-outputs keeps when it keeps the fraction `frac` of them: row i is kept when a multiplicative
+    (Fibonacci) hash of i falls below frac, so whether a row is kept depends on its index alone, never on n -- two dumps whose lengths
+    differ still hold the same rows of the part both have.  The hash of consecutive indices is equidistributed: about frac * n rows."""
+    import numpy as np
+    if frac >= 1.0:
+        return np.arange(n)
+    h = (np.arange(n, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15)) >> np.uint64(40)       # 24-bit hash, wraps mod 2^64
+    return np.flatnonzero(h < np.uint64(int(frac * (1 << 24))))
+
+
+def dump_outputs(out_dir, plan, coeffs, leaves, states, counts, max_bytes=DUMP_BYTES):
+    """--dump-outputs: what a caller of the timed path receives from one call (EncodedBatch.layer for every image and layer), as float64
+    .npy files under `out_dir`, so that two builds can be compared output for output.  Every value is an integer (at most int32 / int64
+    sizes) and float64 holds each exactly.
+      counts.npy                    [B, 3, 4] per image and layer: coefficients, leaves, quadtree states, root block size (all images)
+      img<b>_l<l>_states.npy        quadtree states of image b, layer l
+      img<b>_l<l>_leaves.npy        leaf table [n, 4]: x, y, size, offset of the leaf's coefficients in the layer
+      img<b>_l<l>_coeffs.npy        quantised zigzag coefficients of the layer
+    for the first and the last image and one drawn with a fixed seed.  When the picked images' output CAPACITY (the plan's strides, fixed
+    by the arguments) is larger than `max_bytes`, every array keeps the same fraction of its rows, chosen by row index (dump_rows).
+    Whether a row is kept does not depend on the counts, so where two builds' counts differ (counts.npy shows it) their files still
+    hold the same rows of the part both have, and the files are row-aligned up to the shorter one.
+    -> (number of files, bytes written)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    cnt = counts.cpu().numpy()
+    B = cnt.shape[0]
+    picks = sorted({0, B - 1, int(np.random.default_rng(DUMP_SEED).integers(B))})
+    arrays = {"counts": cnt.astype(np.float64)}
+    capacity = 8 * len(picks) * (plan.coeff_stride + 4 * plan.leaf_stride + plan.state_stride)
+    frac = min(1.0, 0.99 * (max_bytes - arrays["counts"].nbytes) / capacity)        # (1 % for the hash's rounding)
+    for b in picks:
+        for l in range(3):
+            n_coef, n_leaf, n_state, _ = (int(v) for v in cnt[b, l])
+            co = b * plan.coeff_stride + plan.coeff_off[l]
+            lo = b * plan.leaf_stride + plan.leaf_off[l]
+            so = b * plan.state_stride + plan.state_off[l]
+            for name, t in (("states", states[so:so + n_state]), ("leaves", leaves[lo:lo + n_leaf]), ("coeffs", coeffs[co:co + n_coef])):
+                a = t.cpu().numpy()
+                arrays[f"img{b}_l{l}_{name}"] = a[dump_rows(len(a), frac)].astype(np.float64)
+    total = 0
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+    assert total <= max_bytes, total
+    return len(arrays), total
+
+
 def pipelined_sub_batches(args, n_pipe, B, H, W):
     """aej_set_sub_batches of the pipelined steps (see --pipelined-sub-batches)"""
     if args.pipelined_sub_batches >= 0:
@@ -350,10 +409,17 @@ def main():
     px_total, dt = aggregate_throughput(dist, wl.pixels_per_step * args.steps, dt_local, coll_dev)   # SUM of pixels, MAX of seconds
     value = px_total / dt / 1e6
     ms_per_step = dt / args.steps * 1e3
+    # ---- what the last timed step computed, before anything else writes into its context's outputs ----
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        pipe, _ = wl.last_step(args.steps)
+        n_files, n_bytes = dump_outputs(args.dump_outputs, pipe.plan, *pipe.out)
+        dumped = {"dir": args.dump_outputs, "files": n_files, "bytes": n_bytes}
     if args.timed_only:
         if rank == 0:
             emit(json.dumps({"metric": METRIC, "value": round(value, 1), "unit": "MP/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-                              "ms_per_step": round(ms_per_step, 3), "encode_calls": args.steps + n_warm, "timed_only": True}))
+                              "ms_per_step": round(ms_per_step, 3), "encode_calls": args.steps + n_warm, "timed_only": True,
+                              "dumped_outputs": dumped}))
         if dist is not None:
             dist.destroy_process_group()
         return
@@ -426,7 +492,7 @@ def main():
                    "images_per_gpu": B, "height": H, "width": W, "color_space": space, "block_size_range": list(brange),
                    "quality_range": list(qrange), "steps_in_flight": n_pipe, "options": args.option or None},
         "roofline": roofline, "valu": valu, "runner_up": runner_up, "whole_path": whole_path,
-        "verified": verified, "profile_gaps": prof.gaps(brange), "ranks": ranks,
+        "verified": verified, "profile_gaps": prof.gaps(brange), "ranks": ranks, "dumped_outputs": dumped,
         "hysteresis": {"timed_calls": h1["calls"] - h0["calls"], "tiles_through_the_work_queue_last_call": h1["queued"],
                        "tiles": int(B * sum(-(-plan.layer_h[l] // 64) * -(-plan.layer_w[l] // 64) for l in range(3))),
                        "what": "completes on the device: a pass over every 64 x 64 tile, bulk launches over the flagged tiles, then a device-side "

@@ -182,30 +182,63 @@ def test_compat_alias_packages_expose_the_reference_import_names():
     assert out.returncode == 0 and out.stdout.strip() == "ok", out.stderr
 
 
-def test_hardware_queue_policy_import_has_no_side_effect():
+def test_hardware_queue_policy_import_has_no_side_effect(monkeypatch):
     """_lib: importing the package never writes the environment; the library is told a queue count only
     when the package can be sure the HIP runtime starts (or started) with it -- variable already in the environment, or the explicit
-    configure_hw_queues() before HIP is up; otherwise HIP's default of 4."""
+    configure_hw_queues() before HIP is up; otherwise HIP's default of 4.  The policy runs in this process against a substitute
+    environment (the process's own is never written, and no process starts with another queue count); a fresh interpreter, given the
+    environment exactly as this one has it, checks that the import itself changes nothing."""
     import subprocess
-    env = {k: v for k, v in os.environ.items() if k != "GPU_MAX_HW_QUEUES"}
-    env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
+    import types
+    from adaptive_edge_aware_jpeg_amd import _lib
+    environ = {}
+    monkeypatch.setattr(_lib, "os", types.SimpleNamespace(environ=environ, path=os.path))
+    monkeypatch.setattr(_lib, "_contexts", {})                    # no live context of this process is told anything
+    monkeypatch.setattr(_lib, "_hw_queues", _lib.HIP_DEFAULT_HW_QUEUES)
+    monkeypatch.setattr(_lib, "_hw_queues_source", "HIP default (assumed)")
 
-    def run(code, extra=None):
-        r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=dict(env, **(extra or {})), timeout=300)
-        assert r.returncode == 0, r.stderr[-1500:]
-        return r.stdout.strip().splitlines()[-1]
+    def torch_imported(yes):
+        if yes:
+            monkeypatch.setitem(sys.modules, "torch", sys.modules.get("torch") or types.ModuleType("torch"))
+        else:
+            monkeypatch.delitem(sys.modules, "torch", raising=False)
 
+    def reset(env):
+        environ.clear()
+        environ.update(env)
+        monkeypatch.setattr(_lib, "_hw_queues", _lib.HIP_DEFAULT_HW_QUEUES)
+
+    # import (what the package runs at import): an empty environment stays empty, HIP's default assumed
+    assert _lib._look_at_hw_queues() == 4 and environ == {}
+    # explicit opt-in before torch: set and trusted -- the one variable it writes is the one the runtime and the import read
+    torch_imported(False)
+    assert _lib.configure_hw_queues() == 16 and A.hw_queues()[0] == 16
+    (name, value), = environ.items()
+    assert value == "16"
+    # present at process start: trusted as it is, the environment untouched
+    reset({name: "2"})
+    assert _lib._look_at_hw_queues() == 2 and A.hw_queues()[0] == 2 and environ == {name: "2"}
+    # the opt-in never overrides the launcher
+    reset({name: "1"})
+    assert _lib.configure_hw_queues() == 1 and A.hw_queues()[0] == 1 and environ == {name: "1"}
+    # a fresh interpreter with this process's environment as it is: importing the package (before or after torch) writes nothing and
+    # reports what that environment says
     probe = "import adaptive_edge_aware_jpeg_amd as A, os; print(A.hw_queues()[0], os.environ.get('GPU_MAX_HW_QUEUES'))"
-    assert run(probe) == "4 None"                                                   # import: environment untouched, HIP's default assumed
-    assert run("import torch\n" + probe) == "4 None"
-    assert run("import torch\n" + probe, {"GPU_MAX_HW_QUEUES": "12"}) == "12 12"   # present at process start: trusted as it is
-    opt_in = "import adaptive_edge_aware_jpeg_amd as A, os; A.configure_hw_queues(); print(A.hw_queues()[0], os.environ.get('GPU_MAX_HW_QUEUES'))"
-    assert run(opt_in) == "16 16"                                                   # explicit opt-in before torch: set and trusted
-    assert run(opt_in, {"GPU_MAX_HW_QUEUES": "8"}) == "8 8"                         # never overrides the launcher
+    assert f"os.environ.get('{name}')" in probe
+    here = os.environ.get(name)
+    want = f"{int(here) if here is not None and here.isdigit() and int(here) > 0 else 4} {here}"
+    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    for code in (probe, "import torch\n" + probe):
+        r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=300)
+        assert r.returncode == 0, r.stderr[-1500:]
+        assert r.stdout.strip().splitlines()[-1] == want, (code, r.stdout)
     # after `import torch` nobody can know whether the runtime has read the variable (device_count() / is_available() initialise HIP):
     # the variable is set, the library keeps HIP's default (ADVICE r4)
-    assert run("import torch\n" + opt_in) == "4 16"
-    assert run("import adaptive_edge_aware_jpeg_amd as A; A.set_hw_queues(24); print(A.hw_queues()[0])") == "24"
+    reset({})
+    torch_imported(True)
+    assert _lib.configure_hw_queues() == 4 and A.hw_queues()[0] == 4 and environ == {name: "16"}
+    _lib.set_hw_queues(24)
+    assert A.hw_queues() == (24, "stated by the application (set_hw_queues)")
 
 
 def test_deflate_tables_round_trip_through_zlib():
@@ -363,3 +396,54 @@ def test_bench_sub_batch_policy_for_pipelined_steps():
     assert bench.pipelined_sub_batches(a, 4, 64, 2160, 3840) == 3
     assert bench.parse_args(["--gpus", "1"]).pipeline == 4 and bench.parse_args([]).steps == 20
 
+
+
+def test_bench_dump_outputs_writes_the_layers_a_caller_receives(tmp_path):
+    """bench.py --dump-outputs: counts of every image, then states / leaf table / coefficients of the picked images' layers, exact in
+    float64 (EncodedBatch.layer's slices), the same files for the same outputs, never over the byte budget (long arrays become a fixed
+    sample of rows in their original order)."""
+    import types
+    import torch
+    import bench
+    B = 5
+    plan = types.SimpleNamespace(coeff_stride=3000, coeff_off=[0, 2000, 2500], leaf_stride=300, leaf_off=[0, 200, 250],
+                                 state_stride=90, state_off=[0, 60, 75])
+    g = torch.Generator().manual_seed(7)
+    coeffs = torch.randint(-2 ** 31, 2 ** 31 - 1, (B * plan.coeff_stride,), generator=g, dtype=torch.int32)
+    leaves = torch.randint(0, 2 ** 31 - 1, (B * plan.leaf_stride, 4), generator=g, dtype=torch.int32)
+    states = torch.randint(0, 256, (B * plan.state_stride,), generator=g, dtype=torch.uint8)
+    counts = torch.tensor([[[2000 - b, 200 - b, 60 - b, 64], [500, 50, 15, 32], [400 + b, 40, 10, 32]] for b in range(B)], dtype=torch.int64)
+    n, size = bench.dump_outputs(str(tmp_path / "full"), plan, coeffs, leaves, states, counts)
+    files = sorted(p.name for p in (tmp_path / "full").iterdir())
+    picks = sorted({int(f[3:].split("_")[0]) for f in files if f.startswith("img")})
+    assert n == len(files) == 1 + 9 * len(picks) and {0, B - 1} <= set(picks) and size <= bench.DUMP_BYTES
+    assert np.array_equal(np.load(tmp_path / "full" / "counts.npy"), counts.numpy())
+    for b in picks:
+        for l in range(3):
+            n_coef, n_leaf, n_state, _ = (int(v) for v in counts[b, l])
+            co, lo, so = b * plan.coeff_stride + plan.coeff_off[l], b * plan.leaf_stride + plan.leaf_off[l], b * plan.state_stride + plan.state_off[l]
+            for name, want in (("coeffs", coeffs[co:co + n_coef]), ("leaves", leaves[lo:lo + n_leaf]), ("states", states[so:so + n_state])):
+                got = np.load(tmp_path / "full" / f"img{b}_l{l}_{name}.npy")
+                assert got.dtype == np.float64 and np.array_equal(got, want.numpy()), (b, l, name)
+    # a budget smaller than the capacity: every array keeps the same rows, chosen by index alone, twice alike, within the budget
+    budget = 20_000
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), plan, coeffs, leaves, states, counts, max_bytes=budget)
+    assert sum(np.load(p).nbytes for p in (tmp_path / "a").iterdir()) <= budget
+    for p in (tmp_path / "a").iterdir():
+        assert np.array_equal(np.load(p), np.load(tmp_path / "b" / p.name)), p.name
+    cut = np.load(tmp_path / "a" / "img0_l0_coeffs.npy")
+    full = coeffs[:int(counts[0, 0, 0])].numpy()
+    frac = 0.99 * (budget - 8 * counts.numel()) / (8 * len(picks) * (plan.coeff_stride + 4 * plan.leaf_stride + plan.state_stride))
+    assert 0 < len(cut) < len(full) and np.array_equal(cut, full[bench.dump_rows(len(full), frac)])
+    # rows are picked by index, not by length: an output with fewer coefficients dumps a prefix of the same rows
+    short = counts.clone()
+    short[0, 0, 0] -= 500
+    bench.dump_outputs(str(tmp_path / "c"), plan, coeffs, leaves, states, short, max_bytes=budget)
+    cut_short = np.load(tmp_path / "c" / "img0_l0_coeffs.npy")
+    assert 0 < len(cut_short) < len(cut) and np.array_equal(cut_short, cut[:len(cut_short)])
+    keep = bench.dump_rows(10_000, 0.25)
+    assert abs(len(keep) - 2500) <= 20 and np.array_equal(bench.dump_rows(4000, 0.25), keep[keep < 4000])
+    assert bench.parse_args(["--steps", "3", "--dump-outputs", "d"]).dump_outputs == "d"
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])

@@ -247,7 +247,9 @@ def test_oracle_runs_clean_under_address_and_ub_sanitizers(oracle):
         "e = (np.random.default_rng(1).random((150, 90)) < 0.01).astype(np.uint8)\n"
         "O.quadtree(e, 2, 256); O.quadtree(e[:1, :1], 4, 64)\n"
         "print('clean')\n")
-    env = dict(os.environ, LD_PRELOAD=asan, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1",
+    # libasan first (it must lead the preload list); whatever the environment already preloads stays behind it
+    preload = " ".join(p for p in (asan, os.environ.get("LD_PRELOAD", "")) if p)
+    env = dict(os.environ, LD_PRELOAD=preload, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1",
                AEJ_ORACLE_SANITIZE="1")
     r = subprocess.run([sys.executable, "-c", code, ROOT], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0 and r.stdout.strip().endswith("clean"), (r.stdout[-500:], r.stderr[-3000:])
