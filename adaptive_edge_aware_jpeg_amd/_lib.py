@@ -177,7 +177,17 @@ SIGNATURES = {
     "aej_decode_batch": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _U64]),
     "aej_color_convert_inverse": (_I, [_P, _I, _P, _P, _I64]),
     "aej_leaf_positions_host": (_I64, [_P, _I64, _I, _I, _I, _P]),
+    "aej_inflate_batch": (_I, [_P, _P, _P, _I, _P, _U64, _P, _P]),
+    "aej_decode_headers_workspace_bytes": (_U64, [_P, _I, _I, _I]),
+    "aej_decode_headers": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _U64]),
 }
+
+# status values of aej_inflate_batch / aej_decode_headers (include/aej.h AEJ_INFLATE_* / AEJ_HEADER_*)
+INFLATE_STATUS = ["ok", "bad zlib header", "bad block type", "bad code lengths", "invalid literal/length or distance code",
+                  "distance too far back", "stored block LEN/NLEN mismatch", "truncated stream", "output over capacity",
+                  "Adler-32 mismatch", "bad stream descriptor"]
+HEADER_STATUS = ["ok", "more leaves than the layer holds", "leaf size outside the block-size range of the header",
+                 "quadtree header does not tile the layer", "coefficient count does not match the quadtree header", "bad layer descriptor"]
 
 
 def load_library():

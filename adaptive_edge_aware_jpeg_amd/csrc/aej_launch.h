@@ -133,6 +133,21 @@ void launch_deflate(hipStream_t st, const int *coeffs, const long long *counts, 
                     const long long *coeff_cap, const unsigned *tables /* [3][448] or null */, int reuse_parse, unsigned char *out,
                     unsigned long long stream_stride, long long *sizes, void *workspace);
 
+// inflate.hip -- zlib streams (RFC 1950 / 1951), one wave per stream.  desc: device [n][4] int64 = in_off, in_len, out_off, out_cap (bytes)
+void launch_inflate(hipStream_t st, const unsigned char *src, const long long *desc, int n, unsigned char *dst, long long dst_bytes,
+                    long long *out_bytes, int *status);
+
+// headers.hip -- quadtree headers of .ajpg layers -> leaf tables and counts in the plan layout
+struct HdrGeom {
+    int bmin, bmax;
+    int h[3], w[3];
+    int proot[3];                        // root of the position walk (QtGeom::root: 2 * largest_power_of_2(max(h, w)), jpeg.py:425)
+    long long leaf_off[3], leaf_span[3], leaf_stride;
+    long long coeff_span[3];
+};
+void launch_headers(hipStream_t st, const unsigned char *states, const long long *desc, const long long *inflated, int nlayers, const HdrGeom &g,
+                    unsigned char *codes, int *leaves, long long *counts, int *status);
+
 // metrics.hip
 void launch_metric_prep(hipStream_t st, const float *a, const float *b, int B, long long npx, double *acc, unsigned char *ga, unsigned char *gb);
 void launch_metric_pool_grey(hipStream_t st, const unsigned char *ga, const unsigned char *gb, int B, int H, int W, int f, int hp, int wp, float *xa,

@@ -1344,6 +1344,66 @@ extern "C" int64_t aej_leaf_positions_host(const int32_t *sizes_host, int64_t n,
     return li;
 }
 
+// ---- .ajpg containers decoded on the device (inflate.hip, headers.hip) ----------------------------------------------------------------
+extern "C" int aej_inflate_batch(aej_ctx *ctx, const uint8_t *src, const int64_t *streams, int n, uint8_t *dst, uint64_t dst_bytes,
+                                 int64_t *out_bytes, int32_t *status)
+{
+    if (!ctx) return AEJ_ERR_ARG;
+    if (call_in_flight(ctx)) return fail(ctx, AEJ_ERR_STATE, "%s between aej_encode_batch_begin and aej_encode_batch_end", __func__);
+    if (n < 0) return fail(ctx, AEJ_ERR_ARG, "negative stream count");
+    if (n == 0) return 0;
+    if (!src || !streams || !dst || !out_bytes || !status) return fail(ctx, AEJ_ERR_ARG, "NULL buffer");
+    if (reinterpret_cast<uintptr_t>(src) & 3 || reinterpret_cast<uintptr_t>(dst) & 3) return fail(ctx, AEJ_ERR_ARG, "src and dst must be 4-byte aligned");
+    if (dst_bytes > (uint64_t)INT64_MAX) return fail(ctx, AEJ_ERR_ARG, "dst_bytes too large");
+    AEJ_HIP_CHECK(hipSetDevice(ctx->device));
+    launch_inflate(ctx->stream, src, reinterpret_cast<const long long *>(streams), n, dst, (long long)dst_bytes,
+                   reinterpret_cast<long long *>(out_bytes), status);
+    AEJ_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" uint64_t aej_decode_headers_workspace_bytes(aej_ctx *ctx, int batch, int H, int W)
+{
+    if (check_encode_args(ctx, batch, H, W)) return 0;
+    Geom g;
+    QtGeom q;
+    if (make_geom(ctx, ctx->space, batch, H, W, g) || make_qtgeom(ctx, g, ctx->bmin, ctx->bmax, q)) return 0;
+    return ((unsigned long long)batch * q.leaf_stride + 255) & ~255ull;         // one log2(size) byte per leaf slot
+}
+
+extern "C" int aej_decode_headers(aej_ctx *ctx, const uint8_t *states, const int64_t *layers, const int64_t *inflated_bytes, int batch, int H, int W,
+                                  int32_t *leaves, int64_t *counts, int32_t *status, void *workspace, uint64_t workspace_bytes)
+{
+    int rc = check_encode_args(ctx, batch, H, W);
+    if (rc) return rc;
+    if (call_in_flight(ctx)) return fail(ctx, AEJ_ERR_STATE, "%s between aej_encode_batch_begin and aej_encode_batch_end", __func__);
+    if (!states || !layers || !inflated_bytes || !leaves || !counts || !status || !workspace) return fail(ctx, AEJ_ERR_ARG, "NULL buffer");
+    if (reinterpret_cast<uintptr_t>(leaves) & 15 || reinterpret_cast<uintptr_t>(workspace) & 15) return fail(ctx, AEJ_ERR_ARG, "leaves and workspace must be 16-byte aligned");
+    AEJ_HIP_CHECK(hipSetDevice(ctx->device));
+    Geom g;
+    QtGeom q;
+    if ((rc = make_geom(ctx, ctx->space, batch, H, W, g))) return rc;
+    if ((rc = make_qtgeom(ctx, g, ctx->bmin, ctx->bmax, q))) return rc;
+    if ((unsigned long long)batch * q.leaf_stride > workspace_bytes)
+        return fail(ctx, AEJ_ERR_CAPACITY, "workspace too small: need %llu bytes", (unsigned long long)batch * q.leaf_stride);
+    HdrGeom hg;
+    hg.bmin = q.bmin;
+    hg.bmax = q.bmax;
+    for (int l = 0; l < 3; l++) {
+        hg.h[l] = g.h[l];
+        hg.w[l] = g.w[l];
+        hg.proot[l] = q.root[l];
+        hg.leaf_off[l] = q.leaf_off[l];
+        hg.leaf_span[l] = (l < 2 ? q.leaf_off[l + 1] : q.leaf_stride) - q.leaf_off[l];
+        hg.coeff_span[l] = (l < 2 ? q.coeff_off[l + 1] : q.coeff_stride) - q.coeff_off[l];
+    }
+    hg.leaf_stride = q.leaf_stride;
+    launch_headers(ctx->stream, states, reinterpret_cast<const long long *>(layers), reinterpret_cast<const long long *>(inflated_bytes), batch * 3, hg,
+                   static_cast<unsigned char *>(workspace), leaves, reinterpret_cast<long long *>(counts), status);
+    AEJ_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 extern "C" int aej_color_convert_inverse(aej_ctx *ctx, int space, const float *in, float *out_rgb, int64_t n)
 {
     if (!ctx) return AEJ_ERR_ARG;

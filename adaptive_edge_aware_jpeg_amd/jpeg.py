@@ -29,6 +29,48 @@ def usable_cpus() -> int:
         return max(1, os.cpu_count() or 1)
 
 
+HEADER_FIELDS = ("height", "width", "num_layers", "color_space", "quality_min", "quality_max", "block_size_min", "block_size_max", "extension")
+
+
+def parse_container(data):
+    """The framing of one ``.ajpg`` file (jpeg.py:599-661) and nothing else: -> (header dict, [(n_states, root_size, packed state bytes,
+    zlib stream)] per layer), the byte pieces as memoryviews into ``data``.  Reads as ``Jpeg._entropy_decode`` reads (a short read at the
+    end gives what is there), so the state symbols of a layer are ``min(bits_len // 2, 4 * len(packed))``."""
+    view = memoryview(data).cast("B")
+    pos = 0
+
+    def read(k):
+        nonlocal pos
+        piece = view[pos:pos + max(k, 0)]
+        pos += len(piece)
+        return piece
+
+    mlen = int.from_bytes(read(4), byteorder="big")
+    meta = json.loads(bytes(read(mlen)).decode("utf-8"))
+    if not isinstance(meta, dict) or not isinstance(meta.get("num_layers"), int):
+        raise ValueError("corrupt stream: bad container header")
+    layers = []
+    for _ in range(meta["num_layers"]):
+        bits_len = int.from_bytes(read(4), byteorder="big")
+        root = int.from_bytes(read(4), byteorder="big")
+        packed = read((bits_len + 7) // 8)
+        clen = int.from_bytes(read(4), byteorder="big")
+        layers.append((min(bits_len // 2, 4 * len(packed)), root, packed, read(clen)))
+    return meta, layers
+
+
+def check_same_headers(metas):
+    """-> the header every file of a decompress_many call shares; ValueError naming the first file and field that differ."""
+    first = metas[0]
+    if first.get("num_layers") != 3:
+        raise ValueError(f"file 0: num_layers is {first.get('num_layers')!r}, the codec writes 3")
+    for i, m in enumerate(metas[1:], 1):
+        for k in HEADER_FIELDS:
+            if m.get(k) != first.get(k):
+                raise ValueError(f"file {i} differs from file 0 in header field {k!r}: {m.get(k)!r} != {first.get(k)!r}")
+    return first
+
+
 class EncodedBatch:
     """Device-resident result of the encode hot path for a batch (layout: include/aej.h, aej_plan)."""
 
@@ -276,6 +318,137 @@ class Jpeg:
         enc = EncodedBatch(plan, ctx.to_device(coeffs, t.int32), ctx.to_device(leaves, t.int32), None, ctx.to_device(counts, t.int64))
         rgb = self.decompress_batch(enc)[0].cpu().numpy()
         return Image.from_array(rgb, rgb.shape, self.extension)
+
+    def decompress_many(self, files, entropy: str = "gpu", workers: Optional[int] = None):
+        """``decompress`` for a sequence of ``.ajpg`` files with one header: -> torch float32 [B, H, W, 3] on the codec's device, element i
+        bit-identical to ``decompress(files[i]).data``.  The host reads only the container framing (``parse_container``); the packed state
+        symbols and the zlib streams of the whole batch cross to the GPU in one copy, where ``aej_inflate_batch`` (``entropy="gpu"``) decodes
+        the streams straight into the coefficient layout and ``aej_decode_headers`` turns the quadtree headers into leaf tables, with every
+        check ``decompress`` makes.  ``entropy="host"``: ``zlib.decompress`` on a thread pool instead (the A / B partner).  Settings and
+        extension come from the header, as in ``decompress``.  Raises ``ValueError`` for an empty sequence, files whose headers differ, and
+        any file ``decompress`` would refuse."""
+        if entropy not in ("gpu", "host"):
+            raise ValueError("entropy must be 'gpu' or 'host'")
+        parsed = [parse_container(f) for f in files]
+        if not parsed:
+            raise ValueError("decompress_many needs at least one file")
+        meta = check_same_headers([m for m, _ in parsed])
+        self.extension = meta["extension"]
+        self.update_settings(JpegCompressionSettings(color_space=meta["color_space"],
+                                                     quality_range=(meta["quality_min"], meta["quality_max"]),
+                                                     block_size_range=(meta["block_size_min"], meta["block_size_max"])),
+                             (meta["height"], meta["width"]))
+        H, W = self.layer_shape
+        B = len(parsed)
+        ctx = self._bind()
+        t = ctx.torch
+        plan = ctx.plan(B, H, W)
+        n = 3 * B
+        span = [((plan.coeff_off[l + 1] if l < 2 else plan.coeff_stride) - plan.coeff_off[l]) for l in range(3)]
+        recs = [rec for _, layers in parsed for rec in layers]           # (n_states, root, packed, stream) per (image, layer)
+
+        def align(v, a=16):
+            return (v + a - 1) // a * a
+
+        # one page-locked staging buffer, one host-to-device copy: stream descriptors, layer descriptors, inflated sizes, states, streams
+        off_sd = 0
+        off_ld = off_sd + align(n * 4 * 8)
+        off_inf = off_ld + align(n * 3 * 8)
+        pos = off_inf + align(n * 8)
+        st_off = []
+        for r in recs:
+            st_off.append(pos)
+            pos = align(pos + len(r[2]), 4)
+        in_off = []
+        if entropy == "gpu":
+            for r in recs:
+                in_off.append(pos)
+                pos = align(pos + len(r[3]), 4)
+        total = align(pos)
+        stage = ctx.pinned(total)[:total]
+        host = stage.numpy()
+        sd = host[off_sd:off_sd + n * 32].view(np.int64).reshape(n, 4)
+        ld = host[off_ld:off_ld + n * 24].view(np.int64).reshape(n, 3)
+        inf = host[off_inf:off_inf + n * 8].view(np.int64)
+        for i, r in enumerate(recs):
+            b, l = divmod(i, 3)
+            ld[i] = (st_off[i], r[0], r[1])
+            host[st_off[i]:st_off[i] + len(r[2])] = np.frombuffer(r[2], np.uint8)
+            if entropy == "gpu":
+                host[in_off[i]:in_off[i] + len(r[3])] = np.frombuffer(r[3], np.uint8)
+                sd[i] = (in_off[i], len(r[3]), 4 * (b * plan.coeff_stride + plan.coeff_off[l]), 4 * span[l])
+        coeffs = ctx.empty((B * plan.coeff_stride,), t.int32)
+        if entropy == "host":
+            inf[:] = self._inflate_on_host(ctx, recs, coeffs, plan, span, workers)
+        dev = ctx.empty((total,), t.uint8)
+        dev.copy_(stage, non_blocking=True)
+        base = dev.data_ptr()
+        stat = ctx.empty((2, n), t.int32)
+        if entropy == "gpu":
+            inflated = ctx.empty((n,), t.int64)
+            ctx.check(ctx.lib.aej_inflate_batch(ctx.handle, base, base + off_sd, n, coeffs.data_ptr(), ctypes.c_uint64(4 * coeffs.numel()),
+                                                inflated.data_ptr(), stat[0].data_ptr()))
+            inflated_ptr = inflated.data_ptr()
+        else:
+            stat[0].zero_()
+            inflated_ptr = base + off_inf
+        leaves = ctx.empty((B * plan.leaf_stride, 4), t.int32)
+        counts = ctx.empty((B, 3, 4), t.int64)
+        nws = int(ctx.lib.aej_decode_headers_workspace_bytes(ctx.handle, B, H, W))
+        ws = ctx.workspace(nws)
+        ctx.check(ctx.lib.aej_decode_headers(ctx.handle, base, base + off_ld, inflated_ptr, B, H, W, leaves.data_ptr(),
+                                             counts.data_ptr(), stat[1].data_ptr(), ws.data_ptr(), ctypes.c_uint64(nws)))
+        s = stat.cpu().numpy()                       # the only read-back before the decode; it also ends the staging buffer's use
+        from ._lib import HEADER_STATUS, INFLATE_STATUS
+        for i in range(n):
+            if s[0, i]:
+                raise ValueError(f"corrupt stream: {INFLATE_STATUS[s[0, i]] if s[0, i] < len(INFLATE_STATUS) else s[0, i]} (image {i // 3}, layer {i % 3})")
+            if s[1, i]:
+                raise ValueError(f"corrupt stream: {HEADER_STATUS[s[1, i]] if s[1, i] < len(HEADER_STATUS) else s[1, i]} (image {i // 3}, layer {i % 3})")
+        return self.decompress_batch(EncodedBatch(plan, coeffs, leaves, None, counts))
+
+    def _inflate_on_host(self, ctx, recs, coeffs, plan, span, workers):
+        """entropy="host" of decompress_many: zlib.decompress of every stream on a thread pool, each result through a page-locked buffer
+        into its layer's slot of ``coeffs``.  -> the inflated sizes."""
+        from concurrent.futures import ThreadPoolExecutor
+        t = ctx.torch
+        dst = coeffs.view(t.uint8)
+        chunk = 256 << 20
+        buf = self.__dict__.get("_inflate_pinned")
+        if buf is None:
+            buf = self._inflate_pinned = t.empty(chunk, dtype=t.uint8, pin_memory=True)
+        hb = buf.numpy()
+        sizes = []
+        used = 0
+
+        def one(r):
+            try:
+                return zlib.decompress(r[3])
+            except zlib.error as e:
+                return e
+
+        with ThreadPoolExecutor(max_workers=workers or usable_cpus()) as ex:
+            for i, raw in enumerate(ex.map(one, recs)):
+                b, l = divmod(i, 3)
+                if isinstance(raw, zlib.error):
+                    raise ValueError(f"corrupt stream: {raw} (image {b}, layer {l})")
+                nb = len(raw)
+                sizes.append(nb)
+                if nb > 4 * span[l]:
+                    raise ValueError(f"corrupt stream: coefficient count does not match the quadtree header (image {b}, layer {l})")
+                o = 4 * (b * plan.coeff_stride + plan.coeff_off[l])
+                done = 0
+                while done < nb:
+                    if used == chunk:                    # the buffer is full: wait for its copies before refilling it
+                        t.cuda.current_stream(ctx.device).synchronize()
+                        used = 0
+                    k = min(nb - done, chunk - used)
+                    hb[used:used + k] = np.frombuffer(raw, np.uint8, k, done)
+                    dst[o + done:o + done + k].copy_(buf[used:used + k], non_blocking=True)
+                    used += k
+                    done += k
+        t.cuda.current_stream(ctx.device).synchronize()
+        return sizes
 
     def _entropy_decode(self, encoded_data: bytes):
         """Container parsing of jpeg.py:599-661: restores settings from the JSON header (jpeg.py:613-631) and returns the

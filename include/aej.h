@@ -281,6 +281,38 @@ AEJ_API int aej_color_convert_inverse(aej_ctx *ctx, int space, const float *in, 
  * leaves leave a part of the layer uncovered. */
 AEJ_API int64_t aej_leaf_positions_host(const int32_t *sizes_host, int64_t n, int root, int H, int W, int32_t *xy_host);
 
+/* ---- .ajpg containers decoded on the device (Jpeg.decompress_many): the entropy decode and the quadtree headers ------------------
+ * Both calls only enqueue work on the context's stream (no synchronisation, no read-back); their per-stream / per-layer status arrays
+ * stay on the device for the caller.  The inflate needs no workspace (its state lives in LDS).
+ *
+ * aej_inflate_batch: n zlib streams (RFC 1950 / 1951: stored, fixed and dynamic blocks, Adler-32 checked, bytes after the trailer ignored),
+ *   one wave per stream.  streams: device [n][4] int64 = { input offset in src (bytes, a multiple of 4), input length, output offset in dst
+ *   (bytes, a multiple of 4), output capacity (bytes) }; src and dst must be 4-byte aligned.  A stream writes only inside
+ *   [out_off, out_off + cap), which must lie inside dst_bytes.  out_bytes[i] (device int64): bytes decoded; status[i] (device int32):
+ *   AEJ_INFLATE_*.  A bad stream leaves the others alone. */
+enum {
+    AEJ_INFLATE_OK = 0, AEJ_INFLATE_BAD_HEADER = 1 /* CM, CINFO, FCHECK or FDICT */, AEJ_INFLATE_BAD_BLOCK_TYPE = 2,
+    AEJ_INFLATE_BAD_CODE_LENGTHS = 3 /* over-subscribed / incomplete code, bad repeat, too many symbols */,
+    AEJ_INFLATE_BAD_SYMBOL = 4 /* a code that is not in the table, literal / length 286-287, distance 30-31 */,
+    AEJ_INFLATE_DISTANCE_TOO_FAR = 5, AEJ_INFLATE_STORED_LENGTH = 6 /* LEN != ~NLEN */, AEJ_INFLATE_TRUNCATED = 7,
+    AEJ_INFLATE_OVER_CAPACITY = 8, AEJ_INFLATE_ADLER = 9, AEJ_INFLATE_BAD_ARG = 10 /* descriptor outside dst or misaligned */
+};
+AEJ_API int aej_inflate_batch(aej_ctx *ctx, const uint8_t *src, const int64_t *streams, int n, uint8_t *dst, uint64_t dst_bytes,
+                              int64_t *out_bytes, int32_t *status);
+/* aej_decode_headers: the quadtree header of every layer of a batch (the walks of Jpeg._decode_leaf_sizes and aej_leaf_positions_host, with
+ *   every check Jpeg.decompress makes) into the tables aej_decode_batch reads.  layers: device [batch * 3][3] int64 = { offset of the layer's
+ *   packed 2-bit state symbols in `states` (the container's packing: first symbol in the top bits of a byte), number of symbols, the root
+ *   size the container stores }.  inflated_bytes: device [batch * 3] int64, the size of each layer's decoded coefficient stream.  leaves /
+ *   counts: aej_encode_batch's layout (counts[b][l] = { n_coeffs, n_leaves, n_states, root }; a layer in error gets n_coeffs = n_leaves = 0).
+ *   status: device [batch * 3] int32, AEJ_HEADER_*.  leaves and workspace 16-byte aligned. */
+enum {
+    AEJ_HEADER_OK = 0, AEJ_HEADER_TOO_MANY_LEAVES = 1, AEJ_HEADER_BAD_SIZE = 2 /* leaf size outside the settings' block range */,
+    AEJ_HEADER_NO_TILING = 3, AEJ_HEADER_COEFF_COUNT = 4 /* inflated bytes != 4 * sum(size^2) */, AEJ_HEADER_BAD_ARG = 5
+};
+AEJ_API uint64_t aej_decode_headers_workspace_bytes(aej_ctx *ctx, int batch, int H, int W);
+AEJ_API int aej_decode_headers(aej_ctx *ctx, const uint8_t *states, const int64_t *layers, const int64_t *inflated_bytes, int batch, int H, int W,
+                               int32_t *leaves, int64_t *counts, int32_t *status, void *workspace, uint64_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif
