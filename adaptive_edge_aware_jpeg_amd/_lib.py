@@ -175,6 +175,8 @@ SIGNATURES = {
     "aej_pack_u8_levels_host": (_I, [_P, _I64, _P, _I]),
     "aej_decode_workspace_bytes": (_U64, [_P, _I, _I, _I]),
     "aej_decode_batch": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _U64]),
+    "aej_decode_batch_tables": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _U64]),
+    "aej_requantise_batch": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _U64]),
     "aej_color_convert_inverse": (_I, [_P, _I, _P, _P, _I64]),
     "aej_leaf_positions_host": (_I64, [_P, _I64, _I, _I, _I, _P]),
     "aej_inflate_batch": (_I, [_P, _P, _P, _I, _P, _U64, _P, _P]),

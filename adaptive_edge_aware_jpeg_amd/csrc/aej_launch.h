@@ -148,6 +148,13 @@ struct HdrGeom {
 void launch_headers(hipStream_t st, const unsigned char *states, const long long *desc, const long long *inflated, int nlayers, const HdrGeom &g,
                     unsigned char *codes, int *leaves, long long *counts, int *status);
 
+// requant.hip -- requantisation of stored DCT values (aej_requantise_batch).  bad: device word, zeroed by the caller; the check sets it (1 leaf
+// tables, 2 quantisers) and k_requant then writes nothing
+void launch_requant_check(hipStream_t st, const Geom &g, const QtGeom &q, const int *leaves, const long long *counts, const int *qmats,
+                          long long qmat_words, int *bad);
+int launch_requant(hipStream_t st, const Geom &g, const QtGeom &q, const float *dct, const int *leaves, const long long *counts, int n_sets,
+                   const int *qmats, const int *const *zz, int *out, long long set_stride, int *bad, int blocks_per_plane);
+
 // metrics.hip
 void launch_metric_prep(hipStream_t st, const float *a, const float *b, int B, long long npx, double *acc, unsigned char *ga, unsigned char *gb);
 void launch_metric_pool_grey(hipStream_t st, const unsigned char *ga, const unsigned char *gb, int B, int H, int W, int f, int hp, int wp, float *xa,

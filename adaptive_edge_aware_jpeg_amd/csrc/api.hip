@@ -32,6 +32,7 @@ struct aej_ctx {
     const int *d_zzinv[kMaxSizes] = {};
     const int *d_zz[kMaxSizes] = {};
     const int *d_qm[3][kMaxSizes] = {};
+    int *d_check = nullptr;            // device word in `tables`: aej_requantise_batch's "leaf tables / quantisers do not fit" flag
     const float *d_space_w = nullptr, *d_color_w = nullptr;
     float *d_bilateral = nullptr;      // [16 + 256] space / colour weights of the bilateral filter (own allocation: aej_set_canny_params rebuilds it)
     aej_canny_params canny = { 0.10, 0.30, 0.75, 75.0, 75.0, 1 };     // edge_detection.py:31-40 defaults
@@ -478,6 +479,8 @@ extern "C" int aej_set_settings(aej_ctx *ctx, int space, int bmin, int bmax, con
             qpos += (size_t)s * s;
         }
     }
+    const int zero_words[64] = {};
+    const size_t oCheck = put(zero_words, sizeof zero_words);
     drop_graphs(ctx);                  // captured kernel arguments point into the old tables
     if (ctx->tables) { AEJ_HIP_CHECK(hipStreamSynchronize(ctx->stream)); AEJ_HIP_CHECK(hipFree(ctx->tables)); ctx->tables = nullptr; }
     AEJ_HIP_CHECK(hipMalloc(&ctx->tables, blob.size()));
@@ -493,6 +496,7 @@ extern "C" int aej_set_settings(aej_ctx *ctx, int space, int bmin, int bmax, con
         ctx->d_zz[i] = reinterpret_cast<const int *>(base + oZf[i]);
         for (int l = 0; l < 3; l++) ctx->d_qm[l][i] = reinterpret_cast<const int *>(base + oQ[l][i]);
     }
+    ctx->d_check = reinterpret_cast<int *>(base + oCheck);
     ctx->space = space; ctx->bmin = bmin; ctx->bmax = bmax; ctx->nsizes = nsizes;
     ctx->has_settings = true;
     return 0;
@@ -1450,12 +1454,13 @@ extern "C" uint64_t aej_decode_workspace_bytes(aej_ctx *ctx, int batch, int H, i
     return w.bytes;
 }
 
-extern "C" int aej_decode_batch(aej_ctx *ctx, const int32_t *coeffs, const int32_t *leaves, const int64_t *counts, int batch, int H, int W,
-                                float *rgb_out, void *workspace, uint64_t workspace_bytes)
+// aej_decode_batch with the dequantisation tables qm[layer][size index] (the context's, or one set of a device blob)
+static int decode_batch_impl(aej_ctx *ctx, const char *who, const int32_t *coeffs, const int32_t *leaves, const int64_t *counts, int batch, int H, int W,
+                             const int *const qm[3][kMaxSizes], float *rgb_out, void *workspace, uint64_t workspace_bytes)
 {
     int rc = check_encode_args(ctx, batch, H, W);
     if (rc) return rc;
-    if (call_in_flight(ctx)) return fail(ctx, AEJ_ERR_STATE, "%s between aej_encode_batch_begin and aej_encode_batch_end", __func__);
+    if (call_in_flight(ctx)) return fail(ctx, AEJ_ERR_STATE, "%s between aej_encode_batch_begin and aej_encode_batch_end", who);
     if (!coeffs || !leaves || !counts || !rgb_out || !workspace) return fail(ctx, AEJ_ERR_ARG, "NULL buffer");
     AEJ_HIP_CHECK(hipSetDevice(ctx->device));
     Geom g;
@@ -1475,7 +1480,7 @@ extern "C" int aej_decode_batch(aej_ctx *ctx, const int32_t *coeffs, const int32
         a.coeffs = coeffs; a.planes = w.planes; a.work = w.work[k]; a.work_count = w.work_count; a.k = k; a.nplanes = batch * 3;
         a.scratch = w.big;
         a.D = ctx->d_D[k]; a.zz = ctx->d_zz[k]; a.zzinv = ctx->d_zzinv[k];
-        for (int l = 0; l < 3; l++) { a.qm[l] = ctx->d_qm[l][k]; a.mid[l] = (float)kMid[ctx->space][l]; a.scale[l] = (float)kScale[ctx->space][l]; }
+        for (int l = 0; l < 3; l++) { a.qm[l] = qm[l][k]; a.mid[l] = (float)kMid[ctx->space][l]; a.scale[l] = (float)kScale[ctx->space][l]; }
         if (launch_idct(st, s, g, q, a, w.work_cap[k])) return fail(ctx, AEJ_ERR_UNSUPPORTED, "no IDCT kernel for block size %d with %d planes", s, a.nplanes);
     }
     if (launch_upsample_color(st, ctx->space, g, w.planes, rgb_out)) return fail(ctx, AEJ_ERR_ARG, "bad colour space");
@@ -1483,6 +1488,74 @@ extern "C" int aej_decode_batch(aej_ctx *ctx, const int32_t *coeffs, const int32
     AEJ_HIP_CHECK(hipMemcpyAsync(ctx->h_flag, bad, sizeof(int), hipMemcpyDeviceToHost, st));
     AEJ_HIP_CHECK(hipStreamSynchronize(st));
     if (*ctx->h_flag) return fail(ctx, AEJ_ERR_ARG, "corrupt stream: the leaf tables do not fit the plan (leaf count, block size outside %d-%d, or too many leaves of one size)", q.bmin, q.bmax);
+    return 0;
+}
+
+extern "C" int aej_decode_batch(aej_ctx *ctx, const int32_t *coeffs, const int32_t *leaves, const int64_t *counts, int batch, int H, int W,
+                                float *rgb_out, void *workspace, uint64_t workspace_bytes)
+{
+    if (!ctx) return AEJ_ERR_ARG;
+    return decode_batch_impl(ctx, __func__, coeffs, leaves, counts, batch, H, W, ctx->d_qm, rgb_out, workspace, workspace_bytes);
+}
+
+// the per-layer, per-size quantiser pointers of one set of a [layer][size][s*s] blob laid out for the bound block range
+static void qm_of_set(const aej_ctx *ctx, const int32_t *set, const int *qm[3][kMaxSizes])
+{
+    long long lw = 0;
+    for (int s = ctx->bmin; s <= ctx->bmax; s *= 2) lw += (long long)s * s;
+    for (int l = 0; l < 3; l++) {
+        long long o = l * lw;
+        for (int k = 0; k < kMaxSizes; k++) {
+            const int s = ctx->bmin << k;
+            qm[l][k] = k < ctx->nsizes ? set + o : nullptr;
+            if (k < ctx->nsizes) o += (long long)s * s;
+        }
+    }
+}
+
+extern "C" int aej_decode_batch_tables(aej_ctx *ctx, const int32_t *coeffs, const int32_t *leaves, const int64_t *counts, int batch, int H, int W,
+                                       const int32_t *qmats_dev, float *rgb_out, void *workspace, uint64_t workspace_bytes)
+{
+    int rc = check_encode_args(ctx, batch, H, W);
+    if (rc) return rc;
+    if (!qmats_dev) return fail(ctx, AEJ_ERR_ARG, "NULL buffer");
+    const int *qm[3][kMaxSizes];
+    qm_of_set(ctx, qmats_dev, qm);
+    return decode_batch_impl(ctx, __func__, coeffs, leaves, counts, batch, H, W, qm, rgb_out, workspace, workspace_bytes);
+}
+
+// ---- requantisation of stored DCT values (requant.hip) --------------------------------------------------------------------
+extern "C" int aej_requantise_batch(aej_ctx *ctx, const float *dct_f32, const int32_t *leaves, const int64_t *counts, int batch, int H, int W,
+                                    int n_sets, const int32_t *qmats_dev, int32_t *coeffs_out, uint64_t set_stride_elems)
+{
+    int rc = check_encode_args(ctx, batch, H, W);
+    if (rc) return rc;
+    if (call_in_flight(ctx)) return fail(ctx, AEJ_ERR_STATE, "%s between aej_encode_batch_begin and aej_encode_batch_end", __func__);
+    if (!dct_f32 || !leaves || !counts || !qmats_dev || !coeffs_out) return fail(ctx, AEJ_ERR_ARG, "NULL buffer");
+    if (n_sets < 1) return fail(ctx, AEJ_ERR_ARG, "n_sets must be at least 1 (got %d)", n_sets);
+    AEJ_HIP_CHECK(hipSetDevice(ctx->device));
+    Geom g;
+    QtGeom q;
+    if ((rc = make_geom(ctx, ctx->space, batch, H, W, g))) return rc;
+    if ((rc = make_qtgeom(ctx, g, ctx->bmin, ctx->bmax, q))) return rc;
+    const unsigned long long need = (unsigned long long)batch * q.coeff_stride;
+    if (n_sets > 1 && set_stride_elems < need)
+        return fail(ctx, AEJ_ERR_ARG, "set_stride_elems %llu is smaller than the batch's coefficients (%llu)", (unsigned long long)set_stride_elems, need);
+    long long lw = 0;
+    for (int s = ctx->bmin; s <= ctx->bmax; s *= 2) lw += (long long)s * s;
+    long long maxcap = 0;
+    for (int l = 0; l < 3; l++) maxcap = std::max(maxcap, q.coeff_cap[l]);
+    const int blocks = (int)std::min<long long>(512, std::max<long long>(1, (maxcap + 16383) / 16384));
+    hipStream_t st = ctx->stream;
+    AEJ_HIP_CHECK(hipMemsetAsync(ctx->d_check, 0, sizeof(int), st));
+    launch_requant_check(st, g, q, leaves, reinterpret_cast<const long long *>(counts), qmats_dev, (long long)n_sets * 3 * lw, ctx->d_check);
+    launch_requant(st, g, q, dct_f32, leaves, reinterpret_cast<const long long *>(counts), n_sets, qmats_dev, ctx->d_zz, coeffs_out,
+                   (long long)set_stride_elems, ctx->d_check, blocks);
+    AEJ_HIP_CHECK(hipGetLastError());
+    AEJ_HIP_CHECK(hipMemcpyAsync(ctx->h_flag, ctx->d_check, sizeof(int), hipMemcpyDeviceToHost, st));
+    AEJ_HIP_CHECK(hipStreamSynchronize(st));
+    if (*ctx->h_flag == 2) return fail(ctx, AEJ_ERR_ARG, "quantisation matrix entries must be >= 1");
+    if (*ctx->h_flag) return fail(ctx, AEJ_ERR_ARG, "the leaf tables do not fit the plan (leaf count, block size outside %d-%d, origin or coefficient offset outside the layer)", q.bmin, q.bmax);
     return 0;
 }
 

@@ -274,6 +274,29 @@ AEJ_API int aej_pack_u8_levels_host(const float *rgb_host, int64_t n, uint8_t *u
 AEJ_API uint64_t aej_decode_workspace_bytes(aej_ctx *ctx, int batch, int H, int W);
 AEJ_API int aej_decode_batch(aej_ctx *ctx, const int32_t *coeffs, const int32_t *leaves, const int64_t *counts, int batch, int H,
                              int W, float *rgb_out, void *workspace, uint64_t workspace_bytes);
+/* aej_decode_batch with the dequantisation tables taken from a device buffer instead of the context: qmats_dev is ONE set laid out as
+ * aej_set_settings' qmats_host ([layer 0..2][size = bmin .. bmax][size*size] int32, raster order, no padding) for the block range the
+ * context is bound to; colour space, block range, zigzag orders and DCT bases stay the context's.  Same preconditions, checks and
+ * completion as aej_decode_batch (it waits for its one check word); the quantisers are used as given. */
+AEJ_API int aej_decode_batch_tables(aej_ctx *ctx, const int32_t *coeffs, const int32_t *leaves, const int64_t *counts, int batch, int H, int W,
+                                    const int32_t *qmats_dev, float *rgb_out, void *workspace, uint64_t workspace_bytes);
+
+/* ---- requantisation for rate-distortion sweeps: Jpeg.compress under other quality ranges without colour, Canny, quadtree or DCT work ----
+ * The quality range only enters the encode through the quantisation matrices (jpeg.py:356-404, 485-506, 688-705), so the coefficients
+ * for any other set of matrices follow from the pre-quantisation DCT values of an encode: coefficient i of a leaf of size s is
+ * rint(double(Y[zz_s[i]]) / double(Q[zz_s[i]])) -- the very quantiser of the DCT epilogues, bit for bit what aej_encode_batch writes
+ * when the context is bound to that set.
+ * Preconditions: the context is bound (aej_set_settings) to the colour space and block range that produced the leaves; dct_f32, leaves
+ * and counts are aej_encode_batch's outputs for (batch, H, W) (dct_f32 requested from it; counts is the DEVICE array).
+ * qmats_dev: device [n_sets][layer 0..2][size = bmin .. bmax][size*size] int32, each set laid out as aej_set_settings' qmats_host.
+ * Set j is written at coeffs_out + j * set_stride_elems in aej_encode_batch's coefficient layout (a drop-in `coeffs` for
+ * aej_decode_batch, aej_deflate_* and the container); entries beyond a layer's n_coeffs are left untouched.  set_stride_elems must be
+ * at least batch * coeff_stride when n_sets > 1 (16-byte aligned sets write with 16-byte stores).
+ * A leaf table that does not fit the plan (n_leaves over capacity, a size outside the bound block range, an origin outside the layer, a
+ * coefficient offset outside the layer's span) or a quantiser < 1 returns AEJ_ERR_ARG and nothing is written.  The call enqueues a check
+ * and the requantisation on the context's stream and waits only for the check word. */
+AEJ_API int aej_requantise_batch(aej_ctx *ctx, const float *dct_f32, const int32_t *leaves, const int64_t *counts, int batch, int H, int W,
+                                 int n_sets, const int32_t *qmats_dev, int32_t *coeffs_out, uint64_t set_stride_elems);
 /* color.convert(space, "sRGB", x) (conversion.py:122-124): in [n][3] -> sRGB [n][3], float32 */
 AEJ_API int aej_color_convert_inverse(aej_ctx *ctx, int space, const float *in, float *out_rgb, int64_t n);
 /* HOST helper (no device): leaf positions from leaf sizes, the walk of Jpeg._block_merge (jpeg.py:424-448).
