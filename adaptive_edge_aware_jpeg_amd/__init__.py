@@ -17,10 +17,11 @@ from .edge_detection import EdgeDetection  # noqa: E402
 from .evaluation_metrics import EvaluationMetrics  # noqa: E402
 from .image import Image  # noqa: E402
 from .jpeg import EncodedBatch, Jpeg  # noqa: E402
+from .lpips import LpipsWeights  # noqa: E402
 from .quadtree import QuadNode, QuadTree  # noqa: E402
 from .settings import JpegCompressionSettings  # noqa: E402
 from .sweep import SweepResult, reference_grid, sweep  # noqa: E402
 
 __all__ = ["Jpeg", "JpegCompressionSettings", "EncodedBatch", "Image", "EvaluationMetrics", "EdgeDetection", "QuadTree", "QuadNode",
            "convert", "apply_normalization", "get_color_spaces", "hw_queues", "set_hw_queues", "configure_hw_queues",
-           "sweep", "reference_grid", "SweepResult"]
+           "sweep", "reference_grid", "SweepResult", "LpipsWeights"]

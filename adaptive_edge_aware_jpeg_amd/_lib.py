@@ -182,6 +182,13 @@ SIGNATURES = {
     "aej_inflate_batch": (_I, [_P, _P, _P, _I, _P, _U64, _P, _P]),
     "aej_decode_headers_workspace_bytes": (_U64, [_P, _I, _I, _I]),
     "aej_decode_headers": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _U64]),
+    "aej_lpips_weights_bytes": (_U64, []),
+    "aej_lpips_param_count": (_I64, []),
+    "aej_lpips_pack_weights_host": (_I, [_P, _I64, _P]),
+    "aej_lpips_features_bytes": (_U64, [_I, _I, _I]),
+    "aej_lpips_workspace_bytes": (_U64, [_I, _I, _I]),
+    "aej_lpips_features": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _U64]),
+    "aej_lpips_batch": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _U64]),
 }
 
 # status values of aej_inflate_batch / aej_decode_headers (include/aej.h AEJ_INFLATE_* / AEJ_HEADER_*)

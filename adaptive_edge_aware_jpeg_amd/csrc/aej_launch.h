@@ -166,4 +166,26 @@ void launch_pool2(hipStream_t st, bool interleaved, const float *in, int B, int 
 void launch_metric_final(hipStream_t st, const double *acc, int B, long long npx, long long n_ssim, const long long *n_level, double *out);
 
 
+// lpips.hip: LPIPS(net='alex') (aej_lpips_*, include/aej.h)
+constexpr int kLpipsTaps = 5;
+constexpr int kLpipsHeadPixels = 256;      // pixels of a tap whose distances one workgroup of the head sums into one float64 partial
+struct LpipsLayer { int cin, cinp, cout, k, stride, pad; };
+extern const LpipsLayer kLpipsLayers[kLpipsTaps];
+struct LpipsGeom {
+    int H, W;
+    int h[kLpipsTaps], w[kLpipsTaps];      // conv l's output (= tap l)
+    int ph[2], pw[2];                       // the two maxpools' outputs
+    long long tap_off[kLpipsTaps];          // element offset of tap l inside one image's normalised features
+    long long feat_elems;                   // normalised features per image
+    long long x_elems, y_elems;             // per image: the two ping-pong activation buffers
+    int nblk[kLpipsTaps], max_blk;          // head workgroups (float64 partials) per image and tap
+};
+bool lpips_geom(int H, int W, LpipsGeom &g);          // false below 31 x 31 (torch's second maxpool would have no output)
+long long lpips_param_floats();                        // floats of the canonical parameter list aej_lpips_pack_weights_host reads
+long long lpips_packed_floats(long long off[kLpipsTaps][3]);     // floats of the packed weights; off[l] = {conv weights, bias, lin}
+void lpips_pack_host(const float *params, float *packed);
+// feats_out != NULL: write the normalised taps (features mode); else score against the normalised taps feats_a into out[B] (float64)
+void launch_lpips(hipStream_t st, const float *wpk, const float *img, int B, const LpipsGeom &g, float *X, float *Y, float *feats_out,
+                  const float *feats_a, double *partial, double *out);
+
 }  // namespace aej

@@ -1917,3 +1917,104 @@ extern "C" const char *aej_stage_name(int i)
                                                "hysteresis", "quadtree", "dct2", "dct4", "dct8", "dct16", "dct32", "dct64", "dct128", "dct256", "dct512", "dct1024" };
     return i >= 0 && i < AEJ_N_STAGES ? names[i] : "";
 }
+
+// ---- LPIPS(net='alex') (lpips.hip) ---------------------------------------------------------------------------------------------
+struct LpipsWs {
+    float *x, *y, *feats;      // ping-pong activations, the normalised taps of img_a (aej_lpips_batch with img_a only)
+    double *partial;
+    unsigned long long bytes;
+};
+
+static void carve_lpips(void *base, int B, const LpipsGeom &g, LpipsWs &w)
+{
+    unsigned long long off = 0;
+    auto take = [&](unsigned long long n) { void *p = base ? (char *)base + off : nullptr; off += (unsigned long long)align_up((long long)n, 256); return p; };
+    w.x = (float *)take((unsigned long long)B * g.x_elems * 4);
+    w.y = (float *)take((unsigned long long)B * g.y_elems * 4);
+    w.partial = (double *)take((unsigned long long)B * kLpipsTaps * g.max_blk * 8);
+    w.bytes = off;
+    w.feats = (float *)take((unsigned long long)B * g.feat_elems * 4);      // beyond w.bytes: only aej_lpips_batch with img_a needs it
+}
+
+extern "C" uint64_t aej_lpips_weights_bytes(void)
+{
+    long long off[kLpipsTaps][3];
+    return (uint64_t)lpips_packed_floats(off) * 4;
+}
+
+extern "C" int64_t aej_lpips_param_count(void) { return lpips_param_floats(); }
+
+extern "C" int aej_lpips_pack_weights_host(const float *params, int64_t n_params, void *packed_host)
+{
+    if (!params || !packed_host) return AEJ_ERR_ARG;
+    if (n_params != lpips_param_floats()) return AEJ_ERR_ARG;
+    lpips_pack_host(params, (float *)packed_host);
+    return 0;
+}
+
+extern "C" uint64_t aej_lpips_features_bytes(int batch, int H, int W)
+{
+    LpipsGeom g;
+    if (batch < 1 || !lpips_geom(H, W, g)) return 0;
+    return (uint64_t)batch * g.feat_elems * 4;
+}
+
+extern "C" uint64_t aej_lpips_workspace_bytes(int batch, int H, int W)
+{
+    LpipsGeom g;
+    if (batch < 1 || !lpips_geom(H, W, g)) return 0;
+    LpipsWs w;
+    carve_lpips(nullptr, batch, g, w);
+    return w.bytes;
+}
+
+static int lpips_args(aej_ctx *ctx, const char *fn, const void *weights, int batch, int H, int W, LpipsGeom &g)
+{
+    if (call_in_flight(ctx)) return fail(ctx, AEJ_ERR_STATE, "%s between aej_encode_batch_begin and aej_encode_batch_end", fn);
+    if (!weights) return fail(ctx, AEJ_ERR_ARG, "%s: NULL weights", fn);
+    if (batch < 1 || H < 1 || W < 1) return fail(ctx, AEJ_ERR_ARG, "%s: bad shape %d x %d x %d", fn, batch, H, W);
+    if (!lpips_geom(H, W, g))
+        return fail(ctx, AEJ_ERR_ARG, "%s: LPIPS needs images of at least 31x31 (got %dx%d): AlexNet's second maxpool would have no output", fn, H, W);
+    return 0;
+}
+
+extern "C" int aej_lpips_features(aej_ctx *ctx, const void *weights, const float *img, int batch, int H, int W, float *feats, void *workspace,
+                                  uint64_t workspace_bytes)
+{
+    if (!ctx) return AEJ_ERR_ARG;
+    LpipsGeom g;
+    int rc = lpips_args(ctx, __func__, weights, batch, H, W, g);
+    if (rc) return rc;
+    if (!img || !feats || !workspace) return fail(ctx, AEJ_ERR_ARG, "NULL buffer");
+    LpipsWs w;
+    carve_lpips(workspace, batch, g, w);
+    if (w.bytes > workspace_bytes) return fail(ctx, AEJ_ERR_CAPACITY, "workspace too small: need %llu bytes, got %llu", w.bytes, (unsigned long long)workspace_bytes);
+    AEJ_HIP_CHECK(hipSetDevice(ctx->device));
+    launch_lpips(ctx->stream, (const float *)weights, img, batch, g, w.x, w.y, feats, nullptr, nullptr, nullptr);
+    AEJ_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int aej_lpips_batch(aej_ctx *ctx, const void *weights, const float *img_a, const float *feats_a, const float *img_b, int batch, int H, int W,
+                               double *out, void *workspace, uint64_t workspace_bytes)
+{
+    if (!ctx) return AEJ_ERR_ARG;
+    LpipsGeom g;
+    int rc = lpips_args(ctx, __func__, weights, batch, H, W, g);
+    if (rc) return rc;
+    if (!img_a == !feats_a) return fail(ctx, AEJ_ERR_ARG, "exactly one of img_a and feats_a must be given");
+    if (!img_b || !out || !workspace) return fail(ctx, AEJ_ERR_ARG, "NULL buffer");
+    LpipsWs w;
+    carve_lpips(workspace, batch, g, w);
+    if (img_a) w.bytes += (unsigned long long)batch * g.feat_elems * 4;
+    if (w.bytes > workspace_bytes) return fail(ctx, AEJ_ERR_CAPACITY, "workspace too small: need %llu bytes, got %llu", w.bytes, (unsigned long long)workspace_bytes);
+    AEJ_HIP_CHECK(hipSetDevice(ctx->device));
+    const float *wpk = (const float *)weights;
+    if (img_a) {      // the same two passes as aej_lpips_features + aej_lpips_batch(feats_a): bit-identical results
+        launch_lpips(ctx->stream, wpk, img_a, batch, g, w.x, w.y, w.feats, nullptr, nullptr, nullptr);
+        feats_a = w.feats;
+    }
+    launch_lpips(ctx->stream, wpk, img_b, batch, g, w.x, w.y, nullptr, feats_a, w.partial, out);
+    AEJ_HIP_CHECK(hipGetLastError());
+    return 0;
+}

@@ -2,14 +2,17 @@
 
 Same constructor and method names; ``psnr`` / ``ssim`` / ``ms_ssim`` return 0-dim float32 torch tensors as piq does with
 ``reduction='mean'`` on a batch of one.  ``batch`` scores many pairs in one call (device tensors in, device tensor out):
-that is what a parameter sweep (test/analysis/metrics_computation.py:150-190) needs.  ``lpips`` is not offered: its
-AlexNet weights are fetched from the network by name (evaluation_metrics.py:34-36) and no copy exists offline.
+that is what a parameter sweep (test/analysis/metrics_computation.py:150-190) needs.  ``lpips`` needs AlexNet weights the
+user supplies (``LpipsWeights``, lpips.py): the reference downloads them (evaluation_metrics.py:34-36) and no copy ships here.
+Without weights -- none given to the constructor and the class attribute ``EvaluationMetrics.lpips_weights`` left at None --
+``lpips()`` raises NotImplementedError.
 """
 import ctypes
 from typing import Union
 
 import numpy as np
 
+from . import lpips as _lpips
 from ._lib import get_context
 from .image import Image
 
@@ -33,10 +36,13 @@ def _data(image: Union[Image, np.ndarray]):
 class EvaluationMetrics:
     """A collection of image quality assessment metrics."""
 
-    def __init__(self, original_image: Image, compressed_image: Image, device: int = 0) -> None:
+    lpips_weights = None     # LpipsWeights for lpips() of instances constructed without any (the reference calls lpips() with no arguments)
+
+    def __init__(self, original_image: Image, compressed_image: Image, device: int = 0, lpips_weights=None) -> None:
         self.original_image = original_image
         self.compressed_image = compressed_image
         self._device = device
+        self._lpips_weights = lpips_weights
         self._scores = {}
 
     @staticmethod
@@ -55,6 +61,19 @@ class EvaluationMetrics:
         ctx.check(ctx.lib.aej_metrics_batch(ctx.handle, xa.data_ptr(), xb.data_ptr(), B, H, W, which, out.data_ptr(), ws.data_ptr(),
                                             ctypes.c_uint64(nbytes)))
         return out
+
+    @staticmethod
+    def lpips_batch(a, b, weights, device: int = 0):
+        """LPIPS(net='alex') of each pair: a, b float32 [B, H, W, 3] in [0, 1] (torch on the GPU, or numpy -> copied), weights an
+        LpipsWeights.  Returns a float64 device tensor [B]."""
+        if weights is None:
+            raise ValueError("lpips_batch needs LpipsWeights")
+        ctx = get_context(device)
+        t = ctx.torch
+        xa, xb = ctx.to_device(a, t.float32), ctx.to_device(b, t.float32)
+        if xa.ndim != 4 or xa.shape[3] != 3 or xa.shape != xb.shape:
+            raise ValueError("Input batches must both be [B, H, W, 3].")
+        return _lpips.score(ctx, weights, xb, xa=xa)
 
     def _score(self, which: int, column: int):
         if which not in self._scores:
@@ -76,4 +95,13 @@ class EvaluationMetrics:
         return self._score(MS_SSIM, 2)
 
     def lpips(self) -> float:
-        raise NotImplementedError("LPIPS needs the pretrained AlexNet weights lpips.LPIPS(net='alex') downloads; none are available offline")
+        """LPIPS(net='alex') (evaluation_metrics.py:91-109) with the instance's weights, else EvaluationMetrics.lpips_weights."""
+        weights = self._lpips_weights if self._lpips_weights is not None else EvaluationMetrics.lpips_weights
+        if weights is None:
+            raise NotImplementedError("LPIPS needs the pretrained AlexNet weights lpips.LPIPS(net='alex') downloads; none ship with this "
+                                      "package: pass LpipsWeights.load(...) as lpips_weights= or set EvaluationMetrics.lpips_weights")
+        key = ("lpips", id(weights))
+        if key not in self._scores:
+            a, b = _data(self.original_image), _data(self.compressed_image)
+            self._scores[key] = float(EvaluationMetrics.lpips_batch(a[None], b[None], weights, self._device)[0].item())
+        return self._scores[key]

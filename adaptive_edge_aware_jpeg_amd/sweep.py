@@ -10,6 +10,9 @@ quantisation matrices alone (jpeg.py:356-404, 485-506, 688-705).  So per colour 
 3. requantises them for a group of quality ranges in one ``aej_requantise_batch`` call (csrc/requant.hip),
 4. per quality range: ``aej_decode_batch_tables`` -> ``aej_metrics_batch``, plus the container size.
 
+With ``lpips=`` (an ``LpipsWeights``) the originals' LPIPS features are computed once per image sub-batch (``aej_lpips_features``)
+and every decoded quality set is scored against them (``aej_lpips_batch``): the ``lpips`` column of the reference's CSV.
+
 Sizes: ``"zlib"`` (the default, the reference's number) is host zlib level 9 of every layer on a thread pool, fed by one device-to-host
 copy per quality set and overlapped with the GPU work of the next sets.  ``"gpu"`` takes the lengths of the GPU deflate's streams
 (``Jpeg.deflate_batch``) without copying them back: about 10 % larger than zlib-9, so NOT the reference's compression ratio, and -- the GPU
@@ -30,11 +33,13 @@ import numpy as np
 from . import tables
 from ._lib import AejError, get_context
 from .evaluation_metrics import MS_SSIM, PSNR, SSIM
+from . import lpips as _lpips
 from .jpeg import Jpeg, usable_cpus
 from .settings import JpegCompressionSettings
 
 CSV_COLUMNS = ("image_name", "color_space", "min_quality", "max_quality", "min_block_size", "max_block_size", "psnr", "ssim", "ms_ssim",
                "compression_ratio")      # metrics_computation.py:185-197 without 'lpips' (its weights are a download)
+CSV_COLUMNS_LPIPS = CSV_COLUMNS[:9] + ("lpips",) + CSV_COLUMNS[9:]      # the reference's full header: sweep(..., lpips=weights)
 DEFAULT_MEMORY_FRACTION = 0.5            # max_bytes=None: this share of the device memory free when the sweep starts
 
 
@@ -80,7 +85,7 @@ def qmats_blob(color_space, quality_range, block_size_range) -> np.ndarray:
 class SweepResult:
     """One row per image, one column per cell; ``cells`` in the reference's ``product`` order."""
 
-    def __init__(self, cells, names, shapes, which, sizes):
+    def __init__(self, cells, names, shapes, which, sizes, lpips=False):
         n, c = len(names), len(cells)
         self.cells: List[Tuple[str, Tuple[int, int], Tuple[int, int]]] = cells
         self.names: List[str] = names
@@ -88,29 +93,40 @@ class SweepResult:
         self.psnr = np.full((n, c), np.nan)
         self.ssim = np.full((n, c), np.nan)
         self.ms_ssim = np.full((n, c), np.nan)
+        self.lpips = np.full((n, c), np.nan) if lpips else None      # only when the sweep was given LPIPS weights
         self.bytes = np.zeros((n, c), np.int64)
         self.compression_ratio = np.full((n, c), np.nan)
         self.sizes = sizes
         self.which = which
         self.sub_batches = {}          # (color_space, block_size_range) -> [[image indices of one encode call], ...]
 
+    def columns(self):
+        """CSV_COLUMNS_LPIPS when the sweep computed LPIPS, else CSV_COLUMNS."""
+        return CSV_COLUMNS_LPIPS if self.lpips is not None else CSV_COLUMNS
+
     def rows(self):
-        """dicts with the reference CSV's column names (metrics_computation.py:185-197), LPIPS absent; image by image, cells in order."""
+        """dicts with the reference CSV's column names (metrics_computation.py:185-197), ``lpips`` only when the sweep computed it; image
+        by image, cells in order."""
         out = []
         for i, name in enumerate(self.names):
             for j, (cs, qr, br) in enumerate(self.cells):
-                out.append({"image_name": name, "color_space": cs, "min_quality": qr[0], "max_quality": qr[1], "min_block_size": br[0],
-                            "max_block_size": br[1], "psnr": float(self.psnr[i, j]), "ssim": float(self.ssim[i, j]),
-                            "ms_ssim": float(self.ms_ssim[i, j]), "compression_ratio": float(self.compression_ratio[i, j])})
+                r = {"image_name": name, "color_space": cs, "min_quality": qr[0], "max_quality": qr[1], "min_block_size": br[0],
+                     "max_block_size": br[1], "psnr": float(self.psnr[i, j]), "ssim": float(self.ssim[i, j]), "ms_ssim": float(self.ms_ssim[i, j])}
+                if self.lpips is not None:
+                    r["lpips"] = float(self.lpips[i, j])
+                r["compression_ratio"] = float(self.compression_ratio[i, j])
+                out.append(r)
         return out
 
     def to_csv(self, path):
-        """The reference's CSV (DataFrame.to_csv(index=False)): its column order, metrics and ratio as ``:.4f``, without ``lpips``."""
+        """The reference's CSV (DataFrame.to_csv(index=False)): its column order, metrics and ratio as ``:.4f``; ``lpips`` only when the
+        sweep computed it."""
+        cols = self.columns()
         with open(path, "w", newline="") as f:
             w = csv.writer(f, lineterminator="\n")
-            w.writerow(CSV_COLUMNS)
+            w.writerow(cols)
             for r in self.rows():
-                w.writerow([r[k] if k in CSV_COLUMNS[:6] else f"{r[k]:.4f}" for k in CSV_COLUMNS])
+                w.writerow([r[k] if k in CSV_COLUMNS[:6] else f"{r[k]:.4f}" for k in cols])
 
 
 def _shape_groups(images):
@@ -144,7 +160,7 @@ def _shape_groups(images):
 class _Plan:
     """Sub-batch and quality-group sizes of one (shape, colour space, block range) under the byte budget."""
 
-    def __init__(self, ctx, n_img, H, W, n_q, which, sizes, max_bytes, in_bytes):
+    def __init__(self, ctx, n_img, H, W, n_q, which, sizes, max_bytes, in_bytes, lpips=False):
         lib = ctx.lib
 
         def cost(b, g):
@@ -153,7 +169,10 @@ class _Plan:
             c = in_bytes * b * H * W * 3 + 4 * b * H * W * 3       # input (+ its float32 copy for the metrics) ...
             c += 2 * coef + 16 * b * p.leaf_stride + b * p.state_stride + p.workspace_bytes      # encode outputs with dct_f32, workspace
             c += g * coef + 4 * b * H * W * 3                       # the quality sets, one decoded batch
-            c += max(int(lib.aej_decode_workspace_bytes(ctx.handle, b, H, W)), int(lib.aej_metrics_workspace_bytes(b, H, W)) if which else 0)
+            c += max(int(lib.aej_decode_workspace_bytes(ctx.handle, b, H, W)), int(lib.aej_metrics_workspace_bytes(b, H, W)) if which else 0,
+                     int(lib.aej_lpips_workspace_bytes(b, H, W)) if lpips else 0)
+            if lpips:                                               # the originals' LPIPS features
+                c += int(lib.aej_lpips_features_bytes(b, H, W))
             if sizes == "gpu":
                 c += int(lib.aej_deflate_workspace_bytes(ctx.handle, b, H, W)) + 2 * coef
             return c
@@ -202,7 +221,7 @@ def _gpu_stream_sizes(ctx, coeffs, counts, B, H, W):
 def sweep(images, color_spaces: Sequence[str] = ("YCbCr",), quality_ranges: Sequence[Tuple[int, int]] = ((40, 80),),
           block_size_ranges: Sequence[Tuple[int, int]] = ((4, 64),), metrics: int = PSNR | SSIM | MS_SSIM, sizes: Optional[str] = "zlib",
           extension: Optional[str] = None, names: Optional[Sequence[str]] = None, device: int = 0, max_bytes: Optional[int] = None,
-          workers: Optional[int] = None) -> SweepResult:
+          workers: Optional[int] = None, lpips: Optional[_lpips.LpipsWeights] = None) -> SweepResult:
     """Every (colour space, quality range, block range) cell for every image: metrics and container sizes equal to
     ``EvaluationMetrics.batch(x, decompress_batch(compress_batch(x)))`` and ``len(compress_many(x, extension=...))`` of that cell.
 
@@ -210,12 +229,15 @@ def sweep(images, color_spaces: Sequence[str] = ("YCbCr",), quality_ranges: Sequ
     metrics: PSNR | SSIM | MS_SSIM (evaluation_metrics.py); columns not requested are NaN.  sizes: "zlib" | "gpu" | None (module doc).
     max_bytes: device bytes the sweep's buffers may use at their peak (default DEFAULT_MEMORY_FRACTION of the free memory); images are
     sub-batched and quality ranges grouped to stay below it -- metrics and "zlib" sizes do not depend on it.  workers: host zlib threads
-    (default: the cores this process may use).  The settings are bound on the device's context of the current stream, as Jpeg does: other
+    (default: the cores this process may use).  lpips: LpipsWeights -> also ``SweepResult.lpips`` (equal to
+    ``EvaluationMetrics.lpips_batch`` of every cell) and the ``lpips`` CSV column; images must then be at least 31x31.  The settings are bound on the device's context of the current stream, as Jpeg does: other
     Jpeg objects bind theirs again on their next call."""
     if sizes not in ("zlib", "gpu", None):
         raise ValueError("sizes must be 'zlib', 'gpu' or None")
     if metrics & ~(PSNR | SSIM | MS_SSIM):
         raise ValueError("metrics must be a combination of PSNR, SSIM and MS_SSIM")
+    if lpips is not None and not isinstance(lpips, _lpips.LpipsWeights):
+        raise TypeError("lpips must be LpipsWeights (LpipsWeights.load(...)) or None")
     color_spaces, quality_ranges, block_size_ranges = list(color_spaces), [tuple(q) for q in quality_ranges], [tuple(b) for b in block_size_ranges]
     if not color_spaces or not quality_ranges or not block_size_ranges:
         raise ValueError("every axis of the grid needs at least one value")
@@ -234,8 +256,11 @@ def sweep(images, color_spaces: Sequence[str] = ("YCbCr",), quality_ranges: Sequ
         for i, (h, w) in enumerate(shapes):
             if h < 161 or w < 161:
                 raise ValueError(f"image {i} ({h}x{w}): MS-SSIM needs images of at least 161x161.")
+    if lpips is not None:
+        for i, (h, w) in enumerate(shapes):
+            _lpips.check_size(h, w, f"image {i}")
     cells = list(itertools.product(color_spaces, quality_ranges, block_size_ranges))
-    res = SweepResult(cells, names, shapes, metrics, sizes)
+    res = SweepResult(cells, names, shapes, metrics, sizes, lpips=lpips is not None)
     col = {c: j for j, c in enumerate(cells)}
 
     ctx = get_context(device)
@@ -252,11 +277,12 @@ def sweep(images, color_spaces: Sequence[str] = ("YCbCr",), quality_ranges: Sequ
             x_all = ctx.to_device(batch, t.uint8 if is_u8 else t.float32)
             H, W = int(x_all.shape[1]), int(x_all.shape[2])
             ten_f32_255 = t.full((), 255.0, dtype=t.float32, device=ctx.device)
+            feats = {}                                              # (first image, count) -> the originals' LPIPS features of that sub-batch
             for cs, br in itertools.product(color_spaces, block_size_ranges):
                 codec.update_settings(JpegCompressionSettings(cs, quality_ranges[0], br))
                 ctx = codec._bind()
                 pending = _Pending(2 * n_workers // 3 // max(1, len(idx)) + 2) if pending is None else pending
-                plan = _Plan(ctx, len(idx), H, W, len(quality_ranges), metrics, sizes, max_bytes, 1 if is_u8 else 4)
+                plan = _Plan(ctx, len(idx), H, W, len(quality_ranges), metrics, sizes, max_bytes, 1 if is_u8 else 4, lpips is not None)
                 res.sub_batches.setdefault((cs, br), [])
                 for b0 in range(0, len(idx), plan.batch):
                     sub = idx[b0:b0 + plan.batch]
@@ -264,8 +290,14 @@ def sweep(images, color_spaces: Sequence[str] = ("YCbCr",), quality_ranges: Sequ
                     x = x_all[b0:b0 + len(sub)]
                     xf = (x.float() / ten_f32_255) if is_u8 else x      # Image.load's float32(v) / 255 (a tensor divisor: torch multiplies
                                                                          # by the reciprocal of a Python scalar, which is not always the quotient)
+                    fa = None
+                    if lpips is not None:                           # computed once per sub-batch, reused while the sub-batches repeat
+                        fa = feats.get((b0, len(sub)))
+                        if fa is None:
+                            feats.clear()
+                            fa = feats[b0, len(sub)] = _lpips.features(ctx, lpips, xf.contiguous())
                     _sweep_sub(ctx, codec, res, col, blobs, cs, br, quality_ranges, plan.group, sub, x, xf, metrics, sizes, extension,
-                               pool, pending)
+                               pool, pending, lpips, fa)
         while pending:
             _collect(res, pending.pop(0))
     finally:
@@ -277,7 +309,8 @@ def sweep(images, color_spaces: Sequence[str] = ("YCbCr",), quality_ranges: Sequ
     return res
 
 
-def _sweep_sub(ctx, codec, res, col, blobs, cs, br, quality_ranges, group, sub, x, xf, metrics, sizes, extension, pool, pending):
+def _sweep_sub(ctx, codec, res, col, blobs, cs, br, quality_ranges, group, sub, x, xf, metrics, sizes, extension, pool, pending, lpips=None,
+               feats=None):
     """Steps 2-4 of the module doc for one image sub-batch under one (colour space, block range)."""
     t = ctx.torch
     lib = ctx.lib
@@ -288,8 +321,9 @@ def _sweep_sub(ctx, codec, res, col, blobs, cs, br, quality_ranges, group, sub, 
     set_elems = B * p.coeff_stride
     dec_ws_bytes = int(lib.aej_decode_workspace_bytes(ctx.handle, B, H, W))
     met_ws_bytes = int(lib.aej_metrics_workspace_bytes(B, H, W)) if metrics else 0
+    lp_ws_bytes = int(lib.aej_lpips_workspace_bytes(B, H, W)) if lpips is not None else 0
     rgb = ctx.empty((B, H, W, 3), t.float32)
-    scores = []
+    scores, lp_scores = [], []
     for g0 in range(0, len(quality_ranges), group):
         qrs = quality_ranges[g0:g0 + group]
         blob_host = np.concatenate([blobs[cs, qr, br] for qr in qrs])
@@ -302,14 +336,17 @@ def _sweep_sub(ctx, codec, res, col, blobs, cs, br, quality_ranges, group, sub, 
             j = col[cs, qr, br]
             coeffs = out[s]
             qset = blob[s * set_words:(s + 1) * set_words]
-            if metrics:
-                ws = ctx.workspace(max(dec_ws_bytes, met_ws_bytes))
+            if metrics or lpips is not None:
+                ws = ctx.workspace(max(dec_ws_bytes, met_ws_bytes, lp_ws_bytes))
                 ctx.check(lib.aej_decode_batch_tables(ctx.handle, coeffs.data_ptr(), enc.leaves.data_ptr(), enc.counts.data_ptr(), B, H, W,
                                                       qset.data_ptr(), rgb.data_ptr(), ws.data_ptr(), ctypes.c_uint64(dec_ws_bytes)))
+            if metrics:
                 m = ctx.empty((B, 3), t.float64)
                 ctx.check(lib.aej_metrics_batch(ctx.handle, xf.data_ptr(), rgb.data_ptr(), B, H, W, metrics, m.data_ptr(), ws.data_ptr(),
                                                 ctypes.c_uint64(met_ws_bytes)))
                 scores.append((j, m))
+            if lpips is not None:
+                lp_scores.append((j, _lpips.score(ctx, lpips, rgb, feats_a=feats)))
             if sizes is None:
                 continue
             hdr = container_length(H, W, cs, qr, br, extension, [0, 0, 0], [0, 0, 0]) - 36
@@ -335,6 +372,11 @@ def _sweep_sub(ctx, codec, res, col, blobs, cs, br, quality_ranges, group, sub, 
         for (j, _), v in zip(scores, vals):
             for bi, i in enumerate(sub):
                 res.psnr[i, j], res.ssim[i, j], res.ms_ssim[i, j] = v[bi]
+    if lp_scores:
+        vals = t.stack([m for _, m in lp_scores]).cpu().numpy()   # [sets, B]
+        for (j, _), v in zip(lp_scores, vals):
+            for bi, i in enumerate(sub):
+                res.lpips[i, j] = v[bi]
 
 
 class _Pending(list):

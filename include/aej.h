@@ -173,11 +173,38 @@ AEJ_API int aej_encode_batch_u8(aej_ctx *ctx, const uint8_t *rgb_u8, int batch, 
  * of image pairs.  img_a, img_b: [batch][H][W][3] float32 in [0,1].  out: device [batch][3] float64 = {psnr (dB), ssim of
  * the 8-bit grey images, ms_ssim}; entries not requested in `which` are NaN.  The metrics are piq 0.8.0's (requirements.txt:22)
  * with the reference's arguments; AEJ_ERR_ARG where piq raises ValueError (image smaller than the 11x11 window after
- * pooling, or smaller than 161x161 for MS-SSIM).  lpips() is not offered: its AlexNet weights are a download. */
+ * pooling, or smaller than 161x161 for MS-SSIM).  lpips() is aej_lpips_batch below, with weights the caller supplies. */
 enum { AEJ_METRIC_PSNR = 1, AEJ_METRIC_SSIM = 2, AEJ_METRIC_MS_SSIM = 4 };
 AEJ_API uint64_t aej_metrics_workspace_bytes(int batch, int H, int W);
 AEJ_API int aej_metrics_batch(aej_ctx *ctx, const float *img_a, const float *img_b, int batch, int H, int W, int which,
                       double *out, void *workspace, uint64_t workspace_bytes);
+
+/* ---- EvaluationMetrics.lpips(): LPIPS(net='alex') of lpips 0.1.4 (evaluation_metrics.py:91-109) for a batch of image pairs --------
+ * The ScalingLayer ((x*2 - 1 - shift) / scale), AlexNet's `features` trunk up to conv5's ReLU with a tap after each of its five ReLUs,
+ * per tap and pixel d = sum_c lin[c] * (n0_c - n1_c)^2 of the channel-normalised features n = f / (sqrt(sum_c f_c^2) + 1e-10), the mean
+ * of d over the tap's pixels, and the sum over the taps.  Convolutions and normalisation in float32; the spatial means are accumulated in
+ * float64 in a fixed order without atomics, so a result is the same from run to run and element i of a batch equals a batch of one.
+ * Images must be at least 31 x 31 (AEJ_ERR_ARG otherwise: torch's second maxpool raises below that).
+ *
+ * Weights: the caller lists the parameters in the canonical order -- conv1..conv5 each as weight [Cout][Cin][k][k] then bias [Cout]
+ * (Cin, Cout, k = 3, 64, 11 / 64, 192, 5 / 192, 384, 3 / 384, 256, 3 / 256, 256, 3), then lin0..lin4 [Cout] -- aej_lpips_param_count()
+ * floats, and aej_lpips_pack_weights_host turns them into aej_lpips_weights_bytes() bytes of host memory in the kernels' layout; the
+ * caller copies that to the device and passes it as `weights` (it stays caller-owned).
+ * aej_lpips_features: the normalised taps of a batch of images into feats (aej_lpips_features_bytes; per image the five taps NHWC float32,
+ *   one image after the other) -- computed once, they stand for img_a in every later aej_lpips_batch with the same (H, W).
+ * aej_lpips_batch: out[b] (device float64) = LPIPS(img_a[b] or the taps feats_a[b], img_b[b]).  Exactly one of img_a / feats_a is given;
+ *   the two give bit-identical results.  img_*: [batch][H][W][3] float32 in [0, 1].
+ * Workspace: aej_lpips_workspace_bytes(batch, H, W) for aej_lpips_features and for aej_lpips_batch with feats_a; with img_a
+ *   aej_lpips_batch needs aej_lpips_features_bytes(batch, H, W) more (img_a's taps are kept there).  Both calls only enqueue work. */
+AEJ_API uint64_t aej_lpips_weights_bytes(void);
+AEJ_API int64_t aej_lpips_param_count(void);
+AEJ_API int aej_lpips_pack_weights_host(const float *params, int64_t n_params, void *packed_host);
+AEJ_API uint64_t aej_lpips_features_bytes(int batch, int H, int W);
+AEJ_API uint64_t aej_lpips_workspace_bytes(int batch, int H, int W);
+AEJ_API int aej_lpips_features(aej_ctx *ctx, const void *weights, const float *img, int batch, int H, int W, float *feats,
+                               void *workspace, uint64_t workspace_bytes);
+AEJ_API int aej_lpips_batch(aej_ctx *ctx, const void *weights, const float *img_a, const float *feats_a, const float *img_b, int batch,
+                            int H, int W, double *out, void *workspace, uint64_t workspace_bytes);
 
 /* ---- stage entry points (same kernels; used by the Python mirrors and the parity tests) -------- */
 
