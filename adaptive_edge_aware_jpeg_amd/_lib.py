@@ -189,6 +189,10 @@ SIGNATURES = {
     "aej_lpips_workspace_bytes": (_U64, [_I, _I, _I]),
     "aej_lpips_features": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _U64]),
     "aej_lpips_batch": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _U64]),
+    "aej_jfif_workspace_bytes": (_U64, [_I, _I, _I, _I]),
+    "aej_jfif_headers_host": (_I, [_I, _I, _I, _P, _I]),
+    "aej_jfif_encode_batch": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _U64, _P, _P, _P, _P, _U64]),
+    "aej_jfif_recon_batch": (_I, [_P, _I, _I, _I, _I, _P, _P, _U64]),
 }
 
 # status values of aej_inflate_batch / aej_decode_headers (include/aej.h AEJ_INFLATE_* / AEJ_HEADER_*)

@@ -188,4 +188,33 @@ void lpips_pack_host(const float *params, float *packed);
 void launch_lpips(hipStream_t st, const float *wpk, const float *img, int B, const LpipsGeom &g, float *X, float *Y, float *feats_out,
                   const float *feats_a, double *partial, double *out);
 
+
+// jfif.hip: baseline JPEG as Pillow / libjpeg-turbo writes it, and its decode (aej_jfif_*)
+constexpr int kJfifBlockWords = 52;    // 32-bit words that bound one block's Huffman codes (DC <= 22 bits, 63 AC <= 26 bits each)
+constexpr int kJfifHdrMax = 1024;      // SOI .. SOS are 623 bytes
+struct JfifGeom {
+    int B, H, W, nq;
+    int mcux, mcuy, ybx, yby;          // MCUs; real luma blocks per row / column
+    int yw, yh, cw, ch;                // reconstruction sample planes
+    long long n_mcu, nblk;             // blocks per image, 6 per MCU, dummies included
+    long long stream_words, n_chunks;  // per (quality, image): unstuffed scan words, 64-byte stuffing chunks
+    long long plane_bytes;             // per (quality, image): Y, Cb, Cr sample planes
+};
+struct JfifParams {                    // one quality: quantisers in zigzag order (luma, chroma) and the markers SOI .. SOS
+    int qt[2][64];
+    int hdr_len, pad_[3];
+    unsigned char hdr[kJfifHdrMax];
+};
+struct JfifBufs {
+    JfifParams *par; int *dct; short *coef; int *lens; long long *boff, *btot; unsigned *stream; int *ffcnt; long long *ffpre, *fftot, *total;
+    unsigned char *planes;
+};
+bool jfif_geom(int B, int H, int W, int nq, JfifGeom &g);
+unsigned long long jfif_carve(void *base, const JfifGeom &g, JfifBufs &w);
+void jfif_quant_tables(int q, int luma[64], int chroma[64]);
+void jfif_params_host(int q, int H, int W, JfifParams &p);
+hipError_t launch_jfif_encode(hipStream_t st, const JfifGeom &g, const JfifBufs &w, const JfifParams *par_host, const unsigned char *rgb,
+                              unsigned char *out, unsigned long long cap, long long *lengths, long long *offsets);
+hipError_t launch_jfif_recon(hipStream_t st, const JfifGeom &g, const JfifBufs &w, unsigned char *rgb_out);
+
 }  // namespace aej

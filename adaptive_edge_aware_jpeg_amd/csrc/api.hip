@@ -2018,3 +2018,75 @@ extern "C" int aej_lpips_batch(aej_ctx *ctx, const void *weights, const float *i
     AEJ_HIP_CHECK(hipGetLastError());
     return 0;
 }
+
+// ---- baseline JPEG as Pillow / libjpeg-turbo writes it (jfif.hip) --------------------------------------------------------------------
+static int jfif_args(aej_ctx *ctx, const char *fn, int batch, int H, int W, int n_q, JfifGeom &g)
+{
+    if (ctx && call_in_flight(ctx)) return fail(ctx, AEJ_ERR_STATE, "%s between aej_encode_batch_begin and aej_encode_batch_end", fn);
+    if (!jfif_geom(batch, H, W, n_q, g))
+        return fail(ctx, AEJ_ERR_ARG, "%s: bad shape %d x %d x %d with %d qualities (1 <= H, W <= 65535)", fn, batch, H, W, n_q);
+    return 0;
+}
+
+extern "C" uint64_t aej_jfif_workspace_bytes(int batch, int H, int W, int n_q)
+{
+    JfifGeom g;
+    if (!jfif_geom(batch, H, W, n_q, g)) return 0;
+    JfifBufs w;
+    return jfif_carve(nullptr, g, w);
+}
+
+extern "C" int aej_jfif_headers_host(int quality, int H, int W, uint8_t *out_host, int capacity)
+{
+    JfifGeom g;
+    if (quality < 1 || quality > 100 || !jfif_geom(1, H, W, 1, g) || !out_host) return AEJ_ERR_ARG;
+    JfifParams p;
+    jfif_params_host(quality, H, W, p);
+    if (capacity < p.hdr_len) return AEJ_ERR_CAPACITY;
+    memcpy(out_host, p.hdr, p.hdr_len);
+    return p.hdr_len;
+}
+
+extern "C" int aej_jfif_encode_batch(aej_ctx *ctx, const uint8_t *rgb, int batch, int H, int W, int n_q, const int32_t *qualities_host, uint8_t *out,
+                                     uint64_t out_capacity, int64_t *offsets, int64_t *lengths, uint64_t *total_host, void *workspace,
+                                     uint64_t workspace_bytes)
+{
+    if (!ctx) return AEJ_ERR_ARG;
+    JfifGeom g;
+    int rc = jfif_args(ctx, __func__, batch, H, W, n_q, g);
+    if (rc) return rc;
+    if (!rgb || !qualities_host || !offsets || !lengths || !total_host || !workspace) return fail(ctx, AEJ_ERR_ARG, "%s: NULL buffer", __func__);
+    std::vector<JfifParams> par(n_q);
+    for (int i = 0; i < n_q; i++) {
+        if (qualities_host[i] < 1 || qualities_host[i] > 100) return fail(ctx, AEJ_ERR_ARG, "%s: quality %d outside 1..100", __func__, qualities_host[i]);
+        jfif_params_host(qualities_host[i], H, W, par[i]);
+    }
+    JfifBufs w;
+    const unsigned long long need = jfif_carve(workspace, g, w);
+    if (need > workspace_bytes) return fail(ctx, AEJ_ERR_CAPACITY, "workspace too small: need %llu bytes, got %llu", need, (unsigned long long)workspace_bytes);
+    AEJ_HIP_CHECK(hipSetDevice(ctx->device));
+    AEJ_HIP_CHECK(launch_jfif_encode(ctx->stream, g, w, par.data(), rgb, out, out_capacity, (long long *)lengths, (long long *)offsets));
+    long long total = 0;
+    AEJ_HIP_CHECK(hipMemcpyAsync(&total, w.total, 8, hipMemcpyDeviceToHost, ctx->stream));
+    AEJ_HIP_CHECK(hipStreamSynchronize(ctx->stream));     // also keeps `par` alive until its upload has run
+    *total_host = (uint64_t)total;
+    if (out && (uint64_t)total > out_capacity)
+        return fail(ctx, AEJ_ERR_CAPACITY, "%s: the files need %lld bytes, the output holds %llu (nothing was written)", __func__, total,
+                    (unsigned long long)out_capacity);
+    return 0;
+}
+
+extern "C" int aej_jfif_recon_batch(aej_ctx *ctx, int batch, int H, int W, int n_q, uint8_t *rgb_out, void *workspace, uint64_t workspace_bytes)
+{
+    if (!ctx) return AEJ_ERR_ARG;
+    JfifGeom g;
+    int rc = jfif_args(ctx, __func__, batch, H, W, n_q, g);
+    if (rc) return rc;
+    if (!rgb_out || !workspace) return fail(ctx, AEJ_ERR_ARG, "%s: NULL buffer", __func__);
+    JfifBufs w;
+    const unsigned long long need = jfif_carve(workspace, g, w);
+    if (need > workspace_bytes) return fail(ctx, AEJ_ERR_CAPACITY, "workspace too small: need %llu bytes, got %llu", need, (unsigned long long)workspace_bytes);
+    AEJ_HIP_CHECK(hipSetDevice(ctx->device));
+    AEJ_HIP_CHECK(launch_jfif_recon(ctx->stream, g, w, rgb_out));
+    return 0;
+}

@@ -1,0 +1,602 @@
+// jfif.hip -- baseline JPEG as Pillow writes it with libjpeg-turbo (quality q, 4:2:0, Annex K tables, islow DCT, no restarts) and the
+// pixels Pillow's decoder returns for it (aej_jfif_*, include/aej.h).  The arithmetic restates libjpeg's published integer algorithm;
+// tests/jfif_reference.py is the same algorithm in numpy and tests/test_gpu_jfif.py pins both to Pillow's files byte for byte.
+//
+// Stages (one launch each, every quality of a call in the same launch after the first):
+//   k_jfif_fdct     one thread per 8 x 8 block of one image: colour, edge padding, 2 x 2 down-sampling, islow FDCT -> int32 (zigzag order)
+//   k_jfif_quant    one thread per (quality, image, block): quantise, resolve dummy blocks, count the block's Huffman bits
+//   k_jfif_scan     one workgroup per (quality, image): exclusive scan of per-block bit counts (and later of per-chunk 0xFF counts)
+//   k_jfif_emit     one thread per block: its code string at its bit offset, boundary words by atomicOr; the last block pads with 1-bits
+//   k_jfif_ffcount  one thread per 64-byte chunk of a stream: its 0xFF bytes
+//   k_jfif_layout   one thread: file lengths (markers + stuffed data + EOI) and their offsets in the packed output
+//   k_jfif_scatter  one thread per chunk: the chunk with a 0x00 after every 0xFF at its final place; chunk 0 also writes markers and EOI
+//   k_jfif_idct     one thread per (quality, image, real block): dequantise, islow IDCT, masked range limit -> uint8 sample planes
+//   k_jfif_rgb      one thread per output pixel: h2v2 fancy up-sampling (plain 2 x 2 replication when the chroma is <= 2 wide, as
+//                   libjpeg-turbo does) and the fixed-point YCbCr -> RGB
+// Bounds: every index derives from JfifGeom; a stream's words stay inside its stride (the per-block bound kJfifBlockWords holds for every
+// input: DC <= 22 bits, 63 AC <= 26 bits each); k_jfif_scatter writes a file only if it ends inside the caller's capacity.
+#include "aej_common.h"
+#include "aej_launch.h"
+
+namespace aej {
+
+constexpr int kJfThreads = 256;
+constexpr int kJfScanThreads = 1024;
+constexpr int kJfChunk = 64;           // bytes per stuffing chunk
+
+__constant__ unsigned char k_zz[64] = { 0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14,
+                                        21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46,
+                                        53, 60, 61, 54, 47, 55, 62, 63 };
+constexpr unsigned char kJfInvZz[64] = { 0, 1, 5, 6, 14, 15, 27, 28, 2, 4, 7, 13, 16, 26, 29, 42, 3, 8, 12, 17, 25, 30, 41, 43, 9, 11, 18, 24, 31, 40, 44, 53, 10, 19, 23, 32, 39, 45, 52, 54, 20, 22, 33, 38, 46, 51, 55, 60, 21, 34, 37, 47, 50, 56, 59, 61, 35, 36, 48, 49, 57, 58, 62, 63 };      // zigzag position of natural index
+// Annex K.3 Huffman codes, (code << 8) | length, indexed by symbol (0 = symbol not in the table)
+// dc_luma: (code << 8) | length
+__constant__ unsigned k_dc_luma[16] = {
+    2, 515, 771, 1027, 1283, 1539, 3588, 7685, 15878, 32263, 65032, 130569, 0, 0, 0, 0};
+// dc_chroma: (code << 8) | length
+__constant__ unsigned k_dc_chroma[16] = {
+    2, 258, 514, 1539, 3588, 7685, 15878, 32263, 65032, 130569, 261642, 523787, 0, 0, 0, 0};
+// ac_luma: (code << 8) | length
+__constant__ unsigned k_ac_luma[256] = {
+    2564, 2, 258, 1027, 2820, 6661, 30727, 63496, 259594, 16744976, 16745232, 0, 0, 0, 0, 0,
+    0, 3076, 6917, 30983, 128521, 521739, 16745488, 16745744, 16746000, 16746256, 16746512, 0, 0, 0, 0, 0,
+    0, 7173, 63752, 259850, 1045516, 16746768, 16747024, 16747280, 16747536, 16747792, 16748048, 0, 0, 0, 0, 0,
+    0, 14854, 128777, 1045772, 16748304, 16748560, 16748816, 16749072, 16749328, 16749584, 16749840, 0, 0, 0, 0, 0,
+    0, 15110, 260106, 16750096, 16750352, 16750608, 16750864, 16751120, 16751376, 16751632, 16751888, 0, 0, 0, 0, 0,
+    0, 31239, 521995, 16752144, 16752400, 16752656, 16752912, 16753168, 16753424, 16753680, 16753936, 0, 0, 0, 0, 0,
+    0, 31495, 1046028, 16754192, 16754448, 16754704, 16754960, 16755216, 16755472, 16755728, 16755984, 0, 0, 0, 0, 0,
+    0, 64008, 1046284, 16756240, 16756496, 16756752, 16757008, 16757264, 16757520, 16757776, 16758032, 0, 0, 0, 0, 0,
+    0, 129033, 8372239, 16758288, 16758544, 16758800, 16759056, 16759312, 16759568, 16759824, 16760080, 0, 0, 0, 0, 0,
+    0, 129289, 16760336, 16760592, 16760848, 16761104, 16761360, 16761616, 16761872, 16762128, 16762384, 0, 0, 0, 0, 0,
+    0, 129545, 16762640, 16762896, 16763152, 16763408, 16763664, 16763920, 16764176, 16764432, 16764688, 0, 0, 0, 0, 0,
+    0, 260362, 16764944, 16765200, 16765456, 16765712, 16765968, 16766224, 16766480, 16766736, 16766992, 0, 0, 0, 0, 0,
+    0, 260618, 16767248, 16767504, 16767760, 16768016, 16768272, 16768528, 16768784, 16769040, 16769296, 0, 0, 0, 0, 0,
+    0, 522251, 16769552, 16769808, 16770064, 16770320, 16770576, 16770832, 16771088, 16771344, 16771600, 0, 0, 0, 0, 0,
+    0, 16771856, 16772112, 16772368, 16772624, 16772880, 16773136, 16773392, 16773648, 16773904, 16774160, 0, 0, 0, 0, 0,
+    522507, 16774416, 16774672, 16774928, 16775184, 16775440, 16775696, 16775952, 16776208, 16776464, 16776720, 0, 0, 0, 0, 0};
+// ac_chroma: (code << 8) | length
+__constant__ unsigned k_ac_chroma[256] = {
+    2, 258, 1027, 2564, 6149, 6405, 14342, 30727, 128009, 259594, 1045516, 0, 0, 0, 0, 0,
+    0, 2820, 14598, 62984, 128265, 521739, 1045772, 16746512, 16746768, 16747024, 16747280, 0, 0, 0, 0, 0,
+    0, 6661, 63240, 259850, 1046028, 8372751, 16747536, 16747792, 16748048, 16748304, 16748560, 0, 0, 0, 0, 0,
+    0, 6917, 63496, 260106, 1046284, 16748816, 16749072, 16749328, 16749584, 16749840, 16750096, 0, 0, 0, 0, 0,
+    0, 14854, 128521, 16750352, 16750608, 16750864, 16751120, 16751376, 16751632, 16751888, 16752144, 0, 0, 0, 0, 0,
+    0, 15110, 260362, 16752400, 16752656, 16752912, 16753168, 16753424, 16753680, 16753936, 16754192, 0, 0, 0, 0, 0,
+    0, 30983, 521995, 16754448, 16754704, 16754960, 16755216, 16755472, 16755728, 16755984, 16756240, 0, 0, 0, 0, 0,
+    0, 31239, 522251, 16756496, 16756752, 16757008, 16757264, 16757520, 16757776, 16758032, 16758288, 0, 0, 0, 0, 0,
+    0, 63752, 16758544, 16758800, 16759056, 16759312, 16759568, 16759824, 16760080, 16760336, 16760592, 0, 0, 0, 0, 0,
+    0, 128777, 16760848, 16761104, 16761360, 16761616, 16761872, 16762128, 16762384, 16762640, 16762896, 0, 0, 0, 0, 0,
+    0, 129033, 16763152, 16763408, 16763664, 16763920, 16764176, 16764432, 16764688, 16764944, 16765200, 0, 0, 0, 0, 0,
+    0, 129289, 16765456, 16765712, 16765968, 16766224, 16766480, 16766736, 16766992, 16767248, 16767504, 0, 0, 0, 0, 0,
+    0, 129545, 16767760, 16768016, 16768272, 16768528, 16768784, 16769040, 16769296, 16769552, 16769808, 0, 0, 0, 0, 0,
+    0, 522507, 16770064, 16770320, 16770576, 16770832, 16771088, 16771344, 16771600, 16771856, 16772112, 0, 0, 0, 0, 0,
+    0, 4186126, 16772368, 16772624, 16772880, 16773136, 16773392, 16773648, 16773904, 16774160, 16774416, 0, 0, 0, 0, 0,
+    260618, 8373007, 16774672, 16774928, 16775184, 16775440, 16775696, 16775952, 16776208, 16776464, 16776720, 0, 0, 0, 0, 0};
+
+// ---- arithmetic shared by the stages ----------------------------------------------------------------------------------------------
+__device__ __forceinline__ int jf_y(const unsigned char *p) { return (19595 * p[0] + 38470 * p[1] + 7471 * p[2] + 32768) >> 16; }
+__device__ __forceinline__ int jf_c(const unsigned char *p, int comp)      // Cb (0) / Cr (1), libjpeg's rounding (ONE_HALF - 1)
+{
+    return comp == 0 ? (-11059 * p[0] - 21709 * p[1] + 32768 * p[2] + (128 << 16) + 32767) >> 16
+                     : (32768 * p[0] - 27439 * p[1] - 5329 * p[2] + (128 << 16) + 32767) >> 16;
+}
+__device__ __forceinline__ long long jf_descale(long long x, int n) { return (x + (1LL << (n - 1))) >> n; }
+
+// jfdctint, one 8-point pass over d[0], d[s], ..., d[7s]; pass 1 keeps PASS1_BITS of extra precision, pass 2 removes it
+template <bool kPass1>
+__device__ __forceinline__ void jf_fdct8(long long *d, int s)
+{
+    const int n = kPass1 ? 11 : 15;
+    long long t0 = d[0] + d[7 * s], t7 = d[0] - d[7 * s], t1 = d[s] + d[6 * s], t6 = d[s] - d[6 * s];
+    long long t2 = d[2 * s] + d[5 * s], t5 = d[2 * s] - d[5 * s], t3 = d[3 * s] + d[4 * s], t4 = d[3 * s] - d[4 * s];
+    long long t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+    d[0] = kPass1 ? (t10 + t11) * 4 : jf_descale(t10 + t11, 2);
+    d[4 * s] = kPass1 ? (t10 - t11) * 4 : jf_descale(t10 - t11, 2);
+    long long z1 = (t12 + t13) * 4433;
+    d[2 * s] = jf_descale(z1 + t13 * 6270, n);
+    d[6 * s] = jf_descale(z1 - t12 * 15137, n);
+    z1 = t4 + t7;
+    long long z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7, z5 = (z3 + z4) * 9633;
+    t4 *= 2446; t5 *= 16819; t6 *= 25172; t7 *= 12299;
+    z1 *= -7373; z2 *= -20995; z3 = z3 * -16069 + z5; z4 = z4 * -3196 + z5;
+    d[7 * s] = jf_descale(t4 + z1 + z3, n);
+    d[5 * s] = jf_descale(t5 + z2 + z4, n);
+    d[3 * s] = jf_descale(t6 + z2 + z3, n);
+    d[s] = jf_descale(t7 + z1 + z4, n);
+}
+
+// jidctint, one 8-point pass; pass 1 (columns) descales by CONST_BITS - PASS1_BITS, pass 2 (rows) by CONST_BITS + PASS1_BITS + 3
+template <bool kPass1>
+__device__ __forceinline__ void jf_idct8(long long *d, int s)
+{
+    const int n = kPass1 ? 11 : 18;
+    long long z2 = d[2 * s], z3 = d[6 * s], z1 = (z2 + z3) * 4433;
+    long long t2 = z1 - z3 * 15137, t3 = z1 + z2 * 6270;
+    long long t0 = (d[0] + d[4 * s]) * 8192, t1 = (d[0] - d[4 * s]) * 8192;
+    long long t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+    t0 = d[7 * s]; t1 = d[5 * s]; t2 = d[3 * s]; t3 = d[s];
+    z1 = t0 + t3; z2 = t1 + t2; z3 = t0 + t2;
+    long long z4 = t1 + t3, z5 = (z3 + z4) * 9633;
+    t0 *= 2446; t1 *= 16819; t2 *= 25172; t3 *= 12299;
+    z1 *= -7373; z2 *= -20995; z3 = z3 * -16069 + z5; z4 = z4 * -3196 + z5;
+    t0 += z1 + z3; t1 += z2 + z4; t2 += z2 + z3; t3 += z1 + z4;
+    d[0] = jf_descale(t10 + t3, n); d[7 * s] = jf_descale(t10 - t3, n);
+    d[s] = jf_descale(t11 + t2, n); d[6 * s] = jf_descale(t11 - t2, n);
+    d[2 * s] = jf_descale(t12 + t1, n); d[5 * s] = jf_descale(t12 - t1, n);
+    d[3 * s] = jf_descale(t13 + t0, n); d[4 * s] = jf_descale(t13 - t0, n);
+}
+
+__device__ __forceinline__ int jf_quant(int c, int qt)      // libjpeg's quantiser of islow output: divisor 8 qt, rounded half away from zero
+{
+    const int q = qt << 3, a = ((c < 0 ? -c : c) + (q >> 1)) / q;
+    return c < 0 ? -a : a;
+}
+__device__ __forceinline__ int jf_cat(int v) { return v == 0 ? 0 : 32 - __clz(v < 0 ? -v : v); }
+
+// MCU geometry: block k (0..3 luma in raster order, 4 Cb, 5 Cr) of MCU m; luma blocks outside ceil(H/8) x ceil(W/8) are dummies
+__device__ __forceinline__ bool jf_real(const JfifGeom &g, long long m, int k)
+{
+    if (k >= 4) return true;
+    const int my = (int)(m / g.mcux), mx = (int)(m % g.mcux);
+    return 2 * my + (k >> 1) < g.yby && 2 * mx + (k & 1) < g.ybx;
+}
+// quantised DC of block k of MCU m under the quality's tables: a dummy takes the DC of the block before it in the MCU (block 0 is real)
+__device__ __forceinline__ int jf_qdc(const JfifGeom &g, const int *dct_img, const JfifParams &p, long long m, int k)
+{
+    while (!jf_real(g, m, k)) k--;
+    return jf_quant(dct_img[(m * 6 + k) * 64], p.qt[k >= 4][0]);
+}
+// the block of the same component before block (m, k) in scan order, -1 at the start of the scan
+__device__ __forceinline__ long long jf_prev(long long m, int k)
+{
+    if (k >= 1 && k <= 3) return m * 6 + k - 1;
+    if (m == 0) return -1;
+    return k == 0 ? (m - 1) * 6 + 3 : (m - 1) * 6 + k;
+}
+
+// ---- encode ------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kJfThreads) void k_jfif_fdct(JfifGeom g, const unsigned char *__restrict__ rgb, int *__restrict__ dct)
+{
+    const long long idx = (long long)blockIdx.x * kJfThreads + threadIdx.x;
+    if (idx >= (long long)g.B * g.nblk) return;
+    const int b = (int)(idx / g.nblk);
+    const long long blk = idx % g.nblk, m = blk / 6;
+    const int k = (int)(blk % 6), my = (int)(m / g.mcux), mx = (int)(m % g.mcux);
+    const unsigned char *img = rgb + (long long)b * g.H * g.W * 3;
+    long long d[64];
+    if (k < 4) {
+        const int by = 2 * my + (k >> 1), bx = 2 * mx + (k & 1);
+        if (by >= g.yby || bx >= g.ybx) return;          // dummy: never read
+#pragma unroll
+        for (int r = 0; r < 8; r++) {
+            const int py = min(by * 8 + r, g.H - 1);
+#pragma unroll
+            for (int c = 0; c < 8; c++) d[r * 8 + c] = jf_y(img + ((long long)py * g.W + min(bx * 8 + c, g.W - 1)) * 3) - 128;
+        }
+    } else {
+        const int comp = k - 4, hc = (g.H + 1) / 2;
+#pragma unroll
+        for (int r = 0; r < 8; r++) {
+            const int cy = min(my * 8 + r, hc - 1), y0 = 2 * cy, y1 = min(2 * cy + 1, g.H - 1);
+            const unsigned char *r0 = img + (long long)y0 * g.W * 3, *r1 = img + (long long)y1 * g.W * 3;
+#pragma unroll
+            for (int c = 0; c < 8; c++) {
+                const int cx = mx * 8 + c, x0 = min(2 * cx, g.W - 1) * 3, x1 = min(2 * cx + 1, g.W - 1) * 3;
+                const int sum = jf_c(r0 + x0, comp) + jf_c(r0 + x1, comp) + jf_c(r1 + x0, comp) + jf_c(r1 + x1, comp);
+                d[r * 8 + c] = ((sum + 1 + (cx & 1)) >> 2) - 128;
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 8; r++) jf_fdct8<true>(d + r * 8, 1);
+#pragma unroll
+    for (int c = 0; c < 8; c++) jf_fdct8<false>(d + c, 8);
+    int *o = dct + idx * 64;
+#pragma unroll
+    for (int i = 0; i < 64; i++) o[i] = (int)d[i];
+}
+
+struct JfCodes { const unsigned *dc, *ac; };
+__device__ __forceinline__ JfCodes jf_codes(int k) { return k >= 4 ? JfCodes{ k_dc_chroma, k_ac_chroma } : JfCodes{ k_dc_luma, k_ac_luma }; }
+
+// (a) quantise every block of every (quality, image) and count its Huffman bits
+__global__ __launch_bounds__(kJfThreads) void k_jfif_quant(JfifGeom g, const JfifParams *__restrict__ par, const int *__restrict__ dct,
+                                                           short *__restrict__ coef, int *__restrict__ lens)
+{
+    const long long idx = (long long)blockIdx.x * kJfThreads + threadIdx.x;
+    if (idx >= (long long)g.nq * g.B * g.nblk) return;
+    const long long seg = idx / g.nblk, blk = idx % g.nblk, m = blk / 6;
+    const int k = (int)(blk % 6), b = (int)(seg % g.B);
+    const JfifParams &p = par[seg / g.B];
+    const int *qt = p.qt[k >= 4];
+    const int *img = dct + (long long)b * g.nblk * 64;
+    const JfCodes hc = jf_codes(k);
+    short *o = coef + idx * 64;
+    const int dc = jf_qdc(g, img, p, m, k);
+    const long long pb = jf_prev(m, k);
+    const int diff = dc - (pb < 0 ? 0 : jf_qdc(g, img, p, pb / 6, (int)(pb % 6)));
+    const int dcat = jf_cat(diff);
+    int bits = (int)(hc.dc[dcat] & 255) + dcat;
+    o[0] = (short)dc;
+    if (!jf_real(g, m, k)) {
+        for (int i = 1; i < 64; i++) o[i] = 0;
+        lens[idx] = bits + (int)(hc.ac[0] & 255);
+        return;
+    }
+    const int *d = img + blk * 64;
+    int run = 0;
+    for (int i = 1; i < 64; i++) {
+        const int v = jf_quant(d[k_zz[i]], qt[i]);
+        o[i] = (short)v;
+        if (v == 0) { run++; continue; }
+        const int cat = jf_cat(v);
+        bits += (run >> 4) * (int)(hc.ac[0xF0] & 255) + (int)(hc.ac[((run & 15) << 4) | cat] & 255) + cat;
+        run = 0;
+    }
+    if (run) bits += (int)(hc.ac[0] & 255);
+    lens[idx] = bits;
+}
+
+// (b) exclusive scan of n int32 per segment (one workgroup per segment) -> int64 offsets and the segment's total
+__global__ __launch_bounds__(kJfScanThreads) void k_jfif_scan(const int *__restrict__ in, long long n, long long *__restrict__ out,
+                                                              long long *__restrict__ tot)
+{
+    __shared__ long long s[kJfScanThreads];
+    const long long seg = blockIdx.x, per = (n + kJfScanThreads - 1) / kJfScanThreads;
+    const long long lo = min(n, threadIdx.x * per), hi = min(n, lo + per);
+    const int *src = in + seg * n;
+    long long sum = 0;
+    for (long long i = lo; i < hi; i++) sum += src[i];
+    s[threadIdx.x] = sum;
+    __syncthreads();
+    for (int off = 1; off < kJfScanThreads; off <<= 1) {     // Hillis-Steele inclusive scan of the thread sums
+        const long long v = threadIdx.x >= off ? s[threadIdx.x - off] : 0;
+        __syncthreads();
+        s[threadIdx.x] += v;
+        __syncthreads();
+    }
+    long long run = s[threadIdx.x] - sum;
+    long long *dst = out + seg * n;
+    for (long long i = lo; i < hi; i++) {
+        dst[i] = run;
+        run += src[i];
+    }
+    if (threadIdx.x == kJfScanThreads - 1) tot[seg] = s[kJfScanThreads - 1];
+}
+
+// big-endian bit writer into 32-bit words (stream byte order in memory); words shared with neighbouring blocks are ORed in
+struct JfBits {
+    unsigned *w;
+    long long wi, limit;
+    unsigned long long acc;
+    int n;
+    __device__ JfBits(unsigned *words, long long pos, long long lim) : w(words), wi(pos >> 5), limit(lim), acc(0), n((int)(pos & 31)) {}
+    __device__ __forceinline__ void word(unsigned v)
+    {
+        if (wi < limit) atomicOr(w + wi, __builtin_bswap32(v));
+        wi++;
+    }
+    __device__ __forceinline__ void put(unsigned code, int len)      // len <= 27
+    {
+        acc = (acc << len) | code;
+        n += len;
+        if (n >= 32) {
+            n -= 32;
+            word((unsigned)(acc >> n));
+            acc &= (1ull << n) - 1;
+        }
+    }
+    __device__ __forceinline__ void finish()
+    {
+        if (n > 0) word((unsigned)(acc << (32 - n)));
+    }
+};
+
+__global__ __launch_bounds__(kJfThreads) void k_jfif_zero(JfifGeom g, const long long *__restrict__ btot, unsigned *__restrict__ stream)
+{
+    const long long seg = blockIdx.y, i = (long long)blockIdx.x * kJfThreads + threadIdx.x;
+    if (i < min(g.stream_words, (btot[seg] + 31) / 32)) stream[seg * g.stream_words + i] = 0;
+}
+
+// (c) every block's code string at its bit offset
+__global__ __launch_bounds__(kJfThreads) void k_jfif_emit(JfifGeom g, const short *__restrict__ coef, const long long *__restrict__ boff,
+                                                          const long long *__restrict__ btot, unsigned *__restrict__ stream)
+{
+    const long long idx = (long long)blockIdx.x * kJfThreads + threadIdx.x;
+    if (idx >= (long long)g.nq * g.B * g.nblk) return;
+    const long long seg = idx / g.nblk, blk = idx % g.nblk, m = blk / 6;
+    const int k = (int)(blk % 6);
+    const JfCodes hc = jf_codes(k);
+    const short *c = coef + idx * 64;
+    const long long pb = jf_prev(m, k);
+    JfBits bw(stream + seg * g.stream_words, boff[idx], g.stream_words);
+    const int diff = c[0] - (pb < 0 ? 0 : coef[(seg * g.nblk + pb) * 64]);
+    const int dcat = jf_cat(diff);
+    bw.put(hc.dc[dcat] >> 8, (int)(hc.dc[dcat] & 255));
+    if (dcat) bw.put((unsigned)(diff < 0 ? diff - 1 : diff) & ((1u << dcat) - 1), dcat);
+    int run = 0;
+    for (int i = 1; i < 64; i++) {
+        const int v = c[i];
+        if (v == 0) { run++; continue; }
+        for (; run > 15; run -= 16) bw.put(hc.ac[0xF0] >> 8, (int)(hc.ac[0xF0] & 255));
+        const int cat = jf_cat(v);
+        const unsigned e = hc.ac[(run << 4) | cat];
+        bw.put(e >> 8, (int)(e & 255));
+        bw.put((unsigned)(v < 0 ? v - 1 : v) & ((1u << cat) - 1), cat);
+        run = 0;
+    }
+    if (run) bw.put(hc.ac[0] >> 8, (int)(hc.ac[0] & 255));
+    if (blk == g.nblk - 1) {                                 // pad the last byte with 1-bits
+        const int pad = (int)((8 - (btot[seg] & 7)) & 7);
+        if (pad) bw.put((1u << pad) - 1, pad);
+    }
+    bw.finish();
+}
+
+// 0xFF bytes per 64-byte chunk of each stream's data
+__global__ __launch_bounds__(kJfThreads) void k_jfif_ffcount(JfifGeom g, const long long *__restrict__ btot, const unsigned *__restrict__ stream,
+                                                             int *__restrict__ cnt)
+{
+    const long long idx = (long long)blockIdx.x * kJfThreads + threadIdx.x;
+    if (idx >= (long long)g.nq * g.B * g.n_chunks) return;
+    const long long seg = idx / g.n_chunks, ch = idx % g.n_chunks, nbytes = min(g.stream_words * 4, (btot[seg] + 7) >> 3);
+    const long long lo = ch * kJfChunk, hi = min(nbytes, lo + kJfChunk);
+    const unsigned char *src = reinterpret_cast<const unsigned char *>(stream + seg * g.stream_words);
+    int n = 0;
+    for (long long i = lo; i < hi; i++) n += src[i] == 0xFF;
+    cnt[idx] = n;
+}
+
+// file lengths (markers + stuffed data + EOI) and their offsets in the packed output, segments in (quality, image) order
+__global__ void k_jfif_layout(JfifGeom g, const JfifParams *__restrict__ par, const long long *__restrict__ btot,
+                              const long long *__restrict__ fftot, long long *__restrict__ lengths, long long *__restrict__ offsets,
+                              long long *__restrict__ total)
+{
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    long long off = 0;
+    for (long long seg = 0; seg < (long long)g.nq * g.B; seg++) {
+        const long long len = par[seg / g.B].hdr_len + ((btot[seg] + 7) >> 3) + fftot[seg] + 2;
+        lengths[seg] = len;
+        offsets[seg] = off;
+        off += len;
+    }
+    *total = off;
+}
+
+__global__ __launch_bounds__(kJfThreads) void k_jfif_scatter(JfifGeom g, const JfifParams *__restrict__ par, const long long *__restrict__ btot,
+                                                             const unsigned *__restrict__ stream, const long long *__restrict__ ffpre,
+                                                             const long long *__restrict__ lengths, const long long *__restrict__ offsets,
+                                                             unsigned char *__restrict__ out, unsigned long long cap)
+{
+    const long long idx = (long long)blockIdx.x * kJfThreads + threadIdx.x;
+    if (idx >= (long long)g.nq * g.B * g.n_chunks) return;
+    const long long seg = idx / g.n_chunks, ch = idx % g.n_chunks;
+    const long long off = offsets[seg], len = lengths[seg];
+    if (off < 0 || len < 0 || (unsigned long long)(off + len) > cap) return;
+    const JfifParams &p = par[seg / g.B];
+    unsigned char *file = out + off;
+    if (ch == 0) {
+        for (int i = 0; i < p.hdr_len; i++) file[i] = p.hdr[i];
+        file[len - 2] = 0xFF;
+        file[len - 1] = 0xD9;
+    }
+    const long long nbytes = (btot[seg] + 7) >> 3, lo = ch * kJfChunk, hi = min(nbytes, lo + kJfChunk);
+    const unsigned char *src = reinterpret_cast<const unsigned char *>(stream + seg * g.stream_words);
+    unsigned char *dst = file + p.hdr_len + lo + (lo < hi ? ffpre[idx] : 0);
+    for (long long i = lo; i < hi; i++) {
+        const unsigned char v = src[i];
+        *dst++ = v;
+        if (v == 0xFF) *dst++ = 0;
+    }
+}
+
+// ---- reconstruction ----------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ unsigned char jf_range_limit(long long x)      // libjpeg's masked table: wraps as the decoder's does
+{
+    const int m = (int)(x & 1023);
+    return (unsigned char)(m < 128 ? m + 128 : m < 512 ? 255 : m < 896 ? 0 : m - 896);
+}
+
+__global__ __launch_bounds__(kJfThreads) void k_jfif_idct(JfifGeom g, const JfifParams *__restrict__ par, const short *__restrict__ coef,
+                                                          unsigned char *__restrict__ planes)
+{
+    const long long idx = (long long)blockIdx.x * kJfThreads + threadIdx.x;
+    if (idx >= (long long)g.nq * g.B * g.nblk) return;
+    const long long seg = idx / g.nblk, blk = idx % g.nblk, m = blk / 6;
+    const int k = (int)(blk % 6), my = (int)(m / g.mcux), mx = (int)(m % g.mcux);
+    if (!jf_real(g, m, k)) return;
+    const int *qt = par[seg / g.B].qt[k >= 4];
+    const short *c = coef + idx * 64;
+    long long d[64];
+#pragma unroll
+    for (int j = 0; j < 64; j++) d[j] = c[kJfInvZz[j]] * qt[kJfInvZz[j]];      // natural order (j constant after unrolling)
+#pragma unroll
+    for (int col = 0; col < 8; col++) jf_idct8<true>(d + col, 8);
+#pragma unroll
+    for (int r = 0; r < 8; r++) jf_idct8<false>(d + r * 8, 1);
+    unsigned char *pl = planes + seg * g.plane_bytes;
+    int stride, y0, x0;
+    if (k < 4) {
+        stride = g.yw; y0 = (2 * my + (k >> 1)) * 8; x0 = (2 * mx + (k & 1)) * 8;
+    } else {
+        pl += (long long)g.yh * g.yw + (long long)(k - 4) * g.ch * g.cw;
+        stride = g.cw; y0 = my * 8; x0 = mx * 8;
+    }
+#pragma unroll
+    for (int r = 0; r < 8; r++)
+#pragma unroll
+        for (int cc = 0; cc < 8; cc++) pl[(long long)(y0 + r) * stride + x0 + cc] = jf_range_limit(d[r * 8 + cc]);
+}
+
+// chroma sample of output pixel (y, x): h2v2 fancy up-sampling of the real ceil(H/2) x ceil(W/2) samples (2 x 2 replication when that
+// is at most 2 wide); the row above the first and below the last real chroma row is that row itself
+__device__ __forceinline__ int jf_chroma(const JfifGeom &g, const unsigned char *p, int y, int x)
+{
+    const int hc = (g.H + 1) / 2, wc = (g.W + 1) / 2, cy = y >> 1, j = x >> 1;
+    if (wc <= 2) return p[(long long)cy * g.cw + j];
+    const int far = (y & 1) ? min(cy + 1, hc - 1) : max(cy - 1, 0);
+    const unsigned char *n0 = p + (long long)cy * g.cw, *n1 = p + (long long)far * g.cw;
+    const int cs = 3 * n0[j] + n1[j];
+    if ((x & 1) == 0) return j == 0 ? (4 * cs + 8) >> 4 : (3 * cs + 3 * n0[j - 1] + n1[j - 1] + 8) >> 4;
+    return j == wc - 1 ? (4 * cs + 7) >> 4 : (3 * cs + 3 * n0[j + 1] + n1[j + 1] + 7) >> 4;
+}
+
+__global__ __launch_bounds__(kJfThreads) void k_jfif_rgb(JfifGeom g, const unsigned char *__restrict__ planes, unsigned char *__restrict__ out)
+{
+    const long long idx = (long long)blockIdx.x * kJfThreads + threadIdx.x;
+    const long long px = (long long)g.H * g.W;
+    if (idx >= (long long)g.nq * g.B * px) return;
+    const long long seg = idx / px, r = idx % px;
+    const int y = (int)(r / g.W), x = (int)(r % g.W);
+    const unsigned char *pl = planes + seg * g.plane_bytes;
+    const int Y = pl[(long long)y * g.yw + x];
+    const unsigned char *cbp = pl + (long long)g.yh * g.yw, *crp = cbp + (long long)g.ch * g.cw;
+    const int cb = jf_chroma(g, cbp, y, x) - 128, cr = jf_chroma(g, crp, y, x) - 128;
+    const int R = Y + ((91881 * cr + 32768) >> 16);
+    const int G = Y + ((-22554 * cb + 32768 - 46802 * cr) >> 16);
+    const int B = Y + ((116130 * cb + 32768) >> 16);
+    unsigned char *o = out + idx * 3;
+    o[0] = (unsigned char)min(max(R, 0), 255);
+    o[1] = (unsigned char)min(max(G, 0), 255);
+    o[2] = (unsigned char)min(max(B, 0), 255);
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------------------
+// Annex K.3 tables as DHT carries them: BITS[1..16] then HUFFVAL (host side, for the markers)
+static const unsigned char kDht_dc_luma[28] = {
+    0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+static const unsigned char kDht_ac_luma[178] = {
+    0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125, 1, 2, 3, 0, 4, 17, 5, 18, 33, 49, 65, 6,
+    19, 81, 97, 7, 34, 113, 20, 50, 129, 145, 161, 8, 35, 66, 177, 193, 21, 82, 209, 240, 36, 51, 98, 114, 130, 9, 10, 22,
+    23, 24, 25, 26, 37, 38, 39, 40, 41, 42, 52, 53, 54, 55, 56, 57, 58, 67, 68, 69, 70, 71, 72, 73, 74, 83, 84, 85,
+    86, 87, 88, 89, 90, 99, 100, 101, 102, 103, 104, 105, 106, 115, 116, 117, 118, 119, 120, 121, 122, 131, 132, 133, 134, 135, 136, 137,
+    138, 146, 147, 148, 149, 150, 151, 152, 153, 154, 162, 163, 164, 165, 166, 167, 168, 169, 170, 178, 179, 180, 181, 182, 183, 184, 185, 186,
+    194, 195, 196, 197, 198, 199, 200, 201, 202, 210, 211, 212, 213, 214, 215, 216, 217, 218, 225, 226, 227, 228, 229, 230, 231, 232, 233, 234,
+    241, 242, 243, 244, 245, 246, 247, 248, 249, 250};
+static const unsigned char kDht_dc_chroma[28] = {
+    0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+static const unsigned char kDht_ac_chroma[178] = {
+    0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119, 0, 1, 2, 3, 17, 4, 5, 33, 49, 6, 18, 65,
+    81, 7, 97, 113, 19, 34, 50, 129, 8, 20, 66, 145, 161, 177, 193, 9, 35, 51, 82, 240, 21, 98, 114, 209, 10, 22, 36, 52,
+    225, 37, 241, 23, 24, 25, 26, 38, 39, 40, 41, 42, 53, 54, 55, 56, 57, 58, 67, 68, 69, 70, 71, 72, 73, 74, 83, 84,
+    85, 86, 87, 88, 89, 90, 99, 100, 101, 102, 103, 104, 105, 106, 115, 116, 117, 118, 119, 120, 121, 122, 130, 131, 132, 133, 134, 135,
+    136, 137, 138, 146, 147, 148, 149, 150, 151, 152, 153, 154, 162, 163, 164, 165, 166, 167, 168, 169, 170, 178, 179, 180, 181, 182, 183, 184,
+    185, 186, 194, 195, 196, 197, 198, 199, 200, 201, 202, 210, 211, 212, 213, 214, 215, 216, 217, 218, 226, 227, 228, 229, 230, 231, 232, 233,
+    234, 242, 243, 244, 245, 246, 247, 248, 249, 250};
+static const unsigned char kLumaBase[64] = { 16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99 };
+static const unsigned char kChromaBase[64] = { 17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99 };
+
+bool jfif_geom(int B, int H, int W, int nq, JfifGeom &g)
+{
+    if (B < 1 || nq < 1 || H < 1 || W < 1 || H > 65535 || W > 65535 || (long long)B * nq > 65535) return false;      // segments index grid.y
+    g.B = B; g.H = H; g.W = W; g.nq = nq;
+    g.mcux = (W + 15) / 16; g.mcuy = (H + 15) / 16;
+    g.ybx = (W + 7) / 8; g.yby = (H + 7) / 8;
+    g.yw = 16 * g.mcux; g.yh = 16 * g.mcuy;               // luma planes cover every MCU (dummy blocks are never written)
+    g.cw = 8 * g.mcux; g.ch = 8 * g.mcuy;
+    g.n_mcu = (long long)g.mcux * g.mcuy;
+    g.nblk = 6 * g.n_mcu;
+    g.stream_words = (g.nblk * kJfifBlockWords + 2 + 15) / 16 * 16;
+    g.n_chunks = g.stream_words * 4 / kJfChunk;
+    g.plane_bytes = ((long long)g.yh * g.yw + 2LL * g.ch * g.cw + 255) / 256 * 256;
+    return true;
+}
+
+unsigned long long jfif_carve(void *base, const JfifGeom &g, JfifBufs &w)
+{
+    unsigned long long off = 0;
+    auto take = [&](unsigned long long n) { void *p = base ? (char *)base + off : nullptr; off += (n + 255) / 256 * 256; return p; };
+    const unsigned long long segs = (unsigned long long)g.nq * g.B;
+    w.par = (JfifParams *)take(sizeof(JfifParams) * g.nq);
+    w.dct = (int *)take((unsigned long long)g.B * g.nblk * 64 * 4);
+    w.coef = (short *)take(segs * g.nblk * 64 * 2);
+    w.lens = (int *)take(segs * g.nblk * 4);
+    w.boff = (long long *)take(segs * g.nblk * 8);
+    w.btot = (long long *)take(segs * 8);
+    w.stream = (unsigned *)take(segs * g.stream_words * 4);
+    w.ffcnt = (int *)take(segs * g.n_chunks * 4);
+    w.ffpre = (long long *)take(segs * g.n_chunks * 8);
+    w.fftot = (long long *)take(segs * 8);
+    w.total = (long long *)take(8);
+    w.planes = (unsigned char *)take(segs * g.plane_bytes);
+    return off;
+}
+
+void jfif_quant_tables(int q, int luma[64], int chroma[64])
+{
+    q = q < 1 ? 1 : q > 100 ? 100 : q;
+    const int scale = q < 50 ? 5000 / q : 200 - 2 * q;
+    for (int i = 0; i < 64; i++) {
+        luma[i] = std::min(255, std::max(1, (kLumaBase[i] * scale + 50) / 100));
+        chroma[i] = std::min(255, std::max(1, (kChromaBase[i] * scale + 50) / 100));
+    }
+}
+
+static const unsigned char kZzHost[64] = { 0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14,
+                                           21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46,
+                                           53, 60, 61, 54, 47, 55, 62, 63 };
+
+void jfif_params_host(int q, int H, int W, JfifParams &p)
+{
+    int t[2][64];
+    jfif_quant_tables(q, t[0], t[1]);
+    for (int c = 0; c < 2; c++)
+        for (int i = 0; i < 64; i++) p.qt[c][i] = t[c][kZzHost[i]];
+    unsigned char *o = p.hdr;
+    int n = 0;
+    auto put = [&](std::initializer_list<int> v) { for (int x : v) o[n++] = (unsigned char)x; };
+    auto seg = [&](int marker, int len) { put({ 0xFF, marker, (len + 2) >> 8, (len + 2) & 255 }); };
+    put({ 0xFF, 0xD8 });
+    seg(0xE0, 14);                                                        // JFIF 1.01, no units, 1:1 density, no thumbnail
+    put({ 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0 });
+    for (int c = 0; c < 2; c++) {
+        seg(0xDB, 65);
+        put({ c });
+        for (int i = 0; i < 64; i++) o[n++] = (unsigned char)p.qt[c][i];
+    }
+    seg(0xC0, 15);
+    put({ 8, H >> 8, H & 255, W >> 8, W & 255, 3, 1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1 });
+    const struct { int id; const unsigned char *t; int len; } dht[4] = {
+        { 0x00, kDht_dc_luma, (int)sizeof kDht_dc_luma }, { 0x10, kDht_ac_luma, (int)sizeof kDht_ac_luma },
+        { 0x01, kDht_dc_chroma, (int)sizeof kDht_dc_chroma }, { 0x11, kDht_ac_chroma, (int)sizeof kDht_ac_chroma } };
+    for (const auto &d : dht) {
+        seg(0xC4, 1 + d.len);
+        put({ d.id });
+        for (int i = 0; i < d.len; i++) o[n++] = d.t[i];
+    }
+    seg(0xDA, 10);
+    put({ 3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0 });
+    p.hdr_len = n;
+}
+
+static unsigned jf_blocks(long long n) { return (unsigned)((n + kJfThreads - 1) / kJfThreads); }
+
+hipError_t launch_jfif_encode(hipStream_t st, const JfifGeom &g, const JfifBufs &w, const JfifParams *par_host, const unsigned char *rgb,
+                              unsigned char *out, unsigned long long cap, long long *lengths, long long *offsets)
+{
+    const long long segs = (long long)g.nq * g.B, nb = segs * g.nblk, nc = segs * g.n_chunks;
+    hipError_t e = hipMemcpyAsync(w.par, par_host, sizeof(JfifParams) * g.nq, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_jfif_fdct, dim3(jf_blocks((long long)g.B * g.nblk)), dim3(kJfThreads), 0, st, g, rgb, w.dct);
+    hipLaunchKernelGGL(k_jfif_quant, dim3(jf_blocks(nb)), dim3(kJfThreads), 0, st, g, w.par, w.dct, w.coef, w.lens);
+    hipLaunchKernelGGL(k_jfif_scan, dim3((unsigned)segs), dim3(kJfScanThreads), 0, st, w.lens, g.nblk, w.boff, w.btot);
+    hipLaunchKernelGGL(k_jfif_zero, dim3((unsigned)((g.stream_words + kJfThreads - 1) / kJfThreads), (unsigned)segs), dim3(kJfThreads), 0, st, g,
+                       w.btot, w.stream);
+    hipLaunchKernelGGL(k_jfif_emit, dim3(jf_blocks(nb)), dim3(kJfThreads), 0, st, g, w.coef, w.boff, w.btot, w.stream);
+    hipLaunchKernelGGL(k_jfif_ffcount, dim3(jf_blocks(nc)), dim3(kJfThreads), 0, st, g, w.btot, w.stream, w.ffcnt);
+    hipLaunchKernelGGL(k_jfif_scan, dim3((unsigned)segs), dim3(kJfScanThreads), 0, st, w.ffcnt, g.n_chunks, w.ffpre, w.fftot);
+    hipLaunchKernelGGL(k_jfif_layout, dim3(1), dim3(1), 0, st, g, w.par, w.btot, w.fftot, lengths, offsets, w.total);
+    if (out)
+        hipLaunchKernelGGL(k_jfif_scatter, dim3(jf_blocks(nc)), dim3(kJfThreads), 0, st, g, w.par, w.btot, w.stream, w.ffpre, lengths, offsets,
+                           out, cap);
+    return hipGetLastError();
+}
+
+hipError_t launch_jfif_recon(hipStream_t st, const JfifGeom &g, const JfifBufs &w, unsigned char *rgb_out)
+{
+    const long long segs = (long long)g.nq * g.B;
+    hipLaunchKernelGGL(k_jfif_idct, dim3(jf_blocks(segs * g.nblk)), dim3(kJfThreads), 0, st, g, w.par, w.coef, w.planes);
+    hipLaunchKernelGGL(k_jfif_rgb, dim3(jf_blocks(segs * g.H * g.W)), dim3(kJfThreads), 0, st, g, w.planes, rgb_out);
+    return hipGetLastError();
+}
+
+}  // namespace aej

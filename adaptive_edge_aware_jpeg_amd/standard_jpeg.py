@@ -1,0 +1,147 @@
+"""Standard (baseline) JPEG on the GPU: the files Pillow writes with ``Image.save(buf, "JPEG", quality=q)`` and the pixels its decoder
+returns for them -- the standard-JPEG side of the reference's comparison (test/analysis/metrics_comparison.py: YCbCr, 4:2:0, 8 x 8
+blocks, quality 10/25/50/75/90).
+
+The files are byte-identical to Pillow's with libjpeg-turbo (JFIF 1.01, Annex K quantisation and Huffman tables, islow DCT, no restart
+markers) and the decoded pixels equal ``np.asarray(Image.open(file).convert("RGB"))``.  Colour, down-sampling and DCT run once per image
+and every requested quality reuses them (csrc/jfif.hip, ``aej_jfif_*`` in include/aej.h).  Images are uint8, or float32 in [0, 1]
+taken as ``rint(x * 255)`` -- the exact inverse of ``Image.load``'s ``uint8 / 255``.
+"""
+import ctypes
+from typing import List, Sequence, Tuple
+
+import numpy as np
+
+from ._lib import get_context
+
+HEADER_CAPACITY = 1024       # SOI .. SOS are 623 bytes
+_ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+                    35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63])
+
+
+def _check_quality(q):
+    if isinstance(q, bool) or int(q) != q or not 1 <= int(q) <= 100:
+        raise ValueError(f"quality {q!r}: an integer in 1..100 required")
+    return int(q)
+
+
+def headers(quality: int, H: int, W: int) -> bytes:
+    """The markers SOI .. SOS of the file of one (quality, H, W) (aej_jfif_headers_host)."""
+    from ._lib import load_library
+    lib = load_library()
+    buf = ctypes.create_string_buffer(HEADER_CAPACITY)
+    n = lib.aej_jfif_headers_host(int(quality), int(H), int(W), ctypes.cast(buf, ctypes.c_void_p), HEADER_CAPACITY)
+    if n < 0:
+        raise ValueError(f"quality {quality}, {H}x{W}: quality must be in 1..100 and H, W in 1..65535")
+    return buf.raw[:n]
+
+
+def quant_tables(quality: int) -> Tuple[List[int], List[int]]:
+    """(luma, chroma) quantisation tables of a quality in natural (row-major) order -- ``Image.open(file).quantization[0 / 1]``."""
+    h = headers(_check_quality(quality), 8, 8)
+    out, i = [], 2
+    while len(out) < 2:                         # walk the marker segments after SOI (table bytes may look like markers)
+        n = int.from_bytes(h[i + 2:i + 4], "big")
+        if h[i + 1] == 0xDB:
+            nat = np.empty(64, np.int64)
+            nat[_ZIGZAG] = np.frombuffer(h[i + 5:i + 69], np.uint8)
+            out.append([int(v) for v in nat])
+        i += 2 + n
+    return out[0], out[1]
+
+
+def _to_u8(ctx, x):
+    """[B, H, W, 3] or [H, W, 3] uint8 / float32 (numpy or torch) -> device uint8 [B, H, W, 3]"""
+    t = ctx.torch
+    is_torch = isinstance(x, t.Tensor)
+    if not is_torch:
+        x = np.asarray(x)
+    if x.ndim == 3:
+        x = x[None]
+    if x.ndim != 4 or x.shape[3] != 3:
+        raise ValueError(f"images must be [B, H, W, 3] (or one [H, W, 3]), got {tuple(x.shape)}")
+    if x.shape[0] < 1:
+        raise ValueError("at least one image required")
+    dt = str(x.dtype)
+    if dt in ("uint8", "torch.uint8"):
+        return ctx.to_device(x, t.uint8)
+    if dt not in ("float32", "torch.float32"):
+        raise TypeError(f"images must be uint8 or float32 in [0, 1], got {dt}")
+    xf = ctx.to_device(x, t.float32)
+    lo, hi = t.aminmax(xf)
+    if not (float(lo) >= 0.0 and float(hi) <= 1.0):
+        raise ValueError("float32 images must lie in [0, 1]")
+    return t.round(xf * t.full((), 255.0, dtype=t.float32, device=ctx.device)).to(t.uint8)
+
+
+class _Encoded:
+    """One aej_jfif_encode_batch: the workspace (it holds the coefficients the reconstruction reads), lengths [Q, B], optional bytes."""
+
+    def __init__(self, ctx, x_u8, qualities, want_bytes):
+        t, lib = ctx.torch, ctx.lib
+        self.ctx, self.qualities = ctx, [_check_quality(q) for q in qualities]
+        if not self.qualities:
+            raise ValueError("at least one quality required")
+        B, H, W = (int(v) for v in x_u8.shape[:3])
+        self.B, self.H, self.W, Q = B, H, W, len(self.qualities)
+        if not (1 <= H <= 65535 and 1 <= W <= 65535):
+            raise ValueError(f"{H}x{W}: baseline JPEG needs 1 <= H, W <= 65535")
+        nbytes = int(lib.aej_jfif_workspace_bytes(B, H, W, Q))
+        self.ws = ctx.empty((nbytes,), t.uint8)
+        q = np.array(self.qualities, np.int32)
+        offsets, lengths = ctx.empty((Q * B,), t.int64), ctx.empty((Q * B,), t.int64)
+        total = ctypes.c_uint64()
+        out, cap = None, 0
+        if want_bytes:
+            cap = Q * B * (HEADER_CAPACITY + H * W * 3 // 4)          # most files are far smaller; a miss costs one more call
+            out = ctx.empty((cap,), t.uint8)
+        args = lambda o, c: (ctx.handle, x_u8.data_ptr(), B, H, W, Q, q.ctypes.data, o.data_ptr() if o is not None else None,  # noqa: E731
+                             ctypes.c_uint64(c), offsets.data_ptr(), lengths.data_ptr(), ctypes.addressof(total), self.ws.data_ptr(),
+                             ctypes.c_uint64(nbytes))
+        rc = lib.aej_jfif_encode_batch(*args(out, cap))
+        if rc == -4 and out is not None and total.value > cap:        # AEJ_ERR_CAPACITY: run again with the exact size
+            cap = int(total.value)
+            out = ctx.empty((cap,), t.uint8)
+            rc = lib.aej_jfif_encode_batch(*args(out, cap))
+        ctx.check(rc)
+        self.lengths = lengths.cpu().numpy().reshape(Q, B)
+        self.offsets = offsets.cpu().numpy().reshape(Q, B)
+        self.out = out
+
+    def files(self) -> List[List[bytes]]:
+        """[quality][image] bytes"""
+        blob = self.out[:int(self.lengths.sum())].cpu().numpy().tobytes()
+        return [[blob[o:o + n] for o, n in zip(orow, nrow)] for orow, nrow in zip(self.offsets.tolist(), self.lengths.tolist())]
+
+    def decoded(self):
+        """device uint8 [Q, B, H, W, 3]: what Pillow's decoder returns for every file"""
+        ctx = self.ctx
+        rgb = ctx.empty((len(self.qualities), self.B, self.H, self.W, 3), ctx.torch.uint8)
+        ctx.check(ctx.lib.aej_jfif_recon_batch(ctx.handle, self.B, self.H, self.W, len(self.qualities), rgb.data_ptr(), self.ws.data_ptr(),
+                                               ctypes.c_uint64(self.ws.numel())))
+        return rgb
+
+
+def encode_decode(ctx, x_u8, qualities, want_bytes=False) -> _Encoded:
+    """The sweep's entry: one encode of device uint8 [B, H, W, 3] for every quality (on ctx's stream)."""
+    return _Encoded(ctx, x_u8, qualities, want_bytes)
+
+
+def workspace_bytes(ctx, B, H, W, n_q) -> int:
+    return int(ctx.lib.aej_jfif_workspace_bytes(B, H, W, n_q))
+
+
+def standard_jpeg_many(x, quality: int, device: int = 0) -> List[bytes]:
+    """Every image's file, equal to ``PIL.Image.fromarray(u8).save(buf, "JPEG", quality=quality)``.
+    x: uint8 or float32 in [0, 1], [B, H, W, 3] or [H, W, 3], numpy or torch."""
+    q = _check_quality(quality)
+    ctx = get_context(device)
+    return _Encoded(ctx, _to_u8(ctx, x), [q], True).files()[0]
+
+
+def standard_jpeg_batch(x, qualities: Sequence[int], device: int = 0):
+    """-> (sizes int64 [B, Q]: len() of every file, decoded uint8 [Q, B, H, W, 3] on the device: Pillow's decode of every file).
+    Colour, down-sampling and DCT run once per image for all the qualities."""
+    ctx = get_context(device)
+    enc = _Encoded(ctx, _to_u8(ctx, x), list(qualities), False)
+    return np.ascontiguousarray(enc.lengths.T.astype(np.int64)), enc.decoded()

@@ -18,6 +18,10 @@ copy per quality set and overlapped with the GPU work of the next sets.  ``"gpu"
 (``Jpeg.deflate_batch``) without copying them back: about 10 % larger than zlib-9, so NOT the reference's compression ratio, and -- the GPU
 deflate counts one Huffman code per layer over a whole call -- dependent on which images share a sub-batch (``SweepResult.sub_batches``).
 ``None`` skips sizes.
+
+With ``standard_qualities=`` (e.g. ``(10, 25, 50, 75, 90)``, the qualities of metrics_comparison.py) the same images also go through
+standard JPEG (standard_jpeg.py: Pillow's files, byte for byte, and Pillow's decode of them), scored with the same metrics against the
+same originals: ``SweepResult.standard`` and ``SweepResult.to_csv_standard``.
 """
 import csv
 import ctypes
@@ -34,12 +38,15 @@ from . import tables
 from ._lib import AejError, get_context
 from .evaluation_metrics import MS_SSIM, PSNR, SSIM
 from . import lpips as _lpips
+from . import standard_jpeg as _std
 from .jpeg import Jpeg, usable_cpus
 from .settings import JpegCompressionSettings
 
 CSV_COLUMNS = ("image_name", "color_space", "min_quality", "max_quality", "min_block_size", "max_block_size", "psnr", "ssim", "ms_ssim",
                "compression_ratio")      # metrics_computation.py:185-197 without 'lpips' (its weights are a download)
 CSV_COLUMNS_LPIPS = CSV_COLUMNS[:9] + ("lpips",) + CSV_COLUMNS[9:]      # the reference's full header: sweep(..., lpips=weights)
+STANDARD_COLUMNS = ("image_name", "quality", "psnr", "ssim", "ms_ssim", "compression_ratio")      # keys of metrics_comparison.py:26-32
+STANDARD_COLUMNS_LPIPS = STANDARD_COLUMNS[:5] + ("lpips",) + STANDARD_COLUMNS[5:]
 DEFAULT_MEMORY_FRACTION = 0.5            # max_bytes=None: this share of the device memory free when the sweep starts
 
 
@@ -82,6 +89,20 @@ def qmats_blob(color_space, quality_range, block_size_range) -> np.ndarray:
                            for qm in settings.quantization_matrices for s in sizes]).astype(np.int32)
 
 
+class StandardResult:
+    """Standard JPEG of every image at every quality: [image, quality] arrays; ``bytes`` are len() of Pillow's files."""
+
+    def __init__(self, qualities, n, lpips=False):
+        self.qualities: List[int] = list(qualities)
+        q = len(self.qualities)
+        self.psnr = np.full((n, q), np.nan)
+        self.ssim = np.full((n, q), np.nan)
+        self.ms_ssim = np.full((n, q), np.nan)
+        self.lpips = np.full((n, q), np.nan) if lpips else None
+        self.bytes = np.zeros((n, q), np.int64)
+        self.compression_ratio = np.full((n, q), np.nan)
+
+
 class SweepResult:
     """One row per image, one column per cell; ``cells`` in the reference's ``product`` order."""
 
@@ -99,6 +120,7 @@ class SweepResult:
         self.sizes = sizes
         self.which = which
         self.sub_batches = {}          # (color_space, block_size_range) -> [[image indices of one encode call], ...]
+        self.standard: Optional[StandardResult] = None      # sweep(..., standard_qualities=...)
 
     def columns(self):
         """CSV_COLUMNS_LPIPS when the sweep computed LPIPS, else CSV_COLUMNS."""
@@ -127,6 +149,24 @@ class SweepResult:
             w.writerow(cols)
             for r in self.rows():
                 w.writerow([r[k] if k in CSV_COLUMNS[:6] else f"{r[k]:.4f}" for k in cols])
+
+
+    def to_csv_standard(self, path):
+        """The standard-JPEG rows (sweep(..., standard_qualities=...)): image by image, qualities in order; metrics and ratio as ``:.4f``,
+        ``lpips`` only when the sweep computed it."""
+        st = self.standard
+        if st is None:
+            raise ValueError("the sweep ran without standard_qualities")
+        cols = STANDARD_COLUMNS_LPIPS if st.lpips is not None else STANDARD_COLUMNS
+        with open(path, "w", newline="") as f:
+            w = csv.writer(f, lineterminator="\n")
+            w.writerow(cols)
+            for i, name in enumerate(self.names):
+                for j, q in enumerate(st.qualities):
+                    v = {"psnr": st.psnr[i, j], "ssim": st.ssim[i, j], "ms_ssim": st.ms_ssim[i, j], "compression_ratio": st.compression_ratio[i, j]}
+                    if st.lpips is not None:
+                        v["lpips"] = st.lpips[i, j]
+                    w.writerow([name, q] + [f"{float(v[k]):.4f}" for k in cols[2:]])
 
 
 def _shape_groups(images):
@@ -221,7 +261,8 @@ def _gpu_stream_sizes(ctx, coeffs, counts, B, H, W):
 def sweep(images, color_spaces: Sequence[str] = ("YCbCr",), quality_ranges: Sequence[Tuple[int, int]] = ((40, 80),),
           block_size_ranges: Sequence[Tuple[int, int]] = ((4, 64),), metrics: int = PSNR | SSIM | MS_SSIM, sizes: Optional[str] = "zlib",
           extension: Optional[str] = None, names: Optional[Sequence[str]] = None, device: int = 0, max_bytes: Optional[int] = None,
-          workers: Optional[int] = None, lpips: Optional[_lpips.LpipsWeights] = None) -> SweepResult:
+          workers: Optional[int] = None, lpips: Optional[_lpips.LpipsWeights] = None,
+          standard_qualities: Optional[Sequence[int]] = None) -> SweepResult:
     """Every (colour space, quality range, block range) cell for every image: metrics and container sizes equal to
     ``EvaluationMetrics.batch(x, decompress_batch(compress_batch(x)))`` and ``len(compress_many(x, extension=...))`` of that cell.
 
@@ -230,7 +271,9 @@ def sweep(images, color_spaces: Sequence[str] = ("YCbCr",), quality_ranges: Sequ
     max_bytes: device bytes the sweep's buffers may use at their peak (default DEFAULT_MEMORY_FRACTION of the free memory); images are
     sub-batched and quality ranges grouped to stay below it -- metrics and "zlib" sizes do not depend on it.  workers: host zlib threads
     (default: the cores this process may use).  lpips: LpipsWeights -> also ``SweepResult.lpips`` (equal to
-    ``EvaluationMetrics.lpips_batch`` of every cell) and the ``lpips`` CSV column; images must then be at least 31x31.  The settings are bound on the device's context of the current stream, as Jpeg does: other
+    ``EvaluationMetrics.lpips_batch`` of every cell) and the ``lpips`` CSV column; images must then be at least 31x31.
+    standard_qualities: JPEG qualities (1..100) -> ``SweepResult.standard``: the same metrics (and LPIPS) of Pillow's standard-JPEG decode
+    (``u8 / 255``) against the same originals, and ``compression_ratio = H * W * 3 / len(file)`` (module doc).  The settings are bound on the device's context of the current stream, as Jpeg does: other
     Jpeg objects bind theirs again on their next call."""
     if sizes not in ("zlib", "gpu", None):
         raise ValueError("sizes must be 'zlib', 'gpu' or None")
@@ -259,8 +302,17 @@ def sweep(images, color_spaces: Sequence[str] = ("YCbCr",), quality_ranges: Sequ
     if lpips is not None:
         for i, (h, w) in enumerate(shapes):
             _lpips.check_size(h, w, f"image {i}")
+    if standard_qualities is not None:
+        standard_qualities = [_std._check_quality(q) for q in standard_qualities]
+        if not standard_qualities:
+            raise ValueError("standard_qualities needs at least one quality")
+        for i, (h, w) in enumerate(shapes):
+            if h > 65535 or w > 65535:
+                raise ValueError(f"image {i} ({h}x{w}): baseline JPEG holds at most 65535 x 65535")
     cells = list(itertools.product(color_spaces, quality_ranges, block_size_ranges))
     res = SweepResult(cells, names, shapes, metrics, sizes, lpips=lpips is not None)
+    if standard_qualities is not None:
+        res.standard = StandardResult(standard_qualities, n_img, lpips=lpips is not None)
     col = {c: j for j, c in enumerate(cells)}
 
     ctx = get_context(device)
@@ -298,6 +350,8 @@ def sweep(images, color_spaces: Sequence[str] = ("YCbCr",), quality_ranges: Sequ
                             fa = feats[b0, len(sub)] = _lpips.features(ctx, lpips, xf.contiguous())
                     _sweep_sub(ctx, codec, res, col, blobs, cs, br, quality_ranges, plan.group, sub, x, xf, metrics, sizes, extension,
                                pool, pending, lpips, fa)
+            if standard_qualities is not None:
+                _sweep_standard(ctx, res.standard, idx, x_all, is_u8, ten_f32_255, metrics, lpips, max_bytes)
         while pending:
             _collect(res, pending.pop(0))
     finally:
@@ -306,7 +360,79 @@ def sweep(images, color_spaces: Sequence[str] = ("YCbCr",), quality_ranges: Sequ
     if sizes is not None:
         px = np.array([h * w * 3 for h, w in shapes], np.float64)
         res.compression_ratio = px[:, None] / res.bytes
+    if res.standard is not None:
+        px = np.array([h * w * 3 for h, w in shapes], np.float64)
+        res.standard.compression_ratio = px[:, None] / res.standard.bytes
     return res
+
+
+def _standard_plan(ctx, n_img, H, W, n_q, which, max_bytes, in_bytes, lpips):
+    """(images per call, qualities per call) of the standard-JPEG pass under the byte budget"""
+    lib = ctx.lib
+
+    def cost(b, g):
+        c = in_bytes * b * H * W * 3 + 4 * b * H * W * 3 + b * H * W * 3        # input, its float32 copy, its uint8 form
+        c += _std.workspace_bytes(ctx, b, H, W, g) + g * b * H * W * 3 + 4 * b * H * W * 3     # encode, decoded sets, one float32 set
+        c += max(int(lib.aej_metrics_workspace_bytes(b, H, W)) if which else 0, int(lib.aej_lpips_workspace_bytes(b, H, W)) if lpips else 0)
+        if lpips:
+            c += int(lib.aej_lpips_features_bytes(b, H, W))
+        return c
+
+    batch, lo, hi = 1, 1, n_img
+    while lo <= hi:
+        mid = (lo + hi) // 2
+        if cost(mid, 1) <= max_bytes:
+            batch, lo = mid, mid + 1
+        else:
+            hi = mid - 1
+    group = next((g for g in range(n_q, 0, -1) if cost(batch, g) <= max_bytes), 1)
+    return batch, group
+
+
+def _sweep_standard(ctx, st, idx, x_all, is_u8, ten_f32_255, metrics, lpips, max_bytes):
+    """Standard JPEG of one shape group: per image sub-batch one encode for a group of qualities, then per quality Pillow's decode scored
+    against the originals (as the adaptive cells are)."""
+    t = ctx.torch
+    lib = ctx.lib
+    H, W = int(x_all.shape[1]), int(x_all.shape[2])
+    batch, group = _standard_plan(ctx, len(idx), H, W, len(st.qualities), metrics, max_bytes, 1 if is_u8 else 4, lpips is not None)
+    for b0 in range(0, len(idx), batch):
+        sub = idx[b0:b0 + batch]
+        x = x_all[b0:b0 + len(sub)]
+        B = len(sub)
+        xf = (x.float() / ten_f32_255) if is_u8 else x
+        x_u8 = x if is_u8 else _std._to_u8(ctx, x)
+        fa = _lpips.features(ctx, lpips, xf.contiguous()) if lpips is not None else None
+        for g0 in range(0, len(st.qualities), group):
+            qs = st.qualities[g0:g0 + group]
+            enc = _std.encode_decode(ctx, x_u8, qs)
+            dec = enc.decoded()
+            scores, lp = [], []
+            for s in range(len(qs)):
+                rgb = dec[s].float() / ten_f32_255
+                if metrics:
+                    ws_bytes = int(lib.aej_metrics_workspace_bytes(B, H, W))
+                    ws = ctx.workspace(ws_bytes)
+                    m = ctx.empty((B, 3), t.float64)
+                    ctx.check(lib.aej_metrics_batch(ctx.handle, xf.data_ptr(), rgb.data_ptr(), B, H, W, metrics, m.data_ptr(), ws.data_ptr(),
+                                                    ctypes.c_uint64(ws_bytes)))
+                    scores.append(m)
+                if lpips is not None:
+                    lp.append(_lpips.score(ctx, lpips, rgb, feats_a=fa))
+            for s in range(len(qs)):
+                j = g0 + s
+                for bi, i in enumerate(sub):
+                    st.bytes[i, j] = int(enc.lengths[s, bi])
+            if scores:
+                vals = t.stack(scores).cpu().numpy()
+                for s in range(len(qs)):
+                    for bi, i in enumerate(sub):
+                        st.psnr[i, g0 + s], st.ssim[i, g0 + s], st.ms_ssim[i, g0 + s] = vals[s, bi]
+            if lp:
+                vals = t.stack(lp).cpu().numpy()
+                for s in range(len(qs)):
+                    for bi, i in enumerate(sub):
+                        st.lpips[i, g0 + s] = vals[s, bi]
 
 
 def _sweep_sub(ctx, codec, res, col, blobs, cs, br, quality_ranges, group, sub, x, xf, metrics, sizes, extension, pool, pending, lpips=None,

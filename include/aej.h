@@ -363,6 +363,26 @@ AEJ_API uint64_t aej_decode_headers_workspace_bytes(aej_ctx *ctx, int batch, int
 AEJ_API int aej_decode_headers(aej_ctx *ctx, const uint8_t *states, const int64_t *layers, const int64_t *inflated_bytes, int batch, int H, int W,
                                int32_t *leaves, int64_t *counts, int32_t *status, void *workspace, uint64_t workspace_bytes);
 
+/* ---- baseline JPEG (the standard-JPEG side of a rate-distortion study) --------------------------------------------------------------
+ * Byte-identical to PIL.Image.fromarray(x).save(buf, "JPEG", quality=q) with libjpeg-turbo: JFIF 1.01 (no units, 1:1), 4:2:0, baseline,
+ * Annex K quantisation (Pillow's quality scaling, clamped to 1..255) and Huffman tables, islow DCT, no restart markers.
+ * aej_jfif_headers_host: the markers SOI .. SOS of one (quality, H, W) file into out_host; returns their length (623), AEJ_ERR_ARG for a
+ *   quality outside 1..100 or H, W outside 1..65535, AEJ_ERR_CAPACITY when capacity is smaller.
+ * aej_jfif_encode_batch: rgb is device uint8 [batch][H][W][3]; colour, down-sampling and DCT run once per image, then every one of the
+ *   n_q qualities.  File (j, b) -- quality qualities_host[j], image b -- is written at out + offsets[j * batch + b] with length
+ *   lengths[j * batch + b] (device int64 [n_q * batch], n_q * batch <= 65535, files packed in that order); *total_host gets their sum.  out may be NULL (sizes
+ *   only); if the files do not fit out_capacity nothing is written to out and AEJ_ERR_CAPACITY is returned with *total_host set.  The
+ *   call waits for that one word.  Workspace: aej_jfif_workspace_bytes(batch, H, W, n_q) bytes, 256-byte aligned.
+ * aej_jfif_recon_batch: the pixels libjpeg-turbo's decoder (islow IDCT, h2v2 fancy up-sampling -- plain replication when the chroma is at
+ *   most 2 samples wide) returns for those files, from the quantised coefficients the preceding aej_jfif_encode_batch of the same
+ *   (batch, H, W, n_q) left in `workspace`: rgb_out is device uint8 [n_q][batch][H][W][3].  Only enqueues work. */
+AEJ_API uint64_t aej_jfif_workspace_bytes(int batch, int H, int W, int n_q);
+AEJ_API int aej_jfif_headers_host(int quality, int H, int W, uint8_t *out_host, int capacity);
+AEJ_API int aej_jfif_encode_batch(aej_ctx *ctx, const uint8_t *rgb, int batch, int H, int W, int n_q, const int32_t *qualities_host, uint8_t *out,
+                                  uint64_t out_capacity, int64_t *offsets, int64_t *lengths, uint64_t *total_host, void *workspace,
+                                  uint64_t workspace_bytes);
+AEJ_API int aej_jfif_recon_batch(aej_ctx *ctx, int batch, int H, int W, int n_q, uint8_t *rgb_out, void *workspace, uint64_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif
