@@ -70,11 +70,9 @@ constexpr int kChunkInts = 4 + kMaxSizes;   // per-chunk record: nsym, nleaf, nc
 constexpr int kMaxPlanes = 3072;            // planes (3 x images) one DCT launch can address
 
 // One unit of DCT work (a leaf), appended by the quadtree emit kernel.
-// accumulator slots (doubles) per image pair of the evaluation metrics (metrics.hip): 0 = sum of squared differences;
-// kMetricSlotGrey + {0, 1} = ssim / cs sums of the grey SSIM map; kMetricSlotScales + (scale * 3 + channel) * 2 + {0, 1} likewise per scale
-constexpr int kMetricSlots = 40;
-constexpr int kMetricSlotGrey = 2;
-constexpr int kMetricSlotScales = 4;
+// evaluation metrics (metrics.hip): an SSIM map's sums are closed per band of this many output rows (bands start at absolute multiples of it:
+// the strip heights 32 / 64 / 128 are multiples), so an image's partial sums do not depend on the strip height or on the batch
+constexpr int kMetricBand = 32;
 
 // One unit of DCT work (a leaf) in a per-size, per-plane list segment: 8 bytes.  The plane is NOT stored: a reader finds an item's
 // segment from the per-plane prefix counts anyway, and that IS the plane (round 4: 16-byte entries carried it a second time; on natural

@@ -155,15 +155,27 @@ void launch_requant_check(hipStream_t st, const Geom &g, const QtGeom &q, const 
 int launch_requant(hipStream_t st, const Geom &g, const QtGeom &q, const float *dct, const int *leaves, const long long *counts, int n_sets,
                    const int *qmats, const int *const *zz, int *out, long long set_stride, int *bad, int blocks_per_plane);
 
-// metrics.hip
-void launch_metric_prep(hipStream_t st, const float *a, const float *b, int B, long long npx, double *acc, unsigned char *ga, unsigned char *gb);
+// metrics.hip.  Every partial sum is written once (no atomics) to [B][stride] doubles and k_metric_final adds an image's in a fixed order, so
+// each image's scores are independent of the batch around it and of scheduling.  Per image: [0, psnr_n) the squared differences of each
+// k_metric_prep block; [grey_off, + grey_n) the grey SSIM map's ssim sums; [lvl_off[l], + 3 lvl_n[l]) MS-SSIM scale l's (cs for scales 0..3,
+// ssim for 4), channel-major.  An SSIM map contributes one sum per (channel, kMetricBand-row band, 128-column strip): ssim_partials().
+struct MetricParts {
+    long long stride;
+    int psnr_n;
+    long long grey_off, grey_n;         // grey_n = 0: not computed
+    long long lvl_off[5], lvl_n[5];     // lvl_n[l] per channel
+};
+int metric_prep_blocks(long long npx);
+long long ssim_partials(int h, int w);     // per channel; 0 below 11 x 11
+void launch_metric_prep(hipStream_t st, const float *a, const float *b, int B, long long npx, double *part, long long stride, unsigned char *ga,
+                        unsigned char *gb);
 void launch_metric_pool_grey(hipStream_t st, const unsigned char *ga, const unsigned char *gb, int B, int H, int W, int f, int hp, int wp, float *xa,
                              float *xb);
-void launch_ssim_level(hipStream_t st, bool interleaved, const float *xa, const float *xb, int B, int C, int h, int w, const float *g11, double *acc,
-                       int slot, bool want_ss, float *pool_a = nullptr, float *pool_b = nullptr);   // pool_*: scale 0 of even-sized images also writes scale 1
+void launch_ssim_level(hipStream_t st, bool interleaved, const float *xa, const float *xb, int B, int C, int h, int w, const float *g11, double *part,
+                       long long stride, long long off, bool want_ss, float *pool_a = nullptr, float *pool_b = nullptr);   // pool_*: scale 0 of even-sized images also writes scale 1
 void launch_pool2_rgb(hipStream_t st, const float *ia, const float *ib, int B, int h, int w, int p, int h2, int w2, float *oa, float *ob);
 void launch_pool2(hipStream_t st, bool interleaved, const float *in, int B, int C, int h, int w, int p, int h2, int w2, float *out);
-void launch_metric_final(hipStream_t st, const double *acc, int B, long long npx, long long n_ssim, const long long *n_level, double *out);
+void launch_metric_final(hipStream_t st, const double *part, const MetricParts &P, int B, long long npx, long long n_ssim, const long long *n_level, double *out);
 
 
 // lpips.hip: LPIPS(net='alex') (aej_lpips_*, include/aej.h)

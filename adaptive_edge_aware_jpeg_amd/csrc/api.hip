@@ -1678,7 +1678,8 @@ extern "C" int aej_deflate_batch(aej_ctx *ctx, const int32_t *coeffs, const int6
 
 // ---- evaluation metrics (evaluation_metrics.py:50-89) ------------------------------------------------------------
 struct MetricsWs {
-    double *acc;
+    double *part;                // [B][parts.stride] partial sums (aej_launch.h)
+    MetricParts parts;
     unsigned char *ga, *gb;
     float *xa, *xb;
     float *pyr[2][4];            // MS-SSIM scales 1..4 of both images, planar [B][3][h][w]
@@ -1691,7 +1692,6 @@ static void carve_metrics(void *base, int B, int H, int W, MetricsWs &w)
 {
     unsigned long long off = 0;
     auto take = [&](unsigned long long n) { void *p = base ? (char *)base + off : nullptr; off += (unsigned long long)align_up((long long)n, 256); return p; };
-    w.acc = (double *)take((unsigned long long)B * kMetricSlots * sizeof(double));
     w.ga = (unsigned char *)take((unsigned long long)B * H * W);
     w.gb = (unsigned char *)take((unsigned long long)B * H * W);
     // piq.ssim: f = max(1, round(min(H, W) / 256)) -- Python round(): ties to even
@@ -1708,6 +1708,14 @@ static void carve_metrics(void *base, int B, int H, int W, MetricsWs &w)
         w.lw[l] = (w.lw[l - 1] + p) / 2;
         for (int i = 0; i < 2; i++) w.pyr[i][l - 1] = (float *)take((unsigned long long)B * 3 * w.lh[l] * w.lw[l] * 4);
     }
+    MetricParts &P = w.parts;
+    P.psnr_n = metric_prep_blocks((long long)H * W);
+    P.grey_off = P.psnr_n;
+    P.grey_n = ssim_partials(w.hp, w.wp);
+    long long n = P.grey_off + P.grey_n;
+    for (int l = 0; l < 5; l++) { P.lvl_off[l] = n; P.lvl_n[l] = ssim_partials(w.lh[l], w.lw[l]); n += 3 * P.lvl_n[l]; }
+    P.stride = n;
+    w.part = (double *)take((unsigned long long)B * n * sizeof(double));
     w.bytes = off;
 }
 
@@ -1742,12 +1750,12 @@ extern "C" int aej_metrics_batch(aej_ctx *ctx, const float *img_a, const float *
         for (int i = 0; i < 11; i++) { double c = (double)i - 5.0; e[i] = exp(-(c * c) / (2.0 * 1.5 * 1.5)); sum += e[i]; }
         for (int i = 0; i < 11; i++) g11[i] = (float)(e[i] / sum);
     }
-    AEJ_HIP_CHECK(hipMemsetAsync(w.acc, 0, (size_t)batch * kMetricSlots * sizeof(double), st));
-    launch_metric_prep(st, img_a, img_b, batch, (long long)H * W, w.acc, want_ssim ? w.ga : nullptr, want_ssim ? w.gb : nullptr);
+    // every partial k_metric_final reads is written below (no accumulation, no clearing)
+    launch_metric_prep(st, img_a, img_b, batch, (long long)H * W, w.part, w.parts.stride, want_ssim ? w.ga : nullptr, want_ssim ? w.gb : nullptr);
     long long n_ssim = 0, n_level[5] = { 0, 0, 0, 0, 0 };
     if (want_ssim) {
         launch_metric_pool_grey(st, w.ga, w.gb, batch, H, W, w.f, w.hp, w.wp, w.xa, w.xb);
-        launch_ssim_level(st, false, w.xa, w.xb, batch, 1, w.hp, w.wp, g11, w.acc, kMetricSlotGrey, true);
+        launch_ssim_level(st, false, w.xa, w.xb, batch, 1, w.hp, w.wp, g11, w.part, w.parts.stride, w.parts.grey_off, true);
         n_ssim = (long long)(w.hp - 10) * (w.wp - 10);
     }
     if (want_ms) {
@@ -1764,12 +1772,12 @@ extern "C" int aej_metrics_batch(aej_ctx *ctx, const float *img_a, const float *
                 }
             }
             const bool fused_pool = l == 0 && w.lp[1] == 0;
-            launch_ssim_level(st, l == 0, xa, xb, batch, 3, w.lh[l], w.lw[l], g11, w.acc, kMetricSlotScales + l * 6, l == 4, fused_pool ? w.pyr[0][0] : nullptr,
-                              fused_pool ? w.pyr[1][0] : nullptr);
+            launch_ssim_level(st, l == 0, xa, xb, batch, 3, w.lh[l], w.lw[l], g11, w.part, w.parts.stride, w.parts.lvl_off[l], l == 4,
+                              fused_pool ? w.pyr[0][0] : nullptr, fused_pool ? w.pyr[1][0] : nullptr);
             n_level[l] = (long long)(w.lh[l] - 10) * (w.lw[l] - 10);
         }
     }
-    launch_metric_final(st, w.acc, batch, (long long)H * W, n_ssim, n_level, out);
+    launch_metric_final(st, w.part, w.parts, batch, (long long)H * W, n_ssim, n_level, out);
     AEJ_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -4,8 +4,10 @@
 //                                                                    average-pooled by round(min(H, W) / 256), 11x11 Gaussian
 //   ms_ssim() = piq.multi_scale_ssim(x, y, data_range=1.0)           5 scales, 2x2 average pooling between them
 // piq 0.8.0 is not under /root/reference (requirements.txt:22); this file restates its published algorithm (piq/psnr.py,
-// piq/ssim.py, piq/ms_ssim.py, piq/functional/filters.py); tests/test_metrics.py compares it with a numpy restatement.  These are float32 reductions whose summation order torch does not define, so parity here is to a stated
-// tolerance, not bitwise.  The window is the normalised Gaussian exp(-(i^2 + j^2) / (2 sigma^2)) / sum, applied as two
+// piq/ssim.py, piq/ms_ssim.py, piq/functional/filters.py); tests/test_metrics.py and tests/test_gpu_metrics.py compare it with a float64 numpy restatement.  These are float32 reductions whose summation
+// order torch does not define, so parity here is to a stated tolerance, not bitwise.  The order HERE is fixed: every partial sum is written
+// once and k_metric_final adds them in index order, and an image's partials do not depend on the batch it is in (aej_launch.h, MetricParts),
+// so a score is bit-identical across calls, batch sizes and batch orders.  The window is the normalised Gaussian exp(-(i^2 + j^2) / (2 sigma^2)) / sum, applied as two
 // separable passes through LDS ('valid' convolution: no padding).
 #include "aej_common.h"
 #include "aej_launch.h"
@@ -39,8 +41,8 @@ __device__ __forceinline__ unsigned char grey_u8(float r, float g, float b)
 }
 
 // ---- pass over both images: squared error (psnr) and the two 8-bit grey planes (ssim) ----
-__global__ __launch_bounds__(256) void k_metric_prep(const float *__restrict__ a, const float *__restrict__ b, long long npx, double *__restrict__ acc,
-                                                     unsigned char *__restrict__ ga, unsigned char *__restrict__ gb)
+__global__ __launch_bounds__(256) void k_metric_prep(const float *__restrict__ a, const float *__restrict__ b, long long npx, double *__restrict__ part,
+                                                     long long part_stride, unsigned char *__restrict__ ga, unsigned char *__restrict__ gb)
 {
     __shared__ double s_red[4];
     const int img = blockIdx.y;
@@ -82,7 +84,7 @@ __global__ __launch_bounds__(256) void k_metric_prep(const float *__restrict__ a
         }
     }
     sum = block_sum(sum, s_red);
-    if (threadIdx.x == 0) atomicAdd(&acc[(long long)img * kMetricSlots + 0], sum);
+    if (threadIdx.x == 0) part[(long long)img * part_stride + blockIdx.x] = sum;
 }
 
 // ---- piq.ssim: x / data_range, then F.avg_pool2d(kernel_size = f) when f > 1 ----
@@ -114,8 +116,8 @@ struct SsimArgs {
     int want_ss;              // the luminance term too (the grey SSIM and the last MS-SSIM scale; the others use cs alone)
     float g[kSsimK];          // normalised 1-D Gaussian: g[i] * g[j] is piq's 2-D window
     float c1, c2;
-    double *acc;              // [B][kMetricSlots]
-    int slot;                 // first slot: channel c adds ss to slot + 2c, cs to slot + 2c + 1
+    double *part;             // [B][stride]: this map's sums from part + off, one per (channel, band, strip), channel-major (aej_launch.h)
+    long long stride, off;
     float *pool_a, *pool_b;   // INTERLEAVED with even h, w: the next scale (2 x 2 means, planar [B][3][h / 2][w / 2]) written on the way, or null
 };
 
@@ -137,8 +139,9 @@ constexpr int kSsimCols = 128;                         // output columns per wav
 constexpr int kSsimIn = kSsimCols + kSsimK - 1;        // input columns per wave: 138
 constexpr int kSsimRow = kSsimIn + 2;                  // LDS row stride in floats (even: 8-byte aligned rows)
 
+// three waves per SIMD (at most 168 VGPRs): left to itself the compiler gives the planar instance 170 since the per-band partials
 template <bool INTERLEAVED>
-__global__ __launch_bounds__(256) void k_ssim_strip(SsimArgs A)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k_ssim_strip(SsimArgs A)
 {
     __shared__ __attribute__((aligned(8))) float rows[4][4][kSsimRow];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -174,7 +177,11 @@ __global__ __launch_bounds__(256) void k_ssim_strip(SsimArgs A)
     };
     fetch(0);
     float h[kSsimK][4][2];
-    float ss_acc = 0.f, cs_acc = 0.f;
+    // the ssim (want_ss) or cs sum of this lane's windows, closed into a double partial at the end of every kMetricBand-row band: y0 is a
+    // multiple of the band, so the bands and what each lane adds into them are the same whatever the strip height
+    float acc = 0.f;
+    const int nby = (oh + kMetricBand - 1) / kMetricBand;
+    double *const part = A.part + (long long)img * A.stride + A.off + (long long)c * nby * nsx + sx_;
     const bool out_ok[2] = { x0 + 2 * lane < ow, x0 + 2 * lane + 1 < ow };
     // 2 x 2 means for the next scale: row pairs (y0 + r even, odd), column pairs = this lane's; the halo only where no other strip owns it
     const bool pool = INTERLEAVED && A.pool_a != nullptr;
@@ -243,9 +250,15 @@ __global__ __launch_bounds__(256) void k_ssim_strip(SsimArgs A)
                     const float mu_xx = v[0] * v[0], mu_yy = v[1] * v[1], mu_xy = v[0] * v[1];
                     const float s_sum = (v[2] - mu_xx) - mu_yy, s_xy = v[3] - mu_xy;
                     const float cs = fmaf(2.f, s_xy, A.c2) * __builtin_amdgcn_rcpf(s_sum + A.c2);
-                    cs_acc += cs;
-                    if (A.want_ss) ss_acc += fmaf(2.f, mu_xy, A.c1) * __builtin_amdgcn_rcpf(mu_xx + mu_yy + A.c1) * cs;
+                    acc += A.want_ss ? fmaf(2.f, mu_xy, A.c1) * __builtin_amdgcn_rcpf(mu_xx + mu_yy + A.c1) * cs : cs;
                 }
+            }
+            const int o = r - (kSsimK - 1);             // output row within the strip (wave-uniform)
+            if (((o + 1) & (kMetricBand - 1)) == 0 || o == rows_out - 1) {
+                double d = (double)acc;
+                for (int s = 32; s > 0; s >>= 1) d += __shfl_down(d, s);
+                if (lane == 0) part[(long long)((y0 + o) / kMetricBand) * nsx] = d;
+                acc = 0.f;
             }
         }
     };
@@ -256,13 +269,6 @@ __global__ __launch_bounds__(256) void k_ssim_strip(SsimArgs A)
         step(std::integral_constant<int, 6>{}, r0 + 6);  step(std::integral_constant<int, 7>{}, r0 + 7);
         step(std::integral_constant<int, 8>{}, r0 + 8);  step(std::integral_constant<int, 9>{}, r0 + 9);
         step(std::integral_constant<int, 10>{}, r0 + 10);
-    }
-    double ss_d = (double)ss_acc, cs_d = (double)cs_acc;
-    for (int o = 32; o > 0; o >>= 1) { ss_d += __shfl_down(ss_d, o); cs_d += __shfl_down(cs_d, o); }
-    if (lane == 0) {
-        double *acc = A.acc + (long long)img * kMetricSlots + A.slot + 2 * c;
-        if (A.want_ss) atomicAdd(&acc[0], ss_d);
-        atomicAdd(&acc[1], cs_d);
     }
 }
 
@@ -316,35 +322,45 @@ __global__ __launch_bounds__(256) void k_pool2_rgb(const float *__restrict__ ia,
     }
 }
 
-// ---- final: sums -> the three scores per image pair ----
+// ---- final: partial sums -> the three scores per image pair; one workgroup per image adds its partials in a fixed order ----
 struct FinalArgs {
+    MetricParts P;
     double npx3;              // H * W * 3
     double n_ssim;            // outputs of the grey SSIM map (0 = not computed)
     double n_level[5];        // outputs per MS-SSIM scale (0 = not computed)
     double weights[5];
 };
 
-__global__ void k_metric_final(const double *__restrict__ acc, FinalArgs F, int B, double *__restrict__ out)
+__device__ double fixed_sum(const double *__restrict__ p, long long n, double *s_red)
 {
-    const int img = blockIdx.x * blockDim.x + threadIdx.x;
-    if (img >= B) return;
-    const double *a = acc + (long long)img * kMetricSlots;
-    out[img * 3 + 0] = -10.0 * log10(a[0] / F.npx3 + 1e-8);
-    out[img * 3 + 1] = F.n_ssim > 0 ? a[kMetricSlotGrey] / F.n_ssim : nan("");
+    double v = 0.0;
+    for (long long i = threadIdx.x; i < n; i += 256) v += p[i];
+    return block_sum(v, s_red);
+}
+
+__global__ __launch_bounds__(256) void k_metric_final(const double *__restrict__ part, FinalArgs F, double *__restrict__ out)
+{
+    __shared__ double s_red[4];
+    const int img = blockIdx.x;
+    const double *a = part + (long long)img * F.P.stride;
+    const double sq = fixed_sum(a, F.P.psnr_n, s_red);
+    const double grey = F.n_ssim > 0 ? fixed_sum(a + F.P.grey_off, F.P.grey_n, s_red) : 0.0;
+    double mean = 0.0;
     if (F.n_level[0] > 0) {
-        double mean = 0.0;
         for (int c = 0; c < 3; c++) {
             double prod = 1.0;
             for (int l = 0; l < 5; l++) {
-                double v = a[kMetricSlotScales + (l * 3 + c) * 2 + (l == 4 ? 0 : 1)] / F.n_level[l];     // cs for scales 0..3, ssim for the last
+                double v = fixed_sum(a + F.P.lvl_off[l] + c * F.P.lvl_n[l], F.P.lvl_n[l], s_red) / F.n_level[l];   // cs for scales 0..3, ssim for the last
                 v = v > 0.0 ? v : 0.0;                                                   // torch.relu
                 prod *= pow(v, F.weights[l]);
             }
             mean += prod;
         }
-        out[img * 3 + 2] = mean / 3.0;
-    } else {
-        out[img * 3 + 2] = nan("");
+    }
+    if (threadIdx.x == 0) {
+        out[img * 3 + 0] = -10.0 * log10(sq / F.npx3 + 1e-8);
+        out[img * 3 + 1] = F.n_ssim > 0 ? grey / F.n_ssim : nan("");
+        out[img * 3 + 2] = F.n_level[0] > 0 ? mean / 3.0 : nan("");
     }
 }
 
@@ -355,9 +371,22 @@ static int grid_for(long long n)
     return (int)(b < 1 ? 1 : b > 4096 ? 4096 : b);
 }
 
-void launch_metric_prep(hipStream_t st, const float *a, const float *b, int B, long long npx, double *acc, unsigned char *ga, unsigned char *gb)
+int metric_prep_blocks(long long npx)
 {
-    hipLaunchKernelGGL(k_metric_prep, dim3(grid_for((npx & 3) == 0 ? npx / 4 : npx), B), dim3(256), 0, st, a, b, npx, acc, ga, gb);
+    return grid_for((npx & 3) == 0 ? npx / 4 : npx);
+}
+
+long long ssim_partials(int h, int w)
+{
+    if (h < kSsimK || w < kSsimK) return 0;
+    const int oh = h - (kSsimK - 1), ow = w - (kSsimK - 1);
+    return (long long)((oh + kMetricBand - 1) / kMetricBand) * ((ow + kSsimCols - 1) / kSsimCols);
+}
+
+void launch_metric_prep(hipStream_t st, const float *a, const float *b, int B, long long npx, double *part, long long stride, unsigned char *ga,
+                        unsigned char *gb)
+{
+    hipLaunchKernelGGL(k_metric_prep, dim3(metric_prep_blocks(npx), B), dim3(256), 0, st, a, b, npx, part, stride, ga, gb);
 }
 
 void launch_metric_pool_grey(hipStream_t st, const unsigned char *ga, const unsigned char *gb, int B, int H, int W, int f, int hp, int wp, float *xa, float *xb)
@@ -365,18 +394,18 @@ void launch_metric_pool_grey(hipStream_t st, const unsigned char *ga, const unsi
     hipLaunchKernelGGL(k_metric_pool_grey, dim3(grid_for((long long)hp * wp), B), dim3(256), 0, st, ga, gb, H, W, f, hp, wp, xa, xb);
 }
 
-void launch_ssim_level(hipStream_t st, bool interleaved, const float *xa, const float *xb, int B, int C, int h, int w, const float *g11, double *acc, int slot,
-                       bool want_ss, float *pool_a, float *pool_b)
+void launch_ssim_level(hipStream_t st, bool interleaved, const float *xa, const float *xb, int B, int C, int h, int w, const float *g11, double *part,
+                       long long stride, long long off, bool want_ss, float *pool_a, float *pool_b)
 {
     SsimArgs A;
     A.xa = xa; A.xb = xb; A.h = h; A.w = w; A.C = C;
     for (int i = 0; i < kSsimK; i++) A.g[i] = g11[i];
     A.c1 = (float)(0.01 * 0.01); A.c2 = (float)(0.03 * 0.03);
-    A.acc = acc; A.slot = slot; A.want_ss = want_ss ? 1 : 0;
+    A.part = part; A.stride = stride; A.off = off; A.want_ss = want_ss ? 1 : 0;
     A.pool_a = pool_a; A.pool_b = pool_b;
     const int oh = h - (kSsimK - 1), ow = w - (kSsimK - 1);
     // strips of 128 output rows (138 input rows: 8 % of the horizontal sums are formed twice) while that still leaves eight waves per SIMD of the
-    // chip; 64 (16 %) below
+    // chip; 64 (16 %) below.  The height follows the whole batch; the scores do not (the sums close per kMetricBand rows).
     const int nsx = (ow + kSsimCols - 1) / kSsimCols;
     const long long waves128 = (long long)nsx * ((oh + 127) / 128) * C * B;
     A.strip_rows = waves128 >= 8LL * 4 * 256 ? 128 : waves128 >= 2LL * 4 * 256 ? 64 : 32;
@@ -397,14 +426,15 @@ void launch_pool2_rgb(hipStream_t st, const float *ia, const float *ib, int B, i
     hipLaunchKernelGGL(k_pool2_rgb, dim3(grid_for((long long)h2 * w2), B), dim3(256), 0, st, ia, ib, h, w, p, h2, w2, oa, ob);
 }
 
-void launch_metric_final(hipStream_t st, const double *acc, int B, long long npx, long long n_ssim, const long long *n_level, double *out)
+void launch_metric_final(hipStream_t st, const double *part, const MetricParts &P, int B, long long npx, long long n_ssim, const long long *n_level, double *out)
 {
     FinalArgs F;
+    F.P = P;
     F.npx3 = (double)npx * 3.0;
     F.n_ssim = (double)n_ssim;
     const double wts[5] = { 0.0448, 0.2856, 0.3001, 0.2363, 0.1333 };      // piq/ms_ssim.py default scale_weights (float32 tensor)
     for (int l = 0; l < 5; l++) { F.n_level[l] = (double)n_level[l]; F.weights[l] = (double)(float)wts[l]; }
-    hipLaunchKernelGGL(k_metric_final, dim3((B + 63) / 64), dim3(64), 0, st, acc, F, B, out);
+    hipLaunchKernelGGL(k_metric_final, dim3(B), dim3(256), 0, st, part, F, out);
 }
 
 }  // namespace aej

@@ -6,7 +6,7 @@ import pytest
 from oracle import metrics_oracle as M
 
 SSIM_TOL = 1e-4        # absolute, on scores in [0, 1]: sigma = E[x^2] - mu^2 cancels in float32 (piq's type and ours); the restatement uses float64
-PSNR_TOL = 1e-3        # dB
+PSNR_TOL = 1e-4        # dB: the float32 squared differences are within 16 u relative (tests/test_gpu_metrics.py), 7e-5 dB
 
 
 def pair(oracle, H, W, seed, sigma=0.03):
@@ -42,6 +42,44 @@ def test_oracle_ssim_properties(oracle):
         M.ms_ssim(a[:160], b[:160])
     with pytest.raises(ValueError):
         M.ssim(a[:10], b[:10])
+
+
+# Every parity of the MS-SSIM pad chain (scale sizes (h % 2, w % 2) = (0, 0), (0, 1), (1, 0), (1, 1) at the pooling steps) and f = 1, 2, 3
+DEF_VS_FAST = [(161, 161), (162, 163), (163, 162), (176, 200), (322, 323), (384, 401), (770, 700)]
+
+
+@pytest.mark.parametrize("H,W", DEF_VS_FAST, ids=[f"{h}x{w}" for h, w in DEF_VS_FAST])
+def test_fast_reference_matches_definition(oracle, H, W):
+    """The separable float64 restatement against the 2-D one.  With the 1-D taps scaled so that g g^T has the sum of piq's float32
+    2-D window, what is left of the window difference is a zero-sum perturbation of at most rho relative per entry (rho from the windows
+    themselves, about 5.7e-7); M.ssim_stats(rho=...) turns that and the definition's float32 rounding of pooled inputs into a bound per
+    score (first order, no float32 arithmetic on the fast side)."""
+    w32 = M.gaussian_window().astype(np.float64)
+    g = M.gaussian_1d() * np.sqrt(w32.sum())
+    rho = float(np.abs(w32 / np.outer(g, g) - 1).max())
+    assert rho < 1e-6
+    a, b = pair(oracle, H, W, H * 7 + W)
+    f = M.grey_pool_factor(H, W)
+    assert f == {770: 3, 384: 2}.get(H, 1)
+    s, bound = M.ssim_fast(a, b, g=g, rho=rho)
+    assert abs(s - M.ssim(a, b)) <= bound * 1.01 + 1e-12
+    fast, ref = M.ms_ssim_scales(a, b, g=g, rho=rho), M.ms_ssim_scales_def(a, b)
+    for l in range(5):
+        assert np.all(np.abs(fast[l][0] - ref[l]) <= fast[l][1] * 1.01 + 1e-12), (l, fast[l], ref[l])
+    assert M.ms_ssim_from_scales(fast)[0] == pytest.approx(M.ms_ssim(a, b), abs=M.ms_ssim_from_scales(fast)[1] * 1.01 + 1e-12)
+
+
+def test_fast_reference_geometry_rules():
+    """piq 0.8.0's rules as the module docstring states them"""
+    assert [M.grey_pool_factor(n, 5000) for n in (383, 384, 385, 639, 640, 641, 895, 896, 1152, 11)] == [1, 2, 2, 2, 2, 3, 3, 4, 4, 1]
+    assert [M.grey_pool_factor(n, 5000, "half_up") for n in (384, 640, 896, 1152)] == [2, 3, 4, 5]
+    a = np.zeros((163, 165, 3), np.float32)
+    a[0, 0] = 1
+    (v0, _), (v1, _) = M.ms_ssim_scales(a, a)[:2]
+    assert np.allclose(v0, 1) and np.allclose(v1, 1)
+    a = np.random.default_rng(0).random((30, 31, 3)).astype(np.float32)
+    xa, _ = M.grey_planes(a, a)
+    assert xa.shape == (30, 31)
 
 
 # ------------------------------------------------------------------ GPU
