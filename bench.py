@@ -6,14 +6,17 @@ quantise -> zigzag) over one device-residen
 images per GPU (BASELINE config 4: 512 4K images over 8 GPUs = 64 per GPU; weak scaling).  Inputs are in HBM before the timed
 region; outputs stay in HBM.
 
-    python bench.py                      # 1 GPU, 64 x 4K, 10 steps
+    python bench.py                      # 1 GPU, 64 x 4K, 20 steps: the headline figure only
+    python bench.py --full               # the same, then every check and figure listed below
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 The measurement (main(), section "the measurement"): W warm-up steps, then EXACTLY K steps inside timed_loop() -- barrier +
 synchronize on both sides -- rotating over `--pipeline` contexts (tools/benchlib/workload.py: what a step is, how the two input batches
-alternate).  Nothing is profiled, verified or read back inside the timed region; after it the outputs of the LAST timed step are
-compared with the CPU oracle (`verified`), stage times come from separate profiled steps, and rank 0 prints ONE JSON line with
+alternate).  Nothing is profiled, verified or read back inside the timed region.  A plain run stops there: it writes the outputs of the
+LAST timed step if --dump-outputs asks for them, and rank 0 prints ONE JSON line with the headline figure (`value`, `ms_per_step`) and
+the configuration it was taken with.  With --full the outputs of the last timed step are also compared with the CPU oracle
+(`verified`), stage times come from separate profiled steps, and the line carries
 * `roofline`: the longest kernel of the chain a step waits for (the colour stage is a background kernel: `runner_up`), its
   ALGORITHMIC bytes per launch over its HIP-event time, against the 8 TB/s HBM peak; `traffic` from the committed PMC profile;
 * `whole_path`: the same for the whole step, with the measured HBM traffic and the vector-issue share of the step;
@@ -59,9 +62,12 @@ def parse_args(argv=None):
     ap.add_argument("--data", choices=["synthetic", "natural"], default="synthetic",
                     help="synthetic = SURVEY 8d's 'mixed' generator (the headline); natural = the reference's own test images mirror-tiled to "
                          "the image size (a labelled variant: textures change the leaf mix and the hysteresis work)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-verify", action="store_true", help="skip the post-timing oracle comparison")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the other BASELINE configurations after the headline measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement, also the oracle check, the blocking-call figure, stage times, roofline, CPU baseline and "
+                         "other BASELINE configurations (a plain run times the steps and prints the headline figure only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-verify", action="store_true", help="--full without the post-timing oracle comparison")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full without the other BASELINE configurations after the headline measurement")
     ap.add_argument("--cpu-threads", type=int, default=0, help="host threads for cpu_baseline; 0 = min(cores this process may use, 64)")
     ap.add_argument("--graph", type=int, choices=[0, 1, 2], default=0,
                     help="aej_set_graph_mode: 0 never replay a captured hipGraph (the library default), 1 automatic (calls of at most 8 Mpx), 2 whenever possible")
@@ -75,9 +81,6 @@ def parse_args(argv=None):
                     help="contexts (each on its own stream, with its own output buffers and workspace) the timed steps rotate over; 1 = blocking calls")
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE",
                     help="aej_set_option on every context (include/aej.h has the table), e.g. --option dct64_kernel=1; A / B runs only")
-    ap.add_argument("--timed-only", action="store_true",
-                    help="profiler runs (tools/profiling/*.sh): only the W warm-up and K timed steps, so every kernel is launched a known "
-                         "number of times; prints value / ms_per_step only")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (see dump_outputs; dumps/<name> inside "
                          "the tree is git-ignored); rank 0 only")
@@ -399,8 +402,9 @@ def main():
     n_warm = wl.warm(args.warmup)
     # the first collective of the process -- after every context, stream and sub-batch stream exists (hw_queue_default) -- holds the
     # barrier behind which ONE process per node builds the checker: it exists before anything is timed and is not used until after
+    # (in a plain run the barrier of timed_loop is that first collective)
     O = None
-    if not (args.no_verify and args.no_cpu_baseline) and not args.timed_only:      # (the same decision on every rank)
+    if args.full and not (args.no_verify and args.no_cpu_baseline):      # (the same decision on every rank)
         O = build_oracle_once(dist, int(os.environ.get("LOCAL_RANK", "0")))
     h0 = wl.hyst_stats()
     dt_local = timed_loop(torch, dist, wl.step, args.steps, wl.sync)
@@ -415,11 +419,24 @@ def main():
         pipe, _ = wl.last_step(args.steps)
         n_files, n_bytes = dump_outputs(args.dump_outputs, pipe.plan, *pipe.out)
         dumped = {"dir": args.dump_outputs, "files": n_files, "bytes": n_bytes}
-    if args.timed_only:
+    headline = (B, H, W, space, tuple(brange), args.data, args.ingest) == (64, H4K, W4K, "YCbCr", (4, 64), "synthetic", "f32")
+    out = {
+        "metric": METRIC, "value": round(value, 1), "unit": "MP/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "f32",
+        "data": ("synthetic ('mixed' images generated on the GPU, SURVEY.md 8d recipe); two batches of different seeds alternate across steps"
+                 if args.data == "synthetic" else
+                 "natural: the reference's own test images (baboon, peppers, house, jelly_beans, LIVE bikes / buildings) mirror-tiled to the image "
+                 "size, uint8 levels / 255; two batches alternate across steps -- a labelled variant, not the headline recipe"),
+        "config": {"workload": f"{B} x {W}x{H} {'uint8' if args.ingest == 'u8' else 'float32'} RGB per GPU, {space}, blocks {brange[0]}-{brange[1]}, "
+                               f"quality {qrange[0]}-{qrange[1]} " + ("(BASELINE config 4: 512 4K images / 8 GPUs)" if headline else "(not the headline workload)"),
+                   "images_per_gpu": B, "height": H, "width": W, "color_space": space, "block_size_range": list(brange),
+                   "quality_range": list(qrange), "steps_in_flight": n_pipe, "options": args.option or None},
+        "encode_calls": args.steps + n_warm,      # warm-up and timed calls (tools/profiling/pmc.py divides its counters by them)
+        "full": args.full, "dumped_outputs": dumped,
+    }
+    if not args.full:
         if rank == 0:
-            emit(json.dumps({"metric": METRIC, "value": round(value, 1), "unit": "MP/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-                              "ms_per_step": round(ms_per_step, 3), "encode_calls": args.steps + n_warm, "timed_only": True,
-                              "dumped_outputs": dumped}))
+            emit(json.dumps(out))
         if dist is not None:
             dist.destroy_process_group()
         return
@@ -478,21 +495,10 @@ def main():
                   "note": "traffic / valu: every kernel of one blocking call summed (rocprofv3 PMC passes of this command, tools/profiling/pmc.py), "
                           "divided by THIS run's step time; valu_frac_of_step = instructions x %.1f ns / %d SIMDs / step" % (VALU_ISSUE_NS, N_SIMD)}
     per_stage = {k: {"ms": round(v, 4), "GBps": round(algo[k] / (v * 1e-3) / 1e9, 1) if v > 0 else None} for k, v in kernels.items()}
-    headline = (B, H, W, space, tuple(brange), args.data, args.ingest) == (64, H4K, W4K, "YCbCr", (4, 64), "synthetic", "f32")
 
-    out = {
-        "metric": METRIC, "value": round(value, 1), "unit": "MP/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "f32",
-        "data": ("synthetic ('mixed' images generated on the GPU, SURVEY.md 8d recipe); two batches of different seeds alternate across steps"
-                 if args.data == "synthetic" else
-                 "natural: the reference's own test images (baboon, peppers, house, jelly_beans, LIVE bikes / buildings) mirror-tiled to the image "
-                 "size, uint8 levels / 255; two batches alternate across steps -- a labelled variant, not the headline recipe"),
-        "config": {"workload": f"{B} x {W}x{H} {'uint8' if args.ingest == 'u8' else 'float32'} RGB per GPU, {space}, blocks {brange[0]}-{brange[1]}, "
-                               f"quality {qrange[0]}-{qrange[1]} " + ("(BASELINE config 4: 512 4K images / 8 GPUs)" if headline else "(not the headline workload)"),
-                   "images_per_gpu": B, "height": H, "width": W, "color_space": space, "block_size_range": list(brange),
-                   "quality_range": list(qrange), "steps_in_flight": n_pipe, "options": args.option or None},
+    out.update({
         "roofline": roofline, "valu": valu, "runner_up": runner_up, "whole_path": whole_path,
-        "verified": verified, "profile_gaps": prof.gaps(brange), "ranks": ranks, "dumped_outputs": dumped,
+        "verified": verified, "profile_gaps": prof.gaps(brange), "ranks": ranks,
         "hysteresis": {"timed_calls": h1["calls"] - h0["calls"], "tiles_through_the_work_queue_last_call": h1["queued"],
                        "tiles": int(B * sum(-(-plan.layer_h[l] // 64) * -(-plan.layer_w[l] // 64) for l in range(3))),
                        "what": "completes on the device: a pass over every 64 x 64 tile, bulk launches over the flagged tiles, then a device-side "
@@ -509,7 +515,7 @@ def main():
         "leaf_histogram": {"per_image": {str(k): round(v / B, 1) for k, v in leaf_hist.items()},
                            "area_share": {str(k): round(k * k * v / leaf_area, 4) for k, v in leaf_hist.items()}},
         "dct_by_block_size": dct_by_block_size(leaf_hist, stage_ms),
-    }
+    })
     # Canny chain a-3 .. a-8 (5 B per plane pixel = float32 plane in, uint8 edge map out -> 7.5 B per image pixel)
     canny_ms = sum(stage_ms.get(k, 0.0) for k in ("clahe_lut", "clahe_blur", "thresholds", "sobel_nms", "hysteresis"))
     if canny_ms > 0:

@@ -416,6 +416,33 @@ def test_bench_configuration_64x4k_four_contexts(env, oracle):
         c.check(c.lib.aej_set_hw_queues(c.handle, hw_queues()[0]))
 
 
+def test_bench_plain_run_prints_the_headline_and_full_run_checks(tmp_path):
+    """bench.py in a child process at a small shape: a plain run prints the headline fields and nothing that needs work beyond the timed
+    steps; --full adds the oracle check of the last timed step, the blocking-call figure and the stage times, and exits 0."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    small = ["--steps", "2", "--warmup", "1", "--batch", "2", "--height", "256", "--width", "384"]
+
+    def run(extra):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + small + extra, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = r.stdout.splitlines()
+        assert len(lines) == 1, r.stdout
+        return json.loads(lines[0])
+
+    plain = run(["--dump-outputs", str(tmp_path / "dump")])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in plain, k
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["full"] is False and plain["dumped_outputs"]["files"] > 0
+    assert not {"verified", "pipeline", "stages", "roofline", "cpu_baseline", "other_configs"} & set(plain)
+    full = run(["--full", "--no-cpu-baseline"])
+    assert full["full"] is True and full["verified"]["ok"] and full["ranks"]["all_verified"]
+    assert full["pipeline"]["serial_ms_per_step"] > 0 and full["stages"] and "other_configs" not in full      # (not the headline shape)
+
+
 def test_failed_begin_drains_what_it_enqueued(env, oracle):
     """A whole-path call that fails after it has put work in flight (aej_test_fail_after_stage: test instrumentation of the ABI) must
     return with its streams drained -- unsplit and sub-batch paths alike -- leave the context usable, and leave no stale chain hook."""

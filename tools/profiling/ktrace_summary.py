@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Per-kernel durations of a pipelined bench run from a rocprofv3 kernel trace (GPU box):
 
-    rocprofv3 --kernel-trace --output-format csv -d gpurun_out/kt -- python3 bench.py --timed-only --steps 6 --warmup 4
-    python3 tools/profiling/ktrace_summary.py gpurun_out/kt <encode calls in the run> [serial_stats.csv]
+    rocprofv3 --kernel-trace --output-format csv -d build/kt -- python3 bench.py --steps 6 --warmup 4
+    python3 tools/profiling/ktrace_summary.py build/kt <encode calls in the run> [serial_stats.csv]
 
 Prints, per kernel: launches per call, average duration, summed duration per call, and -- with the kernel stats of a serial run --
 the dilation factor under overlap; then the busy / idle split of the device timeline (union of kernel intervals).

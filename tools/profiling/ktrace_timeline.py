@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Steady-state timeline analysis of a pipelined bench run (GPU box):
 
-    rocprofv3 --kernel-trace --output-format csv -d gpurun_out/kt -- python3 bench.py --timed-only --steps 12 --warmup 6
-    python3 tools/profiling/ktrace_timeline.py gpurun_out/kt
+    rocprofv3 --kernel-trace --output-format csv -d build/kt -- python3 bench.py --steps 12 --warmup 6
+    python3 tools/profiling/ktrace_timeline.py build/kt
 
 Takes the last 60 % of the aej kernels (steady state), and prints: how long N kernels were running at once, per kernel kind the average
 duration and what else was running beside it (time-weighted), and the idle share of the window.

@@ -5,6 +5,6 @@ reps=$1; shift
 for rep in $(seq $reps); do
   for set in "$@"; do
     args=""; [ "$set" != "-" ] && for o in $set; do args="$args --option $o"; done
-    python3 bench.py --no-cpu-baseline --no-verify --steps 40 --warmup 6 $args 2>/dev/null | python3 -c "import json,sys;d=json.load(sys.stdin);print('[$set]', d['ms_per_step'], 'blocking', d['pipeline']['serial_ms_per_step'])"
+    python3 bench.py --full --no-cpu-baseline --no-verify --steps 40 --warmup 6 $args 2>/dev/null | python3 -c "import json,sys;d=json.load(sys.stdin);print('[$set]', d['ms_per_step'], 'blocking', d['pipeline']['serial_ms_per_step'])"
   done
 done

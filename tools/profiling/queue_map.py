@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Which hardware queue each stream's kernels ran on (rocprofv3 --kernel-trace CSV of a pipelined bench run):
-    rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 bench.py --timed-only --steps 8 --warmup 4 ; python3 tools/profiling/queue_map.py DIR
+    rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 bench.py --steps 8 --warmup 4 ; python3 tools/profiling/queue_map.py DIR
 Two busy streams on one queue run one after the other."""
 import collections, csv, glob, sys
 f = glob.glob(sys.argv[1] + "/**/*kernel_trace.csv", recursive=True)[0]

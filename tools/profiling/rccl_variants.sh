@@ -1,7 +1,7 @@
 #!/bin/bash
 # a live RCCL communicator and the hardware queues: one GPU, one rank, interleaved
 #   no group | group, bench.py's defaults (24 queues, communicator created after our streams) | communicator first, 16 / 24 queues | ours first, 16 queues
-run() { env $1 python3 bench.py --no-cpu-baseline --no-verify --steps 30 --warmup 6 2>/dev/null | python3 -c "
+run() { env $1 python3 bench.py --full --no-cpu-baseline --no-verify --steps 30 --warmup 6 2>/dev/null | python3 -c "
 import json,sys
 d=json.load(sys.stdin)
 print('[$1]:', d['ms_per_step'], 'ms/step; blocking', d['pipeline']['serial_ms_per_step'], (d['ranks'].get('collectives') or {}).get('backend'))"; }

@@ -54,7 +54,7 @@ def run(bench_args):
             env = dict(os.environ)
             if n != "base":
                 env["AEJ_LIBRARY"] = os.path.join(VDIR, n, "libaejpeg_hip.so")
-            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--steps", "6", "--warmup", "2"] + bench_args,
+            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--steps", "6", "--warmup", "2"] + bench_args,
                                env=env, capture_output=True, text=True)
             line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
             if r.returncode != 0 or not line:
