@@ -106,7 +106,7 @@ def test_reflect_pad_and_quantise_equal_numpy(oracle):
     assert np.round(y / q).astype(np.int32).tolist() == [2, 4, -2, 4, 0, 0]
 
 
-@pytest.mark.parametrize("s", [4, 8, 16, 32, 64, 128])
+@pytest.mark.parametrize("s", [2, 4, 8, 16, 32, 64, 128, 256, 512, 1024])
 def test_dct_contract_tolerance(oracle, s):
     """pre-quantisation DCT: float32 fma chains vs float64 orthonormal DCT-II; stated tolerance 1e-6 * s * 127."""
     rng = np.random.default_rng(s)
