@@ -3,7 +3,8 @@
 Same Python surface as the reference for this path (fevzibabaoglu/adaptive-edge-aware-jpeg):
 ``Jpeg``, ``JpegCompressionSettings``, ``Image``, ``EvaluationMetrics``, ``EdgeDetection``, ``QuadTree``, ``convert``,
 ``apply_normalization``, ``get_color_spaces``; and standard JPEG (``standard_jpeg_many`` / ``standard_jpeg_batch``, byte-identical to
-Pillow's files) for the reference's comparison against it.  The arithmetic runs in hand-written HIP kernels behind the
+Pillow's files) for the reference's comparison against it, and ``standard_jpeg_decode_many`` (baseline .jpg files decoded on the GPU,
+pixel-identical to Pillow).  The arithmetic runs in hand-written HIP kernels behind the
 C ABI of ``libaejpeg_hip.so`` (include/aej.h); there is no CPU fallback.
 """
 from ._lib import _look_at_hw_queues, configure_hw_queues, hw_queues, set_hw_queues
@@ -21,9 +22,10 @@ from .jpeg import EncodedBatch, Jpeg  # noqa: E402
 from .lpips import LpipsWeights  # noqa: E402
 from .quadtree import QuadNode, QuadTree  # noqa: E402
 from .settings import JpegCompressionSettings  # noqa: E402
-from .standard_jpeg import standard_jpeg_batch, standard_jpeg_many  # noqa: E402
+from .standard_jpeg import standard_jpeg_batch, standard_jpeg_decode_many, standard_jpeg_many  # noqa: E402
 from .sweep import SweepResult, reference_grid, sweep  # noqa: E402
 
 __all__ = ["Jpeg", "JpegCompressionSettings", "EncodedBatch", "Image", "EvaluationMetrics", "EdgeDetection", "QuadTree", "QuadNode",
            "convert", "apply_normalization", "get_color_spaces", "hw_queues", "set_hw_queues", "configure_hw_queues",
-           "sweep", "reference_grid", "SweepResult", "LpipsWeights", "standard_jpeg_many", "standard_jpeg_batch"]
+           "sweep", "reference_grid", "SweepResult", "LpipsWeights", "standard_jpeg_many", "standard_jpeg_batch",
+           "standard_jpeg_decode_many"]

@@ -130,6 +130,21 @@ class CannyParams(ctypes.Structure):
                 ("bilateral_sigma_color", ctypes.c_double), ("bilateral_sigma_space", ctypes.c_double), ("use_l2_gradient", ctypes.c_int)]
 
 
+class JpegDecHuff(ctypes.Structure):
+    """aej_jpegdec_huff (include/aej.h)"""
+    _fields_ = [("lut", ctypes.c_uint16 * 512), ("maxcode", ctypes.c_int32 * 18), ("valoff", ctypes.c_int32 * 18), ("vals", ctypes.c_uint8 * 256)]
+
+
+class JpegDecDesc(ctypes.Structure):
+    """aej_jpegdec_desc (include/aej.h): what aej_jpegdec_parse_host reads from a file's markers"""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("ncomp", ctypes.c_int32), ("hs", ctypes.c_int32), ("vs", ctypes.c_int32),
+                ("mcux", ctypes.c_int32), ("mcuy", ctypes.c_int32), ("blocks_per_mcu", ctypes.c_int32), ("restart_interval", ctypes.c_int32),
+                ("n_segments", ctypes.c_int32), ("sof", ctypes.c_int32), ("precision16", ctypes.c_int32),
+                ("comp_id", ctypes.c_uint8 * 4), ("comp_h", ctypes.c_uint8 * 4), ("comp_v", ctypes.c_uint8 * 4), ("comp_tq", ctypes.c_uint8 * 4),
+                ("qt", (ctypes.c_uint16 * 64) * 3), ("dc", JpegDecHuff * 3), ("ac", JpegDecHuff * 3),
+                ("scan_offset", ctypes.c_int64), ("scan_length", ctypes.c_int64)]
+
+
 SIGNATURES = {
     "aej_abi_version": (_I, []),
     "aej_create": (_P, [_I, _P]),
@@ -193,12 +208,18 @@ SIGNATURES = {
     "aej_jfif_headers_host": (_I, [_I, _I, _I, _P, _I]),
     "aej_jfif_encode_batch": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _U64, _P, _P, _P, _P, _U64]),
     "aej_jfif_recon_batch": (_I, [_P, _I, _I, _I, _I, _P, _P, _U64]),
+    "aej_jpegdec_parse_host": (_I, [_P, _U64, _P, _P, _I]),
+    "aej_jpegdec_workspace_bytes": (_U64, [_P, _P, _I]),
+    "aej_jpegdec_batch": (_I, [_P, _P, _I, _P, _U64, _P, _P, _U64, _P, _P, _P, _U64]),
+    "aej_jpegdec_sync_rounds": (_I64, [_P]),
 }
 
 # status values of aej_inflate_batch / aej_decode_headers (include/aej.h AEJ_INFLATE_* / AEJ_HEADER_*)
 INFLATE_STATUS = ["ok", "bad zlib header", "bad block type", "bad code lengths", "invalid literal/length or distance code",
                   "distance too far back", "stored block LEN/NLEN mismatch", "truncated stream", "output over capacity",
                   "Adler-32 mismatch", "bad stream descriptor"]
+JPEGDEC_STATUS = ["ok", "truncated scan (it ends before the last MCU)", "bad Huffman code", "coefficient run past 63",
+                  "DC category above 11", "restart marker out of sequence, missing or unexpected"]
 HEADER_STATUS = ["ok", "more leaves than the layer holds", "leaf size outside the block-size range of the header",
                  "quadtree header does not tile the layer", "coefficient count does not match the quadtree header", "bad layer descriptor"]
 

@@ -230,3 +230,24 @@ hipError_t launch_jfif_encode(hipStream_t st, const JfifGeom &g, const JfifBufs 
 hipError_t launch_jfif_recon(hipStream_t st, const JfifGeom &g, const JfifBufs &w, unsigned char *rgb_out);
 
 }  // namespace aej
+
+// jpegdec.hip: baseline JPEG files decoded on the device (aej_jpegdec_*)
+#include <string>
+#include <vector>
+#include "jpegdec_core.h"
+
+namespace aej {
+struct JdBufSizes { long long chunks, segs, slots, blocks, clean, planes, px; };      // totals over the files of one call
+struct JdBufs {
+    JdFile *files; aej_jpegdec_desc *descs; int *last_change;      // one upload: files, descriptors, the "last round that changed" word
+    int *cnt; long long *pre, *clean_len; JdSeg *segs; unsigned char *clean; JdSlots sl; short *coef; unsigned char *planes;
+};
+int jpegdec_parse(const unsigned char *data, unsigned long long n, aej_jpegdec_desc &d, std::string &msg);
+long long jpegdec_layout(const aej_jpegdec_desc *descs, int n, int S, std::vector<JdFile> &files, JdBufSizes &z);
+unsigned long long jpegdec_carve(void *base, int n, const JdBufSizes &z, JdBufs &w);
+hipError_t launch_jpegdec_begin(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, const void *blob_host, unsigned long long blob_bytes,
+                                const unsigned char *scans, int S, int *status);
+hipError_t launch_jpegdec_sync(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, int S, int first_round, int rounds);
+hipError_t launch_jpegdec_finish(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, int S, unsigned char *out, int *status);
+
+}  // namespace aej

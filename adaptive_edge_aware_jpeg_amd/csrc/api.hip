@@ -73,6 +73,8 @@ struct aej_ctx {
     int chain_hook = 0;                // run_canny_chain publishes chain_event after the blur (2) / Sobel (3) stage of the part being enqueued
     hipEvent_t chain_event = nullptr;
     Tuning tune;                       // aej_set_option: kernel / launch-shape choices (nothing in the library reads the environment)
+    int jd_subseq_bits = 2048;         // aej_set_option "jpegdec_subseq_bits": subsequence length of aej_jpegdec_batch's Huffman decode
+    long long jd_sync_rounds = 0;      // sync rounds of the last aej_jpegdec_batch
     struct aej_pending *pending = nullptr;     // the call between aej_encode_batch_begin and aej_encode_batch_end
     // optional stage timing (aej_set_profiling): events on ctx->stream around each stage of aej_encode_batch
     bool profiling = false;
@@ -1844,6 +1846,7 @@ const OptionDef kOptions[] = {
     { "sobel_xcd", &aej::Tuning::sobel_xcd, nullptr, 0, 1, true },
     { "dct_multi", &aej::Tuning::dct_multi, nullptr, 0, 1, true },
     { "sub_chain", nullptr, &aej_ctx::sub_chain, -1, 3, false },
+    { "jpegdec_subseq_bits", nullptr, &aej_ctx::jd_subseq_bits, 32, 1 << 20, false },
 };
 const OptionDef *find_option(const char *name)
 {
@@ -2097,4 +2100,102 @@ extern "C" int aej_jfif_recon_batch(aej_ctx *ctx, int batch, int H, int W, int n
     AEJ_HIP_CHECK(hipSetDevice(ctx->device));
     AEJ_HIP_CHECK(launch_jfif_recon(ctx->stream, g, w, rgb_out));
     return 0;
+}
+
+// ---- baseline JPEG files decoded on the device (jpegdec.hip) --------------------------------------------------------------------------
+extern "C" int aej_jpegdec_parse_host(const uint8_t *data_host, uint64_t nbytes, aej_jpegdec_desc *desc_host, char *msg, int msg_capacity)
+{
+    if (!desc_host) return AEJ_ERR_ARG;
+    std::string m;
+    const int rc = jpegdec_parse(data_host, nbytes, *desc_host, m);
+    if (msg && msg_capacity > 0) {
+        const size_t k = std::min(m.size(), (size_t)msg_capacity - 1);
+        memcpy(msg, m.data(), k);
+        msg[k] = 0;
+    }
+    return rc;
+}
+
+static bool jpegdec_descs_ok(const aej_jpegdec_desc *d, int n)
+{
+    if (!d || n < 1) return false;
+    for (int i = 0; i < n; i++) {
+        const aej_jpegdec_desc &e = d[i];
+        const bool color = e.ncomp == 3 && ((e.hs == 1 && e.vs == 1) || (e.hs == 2 && (e.vs == 1 || e.vs == 2)));
+        if (!(color || (e.ncomp == 1 && e.hs == 1 && e.vs == 1))) return false;
+        if (e.width < 1 || e.height < 1 || e.width > 65535 || e.height > 65535 || e.scan_length < 0) return false;
+        if (e.mcux != (e.width + 8 * e.hs - 1) / (8 * e.hs) || e.mcuy != (e.height + 8 * e.vs - 1) / (8 * e.vs)) return false;
+        if (e.blocks_per_mcu != (e.ncomp == 1 ? 1 : e.hs * e.vs + 2) || e.restart_interval < 0) return false;
+        const long long mcus = (long long)e.mcux * e.mcuy;
+        if (e.n_segments != (e.restart_interval ? (mcus + e.restart_interval - 1) / e.restart_interval : 1)) return false;
+    }
+    return true;
+}
+
+extern "C" uint64_t aej_jpegdec_workspace_bytes(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n)
+{
+    if (!ctx || !jpegdec_descs_ok(descs_host, n)) return 0;
+    std::vector<JdFile> files;
+    JdBufSizes z;
+    jpegdec_layout(descs_host, n, ctx->jd_subseq_bits, files, z);
+    JdBufs w;
+    return jpegdec_carve(nullptr, n, z, w);
+}
+
+extern "C" int aej_jpegdec_batch(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const uint8_t *scans, uint64_t scans_bytes,
+                                 const int64_t *scan_offsets_host, uint8_t *out, uint64_t out_bytes, const int64_t *out_offsets_host,
+                                 int32_t *status, void *workspace, uint64_t workspace_bytes)
+{
+    if (!ctx) return AEJ_ERR_ARG;
+    if (call_in_flight(ctx)) return fail(ctx, AEJ_ERR_STATE, "%s between aej_encode_batch_begin and aej_encode_batch_end", __func__);
+    if (!jpegdec_descs_ok(descs_host, n)) return fail(ctx, AEJ_ERR_ARG, "%s: no files, or a descriptor aej_jpegdec_parse_host did not write", __func__);
+    if (!scans || !scan_offsets_host || !out || !out_offsets_host || !status || !workspace) return fail(ctx, AEJ_ERR_ARG, "%s: NULL buffer", __func__);
+    const int S = ctx->jd_subseq_bits;
+    std::vector<JdFile> files;
+    JdBufSizes z;
+    jpegdec_layout(descs_host, n, S, files, z);
+    for (int i = 0; i < n; i++) {
+        const aej_jpegdec_desc &d = descs_host[i];
+        const long long so = scan_offsets_host[i], oo = out_offsets_host[i], ob = (long long)d.width * d.height * 3;
+        if (so < 0 || (uint64_t)so + (uint64_t)d.scan_length > scans_bytes)
+            return fail(ctx, AEJ_ERR_ARG, "%s: file %d: scan outside the scans buffer", __func__, i);
+        if (oo < 0 || (uint64_t)oo + (uint64_t)ob > out_bytes) return fail(ctx, AEJ_ERR_ARG, "%s: file %d: image outside the output", __func__, i);
+        files[i].scan_off = so;
+        files[i].out_off = oo;
+    }
+    JdBufs w;
+    const unsigned long long need = jpegdec_carve(workspace, n, z, w);
+    if (need > workspace_bytes) return fail(ctx, AEJ_ERR_CAPACITY, "workspace too small: need %llu bytes, got %llu", need, (unsigned long long)workspace_bytes);
+    // one upload: files, descriptors, the "last round that changed" word (-1)
+    std::vector<unsigned char> blob(sizeof(JdFile) * n + sizeof(aej_jpegdec_desc) * n + sizeof(int));
+    memcpy(blob.data(), files.data(), sizeof(JdFile) * n);
+    memcpy(blob.data() + sizeof(JdFile) * n, descs_host, sizeof(aej_jpegdec_desc) * n);
+    const int minus1 = -1;
+    memcpy(blob.data() + blob.size() - sizeof(int), &minus1, sizeof(int));
+    long long max_slots = 0;
+    for (const JdFile &f : files) max_slots = std::max(max_slots, f.n_slots);
+    AEJ_HIP_CHECK(hipSetDevice(ctx->device));
+    AEJ_HIP_CHECK(launch_jpegdec_begin(ctx->stream, n, z, w, blob.data(), blob.size(), scans, S, status));
+    // sync rounds: kJdSyncBatch launches, then one word read back; more only while the last launched round still changed something.
+    // Each round settles at least the first unsettled subsequence of every segment, so max_slots rounds always suffice.
+    int launched = 0, last = -1;
+    for (;;) {
+        AEJ_HIP_CHECK(launch_jpegdec_sync(ctx->stream, n, z, w, S, launched + 1, kJdSyncBatch));
+        launched += kJdSyncBatch;
+        AEJ_HIP_CHECK(hipMemcpyAsync(ctx->h_flag, w.last_change, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        AEJ_HIP_CHECK(hipStreamSynchronize(ctx->stream));     // also keeps `blob` alive until its upload has run
+        last = ctx->h_flag[0];
+        if (last < launched) break;
+        if (launched > max_slots + kJdSyncBatch)
+            return fail(ctx, AEJ_ERR_STATE, "%s: the Huffman decode did not settle after %d rounds", __func__, launched);
+    }
+    ctx->jd_sync_rounds = last + 1;
+    AEJ_HIP_CHECK(launch_jpegdec_finish(ctx->stream, n, z, w, S, out, status));
+    return 0;
+}
+
+extern "C" int64_t aej_jpegdec_sync_rounds(aej_ctx *ctx)
+{
+    if (!ctx) return AEJ_ERR_ARG;
+    return ctx->jd_sync_rounds;
 }

@@ -1,0 +1,245 @@
+// jpegdec_core.h -- the per-thread work of jpegdec.hip's stages (aej_jpegdec_*), written as host + device functions so that the same
+// decode can be stepped through on the CPU.  Everything here is bounded by the sizes it is given: the Huffman loop by its stop bit,
+// every read by the file's clean stream (whose allocation carries 8 bytes of slack past the last byte a stop bit can reach).
+#pragma once
+#include <stdint.h>
+
+#include "../../include/aej.h"
+
+#ifndef AEJ_HD
+#define AEJ_HD __host__ __device__
+#endif
+
+namespace aej {
+
+constexpr int kJdChunk = 64;           // bytes per un-stuffing chunk
+constexpr int kJdSyncBatch = 4;        // sync rounds launched between two read-backs of the "changed" word
+
+// per-file layout of one aej_jpegdec_batch (host-computed, uploaded with the descriptors)
+struct JdFile {
+    long long scan_off, scan_len;      // stuffed scan bytes in the caller's buffer
+    long long clean_off;               // byte offset of the file's un-stuffed stream in the clean buffer (4-byte aligned)
+    long long chunk_base, n_chunks;    // un-stuffing chunks
+    long long seg_base;                // first restart segment (global index)
+    long long slot_base, n_slots;      // subsequence slots (an upper bound: every segment's slots start at seg + start_bit / S)
+    long long blk_base, n_blocks;      // coefficient blocks, MCU order
+    long long plane_off;               // byte offset of the sample planes
+    int pw0, ph0, pw1, ph1;            // luma and chroma plane shapes (whole MCUs)
+    long long px_base;                 // first output pixel of the call's pixel range
+    long long out_off;                 // byte offset of the RGB output
+};
+
+// one restart segment: written by the un-stuffing scatter (start) and k_jd_segments (the rest)
+struct JdSeg {
+    long long start, nbytes;           // in the clean stream of its file
+    long long slot_base;               // first slot, relative to the file's slot_base
+    int n_sub;                         // subsequences (>= 1)
+    int first_mcu, n_mcu;
+};
+
+struct JdSlots {
+    unsigned long long *state, *used;     // exit state; the entry state it was decoded from
+    int *cnt;                             // [slot][4]: blocks started, DC sums of components 0..2
+    unsigned char *first;                 // the slot starts a segment
+    long long *blk_pre;                   // exclusive prefix of blocks started within the segment
+    int *dc_pre;                          // [slot][3]
+};
+
+// decoder state at a symbol boundary, packed in one 64-bit word (so that a successor reads it whole):
+// bits 0..5 zigzag index, 6..8 block slot in the MCU, 9 "no state" (the decode that would produce it stopped on an error), 10.. bit offset
+AEJ_HD inline unsigned long long jd_pack(long long pos, int k, int z, int err)
+{
+    return ((unsigned long long)pos << 10) | ((unsigned long long)(err & 1) << 9) | ((unsigned long long)(k & 7) << 6) | (unsigned long long)(z & 63);
+}
+AEJ_HD inline long long jd_pos(unsigned long long s) { return (long long)(s >> 10); }
+AEJ_HD inline int jd_k(unsigned long long s) { return (int)((s >> 6) & 7); }
+AEJ_HD inline int jd_z(unsigned long long s) { return (int)(s & 63); }
+AEJ_HD inline int jd_err(unsigned long long s) { return (int)((s >> 9) & 1); }
+
+AEJ_HD inline unsigned jd_bswap(unsigned v) { return (v >> 24) | ((v >> 8) & 0xFF00u) | ((v << 8) & 0xFF0000u) | (v << 24); }
+
+// big-endian bit window over a 4-byte-aligned byte stream
+struct JdBits {
+    const unsigned *w;
+    long long cw;
+    unsigned a, b;
+    AEJ_HD explicit JdBits(const unsigned char *base) : w(reinterpret_cast<const unsigned *>(base)), cw(-2), a(0), b(0) {}      // -2: the first peek loads both words
+    AEJ_HD inline unsigned peek32(long long pos)       // the 32 bits from bit `pos` on
+    {
+        const long long wi = pos >> 5;
+        if (wi != cw) {
+            if (wi == cw + 1) { a = b; b = jd_bswap(w[wi + 1]); }
+            else { a = jd_bswap(w[wi]); b = jd_bswap(w[wi + 1]); }
+            cw = wi;
+        }
+        const int sh = (int)(pos & 31);
+        return sh ? (a << sh) | (b >> (32 - sh)) : a;
+    }
+};
+
+AEJ_HD inline bool jd_huff(const aej_jpegdec_huff &h, unsigned win, int &len, int &sym)
+{
+    const unsigned e = h.lut[win >> 23];
+    if (e) { len = (int)(e >> 8); sym = (int)(e & 255); return true; }
+    for (int l = 10; l <= 16; l++) {
+        const int code = (int)(win >> (32 - l));
+        if (code <= h.maxcode[l]) { len = l; sym = h.vals[(h.valoff[l] + code) & 255]; return true; }
+    }
+    return false;
+}
+
+// natural index of zigzag position z (z < 64)
+AEJ_HD inline int jd_natural(int z)
+{
+    const unsigned char zz[64] = { 0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14,
+                                   21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46,
+                                   53, 60, 61, 54, 47, 55, 62, 63 };
+    return zz[z];
+}
+
+AEJ_HD inline int jd_comp(const aej_jpegdec_desc &d, int k) { return d.ncomp == 1 ? 0 : (k < d.hs * d.vs ? 0 : k - d.hs * d.vs + 1); }
+
+enum { kJdRunStop = 0, kJdRunOutOfBits = 1, kJdRunBadCode = 2, kJdRunPast63 = 3, kJdRunBadDc = 4, kJdRunDone = 5 };
+
+// Decode symbols from state (pos, k, z) while pos < stop; no symbol may end past seg_end.  Counts the blocks started and sums their
+// DC differences per component.  kWrite: also stores the coefficients (natural order) of blocks [0, seg_blocks) of the segment into
+// coef (its block 0), with DC predictors pred[], `next` being the index of the next block to start; stops once every block is done.
+template <bool kWrite>
+AEJ_HD inline int jd_run(const aej_jpegdec_desc &d, JdBits &br, long long &pos, int &k, int &z, long long stop, long long seg_end,
+                         int &nstart, int dc[3], short *coef, long long &next, long long seg_blocks, int pred[3])
+{
+    const int bpm = d.blocks_per_mcu;
+    while (pos < stop) {
+        if (kWrite && z == 0 && next >= seg_blocks) return kJdRunDone;
+        const int c = jd_comp(d, k);
+        const aej_jpegdec_huff &h = z == 0 ? d.dc[c] : d.ac[c];
+        const unsigned win = br.peek32(pos);
+        int len, sym;
+        if (!jd_huff(h, win, len, sym)) return kJdRunBadCode;
+        const int sz = z == 0 ? sym : (sym & 15);
+        if (z == 0 && sym > 11) return kJdRunBadDc;
+        if (pos + len + sz > seg_end) return kJdRunOutOfBits;
+        int v = 0;
+        if (sz) {
+            const unsigned bits = (win << len) >> (32 - sz);
+            v = bits < (1u << (sz - 1)) ? (int)bits - (1 << sz) + 1 : (int)bits;
+        }
+        pos += len + sz;
+        if (z == 0) {
+            nstart++;
+            dc[c] += v;
+            if (kWrite) {
+                pred[c] += v;
+                coef[next * 64] = (short)pred[c];
+                next++;
+            }
+            z = 1;
+        } else {
+            const int r = sym >> 4;
+            if (sz) {
+                if (z + r > 63) return kJdRunPast63;
+                z += r;
+                if (kWrite) {
+                    const long long cur = next - 1;
+                    if (cur >= 0 && cur < seg_blocks) coef[cur * 64 + jd_natural(z)] = (short)v;
+                }
+                z++;
+            } else if (r == 15) {
+                if (z + 16 > 64) return kJdRunPast63;
+                z += 16;
+            } else {
+                z = 64;
+            }
+        }
+        if (z >= 64) {
+            z = 0;
+            k = k + 1 == bpm ? 0 : k + 1;
+        }
+    }
+    return kJdRunStop;
+}
+
+// ---- reconstruction arithmetic (libjpeg-turbo's islow IDCT, range limit, fancy up-sampling, YCbCr -> RGB) ----------------------------
+AEJ_HD inline long long jd_descale(long long x, int n) { return (x + (1LL << (n - 1))) >> n; }
+
+template <bool kPass1>
+AEJ_HD inline void jd_idct8(long long *d, int s)
+{
+    const int n = kPass1 ? 11 : 18;
+    long long z2 = d[2 * s], z3 = d[6 * s], z1 = (z2 + z3) * 4433;
+    long long t2 = z1 - z3 * 15137, t3 = z1 + z2 * 6270;
+    long long t0 = (d[0] + d[4 * s]) * 8192, t1 = (d[0] - d[4 * s]) * 8192;
+    long long t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+    t0 = d[7 * s]; t1 = d[5 * s]; t2 = d[3 * s]; t3 = d[s];
+    z1 = t0 + t3; z2 = t1 + t2; z3 = t0 + t2;
+    long long z4 = t1 + t3, z5 = (z3 + z4) * 9633;
+    t0 *= 2446; t1 *= 16819; t2 *= 25172; t3 *= 12299;
+    z1 *= -7373; z2 *= -20995; z3 = z3 * -16069 + z5; z4 = z4 * -3196 + z5;
+    t0 += z1 + z3; t1 += z2 + z4; t2 += z2 + z3; t3 += z1 + z4;
+    d[0] = jd_descale(t10 + t3, n); d[7 * s] = jd_descale(t10 - t3, n);
+    d[s] = jd_descale(t11 + t2, n); d[6 * s] = jd_descale(t11 - t2, n);
+    d[2 * s] = jd_descale(t12 + t1, n); d[5 * s] = jd_descale(t12 - t1, n);
+    d[3 * s] = jd_descale(t13 + t0, n); d[4 * s] = jd_descale(t13 - t0, n);
+}
+
+AEJ_HD inline unsigned char jd_range_limit(long long x)      // libjpeg's masked table: wraps as the decoder's does
+{
+    const int m = (int)(x & 1023);
+    return (unsigned char)(m < 128 ? m + 128 : m < 512 ? 255 : m < 896 ? 0 : m - 896);
+}
+
+// one block: coefficients (natural order) times the quantisers -> 8 x 8 samples at dst (row stride `stride`)
+AEJ_HD inline void jd_idct_block(const short *c, const uint16_t *qt, unsigned char *dst, long long stride)
+{
+    long long d[64];
+    for (int j = 0; j < 64; j++) d[j] = (long long)c[j] * qt[j];
+    for (int col = 0; col < 8; col++) jd_idct8<true>(d + col, 8);
+    for (int r = 0; r < 8; r++) jd_idct8<false>(d + r * 8, 1);
+    for (int r = 0; r < 8; r++)
+        for (int cc = 0; cc < 8; cc++) dst[r * stride + cc] = jd_range_limit(d[r * 8 + cc]);
+}
+
+// chroma sample for output pixel (y, x) from a plane of wc x hc real samples (row stride `stride`); hs, vs: luma sampling factors
+AEJ_HD inline int jd_chroma(const unsigned char *p, long long stride, int hs, int vs, int wc, int hc, int y, int x)
+{
+    if (hs == 1) return p[(long long)y * stride + x];                        // 4:4:4
+    const int j = x >> 1;
+    if (wc <= 2) return p[(long long)(vs == 2 ? y >> 1 : y) * stride + j];  // plain replication
+    if (vs == 1) {                                                          // h2v1 fancy
+        const unsigned char *r = p + (long long)y * stride;
+        if ((x & 1) == 0) return j == 0 ? r[0] : (3 * r[j] + r[j - 1] + 1) >> 2;
+        return j == wc - 1 ? r[j] : (3 * r[j] + r[j + 1] + 2) >> 2;
+    }
+    const int cy = y >> 1, far = (y & 1) ? (cy + 1 < hc ? cy + 1 : hc - 1) : (cy > 0 ? cy - 1 : 0);   // h2v2 fancy
+    const unsigned char *n0 = p + (long long)cy * stride, *n1 = p + (long long)far * stride;
+    const int cs = 3 * n0[j] + n1[j];
+    if ((x & 1) == 0) return j == 0 ? (4 * cs + 8) >> 4 : (3 * cs + 3 * n0[j - 1] + n1[j - 1] + 8) >> 4;
+    return j == wc - 1 ? (4 * cs + 7) >> 4 : (3 * cs + 3 * n0[j + 1] + n1[j + 1] + 7) >> 4;
+}
+
+AEJ_HD inline void jd_rgb(int Y, int cb, int cr, unsigned char *o)
+{
+    cb -= 128; cr -= 128;
+    const int R = Y + ((91881 * cr + 32768) >> 16);
+    const int G = Y + ((-22554 * cb + 32768 - 46802 * cr) >> 16);
+    const int B = Y + ((116130 * cb + 32768) >> 16);
+    o[0] = (unsigned char)(R < 0 ? 0 : R > 255 ? 255 : R);
+    o[1] = (unsigned char)(G < 0 ? 0 : G > 255 ? 255 : G);
+    o[2] = (unsigned char)(B < 0 ? 0 : B > 255 ? 255 : B);
+}
+
+// un-stuffing: what byte p of a scan is (the neighbours decide: a run of 0xFF followed by 0x00 is one data 0xFF)
+enum { kJdByteData = 0, kJdByteSkip = 1, kJdByteRst = 2, kJdByteEnd = 3 };
+AEJ_HD inline int jd_byte_class(const unsigned char *s, long long n, long long p)
+{
+    const int b = s[p];
+    if (b == 0xFF) return (p + 1 < n && s[p + 1] == 0x00) ? kJdByteData : kJdByteSkip;
+    if (p > 0 && s[p - 1] == 0xFF) {
+        if (b == 0x00) return kJdByteSkip;
+        if (b >= 0xD0 && b <= 0xD7) return kJdByteRst;
+        return kJdByteEnd;
+    }
+    return kJdByteData;
+}
+
+}  // namespace aej

@@ -2,6 +2,9 @@
 returns for them -- the standard-JPEG side of the reference's comparison (test/analysis/metrics_comparison.py: YCbCr, 4:2:0, 8 x 8
 blocks, quality 10/25/50/75/90).
 
+``standard_jpeg_decode_many`` reads such files back -- any baseline file, not only this library's -- on the device, pixel-identical to
+``Image.open(file).convert("RGB")`` (csrc/jpegdec.hip, ``aej_jpegdec_*``).
+
 The files are byte-identical to Pillow's with libjpeg-turbo (JFIF 1.01, Annex K quantisation and Huffman tables, islow DCT, no restart
 markers) and the decoded pixels equal ``np.asarray(Image.open(file).convert("RGB"))``.  Colour, down-sampling and DCT run once per image
 and every requested quality reuses them (csrc/jfif.hip, ``aej_jfif_*`` in include/aej.h).  Images are uint8, or float32 in [0, 1]
@@ -145,3 +148,74 @@ def standard_jpeg_batch(x, qualities: Sequence[int], device: int = 0):
     ctx = get_context(device)
     enc = _Encoded(ctx, _to_u8(ctx, x), list(qualities), False)
     return np.ascontiguousarray(enc.lengths.T.astype(np.int64)), enc.decoded()
+
+
+def parse_header(data, index: int = 0):
+    """aej_jpegdec_parse_host: the JpegDecDesc of one file's markers (host only).  Raises NotImplementedError for a valid file outside
+    the supported set and ValueError for a malformed header, both naming the file index."""
+    from ._lib import AEJ_ERR_UNSUPPORTED, JpegDecDesc, load_library
+    lib = load_library()
+    mv = memoryview(data).cast("B")
+    buf = (ctypes.c_uint8 * len(mv)).from_buffer_copy(mv) if len(mv) else (ctypes.c_uint8 * 1)()
+    d, msg = JpegDecDesc(), ctypes.create_string_buffer(256)
+    rc = lib.aej_jpegdec_parse_host(ctypes.addressof(buf), len(mv), ctypes.addressof(d), ctypes.addressof(msg), 256)
+    if rc == AEJ_ERR_UNSUPPORTED:
+        raise NotImplementedError(f"file {index}: {msg.value.decode()}")
+    if rc != 0:
+        raise ValueError(f"file {index}: {msg.value.decode()}")
+    return d
+
+
+def standard_jpeg_decode_many(files, device: int = 0) -> list:
+    """Decode baseline JPEG files on the device: -> list of uint8 [H_i, W_i, 3] tensors (views into one packed allocation), in input
+    order, on the context of the current stream; element i equals ``np.asarray(Image.open(io.BytesIO(files[i])).convert("RGB"))``.
+    files: a sequence of bytes-like .jpg contents, of any sizes and of the supported layouts mixed (4:2:0, 4:2:2, 4:4:4, grey).  Every
+    header is read on the host before any device work (NotImplementedError / ValueError naming the file); the scans cross in one copy
+    and are un-stuffed, Huffman-decoded and reconstructed on the device.  A file whose scan is malformed raises ValueError naming its
+    index and the reason (the per-file status words are read back once).  There is no CPU fallback."""
+    from ._lib import JPEGDEC_STATUS, JpegDecDesc
+    files = list(files)
+    if not files:
+        raise ValueError("standard_jpeg_decode_many needs at least one file")
+    n = len(files)
+    descs = (JpegDecDesc * n)()
+    views = []
+    for i, f in enumerate(files):
+        descs[i] = parse_header(f, i)
+        views.append(memoryview(f).cast("B"))
+    ctx = get_context(device)
+    t, lib = ctx.torch, ctx.lib
+    scan_off, out_off = np.zeros(n, np.int64), np.zeros(n, np.int64)
+    pos = opos = 0
+    for i, d in enumerate(descs):
+        scan_off[i], out_off[i] = pos, opos
+        pos += (d.scan_length + 15) // 16 * 16
+        opos += d.width * d.height * 3
+    stage = ctx.pinned(max(pos, 1))
+    host = stage.numpy()
+    for i, d in enumerate(descs):
+        host[scan_off[i]:scan_off[i] + d.scan_length] = np.frombuffer(views[i], np.uint8, d.scan_length, d.scan_offset)
+    scans = ctx.empty((max(pos, 1),), t.uint8)
+    scans.copy_(stage[:max(pos, 1)], non_blocking=True)
+    out = ctx.empty((max(opos, 1),), t.uint8)
+    status = ctx.empty((n,), t.int32)
+    nws = int(lib.aej_jpegdec_workspace_bytes(ctx.handle, ctypes.addressof(descs), n))
+    if nws == 0:
+        raise ValueError("descriptors the library refuses")
+    ws = ctx.workspace(nws)
+    ctx.check(lib.aej_jpegdec_batch(ctx.handle, ctypes.addressof(descs), n, scans.data_ptr(), ctypes.c_uint64(scans.numel()),
+                                    scan_off.ctypes.data, out.data_ptr(), ctypes.c_uint64(out.numel()), out_off.ctypes.data,
+                                    status.data_ptr(), ws.data_ptr(), ctypes.c_uint64(nws)))
+    st = status.cpu().numpy()                    # the one read-back of the per-file status words
+    for i in np.flatnonzero(st):
+        code = int(st[i])
+        reason = JPEGDEC_STATUS[code] if 0 <= code < len(JPEGDEC_STATUS) else f"status {code}"
+        raise ValueError(f"file {int(i)}: {reason}")
+    return [out[int(o):int(o) + d.width * d.height * 3].view(d.height, d.width, 3) for o, d in zip(out_off, descs)]
+
+
+def decode_sync_rounds(device: int = 0) -> int:
+    """Sync rounds of the Huffman decode that the last standard_jpeg_decode_many on this device's current stream ran
+    (aej_jpegdec_sync_rounds): 0 when every segment fit one subsequence."""
+    ctx = get_context(device)
+    return int(ctx.lib.aej_jpegdec_sync_rounds(ctx.handle))

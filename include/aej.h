@@ -127,7 +127,8 @@ AEJ_API int aej_get_schedule_host(aej_ctx *ctx, int batch, int H, int W, int32_t
  *   "dct_multi"             0 | 1 (1)          1: calls of at most 8 Mpx run the DCTs of block sizes 4 .. 64 as ONE launch (latency), 0: one launch per size
  *   "sobel_xcd"             0 | 1 (1)          1: each XCD gets a contiguous range of the register Sobel kernel's tiles (0: round-robin)
  *   "sub_chain"             -1..3 (-1)         which stage of the previously enqueued part a part's colour stage waits for: 0 none, 1 colour,
- *                                              2 blur, 3 Sobel; -1 = 1 */
+ *                                              2 blur, 3 Sobel; -1 = 1
+ *   "jpegdec_subseq_bits"   32..1048576 (2048) bits per subsequence of aej_jpegdec_batch's self-synchronising Huffman decode */
 AEJ_API int aej_set_option(aej_ctx *ctx, const char *name, int64_t value);
 AEJ_API int aej_get_option(aej_ctx *ctx, const char *name, int64_t *value_host);
 /* The two halves of aej_encode_batch / aej_encode_batch_u8 (same arguments; rgb_is_u8 selects the ingest): _begin enqueues the whole
@@ -383,6 +384,59 @@ AEJ_API int aej_jfif_encode_batch(aej_ctx *ctx, const uint8_t *rgb, int batch, i
                                   uint64_t out_capacity, int64_t *offsets, int64_t *lengths, uint64_t *total_host, void *workspace,
                                   uint64_t workspace_bytes);
 AEJ_API int aej_jfif_recon_batch(aej_ctx *ctx, int batch, int H, int W, int n_q, uint8_t *rgb_out, void *workspace, uint64_t workspace_bytes);
+
+/* ---- baseline JPEG files decoded on the device (standard_jpeg_decode_many) ---------------------------------------------------------
+ * Pixel-identical to PIL.Image.open(file).convert("RGB") with libjpeg-turbo (islow IDCT, fancy up-sampling, fixed-point YCbCr -> RGB).
+ * Supported: SOF0 / SOF1 with 8-bit samples, one interleaved scan, 1 component (grey, replicated into RGB) or 3 taken as YCbCr with luma
+ * sampling 1x1, 2x1 or 2x2 and chroma 1x1, any DHT (codes up to 16 bits), 8- and 16-bit DQT, DRI / RSTn.  APPn, COM and EXIF are skipped
+ * (orientation is ignored, as Image.open ignores it); the tables in force at SOS apply.
+ *
+ * aej_jpegdec_parse_host: HOST only.  Reads the markers SOI .. SOS of one file into *desc.  Returns 0; AEJ_ERR_UNSUPPORTED for a valid
+ *   file outside the supported set (progressive, arithmetic, 12-bit, 2 or 4 components, Adobe transform 0, 'R','G','B' ids without JFIF,
+ *   other sampling factors, DNL, a first scan that lists fewer components than the frame); AEJ_ERR_ARG for a malformed header (missing
+ *   SOF / SOS, truncated segment, over-subscribed or undefined Huffman table, undefined quantisation table).  msg (may be NULL) gets the
+ *   reason.  scan_offset is the first byte after the SOS segment; scan_length runs to the end of the file (the device stops at the
+ *   first marker that is not RSTn).
+ * aej_jpegdec_batch: n files.  descs_host [n] from the parser; scans: device bytes, the scan of file i at scan_offsets_host[i] (its
+ *   scan_length bytes must lie inside scans_bytes); out: device uint8, image i as [height][width][3] at out_offsets_host[i] (inside
+ *   out_bytes); status: device [n] int32, AEJ_JPEGDEC_*.  A bad file leaves the others alone and never reads outside its own scan.  The
+ *   Huffman decode of a segment without restart markers is split into subsequences of "jpegdec_subseq_bits" bits (aej_set_option) that
+ *   decode from a guessed state and are re-run until each one's entry state equals its predecessor's exit state; the call reads back one
+ *   word every few of those rounds and returns after the last round has run.  Workspace: aej_jpegdec_workspace_bytes(ctx, descs_host, n)
+ *   bytes (it depends on the context's subsequence length), 256-byte aligned.
+ * aej_jpegdec_sync_rounds: sync rounds the last aej_jpegdec_batch of the context ran (0 when no segment needed more than one subsequence). */
+enum {
+    AEJ_JPEGDEC_OK = 0, AEJ_JPEGDEC_TRUNCATED = 1 /* the scan ends before the last MCU */, AEJ_JPEGDEC_BAD_CODE = 2 /* not in the table */,
+    AEJ_JPEGDEC_RUN_PAST_63 = 3 /* an AC run beyond the block */, AEJ_JPEGDEC_BAD_DC = 4 /* DC category above 11 */,
+    AEJ_JPEGDEC_BAD_RESTART = 5 /* a restart marker out of sequence, missing or unexpected */
+};
+typedef struct aej_jpegdec_huff {
+    uint16_t lut[512];         /* 9-bit look-ahead: (code length << 8) | symbol; 0 = the code is longer than 9 bits */
+    int32_t maxcode[18];       /* [l]: largest code of length l (1..16), -1 if none */
+    int32_t valoff[18];        /* [l]: symbol of code c of length l is vals[valoff[l] + c] */
+    uint8_t vals[256];
+} aej_jpegdec_huff;
+typedef struct aej_jpegdec_desc {
+    int32_t width, height;
+    int32_t ncomp;             /* 1 or 3 */
+    int32_t hs, vs;            /* luma sampling factors (1x1, 2x1, 2x2; 1x1 for grey) */
+    int32_t mcux, mcuy;        /* MCUs per row / column of the scan (grey: one block per MCU) */
+    int32_t blocks_per_mcu;    /* hs * vs + 2, or 1 */
+    int32_t restart_interval;  /* MCUs per restart segment, 0 = none */
+    int32_t n_segments;        /* restart segments of the scan */
+    int32_t sof;               /* 0xC0 or 0xC1 */
+    int32_t precision16;       /* 1 when a quantisation table in force is 16-bit */
+    uint8_t comp_id[4], comp_h[4], comp_v[4], comp_tq[4];    /* frame components (as Pillow's im.layer) */
+    uint16_t qt[3][64];        /* quantisation table of each component, natural (row-major) order */
+    aej_jpegdec_huff dc[3], ac[3];      /* Huffman tables each component of the scan uses */
+    int64_t scan_offset, scan_length;
+} aej_jpegdec_desc;
+AEJ_API int aej_jpegdec_parse_host(const uint8_t *data_host, uint64_t nbytes, aej_jpegdec_desc *desc_host, char *msg, int msg_capacity);
+AEJ_API uint64_t aej_jpegdec_workspace_bytes(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n);
+AEJ_API int aej_jpegdec_batch(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const uint8_t *scans, uint64_t scans_bytes,
+                              const int64_t *scan_offsets_host, uint8_t *out, uint64_t out_bytes, const int64_t *out_offsets_host,
+                              int32_t *status, void *workspace, uint64_t workspace_bytes);
+AEJ_API int64_t aej_jpegdec_sync_rounds(aej_ctx *ctx);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,87 @@
+"""Baseline-JPEG decode timing: 64 x 4K Pillow files (quality 75, 4:2:0) through csrc/jpegdec.hip, written (a) without restart
+markers -- Pillow's default, decoded by the self-synchronising subsequences -- and (b) with restart_marker_rows=1, against Pillow
+decoding them on a thread pool and uploading its pixels.
+
+    python tools/bench_jpeg_decode.py [--batch 64] [--repeats 3] [--threads 16] [--subseq-bits N] [--out FILE]
+
+"gpu" is standard_jpeg_decode_many: host header parsing, one copy of the scans, every device stage, the per-file status read-back;
+it ends with device uint8 [H, W, 3] tensors.  "pillow" is np.asarray(Image.open(buf).convert("RGB")) per file on --threads threads, then
+one stacked host-to-device copy of the pixels.  Every time is a host clock around work that ends in a device synchronise, after one
+warm-up; the median of --repeats is reported, as gigapixels per second.  The GPU's pixels are checked against Pillow's for every file
+before timing.  Prints one JSON line (and writes it to --out) with the sync rounds of each case.
+"""
+import argparse
+import io
+import json
+import os
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+from PIL import Image  # noqa: E402
+
+import adaptive_edge_aware_jpeg_amd as A  # noqa: E402
+from adaptive_edge_aware_jpeg_amd import standard_jpeg as S  # noqa: E402
+
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from bench_jfif import H, W, images, timed  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--subseq-bits", type=int, default=0, help="jpegdec_subseq_bits (0: the library's default)")
+    ap.add_argument("--out")
+    a = ap.parse_args()
+    x = images(a.batch)
+    ctx = A._lib.get_context(0)
+    if a.subseq_bits:
+        ctx.set_option("jpegdec_subseq_bits", a.subseq_bits)
+    gp = a.batch * H * W / 1e9
+    res = {"batch": a.batch, "H": H, "W": W, "quality": 75, "subseq_bits": ctx.get_option("jpegdec_subseq_bits"),
+           "pillow_threads": a.threads, "cases": {}}
+    pool = ThreadPoolExecutor(a.threads)
+
+    def save(i, opts):
+        buf = io.BytesIO()
+        Image.fromarray(x[i]).save(buf, "JPEG", quality=75, **opts)
+        return buf.getvalue()
+
+    def pil_load(f):
+        return np.asarray(Image.open(io.BytesIO(f)).convert("RGB"))
+
+    for name, opts in (("no_restarts", {}), ("restart_rows_1", {"restart_marker_rows": 1})):
+        files = list(pool.map(lambda i: save(i, opts), range(a.batch)))
+        got = A.standard_jpeg_decode_many(files)
+        rounds = S.decode_sync_rounds()
+        for f, g in zip(files, got):
+            assert np.array_equal(g.cpu().numpy(), pil_load(f)), name
+        del got
+        tg = timed(lambda: A.standard_jpeg_decode_many(files), a.repeats)
+
+        def pillow():
+            px = np.stack(list(pool.map(pil_load, files)))
+            return torch.from_numpy(px).to("cuda:0")
+        tp = timed(pillow, a.repeats)
+        mb = sum(len(f) for f in files) / 1e6
+        res["cases"][name] = {"file_mb": mb, "sync_rounds": rounds, "gpu_ms": tg * 1e3, "gpu_gps": gp / tg, "pillow_upload_ms": tp * 1e3,
+                              "pillow_upload_gps": gp / tp, "speedup": tp / tg}
+        print(f"{name}: {mb:.1f} MB of files, {rounds} sync rounds; GPU {tg * 1e3:.1f} ms ({gp / tg:.2f} GP/s), Pillow on {a.threads} threads "
+              f"+ upload {tp * 1e3:.1f} ms ({gp / tp:.2f} GP/s): x{tp / tg:.2f}", flush=True)
+    pool.shutdown()
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
