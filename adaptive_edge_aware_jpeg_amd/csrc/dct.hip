@@ -46,6 +46,13 @@ __device__ __forceinline__ int zigzag_pos(int r, int c)
 // The quantiser (quantise_f64 / quantise_f32 / quantise) lives in aej_quant.h, shared with requant.hip.  Its float32 path holds for
 // quantisers up to (1 << 22) and quotients below 262144.0f (2^18); the kernels below test |y| < 131072.0f (2^17) per row / leaf, which
 // with q >= 1 keeps every quotient inside that range.
+// The float64 fallbacks take the quantiser from the integer table (qm_exact), never from a float copy: a float holds every integer only up
+// to 2^24 (2^24 + 1 becomes 2^24), and rint(y / q) depends on the exact q -- y = 1.5 (2^24 + 1) quantises to 1, not 2.
+__device__ __forceinline__ int qm_exact(const DctArgs &a, int layer, int ridx)      // (selected without indexing the kernel-argument array)
+{
+    const int *qm = layer == 0 ? a.qm[0] : layer == 1 ? a.qm[1] : a.qm[2];
+    return qm ? qm[ridx] : 1;
+}
 
 // Work items of one block size are the concatenation, over planes (b, l), of that plane's Morton-ordered leaf list.
 // s_pref[p] = number of items in planes < p (built once per workgroup by wave 0); an item index is mapped back to
@@ -341,10 +348,8 @@ __device__ __forceinline__ void dct4_body(const Geom &g, const QtGeom &q, const 
 #pragma unroll
             for (int c = 0; c < 4; c++) slab[zz[c]] = ki[c];
         } else {
-            slab[zz[0]] = quantise_f64(y[0], (int)qf.x);
-            slab[zz[1]] = quantise_f64(y[1], (int)qf.y);
-            slab[zz[2]] = quantise_f64(y[2], (int)qf.z);
-            slab[zz[3]] = quantise_f64(y[3], (int)qf.w);
+#pragma unroll
+            for (int c = 0; c < 4; c++) slab[zz[c]] = quantise_f64(y[c], qm_exact(a, layer, r * 4 + c));
         }
         if (active) {
             const int4 o = reinterpret_cast<const int4 *>(slab)[r];
@@ -484,7 +489,7 @@ __device__ __forceinline__ void dct8_body(const Geom &g, const QtGeom &q, const 
             for (int c = 0; c < 8; c++) slab[zz[c]] = quantise_f32(y[c], qf[c]);
         } else {
 #pragma unroll
-            for (int c = 0; c < 8; c++) slab[zz[c]] = quantise_f64(y[c], (int)qf[c]);
+            for (int c = 0; c < 8; c++) slab[zz[c]] = quantise_f64(y[c], qm_exact(a, layer, j * S + c));
         }
         if (active) {
             const int4 o0 = reinterpret_cast<const int4 *>(slab)[2 * j], o1 = reinterpret_cast<const int4 *>(slab)[2 * j + 1];
@@ -700,7 +705,7 @@ __device__ __forceinline__ void dct16_impl(Dct16Lds &L, const Geom &g, const QtG
             for (int r = 0; r < 4; r++) out_slab[zz[r]] = ki[r];
         } else {
 #pragma unroll
-            for (int r = 0; r < 4; r++) out_slab[zz[r]] = quantise_f64(y[r], (int)qf[r]);
+            for (int r = 0; r < 4; r++) out_slab[zz[r]] = quantise_f64(y[r], qm_exact(a, layer, (4 * gq + r) * S + i));
         }
         // (LDS operations of one wave execute in order: the reads below see this wave's writes, and the next leaf's writes
         // come after these reads)
@@ -945,8 +950,8 @@ __device__ __forceinline__ void dct_mfma_leaves(const Geom &g, const QtGeom &q, 
         dct_load_x<S, NWAVES>(src0, w0, h0, g.tiled, make_int4(cur.plane, cur.x, cur.y, cur.coef), sXb, wave, lane, xo);
         wait_vmem_but<0>();
     }
-    // quantisers of this lane's outputs (as floats: they are < 2^24), kept in registers while consecutive leaves belong to the same
-    // layer (the work lists are ordered by plane, so the layer changes a few hundred times per launch)
+    // quantisers of this lane's outputs (as floats; a slow layer's as the integers' bits, see below), kept in registers while consecutive
+    // leaves belong to the same layer (the work lists are ordered by plane, so the layer changes a few hundred times per launch)
     float qf[TPW][16];
     int q_layer = -1;
     bool q_slow = false;               // some quantiser of the layer is too large for the float32 quantiser (never for the codec's own tables)
@@ -970,6 +975,14 @@ __device__ __forceinline__ void dct_mfma_leaves(const Geom &g, const QtGeom &q, 
                     qf[t][r] = (float)qi;
                 }
             q_slow = __any(qmax > (1 << 22));
+            if (q_slow) {
+                // (never with the codec's own tables) the float64 quantiser needs the exact integer, which a float only holds up to 2^24
+                // (2^24 + 1 -> 2^24): a slow layer keeps the integers' bits, which only its float64 quantiser reads (no skip test)
+#pragma unroll
+                for (int t = 0; t < TPW; t++)
+#pragma unroll
+                    for (int r = 0; r < 16; r++) qf[t][r] = __int_as_float(qm[((wi0 + t * (NT / TPW)) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * S + J0 + li]);
+            }
             q_layer = layer;
             if (S != 128) {                       // rare path: leave no load pending across the prefetch below
 #pragma unroll
@@ -1034,7 +1047,8 @@ __device__ __forceinline__ void dct_mfma_leaves(const Geom &g, const QtGeom &q, 
                 if (WANT_DCT) a.dct_f32[out_base + row * S + J0 + li] = acc[t][r];
                 const float y = acc[t][r], qq = qf[t][r];
                 int v = 0;
-                if (!__all(__builtin_fabsf(y) < 0.499f * qq)) v = slow ? quantise_f64(y, (int)qq) : quantise_f32(y, qq);
+                if (q_slow) v = quantise_f64(y, __float_as_int(qq));
+                else if (!__all(__builtin_fabsf(y) < 0.499f * qq)) v = slow ? quantise_f64(y, (int)qq) : quantise_f32(y, qq);
                 sQ[zigzag_pos<S>(row, J0 + li)] = v;
             }
         lds_barrier();
@@ -1412,8 +1426,9 @@ __global__ __launch_bounds__(kW64Waves * 64, 1) void k_dct64_wave(Geom g, QtGeom
                     const int u = 32 * iu + 8 * (r >> 2) + 4 * lh + (r & 3), v = 32 * jv + li;
                     const float qq = qT[v][u];
                     const int zz = L.zT[v][u];
-                    const bool slow = redo && (L.q_slow[layer] != 0 || __any(!(__builtin_fabsf(y) < 131072.0f)));
-                    const int val = slow ? quantise_f64(y, (int)qq) : quantise_f32(y, qq);
+                    // (the range test holds without redo too: the groups past position 1 024 never set hi_lane's range bit)
+                    const bool slow = L.q_slow[layer] != 0 || __any(!(__builtin_fabsf(y) < 131072.0f));
+                    const int val = slow ? quantise_f64(y, qm_exact(a, layer, u * S + v)) : quantise_f32(y, qq);
                     if (redo || zz >= 1024) a.coeffs[out_base + zz] = val;
                 }
             }
