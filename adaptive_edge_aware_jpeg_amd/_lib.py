@@ -145,6 +145,24 @@ class JpegDecDesc(ctypes.Structure):
                 ("scan_offset", ctypes.c_int64), ("scan_length", ctypes.c_int64)]
 
 
+class JpegProgFrame(ctypes.Structure):
+    """aej_jpegprog_frame (include/aej.h): the frame of a progressive file"""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("ncomp", ctypes.c_int32), ("hs", ctypes.c_int32), ("vs", ctypes.c_int32),
+                ("mcux", ctypes.c_int32), ("mcuy", ctypes.c_int32), ("blocks_per_mcu", ctypes.c_int32), ("sof", ctypes.c_int32),
+                ("precision16", ctypes.c_int32), ("n_scans", ctypes.c_int32), ("n_levels", ctypes.c_int32),
+                ("comp_id", ctypes.c_uint8 * 4), ("comp_h", ctypes.c_uint8 * 4), ("comp_v", ctypes.c_uint8 * 4), ("comp_tq", ctypes.c_uint8 * 4),
+                ("qt", (ctypes.c_uint16 * 64) * 3)]
+
+
+class JpegProgScan(ctypes.Structure):
+    """aej_jpegprog_scan (include/aej.h): one scan of a progressive file, with the Huffman tables in force at its SOS"""
+    _fields_ = [("ncomp", ctypes.c_int32), ("comp", ctypes.c_int32 * 4), ("td", ctypes.c_int32 * 4), ("ta", ctypes.c_int32 * 4),
+                ("ss", ctypes.c_int32), ("se", ctypes.c_int32), ("ah", ctypes.c_int32), ("al", ctypes.c_int32),
+                ("restart_interval", ctypes.c_int32), ("units_x", ctypes.c_int32), ("units_y", ctypes.c_int32),
+                ("n_segments", ctypes.c_int32), ("level", ctypes.c_int32), ("dc", JpegDecHuff * 3), ("ac", JpegDecHuff),
+                ("data_offset", ctypes.c_int64), ("data_length", ctypes.c_int64)]
+
+
 SIGNATURES = {
     "aej_abi_version": (_I, []),
     "aej_create": (_P, [_I, _P]),
@@ -212,6 +230,11 @@ SIGNATURES = {
     "aej_jpegdec_workspace_bytes": (_U64, [_P, _P, _I]),
     "aej_jpegdec_batch": (_I, [_P, _P, _I, _P, _U64, _P, _P, _U64, _P, _P, _P, _U64]),
     "aej_jpegdec_sync_rounds": (_I64, [_P]),
+    "aej_jpegprog_parse_host": (_I, [_P, _U64, _P, _P, _I, _P, _I]),
+    "aej_jpegprog_workspace_bytes": (_U64, [_P, _P, _P, _I]),
+    "aej_jpegprog_batch": (_I, [_P, _P, _P, _I, _P, _U64, _P, _P, _U64, _P, _P, _P, _U64]),
+    "aej_test_jpegprog_coefs": (_I, [_P, _P, _P, _I, _P, _U64, _P, _I, _P, _U64, _P, _P, _U64]),             # include/aej_testing.h (tests only)
+    "aej_test_jpegprog_coefs_host": (_I, [_P, _P, _P, _U64, _I, _P, _U64]),                                 # include/aej_testing.h (tests only)
 }
 
 # status values of aej_inflate_batch / aej_decode_headers (include/aej.h AEJ_INFLATE_* / AEJ_HEADER_*)

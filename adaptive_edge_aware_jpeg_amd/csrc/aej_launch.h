@@ -242,12 +242,43 @@ struct JdBufs {
     JdFile *files; aej_jpegdec_desc *descs; int *last_change;      // one upload: files, descriptors, the "last round that changed" word
     int *cnt; long long *pre, *clean_len; JdSeg *segs; unsigned char *clean; JdSlots sl; short *coef; unsigned char *planes;
 };
+struct JdHuffSrc { bool defined = false; unsigned char bits[17] = {}; unsigned char vals[256] = {}; int count = 0; };      // one DHT table
+bool jd_build_huff(const JdHuffSrc &s, aej_jpegdec_huff &h);
 int jpegdec_parse(const unsigned char *data, unsigned long long n, aej_jpegdec_desc &d, std::string &msg);
 long long jpegdec_layout(const aej_jpegdec_desc *descs, int n, int S, std::vector<JdFile> &files, JdBufSizes &z);
 unsigned long long jpegdec_carve(void *base, int n, const JdBufSizes &z, JdBufs &w);
 hipError_t launch_jpegdec_begin(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, const void *blob_host, unsigned long long blob_bytes,
                                 const unsigned char *scans, int S, int *status);
+hipError_t launch_jpegdec_unstuff(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, const unsigned char *scans, int S, int *status);
+hipError_t launch_jpegdec_recon(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, unsigned char *out);
 hipError_t launch_jpegdec_sync(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, int S, int first_round, int rounds);
 hipError_t launch_jpegdec_finish(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, int S, unsigned char *out, int *status);
+
+}  // namespace aej
+
+// jpegprog.hip: progressive JPEG files decoded on the device (aej_jpegprog_*)
+#include "jpegprog_core.h"
+
+namespace aej {
+struct JpLayout {                      // host-computed layout of one aej_jpegprog_batch; scans ordered by dependency level
+    std::vector<JdFile> sfiles, ffiles;                // one un-stuffing stream per scan; one reconstruction entry per file
+    std::vector<aej_jpegdec_desc> sdescs, fdescs;      // per scan: segments, unit counts, Huffman tables; per file: what k_jd_idct / k_jd_rgb read
+    std::vector<JpScan> scans;
+    std::vector<int> src;                              // scans[t] is the caller's scan src[t]
+    std::vector<JpItem> items;
+    std::vector<long long> level_items;                // items of level l: [level_items[l], level_items[l + 1])
+    JdBufSizes sz{}, fz{};                             // totals over the scans (chunks, segs, slots, clean) and the files (blocks, planes, px)
+    int n_levels = 0;
+};
+struct JpBufs { void *blob; JdBufs s, f; JpScan *scans; JpItem *items; int *sstatus; };
+int jpegprog_parse(const unsigned char *data, unsigned long long n, aej_jpegprog_frame &f, std::vector<aej_jpegprog_scan> &scans, std::string &msg);
+bool jpegprog_layout(const aej_jpegprog_frame *frames, const aej_jpegprog_scan *scans, int n, JpLayout &y);
+unsigned long long jpegprog_blob(const JpLayout &y, std::vector<unsigned char> *out);
+unsigned long long jpegprog_carve(void *base, const JpLayout &y, JpBufs &w);
+hipError_t launch_jpegprog_entropy(hipStream_t st, const JpLayout &y, const JpBufs &w, const void *blob_host, unsigned long long blob_bytes,
+                                   const unsigned char *data, int n_levels, int *status);
+hipError_t launch_jpegprog_recon(hipStream_t st, const JpLayout &y, const JpBufs &w, unsigned char *out);
+int jpegprog_coefs_host(const aej_jpegprog_frame &frame, const aej_jpegprog_scan *scans, const unsigned char *file, unsigned long long nbytes,
+                        int n_levels, short *coef, unsigned long long coef_blocks);
 
 }  // namespace aej

@@ -2199,3 +2199,94 @@ extern "C" int64_t aej_jpegdec_sync_rounds(aej_ctx *ctx)
     if (!ctx) return AEJ_ERR_ARG;
     return ctx->jd_sync_rounds;
 }
+
+// ---- progressive JPEG files decoded on the device (jpegprog.hip) ----------------------------------------------------------------------
+extern "C" int aej_jpegprog_parse_host(const uint8_t *data_host, uint64_t nbytes, aej_jpegprog_frame *frame_host, aej_jpegprog_scan *scans_host,
+                                       int scan_capacity, char *msg, int msg_capacity)
+{
+    if (!frame_host) return AEJ_ERR_ARG;
+    std::string m;
+    std::vector<aej_jpegprog_scan> scans;
+    int rc = jpegprog_parse(data_host, nbytes, *frame_host, scans, m);
+    if (rc == 0 && scans_host) {
+        if (scan_capacity < (int)scans.size()) { rc = AEJ_ERR_CAPACITY; m = "scan capacity below the file's " + std::to_string(scans.size()) + " scans"; }
+        else memcpy(scans_host, scans.data(), sizeof(aej_jpegprog_scan) * scans.size());
+    }
+    if (msg && msg_capacity > 0) {
+        const size_t k = std::min(m.size(), (size_t)msg_capacity - 1);
+        memcpy(msg, m.data(), k);
+        msg[k] = 0;
+    }
+    return rc;
+}
+
+extern "C" uint64_t aej_jpegprog_workspace_bytes(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n)
+{
+    JpLayout y;
+    if (!ctx || !jpegprog_layout(frames_host, scans_host, n, y)) return 0;
+    JpBufs w;
+    return jpegprog_carve(nullptr, y, w);
+}
+
+// levels [0, n_levels) of the entropy stage, then either the reconstruction into `out` or (tests) a copy of the coefficients
+static int jpegprog_run(aej_ctx *ctx, const char *fn, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
+                        const uint8_t *data, uint64_t data_bytes, const int64_t *data_offsets_host, int n_levels, uint8_t *out, uint64_t out_bytes,
+                        const int64_t *out_offsets_host, int16_t *coef_out, uint64_t coef_blocks, int32_t *status, void *workspace,
+                        uint64_t workspace_bytes)
+{
+    if (!ctx) return AEJ_ERR_ARG;
+    if (call_in_flight(ctx)) return fail(ctx, AEJ_ERR_STATE, "%s between aej_encode_batch_begin and aej_encode_batch_end", fn);
+    JpLayout y;
+    if (!jpegprog_layout(frames_host, scans_host, n, y))
+        return fail(ctx, AEJ_ERR_ARG, "%s: no files, or descriptors aej_jpegprog_parse_host did not write", fn);
+    if (!data || !data_offsets_host || !status || !workspace || (!out && !coef_out) || (out && !out_offsets_host))
+        return fail(ctx, AEJ_ERR_ARG, "%s: NULL buffer", fn);
+    for (size_t t = 0; t < y.scans.size(); t++) {
+        const long long so = data_offsets_host[y.src[t]];
+        if (so < 0 || (uint64_t)so + (uint64_t)y.sfiles[t].scan_len > data_bytes)
+            return fail(ctx, AEJ_ERR_ARG, "%s: scan %d: bytes outside the data buffer", fn, y.src[t]);
+        y.sfiles[t].scan_off = so;
+    }
+    for (int i = 0; out && i < n; i++) {
+        const long long oo = out_offsets_host[i], ob = (long long)frames_host[i].width * frames_host[i].height * 3;
+        if (oo < 0 || (uint64_t)oo + (uint64_t)ob > out_bytes) return fail(ctx, AEJ_ERR_ARG, "%s: file %d: image outside the output", fn, i);
+        y.ffiles[i].out_off = oo;
+    }
+    if (coef_out && (uint64_t)y.fz.blocks > coef_blocks) return fail(ctx, AEJ_ERR_CAPACITY, "%s: %lld coefficient blocks, room for %llu", fn, y.fz.blocks, (unsigned long long)coef_blocks);
+    JpBufs w;
+    const unsigned long long need = jpegprog_carve(workspace, y, w);
+    if (need > workspace_bytes) return fail(ctx, AEJ_ERR_CAPACITY, "workspace too small: need %llu bytes, got %llu", need, (unsigned long long)workspace_bytes);
+    std::vector<unsigned char> blob;
+    jpegprog_blob(y, &blob);
+    AEJ_HIP_CHECK(hipSetDevice(ctx->device));
+    AEJ_HIP_CHECK(launch_jpegprog_entropy(ctx->stream, y, w, blob.data(), blob.size(), data, n_levels, status));
+    if (out) AEJ_HIP_CHECK(launch_jpegprog_recon(ctx->stream, y, w, out));
+    if (coef_out) AEJ_HIP_CHECK(hipMemcpyAsync(coef_out, w.f.coef, (size_t)y.fz.blocks * 128, hipMemcpyDeviceToDevice, ctx->stream));
+    AEJ_HIP_CHECK(hipStreamSynchronize(ctx->stream));         // keeps `blob` alive until its upload has run
+    return 0;
+}
+
+extern "C" int aej_jpegprog_batch(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
+                                  const uint8_t *data, uint64_t data_bytes, const int64_t *data_offsets_host, uint8_t *out, uint64_t out_bytes,
+                                  const int64_t *out_offsets_host, int32_t *status, void *workspace, uint64_t workspace_bytes)
+{
+    if (!out) return ctx ? fail(ctx, AEJ_ERR_ARG, "%s: NULL buffer", __func__) : AEJ_ERR_ARG;
+    return jpegprog_run(ctx, __func__, frames_host, scans_host, n, data, data_bytes, data_offsets_host, 1 << 30, out, out_bytes, out_offsets_host,
+                        nullptr, 0, status, workspace, workspace_bytes);
+}
+
+extern "C" int aej_test_jpegprog_coefs(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
+                                       const uint8_t *data, uint64_t data_bytes, const int64_t *data_offsets_host, int n_levels,
+                                       int16_t *coef_out, uint64_t coef_blocks, int32_t *status, void *workspace, uint64_t workspace_bytes)
+{
+    if (!coef_out) return ctx ? fail(ctx, AEJ_ERR_ARG, "%s: NULL buffer", __func__) : AEJ_ERR_ARG;
+    return jpegprog_run(ctx, __func__, frames_host, scans_host, n, data, data_bytes, data_offsets_host, n_levels, nullptr, 0, nullptr, coef_out,
+                        coef_blocks, status, workspace, workspace_bytes);
+}
+
+extern "C" int aej_test_jpegprog_coefs_host(const aej_jpegprog_frame *frame_host, const aej_jpegprog_scan *scans_host, const uint8_t *file_host,
+                                            uint64_t nbytes, int n_levels, int16_t *coef_out_host, uint64_t coef_blocks)
+{
+    if (!frame_host || !scans_host || !file_host || !coef_out_host) return AEJ_ERR_ARG;
+    return jpegprog_coefs_host(*frame_host, scans_host, file_host, nbytes, n_levels, coef_out_host, coef_blocks);
+}

@@ -378,9 +378,6 @@ __global__ __launch_bounds__(kJdThreads) void k_jd_rgb(const JdFile *__restrict_
 }
 
 // ---- host: the header parser ---------------------------------------------------------------------------------------------------------
-namespace {
-struct JdHuffSrc { bool defined = false; unsigned char bits[17] = {}; unsigned char vals[256] = {}; int count = 0; };
-
 // libjpeg's jpeg_make_d_derived_tbl: canonical codes, over-subscription check, then the decode tables
 bool jd_build_huff(const JdHuffSrc &s, aej_jpegdec_huff &h)
 {
@@ -417,7 +414,6 @@ bool jd_build_huff(const JdHuffSrc &s, aej_jpegdec_huff &h)
         }
     return true;
 }
-}  // namespace
 
 int jpegdec_parse(const unsigned char *b, unsigned long long n, aej_jpegdec_desc &d, std::string &msg)
 {
@@ -639,7 +635,17 @@ hipError_t launch_jpegdec_begin(hipStream_t st, int n, const JdBufSizes &z, cons
 {
     hipError_t e = hipMemcpyAsync(w.files, blob_host, blob_bytes, hipMemcpyHostToDevice, st);
     if (e != hipSuccess) return e;
-    if ((e = hipMemsetAsync(status, 0, sizeof(int) * n, st)) != hipSuccess) return e;
+    if ((e = launch_jpegdec_unstuff(st, n, z, w, scans, S, status)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_jd_init, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.slots, w.segs, w.clean, w.sl, S,
+                       w.last_change);
+    return hipGetLastError();
+}
+
+// un-stuffing and restart segments of n streams (files here; the scans of progressive files in jpegprog.hip); zeroes status first
+hipError_t launch_jpegdec_unstuff(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, const unsigned char *scans, int S, int *status)
+{
+    hipError_t e = hipMemsetAsync(status, 0, sizeof(int) * n, st);
+    if (e != hipSuccess) return e;
     if ((e = hipMemsetAsync(w.clean_len, 0, 8 * n, st)) != hipSuccess) return e;
     if (z.chunks > 0) hipLaunchKernelGGL(k_jd_count, dim3(jd_grid(z.chunks)), dim3(kJdThreads), 0, st, w.files, n, z.chunks, scans, w.cnt);
     hipLaunchKernelGGL(k_jd_scan_chunks, dim3(n), dim3(kJdScanThreads), 0, st, w.files, w.descs, w.cnt, w.pre, w.clean_len, w.segs, status);
@@ -647,8 +653,6 @@ hipError_t launch_jpegdec_begin(hipStream_t st, int n, const JdBufSizes &z, cons
         hipLaunchKernelGGL(k_jd_scatter, dim3(jd_grid(z.chunks)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.chunks, scans, w.pre, w.clean,
                            w.segs, status);
     hipLaunchKernelGGL(k_jd_segments, dim3(jd_grid(z.segs)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.segs, w.clean_len, w.segs, S, status);
-    hipLaunchKernelGGL(k_jd_init, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.slots, w.segs, w.clean, w.sl, S,
-                       w.last_change);
     return hipGetLastError();
 }
 
@@ -667,6 +671,12 @@ hipError_t launch_jpegdec_finish(hipStream_t st, int n, const JdBufSizes &z, con
     hipLaunchKernelGGL(k_jd_scan_slots, dim3(n), dim3(kJdScanThreads), 0, st, w.files, w.sl);
     hipLaunchKernelGGL(k_jd_write, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.slots, w.segs, w.clean, w.sl, S, w.coef,
                        status);
+    return launch_jpegdec_recon(st, n, z, w, out);
+}
+
+// coefficients (natural order, MCU order) -> RGB, for n files
+hipError_t launch_jpegdec_recon(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, unsigned char *out)
+{
     hipLaunchKernelGGL(k_jd_idct, dim3(jd_grid(z.blocks)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.blocks, w.coef, w.planes);
     hipLaunchKernelGGL(k_jd_rgb, dim3(jd_grid(z.px)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.px, w.planes, out);
     return hipGetLastError();

@@ -2,8 +2,9 @@
 returns for them -- the standard-JPEG side of the reference's comparison (test/analysis/metrics_comparison.py: YCbCr, 4:2:0, 8 x 8
 blocks, quality 10/25/50/75/90).
 
-``standard_jpeg_decode_many`` reads such files back -- any baseline file, not only this library's -- on the device, pixel-identical to
-``Image.open(file).convert("RGB")`` (csrc/jpegdec.hip, ``aej_jpegdec_*``).
+``standard_jpeg_decode_many`` reads such files back -- any baseline file, not only this library's, and with ``progressive=True`` any
+complete progressive file -- on the device, pixel-identical to ``Image.open(file).convert("RGB")`` (csrc/jpegdec.hip, ``aej_jpegdec_*``;
+csrc/jpegprog.hip, ``aej_jpegprog_*``).
 
 The files are byte-identical to Pillow's with libjpeg-turbo (JFIF 1.01, Annex K quantisation and Huffman tables, islow DCT, no restart
 markers) and the decoded pixels equal ``np.asarray(Image.open(file).convert("RGB"))``.  Colour, down-sampling and DCT run once per image
@@ -166,52 +167,129 @@ def parse_header(data, index: int = 0):
     return d
 
 
-def standard_jpeg_decode_many(files, device: int = 0) -> list:
-    """Decode baseline JPEG files on the device: -> list of uint8 [H_i, W_i, 3] tensors (views into one packed allocation), in input
-    order, on the context of the current stream; element i equals ``np.asarray(Image.open(io.BytesIO(files[i])).convert("RGB"))``.
-    files: a sequence of bytes-like .jpg contents, of any sizes and of the supported layouts mixed (4:2:0, 4:2:2, 4:4:4, grey).  Every
-    header is read on the host before any device work (NotImplementedError / ValueError naming the file); the scans cross in one copy
-    and are un-stuffed, Huffman-decoded and reconstructed on the device.  A file whose scan is malformed raises ValueError naming its
-    index and the reason (the per-file status words are read back once).  There is no CPU fallback."""
-    from ._lib import JPEGDEC_STATUS, JpegDecDesc
-    files = list(files)
-    if not files:
-        raise ValueError("standard_jpeg_decode_many needs at least one file")
-    n = len(files)
-    descs = (JpegDecDesc * n)()
-    views = []
-    for i, f in enumerate(files):
-        descs[i] = parse_header(f, i)
-        views.append(memoryview(f).cast("B"))
-    ctx = get_context(device)
-    t, lib = ctx.torch, ctx.lib
-    scan_off, out_off = np.zeros(n, np.int64), np.zeros(n, np.int64)
-    pos = opos = 0
-    for i, d in enumerate(descs):
-        scan_off[i], out_off[i] = pos, opos
-        pos += (d.scan_length + 15) // 16 * 16
-        opos += d.width * d.height * 3
+def parse_scans(data, index: int = 0):
+    """aej_jpegprog_parse_host: (JpegProgFrame, [JpegProgScan, ...]) of one progressive (SOF2) file, every marker SOI .. EOI walked on
+    the host.  Raises ValueError for a malformed file or a scan script that violates T.81 G.1.1.1 and NotImplementedError for a valid
+    file outside the supported set (an incomplete progression, arithmetic coding, a file that is not progressive, ...), both naming the
+    file index."""
+    from ._lib import AEJ_ERR_UNSUPPORTED, JpegProgFrame, JpegProgScan, load_library
+    lib = load_library()
+    mv = memoryview(data).cast("B")
+    buf = (ctypes.c_uint8 * len(mv)).from_buffer_copy(mv) if len(mv) else (ctypes.c_uint8 * 1)()
+    frame, msg = JpegProgFrame(), ctypes.create_string_buffer(256)
+    rc = lib.aej_jpegprog_parse_host(ctypes.addressof(buf), len(mv), ctypes.addressof(frame), None, 0, ctypes.addressof(msg), 256)
+    scans = (JpegProgScan * max(frame.n_scans, 1))()
+    if rc == 0:
+        rc = lib.aej_jpegprog_parse_host(ctypes.addressof(buf), len(mv), ctypes.addressof(frame), ctypes.addressof(scans), frame.n_scans,
+                                         ctypes.addressof(msg), 256)
+    if rc == AEJ_ERR_UNSUPPORTED:
+        raise NotImplementedError(f"file {index}: {msg.value.decode()}")
+    if rc != 0:
+        raise ValueError(f"file {index}: {msg.value.decode()}")
+    return frame, list(scans)
+
+
+def _stage(ctx, views, pieces):
+    """pieces: [(file, offset, length)] -> (device uint8 buffer holding them 16-byte aligned, int64 offsets), in one pinned copy"""
+    t = ctx.torch
+    off = np.zeros(max(len(pieces), 1), np.int64)
+    pos = 0
+    for k, (_, _, length) in enumerate(pieces):
+        off[k] = pos
+        pos += (length + 15) // 16 * 16
     stage = ctx.pinned(max(pos, 1))
     host = stage.numpy()
-    for i, d in enumerate(descs):
-        host[scan_off[i]:scan_off[i] + d.scan_length] = np.frombuffer(views[i], np.uint8, d.scan_length, d.scan_offset)
-    scans = ctx.empty((max(pos, 1),), t.uint8)
-    scans.copy_(stage[:max(pos, 1)], non_blocking=True)
-    out = ctx.empty((max(opos, 1),), t.uint8)
+    for k, (i, o, length) in enumerate(pieces):
+        host[off[k]:off[k] + length] = np.frombuffer(views[i], np.uint8, length, o)
+    dev = ctx.empty((max(pos, 1),), t.uint8)
+    dev.copy_(stage[:max(pos, 1)], non_blocking=True)
+    return dev, off
+
+
+def _decode_baseline(ctx, idx, parsed, views, out, out_off):
+    """aej_jpegdec_batch over the files idx -> their status words (device int32)"""
+    from ._lib import JpegDecDesc
+    t, lib, n = ctx.torch, ctx.lib, len(idx)
+    descs = (JpegDecDesc * n)(*[parsed[i] for i in idx])
+    scans, scan_off = _stage(ctx, views, [(i, parsed[i].scan_offset, parsed[i].scan_length) for i in idx])
+    oo = np.ascontiguousarray(out_off[idx])
     status = ctx.empty((n,), t.int32)
     nws = int(lib.aej_jpegdec_workspace_bytes(ctx.handle, ctypes.addressof(descs), n))
     if nws == 0:
         raise ValueError("descriptors the library refuses")
     ws = ctx.workspace(nws)
     ctx.check(lib.aej_jpegdec_batch(ctx.handle, ctypes.addressof(descs), n, scans.data_ptr(), ctypes.c_uint64(scans.numel()),
-                                    scan_off.ctypes.data, out.data_ptr(), ctypes.c_uint64(out.numel()), out_off.ctypes.data,
+                                    scan_off.ctypes.data, out.data_ptr(), ctypes.c_uint64(out.numel()), oo.ctypes.data,
                                     status.data_ptr(), ws.data_ptr(), ctypes.c_uint64(nws)))
-    st = status.cpu().numpy()                    # the one read-back of the per-file status words
+    return status
+
+
+def _decode_progressive(ctx, idx, parsed, views, out, out_off):
+    """aej_jpegprog_batch over the files idx -> their status words (device int32)"""
+    from ._lib import JpegProgFrame, JpegProgScan
+    t, lib, n = ctx.torch, ctx.lib, len(idx)
+    frames = (JpegProgFrame * n)(*[parsed[i][0] for i in idx])
+    flat = [(i, s) for i in idx for s in parsed[i][1]]
+    scans = (JpegProgScan * len(flat))(*[s for _, s in flat])
+    data, data_off = _stage(ctx, views, [(i, s.data_offset, s.data_length) for i, s in flat])
+    oo = np.ascontiguousarray(out_off[idx])
+    status = ctx.empty((n,), t.int32)
+    nws = int(lib.aej_jpegprog_workspace_bytes(ctx.handle, ctypes.addressof(frames), ctypes.addressof(scans), n))
+    if nws == 0:
+        raise ValueError("descriptors the library refuses")
+    ws = ctx.workspace(nws)
+    ctx.check(lib.aej_jpegprog_batch(ctx.handle, ctypes.addressof(frames), ctypes.addressof(scans), n, data.data_ptr(),
+                                     ctypes.c_uint64(data.numel()), data_off.ctypes.data, out.data_ptr(), ctypes.c_uint64(out.numel()),
+                                     oo.ctypes.data, status.data_ptr(), ws.data_ptr(), ctypes.c_uint64(nws)))
+    return status
+
+
+def standard_jpeg_decode_many(files, device: int = 0, progressive: bool = False) -> list:
+    """Decode JPEG files on the device: -> list of uint8 [H_i, W_i, 3] tensors (views into one packed allocation), in input
+    order, on the context of the current stream; element i equals ``np.asarray(Image.open(io.BytesIO(files[i])).convert("RGB"))``.
+    files: a sequence of bytes-like .jpg contents, of any sizes and of the supported layouts mixed (4:2:0, 4:2:2, 4:4:4, grey).
+    Baseline files always; with ``progressive=True`` also progressive (SOF2) files whose scans complete every coefficient, mixed
+    freely with baseline ones (csrc/jpegprog.hip, ``aej_jpegprog_*``) -- without it a progressive file is refused as before.  Every
+    header -- of a progressive file every marker up to EOI -- is read on the host before any device work (NotImplementedError /
+    ValueError naming the file); the scans cross in one copy per kind and are un-stuffed, Huffman-decoded and reconstructed on the
+    device.  A file whose scan is malformed raises ValueError naming its index and the reason (the per-file status words are read back
+    once per kind).  There is no CPU fallback."""
+    from ._lib import JPEGDEC_STATUS
+    files = list(files)
+    if not files:
+        raise ValueError("standard_jpeg_decode_many needs at least one file")
+    n = len(files)
+    parsed, views, base_idx, prog_idx = [None] * n, [], [], []
+    for i, f in enumerate(files):
+        try:
+            parsed[i] = parse_header(f, i)
+            base_idx.append(i)
+        except NotImplementedError as e:
+            if "progressive JPEG (SOF2)" not in str(e):
+                raise
+            if not progressive:
+                raise NotImplementedError(f"{e}; pass progressive=True to standard_jpeg_decode_many") from None
+            parsed[i] = parse_scans(f, i)
+            prog_idx.append(i)
+        views.append(memoryview(f).cast("B"))
+    ctx = get_context(device)
+    t = ctx.torch
+    shapes = [(d.height, d.width) for d in (p if i in set(base_idx) else p[0] for i, p in enumerate(parsed))]
+    out_off = np.zeros(n, np.int64)
+    opos = 0
+    for i, (h, w) in enumerate(shapes):
+        out_off[i] = opos
+        opos += h * w * 3
+    out = ctx.empty((max(opos, 1),), t.uint8)
+    st = np.zeros(n, np.int64)
+    for idx, run in ((base_idx, _decode_baseline), (prog_idx, _decode_progressive)):
+        if idx:
+            st[idx] = run(ctx, idx, parsed, views, out, out_off).cpu().numpy()      # the one read-back of the per-file status words
     for i in np.flatnonzero(st):
         code = int(st[i])
         reason = JPEGDEC_STATUS[code] if 0 <= code < len(JPEGDEC_STATUS) else f"status {code}"
         raise ValueError(f"file {int(i)}: {reason}")
-    return [out[int(o):int(o) + d.width * d.height * 3].view(d.height, d.width, 3) for o, d in zip(out_off, descs)]
+    return [out[int(o):int(o) + h * w * 3].view(h, w, 3) for o, (h, w) in zip(out_off, shapes)]
 
 
 def decode_sync_rounds(device: int = 0) -> int:

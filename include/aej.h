@@ -438,6 +438,59 @@ AEJ_API int aej_jpegdec_batch(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, 
                               int32_t *status, void *workspace, uint64_t workspace_bytes);
 AEJ_API int64_t aej_jpegdec_sync_rounds(aej_ctx *ctx);
 
+/* ---- progressive JPEG files decoded on the device (standard_jpeg_decode_many(..., progressive=True)) ----------------------------------
+ * SOF2 files with Huffman coding, under the frame rules of aej_jpegdec_parse_host (8-bit, 1 or 3 components, 4:4:4 / 4:2:2 / 4:2:0 /
+ * grey, the JFIF / Adobe colour rules, no DNL), pixel-identical to Pillow for every COMPLETE progression: one whose scans bring every
+ * coefficient of every component down to Al = 0 (libjpeg-turbo then reconstructs exactly as for a baseline file, csrc/jpegprog.hip).
+ *
+ * aej_jpegprog_parse_host: HOST only.  Walks every marker SOI .. EOI of one file.  *frame always gets the frame and n_scans; scans (may
+ *   be NULL: a count query) gets the scan descriptors when scan_capacity >= n_scans, otherwise the call returns AEJ_ERR_CAPACITY.  A
+ *   scan's Huffman tables are those in force at its SOS (dc[i] for the scan's component i of a first DC scan, ac for an AC scan; the
+ *   others are zero); data_offset / data_length are its entropy-coded bytes in the file, up to the first FF xx with xx not 00 / D0..D7;
+ *   units_x x units_y is what it walks (the MCU grid when interleaved, the component's own block grid otherwise); level is its
+ *   dependency level: one more than the highest level among earlier scans that touch the same (component, coefficient) cells.
+ *   AEJ_ERR_ARG for a malformed file or a scan script that violates T.81 G.1.1.1 (Ss > Se, Se > 63, a DC scan with Se != 0, an AC
+ *   scan of several components or before the component's DC, Al > 13, Ah not the previous Al, Al != Ah - 1, a repeated first scan, an
+ *   undefined Huffman table, a scan that runs past the file, no EOI) -- libjpeg only warns on some of these; this library refuses.
+ *   AEJ_ERR_UNSUPPORTED for a valid file outside the set: an INCOMPLETE progression (libjpeg-turbo would smooth between blocks),
+ *   arithmetic coding (SOF10), an interleaved scan that does not list every component, a file that is not SOF2, and what the baseline
+ *   parser refuses.
+ * aej_jpegprog_batch: n files.  frames_host [n]; scans_host: the scan descriptors of file 0, then file 1, ... (frames_host[i].n_scans
+ *   each); data: device bytes, the entropy-coded bytes of scan j (in that order) at data_offsets_host[j]; out / out_offsets_host /
+ *   status as aej_jpegdec_batch (status values AEJ_JPEGDEC_*).  Every scan is un-stuffed and cut into restart segments at once; then
+ *   one launch per dependency level decodes every restart segment of every scan of that level, one thread per segment (DC refinement:
+ *   one thread per MCU), into the file's coefficients; the baseline path's IDCT and colour kernels finish.  A bad scan marks its file
+ *   and never reads or writes outside its own bytes and its file's coefficients.  Workspace: aej_jpegprog_workspace_bytes. */
+typedef struct aej_jpegprog_frame {
+    int32_t width, height;
+    int32_t ncomp;             /* 1 or 3 */
+    int32_t hs, vs;            /* luma sampling factors (1x1 for grey) */
+    int32_t mcux, mcuy, blocks_per_mcu;
+    int32_t sof;               /* 0xC2 */
+    int32_t precision16;       /* 1 when a quantisation table in force is 16-bit */
+    int32_t n_scans, n_levels;
+    uint8_t comp_id[4], comp_h[4], comp_v[4], comp_tq[4];
+    uint16_t qt[3][64];        /* quantisation table of each component (in force at its first scan), natural order */
+} aej_jpegprog_frame;
+typedef struct aej_jpegprog_scan {
+    int32_t ncomp;             /* components in the scan */
+    int32_t comp[4];           /* their indices in the frame */
+    int32_t td[4], ta[4];      /* the DC / AC table selectors of the SOS */
+    int32_t ss, se, ah, al;
+    int32_t restart_interval;  /* in force at the SOS; counts units */
+    int32_t units_x, units_y;
+    int32_t n_segments;
+    int32_t level;
+    aej_jpegdec_huff dc[3], ac;
+    int64_t data_offset, data_length;
+} aej_jpegprog_scan;
+AEJ_API int aej_jpegprog_parse_host(const uint8_t *data_host, uint64_t nbytes, aej_jpegprog_frame *frame_host, aej_jpegprog_scan *scans_host,
+                                    int scan_capacity, char *msg, int msg_capacity);
+AEJ_API uint64_t aej_jpegprog_workspace_bytes(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n);
+AEJ_API int aej_jpegprog_batch(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
+                               const uint8_t *data, uint64_t data_bytes, const int64_t *data_offsets_host, uint8_t *out, uint64_t out_bytes,
+                               const int64_t *out_offsets_host, int32_t *status, void *workspace, uint64_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

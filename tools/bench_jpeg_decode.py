@@ -2,7 +2,11 @@
 markers -- Pillow's default, decoded by the self-synchronising subsequences -- and (b) with restart_marker_rows=1, against Pillow
 decoding them on a thread pool and uploading its pixels.
 
-    python tools/bench_jpeg_decode.py [--batch 64] [--repeats 3] [--threads 16] [--subseq-bits N] [--out FILE]
+    python tools/bench_jpeg_decode.py [--batch 64] [--repeats 3] [--threads 16] [--subseq-bits N] [--progressive] [--out FILE]
+
+--progressive writes the same files with progressive=True and decodes them with standard_jpeg_decode_many(..., progressive=True)
+(csrc/jpegprog.hip: one thread per restart segment and dependency level, so the files without restart markers are a serial decode
+per scan and the restart-per-row files show what the kernels do when the format allows parallelism).
 
 "gpu" is standard_jpeg_decode_many: host header parsing, one copy of the scans, every device stage, the per-file status read-back;
 it ends with device uint8 [H, W, 3] tensors.  "pillow" is np.asarray(Image.open(buf).convert("RGB")) per file on --threads threads, then
@@ -38,6 +42,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--subseq-bits", type=int, default=0, help="jpegdec_subseq_bits (0: the library's default)")
+    ap.add_argument("--progressive", action="store_true", help="progressive files through csrc/jpegprog.hip")
     ap.add_argument("--out")
     a = ap.parse_args()
     x = images(a.batch)
@@ -46,7 +51,7 @@ def main():
         ctx.set_option("jpegdec_subseq_bits", a.subseq_bits)
     gp = a.batch * H * W / 1e9
     res = {"batch": a.batch, "H": H, "W": W, "quality": 75, "subseq_bits": ctx.get_option("jpegdec_subseq_bits"),
-           "pillow_threads": a.threads, "cases": {}}
+           "pillow_threads": a.threads, "progressive": a.progressive, "cases": {}}
     pool = ThreadPoolExecutor(a.threads)
 
     def save(i, opts):
@@ -57,14 +62,19 @@ def main():
     def pil_load(f):
         return np.asarray(Image.open(io.BytesIO(f)).convert("RGB"))
 
+    def decode(files):
+        return A.standard_jpeg_decode_many(files, progressive=True) if a.progressive else A.standard_jpeg_decode_many(files)
+
     for name, opts in (("no_restarts", {}), ("restart_rows_1", {"restart_marker_rows": 1})):
+        if a.progressive:
+            opts = dict(opts, progressive=True)
         files = list(pool.map(lambda i: save(i, opts), range(a.batch)))
-        got = A.standard_jpeg_decode_many(files)
+        got = decode(files)
         rounds = S.decode_sync_rounds()
         for f, g in zip(files, got):
             assert np.array_equal(g.cpu().numpy(), pil_load(f)), name
         del got
-        tg = timed(lambda: A.standard_jpeg_decode_many(files), a.repeats)
+        tg = timed(lambda: decode(files), a.repeats)
 
         def pillow():
             px = np.stack(list(pool.map(pil_load, files)))
