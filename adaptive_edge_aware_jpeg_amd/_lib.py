@@ -226,6 +226,11 @@ SIGNATURES = {
     "aej_jfif_headers_host": (_I, [_I, _I, _I, _P, _I]),
     "aej_jfif_encode_batch": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _U64, _P, _P, _P, _P, _U64]),
     "aej_jfif_recon_batch": (_I, [_P, _I, _I, _I, _I, _P, _P, _U64]),
+    "aej_jfif_workspace_bytes_opt": (_U64, [_I, _I, _I, _I, _I, _I]),
+    "aej_jfif_headers_host_opt": (_I, [_I, _I, _I, _I, _P, _I]),
+    "aej_jfif_huffman_host": (_I, [_P, _P, _P, _I]),
+    "aej_jfif_encode_batch_opt": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _P, _U64, _P, _P, _P, _P, _U64]),
+    "aej_jfif_recon_batch_opt": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _U64]),
     "aej_jpegdec_parse_host": (_I, [_P, _U64, _P, _P, _I]),
     "aej_jpegdec_workspace_bytes": (_U64, [_P, _P, _I]),
     "aej_jpegdec_batch": (_I, [_P, _P, _I, _P, _U64, _P, _P, _U64, _P, _P, _P, _U64]),

@@ -203,28 +203,34 @@ void launch_lpips(hipStream_t st, const float *wpk, const float *img, int B, con
 
 // jfif.hip: baseline JPEG as Pillow / libjpeg-turbo writes it, and its decode (aej_jfif_*)
 constexpr int kJfifBlockWords = 52;    // 32-bit words that bound one block's Huffman codes (DC <= 22 bits, 63 AC <= 26 bits each)
-constexpr int kJfifHdrMax = 1024;      // SOI .. SOS are 623 bytes
+constexpr int kJfifBlockWordsOpt = 53; // the same with a file's own tables, whose codes reach 16 bits: 27 + 63 x 26 = 1665 bits
+constexpr int kJfifHdrMax = 1024;      // SOI .. SOS are 623 bytes with the Annex K tables and never longer with optimised ones
 struct JfifGeom {
     int B, H, W, nq;
     int mcux, mcuy, ybx, yby;          // MCUs; real luma blocks per row / column
     int yw, yh, cw, ch;                // reconstruction sample planes
-    long long n_mcu, nblk;             // blocks per image, 6 per MCU, dummies included
+    long long n_mcu, nblk;             // per image; nblk = (hs * vs + 2) * n_mcu, dummy luma blocks included
     long long stream_words, n_chunks;  // per (quality, image): unstuffed scan words, 64-byte stuffing chunks
     long long plane_bytes;             // per (quality, image): Y, Cb, Cr sample planes
+    int hs, vs, opt, pad_;             // luma sampling factors (2 x 2, 2 x 1, 1 x 1; chroma is 1 x 1); Huffman tables per file
 };
 struct JfifParams {                    // one quality: quantisers in zigzag order (luma, chroma) and the markers SOI .. SOS
     int qt[2][64];
-    int hdr_len, pad_[3];
+    int hdr_len, dht_off, pad_[2];     // dht_off: where the first DHT segment starts (SOS follows the fourth)
     unsigned char hdr[kJfifHdrMax];
 };
 struct JfifBufs {
     JfifParams *par; int *dct; short *coef; int *lens; long long *boff, *btot; unsigned *stream; int *ffcnt; long long *ffpre, *fftot, *total;
     unsigned char *planes;
+    // per-file Huffman tables (opt only): symbol counts [seg][4][257], (code << 8) | length [seg][4][256], markers [seg][kJfifHdrMax]
+    unsigned long long *hist; unsigned *codes; unsigned char *fhdr; int *fhdr_len;
 };
-bool jfif_geom(int B, int H, int W, int nq, JfifGeom &g);
+// ss: Pillow's subsampling code (0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0); opt: optimise the Huffman tables per file
+bool jfif_geom(int B, int H, int W, int nq, JfifGeom &g, int ss = 2, int opt = 0);
 unsigned long long jfif_carve(void *base, const JfifGeom &g, JfifBufs &w);
 void jfif_quant_tables(int q, int luma[64], int chroma[64]);
-void jfif_params_host(int q, int H, int W, JfifParams &p);
+void jfif_params_host(int q, int H, int W, JfifParams &p, int ss = 2);
+int jfif_huffman_host(const long long *counts, unsigned char *bits, unsigned char *huffval);
 hipError_t launch_jfif_encode(hipStream_t st, const JfifGeom &g, const JfifBufs &w, const JfifParams *par_host, const unsigned char *rgb,
                               unsigned char *out, unsigned long long cap, long long *lengths, long long *offsets);
 hipError_t launch_jfif_recon(hipStream_t st, const JfifGeom &g, const JfifBufs &w, unsigned char *rgb_out);

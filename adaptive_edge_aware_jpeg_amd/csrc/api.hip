@@ -2031,46 +2031,67 @@ extern "C" int aej_lpips_batch(aej_ctx *ctx, const void *weights, const float *i
 }
 
 // ---- baseline JPEG as Pillow / libjpeg-turbo writes it (jfif.hip) --------------------------------------------------------------------
-static int jfif_args(aej_ctx *ctx, const char *fn, int batch, int H, int W, int n_q, JfifGeom &g)
+static int jfif_args(aej_ctx *ctx, const char *fn, int batch, int H, int W, int n_q, int ss, int opt, JfifGeom &g)
 {
     if (ctx && call_in_flight(ctx)) return fail(ctx, AEJ_ERR_STATE, "%s between aej_encode_batch_begin and aej_encode_batch_end", fn);
-    if (!jfif_geom(batch, H, W, n_q, g))
+    if (ss < 0 || ss > 2) return fail(ctx, AEJ_ERR_ARG, "%s: subsampling %d (0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0)", fn, ss);
+    if (opt != 0 && opt != 1) return fail(ctx, AEJ_ERR_ARG, "%s: optimize %d (0 or 1)", fn, opt);
+    if (!jfif_geom(batch, H, W, n_q, g, ss, opt))
         return fail(ctx, AEJ_ERR_ARG, "%s: bad shape %d x %d x %d with %d qualities (1 <= H, W <= 65535)", fn, batch, H, W, n_q);
     return 0;
 }
 
-extern "C" uint64_t aej_jfif_workspace_bytes(int batch, int H, int W, int n_q)
+extern "C" uint64_t aej_jfif_workspace_bytes_opt(int batch, int H, int W, int n_q, int subsampling, int optimize)
 {
     JfifGeom g;
-    if (!jfif_geom(batch, H, W, n_q, g)) return 0;
+    if ((optimize != 0 && optimize != 1) || !jfif_geom(batch, H, W, n_q, g, subsampling, optimize)) return 0;
     JfifBufs w;
     return jfif_carve(nullptr, g, w);
 }
 
-extern "C" int aej_jfif_headers_host(int quality, int H, int W, uint8_t *out_host, int capacity)
+extern "C" uint64_t aej_jfif_workspace_bytes(int batch, int H, int W, int n_q) { return aej_jfif_workspace_bytes_opt(batch, H, W, n_q, 2, 0); }
+
+extern "C" int aej_jfif_headers_host_opt(int quality, int H, int W, int subsampling, uint8_t *out_host, int capacity)
 {
     JfifGeom g;
-    if (quality < 1 || quality > 100 || !jfif_geom(1, H, W, 1, g) || !out_host) return AEJ_ERR_ARG;
+    if (quality < 1 || quality > 100 || !jfif_geom(1, H, W, 1, g, subsampling, 0) || !out_host) return AEJ_ERR_ARG;
     JfifParams p;
-    jfif_params_host(quality, H, W, p);
+    jfif_params_host(quality, H, W, p, subsampling);
     if (capacity < p.hdr_len) return AEJ_ERR_CAPACITY;
     memcpy(out_host, p.hdr, p.hdr_len);
     return p.hdr_len;
 }
 
-extern "C" int aej_jfif_encode_batch(aej_ctx *ctx, const uint8_t *rgb, int batch, int H, int W, int n_q, const int32_t *qualities_host, uint8_t *out,
-                                     uint64_t out_capacity, int64_t *offsets, int64_t *lengths, uint64_t *total_host, void *workspace,
-                                     uint64_t workspace_bytes)
+extern "C" int aej_jfif_headers_host(int quality, int H, int W, uint8_t *out_host, int capacity)
+{
+    return aej_jfif_headers_host_opt(quality, H, W, 2, out_host, capacity);
+}
+
+extern "C" int aej_jfif_huffman_host(const int64_t *counts_host, uint8_t *bits_host, uint8_t *huffval_host, int capacity)
+{
+    if (!counts_host || !bits_host || !huffval_host || capacity < 0) return AEJ_ERR_ARG;
+    unsigned char bits[16], vals[256];
+    const int n = jfif_huffman_host((const long long *)counts_host, bits, vals);
+    if (n < 0) return AEJ_ERR_ARG;
+    if (n > capacity) return AEJ_ERR_CAPACITY;
+    memcpy(bits_host, bits, 16);
+    memcpy(huffval_host, vals, n);
+    return n;
+}
+
+extern "C" int aej_jfif_encode_batch_opt(aej_ctx *ctx, const uint8_t *rgb, int batch, int H, int W, int n_q, const int32_t *qualities_host,
+                                         int subsampling, int optimize, uint8_t *out, uint64_t out_capacity, int64_t *offsets, int64_t *lengths,
+                                         uint64_t *total_host, void *workspace, uint64_t workspace_bytes)
 {
     if (!ctx) return AEJ_ERR_ARG;
     JfifGeom g;
-    int rc = jfif_args(ctx, __func__, batch, H, W, n_q, g);
+    int rc = jfif_args(ctx, __func__, batch, H, W, n_q, subsampling, optimize, g);
     if (rc) return rc;
     if (!rgb || !qualities_host || !offsets || !lengths || !total_host || !workspace) return fail(ctx, AEJ_ERR_ARG, "%s: NULL buffer", __func__);
     std::vector<JfifParams> par(n_q);
     for (int i = 0; i < n_q; i++) {
         if (qualities_host[i] < 1 || qualities_host[i] > 100) return fail(ctx, AEJ_ERR_ARG, "%s: quality %d outside 1..100", __func__, qualities_host[i]);
-        jfif_params_host(qualities_host[i], H, W, par[i]);
+        jfif_params_host(qualities_host[i], H, W, par[i], subsampling);
     }
     JfifBufs w;
     const unsigned long long need = jfif_carve(workspace, g, w);
@@ -2087,11 +2108,20 @@ extern "C" int aej_jfif_encode_batch(aej_ctx *ctx, const uint8_t *rgb, int batch
     return 0;
 }
 
-extern "C" int aej_jfif_recon_batch(aej_ctx *ctx, int batch, int H, int W, int n_q, uint8_t *rgb_out, void *workspace, uint64_t workspace_bytes)
+extern "C" int aej_jfif_encode_batch(aej_ctx *ctx, const uint8_t *rgb, int batch, int H, int W, int n_q, const int32_t *qualities_host, uint8_t *out,
+                                     uint64_t out_capacity, int64_t *offsets, int64_t *lengths, uint64_t *total_host, void *workspace,
+                                     uint64_t workspace_bytes)
+{
+    return aej_jfif_encode_batch_opt(ctx, rgb, batch, H, W, n_q, qualities_host, 2, 0, out, out_capacity, offsets, lengths, total_host, workspace,
+                                     workspace_bytes);
+}
+
+extern "C" int aej_jfif_recon_batch_opt(aej_ctx *ctx, int batch, int H, int W, int n_q, int subsampling, int optimize, uint8_t *rgb_out,
+                                        void *workspace, uint64_t workspace_bytes)
 {
     if (!ctx) return AEJ_ERR_ARG;
     JfifGeom g;
-    int rc = jfif_args(ctx, __func__, batch, H, W, n_q, g);
+    int rc = jfif_args(ctx, __func__, batch, H, W, n_q, subsampling, optimize, g);
     if (rc) return rc;
     if (!rgb_out || !workspace) return fail(ctx, AEJ_ERR_ARG, "%s: NULL buffer", __func__);
     JfifBufs w;
@@ -2100,6 +2130,11 @@ extern "C" int aej_jfif_recon_batch(aej_ctx *ctx, int batch, int H, int W, int n
     AEJ_HIP_CHECK(hipSetDevice(ctx->device));
     AEJ_HIP_CHECK(launch_jfif_recon(ctx->stream, g, w, rgb_out));
     return 0;
+}
+
+extern "C" int aej_jfif_recon_batch(aej_ctx *ctx, int batch, int H, int W, int n_q, uint8_t *rgb_out, void *workspace, uint64_t workspace_bytes)
+{
+    return aej_jfif_recon_batch_opt(ctx, batch, H, W, n_q, 2, 0, rgb_out, workspace, workspace_bytes);
 }
 
 // ---- baseline JPEG files decoded on the device (jpegdec.hip) --------------------------------------------------------------------------

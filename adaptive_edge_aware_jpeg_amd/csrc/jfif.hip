@@ -1,22 +1,32 @@
-// jfif.hip -- baseline JPEG as Pillow writes it with libjpeg-turbo (quality q, 4:2:0, Annex K tables, islow DCT, no restarts) and the
-// pixels Pillow's decoder returns for it (aej_jfif_*, include/aej.h).  The arithmetic restates libjpeg's published integer algorithm;
-// tests/jfif_reference.py is the same algorithm in numpy and tests/test_gpu_jfif.py pins both to Pillow's files byte for byte.
+// jfif.hip -- baseline JPEG as Pillow writes it with libjpeg-turbo (quality q, subsampling 4:2:0 / 4:2:2 / 4:4:4, the Annex K Huffman
+// tables or with optimize=True the file's own, islow DCT, no restarts) and the pixels Pillow's decoder returns for it (aej_jfif_*,
+// include/aej.h).  The arithmetic restates libjpeg's published integer algorithm; tests/jfif_reference.py and
+// tests/jfif_options_reference.py are the same algorithm in numpy and tests/test_gpu_jfif*.py pin both to Pillow's files byte for byte.
 //
+// Every kernel that walks blocks is a template over the luma sampling factors <HS, VS> (2 x 2, 2 x 1, 1 x 1): an MCU holds HS * VS luma
+// blocks in raster order, then Cb, then Cr.
 // Stages (one launch each, every quality of a call in the same launch after the first):
-//   k_jfif_fdct     one thread per 8 x 8 block of one image: colour, edge padding, 2 x 2 down-sampling, islow FDCT -> int32 (zigzag order)
-//   k_jfif_quant    one thread per (quality, image, block): quantise, resolve dummy blocks, count the block's Huffman bits
+//   k_jfif_fdct     one thread per 8 x 8 block of one image: colour, edge padding, chroma down-sampling, islow FDCT -> int32 (zigzag order)
+//   k_jfif_quant    one thread per (quality, image, block): quantise, resolve dummy blocks, count the block's Huffman bits (Annex K)
+//   optimize only, between k_jfif_quant and the scan:
+//   k_jfif_hist     one thread per block: the symbols the emitter will write, counted per wave in LDS, then one add per non-zero bin
+//   k_jfif_tables   one workgroup per (quality, image), one wave per table: jh_build (jfif_huff_core.h), the codes, the file's markers
+//   k_jfif_count    one thread per block: its bits under the file's own tables
 //   k_jfif_scan     one workgroup per (quality, image): exclusive scan of per-block bit counts (and later of per-chunk 0xFF counts)
 //   k_jfif_emit     one thread per block: its code string at its bit offset, boundary words by atomicOr; the last block pads with 1-bits
 //   k_jfif_ffcount  one thread per 64-byte chunk of a stream: its 0xFF bytes
 //   k_jfif_layout   one thread: file lengths (markers + stuffed data + EOI) and their offsets in the packed output
 //   k_jfif_scatter  one thread per chunk: the chunk with a 0x00 after every 0xFF at its final place; chunk 0 also writes markers and EOI
 //   k_jfif_idct     one thread per (quality, image, real block): dequantise, islow IDCT, masked range limit -> uint8 sample planes
-//   k_jfif_rgb      one thread per output pixel: h2v2 fancy up-sampling (plain 2 x 2 replication when the chroma is <= 2 wide, as
-//                   libjpeg-turbo does) and the fixed-point YCbCr -> RGB
+//   k_jfif_rgb      one thread per output pixel: h2v2 / h2v1 fancy up-sampling (plain replication when the chroma is <= 2 wide, as
+//                   libjpeg-turbo does; none at 4:4:4) -- jd_chroma of jpegdec_core.h -- and the fixed-point YCbCr -> RGB
 // Bounds: every index derives from JfifGeom; a stream's words stay inside its stride (the per-block bound kJfifBlockWords holds for every
-// input: DC <= 22 bits, 63 AC <= 26 bits each); k_jfif_scatter writes a file only if it ends inside the caller's capacity.
+// input: DC <= 22 bits, 63 AC <= 26 bits each; kJfifBlockWordsOpt with a file's own tables: DC <= 27, AC <= 26) and every store into
+// a stream checks that stride; k_jfif_scatter writes a file only if it ends inside the caller's capacity.
 #include "aej_common.h"
 #include "aej_launch.h"
+#include "jfif_huff_core.h"
+#include "jpegdec_core.h"
 
 namespace aej {
 
@@ -132,39 +142,46 @@ __device__ __forceinline__ int jf_quant(int c, int qt)      // libjpeg's quantis
 }
 __device__ __forceinline__ int jf_cat(int v) { return v == 0 ? 0 : 32 - __clz(v < 0 ? -v : v); }
 
-// MCU geometry: block k (0..3 luma in raster order, 4 Cb, 5 Cr) of MCU m; luma blocks outside ceil(H/8) x ceil(W/8) are dummies
+// MCU geometry: block k (0 .. HS * VS - 1 luma in raster order, then Cb, Cr) of MCU m; luma blocks outside ceil(H/8) x ceil(W/8) are
+// dummies (right edge when HS = 2, bottom edge when VS = 2)
+template <int HS, int VS>
 __device__ __forceinline__ bool jf_real(const JfifGeom &g, long long m, int k)
 {
-    if (k >= 4) return true;
+    if (k >= HS * VS) return true;
     const int my = (int)(m / g.mcux), mx = (int)(m % g.mcux);
-    return 2 * my + (k >> 1) < g.yby && 2 * mx + (k & 1) < g.ybx;
+    return VS * my + k / HS < g.yby && HS * mx + k % HS < g.ybx;
 }
 // quantised DC of block k of MCU m under the quality's tables: a dummy takes the DC of the block before it in the MCU (block 0 is real)
+template <int HS, int VS>
 __device__ __forceinline__ int jf_qdc(const JfifGeom &g, const int *dct_img, const JfifParams &p, long long m, int k)
 {
-    while (!jf_real(g, m, k)) k--;
-    return jf_quant(dct_img[(m * 6 + k) * 64], p.qt[k >= 4][0]);
+    while (!jf_real<HS, VS>(g, m, k)) k--;
+    return jf_quant(dct_img[(m * (HS * VS + 2) + k) * 64], p.qt[k >= HS * VS][0]);
 }
 // the block of the same component before block (m, k) in scan order, -1 at the start of the scan
+template <int HS, int VS>
 __device__ __forceinline__ long long jf_prev(long long m, int k)
 {
-    if (k >= 1 && k <= 3) return m * 6 + k - 1;
+    constexpr int NL = HS * VS, BPM = NL + 2;
+    if (k >= 1 && k < NL) return m * BPM + k - 1;
     if (m == 0) return -1;
-    return k == 0 ? (m - 1) * 6 + 3 : (m - 1) * 6 + k;
+    return k == 0 ? (m - 1) * BPM + NL - 1 : (m - 1) * BPM + k;
 }
 
 // ---- encode ------------------------------------------------------------------------------------------------------------------------
+template <int HS, int VS>
 __global__ __launch_bounds__(kJfThreads) void k_jfif_fdct(JfifGeom g, const unsigned char *__restrict__ rgb, int *__restrict__ dct)
 {
+    constexpr int NL = HS * VS, BPM = NL + 2;
     const long long idx = (long long)blockIdx.x * kJfThreads + threadIdx.x;
     if (idx >= (long long)g.B * g.nblk) return;
     const int b = (int)(idx / g.nblk);
-    const long long blk = idx % g.nblk, m = blk / 6;
-    const int k = (int)(blk % 6), my = (int)(m / g.mcux), mx = (int)(m % g.mcux);
+    const long long blk = idx % g.nblk, m = blk / BPM;
+    const int k = (int)(blk % BPM), my = (int)(m / g.mcux), mx = (int)(m % g.mcux);
     const unsigned char *img = rgb + (long long)b * g.H * g.W * 3;
     long long d[64];
-    if (k < 4) {
-        const int by = 2 * my + (k >> 1), bx = 2 * mx + (k & 1);
+    if (k < NL) {
+        const int by = VS * my + k / HS, bx = HS * mx + k % HS;
         if (by >= g.yby || bx >= g.ybx) return;          // dummy: never read
 #pragma unroll
         for (int r = 0; r < 8; r++) {
@@ -172,8 +189,27 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_fdct(JfifGeom g, const unsi
 #pragma unroll
             for (int c = 0; c < 8; c++) d[r * 8 + c] = jf_y(img + ((long long)py * g.W + min(bx * 8 + c, g.W - 1)) * 3) - 128;
         }
-    } else {
-        const int comp = k - 4, hc = (g.H + 1) / 2;
+    } else if (HS == 1) {                                    // 4:4:4: full-size chroma, edges replicated
+        const int comp = k - NL;
+#pragma unroll
+        for (int r = 0; r < 8; r++) {
+            const int py = min(my * 8 + r, g.H - 1);
+#pragma unroll
+            for (int c = 0; c < 8; c++) d[r * 8 + c] = jf_c(img + ((long long)py * g.W + min(mx * 8 + c, g.W - 1)) * 3, comp) - 128;
+        }
+    } else if (VS == 1) {                                    // 4:2:2: h2v1_downsample, bias 0, 1, 0, 1, ... from column 0
+        const int comp = k - NL;
+#pragma unroll
+        for (int r = 0; r < 8; r++) {
+            const unsigned char *r0 = img + (long long)min(my * 8 + r, g.H - 1) * g.W * 3;
+#pragma unroll
+            for (int c = 0; c < 8; c++) {
+                const int cx = mx * 8 + c, x0 = min(2 * cx, g.W - 1) * 3, x1 = min(2 * cx + 1, g.W - 1) * 3;
+                d[r * 8 + c] = ((jf_c(r0 + x0, comp) + jf_c(r0 + x1, comp) + (cx & 1)) >> 1) - 128;
+            }
+        }
+    } else {                                                 // 4:2:0: h2v2_downsample
+        const int comp = k - NL, hc = (g.H + 1) / 2;
 #pragma unroll
         for (int r = 0; r < 8; r++) {
             const int cy = min(my * 8 + r, hc - 1), y0 = 2 * cy, y1 = min(2 * cy + 1, g.H - 1);
@@ -196,28 +232,36 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_fdct(JfifGeom g, const unsi
 }
 
 struct JfCodes { const unsigned *dc, *ac; };
-__device__ __forceinline__ JfCodes jf_codes(int k) { return k >= 4 ? JfCodes{ k_dc_chroma, k_ac_chroma } : JfCodes{ k_dc_luma, k_ac_luma }; }
+__device__ __forceinline__ JfCodes jf_codes(bool chroma) { return chroma ? JfCodes{ k_dc_chroma, k_ac_chroma } : JfCodes{ k_dc_luma, k_ac_luma }; }
+// a file's own tables: [seg][DC luma, AC luma, DC chroma, AC chroma][256]
+__device__ __forceinline__ JfCodes jf_file_codes(const unsigned *codes, long long seg, bool chroma)
+{
+    const unsigned *t = codes + (seg * 4 + (chroma ? 2 : 0)) * 256;
+    return JfCodes{ t, t + 256 };
+}
 
 // (a) quantise every block of every (quality, image) and count its Huffman bits
+template <int HS, int VS>
 __global__ __launch_bounds__(kJfThreads) void k_jfif_quant(JfifGeom g, const JfifParams *__restrict__ par, const int *__restrict__ dct,
                                                            short *__restrict__ coef, int *__restrict__ lens)
 {
+    constexpr int NL = HS * VS, BPM = NL + 2;
     const long long idx = (long long)blockIdx.x * kJfThreads + threadIdx.x;
     if (idx >= (long long)g.nq * g.B * g.nblk) return;
-    const long long seg = idx / g.nblk, blk = idx % g.nblk, m = blk / 6;
-    const int k = (int)(blk % 6), b = (int)(seg % g.B);
+    const long long seg = idx / g.nblk, blk = idx % g.nblk, m = blk / BPM;
+    const int k = (int)(blk % BPM), b = (int)(seg % g.B);
     const JfifParams &p = par[seg / g.B];
-    const int *qt = p.qt[k >= 4];
+    const int *qt = p.qt[k >= NL];
     const int *img = dct + (long long)b * g.nblk * 64;
-    const JfCodes hc = jf_codes(k);
+    const JfCodes hc = jf_codes(k >= NL);
     short *o = coef + idx * 64;
-    const int dc = jf_qdc(g, img, p, m, k);
-    const long long pb = jf_prev(m, k);
-    const int diff = dc - (pb < 0 ? 0 : jf_qdc(g, img, p, pb / 6, (int)(pb % 6)));
+    const int dc = jf_qdc<HS, VS>(g, img, p, m, k);
+    const long long pb = jf_prev<HS, VS>(m, k);
+    const int diff = dc - (pb < 0 ? 0 : jf_qdc<HS, VS>(g, img, p, pb / BPM, (int)(pb % BPM)));
     const int dcat = jf_cat(diff);
     int bits = (int)(hc.dc[dcat] & 255) + dcat;
     o[0] = (short)dc;
-    if (!jf_real(g, m, k)) {
+    if (!jf_real<HS, VS>(g, m, k)) {
         for (int i = 1; i < 64; i++) o[i] = 0;
         lens[idx] = bits + (int)(hc.ac[0] & 255);
         return;
@@ -227,6 +271,108 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_quant(JfifGeom g, const Jfi
     for (int i = 1; i < 64; i++) {
         const int v = jf_quant(d[k_zz[i]], qt[i]);
         o[i] = (short)v;
+        if (v == 0) { run++; continue; }
+        const int cat = jf_cat(v);
+        bits += (run >> 4) * (int)(hc.ac[0xF0] & 255) + (int)(hc.ac[((run & 15) << 4) | cat] & 255) + cat;
+        run = 0;
+    }
+    if (run) bits += (int)(hc.ac[0] & 255);
+    lens[idx] = bits;
+}
+
+// ---- optimize: the file's own Huffman tables -----------------------------------------------------------------------------------------
+// (a1) the symbols k_jfif_emit will write for every block, dummies included: DC categories, (run << 4) | size, ZRL per 16 zeros, EOB.
+// grid (blocks of one segment, segment); counts are private to a wave in LDS, then one 64-bit add per non-zero bin.
+template <int HS, int VS>
+__global__ __launch_bounds__(kJfThreads) void k_jfif_hist(JfifGeom g, const short *__restrict__ coef, unsigned long long *__restrict__ hist)
+{
+    constexpr int NL = HS * VS, BPM = NL + 2, kWaves = kJfThreads / 64;
+    __shared__ unsigned cnt[kWaves][4][kJhSymbols];
+    for (int i = threadIdx.x; i < kWaves * 4 * kJhSymbols; i += kJfThreads) (&cnt[0][0][0])[i] = 0;
+    __syncthreads();
+    const long long seg = blockIdx.y, blk = (long long)blockIdx.x * kJfThreads + threadIdx.x;
+    if (blk < g.nblk) {
+        const long long m = blk / BPM;
+        const int k = (int)(blk % BPM);
+        unsigned(*h)[kJhSymbols] = cnt[threadIdx.x / 64] + (k >= NL ? 2 : 0);      // [0] DC, [1] AC of the block's component class
+        const short *c = coef + (seg * g.nblk + blk) * 64;
+        const long long pb = jf_prev<HS, VS>(m, k);
+        atomicAdd(&h[0][jf_cat(c[0] - (pb < 0 ? 0 : coef[(seg * g.nblk + pb) * 64]))], 1u);
+        int run = 0;
+        for (int i = 1; i < 64; i++) {
+            const int v = c[i];
+            if (v == 0) { run++; continue; }
+            if (run > 15) atomicAdd(&h[1][0xF0], (unsigned)(run >> 4));
+            atomicAdd(&h[1][((run & 15) << 4) | jf_cat(v)], 1u);
+            run = 0;
+        }
+        if (run) atomicAdd(&h[1][0], 1u);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 4 * kJhSymbols; i += kJfThreads) {
+        unsigned n = 0;
+        for (int w = 0; w < kWaves; w++) n += (&cnt[w][0][0])[i];
+        if (n) atomicAdd(hist + seg * 4 * kJhSymbols + i, (unsigned long long)n);
+    }
+}
+
+// (a2) one workgroup per (quality, image), one wave per table (DC luma, AC luma, DC chroma, AC chroma): the table (jh_build, serial on
+// the wave's first lane with its work arrays in LDS), its codes, and the file's markers: those of its quality with these four DHTs
+__global__ __launch_bounds__(kJfThreads) void k_jfif_tables(JfifGeom g, const JfifParams *__restrict__ par, const unsigned long long *__restrict__ hist,
+                                                            unsigned *__restrict__ codes, unsigned char *__restrict__ fhdr, int *__restrict__ fhdr_len)
+{
+    static_assert(kJfThreads == 4 * 64, "one wave per table");
+    __shared__ JhWork work[4];
+    __shared__ unsigned char bits[4][16], vals[4][256];
+    __shared__ int nsym[4];
+    const long long seg = blockIdx.x;
+    const int t = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    unsigned *tc = codes + (seg * 4 + t) * 256;
+    for (int i = lane; i < 256; i += 64) {
+        work[t].freq[i] = (long long)hist[(seg * 4 + t) * kJhSymbols + i];
+        tc[i] = 0;
+    }
+    __syncthreads();
+    if (lane == 0) nsym[t] = jh_build(work[t], bits[t], vals[t]);
+    __syncthreads();
+    if (lane == 0) jh_codes(bits[t], vals[t], tc);
+    const JfifParams &p = par[seg / g.B];
+    unsigned char *o = fhdr + seg * kJfifHdrMax;
+    for (int i = threadIdx.x; i < p.dht_off; i += kJfThreads) o[i] = p.hdr[i];
+    int off = p.dht_off, end = p.dht_off;
+    for (int u = 0; u < 4; u++) {
+        if (u < t) off += 5 + 16 + nsym[u];
+        end += 5 + 16 + nsym[u];
+    }
+    if (end + 14 <= kJfifHdrMax) {                           // always: at most 12 DC and 162 AC symbols, the Annex K sizes
+        const int n = nsym[t];
+        if (lane == 0) {
+            o[off] = 0xFF; o[off + 1] = 0xC4; o[off + 2] = (unsigned char)((19 + n) >> 8); o[off + 3] = (unsigned char)((19 + n) & 255);
+            o[off + 4] = (unsigned char)(((t & 1) << 4) | (t >> 1));
+        }
+        for (int i = lane; i < 16 + n; i += 64) o[off + 5 + i] = i < 16 ? bits[t][i] : vals[t][i - 16];
+        if (threadIdx.x < 14) o[end + threadIdx.x] = p.hdr[p.hdr_len - 14 + threadIdx.x];      // SOS
+    }
+    if (threadIdx.x == 0) fhdr_len[seg] = end + 14 <= kJfifHdrMax ? end + 14 : 0;
+}
+
+// (a3) every block's bits under its file's tables (k_jfif_quant counted them with the Annex K lengths)
+template <int HS, int VS>
+__global__ __launch_bounds__(kJfThreads) void k_jfif_count(JfifGeom g, const short *__restrict__ coef, const unsigned *__restrict__ codes,
+                                                           int *__restrict__ lens)
+{
+    constexpr int NL = HS * VS, BPM = NL + 2;
+    const long long idx = (long long)blockIdx.x * kJfThreads + threadIdx.x;
+    if (idx >= (long long)g.nq * g.B * g.nblk) return;
+    const long long seg = idx / g.nblk, blk = idx % g.nblk, m = blk / BPM;
+    const int k = (int)(blk % BPM);
+    const JfCodes hc = jf_file_codes(codes, seg, k >= NL);
+    const short *c = coef + idx * 64;
+    const long long pb = jf_prev<HS, VS>(m, k);
+    const int dcat = jf_cat(c[0] - (pb < 0 ? 0 : coef[(seg * g.nblk + pb) * 64]));
+    int bits = (int)(hc.dc[dcat] & 255) + dcat, run = 0;
+    for (int i = 1; i < 64; i++) {
+        const int v = c[i];
         if (v == 0) { run++; continue; }
         const int cat = jf_cat(v);
         bits += (run >> 4) * (int)(hc.ac[0xF0] & 255) + (int)(hc.ac[((run & 15) << 4) | cat] & 255) + cat;
@@ -298,16 +444,20 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_zero(JfifGeom g, const long
 }
 
 // (c) every block's code string at its bit offset
+// kOpt: the codes are the file's own (k_jfif_tables) instead of the Annex K constants
+template <int HS, int VS, bool kOpt>
 __global__ __launch_bounds__(kJfThreads) void k_jfif_emit(JfifGeom g, const short *__restrict__ coef, const long long *__restrict__ boff,
-                                                          const long long *__restrict__ btot, unsigned *__restrict__ stream)
+                                                          const long long *__restrict__ btot, const unsigned *__restrict__ codes,
+                                                          unsigned *__restrict__ stream)
 {
+    constexpr int NL = HS * VS, BPM = NL + 2;
     const long long idx = (long long)blockIdx.x * kJfThreads + threadIdx.x;
     if (idx >= (long long)g.nq * g.B * g.nblk) return;
-    const long long seg = idx / g.nblk, blk = idx % g.nblk, m = blk / 6;
-    const int k = (int)(blk % 6);
-    const JfCodes hc = jf_codes(k);
+    const long long seg = idx / g.nblk, blk = idx % g.nblk, m = blk / BPM;
+    const int k = (int)(blk % BPM);
+    const JfCodes hc = kOpt ? jf_file_codes(codes, seg, k >= NL) : jf_codes(k >= NL);
     const short *c = coef + idx * 64;
-    const long long pb = jf_prev(m, k);
+    const long long pb = jf_prev<HS, VS>(m, k);
     JfBits bw(stream + seg * g.stream_words, boff[idx], g.stream_words);
     const int diff = c[0] - (pb < 0 ? 0 : coef[(seg * g.nblk + pb) * 64]);
     const int dcat = jf_cat(diff);
@@ -347,14 +497,15 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_ffcount(JfifGeom g, const l
 }
 
 // file lengths (markers + stuffed data + EOI) and their offsets in the packed output, segments in (quality, image) order
-__global__ void k_jfif_layout(JfifGeom g, const JfifParams *__restrict__ par, const long long *__restrict__ btot,
-                              const long long *__restrict__ fftot, long long *__restrict__ lengths, long long *__restrict__ offsets,
-                              long long *__restrict__ total)
+// (with per-file tables the markers of file seg are fhdr[seg], fhdr_len[seg] bytes; otherwise those of its quality)
+__global__ void k_jfif_layout(JfifGeom g, const JfifParams *__restrict__ par, const int *__restrict__ fhdr_len,
+                              const long long *__restrict__ btot, const long long *__restrict__ fftot, long long *__restrict__ lengths,
+                              long long *__restrict__ offsets, long long *__restrict__ total)
 {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
     long long off = 0;
     for (long long seg = 0; seg < (long long)g.nq * g.B; seg++) {
-        const long long len = par[seg / g.B].hdr_len + ((btot[seg] + 7) >> 3) + fftot[seg] + 2;
+        const long long len = (g.opt ? fhdr_len[seg] : par[seg / g.B].hdr_len) + ((btot[seg] + 7) >> 3) + fftot[seg] + 2;
         lengths[seg] = len;
         offsets[seg] = off;
         off += len;
@@ -362,7 +513,9 @@ __global__ void k_jfif_layout(JfifGeom g, const JfifParams *__restrict__ par, co
     *total = off;
 }
 
-__global__ __launch_bounds__(kJfThreads) void k_jfif_scatter(JfifGeom g, const JfifParams *__restrict__ par, const long long *__restrict__ btot,
+__global__ __launch_bounds__(kJfThreads) void k_jfif_scatter(JfifGeom g, const JfifParams *__restrict__ par,
+                                                             const unsigned char *__restrict__ fhdr, const int *__restrict__ fhdr_len,
+                                                             const long long *__restrict__ btot,
                                                              const unsigned *__restrict__ stream, const long long *__restrict__ ffpre,
                                                              const long long *__restrict__ lengths, const long long *__restrict__ offsets,
                                                              unsigned char *__restrict__ out, unsigned long long cap)
@@ -372,16 +525,17 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_scatter(JfifGeom g, const J
     const long long seg = idx / g.n_chunks, ch = idx % g.n_chunks;
     const long long off = offsets[seg], len = lengths[seg];
     if (off < 0 || len < 0 || (unsigned long long)(off + len) > cap) return;
-    const JfifParams &p = par[seg / g.B];
+    const unsigned char *hdr = g.opt ? fhdr + seg * kJfifHdrMax : par[seg / g.B].hdr;
+    const int hdr_len = g.opt ? fhdr_len[seg] : par[seg / g.B].hdr_len;
     unsigned char *file = out + off;
     if (ch == 0) {
-        for (int i = 0; i < p.hdr_len; i++) file[i] = p.hdr[i];
+        for (int i = 0; i < hdr_len; i++) file[i] = hdr[i];
         file[len - 2] = 0xFF;
         file[len - 1] = 0xD9;
     }
     const long long nbytes = (btot[seg] + 7) >> 3, lo = ch * kJfChunk, hi = min(nbytes, lo + kJfChunk);
     const unsigned char *src = reinterpret_cast<const unsigned char *>(stream + seg * g.stream_words);
-    unsigned char *dst = file + p.hdr_len + lo + (lo < hi ? ffpre[idx] : 0);
+    unsigned char *dst = file + hdr_len + lo + (lo < hi ? ffpre[idx] : 0);
     for (long long i = lo; i < hi; i++) {
         const unsigned char v = src[i];
         *dst++ = v;
@@ -396,15 +550,17 @@ __device__ __forceinline__ unsigned char jf_range_limit(long long x)      // lib
     return (unsigned char)(m < 128 ? m + 128 : m < 512 ? 255 : m < 896 ? 0 : m - 896);
 }
 
+template <int HS, int VS>
 __global__ __launch_bounds__(kJfThreads) void k_jfif_idct(JfifGeom g, const JfifParams *__restrict__ par, const short *__restrict__ coef,
                                                           unsigned char *__restrict__ planes)
 {
+    constexpr int NL = HS * VS, BPM = NL + 2;
     const long long idx = (long long)blockIdx.x * kJfThreads + threadIdx.x;
     if (idx >= (long long)g.nq * g.B * g.nblk) return;
-    const long long seg = idx / g.nblk, blk = idx % g.nblk, m = blk / 6;
-    const int k = (int)(blk % 6), my = (int)(m / g.mcux), mx = (int)(m % g.mcux);
-    if (!jf_real(g, m, k)) return;
-    const int *qt = par[seg / g.B].qt[k >= 4];
+    const long long seg = idx / g.nblk, blk = idx % g.nblk, m = blk / BPM;
+    const int k = (int)(blk % BPM), my = (int)(m / g.mcux), mx = (int)(m % g.mcux);
+    if (!jf_real<HS, VS>(g, m, k)) return;
+    const int *qt = par[seg / g.B].qt[k >= NL];
     const short *c = coef + idx * 64;
     long long d[64];
 #pragma unroll
@@ -415,10 +571,10 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_idct(JfifGeom g, const Jfif
     for (int r = 0; r < 8; r++) jf_idct8<false>(d + r * 8, 1);
     unsigned char *pl = planes + seg * g.plane_bytes;
     int stride, y0, x0;
-    if (k < 4) {
-        stride = g.yw; y0 = (2 * my + (k >> 1)) * 8; x0 = (2 * mx + (k & 1)) * 8;
+    if (k < NL) {
+        stride = g.yw; y0 = (VS * my + k / HS) * 8; x0 = (HS * mx + k % HS) * 8;
     } else {
-        pl += (long long)g.yh * g.yw + (long long)(k - 4) * g.ch * g.cw;
+        pl += (long long)g.yh * g.yw + (long long)(k - NL) * g.ch * g.cw;
         stride = g.cw; y0 = my * 8; x0 = mx * 8;
     }
 #pragma unroll
@@ -427,19 +583,9 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_idct(JfifGeom g, const Jfif
         for (int cc = 0; cc < 8; cc++) pl[(long long)(y0 + r) * stride + x0 + cc] = jf_range_limit(d[r * 8 + cc]);
 }
 
-// chroma sample of output pixel (y, x): h2v2 fancy up-sampling of the real ceil(H/2) x ceil(W/2) samples (2 x 2 replication when that
-// is at most 2 wide); the row above the first and below the last real chroma row is that row itself
-__device__ __forceinline__ int jf_chroma(const JfifGeom &g, const unsigned char *p, int y, int x)
-{
-    const int hc = (g.H + 1) / 2, wc = (g.W + 1) / 2, cy = y >> 1, j = x >> 1;
-    if (wc <= 2) return p[(long long)cy * g.cw + j];
-    const int far = (y & 1) ? min(cy + 1, hc - 1) : max(cy - 1, 0);
-    const unsigned char *n0 = p + (long long)cy * g.cw, *n1 = p + (long long)far * g.cw;
-    const int cs = 3 * n0[j] + n1[j];
-    if ((x & 1) == 0) return j == 0 ? (4 * cs + 8) >> 4 : (3 * cs + 3 * n0[j - 1] + n1[j - 1] + 8) >> 4;
-    return j == wc - 1 ? (4 * cs + 7) >> 4 : (3 * cs + 3 * n0[j + 1] + n1[j + 1] + 7) >> 4;
-}
-
+// chroma of output pixel (y, x): jd_chroma (jpegdec_core.h) over the real ceil(H / VS) x ceil(W / HS) samples -- h2v2 / h2v1 fancy
+// up-sampling, replication when that is at most 2 wide, the sample itself at 4:4:4
+template <int HS, int VS>
 __global__ __launch_bounds__(kJfThreads) void k_jfif_rgb(JfifGeom g, const unsigned char *__restrict__ planes, unsigned char *__restrict__ out)
 {
     const long long idx = (long long)blockIdx.x * kJfThreads + threadIdx.x;
@@ -450,7 +596,8 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_rgb(JfifGeom g, const unsig
     const unsigned char *pl = planes + seg * g.plane_bytes;
     const int Y = pl[(long long)y * g.yw + x];
     const unsigned char *cbp = pl + (long long)g.yh * g.yw, *crp = cbp + (long long)g.ch * g.cw;
-    const int cb = jf_chroma(g, cbp, y, x) - 128, cr = jf_chroma(g, crp, y, x) - 128;
+    const int wc = (g.W + HS - 1) / HS, hc = (g.H + VS - 1) / VS;
+    const int cb = jd_chroma(cbp, g.cw, HS, VS, wc, hc, y, x) - 128, cr = jd_chroma(crp, g.cw, HS, VS, wc, hc, y, x) - 128;
     const int R = Y + ((91881 * cr + 32768) >> 16);
     const int G = Y + ((-22554 * cb + 32768 - 46802 * cr) >> 16);
     const int B = Y + ((116130 * cb + 32768) >> 16);
@@ -485,17 +632,19 @@ static const unsigned char kDht_ac_chroma[178] = {
 static const unsigned char kLumaBase[64] = { 16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99 };
 static const unsigned char kChromaBase[64] = { 17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99 };
 
-bool jfif_geom(int B, int H, int W, int nq, JfifGeom &g)
+bool jfif_geom(int B, int H, int W, int nq, JfifGeom &g, int ss, int opt)
 {
     if (B < 1 || nq < 1 || H < 1 || W < 1 || H > 65535 || W > 65535 || (long long)B * nq > 65535) return false;      // segments index grid.y
+    if (ss < 0 || ss > 2) return false;
     g.B = B; g.H = H; g.W = W; g.nq = nq;
-    g.mcux = (W + 15) / 16; g.mcuy = (H + 15) / 16;
+    g.hs = ss == 0 ? 1 : 2; g.vs = ss == 2 ? 2 : 1; g.opt = opt ? 1 : 0; g.pad_ = 0;
+    g.mcux = (W + 8 * g.hs - 1) / (8 * g.hs); g.mcuy = (H + 8 * g.vs - 1) / (8 * g.vs);
     g.ybx = (W + 7) / 8; g.yby = (H + 7) / 8;
-    g.yw = 16 * g.mcux; g.yh = 16 * g.mcuy;               // luma planes cover every MCU (dummy blocks are never written)
+    g.yw = 8 * g.hs * g.mcux; g.yh = 8 * g.vs * g.mcuy;   // luma planes cover every MCU (dummy blocks are never written)
     g.cw = 8 * g.mcux; g.ch = 8 * g.mcuy;
     g.n_mcu = (long long)g.mcux * g.mcuy;
-    g.nblk = 6 * g.n_mcu;
-    g.stream_words = (g.nblk * kJfifBlockWords + 2 + 15) / 16 * 16;
+    g.nblk = (g.hs * g.vs + 2) * g.n_mcu;
+    g.stream_words = (g.nblk * (g.opt ? kJfifBlockWordsOpt : kJfifBlockWords) + 2 + 15) / 16 * 16;
     g.n_chunks = g.stream_words * 4 / kJfChunk;
     g.plane_bytes = ((long long)g.yh * g.yw + 2LL * g.ch * g.cw + 255) / 256 * 256;
     return true;
@@ -518,7 +667,27 @@ unsigned long long jfif_carve(void *base, const JfifGeom &g, JfifBufs &w)
     w.fftot = (long long *)take(segs * 8);
     w.total = (long long *)take(8);
     w.planes = (unsigned char *)take(segs * g.plane_bytes);
+    w.hist = nullptr; w.codes = nullptr; w.fhdr = nullptr; w.fhdr_len = nullptr;
+    if (g.opt) {
+        w.hist = (unsigned long long *)take(segs * 4 * kJhSymbols * 8);
+        w.codes = (unsigned *)take(segs * 4 * 256 * 4);
+        w.fhdr = (unsigned char *)take(segs * kJfifHdrMax);
+        w.fhdr_len = (int *)take(segs * 4);
+    }
     return off;
+}
+
+int jfif_huffman_host(const long long *counts, unsigned char *bits, unsigned char *huffval)
+{
+    JhWork w;
+    bool any = false;
+    for (int i = 0; i < 256; i++) {
+        if (counts[i] < 0) return -1;
+        any |= counts[i] > 0;
+        w.freq[i] = counts[i];
+    }
+    if (!any || counts[256] < 0) return -1;
+    return jh_build(w, bits, huffval);
 }
 
 void jfif_quant_tables(int q, int luma[64], int chroma[64])
@@ -535,7 +704,7 @@ static const unsigned char kZzHost[64] = { 0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32,
                                            21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46,
                                            53, 60, 61, 54, 47, 55, 62, 63 };
 
-void jfif_params_host(int q, int H, int W, JfifParams &p)
+void jfif_params_host(int q, int H, int W, JfifParams &p, int ss)
 {
     int t[2][64];
     jfif_quant_tables(q, t[0], t[1]);
@@ -554,7 +723,8 @@ void jfif_params_host(int q, int H, int W, JfifParams &p)
         for (int i = 0; i < 64; i++) o[n++] = (unsigned char)p.qt[c][i];
     }
     seg(0xC0, 15);
-    put({ 8, H >> 8, H & 255, W >> 8, W & 255, 3, 1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1 });
+    put({ 8, H >> 8, H & 255, W >> 8, W & 255, 3, 1, ss == 0 ? 0x11 : ss == 1 ? 0x21 : 0x22, 0, 2, 0x11, 1, 3, 0x11, 1 });
+    p.dht_off = n;
     const struct { int id; const unsigned char *t; int len; } dht[4] = {
         { 0x00, kDht_dc_luma, (int)sizeof kDht_dc_luma }, { 0x10, kDht_ac_luma, (int)sizeof kDht_ac_luma },
         { 0x01, kDht_dc_chroma, (int)sizeof kDht_dc_chroma }, { 0x11, kDht_ac_chroma, (int)sizeof kDht_ac_chroma } };
@@ -570,33 +740,60 @@ void jfif_params_host(int q, int H, int W, JfifParams &p)
 
 static unsigned jf_blocks(long long n) { return (unsigned)((n + kJfThreads - 1) / kJfThreads); }
 
-hipError_t launch_jfif_encode(hipStream_t st, const JfifGeom &g, const JfifBufs &w, const JfifParams *par_host, const unsigned char *rgb,
-                              unsigned char *out, unsigned long long cap, long long *lengths, long long *offsets)
+template <int HS, int VS>
+static hipError_t jf_encode(hipStream_t st, const JfifGeom &g, const JfifBufs &w, const JfifParams *par_host, const unsigned char *rgb,
+                            unsigned char *out, unsigned long long cap, long long *lengths, long long *offsets)
 {
     const long long segs = (long long)g.nq * g.B, nb = segs * g.nblk, nc = segs * g.n_chunks;
     hipError_t e = hipMemcpyAsync(w.par, par_host, sizeof(JfifParams) * g.nq, hipMemcpyHostToDevice, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_jfif_fdct, dim3(jf_blocks((long long)g.B * g.nblk)), dim3(kJfThreads), 0, st, g, rgb, w.dct);
-    hipLaunchKernelGGL(k_jfif_quant, dim3(jf_blocks(nb)), dim3(kJfThreads), 0, st, g, w.par, w.dct, w.coef, w.lens);
+    hipLaunchKernelGGL((k_jfif_fdct<HS, VS>), dim3(jf_blocks((long long)g.B * g.nblk)), dim3(kJfThreads), 0, st, g, rgb, w.dct);
+    hipLaunchKernelGGL((k_jfif_quant<HS, VS>), dim3(jf_blocks(nb)), dim3(kJfThreads), 0, st, g, w.par, w.dct, w.coef, w.lens);
+    if (g.opt) {
+        e = hipMemsetAsync(w.hist, 0, (size_t)segs * 4 * kJhSymbols * 8, st);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((k_jfif_hist<HS, VS>), dim3(jf_blocks(g.nblk), (unsigned)segs), dim3(kJfThreads), 0, st, g, w.coef, w.hist);
+        hipLaunchKernelGGL(k_jfif_tables, dim3((unsigned)segs), dim3(kJfThreads), 0, st, g, w.par, w.hist, w.codes, w.fhdr, w.fhdr_len);
+        hipLaunchKernelGGL((k_jfif_count<HS, VS>), dim3(jf_blocks(nb)), dim3(kJfThreads), 0, st, g, w.coef, w.codes, w.lens);
+    }
     hipLaunchKernelGGL(k_jfif_scan, dim3((unsigned)segs), dim3(kJfScanThreads), 0, st, w.lens, g.nblk, w.boff, w.btot);
     hipLaunchKernelGGL(k_jfif_zero, dim3((unsigned)((g.stream_words + kJfThreads - 1) / kJfThreads), (unsigned)segs), dim3(kJfThreads), 0, st, g,
                        w.btot, w.stream);
-    hipLaunchKernelGGL(k_jfif_emit, dim3(jf_blocks(nb)), dim3(kJfThreads), 0, st, g, w.coef, w.boff, w.btot, w.stream);
+    if (g.opt)
+        hipLaunchKernelGGL((k_jfif_emit<HS, VS, true>), dim3(jf_blocks(nb)), dim3(kJfThreads), 0, st, g, w.coef, w.boff, w.btot, w.codes, w.stream);
+    else
+        hipLaunchKernelGGL((k_jfif_emit<HS, VS, false>), dim3(jf_blocks(nb)), dim3(kJfThreads), 0, st, g, w.coef, w.boff, w.btot, w.codes, w.stream);
     hipLaunchKernelGGL(k_jfif_ffcount, dim3(jf_blocks(nc)), dim3(kJfThreads), 0, st, g, w.btot, w.stream, w.ffcnt);
     hipLaunchKernelGGL(k_jfif_scan, dim3((unsigned)segs), dim3(kJfScanThreads), 0, st, w.ffcnt, g.n_chunks, w.ffpre, w.fftot);
-    hipLaunchKernelGGL(k_jfif_layout, dim3(1), dim3(1), 0, st, g, w.par, w.btot, w.fftot, lengths, offsets, w.total);
+    hipLaunchKernelGGL(k_jfif_layout, dim3(1), dim3(1), 0, st, g, w.par, w.fhdr_len, w.btot, w.fftot, lengths, offsets, w.total);
     if (out)
-        hipLaunchKernelGGL(k_jfif_scatter, dim3(jf_blocks(nc)), dim3(kJfThreads), 0, st, g, w.par, w.btot, w.stream, w.ffpre, lengths, offsets,
-                           out, cap);
+        hipLaunchKernelGGL(k_jfif_scatter, dim3(jf_blocks(nc)), dim3(kJfThreads), 0, st, g, w.par, w.fhdr, w.fhdr_len, w.btot, w.stream, w.ffpre,
+                           lengths, offsets, out, cap);
+    return hipGetLastError();
+}
+
+hipError_t launch_jfif_encode(hipStream_t st, const JfifGeom &g, const JfifBufs &w, const JfifParams *par_host, const unsigned char *rgb,
+                              unsigned char *out, unsigned long long cap, long long *lengths, long long *offsets)
+{
+    if (g.hs == 1) return jf_encode<1, 1>(st, g, w, par_host, rgb, out, cap, lengths, offsets);
+    if (g.vs == 1) return jf_encode<2, 1>(st, g, w, par_host, rgb, out, cap, lengths, offsets);
+    return jf_encode<2, 2>(st, g, w, par_host, rgb, out, cap, lengths, offsets);
+}
+
+template <int HS, int VS>
+static hipError_t jf_recon(hipStream_t st, const JfifGeom &g, const JfifBufs &w, unsigned char *rgb_out)
+{
+    const long long segs = (long long)g.nq * g.B;
+    hipLaunchKernelGGL((k_jfif_idct<HS, VS>), dim3(jf_blocks(segs * g.nblk)), dim3(kJfThreads), 0, st, g, w.par, w.coef, w.planes);
+    hipLaunchKernelGGL((k_jfif_rgb<HS, VS>), dim3(jf_blocks(segs * g.H * g.W)), dim3(kJfThreads), 0, st, g, w.planes, rgb_out);
     return hipGetLastError();
 }
 
 hipError_t launch_jfif_recon(hipStream_t st, const JfifGeom &g, const JfifBufs &w, unsigned char *rgb_out)
 {
-    const long long segs = (long long)g.nq * g.B;
-    hipLaunchKernelGGL(k_jfif_idct, dim3(jf_blocks(segs * g.nblk)), dim3(kJfThreads), 0, st, g, w.par, w.coef, w.planes);
-    hipLaunchKernelGGL(k_jfif_rgb, dim3(jf_blocks(segs * g.H * g.W)), dim3(kJfThreads), 0, st, g, w.planes, rgb_out);
-    return hipGetLastError();
+    if (g.hs == 1) return jf_recon<1, 1>(st, g, w, rgb_out);
+    if (g.vs == 1) return jf_recon<2, 1>(st, g, w, rgb_out);
+    return jf_recon<2, 2>(st, g, w, rgb_out);
 }
 
 }  // namespace aej

@@ -1,6 +1,8 @@
 """Standard (baseline) JPEG on the GPU: the files Pillow writes with ``Image.save(buf, "JPEG", quality=q)`` and the pixels its decoder
 returns for them -- the standard-JPEG side of the reference's comparison (test/analysis/metrics_comparison.py: YCbCr, 4:2:0, 8 x 8
-blocks, quality 10/25/50/75/90).
+blocks, quality 10/25/50/75/90).  ``subsampling=`` ("4:4:4", "4:2:2", "4:2:0" or Pillow's 0, 1, 2) and ``optimize=True`` are Pillow's
+keywords of the same call: the chroma layout, and per file the Huffman tables libjpeg builds from that file's own symbols (built on the
+device: histogram, tables, table-driven emit) instead of the Annex K ones.  The defaults are Pillow's: 4:2:0, not optimised.
 
 ``standard_jpeg_decode_many`` reads such files back -- any baseline file, not only this library's, and with ``progressive=True`` any
 complete progressive file -- on the device, pixel-identical to ``Image.open(file).convert("RGB")`` (csrc/jpegdec.hip, ``aej_jpegdec_*``;
@@ -18,7 +20,9 @@ import numpy as np
 
 from ._lib import get_context
 
-HEADER_CAPACITY = 1024       # SOI .. SOS are 623 bytes
+HEADER_CAPACITY = 1024       # SOI .. SOS are 623 bytes with the Annex K Huffman tables; optimised tables are never longer
+SUBSAMPLING = {"4:4:4": 0, "4:2:2": 1, "4:2:0": 2}
+SUBSAMPLING_NAMES = ("4:4:4", "4:2:2", "4:2:0")
 _ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
                     35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63])
 
@@ -29,12 +33,29 @@ def _check_quality(q):
     return int(q)
 
 
-def headers(quality: int, H: int, W: int) -> bytes:
-    """The markers SOI .. SOS of the file of one (quality, H, W) (aej_jfif_headers_host)."""
+def _check_subsampling(s) -> int:
+    """"4:4:4" / "4:2:2" / "4:2:0" or Pillow's 0 / 1 / 2 -> 0 / 1 / 2"""
+    if isinstance(s, str) and s in SUBSAMPLING:
+        return SUBSAMPLING[s]
+    if isinstance(s, (int, np.integer)) and not isinstance(s, (bool, np.bool_)) and 0 <= int(s) <= 2:
+        return int(s)
+    raise ValueError(f"subsampling {s!r}: '4:4:4', '4:2:2', '4:2:0' or 0, 1, 2 required")
+
+
+def _check_optimize(o) -> bool:
+    if not isinstance(o, (bool, np.bool_)):
+        raise TypeError(f"optimize {o!r}: a bool required")
+    return bool(o)
+
+
+def headers(quality: int, H: int, W: int, subsampling="4:2:0") -> bytes:
+    """The markers SOI .. SOS of the file of one (quality, H, W, subsampling) with the Annex K Huffman tables
+    (aej_jfif_headers_host_opt)."""
     from ._lib import load_library
+    ss = _check_subsampling(subsampling)
     lib = load_library()
     buf = ctypes.create_string_buffer(HEADER_CAPACITY)
-    n = lib.aej_jfif_headers_host(int(quality), int(H), int(W), ctypes.cast(buf, ctypes.c_void_p), HEADER_CAPACITY)
+    n = lib.aej_jfif_headers_host_opt(int(quality), int(H), int(W), ss, ctypes.cast(buf, ctypes.c_void_p), HEADER_CAPACITY)
     if n < 0:
         raise ValueError(f"quality {quality}, {H}x{W}: quality must be in 1..100 and H, W in 1..65535")
     return buf.raw[:n]
@@ -52,6 +73,20 @@ def quant_tables(quality: int) -> Tuple[List[int], List[int]]:
             out.append([int(v) for v in nat])
         i += 2 + n
     return out[0], out[1]
+
+
+def huffman_table(counts) -> Tuple[List[int], List[int]]:
+    """(BITS[1..16], HUFFVAL) of the optimal table libjpeg builds from 257 symbol counts (aej_jfif_huffman_host, host only: the routine
+    the device runs per table).  Entry 256, the reserved all-ones code, is taken as 1."""
+    from ._lib import load_library
+    c = np.ascontiguousarray(np.asarray(counts, np.int64))
+    if c.shape != (257,):
+        raise ValueError(f"257 counts required, got shape {c.shape}")
+    bits, vals = (ctypes.c_uint8 * 16)(), (ctypes.c_uint8 * 256)()
+    n = load_library().aej_jfif_huffman_host(c.ctypes.data, ctypes.addressof(bits), ctypes.addressof(vals), 256)
+    if n < 0:
+        raise ValueError("counts must be >= 0 and not all zero")
+    return list(bits), list(vals[:n])
 
 
 def _to_u8(ctx, x):
@@ -81,32 +116,33 @@ def _to_u8(ctx, x):
 class _Encoded:
     """One aej_jfif_encode_batch: the workspace (it holds the coefficients the reconstruction reads), lengths [Q, B], optional bytes."""
 
-    def __init__(self, ctx, x_u8, qualities, want_bytes):
+    def __init__(self, ctx, x_u8, qualities, want_bytes, subsampling=2, optimize=False):
         t, lib = ctx.torch, ctx.lib
         self.ctx, self.qualities = ctx, [_check_quality(q) for q in qualities]
+        self.ss, self.opt = ss, opt = _check_subsampling(subsampling), int(_check_optimize(optimize))
         if not self.qualities:
             raise ValueError("at least one quality required")
         B, H, W = (int(v) for v in x_u8.shape[:3])
         self.B, self.H, self.W, Q = B, H, W, len(self.qualities)
         if not (1 <= H <= 65535 and 1 <= W <= 65535):
             raise ValueError(f"{H}x{W}: baseline JPEG needs 1 <= H, W <= 65535")
-        nbytes = int(lib.aej_jfif_workspace_bytes(B, H, W, Q))
+        nbytes = int(lib.aej_jfif_workspace_bytes_opt(B, H, W, Q, ss, opt))
         self.ws = ctx.empty((nbytes,), t.uint8)
         q = np.array(self.qualities, np.int32)
         offsets, lengths = ctx.empty((Q * B,), t.int64), ctx.empty((Q * B,), t.int64)
         total = ctypes.c_uint64()
         out, cap = None, 0
         if want_bytes:
-            cap = Q * B * (HEADER_CAPACITY + H * W * 3 // 4)          # most files are far smaller; a miss costs one more call
+            cap = Q * B * (HEADER_CAPACITY + H * W * 3 // (4 if ss == 2 else 2))      # most files are far smaller; a miss costs one more call
             out = ctx.empty((cap,), t.uint8)
-        args = lambda o, c: (ctx.handle, x_u8.data_ptr(), B, H, W, Q, q.ctypes.data, o.data_ptr() if o is not None else None,  # noqa: E731
+        args = lambda o, c: (ctx.handle, x_u8.data_ptr(), B, H, W, Q, q.ctypes.data, ss, opt, o.data_ptr() if o is not None else None,  # noqa: E731
                              ctypes.c_uint64(c), offsets.data_ptr(), lengths.data_ptr(), ctypes.addressof(total), self.ws.data_ptr(),
                              ctypes.c_uint64(nbytes))
-        rc = lib.aej_jfif_encode_batch(*args(out, cap))
+        rc = lib.aej_jfif_encode_batch_opt(*args(out, cap))
         if rc == -4 and out is not None and total.value > cap:        # AEJ_ERR_CAPACITY: run again with the exact size
             cap = int(total.value)
             out = ctx.empty((cap,), t.uint8)
-            rc = lib.aej_jfif_encode_batch(*args(out, cap))
+            rc = lib.aej_jfif_encode_batch_opt(*args(out, cap))
         ctx.check(rc)
         self.lengths = lengths.cpu().numpy().reshape(Q, B)
         self.offsets = offsets.cpu().numpy().reshape(Q, B)
@@ -121,33 +157,37 @@ class _Encoded:
         """device uint8 [Q, B, H, W, 3]: what Pillow's decoder returns for every file"""
         ctx = self.ctx
         rgb = ctx.empty((len(self.qualities), self.B, self.H, self.W, 3), ctx.torch.uint8)
-        ctx.check(ctx.lib.aej_jfif_recon_batch(ctx.handle, self.B, self.H, self.W, len(self.qualities), rgb.data_ptr(), self.ws.data_ptr(),
-                                               ctypes.c_uint64(self.ws.numel())))
+        ctx.check(ctx.lib.aej_jfif_recon_batch_opt(ctx.handle, self.B, self.H, self.W, len(self.qualities), self.ss, self.opt, rgb.data_ptr(),
+                                                   self.ws.data_ptr(), ctypes.c_uint64(self.ws.numel())))
         return rgb
 
 
-def encode_decode(ctx, x_u8, qualities, want_bytes=False) -> _Encoded:
+def encode_decode(ctx, x_u8, qualities, want_bytes=False, subsampling=2, optimize=False) -> _Encoded:
     """The sweep's entry: one encode of device uint8 [B, H, W, 3] for every quality (on ctx's stream)."""
-    return _Encoded(ctx, x_u8, qualities, want_bytes)
+    return _Encoded(ctx, x_u8, qualities, want_bytes, subsampling, optimize)
 
 
-def workspace_bytes(ctx, B, H, W, n_q) -> int:
-    return int(ctx.lib.aej_jfif_workspace_bytes(B, H, W, n_q))
+def workspace_bytes(ctx, B, H, W, n_q, subsampling=2, optimize=False) -> int:
+    return int(ctx.lib.aej_jfif_workspace_bytes_opt(B, H, W, n_q, _check_subsampling(subsampling), int(_check_optimize(optimize))))
 
 
-def standard_jpeg_many(x, quality: int, device: int = 0) -> List[bytes]:
-    """Every image's file, equal to ``PIL.Image.fromarray(u8).save(buf, "JPEG", quality=quality)``.
-    x: uint8 or float32 in [0, 1], [B, H, W, 3] or [H, W, 3], numpy or torch."""
-    q = _check_quality(quality)
+def standard_jpeg_many(x, quality: int, device: int = 0, subsampling="4:2:0", optimize: bool = False) -> List[bytes]:
+    """Every image's file, equal to ``PIL.Image.fromarray(u8).save(buf, "JPEG", quality=quality, subsampling=subsampling,
+    optimize=optimize)``.  x: uint8 or float32 in [0, 1], [B, H, W, 3] or [H, W, 3], numpy or torch.  subsampling: "4:4:4", "4:2:2",
+    "4:2:0" or 0, 1, 2 (ValueError otherwise); optimize: a bool (TypeError otherwise) -- per file the Huffman tables built from its
+    own symbols."""
+    q, ss, opt = _check_quality(quality), _check_subsampling(subsampling), _check_optimize(optimize)
     ctx = get_context(device)
-    return _Encoded(ctx, _to_u8(ctx, x), [q], True).files()[0]
+    return _Encoded(ctx, _to_u8(ctx, x), [q], True, ss, opt).files()[0]
 
 
-def standard_jpeg_batch(x, qualities: Sequence[int], device: int = 0):
+def standard_jpeg_batch(x, qualities: Sequence[int], device: int = 0, subsampling="4:2:0", optimize: bool = False):
     """-> (sizes int64 [B, Q]: len() of every file, decoded uint8 [Q, B, H, W, 3] on the device: Pillow's decode of every file).
-    Colour, down-sampling and DCT run once per image for all the qualities."""
+    Colour, down-sampling and DCT run once per image for all the qualities.  subsampling, optimize: as standard_jpeg_many."""
+    qualities = [_check_quality(q) for q in qualities]
+    ss, opt = _check_subsampling(subsampling), _check_optimize(optimize)
     ctx = get_context(device)
-    enc = _Encoded(ctx, _to_u8(ctx, x), list(qualities), False)
+    enc = _Encoded(ctx, _to_u8(ctx, x), qualities, False, ss, opt)
     return np.ascontiguousarray(enc.lengths.T.astype(np.int64)), enc.decoded()
 
 

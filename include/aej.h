@@ -384,6 +384,25 @@ AEJ_API int aej_jfif_encode_batch(aej_ctx *ctx, const uint8_t *rgb, int batch, i
                                   uint64_t out_capacity, int64_t *offsets, int64_t *lengths, uint64_t *total_host, void *workspace,
                                   uint64_t workspace_bytes);
 AEJ_API int aej_jfif_recon_batch(aej_ctx *ctx, int batch, int H, int W, int n_q, uint8_t *rgb_out, void *workspace, uint64_t workspace_bytes);
+/* The same with Pillow's subsampling= and optimize= keywords: subsampling 0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0 (Pillow's integers; the MCU is
+ * 8 x 8, 16 x 8, 16 x 16 pixels), optimize 0 / 1 = the Annex K Huffman tables / per file the tables libjpeg builds from the counts of that
+ * file's own symbols (T.81 K.2; four DHT segments of variable length, never longer than the Annex K ones).  (2, 0) is exactly the calls
+ * above; any other value is AEJ_ERR_ARG (workspace size 0).  With optimize the tables are built on the device between quantisation and
+ * the bit-offset scan (symbol histogram, one table per wave, bit counts under the new codes); the call still waits once, at its end.
+ * aej_jfif_recon_batch_opt takes the options of the encode that filled `workspace`.
+ * aej_jfif_headers_host_opt: the markers of a file with the Annex K tables (optimize = 0) of that layout.
+ * aej_jfif_huffman_host: HOST only, the routine the device runs per table.  counts_host: 257 symbol counts (entry 256, the reserved
+ *   all-ones code, is taken as 1); ties between equal counts go to the larger symbol.  Writes BITS[1..16] to bits_host[16] and the
+ *   symbols sorted by code length, then value, to huffval_host; returns their number (<= 256).  AEJ_ERR_ARG for a negative count or
+ *   when counts 0..255 are all zero, AEJ_ERR_CAPACITY when capacity is smaller than the number of symbols. */
+AEJ_API uint64_t aej_jfif_workspace_bytes_opt(int batch, int H, int W, int n_q, int subsampling, int optimize);
+AEJ_API int aej_jfif_headers_host_opt(int quality, int H, int W, int subsampling, uint8_t *out_host, int capacity);
+AEJ_API int aej_jfif_huffman_host(const int64_t *counts_host, uint8_t *bits_host, uint8_t *huffval_host, int capacity);
+AEJ_API int aej_jfif_encode_batch_opt(aej_ctx *ctx, const uint8_t *rgb, int batch, int H, int W, int n_q, const int32_t *qualities_host,
+                                      int subsampling, int optimize, uint8_t *out, uint64_t out_capacity, int64_t *offsets, int64_t *lengths,
+                                      uint64_t *total_host, void *workspace, uint64_t workspace_bytes);
+AEJ_API int aej_jfif_recon_batch_opt(aej_ctx *ctx, int batch, int H, int W, int n_q, int subsampling, int optimize, uint8_t *rgb_out,
+                                     void *workspace, uint64_t workspace_bytes);
 
 /* ---- baseline JPEG files decoded on the device (standard_jpeg_decode_many) ---------------------------------------------------------
  * Pixel-identical to PIL.Image.open(file).convert("RGB") with libjpeg-turbo (islow IDCT, fancy up-sampling, fixed-point YCbCr -> RGB).

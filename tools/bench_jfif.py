@@ -1,7 +1,11 @@
 """Standard-JPEG timing: 64 x 4K images through csrc/jfif.hip, per quality and with the five qualities of the reference comparison
 (10, 25, 50, 75, 90) in one call, against Pillow's save + load on a thread pool.
 
-    python tools/bench_jfif.py [--batch 64] [--repeats 3] [--threads 16] [--out FILE]
+    python tools/bench_jfif.py [--batch 64] [--repeats 3] [--threads 16] [--subsampling 4:2:0] [--optimize] [--grouped-only]
+                               [--no-pillow] [--out FILE]
+
+--subsampling / --optimize are Pillow's keywords of the same names, given to both sides; --grouped-only times the five-quality call
+alone and --no-pillow leaves the CPU side out (for A/B runs of the library against itself).
 
 "encode" is aej_jfif_encode_batch writing the files to device memory (the library waits for the total length at its end); "encode+recon"
 adds aej_jfif_recon_batch, Pillow's decode of every file as device uint8.  Neither copies the files back to the host.  Pillow does
@@ -64,21 +68,26 @@ def main():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--subsampling", default="4:2:0", choices=("4:4:4", "4:2:2", "4:2:0"))
+    ap.add_argument("--optimize", action="store_true")
+    ap.add_argument("--grouped-only", action="store_true")
+    ap.add_argument("--no-pillow", action="store_true")
     ap.add_argument("--out")
     a = ap.parse_args()
+    kw = dict(subsampling=a.subsampling, optimize=a.optimize)
     x = images(a.batch)
     ctx = A._lib.get_context(0)
     xd = ctx.to_device(x, torch.uint8)
     gp = a.batch * H * W / 1e9
-    res = {"batch": a.batch, "H": H, "W": W, "per_quality": {}}
+    res = {"batch": a.batch, "H": H, "W": W, "subsampling": a.subsampling, "optimize": a.optimize, "per_quality": {}}
 
     def enc(qs, recon):
-        e = S.encode_decode(ctx, xd, qs, want_bytes=True)
+        e = S.encode_decode(ctx, xd, qs, want_bytes=True, **kw)
         if recon:
             e.decoded()
         return e
 
-    for q in QUALITIES:
+    for q in () if a.grouped_only else QUALITIES:
         te = timed(lambda: enc([q], False), a.repeats)
         tr = timed(lambda: enc([q], True), a.repeats)
         mb = float(enc([q], False).lengths.sum()) / 1e6
@@ -89,18 +98,27 @@ def main():
     te = timed(lambda: enc(list(QUALITIES), False), a.repeats)
     tr = timed(lambda: enc(list(QUALITIES), True), a.repeats)
     n = len(QUALITIES)
-    res["grouped"] = {"encode_ms": te * 1e3, "encode_gps": n * gp / te, "encode_recon_ms": tr * 1e3, "encode_recon_gps": n * gp / tr}
+    res["grouped"] = {"encode_ms": te * 1e3, "encode_gps": n * gp / te, "encode_recon_ms": tr * 1e3, "encode_recon_gps": n * gp / tr,
+                      "file_mb": float(enc(list(QUALITIES), False).lengths.sum()) / 1e6}
     print(f"5 qualities in one call: encode {te * 1e3:.1f} ms ({n * gp / te:.2f} GP/s), +recon {tr * 1e3:.1f} ms ({n * gp / tr:.2f} GP/s)", flush=True)
+
+    if a.no_pillow:
+        line = json.dumps(res)
+        print(line)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return
 
     # the GPU's files are Pillow's: check one image per quality before timing Pillow
     for q in QUALITIES:
         buf = io.BytesIO()
-        Image.fromarray(x[0]).save(buf, "JPEG", quality=q)
-        assert A.standard_jpeg_many(x[:1], q)[0] == buf.getvalue(), q
+        Image.fromarray(x[0]).save(buf, "JPEG", quality=q, **kw)
+        assert A.standard_jpeg_many(x[:1], q, **kw)[0] == buf.getvalue(), q
 
     def pil_one(i, q, load):
         buf = io.BytesIO()
-        Image.fromarray(x[i]).save(buf, "JPEG", quality=q)
+        Image.fromarray(x[i]).save(buf, "JPEG", quality=q, **kw)
         if load:
             buf.seek(0)
             np.asarray(Image.open(buf).convert("RGB"))
