@@ -234,6 +234,45 @@ int jfif_huffman_host(const long long *counts, unsigned char *bits, unsigned cha
 hipError_t launch_jfif_encode(hipStream_t st, const JfifGeom &g, const JfifBufs &w, const JfifParams *par_host, const unsigned char *rgb,
                               unsigned char *out, unsigned long long cap, long long *lengths, long long *offsets);
 hipError_t launch_jfif_recon(hipStream_t st, const JfifGeom &g, const JfifBufs &w, unsigned char *rgb_out);
+// the stages before entropy coding alone: parameters up, colour / down-sampling / FDCT, quantisation -> w.coef (w.lens is scratch)
+hipError_t launch_jfif_coefs(hipStream_t st, const JfifGeom &g, const JfifBufs &w, const JfifParams *par_host, const unsigned char *rgb);
+
+// jfifprog.hip: the progressive file Pillow writes with progressive=True from the same coefficients (aej_jfif_*_prog)
+constexpr int kJfpMaxScans = 10;       // jpeg_simple_progression of a three-component file
+constexpr int kJfpPiece = 576;         // bytes that bound the markers before one scan's data: two DHT of 5 + 16 + 256 and an SOS of 14
+struct JfpScan {
+    int Ss, Se, Ah, Al;
+    int comp, tbl;                     // -1: every block in MCU order, else 0 Y / 1 Cb / 2 Cr in the component's raster order; first table slot
+    long long n, ioff;                 // blocks, and the first of them among the file's items
+    long long woff, wcap, coff;        // the scan's stream: first word, words, first 64-byte chunk
+};
+struct JfpGeom {
+    int segs, hs, vs, nchroma;         // files (quality x image); luma sampling factors; chroma blocks per MCU (0: the testing entry's plain list)
+    int mcux, ybx, nscan, ntab;
+    int raw, B;                        // raw: no markers, the scan bytes alone (the testing entry); images per quality
+    long long nblk, T, nmax;           // coefficient blocks per file; items per file (the sum of the scans' blocks); the longest scan
+    long long stream_words, n_chunks;
+    JfpScan sc[kJfpMaxScans];
+};
+struct JfpBufs {
+    unsigned short *flags;             // [seg][T] what each block leaves pending (k_jfp_facts)
+    unsigned long long *pre;           // [seg][T + 1] prefix sums: of je_pack for the partition, afterwards of the bit counts
+    int *plen, *lens;                  // [seg][T] blocks of the piece an item opens (0: opens none); bits of an item
+    unsigned *stream; int *ffcnt; unsigned long long *ffpre;
+    unsigned long long *hist; unsigned *codes; unsigned char *fhdr; int *fhdr_len, *cuts;
+    long long *total;
+};
+bool jfifprog_geom(const JfifGeom &g, JfpGeom &p);
+unsigned long long jfifprog_carve(void *base, const JfifGeom &g, const JfpGeom &p, JfifBufs &w, JfpBufs &pw);
+hipError_t launch_jfifprog_encode(hipStream_t st, const JfifGeom &g, const JfpGeom &p, const JfifBufs &w, const JfpBufs &pw,
+                                  const JfifParams *par_host, const unsigned char *rgb, unsigned char *out, unsigned long long cap,
+                                  long long *lengths, long long *offsets);
+// one scan over n blocks of given coefficients (int16 [n][64], zigzag order): the padded, stuffed scan bytes, the counts of its
+// symbols [257] and its cuts (by kJeMaxRun, by kJeMaxDeferred).  -> 0, or AEJ_ERR_ARG / AEJ_ERR_CAPACITY (out_len is set)
+int jfifprog_scan_host(const short *coefs, long long n, int Ss, int Se, int Ah, int Al, unsigned char *out, unsigned long long cap,
+                       unsigned long long *out_len, long long *counts, long long *cuts);
+int jfifprog_scan_device(hipStream_t st, const short *coefs_host, long long n, int Ss, int Se, int Ah, int Al, unsigned char *out_host,
+                         unsigned long long cap, unsigned long long *out_len, long long *counts, long long *cuts, hipError_t *err);
 
 }  // namespace aej
 

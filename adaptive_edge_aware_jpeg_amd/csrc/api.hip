@@ -2137,6 +2137,97 @@ extern "C" int aej_jfif_recon_batch(aej_ctx *ctx, int batch, int H, int W, int n
     return aej_jfif_recon_batch_opt(ctx, batch, H, W, n_q, 2, 0, rgb_out, workspace, workspace_bytes);
 }
 
+// ---- the progressive file of the same coefficients (jfifprog.hip) --------------------------------------------------------------------------
+extern "C" uint64_t aej_jfif_workspace_bytes_prog(int batch, int H, int W, int n_q, int subsampling)
+{
+    JfifGeom g;
+    JfpGeom p;
+    if (!jfif_geom(batch, H, W, n_q, g, subsampling, 0) || !jfifprog_geom(g, p)) return 0;
+    JfifBufs w;
+    JfpBufs pw;
+    return jfifprog_carve(nullptr, g, p, w, pw);
+}
+
+extern "C" int aej_jfif_encode_batch_prog(aej_ctx *ctx, const uint8_t *rgb, int batch, int H, int W, int n_q, const int32_t *qualities_host,
+                                          int subsampling, uint8_t *out, uint64_t out_capacity, int64_t *offsets, int64_t *lengths,
+                                          uint64_t *total_host, void *workspace, uint64_t workspace_bytes)
+{
+    if (!ctx) return AEJ_ERR_ARG;
+    JfifGeom g;
+    JfpGeom p;
+    int rc = jfif_args(ctx, __func__, batch, H, W, n_q, subsampling, 0, g);
+    if (rc) return rc;
+    if (!jfifprog_geom(g, p)) return fail(ctx, AEJ_ERR_ARG, "%s: bad shape", __func__);
+    if (!rgb || !qualities_host || !offsets || !lengths || !total_host || !workspace) return fail(ctx, AEJ_ERR_ARG, "%s: NULL buffer", __func__);
+    std::vector<JfifParams> par(n_q);
+    for (int i = 0; i < n_q; i++) {
+        if (qualities_host[i] < 1 || qualities_host[i] > 100) return fail(ctx, AEJ_ERR_ARG, "%s: quality %d outside 1..100", __func__, qualities_host[i]);
+        jfif_params_host(qualities_host[i], H, W, par[i], subsampling);
+        unsigned char *sof = par[i].hdr + par[i].dht_off - 19;      // the frame header is the last segment before the tables: SOF0 -> SOF2
+        if (par[i].dht_off < 19 || sof[0] != 0xFF || sof[1] != 0xC0) return fail(ctx, AEJ_ERR_STATE, "%s: no SOF0 segment before the tables", __func__);
+        sof[1] = 0xC2;
+    }
+    JfifBufs w;
+    JfpBufs pw;
+    const unsigned long long need = jfifprog_carve(workspace, g, p, w, pw);
+    if (need > workspace_bytes) return fail(ctx, AEJ_ERR_CAPACITY, "workspace too small: need %llu bytes, got %llu", need, (unsigned long long)workspace_bytes);
+    AEJ_HIP_CHECK(hipSetDevice(ctx->device));
+    AEJ_HIP_CHECK(launch_jfifprog_encode(ctx->stream, g, p, w, pw, par.data(), rgb, out, out_capacity, (long long *)lengths, (long long *)offsets));
+    long long total = 0;
+    AEJ_HIP_CHECK(hipMemcpyAsync(&total, pw.total, 8, hipMemcpyDeviceToHost, ctx->stream));
+    AEJ_HIP_CHECK(hipStreamSynchronize(ctx->stream));     // also keeps `par` alive until its upload has run
+    *total_host = (uint64_t)total;
+    if (out && (uint64_t)total > out_capacity)
+        return fail(ctx, AEJ_ERR_CAPACITY, "%s: the files need %lld bytes, the output holds %llu (nothing was written)", __func__, total,
+                    (unsigned long long)out_capacity);
+    return 0;
+}
+
+extern "C" int aej_jfif_recon_batch_prog(aej_ctx *ctx, int batch, int H, int W, int n_q, int subsampling, uint8_t *rgb_out, void *workspace,
+                                         uint64_t workspace_bytes)
+{
+    if (!ctx) return AEJ_ERR_ARG;
+    JfifGeom g;
+    JfpGeom p;
+    int rc = jfif_args(ctx, __func__, batch, H, W, n_q, subsampling, 0, g);
+    if (rc) return rc;
+    if (!jfifprog_geom(g, p)) return fail(ctx, AEJ_ERR_ARG, "%s: bad shape", __func__);
+    if (!rgb_out || !workspace) return fail(ctx, AEJ_ERR_ARG, "%s: NULL buffer", __func__);
+    JfifBufs w;
+    JfpBufs pw;
+    const unsigned long long need = jfifprog_carve(workspace, g, p, w, pw);
+    if (need > workspace_bytes) return fail(ctx, AEJ_ERR_CAPACITY, "workspace too small: need %llu bytes, got %llu", need, (unsigned long long)workspace_bytes);
+    AEJ_HIP_CHECK(hipSetDevice(ctx->device));
+    AEJ_HIP_CHECK(launch_jfif_recon(ctx->stream, g, w, rgb_out));
+    return 0;
+}
+
+extern "C" int aej_test_jfif_prog_scan_host(const int16_t *coefs_host, int64_t n_blocks, int Ss, int Se, int Ah, int Al, uint8_t *out_host,
+                                            uint64_t capacity, uint64_t *out_len_host, int64_t *counts_host, int64_t *cuts_host)
+{
+    unsigned long long len = 0;
+    const int rc = jfifprog_scan_host(coefs_host, n_blocks, Ss, Se, Ah, Al, out_host, capacity, &len, (long long *)counts_host, (long long *)cuts_host);
+    if (out_len_host) *out_len_host = len;
+    return rc;
+}
+
+extern "C" int aej_test_jfif_prog_scan(aej_ctx *ctx, const int16_t *coefs_host, int64_t n_blocks, int Ss, int Se, int Ah, int Al, uint8_t *out_host,
+                                       uint64_t capacity, uint64_t *out_len_host, int64_t *counts_host, int64_t *cuts_host)
+{
+    if (!ctx) return AEJ_ERR_ARG;
+    if (call_in_flight(ctx)) return fail(ctx, AEJ_ERR_STATE, "%s between aej_encode_batch_begin and aej_encode_batch_end", __func__);
+    AEJ_HIP_CHECK(hipSetDevice(ctx->device));
+    unsigned long long len = 0;
+    hipError_t e = hipSuccess;
+    const int rc = jfifprog_scan_device(ctx->stream, coefs_host, n_blocks, Ss, Se, Ah, Al, out_host, capacity, &len, (long long *)counts_host,
+                                        (long long *)cuts_host, &e);
+    if (out_len_host) *out_len_host = len;
+    if (rc == AEJ_ERR_HIP) AEJ_HIP_CHECK(e);
+    if (rc == AEJ_ERR_ARG) return fail(ctx, rc, "%s: bad scan parameters or coefficients", __func__);
+    if (rc == AEJ_ERR_CAPACITY) return fail(ctx, rc, "%s: the scan needs %llu bytes", __func__, len);
+    return rc;
+}
+
 // ---- baseline JPEG files decoded on the device (jpegdec.hip) --------------------------------------------------------------------------
 extern "C" int aej_jpegdec_parse_host(const uint8_t *data_host, uint64_t nbytes, aej_jpegdec_desc *desc_host, char *msg, int msg_capacity)
 {

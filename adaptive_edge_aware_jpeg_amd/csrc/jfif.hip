@@ -781,6 +781,24 @@ hipError_t launch_jfif_encode(hipStream_t st, const JfifGeom &g, const JfifBufs 
 }
 
 template <int HS, int VS>
+static hipError_t jf_coefs(hipStream_t st, const JfifGeom &g, const JfifBufs &w, const JfifParams *par_host, const unsigned char *rgb)
+{
+    hipError_t e = hipMemcpyAsync(w.par, par_host, sizeof(JfifParams) * g.nq, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_jfif_fdct<HS, VS>), dim3(jf_blocks((long long)g.B * g.nblk)), dim3(kJfThreads), 0, st, g, rgb, w.dct);
+    hipLaunchKernelGGL((k_jfif_quant<HS, VS>), dim3(jf_blocks((long long)g.nq * g.B * g.nblk)), dim3(kJfThreads), 0, st, g, w.par, w.dct, w.coef,
+                       w.lens);
+    return hipGetLastError();
+}
+
+hipError_t launch_jfif_coefs(hipStream_t st, const JfifGeom &g, const JfifBufs &w, const JfifParams *par_host, const unsigned char *rgb)
+{
+    if (g.hs == 1) return jf_coefs<1, 1>(st, g, w, par_host, rgb);
+    if (g.vs == 1) return jf_coefs<2, 1>(st, g, w, par_host, rgb);
+    return jf_coefs<2, 2>(st, g, w, par_host, rgb);
+}
+
+template <int HS, int VS>
 static hipError_t jf_recon(hipStream_t st, const JfifGeom &g, const JfifBufs &w, unsigned char *rgb_out)
 {
     const long long segs = (long long)g.nq * g.B;

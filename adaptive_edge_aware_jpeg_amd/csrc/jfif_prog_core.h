@@ -1,0 +1,228 @@
+// jfif_prog_core.h -- the Annex G (progressive) entropy coder as libjpeg's jcphuff.c runs it, written once as host + device functions so
+// that aej_test_jfif_prog_scan_host steps through the text the kernels of jfifprog.hip run.
+//
+// libjpeg codes a scan serially: an end-of-band run (EOBRUN) and the correction bits deferred behind it (BE) pass from block to block.
+// Here a block is coded on its own (je_dc_*, je_ac_first, je_ac_refine report what it emits to a sink and what it leaves pending), and
+// the state between blocks is a partition of the scan into pieces:
+//   a block "joins" when it ends with zeros or deferred bits pending (r > 0 || BR > 0); a block that emits no symbol always joins;
+//   a chain is a joining block followed by the blocks that emit nothing, up to the next block that emits; libjpeg's run cannot
+//   outlive the chain, because a block's first symbol flushes it;
+//   within a chain libjpeg flushes when the run reaches 0x7FFF blocks or more than 937 deferred bits are pending; each flush ends a
+//   piece (je_chain_end, je_piece_end: binary searches over an exclusive prefix sum of packed (break, BR) values, je_pack);
+//   the stream is then, block after block: the block's own symbols, the EOBn symbol of the piece it opens, its deferred bits.
+#pragma once
+#include <stdint.h>
+
+#ifndef AEJ_HD
+#define AEJ_HD __host__ __device__
+#endif
+
+namespace aej {
+
+constexpr int kJeMaxRun = 0x7FFF;      // blocks in one end-of-band run
+constexpr int kJeMaxDeferred = 937;    // MAX_CORR_BITS - DCTSIZE2 + 1: a run is flushed once more bits than this are deferred
+constexpr int kJeMaxCoef = 2047;       // |coefficient| the bit bounds below hold for (8-bit JPEG stays within 1023 AC, 1024 DC)
+constexpr int kJeBrShift = 36;         // je_pack: deferred bits in the low 36 bits, breaks above
+
+struct JeBlock {
+    int e, r, br;                      // emits a symbol; zeros pending at the end of the band; correction bits pending
+    unsigned long long brbits;         // those bits, the first one highest
+};
+
+AEJ_HD inline int je_nbits(int v)      // v >= 0
+{
+    int n = 0;
+    while (v) { n++; v >>= 1; }
+    return n;
+}
+
+// bits that bound one block of a scan (|coefficients| <= kJeMaxCoef): DC first 16 + 12; DC refinement 1; AC first 16 + 11 per
+// coefficient (a ZRL stands for 16 of them); AC refinement 16 + 1 per coefficient; the EOBn symbol 16 + 14
+AEJ_HD inline int je_block_bound(int Ss, int Se, int Ah)
+{
+    if (Ss == 0) return Ah ? 1 : 28;
+    return (Ah ? 17 : 27) * (Se - Ss + 1) + 30;
+}
+
+// A sink takes sym(s): one Huffman symbol; bits(v, n): n <= 16 raw bits; many(v, n): n <= 63 raw bits, the first one highest.
+template <class Sink>
+AEJ_HD inline void je_dc_first(int cur, int prev, int Al, Sink &s)      // prev: the component's block before in scan order (0 at the start)
+{
+    const int diff = (cur >> Al) - (prev >> Al), n = je_nbits(diff < 0 ? -diff : diff);
+    s.sym(n);
+    if (n) s.bits((unsigned)(diff < 0 ? diff - 1 : diff) & ((1u << n) - 1), n);
+}
+template <class Sink>
+AEJ_HD inline void je_dc_refine(int cur, int Al, Sink &s) { s.bits((unsigned)(cur >> Al) & 1u, 1); }
+
+template <class Sink>
+AEJ_HD inline JeBlock je_ac_first(const short *c, int Ss, int Se, int Al, Sink &s)
+{
+    JeBlock b = { 0, 0, 0, 0 };
+    int r = 0;
+    for (int k = Ss; k <= Se; k++) {
+        const int v = c[k], t = (v < 0 ? -v : v) >> Al;
+        if (t == 0) { r++; continue; }
+        b.e = 1;                                             // here libjpeg flushes the run before: it ended with the block before
+        for (; r > 15; r -= 16) s.sym(0xF0);
+        const int n = je_nbits(t);
+        s.sym((r << 4) | n);
+        s.bits((unsigned)(v < 0 ? ~t : t) & ((1u << n) - 1), n);
+        r = 0;
+    }
+    b.r = r;
+    return b;
+}
+
+template <class Sink>
+AEJ_HD inline JeBlock je_ac_refine(const short *c, int Ss, int Se, int Al, Sink &s)
+{
+    JeBlock b = { 0, 0, 0, 0 };
+    int eob = -1, r = 0, br = 0;
+    unsigned long long bb = 0;
+    for (int k = Ss; k <= Se; k++) {
+        const int v = c[k];
+        if (((v < 0 ? -v : v) >> Al) == 1) eob = k;
+    }
+    for (int k = Ss; k <= Se; k++) {
+        const int v = c[k], a = (v < 0 ? -v : v) >> Al;
+        if (a == 0) { r++; continue; }
+        while (r > 15 && k <= eob) {                         // a ZRL that cannot be folded into the end of band takes the buffered bits
+            b.e = 1;
+            s.sym(0xF0);
+            r -= 16;
+            s.many(bb, br);
+            bb = 0; br = 0;
+        }
+        if (a > 1) {                                         // already non-zero: its next bit waits for the next symbol
+            bb = (bb << 1) | (unsigned)(a & 1);
+            br++;
+            continue;
+        }
+        b.e = 1;
+        s.sym((r << 4) | 1);
+        s.bits(v < 0 ? 0u : 1u, 1);
+        s.many(bb, br);
+        bb = 0; br = 0; r = 0;
+    }
+    b.r = r; b.br = br; b.brbits = bb;
+    return b;
+}
+
+template <class Sink>
+AEJ_HD inline void je_eobrun(int run, Sink &s)              // the EOBn symbol of a piece of `run` >= 1 blocks
+{
+    const int n = je_nbits(run) - 1;
+    s.sym(n << 4);
+    if (n) s.bits((unsigned)run & ((1u << n) - 1), n);
+}
+
+// ---- the partition -------------------------------------------------------------------------------------------------------------------
+// value of one block of an AC scan for the prefix sum: a break (the block does not continue the chain of the block before: it is the
+// first of the scan, it emits, or the block before left nothing pending) and its pending correction bits
+AEJ_HD inline unsigned long long je_pack(bool first, bool e, bool prev_joins, int br)
+{
+    return ((unsigned long long)(first || e || !prev_joins) << kJeBrShift) | (unsigned long long)br;
+}
+// P: exclusive prefix sums of je_pack over the n blocks of a scan, n + 1 entries (only differences are used, so P may be a window
+// of a longer sum).  The chain that starts at block s ends before the first break after s.
+AEJ_HD inline long long je_chain_end(const unsigned long long *P, long long s, long long n)
+{
+    const unsigned long long base = P[s + 1] >> kJeBrShift;
+    long long lo = s + 1, hi = n;                           // the answer lies in [lo, hi]
+    while (lo < hi) {
+        const long long mid = lo + (hi - lo) / 2;
+        if ((P[mid + 1] >> kJeBrShift) != base) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+// the piece that opens at block p of a chain ending before ce: -> the block after its last.  why: 1 the run reached kJeMaxRun,
+// 2 more than kJeMaxDeferred bits were pending, 0 the chain ended
+AEJ_HD inline long long je_piece_end(const unsigned long long *P, long long p, long long ce, int *why)
+{
+    const unsigned long long mask = (1ull << kJeBrShift) - 1, base = P[p] & mask;
+    const bool full = ce - p >= kJeMaxRun;
+    const long long lim = full ? p + kJeMaxRun : ce;
+    long long lo = p, hi = lim;                             // the first j in [p, lim) with more than kJeMaxDeferred bits in p .. j, else lim
+    for (long long step = 16; lo + step < hi; step *= 2) {  // gallop first: where bits are deferred at all the cut is near (from 15 blocks on)
+        if ((P[lo + step] & mask) - base > (unsigned long long)kJeMaxDeferred) { hi = lo + step - 1; break; }
+        lo += step;                                          // blocks p .. lo - 1 hold no cut
+    }
+    while (lo < hi) {
+        const long long mid = lo + (hi - lo) / 2;
+        if ((P[mid + 1] & mask) - base > (unsigned long long)kJeMaxDeferred) hi = mid; else lo = mid + 1;
+    }
+    if (lo < lim) {
+        *why = (lo + 1 == lim && full) ? 1 : 2;
+        return lo + 1;
+    }
+    *why = full ? 1 : 0;
+    return lim;
+}
+
+// ---- big-endian bit writer into zeroed 32-bit words (stream byte order in memory); on the device words shared with neighbouring
+// blocks are ORed in atomically; stores beyond `limit` words are dropped
+AEJ_HD inline unsigned je_bswap(unsigned v) { return (v >> 24) | ((v >> 8) & 0xFF00u) | ((v << 8) & 0xFF0000u) | (v << 24); }
+struct JeBits {
+    unsigned *w;
+    long long wi, limit;
+    unsigned long long acc;
+    int n;
+    AEJ_HD JeBits(unsigned *words, long long pos, long long lim) : w(words), wi(pos >> 5), limit(lim), acc(0), n((int)(pos & 31)) {}
+    AEJ_HD inline void word(unsigned v)
+    {
+        if (v != 0 && wi < limit) {                          // the words start as 0: an item that writes no bit touches no memory
+#if defined(__HIP_DEVICE_COMPILE__)
+            atomicOr(w + wi, je_bswap(v));
+#else
+            w[wi] |= je_bswap(v);
+#endif
+        }
+        wi++;
+    }
+    AEJ_HD inline void put(unsigned code, int len)          // len <= 32, code < 2^len
+    {
+        if (len == 0) return;
+        acc = (acc << len) | code;
+        n += len;
+        if (n >= 32) {
+            n -= 32;
+            word((unsigned)(acc >> n));
+            acc &= (1ull << n) - 1;
+        }
+    }
+    AEJ_HD inline void finish()
+    {
+        if (n > 0) word((unsigned)(acc << (32 - n)));
+    }
+};
+
+// sinks.  codes: (code << 8) | length per symbol (jh_codes)
+struct JeNull {
+    AEJ_HD inline void sym(int) {}
+    AEJ_HD inline void bits(unsigned, int) {}
+    AEJ_HD inline void many(unsigned long long, int) {}
+};
+struct JeLen {
+    const unsigned *codes;
+    int total;
+    AEJ_HD inline void sym(int s) { total += (int)(codes[s] & 255); }
+    AEJ_HD inline void bits(unsigned, int n) { total += n; }
+    AEJ_HD inline void many(unsigned long long, int n) { total += n; }
+};
+struct JeEmit {
+    const unsigned *codes;
+    JeBits bw;
+    AEJ_HD inline void sym(int s) { bw.put(codes[s] >> 8, (int)(codes[s] & 255)); }
+    AEJ_HD inline void bits(unsigned v, int n) { bw.put(v, n); }
+    AEJ_HD inline void many(unsigned long long v, int n)
+    {
+        if (n > 32) {
+            bw.put((unsigned)(v >> 32), n - 32);
+            n = 32;
+        }
+        bw.put((unsigned)(v & 0xFFFFFFFFull), n);
+    }
+};
+
+}  // namespace aej

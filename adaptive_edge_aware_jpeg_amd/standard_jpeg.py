@@ -2,7 +2,9 @@
 returns for them -- the standard-JPEG side of the reference's comparison (test/analysis/metrics_comparison.py: YCbCr, 4:2:0, 8 x 8
 blocks, quality 10/25/50/75/90).  ``subsampling=`` ("4:4:4", "4:2:2", "4:2:0" or Pillow's 0, 1, 2) and ``optimize=True`` are Pillow's
 keywords of the same call: the chroma layout, and per file the Huffman tables libjpeg builds from that file's own symbols (built on the
-device: histogram, tables, table-driven emit) instead of the Annex K ones.  The defaults are Pillow's: 4:2:0, not optimised.
+device: histogram, tables, table-driven emit) instead of the Annex K ones.  ``progressive=True`` is Pillow's keyword too: the SOF2 file
+of libjpeg's ten-scan simple progression, its Annex G entropy coder run on the device (csrc/jfifprog.hip, ``aej_jfif_*_prog``); the
+coefficients, and so the decoded pixels, are those of the baseline file.  The defaults are Pillow's: 4:2:0, not optimised, baseline.
 
 ``standard_jpeg_decode_many`` reads such files back -- any baseline file, not only this library's, and with ``progressive=True`` any
 complete progressive file -- on the device, pixel-identical to ``Image.open(file).convert("RGB")`` (csrc/jpegdec.hip, ``aej_jpegdec_*``;
@@ -21,6 +23,7 @@ import numpy as np
 from ._lib import get_context
 
 HEADER_CAPACITY = 1024       # SOI .. SOS are 623 bytes with the Annex K Huffman tables; optimised tables are never longer
+PROGRESSIVE_HEADER_CAPACITY = 4096   # SOI .. SOF2, ten SOS and eleven DHT, each of them no longer than 5 + 16 + 256 bytes at its largest
 SUBSAMPLING = {"4:4:4": 0, "4:2:2": 1, "4:2:0": 2}
 SUBSAMPLING_NAMES = ("4:4:4", "4:2:2", "4:2:0")
 _ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
@@ -46,6 +49,12 @@ def _check_optimize(o) -> bool:
     if not isinstance(o, (bool, np.bool_)):
         raise TypeError(f"optimize {o!r}: a bool required")
     return bool(o)
+
+
+def _check_progressive(p) -> bool:
+    if not isinstance(p, (bool, np.bool_)):
+        raise TypeError(f"progressive {p!r}: a bool required")
+    return bool(p)
 
 
 def headers(quality: int, H: int, W: int, subsampling="4:2:0") -> bytes:
@@ -116,33 +125,37 @@ def _to_u8(ctx, x):
 class _Encoded:
     """One aej_jfif_encode_batch: the workspace (it holds the coefficients the reconstruction reads), lengths [Q, B], optional bytes."""
 
-    def __init__(self, ctx, x_u8, qualities, want_bytes, subsampling=2, optimize=False):
+    def __init__(self, ctx, x_u8, qualities, want_bytes, subsampling=2, optimize=False, progressive=False):
         t, lib = ctx.torch, ctx.lib
         self.ctx, self.qualities = ctx, [_check_quality(q) for q in qualities]
         self.ss, self.opt = ss, opt = _check_subsampling(subsampling), int(_check_optimize(optimize))
+        self.prog = prog = _check_progressive(progressive)      # a progressive file's tables are always its own: optimize changes nothing
         if not self.qualities:
             raise ValueError("at least one quality required")
         B, H, W = (int(v) for v in x_u8.shape[:3])
         self.B, self.H, self.W, Q = B, H, W, len(self.qualities)
         if not (1 <= H <= 65535 and 1 <= W <= 65535):
             raise ValueError(f"{H}x{W}: baseline JPEG needs 1 <= H, W <= 65535")
-        nbytes = int(lib.aej_jfif_workspace_bytes_opt(B, H, W, Q, ss, opt))
+        nbytes = int(lib.aej_jfif_workspace_bytes_prog(B, H, W, Q, ss) if prog else lib.aej_jfif_workspace_bytes_opt(B, H, W, Q, ss, opt))
         self.ws = ctx.empty((nbytes,), t.uint8)
         q = np.array(self.qualities, np.int32)
         offsets, lengths = ctx.empty((Q * B,), t.int64), ctx.empty((Q * B,), t.int64)
         total = ctypes.c_uint64()
         out, cap = None, 0
         if want_bytes:
-            cap = Q * B * (HEADER_CAPACITY + H * W * 3 // (4 if ss == 2 else 2))      # most files are far smaller; a miss costs one more call
+            hdr = PROGRESSIVE_HEADER_CAPACITY if prog else HEADER_CAPACITY
+            cap = Q * B * (hdr + H * W * 3 // (4 if ss == 2 else 2))      # most files are far smaller; a miss costs one more call
             out = ctx.empty((cap,), t.uint8)
-        args = lambda o, c: (ctx.handle, x_u8.data_ptr(), B, H, W, Q, q.ctypes.data, ss, opt, o.data_ptr() if o is not None else None,  # noqa: E731
+        encode = lib.aej_jfif_encode_batch_prog if prog else lib.aej_jfif_encode_batch_opt
+        args = lambda o, c: (ctx.handle, x_u8.data_ptr(), B, H, W, Q, q.ctypes.data, ss, *(() if prog else (opt,)),  # noqa: E731
+                             o.data_ptr() if o is not None else None,
                              ctypes.c_uint64(c), offsets.data_ptr(), lengths.data_ptr(), ctypes.addressof(total), self.ws.data_ptr(),
                              ctypes.c_uint64(nbytes))
-        rc = lib.aej_jfif_encode_batch_opt(*args(out, cap))
+        rc = encode(*args(out, cap))
         if rc == -4 and out is not None and total.value > cap:        # AEJ_ERR_CAPACITY: run again with the exact size
             cap = int(total.value)
             out = ctx.empty((cap,), t.uint8)
-            rc = lib.aej_jfif_encode_batch_opt(*args(out, cap))
+            rc = encode(*args(out, cap))
         ctx.check(rc)
         self.lengths = lengths.cpu().numpy().reshape(Q, B)
         self.offsets = offsets.cpu().numpy().reshape(Q, B)
@@ -157,37 +170,45 @@ class _Encoded:
         """device uint8 [Q, B, H, W, 3]: what Pillow's decoder returns for every file"""
         ctx = self.ctx
         rgb = ctx.empty((len(self.qualities), self.B, self.H, self.W, 3), ctx.torch.uint8)
+        if self.prog:
+            ctx.check(ctx.lib.aej_jfif_recon_batch_prog(ctx.handle, self.B, self.H, self.W, len(self.qualities), self.ss, rgb.data_ptr(),
+                                                        self.ws.data_ptr(), ctypes.c_uint64(self.ws.numel())))
+            return rgb
         ctx.check(ctx.lib.aej_jfif_recon_batch_opt(ctx.handle, self.B, self.H, self.W, len(self.qualities), self.ss, self.opt, rgb.data_ptr(),
                                                    self.ws.data_ptr(), ctypes.c_uint64(self.ws.numel())))
         return rgb
 
 
-def encode_decode(ctx, x_u8, qualities, want_bytes=False, subsampling=2, optimize=False) -> _Encoded:
+def encode_decode(ctx, x_u8, qualities, want_bytes=False, subsampling=2, optimize=False, progressive=False) -> _Encoded:
     """The sweep's entry: one encode of device uint8 [B, H, W, 3] for every quality (on ctx's stream)."""
-    return _Encoded(ctx, x_u8, qualities, want_bytes, subsampling, optimize)
+    return _Encoded(ctx, x_u8, qualities, want_bytes, subsampling, optimize, progressive)
 
 
-def workspace_bytes(ctx, B, H, W, n_q, subsampling=2, optimize=False) -> int:
+def workspace_bytes(ctx, B, H, W, n_q, subsampling=2, optimize=False, progressive=False) -> int:
+    if _check_progressive(progressive):
+        return int(ctx.lib.aej_jfif_workspace_bytes_prog(B, H, W, n_q, _check_subsampling(subsampling)))
     return int(ctx.lib.aej_jfif_workspace_bytes_opt(B, H, W, n_q, _check_subsampling(subsampling), int(_check_optimize(optimize))))
 
 
-def standard_jpeg_many(x, quality: int, device: int = 0, subsampling="4:2:0", optimize: bool = False) -> List[bytes]:
+def standard_jpeg_many(x, quality: int, device: int = 0, subsampling="4:2:0", optimize: bool = False, progressive: bool = False) -> List[bytes]:
     """Every image's file, equal to ``PIL.Image.fromarray(u8).save(buf, "JPEG", quality=quality, subsampling=subsampling,
-    optimize=optimize)``.  x: uint8 or float32 in [0, 1], [B, H, W, 3] or [H, W, 3], numpy or torch.  subsampling: "4:4:4", "4:2:2",
+    optimize=optimize, progressive=progressive)``.  x: uint8 or float32 in [0, 1], [B, H, W, 3] or [H, W, 3], numpy or torch.  subsampling: "4:4:4", "4:2:2",
     "4:2:0" or 0, 1, 2 (ValueError otherwise); optimize: a bool (TypeError otherwise) -- per file the Huffman tables built from its
-    own symbols."""
-    q, ss, opt = _check_quality(quality), _check_subsampling(subsampling), _check_optimize(optimize)
+    own symbols; progressive: a bool (TypeError otherwise) -- the progressive (SOF2) file of libjpeg's ten scans, whose tables are
+    always its own, so optimize does not change its bytes."""
+    q, ss, opt, prog = _check_quality(quality), _check_subsampling(subsampling), _check_optimize(optimize), _check_progressive(progressive)
     ctx = get_context(device)
-    return _Encoded(ctx, _to_u8(ctx, x), [q], True, ss, opt).files()[0]
+    return _Encoded(ctx, _to_u8(ctx, x), [q], True, ss, opt, prog).files()[0]
 
 
-def standard_jpeg_batch(x, qualities: Sequence[int], device: int = 0, subsampling="4:2:0", optimize: bool = False):
+def standard_jpeg_batch(x, qualities: Sequence[int], device: int = 0, subsampling="4:2:0", optimize: bool = False, progressive: bool = False):
     """-> (sizes int64 [B, Q]: len() of every file, decoded uint8 [Q, B, H, W, 3] on the device: Pillow's decode of every file).
-    Colour, down-sampling and DCT run once per image for all the qualities.  subsampling, optimize: as standard_jpeg_many."""
+    Colour, down-sampling and DCT run once per image for all the qualities.  subsampling, optimize, progressive: as standard_jpeg_many
+    (with progressive the sizes are those of the progressive files; the pixels do not change)."""
     qualities = [_check_quality(q) for q in qualities]
-    ss, opt = _check_subsampling(subsampling), _check_optimize(optimize)
+    ss, opt, prog = _check_subsampling(subsampling), _check_optimize(optimize), _check_progressive(progressive)
     ctx = get_context(device)
-    enc = _Encoded(ctx, _to_u8(ctx, x), qualities, False, ss, opt)
+    enc = _Encoded(ctx, _to_u8(ctx, x), qualities, False, ss, opt, prog)
     return np.ascontiguousarray(enc.lengths.T.astype(np.int64)), enc.decoded()
 
 

@@ -92,10 +92,11 @@ def qmats_blob(color_space, quality_range, block_size_range) -> np.ndarray:
 class StandardResult:
     """Standard JPEG of every image at every quality: [image, quality] arrays; ``bytes`` are len() of Pillow's files."""
 
-    def __init__(self, qualities, n, lpips=False, subsampling="4:2:0", optimize=False):
+    def __init__(self, qualities, n, lpips=False, subsampling="4:2:0", optimize=False, progressive=False):
         self.qualities: List[int] = list(qualities)
         self.subsampling: str = subsampling      # "4:4:4" / "4:2:2" / "4:2:0": the one setting of the sweep
         self.optimize: bool = optimize
+        self.progressive: bool = progressive
         q = len(self.qualities)
         self.psnr = np.full((n, q), np.nan)
         self.ssim = np.full((n, q), np.nan)
@@ -264,7 +265,8 @@ def sweep(images, color_spaces: Sequence[str] = ("YCbCr",), quality_ranges: Sequ
           block_size_ranges: Sequence[Tuple[int, int]] = ((4, 64),), metrics: int = PSNR | SSIM | MS_SSIM, sizes: Optional[str] = "zlib",
           extension: Optional[str] = None, names: Optional[Sequence[str]] = None, device: int = 0, max_bytes: Optional[int] = None,
           workers: Optional[int] = None, lpips: Optional[_lpips.LpipsWeights] = None,
-          standard_qualities: Optional[Sequence[int]] = None, standard_subsampling="4:2:0", standard_optimize: bool = False) -> SweepResult:
+          standard_qualities: Optional[Sequence[int]] = None, standard_subsampling="4:2:0", standard_optimize: bool = False,
+          standard_progressive: bool = False) -> SweepResult:
     """Every (colour space, quality range, block range) cell for every image: metrics and container sizes equal to
     ``EvaluationMetrics.batch(x, decompress_batch(compress_batch(x)))`` and ``len(compress_many(x, extension=...))`` of that cell.
 
@@ -277,7 +279,9 @@ def sweep(images, color_spaces: Sequence[str] = ("YCbCr",), quality_ranges: Sequ
     standard_qualities: JPEG qualities (1..100) -> ``SweepResult.standard``: the same metrics (and LPIPS) of Pillow's standard-JPEG decode
     (``u8 / 255``) against the same originals, and ``compression_ratio = H * W * 3 / len(file)`` (module doc).
     standard_subsampling ("4:4:4", "4:2:2", "4:2:0" or 0, 1, 2), standard_optimize (bool): Pillow's ``subsampling=`` and ``optimize=`` of
-    those files, one setting per sweep, recorded in ``SweepResult.standard.subsampling / .optimize``; they need standard_qualities.  The settings are bound on the device's context of the current stream, as Jpeg does: other
+    those files, one setting per sweep, recorded in ``SweepResult.standard.subsampling / .optimize``; they need standard_qualities.
+    standard_progressive (bool): Pillow's ``progressive=`` of those files (``SweepResult.standard.progressive``): the sizes and ratios
+    are the progressive files', the metrics do not change.  The settings are bound on the device's context of the current stream, as Jpeg does: other
     Jpeg objects bind theirs again on their next call."""
     if sizes not in ("zlib", "gpu", None):
         raise ValueError("sizes must be 'zlib', 'gpu' or None")
@@ -307,8 +311,9 @@ def sweep(images, color_spaces: Sequence[str] = ("YCbCr",), quality_ranges: Sequ
         for i, (h, w) in enumerate(shapes):
             _lpips.check_size(h, w, f"image {i}")
     std_ss, std_opt = _std._check_subsampling(standard_subsampling), _std._check_optimize(standard_optimize)
-    if standard_qualities is None and (std_ss != 2 or std_opt):
-        raise ValueError("standard_subsampling / standard_optimize need standard_qualities")
+    std_prog = _std._check_progressive(standard_progressive)
+    if standard_qualities is None and (std_ss != 2 or std_opt or std_prog):
+        raise ValueError("standard_subsampling / standard_optimize / standard_progressive need standard_qualities")
     if standard_qualities is not None:
         standard_qualities = [_std._check_quality(q) for q in standard_qualities]
         if not standard_qualities:
@@ -320,7 +325,7 @@ def sweep(images, color_spaces: Sequence[str] = ("YCbCr",), quality_ranges: Sequ
     res = SweepResult(cells, names, shapes, metrics, sizes, lpips=lpips is not None)
     if standard_qualities is not None:
         res.standard = StandardResult(standard_qualities, n_img, lpips=lpips is not None, subsampling=_std.SUBSAMPLING_NAMES[std_ss],
-                                      optimize=std_opt)
+                                      optimize=std_opt, progressive=std_prog)
     col = {c: j for j, c in enumerate(cells)}
 
     ctx = get_context(device)
@@ -374,13 +379,13 @@ def sweep(images, color_spaces: Sequence[str] = ("YCbCr",), quality_ranges: Sequ
     return res
 
 
-def _standard_plan(ctx, n_img, H, W, n_q, which, max_bytes, in_bytes, lpips, subsampling=2, optimize=False):
+def _standard_plan(ctx, n_img, H, W, n_q, which, max_bytes, in_bytes, lpips, subsampling=2, optimize=False, progressive=False):
     """(images per call, qualities per call) of the standard-JPEG pass under the byte budget"""
     lib = ctx.lib
 
     def cost(b, g):
         c = in_bytes * b * H * W * 3 + 4 * b * H * W * 3 + b * H * W * 3        # input, its float32 copy, its uint8 form
-        c += _std.workspace_bytes(ctx, b, H, W, g, subsampling, optimize) + g * b * H * W * 3 + 4 * b * H * W * 3     # encode, decoded sets, one float32 set
+        c += _std.workspace_bytes(ctx, b, H, W, g, subsampling, optimize, progressive) + g * b * H * W * 3 + 4 * b * H * W * 3     # encode, decoded sets, one float32 set
         c += max(int(lib.aej_metrics_workspace_bytes(b, H, W)) if which else 0, int(lib.aej_lpips_workspace_bytes(b, H, W)) if lpips else 0)
         if lpips:
             c += int(lib.aej_lpips_features_bytes(b, H, W))
@@ -404,7 +409,7 @@ def _sweep_standard(ctx, st, idx, x_all, is_u8, ten_f32_255, metrics, lpips, max
     lib = ctx.lib
     H, W = int(x_all.shape[1]), int(x_all.shape[2])
     batch, group = _standard_plan(ctx, len(idx), H, W, len(st.qualities), metrics, max_bytes, 1 if is_u8 else 4, lpips is not None,
-                                  st.subsampling, st.optimize)
+                                  st.subsampling, st.optimize, st.progressive)
     for b0 in range(0, len(idx), batch):
         sub = idx[b0:b0 + batch]
         x = x_all[b0:b0 + len(sub)]
@@ -414,7 +419,7 @@ def _sweep_standard(ctx, st, idx, x_all, is_u8, ten_f32_255, metrics, lpips, max
         fa = _lpips.features(ctx, lpips, xf.contiguous()) if lpips is not None else None
         for g0 in range(0, len(st.qualities), group):
             qs = st.qualities[g0:g0 + group]
-            enc = _std.encode_decode(ctx, x_u8, qs, False, st.subsampling, st.optimize)
+            enc = _std.encode_decode(ctx, x_u8, qs, False, st.subsampling, st.optimize, st.progressive)
             dec = enc.decoded()
             scores, lp = [], []
             for s in range(len(qs)):

@@ -404,6 +404,21 @@ AEJ_API int aej_jfif_encode_batch_opt(aej_ctx *ctx, const uint8_t *rgb, int batc
 AEJ_API int aej_jfif_recon_batch_opt(aej_ctx *ctx, int batch, int H, int W, int n_q, int subsampling, int optimize, uint8_t *rgb_out,
                                      void *workspace, uint64_t workspace_bytes);
 
+/* The progressive file of the same call: PIL.Image.fromarray(u8).save(buf, "JPEG", quality=q, subsampling=s, progressive=True) byte for
+ * byte -- SOF2 and libjpeg's jpeg_simple_progression of ten scans (DC with successive approximation, luma 1-5 and 6-63, chroma 1-63,
+ * then the refinements), every scan under its own optimal Huffman table, so optimize= makes no difference, as in Pillow.  Arguments as
+ * the _opt family without `optimize`.  The file is SOI .. SOF2, then per scan [DHT] SOS data, then EOI.  The coefficients are those of
+ * the baseline file, so aej_jfif_recon_batch_prog returns the same pixels; it takes the workspace an aej_jfif_encode_batch_prog of the
+ * same shape filled.  The workspace is larger than the baseline one (aej_jfif_workspace_bytes_prog; 0 for arguments the call refuses).
+ * The Annex G coder runs on the device: what each block emits and leaves pending, a prefix sum, the end-of-band runs cut where
+ * libjpeg cuts them (0x7FFF blocks, more than 937 deferred bits), then histogram, tables, bit offsets and emit per scan. */
+AEJ_API uint64_t aej_jfif_workspace_bytes_prog(int batch, int H, int W, int n_q, int subsampling);
+AEJ_API int aej_jfif_encode_batch_prog(aej_ctx *ctx, const uint8_t *rgb, int batch, int H, int W, int n_q, const int32_t *qualities_host,
+                                       int subsampling, uint8_t *out, uint64_t out_capacity, int64_t *offsets, int64_t *lengths,
+                                       uint64_t *total_host, void *workspace, uint64_t workspace_bytes);
+AEJ_API int aej_jfif_recon_batch_prog(aej_ctx *ctx, int batch, int H, int W, int n_q, int subsampling, uint8_t *rgb_out, void *workspace,
+                                      uint64_t workspace_bytes);
+
 /* ---- baseline JPEG files decoded on the device (standard_jpeg_decode_many) ---------------------------------------------------------
  * Pixel-identical to PIL.Image.open(file).convert("RGB") with libjpeg-turbo (islow IDCT, fancy up-sampling, fixed-point YCbCr -> RGB).
  * Supported: SOF0 / SOF1 with 8-bit samples, one interleaved scan, 1 component (grey, replicated into RGB) or 3 taken as YCbCr with luma

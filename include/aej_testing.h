@@ -26,6 +26,18 @@ AEJ_API int aej_test_jpegprog_coefs(aej_ctx *ctx, const aej_jpegprog_frame *fram
 AEJ_API int aej_test_jpegprog_coefs_host(const aej_jpegprog_frame *frame_host, const aej_jpegprog_scan *scans_host, const uint8_t *file_host,
                                          uint64_t nbytes, int n_levels, int16_t *coef_out_host, uint64_t coef_blocks);
 
+/* One progressive scan over given quantised coefficients (int16 [n_blocks][64] in zigzag order, |value| <= 2047; the blocks are one
+ * component in scan order), for the cases pixels cannot reach: Ss..Se the band (0-0 a DC scan), Ah / Al the successive approximation
+ * (Ah is 0 or Al + 1).  Writes the scan's bytes -- coded under the optimal table of its own symbols, padded with 1-bits, 0xFF stuffed --
+ * to out_host, their number to *out_len_host, the count of every symbol to counts_host[257] and to cuts_host[2] how many end-of-band
+ * runs were cut at 0x7FFF blocks and how many at more than 937 deferred bits.  AEJ_ERR_CAPACITY (with *out_len_host set) when capacity
+ * is too small.  aej_test_jfif_prog_scan_host: HOST only, the per-block and partition routines of csrc/jfif_prog_core.h stepped through
+ * on the CPU.  aej_test_jfif_prog_scan: the kernels of csrc/jfifprog.hip over the same coefficients (all pointers are host memory). */
+AEJ_API int aej_test_jfif_prog_scan_host(const int16_t *coefs_host, int64_t n_blocks, int Ss, int Se, int Ah, int Al, uint8_t *out_host,
+                                         uint64_t capacity, uint64_t *out_len_host, int64_t *counts_host, int64_t *cuts_host);
+AEJ_API int aej_test_jfif_prog_scan(aej_ctx *ctx, const int16_t *coefs_host, int64_t n_blocks, int Ss, int Se, int Ah, int Al, uint8_t *out_host,
+                                    uint64_t capacity, uint64_t *out_len_host, int64_t *counts_host, int64_t *cuts_host);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,10 +1,10 @@
 """Standard-JPEG timing: 64 x 4K images through csrc/jfif.hip, per quality and with the five qualities of the reference comparison
 (10, 25, 50, 75, 90) in one call, against Pillow's save + load on a thread pool.
 
-    python tools/bench_jfif.py [--batch 64] [--repeats 3] [--threads 16] [--subsampling 4:2:0] [--optimize] [--grouped-only]
-                               [--no-pillow] [--out FILE]
+    python tools/bench_jfif.py [--batch 64] [--repeats 3] [--threads 16] [--subsampling 4:2:0] [--optimize] [--progressive]
+                               [--grouped-only] [--no-pillow] [--out FILE]
 
---subsampling / --optimize are Pillow's keywords of the same names, given to both sides; --grouped-only times the five-quality call
+--subsampling / --optimize / --progressive are Pillow's keywords of the same names, given to both sides; --grouped-only times the five-quality call
 alone and --no-pillow leaves the CPU side out (for A/B runs of the library against itself).
 
 "encode" is aej_jfif_encode_batch writing the files to device memory (the library waits for the total length at its end); "encode+recon"
@@ -70,16 +70,17 @@ def main():
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--subsampling", default="4:2:0", choices=("4:4:4", "4:2:2", "4:2:0"))
     ap.add_argument("--optimize", action="store_true")
+    ap.add_argument("--progressive", action="store_true")
     ap.add_argument("--grouped-only", action="store_true")
     ap.add_argument("--no-pillow", action="store_true")
     ap.add_argument("--out")
     a = ap.parse_args()
-    kw = dict(subsampling=a.subsampling, optimize=a.optimize)
+    kw = dict(subsampling=a.subsampling, optimize=a.optimize, progressive=a.progressive)
     x = images(a.batch)
     ctx = A._lib.get_context(0)
     xd = ctx.to_device(x, torch.uint8)
     gp = a.batch * H * W / 1e9
-    res = {"batch": a.batch, "H": H, "W": W, "subsampling": a.subsampling, "optimize": a.optimize, "per_quality": {}}
+    res = {"batch": a.batch, "H": H, "W": W, "subsampling": a.subsampling, "optimize": a.optimize, "progressive": a.progressive, "per_quality": {}}
 
     def enc(qs, recon):
         e = S.encode_decode(ctx, xd, qs, want_bytes=True, **kw)
