@@ -1,0 +1,364 @@
+// api_jpeg.hip -- the standard-JPEG entries of the C ABI (include/aej.h): baseline and progressive files written (aej_jfif_*) and
+// decoded (aej_jpegdec_*, aej_jpegprog_*).  Host code only.
+#include "aej_ctx.h"
+
+using namespace aej;
+
+// ---- baseline JPEG as Pillow / libjpeg-turbo writes it (jfif.hip) --------------------------------------------------------------------
+static int jfif_args(aej_ctx *ctx, const char *fn, int batch, int H, int W, int n_q, int ss, int opt, JfifGeom &g)
+{
+    AEJ_TRY(enter(ctx, fn));
+    if (ss < 0 || ss > 2) return fail(ctx, AEJ_ERR_ARG, "%s: subsampling %d (0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0)", fn, ss);
+    if (opt != 0 && opt != 1) return fail(ctx, AEJ_ERR_ARG, "%s: optimize %d (0 or 1)", fn, opt);
+    if (!jfif_geom(batch, H, W, n_q, g, ss, opt))
+        return fail(ctx, AEJ_ERR_ARG, "%s: bad shape %d x %d x %d with %d qualities (1 <= H, W <= 65535)", fn, batch, H, W, n_q);
+    return 0;
+}
+
+extern "C" uint64_t aej_jfif_workspace_bytes_opt(int batch, int H, int W, int n_q, int subsampling, int optimize)
+{
+    JfifGeom g;
+    if ((optimize != 0 && optimize != 1) || !jfif_geom(batch, H, W, n_q, g, subsampling, optimize)) return 0;
+    JfifBufs w;
+    return jfif_carve(nullptr, g, w);
+}
+
+extern "C" uint64_t aej_jfif_workspace_bytes(int batch, int H, int W, int n_q) { return aej_jfif_workspace_bytes_opt(batch, H, W, n_q, 2, 0); }
+
+extern "C" int aej_jfif_headers_host_opt(int quality, int H, int W, int subsampling, uint8_t *out_host, int capacity)
+{
+    JfifGeom g;
+    if (quality < 1 || quality > 100 || !jfif_geom(1, H, W, 1, g, subsampling, 0) || !out_host) return AEJ_ERR_ARG;
+    JfifParams p;
+    jfif_params_host(quality, H, W, p, subsampling);
+    if (capacity < p.hdr_len) return AEJ_ERR_CAPACITY;
+    memcpy(out_host, p.hdr, p.hdr_len);
+    return p.hdr_len;
+}
+
+extern "C" int aej_jfif_headers_host(int quality, int H, int W, uint8_t *out_host, int capacity)
+{
+    return aej_jfif_headers_host_opt(quality, H, W, 2, out_host, capacity);
+}
+
+extern "C" int aej_jfif_huffman_host(const int64_t *counts_host, uint8_t *bits_host, uint8_t *huffval_host, int capacity)
+{
+    if (!counts_host || !bits_host || !huffval_host || capacity < 0) return AEJ_ERR_ARG;
+    unsigned char bits[16], vals[256];
+    const int n = jfif_huffman_host((const long long *)counts_host, bits, vals);
+    if (n < 0) return AEJ_ERR_ARG;
+    if (n > capacity) return AEJ_ERR_CAPACITY;
+    memcpy(bits_host, bits, 16);
+    memcpy(huffval_host, vals, n);
+    return n;
+}
+
+// One routine writes the baseline files (optimize 0 / 1) and the progressive ones: `prog` adds the scan geometry, carves jfifprog.hip's
+// buffers behind the shared ones, turns the frame marker SOF0 into SOF2 and launches the progressive coder.
+static int jfif_encode(aej_ctx *ctx, const char *fn, bool prog, const uint8_t *rgb, int batch, int H, int W, int n_q, const int32_t *qualities_host,
+                       int subsampling, int optimize, uint8_t *out, uint64_t out_capacity, int64_t *offsets, int64_t *lengths, uint64_t *total_host,
+                       void *workspace, uint64_t workspace_bytes)
+{
+    JfifGeom g;
+    JfpGeom p;
+    AEJ_TRY(jfif_args(ctx, fn, batch, H, W, n_q, subsampling, optimize, g));
+    if (prog && !jfifprog_geom(g, p)) return fail(ctx, AEJ_ERR_ARG, "%s: bad shape", fn);
+    if (!rgb || !qualities_host || !offsets || !lengths || !total_host || !workspace) return null_buffer(ctx, fn);
+    std::vector<JfifParams> par(n_q);
+    for (int i = 0; i < n_q; i++) {
+        if (qualities_host[i] < 1 || qualities_host[i] > 100) return fail(ctx, AEJ_ERR_ARG, "%s: quality %d outside 1..100", fn, qualities_host[i]);
+        jfif_params_host(qualities_host[i], H, W, par[i], subsampling);
+        if (!prog) continue;
+        unsigned char *sof = par[i].hdr + par[i].dht_off - 19;      // the frame header is the last segment before the tables: SOF0 -> SOF2
+        if (par[i].dht_off < 19 || sof[0] != 0xFF || sof[1] != 0xC0) return fail(ctx, AEJ_ERR_STATE, "%s: no SOF0 segment before the tables", fn);
+        sof[1] = 0xC2;
+    }
+    JfifBufs w;
+    JfpBufs pw;
+    AEJ_TRY(check_workspace(ctx, prog ? jfifprog_carve(workspace, g, p, w, pw) : jfif_carve(workspace, g, w), workspace_bytes));
+    AEJ_TRY(bind_device(ctx));
+    if (prog) AEJ_HIP_CHECK(launch_jfifprog_encode(ctx->stream, g, p, w, pw, par.data(), rgb, out, out_capacity, (long long *)lengths, (long long *)offsets));
+    else AEJ_HIP_CHECK(launch_jfif_encode(ctx->stream, g, w, par.data(), rgb, out, out_capacity, (long long *)lengths, (long long *)offsets));
+    long long total = 0;
+    AEJ_HIP_CHECK(hipMemcpyAsync(&total, w.total, 8, hipMemcpyDeviceToHost, ctx->stream));      // (the progressive carve points w.total at its own word)
+    AEJ_HIP_CHECK(hipStreamSynchronize(ctx->stream));     // also keeps `par` alive until its upload has run
+    *total_host = (uint64_t)total;
+    if (out && (uint64_t)total > out_capacity)
+        return fail(ctx, AEJ_ERR_CAPACITY, "%s: the files need %lld bytes, the output holds %llu (nothing was written)", fn, total,
+                    (unsigned long long)out_capacity);
+    return 0;
+}
+
+extern "C" int aej_jfif_encode_batch_opt(aej_ctx *ctx, const uint8_t *rgb, int batch, int H, int W, int n_q, const int32_t *qualities_host,
+                                         int subsampling, int optimize, uint8_t *out, uint64_t out_capacity, int64_t *offsets, int64_t *lengths,
+                                         uint64_t *total_host, void *workspace, uint64_t workspace_bytes)
+{
+    return jfif_encode(ctx, __func__, false, rgb, batch, H, W, n_q, qualities_host, subsampling, optimize, out, out_capacity, offsets, lengths, total_host,
+                       workspace, workspace_bytes);
+}
+
+extern "C" int aej_jfif_encode_batch(aej_ctx *ctx, const uint8_t *rgb, int batch, int H, int W, int n_q, const int32_t *qualities_host, uint8_t *out,
+                                     uint64_t out_capacity, int64_t *offsets, int64_t *lengths, uint64_t *total_host, void *workspace,
+                                     uint64_t workspace_bytes)
+{
+    return aej_jfif_encode_batch_opt(ctx, rgb, batch, H, W, n_q, qualities_host, 2, 0, out, out_capacity, offsets, lengths, total_host, workspace,
+                                     workspace_bytes);
+}
+
+// the reconstruction reads the quantised coefficients either encode left in the workspace: only the carve differs
+static int jfif_recon(aej_ctx *ctx, const char *fn, bool prog, int batch, int H, int W, int n_q, int subsampling, int optimize, uint8_t *rgb_out,
+                      void *workspace, uint64_t workspace_bytes)
+{
+    JfifGeom g;
+    JfpGeom p;
+    AEJ_TRY(jfif_args(ctx, fn, batch, H, W, n_q, subsampling, optimize, g));
+    if (prog && !jfifprog_geom(g, p)) return fail(ctx, AEJ_ERR_ARG, "%s: bad shape", fn);
+    if (!rgb_out || !workspace) return null_buffer(ctx, fn);
+    JfifBufs w;
+    JfpBufs pw;
+    AEJ_TRY(check_workspace(ctx, prog ? jfifprog_carve(workspace, g, p, w, pw) : jfif_carve(workspace, g, w), workspace_bytes));
+    AEJ_TRY(bind_device(ctx));
+    AEJ_HIP_CHECK(launch_jfif_recon(ctx->stream, g, w, rgb_out));
+    return 0;
+}
+
+extern "C" int aej_jfif_recon_batch_opt(aej_ctx *ctx, int batch, int H, int W, int n_q, int subsampling, int optimize, uint8_t *rgb_out,
+                                        void *workspace, uint64_t workspace_bytes)
+{
+    return jfif_recon(ctx, __func__, false, batch, H, W, n_q, subsampling, optimize, rgb_out, workspace, workspace_bytes);
+}
+
+extern "C" int aej_jfif_recon_batch(aej_ctx *ctx, int batch, int H, int W, int n_q, uint8_t *rgb_out, void *workspace, uint64_t workspace_bytes)
+{
+    return aej_jfif_recon_batch_opt(ctx, batch, H, W, n_q, 2, 0, rgb_out, workspace, workspace_bytes);
+}
+
+// ---- the progressive file of the same coefficients (jfifprog.hip) --------------------------------------------------------------------------
+extern "C" uint64_t aej_jfif_workspace_bytes_prog(int batch, int H, int W, int n_q, int subsampling)
+{
+    JfifGeom g;
+    JfpGeom p;
+    if (!jfif_geom(batch, H, W, n_q, g, subsampling, 0) || !jfifprog_geom(g, p)) return 0;
+    JfifBufs w;
+    JfpBufs pw;
+    return jfifprog_carve(nullptr, g, p, w, pw);
+}
+
+extern "C" int aej_jfif_encode_batch_prog(aej_ctx *ctx, const uint8_t *rgb, int batch, int H, int W, int n_q, const int32_t *qualities_host,
+                                          int subsampling, uint8_t *out, uint64_t out_capacity, int64_t *offsets, int64_t *lengths,
+                                          uint64_t *total_host, void *workspace, uint64_t workspace_bytes)
+{
+    return jfif_encode(ctx, __func__, true, rgb, batch, H, W, n_q, qualities_host, subsampling, 0, out, out_capacity, offsets, lengths, total_host, workspace,
+                       workspace_bytes);
+}
+
+extern "C" int aej_jfif_recon_batch_prog(aej_ctx *ctx, int batch, int H, int W, int n_q, int subsampling, uint8_t *rgb_out, void *workspace,
+                                         uint64_t workspace_bytes)
+{
+    return jfif_recon(ctx, __func__, true, batch, H, W, n_q, subsampling, 0, rgb_out, workspace, workspace_bytes);
+}
+
+extern "C" int aej_test_jfif_prog_scan_host(const int16_t *coefs_host, int64_t n_blocks, int Ss, int Se, int Ah, int Al, uint8_t *out_host,
+                                            uint64_t capacity, uint64_t *out_len_host, int64_t *counts_host, int64_t *cuts_host)
+{
+    unsigned long long len = 0;
+    const int rc = jfifprog_scan_host(coefs_host, n_blocks, Ss, Se, Ah, Al, out_host, capacity, &len, (long long *)counts_host, (long long *)cuts_host);
+    if (out_len_host) *out_len_host = len;
+    return rc;
+}
+
+extern "C" int aej_test_jfif_prog_scan(aej_ctx *ctx, const int16_t *coefs_host, int64_t n_blocks, int Ss, int Se, int Ah, int Al, uint8_t *out_host,
+                                       uint64_t capacity, uint64_t *out_len_host, int64_t *counts_host, int64_t *cuts_host)
+{
+    AEJ_TRY(enter(ctx, __func__));
+    AEJ_TRY(bind_device(ctx));
+    unsigned long long len = 0;
+    hipError_t e = hipSuccess;
+    const int rc = jfifprog_scan_device(ctx->stream, coefs_host, n_blocks, Ss, Se, Ah, Al, out_host, capacity, &len, (long long *)counts_host,
+                                        (long long *)cuts_host, &e);
+    if (out_len_host) *out_len_host = len;
+    if (rc == AEJ_ERR_HIP) AEJ_HIP_CHECK(e);
+    if (rc == AEJ_ERR_ARG) return fail(ctx, rc, "%s: bad scan parameters or coefficients", __func__);
+    if (rc == AEJ_ERR_CAPACITY) return fail(ctx, rc, "%s: the scan needs %llu bytes", __func__, len);
+    return rc;
+}
+
+// ---- baseline JPEG files decoded on the device (jpegdec.hip) --------------------------------------------------------------------------
+extern "C" int aej_jpegdec_parse_host(const uint8_t *data_host, uint64_t nbytes, aej_jpegdec_desc *desc_host, char *msg, int msg_capacity)
+{
+    if (!desc_host) return AEJ_ERR_ARG;
+    std::string m;
+    const int rc = jpegdec_parse(data_host, nbytes, *desc_host, m);
+    copy_msg(m, msg, msg_capacity);
+    return rc;
+}
+
+static bool jpegdec_descs_ok(const aej_jpegdec_desc *d, int n)
+{
+    if (!d || n < 1) return false;
+    for (int i = 0; i < n; i++) {
+        const aej_jpegdec_desc &e = d[i];
+        const bool color = e.ncomp == 3 && ((e.hs == 1 && e.vs == 1) || (e.hs == 2 && (e.vs == 1 || e.vs == 2)));
+        if (!(color || (e.ncomp == 1 && e.hs == 1 && e.vs == 1))) return false;
+        if (e.width < 1 || e.height < 1 || e.width > 65535 || e.height > 65535 || e.scan_length < 0) return false;
+        if (e.mcux != (e.width + 8 * e.hs - 1) / (8 * e.hs) || e.mcuy != (e.height + 8 * e.vs - 1) / (8 * e.vs)) return false;
+        if (e.blocks_per_mcu != (e.ncomp == 1 ? 1 : e.hs * e.vs + 2) || e.restart_interval < 0) return false;
+        const long long mcus = (long long)e.mcux * e.mcuy;
+        if (e.n_segments != (e.restart_interval ? (mcus + e.restart_interval - 1) / e.restart_interval : 1)) return false;
+    }
+    return true;
+}
+
+extern "C" uint64_t aej_jpegdec_workspace_bytes(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n)
+{
+    if (!ctx || !jpegdec_descs_ok(descs_host, n)) return 0;
+    std::vector<JdFile> files;
+    JdBufSizes z;
+    jpegdec_layout(descs_host, n, ctx->jd_subseq_bits, files, z);
+    JdBufs w;
+    return jpegdec_carve(nullptr, n, z, w);
+}
+
+extern "C" int aej_jpegdec_batch(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const uint8_t *scans, uint64_t scans_bytes,
+                                 const int64_t *scan_offsets_host, uint8_t *out, uint64_t out_bytes, const int64_t *out_offsets_host,
+                                 int32_t *status, void *workspace, uint64_t workspace_bytes)
+{
+    AEJ_TRY(enter(ctx, __func__));
+    if (!jpegdec_descs_ok(descs_host, n)) return fail(ctx, AEJ_ERR_ARG, "%s: no files, or a descriptor aej_jpegdec_parse_host did not write", __func__);
+    if (!scans || !scan_offsets_host || !out || !out_offsets_host || !status || !workspace) return null_buffer(ctx, __func__);
+    const int S = ctx->jd_subseq_bits;
+    std::vector<JdFile> files;
+    JdBufSizes z;
+    jpegdec_layout(descs_host, n, S, files, z);
+    for (int i = 0; i < n; i++) {
+        const aej_jpegdec_desc &d = descs_host[i];
+        const long long so = scan_offsets_host[i], oo = out_offsets_host[i], ob = (long long)d.width * d.height * 3;
+        if (so < 0 || (uint64_t)so + (uint64_t)d.scan_length > scans_bytes)
+            return fail(ctx, AEJ_ERR_ARG, "%s: file %d: scan outside the scans buffer", __func__, i);
+        if (oo < 0 || (uint64_t)oo + (uint64_t)ob > out_bytes) return fail(ctx, AEJ_ERR_ARG, "%s: file %d: image outside the output", __func__, i);
+        files[i].scan_off = so;
+        files[i].out_off = oo;
+    }
+    JdBufs w;
+    const unsigned long long need = jpegdec_carve(workspace, n, z, w);
+    AEJ_TRY(check_workspace(ctx, need, workspace_bytes));
+    // one upload: files, descriptors, the "last round that changed" word (-1)
+    std::vector<unsigned char> blob(sizeof(JdFile) * n + sizeof(aej_jpegdec_desc) * n + sizeof(int));
+    memcpy(blob.data(), files.data(), sizeof(JdFile) * n);
+    memcpy(blob.data() + sizeof(JdFile) * n, descs_host, sizeof(aej_jpegdec_desc) * n);
+    const int minus1 = -1;
+    memcpy(blob.data() + blob.size() - sizeof(int), &minus1, sizeof(int));
+    long long max_slots = 0;
+    for (const JdFile &f : files) max_slots = std::max(max_slots, f.n_slots);
+    AEJ_TRY(bind_device(ctx));
+    AEJ_HIP_CHECK(launch_jpegdec_begin(ctx->stream, n, z, w, blob.data(), blob.size(), scans, S, status));
+    // sync rounds: kJdSyncBatch launches, then one word read back; more only while the last launched round still changed something.
+    // Each round settles at least the first unsettled subsequence of every segment, so max_slots rounds always suffice.
+    int launched = 0, last = -1;
+    for (;;) {
+        AEJ_HIP_CHECK(launch_jpegdec_sync(ctx->stream, n, z, w, S, launched + 1, kJdSyncBatch));
+        launched += kJdSyncBatch;
+        AEJ_HIP_CHECK(hipMemcpyAsync(ctx->h_flag, w.last_change, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        AEJ_HIP_CHECK(hipStreamSynchronize(ctx->stream));     // also keeps `blob` alive until its upload has run
+        last = ctx->h_flag[0];
+        if (last < launched) break;
+        if (launched > max_slots + kJdSyncBatch)
+            return fail(ctx, AEJ_ERR_STATE, "%s: the Huffman decode did not settle after %d rounds", __func__, launched);
+    }
+    ctx->jd_sync_rounds = last + 1;
+    AEJ_HIP_CHECK(launch_jpegdec_finish(ctx->stream, n, z, w, S, out, status));
+    return 0;
+}
+
+extern "C" int64_t aej_jpegdec_sync_rounds(aej_ctx *ctx)
+{
+    if (!ctx) return AEJ_ERR_ARG;
+    return ctx->jd_sync_rounds;
+}
+
+// ---- progressive JPEG files decoded on the device (jpegprog.hip) ----------------------------------------------------------------------
+extern "C" int aej_jpegprog_parse_host(const uint8_t *data_host, uint64_t nbytes, aej_jpegprog_frame *frame_host, aej_jpegprog_scan *scans_host,
+                                       int scan_capacity, char *msg, int msg_capacity)
+{
+    if (!frame_host) return AEJ_ERR_ARG;
+    std::string m;
+    std::vector<aej_jpegprog_scan> scans;
+    int rc = jpegprog_parse(data_host, nbytes, *frame_host, scans, m);
+    if (rc == 0 && scans_host) {
+        if (scan_capacity < (int)scans.size()) { rc = AEJ_ERR_CAPACITY; m = "scan capacity below the file's " + std::to_string(scans.size()) + " scans"; }
+        else memcpy(scans_host, scans.data(), sizeof(aej_jpegprog_scan) * scans.size());
+    }
+    copy_msg(m, msg, msg_capacity);
+    return rc;
+}
+
+extern "C" uint64_t aej_jpegprog_workspace_bytes(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n)
+{
+    JpLayout y;
+    if (!ctx || !jpegprog_layout(frames_host, scans_host, n, y)) return 0;
+    JpBufs w;
+    return jpegprog_carve(nullptr, y, w);
+}
+
+// levels [0, n_levels) of the entropy stage, then either the reconstruction into `out` or (tests) a copy of the coefficients
+static int jpegprog_run(aej_ctx *ctx, const char *fn, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
+                        const uint8_t *data, uint64_t data_bytes, const int64_t *data_offsets_host, int n_levels, uint8_t *out, uint64_t out_bytes,
+                        const int64_t *out_offsets_host, int16_t *coef_out, uint64_t coef_blocks, int32_t *status, void *workspace,
+                        uint64_t workspace_bytes)
+{
+    if (!ctx) return AEJ_ERR_ARG;
+    AEJ_TRY(refuse_in_flight(ctx, fn));
+    JpLayout y;
+    if (!jpegprog_layout(frames_host, scans_host, n, y))
+        return fail(ctx, AEJ_ERR_ARG, "%s: no files, or descriptors aej_jpegprog_parse_host did not write", fn);
+    if (!data || !data_offsets_host || !status || !workspace || (!out && !coef_out) || (out && !out_offsets_host))
+        return null_buffer(ctx, fn);
+    for (size_t t = 0; t < y.scans.size(); t++) {
+        const long long so = data_offsets_host[y.src[t]];
+        if (so < 0 || (uint64_t)so + (uint64_t)y.sfiles[t].scan_len > data_bytes)
+            return fail(ctx, AEJ_ERR_ARG, "%s: scan %d: bytes outside the data buffer", fn, y.src[t]);
+        y.sfiles[t].scan_off = so;
+    }
+    for (int i = 0; out && i < n; i++) {
+        const long long oo = out_offsets_host[i], ob = (long long)frames_host[i].width * frames_host[i].height * 3;
+        if (oo < 0 || (uint64_t)oo + (uint64_t)ob > out_bytes) return fail(ctx, AEJ_ERR_ARG, "%s: file %d: image outside the output", fn, i);
+        y.ffiles[i].out_off = oo;
+    }
+    if (coef_out && (uint64_t)y.fz.blocks > coef_blocks) return fail(ctx, AEJ_ERR_CAPACITY, "%s: %lld coefficient blocks, room for %llu", fn, y.fz.blocks, (unsigned long long)coef_blocks);
+    JpBufs w;
+    const unsigned long long need = jpegprog_carve(workspace, y, w);
+    AEJ_TRY(check_workspace(ctx, need, workspace_bytes));
+    std::vector<unsigned char> blob;
+    jpegprog_blob(y, &blob);
+    AEJ_TRY(bind_device(ctx));
+    AEJ_HIP_CHECK(launch_jpegprog_entropy(ctx->stream, y, w, blob.data(), blob.size(), data, n_levels, status));
+    if (out) AEJ_HIP_CHECK(launch_jpegprog_recon(ctx->stream, y, w, out));
+    if (coef_out) AEJ_HIP_CHECK(hipMemcpyAsync(coef_out, w.f.coef, (size_t)y.fz.blocks * 128, hipMemcpyDeviceToDevice, ctx->stream));
+    AEJ_HIP_CHECK(hipStreamSynchronize(ctx->stream));         // keeps `blob` alive until its upload has run
+    return 0;
+}
+
+extern "C" int aej_jpegprog_batch(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
+                                  const uint8_t *data, uint64_t data_bytes, const int64_t *data_offsets_host, uint8_t *out, uint64_t out_bytes,
+                                  const int64_t *out_offsets_host, int32_t *status, void *workspace, uint64_t workspace_bytes)
+{
+    if (!out) return ctx ? null_buffer(ctx, __func__) : AEJ_ERR_ARG;
+    return jpegprog_run(ctx, __func__, frames_host, scans_host, n, data, data_bytes, data_offsets_host, 1 << 30, out, out_bytes, out_offsets_host,
+                        nullptr, 0, status, workspace, workspace_bytes);
+}
+
+extern "C" int aej_test_jpegprog_coefs(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
+                                       const uint8_t *data, uint64_t data_bytes, const int64_t *data_offsets_host, int n_levels,
+                                       int16_t *coef_out, uint64_t coef_blocks, int32_t *status, void *workspace, uint64_t workspace_bytes)
+{
+    if (!coef_out) return ctx ? null_buffer(ctx, __func__) : AEJ_ERR_ARG;
+    return jpegprog_run(ctx, __func__, frames_host, scans_host, n, data, data_bytes, data_offsets_host, n_levels, nullptr, 0, nullptr, coef_out,
+                        coef_blocks, status, workspace, workspace_bytes);
+}
+
+extern "C" int aej_test_jpegprog_coefs_host(const aej_jpegprog_frame *frame_host, const aej_jpegprog_scan *scans_host, const uint8_t *file_host,
+                                            uint64_t nbytes, int n_levels, int16_t *coef_out_host, uint64_t coef_blocks)
+{
+    if (!frame_host || !scans_host || !file_host || !coef_out_host) return AEJ_ERR_ARG;
+    return jpegprog_coefs_host(*frame_host, scans_host, file_host, nbytes, n_levels, coef_out_host, coef_blocks);
+}

@@ -24,6 +24,7 @@
 // input: DC <= 22 bits, 63 AC <= 26 bits each; kJfifBlockWordsOpt with a file's own tables: DC <= 27, AC <= 26) and every store into
 // a stream checks that stride; k_jfif_scatter writes a file only if it ends inside the caller's capacity.
 #include "aej_common.h"
+#include "aej_ctx.h"
 #include "aej_launch.h"
 #include "jfif_huff_core.h"
 #include "jpegdec_core.h"
@@ -652,29 +653,28 @@ bool jfif_geom(int B, int H, int W, int nq, JfifGeom &g, int ss, int opt)
 
 unsigned long long jfif_carve(void *base, const JfifGeom &g, JfifBufs &w)
 {
-    unsigned long long off = 0;
-    auto take = [&](unsigned long long n) { void *p = base ? (char *)base + off : nullptr; off += (n + 255) / 256 * 256; return p; };
-    const unsigned long long segs = (unsigned long long)g.nq * g.B;
-    w.par = (JfifParams *)take(sizeof(JfifParams) * g.nq);
-    w.dct = (int *)take((unsigned long long)g.B * g.nblk * 64 * 4);
-    w.coef = (short *)take(segs * g.nblk * 64 * 2);
-    w.lens = (int *)take(segs * g.nblk * 4);
-    w.boff = (long long *)take(segs * g.nblk * 8);
-    w.btot = (long long *)take(segs * 8);
-    w.stream = (unsigned *)take(segs * g.stream_words * 4);
-    w.ffcnt = (int *)take(segs * g.n_chunks * 4);
-    w.ffpre = (long long *)take(segs * g.n_chunks * 8);
-    w.fftot = (long long *)take(segs * 8);
-    w.total = (long long *)take(8);
-    w.planes = (unsigned char *)take(segs * g.plane_bytes);
+    Carver c(base);
+    const long long segs = (long long)g.nq * g.B;
+    w.par = c.take<JfifParams>(g.nq);
+    w.dct = c.take<int>((long long)g.B * g.nblk * 64);
+    w.coef = c.take<short>(segs * g.nblk * 64);
+    w.lens = c.take<int>(segs * g.nblk);
+    w.boff = c.take<long long>(segs * g.nblk);
+    w.btot = c.take<long long>(segs);
+    w.stream = c.take<unsigned>(segs * g.stream_words);
+    w.ffcnt = c.take<int>(segs * g.n_chunks);
+    w.ffpre = c.take<long long>(segs * g.n_chunks);
+    w.fftot = c.take<long long>(segs);
+    w.total = c.take<long long>(1);
+    w.planes = c.take<unsigned char>(segs * g.plane_bytes);
     w.hist = nullptr; w.codes = nullptr; w.fhdr = nullptr; w.fhdr_len = nullptr;
     if (g.opt) {
-        w.hist = (unsigned long long *)take(segs * 4 * kJhSymbols * 8);
-        w.codes = (unsigned *)take(segs * 4 * 256 * 4);
-        w.fhdr = (unsigned char *)take(segs * kJfifHdrMax);
-        w.fhdr_len = (int *)take(segs * 4);
+        w.hist = c.take<unsigned long long>(segs * 4 * kJhSymbols);
+        w.codes = c.take<unsigned>(segs * 4 * 256);
+        w.fhdr = c.take<unsigned char>(segs * kJfifHdrMax);
+        w.fhdr_len = c.take<int>(segs);
     }
-    return off;
+    return c.bytes();
 }
 
 int jfif_huffman_host(const long long *counts, unsigned char *bits, unsigned char *huffval)

@@ -23,6 +23,7 @@
 // Bounds: an item's index derives from JfpGeom; a scan's words stay inside its wcap (je_block_bound per block) and every store into a
 // stream checks it; k_jfp_scatter writes a file only if it ends inside the caller's capacity.
 #include "aej_common.h"
+#include "aej_ctx.h"
 #include "aej_launch.h"
 #include "jfif_huff_core.h"
 #include "jfif_prog_core.h"
@@ -446,42 +447,39 @@ bool jfifprog_geom(const JfifGeom &g, JfpGeom &p)
     return true;
 }
 
-static unsigned long long jfp_carve(void *base, unsigned long long off, const JfpGeom &p, JfpBufs &pw)
+static void jfp_carve(Carver &c, const JfpGeom &p, JfpBufs &pw)
 {
-    auto take = [&](unsigned long long n) { void *q = base ? (char *)base + off : nullptr; off += (n + 255) / 256 * 256; return q; };
-    const unsigned long long segs = (unsigned long long)p.segs;
-    pw.flags = (unsigned short *)take(segs * p.T * 2);
-    pw.pre = (unsigned long long *)take(segs * (p.T + 1) * 8);
-    pw.plen = (int *)take(segs * p.T * 4);
-    pw.lens = (int *)take(segs * p.T * 4);
-    pw.stream = (unsigned *)take(segs * p.stream_words * 4);
-    pw.ffcnt = (int *)take(segs * p.n_chunks * 4);
-    pw.ffpre = (unsigned long long *)take(segs * (p.n_chunks + 1) * 8);
-    pw.hist = (unsigned long long *)take(segs * p.ntab * kJhSymbols * 8);
-    pw.codes = (unsigned *)take(segs * p.ntab * 256 * 4);
-    pw.fhdr = (unsigned char *)take(segs * p.nscan * kJfpPiece);
-    pw.fhdr_len = (int *)take(segs * p.nscan * 4);
-    pw.cuts = (int *)take(segs * p.nscan * 2 * 4);
-    pw.total = (long long *)take(8);
-    return off;
+    const long long segs = p.segs;
+    pw.flags = c.take<unsigned short>(segs * p.T);
+    pw.pre = c.take<unsigned long long>(segs * (p.T + 1));
+    pw.plen = c.take<int>(segs * p.T);
+    pw.lens = c.take<int>(segs * p.T);
+    pw.stream = c.take<unsigned>(segs * p.stream_words);
+    pw.ffcnt = c.take<int>(segs * p.n_chunks);
+    pw.ffpre = c.take<unsigned long long>(segs * (p.n_chunks + 1));
+    pw.hist = c.take<unsigned long long>(segs * p.ntab * kJhSymbols);
+    pw.codes = c.take<unsigned>(segs * p.ntab * 256);
+    pw.fhdr = c.take<unsigned char>(segs * p.nscan * kJfpPiece);
+    pw.fhdr_len = c.take<int>(segs * p.nscan);
+    pw.cuts = c.take<int>(segs * p.nscan * 2);
+    pw.total = c.take<long long>(1);
 }
 
 // the workspace: what colour .. quantisation and the reconstruction use of JfifBufs (the baseline coder's buffers are not carved;
 // k_jfif_quant's Annex K bit counts land in pw.lens, which holds T >= nblk entries per file), then JfpBufs
 unsigned long long jfifprog_carve(void *base, const JfifGeom &g, const JfpGeom &p, JfifBufs &w, JfpBufs &pw)
 {
-    unsigned long long off = 0;
-    auto take = [&](unsigned long long n) { void *q = base ? (char *)base + off : nullptr; off += (n + 255) / 256 * 256; return q; };
-    const unsigned long long segs = (unsigned long long)g.nq * g.B;
+    Carver c(base);
+    const long long segs = (long long)g.nq * g.B;
     w = JfifBufs{};
-    w.par = (JfifParams *)take(sizeof(JfifParams) * g.nq);
-    w.dct = (int *)take((unsigned long long)g.B * g.nblk * 64 * 4);
-    w.coef = (short *)take(segs * g.nblk * 64 * 2);
-    w.planes = (unsigned char *)take(segs * g.plane_bytes);
-    off = jfp_carve(base, off, p, pw);
+    w.par = c.take<JfifParams>(g.nq);
+    w.dct = c.take<int>((long long)g.B * g.nblk * 64);
+    w.coef = c.take<short>(segs * g.nblk * 64);
+    w.planes = c.take<unsigned char>(segs * g.plane_bytes);
+    jfp_carve(c, p, pw);
     w.lens = pw.lens;
     w.total = pw.total;
-    return off;
+    return c.bytes();
 }
 
 static unsigned jfp_blocks(long long n) { return (unsigned)((n + kJfpThreads - 1) / kJfpThreads); }
@@ -628,15 +626,23 @@ int jfifprog_scan_device(hipStream_t st, const short *coefs_host, long long n, i
     p.sc[0] = JfpScan{ Ss, Se, Ah, Al, -1, 0, n, 0, 0, 0, 0 };
     jfp_finish_geom(p);
     JfpBufs pw;
-    const unsigned long long coef_bytes = ((unsigned long long)n * 128 + 255) / 256 * 256, out_cap = (unsigned long long)p.stream_words * 8;
-    const unsigned long long need = jfp_carve(nullptr, coef_bytes + out_cap + 256, p, pw);
+    const unsigned long long out_cap = (unsigned long long)p.stream_words * 8;
+    short *coef = nullptr;
+    unsigned char *out = nullptr;
+    long long *lengths = nullptr;
+    auto carve = [&](void *b) {      // the coefficients, the output and its length / offset words, then JfpBufs
+        Carver c(b);
+        coef = c.take<short>(n * 64);
+        out = c.take<unsigned char>((long long)out_cap);
+        lengths = c.take<long long>(2);
+        jfp_carve(c, p, pw);
+        return c.bytes();
+    };
     char *base = nullptr;
-    hipError_t e = hipMalloc((void **)&base, need);
+    hipError_t e = hipMalloc((void **)&base, carve(nullptr));
     if (e != hipSuccess) { *err = e; return AEJ_ERR_HIP; }
-    jfp_carve(base, coef_bytes + out_cap + 256, p, pw);
-    short *coef = (short *)base;
-    unsigned char *out = (unsigned char *)base + coef_bytes;
-    long long *lengths = (long long *)(out + out_cap), *offsets = lengths + 1;
+    carve(base);
+    long long *offsets = lengths + 1;
     long long len = 0;
     int cut32[2] = { 0, 0 };
     std::vector<unsigned long long> hist(kJhSymbols);

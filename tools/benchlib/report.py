@@ -52,7 +52,7 @@ def git_head():
 
 def source_hash(root=None):
     """sha256 (first 16 hex digits) over the CODE of everything the benchmarked launches are built from: the kernel sources, their
-    headers AND api.hip, whose launch shapes, chaining and sub-batching are what a pipelined profile measures -- comments and white space
+    headers AND api.hip and its api_*.hip siblings, whose launch shapes, chaining and sub-batching are what a pipelined profile measures -- comments and white space
     stripped, so that editing a comment does not invalidate a profile.  Left out: deflate / decode / metrics (kernels and entry points
     this benchmark never launches).  tools/profiling/pmc.py stores the same figure in the profile it writes, so staleness needs no git on
     the GPU box."""
