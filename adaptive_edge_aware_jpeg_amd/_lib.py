@@ -243,6 +243,9 @@ SIGNATURES = {
     "aej_jpegprog_parse_host": (_I, [_P, _U64, _P, _P, _I, _P, _I]),
     "aej_jpegprog_workspace_bytes": (_U64, [_P, _P, _P, _I]),
     "aej_jpegprog_batch": (_I, [_P, _P, _P, _I, _P, _U64, _P, _P, _U64, _P, _P, _P, _U64]),
+    "aej_jfif_transcode_headers_host": (_I, [_P, _P, _P, _I, _P, _I]),
+    "aej_jfif_transcode_workspace_bytes": (_U64, [_P, _P, _I, _P, _P, _I, _I]),
+    "aej_jfif_transcode_batch": (_I, [_P, _P, _I, _P, _U64, _P, _P, _P, _I, _P, _U64, _P, _P, _I, _P, _U64, _P, _P, _P, _P, _P, _P, _U64]),
     "aej_test_jpegprog_coefs": (_I, [_P, _P, _P, _I, _P, _U64, _P, _I, _P, _U64, _P, _P, _U64]),             # include/aej_testing.h (tests only)
     "aej_test_jpegprog_coefs_host": (_I, [_P, _P, _P, _U64, _I, _P, _U64]),                                 # include/aej_testing.h (tests only)
 }
@@ -252,7 +255,8 @@ INFLATE_STATUS = ["ok", "bad zlib header", "bad block type", "bad code lengths",
                   "distance too far back", "stored block LEN/NLEN mismatch", "truncated stream", "output over capacity",
                   "Adler-32 mismatch", "bad stream descriptor"]
 JPEGDEC_STATUS = ["ok", "truncated scan (it ends before the last MCU)", "bad Huffman code", "coefficient run past 63",
-                  "DC category above 11", "restart marker out of sequence, missing or unexpected"]
+                  "DC category above 11", "restart marker out of sequence, missing or unexpected",
+                  "coefficient out of range for an 8-bit JPEG (AC beyond +-1023 or DC outside -1024..1023)"]
 HEADER_STATUS = ["ok", "more leaves than the layer holds", "leaf size outside the block-size range of the header",
                  "quadtree header does not tile the layer", "coefficient count does not match the quadtree header", "bad layer descriptor"]
 

@@ -237,6 +237,14 @@ hipError_t launch_jfif_recon(hipStream_t st, const JfifGeom &g, const JfifBufs &
 // the stages before entropy coding alone: parameters up, colour / down-sampling / FDCT, quantisation -> w.coef (w.lens is scratch)
 hipError_t launch_jfif_coefs(hipStream_t st, const JfifGeom &g, const JfifBufs &w, const JfifParams *par_host, const unsigned char *rgb);
 
+// the entropy stages alone (optimised tables): from w.coef and the markers in w.par, both already on the device, to lengths / offsets;
+// the scatter is a launch of its own, so that a caller can place the files of several such chains first (jfiftrans.hip)
+struct Carver;
+unsigned long long jfif_carve_coded(Carver &c, const JfifGeom &g, JfifBufs &w);      // requires g.opt
+hipError_t launch_jfif_entropy(hipStream_t st, const JfifGeom &g, const JfifBufs &w, long long *lengths, long long *offsets);
+hipError_t launch_jfif_scatter(hipStream_t st, const JfifGeom &g, const JfifBufs &w, const long long *lengths, const long long *offsets,
+                               unsigned char *out, unsigned long long cap);
+
 // jfifprog.hip: the progressive file Pillow writes with progressive=True from the same coefficients (aej_jfif_*_prog)
 constexpr int kJfpMaxScans = 10;       // jpeg_simple_progression of a three-component file
 constexpr int kJfpPiece = 576;         // bytes that bound the markers before one scan's data: two DHT of 5 + 16 + 256 and an SOS of 14
@@ -267,6 +275,11 @@ unsigned long long jfifprog_carve(void *base, const JfifGeom &g, const JfpGeom &
 hipError_t launch_jfifprog_encode(hipStream_t st, const JfifGeom &g, const JfpGeom &p, const JfifBufs &w, const JfpBufs &pw,
                                   const JfifParams *par_host, const unsigned char *rgb, unsigned char *out, unsigned long long cap,
                                   long long *lengths, long long *offsets);
+unsigned long long jfifprog_carve_coded(Carver &c, const JfifGeom &g, const JfpGeom &p, JfifBufs &w, JfpBufs &pw);
+hipError_t launch_jfifprog_entropy(hipStream_t st, const JfpGeom &p, const JfpBufs &pw, const short *coef, const JfifParams *par, long long *lengths,
+                                   long long *offsets);
+hipError_t launch_jfifprog_scatter(hipStream_t st, const JfpGeom &p, const JfpBufs &pw, const JfifParams *par, const long long *lengths,
+                                   const long long *offsets, unsigned char *out, unsigned long long cap);
 // one scan over n blocks of given coefficients (int16 [n][64], zigzag order): the padded, stuffed scan bytes, the counts of its
 // symbols [257] and its cuts (by kJeMaxRun, by kJeMaxDeferred).  -> 0, or AEJ_ERR_ARG / AEJ_ERR_CAPACITY (out_len is set)
 int jfifprog_scan_host(const short *coefs, long long n, int Ss, int Se, int Ah, int Al, unsigned char *out, unsigned long long cap,
@@ -297,6 +310,7 @@ hipError_t launch_jpegdec_begin(hipStream_t st, int n, const JdBufSizes &z, cons
 hipError_t launch_jpegdec_unstuff(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, const unsigned char *scans, int S, int *status);
 hipError_t launch_jpegdec_recon(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, unsigned char *out);
 hipError_t launch_jpegdec_sync(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, int S, int first_round, int rounds);
+hipError_t launch_jpegdec_write(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, int S, int *status);      // finish without the reconstruction
 hipError_t launch_jpegdec_finish(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, int S, unsigned char *out, int *status);
 
 }  // namespace aej
@@ -325,5 +339,45 @@ hipError_t launch_jpegprog_entropy(hipStream_t st, const JpLayout &y, const JpBu
 hipError_t launch_jpegprog_recon(hipStream_t st, const JpLayout &y, const JpBufs &w, unsigned char *out);
 int jpegprog_coefs_host(const aej_jpegprog_frame &frame, const aej_jpegprog_scan *scans, const unsigned char *file, unsigned long long nbytes,
                         int n_levels, short *coef, unsigned long long coef_blocks);
+
+// jfiftrans.hip: lossless transcode -- the decoders' coefficients entropy-coded again under optimal tables (aej_jfif_transcode_*)
+struct JtSource {                      // what the output's markers take from one parsed file
+    int width, height, hs, vs;
+    unsigned char comp_id[3], comp_tq[3];
+    unsigned short qt[3][64];          // natural order
+    int units, xdensity, ydensity;     // of the JFIF APP0
+};
+struct JtFile {                        // one file of a call (host-computed, uploaded): where the bridge reads and writes its blocks
+    long long src_base, n_blocks;      // its first block among the call's blocks, files in the caller's order, and their number
+    const short *src;                  // its coefficients as its decoder left them: natural order, MCU order (JdFile::blk_base)
+    short *dst;                        // its segment of its group's w.coef: zigzag order, the same MCU order
+    int status_index, out_pos;         // its word in the status array; its place in output order (group after group)
+};
+struct JtGroup {                       // the files of one (H, W, hs, vs): one entropy-encode chain, every file one "quality" of one image
+    JfifGeom g; JfpGeom p; JfifBufs w; JfpBufs pw;
+    std::vector<int> files;            // caller's indices, in segment order
+    std::vector<JfifParams> par;       // their markers (kept until the upload has run)
+    long long first;                   // its first file in output order
+    bool foreign_ids;                  // a file's component ids are not 1, 2, 3
+};
+struct JtPlan {
+    bool prog = false;
+    std::vector<JtFile> files;         // caller's order
+    std::vector<JtGroup> groups;
+    long long n_blocks = 0;
+    JtFile *d_files = nullptr;         // device: the table,
+    long long *glen = nullptr, *goff = nullptr, *total = nullptr;      // lengths and offsets in output order, their sum
+};
+void jfiftrans_source(const aej_jpegdec_desc &d, JtSource &s);
+void jfiftrans_source(const aej_jpegprog_frame &f, JtSource &s);
+// the markers SOI .. SOF0 / SOF2 the transcoder writes for one source -> their length, or -1 when they do not fit
+int jfiftrans_prefix_host(const JtSource &s, bool prog, unsigned char *out, int capacity);
+// n_blocks[i]: blocks the decoder holds for file i (must equal the source's MCU-padded count)
+bool jfiftrans_plan(const std::vector<JtSource> &src, const std::vector<long long> &n_blocks, bool prog, JtPlan &plan);
+unsigned long long jfiftrans_carve(void *base, JtPlan &plan);
+// bridge, one entropy chain per group, placement, scatter.  Before it: plan.files[i].src / status_index set by the caller.  status: the
+// call's status words (the decoders' results in; out-of-range coefficients added); lengths / offsets: device, caller's order
+hipError_t launch_jfiftrans(hipStream_t st, JtPlan &plan, int *status, unsigned char *out, unsigned long long cap, long long *lengths,
+                            long long *offsets);
 
 }  // namespace aej

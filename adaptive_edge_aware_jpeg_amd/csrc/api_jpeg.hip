@@ -219,29 +219,12 @@ extern "C" uint64_t aej_jpegdec_workspace_bytes(aej_ctx *ctx, const aej_jpegdec_
     return jpegdec_carve(nullptr, n, z, w);
 }
 
-extern "C" int aej_jpegdec_batch(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const uint8_t *scans, uint64_t scans_bytes,
-                                 const int64_t *scan_offsets_host, uint8_t *out, uint64_t out_bytes, const int64_t *out_offsets_host,
-                                 int32_t *status, void *workspace, uint64_t workspace_bytes)
+// the entropy decode of n baseline files up to the fixed point of the sync rounds: everything of aej_jpegdec_batch before the
+// coefficient write (`files` carries the scan offsets; the caller has carved `w`)
+static int jpegdec_decode(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs_host, int n, const std::vector<JdFile> &files, const JdBufSizes &z,
+                          const JdBufs &w, const uint8_t *scans, int32_t *status)
 {
-    AEJ_TRY(enter(ctx, __func__));
-    if (!jpegdec_descs_ok(descs_host, n)) return fail(ctx, AEJ_ERR_ARG, "%s: no files, or a descriptor aej_jpegdec_parse_host did not write", __func__);
-    if (!scans || !scan_offsets_host || !out || !out_offsets_host || !status || !workspace) return null_buffer(ctx, __func__);
     const int S = ctx->jd_subseq_bits;
-    std::vector<JdFile> files;
-    JdBufSizes z;
-    jpegdec_layout(descs_host, n, S, files, z);
-    for (int i = 0; i < n; i++) {
-        const aej_jpegdec_desc &d = descs_host[i];
-        const long long so = scan_offsets_host[i], oo = out_offsets_host[i], ob = (long long)d.width * d.height * 3;
-        if (so < 0 || (uint64_t)so + (uint64_t)d.scan_length > scans_bytes)
-            return fail(ctx, AEJ_ERR_ARG, "%s: file %d: scan outside the scans buffer", __func__, i);
-        if (oo < 0 || (uint64_t)oo + (uint64_t)ob > out_bytes) return fail(ctx, AEJ_ERR_ARG, "%s: file %d: image outside the output", __func__, i);
-        files[i].scan_off = so;
-        files[i].out_off = oo;
-    }
-    JdBufs w;
-    const unsigned long long need = jpegdec_carve(workspace, n, z, w);
-    AEJ_TRY(check_workspace(ctx, need, workspace_bytes));
     // one upload: files, descriptors, the "last round that changed" word (-1)
     std::vector<unsigned char> blob(sizeof(JdFile) * n + sizeof(aej_jpegdec_desc) * n + sizeof(int));
     memcpy(blob.data(), files.data(), sizeof(JdFile) * n);
@@ -263,9 +246,42 @@ extern "C" int aej_jpegdec_batch(aej_ctx *ctx, const aej_jpegdec_desc *descs_hos
         last = ctx->h_flag[0];
         if (last < launched) break;
         if (launched > max_slots + kJdSyncBatch)
-            return fail(ctx, AEJ_ERR_STATE, "%s: the Huffman decode did not settle after %d rounds", __func__, launched);
+            return fail(ctx, AEJ_ERR_STATE, "%s: the Huffman decode did not settle after %d rounds", fn, launched);
     }
     ctx->jd_sync_rounds = last + 1;
+    return 0;
+}
+
+// the scan offset of baseline file i checked against the scans buffer and entered into the layout
+static int jpegdec_scan_offset(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc &d, int i, uint64_t scans_bytes, long long so, JdFile &file)
+{
+    if (so < 0 || (uint64_t)so + (uint64_t)d.scan_length > scans_bytes) return fail(ctx, AEJ_ERR_ARG, "%s: file %d: scan outside the scans buffer", fn, i);
+    file.scan_off = so;
+    return 0;
+}
+
+extern "C" int aej_jpegdec_batch(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const uint8_t *scans, uint64_t scans_bytes,
+                                 const int64_t *scan_offsets_host, uint8_t *out, uint64_t out_bytes, const int64_t *out_offsets_host,
+                                 int32_t *status, void *workspace, uint64_t workspace_bytes)
+{
+    AEJ_TRY(enter(ctx, __func__));
+    if (!jpegdec_descs_ok(descs_host, n)) return fail(ctx, AEJ_ERR_ARG, "%s: no files, or a descriptor aej_jpegdec_parse_host did not write", __func__);
+    if (!scans || !scan_offsets_host || !out || !out_offsets_host || !status || !workspace) return null_buffer(ctx, __func__);
+    const int S = ctx->jd_subseq_bits;
+    std::vector<JdFile> files;
+    JdBufSizes z;
+    jpegdec_layout(descs_host, n, S, files, z);
+    for (int i = 0; i < n; i++) {                            // file by file, scan before image, as the errors were always reported
+        const aej_jpegdec_desc &d = descs_host[i];
+        AEJ_TRY(jpegdec_scan_offset(ctx, __func__, d, i, scans_bytes, scan_offsets_host[i], files[i]));
+        const long long oo = out_offsets_host[i], ob = (long long)d.width * d.height * 3;
+        if (oo < 0 || (uint64_t)oo + (uint64_t)ob > out_bytes) return fail(ctx, AEJ_ERR_ARG, "%s: file %d: image outside the output", __func__, i);
+        files[i].out_off = oo;
+    }
+    JdBufs w;
+    const unsigned long long need = jpegdec_carve(workspace, n, z, w);
+    AEJ_TRY(check_workspace(ctx, need, workspace_bytes));
+    AEJ_TRY(jpegdec_decode(ctx, __func__, descs_host, n, files, z, w, scans, status));
     AEJ_HIP_CHECK(launch_jpegdec_finish(ctx->stream, n, z, w, S, out, status));
     return 0;
 }
@@ -361,4 +377,133 @@ extern "C" int aej_test_jpegprog_coefs_host(const aej_jpegprog_frame *frame_host
 {
     if (!frame_host || !scans_host || !file_host || !coef_out_host) return AEJ_ERR_ARG;
     return jpegprog_coefs_host(*frame_host, scans_host, file_host, nbytes, n_levels, coef_out_host, coef_blocks);
+}
+
+// ---- lossless transcode (jfiftrans.hip): the decoders' entropy stages, the bridge, the encoders' entropy stages ---------------------------
+template <class D>
+static bool jt_source_ok(const D &d)
+{
+    if (d.ncomp != 3 || d.precision16) return false;
+    for (int c = 0; c < 3; c++)
+        for (int i = 0; i < 64; i++)
+            if (d.qt[c][i] < 1 || d.qt[c][i] > 255) return false;
+    return true;
+}
+
+// the call's layout: baseline files first, then progressive ones.  -> 0, or the error (ctx is never NULL: the entries check it first)
+struct JtCall {
+    std::vector<JdFile> files; JdBufSizes z{};      // baseline decode
+    JpLayout y;                                     // progressive decode
+    JtPlan plan;
+    std::vector<JtSource> src;
+};
+static int jt_layout(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs, int n_base, const aej_jpegprog_frame *frames,
+                     const aej_jpegprog_scan *pscans, int n_prog, const uint16_t *density, int progressive, JtCall &c)
+{
+    if (n_base < 0 || n_prog < 0 || n_base + n_prog < 1 || (long long)n_base + n_prog > 65535 || (progressive != 0 && progressive != 1))
+        return fail(ctx, AEJ_ERR_ARG, "%s: 1 .. 65535 files and progressive 0 or 1 required", fn);
+    if (n_base && !jpegdec_descs_ok(descs, n_base)) return fail(ctx, AEJ_ERR_ARG, "%s: a descriptor aej_jpegdec_parse_host did not write", fn);
+    if (n_prog && !jpegprog_layout(frames, pscans, n_prog, c.y)) return fail(ctx, AEJ_ERR_ARG, "%s: descriptors aej_jpegprog_parse_host did not write", fn);
+    const int n = n_base + n_prog;
+    c.src.assign(n, JtSource{});
+    std::vector<long long> nblk(n);
+    if (n_base) jpegdec_layout(descs, n_base, ctx->jd_subseq_bits, c.files, c.z);
+    c.z.planes = c.z.px = 0;                                 // no reconstruction: no sample planes
+    c.y.fz.planes = c.y.fz.px = 0;
+    for (int i = 0; i < n; i++) {
+        const bool ok = i < n_base ? jt_source_ok(descs[i]) : jt_source_ok(frames[i - n_base]);
+        if (!ok) return fail(ctx, AEJ_ERR_UNSUPPORTED, "%s: file %d: three components with 8-bit quantisation tables required", fn, i);
+        if (i < n_base) jfiftrans_source(descs[i], c.src[i]); else jfiftrans_source(frames[i - n_base], c.src[i]);
+        nblk[i] = i < n_base ? c.files[i].n_blocks : c.y.ffiles[i - n_base].n_blocks;
+        if (density) { c.src[i].units = density[3 * i] & 255; c.src[i].xdensity = density[3 * i + 1]; c.src[i].ydensity = density[3 * i + 2]; }
+    }
+    if (!jfiftrans_plan(c.src, nblk, progressive != 0, c.plan)) return fail(ctx, AEJ_ERR_ARG, "%s: descriptors whose sampling or block counts do not fit", fn);
+    return 0;
+}
+
+struct JtWorkspace { JdBufs wb; JpBufs wp; unsigned long long bytes; };
+static JtWorkspace jt_carve(void *workspace, int n_base, int n_prog, JtCall &c)
+{
+    JtWorkspace r{};
+    char *base = static_cast<char *>(workspace);
+    unsigned long long off = 0;
+    if (n_base) off += jpegdec_carve(base ? base + off : nullptr, n_base, c.z, r.wb);
+    if (n_prog) off += jpegprog_carve(base ? base + off : nullptr, c.y, r.wp);
+    off += jfiftrans_carve(base ? base + off : nullptr, c.plan);
+    r.bytes = off;
+    return r;
+}
+
+extern "C" int aej_jfif_transcode_headers_host(const aej_jpegdec_desc *desc_host, const aej_jpegprog_frame *frame_host, const uint16_t *density3_host,
+                                               int progressive, uint8_t *out_host, int capacity)
+{
+    if ((!desc_host) == (!frame_host) || !out_host || capacity < 0 || (progressive != 0 && progressive != 1)) return AEJ_ERR_ARG;
+    if (!(desc_host ? jt_source_ok(*desc_host) : jt_source_ok(*frame_host))) return AEJ_ERR_UNSUPPORTED;
+    JtSource s;
+    if (desc_host) jfiftrans_source(*desc_host, s); else jfiftrans_source(*frame_host, s);
+    if (density3_host) { s.units = density3_host[0] & 255; s.xdensity = density3_host[1]; s.ydensity = density3_host[2]; }
+    const int n = jfiftrans_prefix_host(s, progressive != 0, out_host, capacity);
+    return n < 0 ? AEJ_ERR_CAPACITY : n;
+}
+
+extern "C" uint64_t aej_jfif_transcode_workspace_bytes(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base,
+                                                       const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *pscans_host, int n_prog,
+                                                       int progressive)
+{
+    if (!ctx || (n_base > 0 && !descs_host) || (n_prog > 0 && (!frames_host || !pscans_host))) return 0;
+    JtCall c;
+    const std::string keep = ctx->err;
+    const int rc = jt_layout(ctx, __func__, descs_host, n_base, frames_host, pscans_host, n_prog, nullptr, progressive, c);
+    ctx->err = keep;                                         // a size query leaves the context's last error alone
+    return rc ? 0 : jt_carve(nullptr, n_base, n_prog, c).bytes;
+}
+
+extern "C" int aej_jfif_transcode_batch(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base, const uint8_t *scans, uint64_t scans_bytes,
+                                        const int64_t *scan_offsets_host, const aej_jpegprog_frame *frames_host,
+                                        const aej_jpegprog_scan *pscans_host, int n_prog, const uint8_t *data, uint64_t data_bytes,
+                                        const int64_t *data_offsets_host, const uint16_t *density_host, int progressive, uint8_t *out,
+                                        uint64_t out_capacity, int64_t *offsets, int64_t *lengths, uint64_t *total_host, int32_t *status,
+                                        int32_t *n_groups_host, void *workspace, uint64_t workspace_bytes)
+{
+    AEJ_TRY(enter(ctx, __func__));
+    if ((n_base > 0 && (!descs_host || !scans || !scan_offsets_host)) || (n_prog > 0 && (!frames_host || !pscans_host || !data || !data_offsets_host)) ||
+        !offsets || !lengths || !total_host || !status || !workspace)
+        return null_buffer(ctx, __func__);
+    JtCall c;
+    AEJ_TRY(jt_layout(ctx, __func__, descs_host, n_base, frames_host, pscans_host, n_prog, density_host, progressive, c));
+    for (int i = 0; i < n_base; i++) AEJ_TRY(jpegdec_scan_offset(ctx, __func__, descs_host[i], i, scans_bytes, scan_offsets_host[i], c.files[i]));
+    for (size_t t = 0; t < c.y.scans.size(); t++) {
+        const long long so = data_offsets_host[c.y.src[t]];
+        if (so < 0 || (uint64_t)so + (uint64_t)c.y.sfiles[t].scan_len > data_bytes)
+            return fail(ctx, AEJ_ERR_ARG, "%s: scan %d: bytes outside the data buffer", __func__, c.y.src[t]);
+        c.y.sfiles[t].scan_off = so;
+    }
+    const JtWorkspace ws = jt_carve(workspace, n_base, n_prog, c);
+    AEJ_TRY(check_workspace(ctx, ws.bytes, workspace_bytes));
+    const int n = n_base + n_prog;
+    for (int i = 0; i < n; i++) {
+        JtFile &F = c.plan.files[i];
+        F.src = i < n_base ? ws.wb.coef + c.files[i].blk_base * 64 : ws.wp.f.coef + c.y.ffiles[i - n_base].blk_base * 64;
+        F.status_index = i;
+    }
+    if (n_groups_host) *n_groups_host = (int32_t)c.plan.groups.size();
+    std::vector<unsigned char> blob;
+    if (n_base) {
+        AEJ_TRY(jpegdec_decode(ctx, __func__, descs_host, n_base, c.files, c.z, ws.wb, scans, status));
+        AEJ_HIP_CHECK(launch_jpegdec_write(ctx->stream, n_base, c.z, ws.wb, ctx->jd_subseq_bits, status));
+    } else {
+        AEJ_TRY(bind_device(ctx));
+    }
+    if (n_prog) {
+        jpegprog_blob(c.y, &blob);
+        AEJ_HIP_CHECK(launch_jpegprog_entropy(ctx->stream, c.y, ws.wp, blob.data(), blob.size(), data, 1 << 30, status + n_base));
+    }
+    AEJ_HIP_CHECK(launch_jfiftrans(ctx->stream, c.plan, status, out, out_capacity, (long long *)lengths, (long long *)offsets));
+    long long total = 0;
+    AEJ_HIP_CHECK(hipMemcpyAsync(&total, c.plan.total, 8, hipMemcpyDeviceToHost, ctx->stream));
+    AEJ_HIP_CHECK(hipStreamSynchronize(ctx->stream));         // also keeps `blob` and the plan's tables alive until their uploads have run
+    *total_host = (uint64_t)total;
+    if (out && (uint64_t)total > out_capacity)
+        return fail(ctx, AEJ_ERR_CAPACITY, "%s: the files need %lld bytes, the output holds %llu", __func__, total, (unsigned long long)out_capacity);
+    return 0;
 }

@@ -677,6 +677,29 @@ unsigned long long jfif_carve(void *base, const JfifGeom &g, JfifBufs &w)
     return c.bytes();
 }
 
+// the transcoder's workspace of one group of files (jfiftrans.hip): jfif_carve without what colour, DCT and reconstruction use -- the
+// markers, the coefficients and every buffer of the optimised entropy stages.  Kept beside jfif_carve so that the two lists stay one.
+unsigned long long jfif_carve_coded(Carver &c, const JfifGeom &g, JfifBufs &w)
+{
+    const long long segs = (long long)g.nq * g.B;
+    w = JfifBufs{};
+    w.par = c.take<JfifParams>(g.nq);
+    w.coef = c.take<short>(segs * g.nblk * 64);
+    w.lens = c.take<int>(segs * g.nblk);
+    w.boff = c.take<long long>(segs * g.nblk);
+    w.btot = c.take<long long>(segs);
+    w.stream = c.take<unsigned>(segs * g.stream_words);
+    w.ffcnt = c.take<int>(segs * g.n_chunks);
+    w.ffpre = c.take<long long>(segs * g.n_chunks);
+    w.fftot = c.take<long long>(segs);
+    w.total = c.take<long long>(1);
+    w.hist = c.take<unsigned long long>(segs * 4 * kJhSymbols);
+    w.codes = c.take<unsigned>(segs * 4 * 256);
+    w.fhdr = c.take<unsigned char>(segs * kJfifHdrMax);
+    w.fhdr_len = c.take<int>(segs);
+    return c.bytes();
+}
+
 int jfif_huffman_host(const long long *counts, unsigned char *bits, unsigned char *huffval)
 {
     JhWork w;
@@ -740,17 +763,13 @@ void jfif_params_host(int q, int H, int W, JfifParams &p, int ss)
 
 static unsigned jf_blocks(long long n) { return (unsigned)((n + kJfThreads - 1) / kJfThreads); }
 
+// the stages from w.coef to the file lengths and offsets (k_jfif_quant has left the Annex K bit counts in w.lens)
 template <int HS, int VS>
-static hipError_t jf_encode(hipStream_t st, const JfifGeom &g, const JfifBufs &w, const JfifParams *par_host, const unsigned char *rgb,
-                            unsigned char *out, unsigned long long cap, long long *lengths, long long *offsets)
+static hipError_t jf_entropy(hipStream_t st, const JfifGeom &g, const JfifBufs &w, long long *lengths, long long *offsets)
 {
     const long long segs = (long long)g.nq * g.B, nb = segs * g.nblk, nc = segs * g.n_chunks;
-    hipError_t e = hipMemcpyAsync(w.par, par_host, sizeof(JfifParams) * g.nq, hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_jfif_fdct<HS, VS>), dim3(jf_blocks((long long)g.B * g.nblk)), dim3(kJfThreads), 0, st, g, rgb, w.dct);
-    hipLaunchKernelGGL((k_jfif_quant<HS, VS>), dim3(jf_blocks(nb)), dim3(kJfThreads), 0, st, g, w.par, w.dct, w.coef, w.lens);
     if (g.opt) {
-        e = hipMemsetAsync(w.hist, 0, (size_t)segs * 4 * kJhSymbols * 8, st);
+        const hipError_t e = hipMemsetAsync(w.hist, 0, (size_t)segs * 4 * kJhSymbols * 8, st);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL((k_jfif_hist<HS, VS>), dim3(jf_blocks(g.nblk), (unsigned)segs), dim3(kJfThreads), 0, st, g, w.coef, w.hist);
         hipLaunchKernelGGL(k_jfif_tables, dim3((unsigned)segs), dim3(kJfThreads), 0, st, g, w.par, w.hist, w.codes, w.fhdr, w.fhdr_len);
@@ -766,10 +785,28 @@ static hipError_t jf_encode(hipStream_t st, const JfifGeom &g, const JfifBufs &w
     hipLaunchKernelGGL(k_jfif_ffcount, dim3(jf_blocks(nc)), dim3(kJfThreads), 0, st, g, w.btot, w.stream, w.ffcnt);
     hipLaunchKernelGGL(k_jfif_scan, dim3((unsigned)segs), dim3(kJfScanThreads), 0, st, w.ffcnt, g.n_chunks, w.ffpre, w.fftot);
     hipLaunchKernelGGL(k_jfif_layout, dim3(1), dim3(1), 0, st, g, w.par, w.fhdr_len, w.btot, w.fftot, lengths, offsets, w.total);
-    if (out)
-        hipLaunchKernelGGL(k_jfif_scatter, dim3(jf_blocks(nc)), dim3(kJfThreads), 0, st, g, w.par, w.fhdr, w.fhdr_len, w.btot, w.stream, w.ffpre,
-                           lengths, offsets, out, cap);
     return hipGetLastError();
+}
+
+static hipError_t jf_scatter(hipStream_t st, const JfifGeom &g, const JfifBufs &w, const long long *lengths, const long long *offsets,
+                             unsigned char *out, unsigned long long cap)
+{
+    hipLaunchKernelGGL(k_jfif_scatter, dim3(jf_blocks((long long)g.nq * g.B * g.n_chunks)), dim3(kJfThreads), 0, st, g, w.par, w.fhdr, w.fhdr_len,
+                       w.btot, w.stream, w.ffpre, lengths, offsets, out, cap);
+    return hipGetLastError();
+}
+
+template <int HS, int VS>
+static hipError_t jf_encode(hipStream_t st, const JfifGeom &g, const JfifBufs &w, const JfifParams *par_host, const unsigned char *rgb,
+                            unsigned char *out, unsigned long long cap, long long *lengths, long long *offsets)
+{
+    hipError_t e = hipMemcpyAsync(w.par, par_host, sizeof(JfifParams) * g.nq, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_jfif_fdct<HS, VS>), dim3(jf_blocks((long long)g.B * g.nblk)), dim3(kJfThreads), 0, st, g, rgb, w.dct);
+    hipLaunchKernelGGL((k_jfif_quant<HS, VS>), dim3(jf_blocks((long long)g.nq * g.B * g.nblk)), dim3(kJfThreads), 0, st, g, w.par, w.dct, w.coef,
+                       w.lens);
+    if ((e = jf_entropy<HS, VS>(st, g, w, lengths, offsets)) != hipSuccess) return e;
+    return out ? jf_scatter(st, g, w, lengths, offsets, out, cap) : hipSuccess;
 }
 
 hipError_t launch_jfif_encode(hipStream_t st, const JfifGeom &g, const JfifBufs &w, const JfifParams *par_host, const unsigned char *rgb,
@@ -778,6 +815,21 @@ hipError_t launch_jfif_encode(hipStream_t st, const JfifGeom &g, const JfifBufs 
     if (g.hs == 1) return jf_encode<1, 1>(st, g, w, par_host, rgb, out, cap, lengths, offsets);
     if (g.vs == 1) return jf_encode<2, 1>(st, g, w, par_host, rgb, out, cap, lengths, offsets);
     return jf_encode<2, 2>(st, g, w, par_host, rgb, out, cap, lengths, offsets);
+}
+
+// the transcoder's cut (jfiftrans.hip): given coefficients in w.coef and the files' markers in w.par (uploaded by the caller), the
+// optimised entropy stages up to the lengths, and the scatter as a launch of its own once the caller has placed the files
+hipError_t launch_jfif_entropy(hipStream_t st, const JfifGeom &g, const JfifBufs &w, long long *lengths, long long *offsets)
+{
+    if (g.hs == 1) return jf_entropy<1, 1>(st, g, w, lengths, offsets);
+    if (g.vs == 1) return jf_entropy<2, 1>(st, g, w, lengths, offsets);
+    return jf_entropy<2, 2>(st, g, w, lengths, offsets);
+}
+
+hipError_t launch_jfif_scatter(hipStream_t st, const JfifGeom &g, const JfifBufs &w, const long long *lengths, const long long *offsets,
+                               unsigned char *out, unsigned long long cap)
+{
+    return jf_scatter(st, g, w, lengths, offsets, out, cap);
 }
 
 template <int HS, int VS>

@@ -482,6 +482,18 @@ unsigned long long jfifprog_carve(void *base, const JfifGeom &g, const JfpGeom &
     return c.bytes();
 }
 
+// the transcoder's workspace of one group of files: their markers and coefficients, then JfpBufs (no colour, DCT or sample planes)
+unsigned long long jfifprog_carve_coded(Carver &c, const JfifGeom &g, const JfpGeom &p, JfifBufs &w, JfpBufs &pw)
+{
+    w = JfifBufs{};
+    w.par = c.take<JfifParams>(g.nq);
+    w.coef = c.take<short>((long long)g.nq * g.B * g.nblk * 64);
+    jfp_carve(c, p, pw);
+    w.lens = pw.lens;
+    w.total = pw.total;
+    return c.bytes();
+}
+
 static unsigned jfp_blocks(long long n) { return (unsigned)((n + kJfpThreads - 1) / kJfpThreads); }
 
 // every stage after quantisation
@@ -506,9 +518,23 @@ static hipError_t jfp_entropy(hipStream_t st, const JfpGeom &p, const JfpBufs &p
     hipLaunchKernelGGL(k_jfp_ffcount, chunks, th, 0, st, p, pw.pre, pw.stream, pw.ffcnt);
     hipLaunchKernelGGL(k_jfp_scan<1>, dim3(segs), dim3(kJfpScanThreads), 0, st, nullptr, pw.ffcnt, p.n_chunks, pw.ffpre);
     hipLaunchKernelGGL(k_jfp_layout, dim3(1), th, 0, st, p, par, pw.fhdr_len, pw.pre, pw.ffpre, lengths, offsets, pw.total);
-    if (out)
-        hipLaunchKernelGGL(k_jfp_scatter, chunks, th, 0, st, p, par, pw.fhdr, pw.fhdr_len, pw.pre, pw.stream, pw.ffpre, lengths, offsets, out, cap);
+    return out ? launch_jfifprog_scatter(st, p, pw, par, lengths, offsets, out, cap) : hipGetLastError();
+}
+
+hipError_t launch_jfifprog_scatter(hipStream_t st, const JfpGeom &p, const JfpBufs &pw, const JfifParams *par, const long long *lengths,
+                                   const long long *offsets, unsigned char *out, unsigned long long cap)
+{
+    hipLaunchKernelGGL(k_jfp_scatter, dim3(jfp_blocks(p.n_chunks), (unsigned)p.segs), dim3(kJfpThreads), 0, st, p, par, pw.fhdr, pw.fhdr_len, pw.pre,
+                       pw.stream, pw.ffpre, lengths, offsets, out, cap);
     return hipGetLastError();
+}
+
+// the transcoder's cut (jfiftrans.hip): every stage after quantisation up to the lengths, from coefficients and markers (par, device)
+// the caller has put in place
+hipError_t launch_jfifprog_entropy(hipStream_t st, const JfpGeom &p, const JfpBufs &pw, const short *coef, const JfifParams *par, long long *lengths,
+                                   long long *offsets)
+{
+    return jfp_entropy(st, p, pw, coef, par, nullptr, 0, lengths, offsets);
 }
 
 hipError_t launch_jfifprog_encode(hipStream_t st, const JfifGeom &g, const JfpGeom &p, const JfifBufs &w, const JfpBufs &pw,

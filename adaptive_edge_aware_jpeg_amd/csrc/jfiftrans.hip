@@ -1,0 +1,249 @@
+// jfiftrans.hip -- lossless transcode: JPEG files Huffman-decoded to their quantised coefficients (jpegdec.hip, jpegprog.hip) and
+// entropy-coded again under optimal tables, as a baseline (jfif.hip, optimize) or a progressive file (jfifprog.hip), with no IDCT,
+// colour, FDCT or second quantisation in between (aej_jfif_transcode_*, include/aej.h).  What jpegtran -optimize / -progressive do.
+//
+// The decoders leave a file's blocks in MCU order with the dummy edge blocks, natural order inside a block; the coders read the same
+// MCU order, zigzag order inside a block.  Files are grouped by (H, W, hs, vs); a group runs the existing entropy stages once, every
+// file of it one "quality" of a one-image batch, so that JfifParams::hdr -- per quality in the coders -- carries each file's own
+// markers (SOI, JFIF APP0 with the source's density, the source's quantisation tables and frame header).  Stages:
+//   k_jt_bridge     one wave per block: lane z reads natural index k_jt_zz[z] of the source block and writes position z of the coder's
+//                   block (128 contiguous bytes in, 128 out); the range check of libjpeg's encoder (AC |v| <= 1023, DC -1024 .. 1023)
+//                   is one ballot, and a block that fails marks its file by one atomicCAS and is written as zeros.  So are the blocks
+//                   of a file whose decode had failed before this launch; whether the GOOD blocks of a file that fails in this launch
+//                   arrive as data or as zeros depends on when their wave reads the status word, and does not matter: the file's
+//                   length becomes 0, and every block the coders are given is in range, so their per-block stream bound holds
+//   (per group)     launch_jfif_entropy / launch_jfifprog_entropy: histogram .. file lengths, unchanged
+//   k_jt_sos_ids    progressive groups with component ids other than 1, 2, 3 only: the ids in the SOS markers k_jfp_tables wrote
+//   k_jt_place      one thread: the files' offsets in the packed output, group after group
+//   (per group)     launch_jfif_scatter / launch_jfifprog_scatter
+//   k_jt_finish     one thread per file: length and offset in the caller's order; a failed file's length is 0
+// Bounds: every index derives from the host layout (JtPlan): a wave's block lies inside [0, n_blocks) of the file jt_find_file returns,
+// src and dst are that file's own ranges of the decoder's and the group's coefficient buffers, the status index is below the call's
+// file count, and an SOS marker is patched only inside the kJfpPiece bytes of its own piece.
+#include "aej_common.h"
+#include "aej_ctx.h"
+#include "aej_launch.h"
+#include "jfif_huff_core.h"
+
+namespace aej {
+
+constexpr int kJtThreads = 256;
+
+__constant__ unsigned char k_jt_zz[64] = { 0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14,
+                                           21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46,
+                                           53, 60, 61, 54, 47, 55, 62, 63 };
+
+__device__ __forceinline__ int jt_find_file(const JtFile *f, int n, long long t)      // last file whose src_base <= t (jd_find_file)
+{
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (f[mid].src_base <= t) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(kJtThreads) void k_jt_bridge(const JtFile *__restrict__ files, int n, long long n_blocks, int *__restrict__ status)
+{
+    const long long t = (long long)blockIdx.x * (kJtThreads / 64) + (threadIdx.x >> 6);      // uniform over the wave
+    if (t >= n_blocks) return;
+    const int z = threadIdx.x & 63;
+    const JtFile F = files[jt_find_file(files, n, t)];
+    const long long b = t - F.src_base;
+    if (b >= F.n_blocks) return;                             // never: the files' ranges tile [0, n_blocks)
+    const int v = F.src[b * 64 + k_jt_zz[z]];
+    const bool bad = z == 0 ? (v < -1024 || v > 1023) : (v < -1023 || v > 1023);
+    const bool any_bad = __ballot(bad) != 0ull;
+    if (any_bad && z == 0) atomicCAS(status + F.status_index, 0, AEJ_JPEGDEC_COEF_RANGE);
+    const bool failed = any_bad || status[F.status_index] != 0;
+    F.dst[b * 64 + z] = failed ? (short)0 : (short)v;
+}
+
+// the component ids of the SOS markers of a progressive group: k_jfp_tables writes index + 1; the frame header in the file's prefix
+// (the last 19 bytes before dht_off) has the source's.  One thread per (file, scan).
+__global__ __launch_bounds__(kJtThreads) void k_jt_sos_ids(JfpGeom g, const JfifParams *__restrict__ par, unsigned char *__restrict__ fhdr,
+                                                           const int *__restrict__ fhdr_len)
+{
+    const long long idx = (long long)blockIdx.x * kJtThreads + threadIdx.x;
+    if (idx >= (long long)g.segs * g.nscan) return;
+    const long long seg = idx / g.nscan;
+    const int si = (int)(idx % g.nscan);
+    const JfifParams &p = par[seg / g.B];
+    const int nc = g.sc[si].Ss == 0 ? 1 + g.nchroma : 1, hl = fhdr_len[idx], at = hl - (8 + 2 * nc);
+    if (p.dht_off < 19 || p.dht_off > kJfifHdrMax || at < 0 || hl > kJfpPiece) return;
+    const unsigned char *sof = p.hdr + p.dht_off - 19;
+    unsigned char *q = fhdr + idx * kJfpPiece + at;
+    for (int c = 0; c < nc; c++) {
+        const int k = q[5 + 2 * c] - 1;
+        if (k >= 0 && k < 3) q[5 + 2 * c] = sof[10 + 3 * k];
+    }
+}
+
+__global__ void k_jt_place(int n, const long long *__restrict__ glen, long long *__restrict__ goff, long long *__restrict__ total)
+{
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    long long off = 0;
+    for (int o = 0; o < n; o++) {
+        goff[o] = off;
+        off += glen[o];
+    }
+    *total = off;
+}
+
+__global__ __launch_bounds__(kJtThreads) void k_jt_finish(const JtFile *__restrict__ files, int n, const int *__restrict__ status,
+                                                          const long long *__restrict__ glen, const long long *__restrict__ goff,
+                                                          long long *__restrict__ lengths, long long *__restrict__ offsets)
+{
+    const int i = blockIdx.x * kJtThreads + threadIdx.x;
+    if (i >= n) return;
+    const JtFile &F = files[i];
+    lengths[i] = status[F.status_index] ? 0 : glen[F.out_pos];
+    offsets[i] = goff[F.out_pos];
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------------------
+static const unsigned char kJtZzHost[64] = { 0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14,
+                                             21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46,
+                                             53, 60, 61, 54, 47, 55, 62, 63 };
+
+template <class D>
+static void jt_source(const D &d, JtSource &s)
+{
+    s = JtSource{};
+    s.width = d.width; s.height = d.height; s.hs = d.hs; s.vs = d.vs;
+    for (int c = 0; c < 3; c++) {
+        s.comp_id[c] = d.comp_id[c];
+        s.comp_tq[c] = d.comp_tq[c];
+        for (int i = 0; i < 64; i++) s.qt[c][i] = d.qt[c][i];
+    }
+    s.units = 0; s.xdensity = 1; s.ydensity = 1;
+}
+void jfiftrans_source(const aej_jpegdec_desc &d, JtSource &s) { jt_source(d, s); }
+void jfiftrans_source(const aej_jpegprog_frame &f, JtSource &s) { jt_source(f, s); }
+
+// SOI, JFIF 1.01 APP0 with the source's density, one DQT per distinct table id in order of first reference, SOF0 / SOF2
+int jfiftrans_prefix_host(const JtSource &s, bool prog, unsigned char *o, int capacity)
+{
+    unsigned char b[2 + 18 + 3 * 69 + 19];
+    int n = 0;
+    auto put = [&](std::initializer_list<int> v) { for (int x : v) b[n++] = (unsigned char)x; };
+    put({ 0xFF, 0xD8, 0xFF, 0xE0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, s.units, s.xdensity >> 8, s.xdensity & 255, s.ydensity >> 8, s.ydensity & 255, 0, 0 });
+    for (int c = 0; c < 3; c++) {
+        bool seen = false;
+        for (int e = 0; e < c; e++) seen |= s.comp_tq[e] == s.comp_tq[c];
+        if (seen) continue;
+        put({ 0xFF, 0xDB, 0, 67, s.comp_tq[c] & 15 });
+        for (int i = 0; i < 64; i++) b[n++] = (unsigned char)s.qt[c][kJtZzHost[i]];
+    }
+    put({ 0xFF, prog ? 0xC2 : 0xC0, 0, 17, 8, s.height >> 8, s.height & 255, s.width >> 8, s.width & 255, 3 });
+    for (int c = 0; c < 3; c++) put({ s.comp_id[c], c == 0 ? (s.hs << 4) | s.vs : 0x11, s.comp_tq[c] });
+    if (n > capacity) return -1;
+    memcpy(o, b, n);
+    return n;
+}
+
+bool jfiftrans_plan(const std::vector<JtSource> &src, const std::vector<long long> &n_blocks, bool prog, JtPlan &plan)
+{
+    const int n = (int)src.size();
+    if (n < 1 || n > 65535 || n_blocks.size() != src.size()) return false;
+    plan = JtPlan{};
+    plan.prog = prog;
+    plan.files.assign(n, JtFile{});
+    for (int i = 0; i < n; i++) {
+        const JtSource &s = src[i];
+        const int ss = s.hs == 1 && s.vs == 1 ? 0 : s.hs == 2 && s.vs == 1 ? 1 : s.hs == 2 && s.vs == 2 ? 2 : -1;
+        if (ss < 0) return false;
+        JtGroup *grp = nullptr;
+        for (JtGroup &c : plan.groups)
+            if (c.g.H == s.height && c.g.W == s.width && c.g.hs == s.hs && c.g.vs == s.vs) grp = &c;
+        if (!grp) {
+            plan.groups.emplace_back();
+            grp = &plan.groups.back();
+            grp->foreign_ids = false;
+            if (!jfif_geom(1, s.height, s.width, 1, grp->g, ss, 1)) return false;
+        }
+        if (n_blocks[i] != grp->g.nblk) return false;
+        grp->files.push_back(i);
+        grp->foreign_ids |= s.comp_id[0] != 1 || s.comp_id[1] != 2 || s.comp_id[2] != 3;
+        plan.files[i].src_base = plan.n_blocks;
+        plan.files[i].n_blocks = n_blocks[i];
+        plan.n_blocks += n_blocks[i];
+    }
+    long long first = 0;
+    for (JtGroup &c : plan.groups) {
+        const int ng = (int)c.files.size(), ss = c.g.hs == 1 ? 0 : c.g.vs == 1 ? 1 : 2;
+        if (!jfif_geom(1, c.g.H, c.g.W, ng, c.g, ss, 1) || (prog && !jfifprog_geom(c.g, c.p))) return false;
+        c.first = first;
+        c.par.assign(ng, JfifParams{});
+        for (int k = 0; k < ng; k++) {
+            const JtSource &s = src[c.files[k]];
+            JfifParams &p = c.par[k];
+            const int len = jfiftrans_prefix_host(s, prog, p.hdr, kJfifHdrMax - 14);
+            if (len < 0) return false;
+            p.dht_off = p.hdr_len = len;
+            if (!prog) {                                     // k_jfif_tables takes the SOS from the end of the markers
+                const unsigned char sos[14] = { 0xFF, 0xDA, 0, 12, 3, s.comp_id[0], 0x00, s.comp_id[1], 0x11, s.comp_id[2], 0x11, 0, 63, 0 };
+                memcpy(p.hdr + len, sos, 14);
+                p.hdr_len = len + 14;
+            }
+            plan.files[c.files[k]].out_pos = (int)(first + k);
+        }
+        first += ng;
+    }
+    return true;
+}
+
+unsigned long long jfiftrans_carve(void *base, JtPlan &plan)
+{
+    Carver c(base);
+    const long long n = (long long)plan.files.size();
+    plan.d_files = c.take<JtFile>(n);
+    plan.glen = c.take<long long>(n);
+    plan.goff = c.take<long long>(n);
+    plan.total = c.take<long long>(1);
+    for (JtGroup &grp : plan.groups) {
+        const JfifGeom &g = grp.g;
+        if (plan.prog) {
+            jfifprog_carve_coded(c, g, grp.p, grp.w, grp.pw);
+        } else {
+            jfif_carve_coded(c, g, grp.w);
+        }
+        for (size_t k = 0; k < grp.files.size(); k++)
+            plan.files[grp.files[k]].dst = grp.w.coef ? grp.w.coef + (long long)k * g.nblk * 64 : nullptr;
+    }
+    return c.bytes();
+}
+
+hipError_t launch_jfiftrans(hipStream_t st, JtPlan &plan, int *status, unsigned char *out, unsigned long long cap, long long *lengths,
+                            long long *offsets)
+{
+    const int n = (int)plan.files.size();
+    hipError_t e = hipMemcpyAsync(plan.d_files, plan.files.data(), sizeof(JtFile) * n, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_jt_bridge, dim3((unsigned)((plan.n_blocks + kJtThreads / 64 - 1) / (kJtThreads / 64))), dim3(kJtThreads), 0, st, plan.d_files, n,
+                       plan.n_blocks, status);
+    for (JtGroup &c : plan.groups) {
+        if ((e = hipMemcpyAsync(c.w.par, c.par.data(), sizeof(JfifParams) * c.par.size(), hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+        long long *len = plan.glen + c.first, *off = plan.goff + c.first;
+        if (!plan.prog) {
+            if ((e = launch_jfif_entropy(st, c.g, c.w, len, off)) != hipSuccess) return e;
+            continue;
+        }
+        if ((e = launch_jfifprog_entropy(st, c.p, c.pw, c.w.coef, c.w.par, len, off)) != hipSuccess) return e;
+        if (c.foreign_ids)
+            hipLaunchKernelGGL(k_jt_sos_ids, dim3((unsigned)(((long long)c.p.segs * c.p.nscan + kJtThreads - 1) / kJtThreads)), dim3(kJtThreads), 0, st,
+                               c.p, c.w.par, c.pw.fhdr, c.pw.fhdr_len);
+    }
+    hipLaunchKernelGGL(k_jt_place, dim3(1), dim3(1), 0, st, n, plan.glen, plan.goff, plan.total);
+    for (JtGroup &c : plan.groups) {
+        if (!out) break;
+        e = plan.prog ? launch_jfifprog_scatter(st, c.p, c.pw, c.w.par, plan.glen + c.first, plan.goff + c.first, out, cap)
+                      : launch_jfif_scatter(st, c.g, c.w, plan.glen + c.first, plan.goff + c.first, out, cap);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_jt_finish, dim3((unsigned)((n + kJtThreads - 1) / kJtThreads)), dim3(kJtThreads), 0, st, plan.d_files, n, status, plan.glen,
+                       plan.goff, lengths, offsets);
+    return hipGetLastError();
+}
+
+}  // namespace aej

@@ -664,13 +664,21 @@ hipError_t launch_jpegdec_sync(hipStream_t st, int n, const JdBufSizes &z, const
     return hipGetLastError();
 }
 
-hipError_t launch_jpegdec_finish(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, int S, unsigned char *out, int *status)
+// after the last sync round: the coefficients of every file (natural order, MCU order, dummy blocks included) and the decode's status words
+hipError_t launch_jpegdec_write(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, int S, int *status)
 {
     hipError_t e = hipMemsetAsync(w.coef, 0, (size_t)z.blocks * 128, st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_jd_scan_slots, dim3(n), dim3(kJdScanThreads), 0, st, w.files, w.sl);
     hipLaunchKernelGGL(k_jd_write, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.slots, w.segs, w.clean, w.sl, S, w.coef,
                        status);
+    return hipGetLastError();
+}
+
+hipError_t launch_jpegdec_finish(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, int S, unsigned char *out, int *status)
+{
+    const hipError_t e = launch_jpegdec_write(st, n, z, w, S, status);
+    if (e != hipSuccess) return e;
     return launch_jpegdec_recon(st, n, z, w, out);
 }
 

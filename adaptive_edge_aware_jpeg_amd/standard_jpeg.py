@@ -10,6 +10,13 @@ coefficients, and so the decoded pixels, are those of the baseline file.  The de
 complete progressive file -- on the device, pixel-identical to ``Image.open(file).convert("RGB")`` (csrc/jpegdec.hip, ``aej_jpegdec_*``;
 csrc/jpegprog.hip, ``aej_jpegprog_*``).
 
+``standard_jpeg_transcode_many`` joins the two without touching a pixel: it Huffman-decodes existing files to their quantised
+coefficients on the device and entropy-codes the same coefficients again, as a baseline file under the file's own optimal Huffman
+tables or as the ten-scan progressive file (csrc/jfiftrans.hip, ``aej_jfif_transcode_*``) -- what ``jpegtran -optimize`` and
+``jpegtran -progressive`` do.  The output keeps the source's quantisation tables, component ids, sampling and JFIF density, drops its
+restart markers, and with ``keep_metadata=True`` carries its APP1..APP13, APP15 and COM segments over (spliced on the host).  A
+Pillow file transcoded this way equals Pillow's own ``optimize=True`` / ``progressive=True`` file of the same pixels byte for byte.
+
 The files are byte-identical to Pillow's with libjpeg-turbo (JFIF 1.01, Annex K quantisation and Huffman tables, islow DCT, no restart
 markers) and the decoded pixels equal ``np.asarray(Image.open(file).convert("RGB"))``.  Colour, down-sampling and DCT run once per image
 and every requested quality reuses them (csrc/jfif.hip, ``aej_jfif_*`` in include/aej.h).  Images are uint8, or float32 in [0, 1]
@@ -358,3 +365,175 @@ def decode_sync_rounds(device: int = 0) -> int:
     (aej_jpegdec_sync_rounds): 0 when every segment fit one subsequence."""
     ctx = get_context(device)
     return int(ctx.lib.aej_jpegdec_sync_rounds(ctx.handle))
+
+
+# ---- lossless transcode -------------------------------------------------------------------------------------------------------------
+def _check_bool(name, v) -> bool:
+    if not isinstance(v, (bool, np.bool_)):
+        raise TypeError(f"{name} {v!r}: a bool required")
+    return bool(v)
+
+
+def marker_segments(data, index: int = 0):
+    """[(marker, start, end)] of the marker segments between SOI and the first SOS of one file: data[start:end] is the whole segment,
+    FF xx and its length included (host only).  ValueError naming the file for bytes that are not such a sequence."""
+    mv = memoryview(data).cast("B")
+    n, i, out = len(mv), 2, []
+    if n < 4 or mv[0] != 0xFF or mv[1] != 0xD8:
+        raise ValueError(f"file {index}: no SOI marker")
+    while True:
+        if i + 4 > n or mv[i] != 0xFF:
+            raise ValueError(f"file {index}: marker expected at byte {i}")
+        m = mv[i + 1]
+        if m == 0xFF:                              # fill byte
+            i += 1
+            continue
+        if m == 0xDA:
+            return out
+        if m == 0x01 or 0xD0 <= m <= 0xD9:
+            raise ValueError(f"file {index}: marker FF{m:02X} before SOS")
+        length = (mv[i + 2] << 8) | mv[i + 3]
+        if length < 2 or i + 2 + length > n:
+            raise ValueError(f"file {index}: truncated segment FF{m:02X}")
+        out.append((m, i, i + 2 + length))
+        i += 2 + length
+
+
+def _jfif_density(mv, segs):
+    """(units, Xdensity, Ydensity) of the source's JFIF APP0; (0, 1, 1) -- what Pillow writes without dpi= -- when it has none"""
+    for m, a, b in segs:
+        if m == 0xE0 and b - a >= 16 and bytes(mv[a + 4:a + 9]) == b"JFIF\0":
+            return mv[a + 11], (mv[a + 12] << 8) | mv[a + 13], (mv[a + 14] << 8) | mv[a + 15]
+    return 0, 1, 1
+
+
+def metadata_segments(data, index: int = 0) -> bytes:
+    """What keep_metadata=True carries over: the file's APP1 .. APP13, APP15 and COM segments, verbatim and in order.  APP0 (JFIF,
+    JFXX: the output has its own) and APP14 (Adobe: the output is a JFIF file) never are."""
+    mv = memoryview(data).cast("B")
+    return b"".join(bytes(mv[a:b]) for m, a, b in marker_segments(mv, index) if 0xE1 <= m <= 0xED or m == 0xEF or m == 0xFE)
+
+
+def _parse_any(f, i):
+    """-> (is_progressive, JpegDecDesc | (JpegProgFrame, scans)); refuses what the transcoder does not take, naming the file"""
+    try:
+        d, prog = parse_header(f, i), False
+        frame = d
+    except NotImplementedError as e:
+        if "progressive JPEG (SOF2)" not in str(e):
+            raise
+        d, prog = parse_scans(f, i), True
+        frame = d[0]
+    if frame.ncomp != 3:
+        raise NotImplementedError(f"file {i}: a single-component (grey) file: the transcoder takes three-component files")
+    if frame.precision16:
+        raise NotImplementedError(f"file {i}: a 16-bit quantisation table: the transcoder writes 8-bit tables")
+    return prog, d
+
+
+def transcode_prefix(data, progressive: bool = False, index: int = 0) -> bytes:
+    """The bytes SOI .. end of SOF0 / SOF2 that standard_jpeg_transcode_many writes for one file (aej_jfif_transcode_headers_host,
+    host only): JFIF APP0 with the source's density, its quantisation tables, its frame header."""
+    from ._lib import load_library
+    progressive = _check_progressive(progressive)
+    is_prog, d = _parse_any(data, index)
+    mv = memoryview(data).cast("B")
+    dens = (ctypes.c_uint16 * 3)(*_jfif_density(mv, marker_segments(mv, index)))
+    frame = d[0] if is_prog else d
+    buf = (ctypes.c_uint8 * 512)()
+    n = load_library().aej_jfif_transcode_headers_host(None if is_prog else ctypes.addressof(frame), ctypes.addressof(frame) if is_prog else None,
+                                                       ctypes.addressof(dens), int(progressive), ctypes.addressof(buf), 512)
+    if n < 0:
+        raise ValueError(f"file {index}: the library refuses its descriptor ({n})")
+    return bytes(buf[:n])
+
+
+def splice_metadata(out: bytes, meta: bytes) -> bytes:
+    """`meta` (metadata_segments) right after the JFIF APP0 of a file this library wrote: SOI (2 bytes) and APP0 (18) come first"""
+    return out[:20] + meta + out[20:] if meta else out
+
+
+_last_transcode_groups = 0
+
+
+def transcode_groups() -> int:
+    """Entropy-encode chains the last successful standard_jpeg_transcode_many of this process ran: one per distinct (height, width,
+    sampling) among its files.  A diagnostic for tests and tools, nothing to build on: one module-level value for every device and
+    thread, which a call that raises leaves as it was."""
+    return _last_transcode_groups
+
+
+def standard_jpeg_transcode_many(files, progressive: bool = False, device: int = 0, keep_metadata: bool = False) -> List[bytes]:
+    """Lossless transcode on the device: -> every file entropy-coded again, in input order.  files: a non-empty sequence of bytes-like
+    JPEG contents, baseline / extended-sequential (SOF0 / SOF1) and complete progressive (SOF2) files of any sizes and of the 4:4:4,
+    4:2:2 and 4:2:0 layouts mixed freely.  progressive=False: a baseline file under the file's own optimal Huffman tables (what
+    optimize=True writes); progressive=True: libjpeg's ten-scan progressive file (what progressive=True writes).  Every quantised
+    coefficient of the output equals the source's, so both decode to the same pixels, and a file Pillow wrote gives Pillow's own
+    optimize=True / progressive=True file byte for byte.  The output: SOI, JFIF 1.01 APP0 with the source's density, with
+    keep_metadata=True the source's APP1 .. APP13, APP15 and COM segments (host work; never APP0 or Adobe APP14), the source's
+    quantisation tables (8-bit, one DQT per table), its frame header, then tables and scans as the encoders lay them out.  Restart
+    markers are dropped.  Refused before any device work, naming the file: what the decoders' parsers refuse, grey files and 16-bit
+    quantisation tables (NotImplementedError), malformed headers (ValueError).  A file whose scan is corrupt, or that decodes to a
+    coefficient an 8-bit JPEG cannot hold, raises ValueError naming its index and the reason; nothing is returned then.  There is no
+    CPU fallback."""
+    global _last_transcode_groups
+    from ._lib import JPEGDEC_STATUS, JpegDecDesc, JpegProgFrame, JpegProgScan
+    progressive, keep_metadata = _check_bool("progressive", progressive), _check_bool("keep_metadata", keep_metadata)
+    files = list(files)
+    if not files:
+        raise ValueError("standard_jpeg_transcode_many needs at least one file")
+    n = len(files)
+    views, parsed, base_idx, prog_idx, density, meta = [], [None] * n, [], [], [None] * n, [b""] * n
+    for i, f in enumerate(files):
+        is_prog, parsed[i] = _parse_any(f, i)
+        (prog_idx if is_prog else base_idx).append(i)
+        mv = memoryview(f).cast("B")
+        views.append(mv)
+        segs = marker_segments(mv, i)
+        density[i] = _jfif_density(mv, segs)
+        if keep_metadata:
+            meta[i] = metadata_segments(mv, i)
+    order = base_idx + prog_idx                     # the call's file order: baseline sources first
+    nb, npg = len(base_idx), len(prog_idx)
+    ctx = get_context(device)
+    t, lib = ctx.torch, ctx.lib
+    descs = (JpegDecDesc * max(nb, 1))(*[parsed[i] for i in base_idx])
+    frames = (JpegProgFrame * max(npg, 1))(*[parsed[i][0] for i in prog_idx])
+    flat = [(i, s) for i in prog_idx for s in parsed[i][1]]
+    pscans = (JpegProgScan * max(len(flat), 1))(*[s for _, s in flat])
+    # one staging copy for both kinds (the pinned buffer behind _stage is only valid until its next use)
+    scans, off = _stage(ctx, views, [(i, parsed[i].scan_offset, parsed[i].scan_length) for i in base_idx] +
+                        [(i, s.data_offset, s.data_length) for i, s in flat])
+    data, scan_off, data_off = scans, np.ascontiguousarray(off[:max(nb, 1)]), np.ascontiguousarray(off[nb:nb + max(len(flat), 1)])
+    dens = np.ascontiguousarray(np.array([density[i] for i in order], np.uint16))
+    nws = int(lib.aej_jfif_transcode_workspace_bytes(ctx.handle, ctypes.addressof(descs), nb, ctypes.addressof(frames), ctypes.addressof(pscans),
+                                                     npg, int(progressive)))
+    if nws == 0:
+        raise ValueError("descriptors the library refuses")
+    ws = ctx.workspace(nws)
+    status, offsets, lengths = ctx.empty((n,), t.int32), ctx.empty((n,), t.int64), ctx.empty((n,), t.int64)
+    total, groups = ctypes.c_uint64(), ctypes.c_int32()
+    cap = sum(len(v) for v in views) * 5 // 4 + (PROGRESSIVE_HEADER_CAPACITY if progressive else HEADER_CAPACITY) * n
+    out = ctx.empty((cap,), t.uint8)
+    call = lambda o, c: lib.aej_jfif_transcode_batch(  # noqa: E731
+        ctx.handle, ctypes.addressof(descs), nb, scans.data_ptr(), ctypes.c_uint64(scans.numel()), scan_off.ctypes.data, ctypes.addressof(frames),
+        ctypes.addressof(pscans), npg, data.data_ptr(), ctypes.c_uint64(data.numel()), data_off.ctypes.data, dens.ctypes.data, int(progressive),
+        o.data_ptr(), ctypes.c_uint64(c), offsets.data_ptr(), lengths.data_ptr(), ctypes.addressof(total), status.data_ptr(),
+        ctypes.addressof(groups), ws.data_ptr(), ctypes.c_uint64(nws))
+    rc = call(out, cap)
+    if rc == -4 and total.value > cap:             # AEJ_ERR_CAPACITY: run again with the exact size
+        cap = int(total.value)
+        out = ctx.empty((cap,), t.uint8)
+        rc = call(out, cap)
+    ctx.check(rc)
+    _last_transcode_groups = int(groups.value)
+    st = status.cpu().numpy()                       # the one read-back of the per-file status words
+    bad = sorted((order[int(k)], int(st[k])) for k in np.flatnonzero(st))
+    if bad:
+        i, code = bad[0]
+        raise ValueError(f"file {i}: {JPEGDEC_STATUS[code] if 0 <= code < len(JPEGDEC_STATUS) else f'status {code}'}")
+    blob = out[:int(total.value)].cpu().numpy().tobytes()
+    res = [None] * n
+    for k, (o, m) in enumerate(zip(offsets.cpu().tolist(), lengths.cpu().tolist())):
+        res[order[k]] = splice_metadata(blob[o:o + m], meta[order[k]])
+    return res

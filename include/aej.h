@@ -442,7 +442,8 @@ AEJ_API int aej_jfif_recon_batch_prog(aej_ctx *ctx, int batch, int H, int W, int
 enum {
     AEJ_JPEGDEC_OK = 0, AEJ_JPEGDEC_TRUNCATED = 1 /* the scan ends before the last MCU */, AEJ_JPEGDEC_BAD_CODE = 2 /* not in the table */,
     AEJ_JPEGDEC_RUN_PAST_63 = 3 /* an AC run beyond the block */, AEJ_JPEGDEC_BAD_DC = 4 /* DC category above 11 */,
-    AEJ_JPEGDEC_BAD_RESTART = 5 /* a restart marker out of sequence, missing or unexpected */
+    AEJ_JPEGDEC_BAD_RESTART = 5 /* a restart marker out of sequence, missing or unexpected */,
+    AEJ_JPEGDEC_COEF_RANGE = 6 /* aej_jfif_transcode_batch only: a coefficient an 8-bit JPEG cannot hold (AC beyond +-1023, DC outside -1024 .. 1023) */
 };
 typedef struct aej_jpegdec_huff {
     uint16_t lut[512];         /* 9-bit look-ahead: (code length << 8) | symbol; 0 = the code is longer than 9 bits */
@@ -524,6 +525,40 @@ AEJ_API uint64_t aej_jpegprog_workspace_bytes(aej_ctx *ctx, const aej_jpegprog_f
 AEJ_API int aej_jpegprog_batch(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
                                const uint8_t *data, uint64_t data_bytes, const int64_t *data_offsets_host, uint8_t *out, uint64_t out_bytes,
                                const int64_t *out_offsets_host, int32_t *status, void *workspace, uint64_t workspace_bytes);
+
+/* ---- lossless transcode: existing files entropy-coded again (standard_jpeg_transcode_many) ----------------------------------------------
+ * What jpegtran -optimize / -progressive do, on the device: the files are Huffman-decoded to their quantised coefficients by the stages of
+ * aej_jpegdec_batch / aej_jpegprog_batch (no IDCT, no colour) and those coefficients -- every one, the dummy edge blocks of the MCU grid
+ * included -- are coded again by the entropy stages of aej_jfif_encode_batch_opt with optimize (progressive = 0: a baseline SOF0 file
+ * under its own optimal Huffman tables) or of aej_jfif_encode_batch_prog (progressive = 1: SOF2, libjpeg's ten scans).  One call takes
+ * baseline sources (descs_host, n_base, scans ... as aej_jpegdec_batch) and progressive ones (frames_host, pscans_host, n_prog, data ...
+ * as aej_jpegprog_batch) together; either count may be 0, not both.  File i of the call is baseline source i for i < n_base, otherwise
+ * progressive source i - n_base.  Three-component files only (AEJ_ERR_UNSUPPORTED for a grey one or one with a 16-bit quantisation
+ * table); restart markers of a source are not written again.
+ *
+ * Output file: SOI; JFIF 1.01 APP0 with the density density_host[3 i .. 3 i + 2] = units, Xdensity, Ydensity (density_host NULL: 0, 1, 1);
+ * one 8-bit DQT per distinct table id the components reference, in order of first reference; SOF0 / SOF2 with the source's component
+ * ids, sampling factors and table selectors; then DHT / SOS as the encoders write them (luma tables in slots 0, chroma in slots 1).
+ * aej_jfif_transcode_headers_host: HOST only, the bytes SOI .. end of SOF of one source (exactly one of desc_host / frame_host given;
+ *   density3_host may be NULL) -> their length, AEJ_ERR_CAPACITY, AEJ_ERR_UNSUPPORTED or AEJ_ERR_ARG.
+ * aej_jfif_transcode_batch: out / out_capacity / offsets / lengths / total_host as aej_jfif_encode_batch_opt, offsets and lengths being
+ *   device int64 [n_base + n_prog] in the call's file order (the files are packed group after group, not in that order).  status:
+ *   device int32 [n_base + n_prog], AEJ_JPEGDEC_*: a source whose scan is malformed, or that decodes to a coefficient an 8-bit file
+ *   cannot hold (AEJ_JPEGDEC_COEF_RANGE: the coders' per-block bounds rest on that range, so such a block never reaches them), gets
+ *   its reason there and length 0; the other files are written.  Files are grouped by (height, width, sampling): each group runs one
+ *   entropy-encode chain (*n_groups_host, may be NULL, gets their number).  The call waits for the decode's sync rounds and, at its
+ *   end, for the total.  Workspace: aej_jfif_transcode_workspace_bytes with the same descriptors (0 for descriptors the call refuses). */
+AEJ_API int aej_jfif_transcode_headers_host(const aej_jpegdec_desc *desc_host, const aej_jpegprog_frame *frame_host, const uint16_t *density3_host,
+                                            int progressive, uint8_t *out_host, int capacity);
+AEJ_API uint64_t aej_jfif_transcode_workspace_bytes(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base,
+                                                    const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *pscans_host, int n_prog,
+                                                    int progressive);
+AEJ_API int aej_jfif_transcode_batch(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base, const uint8_t *scans, uint64_t scans_bytes,
+                                     const int64_t *scan_offsets_host, const aej_jpegprog_frame *frames_host,
+                                     const aej_jpegprog_scan *pscans_host, int n_prog, const uint8_t *data, uint64_t data_bytes,
+                                     const int64_t *data_offsets_host, const uint16_t *density_host, int progressive, uint8_t *out,
+                                     uint64_t out_capacity, int64_t *offsets, int64_t *lengths, uint64_t *total_host, int32_t *status,
+                                     int32_t *n_groups_host, void *workspace, uint64_t workspace_bytes);
 
 #ifdef __cplusplus
 }

@@ -2,10 +2,11 @@
 (10, 25, 50, 75, 90) in one call, against Pillow's save + load on a thread pool.
 
     python tools/bench_jfif.py [--batch 64] [--repeats 3] [--threads 16] [--subsampling 4:2:0] [--optimize] [--progressive]
-                               [--grouped-only] [--no-pillow] [--out FILE]
+                               [--grouped-only] [--no-pillow] [--transcode [--ab ROOT] [--routes a,b]] [--out FILE]
 
 --subsampling / --optimize / --progressive are Pillow's keywords of the same names, given to both sides; --grouped-only times the five-quality call
-alone and --no-pillow leaves the CPU side out (for A/B runs of the library against itself).
+alone and --no-pillow leaves the CPU side out (for A/B runs of the library against itself).  --transcode is a mode of its own: the
+lossless transcoder against decode + encode over pixels (see transcode()).
 
 "encode" is aej_jfif_encode_batch writing the files to device memory (the library waits for the total length at its end); "encode+recon"
 adds aej_jfif_recon_batch, Pillow's decode of every file as device uint8.  Neither copies the files back to the host.  Pillow does
@@ -22,7 +23,8 @@ import time
 from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+# --root DIR: import the package of another checkout (the --ab worker); the test images always come from this one
+sys.path.insert(0, os.path.abspath(sys.argv[sys.argv.index("--root") + 1]) if "--root" in sys.argv[1:-1] else ROOT)
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
@@ -63,6 +65,109 @@ def timed(fn, repeats):
     return float(np.median(ts))
 
 
+def transcode_routes(a):
+    """name -> callable returning the bytes a route wrote (0 where it writes none), for the package this process imported"""
+    x = images(a.batch)
+    files = A.standard_jpeg_many(x, 75, subsampling=a.subsampling)
+    xd = A._lib.get_context(0).to_device(x, torch.uint8)
+
+    def pixels(**kw):
+        dec = A.standard_jpeg_decode_many(files)
+        return sum(len(f) for f in A.standard_jpeg_many(torch.stack(dec), 75, subsampling=a.subsampling, **kw))
+
+    def batch_default():
+        A.standard_jpeg_batch(xd, [75])
+        return 0
+
+    def decode_default():
+        A.standard_jpeg_decode_many(files)
+        return 0
+
+    routes = {"decode_encode_optimize": lambda: pixels(optimize=True), "decode_encode_progressive": lambda: pixels(progressive=True),
+              "standard_jpeg_batch": batch_default, "standard_jpeg_decode_many": decode_default}
+    if hasattr(A, "standard_jpeg_transcode_many"):
+        routes["transcode_optimize"] = lambda: sum(len(f) for f in A.standard_jpeg_transcode_many(files, progressive=False))
+        routes["transcode_progressive"] = lambda: sum(len(f) for f in A.standard_jpeg_transcode_many(files, progressive=True))
+    return routes, sum(len(f) for f in files)
+
+
+def run_route(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    nbytes = fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3, int(nbytes)
+
+
+def worker(a):
+    """--worker: serve one route per line of standard input, answer "@@ <ms> <bytes>" (the other side of --ab: a process that imported
+    the package of another checkout through --root)"""
+    routes, _ = transcode_routes(a)
+    print("@@ ready", flush=True)
+    for line in sys.stdin:
+        name = line.strip()
+        if name == "quit":
+            break
+        ms, nbytes = run_route(routes[name])
+        print(f"@@ {ms} {nbytes}", flush=True)
+
+
+def transcode(a):
+    """--transcode: --batch natural 4K files (quality 75, --subsampling, plain baseline) through standard_jpeg_transcode_many to
+    optimised baseline and to progressive files, beside the lossy route over pixels on the same files (standard_jpeg_decode_many, then
+    standard_jpeg_many(optimize=True / progressive=True)) and the plain standard_jpeg_batch / standard_jpeg_decode_many calls.  With
+    --ab ROOT a second process imports the package of the checkout at ROOT (its library built there) and runs the routes it has; the
+    two sides alternate route by route inside every round, so both see the same machine state.  One warm-up round, then the medians
+    of --repeats rounds, with the bytes of the sources and of the outputs.  --routes a,b restricts the run (for a profiler)."""
+    import subprocess
+    routes, source_bytes = transcode_routes(a)
+    if a.routes:
+        routes = {k: routes[k] for k in a.routes.split(",")}
+    child, sides = None, {"branch": list(routes)}
+    if a.ab:
+        child = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--worker", "--root", a.ab, "--batch", str(a.batch), "--subsampling",
+                                  a.subsampling], stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True)
+
+        def answer():
+            for line in child.stdout:
+                if line.startswith("@@ "):
+                    return line.split()[1:]
+            raise RuntimeError("the --ab worker ended")
+
+        answer()
+        sides["parent"] = [k for k in routes if not k.startswith("transcode")]
+
+    def ask(name):
+        child.stdin.write(name + "\n")
+        child.stdin.flush()
+        ms, nbytes = answer()
+        return float(ms), int(nbytes)
+
+    times = {s: {k: [] for k in ks} for s, ks in sides.items()}
+    size = {s: {} for s in sides}
+    for r in range(a.repeats + 1):
+        for k in routes:
+            for s in sides:
+                if k not in times[s]:
+                    continue
+                ms, nbytes = run_route(routes[k]) if s == "branch" else ask(k)
+                if r:
+                    times[s][k].append(ms)
+                size[s][k] = nbytes
+    if child:
+        child.stdin.write("quit\n")
+        child.stdin.flush()
+        child.wait()
+    res = {"mode": "transcode", "batch": a.batch, "H": H, "W": W, "subsampling": a.subsampling, "quality": 75, "repeats": a.repeats,
+           "source_bytes": source_bytes, "output_bytes": size,
+           "ms": {s: {k: float(np.median(v)) for k, v in t.items()} for s, t in times.items()}, "ms_all": times}
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=64)
@@ -73,8 +178,17 @@ def main():
     ap.add_argument("--progressive", action="store_true")
     ap.add_argument("--grouped-only", action="store_true")
     ap.add_argument("--no-pillow", action="store_true")
+    ap.add_argument("--transcode", action="store_true")
+    ap.add_argument("--ab", metavar="ROOT")
+    ap.add_argument("--routes")
+    ap.add_argument("--worker", action="store_true")
+    ap.add_argument("--root")
     ap.add_argument("--out")
     a = ap.parse_args()
+    if a.worker:
+        return worker(a)
+    if a.transcode:
+        return transcode(a)
     kw = dict(subsampling=a.subsampling, optimize=a.optimize, progressive=a.progressive)
     x = images(a.batch)
     ctx = A._lib.get_context(0)
