@@ -246,6 +246,11 @@ SIGNATURES = {
     "aej_jfif_transcode_headers_host": (_I, [_P, _P, _P, _I, _P, _I]),
     "aej_jfif_transcode_workspace_bytes": (_U64, [_P, _P, _I, _P, _P, _I, _I]),
     "aej_jfif_transcode_batch": (_I, [_P, _P, _I, _P, _U64, _P, _P, _P, _I, _P, _U64, _P, _P, _I, _P, _U64, _P, _P, _P, _P, _P, _P, _U64]),
+    "aej_jfif_transform_geometry_host": (_I, [_I, _I, _I, _I, _I, _I, _P]),
+    "aej_jfif_transform_coefs_host": (_I64, [_I, _I, _I, _I, _I, _I, _P, _I64, _P, _I64]),
+    "aej_jfif_transform_headers_host": (_I, [_P, _P, _P, _I, _I, _I, _P, _I]),
+    "aej_jfif_transform_workspace_bytes": (_U64, [_P, _P, _I, _P, _P, _I, _I, _P, _I]),
+    "aej_jfif_transform_batch": (_I, [_P, _P, _I, _P, _U64, _P, _P, _P, _I, _P, _U64, _P, _P, _I, _P, _I, _P, _U64, _P, _P, _P, _P, _P, _P, _U64]),
     "aej_test_jpegprog_coefs": (_I, [_P, _P, _P, _I, _P, _U64, _P, _I, _P, _U64, _P, _P, _U64]),             # include/aej_testing.h (tests only)
     "aej_test_jpegprog_coefs_host": (_I, [_P, _P, _P, _U64, _I, _P, _U64]),                                 # include/aej_testing.h (tests only)
 }

@@ -340,7 +340,13 @@ hipError_t launch_jpegprog_recon(hipStream_t st, const JpLayout &y, const JpBufs
 int jpegprog_coefs_host(const aej_jpegprog_frame &frame, const aej_jpegprog_scan *scans, const unsigned char *file, unsigned long long nbytes,
                         int n_levels, short *coef, unsigned long long coef_blocks);
 
-// jfiftrans.hip: lossless transcode -- the decoders' coefficients entropy-coded again under optimal tables (aej_jfif_transcode_*)
+}  // namespace aej
+
+// jfiftrans.hip: lossless transcode -- the decoders' coefficients entropy-coded again under optimal tables (aej_jfif_transcode_*),
+// with a lossless flip / rotation / transposition on the way (aej_jfif_transform_*)
+#include "jfif_transform_core.h"
+
+namespace aej {
 struct JtSource {                      // what the output's markers take from one parsed file
     int width, height, hs, vs;
     unsigned char comp_id[3], comp_tq[3];
@@ -348,12 +354,12 @@ struct JtSource {                      // what the output's markers take from on
     int units, xdensity, ydensity;     // of the JFIF APP0
 };
 struct JtFile {                        // one file of a call (host-computed, uploaded): where the bridge reads and writes its blocks
-    long long src_base, n_blocks;      // its first block among the call's blocks, files in the caller's order, and their number
-    const short *src;                  // its coefficients as its decoder left them: natural order, MCU order (JdFile::blk_base)
-    short *dst;                        // its segment of its group's w.coef: zigzag order, the same MCU order
+    long long src_base, n_blocks;      // its first block among the call's OUTPUT blocks, files in the caller's order, and their number
+    const short *src;                  // its coefficients as its decoder left them: natural order, the source's MCU order (JdFile::blk_base)
+    short *dst;                        // its segment of its group's w.coef: zigzag order, the group's MCU order
     int status_index, out_pos;         // its word in the status array; its place in output order (group after group)
 };
-struct JtGroup {                       // the files of one (H, W, hs, vs): one entropy-encode chain, every file one "quality" of one image
+struct JtGroup {                       // the files of one OUTPUT (H, W, hs, vs): one entropy-encode chain, every file one "quality" of one image
     JfifGeom g; JfpGeom p; JfifBufs w; JfpBufs pw;
     std::vector<int> files;            // caller's indices, in segment order
     std::vector<JfifParams> par;       // their markers (kept until the upload has run)
@@ -362,18 +368,29 @@ struct JtGroup {                       // the files of one (H, W, hs, vs): one e
 };
 struct JtPlan {
     bool prog = false;
+    bool transform = false;            // a file has a transform other than kJxNone: k_jt_transform takes the place of k_jt_bridge
     std::vector<JtFile> files;         // caller's order
+    std::vector<JxGeom> geom;          // caller's order (transform only)
     std::vector<JtGroup> groups;
     long long n_blocks = 0;
     JtFile *d_files = nullptr;         // device: the table,
+    JxGeom *d_geom = nullptr;          // the transforms beside it (transform only),
     long long *glen = nullptr, *goff = nullptr, *total = nullptr;      // lengths and offsets in output order, their sum
 };
 void jfiftrans_source(const aej_jpegdec_desc &d, JtSource &s);
 void jfiftrans_source(const aej_jpegprog_frame &f, JtSource &s);
 // the markers SOI .. SOF0 / SOF2 the transcoder writes for one source -> their length, or -1 when they do not fit
 int jfiftrans_prefix_host(const JtSource &s, bool prog, unsigned char *out, int capacity);
-// n_blocks[i]: blocks the decoder holds for file i (must equal the source's MCU-padded count)
-bool jfiftrans_plan(const std::vector<JtSource> &src, const std::vector<long long> &n_blocks, bool prog, JtPlan &plan);
+// what the markers of the transformed file take: the output size and sampling of g, the tables transposed with it
+JtSource jfiftrans_transformed(const JtSource &s, const JxGeom &g);
+// n_blocks[i]: blocks the decoder holds for file i (must equal the source's MCU-padded count).  xf (may be NULL: the transcoder):
+// one transform code per file.  -> -1, or the first file that does not fit: *why (may be NULL) gets jx_geom's answer, kJxBadArg for
+// descriptors that disagree.
+int jfiftrans_plan(const std::vector<JtSource> &src, const std::vector<long long> &n_blocks, bool prog, const int *xf, int trim, JtPlan &plan,
+                   int *why);
+// HOST: the transform of one file's coefficients, the code k_jt_transform runs.  src: [g.n_src][64] natural order, the source's MCU
+// order; dst: [g.n_out][64] zigzag order, the output's MCU order
+void jfiftrans_coefs_host(const JxGeom &g, const short *src, short *dst);
 unsigned long long jfiftrans_carve(void *base, JtPlan &plan);
 // bridge, one entropy chain per group, placement, scatter.  Before it: plan.files[i].src / status_index set by the caller.  status: the
 // call's status words (the decoders' results in; out-of-range coefficients added); lengths / offsets: device, caller's order

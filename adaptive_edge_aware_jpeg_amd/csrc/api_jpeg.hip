@@ -379,7 +379,8 @@ extern "C" int aej_test_jpegprog_coefs_host(const aej_jpegprog_frame *frame_host
     return jpegprog_coefs_host(*frame_host, scans_host, file_host, nbytes, n_levels, coef_out_host, coef_blocks);
 }
 
-// ---- lossless transcode (jfiftrans.hip): the decoders' entropy stages, the bridge, the encoders' entropy stages ---------------------------
+// ---- lossless transcode and transform (jfiftrans.hip): the decoders' entropy stages, the bridge, the encoders' entropy stages ----------------
+// One routine each serves aej_jfif_transcode_* and aej_jfif_transform_*: the transcoder is the transform "none" of every file (xf NULL).
 template <class D>
 static bool jt_source_ok(const D &d)
 {
@@ -398,8 +399,9 @@ struct JtCall {
     std::vector<JtSource> src;
 };
 static int jt_layout(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs, int n_base, const aej_jpegprog_frame *frames,
-                     const aej_jpegprog_scan *pscans, int n_prog, const uint16_t *density, int progressive, JtCall &c)
+                     const aej_jpegprog_scan *pscans, int n_prog, const uint16_t *density, int progressive, const int32_t *xf, int trim, JtCall &c)
 {
+    if (trim != 0 && trim != 1) return fail(ctx, AEJ_ERR_ARG, "%s: trim %d (0 or 1)", fn, trim);
     if (n_base < 0 || n_prog < 0 || n_base + n_prog < 1 || (long long)n_base + n_prog > 65535 || (progressive != 0 && progressive != 1))
         return fail(ctx, AEJ_ERR_ARG, "%s: 1 .. 65535 files and progressive 0 or 1 required", fn);
     if (n_base && !jpegdec_descs_ok(descs, n_base)) return fail(ctx, AEJ_ERR_ARG, "%s: a descriptor aej_jpegdec_parse_host did not write", fn);
@@ -417,8 +419,16 @@ static int jt_layout(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs
         nblk[i] = i < n_base ? c.files[i].n_blocks : c.y.ffiles[i - n_base].n_blocks;
         if (density) { c.src[i].units = density[3 * i] & 255; c.src[i].xdensity = density[3 * i + 1]; c.src[i].ydensity = density[3 * i + 2]; }
     }
-    if (!jfiftrans_plan(c.src, nblk, progressive != 0, c.plan)) return fail(ctx, AEJ_ERR_ARG, "%s: descriptors whose sampling or block counts do not fit", fn);
-    return 0;
+    int why = kJxOk;
+    const int bad = jfiftrans_plan(c.src, nblk, progressive != 0, xf, trim, c.plan, &why);
+    if (bad < 0) return 0;
+    if (why == kJxLayout)
+        return fail(ctx, AEJ_ERR_UNSUPPORTED, "%s: file %d: a transposing transform of a 4:2:2 file would be a 4:4:0 file, which is not built", fn, bad);
+    if (why == kJxNotPerfect)
+        return fail(ctx, AEJ_ERR_ARG, "%s: file %d: transform %d mirrors an axis that is not a whole number of MCUs (trim = 1 drops the partial ones)", fn,
+                    bad, xf ? xf[bad] : 0);
+    if (why == kJxTrimsToZero) return fail(ctx, AEJ_ERR_ARG, "%s: file %d: nothing is left of the mirrored axis after the trim", fn, bad);
+    return fail(ctx, AEJ_ERR_ARG, "%s: file %d: a transform code outside 0 .. 7, or descriptors whose sampling or block counts do not fit", fn, bad);
 }
 
 struct JtWorkspace { JdBufs wb; JpBufs wp; unsigned long long bytes; };
@@ -434,48 +444,101 @@ static JtWorkspace jt_carve(void *workspace, int n_base, int n_prog, JtCall &c)
     return r;
 }
 
-extern "C" int aej_jfif_transcode_headers_host(const aej_jpegdec_desc *desc_host, const aej_jpegprog_frame *frame_host, const uint16_t *density3_host,
-                                               int progressive, uint8_t *out_host, int capacity)
+static int jt_headers(const aej_jpegdec_desc *desc_host, const aej_jpegprog_frame *frame_host, const uint16_t *density3_host, int progressive,
+                      int transform, int trim, uint8_t *out_host, int capacity)
 {
-    if ((!desc_host) == (!frame_host) || !out_host || capacity < 0 || (progressive != 0 && progressive != 1)) return AEJ_ERR_ARG;
+    if ((!desc_host) == (!frame_host) || !out_host || capacity < 0 || (progressive != 0 && progressive != 1) || (trim != 0 && trim != 1)) return AEJ_ERR_ARG;
     if (!(desc_host ? jt_source_ok(*desc_host) : jt_source_ok(*frame_host))) return AEJ_ERR_UNSUPPORTED;
     JtSource s;
     if (desc_host) jfiftrans_source(*desc_host, s); else jfiftrans_source(*frame_host, s);
     if (density3_host) { s.units = density3_host[0] & 255; s.xdensity = density3_host[1]; s.ydensity = density3_host[2]; }
-    const int n = jfiftrans_prefix_host(s, progressive != 0, out_host, capacity);
+    JxGeom x;
+    const int rc = jx_geom(s.height, s.width, s.hs, s.vs, transform, trim, x);
+    if (rc != kJxOk) return rc == kJxLayout ? AEJ_ERR_UNSUPPORTED : AEJ_ERR_ARG;
+    const int n = jfiftrans_prefix_host(jfiftrans_transformed(s, x), progressive != 0, out_host, capacity);
     return n < 0 ? AEJ_ERR_CAPACITY : n;
+}
+
+extern "C" int aej_jfif_transcode_headers_host(const aej_jpegdec_desc *desc_host, const aej_jpegprog_frame *frame_host, const uint16_t *density3_host,
+                                               int progressive, uint8_t *out_host, int capacity)
+{
+    return jt_headers(desc_host, frame_host, density3_host, progressive, kJxNone, 0, out_host, capacity);
+}
+
+extern "C" int aej_jfif_transform_headers_host(const aej_jpegdec_desc *desc_host, const aej_jpegprog_frame *frame_host, const uint16_t *density3_host,
+                                               int progressive, int transform, int trim, uint8_t *out_host, int capacity)
+{
+    return jt_headers(desc_host, frame_host, density3_host, progressive, transform, trim, out_host, capacity);
+}
+
+extern "C" int aej_jfif_transform_geometry_host(int H, int W, int hs, int vs, int transform, int trim, int32_t *out4_host)
+{
+    JxGeom x;
+    const int rc = jx_geom(H, W, hs, vs, transform, trim != 0, x);
+    if ((trim != 0 && trim != 1) || rc == kJxBadArg) return AEJ_ERR_ARG;
+    if (rc == kJxLayout) return AEJ_ERR_UNSUPPORTED;
+    if (rc != kJxOk) return rc == kJxNotPerfect ? AEJ_JFIF_TRANSFORM_NOT_PERFECT : AEJ_JFIF_TRANSFORM_TRIMS_TO_ZERO;
+    if (out4_host) { out4_host[0] = x.oH; out4_host[1] = x.oW; out4_host[2] = x.ohs; out4_host[3] = x.ovs; }
+    return 0;
+}
+
+extern "C" int64_t aej_jfif_transform_coefs_host(int H, int W, int hs, int vs, int transform, int trim, const int16_t *src_host, int64_t src_blocks,
+                                                 int16_t *dst_host, int64_t dst_blocks)
+{
+    JxGeom x;
+    const int rc = aej_jfif_transform_geometry_host(H, W, hs, vs, transform, trim, nullptr);
+    if (rc) return rc;
+    jx_geom(H, W, hs, vs, transform, trim, x);
+    if (!src_host && !dst_host) return x.n_out;              // a size query
+    if (!src_host || !dst_host || src_blocks != x.n_src) return AEJ_ERR_ARG;
+    if (dst_blocks < x.n_out) return AEJ_ERR_CAPACITY;
+    jfiftrans_coefs_host(x, src_host, dst_host);
+    return x.n_out;
+}
+
+static uint64_t jt_workspace_bytes(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs_host, int n_base, const aej_jpegprog_frame *frames_host,
+                                   const aej_jpegprog_scan *pscans_host, int n_prog, int progressive, const int32_t *xf, int trim)
+{
+    if (!ctx || (n_base > 0 && !descs_host) || (n_prog > 0 && (!frames_host || !pscans_host))) return 0;
+    JtCall c;
+    const std::string keep = ctx->err;
+    const int rc = jt_layout(ctx, fn, descs_host, n_base, frames_host, pscans_host, n_prog, nullptr, progressive, xf, trim, c);
+    ctx->err = keep;                                         // a size query leaves the context's last error alone
+    return rc ? 0 : jt_carve(nullptr, n_base, n_prog, c).bytes;
 }
 
 extern "C" uint64_t aej_jfif_transcode_workspace_bytes(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base,
                                                        const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *pscans_host, int n_prog,
                                                        int progressive)
 {
-    if (!ctx || (n_base > 0 && !descs_host) || (n_prog > 0 && (!frames_host || !pscans_host))) return 0;
-    JtCall c;
-    const std::string keep = ctx->err;
-    const int rc = jt_layout(ctx, __func__, descs_host, n_base, frames_host, pscans_host, n_prog, nullptr, progressive, c);
-    ctx->err = keep;                                         // a size query leaves the context's last error alone
-    return rc ? 0 : jt_carve(nullptr, n_base, n_prog, c).bytes;
+    return jt_workspace_bytes(ctx, __func__, descs_host, n_base, frames_host, pscans_host, n_prog, progressive, nullptr, 0);
 }
 
-extern "C" int aej_jfif_transcode_batch(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base, const uint8_t *scans, uint64_t scans_bytes,
-                                        const int64_t *scan_offsets_host, const aej_jpegprog_frame *frames_host,
-                                        const aej_jpegprog_scan *pscans_host, int n_prog, const uint8_t *data, uint64_t data_bytes,
-                                        const int64_t *data_offsets_host, const uint16_t *density_host, int progressive, uint8_t *out,
-                                        uint64_t out_capacity, int64_t *offsets, int64_t *lengths, uint64_t *total_host, int32_t *status,
-                                        int32_t *n_groups_host, void *workspace, uint64_t workspace_bytes)
+extern "C" uint64_t aej_jfif_transform_workspace_bytes(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base,
+                                                       const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *pscans_host, int n_prog,
+                                                       int progressive, const int32_t *transforms_host, int trim)
 {
-    AEJ_TRY(enter(ctx, __func__));
+    if (!transforms_host) return 0;
+    return jt_workspace_bytes(ctx, __func__, descs_host, n_base, frames_host, pscans_host, n_prog, progressive, transforms_host, trim);
+}
+
+static int jt_batch(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs_host, int n_base, const uint8_t *scans, uint64_t scans_bytes,
+                    const int64_t *scan_offsets_host, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *pscans_host, int n_prog,
+                    const uint8_t *data, uint64_t data_bytes, const int64_t *data_offsets_host, const uint16_t *density_host, int progressive,
+                    const int32_t *xf, int trim, uint8_t *out, uint64_t out_capacity, int64_t *offsets, int64_t *lengths, uint64_t *total_host,
+                    int32_t *status, int32_t *n_groups_host, void *workspace, uint64_t workspace_bytes)
+{
+    AEJ_TRY(enter(ctx, fn));
     if ((n_base > 0 && (!descs_host || !scans || !scan_offsets_host)) || (n_prog > 0 && (!frames_host || !pscans_host || !data || !data_offsets_host)) ||
         !offsets || !lengths || !total_host || !status || !workspace)
-        return null_buffer(ctx, __func__);
+        return null_buffer(ctx, fn);
     JtCall c;
-    AEJ_TRY(jt_layout(ctx, __func__, descs_host, n_base, frames_host, pscans_host, n_prog, density_host, progressive, c));
-    for (int i = 0; i < n_base; i++) AEJ_TRY(jpegdec_scan_offset(ctx, __func__, descs_host[i], i, scans_bytes, scan_offsets_host[i], c.files[i]));
+    AEJ_TRY(jt_layout(ctx, fn, descs_host, n_base, frames_host, pscans_host, n_prog, density_host, progressive, xf, trim, c));
+    for (int i = 0; i < n_base; i++) AEJ_TRY(jpegdec_scan_offset(ctx, fn, descs_host[i], i, scans_bytes, scan_offsets_host[i], c.files[i]));
     for (size_t t = 0; t < c.y.scans.size(); t++) {
         const long long so = data_offsets_host[c.y.src[t]];
         if (so < 0 || (uint64_t)so + (uint64_t)c.y.sfiles[t].scan_len > data_bytes)
-            return fail(ctx, AEJ_ERR_ARG, "%s: scan %d: bytes outside the data buffer", __func__, c.y.src[t]);
+            return fail(ctx, AEJ_ERR_ARG, "%s: scan %d: bytes outside the data buffer", fn, c.y.src[t]);
         c.y.sfiles[t].scan_off = so;
     }
     const JtWorkspace ws = jt_carve(workspace, n_base, n_prog, c);
@@ -489,7 +552,7 @@ extern "C" int aej_jfif_transcode_batch(aej_ctx *ctx, const aej_jpegdec_desc *de
     if (n_groups_host) *n_groups_host = (int32_t)c.plan.groups.size();
     std::vector<unsigned char> blob;
     if (n_base) {
-        AEJ_TRY(jpegdec_decode(ctx, __func__, descs_host, n_base, c.files, c.z, ws.wb, scans, status));
+        AEJ_TRY(jpegdec_decode(ctx, fn, descs_host, n_base, c.files, c.z, ws.wb, scans, status));
         AEJ_HIP_CHECK(launch_jpegdec_write(ctx->stream, n_base, c.z, ws.wb, ctx->jd_subseq_bits, status));
     } else {
         AEJ_TRY(bind_device(ctx));
@@ -504,6 +567,33 @@ extern "C" int aej_jfif_transcode_batch(aej_ctx *ctx, const aej_jpegdec_desc *de
     AEJ_HIP_CHECK(hipStreamSynchronize(ctx->stream));         // also keeps `blob` and the plan's tables alive until their uploads have run
     *total_host = (uint64_t)total;
     if (out && (uint64_t)total > out_capacity)
-        return fail(ctx, AEJ_ERR_CAPACITY, "%s: the files need %lld bytes, the output holds %llu", __func__, total, (unsigned long long)out_capacity);
+        return fail(ctx, AEJ_ERR_CAPACITY, "%s: the files need %lld bytes, the output holds %llu", fn, total, (unsigned long long)out_capacity);
     return 0;
+}
+
+extern "C" int aej_jfif_transcode_batch(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base, const uint8_t *scans, uint64_t scans_bytes,
+                                        const int64_t *scan_offsets_host, const aej_jpegprog_frame *frames_host,
+                                        const aej_jpegprog_scan *pscans_host, int n_prog, const uint8_t *data, uint64_t data_bytes,
+                                        const int64_t *data_offsets_host, const uint16_t *density_host, int progressive, uint8_t *out,
+                                        uint64_t out_capacity, int64_t *offsets, int64_t *lengths, uint64_t *total_host, int32_t *status,
+                                        int32_t *n_groups_host, void *workspace, uint64_t workspace_bytes)
+{
+    return jt_batch(ctx, __func__, descs_host, n_base, scans, scans_bytes, scan_offsets_host, frames_host, pscans_host, n_prog, data, data_bytes,
+                    data_offsets_host, density_host, progressive, nullptr, 0, out, out_capacity, offsets, lengths, total_host, status, n_groups_host,
+                    workspace, workspace_bytes);
+}
+
+extern "C" int aej_jfif_transform_batch(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base, const uint8_t *scans, uint64_t scans_bytes,
+                                        const int64_t *scan_offsets_host, const aej_jpegprog_frame *frames_host,
+                                        const aej_jpegprog_scan *pscans_host, int n_prog, const uint8_t *data, uint64_t data_bytes,
+                                        const int64_t *data_offsets_host, const uint16_t *density_host, int progressive,
+                                        const int32_t *transforms_host, int trim, uint8_t *out, uint64_t out_capacity, int64_t *offsets,
+                                        int64_t *lengths, uint64_t *total_host, int32_t *status, int32_t *n_groups_host, void *workspace,
+                                        uint64_t workspace_bytes)
+{
+    AEJ_TRY(enter(ctx, __func__));
+    if (!transforms_host) return null_buffer(ctx, __func__);
+    return jt_batch(ctx, __func__, descs_host, n_base, scans, scans_bytes, scan_offsets_host, frames_host, pscans_host, n_prog, data, data_bytes,
+                    data_offsets_host, density_host, progressive, transforms_host, trim, out, out_capacity, offsets, lengths, total_host, status,
+                    n_groups_host, workspace, workspace_bytes);
 }

@@ -3,7 +3,7 @@
 // colour, FDCT or second quantisation in between (aej_jfif_transcode_*, include/aej.h).  What jpegtran -optimize / -progressive do.
 //
 // The decoders leave a file's blocks in MCU order with the dummy edge blocks, natural order inside a block; the coders read the same
-// MCU order, zigzag order inside a block.  Files are grouped by (H, W, hs, vs); a group runs the existing entropy stages once, every
+// MCU order, zigzag order inside a block.  Files are grouped by the (H, W, hs, vs) of their output; a group runs the existing entropy stages once, every
 // file of it one "quality" of a one-image batch, so that JfifParams::hdr -- per quality in the coders -- carries each file's own
 // markers (SOI, JFIF APP0 with the source's density, the source's quantisation tables and frame header).  Stages:
 //   k_jt_bridge     one wave per block: lane z reads natural index k_jt_zz[z] of the source block and writes position z of the coder's
@@ -12,6 +12,14 @@
 //                   of a file whose decode had failed before this launch; whether the GOOD blocks of a file that fails in this launch
 //                   arrive as data or as zeros depends on when their wave reads the status word, and does not matter: the file's
 //                   length becomes 0, and every block the coders are given is in range, so their per-block stream bound holds
+//   k_jt_transform  in the place of k_jt_bridge when a file of the call has a lossless transform (aej_jfif_transform_*; flips, rotations,
+//                   transposition: jfif_transform_core.h).  Still one wave per OUTPUT block, lane z writing position z of the coder's block:
+//                   the wave is block b of its file in the OUTPUT group's MCU order, reads block jx_source_block(b) of the SOURCE's MCU
+//                   order (another sampling after a transposition, fewer MCUs after a trim) and there natural index
+//                   jx_source_index(k_jt_zz[z]), negated where the mirror says so -- one 128-byte block in, one out, as the bridge.  A
+//                   dummy output block is written as libjpeg writes it: lane 0 takes the DC of the real block before it in the MCU, the
+//                   AC lanes read nothing and write 0.  Range ballot and status protocol are the bridge's (the limits are symmetric but
+//                   for the DC, which no transform negates).  A file whose transform is "none" goes through it unchanged, dummies too.
 //   (per group)     launch_jfif_entropy / launch_jfifprog_entropy: histogram .. file lengths, unchanged
 //   k_jt_sos_ids    progressive groups with component ids other than 1, 2, 3 only: the ids in the SOS markers k_jfp_tables wrote
 //   k_jt_place      one thread: the files' offsets in the packed output, group after group
@@ -19,7 +27,11 @@
 //   k_jt_finish     one thread per file: length and offset in the caller's order; a failed file's length is 0
 // Bounds: every index derives from the host layout (JtPlan): a wave's block lies inside [0, n_blocks) of the file jt_find_file returns,
 // src and dst are that file's own ranges of the decoder's and the group's coefficient buffers, the status index is below the call's
-// file count, and an SOS marker is patched only inside the kJfpPiece bytes of its own piece.
+// file count, and an SOS marker is patched only inside the kJfpPiece bytes of its own piece.  With a transform the file's JxGeom, made
+// by jx_geom on the host, is all the mapping reads: jfiftrans_plan has checked that its n_out is the group's block count (the size of
+// dst, and the file's n_blocks) and its n_src the count the decoder holds (the size of src); jx_source_block maps [0, n_out) into
+// [0, n_src) -- a mirrored axis is a whole number of MCUs, a transposed block of an h x v grid lies in the v x h grid, the walk back from
+// a dummy block stays inside its MCU -- and the kernel still drops a wave whose source block would lie outside.
 #include "aej_common.h"
 #include "aej_ctx.h"
 #include "aej_launch.h"
@@ -52,6 +64,34 @@ __global__ __launch_bounds__(kJtThreads) void k_jt_bridge(const JtFile *__restri
     const long long b = t - F.src_base;
     if (b >= F.n_blocks) return;                             // never: the files' ranges tile [0, n_blocks)
     const int v = F.src[b * 64 + k_jt_zz[z]];
+    const bool bad = z == 0 ? (v < -1024 || v > 1023) : (v < -1023 || v > 1023);
+    const bool any_bad = __ballot(bad) != 0ull;
+    if (any_bad && z == 0) atomicCAS(status + F.status_index, 0, AEJ_JPEGDEC_COEF_RANGE);
+    const bool failed = any_bad || status[F.status_index] != 0;
+    F.dst[b * 64 + z] = failed ? (short)0 : (short)v;
+}
+
+// The bridge with a lossless transform (header comment): geom[i] belongs to files[i].
+__global__ __launch_bounds__(kJtThreads) void k_jt_transform(const JtFile *__restrict__ files, const JxGeom *__restrict__ geom, int n, long long n_blocks,
+                                                             int *__restrict__ status)
+{
+    const long long t = (long long)blockIdx.x * (kJtThreads / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // scalar: the maps are per wave
+    if (t >= n_blocks) return;
+    const int z = threadIdx.x & 63;
+    const int fi = jt_find_file(files, n, t);
+    const JtFile F = files[fi];
+    const JxGeom G = geom[fi];
+    const long long b = t - F.src_base;
+    if (b >= F.n_blocks || b >= G.n_out) return;             // never: the files' ranges tile [0, n_blocks), and n_blocks is n_out
+    int sb = (int)b, si = k_jt_zz[z];
+    bool dummy = false, negate = false;
+    if (G.xf != kJxNone) {
+        sb = jx_source_block(G, (int)b, &dummy);
+        si = jx_source_index(G, si, &negate);
+    }
+    if (sb < 0 || sb >= G.n_src) return;                     // never (header comment)
+    int v = dummy && z != 0 ? 0 : F.src[(long long)sb * 64 + si];
+    if (negate) v = -v;
     const bool bad = z == 0 ? (v < -1024 || v > 1023) : (v < -1023 || v > 1023);
     const bool any_bad = __ballot(bad) != 0ull;
     if (any_bad && z == 0) atomicCAS(status + F.status_index, 0, AEJ_JPEGDEC_COEF_RANGE);
@@ -142,44 +182,72 @@ int jfiftrans_prefix_host(const JtSource &s, bool prog, unsigned char *o, int ca
     return n;
 }
 
-bool jfiftrans_plan(const std::vector<JtSource> &src, const std::vector<long long> &n_blocks, bool prog, JtPlan &plan)
+JtSource jfiftrans_transformed(const JtSource &s, const JxGeom &g)
 {
+    JtSource o = s;
+    o.width = g.oW; o.height = g.oH; o.hs = g.ohs; o.vs = g.ovs;
+    for (int c = 0; c < 3 && g.t; c++)
+        for (int i = 0; i < 64; i++) o.qt[c][i] = s.qt[c][(i & 7) * 8 + (i >> 3)];
+    return o;
+}
+
+void jfiftrans_coefs_host(const JxGeom &g, const short *src, short *dst)
+{
+    for (int b = 0; b < g.n_out; b++) {
+        bool dummy = false;
+        const int sb = g.xf != kJxNone ? jx_source_block(g, b, &dummy) : b;
+        for (int z = 0; z < 64; z++) {
+            bool negate = false;
+            const int si = g.xf != kJxNone ? jx_source_index(g, kJtZzHost[z], &negate) : kJtZzHost[z];
+            const int v = dummy && z != 0 ? 0 : src[(long long)sb * 64 + si];
+            dst[(long long)b * 64 + z] = (short)(negate ? -v : v);
+        }
+    }
+}
+
+int jfiftrans_plan(const std::vector<JtSource> &src, const std::vector<long long> &n_blocks, bool prog, const int *xf, int trim, JtPlan &plan,
+                   int *why)
+{
+    auto refuse = [&](int i, int w) { if (why) *why = w; return i; };
     const int n = (int)src.size();
-    if (n < 1 || n > 65535 || n_blocks.size() != src.size()) return false;
+    if (n < 1 || n > 65535 || n_blocks.size() != src.size()) return refuse(0, kJxBadArg);
     plan = JtPlan{};
     plan.prog = prog;
     plan.files.assign(n, JtFile{});
+    plan.geom.assign(n, JxGeom{});
     for (int i = 0; i < n; i++) {
         const JtSource &s = src[i];
-        const int ss = s.hs == 1 && s.vs == 1 ? 0 : s.hs == 2 && s.vs == 1 ? 1 : s.hs == 2 && s.vs == 2 ? 2 : -1;
-        if (ss < 0) return false;
+        JxGeom &x = plan.geom[i];
+        const int rc = jx_geom(s.height, s.width, s.hs, s.vs, xf ? xf[i] : kJxNone, trim, x);
+        if (rc != kJxOk) return refuse(i, rc);
+        plan.transform |= x.xf != kJxNone;
         JtGroup *grp = nullptr;
         for (JtGroup &c : plan.groups)
-            if (c.g.H == s.height && c.g.W == s.width && c.g.hs == s.hs && c.g.vs == s.vs) grp = &c;
+            if (c.g.H == x.oH && c.g.W == x.oW && c.g.hs == x.ohs && c.g.vs == x.ovs) grp = &c;
         if (!grp) {
             plan.groups.emplace_back();
             grp = &plan.groups.back();
             grp->foreign_ids = false;
-            if (!jfif_geom(1, s.height, s.width, 1, grp->g, ss, 1)) return false;
+            if (!jfif_geom(1, x.oH, x.oW, 1, grp->g, x.ohs == 1 ? 0 : x.ovs == 1 ? 1 : 2, 1)) return refuse(i, kJxBadArg);
         }
-        if (n_blocks[i] != grp->g.nblk) return false;
+        if (n_blocks[i] != x.n_src || grp->g.nblk != x.n_out) return refuse(i, kJxBadArg);
         grp->files.push_back(i);
         grp->foreign_ids |= s.comp_id[0] != 1 || s.comp_id[1] != 2 || s.comp_id[2] != 3;
         plan.files[i].src_base = plan.n_blocks;
-        plan.files[i].n_blocks = n_blocks[i];
-        plan.n_blocks += n_blocks[i];
+        plan.files[i].n_blocks = x.n_out;
+        plan.n_blocks += x.n_out;
     }
     long long first = 0;
     for (JtGroup &c : plan.groups) {
         const int ng = (int)c.files.size(), ss = c.g.hs == 1 ? 0 : c.g.vs == 1 ? 1 : 2;
-        if (!jfif_geom(1, c.g.H, c.g.W, ng, c.g, ss, 1) || (prog && !jfifprog_geom(c.g, c.p))) return false;
+        if (!jfif_geom(1, c.g.H, c.g.W, ng, c.g, ss, 1) || (prog && !jfifprog_geom(c.g, c.p))) return refuse(c.files[0], kJxBadArg);
         c.first = first;
         c.par.assign(ng, JfifParams{});
         for (int k = 0; k < ng; k++) {
-            const JtSource &s = src[c.files[k]];
+            const JtSource s = jfiftrans_transformed(src[c.files[k]], plan.geom[c.files[k]]);
             JfifParams &p = c.par[k];
             const int len = jfiftrans_prefix_host(s, prog, p.hdr, kJfifHdrMax - 14);
-            if (len < 0) return false;
+            if (len < 0) return refuse(c.files[k], kJxBadArg);
             p.dht_off = p.hdr_len = len;
             if (!prog) {                                     // k_jfif_tables takes the SOS from the end of the markers
                 const unsigned char sos[14] = { 0xFF, 0xDA, 0, 12, 3, s.comp_id[0], 0x00, s.comp_id[1], 0x11, s.comp_id[2], 0x11, 0, 63, 0 };
@@ -190,7 +258,7 @@ bool jfiftrans_plan(const std::vector<JtSource> &src, const std::vector<long lon
         }
         first += ng;
     }
-    return true;
+    return -1;
 }
 
 unsigned long long jfiftrans_carve(void *base, JtPlan &plan)
@@ -198,6 +266,7 @@ unsigned long long jfiftrans_carve(void *base, JtPlan &plan)
     Carver c(base);
     const long long n = (long long)plan.files.size();
     plan.d_files = c.take<JtFile>(n);
+    if (plan.transform) plan.d_geom = c.take<JxGeom>(n);
     plan.glen = c.take<long long>(n);
     plan.goff = c.take<long long>(n);
     plan.total = c.take<long long>(1);
@@ -220,8 +289,13 @@ hipError_t launch_jfiftrans(hipStream_t st, JtPlan &plan, int *status, unsigned 
     const int n = (int)plan.files.size();
     hipError_t e = hipMemcpyAsync(plan.d_files, plan.files.data(), sizeof(JtFile) * n, hipMemcpyHostToDevice, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_jt_bridge, dim3((unsigned)((plan.n_blocks + kJtThreads / 64 - 1) / (kJtThreads / 64))), dim3(kJtThreads), 0, st, plan.d_files, n,
-                       plan.n_blocks, status);
+    const dim3 grid((unsigned)((plan.n_blocks + kJtThreads / 64 - 1) / (kJtThreads / 64)));
+    if (plan.transform) {
+        if ((e = hipMemcpyAsync(plan.d_geom, plan.geom.data(), sizeof(JxGeom) * n, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_jt_transform, grid, dim3(kJtThreads), 0, st, plan.d_files, plan.d_geom, n, plan.n_blocks, status);
+    } else {
+        hipLaunchKernelGGL(k_jt_bridge, grid, dim3(kJtThreads), 0, st, plan.d_files, n, plan.n_blocks, status);
+    }
     for (JtGroup &c : plan.groups) {
         if ((e = hipMemcpyAsync(c.w.par, c.par.data(), sizeof(JfifParams) * c.par.size(), hipMemcpyHostToDevice, st)) != hipSuccess) return e;
         long long *len = plan.glen + c.first, *off = plan.goff + c.first;

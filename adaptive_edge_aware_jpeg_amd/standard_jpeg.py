@@ -16,6 +16,8 @@ tables or as the ten-scan progressive file (csrc/jfiftrans.hip, ``aej_jfif_trans
 ``jpegtran -progressive`` do.  The output keeps the source's quantisation tables, component ids, sampling and JFIF density, drops its
 restart markers, and with ``keep_metadata=True`` carries its APP1..APP13, APP15 and COM segments over (spliced on the host).  A
 Pillow file transcoded this way equals Pillow's own ``optimize=True`` / ``progressive=True`` file of the same pixels byte for byte.
+``standard_jpeg_transform_many`` is the same call with a lossless flip, rotation or transposition of every file on the way, by name or
+from the EXIF Orientation tag (``jpegtran -flip / -rotate / -transpose``, ``exiftran -a``; ``aej_jfif_transform_*``).
 
 The files are byte-identical to Pillow's with libjpeg-turbo (JFIF 1.01, Annex K quantisation and Huffman tables, islow DCT, no restart
 markers) and the decoded pixels equal ``np.asarray(Image.open(file).convert("RGB"))``.  Colour, down-sampling and DCT run once per image
@@ -407,11 +409,15 @@ def _jfif_density(mv, segs):
     return 0, 1, 1
 
 
+def _is_metadata(m) -> bool:
+    return 0xE1 <= m <= 0xED or m == 0xEF or m == 0xFE
+
+
 def metadata_segments(data, index: int = 0) -> bytes:
     """What keep_metadata=True carries over: the file's APP1 .. APP13, APP15 and COM segments, verbatim and in order.  APP0 (JFIF,
     JFXX: the output has its own) and APP14 (Adobe: the output is a JFIF file) never are."""
     mv = memoryview(data).cast("B")
-    return b"".join(bytes(mv[a:b]) for m, a, b in marker_segments(mv, index) if 0xE1 <= m <= 0xED or m == 0xEF or m == 0xFE)
+    return b"".join(bytes(mv[a:b]) for m, a, b in marker_segments(mv, index) if _is_metadata(m))
 
 
 def _parse_any(f, i):
@@ -463,6 +469,129 @@ def transcode_groups() -> int:
     return _last_transcode_groups
 
 
+TRANSFORMS = ("none", "flip_h", "flip_v", "transpose", "transverse", "rot90", "rot180", "rot270")      # codes 0..7: jpegtran's JXFORM order
+_EXIF_TRANSFORM = (None, "none", "flip_h", "rot180", "flip_v", "transpose", "rot90", "transverse", "rot270")      # by Orientation value
+_TRANSPOSING = ("transpose", "transverse", "rot90", "rot270")
+
+
+def _exif_orientation_at(mv, segs):
+    """(value, offset of its two bytes in the file, byte order) of the Orientation tag (0x0112, one SHORT) in IFD0 of the first EXIF
+    APP1 segment; None when there is no such segment or tag or the block is malformed"""
+    for m, a, b in segs:
+        if m != 0xE1 or b - a < 10 or bytes(mv[a + 4:a + 10]) != b"Exif\0\0":
+            continue
+        t = a + 10                                  # the TIFF header; offsets count from here and must stay inside the segment
+        if b - t < 8:
+            return None
+        order = {b"II*\0": "little", b"MM\0*": "big"}.get(bytes(mv[t:t + 4]))
+        if order is None:
+            return None
+        num = lambda o, k: int.from_bytes(bytes(mv[o:o + k]), order)  # noqa: E731
+        ifd = t + num(t + 4, 4)
+        if ifd + 2 > b:
+            return None
+        for e in range(ifd + 2, ifd + 2 + 12 * num(ifd, 2), 12):
+            if e + 12 > b:
+                return None
+            if num(e, 2) == 0x0112:
+                return (num(e + 8, 2), e + 8, order) if num(e + 2, 2) == 3 and num(e + 4, 4) == 1 else None
+        return None
+    return None
+
+
+def exif_orientation(data, index: int = 0) -> int:
+    """The EXIF Orientation tag of one file (host only): 1..8 as ``Image.open(f).getexif().get(0x0112, 1)`` gives it; 1 when the file
+    has no EXIF APP1 segment, no such tag in IFD0, a malformed EXIF block or a value outside 1..8."""
+    mv = memoryview(data).cast("B")
+    try:
+        at = _exif_orientation_at(mv, marker_segments(mv, index))
+    except ValueError:
+        return 1
+    return at[0] if at and 1 <= at[0] <= 8 else 1
+
+
+def _transform_geometry(i, height, width, hs, vs, name, trim):
+    """-> the output's (height, width, hs, vs); the refusals of a transform, naming the file, before any device work"""
+    from ._lib import load_library
+    if name in _TRANSPOSING and hs != vs:
+        raise NotImplementedError(f"file {i}: {name} of a 4:2:2 file would be a 4:4:0 file, which neither the coders nor the decoders here have")
+    out = (ctypes.c_int32 * 4)()
+    rc = load_library().aej_jfif_transform_geometry_host(height, width, hs, vs, TRANSFORMS.index(name), int(trim), ctypes.addressof(out))
+    if rc == 1:
+        raise ValueError(f"file {i}: {name} of a {width} x {height} file mirrors an axis that is not a whole number of its {8 * hs} x {8 * vs} MCUs; "
+                         "trim=True drops the partial MCUs at that edge first")
+    if rc == 2:
+        raise ValueError(f"file {i}: {name} with trim=True leaves nothing of a {width} x {height} file with {8 * hs} x {8 * vs} MCUs")
+    if rc:
+        raise ValueError(f"file {i}: the library refuses the transform ({rc})")
+    return tuple(out)
+
+
+def _check_transform(name, i):
+    if not isinstance(name, str) or name not in TRANSFORMS:
+        raise ValueError(f"file {i}: unknown transform {name!r}: one of {', '.join(TRANSFORMS)} required" +
+                         (" ('exif' is a setting of the whole call)" if name == "exif" else ""))
+    return name
+
+
+def transform_prefix(data, transform, progressive: bool = False, trim: bool = False, index: int = 0) -> bytes:
+    """The bytes SOI .. end of SOF0 / SOF2 that standard_jpeg_transform_many writes for one file under one transform name
+    (aej_jfif_transform_headers_host, host only): transcode_prefix with the output's size and sampling and, for a transposing
+    transform, every quantisation table transposed."""
+    from ._lib import load_library
+    progressive, trim = _check_progressive(progressive), _check_bool("trim", trim)
+    is_prog, d = _parse_any(data, index)
+    frame = d[0] if is_prog else d
+    _transform_geometry(index, frame.height, frame.width, frame.hs, frame.vs, _check_transform(transform, index), trim)
+    mv = memoryview(data).cast("B")
+    dens = (ctypes.c_uint16 * 3)(*_jfif_density(mv, marker_segments(mv, index)))
+    buf = (ctypes.c_uint8 * 512)()
+    n = load_library().aej_jfif_transform_headers_host(None if is_prog else ctypes.addressof(frame), ctypes.addressof(frame) if is_prog else None,
+                                                       ctypes.addressof(dens), int(progressive), TRANSFORMS.index(transform), int(trim),
+                                                       ctypes.addressof(buf), 512)
+    if n < 0:
+        raise ValueError(f"file {index}: the library refuses its descriptor ({n})")
+    return bytes(buf[:n])
+
+
+def standard_jpeg_transform_many(files, transform, progressive: bool = False, trim: bool = False, device: int = 0,
+                                 keep_metadata: bool = False) -> List[bytes]:
+    """Lossless flip, rotation or transposition on the device: standard_jpeg_transcode_many with the files' quantised coefficients
+    rearranged between the Huffman decode and the entropy coders (one kernel in the place of the transcoder's bridge), so that no
+    sample is quantised a second time -- ``jpegtran -flip / -rotate / -transpose / -transverse``.  files, progressive, device and
+    keep_metadata are the transcoder's, and so is what is accepted and refused.
+
+    transform: one name for every file, a sequence of one name per file, or "exif".  With W, H the source size, rotations clockwise:
+    "none" out = in; "flip_h" out[y, x] = in[y, W-1-x]; "flip_v" in[H-1-y, x]; "transpose" in[x, y]; "transverse" in[H-1-x, W-1-y];
+    "rot90" np.rot90(in, -1); "rot180" in[::-1, ::-1]; "rot270" np.rot90(in, 1).  "exif" takes each file's transform from the
+    Orientation tag of its EXIF APP1 segment (exif_orientation; 1..8: none, flip_h, rot180, flip_v, transpose, rot90, transverse,
+    rot270 -- PIL.ImageOps.exif_transpose), "none" for a file without a usable tag; with keep_metadata=True it then sets the tag's
+    two bytes to 1 in the carried-over segment and changes nothing else in it.  EXIF thumbnails and pixel-dimension tags
+    (PixelXDimension, ImageWidth, ...) are NOT rewritten, in no mode; explicit names leave the metadata untouched, as jpegtran does.
+
+    A transposing transform swaps width, height and the luma sampling factors and writes the quantisation tables transposed.  A
+    mirrored axis has to be a whole number of the source's MCUs (8 hs x 8 vs): flip_h and rot270 need it of the width, flip_v and
+    rot90 of the height, rot180 and transverse of both.  Otherwise trim=False raises ValueError (jpegtran -perfect) and trim=True
+    drops the partial MCU column / row at the right / bottom edge first (jpegtran -trim); a dimension that trims to 0 raises
+    ValueError.  The padding samples of real edge blocks travel with their block; the dummy blocks of edge MCUs are written as
+    libjpeg writes them.  "none" is exactly the transcode.  Not built: a transposing transform of a 4:2:2 file (it would be 4:4:0;
+    NotImplementedError), crop, grey files.  Every refusal names the file and comes before any device work; there is no CPU fallback."""
+    progressive, keep_metadata = _check_bool("progressive", progressive), _check_bool("keep_metadata", keep_metadata)
+    trim = _check_bool("trim", trim)
+    files = list(files)
+    if not files:
+        raise ValueError("standard_jpeg_transform_many needs at least one file")
+    n = len(files)
+    if isinstance(transform, str):
+        names = None if transform == "exif" else [_check_transform(transform, 0)] * n
+    else:
+        names = list(transform)
+        if len(names) != n:
+            raise ValueError(f"file {min(len(names), n)}: {len(names)} transforms for {n} files")
+        names = [_check_transform(t, i) for i, t in enumerate(names)]
+    return _transcode_many(files, progressive, device, keep_metadata, names, trim, names is None)
+
+
 def standard_jpeg_transcode_many(files, progressive: bool = False, device: int = 0, keep_metadata: bool = False) -> List[bytes]:
     """Lossless transcode on the device: -> every file entropy-coded again, in input order.  files: a non-empty sequence of bytes-like
     JPEG contents, baseline / extended-sequential (SOF0 / SOF1) and complete progressive (SOF2) files of any sizes and of the 4:4:4,
@@ -476,13 +605,19 @@ def standard_jpeg_transcode_many(files, progressive: bool = False, device: int =
     quantisation tables (NotImplementedError), malformed headers (ValueError).  A file whose scan is corrupt, or that decodes to a
     coefficient an 8-bit JPEG cannot hold, raises ValueError naming its index and the reason; nothing is returned then.  There is no
     CPU fallback."""
-    global _last_transcode_groups
-    from ._lib import JPEGDEC_STATUS, JpegDecDesc, JpegProgFrame, JpegProgScan
     progressive, keep_metadata = _check_bool("progressive", progressive), _check_bool("keep_metadata", keep_metadata)
     files = list(files)
     if not files:
         raise ValueError("standard_jpeg_transcode_many needs at least one file")
+    return _transcode_many(files, progressive, device, keep_metadata, None, False, False)
+
+
+def _transcode_many(files, progressive, device, keep_metadata, names, trim, exif):
+    """the transcode (names None and not exif) and the transform: names[i] is file i's transform, exif takes it from the file"""
+    global _last_transcode_groups
+    from ._lib import JPEGDEC_STATUS, JpegDecDesc, JpegProgFrame, JpegProgScan
     n = len(files)
+    names = ["none"] * n if names is None else names
     views, parsed, base_idx, prog_idx, density, meta = [], [None] * n, [], [], [None] * n, [b""] * n
     for i, f in enumerate(files):
         is_prog, parsed[i] = _parse_any(f, i)
@@ -491,8 +626,17 @@ def standard_jpeg_transcode_many(files, progressive: bool = False, device: int =
         views.append(mv)
         segs = marker_segments(mv, i)
         density[i] = _jfif_density(mv, segs)
+        at = _exif_orientation_at(mv, segs) if exif else None
+        if at and 1 <= at[0] <= 8:
+            names[i] = _EXIF_TRANSFORM[at[0]]
+        if names[i] != "none":
+            frame = parsed[i][0] if is_prog else parsed[i]
+            _transform_geometry(i, frame.height, frame.width, frame.hs, frame.vs, names[i], trim)
         if keep_metadata:
             meta[i] = metadata_segments(mv, i)
+            if at and 1 < at[0] <= 8:                # the tag's value becomes 1, in the TIFF block's byte order; nothing else changes
+                k = sum(min(b, at[1]) - a for m, a, b in segs if a < at[1] and _is_metadata(m))      # its place among the carried bytes
+                meta[i] = meta[i][:k] + (1).to_bytes(2, at[2]) + meta[i][k + 2:]
     order = base_idx + prog_idx                     # the call's file order: baseline sources first
     nb, npg = len(base_idx), len(prog_idx)
     ctx = get_context(device)
@@ -506,8 +650,14 @@ def standard_jpeg_transcode_many(files, progressive: bool = False, device: int =
                         [(i, s.data_offset, s.data_length) for i, s in flat])
     data, scan_off, data_off = scans, np.ascontiguousarray(off[:max(nb, 1)]), np.ascontiguousarray(off[nb:nb + max(len(flat), 1)])
     dens = np.ascontiguousarray(np.array([density[i] for i in order], np.uint16))
-    nws = int(lib.aej_jfif_transcode_workspace_bytes(ctx.handle, ctypes.addressof(descs), nb, ctypes.addressof(frames), ctypes.addressof(pscans),
-                                                     npg, int(progressive)))
+    codes = np.ascontiguousarray(np.array([TRANSFORMS.index(names[i]) for i in order], np.int32))
+    plain = not codes.any()                         # every file "none": the transcoder's own entries
+    if plain:
+        nws = int(lib.aej_jfif_transcode_workspace_bytes(ctx.handle, ctypes.addressof(descs), nb, ctypes.addressof(frames), ctypes.addressof(pscans),
+                                                         npg, int(progressive)))
+    else:
+        nws = int(lib.aej_jfif_transform_workspace_bytes(ctx.handle, ctypes.addressof(descs), nb, ctypes.addressof(frames), ctypes.addressof(pscans),
+                                                         npg, int(progressive), codes.ctypes.data, int(trim)))
     if nws == 0:
         raise ValueError("descriptors the library refuses")
     ws = ctx.workspace(nws)
@@ -515,11 +665,14 @@ def standard_jpeg_transcode_many(files, progressive: bool = False, device: int =
     total, groups = ctypes.c_uint64(), ctypes.c_int32()
     cap = sum(len(v) for v in views) * 5 // 4 + (PROGRESSIVE_HEADER_CAPACITY if progressive else HEADER_CAPACITY) * n
     out = ctx.empty((cap,), t.uint8)
-    call = lambda o, c: lib.aej_jfif_transcode_batch(  # noqa: E731
-        ctx.handle, ctypes.addressof(descs), nb, scans.data_ptr(), ctypes.c_uint64(scans.numel()), scan_off.ctypes.data, ctypes.addressof(frames),
-        ctypes.addressof(pscans), npg, data.data_ptr(), ctypes.c_uint64(data.numel()), data_off.ctypes.data, dens.ctypes.data, int(progressive),
-        o.data_ptr(), ctypes.c_uint64(c), offsets.data_ptr(), lengths.data_ptr(), ctypes.addressof(total), status.data_ptr(),
-        ctypes.addressof(groups), ws.data_ptr(), ctypes.c_uint64(nws))
+    head = (ctx.handle, ctypes.addressof(descs), nb, scans.data_ptr(), ctypes.c_uint64(scans.numel()), scan_off.ctypes.data, ctypes.addressof(frames),
+            ctypes.addressof(pscans), npg, data.data_ptr(), ctypes.c_uint64(data.numel()), data_off.ctypes.data, dens.ctypes.data, int(progressive))
+    tail = (offsets.data_ptr(), lengths.data_ptr(), ctypes.addressof(total), status.data_ptr(), ctypes.addressof(groups), ws.data_ptr(),
+            ctypes.c_uint64(nws))
+    if plain:
+        call = lambda o, c: lib.aej_jfif_transcode_batch(*head, o.data_ptr(), ctypes.c_uint64(c), *tail)  # noqa: E731
+    else:
+        call = lambda o, c: lib.aej_jfif_transform_batch(*head, codes.ctypes.data, int(trim), o.data_ptr(), ctypes.c_uint64(c), *tail)  # noqa: E731
     rc = call(out, cap)
     if rc == -4 and total.value > cap:             # AEJ_ERR_CAPACITY: run again with the exact size
         cap = int(total.value)

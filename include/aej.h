@@ -560,6 +560,51 @@ AEJ_API int aej_jfif_transcode_batch(aej_ctx *ctx, const aej_jpegdec_desc *descs
                                      uint64_t out_capacity, int64_t *offsets, int64_t *lengths, uint64_t *total_host, int32_t *status,
                                      int32_t *n_groups_host, void *workspace, uint64_t workspace_bytes);
 
+/* ---- lossless flip, rotation and transposition (standard_jpeg_transform_many) -------------------------------------------------------
+ * What jpegtran -flip / -rotate / -transpose / -transverse do with -perfect or -trim, on the device: the transcode above with one
+ * transform per file, applied to the quantised coefficients between the decoders' and the coders' entropy stages by the one kernel that
+ * takes the bridge's place (csrc/jfiftrans.hip, k_jt_transform; the mapping is csrc/jfif_transform_core.h).  The codes are jpegtran's
+ * JXFORM order; with W, H the source size and rotations clockwise:
+ *   0 none  1 flip_h  out[y][x] = in[y][W-1-x]   2 flip_v  in[H-1-y][x]   3 transpose  in[x][y]   4 transverse  in[H-1-x][W-1-y]
+ *   5 rot90   6 rot180   7 rot270   (rot90 = transpose then flip_h, rot270 = flip_h then transpose, transverse = transpose then rot180)
+ * On a block's coefficients c(v, u): flip_h multiplies by (-1)^u and reverses every component's block columns, flip_v by (-1)^v and
+ * reverses the block rows, transpose reads c(u, v) of block (bx, by), swaps width and height and the luma sampling factors and writes
+ * every quantisation table transposed.  A mirrored axis must be a whole number of the source's MCUs (flip_h and rot270: the width;
+ * flip_v and rot90: the height; rot180 and transverse: both): with trim = 0 a file that is not is refused, with trim = 1 the partial
+ * MCU column / row at its right / bottom edge is dropped first.  The dummy blocks of the output's edge MCUs are written as libjpeg
+ * writes them (AC zero, DC of the block before in the MCU); a file with the code 0 is transcoded exactly as above, its dummy blocks
+ * carried.  A transposing code on a 4:2:2 source would give a 4:4:0 file: AEJ_ERR_UNSUPPORTED.  Files are grouped by the (height,
+ * width, sampling) of their OUTPUT.
+ *
+ * aej_jfif_transform_geometry_host: HOST only.  out4_host (may be NULL) gets the output's height, width, hs, vs.  -> 0, AEJ_ERR_ARG,
+ *   AEJ_ERR_UNSUPPORTED (4:4:0), AEJ_JFIF_TRANSFORM_NOT_PERFECT (trim = 0 and a mirrored axis with a partial MCU) or
+ *   AEJ_JFIF_TRANSFORM_TRIMS_TO_ZERO (trim = 1 and nothing left of it).
+ * aej_jfif_transform_coefs_host: HOST only, the code the kernel runs, on one file's coefficients.  src_host: int16 [src_blocks][64], natural
+ *   order inside a block, the blocks in the SOURCE's MCU order (MCUs in raster order; in each the hs x vs luma blocks in raster order,
+ *   then Cb, Cr), src_blocks = (hs vs + 2) x its MCUs.  dst_host: int16 [>= the result][64], zigzag order inside a block, the OUTPUT's MCU
+ *   order.  -> the output's blocks (also with both pointers NULL: a size query), or the geometry entry's refusals, AEJ_ERR_ARG for a
+ *   wrong src_blocks, AEJ_ERR_CAPACITY for dst_blocks too small.  No range check.
+ * aej_jfif_transform_headers_host, _workspace_bytes, _batch: the aej_jfif_transcode_* entries with, before their output arguments,
+ *   transforms_host [n_base + n_prog] int32 in the call's file order (headers: the one code) and trim (0 or 1).  The headers carry the
+ *   output's size and sampling and the transposed tables; a refused geometry is AEJ_ERR_ARG (the message names the file), 4:4:0
+ *   AEJ_ERR_UNSUPPORTED, and the workspace size of a refused call is 0. */
+enum { AEJ_JFIF_TRANSFORM_NOT_PERFECT = 1, AEJ_JFIF_TRANSFORM_TRIMS_TO_ZERO = 2 };
+AEJ_API int aej_jfif_transform_geometry_host(int H, int W, int hs, int vs, int transform, int trim, int32_t *out4_host);
+AEJ_API int64_t aej_jfif_transform_coefs_host(int H, int W, int hs, int vs, int transform, int trim, const int16_t *src_host, int64_t src_blocks,
+                                              int16_t *dst_host, int64_t dst_blocks);
+AEJ_API int aej_jfif_transform_headers_host(const aej_jpegdec_desc *desc_host, const aej_jpegprog_frame *frame_host, const uint16_t *density3_host,
+                                            int progressive, int transform, int trim, uint8_t *out_host, int capacity);
+AEJ_API uint64_t aej_jfif_transform_workspace_bytes(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base,
+                                                    const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *pscans_host, int n_prog,
+                                                    int progressive, const int32_t *transforms_host, int trim);
+AEJ_API int aej_jfif_transform_batch(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base, const uint8_t *scans, uint64_t scans_bytes,
+                                     const int64_t *scan_offsets_host, const aej_jpegprog_frame *frames_host,
+                                     const aej_jpegprog_scan *pscans_host, int n_prog, const uint8_t *data, uint64_t data_bytes,
+                                     const int64_t *data_offsets_host, const uint16_t *density_host, int progressive,
+                                     const int32_t *transforms_host, int trim, uint8_t *out, uint64_t out_capacity, int64_t *offsets,
+                                     int64_t *lengths, uint64_t *total_host, int32_t *status, int32_t *n_groups_host, void *workspace,
+                                     uint64_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -88,6 +88,9 @@ def transcode_routes(a):
     if hasattr(A, "standard_jpeg_transcode_many"):
         routes["transcode_optimize"] = lambda: sum(len(f) for f in A.standard_jpeg_transcode_many(files, progressive=False))
         routes["transcode_progressive"] = lambda: sum(len(f) for f in A.standard_jpeg_transcode_many(files, progressive=True))
+    if hasattr(A, "standard_jpeg_transform_many"):               # the transcode with a lossless transform on the way, over the same files
+        routes["transform_rot90"] = lambda: sum(len(f) for f in A.standard_jpeg_transform_many(files, "rot90", progressive=False))
+        routes["transform_flip_h"] = lambda: sum(len(f) for f in A.standard_jpeg_transform_many(files, "flip_h", progressive=False))
     return routes, sum(len(f) for f in files)
 
 
@@ -115,7 +118,8 @@ def worker(a):
 def transcode(a):
     """--transcode: --batch natural 4K files (quality 75, --subsampling, plain baseline) through standard_jpeg_transcode_many to
     optimised baseline and to progressive files, beside the lossy route over pixels on the same files (standard_jpeg_decode_many, then
-    standard_jpeg_many(optimize=True / progressive=True)) and the plain standard_jpeg_batch / standard_jpeg_decode_many calls.  With
+    standard_jpeg_many(optimize=True / progressive=True)) and the plain standard_jpeg_batch / standard_jpeg_decode_many calls; the
+    routes transform_rot90 and transform_flip_h are standard_jpeg_transform_many over the same files (baseline output).  With
     --ab ROOT a second process imports the package of the checkout at ROOT (its library built there) and runs the routes it has; the
     two sides alternate route by route inside every round, so both see the same machine state.  One warm-up round, then the medians
     of --repeats rounds, with the bytes of the sources and of the outputs.  --routes a,b restricts the run (for a profiler)."""
@@ -135,7 +139,7 @@ def transcode(a):
             raise RuntimeError("the --ab worker ended")
 
         answer()
-        sides["parent"] = [k for k in routes if not k.startswith("transcode")]
+        sides["parent"] = [k for k in routes if not k.startswith(("transcode", "transform"))]
 
     def ask(name):
         child.stdin.write(name + "\n")
