@@ -289,7 +289,7 @@ int jfifprog_scan_device(hipStream_t st, const short *coefs_host, long long n, i
 
 }  // namespace aej
 
-// jpegdec.hip: baseline JPEG files decoded on the device (aej_jpegdec_*)
+// jpegdec.hip: baseline JPEG files decoded on the device (aej_jpegdec_*); jpegparse.hip: the marker walk of both decoders
 #include <string>
 #include <vector>
 #include "jpegdec_core.h"
@@ -301,9 +301,24 @@ struct JdBufs {
     int *cnt; long long *pre, *clean_len; JdSeg *segs; unsigned char *clean; JdSlots sl; short *coef; unsigned char *planes;
 };
 struct JdHuffSrc { bool defined = false; unsigned char bits[17] = {}; unsigned char vals[256] = {}; int count = 0; };      // one DHT table
-bool jd_build_huff(const JdHuffSrc &s, aej_jpegdec_huff &h);
-int jpegdec_parse(const unsigned char *data, unsigned long long n, aej_jpegdec_desc &d, std::string &msg);
-long long jpegdec_layout(const aej_jpegdec_desc *descs, int n, int S, std::vector<JdFile> &files, JdBufSizes &z);
+bool jd_build_huff(const JdHuffSrc &s, aej_jpegdec_huff &h);                                                              // jpegparse.hip
+int jpegdec_parse(const unsigned char *data, unsigned long long n, aej_jpegdec_desc &d, std::string &msg);             // jpegparse.hip
+// did one of the parsers write this frame?  D: aej_jpegdec_desc or aej_jpegprog_frame -- what the layouts below size buffers from
+template <class D>
+bool jpeg_frame_ok(const D &e)
+{
+    const bool color = e.ncomp == 3 && ((e.hs == 1 && e.vs == 1) || (e.hs == 2 && (e.vs == 1 || e.vs == 2)));
+    if (!(color || (e.ncomp == 1 && e.hs == 1 && e.vs == 1))) return false;
+    if (e.width < 1 || e.height < 1 || e.width > 65535 || e.height > 65535) return false;
+    if (e.mcux != (e.width + 8 * e.hs - 1) / (8 * e.hs) || e.mcuy != (e.height + 8 * e.vs - 1) / (8 * e.vs)) return false;
+    return e.blocks_per_mcu == (e.ncomp == 1 ? 1 : e.hs * e.vs + 2);
+}
+bool jpegdec_descs_ok(const aej_jpegdec_desc *descs, int n);      // n >= 1 descriptors aej_jpegdec_parse_host wrote
+// one un-stuffing stream of len stuffed bytes and n_segments restart segments, subsequences of S bits: F's stream fields, z's totals
+void jpeg_stream_layout(long long len, int n_segments, int S, JdFile &F, JdBufSizes &z);
+// one file's coefficient blocks, sample planes and pixels (d's frame fields): F's reconstruction fields, z's totals
+void jpeg_recon_layout(const aej_jpegdec_desc &d, JdFile &F, JdBufSizes &z);
+void jpegdec_layout(const aej_jpegdec_desc *descs, int n, int S, std::vector<JdFile> &files, JdBufSizes &z);
 unsigned long long jpegdec_carve(void *base, int n, const JdBufSizes &z, JdBufs &w);
 hipError_t launch_jpegdec_begin(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, const void *blob_host, unsigned long long blob_bytes,
                                 const unsigned char *scans, int S, int *status);
@@ -330,7 +345,13 @@ struct JpLayout {                      // host-computed layout of one aej_jpegpr
     int n_levels = 0;
 };
 struct JpBufs { void *blob; JdBufs s, f; JpScan *scans; JpItem *items; int *sstatus; };
-int jpegprog_parse(const unsigned char *data, unsigned long long n, aej_jpegprog_frame &f, std::vector<aej_jpegprog_scan> &scans, std::string &msg);
+inline void jp_scan_units(const aej_jpegprog_frame &f, int ncomp, int comp0, int &ux, int &uy)      // the units a progressive scan walks
+{
+    if (ncomp > 1 || f.ncomp == 1 || comp0 > 0) { ux = f.mcux; uy = f.mcuy; }      // chroma is sampled 1x1: its block grid is the MCU grid
+    else { ux = (f.width + 7) / 8; uy = (f.height + 7) / 8; }
+}
+int jpegprog_parse(const unsigned char *data, unsigned long long n, aej_jpegprog_frame &f, std::vector<aej_jpegprog_scan> &scans,
+                   std::string &msg);                                                                                  // jpegparse.hip
 bool jpegprog_layout(const aej_jpegprog_frame *frames, const aej_jpegprog_scan *scans, int n, JpLayout &y);
 unsigned long long jpegprog_blob(const JpLayout &y, std::vector<unsigned char> *out);
 unsigned long long jpegprog_carve(void *base, const JpLayout &y, JpBufs &w);

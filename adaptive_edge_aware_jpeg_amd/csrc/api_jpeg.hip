@@ -183,7 +183,7 @@ extern "C" int aej_test_jfif_prog_scan(aej_ctx *ctx, const int16_t *coefs_host, 
     return rc;
 }
 
-// ---- baseline JPEG files decoded on the device (jpegdec.hip) --------------------------------------------------------------------------
+// ---- baseline JPEG files decoded on the device (jpegdec.hip; the marker walk: jpegparse.hip) --------------------------------------------------------------------------
 extern "C" int aej_jpegdec_parse_host(const uint8_t *data_host, uint64_t nbytes, aej_jpegdec_desc *desc_host, char *msg, int msg_capacity)
 {
     if (!desc_host) return AEJ_ERR_ARG;
@@ -193,20 +193,34 @@ extern "C" int aej_jpegdec_parse_host(const uint8_t *data_host, uint64_t nbytes,
     return rc;
 }
 
-static bool jpegdec_descs_ok(const aej_jpegdec_desc *d, int n)
+// ---- what a call's offsets must satisfy (shared by the decoders and the transcoder) -------------------------------------------------------
+static bool inside(long long off, long long len, uint64_t bytes) { return off >= 0 && (uint64_t)off + (uint64_t)len <= bytes; }
+
+// the scan offset of baseline file i checked against the scans buffer and entered into the layout
+static int jpegdec_scan_offset(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc &d, int i, uint64_t scans_bytes, long long so, JdFile &file)
 {
-    if (!d || n < 1) return false;
-    for (int i = 0; i < n; i++) {
-        const aej_jpegdec_desc &e = d[i];
-        const bool color = e.ncomp == 3 && ((e.hs == 1 && e.vs == 1) || (e.hs == 2 && (e.vs == 1 || e.vs == 2)));
-        if (!(color || (e.ncomp == 1 && e.hs == 1 && e.vs == 1))) return false;
-        if (e.width < 1 || e.height < 1 || e.width > 65535 || e.height > 65535 || e.scan_length < 0) return false;
-        if (e.mcux != (e.width + 8 * e.hs - 1) / (8 * e.hs) || e.mcuy != (e.height + 8 * e.vs - 1) / (8 * e.vs)) return false;
-        if (e.blocks_per_mcu != (e.ncomp == 1 ? 1 : e.hs * e.vs + 2) || e.restart_interval < 0) return false;
-        const long long mcus = (long long)e.mcux * e.mcuy;
-        if (e.n_segments != (e.restart_interval ? (mcus + e.restart_interval - 1) / e.restart_interval : 1)) return false;
+    if (!inside(so, d.scan_length, scans_bytes)) return fail(ctx, AEJ_ERR_ARG, "%s: file %d: scan outside the scans buffer", fn, i);
+    file.scan_off = so;
+    return 0;
+}
+
+// the same for every scan of the progressive files of a call (data_offsets_host is in the caller's scan order)
+static int jpegprog_scan_offsets(aej_ctx *ctx, const char *fn, JpLayout &y, uint64_t data_bytes, const int64_t *data_offsets_host)
+{
+    for (size_t t = 0; t < y.scans.size(); t++) {
+        const long long so = data_offsets_host[y.src[t]];
+        if (!inside(so, y.sfiles[t].scan_len, data_bytes)) return fail(ctx, AEJ_ERR_ARG, "%s: scan %d: bytes outside the data buffer", fn, y.src[t]);
+        y.sfiles[t].scan_off = so;
     }
-    return true;
+    return 0;
+}
+
+// the RGB image of file i checked against the output and entered into the layout
+static int image_offset(aej_ctx *ctx, const char *fn, int i, int width, int height, uint64_t out_bytes, long long oo, JdFile &file)
+{
+    if (!inside(oo, (long long)width * height * 3, out_bytes)) return fail(ctx, AEJ_ERR_ARG, "%s: file %d: image outside the output", fn, i);
+    file.out_off = oo;
+    return 0;
 }
 
 extern "C" uint64_t aej_jpegdec_workspace_bytes(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n)
@@ -252,14 +266,6 @@ static int jpegdec_decode(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *
     return 0;
 }
 
-// the scan offset of baseline file i checked against the scans buffer and entered into the layout
-static int jpegdec_scan_offset(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc &d, int i, uint64_t scans_bytes, long long so, JdFile &file)
-{
-    if (so < 0 || (uint64_t)so + (uint64_t)d.scan_length > scans_bytes) return fail(ctx, AEJ_ERR_ARG, "%s: file %d: scan outside the scans buffer", fn, i);
-    file.scan_off = so;
-    return 0;
-}
-
 extern "C" int aej_jpegdec_batch(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const uint8_t *scans, uint64_t scans_bytes,
                                  const int64_t *scan_offsets_host, uint8_t *out, uint64_t out_bytes, const int64_t *out_offsets_host,
                                  int32_t *status, void *workspace, uint64_t workspace_bytes)
@@ -274,9 +280,7 @@ extern "C" int aej_jpegdec_batch(aej_ctx *ctx, const aej_jpegdec_desc *descs_hos
     for (int i = 0; i < n; i++) {                            // file by file, scan before image, as the errors were always reported
         const aej_jpegdec_desc &d = descs_host[i];
         AEJ_TRY(jpegdec_scan_offset(ctx, __func__, d, i, scans_bytes, scan_offsets_host[i], files[i]));
-        const long long oo = out_offsets_host[i], ob = (long long)d.width * d.height * 3;
-        if (oo < 0 || (uint64_t)oo + (uint64_t)ob > out_bytes) return fail(ctx, AEJ_ERR_ARG, "%s: file %d: image outside the output", __func__, i);
-        files[i].out_off = oo;
+        AEJ_TRY(image_offset(ctx, __func__, i, d.width, d.height, out_bytes, out_offsets_host[i], files[i]));
     }
     JdBufs w;
     const unsigned long long need = jpegdec_carve(workspace, n, z, w);
@@ -329,17 +333,9 @@ static int jpegprog_run(aej_ctx *ctx, const char *fn, const aej_jpegprog_frame *
         return fail(ctx, AEJ_ERR_ARG, "%s: no files, or descriptors aej_jpegprog_parse_host did not write", fn);
     if (!data || !data_offsets_host || !status || !workspace || (!out && !coef_out) || (out && !out_offsets_host))
         return null_buffer(ctx, fn);
-    for (size_t t = 0; t < y.scans.size(); t++) {
-        const long long so = data_offsets_host[y.src[t]];
-        if (so < 0 || (uint64_t)so + (uint64_t)y.sfiles[t].scan_len > data_bytes)
-            return fail(ctx, AEJ_ERR_ARG, "%s: scan %d: bytes outside the data buffer", fn, y.src[t]);
-        y.sfiles[t].scan_off = so;
-    }
-    for (int i = 0; out && i < n; i++) {
-        const long long oo = out_offsets_host[i], ob = (long long)frames_host[i].width * frames_host[i].height * 3;
-        if (oo < 0 || (uint64_t)oo + (uint64_t)ob > out_bytes) return fail(ctx, AEJ_ERR_ARG, "%s: file %d: image outside the output", fn, i);
-        y.ffiles[i].out_off = oo;
-    }
+    AEJ_TRY(jpegprog_scan_offsets(ctx, fn, y, data_bytes, data_offsets_host));
+    for (int i = 0; out && i < n; i++)
+        AEJ_TRY(image_offset(ctx, fn, i, frames_host[i].width, frames_host[i].height, out_bytes, out_offsets_host[i], y.ffiles[i]));
     if (coef_out && (uint64_t)y.fz.blocks > coef_blocks) return fail(ctx, AEJ_ERR_CAPACITY, "%s: %lld coefficient blocks, room for %llu", fn, y.fz.blocks, (unsigned long long)coef_blocks);
     JpBufs w;
     const unsigned long long need = jpegprog_carve(workspace, y, w);
@@ -535,12 +531,7 @@ static int jt_batch(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs_
     JtCall c;
     AEJ_TRY(jt_layout(ctx, fn, descs_host, n_base, frames_host, pscans_host, n_prog, density_host, progressive, xf, trim, c));
     for (int i = 0; i < n_base; i++) AEJ_TRY(jpegdec_scan_offset(ctx, fn, descs_host[i], i, scans_bytes, scan_offsets_host[i], c.files[i]));
-    for (size_t t = 0; t < c.y.scans.size(); t++) {
-        const long long so = data_offsets_host[c.y.src[t]];
-        if (so < 0 || (uint64_t)so + (uint64_t)c.y.sfiles[t].scan_len > data_bytes)
-            return fail(ctx, AEJ_ERR_ARG, "%s: scan %d: bytes outside the data buffer", fn, c.y.src[t]);
-        c.y.sfiles[t].scan_off = so;
-    }
+    AEJ_TRY(jpegprog_scan_offsets(ctx, fn, c.y, data_bytes, data_offsets_host));
     const JtWorkspace ws = jt_carve(workspace, n_base, n_prog, c);
     AEJ_TRY(check_workspace(ctx, ws.bytes, workspace_bytes));
     const int n = n_base + n_prog;

@@ -35,9 +35,7 @@ constexpr int kJfThreads = 256;
 constexpr int kJfScanThreads = 1024;
 constexpr int kJfChunk = 64;           // bytes per stuffing chunk
 
-__constant__ unsigned char k_zz[64] = { 0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14,
-                                        21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46,
-                                        53, 60, 61, 54, 47, 55, 62, 63 };
+__constant__ unsigned char k_zz[64] = { AEJ_ZIGZAG_8X8 };
 constexpr unsigned char kJfInvZz[64] = { 0, 1, 5, 6, 14, 15, 27, 28, 2, 4, 7, 13, 16, 26, 29, 42, 3, 8, 12, 17, 25, 30, 41, 43, 9, 11, 18, 24, 31, 40, 44, 53, 10, 19, 23, 32, 39, 45, 52, 54, 20, 22, 33, 38, 46, 51, 55, 60, 21, 34, 37, 47, 50, 56, 59, 61, 35, 36, 48, 49, 57, 58, 62, 63 };      // zigzag position of natural index
 // Annex K.3 Huffman codes, (code << 8) | length, indexed by symbol (0 = symbol not in the table)
 // dc_luma: (code << 8) | length
@@ -723,9 +721,7 @@ void jfif_quant_tables(int q, int luma[64], int chroma[64])
     }
 }
 
-static const unsigned char kZzHost[64] = { 0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14,
-                                           21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46,
-                                           53, 60, 61, 54, 47, 55, 62, 63 };
+static const unsigned char kZzHost[64] = { AEJ_ZIGZAG_8X8 };
 
 void jfif_params_host(int q, int H, int W, JfifParams &p, int ss)
 {

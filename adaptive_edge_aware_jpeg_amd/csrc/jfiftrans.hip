@@ -41,9 +41,7 @@ namespace aej {
 
 constexpr int kJtThreads = 256;
 
-__constant__ unsigned char k_jt_zz[64] = { 0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14,
-                                           21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46,
-                                           53, 60, 61, 54, 47, 55, 62, 63 };
+__constant__ unsigned char k_jt_zz[64] = { AEJ_ZIGZAG_8X8 };
 
 __device__ __forceinline__ int jt_find_file(const JtFile *f, int n, long long t)      // last file whose src_base <= t (jd_find_file)
 {
@@ -142,9 +140,7 @@ __global__ __launch_bounds__(kJtThreads) void k_jt_finish(const JtFile *__restri
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------
-static const unsigned char kJtZzHost[64] = { 0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14,
-                                             21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46,
-                                             53, 60, 61, 54, 47, 55, 62, 63 };
+static const unsigned char kJtZzHost[64] = { AEJ_ZIGZAG_8X8 };
 
 template <class D>
 static void jt_source(const D &d, JtSource &s)

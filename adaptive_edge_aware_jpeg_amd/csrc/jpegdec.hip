@@ -1,5 +1,6 @@
 // jpegdec.hip -- baseline JPEG files decoded on the device, pixel-identical to Pillow with libjpeg-turbo (aej_jpegdec_*, include/aej.h).
-// The host reads the markers up to SOS (aej_jpegdec_parse_host); everything after that runs here, one launch per stage over the whole call:
+// The host reads the markers up to SOS (aej_jpegdec_parse_host, jpegparse.hip); everything after that runs here, one launch per stage over
+// the whole call:
 //   k_jd_count      one thread per 64-byte chunk of a scan: data bytes, RSTn markers and whether the scan ends in it (jd_byte_class)
 //   k_jd_scan_chunks one workgroup per file: exclusive scan of those counts, the clean length; restart-marker count check
 //   k_jd_scatter    one thread per chunk: the chunk's data bytes at their place in the clean stream (0x00 after 0xFF removed), the start
@@ -23,8 +24,7 @@
 #include <string>
 #include <vector>
 
-#include "aej_common.h"
-#include "aej_launch.h"
+#include "aej_ctx.h"
 
 namespace aej {
 
@@ -377,254 +377,77 @@ __global__ __launch_bounds__(kJdThreads) void k_jd_rgb(const JdFile *__restrict_
     jd_rgb(Y, jd_chroma(cb, F.pw1, d.hs, d.vs, wc, hc, y, x), jd_chroma(cr, F.pw1, d.hs, d.vs, wc, hc, y, x), o);
 }
 
-// ---- host: the header parser ---------------------------------------------------------------------------------------------------------
-// libjpeg's jpeg_make_d_derived_tbl: canonical codes, over-subscription check, then the decode tables
-bool jd_build_huff(const JdHuffSrc &s, aej_jpegdec_huff &h)
+// ---- host: descriptor checks, layout and launch sequence -----------------------------------------------------------------------------------
+bool jpegdec_descs_ok(const aej_jpegdec_desc *d, int n)
 {
-    memset(&h, 0, sizeof h);
-    int size[257], code[257], p = 0;
-    for (int l = 1; l <= 16; l++)
-        for (int i = 0; i < s.bits[l]; i++) size[p++] = l;
-    size[p] = 0;
-    int c = 0, si = size[0];
-    p = 0;
-    while (size[p]) {
-        while (size[p] == si) code[p++] = c++;
-        if (c >= (1 << si)) return false;
-        c <<= 1;
-        si++;
+    if (!d || n < 1) return false;
+    for (int i = 0; i < n; i++) {
+        const aej_jpegdec_desc &e = d[i];
+        if (!jpeg_frame_ok(e) || e.scan_length < 0 || e.restart_interval < 0) return false;
+        const long long mcus = (long long)e.mcux * e.mcuy;
+        if (e.n_segments != (e.restart_interval ? (mcus + e.restart_interval - 1) / e.restart_interval : 1)) return false;
     }
-    p = 0;
-    for (int l = 1; l <= 16; l++) {
-        if (s.bits[l]) {
-            h.valoff[l] = p - code[p];
-            p += s.bits[l];
-            h.maxcode[l] = code[p - 1];
-        } else {
-            h.maxcode[l] = -1;
-        }
-    }
-    h.maxcode[17] = -1;
-    memcpy(h.vals, s.vals, sizeof h.vals);
-    p = 0;
-    for (int l = 1; l <= 9; l++)
-        for (int i = 0; i < s.bits[l]; i++, p++) {
-            const int lo = code[p] << (9 - l);
-            for (int e = 0; e < (1 << (9 - l)); e++) h.lut[lo + e] = (uint16_t)((l << 8) | s.vals[p]);
-        }
     return true;
 }
 
-int jpegdec_parse(const unsigned char *b, unsigned long long n, aej_jpegdec_desc &d, std::string &msg)
+void jpeg_stream_layout(long long len, int n_segments, int S, JdFile &F, JdBufSizes &z)
 {
-    memset(&d, 0, sizeof d);
-    auto bad = [&](const std::string &m) { msg = m; return -1; };
-    auto unsup = [&](const std::string &m) { msg = m; return -5; };
-    if (!b || n < 4 || b[0] != 0xFF || b[1] != 0xD8) return bad("not a JPEG file (no SOI marker)");
-    uint16_t qt[4][64];
-    bool qdef[4] = {}, q16[4] = {}, sof = false, jfif = false, adobe = false;
-    int adobe_transform = -1, ri = 0, nf = 0;
-    JdHuffSrc hs[2][4];
-    unsigned long long p = 2;
-    for (;;) {
-        if (p >= n) return bad("no SOS marker (the file ends in its header)");
-        if (b[p] != 0xFF) return bad("bytes between markers in the header");
-        while (p < n && b[p] == 0xFF) p++;
-        if (p >= n) return bad("no SOS marker (the file ends in its header)");
-        const int m = b[p++];
-        if (m == 0x01 || (m >= 0xD0 && m <= 0xD7)) continue;
-        if (m == 0xD8) return bad("second SOI marker");
-        if (m == 0xD9) return bad("EOI before SOS");
-        if (p + 2 > n) return bad("truncated marker segment");
-        const unsigned L = (unsigned)b[p] << 8 | b[p + 1];
-        if (L < 2 || p + L > n) return bad("truncated marker segment");
-        const unsigned char *s = b + p + 2;
-        const unsigned len = L - 2;
-        switch (m) {
-        case 0xC0: case 0xC1: {
-            if (sof) return bad("two SOF markers");
-            if (len < 6) return bad("truncated SOF segment");
-            if (s[0] != 8) return unsup("sample precision " + std::to_string(s[0]) + " (only 8-bit)");
-            d.height = s[1] << 8 | s[2];
-            d.width = s[3] << 8 | s[4];
-            nf = s[5];
-            if (len != 6u + 3u * nf) return bad("SOF length does not match its component count");
-            if (d.height == 0) return unsup("DNL (height defined after the scan)");
-            if (d.width == 0) return bad("zero image width");
-            if (nf != 1 && nf != 3) return unsup(std::to_string(nf) + " components (only 1 or 3)");
-            for (int i = 0; i < nf; i++) {
-                d.comp_id[i] = s[6 + 3 * i];
-                d.comp_h[i] = s[7 + 3 * i] >> 4;
-                d.comp_v[i] = s[7 + 3 * i] & 15;
-                d.comp_tq[i] = s[8 + 3 * i];
-                if (d.comp_h[i] < 1 || d.comp_h[i] > 4 || d.comp_v[i] < 1 || d.comp_v[i] > 4 || d.comp_tq[i] > 3)
-                    return bad("bad component sampling factor or table index");
-            }
-            d.sof = m;
-            sof = true;
-            break;
-        }
-        case 0xC2: return unsup("progressive JPEG (SOF2)");
-        case 0xC3: return unsup("lossless JPEG (SOF3)");
-        case 0xC5: case 0xC6: case 0xC7: return unsup("hierarchical JPEG (SOF" + std::to_string(m - 0xC0) + ")");
-        case 0xC9: case 0xCA: case 0xCB: case 0xCD: case 0xCE: case 0xCF: case 0xCC:
-            return unsup("arithmetic coding (" + std::string(m == 0xCC ? "DAC" : "SOF" + std::to_string(m - 0xC0)) + ")");
-        case 0xDC: return unsup("DNL marker");
-        case 0xC4: {
-            unsigned i = 0;
-            while (i < len) {
-                const int tc = s[i] >> 4, th = s[i] & 15;
-                if (tc > 1 || th > 3) return bad("bad DHT table class or index");
-                if (i + 17 > len) return bad("truncated DHT segment");
-                JdHuffSrc &t = hs[tc][th];
-                int cnt = 0;
-                for (int l = 1; l <= 16; l++) { t.bits[l] = s[i + l]; cnt += s[i + l]; }
-                if (cnt > 256 || i + 17 + cnt > len) return bad("bad DHT symbol count");
-                memset(t.vals, 0, sizeof t.vals);
-                memcpy(t.vals, s + i + 17, cnt);
-                t.count = cnt;
-                if (tc == 0)
-                    for (int v = 0; v < cnt; v++) if (t.vals[v] > 15) return bad("DC Huffman symbol above 15");
-                aej_jpegdec_huff tmp;
-                if (!jd_build_huff(t, tmp)) return bad("over-subscribed Huffman table");
-                t.defined = true;
-                i += 17 + cnt;
-            }
-            break;
-        }
-        case 0xDB: {
-            unsigned i = 0;
-            while (i < len) {
-                const int pq = s[i] >> 4, tq = s[i] & 15;
-                if (pq > 1 || tq > 3) return bad("bad DQT precision or index");
-                const unsigned need = 1 + 64u * (pq + 1);
-                if (i + need > len) return bad("truncated DQT segment");
-                for (int z = 0; z < 64; z++)
-                    qt[tq][jd_natural(z)] = pq ? (uint16_t)(s[i + 1 + 2 * z] << 8 | s[i + 2 + 2 * z]) : s[i + 1 + z];
-                qdef[tq] = true;
-                q16[tq] = pq == 1;
-                i += need;
-            }
-            break;
-        }
-        case 0xDD:
-            if (len != 2) return bad("bad DRI length");
-            ri = s[0] << 8 | s[1];
-            break;
-        case 0xE0:
-            if (len >= 5 && !memcmp(s, "JFIF\0", 5)) jfif = true;
-            break;
-        case 0xEE:
-            if (len >= 12 && !memcmp(s, "Adobe", 5)) { adobe = true; adobe_transform = s[11]; }
-            break;
-        case 0xDA: {
-            if (!sof) return bad("SOS before SOF");
-            if (len < 1) return bad("truncated SOS segment");
-            const int ns = s[0];
-            if (len != 4u + 2u * ns || ns < 1) return bad("SOS length does not match its component count");
-            if (ns < nf) return unsup("multi-scan sequential JPEG (the first scan holds " + std::to_string(ns) + " of " + std::to_string(nf) + " components)");
-            if (ns != nf) return bad("SOS lists more components than the frame");
-            for (int i = 0; i < ns; i++)
-                if (s[1 + 2 * i] != d.comp_id[i]) return unsup("scan components in another order than the frame's");
-            if (s[1 + 2 * ns] != 0 || s[2 + 2 * ns] != 63 || s[3 + 2 * ns] != 0) return bad("bad spectral selection / approximation for a sequential scan");
-            if (nf == 3) {
-                const bool rgb_ids = d.comp_id[0] == 'R' && d.comp_id[1] == 'G' && d.comp_id[2] == 'B';
-                if (!jfif && adobe && adobe_transform == 0) return unsup("Adobe APP14 transform 0 (RGB colour)");
-                if (!jfif && !adobe && rgb_ids) return unsup("component ids 'R','G','B' without JFIF (RGB colour)");
-                const int h0 = d.comp_h[0], v0 = d.comp_v[0];
-                if (d.comp_h[1] != 1 || d.comp_v[1] != 1 || d.comp_h[2] != 1 || d.comp_v[2] != 1 ||
-                    !((h0 == 1 && v0 == 1) || (h0 == 2 && v0 == 1) || (h0 == 2 && v0 == 2)))
-                    return unsup("sampling factors " + std::to_string(h0) + "x" + std::to_string(v0) + "," + std::to_string(d.comp_h[1]) + "x" +
-                                 std::to_string(d.comp_v[1]) + "," + std::to_string(d.comp_h[2]) + "x" + std::to_string(d.comp_v[2]));
-                d.hs = h0; d.vs = v0;
-                d.mcux = (d.width + 8 * h0 - 1) / (8 * h0);
-                d.mcuy = (d.height + 8 * v0 - 1) / (8 * v0);
-                d.blocks_per_mcu = h0 * v0 + 2;
-            } else {                                     // one component: a non-interleaved scan, whatever its sampling factors say
-                d.hs = d.vs = 1;
-                d.mcux = (d.width + 7) / 8;
-                d.mcuy = (d.height + 7) / 8;
-                d.blocks_per_mcu = 1;
-            }
-            for (int i = 0; i < nf; i++) {
-                const int tq = d.comp_tq[i], td = s[2 + 2 * i] >> 4, ta = s[2 + 2 * i] & 15;
-                if (!qdef[tq]) return bad("undefined quantisation table " + std::to_string(tq));
-                if (td > 3 || ta > 3 || !hs[0][td].defined || !hs[1][ta].defined) return bad("undefined Huffman table");
-                memcpy(d.qt[i], qt[tq], sizeof d.qt[i]);
-                d.precision16 |= q16[tq];
-                jd_build_huff(hs[0][td], d.dc[i]);
-                jd_build_huff(hs[1][ta], d.ac[i]);
-            }
-            const long long mcus = (long long)d.mcux * d.mcuy;
-            d.restart_interval = ri;
-            d.n_segments = ri ? (int)((mcus + ri - 1) / ri) : 1;
-            d.ncomp = nf;
-            d.scan_offset = (long long)(p + L);
-            d.scan_length = (long long)(n - (p + L));
-            return 0;
-        }
-        default:
-            break;                                   // APPn, COM, JPGn, ...
-        }
-        p += L;
-    }
+    F.scan_len = len;
+    F.clean_off = z.clean;
+    z.clean += align_up(len, 4) + 16;
+    F.chunk_base = z.chunks;
+    F.n_chunks = (len + kJdChunk - 1) / kJdChunk;
+    z.chunks += F.n_chunks;
+    F.seg_base = z.segs;
+    z.segs += n_segments;
+    F.slot_base = z.slots;
+    F.n_slots = n_segments + (len * 8 + S - 1) / S + 1;
+    z.slots += F.n_slots;
 }
 
-// ---- host: layout and launch sequence ----------------------------------------------------------------------------------------------------
-static long long jd_align(long long v, long long a) { return (v + a - 1) / a * a; }
+void jpeg_recon_layout(const aej_jpegdec_desc &d, JdFile &F, JdBufSizes &z)
+{
+    F.blk_base = z.blocks;
+    F.n_blocks = (long long)d.mcux * d.mcuy * d.blocks_per_mcu;
+    z.blocks += F.n_blocks;
+    F.pw0 = d.mcux * 8 * d.hs; F.ph0 = d.mcuy * 8 * d.vs;
+    F.pw1 = d.ncomp == 3 ? d.mcux * 8 : 0; F.ph1 = d.ncomp == 3 ? d.mcuy * 8 : 0;
+    F.plane_off = z.planes;
+    z.planes += align_up((long long)F.pw0 * F.ph0 + 2LL * F.pw1 * F.ph1, 256);
+    F.px_base = z.px;
+    z.px += (long long)d.width * d.height;
+}
 
-long long jpegdec_layout(const aej_jpegdec_desc *descs, int n, int S, std::vector<JdFile> &files, JdBufSizes &z)
+void jpegdec_layout(const aej_jpegdec_desc *descs, int n, int S, std::vector<JdFile> &files, JdBufSizes &z)
 {
     files.assign(n, JdFile{});
     z = JdBufSizes{};
     for (int i = 0; i < n; i++) {
-        const aej_jpegdec_desc &d = descs[i];
-        JdFile &F = files[i];
-        F.scan_len = d.scan_length;
-        F.clean_off = z.clean;
-        z.clean += jd_align(d.scan_length, 4) + 16;
-        F.chunk_base = z.chunks;
-        F.n_chunks = (d.scan_length + kJdChunk - 1) / kJdChunk;
-        z.chunks += F.n_chunks;
-        F.seg_base = z.segs;
-        z.segs += d.n_segments;
-        F.slot_base = z.slots;
-        F.n_slots = d.n_segments + (d.scan_length * 8 + S - 1) / S + 1;
-        z.slots += F.n_slots;
-        F.blk_base = z.blocks;
-        F.n_blocks = (long long)d.mcux * d.mcuy * d.blocks_per_mcu;
-        z.blocks += F.n_blocks;
-        F.pw0 = d.mcux * 8 * d.hs; F.ph0 = d.mcuy * 8 * d.vs;
-        F.pw1 = d.ncomp == 3 ? d.mcux * 8 : 0; F.ph1 = d.ncomp == 3 ? d.mcuy * 8 : 0;
-        F.plane_off = z.planes;
-        z.planes += jd_align((long long)F.pw0 * F.ph0 + 2LL * F.pw1 * F.ph1, 256);
-        F.px_base = z.px;
-        z.px += (long long)d.width * d.height;
+        jpeg_stream_layout(descs[i].scan_length, descs[i].n_segments, S, files[i], z);
+        jpeg_recon_layout(descs[i], files[i], z);
     }
-    return 0;
 }
 
 unsigned long long jpegdec_carve(void *base, int n, const JdBufSizes &z, JdBufs &w)
 {
-    unsigned long long off = 0;
-    auto take = [&](unsigned long long bytes) { void *p = base ? (char *)base + off : nullptr; off += (bytes + 255) / 256 * 256; return p; };
-    w.files = (JdFile *)take(sizeof(JdFile) * n + sizeof(aej_jpegdec_desc) * n + 16);
+    Carver c(base);
+    w.files = (JdFile *)c.take<char>(sizeof(JdFile) * n + sizeof(aej_jpegdec_desc) * n + 16);      // one upload: see JdBufs
     w.descs = base ? (aej_jpegdec_desc *)((char *)w.files + sizeof(JdFile) * n) : nullptr;
     w.last_change = base ? (int *)((char *)w.descs + sizeof(aej_jpegdec_desc) * n) : nullptr;
-    w.cnt = (int *)take(z.chunks * 3 * 4);
-    w.pre = (long long *)take(z.chunks * 3 * 8);
-    w.clean_len = (long long *)take(n * 8);
-    w.segs = (JdSeg *)take(z.segs * sizeof(JdSeg));
-    w.clean = (unsigned char *)take(z.clean);
-    w.sl.state = (unsigned long long *)take(z.slots * 8);
-    w.sl.used = (unsigned long long *)take(z.slots * 8);
-    w.sl.cnt = (int *)take(z.slots * 16);
-    w.sl.first = (unsigned char *)take(z.slots);
-    w.sl.blk_pre = (long long *)take(z.slots * 8);
-    w.sl.dc_pre = (int *)take(z.slots * 12);
-    w.coef = (short *)take(z.blocks * 128);
-    w.planes = (unsigned char *)take(z.planes);
-    return off;
+    w.cnt = c.take<int>(z.chunks * 3);
+    w.pre = c.take<long long>(z.chunks * 3);
+    w.clean_len = c.take<long long>(n);
+    w.segs = c.take<JdSeg>(z.segs);
+    w.clean = c.take<unsigned char>(z.clean);
+    w.sl.state = c.take<unsigned long long>(z.slots);
+    w.sl.used = c.take<unsigned long long>(z.slots);
+    w.sl.cnt = c.take<int>(z.slots * 4);
+    w.sl.first = c.take<unsigned char>(z.slots);
+    w.sl.blk_pre = c.take<long long>(z.slots);
+    w.sl.dc_pre = c.take<int>(z.slots * 3);
+    w.coef = c.take<short>(z.blocks * 64);
+    w.planes = c.take<unsigned char>(z.planes);
+    return c.bytes();
 }
 
 static unsigned jd_grid(long long n) { return (unsigned)((n + kJdThreads - 1) / kJdThreads); }

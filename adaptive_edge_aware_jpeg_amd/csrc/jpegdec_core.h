@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/aej.h"
+#include "aej_common.h"
 
 #ifndef AEJ_HD
 #define AEJ_HD __host__ __device__
@@ -91,9 +92,7 @@ AEJ_HD inline bool jd_huff(const aej_jpegdec_huff &h, unsigned win, int &len, in
 // natural index of zigzag position z (z < 64)
 AEJ_HD inline int jd_natural(int z)
 {
-    const unsigned char zz[64] = { 0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14,
-                                   21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46,
-                                   53, 60, 61, 54, 47, 55, 62, 63 };
+    const unsigned char zz[64] = { AEJ_ZIGZAG_8X8 };
     return zz[z];
 }
 

@@ -1,6 +1,6 @@
 // jpegprog.hip -- progressive JPEG files (SOF2) decoded on the device, pixel-identical to Pillow with libjpeg-turbo for every complete
-// progression (aej_jpegprog_*, include/aej.h).  The host walks all markers (jpegprog_parse); the device does the rest, over every file
-// of the call at once:
+// progression (aej_jpegprog_*, include/aej.h).  The host walks all markers (jpegprog_parse, jpegparse.hip); the device does the rest, over
+// every file of the call at once:
 //   un-stuffing      jpegdec.hip's k_jd_count / k_jd_scan_chunks / k_jd_scatter / k_jd_segments, unchanged, with one stream per SCAN where
 //                    the baseline path has one per file (launch_jpegdec_unstuff)
 //   k_jp_level       one launch per dependency level: a workgroup serves kJpItem restart segments of one scan, stages that scan's
@@ -17,8 +17,7 @@
 #include <string>
 #include <vector>
 
-#include "aej_common.h"
-#include "aej_launch.h"
+#include "aej_ctx.h"
 
 namespace aej {
 
@@ -68,237 +67,7 @@ __global__ __launch_bounds__(256) void k_jp_status(const JpScan *__restrict__ sc
     if (v) atomicCAS(status + scans[s].file, 0, v);
 }
 
-// ---- host: the marker walk -------------------------------------------------------------------------------------------------------------
-static void jp_scan_units(const aej_jpegprog_frame &f, int ncomp, int comp0, int &ux, int &uy)
-{
-    if (ncomp > 1 || f.ncomp == 1 || comp0 > 0) { ux = f.mcux; uy = f.mcuy; }      // chroma is sampled 1x1: its block grid is the MCU grid
-    else { ux = (f.width + 7) / 8; uy = (f.height + 7) / 8; }
-}
-
-int jpegprog_parse(const unsigned char *b, unsigned long long n, aej_jpegprog_frame &f, std::vector<aej_jpegprog_scan> &scans, std::string &msg)
-{
-    memset(&f, 0, sizeof f);
-    scans.clear();
-    auto bad = [&](const std::string &m) { msg = m; return (int)AEJ_ERR_ARG; };
-    auto unsup = [&](const std::string &m) { msg = m; return (int)AEJ_ERR_UNSUPPORTED; };
-    if (!b || n < 4 || b[0] != 0xFF || b[1] != 0xD8) return bad("not a JPEG file (no SOI marker)");
-    uint16_t qt[4][64];
-    bool qdef[4] = {}, q16[4] = {}, sof = false, jfif = false, adobe = false, qlatched[3] = {};
-    int adobe_transform = -1, ri = 0, nf = 0;
-    int coef_al[3][64], cell_level[3][64];
-    for (int c = 0; c < 3; c++)
-        for (int k = 0; k < 64; k++) { coef_al[c][k] = -1; cell_level[c][k] = -1; }
-    JdHuffSrc hs[2][4];
-    unsigned long long p = 2;
-    for (;;) {
-        if (p >= n) return bad("no EOI marker (the file ends after " + std::to_string(scans.size()) + " scans)");
-        if (b[p] != 0xFF) return bad("bytes between markers");
-        while (p < n && b[p] == 0xFF) p++;
-        if (p >= n) return bad("no EOI marker (the file ends in a marker)");
-        const int m = b[p++];
-        if (m == 0x01 || (m >= 0xD0 && m <= 0xD7)) continue;
-        if (m == 0xD8) return bad("second SOI marker");
-        if (m == 0xD9) break;
-        if (p + 2 > n) return bad("truncated marker segment");
-        const unsigned L = (unsigned)b[p] << 8 | b[p + 1];
-        if (L < 2 || p + L > n) return bad("truncated marker segment");
-        const unsigned char *s = b + p + 2;
-        const unsigned len = L - 2;
-        switch (m) {
-        case 0xC0: case 0xC1: return unsup("not a progressive file (SOF" + std::to_string(m - 0xC0) + ")");
-        case 0xC2: {
-            if (sof) return bad("two SOF markers");
-            if (len < 6) return bad("truncated SOF segment");
-            if (s[0] != 8) return unsup("sample precision " + std::to_string(s[0]) + " (only 8-bit)");
-            f.height = s[1] << 8 | s[2];
-            f.width = s[3] << 8 | s[4];
-            nf = s[5];
-            if (len != 6u + 3u * nf) return bad("SOF length does not match its component count");
-            if (f.height == 0) return unsup("DNL (height defined after the scan)");
-            if (f.width == 0) return bad("zero image width");
-            if (nf != 1 && nf != 3) return unsup(std::to_string(nf) + " components (only 1 or 3)");
-            for (int i = 0; i < nf; i++) {
-                f.comp_id[i] = s[6 + 3 * i];
-                f.comp_h[i] = s[7 + 3 * i] >> 4;
-                f.comp_v[i] = s[7 + 3 * i] & 15;
-                f.comp_tq[i] = s[8 + 3 * i];
-                if (f.comp_h[i] < 1 || f.comp_h[i] > 4 || f.comp_v[i] < 1 || f.comp_v[i] > 4 || f.comp_tq[i] > 3)
-                    return bad("bad component sampling factor or table index");
-                for (int j = 0; j < i; j++) if (f.comp_id[j] == f.comp_id[i]) return bad("two frame components with one id");
-            }
-            if (nf == 3) {
-                const int h0 = f.comp_h[0], v0 = f.comp_v[0];
-                if (f.comp_h[1] != 1 || f.comp_v[1] != 1 || f.comp_h[2] != 1 || f.comp_v[2] != 1 ||
-                    !((h0 == 1 && v0 == 1) || (h0 == 2 && v0 == 1) || (h0 == 2 && v0 == 2)))
-                    return unsup("sampling factors " + std::to_string(h0) + "x" + std::to_string(v0) + "," + std::to_string(f.comp_h[1]) + "x" +
-                                 std::to_string(f.comp_v[1]) + "," + std::to_string(f.comp_h[2]) + "x" + std::to_string(f.comp_v[2]));
-                f.hs = h0; f.vs = v0;
-                f.blocks_per_mcu = h0 * v0 + 2;
-            } else {
-                f.hs = f.vs = 1;
-                f.blocks_per_mcu = 1;
-            }
-            f.mcux = (f.width + 8 * f.hs - 1) / (8 * f.hs);
-            f.mcuy = (f.height + 8 * f.vs - 1) / (8 * f.vs);
-            f.ncomp = nf;
-            f.sof = m;
-            sof = true;
-            break;
-        }
-        case 0xC3: return unsup("lossless JPEG (SOF3)");
-        case 0xC5: case 0xC6: case 0xC7: return unsup("hierarchical JPEG (SOF" + std::to_string(m - 0xC0) + ")");
-        case 0xC9: case 0xCA: case 0xCB: case 0xCD: case 0xCE: case 0xCF: case 0xCC:
-            return unsup("arithmetic coding (" + std::string(m == 0xCC ? "DAC" : "SOF" + std::to_string(m - 0xC0)) + ")");
-        case 0xDC: return unsup("DNL marker");
-        case 0xC4: {
-            unsigned i = 0;
-            while (i < len) {
-                const int tc = s[i] >> 4, th = s[i] & 15;
-                if (tc > 1 || th > 3) return bad("bad DHT table class or index");
-                if (i + 17 > len) return bad("truncated DHT segment");
-                JdHuffSrc &t = hs[tc][th];
-                int cnt = 0;
-                for (int l = 1; l <= 16; l++) { t.bits[l] = s[i + l]; cnt += s[i + l]; }
-                if (cnt > 256 || i + 17 + cnt > len) return bad("bad DHT symbol count");
-                memset(t.vals, 0, sizeof t.vals);
-                memcpy(t.vals, s + i + 17, cnt);
-                t.count = cnt;
-                if (tc == 0)
-                    for (int v = 0; v < cnt; v++) if (t.vals[v] > 15) return bad("DC Huffman symbol above 15");
-                aej_jpegdec_huff tmp;
-                if (!jd_build_huff(t, tmp)) return bad("over-subscribed Huffman table");
-                t.defined = true;
-                i += 17 + cnt;
-            }
-            break;
-        }
-        case 0xDB: {
-            unsigned i = 0;
-            while (i < len) {
-                const int pq = s[i] >> 4, tq = s[i] & 15;
-                if (pq > 1 || tq > 3) return bad("bad DQT precision or index");
-                const unsigned need = 1 + 64u * (pq + 1);
-                if (i + need > len) return bad("truncated DQT segment");
-                for (int z = 0; z < 64; z++)
-                    qt[tq][jd_natural(z)] = pq ? (uint16_t)(s[i + 1 + 2 * z] << 8 | s[i + 2 + 2 * z]) : s[i + 1 + z];
-                qdef[tq] = true;
-                q16[tq] = pq == 1;
-                i += need;
-            }
-            break;
-        }
-        case 0xDD:
-            if (len != 2) return bad("bad DRI length");
-            ri = s[0] << 8 | s[1];
-            break;
-        case 0xE0:
-            if (len >= 5 && !memcmp(s, "JFIF\0", 5)) jfif = true;
-            break;
-        case 0xEE:
-            if (len >= 12 && !memcmp(s, "Adobe", 5)) { adobe = true; adobe_transform = s[11]; }
-            break;
-        case 0xDA: {
-            if (!sof) return bad("SOS before SOF");
-            const std::string at = "scan " + std::to_string(scans.size()) + ": ";
-            if (len < 1) return bad("truncated SOS segment");
-            const int ns = s[0];
-            if (ns < 1 || ns > 4 || len != 4u + 2u * ns) return bad(at + "SOS length does not match its component count");
-            if (scans.empty() && nf == 3) {
-                const bool rgb_ids = f.comp_id[0] == 'R' && f.comp_id[1] == 'G' && f.comp_id[2] == 'B';
-                if (!jfif && adobe && adobe_transform == 0) return unsup("Adobe APP14 transform 0 (RGB colour)");
-                if (!jfif && !adobe && rgb_ids) return unsup("component ids 'R','G','B' without JFIF (RGB colour)");
-            }
-            aej_jpegprog_scan sc;
-            memset(&sc, 0, sizeof sc);
-            sc.ncomp = ns;
-            for (int i = 0; i < ns; i++) {
-                int c = -1;
-                for (int j = 0; j < nf; j++) if (f.comp_id[j] == s[1 + 2 * i]) c = j;
-                if (c < 0) return bad(at + "a component the frame does not have");
-                if (i > 0 && c <= sc.comp[i - 1]) return bad(at + "components out of the frame's order");
-                sc.comp[i] = c;
-                sc.td[i] = s[2 + 2 * i] >> 4;
-                sc.ta[i] = s[2 + 2 * i] & 15;
-                if (sc.td[i] > 3 || sc.ta[i] > 3) return bad(at + "bad Huffman table selector");
-            }
-            sc.ss = s[1 + 2 * ns]; sc.se = s[2 + 2 * ns]; sc.ah = s[3 + 2 * ns] >> 4; sc.al = s[3 + 2 * ns] & 15;
-            if (sc.ss > sc.se || sc.se > 63) return bad(at + "spectral selection " + std::to_string(sc.ss) + ".." + std::to_string(sc.se));
-            if (sc.ss == 0 && sc.se != 0) return bad(at + "a DC scan with Se != 0");
-            if (sc.ss > 0 && ns != 1) return bad(at + "an AC scan with " + std::to_string(ns) + " components");
-            if (sc.al > 13) return bad(at + "Al " + std::to_string(sc.al) + " above 13");
-            if (sc.ah != 0 && sc.al != sc.ah - 1) return bad(at + "a refinement with Al != Ah - 1");
-            if (ns > 1 && ns != nf) return unsup(at + "an interleaved scan of " + std::to_string(ns) + " of " + std::to_string(nf) + " components");
-            int level = 0;
-            for (int i = 0; i < ns; i++) {
-                const int c = sc.comp[i];
-                if (sc.ss > 0 && coef_al[c][0] < 0) return bad(at + "an AC scan of a component before its DC scan");
-                for (int k = sc.ss; k <= sc.se; k++) {
-                    if (sc.ah == 0 && coef_al[c][k] >= 0) return bad(at + "a first scan of a coefficient already seen");
-                    if (sc.ah != 0 && coef_al[c][k] != sc.ah)
-                        return bad(at + "Ah " + std::to_string(sc.ah) + " is not the previous Al of coefficient " + std::to_string(k));
-                    coef_al[c][k] = sc.al;
-                    level = std::max(level, cell_level[c][k] + 1);
-                }
-                if (!qlatched[c]) {
-                    const int tq = f.comp_tq[c];
-                    if (!qdef[tq]) return bad("undefined quantisation table " + std::to_string(tq));
-                    memcpy(f.qt[c], qt[tq], sizeof f.qt[c]);
-                    f.precision16 |= q16[tq];
-                    qlatched[c] = true;
-                }
-                if (sc.ss == 0 && sc.ah == 0) {
-                    if (!hs[0][sc.td[i]].defined) return bad(at + "undefined Huffman table");
-                    jd_build_huff(hs[0][sc.td[i]], sc.dc[i]);
-                }
-                if (sc.ss > 0) {
-                    if (!hs[1][sc.ta[i]].defined) return bad(at + "undefined Huffman table");
-                    jd_build_huff(hs[1][sc.ta[i]], sc.ac);
-                }
-            }
-            for (int i = 0; i < ns; i++)
-                for (int k = sc.ss; k <= sc.se; k++) cell_level[sc.comp[i]][k] = level;
-            sc.level = level;
-            f.n_levels = std::max(f.n_levels, level + 1);
-            sc.restart_interval = ri;
-            jp_scan_units(f, ns, sc.comp[0], sc.units_x, sc.units_y);
-            const long long units = (long long)sc.units_x * sc.units_y;
-            sc.n_segments = ri ? (int)((units + ri - 1) / ri) : 1;
-            unsigned long long q = p + L;
-            sc.data_offset = (long long)q;
-            for (;;) {                                   // the scan ends at the first marker that is not RSTn
-                if (q >= n) return bad(at + "the scan runs past the end of the file (no EOI marker)");
-                if (b[q] != 0xFF) { q++; continue; }
-                if (q + 1 >= n) return bad(at + "the scan runs past the end of the file (no EOI marker)");
-                const int x = b[q + 1];
-                if (x == 0xFF) { q++; continue; }
-                if (x == 0x00 || (x >= 0xD0 && x <= 0xD7)) { q += 2; continue; }
-                break;
-            }
-            sc.data_length = (long long)q - sc.data_offset;
-            scans.push_back(sc);
-            p = q;
-            continue;
-        }
-        default:
-            break;                                   // APPn, COM, JPGn, ...
-        }
-        p += L;
-    }
-    if (!sof) return bad("EOI before SOF");
-    if (scans.empty()) return bad("EOI before SOS");
-    for (int c = 0; c < nf; c++)
-        for (int k = 0; k < 64; k++)
-            if (coef_al[c][k] != 0)
-                return unsup("incomplete progression: coefficient " + std::to_string(k) + " of component " + std::to_string(c) +
-                             (coef_al[c][k] < 0 ? " never arrives" : " stops at Al " + std::to_string(coef_al[c][k])) +
-                             " (libjpeg-turbo would smooth between blocks)");
-    f.n_scans = (int)scans.size();
-    return 0;
-}
-
 // ---- host: validation, layout, launch sequence -----------------------------------------------------------------------------------------
-static long long jp_align(long long v, long long a) { return (v + a - 1) / a * a; }
-
 // Everything the kernels index with is recomputed or checked here; the dependency levels are derived again rather than trusted.
 bool jpegprog_layout(const aej_jpegprog_frame *frames, const aej_jpegprog_scan *scans_in, int n, JpLayout &y)
 {
@@ -311,26 +80,13 @@ bool jpegprog_layout(const aej_jpegprog_frame *frames, const aej_jpegprog_scan *
     long long s0 = 0;
     for (int i = 0; i < n; i++) {
         const aej_jpegprog_frame &f = frames[i];
-        const bool color = f.ncomp == 3 && ((f.hs == 1 && f.vs == 1) || (f.hs == 2 && (f.vs == 1 || f.vs == 2)));
-        if (!(color || (f.ncomp == 1 && f.hs == 1 && f.vs == 1))) return false;
-        if (f.width < 1 || f.height < 1 || f.width > 65535 || f.height > 65535 || f.n_scans < 1 || f.n_scans > 4096) return false;
-        if (f.mcux != (f.width + 8 * f.hs - 1) / (8 * f.hs) || f.mcuy != (f.height + 8 * f.vs - 1) / (8 * f.vs)) return false;
-        if (f.blocks_per_mcu != (f.ncomp == 1 ? 1 : f.hs * f.vs + 2)) return false;
+        if (!jpeg_frame_ok(f) || f.n_scans < 1 || f.n_scans > 4096) return false;
         aej_jpegdec_desc &d = y.fdescs[i];
         memset(&d, 0, sizeof d);
         d.width = f.width; d.height = f.height; d.ncomp = f.ncomp; d.hs = f.hs; d.vs = f.vs; d.mcux = f.mcux; d.mcuy = f.mcuy;
         d.blocks_per_mcu = f.blocks_per_mcu; d.n_segments = 1; d.sof = f.sof; d.precision16 = f.precision16;
         memcpy(d.qt, f.qt, sizeof d.qt);
-        JdFile &F = y.ffiles[i];
-        F.blk_base = y.fz.blocks;
-        F.n_blocks = (long long)f.mcux * f.mcuy * f.blocks_per_mcu;
-        y.fz.blocks += F.n_blocks;
-        F.pw0 = f.mcux * 8 * f.hs; F.ph0 = f.mcuy * 8 * f.vs;
-        F.pw1 = f.ncomp == 3 ? f.mcux * 8 : 0; F.ph1 = f.ncomp == 3 ? f.mcuy * 8 : 0;
-        F.plane_off = y.fz.planes;
-        y.fz.planes += jp_align((long long)F.pw0 * F.ph0 + 2LL * F.pw1 * F.ph1, 256);
-        F.px_base = y.fz.px;
-        y.fz.px += (long long)f.width * f.height;
+        jpeg_recon_layout(d, y.ffiles[i], y.fz);
         int cell_level[3][64];
         for (int c = 0; c < 3; c++) for (int k = 0; k < 64; k++) cell_level[c][k] = -1;
         for (int j = 0; j < f.n_scans; j++) {
@@ -372,17 +128,7 @@ bool jpegprog_layout(const aej_jpegprog_frame *frames, const aej_jpegprog_scan *
         memcpy(d.dc, s.dc, sizeof d.dc);
         d.ac[0] = s.ac;
         JdFile &F = y.sfiles[t];
-        F.scan_len = s.data_length;
-        F.clean_off = y.sz.clean;
-        y.sz.clean += jp_align(s.data_length, 4) + 16;
-        F.chunk_base = y.sz.chunks;
-        F.n_chunks = (s.data_length + kJdChunk - 1) / kJdChunk;
-        y.sz.chunks += F.n_chunks;
-        F.seg_base = y.sz.segs;
-        y.sz.segs += s.n_segments;
-        F.slot_base = y.sz.slots;
-        F.n_slots = s.n_segments + (s.data_length * 8 + kJpUnstuffS - 1) / kJpUnstuffS + 1;
-        y.sz.slots += F.n_slots;
+        jpeg_stream_layout(s.data_length, s.n_segments, kJpUnstuffS, F, y.sz);
         JpScan &o = y.scans[t];
         o.file = order[t].file;
         o.kind = s.ss == 0 ? (s.ah ? kJpDcRefine : kJpDcFirst) : (s.ah ? kJpAcRefine : kJpAcFirst);
@@ -404,27 +150,25 @@ bool jpegprog_layout(const aej_jpegprog_frame *frames, const aej_jpegprog_scan *
 
 unsigned long long jpegprog_carve(void *base, const JpLayout &y, JpBufs &w)
 {
-    unsigned long long off = 0;
-    auto take = [&](unsigned long long bytes) { void *p = base ? (char *)base + off : nullptr; off += (bytes + 255) / 256 * 256; return p; };
+    Carver c(base);
     const size_t ns = y.scans.size(), nf = y.ffiles.size();
-    w.blob = take(jpegprog_blob(y, nullptr));
-    char *q = (char *)w.blob;
-    auto part = [&](size_t bytes) { char *r = q; if (q) q += (bytes + 255) / 256 * 256; return (void *)r; };
-    w.s.files = (JdFile *)part(sizeof(JdFile) * ns);
-    w.s.descs = (aej_jpegdec_desc *)part(sizeof(aej_jpegdec_desc) * ns);
-    w.scans = (JpScan *)part(sizeof(JpScan) * ns);
-    w.items = (JpItem *)part(sizeof(JpItem) * y.items.size());
-    w.f.files = (JdFile *)part(sizeof(JdFile) * nf);
-    w.f.descs = (aej_jpegdec_desc *)part(sizeof(aej_jpegdec_desc) * nf);
-    w.s.cnt = (int *)take(y.sz.chunks * 3 * 4);
-    w.s.pre = (long long *)take(y.sz.chunks * 3 * 8);
-    w.s.clean_len = (long long *)take(ns * 8);
-    w.s.segs = (JdSeg *)take(y.sz.segs * sizeof(JdSeg));
-    w.s.clean = (unsigned char *)take(y.sz.clean);
-    w.sstatus = (int *)take(ns * 4);
-    w.f.coef = (short *)take(y.fz.blocks * 128);
-    w.f.planes = (unsigned char *)take(y.fz.planes);
-    return off;
+    w.blob = c.take<char>(jpegprog_blob(y, nullptr));
+    Carver b(w.blob);                                  // the parts of the upload, as jpegprog_blob packs them
+    w.s.files = b.take<JdFile>(ns);
+    w.s.descs = b.take<aej_jpegdec_desc>(ns);
+    w.scans = b.take<JpScan>(ns);
+    w.items = b.take<JpItem>(y.items.size());
+    w.f.files = b.take<JdFile>(nf);
+    w.f.descs = b.take<aej_jpegdec_desc>(nf);
+    w.s.cnt = c.take<int>(y.sz.chunks * 3);
+    w.s.pre = c.take<long long>(y.sz.chunks * 3);
+    w.s.clean_len = c.take<long long>(ns);
+    w.s.segs = c.take<JdSeg>(y.sz.segs);
+    w.s.clean = c.take<unsigned char>(y.sz.clean);
+    w.sstatus = c.take<int>(ns);
+    w.f.coef = c.take<short>(y.fz.blocks * 64);
+    w.f.planes = c.take<unsigned char>(y.fz.planes);
+    return c.bytes();
 }
 
 // the one upload: per-scan streams and descriptors, scans, work items, per-file layout and descriptors (each part 256-byte aligned)

@@ -54,16 +54,10 @@ def _check_subsampling(s) -> int:
     raise ValueError(f"subsampling {s!r}: '4:4:4', '4:2:2', '4:2:0' or 0, 1, 2 required")
 
 
-def _check_optimize(o) -> bool:
-    if not isinstance(o, (bool, np.bool_)):
-        raise TypeError(f"optimize {o!r}: a bool required")
-    return bool(o)
-
-
-def _check_progressive(p) -> bool:
-    if not isinstance(p, (bool, np.bool_)):
-        raise TypeError(f"progressive {p!r}: a bool required")
-    return bool(p)
+def _check_bool(name, v) -> bool:
+    if not isinstance(v, (bool, np.bool_)):
+        raise TypeError(f"{name} {v!r}: a bool required")
+    return bool(v)
 
 
 def headers(quality: int, H: int, W: int, subsampling="4:2:0") -> bytes:
@@ -137,8 +131,8 @@ class _Encoded:
     def __init__(self, ctx, x_u8, qualities, want_bytes, subsampling=2, optimize=False, progressive=False):
         t, lib = ctx.torch, ctx.lib
         self.ctx, self.qualities = ctx, [_check_quality(q) for q in qualities]
-        self.ss, self.opt = ss, opt = _check_subsampling(subsampling), int(_check_optimize(optimize))
-        self.prog = prog = _check_progressive(progressive)      # a progressive file's tables are always its own: optimize changes nothing
+        self.ss, self.opt = ss, opt = _check_subsampling(subsampling), int(_check_bool("optimize", optimize))
+        self.prog = prog = _check_bool("progressive", progressive)      # a progressive file's tables are always its own: optimize changes nothing
         if not self.qualities:
             raise ValueError("at least one quality required")
         B, H, W = (int(v) for v in x_u8.shape[:3])
@@ -194,9 +188,9 @@ def encode_decode(ctx, x_u8, qualities, want_bytes=False, subsampling=2, optimiz
 
 
 def workspace_bytes(ctx, B, H, W, n_q, subsampling=2, optimize=False, progressive=False) -> int:
-    if _check_progressive(progressive):
+    if _check_bool("progressive", progressive):
         return int(ctx.lib.aej_jfif_workspace_bytes_prog(B, H, W, n_q, _check_subsampling(subsampling)))
-    return int(ctx.lib.aej_jfif_workspace_bytes_opt(B, H, W, n_q, _check_subsampling(subsampling), int(_check_optimize(optimize))))
+    return int(ctx.lib.aej_jfif_workspace_bytes_opt(B, H, W, n_q, _check_subsampling(subsampling), int(_check_bool("optimize", optimize))))
 
 
 def standard_jpeg_many(x, quality: int, device: int = 0, subsampling="4:2:0", optimize: bool = False, progressive: bool = False) -> List[bytes]:
@@ -205,7 +199,7 @@ def standard_jpeg_many(x, quality: int, device: int = 0, subsampling="4:2:0", op
     "4:2:0" or 0, 1, 2 (ValueError otherwise); optimize: a bool (TypeError otherwise) -- per file the Huffman tables built from its
     own symbols; progressive: a bool (TypeError otherwise) -- the progressive (SOF2) file of libjpeg's ten scans, whose tables are
     always its own, so optimize does not change its bytes."""
-    q, ss, opt, prog = _check_quality(quality), _check_subsampling(subsampling), _check_optimize(optimize), _check_progressive(progressive)
+    q, ss, opt, prog = _check_quality(quality), _check_subsampling(subsampling), _check_bool("optimize", optimize), _check_bool("progressive", progressive)
     ctx = get_context(device)
     return _Encoded(ctx, _to_u8(ctx, x), [q], True, ss, opt, prog).files()[0]
 
@@ -215,25 +209,41 @@ def standard_jpeg_batch(x, qualities: Sequence[int], device: int = 0, subsamplin
     Colour, down-sampling and DCT run once per image for all the qualities.  subsampling, optimize, progressive: as standard_jpeg_many
     (with progressive the sizes are those of the progressive files; the pixels do not change)."""
     qualities = [_check_quality(q) for q in qualities]
-    ss, opt, prog = _check_subsampling(subsampling), _check_optimize(optimize), _check_progressive(progressive)
+    ss, opt, prog = _check_subsampling(subsampling), _check_bool("optimize", optimize), _check_bool("progressive", progressive)
     ctx = get_context(device)
     enc = _Encoded(ctx, _to_u8(ctx, x), qualities, False, ss, opt, prog)
     return np.ascontiguousarray(enc.lengths.T.astype(np.int64)), enc.decoded()
 
 
-def parse_header(data, index: int = 0):
-    """aej_jpegdec_parse_host: the JpegDecDesc of one file's markers (host only).  Raises NotImplementedError for a valid file outside
-    the supported set and ValueError for a malformed header, both naming the file index."""
-    from ._lib import AEJ_ERR_UNSUPPORTED, JpegDecDesc, load_library
-    lib = load_library()
+def _buffer(data):
+    """bytes-like -> (a ctypes copy of it, its length); an empty input still gets an address"""
     mv = memoryview(data).cast("B")
-    buf = (ctypes.c_uint8 * len(mv)).from_buffer_copy(mv) if len(mv) else (ctypes.c_uint8 * 1)()
-    d, msg = JpegDecDesc(), ctypes.create_string_buffer(256)
-    rc = lib.aej_jpegdec_parse_host(ctypes.addressof(buf), len(mv), ctypes.addressof(d), ctypes.addressof(msg), 256)
+    return ((ctypes.c_uint8 * len(mv)).from_buffer_copy(mv) if len(mv) else (ctypes.c_uint8 * 1)()), len(mv)
+
+
+def _refuse(rc, msg, index):
+    """a parser's return code and message -> NotImplementedError (AEJ_ERR_UNSUPPORTED) or ValueError naming the file; nothing for 0"""
+    from ._lib import AEJ_ERR_UNSUPPORTED
     if rc == AEJ_ERR_UNSUPPORTED:
         raise NotImplementedError(f"file {index}: {msg.value.decode()}")
     if rc != 0:
         raise ValueError(f"file {index}: {msg.value.decode()}")
+
+
+def _raise_status(bad):
+    """bad: [(file index, non-zero AEJ_JPEGDEC_* status word)] in file order -> ValueError for the first; nothing when empty"""
+    from ._lib import JPEGDEC_STATUS
+    for i, code in bad:
+        raise ValueError(f"file {i}: {JPEGDEC_STATUS[code] if 0 <= code < len(JPEGDEC_STATUS) else f'status {code}'}")
+
+
+def parse_header(data, index: int = 0):
+    """aej_jpegdec_parse_host: the JpegDecDesc of one file's markers (host only).  Raises NotImplementedError for a valid file outside
+    the supported set and ValueError for a malformed header, both naming the file index."""
+    from ._lib import JpegDecDesc, load_library
+    buf, n = _buffer(data)
+    d, msg = JpegDecDesc(), ctypes.create_string_buffer(256)
+    _refuse(load_library().aej_jpegdec_parse_host(ctypes.addressof(buf), n, ctypes.addressof(d), ctypes.addressof(msg), 256), msg, index)
     return d
 
 
@@ -242,21 +252,36 @@ def parse_scans(data, index: int = 0):
     the host.  Raises ValueError for a malformed file or a scan script that violates T.81 G.1.1.1 and NotImplementedError for a valid
     file outside the supported set (an incomplete progression, arithmetic coding, a file that is not progressive, ...), both naming the
     file index."""
-    from ._lib import AEJ_ERR_UNSUPPORTED, JpegProgFrame, JpegProgScan, load_library
+    from ._lib import JpegProgFrame, JpegProgScan, load_library
     lib = load_library()
-    mv = memoryview(data).cast("B")
-    buf = (ctypes.c_uint8 * len(mv)).from_buffer_copy(mv) if len(mv) else (ctypes.c_uint8 * 1)()
+    buf, n = _buffer(data)
     frame, msg = JpegProgFrame(), ctypes.create_string_buffer(256)
-    rc = lib.aej_jpegprog_parse_host(ctypes.addressof(buf), len(mv), ctypes.addressof(frame), None, 0, ctypes.addressof(msg), 256)
+    _refuse(lib.aej_jpegprog_parse_host(ctypes.addressof(buf), n, ctypes.addressof(frame), None, 0, ctypes.addressof(msg), 256), msg, index)
     scans = (JpegProgScan * max(frame.n_scans, 1))()
-    if rc == 0:
-        rc = lib.aej_jpegprog_parse_host(ctypes.addressof(buf), len(mv), ctypes.addressof(frame), ctypes.addressof(scans), frame.n_scans,
-                                         ctypes.addressof(msg), 256)
-    if rc == AEJ_ERR_UNSUPPORTED:
-        raise NotImplementedError(f"file {index}: {msg.value.decode()}")
-    if rc != 0:
-        raise ValueError(f"file {index}: {msg.value.decode()}")
+    _refuse(lib.aej_jpegprog_parse_host(ctypes.addressof(buf), n, ctypes.addressof(frame), ctypes.addressof(scans), frame.n_scans,
+                                        ctypes.addressof(msg), 256), msg, index)
     return frame, list(scans)
+
+
+def _parse_sources(files, progressive=True, transcoder=False, start=0):
+    """Parse every file once, telling baseline from progressive: yields (i, is_progressive, JpegDecDesc | (JpegProgFrame, scans), view)
+    file by file, i counting from start.  progressive=False refuses progressive files the way standard_jpeg_decode_many does without
+    its keyword; transcoder=True refuses what the transcoder does not take.  Every refusal names the file."""
+    for i, f in enumerate(files, start):
+        try:
+            d, is_prog = parse_header(f, i), False
+        except NotImplementedError as e:
+            if "progressive JPEG (SOF2)" not in str(e):
+                raise
+            if not progressive:
+                raise NotImplementedError(f"{e}; pass progressive=True to standard_jpeg_decode_many") from None
+            d, is_prog = parse_scans(f, i), True
+        frame = d[0] if is_prog else d
+        if transcoder and frame.ncomp != 3:
+            raise NotImplementedError(f"file {i}: a single-component (grey) file: the transcoder takes three-component files")
+        if transcoder and frame.precision16:
+            raise NotImplementedError(f"file {i}: a 16-bit quantisation table: the transcoder writes 8-bit tables")
+        yield i, is_prog, d, memoryview(f).cast("B")
 
 
 def _stage(ctx, views, pieces):
@@ -324,27 +349,19 @@ def standard_jpeg_decode_many(files, device: int = 0, progressive: bool = False)
     ValueError naming the file); the scans cross in one copy per kind and are un-stuffed, Huffman-decoded and reconstructed on the
     device.  A file whose scan is malformed raises ValueError naming its index and the reason (the per-file status words are read back
     once per kind).  There is no CPU fallback."""
-    from ._lib import JPEGDEC_STATUS
     files = list(files)
     if not files:
         raise ValueError("standard_jpeg_decode_many needs at least one file")
     n = len(files)
-    parsed, views, base_idx, prog_idx = [None] * n, [], [], []
-    for i, f in enumerate(files):
-        try:
-            parsed[i] = parse_header(f, i)
-            base_idx.append(i)
-        except NotImplementedError as e:
-            if "progressive JPEG (SOF2)" not in str(e):
-                raise
-            if not progressive:
-                raise NotImplementedError(f"{e}; pass progressive=True to standard_jpeg_decode_many") from None
-            parsed[i] = parse_scans(f, i)
-            prog_idx.append(i)
-        views.append(memoryview(f).cast("B"))
+    parsed, views, base_idx, prog_idx, shapes = [], [], [], [], []
+    for i, is_prog, d, mv in _parse_sources(files, progressive):
+        parsed.append(d)
+        views.append(mv)
+        (prog_idx if is_prog else base_idx).append(i)
+        frame = d[0] if is_prog else d
+        shapes.append((frame.height, frame.width))
     ctx = get_context(device)
     t = ctx.torch
-    shapes = [(d.height, d.width) for d in (p if i in set(base_idx) else p[0] for i, p in enumerate(parsed))]
     out_off = np.zeros(n, np.int64)
     opos = 0
     for i, (h, w) in enumerate(shapes):
@@ -355,10 +372,7 @@ def standard_jpeg_decode_many(files, device: int = 0, progressive: bool = False)
     for idx, run in ((base_idx, _decode_baseline), (prog_idx, _decode_progressive)):
         if idx:
             st[idx] = run(ctx, idx, parsed, views, out, out_off).cpu().numpy()      # the one read-back of the per-file status words
-    for i in np.flatnonzero(st):
-        code = int(st[i])
-        reason = JPEGDEC_STATUS[code] if 0 <= code < len(JPEGDEC_STATUS) else f"status {code}"
-        raise ValueError(f"file {int(i)}: {reason}")
+    _raise_status((int(i), int(st[i])) for i in np.flatnonzero(st))
     return [out[int(o):int(o) + h * w * 3].view(h, w, 3) for o, (h, w) in zip(out_off, shapes)]
 
 
@@ -370,12 +384,6 @@ def decode_sync_rounds(device: int = 0) -> int:
 
 
 # ---- lossless transcode -------------------------------------------------------------------------------------------------------------
-def _check_bool(name, v) -> bool:
-    if not isinstance(v, (bool, np.bool_)):
-        raise TypeError(f"{name} {v!r}: a bool required")
-    return bool(v)
-
-
 def marker_segments(data, index: int = 0):
     """[(marker, start, end)] of the marker segments between SOI and the first SOS of one file: data[start:end] is the whole segment,
     FF xx and its length included (host only).  ValueError naming the file for bytes that are not such a sequence."""
@@ -420,38 +428,28 @@ def metadata_segments(data, index: int = 0) -> bytes:
     return b"".join(bytes(mv[a:b]) for m, a, b in marker_segments(mv, index) if _is_metadata(m))
 
 
-def _parse_any(f, i):
-    """-> (is_progressive, JpegDecDesc | (JpegProgFrame, scans)); refuses what the transcoder does not take, naming the file"""
-    try:
-        d, prog = parse_header(f, i), False
-        frame = d
-    except NotImplementedError as e:
-        if "progressive JPEG (SOF2)" not in str(e):
-            raise
-        d, prog = parse_scans(f, i), True
-        frame = d[0]
-    if frame.ncomp != 3:
-        raise NotImplementedError(f"file {i}: a single-component (grey) file: the transcoder takes three-component files")
-    if frame.precision16:
-        raise NotImplementedError(f"file {i}: a 16-bit quantisation table: the transcoder writes 8-bit tables")
-    return prog, d
+def _prefix(data, index, transform, trim, headers):
+    """transcode_prefix (transform None) and transform_prefix: headers(lib, frame pointers and density, output buffer and capacity)
+    calls the caller's own ABI entry"""
+    from ._lib import load_library
+    (_, is_prog, d, mv), = _parse_sources([data], transcoder=True, start=index)
+    frame = d[0] if is_prog else d
+    if transform is not None:
+        _transform_geometry(index, frame.height, frame.width, frame.hs, frame.vs, _check_transform(transform, index), trim)
+    dens = (ctypes.c_uint16 * 3)(*_jfif_density(mv, marker_segments(mv, index)))
+    buf = (ctypes.c_uint8 * 512)()
+    n = headers(load_library(), (None if is_prog else ctypes.addressof(frame), ctypes.addressof(frame) if is_prog else None, ctypes.addressof(dens)),
+                (ctypes.addressof(buf), 512))
+    if n < 0:
+        raise ValueError(f"file {index}: the library refuses its descriptor ({n})")
+    return bytes(buf[:n])
 
 
 def transcode_prefix(data, progressive: bool = False, index: int = 0) -> bytes:
     """The bytes SOI .. end of SOF0 / SOF2 that standard_jpeg_transcode_many writes for one file (aej_jfif_transcode_headers_host,
     host only): JFIF APP0 with the source's density, its quantisation tables, its frame header."""
-    from ._lib import load_library
-    progressive = _check_progressive(progressive)
-    is_prog, d = _parse_any(data, index)
-    mv = memoryview(data).cast("B")
-    dens = (ctypes.c_uint16 * 3)(*_jfif_density(mv, marker_segments(mv, index)))
-    frame = d[0] if is_prog else d
-    buf = (ctypes.c_uint8 * 512)()
-    n = load_library().aej_jfif_transcode_headers_host(None if is_prog else ctypes.addressof(frame), ctypes.addressof(frame) if is_prog else None,
-                                                       ctypes.addressof(dens), int(progressive), ctypes.addressof(buf), 512)
-    if n < 0:
-        raise ValueError(f"file {index}: the library refuses its descriptor ({n})")
-    return bytes(buf[:n])
+    progressive = _check_bool("progressive", progressive)
+    return _prefix(data, index, None, False, lambda lib, src, dst: lib.aej_jfif_transcode_headers_host(*src, int(progressive), *dst))
 
 
 def splice_metadata(out: bytes, meta: bytes) -> bytes:
@@ -538,20 +536,9 @@ def transform_prefix(data, transform, progressive: bool = False, trim: bool = Fa
     """The bytes SOI .. end of SOF0 / SOF2 that standard_jpeg_transform_many writes for one file under one transform name
     (aej_jfif_transform_headers_host, host only): transcode_prefix with the output's size and sampling and, for a transposing
     transform, every quantisation table transposed."""
-    from ._lib import load_library
-    progressive, trim = _check_progressive(progressive), _check_bool("trim", trim)
-    is_prog, d = _parse_any(data, index)
-    frame = d[0] if is_prog else d
-    _transform_geometry(index, frame.height, frame.width, frame.hs, frame.vs, _check_transform(transform, index), trim)
-    mv = memoryview(data).cast("B")
-    dens = (ctypes.c_uint16 * 3)(*_jfif_density(mv, marker_segments(mv, index)))
-    buf = (ctypes.c_uint8 * 512)()
-    n = load_library().aej_jfif_transform_headers_host(None if is_prog else ctypes.addressof(frame), ctypes.addressof(frame) if is_prog else None,
-                                                       ctypes.addressof(dens), int(progressive), TRANSFORMS.index(transform), int(trim),
-                                                       ctypes.addressof(buf), 512)
-    if n < 0:
-        raise ValueError(f"file {index}: the library refuses its descriptor ({n})")
-    return bytes(buf[:n])
+    progressive, trim = _check_bool("progressive", progressive), _check_bool("trim", trim)
+    return _prefix(data, index, transform, trim, lambda lib, src, dst: lib.aej_jfif_transform_headers_host(
+        *src, int(progressive), TRANSFORMS.index(transform), int(trim), *dst))
 
 
 def standard_jpeg_transform_many(files, transform, progressive: bool = False, trim: bool = False, device: int = 0,
@@ -615,14 +602,13 @@ def standard_jpeg_transcode_many(files, progressive: bool = False, device: int =
 def _transcode_many(files, progressive, device, keep_metadata, names, trim, exif):
     """the transcode (names None and not exif) and the transform: names[i] is file i's transform, exif takes it from the file"""
     global _last_transcode_groups
-    from ._lib import JPEGDEC_STATUS, JpegDecDesc, JpegProgFrame, JpegProgScan
+    from ._lib import JpegDecDesc, JpegProgFrame, JpegProgScan
     n = len(files)
     names = ["none"] * n if names is None else names
     views, parsed, base_idx, prog_idx, density, meta = [], [None] * n, [], [], [None] * n, [b""] * n
-    for i, f in enumerate(files):
-        is_prog, parsed[i] = _parse_any(f, i)
+    for i, is_prog, d, mv in _parse_sources(files, transcoder=True):
+        parsed[i] = d
         (prog_idx if is_prog else base_idx).append(i)
-        mv = memoryview(f).cast("B")
         views.append(mv)
         segs = marker_segments(mv, i)
         density[i] = _jfif_density(mv, segs)
@@ -681,10 +667,7 @@ def _transcode_many(files, progressive, device, keep_metadata, names, trim, exif
     ctx.check(rc)
     _last_transcode_groups = int(groups.value)
     st = status.cpu().numpy()                       # the one read-back of the per-file status words
-    bad = sorted((order[int(k)], int(st[k])) for k in np.flatnonzero(st))
-    if bad:
-        i, code = bad[0]
-        raise ValueError(f"file {i}: {JPEGDEC_STATUS[code] if 0 <= code < len(JPEGDEC_STATUS) else f'status {code}'}")
+    _raise_status(sorted((order[int(k)], int(st[k])) for k in np.flatnonzero(st)))
     blob = out[:int(total.value)].cpu().numpy().tobytes()
     res = [None] * n
     for k, (o, m) in enumerate(zip(offsets.cpu().tolist(), lengths.cpu().tolist())):

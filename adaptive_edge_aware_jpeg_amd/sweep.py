@@ -310,8 +310,8 @@ def sweep(images, color_spaces: Sequence[str] = ("YCbCr",), quality_ranges: Sequ
     if lpips is not None:
         for i, (h, w) in enumerate(shapes):
             _lpips.check_size(h, w, f"image {i}")
-    std_ss, std_opt = _std._check_subsampling(standard_subsampling), _std._check_optimize(standard_optimize)
-    std_prog = _std._check_progressive(standard_progressive)
+    std_ss, std_opt = _std._check_subsampling(standard_subsampling), _std._check_bool("optimize", standard_optimize)
+    std_prog = _std._check_bool("progressive", standard_progressive)
     if standard_qualities is None and (std_ss != 2 or std_opt or std_prog):
         raise ValueError("standard_subsampling / standard_optimize / standard_progressive need standard_qualities")
     if standard_qualities is not None:

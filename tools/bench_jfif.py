@@ -103,10 +103,10 @@ def run_route(fn):
 
 
 def worker(a):
-    """--worker: serve one route per line of standard input, answer "@@ <ms> <bytes>" (the other side of --ab: a process that imported
-    the package of another checkout through --root)"""
+    """--worker: name the routes this package has ("@@ ready a,b,..."), then serve one route per line of standard input, answer
+    "@@ <ms> <bytes>" (the other side of --ab: a process that imported the package of another checkout through --root)"""
     routes, _ = transcode_routes(a)
-    print("@@ ready", flush=True)
+    print("@@ ready " + ",".join(routes), flush=True)
     for line in sys.stdin:
         name = line.strip()
         if name == "quit":
@@ -138,8 +138,8 @@ def transcode(a):
                     return line.split()[1:]
             raise RuntimeError("the --ab worker ended")
 
-        answer()
-        sides["parent"] = [k for k in routes if not k.startswith(("transcode", "transform"))]
+        has = answer()[1].split(",")                   # the routes the other checkout's package offers
+        sides["parent"] = [k for k in routes if k in has]
 
     def ask(name):
         child.stdin.write(name + "\n")
