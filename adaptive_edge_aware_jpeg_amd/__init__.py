@@ -22,11 +22,11 @@ from .jpeg import EncodedBatch, Jpeg  # noqa: E402
 from .lpips import LpipsWeights  # noqa: E402
 from .quadtree import QuadNode, QuadTree  # noqa: E402
 from .settings import JpegCompressionSettings  # noqa: E402
-from .standard_jpeg import (exif_orientation, standard_jpeg_batch, standard_jpeg_decode_many, standard_jpeg_many,  # noqa: E402
+from .standard_jpeg import (draft_scale, exif_orientation, standard_jpeg_batch, standard_jpeg_decode_many, standard_jpeg_many,  # noqa: E402
                             standard_jpeg_transcode_many, standard_jpeg_transform_many)
 from .sweep import SweepResult, reference_grid, sweep  # noqa: E402
 
 __all__ = ["Jpeg", "JpegCompressionSettings", "EncodedBatch", "Image", "EvaluationMetrics", "EdgeDetection", "QuadTree", "QuadNode",
            "convert", "apply_normalization", "get_color_spaces", "hw_queues", "set_hw_queues", "configure_hw_queues",
            "sweep", "reference_grid", "SweepResult", "LpipsWeights", "standard_jpeg_many", "standard_jpeg_batch",
-           "standard_jpeg_decode_many", "standard_jpeg_transcode_many", "standard_jpeg_transform_many", "exif_orientation"]
+           "standard_jpeg_decode_many", "standard_jpeg_transcode_many", "standard_jpeg_transform_many", "exif_orientation", "draft_scale"]

@@ -240,9 +240,13 @@ SIGNATURES = {
     "aej_jpegdec_workspace_bytes": (_U64, [_P, _P, _I]),
     "aej_jpegdec_batch": (_I, [_P, _P, _I, _P, _U64, _P, _P, _U64, _P, _P, _P, _U64]),
     "aej_jpegdec_sync_rounds": (_I64, [_P]),
+    "aej_jpegdec_workspace_bytes_scaled": (_U64, [_P, _P, _I, _P]),
+    "aej_jpegdec_batch_scaled": (_I, [_P, _P, _I, _P, _P, _U64, _P, _P, _U64, _P, _P, _P, _U64]),
     "aej_jpegprog_parse_host": (_I, [_P, _U64, _P, _P, _I, _P, _I]),
     "aej_jpegprog_workspace_bytes": (_U64, [_P, _P, _P, _I]),
     "aej_jpegprog_batch": (_I, [_P, _P, _P, _I, _P, _U64, _P, _P, _U64, _P, _P, _P, _U64]),
+    "aej_jpegprog_workspace_bytes_scaled": (_U64, [_P, _P, _P, _I, _P]),
+    "aej_jpegprog_batch_scaled": (_I, [_P, _P, _P, _I, _P, _P, _U64, _P, _P, _U64, _P, _P, _P, _U64]),
     "aej_jfif_transcode_headers_host": (_I, [_P, _P, _P, _I, _P, _I]),
     "aej_jfif_transcode_workspace_bytes": (_U64, [_P, _P, _I, _P, _P, _I, _I]),
     "aej_jfif_transcode_batch": (_I, [_P, _P, _I, _P, _U64, _P, _P, _P, _I, _P, _U64, _P, _P, _I, _P, _U64, _P, _P, _P, _P, _P, _P, _U64]),
@@ -253,6 +257,7 @@ SIGNATURES = {
     "aej_jfif_transform_batch": (_I, [_P, _P, _I, _P, _U64, _P, _P, _P, _I, _P, _U64, _P, _P, _I, _P, _I, _P, _U64, _P, _P, _P, _P, _P, _P, _U64]),
     "aej_test_jpegprog_coefs": (_I, [_P, _P, _P, _I, _P, _U64, _P, _I, _P, _U64, _P, _P, _U64]),             # include/aej_testing.h (tests only)
     "aej_test_jpegprog_coefs_host": (_I, [_P, _P, _P, _U64, _I, _P, _U64]),                                 # include/aej_testing.h (tests only)
+    "aej_test_jpegdec_idct_host": (_I, [_P, _P, _I, _P]),                                                   # include/aej_testing.h (tests only)
 }
 
 # status values of aej_inflate_batch / aej_decode_headers (include/aej.h AEJ_INFLATE_* / AEJ_HEADER_*)

@@ -295,7 +295,7 @@ int jfifprog_scan_device(hipStream_t st, const short *coefs_host, long long n, i
 #include "jpegdec_core.h"
 
 namespace aej {
-struct JdBufSizes { long long chunks, segs, slots, blocks, clean, planes, px; };      // totals over the files of one call
+struct JdBufSizes { long long chunks, segs, slots, blocks, clean, planes, px, grp[3]; };      // totals over the files of one call (grp: JdFile::grp_base)
 struct JdBufs {
     JdFile *files; aej_jpegdec_desc *descs; int *last_change;      // one upload: files, descriptors, the "last round that changed" word
     int *cnt; long long *pre, *clean_len; JdSeg *segs; unsigned char *clean; JdSlots sl; short *coef; unsigned char *planes;
@@ -316,9 +316,12 @@ bool jpeg_frame_ok(const D &e)
 bool jpegdec_descs_ok(const aej_jpegdec_desc *descs, int n);      // n >= 1 descriptors aej_jpegdec_parse_host wrote
 // one un-stuffing stream of len stuffed bytes and n_segments restart segments, subsequences of S bits: F's stream fields, z's totals
 void jpeg_stream_layout(long long len, int n_segments, int S, JdFile &F, JdBufSizes &z);
-// one file's coefficient blocks, sample planes and pixels (d's frame fields): F's reconstruction fields, z's totals
-void jpeg_recon_layout(const aej_jpegdec_desc &d, JdFile &F, JdBufSizes &z);
-void jpegdec_layout(const aej_jpegdec_desc *descs, int n, int S, std::vector<JdFile> &files, JdBufSizes &z);
+// one file's coefficient blocks and, decoded at scale 1 << shift, its sample planes and pixels (shift 0) or its workgroups of the
+// scaled kernel (1..3) (d's frame fields): F's reconstruction fields, z's totals
+void jpeg_recon_layout(const aej_jpegdec_desc &d, int shift, JdFile &F, JdBufSizes &z);
+inline int jpeg_scale_shift(int scale) { return scale == 1 ? 0 : scale == 2 ? 1 : scale == 4 ? 2 : scale == 8 ? 3 : -1; }      // -1: not a scale
+// shifts: log2 of every file's scale, or NULL for all at full size
+void jpegdec_layout(const aej_jpegdec_desc *descs, int n, int S, std::vector<JdFile> &files, JdBufSizes &z, const int *shifts = nullptr);
 unsigned long long jpegdec_carve(void *base, int n, const JdBufSizes &z, JdBufs &w);
 hipError_t launch_jpegdec_begin(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, const void *blob_host, unsigned long long blob_bytes,
                                 const unsigned char *scans, int S, int *status);
@@ -352,7 +355,7 @@ inline void jp_scan_units(const aej_jpegprog_frame &f, int ncomp, int comp0, int
 }
 int jpegprog_parse(const unsigned char *data, unsigned long long n, aej_jpegprog_frame &f, std::vector<aej_jpegprog_scan> &scans,
                    std::string &msg);                                                                                  // jpegparse.hip
-bool jpegprog_layout(const aej_jpegprog_frame *frames, const aej_jpegprog_scan *scans, int n, JpLayout &y);
+bool jpegprog_layout(const aej_jpegprog_frame *frames, const aej_jpegprog_scan *scans, int n, JpLayout &y, const int *shifts = nullptr);
 unsigned long long jpegprog_blob(const JpLayout &y, std::vector<unsigned char> *out);
 unsigned long long jpegprog_carve(void *base, const JpLayout &y, JpBufs &w);
 hipError_t launch_jpegprog_entropy(hipStream_t st, const JpLayout &y, const JpBufs &w, const void *blob_host, unsigned long long blob_bytes,

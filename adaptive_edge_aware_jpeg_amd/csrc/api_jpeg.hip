@@ -223,14 +223,40 @@ static int image_offset(aej_ctx *ctx, const char *fn, int i, int width, int heig
     return 0;
 }
 
-extern "C" uint64_t aej_jpegdec_workspace_bytes(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n)
+// the scales of a scaled call (NULL: every file at full size) -> log2 of each; a value that is not 1, 2, 4 or 8 is the caller's error
+static bool scale_shifts(const int *scales_host, int n, std::vector<int> &shifts, int *bad = nullptr)
 {
-    if (!ctx || !jpegdec_descs_ok(descs_host, n)) return 0;
+    shifts.assign(n > 0 ? n : 0, 0);
+    for (int i = 0; scales_host && i < n; i++)
+        if ((shifts[i] = jpeg_scale_shift(scales_host[i])) < 0) { if (bad) *bad = i; return false; }
+    return true;
+}
+static int check_scales(aej_ctx *ctx, const char *fn, const int *scales_host, int n, std::vector<int> &shifts)
+{
+    int bad = 0;
+    if (scale_shifts(scales_host, n, shifts, &bad)) return 0;
+    return fail(ctx, AEJ_ERR_ARG, "%s: file %d: scale %d (1, 2, 4 or 8)", fn, bad, scales_host[bad]);
+}
+
+static uint64_t jpegdec_workspace(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host)
+{
+    std::vector<int> shifts;
+    if (!ctx || !jpegdec_descs_ok(descs_host, n) || !scale_shifts(scales_host, n, shifts)) return 0;
     std::vector<JdFile> files;
     JdBufSizes z;
-    jpegdec_layout(descs_host, n, ctx->jd_subseq_bits, files, z);
+    jpegdec_layout(descs_host, n, ctx->jd_subseq_bits, files, z, shifts.data());
     JdBufs w;
     return jpegdec_carve(nullptr, n, z, w);
+}
+
+extern "C" uint64_t aej_jpegdec_workspace_bytes(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n)
+{
+    return jpegdec_workspace(ctx, descs_host, n, nullptr);
+}
+
+extern "C" uint64_t aej_jpegdec_workspace_bytes_scaled(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host)
+{
+    return scales_host ? jpegdec_workspace(ctx, descs_host, n, scales_host) : 0;
 }
 
 // the entropy decode of n baseline files up to the fixed point of the sync rounds: everything of aej_jpegdec_batch before the
@@ -266,27 +292,54 @@ static int jpegdec_decode(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *
     return 0;
 }
 
-extern "C" int aej_jpegdec_batch(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const uint8_t *scans, uint64_t scans_bytes,
-                                 const int64_t *scan_offsets_host, uint8_t *out, uint64_t out_bytes, const int64_t *out_offsets_host,
-                                 int32_t *status, void *workspace, uint64_t workspace_bytes)
+// aej_jpegdec_batch (scales_host NULL: every file at full size) and aej_jpegdec_batch_scaled
+static int jpegdec_batch(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs_host, int n, const int *scales_host, const uint8_t *scans,
+                         uint64_t scans_bytes, const int64_t *scan_offsets_host, uint8_t *out, uint64_t out_bytes, const int64_t *out_offsets_host,
+                         int32_t *status, void *workspace, uint64_t workspace_bytes)
 {
-    AEJ_TRY(enter(ctx, __func__));
-    if (!jpegdec_descs_ok(descs_host, n)) return fail(ctx, AEJ_ERR_ARG, "%s: no files, or a descriptor aej_jpegdec_parse_host did not write", __func__);
-    if (!scans || !scan_offsets_host || !out || !out_offsets_host || !status || !workspace) return null_buffer(ctx, __func__);
+    AEJ_TRY(enter(ctx, fn));
+    if (!jpegdec_descs_ok(descs_host, n)) return fail(ctx, AEJ_ERR_ARG, "%s: no files, or a descriptor aej_jpegdec_parse_host did not write", fn);
+    if (!scans || !scan_offsets_host || !out || !out_offsets_host || !status || !workspace) return null_buffer(ctx, fn);
+    std::vector<int> shifts;
+    AEJ_TRY(check_scales(ctx, fn, scales_host, n, shifts));
     const int S = ctx->jd_subseq_bits;
     std::vector<JdFile> files;
     JdBufSizes z;
-    jpegdec_layout(descs_host, n, S, files, z);
+    jpegdec_layout(descs_host, n, S, files, z, shifts.data());
     for (int i = 0; i < n; i++) {                            // file by file, scan before image, as the errors were always reported
         const aej_jpegdec_desc &d = descs_host[i];
-        AEJ_TRY(jpegdec_scan_offset(ctx, __func__, d, i, scans_bytes, scan_offsets_host[i], files[i]));
-        AEJ_TRY(image_offset(ctx, __func__, i, d.width, d.height, out_bytes, out_offsets_host[i], files[i]));
+        AEJ_TRY(jpegdec_scan_offset(ctx, fn, d, i, scans_bytes, scan_offsets_host[i], files[i]));
+        AEJ_TRY(image_offset(ctx, fn, i, files[i].ow, files[i].oh, out_bytes, out_offsets_host[i], files[i]));
     }
     JdBufs w;
     const unsigned long long need = jpegdec_carve(workspace, n, z, w);
     AEJ_TRY(check_workspace(ctx, need, workspace_bytes));
-    AEJ_TRY(jpegdec_decode(ctx, __func__, descs_host, n, files, z, w, scans, status));
+    AEJ_TRY(jpegdec_decode(ctx, fn, descs_host, n, files, z, w, scans, status));
     AEJ_HIP_CHECK(launch_jpegdec_finish(ctx->stream, n, z, w, S, out, status));
+    return 0;
+}
+
+extern "C" int aej_jpegdec_batch(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const uint8_t *scans, uint64_t scans_bytes,
+                                 const int64_t *scan_offsets_host, uint8_t *out, uint64_t out_bytes, const int64_t *out_offsets_host,
+                                 int32_t *status, void *workspace, uint64_t workspace_bytes)
+{
+    return jpegdec_batch(ctx, __func__, descs_host, n, nullptr, scans, scans_bytes, scan_offsets_host, out, out_bytes, out_offsets_host, status,
+                         workspace, workspace_bytes);
+}
+
+extern "C" int aej_jpegdec_batch_scaled(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host, const uint8_t *scans,
+                                        uint64_t scans_bytes, const int64_t *scan_offsets_host, uint8_t *out, uint64_t out_bytes,
+                                        const int64_t *out_offsets_host, int32_t *status, void *workspace, uint64_t workspace_bytes)
+{
+    if (!scales_host) return ctx ? null_buffer(ctx, __func__) : AEJ_ERR_ARG;
+    return jpegdec_batch(ctx, __func__, descs_host, n, scales_host, scans, scans_bytes, scan_offsets_host, out, out_bytes, out_offsets_host, status,
+                         workspace, workspace_bytes);
+}
+
+extern "C" int aej_test_jpegdec_idct_host(const int16_t *coef_host, const uint16_t *qt_host, int size, uint8_t *out_host)
+{
+    if (!coef_host || !qt_host || !out_host || (size != 1 && size != 2 && size != 4)) return AEJ_ERR_ARG;
+    jd_idct_sized(coef_host, qt_host, size, out_host, size);
     return 0;
 }
 
@@ -312,30 +365,44 @@ extern "C" int aej_jpegprog_parse_host(const uint8_t *data_host, uint64_t nbytes
     return rc;
 }
 
-extern "C" uint64_t aej_jpegprog_workspace_bytes(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n)
+static uint64_t jpegprog_workspace(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n, const int *scales_host)
 {
     JpLayout y;
-    if (!ctx || !jpegprog_layout(frames_host, scans_host, n, y)) return 0;
+    std::vector<int> shifts;
+    if (!ctx || !scale_shifts(scales_host, n, shifts) || !jpegprog_layout(frames_host, scans_host, n, y, shifts.data())) return 0;
     JpBufs w;
     return jpegprog_carve(nullptr, y, w);
 }
 
+extern "C" uint64_t aej_jpegprog_workspace_bytes(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n)
+{
+    return jpegprog_workspace(ctx, frames_host, scans_host, n, nullptr);
+}
+
+extern "C" uint64_t aej_jpegprog_workspace_bytes_scaled(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
+                                                        const int *scales_host)
+{
+    return scales_host ? jpegprog_workspace(ctx, frames_host, scans_host, n, scales_host) : 0;
+}
+
 // levels [0, n_levels) of the entropy stage, then either the reconstruction into `out` or (tests) a copy of the coefficients
 static int jpegprog_run(aej_ctx *ctx, const char *fn, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
-                        const uint8_t *data, uint64_t data_bytes, const int64_t *data_offsets_host, int n_levels, uint8_t *out, uint64_t out_bytes,
+                        const int *scales_host, const uint8_t *data, uint64_t data_bytes, const int64_t *data_offsets_host, int n_levels, uint8_t *out, uint64_t out_bytes,
                         const int64_t *out_offsets_host, int16_t *coef_out, uint64_t coef_blocks, int32_t *status, void *workspace,
                         uint64_t workspace_bytes)
 {
     if (!ctx) return AEJ_ERR_ARG;
     AEJ_TRY(refuse_in_flight(ctx, fn));
     JpLayout y;
-    if (!jpegprog_layout(frames_host, scans_host, n, y))
+    std::vector<int> shifts;
+    AEJ_TRY(check_scales(ctx, fn, scales_host, n, shifts));
+    if (!jpegprog_layout(frames_host, scans_host, n, y, shifts.data()))
         return fail(ctx, AEJ_ERR_ARG, "%s: no files, or descriptors aej_jpegprog_parse_host did not write", fn);
     if (!data || !data_offsets_host || !status || !workspace || (!out && !coef_out) || (out && !out_offsets_host))
         return null_buffer(ctx, fn);
     AEJ_TRY(jpegprog_scan_offsets(ctx, fn, y, data_bytes, data_offsets_host));
     for (int i = 0; out && i < n; i++)
-        AEJ_TRY(image_offset(ctx, fn, i, frames_host[i].width, frames_host[i].height, out_bytes, out_offsets_host[i], y.ffiles[i]));
+        AEJ_TRY(image_offset(ctx, fn, i, y.ffiles[i].ow, y.ffiles[i].oh, out_bytes, out_offsets_host[i], y.ffiles[i]));
     if (coef_out && (uint64_t)y.fz.blocks > coef_blocks) return fail(ctx, AEJ_ERR_CAPACITY, "%s: %lld coefficient blocks, room for %llu", fn, y.fz.blocks, (unsigned long long)coef_blocks);
     JpBufs w;
     const unsigned long long need = jpegprog_carve(workspace, y, w);
@@ -355,8 +422,18 @@ extern "C" int aej_jpegprog_batch(aej_ctx *ctx, const aej_jpegprog_frame *frames
                                   const int64_t *out_offsets_host, int32_t *status, void *workspace, uint64_t workspace_bytes)
 {
     if (!out) return ctx ? null_buffer(ctx, __func__) : AEJ_ERR_ARG;
-    return jpegprog_run(ctx, __func__, frames_host, scans_host, n, data, data_bytes, data_offsets_host, 1 << 30, out, out_bytes, out_offsets_host,
-                        nullptr, 0, status, workspace, workspace_bytes);
+    return jpegprog_run(ctx, __func__, frames_host, scans_host, n, nullptr, data, data_bytes, data_offsets_host, 1 << 30, out, out_bytes,
+                        out_offsets_host, nullptr, 0, status, workspace, workspace_bytes);
+}
+
+extern "C" int aej_jpegprog_batch_scaled(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
+                                         const int *scales_host, const uint8_t *data, uint64_t data_bytes, const int64_t *data_offsets_host,
+                                         uint8_t *out, uint64_t out_bytes, const int64_t *out_offsets_host, int32_t *status, void *workspace,
+                                         uint64_t workspace_bytes)
+{
+    if (!out || !scales_host) return ctx ? null_buffer(ctx, __func__) : AEJ_ERR_ARG;
+    return jpegprog_run(ctx, __func__, frames_host, scans_host, n, scales_host, data, data_bytes, data_offsets_host, 1 << 30, out, out_bytes,
+                        out_offsets_host, nullptr, 0, status, workspace, workspace_bytes);
 }
 
 extern "C" int aej_test_jpegprog_coefs(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
@@ -364,7 +441,7 @@ extern "C" int aej_test_jpegprog_coefs(aej_ctx *ctx, const aej_jpegprog_frame *f
                                        int16_t *coef_out, uint64_t coef_blocks, int32_t *status, void *workspace, uint64_t workspace_bytes)
 {
     if (!coef_out) return ctx ? null_buffer(ctx, __func__) : AEJ_ERR_ARG;
-    return jpegprog_run(ctx, __func__, frames_host, scans_host, n, data, data_bytes, data_offsets_host, n_levels, nullptr, 0, nullptr, coef_out,
+    return jpegprog_run(ctx, __func__, frames_host, scans_host, n, nullptr, data, data_bytes, data_offsets_host, n_levels, nullptr, 0, nullptr, coef_out,
                         coef_blocks, status, workspace, workspace_bytes);
 }
 

@@ -16,6 +16,10 @@
 //                   blocks the segment needs, and a segment that ends before its last block, go to the file's status
 //   k_jd_idct       one thread per real block: dequantise, islow IDCT, range limit -> sample planes
 //   k_jd_rgb        one thread per pixel: up-sampling (h2v2 / h2v1 fancy, replication when the chroma is <= 2 wide) and YCbCr -> RGB
+//   k_jd_scaled     files decoded at scale 2, 4 or 8 (Pillow's draft()) in the place of the two above: one workgroup per run of kJdRun
+//                   MCUs of one MCU row -- reduced IDCTs into LDS, colour into LDS, then the run's output rows stored as whole dwords.
+//                   No sample planes: 4:2:0 chroma comes out of a twice-as-large IDCT at luma resolution, and the one neighbour sample
+//                   the h2v1 filter of a 4:2:2 file needs on either side comes from the chroma blocks of the two adjacent MCUs
 // Bounds: every index derives from the host-computed JdFile layout; a file's reads stay inside its scan and its clean stream, decode loops
 // are bounded by their subsequence's bits, and coefficient writes by the segment's block count.
 #include <string.h>
@@ -30,6 +34,7 @@ namespace aej {
 
 constexpr int kJdThreads = 256;
 constexpr int kJdScanThreads = 1024;
+constexpr int kJdRun = 64;                 // MCUs of one MCU row that a workgroup of k_jd_scaled reconstructs
 
 // index i of the last element with (base array member) <= t, over n files
 template <long long JdFile::*M>
@@ -341,6 +346,7 @@ __global__ __launch_bounds__(kJdThreads) void k_jd_idct(const JdFile *__restrict
     if (idx >= n_blocks) return;
     const int f = jd_find_file<&JdFile::blk_base>(files, n, idx);
     const JdFile &F = files[f];
+    if (F.shift) return;                              // a scaled file: k_jd_scaled reads its coefficients
     const aej_jpegdec_desc &d = descs[f];
     const long long b = idx - F.blk_base, mcu = b / d.blocks_per_mcu;
     const int k = (int)(b % d.blocks_per_mcu), my = (int)(mcu / d.mcux), mx = (int)(mcu % d.mcux);
@@ -377,6 +383,85 @@ __global__ __launch_bounds__(kJdThreads) void k_jd_rgb(const JdFile *__restrict_
     jd_rgb(Y, jd_chroma(cb, F.pw1, d.hs, d.vs, wc, hc, y, x), jd_chroma(cr, F.pw1, d.hs, d.vs, wc, hc, y, x), o);
 }
 
+// Scaled reconstruction, coefficients -> RGB in one kernel.  Workgroup `blockIdx.x` of the launch for scale 1 << kShift is run
+// g - grp_base of its file: MCUs [g0, g0 + ng) of MCU row my.  m = 8 >> kShift samples per luma block side.
+// LDS: three sample planes of 2m rows x kJdRun * 2m columns (the widest run: two luma blocks per MCU side) and the run's RGB rows.
+// Bounds: block indices stay below the file's mcux * mcuy * blocks_per_mcu; LDS columns below ng * hs * m <= kCols for luma and
+// (ng + 2) * nc <= kCols for chroma; only bytes of pixels (y < oh, x < ow) of the file's own image are stored.
+template <int kShift>
+__global__ __launch_bounds__(kJdThreads) void k_jd_scaled(const JdFile *__restrict__ files, const aej_jpegdec_desc *__restrict__ descs, int n,
+                                                          const short *__restrict__ coef, unsigned char *__restrict__ out)
+{
+    constexpr int m = 8 >> kShift, kRows = 2 * m, kCols = kJdRun * 2 * m, kRgbStride = kCols * 3 + 4;
+    __shared__ unsigned char sy[kRows * kCols], scb[kRows * kCols], scr[kRows * kCols];
+    __shared__ __align__(4) unsigned char srgb[kRows * kRgbStride];
+    int lo = 0, hi = n - 1;                           // the last file whose first workgroup is <= blockIdx.x
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (files[mid].grp_base[kShift - 1] <= (long long)blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+    const JdFile &F = files[lo];
+    const aej_jpegdec_desc &d = descs[lo];
+    const int per_row = (d.mcux + kJdRun - 1) / kJdRun, g = (int)(blockIdx.x - F.grp_base[kShift - 1]);
+    const int my = g / per_row, g0 = (g % per_row) * kJdRun, ng = min(kJdRun, d.mcux - g0);
+    const bool color = d.ncomp == 3;
+    const int hs = d.hs, vs = d.vs, nl = color ? hs * vs : 1, nc = jd_chroma_idct_size(hs, vs, m);
+    const bool h2v1 = color && hs == 2 && vs == 1;    // the one layout whose chroma is still up-sampled
+    const int wc = (F.ow + 1) >> 1;                   // its real chroma width
+    const bool fancy = h2v1 && kShift < 3 && wc > 2;  // libjpeg: no fancy up-sampling beside a 1 x 1 IDCT, nor for <= 2 samples
+    const int c0 = fancy && g0 > 0 ? g0 - 1 : g0, c1 = fancy && g0 + ng < d.mcux ? g0 + ng + 1 : g0 + ng;      // MCUs whose chroma is needed
+    const int nY = ng * nl, nC = color ? (c1 - c0) * 2 : 0;
+    const int bw = (d.width + 7) / 8, bh = (d.height + 7) / 8;
+    for (int i = threadIdx.x; i < nY + nC; i += kJdThreads) {
+        int mcu, k, c, size;
+        unsigned char *dst;
+        if (i < nY) {
+            mcu = g0 + i / nl; k = i % nl; c = 0; size = m;
+            const int ky = k / hs, kx = k % hs;
+            if (my * vs + ky >= bh || mcu * hs + kx >= bw) continue;      // dummy block of an edge MCU
+            dst = sy + ky * m * kCols + ((mcu - g0) * hs + kx) * m;
+        } else {
+            const int j = i - nY;
+            mcu = c0 + (j >> 1); c = 1 + (j & 1); k = nl + (j & 1); size = nc;
+            dst = (c == 1 ? scb : scr) + (mcu - c0) * nc;
+        }
+        const short *cf = coef + (F.blk_base + ((long long)my * d.mcux + mcu) * d.blocks_per_mcu + k) * 64;
+        if (size == m) jd_idct_sized(cf, d.qt[c], m, dst, kCols);
+        else jd_idct_sized(cf, d.qt[c], 2 * m, dst, kCols);
+    }
+    __syncthreads();
+    const int y0 = my * vs * m, x0 = g0 * hs * m;
+    const int nrows = min(vs * m, F.oh - y0), ncols = min(ng * hs * m, F.ow - x0), nbytes = ncols * 3;
+    unsigned char *img = out + F.out_off;
+    for (int p = threadIdx.x; p < nrows * ncols; p += kJdThreads) {
+        const int r = p / ncols, x = p % ncols;
+        const int a = (int)((uintptr_t)(img + ((long long)(y0 + r) * F.ow + x0) * 3) & 3);      // the row sits in LDS as it does in its dwords
+        unsigned char *o = srgb + r * kRgbStride + a + 3 * x;
+        const int Y = sy[r * kCols + x];
+        if (!color) { o[0] = o[1] = o[2] = (unsigned char)Y; continue; }
+        const unsigned char *rb = scb + r * kCols, *rr = scr + r * kCols;
+        int cb, cr;
+        if (h2v1) {
+            const int j = (x0 + x) >> 1, l = j - c0 * nc, ll = max(l - 1, 0), lr = min(l + 1, (c1 - c0) * nc - 1);
+            cb = fancy ? jd_h2v1(rb[l], rb[ll], rb[lr], x0 + x, j, wc) : rb[l];
+            cr = fancy ? jd_h2v1(rr[l], rr[ll], rr[lr], x0 + x, j, wc) : rr[l];
+        } else {
+            cb = rb[x]; cr = rr[x];
+        }
+        jd_rgb(Y, cb, cr, o);
+    }
+    __syncthreads();
+    const int nslots = (nbytes + 6) / 4;              // dwords a row can touch: up to 3 bytes of shift
+    for (int p = threadIdx.x; p < nrows * nslots; p += kJdThreads) {
+        const int r = p / nslots, k = p % nslots;
+        unsigned char *gp = img + ((long long)(y0 + r) * F.ow + x0) * 3;
+        const int a = (int)((uintptr_t)gp & 3), b0 = max(4 * k, a), b1 = min(4 * k + 4, a + nbytes);
+        const unsigned char *s = srgb + r * kRgbStride;
+        if (b1 - b0 == 4) *reinterpret_cast<unsigned *>(gp + (4 * k - a)) = *reinterpret_cast<const unsigned *>(s + 4 * k);
+        else for (int b = b0; b < b1; b++) gp[b - a] = s[b];      // the ends of a row: its own bytes only
+    }
+}
+
 // ---- host: descriptor checks, layout and launch sequence -----------------------------------------------------------------------------------
 bool jpegdec_descs_ok(const aej_jpegdec_desc *d, int n)
 {
@@ -405,26 +490,34 @@ void jpeg_stream_layout(long long len, int n_segments, int S, JdFile &F, JdBufSi
     z.slots += F.n_slots;
 }
 
-void jpeg_recon_layout(const aej_jpegdec_desc &d, JdFile &F, JdBufSizes &z)
+void jpeg_recon_layout(const aej_jpegdec_desc &d, int shift, JdFile &F, JdBufSizes &z)
 {
     F.blk_base = z.blocks;
     F.n_blocks = (long long)d.mcux * d.mcuy * d.blocks_per_mcu;
     z.blocks += F.n_blocks;
+    F.shift = shift;
+    F.ow = (d.width + (1 << shift) - 1) >> shift; F.oh = (d.height + (1 << shift) - 1) >> shift;
+    for (int s = 0; s < 3; s++) F.grp_base[s] = z.grp[s];
+    F.plane_off = z.planes;
+    F.px_base = z.px;
+    if (shift) {                                      // no sample planes, no pixels of k_jd_rgb's: workgroups of k_jd_scaled<shift>
+        F.pw0 = F.ph0 = F.pw1 = F.ph1 = 0;
+        z.grp[shift - 1] += (long long)d.mcuy * ((d.mcux + kJdRun - 1) / kJdRun);
+        return;
+    }
     F.pw0 = d.mcux * 8 * d.hs; F.ph0 = d.mcuy * 8 * d.vs;
     F.pw1 = d.ncomp == 3 ? d.mcux * 8 : 0; F.ph1 = d.ncomp == 3 ? d.mcuy * 8 : 0;
-    F.plane_off = z.planes;
     z.planes += align_up((long long)F.pw0 * F.ph0 + 2LL * F.pw1 * F.ph1, 256);
-    F.px_base = z.px;
     z.px += (long long)d.width * d.height;
 }
 
-void jpegdec_layout(const aej_jpegdec_desc *descs, int n, int S, std::vector<JdFile> &files, JdBufSizes &z)
+void jpegdec_layout(const aej_jpegdec_desc *descs, int n, int S, std::vector<JdFile> &files, JdBufSizes &z, const int *shifts)
 {
     files.assign(n, JdFile{});
     z = JdBufSizes{};
     for (int i = 0; i < n; i++) {
         jpeg_stream_layout(descs[i].scan_length, descs[i].n_segments, S, files[i], z);
-        jpeg_recon_layout(descs[i], files[i], z);
+        jpeg_recon_layout(descs[i], shifts ? shifts[i] : 0, files[i], z);
     }
 }
 
@@ -505,12 +598,24 @@ hipError_t launch_jpegdec_finish(hipStream_t st, int n, const JdBufSizes &z, con
     return launch_jpegdec_recon(st, n, z, w, out);
 }
 
-// coefficients (natural order, MCU order) -> RGB, for n files
+// the files of a call that decode at scale 2, 4, 8: one launch per scale present (JdFile::shift and ::grp_base pick a file's kernel
+// and workgroups; the layout inside the kernel follows the file's sampling factors)
+static hipError_t launch_jpegdec_recon_scaled(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, unsigned char *out)
+{
+    if (z.grp[0] > 0) hipLaunchKernelGGL(k_jd_scaled<1>, dim3((unsigned)z.grp[0]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
+    if (z.grp[1] > 0) hipLaunchKernelGGL(k_jd_scaled<2>, dim3((unsigned)z.grp[1]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
+    if (z.grp[2] > 0) hipLaunchKernelGGL(k_jd_scaled<3>, dim3((unsigned)z.grp[2]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
+    return hipGetLastError();
+}
+
+// coefficients (natural order, MCU order) -> RGB, for n files: the full-size ones (z.px counts their pixels), then the scaled ones
 hipError_t launch_jpegdec_recon(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, unsigned char *out)
 {
-    hipLaunchKernelGGL(k_jd_idct, dim3(jd_grid(z.blocks)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.blocks, w.coef, w.planes);
-    hipLaunchKernelGGL(k_jd_rgb, dim3(jd_grid(z.px)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.px, w.planes, out);
-    return hipGetLastError();
+    if (z.px > 0) {
+        hipLaunchKernelGGL(k_jd_idct, dim3(jd_grid(z.blocks)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.blocks, w.coef, w.planes);
+        hipLaunchKernelGGL(k_jd_rgb, dim3(jd_grid(z.px)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.px, w.planes, out);
+    }
+    return launch_jpegdec_recon_scaled(st, n, z, w, out);
 }
 
 }  // namespace aej

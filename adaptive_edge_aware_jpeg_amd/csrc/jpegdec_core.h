@@ -26,8 +26,11 @@ struct JdFile {
     long long blk_base, n_blocks;      // coefficient blocks, MCU order
     long long plane_off;               // byte offset of the sample planes
     int pw0, ph0, pw1, ph1;            // luma and chroma plane shapes (whole MCUs)
-    long long px_base;                 // first output pixel of the call's pixel range
+    long long px_base;                 // first output pixel of the call's pixel range (a scaled file has none: k_jd_rgb never meets it)
     long long out_off;                 // byte offset of the RGB output
+    int shift;                         // log2 of the decode scale: 0 full size (k_jd_idct, k_jd_rgb), 1..3 scale 2, 4, 8 (k_jd_scaled)
+    int ow, oh;                        // output shape: ceil(width / scale), ceil(height / scale)
+    long long grp_base[3];             // [shift - 1]: first workgroup of the file in k_jd_scaled<shift>'s grid (kJdRun MCUs of one MCU row each)
 };
 
 // one restart segment: written by the un-stuffing scatter (start) and k_jd_segments (the rest)
@@ -188,7 +191,7 @@ AEJ_HD inline unsigned char jd_range_limit(long long x)      // libjpeg's masked
 }
 
 // one block: coefficients (natural order) times the quantisers -> 8 x 8 samples at dst (row stride `stride`)
-AEJ_HD inline void jd_idct_block(const short *c, const uint16_t *qt, unsigned char *dst, long long stride)
+AEJ_HD inline __attribute__((always_inline)) void jd_idct_block(const short *c, const uint16_t *qt, unsigned char *dst, long long stride)
 {
     long long d[64];
     for (int j = 0; j < 64; j++) d[j] = (long long)c[j] * qt[j];
@@ -196,6 +199,99 @@ AEJ_HD inline void jd_idct_block(const short *c, const uint16_t *qt, unsigned ch
     for (int r = 0; r < 8; r++) jd_idct8<false>(d + r * 8, 1);
     for (int r = 0; r < 8; r++)
         for (int cc = 0; cc < 8; cc++) dst[r * stride + cc] = jd_range_limit(d[r * 8 + cc]);
+}
+
+// ---- reduced-size reconstruction (scale 2, 4, 8: libjpeg-turbo's jidctred.c, as Pillow's draft() selects it) ------------------------
+// The two passes differ in width.  Pass 1 multiplies coefficient * quantiser products (|d| < 2^31) by constants whose absolute values
+// sum to less than 2^17, so its sums need up to 48 bits: 64-bit arithmetic.  Of a pass-2 result only (x >> k) & 1023 with k <= 20
+// survives jd_range_limit, i.e. the sum modulo 2^30.  The sum is an integer-linear form of the pass-1 results, so it is right modulo
+// 2^32 when those are kept modulo 2^32 and the arithmetic wraps: pass 1 stores the low 32 bits, pass 2 runs in uint32.
+AEJ_HD inline unsigned jd_descale_lo(long long x, int n) { return (unsigned)((x + (1LL << (n - 1))) >> n); }
+AEJ_HD inline unsigned char jd_limit_u32(unsigned sum, int n) { return jd_range_limit((long long)((sum + (1u << (n - 1))) >> n)); }
+
+// 4 x 4 samples of one block: row 4 and column 4 of the coefficients are never read
+AEJ_HD inline void jd_idct4_block(const short *c, const uint16_t *qt, unsigned char *dst, long long stride)
+{
+    unsigned w[4][7];                                 // pass 1: columns 0..3, 5..7 (index 4..6)
+#pragma unroll
+    for (int i = 0; i < 7; i++) {
+        const int col = i < 4 ? i : i + 1;
+        long long d[8];
+#pragma unroll
+        for (int r = 0; r < 8; r++) d[r] = r == 4 ? 0 : (long long)((int)c[r * 8 + col] * (int)qt[r * 8 + col]);
+        const long long t0 = d[0] * 16384, t2 = d[2] * 15137 - d[6] * 6270, t10 = t0 + t2, t12 = t0 - t2;
+        const long long o0 = -d[7] * 1730 + d[5] * 11893 - d[3] * 17799 + d[1] * 8697;
+        const long long o2 = -d[7] * 4176 - d[5] * 4926 + d[3] * 7373 + d[1] * 20995;
+        w[0][i] = jd_descale_lo(t10 + o2, 12); w[1][i] = jd_descale_lo(t12 + o0, 12);
+        w[2][i] = jd_descale_lo(t12 - o0, 12); w[3][i] = jd_descale_lo(t10 - o2, 12);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; r++) {                     // pass 2: w[r][4..6] are columns 5..7
+        const unsigned t0 = w[r][0] * 16384u, t2 = w[r][2] * 15137u - w[r][5] * 6270u, t10 = t0 + t2, t12 = t0 - t2;
+        const unsigned o0 = w[r][4] * 11893u - w[r][6] * 1730u - w[r][3] * 17799u + w[r][1] * 8697u;
+        const unsigned o2 = w[r][3] * 7373u - w[r][6] * 4176u - w[r][4] * 4926u + w[r][1] * 20995u;
+        unsigned char *o = dst + r * stride;
+        o[0] = jd_limit_u32(t10 + o2, 19); o[1] = jd_limit_u32(t12 + o0, 19);
+        o[2] = jd_limit_u32(t12 - o0, 19); o[3] = jd_limit_u32(t10 - o2, 19);
+    }
+}
+
+// 2 x 2 samples of one block: only rows and columns 0, 1, 3, 5, 7 are read
+AEJ_HD inline void jd_idct2_block(const short *c, const uint16_t *qt, unsigned char *dst, long long stride)
+{
+    unsigned w[2][5];
+#pragma unroll
+    for (int i = 0; i < 5; i++) {
+        const int col = i < 2 ? i : 2 * i - 1;        // 0, 1, 3, 5, 7
+        long long d[5];
+#pragma unroll
+        for (int j = 0; j < 5; j++) {
+            const int k = (j < 2 ? j : 2 * j - 1) * 8 + col;
+            d[j] = (long long)((int)c[k] * (int)qt[k]);
+        }
+        const long long t10 = d[0] * 32768, t0 = -d[4] * 5906 + d[3] * 6967 - d[2] * 10426 + d[1] * 29692;
+        w[0][i] = jd_descale_lo(t10 + t0, 13); w[1][i] = jd_descale_lo(t10 - t0, 13);
+    }
+#pragma unroll
+    for (int r = 0; r < 2; r++) {
+        const unsigned t10 = w[r][0] * 32768u, t0 = w[r][3] * 6967u - w[r][4] * 5906u - w[r][2] * 10426u + w[r][1] * 29692u;
+        dst[r * stride] = jd_limit_u32(t10 + t0, 20);
+        dst[r * stride + 1] = jd_limit_u32(t10 - t0, 20);
+    }
+}
+
+// The 8 x 8 block behind a call.  jd_idct_block itself is always inlined, so that k_jd_idct compiles as it did when that was its
+// only caller; inlined into k_jd_scaled<1> beside the 4 x 4 one it costs that kernel half its occupancy (measured on 64 4K 4:2:0
+// files: 2.6 ms against 1.25 ms through this call).
+AEJ_HD __attribute__((noinline)) inline void jd_idct_block_call(const short *c, const uint16_t *qt, unsigned char *dst, long long stride)
+{
+    jd_idct_block(c, qt, dst, stride);
+}
+
+// one block at IDCT size n (1, 2, 4 or 8): n x n samples at dst
+AEJ_HD inline void jd_idct_sized(const short *c, const uint16_t *qt, int n, unsigned char *dst, long long stride)
+{
+    if (n == 8) jd_idct_block_call(c, qt, dst, stride);
+    else if (n == 4) jd_idct4_block(c, qt, dst, stride);
+    else if (n == 2) jd_idct2_block(c, qt, dst, stride);
+    else dst[0] = jd_range_limit(jd_descale((long long)((int)c[0] * (int)qt[0]), 3));
+}
+
+// the IDCT size of a chroma component when luma is reconstructed at m = 8 / scale samples per block (libjpeg's
+// jpeg_calc_output_dimensions with chroma sampled 1 x 1): 2m where the luma factors are 2 x 2 -- the chroma then comes out at luma
+// resolution and is not up-sampled -- and m otherwise
+AEJ_HD inline int jd_chroma_idct_size(int hs, int vs, int m)
+{
+    int n = m;
+    while (n < 8 && (hs * m) % (n * 2) == 0 && (vs * m) % (n * 2) == 0) n *= 2;
+    return n;
+}
+
+// libjpeg's h2v1 "fancy" up-sampling of chroma sample j (of wc) with its neighbours, for output column x: jd_chroma's vs == 1 rule
+AEJ_HD inline int jd_h2v1(int cur, int left, int right, int x, int j, int wc)
+{
+    if ((x & 1) == 0) return j == 0 ? cur : (3 * cur + left + 1) >> 2;
+    return j == wc - 1 ? cur : (3 * cur + right + 2) >> 2;
 }
 
 // chroma sample for output pixel (y, x) from a plane of wc x hc real samples (row stride `stride`); hs, vs: luma sampling factors

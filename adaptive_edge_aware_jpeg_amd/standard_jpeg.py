@@ -8,7 +8,11 @@ coefficients, and so the decoded pixels, are those of the baseline file.  The de
 
 ``standard_jpeg_decode_many`` reads such files back -- any baseline file, not only this library's, and with ``progressive=True`` any
 complete progressive file -- on the device, pixel-identical to ``Image.open(file).convert("RGB")`` (csrc/jpegdec.hip, ``aej_jpegdec_*``;
-csrc/jpegprog.hip, ``aej_jpegprog_*``).
+csrc/jpegprog.hip, ``aej_jpegprog_*``).  With ``scale=2``, ``4`` or ``8`` (one value, or one per file) a file is decoded at that fraction of
+its size straight from its coefficients, through libjpeg's reduced inverse DCTs: the ``[ceil(H / s), ceil(W / s), 3]`` pixels Pillow
+returns once ``Image.draft()`` has chosen scale ``s`` -- what ``Image.thumbnail()`` starts from (``aej_jpegdec_batch_scaled``,
+``aej_jpegprog_batch_scaled``; one fused kernel, csrc/jpegdec.hip ``k_jd_scaled``).  ``draft_scale`` is ``draft()``'s choice of that
+scale for a requested size.
 
 ``standard_jpeg_transcode_many`` joins the two without touching a pixel: it Huffman-decodes existing files to their quantised
 coefficients on the device and entropy-codes the same coefficients again, as a baseline file under the file's own optimal Huffman
@@ -301,26 +305,30 @@ def _stage(ctx, views, pieces):
     return dev, off
 
 
-def _decode_baseline(ctx, idx, parsed, views, out, out_off):
-    """aej_jpegdec_batch over the files idx -> their status words (device int32)"""
+def _decode_baseline(ctx, idx, parsed, views, out, out_off, scales=None):
+    """aej_jpegdec_batch (scales None) or aej_jpegdec_batch_scaled over the files idx -> their status words (device int32)"""
     from ._lib import JpegDecDesc
     t, lib, n = ctx.torch, ctx.lib, len(idx)
     descs = (JpegDecDesc * n)(*[parsed[i] for i in idx])
     scans, scan_off = _stage(ctx, views, [(i, parsed[i].scan_offset, parsed[i].scan_length) for i in idx])
     oo = np.ascontiguousarray(out_off[idx])
     status = ctx.empty((n,), t.int32)
-    nws = int(lib.aej_jpegdec_workspace_bytes(ctx.handle, ctypes.addressof(descs), n))
+    sc = () if scales is None else (np.ascontiguousarray(scales[idx], np.int32),)
+    how = () if scales is None else (sc[0].ctypes.data,)
+    nbytes, batch = ((lib.aej_jpegdec_workspace_bytes, lib.aej_jpegdec_batch) if scales is None else
+                     (lib.aej_jpegdec_workspace_bytes_scaled, lib.aej_jpegdec_batch_scaled))
+    nws = int(nbytes(ctx.handle, ctypes.addressof(descs), n, *how))
     if nws == 0:
         raise ValueError("descriptors the library refuses")
     ws = ctx.workspace(nws)
-    ctx.check(lib.aej_jpegdec_batch(ctx.handle, ctypes.addressof(descs), n, scans.data_ptr(), ctypes.c_uint64(scans.numel()),
-                                    scan_off.ctypes.data, out.data_ptr(), ctypes.c_uint64(out.numel()), oo.ctypes.data,
-                                    status.data_ptr(), ws.data_ptr(), ctypes.c_uint64(nws)))
+    ctx.check(batch(ctx.handle, ctypes.addressof(descs), n, *how, scans.data_ptr(), ctypes.c_uint64(scans.numel()),
+                    scan_off.ctypes.data, out.data_ptr(), ctypes.c_uint64(out.numel()), oo.ctypes.data,
+                    status.data_ptr(), ws.data_ptr(), ctypes.c_uint64(nws)))
     return status
 
 
-def _decode_progressive(ctx, idx, parsed, views, out, out_off):
-    """aej_jpegprog_batch over the files idx -> their status words (device int32)"""
+def _decode_progressive(ctx, idx, parsed, views, out, out_off, scales=None):
+    """aej_jpegprog_batch (scales None) or aej_jpegprog_batch_scaled over the files idx -> their status words (device int32)"""
     from ._lib import JpegProgFrame, JpegProgScan
     t, lib, n = ctx.torch, ctx.lib, len(idx)
     frames = (JpegProgFrame * n)(*[parsed[i][0] for i in idx])
@@ -329,19 +337,56 @@ def _decode_progressive(ctx, idx, parsed, views, out, out_off):
     data, data_off = _stage(ctx, views, [(i, s.data_offset, s.data_length) for i, s in flat])
     oo = np.ascontiguousarray(out_off[idx])
     status = ctx.empty((n,), t.int32)
-    nws = int(lib.aej_jpegprog_workspace_bytes(ctx.handle, ctypes.addressof(frames), ctypes.addressof(scans), n))
+    sc = () if scales is None else (np.ascontiguousarray(scales[idx], np.int32),)
+    how = () if scales is None else (sc[0].ctypes.data,)
+    nbytes, batch = ((lib.aej_jpegprog_workspace_bytes, lib.aej_jpegprog_batch) if scales is None else
+                     (lib.aej_jpegprog_workspace_bytes_scaled, lib.aej_jpegprog_batch_scaled))
+    nws = int(nbytes(ctx.handle, ctypes.addressof(frames), ctypes.addressof(scans), n, *how))
     if nws == 0:
         raise ValueError("descriptors the library refuses")
     ws = ctx.workspace(nws)
-    ctx.check(lib.aej_jpegprog_batch(ctx.handle, ctypes.addressof(frames), ctypes.addressof(scans), n, data.data_ptr(),
-                                     ctypes.c_uint64(data.numel()), data_off.ctypes.data, out.data_ptr(), ctypes.c_uint64(out.numel()),
-                                     oo.ctypes.data, status.data_ptr(), ws.data_ptr(), ctypes.c_uint64(nws)))
+    ctx.check(batch(ctx.handle, ctypes.addressof(frames), ctypes.addressof(scans), n, *how, data.data_ptr(),
+                    ctypes.c_uint64(data.numel()), data_off.ctypes.data, out.data_ptr(), ctypes.c_uint64(out.numel()),
+                    oo.ctypes.data, status.data_ptr(), ws.data_ptr(), ctypes.c_uint64(nws)))
     return status
 
 
-def standard_jpeg_decode_many(files, device: int = 0, progressive: bool = False) -> list:
+SCALES = (1, 2, 4, 8)
+
+
+def _check_scale(s) -> int:
+    if isinstance(s, (bool, np.bool_)) or not isinstance(s, (int, np.integer)) or int(s) not in SCALES:
+        raise ValueError(f"scale {s!r}: 1, 2, 4 or 8 required")
+    return int(s)
+
+
+def _check_scales(scale, n):
+    """scale= of standard_jpeg_decode_many -> int32 [n], one of SCALES per file"""
+    if isinstance(scale, (str, bytes)) or not hasattr(scale, "__len__"):
+        return np.full(n, _check_scale(scale), np.int32)
+    if len(scale) != n:
+        raise ValueError(f"scale: {len(scale)} values for {n} files")
+    return np.array([_check_scale(s) for s in scale], np.int32).reshape(n)
+
+
+def draft_scale(width: int, height: int, size) -> int:
+    """The scale ``Image.draft(None, size)`` picks for a width x height JPEG file (host only): the largest of 8, 4, 2, 1 that is not above
+    ``min(width // size[0], height // size[1])`` -- the smallest decode that is still at least ``size`` (width, height) large, which is
+    how ``Image.thumbnail()`` chooses.  Pass it as ``scale=`` of standard_jpeg_decode_many.  ValueError for a size that is not positive."""
+    w, h = int(size[0]), int(size[1])
+    if w < 1 or h < 1 or int(width) < 1 or int(height) < 1:
+        raise ValueError(f"draft_scale: {width} x {height} file, size {tuple(size)!r}: positive sizes required")
+    ratio = min(int(width) // w, int(height) // h)
+    return next((s for s in (8, 4, 2) if s <= ratio), 1)
+
+
+def standard_jpeg_decode_many(files, device: int = 0, progressive: bool = False, scale=1) -> list:
     """Decode JPEG files on the device: -> list of uint8 [H_i, W_i, 3] tensors (views into one packed allocation), in input
     order, on the context of the current stream; element i equals ``np.asarray(Image.open(io.BytesIO(files[i])).convert("RGB"))``.
+    scale: 1, 2, 4 or 8, or a sequence of one such value per file (ValueError naming the value otherwise; a bool is refused): file i
+    is decoded at 1 / scale of its size from its coefficients (reduced inverse DCTs, no full-size image in between) and element i is
+    the [ceil(H_i / s), ceil(W_i / s), 3] image Pillow gives after ``im.draft("RGB", (W_i // s, H_i // s))`` has chosen scale s
+    (draft_scale is that choice).  scale=1 is the call as it always was.
     files: a sequence of bytes-like .jpg contents, of any sizes and of the supported layouts mixed (4:2:0, 4:2:2, 4:4:4, grey).
     Baseline files always; with ``progressive=True`` also progressive (SOF2) files whose scans complete every coefficient, mixed
     freely with baseline ones (csrc/jpegprog.hip, ``aej_jpegprog_*``) -- without it a progressive file is refused as before.  Every
@@ -353,13 +398,16 @@ def standard_jpeg_decode_many(files, device: int = 0, progressive: bool = False)
     if not files:
         raise ValueError("standard_jpeg_decode_many needs at least one file")
     n = len(files)
+    scales = _check_scales(scale, n)
     parsed, views, base_idx, prog_idx, shapes = [], [], [], [], []
     for i, is_prog, d, mv in _parse_sources(files, progressive):
         parsed.append(d)
         views.append(mv)
         (prog_idx if is_prog else base_idx).append(i)
-        frame = d[0] if is_prog else d
-        shapes.append((frame.height, frame.width))
+        frame, s = d[0] if is_prog else d, int(scales[i])
+        shapes.append((-(-frame.height // s), -(-frame.width // s)))
+    if (scales == 1).all():
+        scales = None                                # the unscaled entries, as before
     ctx = get_context(device)
     t = ctx.torch
     out_off = np.zeros(n, np.int64)
@@ -371,7 +419,7 @@ def standard_jpeg_decode_many(files, device: int = 0, progressive: bool = False)
     st = np.zeros(n, np.int64)
     for idx, run in ((base_idx, _decode_baseline), (prog_idx, _decode_progressive)):
         if idx:
-            st[idx] = run(ctx, idx, parsed, views, out, out_off).cpu().numpy()      # the one read-back of the per-file status words
+            st[idx] = run(ctx, idx, parsed, views, out, out_off, scales).cpu().numpy()      # the one read-back of the per-file status words
     _raise_status((int(i), int(st[i])) for i in np.flatnonzero(st))
     return [out[int(o):int(o) + h * w * 3].view(h, w, 3) for o, (h, w) in zip(out_off, shapes)]
 

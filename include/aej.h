@@ -438,7 +438,14 @@ AEJ_API int aej_jfif_recon_batch_prog(aej_ctx *ctx, int batch, int H, int W, int
  *   decode from a guessed state and are re-run until each one's entry state equals its predecessor's exit state; the call reads back one
  *   word every few of those rounds and returns after the last round has run.  Workspace: aej_jpegdec_workspace_bytes(ctx, descs_host, n)
  *   bytes (it depends on the context's subsequence length), 256-byte aligned.
- * aej_jpegdec_sync_rounds: sync rounds the last aej_jpegdec_batch of the context ran (0 when no segment needed more than one subsequence). */
+ * aej_jpegdec_sync_rounds: sync rounds the last aej_jpegdec_batch of the context ran (0 when no segment needed more than one subsequence).
+ * aej_jpegdec_batch_scaled / aej_jpegdec_workspace_bytes_scaled: the same calls with scales_host [n], each 1, 2, 4 or 8 (anything else:
+ *   AEJ_ERR_ARG, 0 bytes): file i is decoded at 1 / scales_host[i] of its size straight from the coefficients, as libjpeg does for
+ *   scale_num / scale_denom = 1 / scale and Pillow after Image.draft() has chosen that scale -- image i is
+ *   [ceil(height / scale)][ceil(width / scale)][3] at out_offsets_host[i].  The entropy decode is the same; the reconstruction of a
+ *   scaled file is one kernel of reduced IDCTs (4 x 4, 2 x 2, 1 x 1 for luma; 4:2:0 chroma one size larger, so it is not up-sampled)
+ *   that needs no sample planes, so the workspace is smaller.  With every scale 1 both calls are aej_jpegdec_batch and
+ *   aej_jpegdec_workspace_bytes byte for byte.  (Additions to ABI 3: no existing signature, struct or behaviour changed.) */
 enum {
     AEJ_JPEGDEC_OK = 0, AEJ_JPEGDEC_TRUNCATED = 1 /* the scan ends before the last MCU */, AEJ_JPEGDEC_BAD_CODE = 2 /* not in the table */,
     AEJ_JPEGDEC_RUN_PAST_63 = 3 /* an AC run beyond the block */, AEJ_JPEGDEC_BAD_DC = 4 /* DC category above 11 */,
@@ -472,6 +479,10 @@ AEJ_API int aej_jpegdec_batch(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, 
                               const int64_t *scan_offsets_host, uint8_t *out, uint64_t out_bytes, const int64_t *out_offsets_host,
                               int32_t *status, void *workspace, uint64_t workspace_bytes);
 AEJ_API int64_t aej_jpegdec_sync_rounds(aej_ctx *ctx);
+AEJ_API uint64_t aej_jpegdec_workspace_bytes_scaled(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host);
+AEJ_API int aej_jpegdec_batch_scaled(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host, const uint8_t *scans,
+                                     uint64_t scans_bytes, const int64_t *scan_offsets_host, uint8_t *out, uint64_t out_bytes,
+                                     const int64_t *out_offsets_host, int32_t *status, void *workspace, uint64_t workspace_bytes);
 
 /* ---- progressive JPEG files decoded on the device (standard_jpeg_decode_many(..., progressive=True)) ----------------------------------
  * SOF2 files with Huffman coding, under the frame rules of aej_jpegdec_parse_host (8-bit, 1 or 3 components, 4:4:4 / 4:2:2 / 4:2:0 /
@@ -495,7 +506,8 @@ AEJ_API int64_t aej_jpegdec_sync_rounds(aej_ctx *ctx);
  *   status as aej_jpegdec_batch (status values AEJ_JPEGDEC_*).  Every scan is un-stuffed and cut into restart segments at once; then
  *   one launch per dependency level decodes every restart segment of every scan of that level, one thread per segment (DC refinement:
  *   one thread per MCU), into the file's coefficients; the baseline path's IDCT and colour kernels finish.  A bad scan marks its file
- *   and never reads or writes outside its own bytes and its file's coefficients.  Workspace: aej_jpegprog_workspace_bytes. */
+ *   and never reads or writes outside its own bytes and its file's coefficients.  Workspace: aej_jpegprog_workspace_bytes.
+ * aej_jpegprog_batch_scaled / aej_jpegprog_workspace_bytes_scaled: with scales_host [n], as aej_jpegdec_batch_scaled. */
 typedef struct aej_jpegprog_frame {
     int32_t width, height;
     int32_t ncomp;             /* 1 or 3 */
@@ -525,6 +537,12 @@ AEJ_API uint64_t aej_jpegprog_workspace_bytes(aej_ctx *ctx, const aej_jpegprog_f
 AEJ_API int aej_jpegprog_batch(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
                                const uint8_t *data, uint64_t data_bytes, const int64_t *data_offsets_host, uint8_t *out, uint64_t out_bytes,
                                const int64_t *out_offsets_host, int32_t *status, void *workspace, uint64_t workspace_bytes);
+AEJ_API uint64_t aej_jpegprog_workspace_bytes_scaled(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
+                                                     const int *scales_host);
+AEJ_API int aej_jpegprog_batch_scaled(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
+                                      const int *scales_host, const uint8_t *data, uint64_t data_bytes, const int64_t *data_offsets_host,
+                                      uint8_t *out, uint64_t out_bytes, const int64_t *out_offsets_host, int32_t *status, void *workspace,
+                                      uint64_t workspace_bytes);
 
 /* ---- lossless transcode: existing files entropy-coded again (standard_jpeg_transcode_many) ----------------------------------------------
  * What jpegtran -optimize / -progressive do, on the device: the files are Huffman-decoded to their quantised coefficients by the stages of

@@ -38,6 +38,11 @@ AEJ_API int aej_test_jfif_prog_scan_host(const int16_t *coefs_host, int64_t n_bl
 AEJ_API int aej_test_jfif_prog_scan(aej_ctx *ctx, const int16_t *coefs_host, int64_t n_blocks, int Ss, int Se, int Ah, int Al, uint8_t *out_host,
                                     uint64_t capacity, uint64_t *out_len_host, int64_t *counts_host, int64_t *cuts_host);
 
+/* One block through the reduced inverse DCT of a scaled decode (aej_jpegdec_batch_scaled), HOST only: coef_host [64] quantised
+ * coefficients and qt_host [64] quantisers, both in natural order; size 1, 2 or 4 (AEJ_ERR_ARG otherwise); out_host gets size x size
+ * samples, row after row -- computed by the function of csrc/jpegdec_core.h that the kernel calls (jd_idct_sized). */
+AEJ_API int aej_test_jpegdec_idct_host(const int16_t *coef_host, const uint16_t *qt_host, int size, uint8_t *out_host);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,11 +2,14 @@
 markers -- Pillow's default, decoded by the self-synchronising subsequences -- and (b) with restart_marker_rows=1, against Pillow
 decoding them on a thread pool and uploading its pixels.
 
-    python tools/bench_jpeg_decode.py [--batch 64] [--repeats 3] [--threads 16] [--subseq-bits N] [--progressive] [--out FILE]
+    python tools/bench_jpeg_decode.py [--batch 64] [--repeats 3] [--threads 16] [--subseq-bits N] [--progressive] [--scale S] [--out FILE]
 
 --progressive writes the same files with progressive=True and decodes them with standard_jpeg_decode_many(..., progressive=True)
 (csrc/jpegprog.hip: one thread per restart segment and dependency level, so the files without restart markers are a serial decode
 per scan and the restart-per-row files show what the kernels do when the format allows parallelism).
+
+--scale 2 / 4 / 8 decodes at that fraction of the size on both sides: standard_jpeg_decode_many(..., scale=S) (csrc/jpegdec.hip
+k_jd_scaled) against Pillow after im.draft("RGB", (W // S, H // S)); the gigapixels per second still count the files' full-size pixels.
 
 "gpu" is standard_jpeg_decode_many: host header parsing, one copy of the scans, every device stage, the per-file status read-back;
 it ends with device uint8 [H, W, 3] tensors.  "pillow" is np.asarray(Image.open(buf).convert("RGB")) per file on --threads threads, then
@@ -43,6 +46,7 @@ def main():
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--subseq-bits", type=int, default=0, help="jpegdec_subseq_bits (0: the library's default)")
     ap.add_argument("--progressive", action="store_true", help="progressive files through csrc/jpegprog.hip")
+    ap.add_argument("--scale", type=int, default=1, choices=(1, 2, 4, 8), help="decode at 1 / scale of the size (Pillow: Image.draft)")
     ap.add_argument("--out")
     a = ap.parse_args()
     x = images(a.batch)
@@ -52,6 +56,8 @@ def main():
     gp = a.batch * H * W / 1e9
     res = {"batch": a.batch, "H": H, "W": W, "quality": 75, "subseq_bits": ctx.get_option("jpegdec_subseq_bits"),
            "pillow_threads": a.threads, "progressive": a.progressive, "cases": {}}
+    if a.scale != 1:
+        res["scale"] = a.scale
     pool = ThreadPoolExecutor(a.threads)
 
     def save(i, opts):
@@ -60,10 +66,14 @@ def main():
         return buf.getvalue()
 
     def pil_load(f):
-        return np.asarray(Image.open(io.BytesIO(f)).convert("RGB"))
+        im = Image.open(io.BytesIO(f))
+        if a.scale != 1:
+            im.draft("RGB", (W // a.scale, H // a.scale))
+        return np.asarray(im.convert("RGB"))
 
     def decode(files):
-        return A.standard_jpeg_decode_many(files, progressive=True) if a.progressive else A.standard_jpeg_decode_many(files)
+        how = dict(scale=a.scale) if a.scale != 1 else {}
+        return A.standard_jpeg_decode_many(files, progressive=True, **how) if a.progressive else A.standard_jpeg_decode_many(files, **how)
 
     for name, opts in (("no_restarts", {}), ("restart_rows_1", {"restart_marker_rows": 1})):
         if a.progressive:
