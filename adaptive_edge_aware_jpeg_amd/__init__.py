@@ -4,7 +4,8 @@ Same Python surface as the reference for this path (fevzibabaoglu/adaptive-edge-
 ``Jpeg``, ``JpegCompressionSettings``, ``Image``, ``EvaluationMetrics``, ``EdgeDetection``, ``QuadTree``, ``convert``,
 ``apply_normalization``, ``get_color_spaces``; and standard JPEG (``standard_jpeg_many`` / ``standard_jpeg_batch``, byte-identical to
 Pillow's files) for the reference's comparison against it, and ``standard_jpeg_decode_many`` (baseline .jpg files decoded on the GPU,
-pixel-identical to Pillow).  The arithmetic runs in hand-written HIP kernels behind the
+pixel-identical to Pillow), ``resize_many`` (``Image.resize``) and ``standard_jpeg_thumbnail_many`` (``Image.thumbnail`` on JPEG files),
+both pixel-identical to Pillow too.  The arithmetic runs in hand-written HIP kernels behind the
 C ABI of ``libaejpeg_hip.so`` (include/aej.h); there is no CPU fallback.
 """
 from ._lib import _look_at_hw_queues, configure_hw_queues, hw_queues, set_hw_queues
@@ -22,11 +23,13 @@ from .jpeg import EncodedBatch, Jpeg  # noqa: E402
 from .lpips import LpipsWeights  # noqa: E402
 from .quadtree import QuadNode, QuadTree  # noqa: E402
 from .settings import JpegCompressionSettings  # noqa: E402
+from .resample import resize_many  # noqa: E402
 from .standard_jpeg import (draft_scale, exif_orientation, standard_jpeg_batch, standard_jpeg_decode_many, standard_jpeg_many,  # noqa: E402
-                            standard_jpeg_transcode_many, standard_jpeg_transform_many)
+                            standard_jpeg_thumbnail_many, standard_jpeg_transcode_many, standard_jpeg_transform_many, thumbnail_plan)
 from .sweep import SweepResult, reference_grid, sweep  # noqa: E402
 
 __all__ = ["Jpeg", "JpegCompressionSettings", "EncodedBatch", "Image", "EvaluationMetrics", "EdgeDetection", "QuadTree", "QuadNode",
            "convert", "apply_normalization", "get_color_spaces", "hw_queues", "set_hw_queues", "configure_hw_queues",
            "sweep", "reference_grid", "SweepResult", "LpipsWeights", "standard_jpeg_many", "standard_jpeg_batch",
-           "standard_jpeg_decode_many", "standard_jpeg_transcode_many", "standard_jpeg_transform_many", "exif_orientation", "draft_scale"]
+           "standard_jpeg_decode_many", "standard_jpeg_transcode_many", "standard_jpeg_transform_many", "exif_orientation", "draft_scale",
+           "resize_many", "standard_jpeg_thumbnail_many", "thumbnail_plan"]

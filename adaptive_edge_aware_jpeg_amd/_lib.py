@@ -163,6 +163,13 @@ class JpegProgScan(ctypes.Structure):
                 ("data_offset", ctypes.c_int64), ("data_length", ctypes.c_int64)]
 
 
+class ResampleDesc(ctypes.Structure):
+    """aej_resample_desc (include/aej.h): one image of aej_resample_batch"""
+    _fields_ = [("src_offset", ctypes.c_int64), ("dst_offset", ctypes.c_int64), ("src_w", ctypes.c_int32), ("src_h", ctypes.c_int32),
+                ("dst_w", ctypes.c_int32), ("dst_h", ctypes.c_int32), ("box", ctypes.c_float * 4), ("filter", ctypes.c_int32),
+                ("reduce_x", ctypes.c_int32), ("reduce_y", ctypes.c_int32), ("reduce_box", ctypes.c_int32 * 4), ("reserved", ctypes.c_int32)]
+
+
 SIGNATURES = {
     "aej_abi_version": (_I, []),
     "aej_create": (_P, [_I, _P]),
@@ -255,6 +262,9 @@ SIGNATURES = {
     "aej_jfif_transform_headers_host": (_I, [_P, _P, _P, _I, _I, _I, _P, _I]),
     "aej_jfif_transform_workspace_bytes": (_U64, [_P, _P, _I, _P, _P, _I, _I, _P, _I]),
     "aej_jfif_transform_batch": (_I, [_P, _P, _I, _P, _U64, _P, _P, _P, _I, _P, _U64, _P, _P, _I, _P, _I, _P, _U64, _P, _P, _P, _P, _P, _P, _U64]),
+    "aej_resample_taps_host": (_I, [_I, ctypes.c_float, ctypes.c_float, _I, _I, _P, _P, _I64]),
+    "aej_resample_workspace_bytes": (_U64, [_P, _P, _I]),
+    "aej_resample_batch": (_I, [_P, _P, _I, _P, _U64, _P, _U64, _P, _U64]),
     "aej_test_jpegprog_coefs": (_I, [_P, _P, _P, _I, _P, _U64, _P, _I, _P, _U64, _P, _P, _U64]),             # include/aej_testing.h (tests only)
     "aej_test_jpegprog_coefs_host": (_I, [_P, _P, _P, _U64, _I, _P, _U64]),                                 # include/aej_testing.h (tests only)
     "aej_test_jpegdec_idct_host": (_I, [_P, _P, _I, _P]),                                                   # include/aej_testing.h (tests only)

@@ -422,3 +422,47 @@ hipError_t launch_jfiftrans(hipStream_t st, JtPlan &plan, int *status, unsigned 
                             long long *offsets);
 
 }  // namespace aej
+
+// resample.hip: Pillow's reduce and two-pass resize of packed 8-bit RGB images (aej_resample_*)
+namespace aej {
+constexpr int kRsBits = 22;            // Pillow's PRECISION_BITS for 8-bit images: taps are int(k * 2^22 +- 0.5)
+constexpr int kRsThreads = 256;
+struct RsReduce {                      // one image of k_rs_reduce (device pointers set by resample_blob)
+    const unsigned char *in;           // the first pixel of the reduce box
+    unsigned char *out;
+    long long tile_base;               // its first workgroup
+    int in_w;                          // pixels per input row
+    int bw, bh, fx, fy, out_w, out_h;  // the box, the factors, ceil(box / factor)
+};
+struct RsConv {                        // one image of k_rs_horizontal / k_rs_vertical
+    const unsigned char *in;
+    unsigned char *out;
+    const int *bounds, *taps;          // [out][2] first source index and count; horizontal [ksize][out_w], vertical [out_h][ksize]
+    long long tile_base;
+    int in_w, out_w, out_h, ksize;
+    int shift;                         // the input's first row in the vertical bounds' coordinates
+    int pad;
+};
+struct RsImage {                       // host: the stages of one image and where they read and write
+    bool reduce, horizontal, vertical;
+    RsReduce r; RsConv h, v;
+    long long src_offset, dst_offset, src_bytes, dst_bytes, r_src, tmp_a, tmp_b, h_table, v_table;
+};
+struct RsPlan {
+    std::vector<RsImage> images;
+    std::vector<int> ints;             // the tables (filled on request)
+    long long n_ints = 0, tmp_bytes = 0, tiles[3] = {0, 0, 0};
+    int count[3] = {0, 0, 0};          // images in the reduce / horizontal / vertical launch
+};
+struct RsBufs { unsigned char *blob, *tmp; };
+double rs_support(int filter);         // 0: not a filter
+int rs_ksize(float in0, float in1, int out_size, int filter);
+void rs_taps(int in_size, float in0, float in1, int out_size, int filter, int ksize, int *bounds, int *taps);
+void rs_bounds_of_row(int in_size, float in0, float in1, int out_size, int filter, int xx, int *bounds);
+const char *rs_check(const aej_resample_desc &d, int *code);
+int resample_plan(const aej_resample_desc *descs, int n, bool fill, RsPlan &plan, const char **why, int *code);
+unsigned long long resample_carve(void *base, const RsPlan &plan, RsBufs &w);
+void resample_blob(const RsPlan &plan, const RsBufs &w, const unsigned char *src, unsigned char *dst, std::vector<unsigned char> &blob);
+hipError_t launch_resample(hipStream_t st, const RsPlan &plan, const RsBufs &w, const void *blob_host, unsigned long long blob_bytes);
+
+}  // namespace aej

@@ -1,0 +1,236 @@
+"""Pillow's ``Image.resize`` for 8-bit RGB images on the GPU, pixel for pixel: ``resize_many`` takes images of mixed sizes and returns
+what ``Image.fromarray(a).resize(size, filter, box=box, reducing_gap=g)`` returns for each, for the five convolution filters
+("box", "bilinear", "hamming", "bicubic", "lanczos", or Pillow's integers 4, 2, 5, 3, 1), down- and up-scaling alike, with Pillow's
+fractional ``box`` and its ``reducing_gap`` step (``Image.reduce`` over ``Image._get_safe_box`` first).  ``standard_jpeg_thumbnail_many``
+(standard_jpeg.py) is ``Image.thumbnail`` on JPEG files built from the scaled decode and this.
+
+The arithmetic is Pillow's (csrc/resample.hip, ``aej_resample_*`` in include/aej.h): per axis a table of int32 taps -- the filter
+evaluated on the host, in double, normalised and rounded to 22 fractional bits -- and on the device one horizontal and one vertical
+pass, each ``clip((2^21 + sum(pixel * tap)) >> 22, 0, 255)`` with the horizontal result rounded to uint8 in between; ``reduce`` is the
+integer cell mean ``((sum + n // 2) * (2^32 // (256 n))) >> 24``.  One call is at most three kernel launches and one upload however
+many images it has, and nothing is read back.
+
+Not built (NotImplementedError): ``nearest`` (Pillow takes another path for it), an image more than 100 times as tall as wide that
+is made shorter (Pillow resizes that one vertically first), and modes other than 8-bit RGB (grey JPEG files decode to three equal
+channels).  There is no CPU fallback.
+"""
+import ctypes
+import math
+
+import numpy as np
+
+from ._lib import get_context
+
+FILTERS = {"box": 4, "bilinear": 2, "hamming": 5, "bicubic": 3, "lanczos": 1}      # Pillow's Image.Resampling integers
+_SUPPORT = {4: 0.5, 2: 1.0, 5: 1.0, 3: 2.0, 1: 3.0}
+
+
+def _check_filter(resample, what="resample") -> int:
+    """one filter -> Pillow's integer.  `what` names the image (or "every image") in a refusal."""
+    if isinstance(resample, str):
+        if resample == "nearest":
+            raise NotImplementedError(f"{what}: resample 'nearest': Pillow takes another path for it, which is not built")
+        if resample in FILTERS:
+            return FILTERS[resample]
+    elif isinstance(resample, (int, np.integer)) and not isinstance(resample, (bool, np.bool_)):
+        if int(resample) == 0:
+            raise NotImplementedError(f"{what}: resample 0 (nearest): Pillow takes another path for it, which is not built")
+        if int(resample) in _SUPPORT:
+            return int(resample)
+    raise ValueError(f"{what}: resample {resample!r}: 'box', 'bilinear', 'hamming', 'bicubic', 'lanczos' or Pillow's 4, 2, 5, 3, 1 required")
+
+
+def _check_filters(resample, n, what):
+    """one filter, or a list / tuple of one per image -> list of n of Pillow's integers.  A refusal names the image (`what` and its
+    index) whose entry it is, or "every `what`" for the one filter all of them share."""
+    if isinstance(resample, (list, tuple)):
+        if len(resample) != n:
+            raise ValueError(f"resample: {len(resample)} entries for {n} {what}s")
+        return [_check_filter(r, f"{what} {i}") for i, r in enumerate(resample)]
+    return [_check_filter(resample, f"every {what}")] * n
+
+
+def _check_gap(gap, what="reducing_gap"):
+    """reducing_gap, which all images of a call share: `what` says so in a refusal ("every image")"""
+    if gap is None:
+        return None
+    if isinstance(gap, (bool, np.bool_)) or not isinstance(gap, (int, float, np.integer, np.floating)) or not gap >= 1.0:
+        raise ValueError(f"{what}: reducing_gap must be 1.0 or greater (got {gap!r})")
+    return float(gap)
+
+
+def _is_number(v):
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+
+
+def _check_size(size, what, integers=True):
+    """one (w, h): positive integers (or, for a thumbnail request, positive numbers whose floor is at least 1)"""
+    ok = not isinstance(size, (str, bytes)) and hasattr(size, "__len__") and len(size) == 2 and all(_is_number(v) for v in size)
+    if ok and integers:
+        ok = all(int(v) == v and v >= 1 for v in size)
+    elif ok:
+        ok = all(math.isfinite(v) and v >= 1 for v in size)
+    if not ok:
+        raise ValueError(f"{what}: size {size!r}: (width, height), positive {'integers' if integers else 'numbers'} (no bools) required")
+    return (int(size[0]), int(size[1])) if integers else (size[0], size[1])
+
+
+def _per_item(value, n, width, name, what):
+    """one value (a sequence of `width` numbers) or a sequence of n such values -> list of n"""
+    if value is None:
+        return [None] * n
+    if isinstance(value, (str, bytes)) or not hasattr(value, "__len__"):
+        raise ValueError(f"{name} {value!r}: {width} numbers, or one such entry per {what}, required")
+    if len(value) == width and all(_is_number(v) or isinstance(v, (bool, np.bool_)) for v in value):
+        return [tuple(value)] * n
+    if len(value) != n:
+        raise ValueError(f"{name}: {len(value)} entries for {n} {what}s")
+    return list(value)
+
+
+def _safe_box(size_img, size, f, box):
+    """Image._get_safe_box: the box grown by the pixels the filter may read, clipped to the image"""
+    fsup = _SUPPORT[f] - 0.5
+    sx, sy = (box[2] - box[0]) / size[0], (box[3] - box[1]) / size[1]
+    return (max(0, int(box[0] - fsup * sx)), max(0, int(box[1] - fsup * sy)),
+            min(size_img[0], math.ceil(box[2] + fsup * sx)), min(size_img[1], math.ceil(box[3] + fsup * sy)))
+
+
+def reduce_factors(box, size, gap):
+    """the integer factors Image.resize reduces by first under reducing_gap=gap"""
+    if gap is None:
+        return 1, 1
+    return int((box[2] - box[0]) / size[0] / gap) or 1, int((box[3] - box[1]) / size[1] / gap) or 1
+
+
+def _steps(what, W, H, size, box, f, gap):
+    """Image.resize's choices for one W x H image, on the host: -> dict(src=(W, H), dst=size, box, factors, reduce_box) for
+    aej_resample_desc.  `what` names the image in a refusal."""
+    w, h = size
+    whole = (0, 0, W, H)
+    if box is None:
+        box = whole
+    else:
+        if len(box) != 4 or not all(_is_number(v) and math.isfinite(v) for v in box):
+            raise ValueError(f"{what}: box {box!r}: four numbers (x0, y0, x1, y1) required")
+        b = [float(np.float32(v)) for v in box]       # as Pillow's C code sees it
+        if b[0] < 0 or b[1] < 0:
+            raise ValueError(f"{what}: box {tuple(box)!r}: box offset can't be negative")
+        if b[2] > W or b[3] > H:
+            raise ValueError(f"{what}: box {tuple(box)!r}: box can't exceed original image size ({W} x {H})")
+        if not (b[2] - b[0] > 0 and b[3] - b[1] > 0):
+            raise ValueError(f"{what}: box {tuple(box)!r}: box can't be empty")
+        box = tuple(box)
+    step = dict(src=(W, H), dst=(w, h), box=tuple(box), factors=(1, 1), reduce_box=(0, 0, 0, 0))
+    if (W, H) == (w, h) and tuple(box) == whole:
+        return step
+    fx, fy = reduce_factors(box, size, gap)
+    if fx > 1 or fy > 1:
+        rb = _safe_box((W, H), size, f, box)
+        step.update(factors=(fx, fy), reduce_box=rb,
+                    box=((box[0] - rb[0]) / fx, (box[1] - rb[1]) / fy, (box[2] - rb[0]) / fx, (box[3] - rb[1]) / fy))
+        W, H = -(-(rb[2] - rb[0]) // fx), -(-(rb[3] - rb[1]) // fy)
+    if H > W * 100 and h < H:
+        raise NotImplementedError(f"{what}: a {W} x {H} image, more than 100 times as tall as wide, made shorter: Pillow resizes it "
+                                  "vertically first, which is not built")
+    return step
+
+
+def _run(ctx, src, src_bytes, src_off, steps, f):
+    """aej_resample_batch over the images at src + src_off[i] -> list of uint8 [h, w, 3] views into one packed allocation.
+    f: one filter per image."""
+    from ._lib import ResampleDesc
+    t, lib, n = ctx.torch, ctx.lib, len(steps)
+    descs = (ResampleDesc * n)()
+    pos = 0
+    dst_off = []
+    for i, s in enumerate(steps):
+        d = descs[i]
+        d.src_offset, d.dst_offset = int(src_off[i]), pos
+        (d.src_w, d.src_h), (d.dst_w, d.dst_h) = s["src"], s["dst"]
+        d.box = (ctypes.c_float * 4)(*s["box"])
+        d.filter = f[i]
+        d.reduce_x, d.reduce_y = s["factors"]
+        d.reduce_box = (ctypes.c_int32 * 4)(*s["reduce_box"])
+        dst_off.append(pos)
+        pos += d.dst_w * d.dst_h * 3
+    out = ctx.empty((pos,), t.uint8)
+    nws = int(lib.aej_resample_workspace_bytes(ctx.handle, ctypes.addressof(descs), n))
+    ws = ctx.workspace(max(nws, 256))
+    ctx.check(lib.aej_resample_batch(ctx.handle, ctypes.addressof(descs), n, ctypes.c_void_p(src), ctypes.c_uint64(src_bytes), out.data_ptr(),
+                                     ctypes.c_uint64(pos), ws.data_ptr(), ctypes.c_uint64(ws.numel())))
+    return [out[o:o + s["dst"][0] * s["dst"][1] * 3].view(s["dst"][1], s["dst"][0], 3) for o, s in zip(dst_off, steps)]
+
+
+def resample_taps(in_size: int, in0: float, in1: float, out_size: int, resample="bicubic"):
+    """aej_resample_taps_host (host only): the table of one axis -> (xmin int32 [out_size], count int32 [out_size], taps int32
+    [out_size, ksize], zero past each row's count)."""
+    from ._lib import load_library
+    lib, f = load_library(), _check_filter(resample, "resample_taps")
+    k = lib.aej_resample_taps_host(int(in_size), float(in0), float(in1), int(out_size), f, None, None, 0)
+    if k < 0:
+        raise ValueError(f"taps of {in_size} -> {out_size} over [{in0}, {in1}]: sizes of at least 1 and 0 <= in0 < in1 <= in_size required")
+    bounds, taps = np.zeros((out_size, 2), np.int32), np.zeros((out_size, k), np.int32)
+    rc = lib.aej_resample_taps_host(int(in_size), float(in0), float(in1), int(out_size), f, bounds.ctypes.data, taps.ctypes.data, taps.size)
+    assert rc == k
+    return bounds[:, 0].copy(), bounds[:, 1].copy(), taps
+
+
+def resize_many(images, size, resample="bicubic", box=None, reducing_gap=None, device: int = 0) -> list:
+    """Resize uint8 [H_i, W_i, 3] images (device tensors or NumPy arrays, of mixed sizes) on the device: -> list of uint8
+    [h_i, w_i, 3] tensors, views into one packed allocation; element i equals
+    ``np.asarray(Image.fromarray(a_i).resize(size_i, F, box=box_i, reducing_gap=reducing_gap))``.
+    size: one (w, h), or one per image.  box: None (the whole image), one (x0, y0, x1, y1) -- fractions allowed, as in Pillow -- or
+    one (or None) per image.  resample (one, or a list of one per image): "box", "bilinear", "hamming", "bicubic", "lanczos" or Pillow's 4, 2, 5, 3, 1; "nearest" / 0
+    raises NotImplementedError.  reducing_gap: None, or a number >= 1.0 (ValueError otherwise): images whose box is more than that
+    many times the size are first reduced by whole factors, as Pillow does.  Up-scaling is the same path.  Every argument is checked
+    on the host before any device work and a refusal names the image; an image more than 100 times as tall as wide that is made
+    shorter raises NotImplementedError."""
+    images = list(images)
+    n = len(images)
+    if n < 1:
+        raise ValueError("resize_many needs at least one image")
+    f, gap = _check_filters(resample, n, "image"), _check_gap(reducing_gap, "every image")
+    if not isinstance(size, (str, bytes)) and hasattr(size, "__len__") and len(size) == 2 and all(_is_number(v) or isinstance(v, (bool, np.bool_)) for v in size):
+        sizes = [_check_size(size, "resize_many")] * n
+    else:
+        if isinstance(size, (str, bytes)) or not hasattr(size, "__len__") or len(size) != n:
+            raise ValueError(f"size {size!r}: one (width, height), or one per image ({n}), required")
+        sizes = [_check_size(s, f"image {i}") for i, s in enumerate(size)]
+    boxes = _per_item(box, n, 4, "box", "image")
+    steps, shapes = [], []
+    for i, a in enumerate(images):
+        shape, dt = tuple(a.shape), str(a.dtype)
+        if len(shape) != 3 or shape[2] != 3 or shape[0] < 1 or shape[1] < 1:
+            raise ValueError(f"image {i}: uint8 [H, W, 3] required, got shape {shape}")
+        if dt not in ("uint8", "torch.uint8"):
+            raise TypeError(f"image {i}: uint8 required, got {dt}")
+        if max(shape[:2]) > 65535 or max(sizes[i]) > 65535:
+            raise ValueError(f"image {i}: sizes up to 65535 a side")
+        steps.append(_steps(f"image {i}", shape[1], shape[0], sizes[i], boxes[i], f[i], gap))
+        shapes.append(shape)
+    ctx = get_context(device)
+    t = ctx.torch
+    # the sources: device tensors are read where they are; NumPy arrays cross in one pinned copy
+    host = [i for i, a in enumerate(images) if not isinstance(a, t.Tensor)]
+    keep = {}
+    if host:
+        off, pos = {}, 0
+        for i in host:
+            off[i] = pos
+            pos += shapes[i][0] * shapes[i][1] * 3
+        stage = ctx.pinned(pos)
+        for i in host:
+            nb = shapes[i][0] * shapes[i][1] * 3
+            stage.numpy()[off[i]:off[i] + nb] = np.ascontiguousarray(images[i]).reshape(-1)
+        up = ctx.empty((pos,), t.uint8)
+        up.copy_(stage[:pos], non_blocking=True)
+        for i in host:
+            keep[i] = up[off[i]:off[i] + shapes[i][0] * shapes[i][1] * 3]
+    for i, a in enumerate(images):
+        if i not in keep:
+            keep[i] = a.to(device=ctx.device).contiguous()
+    ptrs = [keep[i].data_ptr() for i in range(n)]
+    base = min(ptrs)
+    end = max(p + s[0] * s[1] * 3 for p, s in zip(ptrs, shapes))
+    return _run(ctx, base, end - base, [p - base for p in ptrs], steps, f)

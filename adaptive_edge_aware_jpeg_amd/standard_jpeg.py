@@ -14,6 +14,12 @@ returns once ``Image.draft()`` has chosen scale ``s`` -- what ``Image.thumbnail(
 ``aej_jpegprog_batch_scaled``; one fused kernel, csrc/jpegdec.hip ``k_jd_scaled``).  ``draft_scale`` is ``draft()``'s choice of that
 scale for a requested size.
 
+``standard_jpeg_thumbnail_many`` finishes that line: ``Image.thumbnail`` on JPEG files, on the device, pixel-identical to Pillow -- the
+aspect-preserving final size, the decode at the scale ``draft()`` picks for ``size * reducing_gap``, then Pillow's ``resize`` of the
+decoded image over the fractional box ``draft()`` returns: its integer box reduce and its two-pass fixed-point resample (resample.py,
+csrc/resample.hip, ``aej_resample_*``), with nothing read back but the decoder's status words.  ``thumbnail_plan`` is that choice for one
+file size, on the host.  ``resize_many`` (resample.py) is ``Image.resize`` itself for device images.
+
 ``standard_jpeg_transcode_many`` joins the two without touching a pixel: it Huffman-decodes existing files to their quantised
 coefficients on the device and entropy-codes the same coefficients again, as a baseline file under the file's own optimal Huffman
 tables or as the ten-scan progressive file (csrc/jfiftrans.hip, ``aej_jfif_transcode_*``) -- what ``jpegtran -optimize`` and
@@ -397,14 +403,23 @@ def standard_jpeg_decode_many(files, device: int = 0, progressive: bool = False,
     files = list(files)
     if not files:
         raise ValueError("standard_jpeg_decode_many needs at least one file")
+    _, out, out_off, shapes = _decode_files(files, device, progressive, _check_scales(scale, len(files)))
+    return [out[int(o):int(o) + h * w * 3].view(h, w, 3) for o, (h, w) in zip(out_off, shapes)]
+
+
+def _decode_files(files, device, progressive, scales, choose=None):
+    """The decode of standard_jpeg_decode_many -> (context, the packed uint8 output, int64 offsets, [(h, w)]).  scales: int32 [n]; with
+    `choose`, file i's scale is choose(i, width, height) instead, asked once its header is parsed and before any device work."""
     n = len(files)
-    scales = _check_scales(scale, n)
     parsed, views, base_idx, prog_idx, shapes = [], [], [], [], []
     for i, is_prog, d, mv in _parse_sources(files, progressive):
         parsed.append(d)
         views.append(mv)
         (prog_idx if is_prog else base_idx).append(i)
-        frame, s = d[0] if is_prog else d, int(scales[i])
+        frame = d[0] if is_prog else d
+        if choose is not None:
+            scales[i] = choose(i, frame.width, frame.height)
+        s = int(scales[i])
         shapes.append((-(-frame.height // s), -(-frame.width // s)))
     if (scales == 1).all():
         scales = None                                # the unscaled entries, as before
@@ -421,7 +436,88 @@ def standard_jpeg_decode_many(files, device: int = 0, progressive: bool = False,
         if idx:
             st[idx] = run(ctx, idx, parsed, views, out, out_off, scales).cpu().numpy()      # the one read-back of the per-file status words
     _raise_status((int(i), int(st[i])) for i in np.flatnonzero(st))
-    return [out[int(o):int(o) + h * w * 3].view(h, w, 3) for o, (h, w) in zip(out_off, shapes)]
+    return ctx, out, out_off, shapes
+
+
+def _thumbnail_size(width, height, size):
+    """Image.thumbnail's preserve_aspect_ratio: the final (w, h), or None when the request covers the image"""
+    import math
+    x, y = math.floor(size[0]), math.floor(size[1])
+    if x >= width and y >= height:
+        return None
+
+    def round_aspect(number, key):
+        return max(min(math.floor(number), math.ceil(number), key=key), 1)
+
+    aspect = width / height
+    if x / y >= aspect:
+        x = round_aspect(y * aspect, key=lambda n: abs(aspect - n / y))
+    else:
+        y = round_aspect(x / aspect, key=lambda n: 0 if n == 0 else abs(aspect - x / n))
+    return x, y
+
+
+def thumbnail_plan(width: int, height: int, size, reducing_gap=2.0):
+    """What ``Image.thumbnail(size, reducing_gap=reducing_gap)`` does to a width x height JPEG file (host only): None when the request
+    covers the image (it stays as it is), otherwise ``(scale, (fx, fy), final_size, box)``: the scale ``draft()`` decodes at (1 without
+    a reducing_gap), the whole factors ``resize`` reduces the decoded image by first, the aspect-preserving final (w, h), and the box
+    (0, 0, width / scale, height / scale) -- fractional -- that the decoded image is resampled over.  When the decoded size already
+    equals final_size nothing follows the decode and the factors are (1, 1)."""
+    from .resample import _check_gap, _check_size, reduce_factors
+    size, gap = _check_size(size, "thumbnail_plan", integers=False), _check_gap(reducing_gap, "thumbnail_plan")
+    width, height = int(width), int(height)
+    if width < 1 or height < 1:
+        raise ValueError(f"thumbnail_plan: a {width} x {height} file: positive sizes required")
+    final = _thumbnail_size(width, height, size)
+    if final is None:
+        return None
+    s = 1
+    if gap is not None:
+        want = (int(size[0] * gap), int(size[1] * gap))
+        ratio = min(width // want[0], height // want[1]) if want[0] > 0 and want[1] > 0 else 0
+        s = next((v for v in (8, 4, 2) if v <= ratio), 1)
+    box = (0, 0, width / s, height / s)
+    if (-(-width // s), -(-height // s)) == final:
+        return s, (1, 1), final, box
+    return s, reduce_factors(box, final, gap), final, box
+
+
+def standard_jpeg_thumbnail_many(files, size, resample="bicubic", reducing_gap=2.0, progressive: bool = False, device: int = 0) -> list:
+    """``Image.thumbnail`` on JPEG files, on the device: -> list of uint8 [h_i, w_i, 3] tensors, views into one packed allocation;
+    element i equals ``im = Image.open(io.BytesIO(files[i])); im.thumbnail(size_i, F, reducing_gap=reducing_gap);
+    np.asarray(im.convert("RGB"))``.  Per file (thumbnail_plan): the aspect-preserving final size; the decode at the scale ``draft()``
+    picks for ``size * reducing_gap`` (standard_jpeg_decode_many's scaled decode); then ``resize`` to the final size over the fractional
+    box draft() returns, with its own reducing_gap step (resample.py, csrc/resample.hip).  A file the request covers comes back at
+    full size.  Nothing but the decoder's status words is read back.
+    size: one (w, h), or one per file.  resample (one, or a list of one per file) / reducing_gap: as resize_many (reducing_gap=None: full-size decode, one resize).
+    files / progressive: as standard_jpeg_decode_many, which refuses what this refuses, with the same words."""
+    from . import resample as RS
+    files = list(files)
+    n = len(files)
+    if n < 1:
+        raise ValueError("standard_jpeg_thumbnail_many needs at least one file")
+    f, gap = RS._check_filters(resample, n, "file"), RS._check_gap(reducing_gap, "every file")
+    if not isinstance(size, (str, bytes)) and hasattr(size, "__len__") and len(size) == 2 and not any(hasattr(v, "__len__") for v in size):
+        sizes = [RS._check_size(size, "standard_jpeg_thumbnail_many", integers=False)] * n
+    else:
+        if isinstance(size, (str, bytes)) or not hasattr(size, "__len__") or len(size) != n:
+            raise ValueError(f"size {size!r}: one (width, height), or one per file ({n}), required")
+        sizes = [RS._check_size(v, f"file {i}", integers=False) for i, v in enumerate(size)]
+    steps = [None] * n
+
+    def choose(i, width, height):
+        plan = thumbnail_plan(width, height, sizes[i], gap)
+        s, final, box = (1, (width, height), None) if plan is None else (plan[0], plan[2], plan[3])
+        dw, dh = -(-width // s), -(-height // s)
+        if (dw, dh) == final:
+            box = None                               # unchanged, or the drafted size is the final one: a copy
+        steps[i] = RS._steps(f"file {i}", dw, dh, final, box, f[i], gap)
+        return s
+
+    ctx, out, out_off, shapes = _decode_files(files, device, progressive, np.ones(n, np.int32), choose)
+    if all(st["src"] == st["dst"] and st["box"] == (0, 0) + st["src"] for st in steps):
+        return [out[int(o):int(o) + h * w * 3].view(h, w, 3) for o, (h, w) in zip(out_off, shapes)]
+    return RS._run(ctx, out.data_ptr(), out.numel(), out_off, steps, f)
 
 
 def decode_sync_rounds(device: int = 0) -> int:

@@ -623,6 +623,48 @@ AEJ_API int aej_jfif_transform_batch(aej_ctx *ctx, const aej_jpegdec_desc *descs
                                      int64_t *lengths, uint64_t *total_host, int32_t *status, int32_t *n_groups_host, void *workspace,
                                      uint64_t workspace_bytes);
 
+/* ---- Pillow's resize, reduce and thumbnail for packed 8-bit RGB images (resize_many, standard_jpeg_thumbnail_many) ------------------
+ * Image.resize with the convolution filters, Image.reduce and the reducing_gap step of resize, bit for bit, for many images of
+ * different sizes in one call (csrc/resample.hip).  An image is uint8 [h][w][3], packed.  Per image, in this order:
+ *   1. reduce (only when reduce_x > 1 or reduce_y > 1): the region reduce_box = x0, y0, x1, y1 of the source is cut into reduce_x x
+ *      reduce_y cells, clipped at its right and bottom edges, and becomes ceil((x1 - x0) / reduce_x) x ceil((y1 - y0) / reduce_y)
+ *      pixels, each ((sum + n / 2) * (2^32 / (256 n))) >> 24 in uint32 over the n pixels really in its cell (Image.reduce);
+ *   2. the horizontal pass, when dst_w differs from the width at hand or box[0] != 0 or box[2] != dst_w, rounded to uint8;
+ *   3. the vertical pass, likewise with box[1], box[3], dst_h.
+ *   box = x0, y0, x1, y1 is in the pixels of the image step 1 left (the source itself without a reduce): float32, as Pillow's C code
+ *   takes it.  An image that needs no step is copied.  A pass is clip((2^21 + sum(pixel * tap)) >> 22, 0, 255) in int32.
+ * NEAREST (filter 0) is not part of this (Pillow takes another path for it): it is an unknown filter, AEJ_ERR_ARG.  Nor is the image
+ * more than 100 times as tall as wide that is made shorter (Pillow resizes it vertically first): AEJ_ERR_UNSUPPORTED.
+ *
+ * aej_resample_taps_host: HOST only, the table of one axis as Pillow precomputes it, in double and without fused multiply-adds:
+ *   scale = double(in1 - in0) / out_size (the difference in float32), support = the filter's * max(scale, 1); for output xx:
+ *   center = in0 + (xx + 0.5) scale, xmin = max(int(center - support + 0.5), 0), count = min(int(center + support + 0.5), in_size) -
+ *   xmin, k[x] = filter((x + xmin - center + 0.5) / max(scale, 1)) normalised by their sum, tap = int(k 2^22 +- 0.5).  -> ksize =
+ *   2 ceil(support) + 1, the row length of taps_host; bounds_host [out_size][2] gets xmin and count, taps_host [out_size][ksize]
+ *   the taps, zero past count.  Both NULL: a size query.  AEJ_ERR_ARG for an unknown filter, a size below 1 or in1 <= in0;
+ *   AEJ_ERR_CAPACITY when taps_capacity (in int32) is below out_size * ksize.
+ * aej_resample_batch: n images.  src / dst: device bytes; image i is read at src + descs_host[i].src_offset and written at dst +
+ *   dst_offset, exactly dst_w * dst_h * 3 bytes and no other byte of dst.  Enqueues at most three kernels (reduce, horizontal,
+ *   vertical: each one grid over every image that needs it) and one upload of the descriptors and tap tables, then waits for the
+ *   upload; nothing is copied back.  Every descriptor is checked before any device work: AEJ_ERR_ARG naming the image for an unknown
+ *   filter, a size below 1 or above 65535, a reduce factor below 1, an empty box or one outside the image, an image outside src_bytes
+ *   / dst_bytes; AEJ_ERR_UNSUPPORTED naming the image for the tall one.  Workspace: aej_resample_workspace_bytes with the same descriptors (0 for descriptors the call refuses). */
+enum { AEJ_RESAMPLE_LANCZOS = 1, AEJ_RESAMPLE_BILINEAR = 2, AEJ_RESAMPLE_BICUBIC = 3, AEJ_RESAMPLE_BOX = 4, AEJ_RESAMPLE_HAMMING = 5 }; /* Pillow's integers */
+typedef struct aej_resample_desc {
+    int64_t src_offset, dst_offset;
+    int32_t src_w, src_h, dst_w, dst_h;
+    float box[4];
+    int32_t filter;
+    int32_t reduce_x, reduce_y;    /* 1, 1: no reduce */
+    int32_t reduce_box[4];         /* read only with a reduce */
+    int32_t reserved;              /* 0 */
+} aej_resample_desc;
+AEJ_API int aej_resample_taps_host(int in_size, float in0, float in1, int out_size, int filter, int32_t *bounds_host, int32_t *taps_host,
+                                   int64_t taps_capacity);
+AEJ_API uint64_t aej_resample_workspace_bytes(aej_ctx *ctx, const aej_resample_desc *descs_host, int n);
+AEJ_API int aej_resample_batch(aej_ctx *ctx, const aej_resample_desc *descs_host, int n, const uint8_t *src, uint64_t src_bytes, uint8_t *dst,
+                               uint64_t dst_bytes, void *workspace, uint64_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif
