@@ -5,7 +5,8 @@ Same Python surface as the reference for this path (fevzibabaoglu/adaptive-edge-
 ``apply_normalization``, ``get_color_spaces``; and standard JPEG (``standard_jpeg_many`` / ``standard_jpeg_batch``, byte-identical to
 Pillow's files) for the reference's comparison against it, and ``standard_jpeg_decode_many`` (baseline .jpg files decoded on the GPU,
 pixel-identical to Pillow), ``resize_many`` (``Image.resize``) and ``standard_jpeg_thumbnail_many`` (``Image.thumbnail`` on JPEG files),
-both pixel-identical to Pillow too.  The arithmetic runs in hand-written HIP kernels behind the
+both pixel-identical to Pillow too; ``standard_jpeg_encode_many`` encodes images of mixed sizes and qualities in one call and
+``standard_jpeg_thumbnail_jpeg_many`` goes from JPEG files to their JPEG thumbnails on the device.  The arithmetic runs in hand-written HIP kernels behind the
 C ABI of ``libaejpeg_hip.so`` (include/aej.h); there is no CPU fallback.
 """
 from ._lib import _look_at_hw_queues, configure_hw_queues, hw_queues, set_hw_queues
@@ -24,12 +25,13 @@ from .lpips import LpipsWeights  # noqa: E402
 from .quadtree import QuadNode, QuadTree  # noqa: E402
 from .settings import JpegCompressionSettings  # noqa: E402
 from .resample import resize_many  # noqa: E402
-from .standard_jpeg import (draft_scale, exif_orientation, standard_jpeg_batch, standard_jpeg_decode_many, standard_jpeg_many,  # noqa: E402
-                            standard_jpeg_thumbnail_many, standard_jpeg_transcode_many, standard_jpeg_transform_many, thumbnail_plan)
+from .standard_jpeg import (draft_scale, encode_groups, exif_orientation, standard_jpeg_batch, standard_jpeg_decode_many,  # noqa: E402
+                            standard_jpeg_encode_many, standard_jpeg_many, standard_jpeg_thumbnail_jpeg_many, standard_jpeg_thumbnail_many, standard_jpeg_transcode_many, standard_jpeg_transform_many, thumbnail_plan)
 from .sweep import SweepResult, reference_grid, sweep  # noqa: E402
 
 __all__ = ["Jpeg", "JpegCompressionSettings", "EncodedBatch", "Image", "EvaluationMetrics", "EdgeDetection", "QuadTree", "QuadNode",
            "convert", "apply_normalization", "get_color_spaces", "hw_queues", "set_hw_queues", "configure_hw_queues",
            "sweep", "reference_grid", "SweepResult", "LpipsWeights", "standard_jpeg_many", "standard_jpeg_batch",
            "standard_jpeg_decode_many", "standard_jpeg_transcode_many", "standard_jpeg_transform_many", "exif_orientation", "draft_scale",
-           "resize_many", "standard_jpeg_thumbnail_many", "thumbnail_plan"]
+           "resize_many", "standard_jpeg_thumbnail_many", "thumbnail_plan", "standard_jpeg_encode_many", "standard_jpeg_thumbnail_jpeg_many",
+           "encode_groups"]

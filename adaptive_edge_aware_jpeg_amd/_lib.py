@@ -135,6 +135,12 @@ class JpegDecHuff(ctypes.Structure):
     _fields_ = [("lut", ctypes.c_uint16 * 512), ("maxcode", ctypes.c_int32 * 18), ("valoff", ctypes.c_int32 * 18), ("vals", ctypes.c_uint8 * 256)]
 
 
+class JfifManyDesc(ctypes.Structure):
+    """aej_jfif_many_desc (include/aej.h): one image of aej_jfif_many_encode"""
+    _fields_ = [("src_offset", ctypes.c_int64), ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("quality", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
 class JpegDecDesc(ctypes.Structure):
     """aej_jpegdec_desc (include/aej.h): what aej_jpegdec_parse_host reads from a file's markers"""
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("ncomp", ctypes.c_int32), ("hs", ctypes.c_int32), ("vs", ctypes.c_int32),
@@ -257,6 +263,9 @@ SIGNATURES = {
     "aej_jfif_transcode_headers_host": (_I, [_P, _P, _P, _I, _P, _I]),
     "aej_jfif_transcode_workspace_bytes": (_U64, [_P, _P, _I, _P, _P, _I, _I]),
     "aej_jfif_transcode_batch": (_I, [_P, _P, _I, _P, _U64, _P, _P, _P, _I, _P, _U64, _P, _P, _I, _P, _U64, _P, _P, _P, _P, _P, _P, _U64]),
+    "aej_jfif_many_workspace_bytes": (_U64, [_P, _P, _I, _I, _I, _I]),
+    "aej_jfif_many_encode": (_I, [_P, _P, _I, _P, _U64, _I, _I, _I, _P, _U64, _P, _P, _P, _P, _P, _U64]),
+    "aej_jfif_many_coefs_host": (_I64, [_I, _I, _I, _I, _P, _P, _I64]),
     "aej_jfif_transform_geometry_host": (_I, [_I, _I, _I, _I, _I, _I, _P]),
     "aej_jfif_transform_coefs_host": (_I64, [_I, _I, _I, _I, _I, _I, _P, _I64, _P, _I64]),
     "aej_jfif_transform_headers_host": (_I, [_P, _P, _P, _I, _I, _I, _P, _I]),

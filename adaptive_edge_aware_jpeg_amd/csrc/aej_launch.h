@@ -242,6 +242,9 @@ hipError_t launch_jfif_coefs(hipStream_t st, const JfifGeom &g, const JfifBufs &
 struct Carver;
 unsigned long long jfif_carve_coded(Carver &c, const JfifGeom &g, JfifBufs &w);      // requires g.opt
 hipError_t launch_jfif_entropy(hipStream_t st, const JfifGeom &g, const JfifBufs &w, long long *lengths, long long *offsets);
+// the same chain for files that carry the Annex K tables (Pillow's optimize=False): one kernel fills every segment's codes and markers
+// (those of w.par, whole) in the place of the histogram and table stages
+hipError_t launch_jfif_entropy_annexk(hipStream_t st, const JfifGeom &g, const JfifBufs &w, long long *lengths, long long *offsets);
 hipError_t launch_jfif_scatter(hipStream_t st, const JfifGeom &g, const JfifBufs &w, const long long *lengths, const long long *offsets,
                                unsigned char *out, unsigned long long cap);
 
@@ -393,6 +396,7 @@ struct JtGroup {                       // the files of one OUTPUT (H, W, hs, vs)
 struct JtPlan {
     bool prog = false;
     bool transform = false;            // a file has a transform other than kJxNone: k_jt_transform takes the place of k_jt_bridge
+    bool annexk = false;               // baseline files under the Annex K Huffman tables, not their own (the ragged encoder without optimize)
     std::vector<JtFile> files;         // caller's order
     std::vector<JxGeom> geom;          // caller's order (transform only)
     std::vector<JtGroup> groups;
@@ -412,6 +416,14 @@ JtSource jfiftrans_transformed(const JtSource &s, const JxGeom &g);
 // descriptors that disagree.
 int jfiftrans_plan(const std::vector<JtSource> &src, const std::vector<long long> &n_blocks, bool prog, const int *xf, int trim, JtPlan &plan,
                    int *why);
+// the pieces of a plan, shared with the ragged encoder (jfifmany.hip).  Before them: plan.files sized, plan.prog set.
+// the group of one output geometry, made on first use (NULL: a geometry jfif_geom refuses)
+JtGroup *jfiftrans_group(JtPlan &plan, int H, int W, int hs, int vs);
+// file i, of n_out blocks, joins grp: its place among the call's blocks
+void jfiftrans_add(JtPlan &plan, JtGroup &grp, int i, long long n_out);
+// after the last file: every group's geometry with one "quality" per file, its place in output order, empty markers (JtGroup::par) for
+// the caller to fill.  -> -1, or a file of a group that does not fit
+int jfiftrans_close(JtPlan &plan);
 // HOST: the transform of one file's coefficients, the code k_jt_transform runs.  src: [g.n_src][64] natural order, the source's MCU
 // order; dst: [g.n_out][64] zigzag order, the output's MCU order
 void jfiftrans_coefs_host(const JxGeom &g, const short *src, short *dst);
@@ -420,6 +432,38 @@ unsigned long long jfiftrans_carve(void *base, JtPlan &plan);
 // call's status words (the decoders' results in; out-of-range coefficients added); lengths / offsets: device, caller's order
 hipError_t launch_jfiftrans(hipStream_t st, JtPlan &plan, int *status, unsigned char *out, unsigned long long cap, long long *lengths,
                             long long *offsets);
+// its stages after the bridge: given every JtFile::dst filled and plan.d_files uploaded, one entropy chain per group, placement, scatter,
+// finish.  status may be NULL (no file can have failed)
+hipError_t launch_jfiftrans_chains(hipStream_t st, JtPlan &plan, const int *status, unsigned char *out, unsigned long long cap, long long *lengths,
+                                   long long *offsets);
+
+}  // namespace aej
+
+// jfifmany.hip: the encoder for images of mixed sizes and qualities in one call (aej_jfif_many_*): a ragged front end, then the
+// transcoder's chains
+#include "jfif_many_core.h"
+
+namespace aej {
+struct JmImage {                       // one image of a call (host-computed, uploaded): all that k_jm_coefs reads about it
+    long long blk_base;                // its first block among the call's blocks, images in the caller's order
+    long long src_offset;              // its packed uint8 [H][W][3] in the source buffer
+    short *dst;                        // its segment of its group's w.coef: n_blocks x 64, zigzag order, MCU order
+    JmGeom g;
+    unsigned short qt[2][64];          // its quality's quantisers (luma, chroma), zigzag order
+};
+struct JmPlan {
+    JtPlan t;                          // groups, chains and placement: the transcoder's (JtFile::src unused, no status words)
+    std::vector<JmImage> images;       // caller's order
+    JmImage *d_images = nullptr;
+};
+// src_bytes < 0: the source buffer's size is not known yet (a workspace query).  -> -1, or the first image the call refuses and *why
+int jfifmany_plan(const aej_jfif_many_desc *descs, int n, long long src_bytes, int ss, bool opt, bool prog, JmPlan &plan, const char **why);
+unsigned long long jfifmany_carve(void *base, JmPlan &plan);
+hipError_t launch_jfifmany(hipStream_t st, JmPlan &plan, const unsigned char *src, unsigned char *out, unsigned long long cap, long long *lengths,
+                           long long *offsets);
+// HOST: one image's quantised blocks, the code k_jm_coefs runs.  -> its block count (rgb and dst both NULL: a size query), -1 for
+// arguments outside the encoder's
+long long jfifmany_coefs_host(int W, int H, int quality, int ss, const unsigned char *rgb, short *dst);
 
 }  // namespace aej
 

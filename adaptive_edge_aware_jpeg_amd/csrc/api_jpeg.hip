@@ -665,3 +665,50 @@ extern "C" int aej_jfif_transform_batch(aej_ctx *ctx, const aej_jpegdec_desc *de
                     data_offsets_host, density_host, progressive, transforms_host, trim, out, out_capacity, offsets, lengths, total_host, status,
                     n_groups_host, workspace, workspace_bytes);
 }
+
+// ---- images of mixed sizes and qualities in one call (jfifmany.hip): the ragged front end, then the transcoder's chains --------------------
+static bool jm_flags_ok(int optimize, int progressive) { return (optimize == 0 || optimize == 1) && (progressive == 0 || progressive == 1); }
+
+extern "C" uint64_t aej_jfif_many_workspace_bytes(aej_ctx *, const aej_jfif_many_desc *descs_host, int n, int subsampling, int optimize,
+                                                  int progressive)
+{
+    JmPlan plan;
+    if (!jm_flags_ok(optimize, progressive) || jfifmany_plan(descs_host, n, -1, subsampling, optimize != 0, progressive != 0, plan, nullptr) >= 0) return 0;
+    return jfifmany_carve(nullptr, plan);
+}
+
+extern "C" int aej_jfif_many_encode(aej_ctx *ctx, const aej_jfif_many_desc *descs_host, int n, const uint8_t *src, uint64_t src_bytes, int subsampling,
+                                    int optimize, int progressive, uint8_t *out, uint64_t out_capacity, int64_t *offsets, int64_t *lengths,
+                                    uint64_t *total_host, int32_t *n_groups_host, void *workspace, uint64_t workspace_bytes)
+{
+    const char *fn = __func__;
+    AEJ_TRY(enter(ctx, fn));
+    if (!jm_flags_ok(optimize, progressive)) return fail(ctx, AEJ_ERR_ARG, "%s: optimize %d, progressive %d (0 or 1)", fn, optimize, progressive);
+    if (!descs_host || !src || !offsets || !lengths || !total_host || !workspace) return null_buffer(ctx, fn);
+    JmPlan plan;
+    const char *why = "";
+    const long long limit = (long long)std::min<uint64_t>(src_bytes, (uint64_t)INT64_MAX);
+    const int bad = jfifmany_plan(descs_host, n, limit, subsampling, optimize != 0, progressive != 0, plan, &why);
+    if (bad >= 0) return fail(ctx, AEJ_ERR_ARG, "%s: image %d: %s", fn, bad, why);
+    AEJ_TRY(check_workspace(ctx, jfifmany_carve(workspace, plan), workspace_bytes));
+    if (n_groups_host) *n_groups_host = (int32_t)plan.t.groups.size();
+    AEJ_TRY(bind_device(ctx));
+    AEJ_HIP_CHECK(launch_jfifmany(ctx->stream, plan, src, out, out_capacity, (long long *)lengths, (long long *)offsets));
+    long long total = 0;
+    AEJ_HIP_CHECK(hipMemcpyAsync(&total, plan.t.total, 8, hipMemcpyDeviceToHost, ctx->stream));
+    AEJ_HIP_CHECK(hipStreamSynchronize(ctx->stream));         // also keeps the plan's tables alive until their uploads have run
+    *total_host = (uint64_t)total;
+    if (out && (uint64_t)total > out_capacity)
+        return fail(ctx, AEJ_ERR_CAPACITY, "%s: the files need %lld bytes, the output holds %llu", fn, total, (unsigned long long)out_capacity);
+    return 0;
+}
+
+extern "C" int64_t aej_jfif_many_coefs_host(int width, int height, int quality, int subsampling, const uint8_t *rgb_host, int16_t *dst_host,
+                                            int64_t dst_blocks)
+{
+    const long long nb = jfifmany_coefs_host(width, height, quality, subsampling, nullptr, nullptr);
+    if (nb < 0 || (!rgb_host) != (!dst_host)) return AEJ_ERR_ARG;
+    if (!rgb_host) return nb;                                // a size query
+    if (dst_blocks < nb) return AEJ_ERR_CAPACITY;
+    return jfifmany_coefs_host(width, height, quality, subsampling, rgb_host, dst_host);
+}

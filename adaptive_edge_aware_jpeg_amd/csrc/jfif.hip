@@ -26,6 +26,7 @@
 #include "aej_common.h"
 #include "aej_ctx.h"
 #include "aej_launch.h"
+#include "jfif_arith.h"
 #include "jfif_huff_core.h"
 #include "jpegdec_core.h"
 
@@ -82,36 +83,7 @@ __constant__ unsigned k_ac_chroma[256] = {
     260618, 8373007, 16774672, 16774928, 16775184, 16775440, 16775696, 16775952, 16776208, 16776464, 16776720, 0, 0, 0, 0, 0};
 
 // ---- arithmetic shared by the stages ----------------------------------------------------------------------------------------------
-__device__ __forceinline__ int jf_y(const unsigned char *p) { return (19595 * p[0] + 38470 * p[1] + 7471 * p[2] + 32768) >> 16; }
-__device__ __forceinline__ int jf_c(const unsigned char *p, int comp)      // Cb (0) / Cr (1), libjpeg's rounding (ONE_HALF - 1)
-{
-    return comp == 0 ? (-11059 * p[0] - 21709 * p[1] + 32768 * p[2] + (128 << 16) + 32767) >> 16
-                     : (32768 * p[0] - 27439 * p[1] - 5329 * p[2] + (128 << 16) + 32767) >> 16;
-}
-__device__ __forceinline__ long long jf_descale(long long x, int n) { return (x + (1LL << (n - 1))) >> n; }
-
-// jfdctint, one 8-point pass over d[0], d[s], ..., d[7s]; pass 1 keeps PASS1_BITS of extra precision, pass 2 removes it
-template <bool kPass1>
-__device__ __forceinline__ void jf_fdct8(long long *d, int s)
-{
-    const int n = kPass1 ? 11 : 15;
-    long long t0 = d[0] + d[7 * s], t7 = d[0] - d[7 * s], t1 = d[s] + d[6 * s], t6 = d[s] - d[6 * s];
-    long long t2 = d[2 * s] + d[5 * s], t5 = d[2 * s] - d[5 * s], t3 = d[3 * s] + d[4 * s], t4 = d[3 * s] - d[4 * s];
-    long long t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
-    d[0] = kPass1 ? (t10 + t11) * 4 : jf_descale(t10 + t11, 2);
-    d[4 * s] = kPass1 ? (t10 - t11) * 4 : jf_descale(t10 - t11, 2);
-    long long z1 = (t12 + t13) * 4433;
-    d[2 * s] = jf_descale(z1 + t13 * 6270, n);
-    d[6 * s] = jf_descale(z1 - t12 * 15137, n);
-    z1 = t4 + t7;
-    long long z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7, z5 = (z3 + z4) * 9633;
-    t4 *= 2446; t5 *= 16819; t6 *= 25172; t7 *= 12299;
-    z1 *= -7373; z2 *= -20995; z3 = z3 * -16069 + z5; z4 = z4 * -3196 + z5;
-    d[7 * s] = jf_descale(t4 + z1 + z3, n);
-    d[5 * s] = jf_descale(t5 + z2 + z4, n);
-    d[3 * s] = jf_descale(t6 + z2 + z3, n);
-    d[s] = jf_descale(t7 + z1 + z4, n);
-}
+// jf_y, jf_c, jf_h2v1, jf_h2v2, jf_descale, jf_fdct8, jf_quant: jfif_arith.h (shared with jfifmany.hip)
 
 // jidctint, one 8-point pass; pass 1 (columns) descales by CONST_BITS - PASS1_BITS, pass 2 (rows) by CONST_BITS + PASS1_BITS + 3
 template <bool kPass1>
@@ -134,11 +106,6 @@ __device__ __forceinline__ void jf_idct8(long long *d, int s)
     d[3 * s] = jf_descale(t13 + t0, n); d[4 * s] = jf_descale(t13 - t0, n);
 }
 
-__device__ __forceinline__ int jf_quant(int c, int qt)      // libjpeg's quantiser of islow output: divisor 8 qt, rounded half away from zero
-{
-    const int q = qt << 3, a = ((c < 0 ? -c : c) + (q >> 1)) / q;
-    return c < 0 ? -a : a;
-}
 __device__ __forceinline__ int jf_cat(int v) { return v == 0 ? 0 : 32 - __clz(v < 0 ? -v : v); }
 
 // MCU geometry: block k (0 .. HS * VS - 1 luma in raster order, then Cb, Cr) of MCU m; luma blocks outside ceil(H/8) x ceil(W/8) are
@@ -204,7 +171,7 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_fdct(JfifGeom g, const unsi
 #pragma unroll
             for (int c = 0; c < 8; c++) {
                 const int cx = mx * 8 + c, x0 = min(2 * cx, g.W - 1) * 3, x1 = min(2 * cx + 1, g.W - 1) * 3;
-                d[r * 8 + c] = ((jf_c(r0 + x0, comp) + jf_c(r0 + x1, comp) + (cx & 1)) >> 1) - 128;
+                d[r * 8 + c] = jf_h2v1(r0, x0, x1, comp, cx) - 128;
             }
         }
     } else {                                                 // 4:2:0: h2v2_downsample
@@ -216,8 +183,7 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_fdct(JfifGeom g, const unsi
 #pragma unroll
             for (int c = 0; c < 8; c++) {
                 const int cx = mx * 8 + c, x0 = min(2 * cx, g.W - 1) * 3, x1 = min(2 * cx + 1, g.W - 1) * 3;
-                const int sum = jf_c(r0 + x0, comp) + jf_c(r0 + x1, comp) + jf_c(r1 + x0, comp) + jf_c(r1 + x1, comp);
-                d[r * 8 + c] = ((sum + 1 + (cx & 1)) >> 2) - 128;
+                d[r * 8 + c] = jf_h2v2(r0, r1, x0, x1, comp, cx) - 128;
             }
         }
     }
@@ -353,6 +319,25 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_tables(JfifGeom g, const Jf
         if (threadIdx.x < 14) o[end + threadIdx.x] = p.hdr[p.hdr_len - 14 + threadIdx.x];      // SOS
     }
     if (threadIdx.x == 0) fhdr_len[seg] = end + 14 <= kJfifHdrMax ? end + 14 : 0;
+}
+
+// in the place of (a1) and (a2) for files that carry the Annex K tables but run the table-driven stages (launch_jfif_entropy_annexk):
+// one workgroup per (quality, image), thread i symbol i of the four tables; the file's markers are those of its quality, whole
+__global__ __launch_bounds__(kJfThreads) void k_jfif_annexk(JfifGeom g, const JfifParams *__restrict__ par, unsigned *__restrict__ codes,
+                                                            unsigned char *__restrict__ fhdr, int *__restrict__ fhdr_len)
+{
+    static_assert(kJfThreads == 256, "one thread per symbol");
+    const long long seg = blockIdx.x;
+    const int i = threadIdx.x;
+    unsigned *tc = codes + seg * 4 * 256;
+    tc[i] = i < 16 ? k_dc_luma[i] : 0;
+    tc[256 + i] = k_ac_luma[i];
+    tc[512 + i] = i < 16 ? k_dc_chroma[i] : 0;
+    tc[768 + i] = k_ac_chroma[i];
+    const JfifParams &p = par[seg / g.B];
+    const int n = min(max(p.hdr_len, 0), kJfifHdrMax);
+    for (int j = i; j < n; j += kJfThreads) fhdr[seg * kJfifHdrMax + j] = p.hdr[j];
+    if (i == 0) fhdr_len[seg] = n;
 }
 
 // (a3) every block's bits under its file's tables (k_jfif_quant counted them with the Annex K lengths)
@@ -760,17 +745,22 @@ void jfif_params_host(int q, int H, int W, JfifParams &p, int ss)
 static unsigned jf_blocks(long long n) { return (unsigned)((n + kJfThreads - 1) / kJfThreads); }
 
 // the stages from w.coef to the file lengths and offsets (k_jfif_quant has left the Annex K bit counts in w.lens)
+// annexk (requires g.opt): the table-driven stages under the Annex K tables -- k_jfif_annexk in the place of histogram and tables
 template <int HS, int VS>
-static hipError_t jf_entropy(hipStream_t st, const JfifGeom &g, const JfifBufs &w, long long *lengths, long long *offsets)
+static hipError_t jf_entropy(hipStream_t st, const JfifGeom &g, const JfifBufs &w, long long *lengths, long long *offsets, bool annexk = false)
 {
     const long long segs = (long long)g.nq * g.B, nb = segs * g.nblk, nc = segs * g.n_chunks;
-    if (g.opt) {
+    if (annexk && !g.opt) return hipErrorInvalidValue;
+    if (annexk) {
+        hipLaunchKernelGGL(k_jfif_annexk, dim3((unsigned)segs), dim3(kJfThreads), 0, st, g, w.par, w.codes, w.fhdr, w.fhdr_len);
+    } else if (g.opt) {
         const hipError_t e = hipMemsetAsync(w.hist, 0, (size_t)segs * 4 * kJhSymbols * 8, st);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL((k_jfif_hist<HS, VS>), dim3(jf_blocks(g.nblk), (unsigned)segs), dim3(kJfThreads), 0, st, g, w.coef, w.hist);
         hipLaunchKernelGGL(k_jfif_tables, dim3((unsigned)segs), dim3(kJfThreads), 0, st, g, w.par, w.hist, w.codes, w.fhdr, w.fhdr_len);
-        hipLaunchKernelGGL((k_jfif_count<HS, VS>), dim3(jf_blocks(nb)), dim3(kJfThreads), 0, st, g, w.coef, w.codes, w.lens);
     }
+    if (g.opt)
+        hipLaunchKernelGGL((k_jfif_count<HS, VS>), dim3(jf_blocks(nb)), dim3(kJfThreads), 0, st, g, w.coef, w.codes, w.lens);
     hipLaunchKernelGGL(k_jfif_scan, dim3((unsigned)segs), dim3(kJfScanThreads), 0, st, w.lens, g.nblk, w.boff, w.btot);
     hipLaunchKernelGGL(k_jfif_zero, dim3((unsigned)((g.stream_words + kJfThreads - 1) / kJfThreads), (unsigned)segs), dim3(kJfThreads), 0, st, g,
                        w.btot, w.stream);
@@ -820,6 +810,13 @@ hipError_t launch_jfif_entropy(hipStream_t st, const JfifGeom &g, const JfifBufs
     if (g.hs == 1) return jf_entropy<1, 1>(st, g, w, lengths, offsets);
     if (g.vs == 1) return jf_entropy<2, 1>(st, g, w, lengths, offsets);
     return jf_entropy<2, 2>(st, g, w, lengths, offsets);
+}
+
+hipError_t launch_jfif_entropy_annexk(hipStream_t st, const JfifGeom &g, const JfifBufs &w, long long *lengths, long long *offsets)
+{
+    if (g.hs == 1) return jf_entropy<1, 1>(st, g, w, lengths, offsets, true);
+    if (g.vs == 1) return jf_entropy<2, 1>(st, g, w, lengths, offsets, true);
+    return jf_entropy<2, 2>(st, g, w, lengths, offsets, true);
 }
 
 hipError_t launch_jfif_scatter(hipStream_t st, const JfifGeom &g, const JfifBufs &w, const long long *lengths, const long long *offsets,

@@ -25,6 +25,9 @@
 //   k_jt_place      one thread: the files' offsets in the packed output, group after group
 //   (per group)     launch_jfif_scatter / launch_jfifprog_scatter
 //   k_jt_finish     one thread per file: length and offset in the caller's order; a failed file's length is 0
+// Everything after the bridge is launch_jfiftrans_chains, which the ragged encoder (jfifmany.hip) runs too: its front end fills
+// JtFile::dst from pixels, its plan is made of the same jfiftrans_group / jfiftrans_add / jfiftrans_close, and with JtPlan::annexk its
+// baseline files carry the Annex K tables (launch_jfif_entropy_annexk) instead of their own.
 // Bounds: every index derives from the host layout (JtPlan): a wave's block lies inside [0, n_blocks) of the file jt_find_file returns,
 // src and dst are that file's own ranges of the decoder's and the group's coefficient buffers, the status index is below the call's
 // file count, and an SOS marker is patched only inside the kJfpPiece bytes of its own piece.  With a transform the file's JxGeom, made
@@ -135,7 +138,7 @@ __global__ __launch_bounds__(kJtThreads) void k_jt_finish(const JtFile *__restri
     const int i = blockIdx.x * kJtThreads + threadIdx.x;
     if (i >= n) return;
     const JtFile &F = files[i];
-    lengths[i] = status[F.status_index] ? 0 : glen[F.out_pos];
+    lengths[i] = status && status[F.status_index] ? 0 : glen[F.out_pos];      // (the encoder of jfifmany.hip has no status words)
     offsets[i] = goff[F.out_pos];
 }
 
@@ -201,6 +204,39 @@ void jfiftrans_coefs_host(const JxGeom &g, const short *src, short *dst)
     }
 }
 
+JtGroup *jfiftrans_group(JtPlan &plan, int H, int W, int hs, int vs)
+{
+    for (JtGroup &c : plan.groups)
+        if (c.g.H == H && c.g.W == W && c.g.hs == hs && c.g.vs == vs) return &c;
+    JtGroup grp{};
+    grp.foreign_ids = false;
+    if (!jfif_geom(1, H, W, 1, grp.g, hs == 1 ? 0 : vs == 1 ? 1 : 2, 1)) return nullptr;
+    plan.groups.push_back(grp);
+    return &plan.groups.back();
+}
+
+void jfiftrans_add(JtPlan &plan, JtGroup &grp, int i, long long n_out)
+{
+    grp.files.push_back(i);
+    plan.files[i].src_base = plan.n_blocks;
+    plan.files[i].n_blocks = n_out;
+    plan.n_blocks += n_out;
+}
+
+int jfiftrans_close(JtPlan &plan)
+{
+    long long first = 0;
+    for (JtGroup &c : plan.groups) {
+        const int ng = (int)c.files.size(), ss = c.g.hs == 1 ? 0 : c.g.vs == 1 ? 1 : 2;
+        if (!jfif_geom(1, c.g.H, c.g.W, ng, c.g, ss, 1) || (plan.prog && !jfifprog_geom(c.g, c.p))) return c.files[0];
+        c.first = first;
+        c.par.assign(ng, JfifParams{});
+        for (int k = 0; k < ng; k++) plan.files[c.files[k]].out_pos = (int)(first + k);
+        first += ng;
+    }
+    return -1;
+}
+
 int jfiftrans_plan(const std::vector<JtSource> &src, const std::vector<long long> &n_blocks, bool prog, const int *xf, int trim, JtPlan &plan,
                    int *why)
 {
@@ -217,29 +253,15 @@ int jfiftrans_plan(const std::vector<JtSource> &src, const std::vector<long long
         const int rc = jx_geom(s.height, s.width, s.hs, s.vs, xf ? xf[i] : kJxNone, trim, x);
         if (rc != kJxOk) return refuse(i, rc);
         plan.transform |= x.xf != kJxNone;
-        JtGroup *grp = nullptr;
-        for (JtGroup &c : plan.groups)
-            if (c.g.H == x.oH && c.g.W == x.oW && c.g.hs == x.ohs && c.g.vs == x.ovs) grp = &c;
-        if (!grp) {
-            plan.groups.emplace_back();
-            grp = &plan.groups.back();
-            grp->foreign_ids = false;
-            if (!jfif_geom(1, x.oH, x.oW, 1, grp->g, x.ohs == 1 ? 0 : x.ovs == 1 ? 1 : 2, 1)) return refuse(i, kJxBadArg);
-        }
-        if (n_blocks[i] != x.n_src || grp->g.nblk != x.n_out) return refuse(i, kJxBadArg);
-        grp->files.push_back(i);
+        JtGroup *grp = jfiftrans_group(plan, x.oH, x.oW, x.ohs, x.ovs);
+        if (!grp || n_blocks[i] != x.n_src || grp->g.nblk != x.n_out) return refuse(i, kJxBadArg);
+        jfiftrans_add(plan, *grp, i, x.n_out);
         grp->foreign_ids |= s.comp_id[0] != 1 || s.comp_id[1] != 2 || s.comp_id[2] != 3;
-        plan.files[i].src_base = plan.n_blocks;
-        plan.files[i].n_blocks = x.n_out;
-        plan.n_blocks += x.n_out;
     }
-    long long first = 0;
+    const int bad = jfiftrans_close(plan);
+    if (bad >= 0) return refuse(bad, kJxBadArg);
     for (JtGroup &c : plan.groups) {
-        const int ng = (int)c.files.size(), ss = c.g.hs == 1 ? 0 : c.g.vs == 1 ? 1 : 2;
-        if (!jfif_geom(1, c.g.H, c.g.W, ng, c.g, ss, 1) || (prog && !jfifprog_geom(c.g, c.p))) return refuse(c.files[0], kJxBadArg);
-        c.first = first;
-        c.par.assign(ng, JfifParams{});
-        for (int k = 0; k < ng; k++) {
+        for (size_t k = 0; k < c.files.size(); k++) {
             const JtSource s = jfiftrans_transformed(src[c.files[k]], plan.geom[c.files[k]]);
             JfifParams &p = c.par[k];
             const int len = jfiftrans_prefix_host(s, prog, p.hdr, kJfifHdrMax - 14);
@@ -250,9 +272,7 @@ int jfiftrans_plan(const std::vector<JtSource> &src, const std::vector<long long
                 memcpy(p.hdr + len, sos, 14);
                 p.hdr_len = len + 14;
             }
-            plan.files[c.files[k]].out_pos = (int)(first + k);
         }
-        first += ng;
     }
     return -1;
 }
@@ -292,11 +312,19 @@ hipError_t launch_jfiftrans(hipStream_t st, JtPlan &plan, int *status, unsigned 
     } else {
         hipLaunchKernelGGL(k_jt_bridge, grid, dim3(kJtThreads), 0, st, plan.d_files, n, plan.n_blocks, status);
     }
+    return launch_jfiftrans_chains(st, plan, status, out, cap, lengths, offsets);
+}
+
+hipError_t launch_jfiftrans_chains(hipStream_t st, JtPlan &plan, const int *status, unsigned char *out, unsigned long long cap, long long *lengths,
+                                   long long *offsets)
+{
+    const int n = (int)plan.files.size();
+    hipError_t e = hipSuccess;
     for (JtGroup &c : plan.groups) {
         if ((e = hipMemcpyAsync(c.w.par, c.par.data(), sizeof(JfifParams) * c.par.size(), hipMemcpyHostToDevice, st)) != hipSuccess) return e;
         long long *len = plan.glen + c.first, *off = plan.goff + c.first;
         if (!plan.prog) {
-            if ((e = launch_jfif_entropy(st, c.g, c.w, len, off)) != hipSuccess) return e;
+            if ((e = plan.annexk ? launch_jfif_entropy_annexk(st, c.g, c.w, len, off) : launch_jfif_entropy(st, c.g, c.w, len, off)) != hipSuccess) return e;
             continue;
         }
         if ((e = launch_jfifprog_entropy(st, c.p, c.pw, c.w.coef, c.w.par, len, off)) != hipSuccess) return e;

@@ -29,6 +29,11 @@ Pillow file transcoded this way equals Pillow's own ``optimize=True`` / ``progre
 ``standard_jpeg_transform_many`` is the same call with a lossless flip, rotation or transposition of every file on the way, by name or
 from the EXIF Orientation tag (``jpegtran -flip / -rotate / -transpose``, ``exiftran -a``; ``aej_jfif_transform_*``).
 
+``standard_jpeg_encode_many`` is the encoder for images of mixed sizes, each with its own quality, in one call: one front-end kernel over
+every block of every image, then one entropy chain per distinct size (csrc/jfifmany.hip, ``aej_jfif_many_*``); the files are those
+``standard_jpeg_many`` writes for each image alone.  ``standard_jpeg_thumbnail_jpeg_many`` puts it behind
+``standard_jpeg_thumbnail_many``: JPEG bytes in, smaller JPEG bytes out, the pixels never leaving the device.
+
 The files are byte-identical to Pillow's with libjpeg-turbo (JFIF 1.01, Annex K quantisation and Huffman tables, islow DCT, no restart
 markers) and the decoded pixels equal ``np.asarray(Image.open(file).convert("RGB"))``.  Colour, down-sampling and DCT run once per image
 and every requested quality reuses them (csrc/jfif.hip, ``aej_jfif_*`` in include/aej.h).  Images are uint8, or float32 in [0, 1]
@@ -488,7 +493,8 @@ def standard_jpeg_thumbnail_many(files, size, resample="bicubic", reducing_gap=2
     np.asarray(im.convert("RGB"))``.  Per file (thumbnail_plan): the aspect-preserving final size; the decode at the scale ``draft()``
     picks for ``size * reducing_gap`` (standard_jpeg_decode_many's scaled decode); then ``resize`` to the final size over the fractional
     box draft() returns, with its own reducing_gap step (resample.py, csrc/resample.hip).  A file the request covers comes back at
-    full size.  Nothing but the decoder's status words is read back.
+    full size.  Nothing but the decoder's status words is read back.  A tensor whose file has a COM segment carries its text as the
+    attribute ``jpeg_comment`` (bytes), as Pillow keeps ``im.info["comment"]``; standard_jpeg_encode_many writes it again, as Pillow's save does.
     size: one (w, h), or one per file.  resample (one, or a list of one per file) / reducing_gap: as resize_many (reducing_gap=None: full-size decode, one resize).
     files / progressive: as standard_jpeg_decode_many, which refuses what this refuses, with the same words."""
     from . import resample as RS
@@ -516,8 +522,24 @@ def standard_jpeg_thumbnail_many(files, size, resample="bicubic", reducing_gap=2
 
     ctx, out, out_off, shapes = _decode_files(files, device, progressive, np.ones(n, np.int32), choose)
     if all(st["src"] == st["dst"] and st["box"] == (0, 0) + st["src"] for st in steps):
-        return [out[int(o):int(o) + h * w * 3].view(h, w, 3) for o, (h, w) in zip(out_off, shapes)]
-    return RS._run(ctx, out.data_ptr(), out.numel(), out_off, steps, f)
+        res = [out[int(o):int(o) + h * w * 3].view(h, w, 3) for o, (h, w) in zip(out_off, shapes)]
+    else:
+        res = RS._run(ctx, out.data_ptr(), out.numel(), out_off, steps, f)
+    for i, t in enumerate(res):                      # what Pillow keeps in im.info["comment"] over thumbnail(): see standard_jpeg_encode_many
+        com = _jpeg_comment(files[i], i)
+        if com is not None:
+            t.jpeg_comment = com
+    return res
+
+
+def _jpeg_comment(data, index):
+    """the payload of the last COM segment before the first scan of one file (Pillow's ``im.info["comment"]``), or None"""
+    mv = memoryview(data).cast("B")
+    try:
+        com = [bytes(mv[a + 4:b]) for m, a, b in marker_segments(mv, index) if m == 0xFE]
+    except ValueError:
+        return None
+    return com[-1] if com else None
 
 
 def decode_sync_rounds(device: int = 0) -> int:
@@ -817,3 +839,171 @@ def _transcode_many(files, progressive, device, keep_metadata, names, trim, exif
     for k, (o, m) in enumerate(zip(offsets.cpu().tolist(), lengths.cpu().tolist())):
         res[order[k]] = splice_metadata(blob[o:o + m], meta[order[k]])
     return res
+
+
+# ---- images of mixed sizes in one call ------------------------------------------------------------------------------------------------
+_last_encode_groups = 0
+
+
+def encode_groups() -> int:
+    """Entropy-encode chains the last successful standard_jpeg_encode_many of this process ran: one per distinct (height, width) among
+    its images.  The twin of transcode_groups, and like it a diagnostic: one module-level value, which a call that raises leaves as
+    it was."""
+    return _last_encode_groups
+
+
+def _check_qualities(quality, n, what="image"):
+    """quality= of the many-image calls -> [n] ints: one value for all, or one per image (ValueError naming the image otherwise)"""
+    if isinstance(quality, (str, bytes)) or not hasattr(quality, "__len__"):
+        return [_check_quality(quality)] * n
+    if len(quality) != n:
+        raise ValueError(f"quality: {len(quality)} values for {n} {what}s")
+    out = []
+    for i, q in enumerate(quality):
+        try:
+            out.append(_check_quality(q))
+        except (ValueError, TypeError):
+            raise ValueError(f"{what} {i}: quality {q!r}: an integer in 1..100 required") from None
+    return out
+
+
+def _check_images(images):
+    """The host-side checks of standard_jpeg_encode_many, before any device context exists -> [(image, is_torch, is_float)]"""
+    if isinstance(images, (str, bytes)) or not hasattr(images, "__len__") or (hasattr(images, "ndim") and not isinstance(images, (list, tuple))):
+        raise ValueError("standard_jpeg_encode_many needs a sequence of [H, W, 3] images (one [B, H, W, 3] array is standard_jpeg_many's input)")
+    if len(images) < 1:
+        raise ValueError("standard_jpeg_encode_many needs at least one image")
+    if len(images) > 65535:
+        raise ValueError(f"{len(images)} images: at most 65535 in one call")
+    out = []
+    for i, x in enumerate(images):
+        is_torch = type(x).__module__.split(".")[0] == "torch" and hasattr(x, "data_ptr")      # (no import: torch may not see a device yet)
+        if not is_torch:
+            x = np.asarray(x)
+        dt = str(x.dtype)
+        if dt not in ("uint8", "torch.uint8", "float32", "torch.float32"):
+            raise TypeError(f"image {i}: uint8 or float32 in [0, 1] required, got {dt}")
+        if x.ndim != 3 or x.shape[2] != 3:
+            raise ValueError(f"image {i}: [H, W, 3] required, got {tuple(x.shape)}")
+        if not (1 <= x.shape[0] <= 65535 and 1 <= x.shape[1] <= 65535):
+            raise ValueError(f"image {i}: {x.shape[0]}x{x.shape[1]}: JPEG needs 1 <= H, W <= 65535")
+        com = getattr(x, "jpeg_comment", None)
+        if com is not None and (not isinstance(com, (bytes, bytearray)) or len(com) > 65533):
+            raise TypeError(f"image {i}: jpeg_comment must be at most 65533 bytes, got {type(com).__name__}")
+        out.append((x, is_torch, dt.endswith("float32")))
+    return out
+
+
+def _packed_source(ctx, imgs):
+    """-> (a device uint8 tensor that keeps the pixels alive, its address, its bytes, int64 offsets of the images in it).  Device uint8
+    tensors that are contiguous views of one allocation on this device are used where they lie; anything else is packed into a new buffer."""
+    t, n = ctx.torch, len(imgs)
+    if all(is_t and not is_f and x.is_cuda and x.device == ctx.device and x.is_contiguous() for x, is_t, is_f in imgs):
+        st = imgs[0][0].untyped_storage()
+        if all(x.untyped_storage().data_ptr() == st.data_ptr() for x, _, _ in imgs):
+            off = np.array([x.data_ptr() - st.data_ptr() for x, _, _ in imgs], np.int64)
+            return [x for x, _, _ in imgs], st.data_ptr(), st.nbytes(), off
+    sizes = np.array([x.shape[0] * x.shape[1] * 3 for x, _, _ in imgs], np.int64)
+    off = np.concatenate(([0], np.cumsum(sizes)[:-1])).astype(np.int64)
+    total = int(sizes.sum())
+    buf = ctx.empty((total,), t.uint8)
+    if not any(is_t for _, is_t, _ in imgs):                 # every image on the host: one pinned copy
+        stage = ctx.pinned(total)
+        host = stage.numpy()
+        for i, (x, _, is_f) in enumerate(imgs):
+            if is_f:
+                if not (x.min() >= 0.0 and x.max() <= 1.0):
+                    raise ValueError(f"image {i}: float32 images must lie in [0, 1]")
+                x = np.rint(x * np.float32(255)).astype(np.uint8)
+            host[off[i]:off[i] + sizes[i]] = x.reshape(-1)
+        buf.copy_(stage[:total], non_blocking=True)
+    else:
+        for i, (x, _, _) in enumerate(imgs):
+            try:
+                u8 = _to_u8(ctx, x)
+            except ValueError as e:
+                raise ValueError(f"image {i}: {e}") from None
+            buf[int(off[i]):int(off[i] + sizes[i])].copy_(u8.reshape(-1))
+    return buf, buf.data_ptr(), total, off
+
+
+def _encode_many(ctx, imgs, qualities, ss, opt, prog):
+    global _last_encode_groups
+    from ._lib import JfifManyDesc
+    t, lib, n = ctx.torch, ctx.lib, len(imgs)
+    keep, src, src_bytes, off = _packed_source(ctx, imgs)
+    descs = (JfifManyDesc * n)(*[JfifManyDesc(int(off[i]), int(x.shape[1]), int(x.shape[0]), qualities[i], 0) for i, (x, _, _) in enumerate(imgs)])
+    nws = int(lib.aej_jfif_many_workspace_bytes(ctx.handle, ctypes.addressof(descs), n, ss, int(opt), int(prog)))
+    if nws == 0:
+        raise ValueError("descriptors the library refuses")
+    ws = ctx.workspace(nws)
+    offsets, lengths = ctx.empty((n,), t.int64), ctx.empty((n,), t.int64)
+    total, groups = ctypes.c_uint64(), ctypes.c_int32()
+    hdr = PROGRESSIVE_HEADER_CAPACITY if prog else HEADER_CAPACITY
+    cap = sum(hdr + x.shape[0] * x.shape[1] * 3 // (4 if ss == 2 else 2) for x, _, _ in imgs)      # most files are far smaller; a miss costs one more call
+    out = ctx.empty((cap,), t.uint8)
+    call = lambda o, c: lib.aej_jfif_many_encode(ctx.handle, ctypes.addressof(descs), n, src, ctypes.c_uint64(src_bytes), ss, int(opt), int(prog),  # noqa: E731
+                                                 o.data_ptr(), ctypes.c_uint64(c), offsets.data_ptr(), lengths.data_ptr(), ctypes.addressof(total),
+                                                 ctypes.addressof(groups), ws.data_ptr(), ctypes.c_uint64(nws))
+    rc = call(out, cap)
+    if rc == -4 and total.value > cap:                       # AEJ_ERR_CAPACITY: run again with the exact size
+        cap = int(total.value)
+        out = ctx.empty((cap,), t.uint8)
+        rc = call(out, cap)
+    ctx.check(rc)                                            # (`keep` has held the pixels until here)
+    _last_encode_groups = int(groups.value)
+    blob = out[:int(total.value)].cpu().numpy().tobytes()
+    res = [blob[o:o + m] for o, m in zip(offsets.cpu().tolist(), lengths.cpu().tolist())]
+    for i, (x, _, _) in enumerate(imgs):             # a comment the image carries: one COM segment after the JFIF APP0, where libjpeg puts it
+        com = getattr(x, "jpeg_comment", None)
+        if com is not None:
+            res[i] = splice_metadata(res[i], b"\xff\xfe" + (len(com) + 2).to_bytes(2, "big") + bytes(com))
+    return res
+
+
+def standard_jpeg_encode_many(images, quality=75, subsampling="4:2:0", optimize: bool = False, progressive: bool = False, device: int = 0) -> List[bytes]:
+    """Images of mixed sizes encoded in one call: -> every image's file, in input order; file i equals
+    ``Image.fromarray(u8_i).save(buf, "JPEG", quality=q_i, subsampling=subsampling, optimize=optimize, progressive=progressive)`` byte
+    for byte, and ``standard_jpeg_many(images[i], q_i, ...)[0]``.  images: a non-empty sequence of [H_i, W_i, 3] images, each uint8 or
+    float32 in [0, 1] taken as ``rint(x * 255)``, numpy or torch, sizes mixed freely.  quality: one int for all, or one per image.
+    subsampling, optimize, progressive: as standard_jpeg_many, one setting for the call.
+
+    One kernel converts, down-samples, transforms and quantises every block of every image (csrc/jfifmany.hip); the images are then
+    grouped by size and each group runs one entropy chain (encode_groups() tells how many), so launches grow with the number of
+    distinct sizes.  Device uint8 tensors that are contiguous views of one allocation -- what standard_jpeg_thumbnail_many and
+    resize_many return -- are read where they lie, by offset; anything else is packed into one device buffer first.
+
+    A torch image that carries the attribute ``jpeg_comment`` (bytes; standard_jpeg_thumbnail_many sets it from its file's COM segment)
+    gets that text as a COM segment right after the JFIF APP0 -- what Pillow from 9.4 on does with ``im.info["comment"]`` on save, and
+    the only thing its save carries over from a file.  Without the attribute (every NumPy image) no such segment is written.
+
+    Checked before any device work, naming the image: a quality outside 1..100, a shape that is not [H, W, 3] with 1 <= H, W <= 65535,
+    a quality sequence of another length (ValueError); a dtype other than uint8 / float32, optimize / progressive that are not bools
+    (TypeError).  float32 values outside [0, 1] raise ValueError once the image is looked at.  There is no CPU fallback."""
+    ss, opt, prog = _check_subsampling(subsampling), _check_bool("optimize", optimize), _check_bool("progressive", progressive)
+    imgs = _check_images(images)
+    qualities = _check_qualities(quality, len(imgs))
+    return _encode_many(get_context(device), imgs, qualities, ss, opt, prog)
+
+
+def standard_jpeg_thumbnail_jpeg_many(files, size, quality=75, subsampling="4:2:0", optimize: bool = False, progressive_out: bool = False,
+                                      resample="bicubic", reducing_gap=2.0, progressive: bool = False, device: int = 0) -> List[bytes]:
+    """JPEG files in, their thumbnails out as JPEG files: ``standard_jpeg_encode_many(standard_jpeg_thumbnail_many(files, size, resample,
+    reducing_gap, progressive, device), quality, subsampling, optimize, progressive_out, device)`` -- for a three-component source file
+    i equals ``im = Image.open(io.BytesIO(files[i])); im.thumbnail(size, resample, reducing_gap=reducing_gap); im.save(buf, "JPEG",
+    quality=q_i, subsampling=subsampling, optimize=optimize, progressive=progressive_out)`` byte for byte.  The thumbnails never leave
+    the device: only the decoder's status words and the finished files are read back.  Like Pillow's save it carries no metadata
+    over (no EXIF, ICC profile or density) but a source's COM segment, which Pillow from 9.4 on writes again from
+    ``im.info["comment"]``: the thumbnails carry it as ``jpeg_comment`` and the encoder writes it (both documented there).  A grey (single-component) source comes out as a three-component file with neutral chroma; Pillow keeps mode "L"
+    there and writes a one-component file, which this library does not write.
+    files, size, resample, reducing_gap, progressive (whether progressive SOURCES are accepted): standard_jpeg_thumbnail_many's.
+    quality (one, or one per file), subsampling, optimize, progressive_out: standard_jpeg_encode_many's quality, subsampling, optimize
+    and progressive.  Every argument is checked, and every header parsed, before any device work; a file whose scan is corrupt raises
+    the decoder's ValueError naming it and nothing is returned."""
+    ss, opt, prog = _check_subsampling(subsampling), _check_bool("optimize", optimize), _check_bool("progressive_out", progressive_out)
+    files = list(files)
+    if not files:
+        raise ValueError("standard_jpeg_thumbnail_jpeg_many needs at least one file")
+    qualities = _check_qualities(quality, len(files), "file")
+    thumbs = standard_jpeg_thumbnail_many(files, size, resample, reducing_gap, progressive, device)
+    return _encode_many(get_context(device), _check_images(thumbs), qualities, ss, opt, prog)

@@ -544,6 +544,41 @@ AEJ_API int aej_jpegprog_batch_scaled(aej_ctx *ctx, const aej_jpegprog_frame *fr
                                       uint8_t *out, uint64_t out_bytes, const int64_t *out_offsets_host, int32_t *status, void *workspace,
                                       uint64_t workspace_bytes);
 
+/* ---- images of mixed sizes and qualities encoded in one call (standard_jpeg_encode_many) -------------------------------------------------
+ * The files of aej_jfif_encode_batch_opt / _prog -- Pillow's Image.save(buf, "JPEG", quality, subsampling, optimize, progressive), byte
+ * for byte -- for n images that each have their own size and quality.  One kernel covers every 8 x 8 block of every image (colour, edge
+ * replication, h2v1 / h2v2 down-sampling, islow FDCT and the quantisation fused: an image has one quality); the images are then grouped
+ * by (height, width), each group runs one entropy-encode chain as in aej_jfif_transcode_batch, image i of it under the quantisers and
+ * markers of its own quality: optimize = 1 the file's own Huffman tables, optimize = 0 the Annex K tables, progressive = 1 (optimize is
+ * then not looked at beyond its range) libjpeg's ten scans.  Launches grow with the number of distinct sizes, one chain each.
+ *
+ * aej_jfif_many_desc: image i is packed uint8 [height][width][3] at src + src_offset; reserved must be 0.
+ * aej_jfif_many_workspace_bytes: the workspace of such a call, 0 for descriptors the call refuses (ctx is not looked at).
+ * aej_jfif_many_encode: src: device bytes, src_bytes of them.  out / out_capacity / offsets / lengths / total_host as
+ *   aej_jfif_transcode_batch: offsets and lengths are device int64 [n] in the caller's order (the files are packed group after group),
+ *   out may be NULL to size only; when the files do not fit, AEJ_ERR_CAPACITY returns with *total_host exact, a file that would end past
+ *   out_capacity is not written and nothing is written past it (call again with that size).
+ *   Every descriptor is checked before any device work: AEJ_ERR_ARG, the message naming the image, for a width or height outside
+ *   1..65535, a quality outside 1..100 or an image that does not lie inside src_bytes.  An encode cannot fail per image: there are no
+ *   status words.  *n_groups_host (may be NULL) gets the number of chains.  The call waits for the total at its end.
+ * aej_jfif_many_coefs_host: HOST only, the code the kernel runs, on one image.  rgb_host: uint8 [height][width][3]; dst_host: int16
+ *   [>= the result][64], zigzag order inside a block, the blocks in MCU order (MCUs in raster order; in each the hs x vs luma blocks in
+ *   raster order, then Cb, Cr), the dummy luma blocks of edge MCUs as libjpeg writes them (AC zero, DC of the block before in the MCU).
+ *   -> the image's blocks (also with both pointers NULL: a size query), AEJ_ERR_ARG for a size, quality or subsampling outside the
+ *   encoder's or one pointer NULL, AEJ_ERR_CAPACITY for dst_blocks too small.
+ * (Additions to ABI 3: no existing signature, struct or behaviour changed.) */
+typedef struct aej_jfif_many_desc {
+    int64_t src_offset;
+    int32_t width, height, quality, reserved;
+} aej_jfif_many_desc;
+AEJ_API uint64_t aej_jfif_many_workspace_bytes(aej_ctx *ctx, const aej_jfif_many_desc *descs_host, int n, int subsampling, int optimize,
+                                               int progressive);
+AEJ_API int aej_jfif_many_encode(aej_ctx *ctx, const aej_jfif_many_desc *descs_host, int n, const uint8_t *src, uint64_t src_bytes, int subsampling,
+                                 int optimize, int progressive, uint8_t *out, uint64_t out_capacity, int64_t *offsets, int64_t *lengths,
+                                 uint64_t *total_host, int32_t *n_groups_host, void *workspace, uint64_t workspace_bytes);
+AEJ_API int64_t aej_jfif_many_coefs_host(int width, int height, int quality, int subsampling, const uint8_t *rgb_host, int16_t *dst_host,
+                                         int64_t dst_blocks);
+
 /* ---- lossless transcode: existing files entropy-coded again (standard_jpeg_transcode_many) ----------------------------------------------
  * What jpegtran -optimize / -progressive do, on the device: the files are Huffman-decoded to their quantised coefficients by the stages of
  * aej_jpegdec_batch / aej_jpegprog_batch (no IDCT, no colour) and those coefficients -- every one, the dummy edge blocks of the MCU grid
