@@ -138,7 +138,7 @@ class JpegDecHuff(ctypes.Structure):
 class JfifManyDesc(ctypes.Structure):
     """aej_jfif_many_desc (include/aej.h): one image of aej_jfif_many_encode"""
     _fields_ = [("src_offset", ctypes.c_int64), ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("quality", ctypes.c_int32),
-                ("reserved", ctypes.c_int32)]
+                ("components", ctypes.c_int32)]      # 0 or 3: packed RGB; 1: packed grey
 
 
 class JpegDecDesc(ctypes.Structure):
@@ -266,8 +266,11 @@ SIGNATURES = {
     "aej_jfif_many_workspace_bytes": (_U64, [_P, _P, _I, _I, _I, _I]),
     "aej_jfif_many_encode": (_I, [_P, _P, _I, _P, _U64, _I, _I, _I, _P, _U64, _P, _P, _P, _P, _P, _U64]),
     "aej_jfif_many_coefs_host": (_I64, [_I, _I, _I, _I, _P, _P, _I64]),
+    "aej_jfif_headers_grey_host": (_I, [_I, _I, _I, _P, _I]),
+    "aej_jfif_many_coefs_grey_host": (_I64, [_I, _I, _I, _P, _P, _I64]),
     "aej_jfif_transform_geometry_host": (_I, [_I, _I, _I, _I, _I, _I, _P]),
     "aej_jfif_transform_coefs_host": (_I64, [_I, _I, _I, _I, _I, _I, _P, _I64, _P, _I64]),
+    "aej_jfif_transform_coefs_grey_host": (_I64, [_I, _I, _I, _I, _P, _I64, _P, _I64]),
     "aej_jfif_transform_headers_host": (_I, [_P, _P, _P, _I, _I, _I, _P, _I]),
     "aej_jfif_transform_workspace_bytes": (_U64, [_P, _P, _I, _P, _P, _I, _I, _P, _I]),
     "aej_jfif_transform_batch": (_I, [_P, _P, _I, _P, _U64, _P, _P, _P, _I, _P, _U64, _P, _P, _I, _P, _I, _P, _U64, _P, _P, _P, _P, _P, _P, _U64]),

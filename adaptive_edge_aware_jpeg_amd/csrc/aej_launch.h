@@ -209,14 +209,15 @@ struct JfifGeom {
     int B, H, W, nq;
     int mcux, mcuy, ybx, yby;          // MCUs; real luma blocks per row / column
     int yw, yh, cw, ch;                // reconstruction sample planes
-    long long n_mcu, nblk;             // per image; nblk = (hs * vs + 2) * n_mcu, dummy luma blocks included
+    long long n_mcu, nblk;             // per image; nblk = (hs * vs + 2) * n_mcu, dummy luma blocks included (one component: n_mcu)
     long long stream_words, n_chunks;  // per (quality, image): unstuffed scan words, 64-byte stuffing chunks
     long long plane_bytes;             // per (quality, image): Y, Cb, Cr sample planes
-    int hs, vs, opt, pad_;             // luma sampling factors (2 x 2, 2 x 1, 1 x 1; chroma is 1 x 1); Huffman tables per file
+    int hs, vs, opt, ncomp;            // luma sampling factors (2 x 2, 2 x 1, 1 x 1; chroma is 1 x 1); Huffman tables per file;
+                                       // components: 3, or 1 (grey: hs = vs = 1, an MCU is one block, no dummies; entropy chains only)
 };
 struct JfifParams {                    // one quality: quantisers in zigzag order (luma, chroma) and the markers SOI .. SOS
     int qt[2][64];
-    int hdr_len, dht_off, pad_[2];     // dht_off: where the first DHT segment starts (SOS follows the fourth)
+    int hdr_len, dht_off, pad_[2];     // dht_off: where the first DHT segment starts (SOS follows the fourth; the second of a grey file)
     unsigned char hdr[kJfifHdrMax];
 };
 struct JfifBufs {
@@ -225,11 +226,14 @@ struct JfifBufs {
     // per-file Huffman tables (opt only): symbol counts [seg][4][257], (code << 8) | length [seg][4][256], markers [seg][kJfifHdrMax]
     unsigned long long *hist; unsigned *codes; unsigned char *fhdr; int *fhdr_len;
 };
-// ss: Pillow's subsampling code (0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0); opt: optimise the Huffman tables per file
-bool jfif_geom(int B, int H, int W, int nq, JfifGeom &g, int ss = 2, int opt = 0);
+// ss: Pillow's subsampling code (0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0); opt: optimise the Huffman tables per file; ncomp: 3, or 1 (ss is
+// then not looked at)
+bool jfif_geom(int B, int H, int W, int nq, JfifGeom &g, int ss = 2, int opt = 0, int ncomp = 3);
 unsigned long long jfif_carve(void *base, const JfifGeom &g, JfifBufs &w);
 void jfif_quant_tables(int q, int luma[64], int chroma[64]);
-void jfif_params_host(int q, int H, int W, JfifParams &p, int ss = 2);
+void jfif_params_host(int q, int H, int W, JfifParams &p, int ss = 2, int ncomp = 3);
+constexpr int jfif_sof_bytes(int ncomp) { return 10 + 3 * ncomp; }      // a frame header, marker and length included
+constexpr int jfif_sos_bytes(int ncomp) { return 8 + 2 * ncomp; }       // a scan header of every component
 int jfif_huffman_host(const long long *counts, unsigned char *bits, unsigned char *huffval);
 hipError_t launch_jfif_encode(hipStream_t st, const JfifGeom &g, const JfifBufs &w, const JfifParams *par_host, const unsigned char *rgb,
                               unsigned char *out, unsigned long long cap, long long *lengths, long long *offsets);
@@ -249,7 +253,7 @@ hipError_t launch_jfif_scatter(hipStream_t st, const JfifGeom &g, const JfifBufs
                                unsigned char *out, unsigned long long cap);
 
 // jfifprog.hip: the progressive file Pillow writes with progressive=True from the same coefficients (aej_jfif_*_prog)
-constexpr int kJfpMaxScans = 10;       // jpeg_simple_progression of a three-component file
+constexpr int kJfpMaxScans = 10;       // jpeg_simple_progression of a three-component file (six scans for one component)
 constexpr int kJfpPiece = 576;         // bytes that bound the markers before one scan's data: two DHT of 5 + 16 + 256 and an SOS of 14
 struct JfpScan {
     int Ss, Se, Ah, Al;
@@ -375,7 +379,7 @@ int jpegprog_coefs_host(const aej_jpegprog_frame &frame, const aej_jpegprog_scan
 
 namespace aej {
 struct JtSource {                      // what the output's markers take from one parsed file
-    int width, height, hs, vs;
+    int width, height, hs, vs, ncomp;  // ncomp: 3, or 1 (hs = vs = 1 whatever the file's frame header says: the parsers' rule)
     unsigned char comp_id[3], comp_tq[3];
     unsigned short qt[3][64];          // natural order
     int units, xdensity, ydensity;     // of the JFIF APP0
@@ -386,12 +390,12 @@ struct JtFile {                        // one file of a call (host-computed, upl
     short *dst;                        // its segment of its group's w.coef: zigzag order, the group's MCU order
     int status_index, out_pos;         // its word in the status array; its place in output order (group after group)
 };
-struct JtGroup {                       // the files of one OUTPUT (H, W, hs, vs): one entropy-encode chain, every file one "quality" of one image
+struct JtGroup {                       // the files of one OUTPUT (H, W, hs, vs, components): one entropy-encode chain, every file one "quality" of one image
     JfifGeom g; JfpGeom p; JfifBufs w; JfpBufs pw;
     std::vector<int> files;            // caller's indices, in segment order
     std::vector<JfifParams> par;       // their markers (kept until the upload has run)
     long long first;                   // its first file in output order
-    bool foreign_ids;                  // a file's component ids are not 1, 2, 3
+    bool foreign_ids;                  // a file's component ids are not 1, 2, 3 (one component: not 1)
 };
 struct JtPlan {
     bool prog = false;
@@ -418,7 +422,7 @@ int jfiftrans_plan(const std::vector<JtSource> &src, const std::vector<long long
                    int *why);
 // the pieces of a plan, shared with the ragged encoder (jfifmany.hip).  Before them: plan.files sized, plan.prog set.
 // the group of one output geometry, made on first use (NULL: a geometry jfif_geom refuses)
-JtGroup *jfiftrans_group(JtPlan &plan, int H, int W, int hs, int vs);
+JtGroup *jfiftrans_group(JtPlan &plan, int H, int W, int hs, int vs, int ncomp = 3);
 // file i, of n_out blocks, joins grp: its place among the call's blocks
 void jfiftrans_add(JtPlan &plan, JtGroup &grp, int i, long long n_out);
 // after the last file: every group's geometry with one "quality" per file, its place in output order, empty markers (JtGroup::par) for
@@ -446,7 +450,7 @@ hipError_t launch_jfiftrans_chains(hipStream_t st, JtPlan &plan, const int *stat
 namespace aej {
 struct JmImage {                       // one image of a call (host-computed, uploaded): all that k_jm_coefs reads about it
     long long blk_base;                // its first block among the call's blocks, images in the caller's order
-    long long src_offset;              // its packed uint8 [H][W][3] in the source buffer
+    long long src_offset;              // its packed uint8 [H][W][3] (grey: [H][W]) in the source buffer
     short *dst;                        // its segment of its group's w.coef: n_blocks x 64, zigzag order, MCU order
     JmGeom g;
     unsigned short qt[2][64];          // its quality's quantisers (luma, chroma), zigzag order
@@ -455,6 +459,7 @@ struct JmPlan {
     JtPlan t;                          // groups, chains and placement: the transcoder's (JtFile::src unused, no status words)
     std::vector<JmImage> images;       // caller's order
     JmImage *d_images = nullptr;
+    int hs = 2, vs = 2;                // the call's luma sampling factors (its colour images'; a grey image is 1 x 1 whatever they are)
 };
 // src_bytes < 0: the source buffer's size is not known yet (a workspace query).  -> -1, or the first image the call refuses and *why
 int jfifmany_plan(const aej_jfif_many_desc *descs, int n, long long src_bytes, int ss, bool opt, bool prog, JmPlan &plan, const char **why);
@@ -463,7 +468,7 @@ hipError_t launch_jfifmany(hipStream_t st, JmPlan &plan, const unsigned char *sr
                            long long *offsets);
 // HOST: one image's quantised blocks, the code k_jm_coefs runs.  -> its block count (rgb and dst both NULL: a size query), -1 for
 // arguments outside the encoder's
-long long jfifmany_coefs_host(int W, int H, int quality, int ss, const unsigned char *rgb, short *dst);
+long long jfifmany_coefs_host(int W, int H, int quality, int ss, const unsigned char *rgb, short *dst, int ncomp = 3);
 
 }  // namespace aej
 

@@ -36,6 +36,17 @@ extern "C" int aej_jfif_headers_host_opt(int quality, int H, int W, int subsampl
     return p.hdr_len;
 }
 
+extern "C" int aej_jfif_headers_grey_host(int quality, int H, int W, uint8_t *out_host, int capacity)
+{
+    JfifGeom g;
+    if (quality < 1 || quality > 100 || !jfif_geom(1, H, W, 1, g, 0, 0, 1) || !out_host) return AEJ_ERR_ARG;
+    JfifParams p;
+    jfif_params_host(quality, H, W, p, 0, 1);
+    if (capacity < p.hdr_len) return AEJ_ERR_CAPACITY;
+    memcpy(out_host, p.hdr, p.hdr_len);
+    return p.hdr_len;
+}
+
 extern "C" int aej_jfif_headers_host(int quality, int H, int W, uint8_t *out_host, int capacity)
 {
     return aej_jfif_headers_host_opt(quality, H, W, 2, out_host, capacity);
@@ -457,8 +468,8 @@ extern "C" int aej_test_jpegprog_coefs_host(const aej_jpegprog_frame *frame_host
 template <class D>
 static bool jt_source_ok(const D &d)
 {
-    if (d.ncomp != 3 || d.precision16) return false;
-    for (int c = 0; c < 3; c++)
+    if ((d.ncomp != 3 && d.ncomp != 1) || d.precision16) return false;
+    for (int c = 0; c < d.ncomp; c++)
         for (int i = 0; i < 64; i++)
             if (d.qt[c][i] < 1 || d.qt[c][i] > 255) return false;
     return true;
@@ -487,7 +498,7 @@ static int jt_layout(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs
     c.y.fz.planes = c.y.fz.px = 0;
     for (int i = 0; i < n; i++) {
         const bool ok = i < n_base ? jt_source_ok(descs[i]) : jt_source_ok(frames[i - n_base]);
-        if (!ok) return fail(ctx, AEJ_ERR_UNSUPPORTED, "%s: file %d: three components with 8-bit quantisation tables required", fn, i);
+        if (!ok) return fail(ctx, AEJ_ERR_UNSUPPORTED, "%s: file %d: three components or one, with 8-bit quantisation tables, required", fn, i);
         if (i < n_base) jfiftrans_source(descs[i], c.src[i]); else jfiftrans_source(frames[i - n_base], c.src[i]);
         nblk[i] = i < n_base ? c.files[i].n_blocks : c.y.ffiles[i - n_base].n_blocks;
         if (density) { c.src[i].units = density[3 * i] & 255; c.src[i].xdensity = density[3 * i + 1]; c.src[i].ydensity = density[3 * i + 2]; }
@@ -526,7 +537,7 @@ static int jt_headers(const aej_jpegdec_desc *desc_host, const aej_jpegprog_fram
     if (desc_host) jfiftrans_source(*desc_host, s); else jfiftrans_source(*frame_host, s);
     if (density3_host) { s.units = density3_host[0] & 255; s.xdensity = density3_host[1]; s.ydensity = density3_host[2]; }
     JxGeom x;
-    const int rc = jx_geom(s.height, s.width, s.hs, s.vs, transform, trim, x);
+    const int rc = jx_geom(s.height, s.width, s.hs, s.vs, transform, trim, x, s.ncomp);
     if (rc != kJxOk) return rc == kJxLayout ? AEJ_ERR_UNSUPPORTED : AEJ_ERR_ARG;
     const int n = jfiftrans_prefix_host(jfiftrans_transformed(s, x), progressive != 0, out_host, capacity);
     return n < 0 ? AEJ_ERR_CAPACITY : n;
@@ -555,18 +566,32 @@ extern "C" int aej_jfif_transform_geometry_host(int H, int W, int hs, int vs, in
     return 0;
 }
 
-extern "C" int64_t aej_jfif_transform_coefs_host(int H, int W, int hs, int vs, int transform, int trim, const int16_t *src_host, int64_t src_blocks,
-                                                 int16_t *dst_host, int64_t dst_blocks)
+static int64_t jt_coefs_host(int H, int W, int hs, int vs, int nc, int transform, int trim, const int16_t *src_host, int64_t src_blocks,
+                             int16_t *dst_host, int64_t dst_blocks)
 {
     JxGeom x;
     const int rc = aej_jfif_transform_geometry_host(H, W, hs, vs, transform, trim, nullptr);
     if (rc) return rc;
-    jx_geom(H, W, hs, vs, transform, trim, x);
+    jx_geom(H, W, hs, vs, transform, trim, x, nc);
     if (!src_host && !dst_host) return x.n_out;              // a size query
     if (!src_host || !dst_host || src_blocks != x.n_src) return AEJ_ERR_ARG;
     if (dst_blocks < x.n_out) return AEJ_ERR_CAPACITY;
     jfiftrans_coefs_host(x, src_host, dst_host);
     return x.n_out;
+}
+
+extern "C" int64_t aej_jfif_transform_coefs_host(int H, int W, int hs, int vs, int transform, int trim, const int16_t *src_host, int64_t src_blocks,
+                                                 int16_t *dst_host, int64_t dst_blocks)
+{
+    return jt_coefs_host(H, W, hs, vs, 3, transform, trim, src_host, src_blocks, dst_host, dst_blocks);
+}
+
+extern "C" int64_t aej_jfif_transform_coefs_grey_host(int H, int W, int transform, int trim, const int16_t *src_host, int64_t src_blocks,
+                                                      int16_t *dst_host, int64_t dst_blocks)
+{
+    const int64_t rc = jt_coefs_host(H, W, 1, 1, 1, transform, trim, src_host, src_blocks, dst_host, dst_blocks);
+    const bool refused = aej_jfif_transform_geometry_host(H, W, 1, 1, transform, trim, nullptr) > 0;
+    return refused ? AEJ_ERR_ARG : rc;                        // a one-component file can have 1 or 2 blocks: no positive refusal codes here
 }
 
 static uint64_t jt_workspace_bytes(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs_host, int n_base, const aej_jpegprog_frame *frames_host,
@@ -703,12 +728,22 @@ extern "C" int aej_jfif_many_encode(aej_ctx *ctx, const aej_jfif_many_desc *desc
     return 0;
 }
 
+static int64_t jm_coefs_host(int width, int height, int quality, int subsampling, int nc, const uint8_t *src_host, int16_t *dst_host, int64_t dst_blocks)
+{
+    const long long nb = jfifmany_coefs_host(width, height, quality, subsampling, nullptr, nullptr, nc);
+    if (nb < 0 || (!src_host) != (!dst_host)) return AEJ_ERR_ARG;
+    if (!src_host) return nb;                                // a size query
+    if (dst_blocks < nb) return AEJ_ERR_CAPACITY;
+    return jfifmany_coefs_host(width, height, quality, subsampling, src_host, dst_host, nc);
+}
+
 extern "C" int64_t aej_jfif_many_coefs_host(int width, int height, int quality, int subsampling, const uint8_t *rgb_host, int16_t *dst_host,
                                             int64_t dst_blocks)
 {
-    const long long nb = jfifmany_coefs_host(width, height, quality, subsampling, nullptr, nullptr);
-    if (nb < 0 || (!rgb_host) != (!dst_host)) return AEJ_ERR_ARG;
-    if (!rgb_host) return nb;                                // a size query
-    if (dst_blocks < nb) return AEJ_ERR_CAPACITY;
-    return jfifmany_coefs_host(width, height, quality, subsampling, rgb_host, dst_host);
+    return jm_coefs_host(width, height, quality, subsampling, 3, rgb_host, dst_host, dst_blocks);
+}
+
+extern "C" int64_t aej_jfif_many_coefs_grey_host(int width, int height, int quality, const uint8_t *grey_host, int16_t *dst_host, int64_t dst_blocks)
+{
+    return jm_coefs_host(width, height, quality, 0, 1, grey_host, dst_host, dst_blocks);
 }

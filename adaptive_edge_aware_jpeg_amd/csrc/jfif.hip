@@ -4,7 +4,12 @@
 // tests/jfif_options_reference.py are the same algorithm in numpy and tests/test_gpu_jfif*.py pin both to Pillow's files byte for byte.
 //
 // Every kernel that walks blocks is a template over the luma sampling factors <HS, VS> (2 x 2, 2 x 1, 1 x 1): an MCU holds HS * VS luma
-// blocks in raster order, then Cb, then Cr.
+// blocks in raster order, then Cb, then Cr.  The entropy stages that walk blocks (k_jfif_hist, k_jfif_count, k_jfif_emit) also take the
+// component count NC (3, or 1): a one-component (grey) file is <1, 1, 1>, its scan is not interleaved, so its MCU is one block, the blocks
+// are the component's ceil(W / 8) x ceil(H / 8) in raster order and none is a dummy; it uses the luma tables (slots 0 and 1) alone, and
+// k_jfif_tables / k_jfif_annexk leave the chroma slots of such a segment untouched (JfifGeom::ncomp).  Colour, DCT, quantisation and
+// reconstruction (k_jfif_fdct, k_jfif_quant, k_jfif_idct, k_jfif_rgb) are three-component only: grey coefficients come from
+// jfifmany.hip or jfiftrans.hip.
 // Stages (one launch each, every quality of a call in the same launch after the first):
 //   k_jfif_fdct     one thread per 8 x 8 block of one image: colour, edge padding, chroma down-sampling, islow FDCT -> int32 (zigzag order)
 //   k_jfif_quant    one thread per (quality, image, block): quantise, resolve dummy blocks, count the block's Huffman bits (Annex K)
@@ -125,10 +130,10 @@ __device__ __forceinline__ int jf_qdc(const JfifGeom &g, const int *dct_img, con
     return jf_quant(dct_img[(m * (HS * VS + 2) + k) * 64], p.qt[k >= HS * VS][0]);
 }
 // the block of the same component before block (m, k) in scan order, -1 at the start of the scan
-template <int HS, int VS>
+template <int HS, int VS, int NC = 3>
 __device__ __forceinline__ long long jf_prev(long long m, int k)
 {
-    constexpr int NL = HS * VS, BPM = NL + 2;
+    constexpr int NL = HS * VS, BPM = NL + NC - 1;
     if (k >= 1 && k < NL) return m * BPM + k - 1;
     if (m == 0) return -1;
     return k == 0 ? (m - 1) * BPM + NL - 1 : (m - 1) * BPM + k;
@@ -248,10 +253,10 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_quant(JfifGeom g, const Jfi
 // ---- optimize: the file's own Huffman tables -----------------------------------------------------------------------------------------
 // (a1) the symbols k_jfif_emit will write for every block, dummies included: DC categories, (run << 4) | size, ZRL per 16 zeros, EOB.
 // grid (blocks of one segment, segment); counts are private to a wave in LDS, then one 64-bit add per non-zero bin.
-template <int HS, int VS>
+template <int HS, int VS, int NC>
 __global__ __launch_bounds__(kJfThreads) void k_jfif_hist(JfifGeom g, const short *__restrict__ coef, unsigned long long *__restrict__ hist)
 {
-    constexpr int NL = HS * VS, BPM = NL + 2, kWaves = kJfThreads / 64;
+    constexpr int NL = HS * VS, BPM = NL + NC - 1, kWaves = kJfThreads / 64, kTables = NC == 1 ? 2 : 4;
     __shared__ unsigned cnt[kWaves][4][kJhSymbols];
     for (int i = threadIdx.x; i < kWaves * 4 * kJhSymbols; i += kJfThreads) (&cnt[0][0][0])[i] = 0;
     __syncthreads();
@@ -261,7 +266,7 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_hist(JfifGeom g, const shor
         const int k = (int)(blk % BPM);
         unsigned(*h)[kJhSymbols] = cnt[threadIdx.x / 64] + (k >= NL ? 2 : 0);      // [0] DC, [1] AC of the block's component class
         const short *c = coef + (seg * g.nblk + blk) * 64;
-        const long long pb = jf_prev<HS, VS>(m, k);
+        const long long pb = jf_prev<HS, VS, NC>(m, k);
         atomicAdd(&h[0][jf_cat(c[0] - (pb < 0 ? 0 : coef[(seg * g.nblk + pb) * 64]))], 1u);
         int run = 0;
         for (int i = 1; i < 64; i++) {
@@ -274,7 +279,7 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_hist(JfifGeom g, const shor
         if (run) atomicAdd(&h[1][0], 1u);
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < 4 * kJhSymbols; i += kJfThreads) {
+    for (int i = threadIdx.x; i < kTables * kJhSymbols; i += kJfThreads) {
         unsigned n = 0;
         for (int w = 0; w < kWaves; w++) n += (&cnt[w][0][0])[i];
         if (n) atomicAdd(hist + seg * 4 * kJhSymbols + i, (unsigned long long)n);
@@ -282,7 +287,8 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_hist(JfifGeom g, const shor
 }
 
 // (a2) one workgroup per (quality, image), one wave per table (DC luma, AC luma, DC chroma, AC chroma): the table (jh_build, serial on
-// the wave's first lane with its work arrays in LDS), its codes, and the file's markers: those of its quality with these four DHTs
+// the wave's first lane with its work arrays in LDS), its codes, and the file's markers: those of its quality with these four DHTs.
+// A one-component file has the two luma tables alone: the chroma waves only keep the barriers, and the SOS it ends with is shorter
 __global__ __launch_bounds__(kJfThreads) void k_jfif_tables(JfifGeom g, const JfifParams *__restrict__ par, const unsigned long long *__restrict__ hist,
                                                             unsigned *__restrict__ codes, unsigned char *__restrict__ fhdr, int *__restrict__ fhdr_len)
 {
@@ -292,33 +298,37 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_tables(JfifGeom g, const Jf
     __shared__ int nsym[4];
     const long long seg = blockIdx.x;
     const int t = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int ntab = g.ncomp == 1 ? 2 : 4, sos = jfif_sos_bytes(g.ncomp == 1 ? 1 : 3);
+    const bool mine = t < ntab;                              // uniform over the wave
     unsigned *tc = codes + (seg * 4 + t) * 256;
-    for (int i = lane; i < 256; i += 64) {
+    for (int i = lane; mine && i < 256; i += 64) {
         work[t].freq[i] = (long long)hist[(seg * 4 + t) * kJhSymbols + i];
         tc[i] = 0;
     }
     __syncthreads();
-    if (lane == 0) nsym[t] = jh_build(work[t], bits[t], vals[t]);
+    if (mine && lane == 0) nsym[t] = jh_build(work[t], bits[t], vals[t]);
     __syncthreads();
-    if (lane == 0) jh_codes(bits[t], vals[t], tc);
+    if (mine && lane == 0) jh_codes(bits[t], vals[t], tc);
     const JfifParams &p = par[seg / g.B];
     unsigned char *o = fhdr + seg * kJfifHdrMax;
     for (int i = threadIdx.x; i < p.dht_off; i += kJfThreads) o[i] = p.hdr[i];
     int off = p.dht_off, end = p.dht_off;
-    for (int u = 0; u < 4; u++) {
+    for (int u = 0; u < ntab; u++) {
         if (u < t) off += 5 + 16 + nsym[u];
         end += 5 + 16 + nsym[u];
     }
-    if (end + 14 <= kJfifHdrMax) {                           // always: at most 12 DC and 162 AC symbols, the Annex K sizes
-        const int n = nsym[t];
-        if (lane == 0) {
-            o[off] = 0xFF; o[off + 1] = 0xC4; o[off + 2] = (unsigned char)((19 + n) >> 8); o[off + 3] = (unsigned char)((19 + n) & 255);
-            o[off + 4] = (unsigned char)(((t & 1) << 4) | (t >> 1));
+    if (end + sos <= kJfifHdrMax) {                          // always: at most 12 DC and 162 AC symbols, the Annex K sizes
+        if (mine) {
+            const int n = nsym[t];
+            if (lane == 0) {
+                o[off] = 0xFF; o[off + 1] = 0xC4; o[off + 2] = (unsigned char)((19 + n) >> 8); o[off + 3] = (unsigned char)((19 + n) & 255);
+                o[off + 4] = (unsigned char)(((t & 1) << 4) | (t >> 1));
+            }
+            for (int i = lane; i < 16 + n; i += 64) o[off + 5 + i] = i < 16 ? bits[t][i] : vals[t][i - 16];
         }
-        for (int i = lane; i < 16 + n; i += 64) o[off + 5 + i] = i < 16 ? bits[t][i] : vals[t][i - 16];
-        if (threadIdx.x < 14) o[end + threadIdx.x] = p.hdr[p.hdr_len - 14 + threadIdx.x];      // SOS
+        if (threadIdx.x < sos) o[end + threadIdx.x] = p.hdr[p.hdr_len - sos + threadIdx.x];      // SOS
     }
-    if (threadIdx.x == 0) fhdr_len[seg] = end + 14 <= kJfifHdrMax ? end + 14 : 0;
+    if (threadIdx.x == 0) fhdr_len[seg] = end + sos <= kJfifHdrMax ? end + sos : 0;
 }
 
 // in the place of (a1) and (a2) for files that carry the Annex K tables but run the table-driven stages (launch_jfif_entropy_annexk):
@@ -332,8 +342,10 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_annexk(JfifGeom g, const Jf
     unsigned *tc = codes + seg * 4 * 256;
     tc[i] = i < 16 ? k_dc_luma[i] : 0;
     tc[256 + i] = k_ac_luma[i];
-    tc[512 + i] = i < 16 ? k_dc_chroma[i] : 0;
-    tc[768 + i] = k_ac_chroma[i];
+    if (g.ncomp != 1) {                                      // a one-component file has no chroma slots to fill
+        tc[512 + i] = i < 16 ? k_dc_chroma[i] : 0;
+        tc[768 + i] = k_ac_chroma[i];
+    }
     const JfifParams &p = par[seg / g.B];
     const int n = min(max(p.hdr_len, 0), kJfifHdrMax);
     for (int j = i; j < n; j += kJfThreads) fhdr[seg * kJfifHdrMax + j] = p.hdr[j];
@@ -341,18 +353,18 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_annexk(JfifGeom g, const Jf
 }
 
 // (a3) every block's bits under its file's tables (k_jfif_quant counted them with the Annex K lengths)
-template <int HS, int VS>
+template <int HS, int VS, int NC>
 __global__ __launch_bounds__(kJfThreads) void k_jfif_count(JfifGeom g, const short *__restrict__ coef, const unsigned *__restrict__ codes,
                                                            int *__restrict__ lens)
 {
-    constexpr int NL = HS * VS, BPM = NL + 2;
+    constexpr int NL = HS * VS, BPM = NL + NC - 1;
     const long long idx = (long long)blockIdx.x * kJfThreads + threadIdx.x;
     if (idx >= (long long)g.nq * g.B * g.nblk) return;
     const long long seg = idx / g.nblk, blk = idx % g.nblk, m = blk / BPM;
     const int k = (int)(blk % BPM);
     const JfCodes hc = jf_file_codes(codes, seg, k >= NL);
     const short *c = coef + idx * 64;
-    const long long pb = jf_prev<HS, VS>(m, k);
+    const long long pb = jf_prev<HS, VS, NC>(m, k);
     const int dcat = jf_cat(c[0] - (pb < 0 ? 0 : coef[(seg * g.nblk + pb) * 64]));
     int bits = (int)(hc.dc[dcat] & 255) + dcat, run = 0;
     for (int i = 1; i < 64; i++) {
@@ -429,19 +441,19 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_zero(JfifGeom g, const long
 
 // (c) every block's code string at its bit offset
 // kOpt: the codes are the file's own (k_jfif_tables) instead of the Annex K constants
-template <int HS, int VS, bool kOpt>
+template <int HS, int VS, bool kOpt, int NC>
 __global__ __launch_bounds__(kJfThreads) void k_jfif_emit(JfifGeom g, const short *__restrict__ coef, const long long *__restrict__ boff,
                                                           const long long *__restrict__ btot, const unsigned *__restrict__ codes,
                                                           unsigned *__restrict__ stream)
 {
-    constexpr int NL = HS * VS, BPM = NL + 2;
+    constexpr int NL = HS * VS, BPM = NL + NC - 1;
     const long long idx = (long long)blockIdx.x * kJfThreads + threadIdx.x;
     if (idx >= (long long)g.nq * g.B * g.nblk) return;
     const long long seg = idx / g.nblk, blk = idx % g.nblk, m = blk / BPM;
     const int k = (int)(blk % BPM);
     const JfCodes hc = kOpt ? jf_file_codes(codes, seg, k >= NL) : jf_codes(k >= NL);
     const short *c = coef + idx * 64;
-    const long long pb = jf_prev<HS, VS>(m, k);
+    const long long pb = jf_prev<HS, VS, NC>(m, k);
     JfBits bw(stream + seg * g.stream_words, boff[idx], g.stream_words);
     const int diff = c[0] - (pb < 0 ? 0 : coef[(seg * g.nblk + pb) * 64]);
     const int dcat = jf_cat(diff);
@@ -616,18 +628,20 @@ static const unsigned char kDht_ac_chroma[178] = {
 static const unsigned char kLumaBase[64] = { 16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99 };
 static const unsigned char kChromaBase[64] = { 17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99 };
 
-bool jfif_geom(int B, int H, int W, int nq, JfifGeom &g, int ss, int opt)
+bool jfif_geom(int B, int H, int W, int nq, JfifGeom &g, int ss, int opt, int ncomp)
 {
     if (B < 1 || nq < 1 || H < 1 || W < 1 || H > 65535 || W > 65535 || (long long)B * nq > 65535) return false;      // segments index grid.y
+    if (ncomp != 1 && ncomp != 3) return false;
+    if (ncomp == 1) ss = 0;                                  // one component is sampled 1 x 1
     if (ss < 0 || ss > 2) return false;
     g.B = B; g.H = H; g.W = W; g.nq = nq;
-    g.hs = ss == 0 ? 1 : 2; g.vs = ss == 2 ? 2 : 1; g.opt = opt ? 1 : 0; g.pad_ = 0;
+    g.hs = ss == 0 ? 1 : 2; g.vs = ss == 2 ? 2 : 1; g.opt = opt ? 1 : 0; g.ncomp = ncomp;
     g.mcux = (W + 8 * g.hs - 1) / (8 * g.hs); g.mcuy = (H + 8 * g.vs - 1) / (8 * g.vs);
     g.ybx = (W + 7) / 8; g.yby = (H + 7) / 8;
     g.yw = 8 * g.hs * g.mcux; g.yh = 8 * g.vs * g.mcuy;   // luma planes cover every MCU (dummy blocks are never written)
     g.cw = 8 * g.mcux; g.ch = 8 * g.mcuy;
     g.n_mcu = (long long)g.mcux * g.mcuy;
-    g.nblk = (g.hs * g.vs + 2) * g.n_mcu;
+    g.nblk = (g.hs * g.vs + ncomp - 1) * g.n_mcu;
     g.stream_words = (g.nblk * (g.opt ? kJfifBlockWordsOpt : kJfifBlockWords) + 2 + 15) / 16 * 16;
     g.n_chunks = g.stream_words * 4 / kJfChunk;
     g.plane_bytes = ((long long)g.yh * g.yw + 2LL * g.ch * g.cw + 255) / 256 * 256;
@@ -708,8 +722,9 @@ void jfif_quant_tables(int q, int luma[64], int chroma[64])
 
 static const unsigned char kZzHost[64] = { AEJ_ZIGZAG_8X8 };
 
-void jfif_params_host(int q, int H, int W, JfifParams &p, int ss)
+void jfif_params_host(int q, int H, int W, JfifParams &p, int ss, int ncomp)
 {
+    const int nt = ncomp == 1 ? 1 : 2;                       // a grey file: the luma quantiser and the two luma Huffman tables alone
     int t[2][64];
     jfif_quant_tables(q, t[0], t[1]);
     for (int c = 0; c < 2; c++)
@@ -721,24 +736,27 @@ void jfif_params_host(int q, int H, int W, JfifParams &p, int ss)
     put({ 0xFF, 0xD8 });
     seg(0xE0, 14);                                                        // JFIF 1.01, no units, 1:1 density, no thumbnail
     put({ 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0 });
-    for (int c = 0; c < 2; c++) {
+    for (int c = 0; c < nt; c++) {
         seg(0xDB, 65);
         put({ c });
         for (int i = 0; i < 64; i++) o[n++] = (unsigned char)p.qt[c][i];
     }
-    seg(0xC0, 15);
-    put({ 8, H >> 8, H & 255, W >> 8, W & 255, 3, 1, ss == 0 ? 0x11 : ss == 1 ? 0x21 : 0x22, 0, 2, 0x11, 1, 3, 0x11, 1 });
+    seg(0xC0, jfif_sof_bytes(ncomp == 1 ? 1 : 3) - 4);
+    if (ncomp == 1) put({ 8, H >> 8, H & 255, W >> 8, W & 255, 1, 1, 0x11, 0 });
+    else put({ 8, H >> 8, H & 255, W >> 8, W & 255, 3, 1, ss == 0 ? 0x11 : ss == 1 ? 0x21 : 0x22, 0, 2, 0x11, 1, 3, 0x11, 1 });
     p.dht_off = n;
     const struct { int id; const unsigned char *t; int len; } dht[4] = {
         { 0x00, kDht_dc_luma, (int)sizeof kDht_dc_luma }, { 0x10, kDht_ac_luma, (int)sizeof kDht_ac_luma },
         { 0x01, kDht_dc_chroma, (int)sizeof kDht_dc_chroma }, { 0x11, kDht_ac_chroma, (int)sizeof kDht_ac_chroma } };
-    for (const auto &d : dht) {
+    for (int t = 0; t < 2 * nt; t++) {
+        const auto &d = dht[t];
         seg(0xC4, 1 + d.len);
         put({ d.id });
         for (int i = 0; i < d.len; i++) o[n++] = d.t[i];
     }
-    seg(0xDA, 10);
-    put({ 3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0 });
+    seg(0xDA, jfif_sos_bytes(ncomp == 1 ? 1 : 3) - 4);
+    if (ncomp == 1) put({ 1, 1, 0x00, 0, 63, 0 });
+    else put({ 3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0 });
     p.hdr_len = n;
 }
 
@@ -746,7 +764,7 @@ static unsigned jf_blocks(long long n) { return (unsigned)((n + kJfThreads - 1) 
 
 // the stages from w.coef to the file lengths and offsets (k_jfif_quant has left the Annex K bit counts in w.lens)
 // annexk (requires g.opt): the table-driven stages under the Annex K tables -- k_jfif_annexk in the place of histogram and tables
-template <int HS, int VS>
+template <int HS, int VS, int NC = 3>
 static hipError_t jf_entropy(hipStream_t st, const JfifGeom &g, const JfifBufs &w, long long *lengths, long long *offsets, bool annexk = false)
 {
     const long long segs = (long long)g.nq * g.B, nb = segs * g.nblk, nc = segs * g.n_chunks;
@@ -756,18 +774,18 @@ static hipError_t jf_entropy(hipStream_t st, const JfifGeom &g, const JfifBufs &
     } else if (g.opt) {
         const hipError_t e = hipMemsetAsync(w.hist, 0, (size_t)segs * 4 * kJhSymbols * 8, st);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((k_jfif_hist<HS, VS>), dim3(jf_blocks(g.nblk), (unsigned)segs), dim3(kJfThreads), 0, st, g, w.coef, w.hist);
+        hipLaunchKernelGGL((k_jfif_hist<HS, VS, NC>), dim3(jf_blocks(g.nblk), (unsigned)segs), dim3(kJfThreads), 0, st, g, w.coef, w.hist);
         hipLaunchKernelGGL(k_jfif_tables, dim3((unsigned)segs), dim3(kJfThreads), 0, st, g, w.par, w.hist, w.codes, w.fhdr, w.fhdr_len);
     }
     if (g.opt)
-        hipLaunchKernelGGL((k_jfif_count<HS, VS>), dim3(jf_blocks(nb)), dim3(kJfThreads), 0, st, g, w.coef, w.codes, w.lens);
+        hipLaunchKernelGGL((k_jfif_count<HS, VS, NC>), dim3(jf_blocks(nb)), dim3(kJfThreads), 0, st, g, w.coef, w.codes, w.lens);
     hipLaunchKernelGGL(k_jfif_scan, dim3((unsigned)segs), dim3(kJfScanThreads), 0, st, w.lens, g.nblk, w.boff, w.btot);
     hipLaunchKernelGGL(k_jfif_zero, dim3((unsigned)((g.stream_words + kJfThreads - 1) / kJfThreads), (unsigned)segs), dim3(kJfThreads), 0, st, g,
                        w.btot, w.stream);
     if (g.opt)
-        hipLaunchKernelGGL((k_jfif_emit<HS, VS, true>), dim3(jf_blocks(nb)), dim3(kJfThreads), 0, st, g, w.coef, w.boff, w.btot, w.codes, w.stream);
+        hipLaunchKernelGGL((k_jfif_emit<HS, VS, true, NC>), dim3(jf_blocks(nb)), dim3(kJfThreads), 0, st, g, w.coef, w.boff, w.btot, w.codes, w.stream);
     else
-        hipLaunchKernelGGL((k_jfif_emit<HS, VS, false>), dim3(jf_blocks(nb)), dim3(kJfThreads), 0, st, g, w.coef, w.boff, w.btot, w.codes, w.stream);
+        hipLaunchKernelGGL((k_jfif_emit<HS, VS, false, NC>), dim3(jf_blocks(nb)), dim3(kJfThreads), 0, st, g, w.coef, w.boff, w.btot, w.codes, w.stream);
     hipLaunchKernelGGL(k_jfif_ffcount, dim3(jf_blocks(nc)), dim3(kJfThreads), 0, st, g, w.btot, w.stream, w.ffcnt);
     hipLaunchKernelGGL(k_jfif_scan, dim3((unsigned)segs), dim3(kJfScanThreads), 0, st, w.ffcnt, g.n_chunks, w.ffpre, w.fftot);
     hipLaunchKernelGGL(k_jfif_layout, dim3(1), dim3(1), 0, st, g, w.par, w.fhdr_len, w.btot, w.fftot, lengths, offsets, w.total);
@@ -798,6 +816,7 @@ static hipError_t jf_encode(hipStream_t st, const JfifGeom &g, const JfifBufs &w
 hipError_t launch_jfif_encode(hipStream_t st, const JfifGeom &g, const JfifBufs &w, const JfifParams *par_host, const unsigned char *rgb,
                               unsigned char *out, unsigned long long cap, long long *lengths, long long *offsets)
 {
+    if (g.ncomp != 3) return hipErrorInvalidValue;           // the same-size encoder is three-component
     if (g.hs == 1) return jf_encode<1, 1>(st, g, w, par_host, rgb, out, cap, lengths, offsets);
     if (g.vs == 1) return jf_encode<2, 1>(st, g, w, par_host, rgb, out, cap, lengths, offsets);
     return jf_encode<2, 2>(st, g, w, par_host, rgb, out, cap, lengths, offsets);
@@ -807,6 +826,7 @@ hipError_t launch_jfif_encode(hipStream_t st, const JfifGeom &g, const JfifBufs 
 // optimised entropy stages up to the lengths, and the scatter as a launch of its own once the caller has placed the files
 hipError_t launch_jfif_entropy(hipStream_t st, const JfifGeom &g, const JfifBufs &w, long long *lengths, long long *offsets)
 {
+    if (g.ncomp == 1) return jf_entropy<1, 1, 1>(st, g, w, lengths, offsets);
     if (g.hs == 1) return jf_entropy<1, 1>(st, g, w, lengths, offsets);
     if (g.vs == 1) return jf_entropy<2, 1>(st, g, w, lengths, offsets);
     return jf_entropy<2, 2>(st, g, w, lengths, offsets);
@@ -814,6 +834,7 @@ hipError_t launch_jfif_entropy(hipStream_t st, const JfifGeom &g, const JfifBufs
 
 hipError_t launch_jfif_entropy_annexk(hipStream_t st, const JfifGeom &g, const JfifBufs &w, long long *lengths, long long *offsets)
 {
+    if (g.ncomp == 1) return jf_entropy<1, 1, 1>(st, g, w, lengths, offsets, true);
     if (g.hs == 1) return jf_entropy<1, 1>(st, g, w, lengths, offsets, true);
     if (g.vs == 1) return jf_entropy<2, 1>(st, g, w, lengths, offsets, true);
     return jf_entropy<2, 2>(st, g, w, lengths, offsets, true);
@@ -838,6 +859,7 @@ static hipError_t jf_coefs(hipStream_t st, const JfifGeom &g, const JfifBufs &w,
 
 hipError_t launch_jfif_coefs(hipStream_t st, const JfifGeom &g, const JfifBufs &w, const JfifParams *par_host, const unsigned char *rgb)
 {
+    if (g.ncomp != 3) return hipErrorInvalidValue;
     if (g.hs == 1) return jf_coefs<1, 1>(st, g, w, par_host, rgb);
     if (g.vs == 1) return jf_coefs<2, 1>(st, g, w, par_host, rgb);
     return jf_coefs<2, 2>(st, g, w, par_host, rgb);
@@ -854,6 +876,7 @@ static hipError_t jf_recon(hipStream_t st, const JfifGeom &g, const JfifBufs &w,
 
 hipError_t launch_jfif_recon(hipStream_t st, const JfifGeom &g, const JfifBufs &w, unsigned char *rgb_out)
 {
+    if (g.ncomp != 3) return hipErrorInvalidValue;
     if (g.hs == 1) return jf_recon<1, 1>(st, g, w, rgb_out);
     if (g.vs == 1) return jf_recon<2, 1>(st, g, w, rgb_out);
     return jf_recon<2, 2>(st, g, w, rgb_out);

@@ -16,6 +16,9 @@
 // A luma block beyond the component's ceil(w / 8) x ceil(h / 8) real blocks is a dummy: it only fills out an edge MCU, and is written as
 // libjpeg writes it (jctrans.c): AC zero, DC that of the block before it in the MCU.  The first block of an MCU and its chroma blocks are
 // always real, so the walk back ends, and a real output block always maps to a real source block.
+//
+// A one-component (grey) file (JxGeom::nc = 1) is sampled 1 x 1 whatever its frame header says, its MCU is its one block and it has no
+// dummies: the same mapping with hs = vs = 1 and no chroma blocks, so every transform is allowed and a mirrored axis is a multiple of 8.
 #pragma once
 #include <stdint.h>
 
@@ -33,6 +36,7 @@ struct JxGeom {                        // one file's transform (host-computed by
     int sW, sH, shs, svs, smcux, smcuy;      // source frame: size, luma sampling factors, MCU grid
     int oW, oH, ohs, ovs, omcux, omcuy;      // output frame
     int n_src, n_out;                  // blocks of the two MCU grids, dummies included
+    int nc;                            // components: 3, or 1
 };
 
 AEJ_HD inline bool jx_transposes(int xf) { return xf == kJxTranspose || xf == kJxTransverse || xf == kJxRot90 || xf == kJxRot270; }
@@ -40,9 +44,11 @@ AEJ_HD inline bool jx_mirrors_x(int xf) { return xf == kJxFlipH || xf == kJxTran
 AEJ_HD inline bool jx_mirrors_y(int xf) { return xf == kJxFlipV || xf == kJxTransverse || xf == kJxRot180 || xf == kJxRot270; }
 
 // -> kJxOk and g, or why not.  Sampling: 1x1, 2x1 or 2x2 luma over 1x1 chroma; a transposed 2x1 would be 1x2 (4:4:0): kJxLayout.
-AEJ_HD inline int jx_geom(int H, int W, int hs, int vs, int xf, int trim, JxGeom &g)
+AEJ_HD inline int jx_geom(int H, int W, int hs, int vs, int xf, int trim, JxGeom &g, int nc = 3)
 {
-    if (H < 1 || W < 1 || H > 65535 || W > 65535 || xf < 0 || xf > 7) return kJxBadArg;
+    if (H < 1 || W < 1 || H > 65535 || W > 65535 || xf < 0 || xf > 7 || (nc != 1 && nc != 3)) return kJxBadArg;
+    if (nc == 1) hs = vs = 1;                                // the source's sampling factors mean nothing for one component
+    g.nc = nc;
     if (!((hs == 1 && vs == 1) || (hs == 2 && (vs == 1 || vs == 2)))) return kJxBadArg;
     g.xf = xf; g.t = jx_transposes(xf); g.mx = jx_mirrors_x(xf); g.my = jx_mirrors_y(xf);
     if (g.t && hs != vs) return kJxLayout;
@@ -57,8 +63,8 @@ AEJ_HD inline int jx_geom(int H, int W, int hs, int vs, int xf, int trim, JxGeom
         if (g.oW < 1 || g.oH < 1) return kJxTrimsToZero;
     }
     g.omcux = (g.oW + mw - 1) / mw; g.omcuy = (g.oH + mh - 1) / mh;
-    g.n_src = (hs * vs + 2) * g.smcux * g.smcuy;             // <= 3 * 8192 * 8192: an int holds it
-    g.n_out = (g.ohs * g.ovs + 2) * g.omcux * g.omcuy;
+    g.n_src = (hs * vs + nc - 1) * g.smcux * g.smcuy;        // <= 3 * 8192 * 8192: an int holds it
+    g.n_out = (g.ohs * g.ovs + nc - 1) * g.omcux * g.omcuy;
     return kJxOk;
 }
 
@@ -67,7 +73,7 @@ AEJ_HD inline int jx_geom(int H, int W, int hs, int vs, int xf, int trim, JxGeom
 // real blocks (the transcoder proper, which carries a source's dummy blocks as they are, does not come here).
 AEJ_HD inline int jx_source_block(const JxGeom &g, int ob, bool *dummy)
 {
-    const int nl = g.ohs * g.ovs, bpm = nl + 2, mcu = ob / bpm;
+    const int nl = g.ohs * g.ovs, bpm = nl + g.nc - 1, mcu = ob / bpm;
     int k = ob - mcu * bpm;
     const int my = mcu / g.omcux, mx = mcu - my * g.omcux;
     int by = my, bx = mx, ch = 1, cv = 1;                    // block coordinates in the component; its sampling factors
@@ -88,7 +94,7 @@ AEJ_HD inline int jx_source_block(const JxGeom &g, int ob, bool *dummy)
     const int sh = g.t ? cv : ch, sv = g.t ? ch : cv;
     const int smy = sby / sv, smx = sbx / sh;
     const int sk = k < nl ? (sby - smy * sv) * sh + (sbx - smx * sh) : g.shs * g.svs + (k - nl);
-    return (smy * g.smcux + smx) * (g.shs * g.svs + 2) + sk;
+    return (smy * g.smcux + smx) * (g.shs * g.svs + g.nc - 1) + sk;
 }
 
 // Output natural index n = 8 v + u -> source natural index; *negate: the coefficient changes sign.

@@ -1,8 +1,9 @@
 // jfifmany.hip -- the ragged front end of the standard-JPEG encoder: packed RGB images of any sizes, each with its own quality, to the
 // quantised coefficients the entropy coders read, every image of a call in one launch (aej_jfif_many_*, include/aej.h).  The files are
 // those jfif.hip writes for each image alone: the arithmetic is jfif_arith.h's, shared with it, and the entropy stages, placement and
-// scatter are the transcoder's (launch_jfiftrans_chains, jfiftrans.hip): images are grouped by (H, W, sampling), a group runs one
-// chain, every image of it one "quality" slot with its own quantisers and markers (jfif_params_host: Pillow's, not the transcoder's).
+// scatter are the transcoder's (launch_jfiftrans_chains, jfiftrans.hip): images are grouped by (H, W, sampling, components), a group
+// runs one chain, every image of it one "quality" slot with its own quantisers and markers (jfif_params_host: Pillow's, not the
+// transcoder's).  An image is packed RGB, or grey (JmGeom::nc = 1: packed uint8 [H][W], a one-component file); both kinds mix in a call.
 //
 //   k_jm_coefs      eight lanes per 8 x 8 block, 32 blocks per workgroup, every block of every image in one grid.  A lane group finds
 //                   its image by binary search over the images' first blocks (as jt_find_file) and its block's place and kind from the
@@ -12,11 +13,13 @@
 //                   and quantises it with the image's own table -- each image has one quality, so no int32 DCT plane is kept, which is
 //                   where this differs from k_jfif_fdct + k_jfif_quant -- into the block's zigzag order in LDS; then every lane stores
 //                   16 of the block's 128 bytes, so a wave writes 1 KiB contiguously.  A dummy luma block of an edge MCU transforms the
-//                   real block before it in the MCU and keeps its DC alone, as libjpeg writes it.
+//                   real block before it in the MCU and keeps its DC alone, as libjpeg writes it.  A grey image's lane groups take
+//                   the same steps with jm_block's and jm_row's one-component branch: raster-order blocks, the sample as Y, the luma
+//                   quantiser.
 //   (then)          launch_jfiftrans_chains: per group histogram / tables (optimize), k_jfif_annexk (not), or the progressive chain
 // Bounds: every index derives from the host-computed JmImage records, checked by jfifmany_plan before any launch.  A lane group whose
 // block lies at or past the call's block count, or past its image's n_blocks, reads and writes nothing (it still reaches the barriers).
-// jm_row clamps every row to [0, H) and column to [0, W), so reads stay inside [src_offset, src_offset + 3 H W) of the source, which
+// jm_row clamps every row to [0, H) and column to [0, W), so reads stay inside [src_offset, src_offset + 3 H W) (grey: H W) of the source, which
 // the host has checked against the buffer's size; a block's stores are the 128 bytes at dst + 64 b with b < n_blocks, inside the
 // n_blocks * 64 shorts of the image's segment of its group's w.coef (jfiftrans_carve).
 #include "aej_common.h"
@@ -58,7 +61,7 @@ __global__ __launch_bounds__(kJmThreads) void k_jm_coefs(const JmImage *__restri
         I = images + jm_find_image(images, n, t);
         b = t - I->blk_base;
         g = I->g;
-        g.hs = HS; g.vs = VS;                                // the call's sampling, known at compile time
+        if (g.nc != 1) { g.hs = HS; g.vs = VS; }             // the call's sampling, known at compile time (a grey image is 1 x 1)
         live = b < g.n_blocks;                               // never false: the images' ranges tile [0, n_blocks)
     }
     if (live) {
@@ -95,10 +98,10 @@ static void jm_tables(int quality, unsigned short qt[2][64])      // zigzag orde
         for (int i = 0; i < 64; i++) qt[c][i] = (unsigned short)t[c][kJmZzHost[i]];
 }
 
-long long jfifmany_coefs_host(int W, int H, int quality, int ss, const unsigned char *rgb, short *dst)
+long long jfifmany_coefs_host(int W, int H, int quality, int ss, const unsigned char *rgb, short *dst, int ncomp)
 {
     JmGeom g;
-    if (!jm_geom(H, W, ss, g) || quality < 1 || quality > 100) return -1;
+    if (!jm_geom(H, W, ss, g, ncomp) || quality < 1 || quality > 100) return -1;
     if (!rgb || !dst) return g.n_blocks;
     unsigned short qt[2][64];
     jm_tables(quality, qt);
@@ -116,19 +119,22 @@ int jfifmany_plan(const aej_jfif_many_desc *descs, int n, long long src_bytes, i
     plan.t.annexk = !prog && !opt;
     plan.t.files.assign(n, JtFile{});
     plan.images.assign(n, JmImage{});
+    plan.hs = ss == 0 ? 1 : 2; plan.vs = ss == 2 ? 2 : 1;
     for (int i = 0; i < n; i++) {                            // every descriptor before any grouping
         const aej_jfif_many_desc &d = descs[i];
         if (d.width < 1 || d.width > 65535 || d.height < 1 || d.height > 65535) return refuse(i, "width and height in 1..65535 required");
         if (d.quality < 1 || d.quality > 100) return refuse(i, "quality outside 1..100");
-        const long long bytes = 3LL * d.width * d.height;
+        if (d.components != 0 && d.components != 1 && d.components != 3) return refuse(i, "components other than 0 (three), 1 or 3");
+        const long long bytes = (d.components == 1 ? 1LL : 3LL) * d.width * d.height;
         if (src_bytes >= 0 && (d.src_offset < 0 || d.src_offset > src_bytes || bytes > src_bytes - d.src_offset))
             return refuse(i, "pixels outside the source buffer");
     }
     for (int i = 0; i < n; i++) {
         const aej_jfif_many_desc &d = descs[i];
         JmImage &I = plan.images[i];
-        if (!jm_geom(d.height, d.width, ss, I.g)) return refuse(i, "width and height in 1..65535 required");
-        JtGroup *grp = jfiftrans_group(plan.t, d.height, d.width, I.g.hs, I.g.vs);
+        const int nc = d.components == 1 ? 1 : 3;
+        if (!jm_geom(d.height, d.width, ss, I.g, nc)) return refuse(i, "width and height in 1..65535 required");
+        JtGroup *grp = jfiftrans_group(plan.t, d.height, d.width, I.g.hs, I.g.vs, nc);
         if (!grp || grp->g.nblk != I.g.n_blocks) return refuse(i, "a size the coders refuse");
         I.blk_base = plan.t.n_blocks;
         I.src_offset = d.src_offset;
@@ -142,8 +148,8 @@ int jfifmany_plan(const aej_jfif_many_desc *descs, int n, long long src_bytes, i
         for (size_t k = 0; k < c.files.size(); k++) {        // Pillow's markers of this image's quality, size and layout
             const aej_jfif_many_desc &d = descs[c.files[k]];
             JfifParams &p = c.par[k];
-            jfif_params_host(d.quality, d.height, d.width, p, ss);
-            if (prog) p.hdr[p.dht_off - 19 + 1] = 0xC2;      // the frame header is the last segment before the tables: SOF0 -> SOF2
+            jfif_params_host(d.quality, d.height, d.width, p, ss, c.g.ncomp);
+            if (prog) p.hdr[p.dht_off - jfif_sof_bytes(c.g.ncomp) + 1] = 0xC2;      // the frame header is the last segment before the tables: SOF0 -> SOF2
         }
     }
     return -1;
@@ -162,7 +168,7 @@ unsigned long long jfifmany_carve(void *base, JmPlan &plan)
 hipError_t launch_jfifmany(hipStream_t st, JmPlan &plan, const unsigned char *src, unsigned char *out, unsigned long long cap, long long *lengths,
                            long long *offsets)
 {
-    const int n = (int)plan.images.size(), hs = plan.images[0].g.hs, vs = plan.images[0].g.vs;
+    const int n = (int)plan.images.size(), hs = plan.hs, vs = plan.vs;
     hipError_t e = hipMemcpyAsync(plan.d_images, plan.images.data(), sizeof(JmImage) * n, hipMemcpyHostToDevice, st);
     if (e != hipSuccess) return e;
     if ((e = hipMemcpyAsync(plan.t.d_files, plan.t.files.data(), sizeof(JtFile) * n, hipMemcpyHostToDevice, st)) != hipSuccess) return e;      // k_jt_finish reads it

@@ -3,7 +3,9 @@
 // down-sampling, FDCT and quantisation are jfif.hip's (launch_jfif_coefs); this file codes the quantised coefficients.  The rules of
 // the coder -- what one block emits, how end-of-band runs and deferred correction bits partition a scan -- are jfif_prog_core.h;
 // tests/jfif_progressive_reference.py is libjpeg's serial state machine in Python and tests/test_*jfif_progressive*.py pin both to
-// Pillow's files byte for byte.
+// Pillow's files byte for byte.  A one-component (grey) file takes libjpeg's six-scan script and one DC table (JfpGeom::nchroma = 0, as the
+// testing entry's plain list): its DC scans walk the component's blocks in raster order, which is its MCU order, so every kernel below
+// runs it unchanged -- jfifprog_geom alone knows about it.
 //
 // An item is one block of one scan; a file has T of them, scan after scan (interleaved scans walk the MCU-padded blocks in MCU order,
 // single-component scans the component's own blocks in raster order).  Stages (one launch each for every file of a call):
@@ -434,6 +436,18 @@ bool jfifprog_geom(const JfifGeom &g, JfpGeom &p)
     p = JfpGeom{};
     p.segs = g.nq * g.B; p.B = g.B; p.hs = g.hs; p.vs = g.vs; p.nchroma = 2; p.mcux = g.mcux; p.ybx = g.ybx;
     p.nscan = kJfpMaxScans; p.ntab = kJfpMaxTables; p.raw = 0; p.nblk = g.nblk;
+    if (g.ncomp == 1) {                                      // slot 0 the DC table, 1 .. 4 one per AC scan; every scan walks the nblk real blocks
+        static const int grey[6][6] = { { -1, 0, 0, 0, 1, 0 }, { 0, 1, 5, 0, 2, 1 }, { 0, 6, 63, 0, 2, 2 }, { 0, 1, 63, 2, 1, 3 }, { -1, 0, 0, 1, 0, 0 },
+                                        { 0, 1, 63, 1, 0, 4 } };
+        p.nchroma = 0; p.nscan = 6; p.ntab = 5;
+        for (int i = 0; i < p.nscan; i++) {
+            JfpScan &s = p.sc[i];
+            s.comp = grey[i][0]; s.Ss = grey[i][1]; s.Se = grey[i][2]; s.Ah = grey[i][3]; s.Al = grey[i][4]; s.tbl = grey[i][5];
+            s.n = g.nblk;
+        }
+        jfp_finish_geom(p);
+        return true;
+    }
     // jpeg_simple_progression: { component, Ss, Se, Ah, Al, first table slot }; slots 0 / 1 the DC tables, 2 .. 9 one per AC scan
     static const int script[kJfpMaxScans][6] = { { -1, 0, 0, 0, 1, 0 }, { 0, 1, 5, 0, 2, 2 }, { 2, 1, 63, 0, 1, 3 }, { 1, 1, 63, 0, 1, 4 },
                                                  { 0, 6, 63, 0, 2, 5 }, { 0, 1, 63, 2, 1, 6 }, { -1, 0, 0, 1, 0, 0 }, { 2, 1, 63, 1, 0, 7 },

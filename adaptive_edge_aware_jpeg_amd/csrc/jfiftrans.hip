@@ -3,7 +3,8 @@
 // colour, FDCT or second quantisation in between (aej_jfif_transcode_*, include/aej.h).  What jpegtran -optimize / -progressive do.
 //
 // The decoders leave a file's blocks in MCU order with the dummy edge blocks, natural order inside a block; the coders read the same
-// MCU order, zigzag order inside a block.  Files are grouped by the (H, W, hs, vs) of their output; a group runs the existing entropy stages once, every
+// MCU order, zigzag order inside a block (a one-component file: its real blocks in raster order, both sides).  Files are grouped by the
+// (H, W, hs, vs, components) of their output; a group runs the existing entropy stages once, every
 // file of it one "quality" of a one-image batch, so that JfifParams::hdr -- per quality in the coders -- carries each file's own
 // markers (SOI, JFIF APP0 with the source's density, the source's quantisation tables and frame header).  Stages:
 //   k_jt_bridge     one wave per block: lane z reads natural index k_jt_zz[z] of the source block and writes position z of the coder's
@@ -110,13 +111,14 @@ __global__ __launch_bounds__(kJtThreads) void k_jt_sos_ids(JfpGeom g, const Jfif
     const long long seg = idx / g.nscan;
     const int si = (int)(idx % g.nscan);
     const JfifParams &p = par[seg / g.B];
-    const int nc = g.sc[si].Ss == 0 ? 1 + g.nchroma : 1, hl = fhdr_len[idx], at = hl - (8 + 2 * nc);
-    if (p.dht_off < 19 || p.dht_off > kJfifHdrMax || at < 0 || hl > kJfpPiece) return;
-    const unsigned char *sof = p.hdr + p.dht_off - 19;
+    const int nf = 1 + g.nchroma, sofn = jfif_sof_bytes(nf);                             // components of the frame; its header's bytes
+    const int nc = g.sc[si].Ss == 0 ? nf : 1, hl = fhdr_len[idx], at = hl - (8 + 2 * nc);
+    if (p.dht_off < sofn || p.dht_off > kJfifHdrMax || at < 0 || hl > kJfpPiece) return;
+    const unsigned char *sof = p.hdr + p.dht_off - sofn;
     unsigned char *q = fhdr + idx * kJfpPiece + at;
     for (int c = 0; c < nc; c++) {
         const int k = q[5 + 2 * c] - 1;
-        if (k >= 0 && k < 3) q[5 + 2 * c] = sof[10 + 3 * k];
+        if (k >= 0 && k < nf) q[5 + 2 * c] = sof[10 + 3 * k];
     }
 }
 
@@ -149,8 +151,8 @@ template <class D>
 static void jt_source(const D &d, JtSource &s)
 {
     s = JtSource{};
-    s.width = d.width; s.height = d.height; s.hs = d.hs; s.vs = d.vs;
-    for (int c = 0; c < 3; c++) {
+    s.width = d.width; s.height = d.height; s.hs = d.hs; s.vs = d.vs; s.ncomp = d.ncomp == 1 ? 1 : 3;
+    for (int c = 0; c < s.ncomp; c++) {
         s.comp_id[c] = d.comp_id[c];
         s.comp_tq[c] = d.comp_tq[c];
         for (int i = 0; i < 64; i++) s.qt[c][i] = d.qt[c][i];
@@ -160,22 +162,25 @@ static void jt_source(const D &d, JtSource &s)
 void jfiftrans_source(const aej_jpegdec_desc &d, JtSource &s) { jt_source(d, s); }
 void jfiftrans_source(const aej_jpegprog_frame &f, JtSource &s) { jt_source(f, s); }
 
-// SOI, JFIF 1.01 APP0 with the source's density, one DQT per distinct table id in order of first reference, SOF0 / SOF2
+// SOI, JFIF 1.01 APP0 with the source's density, one DQT per distinct table id in order of first reference, SOF0 / SOF2.  One component:
+// its table as table 0, sampled 1 x 1
 int jfiftrans_prefix_host(const JtSource &s, bool prog, unsigned char *o, int capacity)
 {
     unsigned char b[2 + 18 + 3 * 69 + 19];
     int n = 0;
     auto put = [&](std::initializer_list<int> v) { for (int x : v) b[n++] = (unsigned char)x; };
     put({ 0xFF, 0xD8, 0xFF, 0xE0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, s.units, s.xdensity >> 8, s.xdensity & 255, s.ydensity >> 8, s.ydensity & 255, 0, 0 });
-    for (int c = 0; c < 3; c++) {
+    const int nc = s.ncomp == 1 ? 1 : 3;
+    for (int c = 0; c < nc; c++) {
         bool seen = false;
         for (int e = 0; e < c; e++) seen |= s.comp_tq[e] == s.comp_tq[c];
         if (seen) continue;
-        put({ 0xFF, 0xDB, 0, 67, s.comp_tq[c] & 15 });
+        put({ 0xFF, 0xDB, 0, 67, nc == 1 ? 0 : s.comp_tq[c] & 15 });
         for (int i = 0; i < 64; i++) b[n++] = (unsigned char)s.qt[c][kJtZzHost[i]];
     }
-    put({ 0xFF, prog ? 0xC2 : 0xC0, 0, 17, 8, s.height >> 8, s.height & 255, s.width >> 8, s.width & 255, 3 });
-    for (int c = 0; c < 3; c++) put({ s.comp_id[c], c == 0 ? (s.hs << 4) | s.vs : 0x11, s.comp_tq[c] });
+    put({ 0xFF, prog ? 0xC2 : 0xC0, 0, jfif_sof_bytes(nc) - 2, 8, s.height >> 8, s.height & 255, s.width >> 8, s.width & 255, nc });
+    if (nc == 1) put({ s.comp_id[0], 0x11, 0 });
+    for (int c = 0; c < 3 && nc == 3; c++) put({ s.comp_id[c], c == 0 ? (s.hs << 4) | s.vs : 0x11, s.comp_tq[c] });
     if (n > capacity) return -1;
     memcpy(o, b, n);
     return n;
@@ -204,13 +209,13 @@ void jfiftrans_coefs_host(const JxGeom &g, const short *src, short *dst)
     }
 }
 
-JtGroup *jfiftrans_group(JtPlan &plan, int H, int W, int hs, int vs)
+JtGroup *jfiftrans_group(JtPlan &plan, int H, int W, int hs, int vs, int ncomp)
 {
     for (JtGroup &c : plan.groups)
-        if (c.g.H == H && c.g.W == W && c.g.hs == hs && c.g.vs == vs) return &c;
+        if (c.g.H == H && c.g.W == W && c.g.hs == hs && c.g.vs == vs && c.g.ncomp == ncomp) return &c;
     JtGroup grp{};
     grp.foreign_ids = false;
-    if (!jfif_geom(1, H, W, 1, grp.g, hs == 1 ? 0 : vs == 1 ? 1 : 2, 1)) return nullptr;
+    if (!jfif_geom(1, H, W, 1, grp.g, hs == 1 ? 0 : vs == 1 ? 1 : 2, 1, ncomp)) return nullptr;
     plan.groups.push_back(grp);
     return &plan.groups.back();
 }
@@ -228,7 +233,7 @@ int jfiftrans_close(JtPlan &plan)
     long long first = 0;
     for (JtGroup &c : plan.groups) {
         const int ng = (int)c.files.size(), ss = c.g.hs == 1 ? 0 : c.g.vs == 1 ? 1 : 2;
-        if (!jfif_geom(1, c.g.H, c.g.W, ng, c.g, ss, 1) || (plan.prog && !jfifprog_geom(c.g, c.p))) return c.files[0];
+        if (!jfif_geom(1, c.g.H, c.g.W, ng, c.g, ss, 1, c.g.ncomp) || (plan.prog && !jfifprog_geom(c.g, c.p))) return c.files[0];
         c.first = first;
         c.par.assign(ng, JfifParams{});
         for (int k = 0; k < ng; k++) plan.files[c.files[k]].out_pos = (int)(first + k);
@@ -250,13 +255,13 @@ int jfiftrans_plan(const std::vector<JtSource> &src, const std::vector<long long
     for (int i = 0; i < n; i++) {
         const JtSource &s = src[i];
         JxGeom &x = plan.geom[i];
-        const int rc = jx_geom(s.height, s.width, s.hs, s.vs, xf ? xf[i] : kJxNone, trim, x);
+        const int rc = jx_geom(s.height, s.width, s.hs, s.vs, xf ? xf[i] : kJxNone, trim, x, s.ncomp);
         if (rc != kJxOk) return refuse(i, rc);
         plan.transform |= x.xf != kJxNone;
-        JtGroup *grp = jfiftrans_group(plan, x.oH, x.oW, x.ohs, x.ovs);
+        JtGroup *grp = jfiftrans_group(plan, x.oH, x.oW, x.ohs, x.ovs, s.ncomp);
         if (!grp || n_blocks[i] != x.n_src || grp->g.nblk != x.n_out) return refuse(i, kJxBadArg);
         jfiftrans_add(plan, *grp, i, x.n_out);
-        grp->foreign_ids |= s.comp_id[0] != 1 || s.comp_id[1] != 2 || s.comp_id[2] != 3;
+        grp->foreign_ids |= s.comp_id[0] != 1 || (s.ncomp == 3 && (s.comp_id[1] != 2 || s.comp_id[2] != 3));
     }
     const int bad = jfiftrans_close(plan);
     if (bad >= 0) return refuse(bad, kJxBadArg);
@@ -267,7 +272,11 @@ int jfiftrans_plan(const std::vector<JtSource> &src, const std::vector<long long
             const int len = jfiftrans_prefix_host(s, prog, p.hdr, kJfifHdrMax - 14);
             if (len < 0) return refuse(c.files[k], kJxBadArg);
             p.dht_off = p.hdr_len = len;
-            if (!prog) {                                     // k_jfif_tables takes the SOS from the end of the markers
+            if (!prog && s.ncomp == 1) {                     // k_jfif_tables takes the SOS from the end of the markers
+                const unsigned char sos[10] = { 0xFF, 0xDA, 0, 8, 1, s.comp_id[0], 0x00, 0, 63, 0 };
+                memcpy(p.hdr + len, sos, 10);
+                p.hdr_len = len + 10;
+            } else if (!prog) {
                 const unsigned char sos[14] = { 0xFF, 0xDA, 0, 12, 3, s.comp_id[0], 0x00, s.comp_id[1], 0x11, s.comp_id[2], 0x11, 0, 63, 0 };
                 memcpy(p.hdr + len, sos, 14);
                 p.hdr_len = len + 14;

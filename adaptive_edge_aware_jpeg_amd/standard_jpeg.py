@@ -27,11 +27,13 @@ tables or as the ten-scan progressive file (csrc/jfiftrans.hip, ``aej_jfif_trans
 restart markers, and with ``keep_metadata=True`` carries its APP1..APP13, APP15 and COM segments over (spliced on the host).  A
 Pillow file transcoded this way equals Pillow's own ``optimize=True`` / ``progressive=True`` file of the same pixels byte for byte.
 ``standard_jpeg_transform_many`` is the same call with a lossless flip, rotation or transposition of every file on the way, by name or
-from the EXIF Orientation tag (``jpegtran -flip / -rotate / -transpose``, ``exiftran -a``; ``aej_jfif_transform_*``).
+from the EXIF Orientation tag (``jpegtran -flip / -rotate / -transpose``, ``exiftran -a``; ``aej_jfif_transform_*``).  Both take
+one-component (grey) files too when ``grey=True`` is passed.
 
 ``standard_jpeg_encode_many`` is the encoder for images of mixed sizes, each with its own quality, in one call: one front-end kernel over
 every block of every image, then one entropy chain per distinct size (csrc/jfifmany.hip, ``aej_jfif_many_*``); the files are those
-``standard_jpeg_many`` writes for each image alone.  ``standard_jpeg_thumbnail_jpeg_many`` puts it behind
+``standard_jpeg_many`` writes for each image alone; with ``mode="L"`` / ``"auto"`` it also writes the one-component files Pillow saves
+for mode-"L" images, from ``[H, W]`` planes.  ``standard_jpeg_thumbnail_jpeg_many`` puts it behind
 ``standard_jpeg_thumbnail_many``: JPEG bytes in, smaller JPEG bytes out, the pixels never leaving the device.
 
 The files are byte-identical to Pillow's with libjpeg-turbo (JFIF 1.01, Annex K quantisation and Huffman tables, islow DCT, no restart
@@ -75,14 +77,19 @@ def _check_bool(name, v) -> bool:
     return bool(v)
 
 
-def headers(quality: int, H: int, W: int, subsampling="4:2:0") -> bytes:
+def headers(quality: int, H: int, W: int, subsampling="4:2:0", mode: str = "RGB") -> bytes:
     """The markers SOI .. SOS of the file of one (quality, H, W, subsampling) with the Annex K Huffman tables
-    (aej_jfif_headers_host_opt)."""
+    (aej_jfif_headers_host_opt); mode="L": those of the grey file (aej_jfif_headers_grey_host; subsampling does not bear on it)."""
     from ._lib import load_library
     ss = _check_subsampling(subsampling)
+    if mode not in ("RGB", "L"):
+        raise ValueError(f"mode {mode!r}: 'RGB' or 'L' required")
     lib = load_library()
     buf = ctypes.create_string_buffer(HEADER_CAPACITY)
-    n = lib.aej_jfif_headers_host_opt(int(quality), int(H), int(W), ss, ctypes.cast(buf, ctypes.c_void_p), HEADER_CAPACITY)
+    if mode == "L":
+        n = lib.aej_jfif_headers_grey_host(int(quality), int(H), int(W), ctypes.cast(buf, ctypes.c_void_p), HEADER_CAPACITY)
+    else:
+        n = lib.aej_jfif_headers_host_opt(int(quality), int(H), int(W), ss, ctypes.cast(buf, ctypes.c_void_p), HEADER_CAPACITY)
     if n < 0:
         raise ValueError(f"quality {quality}, {H}x{W}: quality must be in 1..100 and H, W in 1..65535")
     return buf.raw[:n]
@@ -128,6 +135,12 @@ def _to_u8(ctx, x):
         raise ValueError(f"images must be [B, H, W, 3] (or one [H, W, 3]), got {tuple(x.shape)}")
     if x.shape[0] < 1:
         raise ValueError("at least one image required")
+    return _values_u8(ctx, x)
+
+
+def _values_u8(ctx, x):
+    """uint8 / float32 in [0, 1] (numpy or torch, any shape) -> device uint8 of that shape: float values as rint(x * 255)"""
+    t = ctx.torch
     dt = str(x.dtype)
     if dt in ("uint8", "torch.uint8"):
         return ctx.to_device(x, t.uint8)
@@ -278,10 +291,11 @@ def parse_scans(data, index: int = 0):
     return frame, list(scans)
 
 
-def _parse_sources(files, progressive=True, transcoder=False, start=0):
+def _parse_sources(files, progressive=True, transcoder=False, start=0, grey=False):
     """Parse every file once, telling baseline from progressive: yields (i, is_progressive, JpegDecDesc | (JpegProgFrame, scans), view)
     file by file, i counting from start.  progressive=False refuses progressive files the way standard_jpeg_decode_many does without
-    its keyword; transcoder=True refuses what the transcoder does not take.  Every refusal names the file."""
+    its keyword; transcoder=True refuses what the transcoder does not take, which without grey=True includes one-component files.
+    Every refusal names the file."""
     for i, f in enumerate(files, start):
         try:
             d, is_prog = parse_header(f, i), False
@@ -292,8 +306,8 @@ def _parse_sources(files, progressive=True, transcoder=False, start=0):
                 raise NotImplementedError(f"{e}; pass progressive=True to standard_jpeg_decode_many") from None
             d, is_prog = parse_scans(f, i), True
         frame = d[0] if is_prog else d
-        if transcoder and frame.ncomp != 3:
-            raise NotImplementedError(f"file {i}: a single-component (grey) file: the transcoder takes three-component files")
+        if transcoder and frame.ncomp != 3 and not (grey and frame.ncomp == 1):
+            raise NotImplementedError(f"file {i}: a single-component (grey) file: the transcoder takes three-component files unless grey=True is passed")
         if transcoder and frame.precision16:
             raise NotImplementedError(f"file {i}: a 16-bit quantisation table: the transcoder writes 8-bit tables")
         yield i, is_prog, d, memoryview(f).cast("B")
@@ -594,11 +608,11 @@ def metadata_segments(data, index: int = 0) -> bytes:
     return b"".join(bytes(mv[a:b]) for m, a, b in marker_segments(mv, index) if _is_metadata(m))
 
 
-def _prefix(data, index, transform, trim, headers):
+def _prefix(data, index, transform, trim, headers, grey=False):
     """transcode_prefix (transform None) and transform_prefix: headers(lib, frame pointers and density, output buffer and capacity)
     calls the caller's own ABI entry"""
     from ._lib import load_library
-    (_, is_prog, d, mv), = _parse_sources([data], transcoder=True, start=index)
+    (_, is_prog, d, mv), = _parse_sources([data], transcoder=True, start=index, grey=_check_bool("grey", grey))
     frame = d[0] if is_prog else d
     if transform is not None:
         _transform_geometry(index, frame.height, frame.width, frame.hs, frame.vs, _check_transform(transform, index), trim)
@@ -611,11 +625,11 @@ def _prefix(data, index, transform, trim, headers):
     return bytes(buf[:n])
 
 
-def transcode_prefix(data, progressive: bool = False, index: int = 0) -> bytes:
+def transcode_prefix(data, progressive: bool = False, index: int = 0, grey: bool = False) -> bytes:
     """The bytes SOI .. end of SOF0 / SOF2 that standard_jpeg_transcode_many writes for one file (aej_jfif_transcode_headers_host,
-    host only): JFIF APP0 with the source's density, its quantisation tables, its frame header."""
+    host only): JFIF APP0 with the source's density, its quantisation tables, its frame header.  grey: as standard_jpeg_transcode_many."""
     progressive = _check_bool("progressive", progressive)
-    return _prefix(data, index, None, False, lambda lib, src, dst: lib.aej_jfif_transcode_headers_host(*src, int(progressive), *dst))
+    return _prefix(data, index, None, False, lambda lib, src, dst: lib.aej_jfif_transcode_headers_host(*src, int(progressive), *dst), grey)
 
 
 def splice_metadata(out: bytes, meta: bytes) -> bytes:
@@ -628,7 +642,7 @@ _last_transcode_groups = 0
 
 def transcode_groups() -> int:
     """Entropy-encode chains the last successful standard_jpeg_transcode_many of this process ran: one per distinct (height, width,
-    sampling) among its files.  A diagnostic for tests and tools, nothing to build on: one module-level value for every device and
+    sampling, components) among its files.  A diagnostic for tests and tools, nothing to build on: one module-level value for every device and
     thread, which a call that raises leaves as it was."""
     return _last_transcode_groups
 
@@ -698,17 +712,17 @@ def _check_transform(name, i):
     return name
 
 
-def transform_prefix(data, transform, progressive: bool = False, trim: bool = False, index: int = 0) -> bytes:
+def transform_prefix(data, transform, progressive: bool = False, trim: bool = False, index: int = 0, grey: bool = False) -> bytes:
     """The bytes SOI .. end of SOF0 / SOF2 that standard_jpeg_transform_many writes for one file under one transform name
     (aej_jfif_transform_headers_host, host only): transcode_prefix with the output's size and sampling and, for a transposing
-    transform, every quantisation table transposed."""
+    transform, every quantisation table transposed.  grey: as standard_jpeg_transform_many."""
     progressive, trim = _check_bool("progressive", progressive), _check_bool("trim", trim)
     return _prefix(data, index, transform, trim, lambda lib, src, dst: lib.aej_jfif_transform_headers_host(
-        *src, int(progressive), TRANSFORMS.index(transform), int(trim), *dst))
+        *src, int(progressive), TRANSFORMS.index(transform), int(trim), *dst), grey)
 
 
 def standard_jpeg_transform_many(files, transform, progressive: bool = False, trim: bool = False, device: int = 0,
-                                 keep_metadata: bool = False) -> List[bytes]:
+                                 keep_metadata: bool = False, grey: bool = False) -> List[bytes]:
     """Lossless flip, rotation or transposition on the device: standard_jpeg_transcode_many with the files' quantised coefficients
     rearranged between the Huffman decode and the entropy coders (one kernel in the place of the transcoder's bridge), so that no
     sample is quantised a second time -- ``jpegtran -flip / -rotate / -transpose / -transverse``.  files, progressive, device and
@@ -727,10 +741,17 @@ def standard_jpeg_transform_many(files, transform, progressive: bool = False, tr
     rot90 of the height, rot180 and transverse of both.  Otherwise trim=False raises ValueError (jpegtran -perfect) and trim=True
     drops the partial MCU column / row at the right / bottom edge first (jpegtran -trim); a dimension that trims to 0 raises
     ValueError.  The padding samples of real edge blocks travel with their block; the dummy blocks of edge MCUs are written as
-    libjpeg writes them.  "none" is exactly the transcode.  Not built: a transposing transform of a 4:2:2 file (it would be 4:4:0;
-    NotImplementedError), crop, grey files.  Every refusal names the file and comes before any device work; there is no CPU fallback."""
+    libjpeg writes them.  "none" is exactly the transcode.
+
+    grey=True also takes one-component (grey) files, mixed freely with colour ones, "exif" included (TypeError for a value that is not a
+    bool; without it such a file is refused as before).  A grey file's MCU is one 8 x 8 block whatever sampling factors its frame header
+    carries, so every transform is allowed, a mirrored axis has to be a multiple of 8 and trim=True drops the partial 8-pixel column /
+    row; it has no dummy blocks.  Its output is the transcoder's grey file with its one table transposed by a transposing transform.
+
+    Not built: a transposing transform of a 4:2:2 file (it would be 4:4:0; NotImplementedError), crop.  Every refusal names the file and
+    comes before any device work; there is no CPU fallback."""
     progressive, keep_metadata = _check_bool("progressive", progressive), _check_bool("keep_metadata", keep_metadata)
-    trim = _check_bool("trim", trim)
+    trim, grey = _check_bool("trim", trim), _check_bool("grey", grey)
     files = list(files)
     if not files:
         raise ValueError("standard_jpeg_transform_many needs at least one file")
@@ -742,10 +763,10 @@ def standard_jpeg_transform_many(files, transform, progressive: bool = False, tr
         if len(names) != n:
             raise ValueError(f"file {min(len(names), n)}: {len(names)} transforms for {n} files")
         names = [_check_transform(t, i) for i, t in enumerate(names)]
-    return _transcode_many(files, progressive, device, keep_metadata, names, trim, names is None)
+    return _transcode_many(files, progressive, device, keep_metadata, names, trim, names is None, grey)
 
 
-def standard_jpeg_transcode_many(files, progressive: bool = False, device: int = 0, keep_metadata: bool = False) -> List[bytes]:
+def standard_jpeg_transcode_many(files, progressive: bool = False, device: int = 0, keep_metadata: bool = False, grey: bool = False) -> List[bytes]:
     """Lossless transcode on the device: -> every file entropy-coded again, in input order.  files: a non-empty sequence of bytes-like
     JPEG contents, baseline / extended-sequential (SOF0 / SOF1) and complete progressive (SOF2) files of any sizes and of the 4:4:4,
     4:2:2 and 4:2:0 layouts mixed freely.  progressive=False: a baseline file under the file's own optimal Huffman tables (what
@@ -754,25 +775,34 @@ def standard_jpeg_transcode_many(files, progressive: bool = False, device: int =
     optimize=True / progressive=True file byte for byte.  The output: SOI, JFIF 1.01 APP0 with the source's density, with
     keep_metadata=True the source's APP1 .. APP13, APP15 and COM segments (host work; never APP0 or Adobe APP14), the source's
     quantisation tables (8-bit, one DQT per table), its frame header, then tables and scans as the encoders lay them out.  Restart
-    markers are dropped.  Refused before any device work, naming the file: what the decoders' parsers refuse, grey files and 16-bit
-    quantisation tables (NotImplementedError), malformed headers (ValueError).  A file whose scan is corrupt, or that decodes to a
+    markers are dropped.
+
+    grey=True also takes one-component (grey) files, baseline or progressive, mixed freely with colour ones (TypeError for a value
+    that is not a bool).  Such a file is sampled 1 x 1 whatever its frame header says; its output has one DQT (its table, as table 0),
+    a one-component frame header, the file's own DC and AC table and one non-interleaved scan -- with progressive=True libjpeg's six
+    scans for one component -- so that a grey file Pillow wrote gives Pillow's optimize=True / progressive=True file of the mode-"L"
+    image byte for byte.
+
+    Refused before any device work, naming the file: what the decoders' parsers refuse, 16-bit quantisation tables and, without
+    grey=True, grey files (NotImplementedError), malformed headers (ValueError).  A file whose scan is corrupt, or that decodes to a
     coefficient an 8-bit JPEG cannot hold, raises ValueError naming its index and the reason; nothing is returned then.  There is no
     CPU fallback."""
     progressive, keep_metadata = _check_bool("progressive", progressive), _check_bool("keep_metadata", keep_metadata)
+    grey = _check_bool("grey", grey)
     files = list(files)
     if not files:
         raise ValueError("standard_jpeg_transcode_many needs at least one file")
-    return _transcode_many(files, progressive, device, keep_metadata, None, False, False)
+    return _transcode_many(files, progressive, device, keep_metadata, None, False, False, grey)
 
 
-def _transcode_many(files, progressive, device, keep_metadata, names, trim, exif):
+def _transcode_many(files, progressive, device, keep_metadata, names, trim, exif, grey=False):
     """the transcode (names None and not exif) and the transform: names[i] is file i's transform, exif takes it from the file"""
     global _last_transcode_groups
     from ._lib import JpegDecDesc, JpegProgFrame, JpegProgScan
     n = len(files)
     names = ["none"] * n if names is None else names
     views, parsed, base_idx, prog_idx, density, meta = [], [None] * n, [], [], [None] * n, [b""] * n
-    for i, is_prog, d, mv in _parse_sources(files, transcoder=True):
+    for i, is_prog, d, mv in _parse_sources(files, transcoder=True, grey=grey):
         parsed[i] = d
         (prog_idx if is_prog else base_idx).append(i)
         views.append(mv)
@@ -846,8 +876,8 @@ _last_encode_groups = 0
 
 
 def encode_groups() -> int:
-    """Entropy-encode chains the last successful standard_jpeg_encode_many of this process ran: one per distinct (height, width) among
-    its images.  The twin of transcode_groups, and like it a diagnostic: one module-level value, which a call that raises leaves as
+    """Entropy-encode chains the last successful standard_jpeg_encode_many of this process ran: one per distinct (height, width,
+    components) among its images.  The twin of transcode_groups, and like it a diagnostic: one module-level value, which a call that raises leaves as
     it was."""
     return _last_encode_groups
 
@@ -867,8 +897,18 @@ def _check_qualities(quality, n, what="image"):
     return out
 
 
-def _check_images(images):
-    """The host-side checks of standard_jpeg_encode_many, before any device context exists -> [(image, is_torch, is_float)]"""
+MODES = ("RGB", "L", "auto")
+
+
+def _check_mode(mode) -> str:
+    if not isinstance(mode, str) or mode not in MODES:
+        raise ValueError(f"mode {mode!r}: 'RGB', 'L' or 'auto' required")
+    return mode
+
+
+def _check_images(images, mode="RGB"):
+    """The host-side checks of standard_jpeg_encode_many, before any device context exists -> [(image, is_torch, is_float)]; a grey
+    image is the one with two dimensions"""
     if isinstance(images, (str, bytes)) or not hasattr(images, "__len__") or (hasattr(images, "ndim") and not isinstance(images, (list, tuple))):
         raise ValueError("standard_jpeg_encode_many needs a sequence of [H, W, 3] images (one [B, H, W, 3] array is standard_jpeg_many's input)")
     if len(images) < 1:
@@ -883,8 +923,10 @@ def _check_images(images):
         dt = str(x.dtype)
         if dt not in ("uint8", "torch.uint8", "float32", "torch.float32"):
             raise TypeError(f"image {i}: uint8 or float32 in [0, 1] required, got {dt}")
-        if x.ndim != 3 or x.shape[2] != 3:
-            raise ValueError(f"image {i}: [H, W, 3] required, got {tuple(x.shape)}")
+        colour, grey = x.ndim == 3 and x.shape[2] == 3, x.ndim == 2
+        if not ((colour and mode != "L") or (grey and mode != "RGB")):
+            want = {"RGB": "[H, W, 3]", "L": "[H, W] (mode 'L')", "auto": "[H, W] or [H, W, 3] (mode 'auto')"}[mode]
+            raise ValueError(f"image {i}: {want} required, got {tuple(x.shape)}")
         if not (1 <= x.shape[0] <= 65535 and 1 <= x.shape[1] <= 65535):
             raise ValueError(f"image {i}: {x.shape[0]}x{x.shape[1]}: JPEG needs 1 <= H, W <= 65535")
         com = getattr(x, "jpeg_comment", None)
@@ -903,7 +945,7 @@ def _packed_source(ctx, imgs):
         if all(x.untyped_storage().data_ptr() == st.data_ptr() for x, _, _ in imgs):
             off = np.array([x.data_ptr() - st.data_ptr() for x, _, _ in imgs], np.int64)
             return [x for x, _, _ in imgs], st.data_ptr(), st.nbytes(), off
-    sizes = np.array([x.shape[0] * x.shape[1] * 3 for x, _, _ in imgs], np.int64)
+    sizes = np.array([int(np.prod(x.shape)) for x, _, _ in imgs], np.int64)      # 3 H W, or H W of a grey image
     off = np.concatenate(([0], np.cumsum(sizes)[:-1])).astype(np.int64)
     total = int(sizes.sum())
     buf = ctx.empty((total,), t.uint8)
@@ -920,7 +962,7 @@ def _packed_source(ctx, imgs):
     else:
         for i, (x, _, _) in enumerate(imgs):
             try:
-                u8 = _to_u8(ctx, x)
+                u8 = _to_u8(ctx, x) if x.ndim == 3 else _values_u8(ctx, x)
             except ValueError as e:
                 raise ValueError(f"image {i}: {e}") from None
             buf[int(off[i]):int(off[i] + sizes[i])].copy_(u8.reshape(-1))
@@ -932,7 +974,7 @@ def _encode_many(ctx, imgs, qualities, ss, opt, prog):
     from ._lib import JfifManyDesc
     t, lib, n = ctx.torch, ctx.lib, len(imgs)
     keep, src, src_bytes, off = _packed_source(ctx, imgs)
-    descs = (JfifManyDesc * n)(*[JfifManyDesc(int(off[i]), int(x.shape[1]), int(x.shape[0]), qualities[i], 0) for i, (x, _, _) in enumerate(imgs)])
+    descs = (JfifManyDesc * n)(*[JfifManyDesc(int(off[i]), int(x.shape[1]), int(x.shape[0]), qualities[i], 1 if x.ndim == 2 else 3) for i, (x, _, _) in enumerate(imgs)])
     nws = int(lib.aej_jfif_many_workspace_bytes(ctx.handle, ctypes.addressof(descs), n, ss, int(opt), int(prog)))
     if nws == 0:
         raise ValueError("descriptors the library refuses")
@@ -961,27 +1003,36 @@ def _encode_many(ctx, imgs, qualities, ss, opt, prog):
     return res
 
 
-def standard_jpeg_encode_many(images, quality=75, subsampling="4:2:0", optimize: bool = False, progressive: bool = False, device: int = 0) -> List[bytes]:
+def standard_jpeg_encode_many(images, quality=75, subsampling="4:2:0", optimize: bool = False, progressive: bool = False, device: int = 0,
+                              mode: str = "RGB") -> List[bytes]:
     """Images of mixed sizes encoded in one call: -> every image's file, in input order; file i equals
     ``Image.fromarray(u8_i).save(buf, "JPEG", quality=q_i, subsampling=subsampling, optimize=optimize, progressive=progressive)`` byte
     for byte, and ``standard_jpeg_many(images[i], q_i, ...)[0]``.  images: a non-empty sequence of [H_i, W_i, 3] images, each uint8 or
     float32 in [0, 1] taken as ``rint(x * 255)``, numpy or torch, sizes mixed freely.  quality: one int for all, or one per image.
     subsampling, optimize, progressive: as standard_jpeg_many, one setting for the call.
 
+    mode: "RGB" (the call as it always was); "L": every image is [H_i, W_i], uint8 or float32 by the same rule, and file i is the
+    one-component file ``Image.fromarray(u8_i).save(buf, "JPEG", quality=q_i, optimize=optimize, progressive=progressive)`` writes for
+    that mode-"L" image, byte for byte; "auto": [H, W] images are grey and [H, W, 3] images colour, mixed freely, each file that of its
+    own single-mode call.  subsampling is checked but does not bear on a grey image: its one component is sampled 1 x 1, which is also
+    what Pillow codes -- given an explicit subsampling= for a mode-"L" image Pillow writes those factors into the frame header's
+    sampling byte and changes nothing else (a decoder ignores them for one component); this library always writes 1 x 1 there, the
+    file of a save without that keyword.
+
     One kernel converts, down-samples, transforms and quantises every block of every image (csrc/jfifmany.hip); the images are then
-    grouped by size and each group runs one entropy chain (encode_groups() tells how many), so launches grow with the number of
-    distinct sizes.  Device uint8 tensors that are contiguous views of one allocation -- what standard_jpeg_thumbnail_many and
+    grouped by (size, components) and each group runs one entropy chain (encode_groups() tells how many), so launches grow with the
+    number of distinct sizes.  Device uint8 tensors that are contiguous views of one allocation -- what standard_jpeg_thumbnail_many and
     resize_many return -- are read where they lie, by offset; anything else is packed into one device buffer first.
 
     A torch image that carries the attribute ``jpeg_comment`` (bytes; standard_jpeg_thumbnail_many sets it from its file's COM segment)
     gets that text as a COM segment right after the JFIF APP0 -- what Pillow from 9.4 on does with ``im.info["comment"]`` on save, and
     the only thing its save carries over from a file.  Without the attribute (every NumPy image) no such segment is written.
 
-    Checked before any device work, naming the image: a quality outside 1..100, a shape that is not [H, W, 3] with 1 <= H, W <= 65535,
-    a quality sequence of another length (ValueError); a dtype other than uint8 / float32, optimize / progressive that are not bools
+    Checked before any device work, naming the image: a quality outside 1..100, a shape that is not the mode's ([H, W, 3], [H, W])
+    with 1 <= H, W <= 65535, a quality sequence of another length, a mode other than the three (ValueError); a dtype other than uint8 / float32, optimize / progressive that are not bools
     (TypeError).  float32 values outside [0, 1] raise ValueError once the image is looked at.  There is no CPU fallback."""
     ss, opt, prog = _check_subsampling(subsampling), _check_bool("optimize", optimize), _check_bool("progressive", progressive)
-    imgs = _check_images(images)
+    imgs = _check_images(images, _check_mode(mode))
     qualities = _check_qualities(quality, len(imgs))
     return _encode_many(get_context(device), imgs, qualities, ss, opt, prog)
 
@@ -995,7 +1046,8 @@ def standard_jpeg_thumbnail_jpeg_many(files, size, quality=75, subsampling="4:2:
     the device: only the decoder's status words and the finished files are read back.  Like Pillow's save it carries no metadata
     over (no EXIF, ICC profile or density) but a source's COM segment, which Pillow from 9.4 on writes again from
     ``im.info["comment"]``: the thumbnails carry it as ``jpeg_comment`` and the encoder writes it (both documented there).  A grey (single-component) source comes out as a three-component file with neutral chroma; Pillow keeps mode "L"
-    there and writes a one-component file, which this library does not write.
+    there and writes a one-component file, which this call does not write (standard_jpeg_encode_many(mode="L") does, from [H, W] planes: the
+    thumbnails here are three-channel).
     files, size, resample, reducing_gap, progressive (whether progressive SOURCES are accepted): standard_jpeg_thumbnail_many's.
     quality (one, or one per file), subsampling, optimize, progressive_out: standard_jpeg_encode_many's quality, subsampling, optimize
     and progressive.  Every argument is checked, and every header parsed, before any device work; a file whose scan is corrupt raises

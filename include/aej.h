@@ -552,7 +552,11 @@ AEJ_API int aej_jpegprog_batch_scaled(aej_ctx *ctx, const aej_jpegprog_frame *fr
  * markers of its own quality: optimize = 1 the file's own Huffman tables, optimize = 0 the Annex K tables, progressive = 1 (optimize is
  * then not looked at beyond its range) libjpeg's ten scans.  Launches grow with the number of distinct sizes, one chain each.
  *
- * aej_jfif_many_desc: image i is packed uint8 [height][width][3] at src + src_offset; reserved must be 0.
+ * aej_jfif_many_desc: image i is packed uint8 [height][width][3] at src + src_offset.  components (the field that was `reserved`, which
+ *   had to be 0): 0 or 3 such an image; 1 a grey image, packed uint8 [height][width], written as the one-component file Pillow saves
+ *   for a mode "L" image (one DQT, a one-component SOF, the luma Huffman tables alone, a non-interleaved scan -- six scans with
+ *   progressive = 1 -- over the ceil(width / 8) x ceil(height / 8) blocks in raster order; subsampling does not bear on it).  Both
+ *   kinds mix in one call; the groups are then by (height, width, components).  Any other value: AEJ_ERR_ARG naming the image.
  * aej_jfif_many_workspace_bytes: the workspace of such a call, 0 for descriptors the call refuses (ctx is not looked at).
  * aej_jfif_many_encode: src: device bytes, src_bytes of them.  out / out_capacity / offsets / lengths / total_host as
  *   aej_jfif_transcode_batch: offsets and lengths are device int64 [n] in the caller's order (the files are packed group after group),
@@ -566,10 +570,14 @@ AEJ_API int aej_jpegprog_batch_scaled(aej_ctx *ctx, const aej_jpegprog_frame *fr
  *   raster order, then Cb, Cr), the dummy luma blocks of edge MCUs as libjpeg writes them (AC zero, DC of the block before in the MCU).
  *   -> the image's blocks (also with both pointers NULL: a size query), AEJ_ERR_ARG for a size, quality or subsampling outside the
  *   encoder's or one pointer NULL, AEJ_ERR_CAPACITY for dst_blocks too small.
- * (Additions to ABI 3: no existing signature, struct or behaviour changed.) */
+ * aej_jfif_headers_grey_host: HOST only, the markers SOI .. SOS of the grey file of one (quality, H, W) with the Annex K luma tables
+ *   (optimize = 0), as aej_jfif_headers_host: one DQT, SOF0 with one component (id 1, 1 x 1, table 0), two DHT, SOS with Ns = 1.
+ * aej_jfif_many_coefs_grey_host: the same for one grey image.  grey_host: uint8 [height][width]; the blocks are the component's
+ *   ceil(width / 8) x ceil(height / 8) in raster order, none a dummy, under the luma quantiser of the quality.
+ * (Additions to ABI 3: no existing signature, struct layout or behaviour of a valid call changed.) */
 typedef struct aej_jfif_many_desc {
     int64_t src_offset;
-    int32_t width, height, quality, reserved;
+    int32_t width, height, quality, components;
 } aej_jfif_many_desc;
 AEJ_API uint64_t aej_jfif_many_workspace_bytes(aej_ctx *ctx, const aej_jfif_many_desc *descs_host, int n, int subsampling, int optimize,
                                                int progressive);
@@ -578,6 +586,8 @@ AEJ_API int aej_jfif_many_encode(aej_ctx *ctx, const aej_jfif_many_desc *descs_h
                                  uint64_t *total_host, int32_t *n_groups_host, void *workspace, uint64_t workspace_bytes);
 AEJ_API int64_t aej_jfif_many_coefs_host(int width, int height, int quality, int subsampling, const uint8_t *rgb_host, int16_t *dst_host,
                                          int64_t dst_blocks);
+AEJ_API int aej_jfif_headers_grey_host(int quality, int H, int W, uint8_t *out_host, int capacity);
+AEJ_API int64_t aej_jfif_many_coefs_grey_host(int width, int height, int quality, const uint8_t *grey_host, int16_t *dst_host, int64_t dst_blocks);
 
 /* ---- lossless transcode: existing files entropy-coded again (standard_jpeg_transcode_many) ----------------------------------------------
  * What jpegtran -optimize / -progressive do, on the device: the files are Huffman-decoded to their quantised coefficients by the stages of
@@ -586,8 +596,11 @@ AEJ_API int64_t aej_jfif_many_coefs_host(int width, int height, int quality, int
  * under its own optimal Huffman tables) or of aej_jfif_encode_batch_prog (progressive = 1: SOF2, libjpeg's ten scans).  One call takes
  * baseline sources (descs_host, n_base, scans ... as aej_jpegdec_batch) and progressive ones (frames_host, pscans_host, n_prog, data ...
  * as aej_jpegprog_batch) together; either count may be 0, not both.  File i of the call is baseline source i for i < n_base, otherwise
- * progressive source i - n_base.  Three-component files only (AEJ_ERR_UNSUPPORTED for a grey one or one with a 16-bit quantisation
- * table); restart markers of a source are not written again.
+ * progressive source i - n_base.  Three-component files, and one-component (grey) files, which used to be refused
+ * (AEJ_ERR_UNSUPPORTED for a file with a 16-bit quantisation table); restart markers of a source are not written again.
+ * A one-component source is sampled 1 x 1 whatever its frame header says (the parsers' rule: hs = vs = 1, blocks_per_mcu = 1); its
+ * output has one DQT -- its component's table, written as table 0 --, a one-component SOF with sampling 1 x 1, the two luma DHT and a
+ * non-interleaved scan (progressive = 1: libjpeg's six scans for one component).
  *
  * Output file: SOI; JFIF 1.01 APP0 with the density density_host[3 i .. 3 i + 2] = units, Xdensity, Ydensity (density_host NULL: 0, 1, 1);
  * one 8-bit DQT per distinct table id the components reference, in order of first reference; SOF0 / SOF2 with the source's component
@@ -598,7 +611,7 @@ AEJ_API int64_t aej_jfif_many_coefs_host(int width, int height, int quality, int
  *   device int64 [n_base + n_prog] in the call's file order (the files are packed group after group, not in that order).  status:
  *   device int32 [n_base + n_prog], AEJ_JPEGDEC_*: a source whose scan is malformed, or that decodes to a coefficient an 8-bit file
  *   cannot hold (AEJ_JPEGDEC_COEF_RANGE: the coders' per-block bounds rest on that range, so such a block never reaches them), gets
- *   its reason there and length 0; the other files are written.  Files are grouped by (height, width, sampling): each group runs one
+ *   its reason there and length 0; the other files are written.  Files are grouped by (height, width, sampling, components): each group runs one
  *   entropy-encode chain (*n_groups_host, may be NULL, gets their number).  The call waits for the decode's sync rounds and, at its
  *   end, for the total.  Workspace: aej_jfif_transcode_workspace_bytes with the same descriptors (0 for descriptors the call refuses). */
 AEJ_API int aej_jfif_transcode_headers_host(const aej_jpegdec_desc *desc_host, const aej_jpegprog_frame *frame_host, const uint16_t *density3_host,
@@ -627,7 +640,7 @@ AEJ_API int aej_jfif_transcode_batch(aej_ctx *ctx, const aej_jpegdec_desc *descs
  * MCU column / row at its right / bottom edge is dropped first.  The dummy blocks of the output's edge MCUs are written as libjpeg
  * writes them (AC zero, DC of the block before in the MCU); a file with the code 0 is transcoded exactly as above, its dummy blocks
  * carried.  A transposing code on a 4:2:2 source would give a 4:4:0 file: AEJ_ERR_UNSUPPORTED.  Files are grouped by the (height,
- * width, sampling) of their OUTPUT.
+ * width, sampling, components) of their OUTPUT.  A one-component source has 8 x 8 MCUs and no dummy blocks, so every code is allowed.
  *
  * aej_jfif_transform_geometry_host: HOST only.  out4_host (may be NULL) gets the output's height, width, hs, vs.  -> 0, AEJ_ERR_ARG,
  *   AEJ_ERR_UNSUPPORTED (4:4:0), AEJ_JFIF_TRANSFORM_NOT_PERFECT (trim = 0 and a mirrored axis with a partial MCU) or
@@ -637,6 +650,9 @@ AEJ_API int aej_jfif_transcode_batch(aej_ctx *ctx, const aej_jpegdec_desc *descs
  *   then Cb, Cr), src_blocks = (hs vs + 2) x its MCUs.  dst_host: int16 [>= the result][64], zigzag order inside a block, the OUTPUT's MCU
  *   order.  -> the output's blocks (also with both pointers NULL: a size query), or the geometry entry's refusals, AEJ_ERR_ARG for a
  *   wrong src_blocks, AEJ_ERR_CAPACITY for dst_blocks too small.  No range check.
+ * aej_jfif_transform_coefs_grey_host: the same for a one-component file: the blocks of both sides are the component's in raster order,
+ *   src_blocks = ceil(W / 8) x ceil(H / 8).  Such a file can have one block or two, so a geometry that is not perfect or trims to
+ *   zero is AEJ_ERR_ARG here (aej_jfif_transform_geometry_host with hs = vs = 1 tells which).
  * aej_jfif_transform_headers_host, _workspace_bytes, _batch: the aej_jfif_transcode_* entries with, before their output arguments,
  *   transforms_host [n_base + n_prog] int32 in the call's file order (headers: the one code) and trim (0 or 1).  The headers carry the
  *   output's size and sampling and the transposed tables; a refused geometry is AEJ_ERR_ARG (the message names the file), 4:4:0
@@ -645,6 +661,8 @@ enum { AEJ_JFIF_TRANSFORM_NOT_PERFECT = 1, AEJ_JFIF_TRANSFORM_TRIMS_TO_ZERO = 2 
 AEJ_API int aej_jfif_transform_geometry_host(int H, int W, int hs, int vs, int transform, int trim, int32_t *out4_host);
 AEJ_API int64_t aej_jfif_transform_coefs_host(int H, int W, int hs, int vs, int transform, int trim, const int16_t *src_host, int64_t src_blocks,
                                               int16_t *dst_host, int64_t dst_blocks);
+AEJ_API int64_t aej_jfif_transform_coefs_grey_host(int H, int W, int transform, int trim, const int16_t *src_host, int64_t src_blocks,
+                                                   int16_t *dst_host, int64_t dst_blocks);
 AEJ_API int aej_jfif_transform_headers_host(const aej_jpegdec_desc *desc_host, const aej_jpegprog_frame *frame_host, const uint16_t *density3_host,
                                             int progressive, int transform, int trim, uint8_t *out_host, int capacity);
 AEJ_API uint64_t aej_jfif_transform_workspace_bytes(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base,
