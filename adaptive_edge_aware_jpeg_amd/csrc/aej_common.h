@@ -66,11 +66,22 @@ struct Tuning {
     int sobel_xcd = 1;             // "sobel_xcd": 1 = each XCD works on a contiguous range of the register Sobel kernel's tiles (0: round-robin, rounds 3-4)
 };
 
-// natural (row-major) index of zigzag positions 0 .. 63 of an 8 x 8 block: the initialiser of every such table in these translation
-// units (a __constant__ array is private to its translation unit, so each keeps its own, filled from here)
+// natural (row-major) index of zigzag positions 0 .. 63 of an 8 x 8 block: the one place the order is written down
 #define AEJ_ZIGZAG_8X8                                                                                                                      \
     0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28, 35, 42, 49, 56, 57, \
         50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63
+// the two tables of the standard-JPEG coders and decoders: natural[z] the natural index of zigzag position z, position[n] its inverse
+struct Zigzag8 {
+    unsigned char natural[64], position[64];
+};
+constexpr Zigzag8 zigzag8_make()
+{
+    Zigzag8 t = { { AEJ_ZIGZAG_8X8 }, {} };
+    for (int z = 0; z < 64; z++) t.position[t.natural[z]] = (unsigned char)z;
+    return t;
+}
+constexpr Zigzag8 kZigzag8 = zigzag8_make();              // host code, and device code that indexes it with compile-time constants
+static __constant__ Zigzag8 k_zigzag8 = zigzag8_make();   // kernels that index it at run time (a copy per translation unit)
 
 constexpr int kChunkInts = 4 + kMaxSizes;   // per-chunk record: nsym, nleaf, ncoef, pad, leaves per size
 constexpr int kMaxPlanes = 3072;            // planes (3 x images) one DCT launch can address

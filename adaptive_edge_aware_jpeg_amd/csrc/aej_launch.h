@@ -221,7 +221,8 @@ struct JfifParams {                    // one quality: quantisers in zigzag orde
     unsigned char hdr[kJfifHdrMax];
 };
 struct JfifBufs {
-    JfifParams *par; int *dct; short *coef; int *lens; long long *boff, *btot; unsigned *stream; int *ffcnt; long long *ffpre, *fftot, *total;
+    JfifParams *par; int *dct; short *coef; int *lens; unsigned *stream; int *ffcnt; long long *total;
+    unsigned long long *boff, *ffpre;  // [seg][nblk + 1], [seg][n_chunks + 1] prefix sums of the blocks' bits and the chunks' 0xFF counts; the last is the total
     unsigned char *planes;
     // per-file Huffman tables (opt only): symbol counts [seg][4][257], (code << 8) | length [seg][4][256], markers [seg][kJfifHdrMax]
     unsigned long long *hist; unsigned *codes; unsigned char *fhdr; int *fhdr_len;

@@ -17,14 +17,18 @@
 //   k_jfif_hist     one thread per block: the symbols the emitter will write, counted per wave in LDS, then one add per non-zero bin
 //   k_jfif_tables   one workgroup per (quality, image), one wave per table: jh_build (jfif_huff_core.h), the codes, the file's markers
 //   k_jfif_count    one thread per block: its bits under the file's own tables
-//   k_jfif_scan     one workgroup per (quality, image): exclusive scan of per-block bit counts (and later of per-chunk 0xFF counts)
+//   k_js_scan       one workgroup per (quality, image): exclusive prefix sums of per-block bit counts (and later of per-chunk 0xFF
+//                   counts), n + 1 entries whose last is the total -- jfif_stream_core.h, shared with jfifprog.hip
 //   k_jfif_emit     one thread per block: its code string at its bit offset, boundary words by atomicOr; the last block pads with 1-bits
 //   k_jfif_ffcount  one thread per 64-byte chunk of a stream: its 0xFF bytes
 //   k_jfif_layout   one thread: file lengths (markers + stuffed data + EOI) and their offsets in the packed output
 //   k_jfif_scatter  one thread per chunk: the chunk with a 0x00 after every 0xFF at its final place; chunk 0 also writes markers and EOI
-//   k_jfif_idct     one thread per (quality, image, real block): dequantise, islow IDCT, masked range limit -> uint8 sample planes
+//   k_jfif_idct     one thread per (quality, image, real block): dequantise (its own load: zigzag order, int quantisers), then the
+//                   decoder's islow IDCT pass and masked range limit (jd_idct8, jd_range_limit) -> uint8 sample planes
 //   k_jfif_rgb      one thread per output pixel: h2v2 / h2v1 fancy up-sampling (plain replication when the chroma is <= 2 wide, as
-//                   libjpeg-turbo does; none at 4:4:4) -- jd_chroma of jpegdec_core.h -- and the fixed-point YCbCr -> RGB
+//                   libjpeg-turbo does; none at 4:4:4) and the fixed-point YCbCr -> RGB -- jd_chroma, jd_rgb of jpegdec_core.h
+// The bit writer (JeBits), magnitude category, predecessor block, 0xFF counting / stuffing loops and the prefix-sum kernel are
+// jfif_stream_core.h's, the zigzag tables aej_common.h's (kZigzag8, k_zigzag8): one copy for every coder and decoder.
 // Bounds: every index derives from JfifGeom; a stream's words stay inside its stride (the per-block bound kJfifBlockWords holds for every
 // input: DC <= 22 bits, 63 AC <= 26 bits each; kJfifBlockWordsOpt with a file's own tables: DC <= 27, AC <= 26) and every store into
 // a stream checks that stride; k_jfif_scatter writes a file only if it ends inside the caller's capacity.
@@ -33,16 +37,14 @@
 #include "aej_launch.h"
 #include "jfif_arith.h"
 #include "jfif_huff_core.h"
+#include "jfif_stream_core.h"
 #include "jpegdec_core.h"
 
 namespace aej {
 
 constexpr int kJfThreads = 256;
-constexpr int kJfScanThreads = 1024;
 constexpr int kJfChunk = 64;           // bytes per stuffing chunk
 
-__constant__ unsigned char k_zz[64] = { AEJ_ZIGZAG_8X8 };
-constexpr unsigned char kJfInvZz[64] = { 0, 1, 5, 6, 14, 15, 27, 28, 2, 4, 7, 13, 16, 26, 29, 42, 3, 8, 12, 17, 25, 30, 41, 43, 9, 11, 18, 24, 31, 40, 44, 53, 10, 19, 23, 32, 39, 45, 52, 54, 20, 22, 33, 38, 46, 51, 55, 60, 21, 34, 37, 47, 50, 56, 59, 61, 35, 36, 48, 49, 57, 58, 62, 63 };      // zigzag position of natural index
 // Annex K.3 Huffman codes, (code << 8) | length, indexed by symbol (0 = symbol not in the table)
 // dc_luma: (code << 8) | length
 __constant__ unsigned k_dc_luma[16] = {
@@ -88,30 +90,8 @@ __constant__ unsigned k_ac_chroma[256] = {
     260618, 8373007, 16774672, 16774928, 16775184, 16775440, 16775696, 16775952, 16776208, 16776464, 16776720, 0, 0, 0, 0, 0};
 
 // ---- arithmetic shared by the stages ----------------------------------------------------------------------------------------------
-// jf_y, jf_c, jf_h2v1, jf_h2v2, jf_descale, jf_fdct8, jf_quant: jfif_arith.h (shared with jfifmany.hip)
-
-// jidctint, one 8-point pass; pass 1 (columns) descales by CONST_BITS - PASS1_BITS, pass 2 (rows) by CONST_BITS + PASS1_BITS + 3
-template <bool kPass1>
-__device__ __forceinline__ void jf_idct8(long long *d, int s)
-{
-    const int n = kPass1 ? 11 : 18;
-    long long z2 = d[2 * s], z3 = d[6 * s], z1 = (z2 + z3) * 4433;
-    long long t2 = z1 - z3 * 15137, t3 = z1 + z2 * 6270;
-    long long t0 = (d[0] + d[4 * s]) * 8192, t1 = (d[0] - d[4 * s]) * 8192;
-    long long t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
-    t0 = d[7 * s]; t1 = d[5 * s]; t2 = d[3 * s]; t3 = d[s];
-    z1 = t0 + t3; z2 = t1 + t2; z3 = t0 + t2;
-    long long z4 = t1 + t3, z5 = (z3 + z4) * 9633;
-    t0 *= 2446; t1 *= 16819; t2 *= 25172; t3 *= 12299;
-    z1 *= -7373; z2 *= -20995; z3 = z3 * -16069 + z5; z4 = z4 * -3196 + z5;
-    t0 += z1 + z3; t1 += z2 + z4; t2 += z2 + z3; t3 += z1 + z4;
-    d[0] = jf_descale(t10 + t3, n); d[7 * s] = jf_descale(t10 - t3, n);
-    d[s] = jf_descale(t11 + t2, n); d[6 * s] = jf_descale(t11 - t2, n);
-    d[2 * s] = jf_descale(t12 + t1, n); d[5 * s] = jf_descale(t12 - t1, n);
-    d[3 * s] = jf_descale(t13 + t0, n); d[4 * s] = jf_descale(t13 - t0, n);
-}
-
-__device__ __forceinline__ int jf_cat(int v) { return v == 0 ? 0 : 32 - __clz(v < 0 ? -v : v); }
+// jf_y, jf_c, jf_h2v1, jf_h2v2, jf_descale, jf_fdct8, jf_quant: jfif_arith.h (shared with jfifmany.hip); js_nbits, js_prev, JeBits,
+// js_stuff_*, k_js_scan: jfif_stream_core.h (shared with jfifprog.hip); jd_idct8, jd_range_limit, jd_chroma, jd_rgb: jpegdec_core.h
 
 // MCU geometry: block k (0 .. HS * VS - 1 luma in raster order, then Cb, Cr) of MCU m; luma blocks outside ceil(H/8) x ceil(W/8) are
 // dummies (right edge when HS = 2, bottom edge when VS = 2)
@@ -129,16 +109,6 @@ __device__ __forceinline__ int jf_qdc(const JfifGeom &g, const int *dct_img, con
     while (!jf_real<HS, VS>(g, m, k)) k--;
     return jf_quant(dct_img[(m * (HS * VS + 2) + k) * 64], p.qt[k >= HS * VS][0]);
 }
-// the block of the same component before block (m, k) in scan order, -1 at the start of the scan
-template <int HS, int VS, int NC = 3>
-__device__ __forceinline__ long long jf_prev(long long m, int k)
-{
-    constexpr int NL = HS * VS, BPM = NL + NC - 1;
-    if (k >= 1 && k < NL) return m * BPM + k - 1;
-    if (m == 0) return -1;
-    return k == 0 ? (m - 1) * BPM + NL - 1 : (m - 1) * BPM + k;
-}
-
 // ---- encode ------------------------------------------------------------------------------------------------------------------------
 template <int HS, int VS>
 __global__ __launch_bounds__(kJfThreads) void k_jfif_fdct(JfifGeom g, const unsigned char *__restrict__ rgb, int *__restrict__ dct)
@@ -226,9 +196,9 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_quant(JfifGeom g, const Jfi
     const JfCodes hc = jf_codes(k >= NL);
     short *o = coef + idx * 64;
     const int dc = jf_qdc<HS, VS>(g, img, p, m, k);
-    const long long pb = jf_prev<HS, VS>(m, k);
+    const long long pb = js_prev(NL, BPM, m, k);
     const int diff = dc - (pb < 0 ? 0 : jf_qdc<HS, VS>(g, img, p, pb / BPM, (int)(pb % BPM)));
-    const int dcat = jf_cat(diff);
+    const int dcat = js_nbits(diff);
     int bits = (int)(hc.dc[dcat] & 255) + dcat;
     o[0] = (short)dc;
     if (!jf_real<HS, VS>(g, m, k)) {
@@ -239,10 +209,10 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_quant(JfifGeom g, const Jfi
     const int *d = img + blk * 64;
     int run = 0;
     for (int i = 1; i < 64; i++) {
-        const int v = jf_quant(d[k_zz[i]], qt[i]);
+        const int v = jf_quant(d[k_zigzag8.natural[i]], qt[i]);
         o[i] = (short)v;
         if (v == 0) { run++; continue; }
-        const int cat = jf_cat(v);
+        const int cat = js_nbits(v);
         bits += (run >> 4) * (int)(hc.ac[0xF0] & 255) + (int)(hc.ac[((run & 15) << 4) | cat] & 255) + cat;
         run = 0;
     }
@@ -266,14 +236,14 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_hist(JfifGeom g, const shor
         const int k = (int)(blk % BPM);
         unsigned(*h)[kJhSymbols] = cnt[threadIdx.x / 64] + (k >= NL ? 2 : 0);      // [0] DC, [1] AC of the block's component class
         const short *c = coef + (seg * g.nblk + blk) * 64;
-        const long long pb = jf_prev<HS, VS, NC>(m, k);
-        atomicAdd(&h[0][jf_cat(c[0] - (pb < 0 ? 0 : coef[(seg * g.nblk + pb) * 64]))], 1u);
+        const long long pb = js_prev(NL, BPM, m, k);
+        atomicAdd(&h[0][js_nbits(c[0] - (pb < 0 ? 0 : coef[(seg * g.nblk + pb) * 64]))], 1u);
         int run = 0;
         for (int i = 1; i < 64; i++) {
             const int v = c[i];
             if (v == 0) { run++; continue; }
             if (run > 15) atomicAdd(&h[1][0xF0], (unsigned)(run >> 4));
-            atomicAdd(&h[1][((run & 15) << 4) | jf_cat(v)], 1u);
+            atomicAdd(&h[1][((run & 15) << 4) | js_nbits(v)], 1u);
             run = 0;
         }
         if (run) atomicAdd(&h[1][0], 1u);
@@ -364,13 +334,13 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_count(JfifGeom g, const sho
     const int k = (int)(blk % BPM);
     const JfCodes hc = jf_file_codes(codes, seg, k >= NL);
     const short *c = coef + idx * 64;
-    const long long pb = jf_prev<HS, VS, NC>(m, k);
-    const int dcat = jf_cat(c[0] - (pb < 0 ? 0 : coef[(seg * g.nblk + pb) * 64]));
+    const long long pb = js_prev(NL, BPM, m, k);
+    const int dcat = js_nbits(c[0] - (pb < 0 ? 0 : coef[(seg * g.nblk + pb) * 64]));
     int bits = (int)(hc.dc[dcat] & 255) + dcat, run = 0;
     for (int i = 1; i < 64; i++) {
         const int v = c[i];
         if (v == 0) { run++; continue; }
-        const int cat = jf_cat(v);
+        const int cat = js_nbits(v);
         bits += (run >> 4) * (int)(hc.ac[0xF0] & 255) + (int)(hc.ac[((run & 15) << 4) | cat] & 255) + cat;
         run = 0;
     }
@@ -378,73 +348,24 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_count(JfifGeom g, const sho
     lens[idx] = bits;
 }
 
-// (b) exclusive scan of n int32 per segment (one workgroup per segment) -> int64 offsets and the segment's total
-__global__ __launch_bounds__(kJfScanThreads) void k_jfif_scan(const int *__restrict__ in, long long n, long long *__restrict__ out,
-                                                              long long *__restrict__ tot)
+// (b) k_js_scan (jfif_stream_core.h): a segment's n + 1 prefix sums of its blocks' bits (boff) and later of its chunks' 0xFF counts (ffpre)
+// the bits of segment seg: the last entry of its prefix sums
+__device__ __forceinline__ long long jf_bits(const JfifGeom &g, const unsigned long long *boff, long long seg)
 {
-    __shared__ long long s[kJfScanThreads];
-    const long long seg = blockIdx.x, per = (n + kJfScanThreads - 1) / kJfScanThreads;
-    const long long lo = min(n, threadIdx.x * per), hi = min(n, lo + per);
-    const int *src = in + seg * n;
-    long long sum = 0;
-    for (long long i = lo; i < hi; i++) sum += src[i];
-    s[threadIdx.x] = sum;
-    __syncthreads();
-    for (int off = 1; off < kJfScanThreads; off <<= 1) {     // Hillis-Steele inclusive scan of the thread sums
-        const long long v = threadIdx.x >= off ? s[threadIdx.x - off] : 0;
-        __syncthreads();
-        s[threadIdx.x] += v;
-        __syncthreads();
-    }
-    long long run = s[threadIdx.x] - sum;
-    long long *dst = out + seg * n;
-    for (long long i = lo; i < hi; i++) {
-        dst[i] = run;
-        run += src[i];
-    }
-    if (threadIdx.x == kJfScanThreads - 1) tot[seg] = s[kJfScanThreads - 1];
+    return (long long)boff[seg * (g.nblk + 1) + g.nblk];
 }
 
-// big-endian bit writer into 32-bit words (stream byte order in memory); words shared with neighbouring blocks are ORed in
-struct JfBits {
-    unsigned *w;
-    long long wi, limit;
-    unsigned long long acc;
-    int n;
-    __device__ JfBits(unsigned *words, long long pos, long long lim) : w(words), wi(pos >> 5), limit(lim), acc(0), n((int)(pos & 31)) {}
-    __device__ __forceinline__ void word(unsigned v)
-    {
-        if (wi < limit) atomicOr(w + wi, __builtin_bswap32(v));
-        wi++;
-    }
-    __device__ __forceinline__ void put(unsigned code, int len)      // len <= 27
-    {
-        acc = (acc << len) | code;
-        n += len;
-        if (n >= 32) {
-            n -= 32;
-            word((unsigned)(acc >> n));
-            acc &= (1ull << n) - 1;
-        }
-    }
-    __device__ __forceinline__ void finish()
-    {
-        if (n > 0) word((unsigned)(acc << (32 - n)));
-    }
-};
-
-__global__ __launch_bounds__(kJfThreads) void k_jfif_zero(JfifGeom g, const long long *__restrict__ btot, unsigned *__restrict__ stream)
+__global__ __launch_bounds__(kJfThreads) void k_jfif_zero(JfifGeom g, const unsigned long long *__restrict__ boff, unsigned *__restrict__ stream)
 {
     const long long seg = blockIdx.y, i = (long long)blockIdx.x * kJfThreads + threadIdx.x;
-    if (i < min(g.stream_words, (btot[seg] + 31) / 32)) stream[seg * g.stream_words + i] = 0;
+    if (i < min(g.stream_words, (jf_bits(g, boff, seg) + 31) / 32)) stream[seg * g.stream_words + i] = 0;
 }
 
 // (c) every block's code string at its bit offset
 // kOpt: the codes are the file's own (k_jfif_tables) instead of the Annex K constants
 template <int HS, int VS, bool kOpt, int NC>
-__global__ __launch_bounds__(kJfThreads) void k_jfif_emit(JfifGeom g, const short *__restrict__ coef, const long long *__restrict__ boff,
-                                                          const long long *__restrict__ btot, const unsigned *__restrict__ codes,
-                                                          unsigned *__restrict__ stream)
+__global__ __launch_bounds__(kJfThreads) void k_jfif_emit(JfifGeom g, const short *__restrict__ coef, const unsigned long long *__restrict__ boff,
+                                                          const unsigned *__restrict__ codes, unsigned *__restrict__ stream)
 {
     constexpr int NL = HS * VS, BPM = NL + NC - 1;
     const long long idx = (long long)blockIdx.x * kJfThreads + threadIdx.x;
@@ -453,10 +374,10 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_emit(JfifGeom g, const shor
     const int k = (int)(blk % BPM);
     const JfCodes hc = kOpt ? jf_file_codes(codes, seg, k >= NL) : jf_codes(k >= NL);
     const short *c = coef + idx * 64;
-    const long long pb = jf_prev<HS, VS, NC>(m, k);
-    JfBits bw(stream + seg * g.stream_words, boff[idx], g.stream_words);
+    const long long pb = js_prev(NL, BPM, m, k);
+    JeBits bw(stream + seg * g.stream_words, (long long)boff[idx + seg], g.stream_words);      // n + 1 entries per segment
     const int diff = c[0] - (pb < 0 ? 0 : coef[(seg * g.nblk + pb) * 64]);
-    const int dcat = jf_cat(diff);
+    const int dcat = js_nbits(diff);
     bw.put(hc.dc[dcat] >> 8, (int)(hc.dc[dcat] & 255));
     if (dcat) bw.put((unsigned)(diff < 0 ? diff - 1 : diff) & ((1u << dcat) - 1), dcat);
     int run = 0;
@@ -464,7 +385,7 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_emit(JfifGeom g, const shor
         const int v = c[i];
         if (v == 0) { run++; continue; }
         for (; run > 15; run -= 16) bw.put(hc.ac[0xF0] >> 8, (int)(hc.ac[0xF0] & 255));
-        const int cat = jf_cat(v);
+        const int cat = js_nbits(v);
         const unsigned e = hc.ac[(run << 4) | cat];
         bw.put(e >> 8, (int)(e & 255));
         bw.put((unsigned)(v < 0 ? v - 1 : v) & ((1u << cat) - 1), cat);
@@ -472,36 +393,35 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_emit(JfifGeom g, const shor
     }
     if (run) bw.put(hc.ac[0] >> 8, (int)(hc.ac[0] & 255));
     if (blk == g.nblk - 1) {                                 // pad the last byte with 1-bits
-        const int pad = (int)((8 - (btot[seg] & 7)) & 7);
+        const int pad = (int)((8 - (jf_bits(g, boff, seg) & 7)) & 7);
         if (pad) bw.put((1u << pad) - 1, pad);
     }
     bw.finish();
 }
 
 // 0xFF bytes per 64-byte chunk of each stream's data
-__global__ __launch_bounds__(kJfThreads) void k_jfif_ffcount(JfifGeom g, const long long *__restrict__ btot, const unsigned *__restrict__ stream,
+__global__ __launch_bounds__(kJfThreads) void k_jfif_ffcount(JfifGeom g, const unsigned long long *__restrict__ boff, const unsigned *__restrict__ stream,
                                                              int *__restrict__ cnt)
 {
     const long long idx = (long long)blockIdx.x * kJfThreads + threadIdx.x;
     if (idx >= (long long)g.nq * g.B * g.n_chunks) return;
-    const long long seg = idx / g.n_chunks, ch = idx % g.n_chunks, nbytes = min(g.stream_words * 4, (btot[seg] + 7) >> 3);
+    const long long seg = idx / g.n_chunks, ch = idx % g.n_chunks, nbytes = min(g.stream_words * 4, (jf_bits(g, boff, seg) + 7) >> 3);
     const long long lo = ch * kJfChunk, hi = min(nbytes, lo + kJfChunk);
     const unsigned char *src = reinterpret_cast<const unsigned char *>(stream + seg * g.stream_words);
-    int n = 0;
-    for (long long i = lo; i < hi; i++) n += src[i] == 0xFF;
-    cnt[idx] = n;
+    cnt[idx] = js_stuff_count(src, lo, hi);
 }
 
 // file lengths (markers + stuffed data + EOI) and their offsets in the packed output, segments in (quality, image) order
 // (with per-file tables the markers of file seg are fhdr[seg], fhdr_len[seg] bytes; otherwise those of its quality)
 __global__ void k_jfif_layout(JfifGeom g, const JfifParams *__restrict__ par, const int *__restrict__ fhdr_len,
-                              const long long *__restrict__ btot, const long long *__restrict__ fftot, long long *__restrict__ lengths,
-                              long long *__restrict__ offsets, long long *__restrict__ total)
+                              const unsigned long long *__restrict__ boff, const unsigned long long *__restrict__ ffpre,
+                              long long *__restrict__ lengths, long long *__restrict__ offsets, long long *__restrict__ total)
 {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
     long long off = 0;
     for (long long seg = 0; seg < (long long)g.nq * g.B; seg++) {
-        const long long len = (g.opt ? fhdr_len[seg] : par[seg / g.B].hdr_len) + ((btot[seg] + 7) >> 3) + fftot[seg] + 2;
+        const long long len = (g.opt ? fhdr_len[seg] : par[seg / g.B].hdr_len) + ((jf_bits(g, boff, seg) + 7) >> 3) +
+                              (long long)ffpre[seg * (g.n_chunks + 1) + g.n_chunks] + 2;
         lengths[seg] = len;
         offsets[seg] = off;
         off += len;
@@ -511,8 +431,8 @@ __global__ void k_jfif_layout(JfifGeom g, const JfifParams *__restrict__ par, co
 
 __global__ __launch_bounds__(kJfThreads) void k_jfif_scatter(JfifGeom g, const JfifParams *__restrict__ par,
                                                              const unsigned char *__restrict__ fhdr, const int *__restrict__ fhdr_len,
-                                                             const long long *__restrict__ btot,
-                                                             const unsigned *__restrict__ stream, const long long *__restrict__ ffpre,
+                                                             const unsigned long long *__restrict__ boff,
+                                                             const unsigned *__restrict__ stream, const unsigned long long *__restrict__ ffpre,
                                                              const long long *__restrict__ lengths, const long long *__restrict__ offsets,
                                                              unsigned char *__restrict__ out, unsigned long long cap)
 {
@@ -529,23 +449,12 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_scatter(JfifGeom g, const J
         file[len - 2] = 0xFF;
         file[len - 1] = 0xD9;
     }
-    const long long nbytes = (btot[seg] + 7) >> 3, lo = ch * kJfChunk, hi = min(nbytes, lo + kJfChunk);
+    const long long nbytes = (jf_bits(g, boff, seg) + 7) >> 3, lo = ch * kJfChunk, hi = min(nbytes, lo + kJfChunk);
     const unsigned char *src = reinterpret_cast<const unsigned char *>(stream + seg * g.stream_words);
-    unsigned char *dst = file + hdr_len + lo + (lo < hi ? ffpre[idx] : 0);
-    for (long long i = lo; i < hi; i++) {
-        const unsigned char v = src[i];
-        *dst++ = v;
-        if (v == 0xFF) *dst++ = 0;
-    }
+    if (lo < hi) js_stuff_copy(file + hdr_len + lo + (long long)ffpre[idx + seg], src, lo, hi);      // n + 1 entries per segment
 }
 
 // ---- reconstruction ----------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned char jf_range_limit(long long x)      // libjpeg's masked table: wraps as the decoder's does
-{
-    const int m = (int)(x & 1023);
-    return (unsigned char)(m < 128 ? m + 128 : m < 512 ? 255 : m < 896 ? 0 : m - 896);
-}
-
 template <int HS, int VS>
 __global__ __launch_bounds__(kJfThreads) void k_jfif_idct(JfifGeom g, const JfifParams *__restrict__ par, const short *__restrict__ coef,
                                                           unsigned char *__restrict__ planes)
@@ -560,11 +469,11 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_idct(JfifGeom g, const Jfif
     const short *c = coef + idx * 64;
     long long d[64];
 #pragma unroll
-    for (int j = 0; j < 64; j++) d[j] = c[kJfInvZz[j]] * qt[kJfInvZz[j]];      // natural order (j constant after unrolling)
+    for (int j = 0; j < 64; j++) d[j] = c[kZigzag8.position[j]] * qt[kZigzag8.position[j]];      // natural order (j constant after unrolling)
 #pragma unroll
-    for (int col = 0; col < 8; col++) jf_idct8<true>(d + col, 8);
+    for (int col = 0; col < 8; col++) jd_idct8<true>(d + col, 8);
 #pragma unroll
-    for (int r = 0; r < 8; r++) jf_idct8<false>(d + r * 8, 1);
+    for (int r = 0; r < 8; r++) jd_idct8<false>(d + r * 8, 1);
     unsigned char *pl = planes + seg * g.plane_bytes;
     int stride, y0, x0;
     if (k < NL) {
@@ -576,7 +485,7 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_idct(JfifGeom g, const Jfif
 #pragma unroll
     for (int r = 0; r < 8; r++)
 #pragma unroll
-        for (int cc = 0; cc < 8; cc++) pl[(long long)(y0 + r) * stride + x0 + cc] = jf_range_limit(d[r * 8 + cc]);
+        for (int cc = 0; cc < 8; cc++) pl[(long long)(y0 + r) * stride + x0 + cc] = jd_range_limit(d[r * 8 + cc]);
 }
 
 // chroma of output pixel (y, x): jd_chroma (jpegdec_core.h) over the real ceil(H / VS) x ceil(W / HS) samples -- h2v2 / h2v1 fancy
@@ -593,14 +502,7 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_rgb(JfifGeom g, const unsig
     const int Y = pl[(long long)y * g.yw + x];
     const unsigned char *cbp = pl + (long long)g.yh * g.yw, *crp = cbp + (long long)g.ch * g.cw;
     const int wc = (g.W + HS - 1) / HS, hc = (g.H + VS - 1) / VS;
-    const int cb = jd_chroma(cbp, g.cw, HS, VS, wc, hc, y, x) - 128, cr = jd_chroma(crp, g.cw, HS, VS, wc, hc, y, x) - 128;
-    const int R = Y + ((91881 * cr + 32768) >> 16);
-    const int G = Y + ((-22554 * cb + 32768 - 46802 * cr) >> 16);
-    const int B = Y + ((116130 * cb + 32768) >> 16);
-    unsigned char *o = out + idx * 3;
-    o[0] = (unsigned char)min(max(R, 0), 255);
-    o[1] = (unsigned char)min(max(G, 0), 255);
-    o[2] = (unsigned char)min(max(B, 0), 255);
+    jd_rgb(Y, jd_chroma(cbp, g.cw, HS, VS, wc, hc, y, x), jd_chroma(crp, g.cw, HS, VS, wc, hc, y, x), out + idx * 3);
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------
@@ -656,12 +558,10 @@ unsigned long long jfif_carve(void *base, const JfifGeom &g, JfifBufs &w)
     w.dct = c.take<int>((long long)g.B * g.nblk * 64);
     w.coef = c.take<short>(segs * g.nblk * 64);
     w.lens = c.take<int>(segs * g.nblk);
-    w.boff = c.take<long long>(segs * g.nblk);
-    w.btot = c.take<long long>(segs);
+    w.boff = c.take<unsigned long long>(segs * (g.nblk + 1));
     w.stream = c.take<unsigned>(segs * g.stream_words);
     w.ffcnt = c.take<int>(segs * g.n_chunks);
-    w.ffpre = c.take<long long>(segs * g.n_chunks);
-    w.fftot = c.take<long long>(segs);
+    w.ffpre = c.take<unsigned long long>(segs * (g.n_chunks + 1));
     w.total = c.take<long long>(1);
     w.planes = c.take<unsigned char>(segs * g.plane_bytes);
     w.hist = nullptr; w.codes = nullptr; w.fhdr = nullptr; w.fhdr_len = nullptr;
@@ -683,12 +583,10 @@ unsigned long long jfif_carve_coded(Carver &c, const JfifGeom &g, JfifBufs &w)
     w.par = c.take<JfifParams>(g.nq);
     w.coef = c.take<short>(segs * g.nblk * 64);
     w.lens = c.take<int>(segs * g.nblk);
-    w.boff = c.take<long long>(segs * g.nblk);
-    w.btot = c.take<long long>(segs);
+    w.boff = c.take<unsigned long long>(segs * (g.nblk + 1));
     w.stream = c.take<unsigned>(segs * g.stream_words);
     w.ffcnt = c.take<int>(segs * g.n_chunks);
-    w.ffpre = c.take<long long>(segs * g.n_chunks);
-    w.fftot = c.take<long long>(segs);
+    w.ffpre = c.take<unsigned long long>(segs * (g.n_chunks + 1));
     w.total = c.take<long long>(1);
     w.hist = c.take<unsigned long long>(segs * 4 * kJhSymbols);
     w.codes = c.take<unsigned>(segs * 4 * 256);
@@ -720,15 +618,13 @@ void jfif_quant_tables(int q, int luma[64], int chroma[64])
     }
 }
 
-static const unsigned char kZzHost[64] = { AEJ_ZIGZAG_8X8 };
-
 void jfif_params_host(int q, int H, int W, JfifParams &p, int ss, int ncomp)
 {
     const int nt = ncomp == 1 ? 1 : 2;                       // a grey file: the luma quantiser and the two luma Huffman tables alone
     int t[2][64];
     jfif_quant_tables(q, t[0], t[1]);
     for (int c = 0; c < 2; c++)
-        for (int i = 0; i < 64; i++) p.qt[c][i] = t[c][kZzHost[i]];
+        for (int i = 0; i < 64; i++) p.qt[c][i] = t[c][kZigzag8.natural[i]];
     unsigned char *o = p.hdr;
     int n = 0;
     auto put = [&](std::initializer_list<int> v) { for (int x : v) o[n++] = (unsigned char)x; };
@@ -762,124 +658,97 @@ void jfif_params_host(int q, int H, int W, JfifParams &p, int ss, int ncomp)
 
 static unsigned jf_blocks(long long n) { return (unsigned)((n + kJfThreads - 1) / kJfThreads); }
 
+// the kernels' template arguments of a geometry: f(JfShape<HS, VS, NC>{}) for g's sampling factors and component count
+template <int HS, int VS, int NC>
+struct JfShape { static constexpr int hs = HS, vs = VS, nc = NC; };
+template <class F>
+static hipError_t jf_dispatch(const JfifGeom &g, F f)
+{
+    if (g.ncomp == 1) return f(JfShape<1, 1, 1>{});
+    if (g.hs == 1) return f(JfShape<1, 1, 3>{});
+    if (g.vs == 1) return f(JfShape<2, 1, 3>{});
+    return f(JfShape<2, 2, 3>{});
+}
+
 // the stages from w.coef to the file lengths and offsets (k_jfif_quant has left the Annex K bit counts in w.lens)
 // annexk (requires g.opt): the table-driven stages under the Annex K tables -- k_jfif_annexk in the place of histogram and tables
-template <int HS, int VS, int NC = 3>
-static hipError_t jf_entropy(hipStream_t st, const JfifGeom &g, const JfifBufs &w, long long *lengths, long long *offsets, bool annexk = false)
+template <int HS, int VS, int NC>
+static hipError_t jf_entropy(hipStream_t st, const JfifGeom &g, const JfifBufs &w, long long *lengths, long long *offsets, bool annexk)
 {
     const long long segs = (long long)g.nq * g.B, nb = segs * g.nblk, nc = segs * g.n_chunks;
+    const dim3 th(kJfThreads), per_seg((unsigned)segs), scan_th(kJsScanThreads);
     if (annexk && !g.opt) return hipErrorInvalidValue;
     if (annexk) {
-        hipLaunchKernelGGL(k_jfif_annexk, dim3((unsigned)segs), dim3(kJfThreads), 0, st, g, w.par, w.codes, w.fhdr, w.fhdr_len);
+        hipLaunchKernelGGL(k_jfif_annexk, per_seg, th, 0, st, g, w.par, w.codes, w.fhdr, w.fhdr_len);
     } else if (g.opt) {
         const hipError_t e = hipMemsetAsync(w.hist, 0, (size_t)segs * 4 * kJhSymbols * 8, st);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((k_jfif_hist<HS, VS, NC>), dim3(jf_blocks(g.nblk), (unsigned)segs), dim3(kJfThreads), 0, st, g, w.coef, w.hist);
-        hipLaunchKernelGGL(k_jfif_tables, dim3((unsigned)segs), dim3(kJfThreads), 0, st, g, w.par, w.hist, w.codes, w.fhdr, w.fhdr_len);
+        hipLaunchKernelGGL((k_jfif_hist<HS, VS, NC>), dim3(jf_blocks(g.nblk), (unsigned)segs), th, 0, st, g, w.coef, w.hist);
+        hipLaunchKernelGGL(k_jfif_tables, per_seg, th, 0, st, g, w.par, w.hist, w.codes, w.fhdr, w.fhdr_len);
     }
-    if (g.opt)
-        hipLaunchKernelGGL((k_jfif_count<HS, VS, NC>), dim3(jf_blocks(nb)), dim3(kJfThreads), 0, st, g, w.coef, w.codes, w.lens);
-    hipLaunchKernelGGL(k_jfif_scan, dim3((unsigned)segs), dim3(kJfScanThreads), 0, st, w.lens, g.nblk, w.boff, w.btot);
-    hipLaunchKernelGGL(k_jfif_zero, dim3((unsigned)((g.stream_words + kJfThreads - 1) / kJfThreads), (unsigned)segs), dim3(kJfThreads), 0, st, g,
-                       w.btot, w.stream);
-    if (g.opt)
-        hipLaunchKernelGGL((k_jfif_emit<HS, VS, true, NC>), dim3(jf_blocks(nb)), dim3(kJfThreads), 0, st, g, w.coef, w.boff, w.btot, w.codes, w.stream);
-    else
-        hipLaunchKernelGGL((k_jfif_emit<HS, VS, false, NC>), dim3(jf_blocks(nb)), dim3(kJfThreads), 0, st, g, w.coef, w.boff, w.btot, w.codes, w.stream);
-    hipLaunchKernelGGL(k_jfif_ffcount, dim3(jf_blocks(nc)), dim3(kJfThreads), 0, st, g, w.btot, w.stream, w.ffcnt);
-    hipLaunchKernelGGL(k_jfif_scan, dim3((unsigned)segs), dim3(kJfScanThreads), 0, st, w.ffcnt, g.n_chunks, w.ffpre, w.fftot);
-    hipLaunchKernelGGL(k_jfif_layout, dim3(1), dim3(1), 0, st, g, w.par, w.fhdr_len, w.btot, w.fftot, lengths, offsets, w.total);
+    if (g.opt) hipLaunchKernelGGL((k_jfif_count<HS, VS, NC>), dim3(jf_blocks(nb)), th, 0, st, g, w.coef, w.codes, w.lens);
+    hipLaunchKernelGGL(k_js_scan<JsInts>, per_seg, scan_th, 0, st, JsInts{ w.lens }, g.nblk, w.boff);
+    hipLaunchKernelGGL(k_jfif_zero, dim3(jf_blocks(g.stream_words), (unsigned)segs), th, 0, st, g, w.boff, w.stream);
+    if (g.opt) hipLaunchKernelGGL((k_jfif_emit<HS, VS, true, NC>), dim3(jf_blocks(nb)), th, 0, st, g, w.coef, w.boff, w.codes, w.stream);
+    else hipLaunchKernelGGL((k_jfif_emit<HS, VS, false, NC>), dim3(jf_blocks(nb)), th, 0, st, g, w.coef, w.boff, w.codes, w.stream);
+    hipLaunchKernelGGL(k_jfif_ffcount, dim3(jf_blocks(nc)), th, 0, st, g, w.boff, w.stream, w.ffcnt);
+    hipLaunchKernelGGL(k_js_scan<JsInts>, per_seg, scan_th, 0, st, JsInts{ w.ffcnt }, g.n_chunks, w.ffpre);
+    hipLaunchKernelGGL(k_jfif_layout, dim3(1), dim3(1), 0, st, g, w.par, w.fhdr_len, w.boff, w.ffpre, lengths, offsets, w.total);
     return hipGetLastError();
 }
 
-static hipError_t jf_scatter(hipStream_t st, const JfifGeom &g, const JfifBufs &w, const long long *lengths, const long long *offsets,
-                             unsigned char *out, unsigned long long cap)
+// the transcoder's cut (jfiftrans.hip): given coefficients in w.coef and the files' markers in w.par (uploaded by the caller), the
+// entropy stages up to the lengths, and the scatter as a launch of its own once the caller has placed the files
+hipError_t launch_jfif_entropy(hipStream_t st, const JfifGeom &g, const JfifBufs &w, long long *lengths, long long *offsets)
+{
+    return jf_dispatch(g, [&](auto s) { return jf_entropy<s.hs, s.vs, s.nc>(st, g, w, lengths, offsets, false); });
+}
+
+hipError_t launch_jfif_entropy_annexk(hipStream_t st, const JfifGeom &g, const JfifBufs &w, long long *lengths, long long *offsets)
+{
+    return jf_dispatch(g, [&](auto s) { return jf_entropy<s.hs, s.vs, s.nc>(st, g, w, lengths, offsets, true); });
+}
+
+hipError_t launch_jfif_scatter(hipStream_t st, const JfifGeom &g, const JfifBufs &w, const long long *lengths, const long long *offsets,
+                               unsigned char *out, unsigned long long cap)
 {
     hipLaunchKernelGGL(k_jfif_scatter, dim3(jf_blocks((long long)g.nq * g.B * g.n_chunks)), dim3(kJfThreads), 0, st, g, w.par, w.fhdr, w.fhdr_len,
-                       w.btot, w.stream, w.ffpre, lengths, offsets, out, cap);
+                       w.boff, w.stream, w.ffpre, lengths, offsets, out, cap);
     return hipGetLastError();
 }
 
-template <int HS, int VS>
-static hipError_t jf_encode(hipStream_t st, const JfifGeom &g, const JfifBufs &w, const JfifParams *par_host, const unsigned char *rgb,
-                            unsigned char *out, unsigned long long cap, long long *lengths, long long *offsets)
+hipError_t launch_jfif_coefs(hipStream_t st, const JfifGeom &g, const JfifBufs &w, const JfifParams *par_host, const unsigned char *rgb)
 {
-    hipError_t e = hipMemcpyAsync(w.par, par_host, sizeof(JfifParams) * g.nq, hipMemcpyHostToDevice, st);
+    if (g.ncomp != 3) return hipErrorInvalidValue;           // colour, FDCT and quantisation are three-component
+    const hipError_t e = hipMemcpyAsync(w.par, par_host, sizeof(JfifParams) * g.nq, hipMemcpyHostToDevice, st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_jfif_fdct<HS, VS>), dim3(jf_blocks((long long)g.B * g.nblk)), dim3(kJfThreads), 0, st, g, rgb, w.dct);
-    hipLaunchKernelGGL((k_jfif_quant<HS, VS>), dim3(jf_blocks((long long)g.nq * g.B * g.nblk)), dim3(kJfThreads), 0, st, g, w.par, w.dct, w.coef,
-                       w.lens);
-    if ((e = jf_entropy<HS, VS>(st, g, w, lengths, offsets)) != hipSuccess) return e;
-    return out ? jf_scatter(st, g, w, lengths, offsets, out, cap) : hipSuccess;
+    return jf_dispatch(g, [&](auto s) {
+        const long long nb = (long long)g.B * g.nblk;
+        hipLaunchKernelGGL((k_jfif_fdct<s.hs, s.vs>), dim3(jf_blocks(nb)), dim3(kJfThreads), 0, st, g, rgb, w.dct);
+        hipLaunchKernelGGL((k_jfif_quant<s.hs, s.vs>), dim3(jf_blocks(g.nq * nb)), dim3(kJfThreads), 0, st, g, w.par, w.dct, w.coef, w.lens);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_jfif_encode(hipStream_t st, const JfifGeom &g, const JfifBufs &w, const JfifParams *par_host, const unsigned char *rgb,
                               unsigned char *out, unsigned long long cap, long long *lengths, long long *offsets)
 {
     if (g.ncomp != 3) return hipErrorInvalidValue;           // the same-size encoder is three-component
-    if (g.hs == 1) return jf_encode<1, 1>(st, g, w, par_host, rgb, out, cap, lengths, offsets);
-    if (g.vs == 1) return jf_encode<2, 1>(st, g, w, par_host, rgb, out, cap, lengths, offsets);
-    return jf_encode<2, 2>(st, g, w, par_host, rgb, out, cap, lengths, offsets);
-}
-
-// the transcoder's cut (jfiftrans.hip): given coefficients in w.coef and the files' markers in w.par (uploaded by the caller), the
-// optimised entropy stages up to the lengths, and the scatter as a launch of its own once the caller has placed the files
-hipError_t launch_jfif_entropy(hipStream_t st, const JfifGeom &g, const JfifBufs &w, long long *lengths, long long *offsets)
-{
-    if (g.ncomp == 1) return jf_entropy<1, 1, 1>(st, g, w, lengths, offsets);
-    if (g.hs == 1) return jf_entropy<1, 1>(st, g, w, lengths, offsets);
-    if (g.vs == 1) return jf_entropy<2, 1>(st, g, w, lengths, offsets);
-    return jf_entropy<2, 2>(st, g, w, lengths, offsets);
-}
-
-hipError_t launch_jfif_entropy_annexk(hipStream_t st, const JfifGeom &g, const JfifBufs &w, long long *lengths, long long *offsets)
-{
-    if (g.ncomp == 1) return jf_entropy<1, 1, 1>(st, g, w, lengths, offsets, true);
-    if (g.hs == 1) return jf_entropy<1, 1>(st, g, w, lengths, offsets, true);
-    if (g.vs == 1) return jf_entropy<2, 1>(st, g, w, lengths, offsets, true);
-    return jf_entropy<2, 2>(st, g, w, lengths, offsets, true);
-}
-
-hipError_t launch_jfif_scatter(hipStream_t st, const JfifGeom &g, const JfifBufs &w, const long long *lengths, const long long *offsets,
-                               unsigned char *out, unsigned long long cap)
-{
-    return jf_scatter(st, g, w, lengths, offsets, out, cap);
-}
-
-template <int HS, int VS>
-static hipError_t jf_coefs(hipStream_t st, const JfifGeom &g, const JfifBufs &w, const JfifParams *par_host, const unsigned char *rgb)
-{
-    hipError_t e = hipMemcpyAsync(w.par, par_host, sizeof(JfifParams) * g.nq, hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_jfif_fdct<HS, VS>), dim3(jf_blocks((long long)g.B * g.nblk)), dim3(kJfThreads), 0, st, g, rgb, w.dct);
-    hipLaunchKernelGGL((k_jfif_quant<HS, VS>), dim3(jf_blocks((long long)g.nq * g.B * g.nblk)), dim3(kJfThreads), 0, st, g, w.par, w.dct, w.coef,
-                       w.lens);
-    return hipGetLastError();
-}
-
-hipError_t launch_jfif_coefs(hipStream_t st, const JfifGeom &g, const JfifBufs &w, const JfifParams *par_host, const unsigned char *rgb)
-{
-    if (g.ncomp != 3) return hipErrorInvalidValue;
-    if (g.hs == 1) return jf_coefs<1, 1>(st, g, w, par_host, rgb);
-    if (g.vs == 1) return jf_coefs<2, 1>(st, g, w, par_host, rgb);
-    return jf_coefs<2, 2>(st, g, w, par_host, rgb);
-}
-
-template <int HS, int VS>
-static hipError_t jf_recon(hipStream_t st, const JfifGeom &g, const JfifBufs &w, unsigned char *rgb_out)
-{
-    const long long segs = (long long)g.nq * g.B;
-    hipLaunchKernelGGL((k_jfif_idct<HS, VS>), dim3(jf_blocks(segs * g.nblk)), dim3(kJfThreads), 0, st, g, w.par, w.coef, w.planes);
-    hipLaunchKernelGGL((k_jfif_rgb<HS, VS>), dim3(jf_blocks(segs * g.H * g.W)), dim3(kJfThreads), 0, st, g, w.planes, rgb_out);
-    return hipGetLastError();
+    hipError_t e = launch_jfif_coefs(st, g, w, par_host, rgb);
+    if (e == hipSuccess) e = launch_jfif_entropy(st, g, w, lengths, offsets);
+    if (e == hipSuccess && out) e = launch_jfif_scatter(st, g, w, lengths, offsets, out, cap);
+    return e;
 }
 
 hipError_t launch_jfif_recon(hipStream_t st, const JfifGeom &g, const JfifBufs &w, unsigned char *rgb_out)
 {
     if (g.ncomp != 3) return hipErrorInvalidValue;
-    if (g.hs == 1) return jf_recon<1, 1>(st, g, w, rgb_out);
-    if (g.vs == 1) return jf_recon<2, 1>(st, g, w, rgb_out);
-    return jf_recon<2, 2>(st, g, w, rgb_out);
+    return jf_dispatch(g, [&](auto s) {
+        const long long segs = (long long)g.nq * g.B;
+        hipLaunchKernelGGL((k_jfif_idct<s.hs, s.vs>), dim3(jf_blocks(segs * g.nblk)), dim3(kJfThreads), 0, st, g, w.par, w.coef, w.planes);
+        hipLaunchKernelGGL((k_jfif_rgb<s.hs, s.vs>), dim3(jf_blocks(segs * g.H * g.W)), dim3(kJfThreads), 0, st, g, w.planes, rgb_out);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace aej

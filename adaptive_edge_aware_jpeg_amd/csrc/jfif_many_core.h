@@ -12,6 +12,7 @@
 // bytes.
 #pragma once
 #include <stdint.h>
+#include "aej_common.h"
 #include "jfif_arith.h"
 
 namespace aej {
@@ -89,9 +90,8 @@ AEJ_HD inline void jm_row(const unsigned char *img, const JmGeom &g, const JmBlo
 // qt (the component's table in zigzag order): a dummy keeps the DC alone
 AEJ_HD __forceinline__ short jm_store(const JmBlock &blk, int n, long long c, int qt) { return blk.dummy && n != 0 ? (short)0 : (short)jf_quant((int)c, qt); }
 
-// One whole block on one thread (the host entry): out[64] in zigzag order.  qt: [2][64] luma, chroma in zigzag order; zz: zigzag
-// position -> natural index
-AEJ_HD inline void jm_block_coefs(const unsigned char *img, const JmGeom &g, int b, const unsigned short *qt, const unsigned char *zz, short *out)
+// One whole block on one thread (the host entry): out[64] in zigzag order.  qt: [2][64] luma, chroma in zigzag order
+AEJ_HD inline void jm_block_coefs(const unsigned char *img, const JmGeom &g, int b, const unsigned short *qt, short *out)
 {
     const JmBlock blk = jm_block(g, b);
     long long d[64];
@@ -100,7 +100,10 @@ AEJ_HD inline void jm_block_coefs(const unsigned char *img, const JmGeom &g, int
         jf_fdct8<true>(d + r * 8, 1);
     }
     for (int c = 0; c < 8; c++) jf_fdct8<false>(d + c, 8);
-    for (int z = 0; z < 64; z++) out[z] = jm_store(blk, zz[z], d[zz[z]], qt[(blk.comp > 0) * 64 + z]);
+    for (int z = 0; z < 64; z++) {
+        const int n = kZigzag8.natural[z];
+        out[z] = jm_store(blk, n, d[n], qt[(blk.comp > 0) * 64 + z]);
+    }
 }
 
 }  // namespace aej

@@ -13,9 +13,7 @@
 #pragma once
 #include <stdint.h>
 
-#ifndef AEJ_HD
-#define AEJ_HD __host__ __device__
-#endif
+#include "jfif_stream_core.h"
 
 namespace aej {
 
@@ -29,13 +27,6 @@ struct JeBlock {
     unsigned long long brbits;         // those bits, the first one highest
 };
 
-AEJ_HD inline int je_nbits(int v)      // v >= 0
-{
-    int n = 0;
-    while (v) { n++; v >>= 1; }
-    return n;
-}
-
 // bits that bound one block of a scan (|coefficients| <= kJeMaxCoef): DC first 16 + 12; DC refinement 1; AC first 16 + 11 per
 // coefficient (a ZRL stands for 16 of them); AC refinement 16 + 1 per coefficient; the EOBn symbol 16 + 14
 AEJ_HD inline int je_block_bound(int Ss, int Se, int Ah)
@@ -48,7 +39,7 @@ AEJ_HD inline int je_block_bound(int Ss, int Se, int Ah)
 template <class Sink>
 AEJ_HD inline void je_dc_first(int cur, int prev, int Al, Sink &s)      // prev: the component's block before in scan order (0 at the start)
 {
-    const int diff = (cur >> Al) - (prev >> Al), n = je_nbits(diff < 0 ? -diff : diff);
+    const int diff = (cur >> Al) - (prev >> Al), n = js_nbits(diff);
     s.sym(n);
     if (n) s.bits((unsigned)(diff < 0 ? diff - 1 : diff) & ((1u << n) - 1), n);
 }
@@ -65,7 +56,7 @@ AEJ_HD inline JeBlock je_ac_first(const short *c, int Ss, int Se, int Al, Sink &
         if (t == 0) { r++; continue; }
         b.e = 1;                                             // here libjpeg flushes the run before: it ended with the block before
         for (; r > 15; r -= 16) s.sym(0xF0);
-        const int n = je_nbits(t);
+        const int n = js_nbits(t);
         s.sym((r << 4) | n);
         s.bits((unsigned)(v < 0 ? ~t : t) & ((1u << n) - 1), n);
         r = 0;
@@ -112,7 +103,7 @@ AEJ_HD inline JeBlock je_ac_refine(const short *c, int Ss, int Se, int Al, Sink 
 template <class Sink>
 AEJ_HD inline void je_eobrun(int run, Sink &s)              // the EOBn symbol of a piece of `run` >= 1 blocks
 {
-    const int n = je_nbits(run) - 1;
+    const int n = js_nbits(run) - 1;
     s.sym(n << 4);
     if (n) s.bits((unsigned)run & ((1u << n) - 1), n);
 }
@@ -160,44 +151,7 @@ AEJ_HD inline long long je_piece_end(const unsigned long long *P, long long p, l
     return lim;
 }
 
-// ---- big-endian bit writer into zeroed 32-bit words (stream byte order in memory); on the device words shared with neighbouring
-// blocks are ORed in atomically; stores beyond `limit` words are dropped
-AEJ_HD inline unsigned je_bswap(unsigned v) { return (v >> 24) | ((v >> 8) & 0xFF00u) | ((v << 8) & 0xFF0000u) | (v << 24); }
-struct JeBits {
-    unsigned *w;
-    long long wi, limit;
-    unsigned long long acc;
-    int n;
-    AEJ_HD JeBits(unsigned *words, long long pos, long long lim) : w(words), wi(pos >> 5), limit(lim), acc(0), n((int)(pos & 31)) {}
-    AEJ_HD inline void word(unsigned v)
-    {
-        if (v != 0 && wi < limit) {                          // the words start as 0: an item that writes no bit touches no memory
-#if defined(__HIP_DEVICE_COMPILE__)
-            atomicOr(w + wi, je_bswap(v));
-#else
-            w[wi] |= je_bswap(v);
-#endif
-        }
-        wi++;
-    }
-    AEJ_HD inline void put(unsigned code, int len)          // len <= 32, code < 2^len
-    {
-        if (len == 0) return;
-        acc = (acc << len) | code;
-        n += len;
-        if (n >= 32) {
-            n -= 32;
-            word((unsigned)(acc >> n));
-            acc &= (1ull << n) - 1;
-        }
-    }
-    AEJ_HD inline void finish()
-    {
-        if (n > 0) word((unsigned)(acc << (32 - n)));
-    }
-};
-
-// sinks.  codes: (code << 8) | length per symbol (jh_codes)
+// ---- sinks.  codes: (code << 8) | length per symbol (jh_codes); JeEmit writes through JeBits (jfif_stream_core.h)
 struct JeNull {
     AEJ_HD inline void sym(int) {}
     AEJ_HD inline void bits(unsigned, int) {}

@@ -31,8 +31,6 @@ namespace aej {
 
 constexpr int kJmThreads = 256, kJmBlocks = kJmThreads / 8, kJmStride = 9;
 
-__constant__ unsigned char k_jm_izz[64] = { 0, 1, 5, 6, 14, 15, 27, 28, 2, 4, 7, 13, 16, 26, 29, 42, 3, 8, 12, 17, 25, 30, 41, 43, 9, 11, 18, 24, 31, 40, 44, 53, 10, 19, 23, 32, 39, 45, 52, 54, 20, 22, 33, 38, 46, 51, 55, 60, 21, 34, 37, 47, 50, 56, 59, 61, 35, 36, 48, 49, 57, 58, 62, 63 };      // zigzag position of natural index
-
 __device__ __forceinline__ int jm_find_image(const JmImage *f, int n, long long t)      // last image whose blk_base <= t (jt_find_file)
 {
     int lo = 0, hi = n - 1;
@@ -79,7 +77,7 @@ __global__ __launch_bounds__(kJmThreads) void k_jm_coefs(const JmImage *__restri
         const unsigned short *qt = I->qt[blk.comp > 0];
 #pragma unroll
         for (int r = 0; r < 8; r++) {
-            const int z = k_jm_izz[r * 8 + l];
+            const int z = k_zigzag8.position[r * 8 + l];
             zz[grp][z] = jm_store(blk, r * 8 + l, d[r], qt[z]);
         }
     }
@@ -88,14 +86,12 @@ __global__ __launch_bounds__(kJmThreads) void k_jm_coefs(const JmImage *__restri
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------
-static const unsigned char kJmZzHost[64] = { AEJ_ZIGZAG_8X8 };
-
 static void jm_tables(int quality, unsigned short qt[2][64])      // zigzag order, as JfifParams::qt
 {
     int t[2][64];
     jfif_quant_tables(quality, t[0], t[1]);
     for (int c = 0; c < 2; c++)
-        for (int i = 0; i < 64; i++) qt[c][i] = (unsigned short)t[c][kJmZzHost[i]];
+        for (int i = 0; i < 64; i++) qt[c][i] = (unsigned short)t[c][kZigzag8.natural[i]];
 }
 
 long long jfifmany_coefs_host(int W, int H, int quality, int ss, const unsigned char *rgb, short *dst, int ncomp)
@@ -105,7 +101,7 @@ long long jfifmany_coefs_host(int W, int H, int quality, int ss, const unsigned 
     if (!rgb || !dst) return g.n_blocks;
     unsigned short qt[2][64];
     jm_tables(quality, qt);
-    for (int b = 0; b < g.n_blocks; b++) jm_block_coefs(rgb, g, b, &qt[0][0], kJmZzHost, dst + (long long)b * 64);
+    for (int b = 0; b < g.n_blocks; b++) jm_block_coefs(rgb, g, b, &qt[0][0], dst + (long long)b * 64);
     return g.n_blocks;
 }
 

@@ -1,7 +1,8 @@
 // jfifprog.hip -- the progressive file Pillow writes with save(..., "JPEG", quality=q, subsampling=s, progressive=True): libjpeg's
 // jpeg_simple_progression of ten scans, every scan Huffman-coded under its own optimal table (aej_jfif_*_prog, include/aej.h).  Colour,
 // down-sampling, FDCT and quantisation are jfif.hip's (launch_jfif_coefs); this file codes the quantised coefficients.  The rules of
-// the coder -- what one block emits, how end-of-band runs and deferred correction bits partition a scan -- are jfif_prog_core.h;
+// the coder -- what one block emits, how end-of-band runs and deferred correction bits partition a scan -- are jfif_prog_core.h; the
+// bit writer, byte stuffing, predecessor block and prefix-sum kernel are jfif_stream_core.h, which the baseline coder shares;
 // tests/jfif_progressive_reference.py is libjpeg's serial state machine in Python and tests/test_*jfif_progressive*.py pin both to
 // Pillow's files byte for byte.  A one-component (grey) file takes libjpeg's six-scan script and one DC table (JfpGeom::nchroma = 0, as the
 // testing entry's plain list): its DC scans walk the component's blocks in raster order, which is its MCU order, so every kernel below
@@ -10,18 +11,19 @@
 // An item is one block of one scan; a file has T of them, scan after scan (interleaved scans walk the MCU-padded blocks in MCU order,
 // single-component scans the component's own blocks in raster order).  Stages (one launch each for every file of a call):
 //   k_jfp_facts    one thread per item of an AC scan: does the block emit, does it leave zeros or correction bits pending, how many
-//   k_jfp_scan     one workgroup per file: exclusive prefix sums of the packed (break, pending bits) values (je_pack)
+//   k_js_scan      one workgroup per file: exclusive prefix sums of the packed (break, pending bits) values (je_pack; JfpPacked) --
+//                  the segmented prefix-sum kernel of jfif_stream_core.h, which jfif.hip runs too
 //   k_jfp_cuts     one thread per chain start: the pieces of its chain, one binary search (je_piece_end) per piece; the opener of a
 //                  piece gets the piece's length.  The longest serial walk is the number of pieces of one chain: a piece spans 0x7FFF
 //                  blocks unless more than 937 bits are deferred, and then at least 15 (a block defers at most 63)
 //   k_jfp_hist     one thread per item: the symbols it writes (its own, and the EOBn of the piece it opens), counted per wave in LDS
 //   k_jfp_tables   one workgroup per file, one wave per table (two DC, eight AC): jh_build, the codes, the DHT / SOS markers per scan
 //   k_jfp_count    one thread per item: its bits under the file's codes (the scan's table staged in LDS, as in k_jfp_emit)
-//   k_jfp_scan     bit offsets
+//   k_js_scan      bit offsets (JsInts)
 //   k_jfp_zero     the words the scans will use
 //   k_jfp_emit     one thread per item: own symbols, EOBn, deferred bits at the item's bit offset; the last item of a scan pads
-//   k_jfp_ffcount, k_jfp_scan, k_jfp_layout, k_jfp_scatter: 0xFF stuffing per 64-byte chunk of every scan's stream and the file
-//                  SOI .. SOF2, then per scan [DHT] SOS data, then EOI
+//   k_jfp_ffcount, k_js_scan, k_jfp_layout, k_jfp_scatter: 0xFF stuffing per 64-byte chunk of every scan's stream (js_stuff_count,
+//                  js_stuff_copy) and the file SOI .. SOF2, then per scan [DHT] SOS data, then EOI
 // Bounds: an item's index derives from JfpGeom; a scan's words stay inside its wcap (je_block_bound per block) and every store into a
 // stream checks it; k_jfp_scatter writes a file only if it ends inside the caller's capacity.
 #include "aej_common.h"
@@ -29,13 +31,13 @@
 #include "aej_launch.h"
 #include "jfif_huff_core.h"
 #include "jfif_prog_core.h"
+#include "jfif_stream_core.h"
 
 #include <vector>
 
 namespace aej {
 
 constexpr int kJfpThreads = 256;
-constexpr int kJfpScanThreads = 1024;
 constexpr int kJfpChunk = 64;          // bytes per stuffing chunk
 constexpr int kJfpMaxTables = 10;
 constexpr unsigned short kFlagE = 1, kFlagJoins = 2, kFlagFirst = 256, kFlagAc = 512;      // bits 2..7: pending correction bits
@@ -53,12 +55,10 @@ __host__ __device__ inline long long jfp_coef_block(const JfpGeom &g, const JfpS
 __host__ __device__ inline long long jfp_prev(const JfpGeom &g, long long i, bool *chroma)
 {
     const int NL = g.hs * g.vs, BPM = NL + g.nchroma, k = (int)(i % BPM);
-    const long long m = i / BPM;
     *chroma = k >= NL;
-    if (k >= 1 && k < NL) return i - 1;
-    if (m == 0) return -1;
-    return k == 0 ? (m - 1) * BPM + NL - 1 : i - BPM;
+    return js_prev(NL, BPM, i / BPM, k);
 }
+// the value of item idx in the partition's prefix sums (je_pack), from the flags k_jfp_facts left
 __device__ __forceinline__ unsigned long long jfp_value(const unsigned short *flags, long long idx)
 {
     const unsigned f = flags[idx];
@@ -95,40 +95,11 @@ __global__ __launch_bounds__(kJfpThreads) void k_jfp_facts(JfpGeom g, const shor
     flags[seg * g.T + s.ioff + i] = (unsigned short)f;
 }
 
-// exclusive prefix sums of n values per file (one workgroup per file) -> n + 1 entries, the last one the total.
-// kMode 0: jfp_value of the flags; 1: int32 values
-template <int kMode>
-__global__ __launch_bounds__(kJfpScanThreads) void k_jfp_scan(const unsigned short *__restrict__ flags, const int *__restrict__ vals, long long n,
-                                                              unsigned long long *__restrict__ out)
-{
-    constexpr int kWaves = kJfpScanThreads / 64;
-    __shared__ unsigned long long wsum[2][kWaves];
-    const long long seg = blockIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long carry = 0;
-    unsigned long long *dst = out + seg * (n + 1);
-    int par = 0;
-    for (long long base = 0; base < n; base += kJfpScanThreads, par ^= 1) {
-        const long long i = base + threadIdx.x;
-        const unsigned long long v = i < n ? (kMode == 0 ? jfp_value(flags, seg * n + i) : (unsigned long long)vals[seg * n + i]) : 0;
-        unsigned long long x = v;
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned long long y = __shfl_up(x, d);
-            if (lane >= d) x += y;
-        }
-        if (lane == 63) wsum[par][wave] = x;
-        __syncthreads();                                     // wsum alternates, so one barrier per tile is enough
-        unsigned long long before = 0, all = 0;
-        for (int w = 0; w < kWaves; w++) {
-            const unsigned long long t = wsum[par][w];
-            before += w < wave ? t : 0;
-            all += t;
-        }
-        if (i < n) dst[i] = carry + before + x - v;
-        carry += all;
-    }
-    if (threadIdx.x == 0) dst[n] = carry;
-}
+// k_js_scan's input for the partition: jfp_value of the flags
+struct JfpPacked {
+    const unsigned short *flags;
+    __device__ __forceinline__ unsigned long long operator()(long long i) const { return jfp_value(flags, i); }
+};
 
 __global__ __launch_bounds__(kJfpThreads) void k_jfp_cuts(JfpGeom g, const unsigned short *__restrict__ flags,
                                                           const unsigned long long *__restrict__ pre, int *__restrict__ plen, int *__restrict__ cuts)
@@ -336,9 +307,7 @@ __global__ __launch_bounds__(kJfpThreads) void k_jfp_ffcount(JfpGeom g, const un
     const long long nbytes = min(s.wcap * 4, (jfp_scan_bits(g, pre, seg, s) + 7) >> 3);
     const long long lo = (ch - s.coff) * kJfpChunk, hi = min(nbytes, lo + kJfpChunk);
     const unsigned char *src = reinterpret_cast<const unsigned char *>(stream + seg * g.stream_words + s.woff);
-    int n = 0;
-    for (long long j = lo; j < hi; j++) n += src[j] == 0xFF;
-    cnt[seg * g.n_chunks + ch] = n;
+    cnt[seg * g.n_chunks + ch] = js_stuff_count(src, lo, hi);
 }
 
 // the bytes of file seg before the markers of scan si (si == nscan: before EOI)
@@ -402,12 +371,7 @@ __global__ __launch_bounds__(kJfpThreads) void k_jfp_scatter(JfpGeom g, const Jf
     }
     const unsigned long long *ff = ffpre + seg * (g.n_chunks + 1);
     const unsigned char *src = reinterpret_cast<const unsigned char *>(stream + seg * g.stream_words + s.woff);
-    unsigned char *dst = file + at + hl + lo + (long long)(ff[ch] - ff[s.coff]);
-    for (long long j = lo; j < hi; j++) {
-        const unsigned char v = src[j];
-        *dst++ = v;
-        if (v == 0xFF) *dst++ = 0;
-    }
+    js_stuff_copy(file + at + hl + lo + (long long)(ff[ch] - ff[s.coff]), src, lo, hi);
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------------
@@ -521,16 +485,16 @@ static hipError_t jfp_entropy(hipStream_t st, const JfpGeom &p, const JfpBufs &p
     if (e == hipSuccess) e = hipMemsetAsync(pw.cuts, 0, (size_t)p.segs * p.nscan * 2 * 4, st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_jfp_facts, items, th, 0, st, p, coef, pw.flags);
-    hipLaunchKernelGGL(k_jfp_scan<0>, dim3(segs), dim3(kJfpScanThreads), 0, st, pw.flags, nullptr, p.T, pw.pre);
+    hipLaunchKernelGGL(k_js_scan<JfpPacked>, dim3(segs), dim3(kJsScanThreads), 0, st, JfpPacked{ pw.flags }, p.T, pw.pre);
     hipLaunchKernelGGL(k_jfp_cuts, items, th, 0, st, p, pw.flags, pw.pre, pw.plen, pw.cuts);
     hipLaunchKernelGGL(k_jfp_hist, items, th, 0, st, p, coef, pw.plen, pw.hist);
     hipLaunchKernelGGL(k_jfp_tables, dim3(segs), dim3(64 * p.ntab), 0, st, p, pw.hist, pw.codes, pw.fhdr, pw.fhdr_len);
     hipLaunchKernelGGL(k_jfp_count, items, th, 0, st, p, coef, pw.plen, pw.codes, pw.lens);
-    hipLaunchKernelGGL(k_jfp_scan<1>, dim3(segs), dim3(kJfpScanThreads), 0, st, nullptr, pw.lens, p.T, pw.pre);
+    hipLaunchKernelGGL(k_js_scan<JsInts>, dim3(segs), dim3(kJsScanThreads), 0, st, JsInts{ pw.lens }, p.T, pw.pre);
     hipLaunchKernelGGL(k_jfp_zero, chunks, th, 0, st, p, pw.pre, pw.stream);
     hipLaunchKernelGGL(k_jfp_emit, items, th, 0, st, p, coef, pw.plen, pw.codes, pw.pre, pw.stream);
     hipLaunchKernelGGL(k_jfp_ffcount, chunks, th, 0, st, p, pw.pre, pw.stream, pw.ffcnt);
-    hipLaunchKernelGGL(k_jfp_scan<1>, dim3(segs), dim3(kJfpScanThreads), 0, st, nullptr, pw.ffcnt, p.n_chunks, pw.ffpre);
+    hipLaunchKernelGGL(k_js_scan<JsInts>, dim3(segs), dim3(kJsScanThreads), 0, st, JsInts{ pw.ffcnt }, p.n_chunks, pw.ffpre);
     hipLaunchKernelGGL(k_jfp_layout, dim3(1), th, 0, st, p, par, pw.fhdr_len, pw.pre, pw.ffpre, lengths, offsets, pw.total);
     return out ? launch_jfifprog_scatter(st, p, pw, par, lengths, offsets, out, cap) : hipGetLastError();
 }
@@ -644,15 +608,10 @@ int jfifprog_scan_host(const short *coefs, long long n, int Ss, int Se, int Ah, 
         em.bw.finish();
     }
     const unsigned char *src = reinterpret_cast<const unsigned char *>(words.data());
-    unsigned long long o = 0;
-    for (long long i = 0; i < nbytes; i++) o += src[i] == 0xFF ? 2 : 1;
+    const unsigned long long o = (unsigned long long)(nbytes + js_stuff_count(src, 0, nbytes));
     *out_len = o;
     if (o > cap || (o && !out)) return AEJ_ERR_CAPACITY;
-    o = 0;
-    for (long long i = 0; i < nbytes; i++) {
-        out[o++] = src[i];
-        if (src[i] == 0xFF) out[o++] = 0;
-    }
+    js_stuff_copy(out, src, 0, nbytes);
     return 0;
 }
 

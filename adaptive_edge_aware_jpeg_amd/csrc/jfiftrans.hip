@@ -7,7 +7,7 @@
 // (H, W, hs, vs, components) of their output; a group runs the existing entropy stages once, every
 // file of it one "quality" of a one-image batch, so that JfifParams::hdr -- per quality in the coders -- carries each file's own
 // markers (SOI, JFIF APP0 with the source's density, the source's quantisation tables and frame header).  Stages:
-//   k_jt_bridge     one wave per block: lane z reads natural index k_jt_zz[z] of the source block and writes position z of the coder's
+//   k_jt_bridge     one wave per block: lane z reads natural index k_zigzag8.natural[z] of the source block and writes position z of the coder's
 //                   block (128 contiguous bytes in, 128 out); the range check of libjpeg's encoder (AC |v| <= 1023, DC -1024 .. 1023)
 //                   is one ballot, and a block that fails marks its file by one atomicCAS and is written as zeros.  So are the blocks
 //                   of a file whose decode had failed before this launch; whether the GOOD blocks of a file that fails in this launch
@@ -17,7 +17,7 @@
 //                   transposition: jfif_transform_core.h).  Still one wave per OUTPUT block, lane z writing position z of the coder's block:
 //                   the wave is block b of its file in the OUTPUT group's MCU order, reads block jx_source_block(b) of the SOURCE's MCU
 //                   order (another sampling after a transposition, fewer MCUs after a trim) and there natural index
-//                   jx_source_index(k_jt_zz[z]), negated where the mirror says so -- one 128-byte block in, one out, as the bridge.  A
+//                   jx_source_index(k_zigzag8.natural[z]), negated where the mirror says so -- one 128-byte block in, one out, as the bridge.  A
 //                   dummy output block is written as libjpeg writes it: lane 0 takes the DC of the real block before it in the MCU, the
 //                   AC lanes read nothing and write 0.  Range ballot and status protocol are the bridge's (the limits are symmetric but
 //                   for the DC, which no transform negates).  A file whose transform is "none" goes through it unchanged, dummies too.
@@ -45,8 +45,6 @@ namespace aej {
 
 constexpr int kJtThreads = 256;
 
-__constant__ unsigned char k_jt_zz[64] = { AEJ_ZIGZAG_8X8 };
-
 __device__ __forceinline__ int jt_find_file(const JtFile *f, int n, long long t)      // last file whose src_base <= t (jd_find_file)
 {
     int lo = 0, hi = n - 1;
@@ -65,7 +63,7 @@ __global__ __launch_bounds__(kJtThreads) void k_jt_bridge(const JtFile *__restri
     const JtFile F = files[jt_find_file(files, n, t)];
     const long long b = t - F.src_base;
     if (b >= F.n_blocks) return;                             // never: the files' ranges tile [0, n_blocks)
-    const int v = F.src[b * 64 + k_jt_zz[z]];
+    const int v = F.src[b * 64 + k_zigzag8.natural[z]];
     const bool bad = z == 0 ? (v < -1024 || v > 1023) : (v < -1023 || v > 1023);
     const bool any_bad = __ballot(bad) != 0ull;
     if (any_bad && z == 0) atomicCAS(status + F.status_index, 0, AEJ_JPEGDEC_COEF_RANGE);
@@ -85,7 +83,7 @@ __global__ __launch_bounds__(kJtThreads) void k_jt_transform(const JtFile *__res
     const JxGeom G = geom[fi];
     const long long b = t - F.src_base;
     if (b >= F.n_blocks || b >= G.n_out) return;             // never: the files' ranges tile [0, n_blocks), and n_blocks is n_out
-    int sb = (int)b, si = k_jt_zz[z];
+    int sb = (int)b, si = k_zigzag8.natural[z];
     bool dummy = false, negate = false;
     if (G.xf != kJxNone) {
         sb = jx_source_block(G, (int)b, &dummy);
@@ -145,8 +143,6 @@ __global__ __launch_bounds__(kJtThreads) void k_jt_finish(const JtFile *__restri
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------
-static const unsigned char kJtZzHost[64] = { AEJ_ZIGZAG_8X8 };
-
 template <class D>
 static void jt_source(const D &d, JtSource &s)
 {
@@ -176,7 +172,7 @@ int jfiftrans_prefix_host(const JtSource &s, bool prog, unsigned char *o, int ca
         for (int e = 0; e < c; e++) seen |= s.comp_tq[e] == s.comp_tq[c];
         if (seen) continue;
         put({ 0xFF, 0xDB, 0, 67, nc == 1 ? 0 : s.comp_tq[c] & 15 });
-        for (int i = 0; i < 64; i++) b[n++] = (unsigned char)s.qt[c][kJtZzHost[i]];
+        for (int i = 0; i < 64; i++) b[n++] = (unsigned char)s.qt[c][kZigzag8.natural[i]];
     }
     put({ 0xFF, prog ? 0xC2 : 0xC0, 0, jfif_sof_bytes(nc) - 2, 8, s.height >> 8, s.height & 255, s.width >> 8, s.width & 255, nc });
     if (nc == 1) put({ s.comp_id[0], 0x11, 0 });
@@ -202,7 +198,7 @@ void jfiftrans_coefs_host(const JxGeom &g, const short *src, short *dst)
         const int sb = g.xf != kJxNone ? jx_source_block(g, b, &dummy) : b;
         for (int z = 0; z < 64; z++) {
             bool negate = false;
-            const int si = g.xf != kJxNone ? jx_source_index(g, kJtZzHost[z], &negate) : kJtZzHost[z];
+            const int si = g.xf != kJxNone ? jx_source_index(g, kZigzag8.natural[z], &negate) : kZigzag8.natural[z];
             const int v = dummy && z != 0 ? 0 : src[(long long)sb * 64 + si];
             dst[(long long)b * 64 + z] = (short)(negate ? -v : v);
         }

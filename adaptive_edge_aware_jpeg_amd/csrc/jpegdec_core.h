@@ -6,10 +6,7 @@
 
 #include "../../include/aej.h"
 #include "aej_common.h"
-
-#ifndef AEJ_HD
-#define AEJ_HD __host__ __device__
-#endif
+#include "jfif_stream_core.h"
 
 namespace aej {
 
@@ -60,8 +57,6 @@ AEJ_HD inline int jd_k(unsigned long long s) { return (int)((s >> 6) & 7); }
 AEJ_HD inline int jd_z(unsigned long long s) { return (int)(s & 63); }
 AEJ_HD inline int jd_err(unsigned long long s) { return (int)((s >> 9) & 1); }
 
-AEJ_HD inline unsigned jd_bswap(unsigned v) { return (v >> 24) | ((v >> 8) & 0xFF00u) | ((v << 8) & 0xFF0000u) | (v << 24); }
-
 // big-endian bit window over a 4-byte-aligned byte stream
 struct JdBits {
     const unsigned *w;
@@ -72,8 +67,8 @@ struct JdBits {
     {
         const long long wi = pos >> 5;
         if (wi != cw) {
-            if (wi == cw + 1) { a = b; b = jd_bswap(w[wi + 1]); }
-            else { a = jd_bswap(w[wi]); b = jd_bswap(w[wi + 1]); }
+            if (wi == cw + 1) { a = b; b = js_bswap(w[wi + 1]); }
+            else { a = js_bswap(w[wi]); b = js_bswap(w[wi + 1]); }
             cw = wi;
         }
         const int sh = (int)(pos & 31);
@@ -93,11 +88,7 @@ AEJ_HD inline bool jd_huff(const aej_jpegdec_huff &h, unsigned win, int &len, in
 }
 
 // natural index of zigzag position z (z < 64)
-AEJ_HD inline int jd_natural(int z)
-{
-    const unsigned char zz[64] = { AEJ_ZIGZAG_8X8 };
-    return zz[z];
-}
+AEJ_HD inline int jd_natural(int z) { return kZigzag8.natural[z]; }
 
 AEJ_HD inline int jd_comp(const aej_jpegdec_desc &d, int k) { return d.ncomp == 1 ? 0 : (k < d.hs * d.vs ? 0 : k - d.hs * d.vs + 1); }
 

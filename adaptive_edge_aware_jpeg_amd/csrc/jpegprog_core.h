@@ -197,7 +197,7 @@ AEJ_HD inline int jp_dc_refine_unit(const JpScan &s, const unsigned char *clean,
         if (bit >= sg.nbytes * 8) return kJdRunOutOfBits;
         const long long pos = sg.start * 8 + bit;
         const long long slot = jp_slot(s, u, k);
-        if (((jd_bswap(w[pos >> 5]) >> (31 - (int)(pos & 31))) & 1) && slot >= 0) coef[slot * 64] |= (short)(1 << s.al);
+        if (((js_bswap(w[pos >> 5]) >> (31 - (int)(pos & 31))) & 1) && slot >= 0) coef[slot * 64] |= (short)(1 << s.al);
     }
     return kJdRunStop;
 }

@@ -184,3 +184,65 @@ def test_sweep_standard_equals_pillow_and_metrics(A, tmp_path):
     assert lines[0] == "image_name,quality,psnr,ssim,ms_ssim,compression_ratio"
     assert len(lines) == 1 + 3 * len(qs)
     assert lines[1].startswith("image_0,10,")
+
+
+# ---- the pieces every stream writer shares (csrc/jfif_stream_core.h): noise through every coder ----------------------------------------
+# 152 x 168 at 4:4:4 is 19 x 21 x 3 = 1197 blocks per file: more than one 1024-value tile of the prefix-sum kernel and no multiple of
+# 64; noise at quality 95 puts 0xFF bytes across 64-byte chunk and 32-bit word boundaries, quality 30 gives short streams.
+SHARED_KINDS = ({}, {"optimize": True}, {"progressive": True})
+_shared_cache = {}
+
+
+def _shared_noise():
+    return np.random.default_rng(20261018).integers(0, 256, (2, 152, 168, 3), np.uint8)
+
+
+def _shared_pillow(q, ss, grey):
+    """Pillow's files of the two noise images (grey: of their channel 0) per kind, made once per case"""
+    from PIL import Image
+    key = (q, ss, grey)
+    if key not in _shared_cache:
+        files = []
+        for kw in SHARED_KINDS:
+            row = []
+            for x in _shared_noise():
+                buf = io.BytesIO()
+                if grey:
+                    Image.fromarray(np.ascontiguousarray(x[:, :, 0])).save(buf, "JPEG", quality=q, **kw)
+                else:
+                    Image.fromarray(x).save(buf, "JPEG", quality=q, subsampling=ss, **kw)
+                assert buf.getvalue().count(b"\xff\x00") >= 5, (q, ss, grey, kw)      # the case cannot pass by never stuffing
+                row.append(buf.getvalue())
+            files.append(row)
+        _shared_cache[key] = files
+    return _shared_cache[key]
+
+
+@live
+@pytest.mark.parametrize("ss", ("4:4:4", "4:2:2", "4:2:0"))
+@pytest.mark.parametrize("q", (95, 30))
+def test_shared_stream_pieces_colour_equal_pillow(A, q, ss):
+    x = _shared_noise()
+    want = _shared_pillow(q, ss, False)
+    for kw, files in zip(SHARED_KINDS, want):
+        assert A.standard_jpeg_many(x, q, subsampling=ss, **kw) == files, (q, ss, kw)
+        sizes, dec = A.standard_jpeg_batch(x, [q], subsampling=ss, **kw)
+        assert sizes[:, 0].tolist() == [len(f) for f in files], (q, ss, kw)
+        for i, f in enumerate(files):
+            assert np.array_equal(dec[0, i].cpu().numpy(), _pil_decode(f)), (q, ss, kw, i)
+    assert A.standard_jpeg_transcode_many(want[0], progressive=False, grey=True) == want[1], (q, ss)
+    assert A.standard_jpeg_transcode_many(want[0], progressive=True, grey=True) == want[2], (q, ss)
+
+
+@live
+@pytest.mark.parametrize("q", (95, 30))
+def test_shared_stream_pieces_grey_equal_pillow(A, q):
+    g = [np.ascontiguousarray(x[:, :, 0]) for x in _shared_noise()]
+    want = _shared_pillow(q, None, True)
+    for kw, files in zip(SHARED_KINDS, want):
+        assert A.standard_jpeg_encode_many(g, q, mode="L", **kw) == files, (q, kw)
+        dec = A.standard_jpeg_decode_many(files, progressive=bool(kw.get("progressive")))
+        for i, f in enumerate(files):
+            assert np.array_equal(dec[i].cpu().numpy(), _pil_decode(f)), (q, kw, i)
+    assert A.standard_jpeg_transcode_many(want[0], progressive=False, grey=True) == want[1], q
+    assert A.standard_jpeg_transcode_many(want[0], progressive=True, grey=True) == want[2], q
