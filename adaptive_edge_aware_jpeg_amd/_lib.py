@@ -274,6 +274,15 @@ SIGNATURES = {
     "aej_jfif_transform_headers_host": (_I, [_P, _P, _P, _I, _I, _I, _P, _I]),
     "aej_jfif_transform_workspace_bytes": (_U64, [_P, _P, _I, _P, _P, _I, _I, _P, _I]),
     "aej_jfif_transform_batch": (_I, [_P, _P, _I, _P, _U64, _P, _P, _P, _I, _P, _U64, _P, _P, _I, _P, _I, _P, _U64, _P, _P, _P, _P, _P, _P, _U64]),
+    "aej_jfif_many_workspace_bytes_rst": (_U64, [_P, _P, _I, _I, _I, _I, _I, _I]),
+    "aej_jfif_many_encode_rst": (_I, [_P, _P, _I, _P, _U64, _I, _I, _I, _I, _I, _P, _U64, _P, _P, _P, _P, _P, _U64]),
+    "aej_jfif_transcode_workspace_bytes_rst": (_U64, [_P, _P, _I, _P, _P, _I, _I, _I, _I]),
+    "aej_jfif_transcode_batch_rst": (_I, [_P, _P, _I, _P, _U64, _P, _P, _P, _I, _P, _U64, _P, _P, _I, _I, _I, _P, _U64, _P, _P, _P, _P, _P, _P, _U64]),
+    "aej_jfif_transform_workspace_bytes_rst": (_U64, [_P, _P, _I, _P, _P, _I, _I, _P, _I, _I, _I]),
+    "aej_jfif_transform_batch_rst": (_I, [_P, _P, _I, _P, _U64, _P, _P, _P, _I, _P, _U64, _P, _P, _I, _P, _I, _I, _I, _P, _U64, _P, _P, _P, _P, _P, _P,
+                                          _U64]),
+    "aej_jfif_headers_rst_host": (_I, [_I, _I, _I, _I, _I, _I, _I, _P, _I]),
+    "aej_jfif_restart_map_host": (_I, [_I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I64, _P, _I64, _P]),
     "aej_resample_taps_host": (_I, [_I, ctypes.c_float, ctypes.c_float, _I, _I, _P, _P, _I64]),
     "aej_resample_workspace_bytes": (_U64, [_P, _P, _I]),
     "aej_resample_batch": (_I, [_P, _P, _I, _P, _U64, _P, _U64, _P, _U64]),

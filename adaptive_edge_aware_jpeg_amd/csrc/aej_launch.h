@@ -204,7 +204,7 @@ void launch_lpips(hipStream_t st, const float *wpk, const float *img, int B, con
 // jfif.hip: baseline JPEG as Pillow / libjpeg-turbo writes it, and its decode (aej_jfif_*)
 constexpr int kJfifBlockWords = 52;    // 32-bit words that bound one block's Huffman codes (DC <= 22 bits, 63 AC <= 26 bits each)
 constexpr int kJfifBlockWordsOpt = 53; // the same with a file's own tables, whose codes reach 16 bits: 27 + 63 x 26 = 1665 bits
-constexpr int kJfifHdrMax = 1024;      // SOI .. SOS are 623 bytes with the Annex K tables and never longer with optimised ones
+constexpr int kJfifHdrMax = 1024;      // SOI .. SOS are 623 bytes with the Annex K tables and never longer with optimised ones; a DRI adds 6
 struct JfifGeom {
     int B, H, W, nq;
     int mcux, mcuy, ybx, yby;          // MCUs; real luma blocks per row / column
@@ -214,6 +214,8 @@ struct JfifGeom {
     long long plane_bytes;             // per (quality, image): Y, Cb, Cr sample planes
     int hs, vs, opt, ncomp;            // luma sampling factors (2 x 2, 2 x 1, 1 x 1; chroma is 1 x 1); Huffman tables per file;
                                        // components: 3, or 1 (grey: hs = vs = 1, an MCU is one block, no dummies; entropy chains only)
+    int R, rst_pad_;                   // restart interval of the baseline scan in MCUs (jfif_geom_restart; 0: none, requires opt otherwise)
+    long long niv;                     // its intervals, ceil(n_mcu / R) (0 without restarts)
 };
 struct JfifParams {                    // one quality: quantisers in zigzag order (luma, chroma) and the markers SOI .. SOS
     int qt[2][64];
@@ -226,13 +228,17 @@ struct JfifBufs {
     unsigned char *planes;
     // per-file Huffman tables (opt only): symbol counts [seg][4][257], (code << 8) | length [seg][4][256], markers [seg][kJfifHdrMax]
     unsigned long long *hist; unsigned *codes; unsigned char *fhdr; int *fhdr_len;
+    unsigned long long *ivoff;         // restarts only: [seg][niv + 1] byte starts of the intervals in the unstuffed stream; the last is its bytes
 };
 // ss: Pillow's subsampling code (0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0); opt: optimise the Huffman tables per file; ncomp: 3, or 1 (ss is
 // then not looked at)
 bool jfif_geom(int B, int H, int W, int nq, JfifGeom &g, int ss = 2, int opt = 0, int ncomp = 3);
+// after jfif_geom: the restart interval of Pillow's restart_marker_blocks / restart_marker_rows (jr_interval, jfif_restart_core.h).
+// false: a value outside 0..65535, or an interval with opt = 0 (the Annex K per-block stream bound has no room for the padding)
+bool jfif_geom_restart(JfifGeom &g, int blocks, int rows);
 unsigned long long jfif_carve(void *base, const JfifGeom &g, JfifBufs &w);
 void jfif_quant_tables(int q, int luma[64], int chroma[64]);
-void jfif_params_host(int q, int H, int W, JfifParams &p, int ss = 2, int ncomp = 3);
+void jfif_params_host(int q, int H, int W, JfifParams &p, int ss = 2, int ncomp = 3, int R = 0);      // R > 0: a DRI before the SOS
 constexpr int jfif_sof_bytes(int ncomp) { return 10 + 3 * ncomp; }      // a frame header, marker and length included
 constexpr int jfif_sos_bytes(int ncomp) { return 8 + 2 * ncomp; }       // a scan header of every component
 int jfif_huffman_host(const long long *counts, unsigned char *bits, unsigned char *huffval);
@@ -255,12 +261,14 @@ hipError_t launch_jfif_scatter(hipStream_t st, const JfifGeom &g, const JfifBufs
 
 // jfifprog.hip: the progressive file Pillow writes with progressive=True from the same coefficients (aej_jfif_*_prog)
 constexpr int kJfpMaxScans = 10;       // jpeg_simple_progression of a three-component file (six scans for one component)
-constexpr int kJfpPiece = 576;         // bytes that bound the markers before one scan's data: two DHT of 5 + 16 + 256 and an SOS of 14
+constexpr int kJfpPiece = 582;         // bytes that bound the markers before one scan's data: two DHT of 5 + 16 + 256, a DRI of 6 and an SOS of 14
 struct JfpScan {
     int Ss, Se, Ah, Al;
     int comp, tbl;                     // -1: every block in MCU order, else 0 Y / 1 Cb / 2 Cr in the component's raster order; first table slot
     long long n, ioff;                 // blocks, and the first of them among the file's items
     long long woff, wcap, coff;        // the scan's stream: first word, words, first 64-byte chunk
+    int R, dri;                        // restart interval in MCUs of this scan (0: none); whether a DRI precedes its SOS (R differs from the scan before)
+    long long per, niv, ivoff;         // restarts only: items per interval (R x blocks per MCU), intervals, the first of them among the file's
 };
 struct JfpGeom {
     int segs, hs, vs, nchroma;         // files (quality x image); luma sampling factors; chroma blocks per MCU (0: the testing entry's plain list)
@@ -268,6 +276,7 @@ struct JfpGeom {
     int raw, B;                        // raw: no markers, the scan bytes alone (the testing entry); images per quality
     long long nblk, T, nmax;           // coefficient blocks per file; items per file (the sum of the scans' blocks); the longest scan
     long long stream_words, n_chunks;
+    long long NIV;                     // restart intervals per file, the sum of the scans' (0: no restarts)
     JfpScan sc[kJfpMaxScans];
 };
 struct JfpBufs {
@@ -277,8 +286,10 @@ struct JfpBufs {
     unsigned *stream; int *ffcnt; unsigned long long *ffpre;
     unsigned long long *hist; unsigned *codes; unsigned char *fhdr; int *fhdr_len, *cuts;
     long long *total;
+    unsigned long long *ivpre;         // restarts only: [seg][NIV + 1] prefix sums of the intervals' bytes (each ceil(bits / 8)), scan after scan
 };
-bool jfifprog_geom(const JfifGeom &g, JfpGeom &p);
+// blocks, rows: Pillow's restart_marker_blocks / restart_marker_rows; every scan takes its own interval (jr_interval)
+bool jfifprog_geom(const JfifGeom &g, JfpGeom &p, int blocks = 0, int rows = 0);
 unsigned long long jfifprog_carve(void *base, const JfifGeom &g, const JfpGeom &p, JfifBufs &w, JfpBufs &pw);
 hipError_t launch_jfifprog_encode(hipStream_t st, const JfifGeom &g, const JfpGeom &p, const JfifBufs &w, const JfpBufs &pw,
                                   const JfifParams *par_host, const unsigned char *rgb, unsigned char *out, unsigned long long cap,
@@ -402,6 +413,7 @@ struct JtPlan {
     bool prog = false;
     bool transform = false;            // a file has a transform other than kJxNone: k_jt_transform takes the place of k_jt_bridge
     bool annexk = false;               // baseline files under the Annex K Huffman tables, not their own (the ragged encoder without optimize)
+    int rst_blocks = 0, rst_rows = 0;  // restart_marker_blocks / restart_marker_rows of the call (jfiftrans_close gives every group its interval)
     std::vector<JtFile> files;         // caller's order
     std::vector<JxGeom> geom;          // caller's order (transform only)
     std::vector<JtGroup> groups;
@@ -420,7 +432,7 @@ JtSource jfiftrans_transformed(const JtSource &s, const JxGeom &g);
 // one transform code per file.  -> -1, or the first file that does not fit: *why (may be NULL) gets jx_geom's answer, kJxBadArg for
 // descriptors that disagree.
 int jfiftrans_plan(const std::vector<JtSource> &src, const std::vector<long long> &n_blocks, bool prog, const int *xf, int trim, JtPlan &plan,
-                   int *why);
+                   int *why, int rst_blocks = 0, int rst_rows = 0);
 // the pieces of a plan, shared with the ragged encoder (jfifmany.hip).  Before them: plan.files sized, plan.prog set.
 // the group of one output geometry, made on first use (NULL: a geometry jfif_geom refuses)
 JtGroup *jfiftrans_group(JtPlan &plan, int H, int W, int hs, int vs, int ncomp = 3);
@@ -463,7 +475,8 @@ struct JmPlan {
     int hs = 2, vs = 2;                // the call's luma sampling factors (its colour images'; a grey image is 1 x 1 whatever they are)
 };
 // src_bytes < 0: the source buffer's size is not known yet (a workspace query).  -> -1, or the first image the call refuses and *why
-int jfifmany_plan(const aej_jfif_many_desc *descs, int n, long long src_bytes, int ss, bool opt, bool prog, JmPlan &plan, const char **why);
+int jfifmany_plan(const aej_jfif_many_desc *descs, int n, long long src_bytes, int ss, bool opt, bool prog, JmPlan &plan, const char **why,
+                  int rst_blocks = 0, int rst_rows = 0);
 unsigned long long jfifmany_carve(void *base, JmPlan &plan);
 hipError_t launch_jfifmany(hipStream_t st, JmPlan &plan, const unsigned char *src, unsigned char *out, unsigned long long cap, long long *lengths,
                            long long *offsets);

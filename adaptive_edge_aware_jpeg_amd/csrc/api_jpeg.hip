@@ -1,6 +1,8 @@
 // api_jpeg.hip -- the standard-JPEG entries of the C ABI (include/aej.h): baseline and progressive files written (aej_jfif_*) and
 // decoded (aej_jpegdec_*, aej_jpegprog_*).  Host code only.
 #include "aej_ctx.h"
+#include "jfif_restart_core.h"
+#include "jfif_stream_core.h"
 
 using namespace aej;
 
@@ -482,10 +484,14 @@ struct JtCall {
     JtPlan plan;
     std::vector<JtSource> src;
 };
+static bool rst_ok(int blocks, int rows) { return blocks >= 0 && blocks <= kJrMaxInterval && rows >= 0 && rows <= kJrMaxInterval; }
+
 static int jt_layout(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs, int n_base, const aej_jpegprog_frame *frames,
-                     const aej_jpegprog_scan *pscans, int n_prog, const uint16_t *density, int progressive, const int32_t *xf, int trim, JtCall &c)
+                     const aej_jpegprog_scan *pscans, int n_prog, const uint16_t *density, int progressive, const int32_t *xf, int trim, int rst_blocks,
+                     int rst_rows, JtCall &c)
 {
     if (trim != 0 && trim != 1) return fail(ctx, AEJ_ERR_ARG, "%s: trim %d (0 or 1)", fn, trim);
+    if (!rst_ok(rst_blocks, rst_rows)) return fail(ctx, AEJ_ERR_ARG, "%s: restart_blocks %d, restart_rows %d (0 .. 65535)", fn, rst_blocks, rst_rows);
     if (n_base < 0 || n_prog < 0 || n_base + n_prog < 1 || (long long)n_base + n_prog > 65535 || (progressive != 0 && progressive != 1))
         return fail(ctx, AEJ_ERR_ARG, "%s: 1 .. 65535 files and progressive 0 or 1 required", fn);
     if (n_base && !jpegdec_descs_ok(descs, n_base)) return fail(ctx, AEJ_ERR_ARG, "%s: a descriptor aej_jpegdec_parse_host did not write", fn);
@@ -504,7 +510,7 @@ static int jt_layout(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs
         if (density) { c.src[i].units = density[3 * i] & 255; c.src[i].xdensity = density[3 * i + 1]; c.src[i].ydensity = density[3 * i + 2]; }
     }
     int why = kJxOk;
-    const int bad = jfiftrans_plan(c.src, nblk, progressive != 0, xf, trim, c.plan, &why);
+    const int bad = jfiftrans_plan(c.src, nblk, progressive != 0, xf, trim, c.plan, &why, rst_blocks, rst_rows);
     if (bad < 0) return 0;
     if (why == kJxLayout)
         return fail(ctx, AEJ_ERR_UNSUPPORTED, "%s: file %d: a transposing transform of a 4:2:2 file would be a 4:4:0 file, which is not built", fn, bad);
@@ -595,43 +601,60 @@ extern "C" int64_t aej_jfif_transform_coefs_grey_host(int H, int W, int transfor
 }
 
 static uint64_t jt_workspace_bytes(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs_host, int n_base, const aej_jpegprog_frame *frames_host,
-                                   const aej_jpegprog_scan *pscans_host, int n_prog, int progressive, const int32_t *xf, int trim)
+                                   const aej_jpegprog_scan *pscans_host, int n_prog, int progressive, const int32_t *xf, int trim, int rst_blocks,
+                                   int rst_rows)
 {
     if (!ctx || (n_base > 0 && !descs_host) || (n_prog > 0 && (!frames_host || !pscans_host))) return 0;
     JtCall c;
     const std::string keep = ctx->err;
-    const int rc = jt_layout(ctx, fn, descs_host, n_base, frames_host, pscans_host, n_prog, nullptr, progressive, xf, trim, c);
+    const int rc = jt_layout(ctx, fn, descs_host, n_base, frames_host, pscans_host, n_prog, nullptr, progressive, xf, trim, rst_blocks, rst_rows, c);
     ctx->err = keep;                                         // a size query leaves the context's last error alone
     return rc ? 0 : jt_carve(nullptr, n_base, n_prog, c).bytes;
+}
+
+extern "C" uint64_t aej_jfif_transcode_workspace_bytes_rst(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base,
+                                                           const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *pscans_host, int n_prog,
+                                                           int progressive, int restart_blocks, int restart_rows)
+{
+    return jt_workspace_bytes(ctx, __func__, descs_host, n_base, frames_host, pscans_host, n_prog, progressive, nullptr, 0, restart_blocks, restart_rows);
 }
 
 extern "C" uint64_t aej_jfif_transcode_workspace_bytes(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base,
                                                        const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *pscans_host, int n_prog,
                                                        int progressive)
 {
-    return jt_workspace_bytes(ctx, __func__, descs_host, n_base, frames_host, pscans_host, n_prog, progressive, nullptr, 0);
+    return jt_workspace_bytes(ctx, __func__, descs_host, n_base, frames_host, pscans_host, n_prog, progressive, nullptr, 0, 0, 0);
+}
+
+extern "C" uint64_t aej_jfif_transform_workspace_bytes_rst(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base,
+                                                           const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *pscans_host, int n_prog,
+                                                           int progressive, const int32_t *transforms_host, int trim, int restart_blocks,
+                                                           int restart_rows)
+{
+    if (!transforms_host) return 0;
+    return jt_workspace_bytes(ctx, __func__, descs_host, n_base, frames_host, pscans_host, n_prog, progressive, transforms_host, trim, restart_blocks,
+                              restart_rows);
 }
 
 extern "C" uint64_t aej_jfif_transform_workspace_bytes(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base,
                                                        const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *pscans_host, int n_prog,
                                                        int progressive, const int32_t *transforms_host, int trim)
 {
-    if (!transforms_host) return 0;
-    return jt_workspace_bytes(ctx, __func__, descs_host, n_base, frames_host, pscans_host, n_prog, progressive, transforms_host, trim);
+    return aej_jfif_transform_workspace_bytes_rst(ctx, descs_host, n_base, frames_host, pscans_host, n_prog, progressive, transforms_host, trim, 0, 0);
 }
 
 static int jt_batch(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs_host, int n_base, const uint8_t *scans, uint64_t scans_bytes,
                     const int64_t *scan_offsets_host, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *pscans_host, int n_prog,
                     const uint8_t *data, uint64_t data_bytes, const int64_t *data_offsets_host, const uint16_t *density_host, int progressive,
-                    const int32_t *xf, int trim, uint8_t *out, uint64_t out_capacity, int64_t *offsets, int64_t *lengths, uint64_t *total_host,
-                    int32_t *status, int32_t *n_groups_host, void *workspace, uint64_t workspace_bytes)
+                    const int32_t *xf, int trim, int rst_blocks, int rst_rows, uint8_t *out, uint64_t out_capacity, int64_t *offsets,
+                    int64_t *lengths, uint64_t *total_host, int32_t *status, int32_t *n_groups_host, void *workspace, uint64_t workspace_bytes)
 {
     AEJ_TRY(enter(ctx, fn));
     if ((n_base > 0 && (!descs_host || !scans || !scan_offsets_host)) || (n_prog > 0 && (!frames_host || !pscans_host || !data || !data_offsets_host)) ||
         !offsets || !lengths || !total_host || !status || !workspace)
         return null_buffer(ctx, fn);
     JtCall c;
-    AEJ_TRY(jt_layout(ctx, fn, descs_host, n_base, frames_host, pscans_host, n_prog, density_host, progressive, xf, trim, c));
+    AEJ_TRY(jt_layout(ctx, fn, descs_host, n_base, frames_host, pscans_host, n_prog, density_host, progressive, xf, trim, rst_blocks, rst_rows, c));
     for (int i = 0; i < n_base; i++) AEJ_TRY(jpegdec_scan_offset(ctx, fn, descs_host[i], i, scans_bytes, scan_offsets_host[i], c.files[i]));
     AEJ_TRY(jpegprog_scan_offsets(ctx, fn, c.y, data_bytes, data_offsets_host));
     const JtWorkspace ws = jt_carve(workspace, n_base, n_prog, c);
@@ -664,6 +687,18 @@ static int jt_batch(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs_
     return 0;
 }
 
+extern "C" int aej_jfif_transcode_batch_rst(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base, const uint8_t *scans, uint64_t scans_bytes,
+                                            const int64_t *scan_offsets_host, const aej_jpegprog_frame *frames_host,
+                                            const aej_jpegprog_scan *pscans_host, int n_prog, const uint8_t *data, uint64_t data_bytes,
+                                            const int64_t *data_offsets_host, const uint16_t *density_host, int progressive, int restart_blocks,
+                                            int restart_rows, uint8_t *out, uint64_t out_capacity, int64_t *offsets, int64_t *lengths,
+                                            uint64_t *total_host, int32_t *status, int32_t *n_groups_host, void *workspace, uint64_t workspace_bytes)
+{
+    return jt_batch(ctx, __func__, descs_host, n_base, scans, scans_bytes, scan_offsets_host, frames_host, pscans_host, n_prog, data, data_bytes,
+                    data_offsets_host, density_host, progressive, nullptr, 0, restart_blocks, restart_rows, out, out_capacity, offsets, lengths,
+                    total_host, status, n_groups_host, workspace, workspace_bytes);
+}
+
 extern "C" int aej_jfif_transcode_batch(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base, const uint8_t *scans, uint64_t scans_bytes,
                                         const int64_t *scan_offsets_host, const aej_jpegprog_frame *frames_host,
                                         const aej_jpegprog_scan *pscans_host, int n_prog, const uint8_t *data, uint64_t data_bytes,
@@ -672,8 +707,34 @@ extern "C" int aej_jfif_transcode_batch(aej_ctx *ctx, const aej_jpegdec_desc *de
                                         int32_t *n_groups_host, void *workspace, uint64_t workspace_bytes)
 {
     return jt_batch(ctx, __func__, descs_host, n_base, scans, scans_bytes, scan_offsets_host, frames_host, pscans_host, n_prog, data, data_bytes,
-                    data_offsets_host, density_host, progressive, nullptr, 0, out, out_capacity, offsets, lengths, total_host, status, n_groups_host,
-                    workspace, workspace_bytes);
+                    data_offsets_host, density_host, progressive, nullptr, 0, 0, 0, out, out_capacity, offsets, lengths, total_host, status,
+                    n_groups_host, workspace, workspace_bytes);
+}
+
+static int jx_batch(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs_host, int n_base, const uint8_t *scans, uint64_t scans_bytes,
+                    const int64_t *scan_offsets_host, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *pscans_host, int n_prog,
+                    const uint8_t *data, uint64_t data_bytes, const int64_t *data_offsets_host, const uint16_t *density_host, int progressive,
+                    const int32_t *transforms_host, int trim, int rst_blocks, int rst_rows, uint8_t *out, uint64_t out_capacity, int64_t *offsets,
+                    int64_t *lengths, uint64_t *total_host, int32_t *status, int32_t *n_groups_host, void *workspace, uint64_t workspace_bytes)
+{
+    AEJ_TRY(enter(ctx, fn));
+    if (!transforms_host) return null_buffer(ctx, fn);
+    return jt_batch(ctx, fn, descs_host, n_base, scans, scans_bytes, scan_offsets_host, frames_host, pscans_host, n_prog, data, data_bytes,
+                    data_offsets_host, density_host, progressive, transforms_host, trim, rst_blocks, rst_rows, out, out_capacity, offsets, lengths,
+                    total_host, status, n_groups_host, workspace, workspace_bytes);
+}
+
+extern "C" int aej_jfif_transform_batch_rst(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base, const uint8_t *scans, uint64_t scans_bytes,
+                                            const int64_t *scan_offsets_host, const aej_jpegprog_frame *frames_host,
+                                            const aej_jpegprog_scan *pscans_host, int n_prog, const uint8_t *data, uint64_t data_bytes,
+                                            const int64_t *data_offsets_host, const uint16_t *density_host, int progressive,
+                                            const int32_t *transforms_host, int trim, int restart_blocks, int restart_rows, uint8_t *out,
+                                            uint64_t out_capacity, int64_t *offsets, int64_t *lengths, uint64_t *total_host, int32_t *status,
+                                            int32_t *n_groups_host, void *workspace, uint64_t workspace_bytes)
+{
+    return jx_batch(ctx, __func__, descs_host, n_base, scans, scans_bytes, scan_offsets_host, frames_host, pscans_host, n_prog, data, data_bytes,
+                    data_offsets_host, density_host, progressive, transforms_host, trim, restart_blocks, restart_rows, out, out_capacity, offsets,
+                    lengths, total_host, status, n_groups_host, workspace, workspace_bytes);
 }
 
 extern "C" int aej_jfif_transform_batch(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base, const uint8_t *scans, uint64_t scans_bytes,
@@ -684,36 +745,42 @@ extern "C" int aej_jfif_transform_batch(aej_ctx *ctx, const aej_jpegdec_desc *de
                                         int64_t *lengths, uint64_t *total_host, int32_t *status, int32_t *n_groups_host, void *workspace,
                                         uint64_t workspace_bytes)
 {
-    AEJ_TRY(enter(ctx, __func__));
-    if (!transforms_host) return null_buffer(ctx, __func__);
-    return jt_batch(ctx, __func__, descs_host, n_base, scans, scans_bytes, scan_offsets_host, frames_host, pscans_host, n_prog, data, data_bytes,
-                    data_offsets_host, density_host, progressive, transforms_host, trim, out, out_capacity, offsets, lengths, total_host, status,
-                    n_groups_host, workspace, workspace_bytes);
+    return jx_batch(ctx, __func__, descs_host, n_base, scans, scans_bytes, scan_offsets_host, frames_host, pscans_host, n_prog, data, data_bytes,
+                    data_offsets_host, density_host, progressive, transforms_host, trim, 0, 0, out, out_capacity, offsets, lengths, total_host,
+                    status, n_groups_host, workspace, workspace_bytes);
 }
 
 // ---- images of mixed sizes and qualities in one call (jfifmany.hip): the ragged front end, then the transcoder's chains --------------------
 static bool jm_flags_ok(int optimize, int progressive) { return (optimize == 0 || optimize == 1) && (progressive == 0 || progressive == 1); }
 
-extern "C" uint64_t aej_jfif_many_workspace_bytes(aej_ctx *, const aej_jfif_many_desc *descs_host, int n, int subsampling, int optimize,
-                                                  int progressive)
+extern "C" uint64_t aej_jfif_many_workspace_bytes_rst(aej_ctx *, const aej_jfif_many_desc *descs_host, int n, int subsampling, int optimize,
+                                                      int progressive, int restart_blocks, int restart_rows)
 {
     JmPlan plan;
-    if (!jm_flags_ok(optimize, progressive) || jfifmany_plan(descs_host, n, -1, subsampling, optimize != 0, progressive != 0, plan, nullptr) >= 0) return 0;
+    if (!jm_flags_ok(optimize, progressive) || !rst_ok(restart_blocks, restart_rows) ||
+        jfifmany_plan(descs_host, n, -1, subsampling, optimize != 0, progressive != 0, plan, nullptr, restart_blocks, restart_rows) >= 0)
+        return 0;
     return jfifmany_carve(nullptr, plan);
 }
 
-extern "C" int aej_jfif_many_encode(aej_ctx *ctx, const aej_jfif_many_desc *descs_host, int n, const uint8_t *src, uint64_t src_bytes, int subsampling,
-                                    int optimize, int progressive, uint8_t *out, uint64_t out_capacity, int64_t *offsets, int64_t *lengths,
-                                    uint64_t *total_host, int32_t *n_groups_host, void *workspace, uint64_t workspace_bytes)
+extern "C" uint64_t aej_jfif_many_workspace_bytes(aej_ctx *ctx, const aej_jfif_many_desc *descs_host, int n, int subsampling, int optimize,
+                                                  int progressive)
 {
-    const char *fn = __func__;
+    return aej_jfif_many_workspace_bytes_rst(ctx, descs_host, n, subsampling, optimize, progressive, 0, 0);
+}
+
+static int jm_encode(aej_ctx *ctx, const char *fn, const aej_jfif_many_desc *descs_host, int n, const uint8_t *src, uint64_t src_bytes, int subsampling,
+                     int optimize, int progressive, int rst_blocks, int rst_rows, uint8_t *out, uint64_t out_capacity, int64_t *offsets,
+                     int64_t *lengths, uint64_t *total_host, int32_t *n_groups_host, void *workspace, uint64_t workspace_bytes)
+{
     AEJ_TRY(enter(ctx, fn));
     if (!jm_flags_ok(optimize, progressive)) return fail(ctx, AEJ_ERR_ARG, "%s: optimize %d, progressive %d (0 or 1)", fn, optimize, progressive);
+    if (!rst_ok(rst_blocks, rst_rows)) return fail(ctx, AEJ_ERR_ARG, "%s: restart_blocks %d, restart_rows %d (0 .. 65535)", fn, rst_blocks, rst_rows);
     if (!descs_host || !src || !offsets || !lengths || !total_host || !workspace) return null_buffer(ctx, fn);
     JmPlan plan;
     const char *why = "";
     const long long limit = (long long)std::min<uint64_t>(src_bytes, (uint64_t)INT64_MAX);
-    const int bad = jfifmany_plan(descs_host, n, limit, subsampling, optimize != 0, progressive != 0, plan, &why);
+    const int bad = jfifmany_plan(descs_host, n, limit, subsampling, optimize != 0, progressive != 0, plan, &why, rst_blocks, rst_rows);
     if (bad >= 0) return fail(ctx, AEJ_ERR_ARG, "%s: image %d: %s", fn, bad, why);
     AEJ_TRY(check_workspace(ctx, jfifmany_carve(workspace, plan), workspace_bytes));
     if (n_groups_host) *n_groups_host = (int32_t)plan.t.groups.size();
@@ -726,6 +793,76 @@ extern "C" int aej_jfif_many_encode(aej_ctx *ctx, const aej_jfif_many_desc *desc
     if (out && (uint64_t)total > out_capacity)
         return fail(ctx, AEJ_ERR_CAPACITY, "%s: the files need %lld bytes, the output holds %llu", fn, total, (unsigned long long)out_capacity);
     return 0;
+}
+
+extern "C" int aej_jfif_many_encode_rst(aej_ctx *ctx, const aej_jfif_many_desc *descs_host, int n, const uint8_t *src, uint64_t src_bytes,
+                                        int subsampling, int optimize, int progressive, int restart_blocks, int restart_rows, uint8_t *out,
+                                        uint64_t out_capacity, int64_t *offsets, int64_t *lengths, uint64_t *total_host, int32_t *n_groups_host,
+                                        void *workspace, uint64_t workspace_bytes)
+{
+    return jm_encode(ctx, __func__, descs_host, n, src, src_bytes, subsampling, optimize, progressive, restart_blocks, restart_rows, out, out_capacity,
+                     offsets, lengths, total_host, n_groups_host, workspace, workspace_bytes);
+}
+
+extern "C" int aej_jfif_many_encode(aej_ctx *ctx, const aej_jfif_many_desc *descs_host, int n, const uint8_t *src, uint64_t src_bytes, int subsampling,
+                                    int optimize, int progressive, uint8_t *out, uint64_t out_capacity, int64_t *offsets, int64_t *lengths,
+                                    uint64_t *total_host, int32_t *n_groups_host, void *workspace, uint64_t workspace_bytes)
+{
+    return jm_encode(ctx, __func__, descs_host, n, src, src_bytes, subsampling, optimize, progressive, 0, 0, out, out_capacity, offsets, lengths,
+                     total_host, n_groups_host, workspace, workspace_bytes);
+}
+
+// ---- restart markers: the Annex K markers with the DRI, and the index rules on the host (jfif_restart_core.h) -------------------------------
+extern "C" int aej_jfif_headers_rst_host(int quality, int H, int W, int subsampling, int components, int restart_blocks, int restart_rows,
+                                         uint8_t *out_host, int capacity)
+{
+    JfifGeom g;
+    const int nc = components == 1 ? 1 : 3;
+    if ((components != 0 && components != 1 && components != 3) || quality < 1 || quality > 100 || !out_host) return AEJ_ERR_ARG;
+    if (!jfif_geom(1, H, W, 1, g, subsampling, 1, nc) || !jfif_geom_restart(g, restart_blocks, restart_rows)) return AEJ_ERR_ARG;
+    JfifParams p;
+    jfif_params_host(quality, H, W, p, subsampling, nc, g.R);
+    if (capacity < p.hdr_len) return AEJ_ERR_CAPACITY;
+    memcpy(out_host, p.hdr, p.hdr_len);
+    return p.hdr_len;
+}
+
+extern "C" int aej_jfif_restart_map_host(int H, int W, int subsampling, int components, int restart_blocks, int restart_rows, int progressive,
+                                         int32_t *scan_r_host, int32_t *scan_dri_host, int32_t *interval_host, uint8_t *reset_host,
+                                         int64_t block_capacity, uint8_t *marker_host, int64_t marker_capacity, int64_t *counts2_host)
+{
+    JfifGeom g;
+    JfpGeom p;
+    const int nc = components == 1 ? 1 : 3;
+    if ((components != 0 && components != 1 && components != 3) || (progressive != 0 && progressive != 1) || !scan_r_host || !scan_dri_host)
+        return AEJ_ERR_ARG;
+    if (!jfif_geom(1, H, W, 1, g, subsampling, 1, nc) || !jfif_geom_restart(g, restart_blocks, restart_rows)) return AEJ_ERR_ARG;
+    int nscan = 1;
+    scan_r_host[0] = g.R;
+    scan_dri_host[0] = g.R != 0;
+    if (progressive) {
+        if (!jfifprog_geom(g, p, restart_blocks, restart_rows)) return AEJ_ERR_ARG;
+        nscan = p.nscan;
+        for (int i = 0; i < nscan; i++) { scan_r_host[i] = p.sc[i].R; scan_dri_host[i] = p.sc[i].dri; }
+    }
+    // the first scan (the baseline file's only one): every block's interval and whether its DC predictor is reset; every interval's marker
+    const int R = scan_r_host[0], NL = g.hs * g.vs, BPM = NL + nc - 1;
+    const long long niv = R ? jr_count(g.n_mcu, R) : 1;
+    if (counts2_host) { counts2_host[0] = g.nblk; counts2_host[1] = niv; }
+    if (interval_host || reset_host) {
+        if (block_capacity < g.nblk) return AEJ_ERR_CAPACITY;
+        for (long long b = 0; b < g.nblk; b++) {
+            const long long m = b / BPM, pb = js_prev(NL, BPM, m, (int)(b % BPM));
+            if (interval_host) interval_host[b] = R ? (int32_t)jr_interval_of(m, R) : 0;
+            if (reset_host) reset_host[b] = pb < 0 || jr_resets(m, pb, BPM, R);
+        }
+    }
+    if (marker_host) {
+        if (marker_capacity < niv) return AEJ_ERR_CAPACITY;
+        marker_host[0] = 0;                                  // no marker before the first interval
+        for (long long k = 1; k < niv; k++) marker_host[k] = (uint8_t)jr_marker(k);
+    }
+    return nscan;
 }
 
 static int64_t jm_coefs_host(int width, int height, int quality, int subsampling, int nc, const uint8_t *src_host, int16_t *dst_host, int64_t dst_blocks)

@@ -1,5 +1,5 @@
 // jfif.hip -- baseline JPEG as Pillow writes it with libjpeg-turbo (quality q, subsampling 4:2:0 / 4:2:2 / 4:4:4, the Annex K Huffman
-// tables or with optimize=True the file's own, islow DCT, no restarts) and the pixels Pillow's decoder returns for it (aej_jfif_*,
+// tables or with optimize=True the file's own, islow DCT; restart markers in the entropy chains, below) and the pixels Pillow's decoder returns for it (aej_jfif_*,
 // include/aej.h).  The arithmetic restates libjpeg's published integer algorithm; tests/jfif_reference.py and
 // tests/jfif_options_reference.py are the same algorithm in numpy and tests/test_gpu_jfif*.py pin both to Pillow's files byte for byte.
 //
@@ -19,10 +19,16 @@
 //   k_jfif_count    one thread per block: its bits under the file's own tables
 //   k_js_scan       one workgroup per (quality, image): exclusive prefix sums of per-block bit counts (and later of per-chunk 0xFF
 //                   counts), n + 1 entries whose last is the total -- jfif_stream_core.h, shared with jfifprog.hip
+//   k_js_scan       restarts only (JfifGeom::R, jfif_restart_core.h): the byte starts of the restart intervals -- the same kernel over the
+//                   intervals' byte lengths, ceil(bits / 8) each, read off the bit prefix sums (JfIntervalBytes)
 //   k_jfif_emit     one thread per block: its code string at its bit offset, boundary words by atomicOr; the last block pads with 1-bits
+//                   (with restarts: the offset is 8 x its interval's byte start + its bits inside the interval, the last block of every
+//                   interval pads, and a block whose predecessor lies in an earlier interval predicts its DC from 0 -- as k_jfif_hist
+//                   and k_jfif_count do)
 //   k_jfif_ffcount  one thread per 64-byte chunk of a stream: its 0xFF bytes
 //   k_jfif_layout   one thread: file lengths (markers + stuffed data + EOI) and their offsets in the packed output
-//   k_jfif_scatter  one thread per chunk: the chunk with a 0x00 after every 0xFF at its final place; chunk 0 also writes markers and EOI
+//   k_jfif_scatter  one thread per chunk: the chunk with a 0x00 after every 0xFF at its final place; chunk 0 also writes markers and EOI;
+//                   with restarts the chunk moves by 2 bytes per RSTn before it and writes those that fall inside it (jr_stuff_copy)
 //   k_jfif_idct     one thread per (quality, image, real block): dequantise (its own load: zigzag order, int quantisers), then the
 //                   decoder's islow IDCT pass and masked range limit (jd_idct8, jd_range_limit) -> uint8 sample planes
 //   k_jfif_rgb      one thread per output pixel: h2v2 / h2v1 fancy up-sampling (plain replication when the chroma is <= 2 wide, as
@@ -37,6 +43,7 @@
 #include "aej_launch.h"
 #include "jfif_arith.h"
 #include "jfif_huff_core.h"
+#include "jfif_restart_core.h"
 #include "jfif_stream_core.h"
 #include "jpegdec_core.h"
 
@@ -237,7 +244,7 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_hist(JfifGeom g, const shor
         unsigned(*h)[kJhSymbols] = cnt[threadIdx.x / 64] + (k >= NL ? 2 : 0);      // [0] DC, [1] AC of the block's component class
         const short *c = coef + (seg * g.nblk + blk) * 64;
         const long long pb = js_prev(NL, BPM, m, k);
-        atomicAdd(&h[0][js_nbits(c[0] - (pb < 0 ? 0 : coef[(seg * g.nblk + pb) * 64]))], 1u);
+        atomicAdd(&h[0][js_nbits(c[0] - (pb < 0 || jr_resets(m, pb, BPM, g.R) ? 0 : coef[(seg * g.nblk + pb) * 64]))], 1u);
         int run = 0;
         for (int i = 1; i < 64; i++) {
             const int v = c[i];
@@ -268,7 +275,7 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_tables(JfifGeom g, const Jf
     __shared__ int nsym[4];
     const long long seg = blockIdx.x;
     const int t = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int ntab = g.ncomp == 1 ? 2 : 4, sos = jfif_sos_bytes(g.ncomp == 1 ? 1 : 3);
+    const int ntab = g.ncomp == 1 ? 2 : 4, sos = jfif_sos_bytes(g.ncomp == 1 ? 1 : 3), dri = g.R ? kJrDriBytes : 0;      // the DRI: between the DHTs and the SOS
     const bool mine = t < ntab;                              // uniform over the wave
     unsigned *tc = codes + (seg * 4 + t) * 256;
     for (int i = lane; mine && i < 256; i += 64) {
@@ -287,7 +294,7 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_tables(JfifGeom g, const Jf
         if (u < t) off += 5 + 16 + nsym[u];
         end += 5 + 16 + nsym[u];
     }
-    if (end + sos <= kJfifHdrMax) {                          // always: at most 12 DC and 162 AC symbols, the Annex K sizes
+    if (end + dri + sos <= kJfifHdrMax) {                    // always: at most 12 DC and 162 AC symbols, the Annex K sizes
         if (mine) {
             const int n = nsym[t];
             if (lane == 0) {
@@ -296,9 +303,10 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_tables(JfifGeom g, const Jf
             }
             for (int i = lane; i < 16 + n; i += 64) o[off + 5 + i] = i < 16 ? bits[t][i] : vals[t][i - 16];
         }
-        if (threadIdx.x < sos) o[end + threadIdx.x] = p.hdr[p.hdr_len - sos + threadIdx.x];      // SOS
+        if (dri && threadIdx.x == 0) jr_dri(o + end, g.R);
+        if (threadIdx.x < sos) o[end + dri + threadIdx.x] = p.hdr[p.hdr_len - sos + threadIdx.x];      // SOS
     }
-    if (threadIdx.x == 0) fhdr_len[seg] = end + sos <= kJfifHdrMax ? end + sos : 0;
+    if (threadIdx.x == 0) fhdr_len[seg] = end + dri + sos <= kJfifHdrMax ? end + dri + sos : 0;
 }
 
 // in the place of (a1) and (a2) for files that carry the Annex K tables but run the table-driven stages (launch_jfif_entropy_annexk):
@@ -335,7 +343,7 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_count(JfifGeom g, const sho
     const JfCodes hc = jf_file_codes(codes, seg, k >= NL);
     const short *c = coef + idx * 64;
     const long long pb = js_prev(NL, BPM, m, k);
-    const int dcat = js_nbits(c[0] - (pb < 0 ? 0 : coef[(seg * g.nblk + pb) * 64]));
+    const int dcat = js_nbits(c[0] - (pb < 0 || jr_resets(m, pb, BPM, g.R) ? 0 : coef[(seg * g.nblk + pb) * 64]));
     int bits = (int)(hc.dc[dcat] & 255) + dcat, run = 0;
     for (int i = 1; i < 64; i++) {
         const int v = c[i];
@@ -355,17 +363,36 @@ __device__ __forceinline__ long long jf_bits(const JfifGeom &g, const unsigned l
     return (long long)boff[seg * (g.nblk + 1) + g.nblk];
 }
 
-__global__ __launch_bounds__(kJfThreads) void k_jfif_zero(JfifGeom g, const unsigned long long *__restrict__ boff, unsigned *__restrict__ stream)
+// the bytes of segment seg's unstuffed stream: its bits rounded up, or with restarts the sum of its byte-aligned intervals
+__device__ __forceinline__ long long jf_bytes(const JfifGeom &g, const unsigned long long *boff, const unsigned long long *ivoff, long long seg)
+{
+    return g.R ? (long long)ivoff[seg * (g.niv + 1) + g.niv] : (jf_bits(g, boff, seg) + 7) >> 3;
+}
+// restarts: k_js_scan's input for the intervals' starts -- interval i of the launch, its blocks' bits (from boff) rounded up to bytes
+struct JfIntervalBytes {
+    const unsigned long long *boff;
+    long long nblk, niv, per;              // blocks per segment, intervals per segment, blocks per interval (R x blocks per MCU)
+    __device__ __forceinline__ unsigned long long operator()(long long i) const
+    {
+        const unsigned long long *b = boff + (i / niv) * (nblk + 1);
+        const long long lo = (i % niv) * per, hi = min(lo + per, nblk);
+        return (b[hi] - b[lo] + 7) >> 3;
+    }
+};
+
+__global__ __launch_bounds__(kJfThreads) void k_jfif_zero(JfifGeom g, const unsigned long long *__restrict__ boff,
+                                                          const unsigned long long *__restrict__ ivoff, unsigned *__restrict__ stream)
 {
     const long long seg = blockIdx.y, i = (long long)blockIdx.x * kJfThreads + threadIdx.x;
-    if (i < min(g.stream_words, (jf_bits(g, boff, seg) + 31) / 32)) stream[seg * g.stream_words + i] = 0;
+    if (i < min(g.stream_words, (jf_bytes(g, boff, ivoff, seg) + 3) >> 2)) stream[seg * g.stream_words + i] = 0;
 }
 
 // (c) every block's code string at its bit offset
 // kOpt: the codes are the file's own (k_jfif_tables) instead of the Annex K constants
 template <int HS, int VS, bool kOpt, int NC>
 __global__ __launch_bounds__(kJfThreads) void k_jfif_emit(JfifGeom g, const short *__restrict__ coef, const unsigned long long *__restrict__ boff,
-                                                          const unsigned *__restrict__ codes, unsigned *__restrict__ stream)
+                                                          const unsigned long long *__restrict__ ivoff, const unsigned *__restrict__ codes,
+                                                          unsigned *__restrict__ stream)
 {
     constexpr int NL = HS * VS, BPM = NL + NC - 1;
     const long long idx = (long long)blockIdx.x * kJfThreads + threadIdx.x;
@@ -375,8 +402,20 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_emit(JfifGeom g, const shor
     const JfCodes hc = kOpt ? jf_file_codes(codes, seg, k >= NL) : jf_codes(k >= NL);
     const short *c = coef + idx * 64;
     const long long pb = js_prev(NL, BPM, m, k);
-    JeBits bw(stream + seg * g.stream_words, (long long)boff[idx + seg], g.stream_words);      // n + 1 entries per segment
-    const int diff = c[0] - (pb < 0 ? 0 : coef[(seg * g.nblk + pb) * 64]);
+    long long pos = (long long)boff[idx + seg], end_bits = 0;                                   // n + 1 entries per segment
+    bool last = blk == g.nblk - 1, reset = pb < 0;
+    if (g.R) {                                               // uniform: the block's place inside its byte-aligned interval
+        const unsigned long long *b = boff + seg * (g.nblk + 1);
+        const long long per = (long long)g.R * BPM, iv = blk / per, lo = iv * per, hi = min(lo + per, g.nblk);
+        pos = 8 * (long long)ivoff[seg * (g.niv + 1) + iv] + (long long)(b[blk] - b[lo]);
+        end_bits = (long long)(b[hi] - b[lo]);
+        last = blk == hi - 1;
+        reset = reset || jr_resets(m, pb, BPM, g.R);
+    } else if (last) {
+        end_bits = jf_bits(g, boff, seg);
+    }
+    JeBits bw(stream + seg * g.stream_words, pos, g.stream_words);
+    const int diff = c[0] - (reset ? 0 : coef[(seg * g.nblk + pb) * 64]);
     const int dcat = js_nbits(diff);
     bw.put(hc.dc[dcat] >> 8, (int)(hc.dc[dcat] & 255));
     if (dcat) bw.put((unsigned)(diff < 0 ? diff - 1 : diff) & ((1u << dcat) - 1), dcat);
@@ -392,20 +431,21 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_emit(JfifGeom g, const shor
         run = 0;
     }
     if (run) bw.put(hc.ac[0] >> 8, (int)(hc.ac[0] & 255));
-    if (blk == g.nblk - 1) {                                 // pad the last byte with 1-bits
-        const int pad = (int)((8 - (jf_bits(g, boff, seg) & 7)) & 7);
+    if (last) {                                              // pad the last byte (of every restart interval) with 1-bits
+        const int pad = (int)((8 - (end_bits & 7)) & 7);
         if (pad) bw.put((1u << pad) - 1, pad);
     }
     bw.finish();
 }
 
 // 0xFF bytes per 64-byte chunk of each stream's data
-__global__ __launch_bounds__(kJfThreads) void k_jfif_ffcount(JfifGeom g, const unsigned long long *__restrict__ boff, const unsigned *__restrict__ stream,
+__global__ __launch_bounds__(kJfThreads) void k_jfif_ffcount(JfifGeom g, const unsigned long long *__restrict__ boff,
+                                                             const unsigned long long *__restrict__ ivoff, const unsigned *__restrict__ stream,
                                                              int *__restrict__ cnt)
 {
     const long long idx = (long long)blockIdx.x * kJfThreads + threadIdx.x;
     if (idx >= (long long)g.nq * g.B * g.n_chunks) return;
-    const long long seg = idx / g.n_chunks, ch = idx % g.n_chunks, nbytes = min(g.stream_words * 4, (jf_bits(g, boff, seg) + 7) >> 3);
+    const long long seg = idx / g.n_chunks, ch = idx % g.n_chunks, nbytes = min(g.stream_words * 4, jf_bytes(g, boff, ivoff, seg));
     const long long lo = ch * kJfChunk, hi = min(nbytes, lo + kJfChunk);
     const unsigned char *src = reinterpret_cast<const unsigned char *>(stream + seg * g.stream_words);
     cnt[idx] = js_stuff_count(src, lo, hi);
@@ -414,14 +454,15 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_ffcount(JfifGeom g, const u
 // file lengths (markers + stuffed data + EOI) and their offsets in the packed output, segments in (quality, image) order
 // (with per-file tables the markers of file seg are fhdr[seg], fhdr_len[seg] bytes; otherwise those of its quality)
 __global__ void k_jfif_layout(JfifGeom g, const JfifParams *__restrict__ par, const int *__restrict__ fhdr_len,
-                              const unsigned long long *__restrict__ boff, const unsigned long long *__restrict__ ffpre,
-                              long long *__restrict__ lengths, long long *__restrict__ offsets, long long *__restrict__ total)
+                              const unsigned long long *__restrict__ boff, const unsigned long long *__restrict__ ivoff,
+                              const unsigned long long *__restrict__ ffpre, long long *__restrict__ lengths, long long *__restrict__ offsets,
+                              long long *__restrict__ total)
 {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
     long long off = 0;
     for (long long seg = 0; seg < (long long)g.nq * g.B; seg++) {
-        const long long len = (g.opt ? fhdr_len[seg] : par[seg / g.B].hdr_len) + ((jf_bits(g, boff, seg) + 7) >> 3) +
-                              (long long)ffpre[seg * (g.n_chunks + 1) + g.n_chunks] + 2;
+        const long long len = (g.opt ? fhdr_len[seg] : par[seg / g.B].hdr_len) + jf_bytes(g, boff, ivoff, seg) +
+                              (long long)ffpre[seg * (g.n_chunks + 1) + g.n_chunks] + (g.R ? 2 * (g.niv - 1) : 0) + 2;      // an RSTn before every interval but the first
         lengths[seg] = len;
         offsets[seg] = off;
         off += len;
@@ -431,7 +472,7 @@ __global__ void k_jfif_layout(JfifGeom g, const JfifParams *__restrict__ par, co
 
 __global__ __launch_bounds__(kJfThreads) void k_jfif_scatter(JfifGeom g, const JfifParams *__restrict__ par,
                                                              const unsigned char *__restrict__ fhdr, const int *__restrict__ fhdr_len,
-                                                             const unsigned long long *__restrict__ boff,
+                                                             const unsigned long long *__restrict__ boff, const unsigned long long *__restrict__ ivoff,
                                                              const unsigned *__restrict__ stream, const unsigned long long *__restrict__ ffpre,
                                                              const long long *__restrict__ lengths, const long long *__restrict__ offsets,
                                                              unsigned char *__restrict__ out, unsigned long long cap)
@@ -449,9 +490,17 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_scatter(JfifGeom g, const J
         file[len - 2] = 0xFF;
         file[len - 1] = 0xD9;
     }
-    const long long nbytes = (jf_bits(g, boff, seg) + 7) >> 3, lo = ch * kJfChunk, hi = min(nbytes, lo + kJfChunk);
+    const long long nbytes = min(g.stream_words * 4, jf_bytes(g, boff, ivoff, seg)), lo = ch * kJfChunk, hi = min(nbytes, lo + kJfChunk);
     const unsigned char *src = reinterpret_cast<const unsigned char *>(stream + seg * g.stream_words);
-    if (lo < hi) js_stuff_copy(file + hdr_len + lo + (long long)ffpre[idx + seg], src, lo, hi);      // n + 1 entries per segment
+    if (lo >= hi) return;
+    unsigned char *dst = file + hdr_len + lo + (long long)ffpre[idx + seg];                         // n + 1 entries per segment
+    if (g.R) {                                               // uniform: the markers before this chunk shift it, those inside it are written here
+        const unsigned long long *starts = ivoff + seg * (g.niv + 1);
+        const long long k = jr_first_from(starts, g.niv, lo);
+        jr_stuff_copy(dst + 2 * (k - 1), src, lo, hi, starts, g.niv, k);
+    } else {
+        js_stuff_copy(dst, src, lo, hi);
+    }
 }
 
 // ---- reconstruction ----------------------------------------------------------------------------------------------------------------
@@ -545,9 +594,21 @@ bool jfif_geom(int B, int H, int W, int nq, JfifGeom &g, int ss, int opt, int nc
     g.n_mcu = (long long)g.mcux * g.mcuy;
     g.nblk = (g.hs * g.vs + ncomp - 1) * g.n_mcu;
     g.stream_words = (g.nblk * (g.opt ? kJfifBlockWordsOpt : kJfifBlockWords) + 2 + 15) / 16 * 16;
+    // With restarts (jfif_geom_restart) every interval is padded to a byte: up to 7 bits for each of at most nblk intervals.  A block
+    // under a file's own tables has 53 x 32 - 1665 = 31 bits to spare, so nblk x 53 words still hold sum(bits) + 7 x intervals; under
+    // the Annex K bound the spare is 52 x 32 - 1660 = 4 bits, which is why an interval requires opt.
+    g.R = 0; g.rst_pad_ = 0; g.niv = 0;
     g.n_chunks = g.stream_words * 4 / kJfChunk;
     g.plane_bytes = ((long long)g.yh * g.yw + 2LL * g.ch * g.cw + 255) / 256 * 256;
     return true;
+}
+
+bool jfif_geom_restart(JfifGeom &g, int blocks, int rows)
+{
+    if (blocks < 0 || blocks > kJrMaxInterval || rows < 0 || rows > kJrMaxInterval) return false;
+    g.R = jr_interval(blocks, rows, g.mcux);                 // one component: mcux is its blocks per row
+    g.niv = g.R ? jr_count(g.n_mcu, g.R) : 0;
+    return g.R == 0 || g.opt != 0;
 }
 
 unsigned long long jfif_carve(void *base, const JfifGeom &g, JfifBufs &w)
@@ -564,7 +625,7 @@ unsigned long long jfif_carve(void *base, const JfifGeom &g, JfifBufs &w)
     w.ffpre = c.take<unsigned long long>(segs * (g.n_chunks + 1));
     w.total = c.take<long long>(1);
     w.planes = c.take<unsigned char>(segs * g.plane_bytes);
-    w.hist = nullptr; w.codes = nullptr; w.fhdr = nullptr; w.fhdr_len = nullptr;
+    w.hist = nullptr; w.codes = nullptr; w.fhdr = nullptr; w.fhdr_len = nullptr; w.ivoff = nullptr;
     if (g.opt) {
         w.hist = c.take<unsigned long long>(segs * 4 * kJhSymbols);
         w.codes = c.take<unsigned>(segs * 4 * 256);
@@ -592,6 +653,7 @@ unsigned long long jfif_carve_coded(Carver &c, const JfifGeom &g, JfifBufs &w)
     w.codes = c.take<unsigned>(segs * 4 * 256);
     w.fhdr = c.take<unsigned char>(segs * kJfifHdrMax);
     w.fhdr_len = c.take<int>(segs);
+    if (g.R) w.ivoff = c.take<unsigned long long>(segs * (g.niv + 1));
     return c.bytes();
 }
 
@@ -618,7 +680,7 @@ void jfif_quant_tables(int q, int luma[64], int chroma[64])
     }
 }
 
-void jfif_params_host(int q, int H, int W, JfifParams &p, int ss, int ncomp)
+void jfif_params_host(int q, int H, int W, JfifParams &p, int ss, int ncomp, int R)
 {
     const int nt = ncomp == 1 ? 1 : 2;                       // a grey file: the luma quantiser and the two luma Huffman tables alone
     int t[2][64];
@@ -649,6 +711,10 @@ void jfif_params_host(int q, int H, int W, JfifParams &p, int ss, int ncomp)
         seg(0xC4, 1 + d.len);
         put({ d.id });
         for (int i = 0; i < d.len; i++) o[n++] = d.t[i];
+    }
+    if (R > 0) {                                             // libjpeg writes the DRI in the scan header, after the tables
+        jr_dri(o + n, R);
+        n += kJrDriBytes;
     }
     seg(0xDA, jfif_sos_bytes(ncomp == 1 ? 1 : 3) - 4);
     if (ncomp == 1) put({ 1, 1, 0x00, 0, 63, 0 });
@@ -688,12 +754,17 @@ static hipError_t jf_entropy(hipStream_t st, const JfifGeom &g, const JfifBufs &
     }
     if (g.opt) hipLaunchKernelGGL((k_jfif_count<HS, VS, NC>), dim3(jf_blocks(nb)), th, 0, st, g, w.coef, w.codes, w.lens);
     hipLaunchKernelGGL(k_js_scan<JsInts>, per_seg, scan_th, 0, st, JsInts{ w.lens }, g.nblk, w.boff);
-    hipLaunchKernelGGL(k_jfif_zero, dim3(jf_blocks(g.stream_words), (unsigned)segs), th, 0, st, g, w.boff, w.stream);
-    if (g.opt) hipLaunchKernelGGL((k_jfif_emit<HS, VS, true, NC>), dim3(jf_blocks(nb)), th, 0, st, g, w.coef, w.boff, w.codes, w.stream);
-    else hipLaunchKernelGGL((k_jfif_emit<HS, VS, false, NC>), dim3(jf_blocks(nb)), th, 0, st, g, w.coef, w.boff, w.codes, w.stream);
-    hipLaunchKernelGGL(k_jfif_ffcount, dim3(jf_blocks(nc)), th, 0, st, g, w.boff, w.stream, w.ffcnt);
+    if (g.R) {                                               // the byte starts of the restart intervals: a second prefix sum, over their byte lengths
+        if (!g.opt || !w.ivoff) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_js_scan<JfIntervalBytes>, per_seg, scan_th, 0, st, JfIntervalBytes{ w.boff, g.nblk, g.niv, (long long)g.R * (HS * VS + NC - 1) },
+                           g.niv, w.ivoff);
+    }
+    hipLaunchKernelGGL(k_jfif_zero, dim3(jf_blocks(g.stream_words), (unsigned)segs), th, 0, st, g, w.boff, w.ivoff, w.stream);
+    if (g.opt) hipLaunchKernelGGL((k_jfif_emit<HS, VS, true, NC>), dim3(jf_blocks(nb)), th, 0, st, g, w.coef, w.boff, w.ivoff, w.codes, w.stream);
+    else hipLaunchKernelGGL((k_jfif_emit<HS, VS, false, NC>), dim3(jf_blocks(nb)), th, 0, st, g, w.coef, w.boff, w.ivoff, w.codes, w.stream);
+    hipLaunchKernelGGL(k_jfif_ffcount, dim3(jf_blocks(nc)), th, 0, st, g, w.boff, w.ivoff, w.stream, w.ffcnt);
     hipLaunchKernelGGL(k_js_scan<JsInts>, per_seg, scan_th, 0, st, JsInts{ w.ffcnt }, g.n_chunks, w.ffpre);
-    hipLaunchKernelGGL(k_jfif_layout, dim3(1), dim3(1), 0, st, g, w.par, w.fhdr_len, w.boff, w.ffpre, lengths, offsets, w.total);
+    hipLaunchKernelGGL(k_jfif_layout, dim3(1), dim3(1), 0, st, g, w.par, w.fhdr_len, w.boff, w.ivoff, w.ffpre, lengths, offsets, w.total);
     return hipGetLastError();
 }
 
@@ -713,7 +784,7 @@ hipError_t launch_jfif_scatter(hipStream_t st, const JfifGeom &g, const JfifBufs
                                unsigned char *out, unsigned long long cap)
 {
     hipLaunchKernelGGL(k_jfif_scatter, dim3(jf_blocks((long long)g.nq * g.B * g.n_chunks)), dim3(kJfThreads), 0, st, g, w.par, w.fhdr, w.fhdr_len,
-                       w.boff, w.stream, w.ffpre, lengths, offsets, out, cap);
+                       w.boff, w.ivoff, w.stream, w.ffpre, lengths, offsets, out, cap);
     return hipGetLastError();
 }
 

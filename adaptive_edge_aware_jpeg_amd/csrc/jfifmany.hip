@@ -106,13 +106,14 @@ long long jfifmany_coefs_host(int W, int H, int quality, int ss, const unsigned 
 }
 
 int jfifmany_plan(const aej_jfif_many_desc *descs, int n, long long src_bytes, int ss, bool opt, bool prog, JmPlan &plan,
-                  const char **why)
+                  const char **why, int rst_blocks, int rst_rows)
 {
     auto refuse = [&](int i, const char *w) { if (why) *why = w; return i; };
     if (!descs || n < 1 || n > 65535 || ss < 0 || ss > 2) return refuse(0, "1 .. 65535 images and subsampling 0, 1 or 2 required");
     plan = JmPlan{};
     plan.t.prog = prog;
     plan.t.annexk = !prog && !opt;
+    plan.t.rst_blocks = rst_blocks; plan.t.rst_rows = rst_rows;
     plan.t.files.assign(n, JtFile{});
     plan.images.assign(n, JmImage{});
     plan.hs = ss == 0 ? 1 : 2; plan.vs = ss == 2 ? 2 : 1;
@@ -144,7 +145,7 @@ int jfifmany_plan(const aej_jfif_many_desc *descs, int n, long long src_bytes, i
         for (size_t k = 0; k < c.files.size(); k++) {        // Pillow's markers of this image's quality, size and layout
             const aej_jfif_many_desc &d = descs[c.files[k]];
             JfifParams &p = c.par[k];
-            jfif_params_host(d.quality, d.height, d.width, p, ss, c.g.ncomp);
+            jfif_params_host(d.quality, d.height, d.width, p, ss, c.g.ncomp, prog ? 0 : c.g.R);      // (a progressive scan's DRI is k_jfp_tables')
             if (prog) p.hdr[p.dht_off - jfif_sof_bytes(c.g.ncomp) + 1] = 0xC2;      // the frame header is the last segment before the tables: SOF0 -> SOF2
         }
     }

@@ -21,7 +21,11 @@
 //   k_jfp_count    one thread per item: its bits under the file's codes (the scan's table staged in LDS, as in k_jfp_emit)
 //   k_js_scan      bit offsets (JsInts)
 //   k_jfp_zero     the words the scans will use
+//   k_js_scan      restarts only (JfpScan::R, jfif_restart_core.h): the byte starts of every scan's restart intervals (JfpIntervalBytes)
 //   k_jfp_emit     one thread per item: own symbols, EOBn, deferred bits at the item's bit offset; the last item of a scan pads
+// Restart markers: every scan has its own interval (jfp_restarts); the first item of an interval is the first item of a scan -- it breaks
+// the end-of-band chain (k_jfp_facts), its DC predictor is 0 -- every interval is byte-aligned and padded in the scan's stream, and
+// k_jfp_scatter inserts the RSTn markers while it stuffs; k_jfp_tables writes a DRI before the SOS of a scan whose interval changed.
 //   k_jfp_ffcount, k_js_scan, k_jfp_layout, k_jfp_scatter: 0xFF stuffing per 64-byte chunk of every scan's stream (js_stuff_count,
 //                  js_stuff_copy) and the file SOI .. SOF2, then per scan [DHT] SOS data, then EOI
 // Bounds: an item's index derives from JfpGeom; a scan's words stay inside its wcap (je_block_bound per block) and every store into a
@@ -31,6 +35,7 @@
 #include "aej_launch.h"
 #include "jfif_huff_core.h"
 #include "jfif_prog_core.h"
+#include "jfif_restart_core.h"
 #include "jfif_stream_core.h"
 
 #include <vector>
@@ -58,6 +63,13 @@ __host__ __device__ inline long long jfp_prev(const JfpGeom &g, long long i, boo
     *chroma = k >= NL;
     return js_prev(NL, BPM, i / BPM, k);
 }
+// DC first scans: the predictor of item i -- the component's block before it in scan order, 0 at the start of the scan and of a restart interval
+__device__ __forceinline__ int jfp_dc_pred(const JfpGeom &g, const JfpScan &s, const short *base, long long i, bool *chroma)
+{
+    const long long pb = jfp_prev(g, i, chroma);
+    const int BPM = g.hs * g.vs + g.nchroma;
+    return pb < 0 || jr_resets(i / BPM, pb, BPM, s.R) ? 0 : base[pb * 64];
+}
 // the value of item idx in the partition's prefix sums (je_pack), from the flags k_jfp_facts left
 __device__ __forceinline__ unsigned long long jfp_value(const unsigned short *flags, long long idx)
 {
@@ -70,6 +82,16 @@ __device__ __forceinline__ long long jfp_scan_bits(const JfpGeom &g, const unsig
 {
     const unsigned long long *p = pre + seg * (g.T + 1) + s.ioff;
     return (long long)(p[s.n] - p[0]);
+}
+// the bytes of scan s of file seg in its unstuffed stream: its bits rounded up, or with restarts the sum of its byte-aligned intervals
+__device__ __forceinline__ long long jfp_scan_bytes(const JfpGeom &g, const unsigned long long *pre, const unsigned long long *ivpre, long long seg,
+                                                    const JfpScan &s)
+{
+    if (g.NIV) {
+        const unsigned long long *v = ivpre + seg * (g.NIV + 1) + s.ivoff;
+        return (long long)(v[s.niv] - v[0]);
+    }
+    return (jfp_scan_bits(g, pre, seg, s) + 7) >> 3;
 }
 __device__ __forceinline__ int jfp_chunk_scan(const JfpGeom &g, long long ch)      // the scan whose stream holds chunk ch
 {
@@ -90,7 +112,8 @@ __global__ __launch_bounds__(kJfpThreads) void k_jfp_facts(JfpGeom g, const shor
         const short *c = coef + (seg * g.nblk + jfp_coef_block(g, s, i)) * 64;
         JeNull nul;
         const JeBlock b = s.Ah ? je_ac_refine(c, s.Ss, s.Se, s.Al, nul) : je_ac_first(c, s.Ss, s.Se, s.Al, nul);
-        f = kFlagAc | (b.e ? kFlagE : 0) | (b.r > 0 || b.br > 0 ? kFlagJoins : 0) | ((unsigned)b.br << 2) | (i == 0 ? kFlagFirst : 0);
+        f = kFlagAc | (b.e ? kFlagE : 0) | (b.r > 0 || b.br > 0 ? kFlagJoins : 0) | ((unsigned)b.br << 2) |
+            (i == 0 || (s.R && i % s.per == 0) ? kFlagFirst : 0);      // the first item of a restart interval is the first of a scan: it breaks the chain
     }
     flags[seg * g.T + s.ioff + i] = (unsigned short)f;
 }
@@ -141,9 +164,9 @@ __global__ __launch_bounds__(kJfpThreads) void k_jfp_hist(JfpGeom g, const short
         const short *base = coef + seg * g.nblk * 64;
         if (s.Ss == 0) {
             bool chroma;
-            const long long pb = jfp_prev(g, i, &chroma);
+            const int pred = jfp_dc_pred(g, s, base, i, &chroma);
             JfpHistSink sink{ cnt[threadIdx.x / 64][chroma ? 1 : 0] };
-            je_dc_first(base[i * 64], pb < 0 ? 0 : base[pb * 64], s.Al, sink);
+            je_dc_first(base[i * 64], pred, s.Al, sink);
         } else {
             JfpHistSink sink{ cnt[threadIdx.x / 64][0] };
             const short *c = base + jfp_coef_block(g, s, i) * 64;
@@ -191,7 +214,7 @@ __global__ __launch_bounds__(kJfpMaxTables * 64) void k_jfp_tables(JfpGeom g, co
         const int ntables = g.raw ? 0 : s.Ss > 0 ? 1 : s.Ah ? 0 : 1 + (g.nchroma > 0);
         for (int u = 0; u < ntables; u++) {
             const int tb = s.tbl + u, n = nsym[tb];
-            if (off + 5 + 16 + n + 14 > kJfpPiece) break;    // never: a DC table holds at most 17 symbols, an AC table 256
+            if (off + 5 + 16 + n + kJrDriBytes + 14 > kJfpPiece) break;      // never: a DC table holds at most 17 symbols, an AC table 256
             if (lane == 0) {
                 o[off] = 0xFF; o[off + 1] = 0xC4; o[off + 2] = (unsigned char)((19 + n) >> 8); o[off + 3] = (unsigned char)((19 + n) & 255);
                 o[off + 4] = (unsigned char)(s.Ss == 0 ? u : 0x10 | (s.comp > 0 ? 1 : 0));
@@ -201,6 +224,10 @@ __global__ __launch_bounds__(kJfpMaxTables * 64) void k_jfp_tables(JfpGeom g, co
         }
         if (!g.raw) {
             const int nc = s.Ss == 0 ? 1 + g.nchroma : 1;
+            if (s.dri) {                                     // the scan's interval differs from the one before: a DRI after its tables
+                if (lane == 0) jr_dri(o + off, s.R);
+                off += kJrDriBytes;
+            }
             if (lane == 0) {
                 unsigned char *q = o + off;
                 q[0] = 0xFF; q[1] = 0xDA; q[2] = 0; q[3] = (unsigned char)(6 + 2 * nc); q[4] = (unsigned char)nc;
@@ -237,9 +264,9 @@ __device__ __forceinline__ void jfp_item(const JfpGeom &g, const JfpScan &s, lon
             je_dc_refine(base[i * 64], s.Al, sink);
         } else {
             bool chroma;
-            const long long pb = jfp_prev(g, i, &chroma);
+            const int pred = jfp_dc_pred(g, s, base, i, &chroma);
             sink.codes = codes + (chroma ? 256 : 0);
-            je_dc_first(base[i * 64], pb < 0 ? 0 : base[pb * 64], s.Al, sink);
+            je_dc_first(base[i * 64], pred, s.Al, sink);
         }
         return;
     }
@@ -268,7 +295,7 @@ __global__ __launch_bounds__(kJfpThreads) void k_jfp_count(JfpGeom g, const shor
 // every item's code string at its bit offset, boundary words by atomicOr
 __global__ __launch_bounds__(kJfpThreads) void k_jfp_emit(JfpGeom g, const short *__restrict__ coef, const int *__restrict__ plen,
                                                           const unsigned *__restrict__ codes, const unsigned long long *__restrict__ pre,
-                                                          unsigned *__restrict__ stream)
+                                                          const unsigned long long *__restrict__ ivpre, unsigned *__restrict__ stream)
 {
     __shared__ unsigned lc[512];
     const JfpScan s = g.sc[blockIdx.y];
@@ -277,10 +304,18 @@ __global__ __launch_bounds__(kJfpThreads) void k_jfp_emit(JfpGeom g, const short
     jfp_stage_codes(g, s, seg, codes, lc);
     if (i >= s.n) return;
     const unsigned long long *p = pre + seg * (g.T + 1) + s.ioff;
-    const long long total = (long long)(p[s.n] - p[0]);
-    JeEmit sink{ nullptr, JeBits(stream + seg * g.stream_words + s.woff, (long long)(p[i] - p[0]), s.wcap) };
+    long long pos = (long long)(p[i] - p[0]), total = (long long)(p[s.n] - p[0]);
+    bool last = i == s.n - 1;
+    if (s.R) {                                               // uniform: the item's place inside its byte-aligned restart interval
+        const unsigned long long *v = ivpre + seg * (g.NIV + 1) + s.ivoff;
+        const long long iv = i / s.per, lo = iv * s.per, hi = min(lo + s.per, s.n);
+        pos = 8 * (long long)(v[iv] - v[0]) + (long long)(p[i] - p[lo]);
+        total = (long long)(p[hi] - p[lo]);
+        last = i == hi - 1;
+    }
+    JeEmit sink{ nullptr, JeBits(stream + seg * g.stream_words + s.woff, pos, s.wcap) };
     jfp_item(g, s, seg, i, coef, plen, lc, sink);
-    if (i == s.n - 1) {                                      // pad the scan's last byte with 1-bits
+    if (last) {                                              // pad the last byte of the scan (of every restart interval) with 1-bits
         const int pad = (int)((8 - (total & 7)) & 7);
         if (pad) sink.bw.put((1u << pad) - 1, pad);
     }
@@ -288,23 +323,25 @@ __global__ __launch_bounds__(kJfpThreads) void k_jfp_emit(JfpGeom g, const short
 }
 
 // grid of the per-chunk kernels: (chunks of a file, file)
-__global__ __launch_bounds__(kJfpThreads) void k_jfp_zero(JfpGeom g, const unsigned long long *__restrict__ pre, unsigned *__restrict__ stream)
+__global__ __launch_bounds__(kJfpThreads) void k_jfp_zero(JfpGeom g, const unsigned long long *__restrict__ pre,
+                                                         const unsigned long long *__restrict__ ivpre, unsigned *__restrict__ stream)
 {
     const long long seg = blockIdx.y, ch = (long long)blockIdx.x * kJfpThreads + threadIdx.x;
     if (ch >= g.n_chunks) return;
     const JfpScan &s = g.sc[jfp_chunk_scan(g, ch)];
-    const long long used = min(s.wcap, (jfp_scan_bits(g, pre, seg, s) + 31) / 32), lo = (ch - s.coff) * (kJfpChunk / 4);
+    const long long used = min(s.wcap, (jfp_scan_bytes(g, pre, ivpre, seg, s) + 3) >> 2), lo = (ch - s.coff) * (kJfpChunk / 4);
     unsigned *w = stream + seg * g.stream_words + s.woff;
     for (long long j = lo; j < min(used, lo + kJfpChunk / 4); j++) w[j] = 0;
 }
 
-__global__ __launch_bounds__(kJfpThreads) void k_jfp_ffcount(JfpGeom g, const unsigned long long *__restrict__ pre, const unsigned *__restrict__ stream,
+__global__ __launch_bounds__(kJfpThreads) void k_jfp_ffcount(JfpGeom g, const unsigned long long *__restrict__ pre,
+                                                             const unsigned long long *__restrict__ ivpre, const unsigned *__restrict__ stream,
                                                              int *__restrict__ cnt)
 {
     const long long seg = blockIdx.y, ch = (long long)blockIdx.x * kJfpThreads + threadIdx.x;
     if (ch >= g.n_chunks) return;
     const JfpScan &s = g.sc[jfp_chunk_scan(g, ch)];
-    const long long nbytes = min(s.wcap * 4, (jfp_scan_bits(g, pre, seg, s) + 7) >> 3);
+    const long long nbytes = min(s.wcap * 4, jfp_scan_bytes(g, pre, ivpre, seg, s));
     const long long lo = (ch - s.coff) * kJfpChunk, hi = min(nbytes, lo + kJfpChunk);
     const unsigned char *src = reinterpret_cast<const unsigned char *>(stream + seg * g.stream_words + s.woff);
     cnt[seg * g.n_chunks + ch] = js_stuff_count(src, lo, hi);
@@ -312,25 +349,27 @@ __global__ __launch_bounds__(kJfpThreads) void k_jfp_ffcount(JfpGeom g, const un
 
 // the bytes of file seg before the markers of scan si (si == nscan: before EOI)
 __device__ __forceinline__ long long jfp_file_pos(const JfpGeom &g, const JfifParams *par, const int *fhdr_len, const unsigned long long *pre,
-                                                  const unsigned long long *ffpre, long long seg, int si)
+                                                  const unsigned long long *ivpre, const unsigned long long *ffpre, long long seg, int si)
 {
     long long pos = g.raw ? 0 : par[seg / g.B].dht_off;
     const unsigned long long *ff = ffpre + seg * (g.n_chunks + 1);
     for (int u = 0; u < si; u++) {
         const JfpScan &s = g.sc[u];
         const long long last = u + 1 < g.nscan ? g.sc[u + 1].coff : g.n_chunks;
-        pos += fhdr_len[seg * g.nscan + u] + ((jfp_scan_bits(g, pre, seg, s) + 7) >> 3) + (long long)(ff[last] - ff[s.coff]);
+        pos += fhdr_len[seg * g.nscan + u] + jfp_scan_bytes(g, pre, ivpre, seg, s) + (long long)(ff[last] - ff[s.coff]) +
+               (g.NIV ? 2 * (s.niv - 1) : 0);                // an RSTn before every interval but the first
     }
     return pos;
 }
 
 __global__ __launch_bounds__(kJfpThreads) void k_jfp_layout(JfpGeom g, const JfifParams *__restrict__ par, const int *__restrict__ fhdr_len,
-                                                            const unsigned long long *__restrict__ pre, const unsigned long long *__restrict__ ffpre,
-                                                            long long *__restrict__ lengths, long long *__restrict__ offsets, long long *__restrict__ total)
+                                                            const unsigned long long *__restrict__ pre, const unsigned long long *__restrict__ ivpre,
+                                                            const unsigned long long *__restrict__ ffpre, long long *__restrict__ lengths,
+                                                            long long *__restrict__ offsets, long long *__restrict__ total)
 {
     // every thread sizes its share of the files, thread 0 lays them out in (quality, image) order
     for (long long seg = threadIdx.x; seg < g.segs; seg += kJfpThreads)
-        lengths[seg] = jfp_file_pos(g, par, fhdr_len, pre, ffpre, seg, g.nscan) + (g.raw ? 0 : 2);
+        lengths[seg] = jfp_file_pos(g, par, fhdr_len, pre, ivpre, ffpre, seg, g.nscan) + (g.raw ? 0 : 2);
     __syncthreads();
     if (threadIdx.x != 0) return;
     long long off = 0;
@@ -343,7 +382,8 @@ __global__ __launch_bounds__(kJfpThreads) void k_jfp_layout(JfpGeom g, const Jfi
 
 __global__ __launch_bounds__(kJfpThreads) void k_jfp_scatter(JfpGeom g, const JfifParams *__restrict__ par, const unsigned char *__restrict__ fhdr,
                                                              const int *__restrict__ fhdr_len, const unsigned long long *__restrict__ pre,
-                                                             const unsigned *__restrict__ stream, const unsigned long long *__restrict__ ffpre,
+                                                             const unsigned long long *__restrict__ ivpre, const unsigned *__restrict__ stream,
+                                                             const unsigned long long *__restrict__ ffpre,
                                                              const long long *__restrict__ lengths, const long long *__restrict__ offsets,
                                                              unsigned char *__restrict__ out, unsigned long long cap)
 {
@@ -353,12 +393,12 @@ __global__ __launch_bounds__(kJfpThreads) void k_jfp_scatter(JfpGeom g, const Jf
     if (off < 0 || len < 0 || (unsigned long long)(off + len) > cap) return;
     const int si = jfp_chunk_scan(g, ch);
     const JfpScan &s = g.sc[si];
-    const long long nbytes = min(s.wcap * 4, (jfp_scan_bits(g, pre, seg, s) + 7) >> 3);
+    const long long nbytes = min(s.wcap * 4, jfp_scan_bytes(g, pre, ivpre, seg, s));
     const long long lo = (ch - s.coff) * kJfpChunk, hi = min(nbytes, lo + kJfpChunk);
     if (lo > 0 && lo >= hi) return;
     unsigned char *file = out + off;
     const int hl = fhdr_len[seg * g.nscan + si];
-    const long long at = jfp_file_pos(g, par, fhdr_len, pre, ffpre, seg, si);
+    const long long at = jfp_file_pos(g, par, fhdr_len, pre, ivpre, ffpre, seg, si);
     if (lo == 0) {                                           // the scan's first chunk also writes the markers before it
         const unsigned char *h = fhdr + (seg * g.nscan + si) * kJfpPiece;
         for (int j = 0; j < hl; j++) file[at + j] = h[j];
@@ -371,32 +411,78 @@ __global__ __launch_bounds__(kJfpThreads) void k_jfp_scatter(JfpGeom g, const Jf
     }
     const unsigned long long *ff = ffpre + seg * (g.n_chunks + 1);
     const unsigned char *src = reinterpret_cast<const unsigned char *>(stream + seg * g.stream_words + s.woff);
-    js_stuff_copy(file + at + hl + lo + (long long)(ff[ch] - ff[s.coff]), src, lo, hi);
+    unsigned char *dst = file + at + hl + lo + (long long)(ff[ch] - ff[s.coff]);
+    if (s.R) {                                               // uniform: the markers before this chunk shift it, those inside it are written here
+        const unsigned long long *starts = ivpre + seg * (g.NIV + 1) + s.ivoff;
+        const long long k = jr_first_from(starts, s.niv, lo);
+        jr_stuff_copy(dst + 2 * (k - 1), src, lo, hi, starts, s.niv, k);
+    } else {
+        js_stuff_copy(dst, src, lo, hi);
+    }
 }
+
+// restarts: k_js_scan's input for the intervals' starts -- interval i of the launch (file after file, scan after scan inside a file),
+// its items' bits (from the bit prefix sums) rounded up to bytes
+struct JfpIntervalBytes {
+    const unsigned long long *pre;
+    JfpGeom g;
+    __device__ __forceinline__ unsigned long long operator()(long long i) const
+    {
+        const long long seg = i / g.NIV, j = i % g.NIV;
+        int si = 0;
+        while (si + 1 < g.nscan && j >= g.sc[si + 1].ivoff) si++;
+        const JfpScan &s = g.sc[si];
+        const unsigned long long *p = pre + seg * (g.T + 1) + s.ioff;
+        const long long lo = (j - s.ivoff) * s.per, hi = min(lo + s.per, s.n);
+        return (p[hi] - p[lo] + 7) >> 3;
+    }
+};
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------------
 static void jfp_finish_geom(JfpGeom &p)
 {
-    long long ioff = 0, woff = 0;
+    long long ioff = 0, woff = 0, ivoff = 0;
     p.nmax = 0;
     for (int i = 0; i < p.nscan; i++) {
         JfpScan &s = p.sc[i];
         s.ioff = ioff;
         s.woff = woff;
         s.coff = woff / (kJfpChunk / 4);
-        s.wcap = ((s.n * je_block_bound(s.Ss, s.Se, s.Ah) + 31) / 32 + 2 + 15) / 16 * 16;
+        s.niv = s.R ? jr_count(s.n, (int)s.per) : 0;         // (per <= 6 x 65535)
+        s.ivoff = ivoff;
+        ivoff += s.niv;
+        // je_block_bound is exact for some scans (a DC refinement item is one bit), so the 1-bits that pad every restart interval to a
+        // byte, up to 7 per interval, are counted on their own
+        s.wcap = ((s.n * je_block_bound(s.Ss, s.Se, s.Ah) + 7 * s.niv + 31) / 32 + 2 + 15) / 16 * 16;
         ioff += s.n;
         woff += s.wcap;
         p.nmax = std::max(p.nmax, s.n);
     }
     p.T = ioff;
+    p.NIV = ivoff;
     p.stream_words = woff;
     p.n_chunks = woff / (kJfpChunk / 4);
 }
 
-bool jfifprog_geom(const JfifGeom &g, JfpGeom &p)
+// the restart interval of every scan of the script: its own MCUs per row (an interleaved scan mcux, a single-component scan the
+// component's blocks per row), a DRI where it differs from the last one written (0 before the first scan)
+static void jfp_restarts(const JfifGeom &g, JfpGeom &p, int blocks, int rows)
+{
+    int written = 0;
+    for (int i = 0; i < p.nscan; i++) {
+        JfpScan &s = p.sc[i];
+        const bool inter = s.comp < 0;
+        s.R = jr_interval(blocks, rows, inter || s.comp > 0 ? g.mcux : g.ybx);
+        s.per = (long long)s.R * (inter ? p.hs * p.vs + p.nchroma : 1);
+        s.dri = s.R != written;
+        written = s.R;
+    }
+}
+
+bool jfifprog_geom(const JfifGeom &g, JfpGeom &p, int blocks, int rows)
 {
     if ((long long)g.nq * g.B > 65535) return false;         // files index grid.z
+    if (blocks < 0 || blocks > kJrMaxInterval || rows < 0 || rows > kJrMaxInterval) return false;
     p = JfpGeom{};
     p.segs = g.nq * g.B; p.B = g.B; p.hs = g.hs; p.vs = g.vs; p.nchroma = 2; p.mcux = g.mcux; p.ybx = g.ybx;
     p.nscan = kJfpMaxScans; p.ntab = kJfpMaxTables; p.raw = 0; p.nblk = g.nblk;
@@ -409,6 +495,7 @@ bool jfifprog_geom(const JfifGeom &g, JfpGeom &p)
             s.comp = grey[i][0]; s.Ss = grey[i][1]; s.Se = grey[i][2]; s.Ah = grey[i][3]; s.Al = grey[i][4]; s.tbl = grey[i][5];
             s.n = g.nblk;
         }
+        jfp_restarts(g, p, blocks, rows);
         jfp_finish_geom(p);
         return true;
     }
@@ -421,6 +508,7 @@ bool jfifprog_geom(const JfifGeom &g, JfpGeom &p)
         s.comp = script[i][0]; s.Ss = script[i][1]; s.Se = script[i][2]; s.Ah = script[i][3]; s.Al = script[i][4]; s.tbl = script[i][5];
         s.n = s.comp < 0 ? g.nblk : s.comp == 0 ? (long long)g.ybx * g.yby : g.n_mcu;
     }
+    jfp_restarts(g, p, blocks, rows);
     jfp_finish_geom(p);
     return true;
 }
@@ -441,6 +529,7 @@ static void jfp_carve(Carver &c, const JfpGeom &p, JfpBufs &pw)
     pw.fhdr_len = c.take<int>(segs * p.nscan);
     pw.cuts = c.take<int>(segs * p.nscan * 2);
     pw.total = c.take<long long>(1);
+    pw.ivpre = p.NIV ? c.take<unsigned long long>(segs * (p.NIV + 1)) : nullptr;
 }
 
 // the workspace: what colour .. quantisation and the reconstruction use of JfifBufs (the baseline coder's buffers are not carved;
@@ -491,11 +580,15 @@ static hipError_t jfp_entropy(hipStream_t st, const JfpGeom &p, const JfpBufs &p
     hipLaunchKernelGGL(k_jfp_tables, dim3(segs), dim3(64 * p.ntab), 0, st, p, pw.hist, pw.codes, pw.fhdr, pw.fhdr_len);
     hipLaunchKernelGGL(k_jfp_count, items, th, 0, st, p, coef, pw.plen, pw.codes, pw.lens);
     hipLaunchKernelGGL(k_js_scan<JsInts>, dim3(segs), dim3(kJsScanThreads), 0, st, JsInts{ pw.lens }, p.T, pw.pre);
-    hipLaunchKernelGGL(k_jfp_zero, chunks, th, 0, st, p, pw.pre, pw.stream);
-    hipLaunchKernelGGL(k_jfp_emit, items, th, 0, st, p, coef, pw.plen, pw.codes, pw.pre, pw.stream);
-    hipLaunchKernelGGL(k_jfp_ffcount, chunks, th, 0, st, p, pw.pre, pw.stream, pw.ffcnt);
+    if (p.NIV) {                                             // the byte starts of the restart intervals: a second prefix sum, over their byte lengths
+        if (!pw.ivpre) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_js_scan<JfpIntervalBytes>, dim3(segs), dim3(kJsScanThreads), 0, st, JfpIntervalBytes{ pw.pre, p }, p.NIV, pw.ivpre);
+    }
+    hipLaunchKernelGGL(k_jfp_zero, chunks, th, 0, st, p, pw.pre, pw.ivpre, pw.stream);
+    hipLaunchKernelGGL(k_jfp_emit, items, th, 0, st, p, coef, pw.plen, pw.codes, pw.pre, pw.ivpre, pw.stream);
+    hipLaunchKernelGGL(k_jfp_ffcount, chunks, th, 0, st, p, pw.pre, pw.ivpre, pw.stream, pw.ffcnt);
     hipLaunchKernelGGL(k_js_scan<JsInts>, dim3(segs), dim3(kJsScanThreads), 0, st, JsInts{ pw.ffcnt }, p.n_chunks, pw.ffpre);
-    hipLaunchKernelGGL(k_jfp_layout, dim3(1), th, 0, st, p, par, pw.fhdr_len, pw.pre, pw.ffpre, lengths, offsets, pw.total);
+    hipLaunchKernelGGL(k_jfp_layout, dim3(1), th, 0, st, p, par, pw.fhdr_len, pw.pre, pw.ivpre, pw.ffpre, lengths, offsets, pw.total);
     return out ? launch_jfifprog_scatter(st, p, pw, par, lengths, offsets, out, cap) : hipGetLastError();
 }
 
@@ -503,7 +596,7 @@ hipError_t launch_jfifprog_scatter(hipStream_t st, const JfpGeom &p, const JfpBu
                                    const long long *offsets, unsigned char *out, unsigned long long cap)
 {
     hipLaunchKernelGGL(k_jfp_scatter, dim3(jfp_blocks(p.n_chunks), (unsigned)p.segs), dim3(kJfpThreads), 0, st, p, par, pw.fhdr, pw.fhdr_len, pw.pre,
-                       pw.stream, pw.ffpre, lengths, offsets, out, cap);
+                       pw.ivpre, pw.stream, pw.ffpre, lengths, offsets, out, cap);
     return hipGetLastError();
 }
 

@@ -21,7 +21,9 @@
 //                   dummy output block is written as libjpeg writes it: lane 0 takes the DC of the real block before it in the MCU, the
 //                   AC lanes read nothing and write 0.  Range ballot and status protocol are the bridge's (the limits are symmetric but
 //                   for the DC, which no transform negates).  A file whose transform is "none" goes through it unchanged, dummies too.
-//   (per group)     launch_jfif_entropy / launch_jfifprog_entropy: histogram .. file lengths, unchanged
+//   (per group)     launch_jfif_entropy / launch_jfifprog_entropy: histogram .. file lengths, unchanged; a source's restart markers
+//                   are gone with its entropy coding, and the output gets those of JtPlan::rst_blocks / rst_rows (jfiftrans_close gives
+//                   every group its interval; 0, 0: none)
 //   k_jt_sos_ids    progressive groups with component ids other than 1, 2, 3 only: the ids in the SOS markers k_jfp_tables wrote
 //   k_jt_place      one thread: the files' offsets in the packed output, group after group
 //   (per group)     launch_jfif_scatter / launch_jfifprog_scatter
@@ -229,7 +231,9 @@ int jfiftrans_close(JtPlan &plan)
     long long first = 0;
     for (JtGroup &c : plan.groups) {
         const int ng = (int)c.files.size(), ss = c.g.hs == 1 ? 0 : c.g.vs == 1 ? 1 : 2;
-        if (!jfif_geom(1, c.g.H, c.g.W, ng, c.g, ss, 1, c.g.ncomp) || (plan.prog && !jfifprog_geom(c.g, c.p))) return c.files[0];
+        if (!jfif_geom(1, c.g.H, c.g.W, ng, c.g, ss, 1, c.g.ncomp) || !jfif_geom_restart(c.g, plan.rst_blocks, plan.rst_rows) ||
+            (plan.prog && !jfifprog_geom(c.g, c.p, plan.rst_blocks, plan.rst_rows)))
+            return c.files[0];
         c.first = first;
         c.par.assign(ng, JfifParams{});
         for (int k = 0; k < ng; k++) plan.files[c.files[k]].out_pos = (int)(first + k);
@@ -239,13 +243,14 @@ int jfiftrans_close(JtPlan &plan)
 }
 
 int jfiftrans_plan(const std::vector<JtSource> &src, const std::vector<long long> &n_blocks, bool prog, const int *xf, int trim, JtPlan &plan,
-                   int *why)
+                   int *why, int rst_blocks, int rst_rows)
 {
     auto refuse = [&](int i, int w) { if (why) *why = w; return i; };
     const int n = (int)src.size();
     if (n < 1 || n > 65535 || n_blocks.size() != src.size()) return refuse(0, kJxBadArg);
     plan = JtPlan{};
     plan.prog = prog;
+    plan.rst_blocks = rst_blocks; plan.rst_rows = rst_rows;  // a source's own markers are never carried over: the call's options alone decide
     plan.files.assign(n, JtFile{});
     plan.geom.assign(n, JxGeom{});
     for (int i = 0; i < n; i++) {

@@ -77,6 +77,17 @@ def _check_bool(name, v) -> bool:
     return bool(v)
 
 
+def _check_restart(blocks, rows):
+    """restart_marker_blocks= / restart_marker_rows= -> two ints in 0..65535 (TypeError for anything but an int, a bool included;
+    ValueError outside the range a DRI segment holds)"""
+    for name, v in (("restart_marker_blocks", blocks), ("restart_marker_rows", rows)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise TypeError(f"{name} must be an int, got {type(v).__name__}")
+        if not 0 <= v <= 65535:
+            raise ValueError(f"{name} {v}: 0..65535 required")
+    return blocks, rows
+
+
 def headers(quality: int, H: int, W: int, subsampling="4:2:0", mode: str = "RGB") -> bytes:
     """The markers SOI .. SOS of the file of one (quality, H, W, subsampling) with the Annex K Huffman tables
     (aej_jfif_headers_host_opt); mode="L": those of the grey file (aej_jfif_headers_grey_host; subsampling does not bear on it)."""
@@ -226,7 +237,9 @@ def standard_jpeg_many(x, quality: int, device: int = 0, subsampling="4:2:0", op
     optimize=optimize, progressive=progressive)``.  x: uint8 or float32 in [0, 1], [B, H, W, 3] or [H, W, 3], numpy or torch.  subsampling: "4:4:4", "4:2:2",
     "4:2:0" or 0, 1, 2 (ValueError otherwise); optimize: a bool (TypeError otherwise) -- per file the Huffman tables built from its
     own symbols; progressive: a bool (TypeError otherwise) -- the progressive (SOF2) file of libjpeg's ten scans, whose tables are
-    always its own, so optimize does not change its bytes."""
+    always its own, so optimize does not change its bytes.  This call, standard_jpeg_batch and sweep write no restart markers (their
+    Annex K bit count is fused into the quantisation kernel); standard_jpeg_encode_many and the transcoder take restart_marker_blocks=
+    and restart_marker_rows=."""
     q, ss, opt, prog = _check_quality(quality), _check_subsampling(subsampling), _check_bool("optimize", optimize), _check_bool("progressive", progressive)
     ctx = get_context(device)
     return _Encoded(ctx, _to_u8(ctx, x), [q], True, ss, opt, prog).files()[0]
@@ -722,7 +735,8 @@ def transform_prefix(data, transform, progressive: bool = False, trim: bool = Fa
 
 
 def standard_jpeg_transform_many(files, transform, progressive: bool = False, trim: bool = False, device: int = 0,
-                                 keep_metadata: bool = False, grey: bool = False) -> List[bytes]:
+                                 keep_metadata: bool = False, grey: bool = False, restart_marker_blocks: int = 0,
+                                 restart_marker_rows: int = 0) -> List[bytes]:
     """Lossless flip, rotation or transposition on the device: standard_jpeg_transcode_many with the files' quantised coefficients
     rearranged between the Huffman decode and the entropy coders (one kernel in the place of the transcoder's bridge), so that no
     sample is quantised a second time -- ``jpegtran -flip / -rotate / -transpose / -transverse``.  files, progressive, device and
@@ -748,10 +762,14 @@ def standard_jpeg_transform_many(files, transform, progressive: bool = False, tr
     carries, so every transform is allowed, a mirrored axis has to be a multiple of 8 and trim=True drops the partial 8-pixel column /
     row; it has no dummy blocks.  Its output is the transcoder's grey file with its one table transposed by a transposing transform.
 
+    restart_marker_blocks, restart_marker_rows: the transcoder's (``jpegtran -restart NB`` / ``-restart N``), counted on the OUTPUT's
+    MCU grid; with both 0 the output has no restart markers whatever the source carries.
+
     Not built: a transposing transform of a 4:2:2 file (it would be 4:4:0; NotImplementedError), crop.  Every refusal names the file and
     comes before any device work; there is no CPU fallback."""
     progressive, keep_metadata = _check_bool("progressive", progressive), _check_bool("keep_metadata", keep_metadata)
     trim, grey = _check_bool("trim", trim), _check_bool("grey", grey)
+    rst = _check_restart(restart_marker_blocks, restart_marker_rows)
     files = list(files)
     if not files:
         raise ValueError("standard_jpeg_transform_many needs at least one file")
@@ -763,10 +781,11 @@ def standard_jpeg_transform_many(files, transform, progressive: bool = False, tr
         if len(names) != n:
             raise ValueError(f"file {min(len(names), n)}: {len(names)} transforms for {n} files")
         names = [_check_transform(t, i) for i, t in enumerate(names)]
-    return _transcode_many(files, progressive, device, keep_metadata, names, trim, names is None, grey)
+    return _transcode_many(files, progressive, device, keep_metadata, names, trim, names is None, grey, rst)
 
 
-def standard_jpeg_transcode_many(files, progressive: bool = False, device: int = 0, keep_metadata: bool = False, grey: bool = False) -> List[bytes]:
+def standard_jpeg_transcode_many(files, progressive: bool = False, device: int = 0, keep_metadata: bool = False, grey: bool = False,
+                                 restart_marker_blocks: int = 0, restart_marker_rows: int = 0) -> List[bytes]:
     """Lossless transcode on the device: -> every file entropy-coded again, in input order.  files: a non-empty sequence of bytes-like
     JPEG contents, baseline / extended-sequential (SOF0 / SOF1) and complete progressive (SOF2) files of any sizes and of the 4:4:4,
     4:2:2 and 4:2:0 layouts mixed freely.  progressive=False: a baseline file under the file's own optimal Huffman tables (what
@@ -774,8 +793,13 @@ def standard_jpeg_transcode_many(files, progressive: bool = False, device: int =
     coefficient of the output equals the source's, so both decode to the same pixels, and a file Pillow wrote gives Pillow's own
     optimize=True / progressive=True file byte for byte.  The output: SOI, JFIF 1.01 APP0 with the source's density, with
     keep_metadata=True the source's APP1 .. APP13, APP15 and COM segments (host work; never APP0 or Adobe APP14), the source's
-    quantisation tables (8-bit, one DQT per table), its frame header, then tables and scans as the encoders lay them out.  Restart
-    markers are dropped.
+    quantisation tables (8-bit, one DQT per table), its frame header, then tables and scans as the encoders lay them out.
+
+    restart_marker_blocks, restart_marker_rows: Pillow's save options of those names, here ``jpegtran -restart NB`` / ``-restart N``
+    (standard_jpeg_encode_many documents them): the output carries a DRI and an RSTn marker every N MCUs / MCU rows, which is what lets
+    a decoder -- this library's among them -- work on the file's restart segments in parallel, and equals Pillow's optimize=True /
+    progressive=True file with the same option byte for byte.  A source's own restart markers are never carried over: the two keywords
+    alone decide, and with both 0 (the default) the output has none.
 
     grey=True also takes one-component (grey) files, baseline or progressive, mixed freely with colour ones (TypeError for a value
     that is not a bool).  Such a file is sampled 1 x 1 whatever its frame header says; its output has one DQT (its table, as table 0),
@@ -789,14 +813,16 @@ def standard_jpeg_transcode_many(files, progressive: bool = False, device: int =
     CPU fallback."""
     progressive, keep_metadata = _check_bool("progressive", progressive), _check_bool("keep_metadata", keep_metadata)
     grey = _check_bool("grey", grey)
+    rst = _check_restart(restart_marker_blocks, restart_marker_rows)
     files = list(files)
     if not files:
         raise ValueError("standard_jpeg_transcode_many needs at least one file")
-    return _transcode_many(files, progressive, device, keep_metadata, None, False, False, grey)
+    return _transcode_many(files, progressive, device, keep_metadata, None, False, False, grey, rst)
 
 
-def _transcode_many(files, progressive, device, keep_metadata, names, trim, exif, grey=False):
-    """the transcode (names None and not exif) and the transform: names[i] is file i's transform, exif takes it from the file"""
+def _transcode_many(files, progressive, device, keep_metadata, names, trim, exif, grey=False, rst=(0, 0)):
+    """the transcode (names None and not exif) and the transform: names[i] is file i's transform, exif takes it from the file; rst:
+    (restart_marker_blocks, restart_marker_rows) -- (0, 0) goes through the entries without restart arguments"""
     global _last_transcode_groups
     from ._lib import JpegDecDesc, JpegProgFrame, JpegProgScan
     n = len(files)
@@ -834,27 +860,31 @@ def _transcode_many(files, progressive, device, keep_metadata, names, trim, exif
     dens = np.ascontiguousarray(np.array([density[i] for i in order], np.uint16))
     codes = np.ascontiguousarray(np.array([TRANSFORMS.index(names[i]) for i in order], np.int32))
     plain = not codes.any()                         # every file "none": the transcoder's own entries
+    rst = tuple(rst) if any(rst) else ()            # the _rst entries' two extra arguments
+    sfx = "_rst" if rst else ""
     if plain:
-        nws = int(lib.aej_jfif_transcode_workspace_bytes(ctx.handle, ctypes.addressof(descs), nb, ctypes.addressof(frames), ctypes.addressof(pscans),
-                                                         npg, int(progressive)))
+        nws = int(getattr(lib, "aej_jfif_transcode_workspace_bytes" + sfx)(ctx.handle, ctypes.addressof(descs), nb, ctypes.addressof(frames),
+                                                                          ctypes.addressof(pscans), npg, int(progressive), *rst))
     else:
-        nws = int(lib.aej_jfif_transform_workspace_bytes(ctx.handle, ctypes.addressof(descs), nb, ctypes.addressof(frames), ctypes.addressof(pscans),
-                                                         npg, int(progressive), codes.ctypes.data, int(trim)))
+        nws = int(getattr(lib, "aej_jfif_transform_workspace_bytes" + sfx)(ctx.handle, ctypes.addressof(descs), nb, ctypes.addressof(frames),
+                                                                          ctypes.addressof(pscans), npg, int(progressive), codes.ctypes.data,
+                                                                          int(trim), *rst))
     if nws == 0:
         raise ValueError("descriptors the library refuses")
     ws = ctx.workspace(nws)
     status, offsets, lengths = ctx.empty((n,), t.int32), ctx.empty((n,), t.int64), ctx.empty((n,), t.int64)
     total, groups = ctypes.c_uint64(), ctypes.c_int32()
-    cap = sum(len(v) for v in views) * 5 // 4 + (PROGRESSIVE_HEADER_CAPACITY if progressive else HEADER_CAPACITY) * n
+    cap = sum(len(v) for v in views) * 5 // 4 + (PROGRESSIVE_HEADER_CAPACITY if progressive else HEADER_CAPACITY) * n      # (a miss costs one more call)
     out = ctx.empty((cap,), t.uint8)
     head = (ctx.handle, ctypes.addressof(descs), nb, scans.data_ptr(), ctypes.c_uint64(scans.numel()), scan_off.ctypes.data, ctypes.addressof(frames),
             ctypes.addressof(pscans), npg, data.data_ptr(), ctypes.c_uint64(data.numel()), data_off.ctypes.data, dens.ctypes.data, int(progressive))
     tail = (offsets.data_ptr(), lengths.data_ptr(), ctypes.addressof(total), status.data_ptr(), ctypes.addressof(groups), ws.data_ptr(),
             ctypes.c_uint64(nws))
     if plain:
-        call = lambda o, c: lib.aej_jfif_transcode_batch(*head, o.data_ptr(), ctypes.c_uint64(c), *tail)  # noqa: E731
+        call = lambda o, c: getattr(lib, "aej_jfif_transcode_batch" + sfx)(*head, *rst, o.data_ptr(), ctypes.c_uint64(c), *tail)  # noqa: E731
     else:
-        call = lambda o, c: lib.aej_jfif_transform_batch(*head, codes.ctypes.data, int(trim), o.data_ptr(), ctypes.c_uint64(c), *tail)  # noqa: E731
+        call = lambda o, c: getattr(lib, "aej_jfif_transform_batch" + sfx)(*head, codes.ctypes.data, int(trim), *rst, o.data_ptr(),  # noqa: E731
+                                                                          ctypes.c_uint64(c), *tail)
     rc = call(out, cap)
     if rc == -4 and total.value > cap:             # AEJ_ERR_CAPACITY: run again with the exact size
         cap = int(total.value)
@@ -969,13 +999,15 @@ def _packed_source(ctx, imgs):
     return buf, buf.data_ptr(), total, off
 
 
-def _encode_many(ctx, imgs, qualities, ss, opt, prog):
+def _encode_many(ctx, imgs, qualities, ss, opt, prog, rst=(0, 0)):
     global _last_encode_groups
+    rst = tuple(rst) if any(rst) else ()            # (0, 0) goes through the entries without restart arguments
+    sfx = "_rst" if rst else ""
     from ._lib import JfifManyDesc
     t, lib, n = ctx.torch, ctx.lib, len(imgs)
     keep, src, src_bytes, off = _packed_source(ctx, imgs)
     descs = (JfifManyDesc * n)(*[JfifManyDesc(int(off[i]), int(x.shape[1]), int(x.shape[0]), qualities[i], 1 if x.ndim == 2 else 3) for i, (x, _, _) in enumerate(imgs)])
-    nws = int(lib.aej_jfif_many_workspace_bytes(ctx.handle, ctypes.addressof(descs), n, ss, int(opt), int(prog)))
+    nws = int(getattr(lib, "aej_jfif_many_workspace_bytes" + sfx)(ctx.handle, ctypes.addressof(descs), n, ss, int(opt), int(prog), *rst))
     if nws == 0:
         raise ValueError("descriptors the library refuses")
     ws = ctx.workspace(nws)
@@ -984,8 +1016,8 @@ def _encode_many(ctx, imgs, qualities, ss, opt, prog):
     hdr = PROGRESSIVE_HEADER_CAPACITY if prog else HEADER_CAPACITY
     cap = sum(hdr + x.shape[0] * x.shape[1] * 3 // (4 if ss == 2 else 2) for x, _, _ in imgs)      # most files are far smaller; a miss costs one more call
     out = ctx.empty((cap,), t.uint8)
-    call = lambda o, c: lib.aej_jfif_many_encode(ctx.handle, ctypes.addressof(descs), n, src, ctypes.c_uint64(src_bytes), ss, int(opt), int(prog),  # noqa: E731
-                                                 o.data_ptr(), ctypes.c_uint64(c), offsets.data_ptr(), lengths.data_ptr(), ctypes.addressof(total),
+    call = lambda o, c: getattr(lib, "aej_jfif_many_encode" + sfx)(ctx.handle, ctypes.addressof(descs), n, src, ctypes.c_uint64(src_bytes), ss,  # noqa: E731
+                                                 int(opt), int(prog), *rst, o.data_ptr(), ctypes.c_uint64(c), offsets.data_ptr(), lengths.data_ptr(), ctypes.addressof(total),
                                                  ctypes.addressof(groups), ws.data_ptr(), ctypes.c_uint64(nws))
     rc = call(out, cap)
     if rc == -4 and total.value > cap:                       # AEJ_ERR_CAPACITY: run again with the exact size
@@ -1004,7 +1036,7 @@ def _encode_many(ctx, imgs, qualities, ss, opt, prog):
 
 
 def standard_jpeg_encode_many(images, quality=75, subsampling="4:2:0", optimize: bool = False, progressive: bool = False, device: int = 0,
-                              mode: str = "RGB") -> List[bytes]:
+                              mode: str = "RGB", restart_marker_blocks: int = 0, restart_marker_rows: int = 0) -> List[bytes]:
     """Images of mixed sizes encoded in one call: -> every image's file, in input order; file i equals
     ``Image.fromarray(u8_i).save(buf, "JPEG", quality=q_i, subsampling=subsampling, optimize=optimize, progressive=progressive)`` byte
     for byte, and ``standard_jpeg_many(images[i], q_i, ...)[0]``.  images: a non-empty sequence of [H_i, W_i, 3] images, each uint8 or
@@ -1028,17 +1060,32 @@ def standard_jpeg_encode_many(images, quality=75, subsampling="4:2:0", optimize:
     gets that text as a COM segment right after the JFIF APP0 -- what Pillow from 9.4 on does with ``im.info["comment"]`` on save, and
     the only thing its save carries over from a file.  Without the attribute (every NumPy image) no such segment is written.
 
+    restart_marker_blocks=N, restart_marker_rows=N: Pillow's save options of those names (libjpeg's restart_interval and
+    restart_in_rows), one setting for the call, for colour and grey images and with optimize= and progressive=; file i equals Pillow's
+    save with the same keywords.  A scan's restart interval R counts MCUs of that scan: blocks=N gives R = N for every scan; rows=N > 0
+    overrides it with R = min(N x the scan's MCUs per row, 65535), per scan (an interleaved scan has ceil(W / (8 hs)) MCUs per row, a
+    grey file's scan or a progressive AC scan the component's blocks per row).  The file carries ``FF DD 00 04 Rhi Rlo`` before the SOS
+    of every scan whose R differs from the last one written, and before MCU k R (k >= 1) the coder flushes, pads the byte with 1-bits,
+    writes ``FF D0+((k-1) & 7)`` and resets the DC predictors (a progressive scan its end-of-band run too); optimised tables are built
+    under the same resets.  Such a file decodes restart segment by restart segment in parallel (standard_jpeg_decode_many).  Both 0 (the
+    default): the file as it always was.  A value that is not an int (a bool or a float included) raises TypeError, one outside 0..65535
+    ValueError -- a deliberate departure from Pillow, which wraps or reinterprets such values silently.  standard_jpeg_many,
+    standard_jpeg_batch and sweep write no restart markers (their Annex K bit count is fused into quantisation): this call, the
+    thumbnail call below, standard_jpeg_transcode_many and standard_jpeg_transform_many do.
+
     Checked before any device work, naming the image: a quality outside 1..100, a shape that is not the mode's ([H, W, 3], [H, W])
     with 1 <= H, W <= 65535, a quality sequence of another length, a mode other than the three (ValueError); a dtype other than uint8 / float32, optimize / progressive that are not bools
     (TypeError).  float32 values outside [0, 1] raise ValueError once the image is looked at.  There is no CPU fallback."""
     ss, opt, prog = _check_subsampling(subsampling), _check_bool("optimize", optimize), _check_bool("progressive", progressive)
+    rst = _check_restart(restart_marker_blocks, restart_marker_rows)
     imgs = _check_images(images, _check_mode(mode))
     qualities = _check_qualities(quality, len(imgs))
-    return _encode_many(get_context(device), imgs, qualities, ss, opt, prog)
+    return _encode_many(get_context(device), imgs, qualities, ss, opt, prog, rst)
 
 
 def standard_jpeg_thumbnail_jpeg_many(files, size, quality=75, subsampling="4:2:0", optimize: bool = False, progressive_out: bool = False,
-                                      resample="bicubic", reducing_gap=2.0, progressive: bool = False, device: int = 0) -> List[bytes]:
+                                      resample="bicubic", reducing_gap=2.0, progressive: bool = False, device: int = 0,
+                                      restart_marker_blocks: int = 0, restart_marker_rows: int = 0) -> List[bytes]:
     """JPEG files in, their thumbnails out as JPEG files: ``standard_jpeg_encode_many(standard_jpeg_thumbnail_many(files, size, resample,
     reducing_gap, progressive, device), quality, subsampling, optimize, progressive_out, device)`` -- for a three-component source file
     i equals ``im = Image.open(io.BytesIO(files[i])); im.thumbnail(size, resample, reducing_gap=reducing_gap); im.save(buf, "JPEG",
@@ -1050,12 +1097,13 @@ def standard_jpeg_thumbnail_jpeg_many(files, size, quality=75, subsampling="4:2:
     thumbnails here are three-channel).
     files, size, resample, reducing_gap, progressive (whether progressive SOURCES are accepted): standard_jpeg_thumbnail_many's.
     quality (one, or one per file), subsampling, optimize, progressive_out: standard_jpeg_encode_many's quality, subsampling, optimize
-    and progressive.  Every argument is checked, and every header parsed, before any device work; a file whose scan is corrupt raises
+    and progressive; restart_marker_blocks, restart_marker_rows: passed through to it (Pillow's save options).  Every argument is checked, and every header parsed, before any device work; a file whose scan is corrupt raises
     the decoder's ValueError naming it and nothing is returned."""
     ss, opt, prog = _check_subsampling(subsampling), _check_bool("optimize", optimize), _check_bool("progressive_out", progressive_out)
+    rst = _check_restart(restart_marker_blocks, restart_marker_rows)
     files = list(files)
     if not files:
         raise ValueError("standard_jpeg_thumbnail_jpeg_many needs at least one file")
     qualities = _check_qualities(quality, len(files), "file")
     thumbs = standard_jpeg_thumbnail_many(files, size, resample, reducing_gap, progressive, device)
-    return _encode_many(get_context(device), _check_images(thumbs), qualities, ss, opt, prog)
+    return _encode_many(get_context(device), _check_images(thumbs), qualities, ss, opt, prog, rst)

@@ -367,7 +367,8 @@ AEJ_API int aej_decode_headers(aej_ctx *ctx, const uint8_t *states, const int64_
 
 /* ---- baseline JPEG (the standard-JPEG side of a rate-distortion study) --------------------------------------------------------------
  * Byte-identical to PIL.Image.fromarray(x).save(buf, "JPEG", quality=q) with libjpeg-turbo: JFIF 1.01 (no units, 1:1), 4:2:0, baseline,
- * Annex K quantisation (Pillow's quality scaling, clamped to 1..255) and Huffman tables, islow DCT, no restart markers.
+ * Annex K quantisation (Pillow's quality scaling, clamped to 1..255) and Huffman tables, islow DCT, no restart markers (the ragged
+ * encoder and the transcoder write them: the _rst entries further down).
  * aej_jfif_headers_host: the markers SOI .. SOS of one (quality, H, W) file into out_host; returns their length (623), AEJ_ERR_ARG for a
  *   quality outside 1..100 or H, W outside 1..65535, AEJ_ERR_CAPACITY when capacity is smaller.
  * aej_jfif_encode_batch: rgb is device uint8 [batch][H][W][3]; colour, down-sampling and DCT run once per image, then every one of the
@@ -597,7 +598,8 @@ AEJ_API int64_t aej_jfif_many_coefs_grey_host(int width, int height, int quality
  * baseline sources (descs_host, n_base, scans ... as aej_jpegdec_batch) and progressive ones (frames_host, pscans_host, n_prog, data ...
  * as aej_jpegprog_batch) together; either count may be 0, not both.  File i of the call is baseline source i for i < n_base, otherwise
  * progressive source i - n_base.  Three-component files, and one-component (grey) files, which used to be refused
- * (AEJ_ERR_UNSUPPORTED for a file with a 16-bit quantisation table); restart markers of a source are not written again.
+ * (AEJ_ERR_UNSUPPORTED for a file with a 16-bit quantisation table); restart markers of a source are never carried over: the output has
+ * those the _rst entries below ask for (jpegtran -restart N / NB), and none through the entries without that suffix.
  * A one-component source is sampled 1 x 1 whatever its frame header says (the parsers' rule: hs = vs = 1, blocks_per_mcu = 1); its
  * output has one DQT -- its component's table, written as table 0 --, a one-component SOF with sampling 1 x 1, the two luma DHT and a
  * non-interleaved scan (progressive = 1: libjpeg's six scans for one component).
@@ -675,6 +677,60 @@ AEJ_API int aej_jfif_transform_batch(aej_ctx *ctx, const aej_jpegdec_desc *descs
                                      const int32_t *transforms_host, int trim, uint8_t *out, uint64_t out_capacity, int64_t *offsets,
                                      int64_t *lengths, uint64_t *total_host, int32_t *status, int32_t *n_groups_host, void *workspace,
                                      uint64_t workspace_bytes);
+
+/* ---- restart markers in the files the three writers above produce ---------------------------------------------------------------------
+ * The _rst entries are their namesakes with two more arguments, Pillow's restart_marker_blocks and restart_marker_rows (libjpeg's
+ * restart_interval and restart_in_rows, jpegtran's -restart NB and -restart N), each 0 .. 65535 (AEJ_ERR_ARG otherwise, a workspace size
+ * of 0); the entries without the suffix are these with 0, 0.  A scan's interval R counts MCUs of that scan: restart_rows > 0 gives
+ * min(restart_rows x the scan's MCUs per row, 65535), per scan, and overrides restart_blocks, which gives R = restart_blocks for every
+ * scan.  An interleaved scan has ceil(W / (8 hs)) MCUs per row; a non-interleaved one (a grey file, a progressive AC scan) the
+ * component's blocks per row.  `FF DD 00 04 Rhi Rlo` is written directly before a scan's SOS, after its DHT segments, when R differs from
+ * the last R written in the file (0 at its start).  Before MCU k R of a scan (k >= 1) the coder flushes what is pending (a progressive
+ * scan's end-of-band run with its correction bits), pads the byte with 1-bits (stuffed like any byte), writes FF D0 + ((k - 1) & 7) and
+ * sets every DC predictor to 0; optimised tables are built from statistics gathered under the same resets.  R >= the scan's MCUs: the
+ * DRI alone.  One setting holds for every file of a call.  The files are Pillow's / libjpeg-turbo's byte for byte.
+ * On the device every interval is byte-aligned in the unstuffed stream (a second prefix sum over the intervals' byte lengths) and the
+ * markers are inserted by the kernel that stuffs 0xFF bytes (csrc/jfif_restart_core.h holds the index rules, host + device).
+ * The same-size encoders (aej_jfif_encode_batch*) write no restart markers: their Annex K bit count is fused into quantisation.
+ * aej_jfif_headers_rst_host: HOST only, aej_jfif_headers_host_opt / _grey_host (components 1; 0 or 3: colour) with the DRI of the
+ *   options before the SOS.
+ * aej_jfif_restart_map_host: HOST only, the index rules on one image.  scan_r_host / scan_dri_host: int32 [10], every scan's R and
+ *   whether a DRI precedes it (progressive = 0: the one scan; 1: libjpeg's ten, or six for one component).  For the first scan -- the
+ *   baseline file's scan, interleaved MCU order -- interval_host (int32) and reset_host (uint8) [>= blocks] (either may be NULL) get every
+ *   block's interval and whether its DC predictor is 0, marker_host [>= intervals] (may be NULL) the second byte of the marker before
+ *   each interval (0 for the first); counts2_host (may be NULL) the blocks and the intervals.  -> the scans, AEJ_ERR_ARG, AEJ_ERR_CAPACITY.
+ * (Additions to ABI 3: no existing signature, struct layout or behaviour of a valid call changed.) */
+AEJ_API uint64_t aej_jfif_many_workspace_bytes_rst(aej_ctx *ctx, const aej_jfif_many_desc *descs_host, int n, int subsampling, int optimize,
+                                                   int progressive, int restart_blocks, int restart_rows);
+AEJ_API int aej_jfif_many_encode_rst(aej_ctx *ctx, const aej_jfif_many_desc *descs_host, int n, const uint8_t *src, uint64_t src_bytes,
+                                     int subsampling, int optimize, int progressive, int restart_blocks, int restart_rows, uint8_t *out,
+                                     uint64_t out_capacity, int64_t *offsets, int64_t *lengths, uint64_t *total_host, int32_t *n_groups_host,
+                                     void *workspace, uint64_t workspace_bytes);
+AEJ_API uint64_t aej_jfif_transcode_workspace_bytes_rst(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base,
+                                                        const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *pscans_host, int n_prog,
+                                                        int progressive, int restart_blocks, int restart_rows);
+AEJ_API int aej_jfif_transcode_batch_rst(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base, const uint8_t *scans, uint64_t scans_bytes,
+                                         const int64_t *scan_offsets_host, const aej_jpegprog_frame *frames_host,
+                                         const aej_jpegprog_scan *pscans_host, int n_prog, const uint8_t *data, uint64_t data_bytes,
+                                         const int64_t *data_offsets_host, const uint16_t *density_host, int progressive, int restart_blocks,
+                                         int restart_rows, uint8_t *out, uint64_t out_capacity, int64_t *offsets, int64_t *lengths,
+                                         uint64_t *total_host, int32_t *status, int32_t *n_groups_host, void *workspace, uint64_t workspace_bytes);
+AEJ_API uint64_t aej_jfif_transform_workspace_bytes_rst(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base,
+                                                        const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *pscans_host, int n_prog,
+                                                        int progressive, const int32_t *transforms_host, int trim, int restart_blocks,
+                                                        int restart_rows);
+AEJ_API int aej_jfif_transform_batch_rst(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base, const uint8_t *scans, uint64_t scans_bytes,
+                                         const int64_t *scan_offsets_host, const aej_jpegprog_frame *frames_host,
+                                         const aej_jpegprog_scan *pscans_host, int n_prog, const uint8_t *data, uint64_t data_bytes,
+                                         const int64_t *data_offsets_host, const uint16_t *density_host, int progressive,
+                                         const int32_t *transforms_host, int trim, int restart_blocks, int restart_rows, uint8_t *out,
+                                         uint64_t out_capacity, int64_t *offsets, int64_t *lengths, uint64_t *total_host, int32_t *status,
+                                         int32_t *n_groups_host, void *workspace, uint64_t workspace_bytes);
+AEJ_API int aej_jfif_headers_rst_host(int quality, int H, int W, int subsampling, int components, int restart_blocks, int restart_rows,
+                                      uint8_t *out_host, int capacity);
+AEJ_API int aej_jfif_restart_map_host(int H, int W, int subsampling, int components, int restart_blocks, int restart_rows, int progressive,
+                                      int32_t *scan_r_host, int32_t *scan_dri_host, int32_t *interval_host, uint8_t *reset_host,
+                                      int64_t block_capacity, uint8_t *marker_host, int64_t marker_capacity, int64_t *counts2_host);
 
 /* ---- Pillow's resize, reduce and thumbnail for packed 8-bit RGB images (resize_many, standard_jpeg_thumbnail_many) ------------------
  * Image.resize with the convolution filters, Image.reduce and the reducing_gap step of resize, bit for bit, for many images of

@@ -15,6 +15,7 @@ Every time is a host clock around work that ends in a device synchronise, after 
 gigapixels per second (images x H x W x qualities / time).  Prints one JSON line (and writes it to --out).
 """
 import argparse
+import inspect
 import io
 import json
 import os
@@ -91,6 +92,19 @@ def transcode_routes(a):
     if hasattr(A, "standard_jpeg_transform_many"):               # the transcode with a lossless transform on the way, over the same files
         routes["transform_rot90"] = lambda: sum(len(f) for f in A.standard_jpeg_transform_many(files, "rot90", progressive=False))
         routes["transform_flip_h"] = lambda: sum(len(f) for f in A.standard_jpeg_transform_many(files, "flip_h", progressive=False))
+    if hasattr(A, "standard_jpeg_encode_many"):                  # the ragged encoder over the same frames, already on the device
+        frames = [xd[i] for i in range(a.batch)]
+        many = lambda **kw: sum(len(f) for f in A.standard_jpeg_encode_many(frames, 75, subsampling=a.subsampling, **kw))  # noqa: E731
+        routes["encode_many_annexk"] = lambda: many()
+        routes["encode_many_optimize"] = lambda: many(optimize=True)
+        routes["encode_many_progressive"] = lambda: many(progressive=True)
+        if "restart_marker_rows" in inspect.signature(A.standard_jpeg_encode_many).parameters:      # restart markers: one per MCU row
+            rows = dict(restart_marker_rows=1)
+            routes["encode_many_annexk_rows1"] = lambda: many(**rows)
+            routes["encode_many_optimize_rows1"] = lambda: many(optimize=True, **rows)
+            routes["encode_many_progressive_rows1"] = lambda: many(progressive=True, **rows)
+            routes["transcode_optimize_rows1"] = lambda: sum(len(f) for f in A.standard_jpeg_transcode_many(files, progressive=False, **rows))
+            routes["transcode_progressive_rows1"] = lambda: sum(len(f) for f in A.standard_jpeg_transcode_many(files, progressive=True, **rows))
     return routes, sum(len(f) for f in files)
 
 
@@ -119,7 +133,9 @@ def transcode(a):
     """--transcode: --batch natural 4K files (quality 75, --subsampling, plain baseline) through standard_jpeg_transcode_many to
     optimised baseline and to progressive files, beside the lossy route over pixels on the same files (standard_jpeg_decode_many, then
     standard_jpeg_many(optimize=True / progressive=True)) and the plain standard_jpeg_batch / standard_jpeg_decode_many calls; the
-    routes transform_rot90 and transform_flip_h are standard_jpeg_transform_many over the same files (baseline output).  With
+    routes transform_rot90 and transform_flip_h are standard_jpeg_transform_many over the same files (baseline output); encode_many_*
+    are standard_jpeg_encode_many (the ragged encoder) over the same frames as device tensors, under the Annex K tables, optimised and
+    progressive, and the *_rows1 routes are the ragged encoder and the transcoder with restart_marker_rows=1.  With
     --ab ROOT a second process imports the package of the checkout at ROOT (its library built there) and runs the routes it has; the
     two sides alternate route by route inside every round, so both see the same machine state.  One warm-up round, then the medians
     of --repeats rounds, with the bytes of the sources and of the outputs.  --routes a,b restricts the run (for a profiler)."""

@@ -2,7 +2,8 @@
 markers -- Pillow's default, decoded by the self-synchronising subsequences -- and (b) with restart_marker_rows=1, against Pillow
 decoding them on a thread pool and uploading its pixels.
 
-    python tools/bench_jpeg_decode.py [--batch 64] [--repeats 3] [--threads 16] [--subseq-bits N] [--progressive] [--scale S] [--out FILE]
+    python tools/bench_jpeg_decode.py [--batch 64] [--repeats 3] [--threads 16] [--subseq-bits N] [--progressive] [--scale S]
+                                      [--transcoded] [--no-pillow] [--out FILE]
 
 --progressive writes the same files with progressive=True and decodes them with standard_jpeg_decode_many(..., progressive=True)
 (csrc/jpegprog.hip: one thread per restart segment and dependency level, so the files without restart markers are a serial decode
@@ -10,6 +11,10 @@ per scan and the restart-per-row files show what the kernels do when the format 
 
 --scale 2 / 4 / 8 decodes at that fraction of the size on both sides: standard_jpeg_decode_many(..., scale=S) (csrc/jpegdec.hip
 k_jd_scaled) against Pillow after im.draft("RGB", (W // S, H // S)); the gigapixels per second still count the files' full-size pixels.
+
+--transcoded adds a third case: the files without restart markers put through standard_jpeg_transcode_many(...,
+restart_marker_rows=1) (progressive output with --progressive) -- the lossless way to make an archive cheap to decode -- with the time
+of that transcode; --no-pillow leaves the CPU side's timing out.
 
 "gpu" is standard_jpeg_decode_many: host header parsing, one copy of the scans, every device stage, the per-file status read-back;
 it ends with device uint8 [H, W, 3] tensors.  "pillow" is np.asarray(Image.open(buf).convert("RGB")) per file on --threads threads, then
@@ -47,6 +52,8 @@ def main():
     ap.add_argument("--subseq-bits", type=int, default=0, help="jpegdec_subseq_bits (0: the library's default)")
     ap.add_argument("--progressive", action="store_true", help="progressive files through csrc/jpegprog.hip")
     ap.add_argument("--scale", type=int, default=1, choices=(1, 2, 4, 8), help="decode at 1 / scale of the size (Pillow: Image.draft)")
+    ap.add_argument("--transcoded", action="store_true", help="also: the no-restart files transcoded with restart_marker_rows=1")
+    ap.add_argument("--no-pillow", action="store_true")
     ap.add_argument("--out")
     a = ap.parse_args()
     x = images(a.batch)
@@ -75,10 +82,17 @@ def main():
         how = dict(scale=a.scale) if a.scale != 1 else {}
         return A.standard_jpeg_decode_many(files, progressive=True, **how) if a.progressive else A.standard_jpeg_decode_many(files, **how)
 
-    for name, opts in (("no_restarts", {}), ("restart_rows_1", {"restart_marker_rows": 1})):
-        if a.progressive:
-            opts = dict(opts, progressive=True)
-        files = list(pool.map(lambda i: save(i, opts), range(a.batch)))
+    plain, extra = None, {}
+    for name, opts in (("no_restarts", {}), ("restart_rows_1", {"restart_marker_rows": 1})) + ((("transcoded_rows_1", None),) if a.transcoded else ()):
+        if opts is None:                                 # the lossless route: the first case's files, transcoded
+            again = lambda: A.standard_jpeg_transcode_many(plain, progressive=a.progressive, restart_marker_rows=1)  # noqa: E731
+            files = again()
+            extra = {"transcode_ms": timed(again, a.repeats) * 1e3}
+        else:
+            if a.progressive:
+                opts = dict(opts, progressive=True)
+            files = list(pool.map(lambda i: save(i, opts), range(a.batch)))
+            plain = plain or files
         got = decode(files)
         rounds = S.decode_sync_rounds()
         for f, g in zip(files, got):
@@ -89,12 +103,14 @@ def main():
         def pillow():
             px = np.stack(list(pool.map(pil_load, files)))
             return torch.from_numpy(px).to("cuda:0")
-        tp = timed(pillow, a.repeats)
         mb = sum(len(f) for f in files) / 1e6
-        res["cases"][name] = {"file_mb": mb, "sync_rounds": rounds, "gpu_ms": tg * 1e3, "gpu_gps": gp / tg, "pillow_upload_ms": tp * 1e3,
-                              "pillow_upload_gps": gp / tp, "speedup": tp / tg}
-        print(f"{name}: {mb:.1f} MB of files, {rounds} sync rounds; GPU {tg * 1e3:.1f} ms ({gp / tg:.2f} GP/s), Pillow on {a.threads} threads "
-              f"+ upload {tp * 1e3:.1f} ms ({gp / tp:.2f} GP/s): x{tp / tg:.2f}", flush=True)
+        res["cases"][name] = {"file_mb": mb, "sync_rounds": rounds, "gpu_ms": tg * 1e3, "gpu_gps": gp / tg, **extra}
+        print(f"{name}: {mb:.1f} MB of files, {rounds} sync rounds; GPU {tg * 1e3:.1f} ms ({gp / tg:.2f} GP/s)", flush=True)
+        if a.no_pillow:
+            continue
+        tp = timed(pillow, a.repeats)
+        res["cases"][name].update({"pillow_upload_ms": tp * 1e3, "pillow_upload_gps": gp / tp, "speedup": tp / tg})
+        print(f"{name}: Pillow on {a.threads} threads + upload {tp * 1e3:.1f} ms ({gp / tp:.2f} GP/s): x{tp / tg:.2f}", flush=True)
     pool.shutdown()
     line = json.dumps(res)
     print(line)
