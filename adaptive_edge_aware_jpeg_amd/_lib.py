@@ -282,6 +282,14 @@ SIGNATURES = {
     "aej_jfif_transform_batch_rst": (_I, [_P, _P, _I, _P, _U64, _P, _P, _P, _I, _P, _U64, _P, _P, _I, _P, _I, _I, _I, _P, _U64, _P, _P, _P, _P, _P, _P,
                                           _U64]),
     "aej_jfif_headers_rst_host": (_I, [_I, _I, _I, _I, _I, _I, _I, _P, _I]),
+    "aej_jpegdec_parse_host_440": (_I, [_P, _U64, _P, _P, _I, _I]),
+    "aej_jpegprog_parse_host_440": (_I, [_P, _U64, _P, _P, _I, _P, _I, _I]),
+    "aej_jfif_transform_geometry_host_440": (_I, [_I, _I, _I, _I, _I, _I, _I, _P]),
+    "aej_jfif_transform_coefs_host_440": (_I64, [_I, _I, _I, _I, _I, _I, _I, _P, _I64, _P, _I64]),
+    "aej_jfif_transform_headers_host_440": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I]),
+    "aej_jfif_transform_workspace_bytes_440": (_U64, [_P, _P, _I, _P, _P, _I, _I, _P, _I, _I, _I, _I]),
+    "aej_jfif_transform_batch_440": (_I, [_P, _P, _I, _P, _U64, _P, _P, _P, _I, _P, _U64, _P, _P, _I, _P, _I, _I, _I, _I, _P, _U64, _P, _P, _P, _P, _P,
+                                          _P, _U64]),
     "aej_jfif_restart_map_host": (_I, [_I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I64, _P, _I64, _P]),
     "aej_resample_taps_host": (_I, [_I, ctypes.c_float, ctypes.c_float, _I, _I, _P, _P, _I64]),
     "aej_resample_workspace_bytes": (_U64, [_P, _P, _I]),

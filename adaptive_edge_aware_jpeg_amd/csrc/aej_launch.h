@@ -212,7 +212,7 @@ struct JfifGeom {
     long long n_mcu, nblk;             // per image; nblk = (hs * vs + 2) * n_mcu, dummy luma blocks included (one component: n_mcu)
     long long stream_words, n_chunks;  // per (quality, image): unstuffed scan words, 64-byte stuffing chunks
     long long plane_bytes;             // per (quality, image): Y, Cb, Cr sample planes
-    int hs, vs, opt, ncomp;            // luma sampling factors (2 x 2, 2 x 1, 1 x 1; chroma is 1 x 1); Huffman tables per file;
+    int hs, vs, opt, ncomp;            // luma sampling factors (2 x 2, 2 x 1, 1 x 1, 1 x 2; chroma is 1 x 1); Huffman tables per file;
                                        // components: 3, or 1 (grey: hs = vs = 1, an MCU is one block, no dummies; entropy chains only)
     int R, rst_pad_;                   // restart interval of the baseline scan in MCUs (jfif_geom_restart; 0: none, requires opt otherwise)
     long long niv;                     // its intervals, ceil(n_mcu / R) (0 without restarts)
@@ -233,6 +233,9 @@ struct JfifBufs {
 // ss: Pillow's subsampling code (0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0); opt: optimise the Huffman tables per file; ncomp: 3, or 1 (ss is
 // then not looked at)
 bool jfif_geom(int B, int H, int W, int nq, JfifGeom &g, int ss = 2, int opt = 0, int ncomp = 3);
+// the same from luma sampling factors: 1 x 1, 2 x 1, 2 x 2 and 1 x 2 (4:4:0, which no subsampling code names: the entropy chains of the
+// transcoder and the transforms alone take it -- launch_jfif_coefs, _encode and _recon refuse such a geometry)
+bool jfif_geom_sampled(int B, int H, int W, int nq, JfifGeom &g, int hs, int vs, int opt = 0, int ncomp = 3);
 // after jfif_geom: the restart interval of Pillow's restart_marker_blocks / restart_marker_rows (jr_interval, jfif_restart_core.h).
 // false: a value outside 0..65535, or an interval with opt = 0 (the Annex K per-block stream bound has no room for the padding)
 bool jfif_geom_restart(JfifGeom &g, int blocks, int rows);
@@ -314,19 +317,20 @@ int jfifprog_scan_device(hipStream_t st, const short *coefs_host, long long n, i
 #include "jpegdec_core.h"
 
 namespace aej {
-struct JdBufSizes { long long chunks, segs, slots, blocks, clean, planes, px, grp[3]; };      // totals over the files of one call (grp: JdFile::grp_base)
+struct JdBufSizes { long long chunks, segs, slots, blocks, clean, planes, px, grp[3], grp440[3]; };      // totals over the files of one call (grp, grp440: JdFile::grp_base, ::grp440_base)
 struct JdBufs {
     JdFile *files; aej_jpegdec_desc *descs; int *last_change;      // one upload: files, descriptors, the "last round that changed" word
     int *cnt; long long *pre, *clean_len; JdSeg *segs; unsigned char *clean; JdSlots sl; short *coef; unsigned char *planes;
 };
 struct JdHuffSrc { bool defined = false; unsigned char bits[17] = {}; unsigned char vals[256] = {}; int count = 0; };      // one DHT table
 bool jd_build_huff(const JdHuffSrc &s, aej_jpegdec_huff &h);                                                              // jpegparse.hip
-int jpegdec_parse(const unsigned char *data, unsigned long long n, aej_jpegdec_desc &d, std::string &msg);             // jpegparse.hip
+// allow440 (both parsers): luma sampled 1 x 2 over 1 x 1 chroma is accepted beside 4:4:4, 4:2:2 and 4:2:0
+int jpegdec_parse(const unsigned char *data, unsigned long long n, aej_jpegdec_desc &d, std::string &msg, bool allow440 = false);      // jpegparse.hip
 // did one of the parsers write this frame?  D: aej_jpegdec_desc or aej_jpegprog_frame -- what the layouts below size buffers from
 template <class D>
 bool jpeg_frame_ok(const D &e)
 {
-    const bool color = e.ncomp == 3 && ((e.hs == 1 && e.vs == 1) || (e.hs == 2 && (e.vs == 1 || e.vs == 2)));
+    const bool color = e.ncomp == 3 && ((e.hs == 1 && (e.vs == 1 || e.vs == 2)) || (e.hs == 2 && (e.vs == 1 || e.vs == 2)));      // 1 x 2: the _440 parsers'
     if (!(color || (e.ncomp == 1 && e.hs == 1 && e.vs == 1))) return false;
     if (e.width < 1 || e.height < 1 || e.width > 65535 || e.height > 65535) return false;
     if (e.mcux != (e.width + 8 * e.hs - 1) / (8 * e.hs) || e.mcuy != (e.height + 8 * e.vs - 1) / (8 * e.vs)) return false;
@@ -373,7 +377,7 @@ inline void jp_scan_units(const aej_jpegprog_frame &f, int ncomp, int comp0, int
     else { ux = (f.width + 7) / 8; uy = (f.height + 7) / 8; }
 }
 int jpegprog_parse(const unsigned char *data, unsigned long long n, aej_jpegprog_frame &f, std::vector<aej_jpegprog_scan> &scans,
-                   std::string &msg);                                                                                  // jpegparse.hip
+                   std::string &msg, bool allow440 = false);                                                           // jpegparse.hip
 bool jpegprog_layout(const aej_jpegprog_frame *frames, const aej_jpegprog_scan *scans, int n, JpLayout &y, const int *shifts = nullptr);
 unsigned long long jpegprog_blob(const JpLayout &y, std::vector<unsigned char> *out);
 unsigned long long jpegprog_carve(void *base, const JpLayout &y, JpBufs &w);
@@ -432,7 +436,7 @@ JtSource jfiftrans_transformed(const JtSource &s, const JxGeom &g);
 // one transform code per file.  -> -1, or the first file that does not fit: *why (may be NULL) gets jx_geom's answer, kJxBadArg for
 // descriptors that disagree.
 int jfiftrans_plan(const std::vector<JtSource> &src, const std::vector<long long> &n_blocks, bool prog, const int *xf, int trim, JtPlan &plan,
-                   int *why, int rst_blocks = 0, int rst_rows = 0);
+                   int *why, int rst_blocks = 0, int rst_rows = 0, bool allow440 = false);
 // the pieces of a plan, shared with the ragged encoder (jfifmany.hip).  Before them: plan.files sized, plan.prog set.
 // the group of one output geometry, made on first use (NULL: a geometry jfif_geom refuses)
 JtGroup *jfiftrans_group(JtPlan &plan, int H, int W, int hs, int vs, int ncomp = 3);

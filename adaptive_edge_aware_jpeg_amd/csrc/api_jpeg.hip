@@ -197,13 +197,24 @@ extern "C" int aej_test_jfif_prog_scan(aej_ctx *ctx, const int16_t *coefs_host, 
 }
 
 // ---- baseline JPEG files decoded on the device (jpegdec.hip; the marker walk: jpegparse.hip) --------------------------------------------------------------------------
-extern "C" int aej_jpegdec_parse_host(const uint8_t *data_host, uint64_t nbytes, aej_jpegdec_desc *desc_host, char *msg, int msg_capacity)
+static int jd_parse_host(const uint8_t *data_host, uint64_t nbytes, aej_jpegdec_desc *desc_host, char *msg, int msg_capacity, int layout_440)
 {
-    if (!desc_host) return AEJ_ERR_ARG;
+    if (!desc_host || (layout_440 != 0 && layout_440 != 1)) return AEJ_ERR_ARG;
     std::string m;
-    const int rc = jpegdec_parse(data_host, nbytes, *desc_host, m);
+    const int rc = jpegdec_parse(data_host, nbytes, *desc_host, m, layout_440 != 0);
     copy_msg(m, msg, msg_capacity);
     return rc;
+}
+
+extern "C" int aej_jpegdec_parse_host(const uint8_t *data_host, uint64_t nbytes, aej_jpegdec_desc *desc_host, char *msg, int msg_capacity)
+{
+    return jd_parse_host(data_host, nbytes, desc_host, msg, msg_capacity, 0);
+}
+
+extern "C" int aej_jpegdec_parse_host_440(const uint8_t *data_host, uint64_t nbytes, aej_jpegdec_desc *desc_host, char *msg, int msg_capacity,
+                                          int layout_440)
+{
+    return jd_parse_host(data_host, nbytes, desc_host, msg, msg_capacity, layout_440);
 }
 
 // ---- what a call's offsets must satisfy (shared by the decoders and the transcoder) -------------------------------------------------------
@@ -363,19 +374,31 @@ extern "C" int64_t aej_jpegdec_sync_rounds(aej_ctx *ctx)
 }
 
 // ---- progressive JPEG files decoded on the device (jpegprog.hip) ----------------------------------------------------------------------
-extern "C" int aej_jpegprog_parse_host(const uint8_t *data_host, uint64_t nbytes, aej_jpegprog_frame *frame_host, aej_jpegprog_scan *scans_host,
-                                       int scan_capacity, char *msg, int msg_capacity)
+static int jp_parse_host(const uint8_t *data_host, uint64_t nbytes, aej_jpegprog_frame *frame_host, aej_jpegprog_scan *scans_host, int scan_capacity,
+                         char *msg, int msg_capacity, int layout_440)
 {
-    if (!frame_host) return AEJ_ERR_ARG;
+    if (!frame_host || (layout_440 != 0 && layout_440 != 1)) return AEJ_ERR_ARG;
     std::string m;
     std::vector<aej_jpegprog_scan> scans;
-    int rc = jpegprog_parse(data_host, nbytes, *frame_host, scans, m);
+    int rc = jpegprog_parse(data_host, nbytes, *frame_host, scans, m, layout_440 != 0);
     if (rc == 0 && scans_host) {
         if (scan_capacity < (int)scans.size()) { rc = AEJ_ERR_CAPACITY; m = "scan capacity below the file's " + std::to_string(scans.size()) + " scans"; }
         else memcpy(scans_host, scans.data(), sizeof(aej_jpegprog_scan) * scans.size());
     }
     copy_msg(m, msg, msg_capacity);
     return rc;
+}
+
+extern "C" int aej_jpegprog_parse_host(const uint8_t *data_host, uint64_t nbytes, aej_jpegprog_frame *frame_host, aej_jpegprog_scan *scans_host,
+                                       int scan_capacity, char *msg, int msg_capacity)
+{
+    return jp_parse_host(data_host, nbytes, frame_host, scans_host, scan_capacity, msg, msg_capacity, 0);
+}
+
+extern "C" int aej_jpegprog_parse_host_440(const uint8_t *data_host, uint64_t nbytes, aej_jpegprog_frame *frame_host, aej_jpegprog_scan *scans_host,
+                                           int scan_capacity, char *msg, int msg_capacity, int layout_440)
+{
+    return jp_parse_host(data_host, nbytes, frame_host, scans_host, scan_capacity, msg, msg_capacity, layout_440);
 }
 
 static uint64_t jpegprog_workspace(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n, const int *scales_host)
@@ -488,8 +511,9 @@ static bool rst_ok(int blocks, int rows) { return blocks >= 0 && blocks <= kJrMa
 
 static int jt_layout(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs, int n_base, const aej_jpegprog_frame *frames,
                      const aej_jpegprog_scan *pscans, int n_prog, const uint16_t *density, int progressive, const int32_t *xf, int trim, int rst_blocks,
-                     int rst_rows, JtCall &c)
+                     int rst_rows, JtCall &c, int allow440 = 0)
 {
+    if (allow440 != 0 && allow440 != 1) return fail(ctx, AEJ_ERR_ARG, "%s: layout_440 %d (0 or 1)", fn, allow440);
     if (trim != 0 && trim != 1) return fail(ctx, AEJ_ERR_ARG, "%s: trim %d (0 or 1)", fn, trim);
     if (!rst_ok(rst_blocks, rst_rows)) return fail(ctx, AEJ_ERR_ARG, "%s: restart_blocks %d, restart_rows %d (0 .. 65535)", fn, rst_blocks, rst_rows);
     if (n_base < 0 || n_prog < 0 || n_base + n_prog < 1 || (long long)n_base + n_prog > 65535 || (progressive != 0 && progressive != 1))
@@ -506,14 +530,16 @@ static int jt_layout(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs
         const bool ok = i < n_base ? jt_source_ok(descs[i]) : jt_source_ok(frames[i - n_base]);
         if (!ok) return fail(ctx, AEJ_ERR_UNSUPPORTED, "%s: file %d: three components or one, with 8-bit quantisation tables, required", fn, i);
         if (i < n_base) jfiftrans_source(descs[i], c.src[i]); else jfiftrans_source(frames[i - n_base], c.src[i]);
+        if (!allow440 && c.src[i].ncomp == 3 && c.src[i].hs == 1 && c.src[i].vs == 2)
+            return fail(ctx, AEJ_ERR_UNSUPPORTED, "%s: file %d: a 4:4:0 file, which the entries with layout_440 take", fn, i);
         nblk[i] = i < n_base ? c.files[i].n_blocks : c.y.ffiles[i - n_base].n_blocks;
         if (density) { c.src[i].units = density[3 * i] & 255; c.src[i].xdensity = density[3 * i + 1]; c.src[i].ydensity = density[3 * i + 2]; }
     }
     int why = kJxOk;
-    const int bad = jfiftrans_plan(c.src, nblk, progressive != 0, xf, trim, c.plan, &why, rst_blocks, rst_rows);
+    const int bad = jfiftrans_plan(c.src, nblk, progressive != 0, xf, trim, c.plan, &why, rst_blocks, rst_rows, allow440 != 0);
     if (bad < 0) return 0;
     if (why == kJxLayout)
-        return fail(ctx, AEJ_ERR_UNSUPPORTED, "%s: file %d: a transposing transform of a 4:2:2 file would be a 4:4:0 file, which is not built", fn, bad);
+        return fail(ctx, AEJ_ERR_UNSUPPORTED, "%s: file %d: a transposing transform of a 4:2:2 file would be a 4:4:0 file, which is not built", fn, bad);      // (the entries with layout_440 write it)
     if (why == kJxNotPerfect)
         return fail(ctx, AEJ_ERR_ARG, "%s: file %d: transform %d mirrors an axis that is not a whole number of MCUs (trim = 1 drops the partial ones)", fn,
                     bad, xf ? xf[bad] : 0);
@@ -535,15 +561,17 @@ static JtWorkspace jt_carve(void *workspace, int n_base, int n_prog, JtCall &c)
 }
 
 static int jt_headers(const aej_jpegdec_desc *desc_host, const aej_jpegprog_frame *frame_host, const uint16_t *density3_host, int progressive,
-                      int transform, int trim, uint8_t *out_host, int capacity)
+                      int transform, int trim, uint8_t *out_host, int capacity, int allow440 = 0)
 {
+    if (allow440 != 0 && allow440 != 1) return AEJ_ERR_ARG;
     if ((!desc_host) == (!frame_host) || !out_host || capacity < 0 || (progressive != 0 && progressive != 1) || (trim != 0 && trim != 1)) return AEJ_ERR_ARG;
     if (!(desc_host ? jt_source_ok(*desc_host) : jt_source_ok(*frame_host))) return AEJ_ERR_UNSUPPORTED;
     JtSource s;
     if (desc_host) jfiftrans_source(*desc_host, s); else jfiftrans_source(*frame_host, s);
     if (density3_host) { s.units = density3_host[0] & 255; s.xdensity = density3_host[1]; s.ydensity = density3_host[2]; }
     JxGeom x;
-    const int rc = jx_geom(s.height, s.width, s.hs, s.vs, transform, trim, x, s.ncomp);
+    if (!allow440 && s.ncomp == 3 && s.hs == 1 && s.vs == 2) return AEJ_ERR_UNSUPPORTED;
+    const int rc = jx_geom(s.height, s.width, s.hs, s.vs, transform, trim, x, s.ncomp, allow440 != 0);
     if (rc != kJxOk) return rc == kJxLayout ? AEJ_ERR_UNSUPPORTED : AEJ_ERR_ARG;
     const int n = jfiftrans_prefix_host(jfiftrans_transformed(s, x), progressive != 0, out_host, capacity);
     return n < 0 ? AEJ_ERR_CAPACITY : n;
@@ -561,10 +589,17 @@ extern "C" int aej_jfif_transform_headers_host(const aej_jpegdec_desc *desc_host
     return jt_headers(desc_host, frame_host, density3_host, progressive, transform, trim, out_host, capacity);
 }
 
-extern "C" int aej_jfif_transform_geometry_host(int H, int W, int hs, int vs, int transform, int trim, int32_t *out4_host)
+extern "C" int aej_jfif_transform_headers_host_440(const aej_jpegdec_desc *desc_host, const aej_jpegprog_frame *frame_host, const uint16_t *density3_host,
+                                                   int progressive, int transform, int trim, int layout_440, uint8_t *out_host, int capacity)
+{
+    return jt_headers(desc_host, frame_host, density3_host, progressive, transform, trim, out_host, capacity, layout_440);
+}
+
+static int jt_geometry_host(int H, int W, int hs, int vs, int transform, int trim, int32_t *out4_host, int allow440)
 {
     JxGeom x;
-    const int rc = jx_geom(H, W, hs, vs, transform, trim != 0, x);
+    if (allow440 != 0 && allow440 != 1) return AEJ_ERR_ARG;
+    const int rc = jx_geom(H, W, hs, vs, transform, trim != 0, x, 3, allow440 != 0);
     if ((trim != 0 && trim != 1) || rc == kJxBadArg) return AEJ_ERR_ARG;
     if (rc == kJxLayout) return AEJ_ERR_UNSUPPORTED;
     if (rc != kJxOk) return rc == kJxNotPerfect ? AEJ_JFIF_TRANSFORM_NOT_PERFECT : AEJ_JFIF_TRANSFORM_TRIMS_TO_ZERO;
@@ -572,13 +607,23 @@ extern "C" int aej_jfif_transform_geometry_host(int H, int W, int hs, int vs, in
     return 0;
 }
 
+extern "C" int aej_jfif_transform_geometry_host(int H, int W, int hs, int vs, int transform, int trim, int32_t *out4_host)
+{
+    return jt_geometry_host(H, W, hs, vs, transform, trim, out4_host, 0);
+}
+
+extern "C" int aej_jfif_transform_geometry_host_440(int H, int W, int hs, int vs, int transform, int trim, int layout_440, int32_t *out4_host)
+{
+    return jt_geometry_host(H, W, hs, vs, transform, trim, out4_host, layout_440);
+}
+
 static int64_t jt_coefs_host(int H, int W, int hs, int vs, int nc, int transform, int trim, const int16_t *src_host, int64_t src_blocks,
-                             int16_t *dst_host, int64_t dst_blocks)
+                             int16_t *dst_host, int64_t dst_blocks, int allow440 = 0)
 {
     JxGeom x;
-    const int rc = aej_jfif_transform_geometry_host(H, W, hs, vs, transform, trim, nullptr);
+    const int rc = jt_geometry_host(H, W, hs, vs, transform, trim, nullptr, allow440);
     if (rc) return rc;
-    jx_geom(H, W, hs, vs, transform, trim, x, nc);
+    jx_geom(H, W, hs, vs, transform, trim, x, nc, allow440 != 0);
     if (!src_host && !dst_host) return x.n_out;              // a size query
     if (!src_host || !dst_host || src_blocks != x.n_src) return AEJ_ERR_ARG;
     if (dst_blocks < x.n_out) return AEJ_ERR_CAPACITY;
@@ -592,6 +637,12 @@ extern "C" int64_t aej_jfif_transform_coefs_host(int H, int W, int hs, int vs, i
     return jt_coefs_host(H, W, hs, vs, 3, transform, trim, src_host, src_blocks, dst_host, dst_blocks);
 }
 
+extern "C" int64_t aej_jfif_transform_coefs_host_440(int H, int W, int hs, int vs, int transform, int trim, int layout_440, const int16_t *src_host,
+                                                     int64_t src_blocks, int16_t *dst_host, int64_t dst_blocks)
+{
+    return jt_coefs_host(H, W, hs, vs, 3, transform, trim, src_host, src_blocks, dst_host, dst_blocks, layout_440);
+}
+
 extern "C" int64_t aej_jfif_transform_coefs_grey_host(int H, int W, int transform, int trim, const int16_t *src_host, int64_t src_blocks,
                                                       int16_t *dst_host, int64_t dst_blocks)
 {
@@ -602,12 +653,12 @@ extern "C" int64_t aej_jfif_transform_coefs_grey_host(int H, int W, int transfor
 
 static uint64_t jt_workspace_bytes(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs_host, int n_base, const aej_jpegprog_frame *frames_host,
                                    const aej_jpegprog_scan *pscans_host, int n_prog, int progressive, const int32_t *xf, int trim, int rst_blocks,
-                                   int rst_rows)
+                                   int rst_rows, int allow440 = 0)
 {
     if (!ctx || (n_base > 0 && !descs_host) || (n_prog > 0 && (!frames_host || !pscans_host))) return 0;
     JtCall c;
     const std::string keep = ctx->err;
-    const int rc = jt_layout(ctx, fn, descs_host, n_base, frames_host, pscans_host, n_prog, nullptr, progressive, xf, trim, rst_blocks, rst_rows, c);
+    const int rc = jt_layout(ctx, fn, descs_host, n_base, frames_host, pscans_host, n_prog, nullptr, progressive, xf, trim, rst_blocks, rst_rows, c, allow440);
     ctx->err = keep;                                         // a size query leaves the context's last error alone
     return rc ? 0 : jt_carve(nullptr, n_base, n_prog, c).bytes;
 }
@@ -636,6 +687,15 @@ extern "C" uint64_t aej_jfif_transform_workspace_bytes_rst(aej_ctx *ctx, const a
                               restart_rows);
 }
 
+extern "C" uint64_t aej_jfif_transform_workspace_bytes_440(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base,
+                                                           const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *pscans_host, int n_prog,
+                                                           int progressive, const int32_t *transforms_host, int trim, int restart_blocks,
+                                                           int restart_rows, int layout_440)
+{
+    return jt_workspace_bytes(ctx, __func__, descs_host, n_base, frames_host, pscans_host, n_prog, progressive, transforms_host, trim, restart_blocks,
+                              restart_rows, layout_440);
+}
+
 extern "C" uint64_t aej_jfif_transform_workspace_bytes(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base,
                                                        const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *pscans_host, int n_prog,
                                                        int progressive, const int32_t *transforms_host, int trim)
@@ -647,14 +707,15 @@ static int jt_batch(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs_
                     const int64_t *scan_offsets_host, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *pscans_host, int n_prog,
                     const uint8_t *data, uint64_t data_bytes, const int64_t *data_offsets_host, const uint16_t *density_host, int progressive,
                     const int32_t *xf, int trim, int rst_blocks, int rst_rows, uint8_t *out, uint64_t out_capacity, int64_t *offsets,
-                    int64_t *lengths, uint64_t *total_host, int32_t *status, int32_t *n_groups_host, void *workspace, uint64_t workspace_bytes)
+                    int64_t *lengths, uint64_t *total_host, int32_t *status, int32_t *n_groups_host, void *workspace, uint64_t workspace_bytes,
+                    int allow440 = 0)
 {
     AEJ_TRY(enter(ctx, fn));
     if ((n_base > 0 && (!descs_host || !scans || !scan_offsets_host)) || (n_prog > 0 && (!frames_host || !pscans_host || !data || !data_offsets_host)) ||
         !offsets || !lengths || !total_host || !status || !workspace)
         return null_buffer(ctx, fn);
     JtCall c;
-    AEJ_TRY(jt_layout(ctx, fn, descs_host, n_base, frames_host, pscans_host, n_prog, density_host, progressive, xf, trim, rst_blocks, rst_rows, c));
+    AEJ_TRY(jt_layout(ctx, fn, descs_host, n_base, frames_host, pscans_host, n_prog, density_host, progressive, xf, trim, rst_blocks, rst_rows, c, allow440));
     for (int i = 0; i < n_base; i++) AEJ_TRY(jpegdec_scan_offset(ctx, fn, descs_host[i], i, scans_bytes, scan_offsets_host[i], c.files[i]));
     AEJ_TRY(jpegprog_scan_offsets(ctx, fn, c.y, data_bytes, data_offsets_host));
     const JtWorkspace ws = jt_carve(workspace, n_base, n_prog, c);
@@ -735,6 +796,19 @@ extern "C" int aej_jfif_transform_batch_rst(aej_ctx *ctx, const aej_jpegdec_desc
     return jx_batch(ctx, __func__, descs_host, n_base, scans, scans_bytes, scan_offsets_host, frames_host, pscans_host, n_prog, data, data_bytes,
                     data_offsets_host, density_host, progressive, transforms_host, trim, restart_blocks, restart_rows, out, out_capacity, offsets,
                     lengths, total_host, status, n_groups_host, workspace, workspace_bytes);
+}
+
+extern "C" int aej_jfif_transform_batch_440(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base, const uint8_t *scans, uint64_t scans_bytes,
+                                            const int64_t *scan_offsets_host, const aej_jpegprog_frame *frames_host,
+                                            const aej_jpegprog_scan *pscans_host, int n_prog, const uint8_t *data, uint64_t data_bytes,
+                                            const int64_t *data_offsets_host, const uint16_t *density_host, int progressive,
+                                            const int32_t *transforms_host, int trim, int restart_blocks, int restart_rows, int layout_440,
+                                            uint8_t *out, uint64_t out_capacity, int64_t *offsets, int64_t *lengths, uint64_t *total_host,
+                                            int32_t *status, int32_t *n_groups_host, void *workspace, uint64_t workspace_bytes)
+{
+    return jt_batch(ctx, __func__, descs_host, n_base, scans, scans_bytes, scan_offsets_host, frames_host, pscans_host, n_prog, data, data_bytes,
+                    data_offsets_host, density_host, progressive, transforms_host, trim, restart_blocks, restart_rows, out, out_capacity, offsets,
+                    lengths, total_host, status, n_groups_host, workspace, workspace_bytes, layout_440);
 }
 
 extern "C" int aej_jfif_transform_batch(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base, const uint8_t *scans, uint64_t scans_bytes,

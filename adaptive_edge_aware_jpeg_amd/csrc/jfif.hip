@@ -3,8 +3,8 @@
 // include/aej.h).  The arithmetic restates libjpeg's published integer algorithm; tests/jfif_reference.py and
 // tests/jfif_options_reference.py are the same algorithm in numpy and tests/test_gpu_jfif*.py pin both to Pillow's files byte for byte.
 //
-// Every kernel that walks blocks is a template over the luma sampling factors <HS, VS> (2 x 2, 2 x 1, 1 x 1): an MCU holds HS * VS luma
-// blocks in raster order, then Cb, then Cr.  The entropy stages that walk blocks (k_jfif_hist, k_jfif_count, k_jfif_emit) also take the
+// Every kernel that walks blocks is a template over the luma sampling factors <HS, VS> (2 x 2, 2 x 1, 1 x 1; the entropy stages also
+// <1, 2>, the 4:4:0 layout the transcoder and the transforms write): an MCU holds HS * VS luma blocks in raster order, then Cb, then Cr.  The entropy stages that walk blocks (k_jfif_hist, k_jfif_count, k_jfif_emit) also take the
 // component count NC (3, or 1): a one-component (grey) file is <1, 1, 1>, its scan is not interleaved, so its MCU is one block, the blocks
 // are the component's ceil(W / 8) x ceil(H / 8) in raster order and none is a dummy; it uses the luma tables (slots 0 and 1) alone, and
 // k_jfif_tables / k_jfif_annexk leave the chroma slots of such a segment untouched (JfifGeom::ncomp).  Colour, DCT, quantisation and
@@ -581,12 +581,19 @@ static const unsigned char kChromaBase[64] = { 17, 18, 24, 47, 99, 99, 99, 99, 1
 
 bool jfif_geom(int B, int H, int W, int nq, JfifGeom &g, int ss, int opt, int ncomp)
 {
-    if (B < 1 || nq < 1 || H < 1 || W < 1 || H > 65535 || W > 65535 || (long long)B * nq > 65535) return false;      // segments index grid.y
-    if (ncomp != 1 && ncomp != 3) return false;
     if (ncomp == 1) ss = 0;                                  // one component is sampled 1 x 1
     if (ss < 0 || ss > 2) return false;
+    return jfif_geom_sampled(B, H, W, nq, g, ss == 0 ? 1 : 2, ss == 2 ? 2 : 1, opt, ncomp);
+}
+
+bool jfif_geom_sampled(int B, int H, int W, int nq, JfifGeom &g, int hs, int vs, int opt, int ncomp)
+{
+    if (B < 1 || nq < 1 || H < 1 || W < 1 || H > 65535 || W > 65535 || (long long)B * nq > 65535) return false;      // segments index grid.y
+    if (ncomp != 1 && ncomp != 3) return false;
+    if (ncomp == 1) hs = vs = 1;
+    if (!((hs == 1 || hs == 2) && (vs == 1 || vs == 2))) return false;
     g.B = B; g.H = H; g.W = W; g.nq = nq;
-    g.hs = ss == 0 ? 1 : 2; g.vs = ss == 2 ? 2 : 1; g.opt = opt ? 1 : 0; g.ncomp = ncomp;
+    g.hs = hs; g.vs = vs; g.opt = opt ? 1 : 0; g.ncomp = ncomp;
     g.mcux = (W + 8 * g.hs - 1) / (8 * g.hs); g.mcuy = (H + 8 * g.vs - 1) / (8 * g.vs);
     g.ybx = (W + 7) / 8; g.yby = (H + 7) / 8;
     g.yw = 8 * g.hs * g.mcux; g.yh = 8 * g.vs * g.mcuy;   // luma planes cover every MCU (dummy blocks are never written)
@@ -701,7 +708,7 @@ void jfif_params_host(int q, int H, int W, JfifParams &p, int ss, int ncomp, int
     }
     seg(0xC0, jfif_sof_bytes(ncomp == 1 ? 1 : 3) - 4);
     if (ncomp == 1) put({ 8, H >> 8, H & 255, W >> 8, W & 255, 1, 1, 0x11, 0 });
-    else put({ 8, H >> 8, H & 255, W >> 8, W & 255, 3, 1, ss == 0 ? 0x11 : ss == 1 ? 0x21 : 0x22, 0, 2, 0x11, 1, 3, 0x11, 1 });
+    else put({ 8, H >> 8, H & 255, W >> 8, W & 255, 3, 1, ss == 0 ? 0x11 : ss == 1 ? 0x21 : ss == 2 ? 0x22 : 0x12, 0, 2, 0x11, 1, 3, 0x11, 1 });      // 3: 4:4:0
     p.dht_off = n;
     const struct { int id; const unsigned char *t; int len; } dht[4] = {
         { 0x00, kDht_dc_luma, (int)sizeof kDht_dc_luma }, { 0x10, kDht_ac_luma, (int)sizeof kDht_ac_luma },
@@ -731,9 +738,17 @@ template <class F>
 static hipError_t jf_dispatch(const JfifGeom &g, F f)
 {
     if (g.ncomp == 1) return f(JfShape<1, 1, 1>{});
+    if (g.hs == 1 && g.vs == 2) return hipErrorInvalidValue;      // 4:4:0 has entropy chains alone (jf_dispatch_coded)
     if (g.hs == 1) return f(JfShape<1, 1, 3>{});
     if (g.vs == 1) return f(JfShape<2, 1, 3>{});
     return f(JfShape<2, 2, 3>{});
+}
+// the same for the entropy chains, which also take 4:4:0 (two luma blocks stacked in the MCU: the transcoder's and the transforms' outputs)
+template <class F>
+static hipError_t jf_dispatch_coded(const JfifGeom &g, F f)
+{
+    if (g.ncomp == 3 && g.hs == 1 && g.vs == 2) return f(JfShape<1, 2, 3>{});
+    return jf_dispatch(g, f);
 }
 
 // the stages from w.coef to the file lengths and offsets (k_jfif_quant has left the Annex K bit counts in w.lens)
@@ -772,12 +787,12 @@ static hipError_t jf_entropy(hipStream_t st, const JfifGeom &g, const JfifBufs &
 // entropy stages up to the lengths, and the scatter as a launch of its own once the caller has placed the files
 hipError_t launch_jfif_entropy(hipStream_t st, const JfifGeom &g, const JfifBufs &w, long long *lengths, long long *offsets)
 {
-    return jf_dispatch(g, [&](auto s) { return jf_entropy<s.hs, s.vs, s.nc>(st, g, w, lengths, offsets, false); });
+    return jf_dispatch_coded(g, [&](auto s) { return jf_entropy<s.hs, s.vs, s.nc>(st, g, w, lengths, offsets, false); });
 }
 
 hipError_t launch_jfif_entropy_annexk(hipStream_t st, const JfifGeom &g, const JfifBufs &w, long long *lengths, long long *offsets)
 {
-    return jf_dispatch(g, [&](auto s) { return jf_entropy<s.hs, s.vs, s.nc>(st, g, w, lengths, offsets, true); });
+    return jf_dispatch_coded(g, [&](auto s) { return jf_entropy<s.hs, s.vs, s.nc>(st, g, w, lengths, offsets, true); });
 }
 
 hipError_t launch_jfif_scatter(hipStream_t st, const JfifGeom &g, const JfifBufs &w, const long long *lengths, const long long *offsets,

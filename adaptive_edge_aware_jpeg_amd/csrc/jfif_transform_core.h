@@ -44,14 +44,15 @@ AEJ_HD inline bool jx_mirrors_x(int xf) { return xf == kJxFlipH || xf == kJxTran
 AEJ_HD inline bool jx_mirrors_y(int xf) { return xf == kJxFlipV || xf == kJxTransverse || xf == kJxRot180 || xf == kJxRot270; }
 
 // -> kJxOk and g, or why not.  Sampling: 1x1, 2x1 or 2x2 luma over 1x1 chroma; a transposed 2x1 would be 1x2 (4:4:0): kJxLayout.
-AEJ_HD inline int jx_geom(int H, int W, int hs, int vs, int xf, int trim, JxGeom &g, int nc = 3)
+// allow440: 1x2 is a source layout too (it transposes to 2x1), and a transposed 2x1 is written as 1x2.
+AEJ_HD inline int jx_geom(int H, int W, int hs, int vs, int xf, int trim, JxGeom &g, int nc = 3, bool allow440 = false)
 {
     if (H < 1 || W < 1 || H > 65535 || W > 65535 || xf < 0 || xf > 7 || (nc != 1 && nc != 3)) return kJxBadArg;
     if (nc == 1) hs = vs = 1;                                // the source's sampling factors mean nothing for one component
     g.nc = nc;
-    if (!((hs == 1 && vs == 1) || (hs == 2 && (vs == 1 || vs == 2)))) return kJxBadArg;
+    if (!((hs == 1 && vs == 1) || (hs == 2 && (vs == 1 || vs == 2)) || (allow440 && hs == 1 && vs == 2))) return kJxBadArg;
     g.xf = xf; g.t = jx_transposes(xf); g.mx = jx_mirrors_x(xf); g.my = jx_mirrors_y(xf);
-    if (g.t && hs != vs) return kJxLayout;
+    if (g.t && hs != vs && !allow440) return kJxLayout;
     g.sW = W; g.sH = H; g.shs = hs; g.svs = vs;
     g.smcux = (W + 8 * hs - 1) / (8 * hs); g.smcuy = (H + 8 * vs - 1) / (8 * vs);
     g.oW = g.t ? H : W; g.oH = g.t ? W : H; g.ohs = g.t ? vs : hs; g.ovs = g.t ? hs : vs;

@@ -213,7 +213,7 @@ JtGroup *jfiftrans_group(JtPlan &plan, int H, int W, int hs, int vs, int ncomp)
         if (c.g.H == H && c.g.W == W && c.g.hs == hs && c.g.vs == vs && c.g.ncomp == ncomp) return &c;
     JtGroup grp{};
     grp.foreign_ids = false;
-    if (!jfif_geom(1, H, W, 1, grp.g, hs == 1 ? 0 : vs == 1 ? 1 : 2, 1, ncomp)) return nullptr;
+    if (!jfif_geom_sampled(1, H, W, 1, grp.g, hs, vs, 1, ncomp)) return nullptr;
     plan.groups.push_back(grp);
     return &plan.groups.back();
 }
@@ -230,8 +230,8 @@ int jfiftrans_close(JtPlan &plan)
 {
     long long first = 0;
     for (JtGroup &c : plan.groups) {
-        const int ng = (int)c.files.size(), ss = c.g.hs == 1 ? 0 : c.g.vs == 1 ? 1 : 2;
-        if (!jfif_geom(1, c.g.H, c.g.W, ng, c.g, ss, 1, c.g.ncomp) || !jfif_geom_restart(c.g, plan.rst_blocks, plan.rst_rows) ||
+        const int ng = (int)c.files.size();
+        if (!jfif_geom_sampled(1, c.g.H, c.g.W, ng, c.g, c.g.hs, c.g.vs, 1, c.g.ncomp) || !jfif_geom_restart(c.g, plan.rst_blocks, plan.rst_rows) ||
             (plan.prog && !jfifprog_geom(c.g, c.p, plan.rst_blocks, plan.rst_rows)))
             return c.files[0];
         c.first = first;
@@ -243,7 +243,7 @@ int jfiftrans_close(JtPlan &plan)
 }
 
 int jfiftrans_plan(const std::vector<JtSource> &src, const std::vector<long long> &n_blocks, bool prog, const int *xf, int trim, JtPlan &plan,
-                   int *why, int rst_blocks, int rst_rows)
+                   int *why, int rst_blocks, int rst_rows, bool allow440)
 {
     auto refuse = [&](int i, int w) { if (why) *why = w; return i; };
     const int n = (int)src.size();
@@ -256,7 +256,7 @@ int jfiftrans_plan(const std::vector<JtSource> &src, const std::vector<long long
     for (int i = 0; i < n; i++) {
         const JtSource &s = src[i];
         JxGeom &x = plan.geom[i];
-        const int rc = jx_geom(s.height, s.width, s.hs, s.vs, xf ? xf[i] : kJxNone, trim, x, s.ncomp);
+        const int rc = jx_geom(s.height, s.width, s.hs, s.vs, xf ? xf[i] : kJxNone, trim, x, s.ncomp, allow440);
         if (rc != kJxOk) return refuse(i, rc);
         plan.transform |= x.xf != kJxNone;
         JtGroup *grp = jfiftrans_group(plan, x.oH, x.oW, x.ohs, x.ovs, s.ncomp);

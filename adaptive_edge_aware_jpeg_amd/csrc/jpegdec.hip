@@ -15,11 +15,15 @@
 //   k_jd_write      one thread per slot: the decode again, now storing coefficients and DC values (prefix + own differences); errors of
 //                   blocks the segment needs, and a segment that ends before its last block, go to the file's status
 //   k_jd_idct       one thread per real block: dequantise, islow IDCT, range limit -> sample planes
-//   k_jd_rgb        one thread per pixel: up-sampling (h2v2 / h2v1 fancy, replication when the chroma is <= 2 wide) and YCbCr -> RGB
+//   k_jd_rgb        one thread per pixel: up-sampling (h2v2 / h2v1 fancy, replication when the chroma is <= 2 wide; h1v2 fancy for a
+//                   4:4:0 file, at any width) and YCbCr -> RGB
 //   k_jd_scaled     files decoded at scale 2, 4 or 8 (Pillow's draft()) in the place of the two above: one workgroup per run of kJdRun
 //                   MCUs of one MCU row -- reduced IDCTs into LDS, colour into LDS, then the run's output rows stored as whole dwords.
 //                   No sample planes: 4:2:0 chroma comes out of a twice-as-large IDCT at luma resolution, and the one neighbour sample
 //                   the h2v1 filter of a 4:2:2 file needs on either side comes from the chroma blocks of the two adjacent MCUs
+//   k_jd_scaled_h1v2 the same for 4:4:0 files (luma 1 x 2), whose chroma IDCT stays at the luma block's size at every scale and is
+//                   up-sampled vertically: the neighbour rows the h1v2 filter needs come from the chroma blocks of the MCU rows above
+//                   and below the run (a vertical halo).  A kernel of its own, so that k_jd_scaled compiles as it did without it
 // Bounds: every index derives from the host-computed JdFile layout; a file's reads stay inside its scan and its clean stream, decode loops
 // are bounded by their subsequence's bits, and coefficient writes by the segment's block count.
 #include <string.h>
@@ -462,6 +466,85 @@ __global__ __launch_bounds__(kJdThreads) void k_jd_scaled(const JdFile *__restri
     }
 }
 
+// Scaled reconstruction of three-component files whose luma is sampled 1 x 2 (4:4:0): k_jd_scaled's plan -- workgroup `blockIdx.x` is run
+// g - grp440_base of its file, MCUs [g0, g0 + ng) of MCU row my -- with the MCU m columns by 2m rows of output.  jd_chroma_idct_size gives
+// this layout an m x m chroma IDCT at every scale, so the chroma is always up-sampled vertically: h1v2 fancy at scales 2 and 4
+// (jd_h1v2), replication beside the 1 x 1 IDCT of scale 8, as libjpeg does.  The filter reads the chroma row above the run's first and
+// below its last: the vertical halo.  The chroma blocks of MCU rows my - 1 and my + 1, where the image has them, are reconstructed here
+// a second time (the horizontal halo of k_jd_scaled does the same with its two neighbour MCUs), whole, into row sets of their own.
+// LDS: luma 2m rows x kJdRun * m columns; per chroma plane three sets of m rows (above, own, below; one set of one row at scale 8);
+// the run's RGB rows.  Bounds: a neighbour MCU row is only addressed when 0 <= row < mcuy, so block indices stay below the file's
+// mcux * mcuy * 4; LDS rows of chroma stay in [m - 1, 2m] of 3m (far row of jd_h1v2_far is one off the run's own rows at most, and
+// off them only where that MCU row exists); only bytes of pixels (y < oh, x < ow) of the file's own image are stored.
+template <int kShift>
+__global__ __launch_bounds__(kJdThreads) void k_jd_scaled_h1v2(const JdFile *__restrict__ files, const aej_jpegdec_desc *__restrict__ descs, int n,
+                                                               const short *__restrict__ coef, unsigned char *__restrict__ out)
+{
+    constexpr int m = 8 >> kShift, kCols = kJdRun * m, kRgbStride = kCols * 3 + 4;
+    constexpr bool kFancy = kShift < 3;               // libjpeg: no fancy up-sampling beside a 1 x 1 IDCT
+    constexpr int kSets = kFancy ? 3 : 1;
+    __shared__ unsigned char sy[2 * m * kCols], scb[kSets * m * kCols], scr[kSets * m * kCols];
+    __shared__ __align__(4) unsigned char srgb[2 * m * kRgbStride];
+    int lo = 0, hi = n - 1;                           // the last file whose first workgroup is <= blockIdx.x
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (files[mid].grp440_base[kShift - 1] <= (long long)blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+    const JdFile &F = files[lo];
+    const aej_jpegdec_desc &d = descs[lo];
+    const int per_row = (d.mcux + kJdRun - 1) / kJdRun, g = (int)(blockIdx.x - F.grp440_base[kShift - 1]);
+    const int my = g / per_row, g0 = (g % per_row) * kJdRun, ng = min(kJdRun, d.mcux - g0);
+    if (my >= d.mcuy || d.hs != 1 || d.vs != 2 || d.ncomp != 3) return;      // never: the host gives these workgroups to such files alone
+    const int bh = (d.height + 7) / 8, hc = (F.oh + 1) >> 1;                 // real luma block rows; real chroma rows
+    const bool up = kFancy && my > 0, down = kFancy && my + 1 < d.mcuy;
+    const int nY = ng * 2, nC = ng * 2 * (1 + (int)up + (int)down);
+    for (int i = threadIdx.x; i < nY + nC; i += kJdThreads) {
+        int mcu, k, c, row = my;
+        unsigned char *dst;
+        if (i < nY) {
+            mcu = g0 + (i >> 1); k = i & 1; c = 0;
+            if (my * 2 + k >= bh) continue;           // the dummy lower block of the last MCU row
+            dst = sy + k * m * kCols + (mcu - g0) * m;
+        } else {
+            const int j = i - nY, set = j / (2 * ng), jj = j - set * 2 * ng;
+            const int which = set == 0 ? 1 : (set == 1 && up) ? 0 : 2;       // 0: the MCU row above, 1: the run's own, 2: the one below
+            mcu = g0 + (jj >> 1); c = 1 + (jj & 1); k = 2 + (jj & 1);
+            row = my + which - 1;
+            dst = (c == 1 ? scb : scr) + (kFancy ? which : 0) * m * kCols + (mcu - g0) * m;
+        }
+        const short *cf = coef + (F.blk_base + ((long long)row * d.mcux + mcu) * 4 + k) * 64;
+        jd_idct_sized(cf, d.qt[c], m, dst, kCols);
+    }
+    __syncthreads();
+    const int y0 = my * 2 * m, x0 = g0 * m;
+    const int nrows = min(2 * m, F.oh - y0), ncols = min(ng * m, F.ow - x0), nbytes = ncols * 3;
+    unsigned char *img = out + F.out_off;
+    for (int p = threadIdx.x; p < nrows * ncols; p += kJdThreads) {
+        const int r = p / ncols, x = p % ncols;
+        const int a = (int)((uintptr_t)(img + ((long long)(y0 + r) * F.ow + x0) * 3) & 3);      // the row sits in LDS as it does in its dwords
+        unsigned char *o = srgb + r * kRgbStride + a + 3 * x;
+        int cb, cr;
+        if (kFancy) {
+            const int y = y0 + r, base = (my - 1) * m, lc = (y >> 1) - base, lf = jd_h1v2_far(y, hc) - base;      // rows of the three sets
+            cb = jd_h1v2(scb[lc * kCols + x], scb[lf * kCols + x], y);
+            cr = jd_h1v2(scr[lc * kCols + x], scr[lf * kCols + x], y);
+        } else {
+            cb = scb[x]; cr = scr[x];
+        }
+        jd_rgb(sy[r * kCols + x], cb, cr, o);
+    }
+    __syncthreads();
+    const int nslots = (nbytes + 6) / 4;              // dwords a row can touch: up to 3 bytes of shift
+    for (int p = threadIdx.x; p < nrows * nslots; p += kJdThreads) {
+        const int r = p / nslots, k = p % nslots;
+        unsigned char *gp = img + ((long long)(y0 + r) * F.ow + x0) * 3;
+        const int a = (int)((uintptr_t)gp & 3), b0 = max(4 * k, a), b1 = min(4 * k + 4, a + nbytes);
+        const unsigned char *s = srgb + r * kRgbStride;
+        if (b1 - b0 == 4) *reinterpret_cast<unsigned *>(gp + (4 * k - a)) = *reinterpret_cast<const unsigned *>(s + 4 * k);
+        else for (int b = b0; b < b1; b++) gp[b - a] = s[b];      // the ends of a row: its own bytes only
+    }
+}
+
 // ---- host: descriptor checks, layout and launch sequence -----------------------------------------------------------------------------------
 bool jpegdec_descs_ok(const aej_jpegdec_desc *d, int n)
 {
@@ -497,12 +580,13 @@ void jpeg_recon_layout(const aej_jpegdec_desc &d, int shift, JdFile &F, JdBufSiz
     z.blocks += F.n_blocks;
     F.shift = shift;
     F.ow = (d.width + (1 << shift) - 1) >> shift; F.oh = (d.height + (1 << shift) - 1) >> shift;
-    for (int s = 0; s < 3; s++) F.grp_base[s] = z.grp[s];
+    for (int s = 0; s < 3; s++) { F.grp_base[s] = z.grp[s]; F.grp440_base[s] = z.grp440[s]; }
     F.plane_off = z.planes;
     F.px_base = z.px;
     if (shift) {                                      // no sample planes, no pixels of k_jd_rgb's: workgroups of k_jd_scaled<shift>
         F.pw0 = F.ph0 = F.pw1 = F.ph1 = 0;
-        z.grp[shift - 1] += (long long)d.mcuy * ((d.mcux + kJdRun - 1) / kJdRun);
+        const bool h1v2 = d.ncomp == 3 && d.hs == 1 && d.vs == 2;      // 4:4:0: k_jd_scaled_h1v2's grid
+        (h1v2 ? z.grp440 : z.grp)[shift - 1] += (long long)d.mcuy * ((d.mcux + kJdRun - 1) / kJdRun);
         return;
     }
     F.pw0 = d.mcux * 8 * d.hs; F.ph0 = d.mcuy * 8 * d.vs;
@@ -605,6 +689,9 @@ static hipError_t launch_jpegdec_recon_scaled(hipStream_t st, int n, const JdBuf
     if (z.grp[0] > 0) hipLaunchKernelGGL(k_jd_scaled<1>, dim3((unsigned)z.grp[0]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
     if (z.grp[1] > 0) hipLaunchKernelGGL(k_jd_scaled<2>, dim3((unsigned)z.grp[1]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
     if (z.grp[2] > 0) hipLaunchKernelGGL(k_jd_scaled<3>, dim3((unsigned)z.grp[2]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
+    if (z.grp440[0] > 0) hipLaunchKernelGGL(k_jd_scaled_h1v2<1>, dim3((unsigned)z.grp440[0]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
+    if (z.grp440[1] > 0) hipLaunchKernelGGL(k_jd_scaled_h1v2<2>, dim3((unsigned)z.grp440[1]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
+    if (z.grp440[2] > 0) hipLaunchKernelGGL(k_jd_scaled_h1v2<3>, dim3((unsigned)z.grp440[2]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
     return hipGetLastError();
 }
 

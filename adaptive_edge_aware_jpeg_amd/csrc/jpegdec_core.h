@@ -28,6 +28,7 @@ struct JdFile {
     int shift;                         // log2 of the decode scale: 0 full size (k_jd_idct, k_jd_rgb), 1..3 scale 2, 4, 8 (k_jd_scaled)
     int ow, oh;                        // output shape: ceil(width / scale), ceil(height / scale)
     long long grp_base[3];             // [shift - 1]: first workgroup of the file in k_jd_scaled<shift>'s grid (kJdRun MCUs of one MCU row each)
+    long long grp440_base[3];          // the same in k_jd_scaled_h1v2<shift>'s grid, where the three-component 1 x 2 (4:4:0) files go
 };
 
 // one restart segment: written by the un-stuffing scatter (start) and k_jd_segments (the rest)
@@ -285,10 +286,19 @@ AEJ_HD inline int jd_h2v1(int cur, int left, int right, int x, int j, int wc)
     return j == wc - 1 ? cur : (3 * cur + right + 2) >> 2;
 }
 
+// libjpeg's h1v2 "fancy" up-sampling for output row y: `cur` is the sample of chroma row y >> 1, `far` that of the row above it (y even)
+// or below it (y odd), the edge rows standing in for rows -1 and hc.  No narrow-plane exception: jdsample.c has none for this layout.
+AEJ_HD inline int jd_h1v2(int cur, int far, int y) { return (3 * cur + far + ((y & 1) ? 2 : 1)) >> 2; }
+// the row `far` is: of hc chroma rows
+AEJ_HD inline int jd_h1v2_far(int y, int hc) { const int cy = y >> 1; return (y & 1) ? (cy + 1 < hc ? cy + 1 : hc - 1) : (cy > 0 ? cy - 1 : 0); }
+
 // chroma sample for output pixel (y, x) from a plane of wc x hc real samples (row stride `stride`); hs, vs: luma sampling factors
 AEJ_HD inline int jd_chroma(const unsigned char *p, long long stride, int hs, int vs, int wc, int hc, int y, int x)
 {
-    if (hs == 1) return p[(long long)y * stride + x];                        // 4:4:4
+    if (hs == 1) {
+        if (vs == 1) return p[(long long)y * stride + x];                    // 4:4:4
+        return jd_h1v2(p[(long long)(y >> 1) * stride + x], p[(long long)jd_h1v2_far(y, hc) * stride + x], y);      // 4:4:0: h1v2 fancy
+    }
     const int j = x >> 1;
     if (wc <= 2) return p[(long long)(vs == 2 ? y >> 1 : y) * stride + j];  // plain replication
     if (vs == 1) {                                                          // h2v1 fancy

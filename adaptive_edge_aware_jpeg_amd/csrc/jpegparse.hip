@@ -82,6 +82,7 @@ struct JpgParse {
     aej_jpegprog_frame f = {};
     bool sof = false;
     int nf = 0;                        // components the frame header lists
+    bool allow440 = false;             // the caller takes luma sampled 1 x 2 over 1 x 1 chroma (4:4:0) too: the _440 entries
 
     JpgParse(const unsigned char *data, unsigned long long bytes, std::string &m_) : b(data), n(bytes), msg(m_) {}
     int bad(const std::string &t) { msg = t; return (int)AEJ_ERR_ARG; }
@@ -235,13 +236,14 @@ struct JpgParse {
         return 0;
     }
 
-    // 4:4:4, 4:2:2 or 4:2:0 (one component: a non-interleaved scan, whatever its sampling factors say) and the MCU grid
+    // 4:4:4, 4:2:2 or 4:2:0, with allow440 also 4:4:0 (one component: a non-interleaved scan, whatever its sampling factors say) and
+    // the MCU grid
     int sampling()
     {
         if (nf == 3) {
             const int h0 = f.comp_h[0], v0 = f.comp_v[0];
             if (f.comp_h[1] != 1 || f.comp_v[1] != 1 || f.comp_h[2] != 1 || f.comp_v[2] != 1 ||
-                !((h0 == 1 && v0 == 1) || (h0 == 2 && v0 == 1) || (h0 == 2 && v0 == 2)))
+                !((h0 == 1 && v0 == 1) || (h0 == 2 && v0 == 1) || (h0 == 2 && v0 == 2) || (allow440 && h0 == 1 && v0 == 2)))
                 return unsup("sampling factors " + std::to_string(h0) + "x" + std::to_string(v0) + "," + std::to_string(f.comp_h[1]) + "x" +
                              std::to_string(f.comp_v[1]) + "," + std::to_string(f.comp_h[2]) + "x" + std::to_string(f.comp_v[2]));
             f.hs = h0; f.vs = v0;
@@ -418,19 +420,22 @@ struct JpgParse {
 
 }  // namespace
 
-int jpegdec_parse(const unsigned char *b, unsigned long long n, aej_jpegdec_desc &d, std::string &msg)
+int jpegdec_parse(const unsigned char *b, unsigned long long n, aej_jpegdec_desc &d, std::string &msg, bool allow440)
 {
     memset(&d, 0, sizeof d);
     JpgParse P(b, n, msg);
+    P.allow440 = allow440;
     const int rc = P.baseline(d);
     P.store(d);
     return rc;
 }
 
-int jpegprog_parse(const unsigned char *b, unsigned long long n, aej_jpegprog_frame &f, std::vector<aej_jpegprog_scan> &scans, std::string &msg)
+int jpegprog_parse(const unsigned char *b, unsigned long long n, aej_jpegprog_frame &f, std::vector<aej_jpegprog_scan> &scans, std::string &msg,
+                   bool allow440)
 {
     scans.clear();
     JpgParse P(b, n, msg);
+    P.allow440 = allow440;
     const int rc = P.progressive(scans);
     f = P.f;
     return rc;

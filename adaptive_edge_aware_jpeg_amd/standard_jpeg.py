@@ -278,46 +278,53 @@ def _raise_status(bad):
         raise ValueError(f"file {i}: {JPEGDEC_STATUS[code] if 0 <= code < len(JPEGDEC_STATUS) else f'status {code}'}")
 
 
-def parse_header(data, index: int = 0):
+def parse_header(data, index: int = 0, layout_440: bool = False):
     """aej_jpegdec_parse_host: the JpegDecDesc of one file's markers (host only).  Raises NotImplementedError for a valid file outside
-    the supported set and ValueError for a malformed header, both naming the file index."""
+    the supported set and ValueError for a malformed header, both naming the file index.  layout_440=True (aej_jpegdec_parse_host_440)
+    also takes a three-component file whose luma is sampled 1 x 2 over 1 x 1 chroma (4:4:0: hs = 1, vs = 2); without it such a file is
+    refused as before."""
     from ._lib import JpegDecDesc, load_library
     buf, n = _buffer(data)
     d, msg = JpegDecDesc(), ctypes.create_string_buffer(256)
-    _refuse(load_library().aej_jpegdec_parse_host(ctypes.addressof(buf), n, ctypes.addressof(d), ctypes.addressof(msg), 256), msg, index)
+    head = (ctypes.addressof(buf), n, ctypes.addressof(d), ctypes.addressof(msg), 256)
+    lib = load_library()
+    _refuse(lib.aej_jpegdec_parse_host_440(*head, 1) if _check_bool("layout_440", layout_440) else lib.aej_jpegdec_parse_host(*head), msg, index)
     return d
 
 
-def parse_scans(data, index: int = 0):
+def parse_scans(data, index: int = 0, layout_440: bool = False):
     """aej_jpegprog_parse_host: (JpegProgFrame, [JpegProgScan, ...]) of one progressive (SOF2) file, every marker SOI .. EOI walked on
     the host.  Raises ValueError for a malformed file or a scan script that violates T.81 G.1.1.1 and NotImplementedError for a valid
     file outside the supported set (an incomplete progression, arithmetic coding, a file that is not progressive, ...), both naming the
-    file index."""
+    file index.  layout_440: as parse_header (aej_jpegprog_parse_host_440)."""
     from ._lib import JpegProgFrame, JpegProgScan, load_library
     lib = load_library()
     buf, n = _buffer(data)
     frame, msg = JpegProgFrame(), ctypes.create_string_buffer(256)
-    _refuse(lib.aej_jpegprog_parse_host(ctypes.addressof(buf), n, ctypes.addressof(frame), None, 0, ctypes.addressof(msg), 256), msg, index)
+    if _check_bool("layout_440", layout_440):
+        parse = lambda *a: lib.aej_jpegprog_parse_host_440(*a, 1)  # noqa: E731
+    else:
+        parse = lib.aej_jpegprog_parse_host
+    _refuse(parse(ctypes.addressof(buf), n, ctypes.addressof(frame), None, 0, ctypes.addressof(msg), 256), msg, index)
     scans = (JpegProgScan * max(frame.n_scans, 1))()
-    _refuse(lib.aej_jpegprog_parse_host(ctypes.addressof(buf), n, ctypes.addressof(frame), ctypes.addressof(scans), frame.n_scans,
-                                        ctypes.addressof(msg), 256), msg, index)
+    _refuse(parse(ctypes.addressof(buf), n, ctypes.addressof(frame), ctypes.addressof(scans), frame.n_scans, ctypes.addressof(msg), 256), msg, index)
     return frame, list(scans)
 
 
-def _parse_sources(files, progressive=True, transcoder=False, start=0, grey=False):
+def _parse_sources(files, progressive=True, transcoder=False, start=0, grey=False, layout_440=False):
     """Parse every file once, telling baseline from progressive: yields (i, is_progressive, JpegDecDesc | (JpegProgFrame, scans), view)
     file by file, i counting from start.  progressive=False refuses progressive files the way standard_jpeg_decode_many does without
     its keyword; transcoder=True refuses what the transcoder does not take, which without grey=True includes one-component files.
-    Every refusal names the file."""
+    layout_440=True: the parsers' keyword of that name, for every file.  Every refusal names the file."""
     for i, f in enumerate(files, start):
         try:
-            d, is_prog = parse_header(f, i), False
+            d, is_prog = parse_header(f, i, layout_440), False
         except NotImplementedError as e:
             if "progressive JPEG (SOF2)" not in str(e):
                 raise
             if not progressive:
                 raise NotImplementedError(f"{e}; pass progressive=True to standard_jpeg_decode_many") from None
-            d, is_prog = parse_scans(f, i), True
+            d, is_prog = parse_scans(f, i, layout_440), True
         frame = d[0] if is_prog else d
         if transcoder and frame.ncomp != 3 and not (grey and frame.ncomp == 1):
             raise NotImplementedError(f"file {i}: a single-component (grey) file: the transcoder takes three-component files unless grey=True is passed")
@@ -418,7 +425,7 @@ def draft_scale(width: int, height: int, size) -> int:
     return next((s for s in (8, 4, 2) if s <= ratio), 1)
 
 
-def standard_jpeg_decode_many(files, device: int = 0, progressive: bool = False, scale=1) -> list:
+def standard_jpeg_decode_many(files, device: int = 0, progressive: bool = False, scale=1, layout_440: bool = False) -> list:
     """Decode JPEG files on the device: -> list of uint8 [H_i, W_i, 3] tensors (views into one packed allocation), in input
     order, on the context of the current stream; element i equals ``np.asarray(Image.open(io.BytesIO(files[i])).convert("RGB"))``.
     scale: 1, 2, 4 or 8, or a sequence of one such value per file (ValueError naming the value otherwise; a bool is refused): file i
@@ -431,20 +438,23 @@ def standard_jpeg_decode_many(files, device: int = 0, progressive: bool = False,
     header -- of a progressive file every marker up to EOI -- is read on the host before any device work (NotImplementedError /
     ValueError naming the file); the scans cross in one copy per kind and are un-stuffed, Huffman-decoded and reconstructed on the
     device.  A file whose scan is malformed raises ValueError naming its index and the reason (the per-file status words are read back
-    once per kind).  There is no CPU fallback."""
+    once per kind).  There is no CPU fallback.
+    layout_440=True (TypeError for a value that is not a bool) also takes 4:4:0 files -- three components, luma sampled 1 x 2 over 1 x 1
+    chroma, what ``jpegtran -rotate 90`` makes of a 4:2:2 photo -- baseline or progressive, at every scale, mixed freely with the other
+    layouts; without it such a file is refused as before (NotImplementedError, "sampling factors 1x2,...")."""
     files = list(files)
     if not files:
         raise ValueError("standard_jpeg_decode_many needs at least one file")
-    _, out, out_off, shapes = _decode_files(files, device, progressive, _check_scales(scale, len(files)))
+    _, out, out_off, shapes = _decode_files(files, device, progressive, _check_scales(scale, len(files)), layout_440=_check_bool("layout_440", layout_440))
     return [out[int(o):int(o) + h * w * 3].view(h, w, 3) for o, (h, w) in zip(out_off, shapes)]
 
 
-def _decode_files(files, device, progressive, scales, choose=None):
+def _decode_files(files, device, progressive, scales, choose=None, layout_440=False):
     """The decode of standard_jpeg_decode_many -> (context, the packed uint8 output, int64 offsets, [(h, w)]).  scales: int32 [n]; with
     `choose`, file i's scale is choose(i, width, height) instead, asked once its header is parsed and before any device work."""
     n = len(files)
     parsed, views, base_idx, prog_idx, shapes = [], [], [], [], []
-    for i, is_prog, d, mv in _parse_sources(files, progressive):
+    for i, is_prog, d, mv in _parse_sources(files, progressive, layout_440=layout_440):
         parsed.append(d)
         views.append(mv)
         (prog_idx if is_prog else base_idx).append(i)
@@ -514,7 +524,8 @@ def thumbnail_plan(width: int, height: int, size, reducing_gap=2.0):
     return s, reduce_factors(box, final, gap), final, box
 
 
-def standard_jpeg_thumbnail_many(files, size, resample="bicubic", reducing_gap=2.0, progressive: bool = False, device: int = 0) -> list:
+def standard_jpeg_thumbnail_many(files, size, resample="bicubic", reducing_gap=2.0, progressive: bool = False, device: int = 0,
+                                 layout_440: bool = False) -> list:
     """``Image.thumbnail`` on JPEG files, on the device: -> list of uint8 [h_i, w_i, 3] tensors, views into one packed allocation;
     element i equals ``im = Image.open(io.BytesIO(files[i])); im.thumbnail(size_i, F, reducing_gap=reducing_gap);
     np.asarray(im.convert("RGB"))``.  Per file (thumbnail_plan): the aspect-preserving final size; the decode at the scale ``draft()``
@@ -523,8 +534,9 @@ def standard_jpeg_thumbnail_many(files, size, resample="bicubic", reducing_gap=2
     full size.  Nothing but the decoder's status words is read back.  A tensor whose file has a COM segment carries its text as the
     attribute ``jpeg_comment`` (bytes), as Pillow keeps ``im.info["comment"]``; standard_jpeg_encode_many writes it again, as Pillow's save does.
     size: one (w, h), or one per file.  resample (one, or a list of one per file) / reducing_gap: as resize_many (reducing_gap=None: full-size decode, one resize).
-    files / progressive: as standard_jpeg_decode_many, which refuses what this refuses, with the same words."""
+    files / progressive / layout_440: as standard_jpeg_decode_many, which refuses what this refuses, with the same words."""
     from . import resample as RS
+    layout_440 = _check_bool("layout_440", layout_440)
     files = list(files)
     n = len(files)
     if n < 1:
@@ -547,7 +559,7 @@ def standard_jpeg_thumbnail_many(files, size, resample="bicubic", reducing_gap=2
         steps[i] = RS._steps(f"file {i}", dw, dh, final, box, f[i], gap)
         return s
 
-    ctx, out, out_off, shapes = _decode_files(files, device, progressive, np.ones(n, np.int32), choose)
+    ctx, out, out_off, shapes = _decode_files(files, device, progressive, np.ones(n, np.int32), choose, layout_440)
     if all(st["src"] == st["dst"] and st["box"] == (0, 0) + st["src"] for st in steps):
         res = [out[int(o):int(o) + h * w * 3].view(h, w, 3) for o, (h, w) in zip(out_off, shapes)]
     else:
@@ -621,14 +633,14 @@ def metadata_segments(data, index: int = 0) -> bytes:
     return b"".join(bytes(mv[a:b]) for m, a, b in marker_segments(mv, index) if _is_metadata(m))
 
 
-def _prefix(data, index, transform, trim, headers, grey=False):
+def _prefix(data, index, transform, trim, headers, grey=False, layout_440=False):
     """transcode_prefix (transform None) and transform_prefix: headers(lib, frame pointers and density, output buffer and capacity)
     calls the caller's own ABI entry"""
     from ._lib import load_library
-    (_, is_prog, d, mv), = _parse_sources([data], transcoder=True, start=index, grey=_check_bool("grey", grey))
+    (_, is_prog, d, mv), = _parse_sources([data], transcoder=True, start=index, grey=_check_bool("grey", grey), layout_440=layout_440)
     frame = d[0] if is_prog else d
     if transform is not None:
-        _transform_geometry(index, frame.height, frame.width, frame.hs, frame.vs, _check_transform(transform, index), trim)
+        _transform_geometry(index, frame.height, frame.width, frame.hs, frame.vs, _check_transform(transform, index), trim, layout_440)
     dens = (ctypes.c_uint16 * 3)(*_jfif_density(mv, marker_segments(mv, index)))
     buf = (ctypes.c_uint8 * 512)()
     n = headers(load_library(), (None if is_prog else ctypes.addressof(frame), ctypes.addressof(frame) if is_prog else None, ctypes.addressof(dens)),
@@ -638,10 +650,14 @@ def _prefix(data, index, transform, trim, headers, grey=False):
     return bytes(buf[:n])
 
 
-def transcode_prefix(data, progressive: bool = False, index: int = 0, grey: bool = False) -> bytes:
+def transcode_prefix(data, progressive: bool = False, index: int = 0, grey: bool = False, layout_440: bool = False) -> bytes:
     """The bytes SOI .. end of SOF0 / SOF2 that standard_jpeg_transcode_many writes for one file (aej_jfif_transcode_headers_host,
-    host only): JFIF APP0 with the source's density, its quantisation tables, its frame header.  grey: as standard_jpeg_transcode_many."""
+    host only): JFIF APP0 with the source's density, its quantisation tables, its frame header.  grey, layout_440: as
+    standard_jpeg_transcode_many (with layout_440 the entry is aej_jfif_transform_headers_host_440 with the code 0)."""
     progressive = _check_bool("progressive", progressive)
+    if _check_bool("layout_440", layout_440):
+        return _prefix(data, index, None, False, lambda lib, src, dst: lib.aej_jfif_transform_headers_host_440(*src, int(progressive), 0, 0, 1, *dst),
+                       grey, True)
     return _prefix(data, index, None, False, lambda lib, src, dst: lib.aej_jfif_transcode_headers_host(*src, int(progressive), *dst), grey)
 
 
@@ -701,13 +717,16 @@ def exif_orientation(data, index: int = 0) -> int:
     return at[0] if at and 1 <= at[0] <= 8 else 1
 
 
-def _transform_geometry(i, height, width, hs, vs, name, trim):
+def _transform_geometry(i, height, width, hs, vs, name, trim, layout_440=False):
     """-> the output's (height, width, hs, vs); the refusals of a transform, naming the file, before any device work"""
     from ._lib import load_library
-    if name in _TRANSPOSING and hs != vs:
+    if name in _TRANSPOSING and hs != vs and not layout_440:
         raise NotImplementedError(f"file {i}: {name} of a 4:2:2 file would be a 4:4:0 file, which neither the coders nor the decoders here have")
     out = (ctypes.c_int32 * 4)()
-    rc = load_library().aej_jfif_transform_geometry_host(height, width, hs, vs, TRANSFORMS.index(name), int(trim), ctypes.addressof(out))
+    if layout_440:
+        rc = load_library().aej_jfif_transform_geometry_host_440(height, width, hs, vs, TRANSFORMS.index(name), int(trim), 1, ctypes.addressof(out))
+    else:
+        rc = load_library().aej_jfif_transform_geometry_host(height, width, hs, vs, TRANSFORMS.index(name), int(trim), ctypes.addressof(out))
     if rc == 1:
         raise ValueError(f"file {i}: {name} of a {width} x {height} file mirrors an axis that is not a whole number of its {8 * hs} x {8 * vs} MCUs; "
                          "trim=True drops the partial MCUs at that edge first")
@@ -725,18 +744,23 @@ def _check_transform(name, i):
     return name
 
 
-def transform_prefix(data, transform, progressive: bool = False, trim: bool = False, index: int = 0, grey: bool = False) -> bytes:
+def transform_prefix(data, transform, progressive: bool = False, trim: bool = False, index: int = 0, grey: bool = False,
+                     layout_440: bool = False) -> bytes:
     """The bytes SOI .. end of SOF0 / SOF2 that standard_jpeg_transform_many writes for one file under one transform name
     (aej_jfif_transform_headers_host, host only): transcode_prefix with the output's size and sampling and, for a transposing
-    transform, every quantisation table transposed.  grey: as standard_jpeg_transform_many."""
+    transform, every quantisation table transposed.  grey, layout_440: as standard_jpeg_transform_many (with layout_440 the entry is
+    aej_jfif_transform_headers_host_440: a transposed 4:2:2 frame carries the sampling byte 0x12)."""
     progressive, trim = _check_bool("progressive", progressive), _check_bool("trim", trim)
+    if _check_bool("layout_440", layout_440):
+        return _prefix(data, index, transform, trim, lambda lib, src, dst: lib.aej_jfif_transform_headers_host_440(
+            *src, int(progressive), TRANSFORMS.index(transform), int(trim), 1, *dst), grey, True)
     return _prefix(data, index, transform, trim, lambda lib, src, dst: lib.aej_jfif_transform_headers_host(
         *src, int(progressive), TRANSFORMS.index(transform), int(trim), *dst), grey)
 
 
 def standard_jpeg_transform_many(files, transform, progressive: bool = False, trim: bool = False, device: int = 0,
                                  keep_metadata: bool = False, grey: bool = False, restart_marker_blocks: int = 0,
-                                 restart_marker_rows: int = 0) -> List[bytes]:
+                                 restart_marker_rows: int = 0, layout_440: bool = False) -> List[bytes]:
     """Lossless flip, rotation or transposition on the device: standard_jpeg_transcode_many with the files' quantised coefficients
     rearranged between the Huffman decode and the entropy coders (one kernel in the place of the transcoder's bridge), so that no
     sample is quantised a second time -- ``jpegtran -flip / -rotate / -transpose / -transverse``.  files, progressive, device and
@@ -765,10 +789,15 @@ def standard_jpeg_transform_many(files, transform, progressive: bool = False, tr
     restart_marker_blocks, restart_marker_rows: the transcoder's (``jpegtran -restart NB`` / ``-restart N``), counted on the OUTPUT's
     MCU grid; with both 0 the output has no restart markers whatever the source carries.
 
-    Not built: a transposing transform of a 4:2:2 file (it would be 4:4:0; NotImplementedError), crop.  Every refusal names the file and
-    comes before any device work; there is no CPU fallback."""
+    layout_440=True (TypeError for a value that is not a bool) takes the 4:4:0 layout on both sides: a transposing transform of a
+    4:2:2 source -- "exif" with Orientation 5..8 on a camera's portrait shot -- writes a 4:4:0 file (luma 1 x 2, frame sampling byte
+    0x12), one of a 4:4:0 source a 4:2:2 file, and 4:4:0 sources are accepted under every transform; the MCU rules above hold with
+    hs, vs = 1, 2.  Such outputs need layout_440=True again to be read back by this library; Pillow and libjpeg read them as they are.
+
+    Not built: without layout_440 a transposing transform of a 4:2:2 file (it would be 4:4:0; NotImplementedError); crop.  Every refusal
+    names the file and comes before any device work; there is no CPU fallback."""
     progressive, keep_metadata = _check_bool("progressive", progressive), _check_bool("keep_metadata", keep_metadata)
-    trim, grey = _check_bool("trim", trim), _check_bool("grey", grey)
+    trim, grey, layout_440 = _check_bool("trim", trim), _check_bool("grey", grey), _check_bool("layout_440", layout_440)
     rst = _check_restart(restart_marker_blocks, restart_marker_rows)
     files = list(files)
     if not files:
@@ -781,11 +810,11 @@ def standard_jpeg_transform_many(files, transform, progressive: bool = False, tr
         if len(names) != n:
             raise ValueError(f"file {min(len(names), n)}: {len(names)} transforms for {n} files")
         names = [_check_transform(t, i) for i, t in enumerate(names)]
-    return _transcode_many(files, progressive, device, keep_metadata, names, trim, names is None, grey, rst)
+    return _transcode_many(files, progressive, device, keep_metadata, names, trim, names is None, grey, rst, layout_440)
 
 
 def standard_jpeg_transcode_many(files, progressive: bool = False, device: int = 0, keep_metadata: bool = False, grey: bool = False,
-                                 restart_marker_blocks: int = 0, restart_marker_rows: int = 0) -> List[bytes]:
+                                 restart_marker_blocks: int = 0, restart_marker_rows: int = 0, layout_440: bool = False) -> List[bytes]:
     """Lossless transcode on the device: -> every file entropy-coded again, in input order.  files: a non-empty sequence of bytes-like
     JPEG contents, baseline / extended-sequential (SOF0 / SOF1) and complete progressive (SOF2) files of any sizes and of the 4:4:4,
     4:2:2 and 4:2:0 layouts mixed freely.  progressive=False: a baseline file under the file's own optimal Huffman tables (what
@@ -807,28 +836,33 @@ def standard_jpeg_transcode_many(files, progressive: bool = False, device: int =
     scans for one component -- so that a grey file Pillow wrote gives Pillow's optimize=True / progressive=True file of the mode-"L"
     image byte for byte.
 
+    layout_440=True (TypeError for a value that is not a bool) also takes 4:4:0 files (three components, luma sampled 1 x 2 over
+    1 x 1 chroma), mixed freely with the rest; the output keeps the layout (frame sampling byte 0x12).  Without it such a file is
+    refused as before.
+
     Refused before any device work, naming the file: what the decoders' parsers refuse, 16-bit quantisation tables and, without
     grey=True, grey files (NotImplementedError), malformed headers (ValueError).  A file whose scan is corrupt, or that decodes to a
     coefficient an 8-bit JPEG cannot hold, raises ValueError naming its index and the reason; nothing is returned then.  There is no
     CPU fallback."""
     progressive, keep_metadata = _check_bool("progressive", progressive), _check_bool("keep_metadata", keep_metadata)
-    grey = _check_bool("grey", grey)
+    grey, layout_440 = _check_bool("grey", grey), _check_bool("layout_440", layout_440)
     rst = _check_restart(restart_marker_blocks, restart_marker_rows)
     files = list(files)
     if not files:
         raise ValueError("standard_jpeg_transcode_many needs at least one file")
-    return _transcode_many(files, progressive, device, keep_metadata, None, False, False, grey, rst)
+    return _transcode_many(files, progressive, device, keep_metadata, None, False, False, grey, rst, layout_440)
 
 
-def _transcode_many(files, progressive, device, keep_metadata, names, trim, exif, grey=False, rst=(0, 0)):
+def _transcode_many(files, progressive, device, keep_metadata, names, trim, exif, grey=False, rst=(0, 0), layout_440=False):
     """the transcode (names None and not exif) and the transform: names[i] is file i's transform, exif takes it from the file; rst:
-    (restart_marker_blocks, restart_marker_rows) -- (0, 0) goes through the entries without restart arguments"""
+    (restart_marker_blocks, restart_marker_rows) -- (0, 0) goes through the entries without restart arguments; layout_440: the one pair
+    of _440 entries serves transcode and transform, with the restart arguments always"""
     global _last_transcode_groups
     from ._lib import JpegDecDesc, JpegProgFrame, JpegProgScan
     n = len(files)
     names = ["none"] * n if names is None else names
     views, parsed, base_idx, prog_idx, density, meta = [], [None] * n, [], [], [None] * n, [b""] * n
-    for i, is_prog, d, mv in _parse_sources(files, transcoder=True, grey=grey):
+    for i, is_prog, d, mv in _parse_sources(files, transcoder=True, grey=grey, layout_440=layout_440):
         parsed[i] = d
         (prog_idx if is_prog else base_idx).append(i)
         views.append(mv)
@@ -839,7 +873,7 @@ def _transcode_many(files, progressive, device, keep_metadata, names, trim, exif
             names[i] = _EXIF_TRANSFORM[at[0]]
         if names[i] != "none":
             frame = parsed[i][0] if is_prog else parsed[i]
-            _transform_geometry(i, frame.height, frame.width, frame.hs, frame.vs, names[i], trim)
+            _transform_geometry(i, frame.height, frame.width, frame.hs, frame.vs, names[i], trim, layout_440)
         if keep_metadata:
             meta[i] = metadata_segments(mv, i)
             if at and 1 < at[0] <= 8:                # the tag's value becomes 1, in the TIFF block's byte order; nothing else changes
@@ -860,9 +894,13 @@ def _transcode_many(files, progressive, device, keep_metadata, names, trim, exif
     dens = np.ascontiguousarray(np.array([density[i] for i in order], np.uint16))
     codes = np.ascontiguousarray(np.array([TRANSFORMS.index(names[i]) for i in order], np.int32))
     plain = not codes.any()                         # every file "none": the transcoder's own entries
+    rst440 = (int(rst[0]), int(rst[1]), 1)
     rst = tuple(rst) if any(rst) else ()            # the _rst entries' two extra arguments
     sfx = "_rst" if rst else ""
-    if plain:
+    if layout_440:
+        nws = int(lib.aej_jfif_transform_workspace_bytes_440(ctx.handle, ctypes.addressof(descs), nb, ctypes.addressof(frames), ctypes.addressof(pscans),
+                                                             npg, int(progressive), codes.ctypes.data, int(trim), *rst440))
+    elif plain:
         nws = int(getattr(lib, "aej_jfif_transcode_workspace_bytes" + sfx)(ctx.handle, ctypes.addressof(descs), nb, ctypes.addressof(frames),
                                                                           ctypes.addressof(pscans), npg, int(progressive), *rst))
     else:
@@ -880,7 +918,9 @@ def _transcode_many(files, progressive, device, keep_metadata, names, trim, exif
             ctypes.addressof(pscans), npg, data.data_ptr(), ctypes.c_uint64(data.numel()), data_off.ctypes.data, dens.ctypes.data, int(progressive))
     tail = (offsets.data_ptr(), lengths.data_ptr(), ctypes.addressof(total), status.data_ptr(), ctypes.addressof(groups), ws.data_ptr(),
             ctypes.c_uint64(nws))
-    if plain:
+    if layout_440:
+        call = lambda o, c: lib.aej_jfif_transform_batch_440(*head, codes.ctypes.data, int(trim), *rst440, o.data_ptr(), ctypes.c_uint64(c), *tail)  # noqa: E731
+    elif plain:
         call = lambda o, c: getattr(lib, "aej_jfif_transcode_batch" + sfx)(*head, *rst, o.data_ptr(), ctypes.c_uint64(c), *tail)  # noqa: E731
     else:
         call = lambda o, c: getattr(lib, "aej_jfif_transform_batch" + sfx)(*head, codes.ctypes.data, int(trim), *rst, o.data_ptr(),  # noqa: E731
@@ -1085,7 +1125,7 @@ def standard_jpeg_encode_many(images, quality=75, subsampling="4:2:0", optimize:
 
 def standard_jpeg_thumbnail_jpeg_many(files, size, quality=75, subsampling="4:2:0", optimize: bool = False, progressive_out: bool = False,
                                       resample="bicubic", reducing_gap=2.0, progressive: bool = False, device: int = 0,
-                                      restart_marker_blocks: int = 0, restart_marker_rows: int = 0) -> List[bytes]:
+                                      restart_marker_blocks: int = 0, restart_marker_rows: int = 0, layout_440: bool = False) -> List[bytes]:
     """JPEG files in, their thumbnails out as JPEG files: ``standard_jpeg_encode_many(standard_jpeg_thumbnail_many(files, size, resample,
     reducing_gap, progressive, device), quality, subsampling, optimize, progressive_out, device)`` -- for a three-component source file
     i equals ``im = Image.open(io.BytesIO(files[i])); im.thumbnail(size, resample, reducing_gap=reducing_gap); im.save(buf, "JPEG",
@@ -1098,12 +1138,13 @@ def standard_jpeg_thumbnail_jpeg_many(files, size, quality=75, subsampling="4:2:
     files, size, resample, reducing_gap, progressive (whether progressive SOURCES are accepted): standard_jpeg_thumbnail_many's.
     quality (one, or one per file), subsampling, optimize, progressive_out: standard_jpeg_encode_many's quality, subsampling, optimize
     and progressive; restart_marker_blocks, restart_marker_rows: passed through to it (Pillow's save options).  Every argument is checked, and every header parsed, before any device work; a file whose scan is corrupt raises
-    the decoder's ValueError naming it and nothing is returned."""
+    the decoder's ValueError naming it and nothing is returned.  layout_440: standard_jpeg_thumbnail_many's, for the SOURCES (the
+    thumbnails are written in `subsampling`, which has no 4:4:0)."""
     ss, opt, prog = _check_subsampling(subsampling), _check_bool("optimize", optimize), _check_bool("progressive_out", progressive_out)
     rst = _check_restart(restart_marker_blocks, restart_marker_rows)
     files = list(files)
     if not files:
         raise ValueError("standard_jpeg_thumbnail_jpeg_many needs at least one file")
     qualities = _check_qualities(quality, len(files), "file")
-    thumbs = standard_jpeg_thumbnail_many(files, size, resample, reducing_gap, progressive, device)
+    thumbs = standard_jpeg_thumbnail_many(files, size, resample, reducing_gap, progressive, device, layout_440)
     return _encode_many(get_context(device), _check_images(thumbs), qualities, ss, opt, prog, rst)

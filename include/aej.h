@@ -732,6 +732,42 @@ AEJ_API int aej_jfif_restart_map_host(int H, int W, int subsampling, int compone
                                       int32_t *scan_r_host, int32_t *scan_dri_host, int32_t *interval_host, uint8_t *reset_host,
                                       int64_t block_capacity, uint8_t *marker_host, int64_t marker_capacity, int64_t *counts2_host);
 
+/* ---- the 4:4:0 layout: luma sampled 1 x 2 over 1 x 1 chroma ----------------------------------------------------------------------------
+ * What `jpegtran -rotate 90` makes of a 4:2:2 file.  Opt-in: the _440 entries are their namesakes with one more argument, layout_440 (0 or
+ * 1; AEJ_ERR_ARG otherwise, a workspace size of 0), and with 0 they answer exactly as their namesakes, which keep refusing the layout
+ * (AEJ_ERR_UNSUPPORTED; aej_jfif_transform_geometry_host / _coefs_host given hs = 1, vs = 2: AEJ_ERR_ARG, as before).  With 1:
+ *   aej_jpegdec_parse_host_440, aej_jpegprog_parse_host_440 also accept a three-component frame whose luma factors are 1 x 2 over 1 x 1
+ *     chroma (hs = 1, vs = 2, blocks_per_mcu 4: two luma blocks stacked, then Cb, Cr; the lower one is a dummy in the last MCU row of
+ *     an image with an odd number of block rows).  The decoders (aej_jpegdec_batch*, aej_jpegprog_batch*) take such descriptors as they
+ *     are: chroma is up-sampled by libjpeg-turbo's h1v2 "fancy" rule -- the upper output row of chroma row j is (3 c[j] + c[j-1] + 1) >> 2,
+ *     the lower (3 c[j] + c[j+1] + 2) >> 2, rows -1 and hc replicate the edge rows, at any width -- and at scale 2 and 4 still so (the
+ *     chroma IDCT of this layout stays at the luma block's size), at scale 8 by replication.  Pixel-identical to Pillow's decode and draft().
+ *   aej_jfif_transform_geometry_host_440, _coefs_host_440, _headers_host_440: hs = 1, vs = 2 is a source layout, a transposing code
+ *     on a 4:2:2 source gives 4:4:0 (sampling byte 0x12) and on a 4:4:0 source 4:2:2; MCUs are 8 hs x 8 vs as for every layout.
+ *   aej_jfif_transform_workspace_bytes_440, aej_jfif_transform_batch_440: the _rst entries with layout_440 after restart_rows;
+ *     transforms_host may be NULL here, which is the transcode (code 0 for every file), so the transcoder needs no entry of its own.
+ * (Additions to ABI 3: no existing signature, struct layout or behaviour of a valid call changed.) */
+AEJ_API int aej_jpegdec_parse_host_440(const uint8_t *data_host, uint64_t nbytes, aej_jpegdec_desc *desc_host, char *msg, int msg_capacity,
+                                       int layout_440);
+AEJ_API int aej_jpegprog_parse_host_440(const uint8_t *data_host, uint64_t nbytes, aej_jpegprog_frame *frame_host, aej_jpegprog_scan *scans_host,
+                                        int scan_capacity, char *msg, int msg_capacity, int layout_440);
+AEJ_API int aej_jfif_transform_geometry_host_440(int H, int W, int hs, int vs, int transform, int trim, int layout_440, int32_t *out4_host);
+AEJ_API int64_t aej_jfif_transform_coefs_host_440(int H, int W, int hs, int vs, int transform, int trim, int layout_440, const int16_t *src_host,
+                                                  int64_t src_blocks, int16_t *dst_host, int64_t dst_blocks);
+AEJ_API int aej_jfif_transform_headers_host_440(const aej_jpegdec_desc *desc_host, const aej_jpegprog_frame *frame_host, const uint16_t *density3_host,
+                                                int progressive, int transform, int trim, int layout_440, uint8_t *out_host, int capacity);
+AEJ_API uint64_t aej_jfif_transform_workspace_bytes_440(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base,
+                                                        const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *pscans_host, int n_prog,
+                                                        int progressive, const int32_t *transforms_host, int trim, int restart_blocks,
+                                                        int restart_rows, int layout_440);
+AEJ_API int aej_jfif_transform_batch_440(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base, const uint8_t *scans, uint64_t scans_bytes,
+                                         const int64_t *scan_offsets_host, const aej_jpegprog_frame *frames_host,
+                                         const aej_jpegprog_scan *pscans_host, int n_prog, const uint8_t *data, uint64_t data_bytes,
+                                         const int64_t *data_offsets_host, const uint16_t *density_host, int progressive,
+                                         const int32_t *transforms_host, int trim, int restart_blocks, int restart_rows, int layout_440,
+                                         uint8_t *out, uint64_t out_capacity, int64_t *offsets, int64_t *lengths, uint64_t *total_host,
+                                         int32_t *status, int32_t *n_groups_host, void *workspace, uint64_t workspace_bytes);
+
 /* ---- Pillow's resize, reduce and thumbnail for packed 8-bit RGB images (resize_many, standard_jpeg_thumbnail_many) ------------------
  * Image.resize with the convolution filters, Image.reduce and the reducing_gap step of resize, bit for bit, for many images of
  * different sizes in one call (csrc/resample.hip).  An image is uint8 [h][w][3], packed.  Per image, in this order:
