@@ -288,6 +288,12 @@ SIGNATURES = {
     "aej_jfif_transform_coefs_host_440": (_I64, [_I, _I, _I, _I, _I, _I, _I, _P, _I64, _P, _I64]),
     "aej_jfif_transform_headers_host_440": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I]),
     "aej_jfif_transform_workspace_bytes_440": (_U64, [_P, _P, _I, _P, _P, _I, _I, _P, _I, _I, _I, _I]),
+    "aej_jfif_transform_geometry_host_cut": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
+    "aej_jfif_transform_coefs_host_cut": (_I64, [_I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I64, _P, _I64]),
+    "aej_jfif_transform_headers_host_cut": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I, _P, _I]),
+    "aej_jfif_transform_workspace_bytes_cut": (_U64, [_P, _P, _I, _P, _P, _I, _I, _P, _I, _I, _I, _I, _P, _I]),
+    "aej_jfif_transform_batch_cut": (_I, [_P, _P, _I, _P, _U64, _P, _P, _P, _I, _P, _U64, _P, _P, _I, _P, _I, _I, _I, _I, _P, _I, _P, _U64, _P, _P, _P, _P, _P,
+                                          _P, _U64]),
     "aej_jfif_transform_batch_440": (_I, [_P, _P, _I, _P, _U64, _P, _P, _P, _I, _P, _U64, _P, _P, _I, _P, _I, _I, _I, _I, _P, _U64, _P, _P, _P, _P, _P,
                                           _P, _U64]),
     "aej_jfif_restart_map_host": (_I, [_I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I64, _P, _I64, _P]),

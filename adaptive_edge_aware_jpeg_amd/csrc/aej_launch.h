@@ -416,6 +416,7 @@ struct JtGroup {                       // the files of one OUTPUT (H, W, hs, vs,
 struct JtPlan {
     bool prog = false;
     bool transform = false;            // a file has a transform other than kJxNone: k_jt_transform takes the place of k_jt_bridge
+    bool cut = false;                  // a file has a crop or drops its chroma (JxGeom::cut): k_jt_cut takes the place of both
     bool annexk = false;               // baseline files under the Annex K Huffman tables, not their own (the ragged encoder without optimize)
     int rst_blocks = 0, rst_rows = 0;  // restart_marker_blocks / restart_marker_rows of the call (jfiftrans_close gives every group its interval)
     std::vector<JtFile> files;         // caller's order
@@ -430,13 +431,14 @@ void jfiftrans_source(const aej_jpegdec_desc &d, JtSource &s);
 void jfiftrans_source(const aej_jpegprog_frame &f, JtSource &s);
 // the markers SOI .. SOF0 / SOF2 the transcoder writes for one source -> their length, or -1 when they do not fit
 int jfiftrans_prefix_host(const JtSource &s, bool prog, unsigned char *out, int capacity);
-// what the markers of the transformed file take: the output size and sampling of g, the tables transposed with it
+// what the markers of the transformed file take: the output size, sampling and component count of g, the tables transposed with it
 JtSource jfiftrans_transformed(const JtSource &s, const JxGeom &g);
 // n_blocks[i]: blocks the decoder holds for file i (must equal the source's MCU-padded count).  xf (may be NULL: the transcoder):
 // one transform code per file.  -> -1, or the first file that does not fit: *why (may be NULL) gets jx_geom's answer, kJxBadArg for
-// descriptors that disagree.
+// descriptors that disagree.  boxes (may be NULL): 4 ints per file, jx_geom's crop box (right == 0: none); drop: jx_geom's chroma drop, for
+// every file.
 int jfiftrans_plan(const std::vector<JtSource> &src, const std::vector<long long> &n_blocks, bool prog, const int *xf, int trim, JtPlan &plan,
-                   int *why, int rst_blocks = 0, int rst_rows = 0, bool allow440 = false);
+                   int *why, int rst_blocks = 0, int rst_rows = 0, bool allow440 = false, const int *boxes = nullptr, bool drop = false);
 // the pieces of a plan, shared with the ragged encoder (jfifmany.hip).  Before them: plan.files sized, plan.prog set.
 // the group of one output geometry, made on first use (NULL: a geometry jfif_geom refuses)
 JtGroup *jfiftrans_group(JtPlan &plan, int H, int W, int hs, int vs, int ncomp = 3);

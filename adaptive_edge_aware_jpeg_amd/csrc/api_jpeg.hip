@@ -511,9 +511,10 @@ static bool rst_ok(int blocks, int rows) { return blocks >= 0 && blocks <= kJrMa
 
 static int jt_layout(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs, int n_base, const aej_jpegprog_frame *frames,
                      const aej_jpegprog_scan *pscans, int n_prog, const uint16_t *density, int progressive, const int32_t *xf, int trim, int rst_blocks,
-                     int rst_rows, JtCall &c, int allow440 = 0)
+                     int rst_rows, JtCall &c, int allow440 = 0, const int32_t *boxes = nullptr, int drop = 0)
 {
     if (allow440 != 0 && allow440 != 1) return fail(ctx, AEJ_ERR_ARG, "%s: layout_440 %d (0 or 1)", fn, allow440);
+    if (drop != 0 && drop != 1) return fail(ctx, AEJ_ERR_ARG, "%s: drop_chroma %d (0 or 1)", fn, drop);
     if (trim != 0 && trim != 1) return fail(ctx, AEJ_ERR_ARG, "%s: trim %d (0 or 1)", fn, trim);
     if (!rst_ok(rst_blocks, rst_rows)) return fail(ctx, AEJ_ERR_ARG, "%s: restart_blocks %d, restart_rows %d (0 .. 65535)", fn, rst_blocks, rst_rows);
     if (n_base < 0 || n_prog < 0 || n_base + n_prog < 1 || (long long)n_base + n_prog > 65535 || (progressive != 0 && progressive != 1))
@@ -536,8 +537,11 @@ static int jt_layout(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs
         if (density) { c.src[i].units = density[3 * i] & 255; c.src[i].xdensity = density[3 * i + 1]; c.src[i].ydensity = density[3 * i + 2]; }
     }
     int why = kJxOk;
-    const int bad = jfiftrans_plan(c.src, nblk, progressive != 0, xf, trim, c.plan, &why, rst_blocks, rst_rows, allow440 != 0);
+    const int bad = jfiftrans_plan(c.src, nblk, progressive != 0, xf, trim, c.plan, &why, rst_blocks, rst_rows, allow440 != 0, boxes, drop != 0);
     if (bad < 0) return 0;
+    if (why == kJxCropRange)
+        return fail(ctx, AEJ_ERR_ARG, "%s: file %d: crop box (%d, %d, %d, %d) does not lie inside the transformed image", fn, bad, boxes[4 * bad],
+                    boxes[4 * bad + 1], boxes[4 * bad + 2], boxes[4 * bad + 3]);
     if (why == kJxLayout)
         return fail(ctx, AEJ_ERR_UNSUPPORTED, "%s: file %d: a transposing transform of a 4:2:2 file would be a 4:4:0 file, which is not built", fn, bad);      // (the entries with layout_440 write it)
     if (why == kJxNotPerfect)
@@ -561,9 +565,9 @@ static JtWorkspace jt_carve(void *workspace, int n_base, int n_prog, JtCall &c)
 }
 
 static int jt_headers(const aej_jpegdec_desc *desc_host, const aej_jpegprog_frame *frame_host, const uint16_t *density3_host, int progressive,
-                      int transform, int trim, uint8_t *out_host, int capacity, int allow440 = 0)
+                      int transform, int trim, uint8_t *out_host, int capacity, int allow440 = 0, const int32_t *box = nullptr, int drop = 0)
 {
-    if (allow440 != 0 && allow440 != 1) return AEJ_ERR_ARG;
+    if ((allow440 != 0 && allow440 != 1) || (drop != 0 && drop != 1)) return AEJ_ERR_ARG;
     if ((!desc_host) == (!frame_host) || !out_host || capacity < 0 || (progressive != 0 && progressive != 1) || (trim != 0 && trim != 1)) return AEJ_ERR_ARG;
     if (!(desc_host ? jt_source_ok(*desc_host) : jt_source_ok(*frame_host))) return AEJ_ERR_UNSUPPORTED;
     JtSource s;
@@ -571,7 +575,7 @@ static int jt_headers(const aej_jpegdec_desc *desc_host, const aej_jpegprog_fram
     if (density3_host) { s.units = density3_host[0] & 255; s.xdensity = density3_host[1]; s.ydensity = density3_host[2]; }
     JxGeom x;
     if (!allow440 && s.ncomp == 3 && s.hs == 1 && s.vs == 2) return AEJ_ERR_UNSUPPORTED;
-    const int rc = jx_geom(s.height, s.width, s.hs, s.vs, transform, trim, x, s.ncomp, allow440 != 0);
+    const int rc = jx_geom(s.height, s.width, s.hs, s.vs, transform, trim, x, s.ncomp, allow440 != 0, box, drop != 0);
     if (rc != kJxOk) return rc == kJxLayout ? AEJ_ERR_UNSUPPORTED : AEJ_ERR_ARG;
     const int n = jfiftrans_prefix_host(jfiftrans_transformed(s, x), progressive != 0, out_host, capacity);
     return n < 0 ? AEJ_ERR_CAPACITY : n;
@@ -595,16 +599,35 @@ extern "C" int aej_jfif_transform_headers_host_440(const aej_jpegdec_desc *desc_
     return jt_headers(desc_host, frame_host, density3_host, progressive, transform, trim, out_host, capacity, layout_440);
 }
 
-static int jt_geometry_host(int H, int W, int hs, int vs, int transform, int trim, int32_t *out4_host, int allow440)
+extern "C" int aej_jfif_transform_headers_host_cut(const aej_jpegdec_desc *desc_host, const aej_jpegprog_frame *frame_host, const uint16_t *density3_host,
+                                                   int progressive, int transform, int trim, int layout_440, const int32_t *box4_host, int drop_chroma,
+                                                   uint8_t *out_host, int capacity)
+{
+    return jt_headers(desc_host, frame_host, density3_host, progressive, transform, trim, out_host, capacity, layout_440, box4_host, drop_chroma);
+}
+
+static int jt_geometry_host(int H, int W, int hs, int vs, int transform, int trim, int32_t *out4_host, int allow440, int nc = 3,
+                            const int32_t *box = nullptr, int drop = 0, int32_t *corner2 = nullptr)
 {
     JxGeom x;
-    if (allow440 != 0 && allow440 != 1) return AEJ_ERR_ARG;
-    const int rc = jx_geom(H, W, hs, vs, transform, trim != 0, x, 3, allow440 != 0);
+    if ((allow440 != 0 && allow440 != 1) || (drop != 0 && drop != 1)) return AEJ_ERR_ARG;
+    const int rc = jx_geom(H, W, hs, vs, transform, trim != 0, x, nc, allow440 != 0, box, drop != 0);
     if ((trim != 0 && trim != 1) || rc == kJxBadArg) return AEJ_ERR_ARG;
     if (rc == kJxLayout) return AEJ_ERR_UNSUPPORTED;
+    if (rc == kJxCropRange) return AEJ_JFIF_TRANSFORM_CROP_RANGE;
     if (rc != kJxOk) return rc == kJxNotPerfect ? AEJ_JFIF_TRANSFORM_NOT_PERFECT : AEJ_JFIF_TRANSFORM_TRIMS_TO_ZERO;
     if (out4_host) { out4_host[0] = x.oH; out4_host[1] = x.oW; out4_host[2] = x.ohs; out4_host[3] = x.ovs; }
+    if (corner2) { corner2[0] = x.cx * 8 * x.ohs; corner2[1] = x.cy * 8 * x.ovs; }
     return 0;
+}
+
+extern "C" int aej_jfif_transform_geometry_host_cut(int H, int W, int hs, int vs, int components, int transform, int trim, int layout_440,
+                                                    const int32_t *box4_host, int drop_chroma, int32_t *out6_host)
+{
+    int32_t o[6] = { 0, 0, 0, 0, 0, 0 };
+    const int rc = jt_geometry_host(H, W, hs, vs, transform, trim, o, layout_440, components, box4_host, drop_chroma, o + 4);
+    if (rc == 0 && out6_host) memcpy(out6_host, o, sizeof o);
+    return rc;
 }
 
 extern "C" int aej_jfif_transform_geometry_host(int H, int W, int hs, int vs, int transform, int trim, int32_t *out4_host)
@@ -618,12 +641,13 @@ extern "C" int aej_jfif_transform_geometry_host_440(int H, int W, int hs, int vs
 }
 
 static int64_t jt_coefs_host(int H, int W, int hs, int vs, int nc, int transform, int trim, const int16_t *src_host, int64_t src_blocks,
-                             int16_t *dst_host, int64_t dst_blocks, int allow440 = 0)
+                             int16_t *dst_host, int64_t dst_blocks, int allow440 = 0, const int32_t *box = nullptr, int drop = 0, bool cut_entry = false)
 {
     JxGeom x;
-    const int rc = jt_geometry_host(H, W, hs, vs, transform, trim, nullptr, allow440);
+    const int rc = cut_entry ? jt_geometry_host(H, W, hs, vs, transform, trim, nullptr, allow440, nc, box, drop)
+                             : jt_geometry_host(H, W, hs, vs, transform, trim, nullptr, allow440);
     if (rc) return rc;
-    jx_geom(H, W, hs, vs, transform, trim, x, nc, allow440 != 0);
+    jx_geom(H, W, hs, vs, transform, trim, x, nc, allow440 != 0, box, drop != 0);
     if (!src_host && !dst_host) return x.n_out;              // a size query
     if (!src_host || !dst_host || src_blocks != x.n_src) return AEJ_ERR_ARG;
     if (dst_blocks < x.n_out) return AEJ_ERR_CAPACITY;
@@ -643,6 +667,16 @@ extern "C" int64_t aej_jfif_transform_coefs_host_440(int H, int W, int hs, int v
     return jt_coefs_host(H, W, hs, vs, 3, transform, trim, src_host, src_blocks, dst_host, dst_blocks, layout_440);
 }
 
+extern "C" int64_t aej_jfif_transform_coefs_host_cut(int H, int W, int hs, int vs, int components, int transform, int trim, int layout_440,
+                                                     const int32_t *box4_host, int drop_chroma, const int16_t *src_host, int64_t src_blocks,
+                                                     int16_t *dst_host, int64_t dst_blocks)
+{
+    const int64_t rc = jt_coefs_host(H, W, hs, vs, components, transform, trim, src_host, src_blocks, dst_host, dst_blocks, layout_440, box4_host,
+                                     drop_chroma, true);
+    const bool refused = jt_geometry_host(H, W, hs, vs, transform, trim, nullptr, layout_440, components, box4_host, drop_chroma) > 0;
+    return refused ? AEJ_ERR_ARG : rc;                        // a cropped file can have 1, 2 or 3 blocks: no positive refusal codes here
+}
+
 extern "C" int64_t aej_jfif_transform_coefs_grey_host(int H, int W, int transform, int trim, const int16_t *src_host, int64_t src_blocks,
                                                       int16_t *dst_host, int64_t dst_blocks)
 {
@@ -653,12 +687,13 @@ extern "C" int64_t aej_jfif_transform_coefs_grey_host(int H, int W, int transfor
 
 static uint64_t jt_workspace_bytes(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs_host, int n_base, const aej_jpegprog_frame *frames_host,
                                    const aej_jpegprog_scan *pscans_host, int n_prog, int progressive, const int32_t *xf, int trim, int rst_blocks,
-                                   int rst_rows, int allow440 = 0)
+                                   int rst_rows, int allow440 = 0, const int32_t *boxes = nullptr, int drop = 0)
 {
     if (!ctx || (n_base > 0 && !descs_host) || (n_prog > 0 && (!frames_host || !pscans_host))) return 0;
     JtCall c;
     const std::string keep = ctx->err;
-    const int rc = jt_layout(ctx, fn, descs_host, n_base, frames_host, pscans_host, n_prog, nullptr, progressive, xf, trim, rst_blocks, rst_rows, c, allow440);
+    const int rc = jt_layout(ctx, fn, descs_host, n_base, frames_host, pscans_host, n_prog, nullptr, progressive, xf, trim, rst_blocks, rst_rows, c, allow440,
+                             boxes, drop);
     ctx->err = keep;                                         // a size query leaves the context's last error alone
     return rc ? 0 : jt_carve(nullptr, n_base, n_prog, c).bytes;
 }
@@ -696,6 +731,15 @@ extern "C" uint64_t aej_jfif_transform_workspace_bytes_440(aej_ctx *ctx, const a
                               restart_rows, layout_440);
 }
 
+extern "C" uint64_t aej_jfif_transform_workspace_bytes_cut(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base,
+                                                           const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *pscans_host, int n_prog,
+                                                           int progressive, const int32_t *transforms_host, int trim, int restart_blocks,
+                                                           int restart_rows, int layout_440, const int32_t *boxes4_host, int drop_chroma)
+{
+    return jt_workspace_bytes(ctx, __func__, descs_host, n_base, frames_host, pscans_host, n_prog, progressive, transforms_host, trim, restart_blocks,
+                              restart_rows, layout_440, boxes4_host, drop_chroma);
+}
+
 extern "C" uint64_t aej_jfif_transform_workspace_bytes(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base,
                                                        const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *pscans_host, int n_prog,
                                                        int progressive, const int32_t *transforms_host, int trim)
@@ -708,14 +752,15 @@ static int jt_batch(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs_
                     const uint8_t *data, uint64_t data_bytes, const int64_t *data_offsets_host, const uint16_t *density_host, int progressive,
                     const int32_t *xf, int trim, int rst_blocks, int rst_rows, uint8_t *out, uint64_t out_capacity, int64_t *offsets,
                     int64_t *lengths, uint64_t *total_host, int32_t *status, int32_t *n_groups_host, void *workspace, uint64_t workspace_bytes,
-                    int allow440 = 0)
+                    int allow440 = 0, const int32_t *boxes = nullptr, int drop = 0)
 {
     AEJ_TRY(enter(ctx, fn));
     if ((n_base > 0 && (!descs_host || !scans || !scan_offsets_host)) || (n_prog > 0 && (!frames_host || !pscans_host || !data || !data_offsets_host)) ||
         !offsets || !lengths || !total_host || !status || !workspace)
         return null_buffer(ctx, fn);
     JtCall c;
-    AEJ_TRY(jt_layout(ctx, fn, descs_host, n_base, frames_host, pscans_host, n_prog, density_host, progressive, xf, trim, rst_blocks, rst_rows, c, allow440));
+    AEJ_TRY(jt_layout(ctx, fn, descs_host, n_base, frames_host, pscans_host, n_prog, density_host, progressive, xf, trim, rst_blocks, rst_rows, c, allow440,
+                      boxes, drop));
     for (int i = 0; i < n_base; i++) AEJ_TRY(jpegdec_scan_offset(ctx, fn, descs_host[i], i, scans_bytes, scan_offsets_host[i], c.files[i]));
     AEJ_TRY(jpegprog_scan_offsets(ctx, fn, c.y, data_bytes, data_offsets_host));
     const JtWorkspace ws = jt_carve(workspace, n_base, n_prog, c);
@@ -809,6 +854,20 @@ extern "C" int aej_jfif_transform_batch_440(aej_ctx *ctx, const aej_jpegdec_desc
     return jt_batch(ctx, __func__, descs_host, n_base, scans, scans_bytes, scan_offsets_host, frames_host, pscans_host, n_prog, data, data_bytes,
                     data_offsets_host, density_host, progressive, transforms_host, trim, restart_blocks, restart_rows, out, out_capacity, offsets,
                     lengths, total_host, status, n_groups_host, workspace, workspace_bytes, layout_440);
+}
+
+extern "C" int aej_jfif_transform_batch_cut(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base, const uint8_t *scans, uint64_t scans_bytes,
+                                            const int64_t *scan_offsets_host, const aej_jpegprog_frame *frames_host,
+                                            const aej_jpegprog_scan *pscans_host, int n_prog, const uint8_t *data, uint64_t data_bytes,
+                                            const int64_t *data_offsets_host, const uint16_t *density_host, int progressive,
+                                            const int32_t *transforms_host, int trim, int restart_blocks, int restart_rows, int layout_440,
+                                            const int32_t *boxes4_host, int drop_chroma, uint8_t *out, uint64_t out_capacity, int64_t *offsets,
+                                            int64_t *lengths, uint64_t *total_host, int32_t *status, int32_t *n_groups_host, void *workspace,
+                                            uint64_t workspace_bytes)
+{
+    return jt_batch(ctx, __func__, descs_host, n_base, scans, scans_bytes, scan_offsets_host, frames_host, pscans_host, n_prog, data, data_bytes,
+                    data_offsets_host, density_host, progressive, transforms_host, trim, restart_blocks, restart_rows, out, out_capacity, offsets,
+                    lengths, total_host, status, n_groups_host, workspace, workspace_bytes, layout_440, boxes4_host, drop_chroma);
 }
 
 extern "C" int aej_jfif_transform_batch(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base, const uint8_t *scans, uint64_t scans_bytes,

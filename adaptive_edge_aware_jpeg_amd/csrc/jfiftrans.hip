@@ -21,6 +21,11 @@
 //                   dummy output block is written as libjpeg writes it: lane 0 takes the DC of the real block before it in the MCU, the
 //                   AC lanes read nothing and write 0.  Range ballot and status protocol are the bridge's (the limits are symmetric but
 //                   for the DC, which no transform negates).  A file whose transform is "none" goes through it unchanged, dummies too.
+//   k_jt_cut        in the place of both when a file of the call has a crop or drops its chroma (aej_jfif_transform_*_cut; JxGeom::cut):
+//                   k_jt_transform with jx_source_block reading the crop offset, the whole transform's grid and the source's own component
+//                   count from the file's JxGeom, so that the output's blocks may be fewer than the source's and of one component where
+//                   the source has three; a file of the call without either takes the path it takes in k_jt_transform.  A call without
+//                   such a file never launches it
 //   (per group)     launch_jfif_entropy / launch_jfifprog_entropy: histogram .. file lengths, unchanged; a source's restart markers
 //                   are gone with its entropy coding, and the output gets those of JtPlan::rst_blocks / rst_rows (jfiftrans_close gives
 //                   every group its interval; 0, 0: none)
@@ -37,7 +42,9 @@
 // by jx_geom on the host, is all the mapping reads: jfiftrans_plan has checked that its n_out is the group's block count (the size of
 // dst, and the file's n_blocks) and its n_src the count the decoder holds (the size of src); jx_source_block maps [0, n_out) into
 // [0, n_src) -- a mirrored axis is a whole number of MCUs, a transposed block of an h x v grid lies in the v x h grid, the walk back from
-// a dummy block stays inside its MCU -- and the kernel still drops a wave whose source block would lie outside.
+// a dummy block stays inside its MCU -- and the kernel still drops a wave whose source block would lie outside.  With a cut the same holds:
+// the output's MCU (mx + cx, my + cy) lies inside the whole transform's grid because the box lies inside the transformed image (jx_geom
+// refuses any other), and a luma block of a chroma drop lies inside the source's MCU grid because its MCU does.
 #include "aej_common.h"
 #include "aej_ctx.h"
 #include "aej_launch.h"
@@ -88,6 +95,38 @@ __global__ __launch_bounds__(kJtThreads) void k_jt_transform(const JtFile *__res
     int sb = (int)b, si = k_zigzag8.natural[z];
     bool dummy = false, negate = false;
     if (G.xf != kJxNone) {
+        sb = jx_source_block(G, (int)b, &dummy);
+        si = jx_source_index(G, si, &negate);
+    }
+    if (sb < 0 || sb >= G.n_src) return;                     // never (header comment)
+    int v = dummy && z != 0 ? 0 : F.src[(long long)sb * 64 + si];
+    if (negate) v = -v;
+    const bool bad = z == 0 ? (v < -1024 || v > 1023) : (v < -1023 || v > 1023);
+    const bool any_bad = __ballot(bad) != 0ull;
+    if (any_bad && z == 0) atomicCAS(status + F.status_index, 0, AEJ_JPEGDEC_COEF_RANGE);
+    const bool failed = any_bad || status[F.status_index] != 0;
+    F.dst[b * 64 + z] = failed ? (short)0 : (short)v;
+}
+
+// The bridge with a crop or a chroma drop (header comment): k_jt_transform's shape -- one wave per OUTPUT block, the mapping scalar, lane z
+// writing position z -- with the cut's fields of JxGeom read.  No LDS: a wave reads one 128-byte block and writes one.
+__global__ __launch_bounds__(kJtThreads) void k_jt_cut(const JtFile *__restrict__ files, const JxGeom *__restrict__ geom, int n, long long n_blocks,
+                                                       int *__restrict__ status)
+{
+    const long long t = (long long)blockIdx.x * (kJtThreads / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // scalar: the maps are per wave
+    if (t >= n_blocks) return;
+    const int z = threadIdx.x & 63;
+    const int fi = jt_find_file(files, n, t);
+    const JtFile F = files[fi];
+    const JxGeom G = geom[fi];
+    const long long b = t - F.src_base;
+    if (b >= F.n_blocks || b >= G.n_out) return;             // never: the files' ranges tile [0, n_blocks), and n_blocks is n_out
+    int sb = (int)b, si = k_zigzag8.natural[z];
+    bool dummy = false, negate = false;
+    if (G.cut) {
+        sb = jx_source_block(G, (int)b, &dummy, true);
+        si = jx_source_index(G, si, &negate);
+    } else if (G.xf != kJxNone) {
         sb = jx_source_block(G, (int)b, &dummy);
         si = jx_source_index(G, si, &negate);
     }
@@ -188,6 +227,7 @@ JtSource jfiftrans_transformed(const JtSource &s, const JxGeom &g)
 {
     JtSource o = s;
     o.width = g.oW; o.height = g.oH; o.hs = g.ohs; o.vs = g.ovs;
+    o.ncomp = g.nc;                                          // a chroma drop: the luma component alone, its id and its table
     for (int c = 0; c < 3 && g.t; c++)
         for (int i = 0; i < 64; i++) o.qt[c][i] = s.qt[c][(i & 7) * 8 + (i >> 3)];
     return o;
@@ -197,10 +237,10 @@ void jfiftrans_coefs_host(const JxGeom &g, const short *src, short *dst)
 {
     for (int b = 0; b < g.n_out; b++) {
         bool dummy = false;
-        const int sb = g.xf != kJxNone ? jx_source_block(g, b, &dummy) : b;
+        const int sb = g.cut ? jx_source_block(g, b, &dummy, true) : g.xf != kJxNone ? jx_source_block(g, b, &dummy) : b;
         for (int z = 0; z < 64; z++) {
             bool negate = false;
-            const int si = g.xf != kJxNone ? jx_source_index(g, kZigzag8.natural[z], &negate) : kZigzag8.natural[z];
+            const int si = g.cut || g.xf != kJxNone ? jx_source_index(g, kZigzag8.natural[z], &negate) : kZigzag8.natural[z];
             const int v = dummy && z != 0 ? 0 : src[(long long)sb * 64 + si];
             dst[(long long)b * 64 + z] = (short)(negate ? -v : v);
         }
@@ -243,7 +283,7 @@ int jfiftrans_close(JtPlan &plan)
 }
 
 int jfiftrans_plan(const std::vector<JtSource> &src, const std::vector<long long> &n_blocks, bool prog, const int *xf, int trim, JtPlan &plan,
-                   int *why, int rst_blocks, int rst_rows, bool allow440)
+                   int *why, int rst_blocks, int rst_rows, bool allow440, const int *boxes, bool drop)
 {
     auto refuse = [&](int i, int w) { if (why) *why = w; return i; };
     const int n = (int)src.size();
@@ -256,13 +296,14 @@ int jfiftrans_plan(const std::vector<JtSource> &src, const std::vector<long long
     for (int i = 0; i < n; i++) {
         const JtSource &s = src[i];
         JxGeom &x = plan.geom[i];
-        const int rc = jx_geom(s.height, s.width, s.hs, s.vs, xf ? xf[i] : kJxNone, trim, x, s.ncomp, allow440);
+        const int rc = jx_geom(s.height, s.width, s.hs, s.vs, xf ? xf[i] : kJxNone, trim, x, s.ncomp, allow440, boxes ? boxes + 4 * i : nullptr, drop);
         if (rc != kJxOk) return refuse(i, rc);
         plan.transform |= x.xf != kJxNone;
-        JtGroup *grp = jfiftrans_group(plan, x.oH, x.oW, x.ohs, x.ovs, s.ncomp);
+        plan.cut |= x.cut != 0;
+        JtGroup *grp = jfiftrans_group(plan, x.oH, x.oW, x.ohs, x.ovs, x.nc);
         if (!grp || n_blocks[i] != x.n_src || grp->g.nblk != x.n_out) return refuse(i, kJxBadArg);
         jfiftrans_add(plan, *grp, i, x.n_out);
-        grp->foreign_ids |= s.comp_id[0] != 1 || (s.ncomp == 3 && (s.comp_id[1] != 2 || s.comp_id[2] != 3));
+        grp->foreign_ids |= s.comp_id[0] != 1 || (x.nc == 3 && (s.comp_id[1] != 2 || s.comp_id[2] != 3));      // the output's components only
     }
     const int bad = jfiftrans_close(plan);
     if (bad >= 0) return refuse(bad, kJxBadArg);
@@ -292,7 +333,7 @@ unsigned long long jfiftrans_carve(void *base, JtPlan &plan)
     Carver c(base);
     const long long n = (long long)plan.files.size();
     plan.d_files = c.take<JtFile>(n);
-    if (plan.transform) plan.d_geom = c.take<JxGeom>(n);
+    if (plan.transform || plan.cut) plan.d_geom = c.take<JxGeom>(n);
     plan.glen = c.take<long long>(n);
     plan.goff = c.take<long long>(n);
     plan.total = c.take<long long>(1);
@@ -316,7 +357,10 @@ hipError_t launch_jfiftrans(hipStream_t st, JtPlan &plan, int *status, unsigned 
     hipError_t e = hipMemcpyAsync(plan.d_files, plan.files.data(), sizeof(JtFile) * n, hipMemcpyHostToDevice, st);
     if (e != hipSuccess) return e;
     const dim3 grid((unsigned)((plan.n_blocks + kJtThreads / 64 - 1) / (kJtThreads / 64)));
-    if (plan.transform) {
+    if (plan.cut) {
+        if ((e = hipMemcpyAsync(plan.d_geom, plan.geom.data(), sizeof(JxGeom) * n, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_jt_cut, grid, dim3(kJtThreads), 0, st, plan.d_files, plan.d_geom, n, plan.n_blocks, status);
+    } else if (plan.transform) {
         if ((e = hipMemcpyAsync(plan.d_geom, plan.geom.data(), sizeof(JxGeom) * n, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
         hipLaunchKernelGGL(k_jt_transform, grid, dim3(kJtThreads), 0, st, plan.d_files, plan.d_geom, n, plan.n_blocks, status);
     } else {

@@ -633,13 +633,15 @@ def metadata_segments(data, index: int = 0) -> bytes:
     return b"".join(bytes(mv[a:b]) for m, a, b in marker_segments(mv, index) if _is_metadata(m))
 
 
-def _prefix(data, index, transform, trim, headers, grey=False, layout_440=False):
+def _prefix(data, index, transform, trim, headers, grey=False, layout_440=False, cut=None):
     """transcode_prefix (transform None) and transform_prefix: headers(lib, frame pointers and density, output buffer and capacity)
-    calls the caller's own ABI entry"""
+    calls the caller's own ABI entry.  cut: None, or (crop box or None, drop_chroma) -- the refusals of _cut_geometry then"""
     from ._lib import load_library
     (_, is_prog, d, mv), = _parse_sources([data], transcoder=True, start=index, grey=_check_bool("grey", grey), layout_440=layout_440)
     frame = d[0] if is_prog else d
-    if transform is not None:
+    if cut is not None:
+        _cut_geometry(index, frame, _check_transform(transform, index), trim, layout_440, cut[0], cut[1])
+    elif transform is not None:
         _transform_geometry(index, frame.height, frame.width, frame.hs, frame.vs, _check_transform(transform, index), trim, layout_440)
     dens = (ctypes.c_uint16 * 3)(*_jfif_density(mv, marker_segments(mv, index)))
     buf = (ctypes.c_uint8 * 512)()
@@ -737,6 +739,80 @@ def _transform_geometry(i, height, width, hs, vs, name, trim, layout_440=False):
     return tuple(out)
 
 
+def _check_box(box, i):
+    """one crop entry -> None or four ints; bool, float and anything that is not four values are refused, naming the file"""
+    if box is None:
+        return None
+    ok = not isinstance(box, (str, bytes)) and hasattr(box, "__len__") and len(box) == 4 and \
+        all(isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) for v in box)
+    if not ok:
+        raise ValueError(f"file {i}: crop {box!r}: (left, upper, right, lower) as four ints, or None, required")
+    return tuple(int(v) for v in box)
+
+
+def _check_crop(crop, n):
+    """crop= -> [n] boxes or None: None, one box for every file, or a sequence of one entry (a box or None) per file"""
+    if crop is None:
+        return [None] * n
+    if isinstance(crop, (str, bytes)) or not hasattr(crop, "__len__"):
+        raise ValueError(f"file 0: crop {crop!r}: (left, upper, right, lower) as four ints, a sequence of one such box or None per file, or None required")
+    entries = list(crop)
+    if entries and not any(e is None or hasattr(e, "__len__") for e in entries):      # plain values: one box
+        return [_check_box(entries, 0)] * n
+    if len(entries) != n:
+        raise ValueError(f"file {min(len(entries), n)}: {len(entries)} crop boxes for {n} files")
+    return [_check_box(e, i) for i, e in enumerate(entries)]
+
+
+def _cut_geometry(i, frame, name, trim, layout_440, box, drop):
+    """_transform_geometry with a crop box (or None) and drop_chroma (aej_jfif_transform_geometry_host_cut) -> the output's (height,
+    width, hs, vs) and the crop's aligned corner (L, U); every refusal names the file and comes before any device work"""
+    from ._lib import load_library
+    nc = 1 if frame.ncomp == 1 else 3
+    one = drop or nc == 1                           # a one-component output: 8 x 8 MCUs, no layout
+    if name in _TRANSPOSING and frame.hs != frame.vs and not layout_440 and not one:
+        raise NotImplementedError(f"file {i}: {name} of a 4:2:2 file would be a 4:4:0 file, which neither the coders nor the decoders here have")
+    out = (ctypes.c_int32 * 6)()
+    entry = lambda b: load_library().aej_jfif_transform_geometry_host_cut(  # noqa: E731
+        frame.height, frame.width, frame.hs, frame.vs, nc, TRANSFORMS.index(name), int(trim), int(layout_440), b, int(drop), ctypes.addressof(out))
+    rc = entry(None)
+    mcu = "8 x 8" if one else f"{8 * frame.hs} x {8 * frame.vs}"
+    if rc == 1:
+        raise ValueError(f"file {i}: {name} of a {frame.width} x {frame.height} file mirrors an axis that is not a whole number of its {mcu} MCUs; "
+                         "trim=True drops the partial MCUs at that edge first")
+    if rc == 2:
+        raise ValueError(f"file {i}: {name} with trim=True leaves nothing of a {frame.width} x {frame.height} file with {mcu} MCUs")
+    if rc:
+        raise ValueError(f"file {i}: the library refuses the transform ({rc})")
+    if box is None:
+        return tuple(out)
+    h, w = out[0], out[1]
+    if not (0 <= box[0] < box[2] <= w and 0 <= box[1] < box[3] <= h):
+        raise ValueError(f"file {i}: crop {box} does not lie inside the {w} x {h} image that {name}{' with trim=True' if trim else ''} leaves: "
+                         f"0 <= left < right <= {w} and 0 <= upper < lower <= {h} required (boxes are not clamped)")
+    rc = entry(ctypes.addressof((ctypes.c_int32 * 4)(*box)))
+    if rc:
+        raise ValueError(f"file {i}: the library refuses the crop {box} ({rc})")
+    return tuple(out)
+
+
+def transform_crop_box(data, transform, crop, trim: bool = False, index: int = 0, grey: bool = False, layout_440: bool = False,
+                       drop_chroma: bool = False):
+    """-> (left, upper, right, lower) that standard_jpeg_transform_many really keeps of one file under one transform name and one crop
+    box, in the coordinates of the transformed (and trimmed) image (host only): the box with its upper-left corner moved up and left to
+    the output's MCU grid -- 8 hs x 8 vs of the output, 8 x 8 for a one-component one -- as jpegtran -crop moves it.  The file written is
+    right - left wide and lower - upper high; an annotation at (x, y) of the transformed image is at (x - left, y - upper) of it.  The
+    refusals are standard_jpeg_transform_many's."""
+    trim, grey, layout_440 = _check_bool("trim", trim), _check_bool("grey", grey), _check_bool("layout_440", layout_440)
+    drop_chroma = _check_bool("drop_chroma", drop_chroma)
+    box = _check_box(crop, index)
+    if box is None:
+        raise ValueError(f"file {index}: crop None: a box required")
+    (_, is_prog, d, _), = _parse_sources([data], transcoder=True, start=index, grey=grey, layout_440=layout_440)
+    g = _cut_geometry(index, d[0] if is_prog else d, _check_transform(transform, index), trim, layout_440, box, drop_chroma)
+    return (g[4], g[5], box[2], box[3])
+
+
 def _check_transform(name, i):
     if not isinstance(name, str) or name not in TRANSFORMS:
         raise ValueError(f"file {i}: unknown transform {name!r}: one of {', '.join(TRANSFORMS)} required" +
@@ -745,12 +821,21 @@ def _check_transform(name, i):
 
 
 def transform_prefix(data, transform, progressive: bool = False, trim: bool = False, index: int = 0, grey: bool = False,
-                     layout_440: bool = False) -> bytes:
+                     layout_440: bool = False, crop=None, drop_chroma: bool = False) -> bytes:
     """The bytes SOI .. end of SOF0 / SOF2 that standard_jpeg_transform_many writes for one file under one transform name
     (aej_jfif_transform_headers_host, host only): transcode_prefix with the output's size and sampling and, for a transposing
     transform, every quantisation table transposed.  grey, layout_440: as standard_jpeg_transform_many (with layout_440 the entry is
-    aej_jfif_transform_headers_host_440: a transposed 4:2:2 frame carries the sampling byte 0x12)."""
+    aej_jfif_transform_headers_host_440: a transposed 4:2:2 frame carries the sampling byte 0x12).  crop (one box, or None),
+    drop_chroma: as standard_jpeg_transform_many (aej_jfif_transform_headers_host_cut): the cropped size; for a dropped chroma one DQT
+    and the one-component frame header."""
     progressive, trim = _check_bool("progressive", progressive), _check_bool("trim", trim)
+    box = _check_box(crop, index)
+    if _check_bool("drop_chroma", drop_chroma) or box is not None:
+        layout_440 = _check_bool("layout_440", layout_440)
+        b4 = (ctypes.c_int32 * 4)(*(box or (0, 0, 0, 0)))
+        return _prefix(data, index, transform, trim, lambda lib, src, dst: lib.aej_jfif_transform_headers_host_cut(
+            *src, int(progressive), TRANSFORMS.index(transform), int(trim), int(layout_440), ctypes.addressof(b4), int(drop_chroma), *dst),
+            grey, layout_440, (box, drop_chroma))
     if _check_bool("layout_440", layout_440):
         return _prefix(data, index, transform, trim, lambda lib, src, dst: lib.aej_jfif_transform_headers_host_440(
             *src, int(progressive), TRANSFORMS.index(transform), int(trim), 1, *dst), grey, True)
@@ -760,7 +845,7 @@ def transform_prefix(data, transform, progressive: bool = False, trim: bool = Fa
 
 def standard_jpeg_transform_many(files, transform, progressive: bool = False, trim: bool = False, device: int = 0,
                                  keep_metadata: bool = False, grey: bool = False, restart_marker_blocks: int = 0,
-                                 restart_marker_rows: int = 0, layout_440: bool = False) -> List[bytes]:
+                                 restart_marker_rows: int = 0, layout_440: bool = False, crop=None, drop_chroma: bool = False) -> List[bytes]:
     """Lossless flip, rotation or transposition on the device: standard_jpeg_transcode_many with the files' quantised coefficients
     rearranged between the Huffman decode and the entropy coders (one kernel in the place of the transcoder's bridge), so that no
     sample is quantised a second time -- ``jpegtran -flip / -rotate / -transpose / -transverse``.  files, progressive, device and
@@ -794,15 +879,36 @@ def standard_jpeg_transform_many(files, transform, progressive: bool = False, tr
     0x12), one of a 4:4:0 source a 4:2:2 file, and 4:4:0 sources are accepted under every transform; the MCU rules above hold with
     hs, vs = 1, 2.  Such outputs need layout_440=True again to be read back by this library; Pillow and libjpeg read them as they are.
 
-    Not built: without layout_440 a transposing transform of a 4:2:2 file (it would be 4:4:0; NotImplementedError); crop.  Every refusal
-    names the file and comes before any device work; there is no CPU fallback."""
+    crop: None, one box for every file, or a sequence of one entry per file, an entry being a box or None -- ``jpegtran -crop``, with
+    no second quantisation.  A box is (left, upper, right, lower) as Image.crop takes it, four ints (bool refused), in the coordinates
+    of the image AFTER the transform and its trim: the upright image for "exif".  With H', W' that image's size 0 <= left < right <= W'
+    and 0 <= upper < lower <= H' are required (ValueError naming the file; boxes are not clamped, and a box reaching into the strip a
+    trim dropped is refused).  The upper-left corner moves up and left to the output's MCU grid, as jpegtran moves it: with mw, mh the
+    output's MCU size, L = left - left % mw, U = upper - upper % mh, and the file is right - L wide, lower - U high and holds
+    [U:lower, L:right] of the transformed image (transform_crop_box gives L, U, right, lower).  trim / perfect are decided on the whole
+    source first; the new right and bottom edges may cut an MCU, whose dummy blocks are then libjpeg's.  The box of the whole image
+    writes the bytes of the call without it; restart intervals count on the cropped output's MCU grid.
+
+    drop_chroma=True (TypeError for a value that is not a bool): ``jpegtran -grayscale``: a three-component source is written as a
+    one-component file, exactly as the transcoder writes a grey source -- one DQT (the luma table as table 0, transposed by a transposing
+    transform), the frame sampling byte 0x11, the luma component's id, one non-interleaved scan or libjpeg's six-scan progression --
+    whose blocks are the source's real luma blocks.  For such a file the MCU of every rule above is 8 x 8: a mirrored axis has to be a
+    multiple of 8, trim=True drops the partial 8-pixel strip, the crop aligns to 8, and a transposing transform of a 4:2:2 source needs
+    no layout_440.  One-component sources still need grey=True and pass through unchanged.  Both keywords combine freely with each
+    other and with every keyword above.
+
+    Not built: without layout_440 a transposing transform of a 4:2:2 file that keeps its chroma (it would be 4:4:0; NotImplementedError);
+    jpegtran's -drop and -wipe, the forced-size "f" suffix of -crop and offsets from the right or bottom edge.  EXIF pixel-dimension tags
+    are not rewritten after a crop either.  Every refusal names the file and comes before any device work; there is no CPU fallback."""
     progressive, keep_metadata = _check_bool("progressive", progressive), _check_bool("keep_metadata", keep_metadata)
     trim, grey, layout_440 = _check_bool("trim", trim), _check_bool("grey", grey), _check_bool("layout_440", layout_440)
+    drop_chroma = _check_bool("drop_chroma", drop_chroma)
     rst = _check_restart(restart_marker_blocks, restart_marker_rows)
     files = list(files)
     if not files:
         raise ValueError("standard_jpeg_transform_many needs at least one file")
     n = len(files)
+    boxes = _check_crop(crop, n)
     if isinstance(transform, str):
         names = None if transform == "exif" else [_check_transform(transform, 0)] * n
     else:
@@ -810,6 +916,8 @@ def standard_jpeg_transform_many(files, transform, progressive: bool = False, tr
         if len(names) != n:
             raise ValueError(f"file {min(len(names), n)}: {len(names)} transforms for {n} files")
         names = [_check_transform(t, i) for i, t in enumerate(names)]
+    if drop_chroma or any(b is not None for b in boxes):
+        return _transcode_many(files, progressive, device, keep_metadata, names, trim, names is None, grey, rst, layout_440, (boxes, drop_chroma))
     return _transcode_many(files, progressive, device, keep_metadata, names, trim, names is None, grey, rst, layout_440)
 
 
@@ -853,10 +961,11 @@ def standard_jpeg_transcode_many(files, progressive: bool = False, device: int =
     return _transcode_many(files, progressive, device, keep_metadata, None, False, False, grey, rst, layout_440)
 
 
-def _transcode_many(files, progressive, device, keep_metadata, names, trim, exif, grey=False, rst=(0, 0), layout_440=False):
+def _transcode_many(files, progressive, device, keep_metadata, names, trim, exif, grey=False, rst=(0, 0), layout_440=False, cut=None):
     """the transcode (names None and not exif) and the transform: names[i] is file i's transform, exif takes it from the file; rst:
     (restart_marker_blocks, restart_marker_rows) -- (0, 0) goes through the entries without restart arguments; layout_440: the one pair
-    of _440 entries serves transcode and transform, with the restart arguments always"""
+    of _440 entries serves transcode and transform, with the restart arguments always; cut: None, or ([n] crop boxes or None,
+    drop_chroma) -- the pair of _cut entries then, which take layout_440 as a value"""
     global _last_transcode_groups
     from ._lib import JpegDecDesc, JpegProgFrame, JpegProgScan
     n = len(files)
@@ -871,7 +980,9 @@ def _transcode_many(files, progressive, device, keep_metadata, names, trim, exif
         at = _exif_orientation_at(mv, segs) if exif else None
         if at and 1 <= at[0] <= 8:
             names[i] = _EXIF_TRANSFORM[at[0]]
-        if names[i] != "none":
+        if cut is not None:
+            _cut_geometry(i, parsed[i][0] if is_prog else parsed[i], names[i], trim, layout_440, cut[0][i], cut[1])
+        elif names[i] != "none":
             frame = parsed[i][0] if is_prog else parsed[i]
             _transform_geometry(i, frame.height, frame.width, frame.hs, frame.vs, names[i], trim, layout_440)
         if keep_metadata:
@@ -897,7 +1008,12 @@ def _transcode_many(files, progressive, device, keep_metadata, names, trim, exif
     rst440 = (int(rst[0]), int(rst[1]), 1)
     rst = tuple(rst) if any(rst) else ()            # the _rst entries' two extra arguments
     sfx = "_rst" if rst else ""
-    if layout_440:
+    if cut is not None:
+        boxes = np.ascontiguousarray(np.array([cut[0][i] or (0, 0, 0, 0) for i in order], np.int32))      # right == 0: no crop
+        cut_args = (int(rst440[0]), int(rst440[1]), int(layout_440), boxes.ctypes.data, int(cut[1]))
+        nws = int(lib.aej_jfif_transform_workspace_bytes_cut(ctx.handle, ctypes.addressof(descs), nb, ctypes.addressof(frames), ctypes.addressof(pscans),
+                                                             npg, int(progressive), codes.ctypes.data, int(trim), *cut_args))
+    elif layout_440:
         nws = int(lib.aej_jfif_transform_workspace_bytes_440(ctx.handle, ctypes.addressof(descs), nb, ctypes.addressof(frames), ctypes.addressof(pscans),
                                                              npg, int(progressive), codes.ctypes.data, int(trim), *rst440))
     elif plain:
@@ -918,7 +1034,9 @@ def _transcode_many(files, progressive, device, keep_metadata, names, trim, exif
             ctypes.addressof(pscans), npg, data.data_ptr(), ctypes.c_uint64(data.numel()), data_off.ctypes.data, dens.ctypes.data, int(progressive))
     tail = (offsets.data_ptr(), lengths.data_ptr(), ctypes.addressof(total), status.data_ptr(), ctypes.addressof(groups), ws.data_ptr(),
             ctypes.c_uint64(nws))
-    if layout_440:
+    if cut is not None:
+        call = lambda o, c: lib.aej_jfif_transform_batch_cut(*head, codes.ctypes.data, int(trim), *cut_args, o.data_ptr(), ctypes.c_uint64(c), *tail)  # noqa: E731
+    elif layout_440:
         call = lambda o, c: lib.aej_jfif_transform_batch_440(*head, codes.ctypes.data, int(trim), *rst440, o.data_ptr(), ctypes.c_uint64(c), *tail)  # noqa: E731
     elif plain:
         call = lambda o, c: getattr(lib, "aej_jfif_transcode_batch" + sfx)(*head, *rst, o.data_ptr(), ctypes.c_uint64(c), *tail)  # noqa: E731

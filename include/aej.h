@@ -768,6 +768,54 @@ AEJ_API int aej_jfif_transform_batch_440(aej_ctx *ctx, const aej_jpegdec_desc *d
                                          uint8_t *out, uint64_t out_capacity, int64_t *offsets, int64_t *lengths, uint64_t *total_host,
                                          int32_t *status, int32_t *n_groups_host, void *workspace, uint64_t workspace_bytes);
 
+/* ---- lossless crop and chroma drop in the transform (standard_jpeg_transform_many crop=, drop_chroma=) --------------------------------
+ * What `jpegtran -crop WxH+X+Y` and `jpegtran -grayscale` do, on the device, with or without a transform in the same call.  The _cut
+ * entries are the _440 entries with two more arguments after layout_440, and with boxes NULL and drop_chroma 0 they answer exactly as
+ * those (the kernel of these entries, k_jt_cut, is launched only by a call in which a file has a crop or drops its chroma).
+ *   boxes4_host (headers, geometry, coefs: box4_host, the one box): NULL, or int32 [n_base + n_prog][4] in the call's file order: left,
+ *     upper, right, lower in Pillow's Image.crop convention, in the coordinates of the image AFTER the transform and its trim (H', W'
+ *     below; the upright image of an EXIF auto-orient), where jpegtran applies -crop.  right == 0: no crop for that file.  Required:
+ *     0 <= left < right <= W' and 0 <= upper < lower <= H'; nothing is clamped, and a box reaching into a strip the trim dropped is
+ *     refused (AEJ_ERR_ARG, the message names the file; geometry: AEJ_JFIF_TRANSFORM_CROP_RANGE).  The corner moves up and left to the
+ *     OUTPUT's MCU grid as jpegtran moves it: with mw = 8 hs', mh = 8 vs' (8, 8 for a one-component output) L = left - left % mw,
+ *     U = upper - upper % mh, and the file written is right - L wide, lower - U high and holds [U, lower) x [L, right) of the transformed
+ *     image: every block is the transformed image's block, none is quantised again.  Where the new right / bottom edge cuts an MCU the
+ *     dummy blocks are written as libjpeg writes them.  trim / -perfect are decided on the whole source first, as without a crop.  The
+ *     box of the whole image (0, 0, W', H') is no crop: the bytes are those of the call without it.  Restart intervals count on the
+ *     cropped output's MCU grid; files are grouped by their output, so crops of equal size share an entropy chain.
+ *   drop_chroma (0 or 1; AEJ_ERR_ARG otherwise, a workspace size of 0), for every file of the call: a three-component source is written
+ *     as a one-component file, as the transcoder writes a one-component source: one DQT (the luma table as table 0, transposed by a
+ *     transposing code), a one-component frame header (sampling byte 0x11) with the luma component's id, one non-interleaved scan or the
+ *     six-scan progression.  Its blocks are the source's REAL luma blocks in raster order, and the MCU of every rule above is 8 x 8: a
+ *     mirrored axis has to be a multiple of 8, trim drops the partial 8-pixel strip, the crop aligns to 8, and a transposing code on a
+ *     4:2:2 source needs no layout_440.  A one-component source passes through unchanged.
+ * aej_jfif_transform_geometry_host_cut, _coefs_host_cut take `components` (3, or 1: the aej_jfif_transform_coefs_grey_host layout of
+ *   the source) after vs.  out6_host (may be NULL): the output's height, width, hs, vs, then L and U.  _coefs_host_cut: dst_host is in the
+ *   output's order (MCU order; one component: raster order); a file of these can have 1 .. 3 blocks, so a refused geometry is AEJ_ERR_ARG
+ *   here (the geometry entry tells which).  EXIF pixel-dimension tags of carried metadata are the caller's: nothing here rewrites them.
+ * (Additions to ABI 3: no existing signature, struct layout or behaviour of a valid call changed.) */
+enum { AEJ_JFIF_TRANSFORM_CROP_RANGE = 3 };
+AEJ_API int aej_jfif_transform_geometry_host_cut(int H, int W, int hs, int vs, int components, int transform, int trim, int layout_440,
+                                                 const int32_t *box4_host, int drop_chroma, int32_t *out6_host);
+AEJ_API int64_t aej_jfif_transform_coefs_host_cut(int H, int W, int hs, int vs, int components, int transform, int trim, int layout_440,
+                                                  const int32_t *box4_host, int drop_chroma, const int16_t *src_host, int64_t src_blocks,
+                                                  int16_t *dst_host, int64_t dst_blocks);
+AEJ_API int aej_jfif_transform_headers_host_cut(const aej_jpegdec_desc *desc_host, const aej_jpegprog_frame *frame_host, const uint16_t *density3_host,
+                                                int progressive, int transform, int trim, int layout_440, const int32_t *box4_host, int drop_chroma,
+                                                uint8_t *out_host, int capacity);
+AEJ_API uint64_t aej_jfif_transform_workspace_bytes_cut(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base,
+                                                        const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *pscans_host, int n_prog,
+                                                        int progressive, const int32_t *transforms_host, int trim, int restart_blocks,
+                                                        int restart_rows, int layout_440, const int32_t *boxes4_host, int drop_chroma);
+AEJ_API int aej_jfif_transform_batch_cut(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base, const uint8_t *scans, uint64_t scans_bytes,
+                                         const int64_t *scan_offsets_host, const aej_jpegprog_frame *frames_host,
+                                         const aej_jpegprog_scan *pscans_host, int n_prog, const uint8_t *data, uint64_t data_bytes,
+                                         const int64_t *data_offsets_host, const uint16_t *density_host, int progressive,
+                                         const int32_t *transforms_host, int trim, int restart_blocks, int restart_rows, int layout_440,
+                                         const int32_t *boxes4_host, int drop_chroma, uint8_t *out, uint64_t out_capacity, int64_t *offsets,
+                                         int64_t *lengths, uint64_t *total_host, int32_t *status, int32_t *n_groups_host, void *workspace,
+                                         uint64_t workspace_bytes);
+
 /* ---- Pillow's resize, reduce and thumbnail for packed 8-bit RGB images (resize_many, standard_jpeg_thumbnail_many) ------------------
  * Image.resize with the convolution filters, Image.reduce and the reducing_gap step of resize, bit for bit, for many images of
  * different sizes in one call (csrc/resample.hip).  An image is uint8 [h][w][3], packed.  Per image, in this order:
