@@ -255,11 +255,15 @@ SIGNATURES = {
     "aej_jpegdec_sync_rounds": (_I64, [_P]),
     "aej_jpegdec_workspace_bytes_scaled": (_U64, [_P, _P, _I, _P]),
     "aej_jpegdec_batch_scaled": (_I, [_P, _P, _I, _P, _P, _U64, _P, _P, _U64, _P, _P, _P, _U64]),
+    "aej_jpegdec_workspace_bytes_mode": (_U64, [_P, _P, _I, _P, _P]),
+    "aej_jpegdec_batch_mode": (_I, [_P, _P, _I, _P, _P, _P, _U64, _P, _P, _U64, _P, _P, _P, _U64]),
     "aej_jpegprog_parse_host": (_I, [_P, _U64, _P, _P, _I, _P, _I]),
     "aej_jpegprog_workspace_bytes": (_U64, [_P, _P, _P, _I]),
     "aej_jpegprog_batch": (_I, [_P, _P, _P, _I, _P, _U64, _P, _P, _U64, _P, _P, _P, _U64]),
     "aej_jpegprog_workspace_bytes_scaled": (_U64, [_P, _P, _P, _I, _P]),
     "aej_jpegprog_batch_scaled": (_I, [_P, _P, _P, _I, _P, _P, _U64, _P, _P, _U64, _P, _P, _P, _U64]),
+    "aej_jpegprog_workspace_bytes_mode": (_U64, [_P, _P, _P, _I, _P, _P]),
+    "aej_jpegprog_batch_mode": (_I, [_P, _P, _P, _I, _P, _P, _P, _U64, _P, _P, _U64, _P, _P, _P, _U64]),
     "aej_jfif_transcode_headers_host": (_I, [_P, _P, _P, _I, _P, _I]),
     "aej_jfif_transcode_workspace_bytes": (_U64, [_P, _P, _I, _P, _P, _I, _I]),
     "aej_jfif_transcode_batch": (_I, [_P, _P, _I, _P, _U64, _P, _P, _P, _I, _P, _U64, _P, _P, _I, _P, _U64, _P, _P, _P, _P, _P, _P, _U64]),
@@ -300,6 +304,8 @@ SIGNATURES = {
     "aej_resample_taps_host": (_I, [_I, ctypes.c_float, ctypes.c_float, _I, _I, _P, _P, _I64]),
     "aej_resample_workspace_bytes": (_U64, [_P, _P, _I]),
     "aej_resample_batch": (_I, [_P, _P, _I, _P, _U64, _P, _U64, _P, _U64]),
+    "aej_resample_workspace_bytes_ch": (_U64, [_P, _P, _I, _P]),
+    "aej_resample_batch_ch": (_I, [_P, _P, _I, _P, _P, _U64, _P, _U64, _P, _U64]),
     "aej_test_jpegprog_coefs": (_I, [_P, _P, _P, _I, _P, _U64, _P, _I, _P, _U64, _P, _P, _U64]),             # include/aej_testing.h (tests only)
     "aej_test_jpegprog_coefs_host": (_I, [_P, _P, _P, _U64, _I, _P, _U64]),                                 # include/aej_testing.h (tests only)
     "aej_test_jpegdec_idct_host": (_I, [_P, _P, _I, _P]),                                                   # include/aej_testing.h (tests only)

@@ -317,7 +317,7 @@ int jfifprog_scan_device(hipStream_t st, const short *coefs_host, long long n, i
 #include "jpegdec_core.h"
 
 namespace aej {
-struct JdBufSizes { long long chunks, segs, slots, blocks, clean, planes, px, grp[3], grp440[3]; };      // totals over the files of one call (grp, grp440: JdFile::grp_base, ::grp440_base)
+struct JdBufSizes { long long chunks, segs, slots, blocks, clean, planes, px, grp[3], grp440[3], grpl[4]; };      // totals over the files of one call (grp, grp440, grpl: JdFile::grp_base, ::grp440_base, ::grpl_base)
 struct JdBufs {
     JdFile *files; aej_jpegdec_desc *descs; int *last_change;      // one upload: files, descriptors, the "last round that changed" word
     int *cnt; long long *pre, *clean_len; JdSeg *segs; unsigned char *clean; JdSlots sl; short *coef; unsigned char *planes;
@@ -340,10 +340,11 @@ bool jpegdec_descs_ok(const aej_jpegdec_desc *descs, int n);      // n >= 1 desc
 // one un-stuffing stream of len stuffed bytes and n_segments restart segments, subsequences of S bits: F's stream fields, z's totals
 void jpeg_stream_layout(long long len, int n_segments, int S, JdFile &F, JdBufSizes &z);
 // one file's coefficient blocks and, decoded at scale 1 << shift, its sample planes and pixels (shift 0) or its workgroups of the
-// scaled kernel (1..3) (d's frame fields): F's reconstruction fields, z's totals
+// scaled kernel (1..3), or, with kJdLuma added to shift, its workgroups of the luma kernel (d's frame fields): F's reconstruction
+// fields, z's totals
 void jpeg_recon_layout(const aej_jpegdec_desc &d, int shift, JdFile &F, JdBufSizes &z);
 inline int jpeg_scale_shift(int scale) { return scale == 1 ? 0 : scale == 2 ? 1 : scale == 4 ? 2 : scale == 8 ? 3 : -1; }      // -1: not a scale
-// shifts: log2 of every file's scale, or NULL for all at full size
+// shifts: log2 of every file's scale (+ kJdLuma for a file that leaves as its luma plane), or NULL for all at full size, RGB
 void jpegdec_layout(const aej_jpegdec_desc *descs, int n, int S, std::vector<JdFile> &files, JdBufSizes &z, const int *shifts = nullptr);
 unsigned long long jpegdec_carve(void *base, int n, const JdBufSizes &z, JdBufs &w);
 hipError_t launch_jpegdec_begin(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, const void *blob_host, unsigned long long blob_bytes,
@@ -492,7 +493,7 @@ long long jfifmany_coefs_host(int W, int H, int quality, int ss, const unsigned 
 
 }  // namespace aej
 
-// resample.hip: Pillow's reduce and two-pass resize of packed 8-bit RGB images (aej_resample_*)
+// resample.hip: Pillow's reduce and two-pass resize of packed 8-bit RGB and one-channel images (aej_resample_*)
 namespace aej {
 constexpr int kRsBits = 22;            // Pillow's PRECISION_BITS for 8-bit images: taps are int(k * 2^22 +- 0.5)
 constexpr int kRsThreads = 256;
@@ -514,14 +515,15 @@ struct RsConv {                        // one image of k_rs_horizontal / k_rs_ve
 };
 struct RsImage {                       // host: the stages of one image and where they read and write
     bool reduce, horizontal, vertical;
+    int ch;                            // bytes per pixel: 3, or 1
     RsReduce r; RsConv h, v;
     long long src_offset, dst_offset, src_bytes, dst_bytes, r_src, tmp_a, tmp_b, h_table, v_table;
 };
 struct RsPlan {
     std::vector<RsImage> images;
     std::vector<int> ints;             // the tables (filled on request)
-    long long n_ints = 0, tmp_bytes = 0, tiles[3] = {0, 0, 0};
-    int count[3] = {0, 0, 0};          // images in the reduce / horizontal / vertical launch
+    long long n_ints = 0, tmp_bytes = 0, tiles[2][3] = {{0, 0, 0}, {0, 0, 0}};      // [0]: the three-channel images, [1]: the one-channel ones
+    int count[2][3] = {{0, 0, 0}, {0, 0, 0}};      // images in the reduce / horizontal / vertical launch of either
 };
 struct RsBufs { unsigned char *blob, *tmp; };
 double rs_support(int filter);         // 0: not a filter
@@ -529,7 +531,7 @@ int rs_ksize(float in0, float in1, int out_size, int filter);
 void rs_taps(int in_size, float in0, float in1, int out_size, int filter, int ksize, int *bounds, int *taps);
 void rs_bounds_of_row(int in_size, float in0, float in1, int out_size, int filter, int xx, int *bounds);
 const char *rs_check(const aej_resample_desc &d, int *code);
-int resample_plan(const aej_resample_desc *descs, int n, bool fill, RsPlan &plan, const char **why, int *code);
+int resample_plan(const aej_resample_desc *descs, int n, bool fill, RsPlan &plan, const char **why, int *code, const int *channels = nullptr);
 unsigned long long resample_carve(void *base, const RsPlan &plan, RsBufs &w);
 void resample_blob(const RsPlan &plan, const RsBufs &w, const unsigned char *src, unsigned char *dst, std::vector<unsigned char> &blob);
 hipError_t launch_resample(hipStream_t st, const RsPlan &plan, const RsBufs &w, const void *blob_host, unsigned long long blob_bytes);

@@ -239,33 +239,43 @@ static int jpegprog_scan_offsets(aej_ctx *ctx, const char *fn, JpLayout &y, uint
     return 0;
 }
 
-// the RGB image of file i checked against the output and entered into the layout
-static int image_offset(aej_ctx *ctx, const char *fn, int i, int width, int height, uint64_t out_bytes, long long oo, JdFile &file)
+// the image of file i (RGB, or its luma plane: file.shift) checked against the output and entered into the layout
+static int image_offset(aej_ctx *ctx, const char *fn, int i, uint64_t out_bytes, long long oo, JdFile &file)
 {
-    if (!inside(oo, (long long)width * height * 3, out_bytes)) return fail(ctx, AEJ_ERR_ARG, "%s: file %d: image outside the output", fn, i);
+    const long long bytes = (long long)file.ow * file.oh * ((file.shift & kJdLuma) ? 1 : 3);
+    if (!inside(oo, bytes, out_bytes)) return fail(ctx, AEJ_ERR_ARG, "%s: file %d: image outside the output", fn, i);
     file.out_off = oo;
     return 0;
 }
 
 // the scales of a scaled call (NULL: every file at full size) -> log2 of each; a value that is not 1, 2, 4 or 8 is the caller's error
-static bool scale_shifts(const int *scales_host, int n, std::vector<int> &shifts, int *bad = nullptr)
+// components_host (the _mode entries; NULL: every file as RGB): 3, or 1 for a file that leaves as its luma plane (kJdLuma added to its
+// shift); anything else is the caller's error too (*bad_comp says which of the two it was)
+static bool scale_shifts(const int *scales_host, int n, std::vector<int> &shifts, int *bad = nullptr, const int *components_host = nullptr,
+                         bool *bad_comp = nullptr)
 {
     shifts.assign(n > 0 ? n : 0, 0);
     for (int i = 0; scales_host && i < n; i++)
         if ((shifts[i] = jpeg_scale_shift(scales_host[i])) < 0) { if (bad) *bad = i; return false; }
+    for (int i = 0; components_host && i < n; i++) {
+        if (components_host[i] == 1) shifts[i] |= kJdLuma;
+        else if (components_host[i] != 3) { if (bad) *bad = i; if (bad_comp) *bad_comp = true; return false; }
+    }
     return true;
 }
-static int check_scales(aej_ctx *ctx, const char *fn, const int *scales_host, int n, std::vector<int> &shifts)
+static int check_scales(aej_ctx *ctx, const char *fn, const int *scales_host, int n, std::vector<int> &shifts, const int *components_host = nullptr)
 {
     int bad = 0;
-    if (scale_shifts(scales_host, n, shifts, &bad)) return 0;
+    bool bad_comp = false;
+    if (scale_shifts(scales_host, n, shifts, &bad, components_host, &bad_comp)) return 0;
+    if (bad_comp) return fail(ctx, AEJ_ERR_ARG, "%s: file %d: %d output components (3: RGB, 1: luma)", fn, bad, components_host[bad]);
     return fail(ctx, AEJ_ERR_ARG, "%s: file %d: scale %d (1, 2, 4 or 8)", fn, bad, scales_host[bad]);
 }
 
-static uint64_t jpegdec_workspace(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host)
+static uint64_t jpegdec_workspace(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host, const int *components_host = nullptr)
 {
     std::vector<int> shifts;
-    if (!ctx || !jpegdec_descs_ok(descs_host, n) || !scale_shifts(scales_host, n, shifts)) return 0;
+    if (!ctx || !jpegdec_descs_ok(descs_host, n) || !scale_shifts(scales_host, n, shifts, nullptr, components_host)) return 0;
     std::vector<JdFile> files;
     JdBufSizes z;
     jpegdec_layout(descs_host, n, ctx->jd_subseq_bits, files, z, shifts.data());
@@ -281,6 +291,12 @@ extern "C" uint64_t aej_jpegdec_workspace_bytes(aej_ctx *ctx, const aej_jpegdec_
 extern "C" uint64_t aej_jpegdec_workspace_bytes_scaled(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host)
 {
     return scales_host ? jpegdec_workspace(ctx, descs_host, n, scales_host) : 0;
+}
+
+extern "C" uint64_t aej_jpegdec_workspace_bytes_mode(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host,
+                                                     const int *components_host)
+{
+    return jpegdec_workspace(ctx, descs_host, n, scales_host, components_host);
 }
 
 // the entropy decode of n baseline files up to the fixed point of the sync rounds: everything of aej_jpegdec_batch before the
@@ -316,8 +332,9 @@ static int jpegdec_decode(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *
     return 0;
 }
 
-// aej_jpegdec_batch (scales_host NULL: every file at full size) and aej_jpegdec_batch_scaled
-static int jpegdec_batch(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs_host, int n, const int *scales_host, const uint8_t *scans,
+// aej_jpegdec_batch (scales_host NULL: every file at full size), aej_jpegdec_batch_scaled and aej_jpegdec_batch_mode (components_host)
+static int jpegdec_batch(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs_host, int n, const int *scales_host, const int *components_host,
+                         const uint8_t *scans,
                          uint64_t scans_bytes, const int64_t *scan_offsets_host, uint8_t *out, uint64_t out_bytes, const int64_t *out_offsets_host,
                          int32_t *status, void *workspace, uint64_t workspace_bytes)
 {
@@ -325,7 +342,7 @@ static int jpegdec_batch(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *d
     if (!jpegdec_descs_ok(descs_host, n)) return fail(ctx, AEJ_ERR_ARG, "%s: no files, or a descriptor aej_jpegdec_parse_host did not write", fn);
     if (!scans || !scan_offsets_host || !out || !out_offsets_host || !status || !workspace) return null_buffer(ctx, fn);
     std::vector<int> shifts;
-    AEJ_TRY(check_scales(ctx, fn, scales_host, n, shifts));
+    AEJ_TRY(check_scales(ctx, fn, scales_host, n, shifts, components_host));
     const int S = ctx->jd_subseq_bits;
     std::vector<JdFile> files;
     JdBufSizes z;
@@ -333,7 +350,7 @@ static int jpegdec_batch(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *d
     for (int i = 0; i < n; i++) {                            // file by file, scan before image, as the errors were always reported
         const aej_jpegdec_desc &d = descs_host[i];
         AEJ_TRY(jpegdec_scan_offset(ctx, fn, d, i, scans_bytes, scan_offsets_host[i], files[i]));
-        AEJ_TRY(image_offset(ctx, fn, i, files[i].ow, files[i].oh, out_bytes, out_offsets_host[i], files[i]));
+        AEJ_TRY(image_offset(ctx, fn, i, out_bytes, out_offsets_host[i], files[i]));
     }
     JdBufs w;
     const unsigned long long need = jpegdec_carve(workspace, n, z, w);
@@ -347,7 +364,7 @@ extern "C" int aej_jpegdec_batch(aej_ctx *ctx, const aej_jpegdec_desc *descs_hos
                                  const int64_t *scan_offsets_host, uint8_t *out, uint64_t out_bytes, const int64_t *out_offsets_host,
                                  int32_t *status, void *workspace, uint64_t workspace_bytes)
 {
-    return jpegdec_batch(ctx, __func__, descs_host, n, nullptr, scans, scans_bytes, scan_offsets_host, out, out_bytes, out_offsets_host, status,
+    return jpegdec_batch(ctx, __func__, descs_host, n, nullptr, nullptr, scans, scans_bytes, scan_offsets_host, out, out_bytes, out_offsets_host, status,
                          workspace, workspace_bytes);
 }
 
@@ -356,8 +373,16 @@ extern "C" int aej_jpegdec_batch_scaled(aej_ctx *ctx, const aej_jpegdec_desc *de
                                         const int64_t *out_offsets_host, int32_t *status, void *workspace, uint64_t workspace_bytes)
 {
     if (!scales_host) return ctx ? null_buffer(ctx, __func__) : AEJ_ERR_ARG;
-    return jpegdec_batch(ctx, __func__, descs_host, n, scales_host, scans, scans_bytes, scan_offsets_host, out, out_bytes, out_offsets_host, status,
-                         workspace, workspace_bytes);
+    return jpegdec_batch(ctx, __func__, descs_host, n, scales_host, nullptr, scans, scans_bytes, scan_offsets_host, out, out_bytes, out_offsets_host,
+                         status, workspace, workspace_bytes);
+}
+
+extern "C" int aej_jpegdec_batch_mode(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host, const int *components_host,
+                                      const uint8_t *scans, uint64_t scans_bytes, const int64_t *scan_offsets_host, uint8_t *out, uint64_t out_bytes,
+                                      const int64_t *out_offsets_host, int32_t *status, void *workspace, uint64_t workspace_bytes)
+{
+    return jpegdec_batch(ctx, __func__, descs_host, n, scales_host, components_host, scans, scans_bytes, scan_offsets_host, out, out_bytes,
+                         out_offsets_host, status, workspace, workspace_bytes);
 }
 
 extern "C" int aej_test_jpegdec_idct_host(const int16_t *coef_host, const uint16_t *qt_host, int size, uint8_t *out_host)
@@ -401,11 +426,12 @@ extern "C" int aej_jpegprog_parse_host_440(const uint8_t *data_host, uint64_t nb
     return jp_parse_host(data_host, nbytes, frame_host, scans_host, scan_capacity, msg, msg_capacity, layout_440);
 }
 
-static uint64_t jpegprog_workspace(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n, const int *scales_host)
+static uint64_t jpegprog_workspace(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n, const int *scales_host,
+                                   const int *components_host = nullptr)
 {
     JpLayout y;
     std::vector<int> shifts;
-    if (!ctx || !scale_shifts(scales_host, n, shifts) || !jpegprog_layout(frames_host, scans_host, n, y, shifts.data())) return 0;
+    if (!ctx || !scale_shifts(scales_host, n, shifts, nullptr, components_host) || !jpegprog_layout(frames_host, scans_host, n, y, shifts.data())) return 0;
     JpBufs w;
     return jpegprog_carve(nullptr, y, w);
 }
@@ -421,24 +447,30 @@ extern "C" uint64_t aej_jpegprog_workspace_bytes_scaled(aej_ctx *ctx, const aej_
     return scales_host ? jpegprog_workspace(ctx, frames_host, scans_host, n, scales_host) : 0;
 }
 
+extern "C" uint64_t aej_jpegprog_workspace_bytes_mode(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
+                                                      const int *scales_host, const int *components_host)
+{
+    return jpegprog_workspace(ctx, frames_host, scans_host, n, scales_host, components_host);
+}
+
 // levels [0, n_levels) of the entropy stage, then either the reconstruction into `out` or (tests) a copy of the coefficients
 static int jpegprog_run(aej_ctx *ctx, const char *fn, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
                         const int *scales_host, const uint8_t *data, uint64_t data_bytes, const int64_t *data_offsets_host, int n_levels, uint8_t *out, uint64_t out_bytes,
                         const int64_t *out_offsets_host, int16_t *coef_out, uint64_t coef_blocks, int32_t *status, void *workspace,
-                        uint64_t workspace_bytes)
+                        uint64_t workspace_bytes, const int *components_host = nullptr)
 {
     if (!ctx) return AEJ_ERR_ARG;
     AEJ_TRY(refuse_in_flight(ctx, fn));
     JpLayout y;
     std::vector<int> shifts;
-    AEJ_TRY(check_scales(ctx, fn, scales_host, n, shifts));
+    AEJ_TRY(check_scales(ctx, fn, scales_host, n, shifts, components_host));
     if (!jpegprog_layout(frames_host, scans_host, n, y, shifts.data()))
         return fail(ctx, AEJ_ERR_ARG, "%s: no files, or descriptors aej_jpegprog_parse_host did not write", fn);
     if (!data || !data_offsets_host || !status || !workspace || (!out && !coef_out) || (out && !out_offsets_host))
         return null_buffer(ctx, fn);
     AEJ_TRY(jpegprog_scan_offsets(ctx, fn, y, data_bytes, data_offsets_host));
     for (int i = 0; out && i < n; i++)
-        AEJ_TRY(image_offset(ctx, fn, i, y.ffiles[i].ow, y.ffiles[i].oh, out_bytes, out_offsets_host[i], y.ffiles[i]));
+        AEJ_TRY(image_offset(ctx, fn, i, out_bytes, out_offsets_host[i], y.ffiles[i]));
     if (coef_out && (uint64_t)y.fz.blocks > coef_blocks) return fail(ctx, AEJ_ERR_CAPACITY, "%s: %lld coefficient blocks, room for %llu", fn, y.fz.blocks, (unsigned long long)coef_blocks);
     JpBufs w;
     const unsigned long long need = jpegprog_carve(workspace, y, w);
@@ -470,6 +502,16 @@ extern "C" int aej_jpegprog_batch_scaled(aej_ctx *ctx, const aej_jpegprog_frame 
     if (!out || !scales_host) return ctx ? null_buffer(ctx, __func__) : AEJ_ERR_ARG;
     return jpegprog_run(ctx, __func__, frames_host, scans_host, n, scales_host, data, data_bytes, data_offsets_host, 1 << 30, out, out_bytes,
                         out_offsets_host, nullptr, 0, status, workspace, workspace_bytes);
+}
+
+extern "C" int aej_jpegprog_batch_mode(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
+                                       const int *scales_host, const int *components_host, const uint8_t *data, uint64_t data_bytes,
+                                       const int64_t *data_offsets_host, uint8_t *out, uint64_t out_bytes, const int64_t *out_offsets_host,
+                                       int32_t *status, void *workspace, uint64_t workspace_bytes)
+{
+    if (!out) return ctx ? null_buffer(ctx, __func__) : AEJ_ERR_ARG;
+    return jpegprog_run(ctx, __func__, frames_host, scans_host, n, scales_host, data, data_bytes, data_offsets_host, 1 << 30, out, out_bytes,
+                        out_offsets_host, nullptr, 0, status, workspace, workspace_bytes, components_host);
 }
 
 extern "C" int aej_test_jpegprog_coefs(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,

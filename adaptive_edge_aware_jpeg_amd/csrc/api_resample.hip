@@ -16,37 +16,48 @@ extern "C" int aej_resample_taps_host(int in_size, float in0, float in1, int out
 }
 
 // the plan of a call, or the refusal of its first bad descriptor (fn NULL: quietly, for the size query)
-static int resample_layout(aej_ctx *ctx, const char *fn, const aej_resample_desc *descs_host, int n, bool fill, RsPlan &plan)
+static int resample_layout(aej_ctx *ctx, const char *fn, const aej_resample_desc *descs_host, int n, bool fill, RsPlan &plan, const int *channels_host)
 {
     if (n < 1) return fn ? fail(ctx, AEJ_ERR_ARG, "%s: no images", fn) : AEJ_ERR_ARG;
     const char *why = nullptr;
     int code = AEJ_ERR_ARG;
-    const int bad = resample_plan(descs_host, n, fill, plan, &why, &code);
+    const int bad = resample_plan(descs_host, n, fill, plan, &why, &code, channels_host);
     if (bad >= 0) return fn ? fail(ctx, code, "%s: image %d: %s", fn, bad, why) : code;
-    for (int s = 0; s < 3; s++)
-        if (plan.tiles[s] > 0x7fffffffLL) return fn ? fail(ctx, AEJ_ERR_UNSUPPORTED, "%s: more than 2^31 workgroups in one launch", fn) : AEJ_ERR_UNSUPPORTED;
+    for (int s = 0; s < 6; s++)
+        if (plan.tiles[s / 3][s % 3] > 0x7fffffffLL) return fn ? fail(ctx, AEJ_ERR_UNSUPPORTED, "%s: more than 2^31 workgroups in one launch", fn) : AEJ_ERR_UNSUPPORTED;
     return 0;
 }
 
-extern "C" uint64_t aej_resample_workspace_bytes(aej_ctx *ctx, const aej_resample_desc *descs_host, int n)
+static uint64_t resample_workspace(aej_ctx *ctx, const aej_resample_desc *descs_host, int n, const int *channels_host)
 {
     RsPlan plan;
-    if (!ctx || !descs_host || resample_layout(ctx, nullptr, descs_host, n, false, plan)) return 0;
+    if (!ctx || !descs_host || resample_layout(ctx, nullptr, descs_host, n, false, plan, channels_host)) return 0;
     RsBufs w;
     return resample_carve(nullptr, plan, w);
 }
 
-extern "C" int aej_resample_batch(aej_ctx *ctx, const aej_resample_desc *descs_host, int n, const uint8_t *src, uint64_t src_bytes, uint8_t *dst,
-                                  uint64_t dst_bytes, void *workspace, uint64_t workspace_bytes)
+extern "C" uint64_t aej_resample_workspace_bytes(aej_ctx *ctx, const aej_resample_desc *descs_host, int n)
 {
-    AEJ_TRY(enter(ctx, __func__));
-    if (!descs_host || !src || !dst || !workspace) return null_buffer(ctx, __func__);
+    return resample_workspace(ctx, descs_host, n, nullptr);
+}
+
+extern "C" uint64_t aej_resample_workspace_bytes_ch(aej_ctx *ctx, const aej_resample_desc *descs_host, int n, const int *channels_host)
+{
+    return resample_workspace(ctx, descs_host, n, channels_host);
+}
+
+// aej_resample_batch (channels_host NULL: every image three channels) and aej_resample_batch_ch
+static int resample_batch(aej_ctx *ctx, const char *fn, const aej_resample_desc *descs_host, int n, const int *channels_host, const uint8_t *src,
+                          uint64_t src_bytes, uint8_t *dst, uint64_t dst_bytes, void *workspace, uint64_t workspace_bytes)
+{
+    AEJ_TRY(enter(ctx, fn));
+    if (!descs_host || !src || !dst || !workspace) return null_buffer(ctx, fn);
     RsPlan plan;
-    AEJ_TRY(resample_layout(ctx, __func__, descs_host, n, true, plan));
+    AEJ_TRY(resample_layout(ctx, fn, descs_host, n, true, plan, channels_host));
     for (int i = 0; i < n; i++) {
         const RsImage &im = plan.images[i];
-        if ((uint64_t)im.src_offset + (uint64_t)im.src_bytes > src_bytes) return fail(ctx, AEJ_ERR_ARG, "%s: image %d: source outside the input", __func__, i);
-        if ((uint64_t)im.dst_offset + (uint64_t)im.dst_bytes > dst_bytes) return fail(ctx, AEJ_ERR_ARG, "%s: image %d: image outside the output", __func__, i);
+        if ((uint64_t)im.src_offset + (uint64_t)im.src_bytes > src_bytes) return fail(ctx, AEJ_ERR_ARG, "%s: image %d: source outside the input", fn, i);
+        if ((uint64_t)im.dst_offset + (uint64_t)im.dst_bytes > dst_bytes) return fail(ctx, AEJ_ERR_ARG, "%s: image %d: image outside the output", fn, i);
     }
     RsBufs w;
     AEJ_TRY(check_workspace(ctx, resample_carve(workspace, plan, w), workspace_bytes));
@@ -56,4 +67,16 @@ extern "C" int aej_resample_batch(aej_ctx *ctx, const aej_resample_desc *descs_h
     AEJ_HIP_CHECK(launch_resample(ctx->stream, plan, w, blob.data(), blob.size()));
     AEJ_HIP_CHECK(hipStreamSynchronize(ctx->stream));         // keeps `blob` alive until its upload has run
     return 0;
+}
+
+extern "C" int aej_resample_batch(aej_ctx *ctx, const aej_resample_desc *descs_host, int n, const uint8_t *src, uint64_t src_bytes, uint8_t *dst,
+                                  uint64_t dst_bytes, void *workspace, uint64_t workspace_bytes)
+{
+    return resample_batch(ctx, __func__, descs_host, n, nullptr, src, src_bytes, dst, dst_bytes, workspace, workspace_bytes);
+}
+
+extern "C" int aej_resample_batch_ch(aej_ctx *ctx, const aej_resample_desc *descs_host, int n, const int *channels_host, const uint8_t *src,
+                                     uint64_t src_bytes, uint8_t *dst, uint64_t dst_bytes, void *workspace, uint64_t workspace_bytes)
+{
+    return resample_batch(ctx, __func__, descs_host, n, channels_host, src, src_bytes, dst, dst_bytes, workspace, workspace_bytes);
 }

@@ -24,6 +24,8 @@
 //   k_jd_scaled_h1v2 the same for 4:4:0 files (luma 1 x 2), whose chroma IDCT stays at the luma block's size at every scale and is
 //                   up-sampled vertically: the neighbour rows the h1v2 filter needs come from the chroma blocks of the MCU rows above
 //                   and below the run (a vertical halo).  A kernel of its own, so that k_jd_scaled compiles as it did without it
+//   k_jd_luma       files that leave as their luma plane alone, [oh][ow] (libjpeg's out_color_space = JCS_GRAYSCALE; a one-component
+//                   file's samples), at scale 1, 2, 4 or 8, in the place of all of the above: k_jd_scaled's plan, luma blocks only
 // Bounds: every index derives from the host-computed JdFile layout; a file's reads stay inside its scan and its clean stream, decode loops
 // are bounded by their subsequence's bits, and coefficient writes by the segment's block count.
 #include <string.h>
@@ -545,6 +547,55 @@ __global__ __launch_bounds__(kJdThreads) void k_jd_scaled_h1v2(const JdFile *__r
     }
 }
 
+// Luma-only reconstruction, coefficients -> [oh][ow] in one kernel, at every scale 1 << kShift (0: full size) and for every layout: the
+// luma blocks of an MCU are the first hs * vs of its blocks_per_mcu whatever the chroma is, and the chroma blocks are never read.
+// k_jd_scaled's plan: workgroup `blockIdx.x` is run g - grpl_base of its file, MCUs [g0, g0 + ng) of MCU row my; m = 8 >> kShift.
+// LDS: one sample plane of 2m rows x kJdRun * 2m columns (the widest run).  Bounds: block indices stay below the file's
+// mcux * mcuy * blocks_per_mcu; LDS columns below ng * hs * m <= kCols, rows below vs * m <= kRows; only bytes of pixels (y < oh,
+// x < ow) of the file's own image are stored -- whole dwords inside a row, single bytes at its unaligned ends.
+template <int kShift>
+__global__ __launch_bounds__(kJdThreads) void k_jd_luma(const JdFile *__restrict__ files, const aej_jpegdec_desc *__restrict__ descs, int n,
+                                                        const short *__restrict__ coef, unsigned char *__restrict__ out)
+{
+    constexpr int m = 8 >> kShift, kRows = 2 * m, kCols = kJdRun * 2 * m;
+    __shared__ unsigned char sy[kRows * kCols];
+    int lo = 0, hi = n - 1;                           // the last file whose first workgroup is <= blockIdx.x
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (files[mid].grpl_base[kShift] <= (long long)blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+    const JdFile &F = files[lo];
+    const aej_jpegdec_desc &d = descs[lo];
+    const int per_row = (d.mcux + kJdRun - 1) / kJdRun, g = (int)(blockIdx.x - F.grpl_base[kShift]);
+    const int my = g / per_row, g0 = (g % per_row) * kJdRun, ng = min(kJdRun, d.mcux - g0);
+    const int hs = d.ncomp == 3 ? d.hs : 1, vs = d.ncomp == 3 ? d.vs : 1, nl = hs * vs;
+    if (my >= d.mcuy || hs > 2 || vs > 2) return;     // never: the host gives a file mcuy * per_row workgroups, the parsers these factors
+    const int bw = (d.width + 7) / 8, bh = (d.height + 7) / 8;
+    for (int i = threadIdx.x; i < ng * nl; i += kJdThreads) {
+        const int mcu = g0 + i / nl, k = i % nl, ky = k / hs, kx = k % hs;
+        if (my * vs + ky >= bh || mcu * hs + kx >= bw) continue;      // dummy block of an edge MCU
+        const short *cf = coef + (F.blk_base + ((long long)my * d.mcux + mcu) * d.blocks_per_mcu + k) * 64;
+        unsigned char *dst = sy + ky * m * kCols + ((mcu - g0) * hs + kx) * m;
+        if (kShift == 0) jd_idct_block(cf, d.qt[0], dst, kCols);      // inlined, as in k_jd_idct: 154 VGPRs, against 248 through jd_idct_block_call
+        else jd_idct_sized(cf, d.qt[0], m, dst, kCols);
+    }
+    __syncthreads();
+    const int y0 = my * vs * m, x0 = g0 * hs * m;
+    const int nrows = min(vs * m, F.oh - y0), nbytes = min(ng * hs * m, F.ow - x0);
+    unsigned char *img = out + F.out_off;
+    const int nslots = (nbytes + 6) / 4;              // dwords a row can touch: up to 3 bytes of shift
+    for (int p = threadIdx.x; p < nrows * nslots; p += kJdThreads) {
+        const int r = p / nslots, k = p % nslots;
+        unsigned char *gp = img + (long long)(y0 + r) * F.ow + x0;
+        const int a = (int)((uintptr_t)gp & 3), b0 = max(4 * k, a), b1 = min(4 * k + 4, a + nbytes);
+        const unsigned char *s = sy + r * kCols - a;  // s[b]: the byte at place b of the row's dwords (read for a <= b < a + nbytes only)
+        if (b1 - b0 == 4)
+            *reinterpret_cast<unsigned *>(gp + (4 * k - a)) = (unsigned)s[4 * k] | ((unsigned)s[4 * k + 1] << 8) | ((unsigned)s[4 * k + 2] << 16) |
+                                                              ((unsigned)s[4 * k + 3] << 24);
+        else for (int b = b0; b < b1; b++) gp[b - a] = s[b];      // the ends of a row: its own bytes only
+    }
+}
+
 // ---- host: descriptor checks, layout and launch sequence -----------------------------------------------------------------------------------
 bool jpegdec_descs_ok(const aej_jpegdec_desc *d, int n)
 {
@@ -578,11 +629,19 @@ void jpeg_recon_layout(const aej_jpegdec_desc &d, int shift, JdFile &F, JdBufSiz
     F.blk_base = z.blocks;
     F.n_blocks = (long long)d.mcux * d.mcuy * d.blocks_per_mcu;
     z.blocks += F.n_blocks;
+    const bool luma = (shift & kJdLuma) != 0;
     F.shift = shift;
+    shift &= kJdLuma - 1;
     F.ow = (d.width + (1 << shift) - 1) >> shift; F.oh = (d.height + (1 << shift) - 1) >> shift;
     for (int s = 0; s < 3; s++) { F.grp_base[s] = z.grp[s]; F.grp440_base[s] = z.grp440[s]; }
+    for (int s = 0; s < 4; s++) F.grpl_base[s] = z.grpl[s];
     F.plane_off = z.planes;
     F.px_base = z.px;
+    if (luma) {                                       // at every scale: no sample planes, no pixels of k_jd_rgb's, workgroups of k_jd_luma<shift>
+        F.pw0 = F.ph0 = F.pw1 = F.ph1 = 0;
+        z.grpl[shift] += (long long)d.mcuy * ((d.mcux + kJdRun - 1) / kJdRun);
+        return;
+    }
     if (shift) {                                      // no sample planes, no pixels of k_jd_rgb's: workgroups of k_jd_scaled<shift>
         F.pw0 = F.ph0 = F.pw1 = F.ph1 = 0;
         const bool h1v2 = d.ncomp == 3 && d.hs == 1 && d.vs == 2;      // 4:4:0: k_jd_scaled_h1v2's grid
@@ -682,8 +741,9 @@ hipError_t launch_jpegdec_finish(hipStream_t st, int n, const JdBufSizes &z, con
     return launch_jpegdec_recon(st, n, z, w, out);
 }
 
-// the files of a call that decode at scale 2, 4, 8: one launch per scale present (JdFile::shift and ::grp_base pick a file's kernel
-// and workgroups; the layout inside the kernel follows the file's sampling factors)
+// the files of a call that decode at scale 2, 4, 8, and the luma-only ones at every scale: one launch per kernel and scale present
+// (JdFile::shift and ::grp_base / ::grp440_base / ::grpl_base pick a file's kernel and workgroups; the layout inside the kernel follows
+// the file's sampling factors)
 static hipError_t launch_jpegdec_recon_scaled(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, unsigned char *out)
 {
     if (z.grp[0] > 0) hipLaunchKernelGGL(k_jd_scaled<1>, dim3((unsigned)z.grp[0]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
@@ -692,10 +752,14 @@ static hipError_t launch_jpegdec_recon_scaled(hipStream_t st, int n, const JdBuf
     if (z.grp440[0] > 0) hipLaunchKernelGGL(k_jd_scaled_h1v2<1>, dim3((unsigned)z.grp440[0]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
     if (z.grp440[1] > 0) hipLaunchKernelGGL(k_jd_scaled_h1v2<2>, dim3((unsigned)z.grp440[1]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
     if (z.grp440[2] > 0) hipLaunchKernelGGL(k_jd_scaled_h1v2<3>, dim3((unsigned)z.grp440[2]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
+    if (z.grpl[0] > 0) hipLaunchKernelGGL(k_jd_luma<0>, dim3((unsigned)z.grpl[0]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
+    if (z.grpl[1] > 0) hipLaunchKernelGGL(k_jd_luma<1>, dim3((unsigned)z.grpl[1]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
+    if (z.grpl[2] > 0) hipLaunchKernelGGL(k_jd_luma<2>, dim3((unsigned)z.grpl[2]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
+    if (z.grpl[3] > 0) hipLaunchKernelGGL(k_jd_luma<3>, dim3((unsigned)z.grpl[3]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
     return hipGetLastError();
 }
 
-// coefficients (natural order, MCU order) -> RGB, for n files: the full-size ones (z.px counts their pixels), then the scaled ones
+// coefficients (natural order, MCU order) -> RGB or luma, for n files: the full-size RGB ones (z.px counts their pixels), then the rest
 hipError_t launch_jpegdec_recon(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, unsigned char *out)
 {
     if (z.px > 0) {

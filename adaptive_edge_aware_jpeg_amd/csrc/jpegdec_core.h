@@ -12,6 +12,7 @@ namespace aej {
 
 constexpr int kJdChunk = 64;           // bytes per un-stuffing chunk
 constexpr int kJdSyncBatch = 4;        // sync rounds launched between two read-backs of the "changed" word
+constexpr int kJdLuma = 4;             // added to log2 of a file's scale: the luma plane alone, [oh][ow] (JdFile::shift)
 
 // per-file layout of one aej_jpegdec_batch (host-computed, uploaded with the descriptors)
 struct JdFile {
@@ -25,10 +26,12 @@ struct JdFile {
     int pw0, ph0, pw1, ph1;            // luma and chroma plane shapes (whole MCUs)
     long long px_base;                 // first output pixel of the call's pixel range (a scaled file has none: k_jd_rgb never meets it)
     long long out_off;                 // byte offset of the RGB output
-    int shift;                         // log2 of the decode scale: 0 full size (k_jd_idct, k_jd_rgb), 1..3 scale 2, 4, 8 (k_jd_scaled)
+    int shift;                         // log2 of the decode scale: 0 full size (k_jd_idct, k_jd_rgb), 1..3 scale 2, 4, 8 (k_jd_scaled);
+                                       // kJdLuma + 0..3: luma only at that scale (k_jd_luma; non-zero, so k_jd_idct leaves the file alone)
     int ow, oh;                        // output shape: ceil(width / scale), ceil(height / scale)
     long long grp_base[3];             // [shift - 1]: first workgroup of the file in k_jd_scaled<shift>'s grid (kJdRun MCUs of one MCU row each)
     long long grp440_base[3];          // the same in k_jd_scaled_h1v2<shift>'s grid, where the three-component 1 x 2 (4:4:0) files go
+    long long grpl_base[4];            // [log2 scale]: the same in k_jd_luma's grid, where the luma-only files of every layout go
 };
 
 // one restart segment: written by the un-stuffing scatter (start) and k_jd_segments (the rest)

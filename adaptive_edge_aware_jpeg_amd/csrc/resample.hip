@@ -1,9 +1,10 @@
 // resample.hip -- Pillow's 8-bit resampling on the device (aej_resample_*): Image.reduce's integer cell mean and Image.resize's two
-// fixed-point convolution passes (box, bilinear, hamming, bicubic, lanczos), bit for bit, over many packed [h][w][3] images of
-// different sizes in one call.  The filters are evaluated on the HOST only, in double (rs_taps below: the arithmetic of Pillow's
+// fixed-point convolution passes (box, bilinear, hamming, bicubic, lanczos), bit for bit, over many packed [h][w][3] (RGB) and [h][w]
+// (mode "L") images of different sizes in one call.  The filters are evaluated on the HOST only, in double (rs_taps below: the arithmetic of Pillow's
 // coefficient precompute, compiled without FP contraction); the device holds int32 taps and an int32 accumulator.
 //
-// One call is at most three launches, each one grid over every image that needs the stage (a per-image entry, a prefix sum of
+// One call is at most three launches per channel count present (the kernels are templated on it: a call of RGB images alone is three, a
+// mixed one six), each one grid over every image of that channel count that needs the stage (a per-image entry, a prefix sum of
 // workgroups, a binary search by blockIdx.x, as jpegdec.hip's k_jd_scaled): k_rs_reduce -> k_rs_horizontal -> k_rs_vertical.  The
 // last stage an image needs writes its destination, the ones before it write the workspace; an image that needs none is copied by
 // the vertical pass under identity taps.  The horizontal pass only covers the source rows the vertical taps touch.
@@ -129,6 +130,7 @@ __device__ __forceinline__ unsigned char rs_clip(int acc)
 
 // Image.reduce: thread = one output pixel, the mean of its fx x fy cell clipped at the box's right and bottom edges.
 // Bounds: x < out_w = ceil(bw / fx) and y < out_h = ceil(bh / fy), so the cell holds at least one pixel and stays inside the box.
+template <int kC>
 __global__ __launch_bounds__(kRsThreads) void k_rs_reduce(const RsReduce *__restrict__ entries, int n)
 {
     const RsReduce &e = rs_entry(entries, n);
@@ -136,21 +138,27 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_reduce(const RsReduce *__rest
     if (p >= (long long)e.out_w * e.out_h) return;
     const int y = (int)(p / e.out_w), x = (int)(p - (long long)y * e.out_w);
     const int x0 = x * e.fx, x1 = min(x0 + e.fx, e.bw), y0 = y * e.fy, y1 = min(y0 + e.fy, e.bh);
-    unsigned s0 = 0, s1 = 0, s2 = 0;
+    unsigned s0 = 0, s1 = 0, s2 = 0;                  // (kC == 1: s1 and s2 stay out of it)
     for (int r = y0; r < y1; r++) {
-        const unsigned char *s = e.in + ((long long)r * e.in_w + x0) * 3;
-        for (int c = x0; c < x1; c++, s += 3) { s0 += s[0]; s1 += s[1]; s2 += s[2]; }
+        const unsigned char *s = e.in + ((long long)r * e.in_w + x0) * kC;
+        for (int c = x0; c < x1; c++, s += kC) {
+            s0 += s[0];
+            if (kC == 3) { s1 += s[1]; s2 += s[2]; }
+        }
     }
     const unsigned cnt = (unsigned)(x1 - x0) * (unsigned)(y1 - y0), mul = (unsigned)((1ull << 32) / (256ull * cnt)), amend = cnt / 2;
-    unsigned char *o = e.out + p * 3;
+    unsigned char *o = e.out + p * kC;
     o[0] = (unsigned char)(((s0 + amend) * mul) >> 24);
-    o[1] = (unsigned char)(((s1 + amend) * mul) >> 24);
-    o[2] = (unsigned char)(((s2 + amend) * mul) >> 24);
+    if (kC == 3) {
+        o[1] = (unsigned char)(((s1 + amend) * mul) >> 24);
+        o[2] = (unsigned char)(((s2 + amend) * mul) >> 24);
+    }
 }
 
 // The horizontal pass: thread = one output pixel of a [out_h][out_w] image whose row y is input row y (e.in already points at the first
 // row the vertical taps touch).  taps are transposed, [ksize][out_w], so that a wave reads them as it reads its pixels: side by side.
 // Bounds: xmin >= 0 and xmin + cnt <= in_w by rs_taps.
+template <int kC>
 __global__ __launch_bounds__(kRsThreads) void k_rs_horizontal(const RsConv *__restrict__ entries, int n)
 {
     const RsConv &e = rs_entry(entries, n);
@@ -158,20 +166,23 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_horizontal(const RsConv *__re
     if (p >= (long long)e.out_w * e.out_h) return;
     const int y = (int)(p / e.out_w), xx = (int)(p - (long long)y * e.out_w);
     const int xmin = e.bounds[2 * xx], cnt = e.bounds[2 * xx + 1];
-    const unsigned char *s = e.in + ((long long)y * e.in_w + xmin) * 3;
+    const unsigned char *s = e.in + ((long long)y * e.in_w + xmin) * kC;
     const int *t = e.taps + xx;
     int a0 = 1 << (kRsBits - 1), a1 = a0, a2 = a0;
-    for (int k = 0; k < cnt; k++, s += 3, t += e.out_w) {
+    for (int k = 0; k < cnt; k++, s += kC, t += e.out_w) {
         const int w = *t;
-        a0 += s[0] * w; a1 += s[1] * w; a2 += s[2] * w;
+        a0 += s[0] * w;
+        if (kC == 3) { a1 += s[1] * w; a2 += s[2] * w; }
     }
-    unsigned char *o = e.out + p * 3;
-    o[0] = rs_clip(a0); o[1] = rs_clip(a1); o[2] = rs_clip(a2);
+    unsigned char *o = e.out + p * kC;
+    o[0] = rs_clip(a0);
+    if (kC == 3) { o[1] = rs_clip(a1); o[2] = rs_clip(a2); }
 }
 
 // The vertical pass: thread = one output pixel; the taps of its row, [out_h][ksize], are the same for a whole row of threads.
 // e.shift is the input's first row in the coordinates of the bounds (the horizontal pass left out the rows above it).
 // Bounds: shift <= ymin and ymin + cnt - shift <= the input's rows by rs_taps and the host's choice of shift.
+template <int kC>
 __global__ __launch_bounds__(kRsThreads) void k_rs_vertical(const RsConv *__restrict__ entries, int n)
 {
     const RsConv &e = rs_entry(entries, n);
@@ -179,16 +190,18 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_vertical(const RsConv *__rest
     if (p >= (long long)e.out_w * e.out_h) return;
     const int yy = (int)(p / e.out_w), x = (int)(p - (long long)yy * e.out_w);
     const int ymin = e.bounds[2 * yy] - e.shift, cnt = e.bounds[2 * yy + 1];
-    const long long pitch = (long long)e.in_w * 3;
-    const unsigned char *s = e.in + ymin * pitch + (long long)x * 3;
+    const long long pitch = (long long)e.in_w * kC;
+    const unsigned char *s = e.in + ymin * pitch + (long long)x * kC;
     const int *t = e.taps + (long long)yy * e.ksize;
     int a0 = 1 << (kRsBits - 1), a1 = a0, a2 = a0;
     for (int k = 0; k < cnt; k++, s += pitch) {
         const int w = t[k];
-        a0 += s[0] * w; a1 += s[1] * w; a2 += s[2] * w;
+        a0 += s[0] * w;
+        if (kC == 3) { a1 += s[1] * w; a2 += s[2] * w; }
     }
-    unsigned char *o = e.out + p * 3;
-    o[0] = rs_clip(a0); o[1] = rs_clip(a1); o[2] = rs_clip(a2);
+    unsigned char *o = e.out + p * kC;
+    o[0] = rs_clip(a0);
+    if (kC == 3) { o[1] = rs_clip(a1); o[2] = rs_clip(a2); }
 }
 
 // ---- host: the plan of a call ----------------------------------------------------------------------------------------------------------------
@@ -257,8 +270,9 @@ static long long rs_table(RsPlan &plan, std::vector<RsTableKey> &keys, std::vect
 }
 
 // fill = false: sizes only (aej_resample_workspace_bytes); the bounds of the vertical tables are needed either way (they size the
-// horizontal pass), so those are computed on the side.  -> -1, or the first descriptor refused (*why, *code)
-int resample_plan(const aej_resample_desc *descs, int n, bool fill, RsPlan &plan, const char **why, int *code)
+// horizontal pass), so those are computed on the side.  channels (may be NULL: every image 3): 3 or 1 per image, the bytes of a pixel;
+// the images of either count form launches of their own (RsPlan::count, ::tiles).  -> -1, or the first descriptor refused (*why, *code)
+int resample_plan(const aej_resample_desc *descs, int n, bool fill, RsPlan &plan, const char **why, int *code, const int *channels)
 {
     plan = RsPlan{};
     std::vector<RsTableKey> keys;
@@ -266,7 +280,11 @@ int resample_plan(const aej_resample_desc *descs, int n, bool fill, RsPlan &plan
     for (int i = 0; i < n; i++) {
         const aej_resample_desc &d = descs[i];
         if ((*why = rs_check(d, code)) != nullptr) return i;
+        const int ch = channels ? channels[i] : 3;
+        if (ch != 1 && ch != 3) { *why = "a channel count other than 1 or 3"; *code = AEJ_ERR_ARG; return i; }
         RsImage im{};
+        im.ch = ch;
+        long long *tiles = plan.tiles[ch == 1];
         int w = d.src_w, h = d.src_h;
         im.reduce = d.reduce_x > 1 || d.reduce_y > 1;
         if (im.reduce) {
@@ -275,11 +293,11 @@ int resample_plan(const aej_resample_desc *descs, int n, bool fill, RsPlan &plan
             e.bw = r[2] - r[0]; e.bh = r[3] - r[1]; e.fx = d.reduce_x; e.fy = d.reduce_y; e.in_w = d.src_w;
             e.out_w = w = (e.bw + e.fx - 1) / e.fx;
             e.out_h = h = (e.bh + e.fy - 1) / e.fy;
-            im.r_src = d.src_offset + ((long long)r[1] * d.src_w + r[0]) * 3;
-            e.tile_base = plan.tiles[0];
-            plan.tiles[0] += rs_tiles((long long)w * h);
+            im.r_src = d.src_offset + ((long long)r[1] * d.src_w + r[0]) * ch;
+            e.tile_base = tiles[0];
+            tiles[0] += rs_tiles((long long)w * h);
             im.tmp_a = plan.tmp_bytes;
-            plan.tmp_bytes += align_up((long long)w * h * 3, 256);
+            plan.tmp_bytes += align_up((long long)w * h * ch, 256);
         }
         const float *b = d.box;
         im.horizontal = d.dst_w != w || b[0] != 0 || b[2] != (float)d.dst_w;
@@ -300,8 +318,8 @@ int resample_plan(const aej_resample_desc *descs, int n, bool fill, RsPlan &plan
             }
             e.shift = first;
             e.in_w = e.out_w = d.dst_w; e.out_h = d.dst_h;
-            e.tile_base = plan.tiles[2];
-            plan.tiles[2] += rs_tiles((long long)e.out_w * e.out_h);
+            e.tile_base = tiles[2];
+            tiles[2] += rs_tiles((long long)e.out_w * e.out_h);
         }
         if (im.horizontal) {
             RsConv &e = im.h;
@@ -309,25 +327,30 @@ int resample_plan(const aej_resample_desc *descs, int n, bool fill, RsPlan &plan
             const RsTableKey key{1, w, d.dst_w, d.filter, b[0], b[2]};
             im.h_table = rs_table(plan, keys, where, key, e.ksize, false, fill);
             e.in_w = w; e.out_w = d.dst_w; e.out_h = last - first; e.shift = first;
-            e.tile_base = plan.tiles[1];
-            plan.tiles[1] += rs_tiles((long long)e.out_w * e.out_h);
+            e.tile_base = tiles[1];
+            tiles[1] += rs_tiles((long long)e.out_w * e.out_h);
             if (im.vertical) {
                 im.tmp_b = plan.tmp_bytes;
-                plan.tmp_bytes += align_up((long long)e.out_w * e.out_h * 3, 256);
+                plan.tmp_bytes += align_up((long long)e.out_w * e.out_h * ch, 256);
             }
         }
         im.src_offset = d.src_offset; im.dst_offset = d.dst_offset;
-        im.src_bytes = (long long)d.src_w * d.src_h * 3; im.dst_bytes = (long long)d.dst_w * d.dst_h * 3;
-        plan.count[0] += im.reduce; plan.count[1] += im.horizontal; plan.count[2] += im.vertical || copy;
+        im.src_bytes = (long long)d.src_w * d.src_h * ch; im.dst_bytes = (long long)d.dst_w * d.dst_h * ch;
+        int *count = plan.count[ch == 1];
+        count[0] += im.reduce; count[1] += im.horizontal; count[2] += im.vertical || copy;
         plan.images.push_back(im);
     }
     return -1;
 }
 
-static long long rs_blob_bytes(const RsPlan &p)
+// the entries of a call: reduce (RGB images, then one-channel ones), horizontal (likewise), vertical (likewise)
+static long long rs_entry_bytes(const RsPlan &p)
 {
-    return align_up(sizeof(RsReduce) * p.count[0] + sizeof(RsConv) * (p.count[1] + p.count[2]), 16) + 4 * p.n_ints;
+    return align_up(sizeof(RsReduce) * (p.count[0][0] + p.count[1][0]) +
+                    sizeof(RsConv) * (p.count[0][1] + p.count[1][1] + p.count[0][2] + p.count[1][2]), 16);
 }
+
+static long long rs_blob_bytes(const RsPlan &p) { return rs_entry_bytes(p) + 4 * p.n_ints; }
 
 unsigned long long resample_carve(void *base, const RsPlan &plan, RsBufs &w)
 {
@@ -341,15 +364,20 @@ unsigned long long resample_carve(void *base, const RsPlan &plan, RsBufs &w)
 void resample_blob(const RsPlan &plan, const RsBufs &w, const unsigned char *src, unsigned char *dst, std::vector<unsigned char> &blob)
 {
     blob.assign(rs_blob_bytes(plan), 0);
-    const long long entries = align_up(sizeof(RsReduce) * plan.count[0] + sizeof(RsConv) * (plan.count[1] + plan.count[2]), 16);
-    RsReduce *r = (RsReduce *)blob.data();
-    RsConv *h = (RsConv *)(r + plan.count[0]), *v = h + plan.count[1];
+    const long long entries = rs_entry_bytes(plan);
+    RsReduce *rr[2];
+    RsConv *hh[2], *vv[2];
+    rr[0] = (RsReduce *)blob.data(); rr[1] = rr[0] + plan.count[0][0];
+    hh[0] = (RsConv *)(rr[1] + plan.count[1][0]); hh[1] = hh[0] + plan.count[0][1];
+    vv[0] = hh[1] + plan.count[1][1]; vv[1] = vv[0] + plan.count[0][2];
     const int *ints = (const int *)(w.blob + entries);
     if (plan.n_ints) memcpy(blob.data() + entries, plan.ints.data(), 4 * plan.n_ints);
     for (const RsImage &im : plan.images) {
         const unsigned char *in = src + im.src_offset;
         unsigned char *out = dst + im.dst_offset;
         const bool copy = !im.reduce && !im.horizontal && !im.vertical;
+        RsReduce *&r = rr[im.ch == 1];
+        RsConv *&h = hh[im.ch == 1], *&v = vv[im.ch == 1];
         if (im.reduce) {
             *r = im.r;
             r->in = src + im.r_src;
@@ -359,7 +387,7 @@ void resample_blob(const RsPlan &plan, const RsBufs &w, const unsigned char *src
         }
         if (im.horizontal) {
             *h = im.h;
-            h->in = in + (long long)im.h.shift * im.h.in_w * 3;
+            h->in = in + (long long)im.h.shift * im.h.in_w * im.ch;
             h->out = im.vertical ? w.tmp + im.tmp_b : out;
             h->bounds = ints + im.h_table;
             h->taps = h->bounds + 2LL * im.h.out_w;
@@ -381,11 +409,17 @@ hipError_t launch_resample(hipStream_t st, const RsPlan &plan, const RsBufs &w, 
 {
     hipError_t e = hipMemcpyAsync(w.blob, blob_host, blob_bytes, hipMemcpyHostToDevice, st);
     if (e != hipSuccess) return e;
-    const RsReduce *r = (const RsReduce *)w.blob;
-    const RsConv *h = (const RsConv *)(r + plan.count[0]), *v = h + plan.count[1];
-    if (plan.count[0]) hipLaunchKernelGGL(k_rs_reduce, dim3((unsigned)plan.tiles[0]), dim3(kRsThreads), 0, st, r, plan.count[0]);
-    if (plan.count[1]) hipLaunchKernelGGL(k_rs_horizontal, dim3((unsigned)plan.tiles[1]), dim3(kRsThreads), 0, st, h, plan.count[1]);
-    if (plan.count[2]) hipLaunchKernelGGL(k_rs_vertical, dim3((unsigned)plan.tiles[2]), dim3(kRsThreads), 0, st, v, plan.count[2]);
+    const int (&c)[2][3] = plan.count;
+    const long long (&tl)[2][3] = plan.tiles;
+    const RsReduce *r3 = (const RsReduce *)w.blob, *r1 = r3 + c[0][0];
+    const RsConv *h3 = (const RsConv *)(r1 + c[1][0]), *h1 = h3 + c[0][1], *v3 = h1 + c[1][1], *v1 = v3 + c[0][2];
+    // stage by stage: an image's stages follow each other on the stream, and images of different channel counts share nothing
+    if (c[0][0]) hipLaunchKernelGGL(k_rs_reduce<3>, dim3((unsigned)tl[0][0]), dim3(kRsThreads), 0, st, r3, c[0][0]);
+    if (c[1][0]) hipLaunchKernelGGL(k_rs_reduce<1>, dim3((unsigned)tl[1][0]), dim3(kRsThreads), 0, st, r1, c[1][0]);
+    if (c[0][1]) hipLaunchKernelGGL(k_rs_horizontal<3>, dim3((unsigned)tl[0][1]), dim3(kRsThreads), 0, st, h3, c[0][1]);
+    if (c[1][1]) hipLaunchKernelGGL(k_rs_horizontal<1>, dim3((unsigned)tl[1][1]), dim3(kRsThreads), 0, st, h1, c[1][1]);
+    if (c[0][2]) hipLaunchKernelGGL(k_rs_vertical<3>, dim3((unsigned)tl[0][2]), dim3(kRsThreads), 0, st, v3, c[0][2]);
+    if (c[1][2]) hipLaunchKernelGGL(k_rs_vertical<1>, dim3((unsigned)tl[1][2]), dim3(kRsThreads), 0, st, v1, c[1][2]);
     return hipGetLastError();
 }
 

@@ -1,4 +1,5 @@
-"""Pillow's ``Image.resize`` for 8-bit RGB images on the GPU, pixel for pixel: ``resize_many`` takes images of mixed sizes and returns
+"""Pillow's ``Image.resize`` for 8-bit RGB and mode-"L" images on the GPU, pixel for pixel: ``resize_many`` takes [H, W, 3] and (with
+``mode="L"`` / ``"auto"``) [H, W] images of mixed sizes, in one call, and returns
 what ``Image.fromarray(a).resize(size, filter, box=box, reducing_gap=g)`` returns for each, for the five convolution filters
 ("box", "bilinear", "hamming", "bicubic", "lanczos", or Pillow's integers 4, 2, 5, 3, 1), down- and up-scaling alike, with Pillow's
 fractional ``box`` and its ``reducing_gap`` step (``Image.reduce`` over ``Image._get_safe_box`` first).  ``standard_jpeg_thumbnail_many``
@@ -7,12 +8,14 @@ fractional ``box`` and its ``reducing_gap`` step (``Image.reduce`` over ``Image.
 The arithmetic is Pillow's (csrc/resample.hip, ``aej_resample_*`` in include/aej.h): per axis a table of int32 taps -- the filter
 evaluated on the host, in double, normalised and rounded to 22 fractional bits -- and on the device one horizontal and one vertical
 pass, each ``clip((2^21 + sum(pixel * tap)) >> 22, 0, 255)`` with the horizontal result rounded to uint8 in between; ``reduce`` is the
-integer cell mean ``((sum + n // 2) * (2^32 // (256 n))) >> 24``.  One call is at most three kernel launches and one upload however
-many images it has, and nothing is read back.
+integer cell mean ``((sum + n // 2) * (2^32 // (256 n))) >> 24``.  A one-channel image runs the same plan, tables and arithmetic on its
+one channel (Pillow's mode-"L" resize equals one channel of its RGB resize of three copies), through one-channel instantiations of
+the three kernels.  One call is at most three kernel launches per channel count present (three for RGB images alone, six for a mix)
+and one upload however many images it has, and nothing is read back.
 
 Not built (NotImplementedError): ``nearest`` (Pillow takes another path for it), an image more than 100 times as tall as wide that
-is made shorter (Pillow resizes that one vertically first), and modes other than 8-bit RGB (grey JPEG files decode to three equal
-channels).  There is no CPU fallback.
+is made shorter (Pillow resizes that one vertically first), and modes other than 8-bit RGB and 8-bit L (no RGBA, LA, 16-bit or
+float images).  There is no CPU fallback.
 """
 import ctypes
 import math
@@ -136,12 +139,14 @@ def _steps(what, W, H, size, box, f, gap):
     return step
 
 
-def _run(ctx, src, src_bytes, src_off, steps, f):
+def _run(ctx, src, src_bytes, src_off, steps, f, channels=None):
     """aej_resample_batch over the images at src + src_off[i] -> list of uint8 [h, w, 3] views into one packed allocation.
-    f: one filter per image."""
+    f: one filter per image.  channels (None: every image 3): 3 or 1 per image; with a 1 among them the call is aej_resample_batch_ch
+    and that image's view is [h, w]."""
     from ._lib import ResampleDesc
     t, lib, n = ctx.torch, ctx.lib, len(steps)
     descs = (ResampleDesc * n)()
+    ch = [3] * n if channels is None else [int(c) for c in channels]
     pos = 0
     dst_off = []
     for i, s in enumerate(steps):
@@ -153,13 +158,18 @@ def _run(ctx, src, src_bytes, src_off, steps, f):
         d.reduce_x, d.reduce_y = s["factors"]
         d.reduce_box = (ctypes.c_int32 * 4)(*s["reduce_box"])
         dst_off.append(pos)
-        pos += d.dst_w * d.dst_h * 3
+        pos += d.dst_w * d.dst_h * ch[i]
     out = ctx.empty((pos,), t.uint8)
-    nws = int(lib.aej_resample_workspace_bytes(ctx.handle, ctypes.addressof(descs), n))
+    how, sfx = (), ""
+    if any(c != 3 for c in ch):                      # every image RGB: the entries without channels, as before
+        cc = np.array(ch, np.int32)
+        how, sfx = (cc.ctypes.data,), "_ch"
+    nws = int(getattr(lib, "aej_resample_workspace_bytes" + sfx)(ctx.handle, ctypes.addressof(descs), n, *how))
     ws = ctx.workspace(max(nws, 256))
-    ctx.check(lib.aej_resample_batch(ctx.handle, ctypes.addressof(descs), n, ctypes.c_void_p(src), ctypes.c_uint64(src_bytes), out.data_ptr(),
-                                     ctypes.c_uint64(pos), ws.data_ptr(), ctypes.c_uint64(ws.numel())))
-    return [out[o:o + s["dst"][0] * s["dst"][1] * 3].view(s["dst"][1], s["dst"][0], 3) for o, s in zip(dst_off, steps)]
+    ctx.check(getattr(lib, "aej_resample_batch" + sfx)(ctx.handle, ctypes.addressof(descs), n, *how, ctypes.c_void_p(src), ctypes.c_uint64(src_bytes),
+                                                       out.data_ptr(), ctypes.c_uint64(pos), ws.data_ptr(), ctypes.c_uint64(ws.numel())))
+    return [out[o:o + s["dst"][0] * s["dst"][1] * c].view(*((s["dst"][1], s["dst"][0]) + ((3,) if c == 3 else ())))
+            for o, s, c in zip(dst_off, steps, ch)]
 
 
 def resample_taps(in_size: int, in0: float, in1: float, out_size: int, resample="bicubic"):
@@ -176,10 +186,13 @@ def resample_taps(in_size: int, in0: float, in1: float, out_size: int, resample=
     return bounds[:, 0].copy(), bounds[:, 1].copy(), taps
 
 
-def resize_many(images, size, resample="bicubic", box=None, reducing_gap=None, device: int = 0) -> list:
-    """Resize uint8 [H_i, W_i, 3] images (device tensors or NumPy arrays, of mixed sizes) on the device: -> list of uint8
-    [h_i, w_i, 3] tensors, views into one packed allocation; element i equals
-    ``np.asarray(Image.fromarray(a_i).resize(size_i, F, box=box_i, reducing_gap=reducing_gap))``.
+def resize_many(images, size, resample="bicubic", box=None, reducing_gap=None, device: int = 0, mode: str = "RGB") -> list:
+    """Resize uint8 [H_i, W_i, 3] (RGB) and, with mode=, [H_i, W_i] (mode "L") images (device tensors or NumPy arrays, of mixed sizes) on
+    the device: -> list of uint8 [h_i, w_i, 3] / [h_i, w_i] tensors -- output i has the rank of input i --, views into one packed
+    allocation; element i equals ``np.asarray(Image.fromarray(a_i).resize(size_i, F, box=box_i, reducing_gap=reducing_gap))``.
+    mode, as standard_jpeg_encode_many's: "RGB" (the default: the call as it always was, every image [H, W, 3], an [H, W] image refused
+    as before); "L": every image [H, W]; "auto": [H, W] and [H, W, 3] images mixed freely in one call.  Other ranks, and a last axis
+    other than 3, are refused under every mode; a mode other than the three raises ValueError.
     size: one (w, h), or one per image.  box: None (the whole image), one (x0, y0, x1, y1) -- fractions allowed, as in Pillow -- or
     one (or None) per image.  resample (one, or a list of one per image): "box", "bilinear", "hamming", "bicubic", "lanczos" or Pillow's 4, 2, 5, 3, 1; "nearest" / 0
     raises NotImplementedError.  reducing_gap: None, or a number >= 1.0 (ValueError otherwise): images whose box is more than that
@@ -191,6 +204,8 @@ def resize_many(images, size, resample="bicubic", box=None, reducing_gap=None, d
     if n < 1:
         raise ValueError("resize_many needs at least one image")
     f, gap = _check_filters(resample, n, "image"), _check_gap(reducing_gap, "every image")
+    if not isinstance(mode, str) or mode not in ("RGB", "L", "auto"):
+        raise ValueError(f"mode {mode!r}: 'RGB', 'L' or 'auto' required")
     if not isinstance(size, (str, bytes)) and hasattr(size, "__len__") and len(size) == 2 and all(_is_number(v) or isinstance(v, (bool, np.bool_)) for v in size):
         sizes = [_check_size(size, "resize_many")] * n
     else:
@@ -201,14 +216,17 @@ def resize_many(images, size, resample="bicubic", box=None, reducing_gap=None, d
     steps, shapes = [], []
     for i, a in enumerate(images):
         shape, dt = tuple(a.shape), str(a.dtype)
-        if len(shape) != 3 or shape[2] != 3 or shape[0] < 1 or shape[1] < 1:
-            raise ValueError(f"image {i}: uint8 [H, W, 3] required, got shape {shape}")
+        colour, grey = len(shape) == 3 and shape[2] == 3, len(shape) == 2
+        if not ((colour and mode != "L") or (grey and mode != "RGB")) or shape[0] < 1 or shape[1] < 1:
+            want = {"RGB": "[H, W, 3]", "L": "[H, W] (mode 'L')", "auto": "[H, W] or [H, W, 3] (mode 'auto')"}[mode]
+            raise ValueError(f"image {i}: uint8 {want} required, got shape {shape}")
         if dt not in ("uint8", "torch.uint8"):
             raise TypeError(f"image {i}: uint8 required, got {dt}")
         if max(shape[:2]) > 65535 or max(sizes[i]) > 65535:
             raise ValueError(f"image {i}: sizes up to 65535 a side")
         steps.append(_steps(f"image {i}", shape[1], shape[0], sizes[i], boxes[i], f[i], gap))
         shapes.append(shape)
+    nbytes = [int(np.prod(s)) for s in shapes]
     ctx = get_context(device)
     t = ctx.torch
     # the sources: device tensors are read where they are; NumPy arrays cross in one pinned copy
@@ -218,19 +236,19 @@ def resize_many(images, size, resample="bicubic", box=None, reducing_gap=None, d
         off, pos = {}, 0
         for i in host:
             off[i] = pos
-            pos += shapes[i][0] * shapes[i][1] * 3
+            pos += nbytes[i]
         stage = ctx.pinned(pos)
         for i in host:
-            nb = shapes[i][0] * shapes[i][1] * 3
+            nb = nbytes[i]
             stage.numpy()[off[i]:off[i] + nb] = np.ascontiguousarray(images[i]).reshape(-1)
         up = ctx.empty((pos,), t.uint8)
         up.copy_(stage[:pos], non_blocking=True)
         for i in host:
-            keep[i] = up[off[i]:off[i] + shapes[i][0] * shapes[i][1] * 3]
+            keep[i] = up[off[i]:off[i] + nbytes[i]]
     for i, a in enumerate(images):
         if i not in keep:
             keep[i] = a.to(device=ctx.device).contiguous()
     ptrs = [keep[i].data_ptr() for i in range(n)]
     base = min(ptrs)
-    end = max(p + s[0] * s[1] * 3 for p, s in zip(ptrs, shapes))
-    return _run(ctx, base, end - base, [p - base for p in ptrs], steps, f)
+    end = max(p + nb for p, nb in zip(ptrs, nbytes))
+    return _run(ctx, base, end - base, [p - base for p in ptrs], steps, f, [3 if len(s) == 3 else 1 for s in shapes])

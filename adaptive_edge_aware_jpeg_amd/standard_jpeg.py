@@ -20,6 +20,14 @@ decoded image over the fractional box ``draft()`` returns: its integer box reduc
 csrc/resample.hip, ``aej_resample_*``), with nothing read back but the decoder's status words.  ``thumbnail_plan`` is that choice for one
 file size, on the host.  ``resize_many`` (resample.py) is ``Image.resize`` itself for device images.
 
+``mode="L"`` / ``"auto"`` (one value, or one per file) on the decode and on both thumbnail calls is Pillow's mode "L" on the pixel side:
+a one-component file comes back as ``[h, w]``, and under ``"L"`` so does a colour file, as its luma plane alone -- what Pillow gives after
+``im.draft("L", size)`` makes libjpeg set ``out_color_space = JCS_GRAYSCALE``: no chroma IDCT, no up-sampling, no colour conversion, and
+not ``convert("L")``, from which it differs by several levels (``aej_jpegdec_batch_mode``, ``aej_jpegprog_batch_mode``; one kernel at
+every scale, csrc/jpegdec.hip ``k_jd_luma``).  ``resize_many(mode="L" / "auto")`` takes ``[H, W]`` images, alone or beside ``[H, W, 3]`` ones
+(``aej_resample_batch_ch``), and ``standard_jpeg_thumbnail_jpeg_many(mode="auto")`` writes a grey source's thumbnail as the
+one-component file Pillow saves.  ``"RGB"``, the default, is every call as it always was.
+
 ``standard_jpeg_transcode_many`` joins the two without touching a pixel: it Huffman-decodes existing files to their quantised
 coefficients on the device and entropy-codes the same coefficients again, as a baseline file under the file's own optimal Huffman
 tables or as the ten-scan progressive file (csrc/jfiftrans.hip, ``aej_jfif_transcode_*``) -- what ``jpegtran -optimize`` and
@@ -350,8 +358,9 @@ def _stage(ctx, views, pieces):
     return dev, off
 
 
-def _decode_baseline(ctx, idx, parsed, views, out, out_off, scales=None):
-    """aej_jpegdec_batch (scales None) or aej_jpegdec_batch_scaled over the files idx -> their status words (device int32)"""
+def _decode_baseline(ctx, idx, parsed, views, out, out_off, scales=None, comps=None):
+    """aej_jpegdec_batch (scales None), aej_jpegdec_batch_scaled or (comps: 3 or 1 per file) aej_jpegdec_batch_mode over the files idx
+    -> their status words (device int32)"""
     from ._lib import JpegDecDesc
     t, lib, n = ctx.torch, ctx.lib, len(idx)
     descs = (JpegDecDesc * n)(*[parsed[i] for i in idx])
@@ -362,6 +371,10 @@ def _decode_baseline(ctx, idx, parsed, views, out, out_off, scales=None):
     how = () if scales is None else (sc[0].ctypes.data,)
     nbytes, batch = ((lib.aej_jpegdec_workspace_bytes, lib.aej_jpegdec_batch) if scales is None else
                      (lib.aej_jpegdec_workspace_bytes_scaled, lib.aej_jpegdec_batch_scaled))
+    if comps is not None:
+        cc = np.ascontiguousarray(comps[idx], np.int32)
+        how = (sc[0].ctypes.data if sc else None, cc.ctypes.data)
+        nbytes, batch = lib.aej_jpegdec_workspace_bytes_mode, lib.aej_jpegdec_batch_mode
     nws = int(nbytes(ctx.handle, ctypes.addressof(descs), n, *how))
     if nws == 0:
         raise ValueError("descriptors the library refuses")
@@ -372,8 +385,9 @@ def _decode_baseline(ctx, idx, parsed, views, out, out_off, scales=None):
     return status
 
 
-def _decode_progressive(ctx, idx, parsed, views, out, out_off, scales=None):
-    """aej_jpegprog_batch (scales None) or aej_jpegprog_batch_scaled over the files idx -> their status words (device int32)"""
+def _decode_progressive(ctx, idx, parsed, views, out, out_off, scales=None, comps=None):
+    """aej_jpegprog_batch (scales None), aej_jpegprog_batch_scaled or (comps) aej_jpegprog_batch_mode over the files idx -> their status
+    words (device int32)"""
     from ._lib import JpegProgFrame, JpegProgScan
     t, lib, n = ctx.torch, ctx.lib, len(idx)
     frames = (JpegProgFrame * n)(*[parsed[i][0] for i in idx])
@@ -386,6 +400,10 @@ def _decode_progressive(ctx, idx, parsed, views, out, out_off, scales=None):
     how = () if scales is None else (sc[0].ctypes.data,)
     nbytes, batch = ((lib.aej_jpegprog_workspace_bytes, lib.aej_jpegprog_batch) if scales is None else
                      (lib.aej_jpegprog_workspace_bytes_scaled, lib.aej_jpegprog_batch_scaled))
+    if comps is not None:
+        cc = np.ascontiguousarray(comps[idx], np.int32)
+        how = (sc[0].ctypes.data if sc else None, cc.ctypes.data)
+        nbytes, batch = lib.aej_jpegprog_workspace_bytes_mode, lib.aej_jpegprog_batch_mode
     nws = int(nbytes(ctx.handle, ctypes.addressof(frames), ctypes.addressof(scans), n, *how))
     if nws == 0:
         raise ValueError("descriptors the library refuses")
@@ -414,6 +432,30 @@ def _check_scales(scale, n):
     return np.array([_check_scale(s) for s in scale], np.int32).reshape(n)
 
 
+def _check_modes(mode, n, what="file"):
+    """mode= of the decoders and thumbnail calls -> list of n of "RGB", "L", "auto": one string for every file, or a list / tuple of
+    one per file.  ValueError for another string (in a sequence naming the file) or a sequence of another length; TypeError for
+    anything that is neither a string nor a list / tuple (in a sequence naming the file)."""
+    def one(m, who):
+        if not isinstance(m, str):
+            raise TypeError(f"{who}: mode {m!r}: a string ('RGB', 'L' or 'auto') required")
+        if m not in ("RGB", "L", "auto"):
+            raise ValueError(f"{who}: mode {m!r}: 'RGB', 'L' or 'auto' required")
+        return m
+    if isinstance(mode, str):
+        return [one(mode, f"every {what}")] * n
+    if not isinstance(mode, (list, tuple)):
+        raise TypeError(f"mode {mode!r}: 'RGB', 'L' or 'auto', or a list of one per {what}, required")
+    if len(mode) != n:
+        raise ValueError(f"mode: {len(mode)} values for {n} {what}s")
+    return [one(m, f"{what} {i}") for i, m in enumerate(mode)]
+
+
+def _views(out, out_off, shapes, comps):
+    """the images of a packed decode: [h, w, 3], or [h, w] where comps says 1"""
+    return [out[int(o):int(o) + h * w * c].view(*((h, w, 3) if c == 3 else (h, w))) for o, (h, w), c in zip(out_off, shapes, comps)]
+
+
 def draft_scale(width: int, height: int, size) -> int:
     """The scale ``Image.draft(None, size)`` picks for a width x height JPEG file (host only): the largest of 8, 4, 2, 1 that is not above
     ``min(width // size[0], height // size[1])`` -- the smallest decode that is still at least ``size`` (width, height) large, which is
@@ -425,7 +467,7 @@ def draft_scale(width: int, height: int, size) -> int:
     return next((s for s in (8, 4, 2) if s <= ratio), 1)
 
 
-def standard_jpeg_decode_many(files, device: int = 0, progressive: bool = False, scale=1, layout_440: bool = False) -> list:
+def standard_jpeg_decode_many(files, device: int = 0, progressive: bool = False, scale=1, layout_440: bool = False, mode="RGB") -> list:
     """Decode JPEG files on the device: -> list of uint8 [H_i, W_i, 3] tensors (views into one packed allocation), in input
     order, on the context of the current stream; element i equals ``np.asarray(Image.open(io.BytesIO(files[i])).convert("RGB"))``.
     scale: 1, 2, 4 or 8, or a sequence of one such value per file (ValueError naming the value otherwise; a bool is refused): file i
@@ -441,44 +483,60 @@ def standard_jpeg_decode_many(files, device: int = 0, progressive: bool = False,
     once per kind).  There is no CPU fallback.
     layout_440=True (TypeError for a value that is not a bool) also takes 4:4:0 files -- three components, luma sampled 1 x 2 over 1 x 1
     chroma, what ``jpegtran -rotate 90`` makes of a 4:2:2 photo -- baseline or progressive, at every scale, mixed freely with the other
-    layouts; without it such a file is refused as before (NotImplementedError, "sampling factors 1x2,...")."""
+    layouts; without it such a file is refused as before (NotImplementedError, "sampling factors 1x2,...").
+    mode: "RGB" (the default: the call as it always was), "L", "auto", or a list / tuple of one of them per file.  "L": element i is
+    uint8 [h, w] -- a one-component file's samples, a colour file's LUMA PLANE: what Pillow gives after ``im.draft("L", (W_i // s,
+    H_i // s))`` (libjpeg's out_color_space = JCS_GRAYSCALE), at every scale, for every layout, baseline and progressive.  This is NOT
+    ``im.convert("L")``: no ITU-R 601 weighting of the clamped R, G, B -- the two differ by several levels where the chroma is strong.
+    The chroma blocks of such a file are entropy-decoded (the scan interleaves them) and then never touched: no chroma IDCT, no
+    up-sampling, no colour conversion, a third of the output bytes.  "auto": each file in Pillow's own mode, ``np.asarray(Image.open(f))``
+    -- [h, w] for a one-component file, [h, w, 3] for a colour one.  The images stay views into one packed allocation (h * w bytes of an
+    L image, h * w * 3 of an RGB one).  A string that is not one of the three, or a sequence of another length than files, raises
+    ValueError (naming the file of a bad entry); a value that is neither a string nor a list / tuple TypeError -- before any device
+    work, like every keyword here."""
     files = list(files)
     if not files:
         raise ValueError("standard_jpeg_decode_many needs at least one file")
-    _, out, out_off, shapes = _decode_files(files, device, progressive, _check_scales(scale, len(files)), layout_440=_check_bool("layout_440", layout_440))
-    return [out[int(o):int(o) + h * w * 3].view(h, w, 3) for o, (h, w) in zip(out_off, shapes)]
+    modes = _check_modes(mode, len(files))
+    _, out, out_off, shapes, comps = _decode_files(files, device, progressive, _check_scales(scale, len(files)),
+                                                   layout_440=_check_bool("layout_440", layout_440), modes=modes)
+    return _views(out, out_off, shapes, comps)
 
 
-def _decode_files(files, device, progressive, scales, choose=None, layout_440=False):
-    """The decode of standard_jpeg_decode_many -> (context, the packed uint8 output, int64 offsets, [(h, w)]).  scales: int32 [n]; with
-    `choose`, file i's scale is choose(i, width, height) instead, asked once its header is parsed and before any device work."""
+def _decode_files(files, device, progressive, scales, choose=None, layout_440=False, modes=None):
+    """The decode of standard_jpeg_decode_many -> (context, the packed uint8 output, int64 offsets, [(h, w)], [3 or 1: the channels of
+    each image]).  scales: int32 [n]; with `choose`, file i's scale is choose(i, width, height) instead, asked once its header
+    is parsed and before any device work.  modes: _check_modes' list (None: every file "RGB")."""
     n = len(files)
-    parsed, views, base_idx, prog_idx, shapes = [], [], [], [], []
+    parsed, views, base_idx, prog_idx, shapes, comps = [], [], [], [], [], []
     for i, is_prog, d, mv in _parse_sources(files, progressive, layout_440=layout_440):
         parsed.append(d)
         views.append(mv)
         (prog_idx if is_prog else base_idx).append(i)
         frame = d[0] if is_prog else d
+        m = "RGB" if modes is None else modes[i]
+        comps.append(1 if m == "L" or (m == "auto" and frame.ncomp == 1) else 3)
         if choose is not None:
             scales[i] = choose(i, frame.width, frame.height)
         s = int(scales[i])
         shapes.append((-(-frame.height // s), -(-frame.width // s)))
     if (scales == 1).all():
         scales = None                                # the unscaled entries, as before
+    comps_arr = None if all(c == 3 for c in comps) else np.array(comps, np.int32)      # every image RGB: the entries without components, as before
     ctx = get_context(device)
     t = ctx.torch
     out_off = np.zeros(n, np.int64)
     opos = 0
     for i, (h, w) in enumerate(shapes):
         out_off[i] = opos
-        opos += h * w * 3
+        opos += h * w * comps[i]
     out = ctx.empty((max(opos, 1),), t.uint8)
     st = np.zeros(n, np.int64)
     for idx, run in ((base_idx, _decode_baseline), (prog_idx, _decode_progressive)):
         if idx:
-            st[idx] = run(ctx, idx, parsed, views, out, out_off, scales).cpu().numpy()      # the one read-back of the per-file status words
+            st[idx] = run(ctx, idx, parsed, views, out, out_off, scales, comps_arr).cpu().numpy()      # the one read-back of the per-file status words
     _raise_status((int(i), int(st[i])) for i in np.flatnonzero(st))
-    return ctx, out, out_off, shapes
+    return ctx, out, out_off, shapes, comps
 
 
 def _thumbnail_size(width, height, size):
@@ -525,7 +583,7 @@ def thumbnail_plan(width: int, height: int, size, reducing_gap=2.0):
 
 
 def standard_jpeg_thumbnail_many(files, size, resample="bicubic", reducing_gap=2.0, progressive: bool = False, device: int = 0,
-                                 layout_440: bool = False) -> list:
+                                 layout_440: bool = False, mode="RGB") -> list:
     """``Image.thumbnail`` on JPEG files, on the device: -> list of uint8 [h_i, w_i, 3] tensors, views into one packed allocation;
     element i equals ``im = Image.open(io.BytesIO(files[i])); im.thumbnail(size_i, F, reducing_gap=reducing_gap);
     np.asarray(im.convert("RGB"))``.  Per file (thumbnail_plan): the aspect-preserving final size; the decode at the scale ``draft()``
@@ -534,13 +592,21 @@ def standard_jpeg_thumbnail_many(files, size, resample="bicubic", reducing_gap=2
     full size.  Nothing but the decoder's status words is read back.  A tensor whose file has a COM segment carries its text as the
     attribute ``jpeg_comment`` (bytes), as Pillow keeps ``im.info["comment"]``; standard_jpeg_encode_many writes it again, as Pillow's save does.
     size: one (w, h), or one per file.  resample (one, or a list of one per file) / reducing_gap: as resize_many (reducing_gap=None: full-size decode, one resize).
-    files / progressive / layout_440: as standard_jpeg_decode_many, which refuses what this refuses, with the same words."""
+    files / progressive / layout_440: as standard_jpeg_decode_many, which refuses what this refuses, with the same words.
+    mode: standard_jpeg_decode_many's ("RGB", the default: the call as it always was).  An image that "L" or "auto" makes one-channel
+    is uint8 [h_i, w_i]: the same plan -- scale, factors, box, final size -- run on the one-channel decode and the one-channel resize.
+    For a one-component file that is ``im.thumbnail(size_i, F, reducing_gap=reducing_gap); np.asarray(im)``, a mode-"L" image.  For a
+    colour file under "L" it is the thumbnail Pillow makes when the file's ONE draft() call asks for mode "L" (thumbnail()'s own draft
+    does nothing after a first one): with ``plan = thumbnail_plan(W, H, size, g)``, the full-size ``im.draft("L", None)`` image when
+    plan is None, otherwise ``res = im.draft("L", (int(size[0] * g), int(size[1] * g)))`` (``im.draft("L", None)`` when g is None) and
+    then, if ``im.size != plan[2]``, ``im.resize(plan[2], F, box=res[1], reducing_gap=g)``.  Luma, not ``convert("L")``."""
     from . import resample as RS
     layout_440 = _check_bool("layout_440", layout_440)
     files = list(files)
     n = len(files)
     if n < 1:
         raise ValueError("standard_jpeg_thumbnail_many needs at least one file")
+    modes = _check_modes(mode, n)
     f, gap = RS._check_filters(resample, n, "file"), RS._check_gap(reducing_gap, "every file")
     if not isinstance(size, (str, bytes)) and hasattr(size, "__len__") and len(size) == 2 and not any(hasattr(v, "__len__") for v in size):
         sizes = [RS._check_size(size, "standard_jpeg_thumbnail_many", integers=False)] * n
@@ -559,11 +625,11 @@ def standard_jpeg_thumbnail_many(files, size, resample="bicubic", reducing_gap=2
         steps[i] = RS._steps(f"file {i}", dw, dh, final, box, f[i], gap)
         return s
 
-    ctx, out, out_off, shapes = _decode_files(files, device, progressive, np.ones(n, np.int32), choose, layout_440)
+    ctx, out, out_off, shapes, comps = _decode_files(files, device, progressive, np.ones(n, np.int32), choose, layout_440, modes)
     if all(st["src"] == st["dst"] and st["box"] == (0, 0) + st["src"] for st in steps):
-        res = [out[int(o):int(o) + h * w * 3].view(h, w, 3) for o, (h, w) in zip(out_off, shapes)]
+        res = _views(out, out_off, shapes, comps)
     else:
-        res = RS._run(ctx, out.data_ptr(), out.numel(), out_off, steps, f)
+        res = RS._run(ctx, out.data_ptr(), out.numel(), out_off, steps, f, comps)
     for i, t in enumerate(res):                      # what Pillow keeps in im.info["comment"] over thumbnail(): see standard_jpeg_encode_many
         com = _jpeg_comment(files[i], i)
         if com is not None:
@@ -1243,16 +1309,20 @@ def standard_jpeg_encode_many(images, quality=75, subsampling="4:2:0", optimize:
 
 def standard_jpeg_thumbnail_jpeg_many(files, size, quality=75, subsampling="4:2:0", optimize: bool = False, progressive_out: bool = False,
                                       resample="bicubic", reducing_gap=2.0, progressive: bool = False, device: int = 0,
-                                      restart_marker_blocks: int = 0, restart_marker_rows: int = 0, layout_440: bool = False) -> List[bytes]:
+                                      restart_marker_blocks: int = 0, restart_marker_rows: int = 0, layout_440: bool = False,
+                                      mode="RGB") -> List[bytes]:
     """JPEG files in, their thumbnails out as JPEG files: ``standard_jpeg_encode_many(standard_jpeg_thumbnail_many(files, size, resample,
     reducing_gap, progressive, device), quality, subsampling, optimize, progressive_out, device)`` -- for a three-component source file
     i equals ``im = Image.open(io.BytesIO(files[i])); im.thumbnail(size, resample, reducing_gap=reducing_gap); im.save(buf, "JPEG",
     quality=q_i, subsampling=subsampling, optimize=optimize, progressive=progressive_out)`` byte for byte.  The thumbnails never leave
     the device: only the decoder's status words and the finished files are read back.  Like Pillow's save it carries no metadata
     over (no EXIF, ICC profile or density) but a source's COM segment, which Pillow from 9.4 on writes again from
-    ``im.info["comment"]``: the thumbnails carry it as ``jpeg_comment`` and the encoder writes it (both documented there).  A grey (single-component) source comes out as a three-component file with neutral chroma; Pillow keeps mode "L"
-    there and writes a one-component file, which this call does not write (standard_jpeg_encode_many(mode="L") does, from [H, W] planes: the
-    thumbnails here are three-channel).
+    ``im.info["comment"]``: the thumbnails carry it as ``jpeg_comment`` and the encoder writes it (both documented there).
+    mode: standard_jpeg_thumbnail_many's, handed to it, and the matching mode to standard_jpeg_encode_many.  "RGB" (the default, the
+    call as it always was): a grey (single-component) source comes out as a three-component file with neutral chroma.  "auto": every
+    file in Pillow's own mode -- a grey source leaves as the ONE-component file of Pillow's ``im.thumbnail(size); im.save(...)``, byte
+    for byte, a third of the pixel traffic on the way; colour sources as without the keyword.  "L": colour sources leave grey too,
+    from their luma plane (standard_jpeg_thumbnail_many's recipe, then ``save``; not ``convert("L")``).  A list gives one mode per file.
     files, size, resample, reducing_gap, progressive (whether progressive SOURCES are accepted): standard_jpeg_thumbnail_many's.
     quality (one, or one per file), subsampling, optimize, progressive_out: standard_jpeg_encode_many's quality, subsampling, optimize
     and progressive; restart_marker_blocks, restart_marker_rows: passed through to it (Pillow's save options).  Every argument is checked, and every header parsed, before any device work; a file whose scan is corrupt raises
@@ -1264,5 +1334,7 @@ def standard_jpeg_thumbnail_jpeg_many(files, size, quality=75, subsampling="4:2:
     if not files:
         raise ValueError("standard_jpeg_thumbnail_jpeg_many needs at least one file")
     qualities = _check_qualities(quality, len(files), "file")
-    thumbs = standard_jpeg_thumbnail_many(files, size, resample, reducing_gap, progressive, device, layout_440)
-    return _encode_many(get_context(device), _check_images(thumbs), qualities, ss, opt, prog, rst)
+    modes = _check_modes(mode, len(files))
+    thumbs = standard_jpeg_thumbnail_many(files, size, resample, reducing_gap, progressive, device, layout_440, modes)
+    enc_mode = modes[0] if all(m == modes[0] for m in modes) else "auto"      # a per-file mix: each thumbnail's rank says what it is
+    return _encode_many(get_context(device), _check_images(thumbs, enc_mode), qualities, ss, opt, prog, rst)

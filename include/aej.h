@@ -446,7 +446,17 @@ AEJ_API int aej_jfif_recon_batch_prog(aej_ctx *ctx, int batch, int H, int W, int
  *   [ceil(height / scale)][ceil(width / scale)][3] at out_offsets_host[i].  The entropy decode is the same; the reconstruction of a
  *   scaled file is one kernel of reduced IDCTs (4 x 4, 2 x 2, 1 x 1 for luma; 4:2:0 chroma one size larger, so it is not up-sampled)
  *   that needs no sample planes, so the workspace is smaller.  With every scale 1 both calls are aej_jpegdec_batch and
- *   aej_jpegdec_workspace_bytes byte for byte.  (Additions to ABI 3: no existing signature, struct or behaviour changed.) */
+ *   aej_jpegdec_workspace_bytes byte for byte.  (Additions to ABI 3: no existing signature, struct or behaviour changed.)
+ * aej_jpegdec_batch_mode / aej_jpegdec_workspace_bytes_mode: the _scaled calls with components_host [n] as well, each 3 or 1 (anything
+ *   else: AEJ_ERR_ARG, 0 bytes).  3: image i is [h][w][3] as above.  1: image i is [h][w], h = ceil(height / scale), w = ceil(width /
+ *   scale): the samples of a one-component file, the luma plane of a three-component one -- libjpeg's out_color_space = JCS_GRAYSCALE,
+ *   Pillow's im.draft("L", ...); NOT a conversion of the RGB image (no ITU-R 601 weighting of clamped R, G, B).  out_offsets_host[i] +
+ *   h * w * components must lie inside out_bytes, and exactly those bytes of out are written.  A NULL scales_host means every scale 1,
+ *   a NULL components_host every count 3.  The entropy decode is the same (an interleaved scan carries its chroma, which is decoded);
+ *   the reconstruction of a luma file is one kernel at every scale, full size included -- the IDCTs of its luma blocks into LDS, then
+ *   whole-dword row stores -- that never reads a chroma block, so such a file adds no sample planes to the workspace: that of a call
+ *   never exceeds the same call's with every count 3.  With every count 3 both calls are the _scaled ones byte for byte, launches
+ *   included.  (Additions to ABI 3: no existing signature, struct or behaviour changed.) */
 enum {
     AEJ_JPEGDEC_OK = 0, AEJ_JPEGDEC_TRUNCATED = 1 /* the scan ends before the last MCU */, AEJ_JPEGDEC_BAD_CODE = 2 /* not in the table */,
     AEJ_JPEGDEC_RUN_PAST_63 = 3 /* an AC run beyond the block */, AEJ_JPEGDEC_BAD_DC = 4 /* DC category above 11 */,
@@ -484,6 +494,11 @@ AEJ_API uint64_t aej_jpegdec_workspace_bytes_scaled(aej_ctx *ctx, const aej_jpeg
 AEJ_API int aej_jpegdec_batch_scaled(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host, const uint8_t *scans,
                                      uint64_t scans_bytes, const int64_t *scan_offsets_host, uint8_t *out, uint64_t out_bytes,
                                      const int64_t *out_offsets_host, int32_t *status, void *workspace, uint64_t workspace_bytes);
+AEJ_API uint64_t aej_jpegdec_workspace_bytes_mode(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host,
+                                                  const int *components_host);
+AEJ_API int aej_jpegdec_batch_mode(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host, const int *components_host,
+                                   const uint8_t *scans, uint64_t scans_bytes, const int64_t *scan_offsets_host, uint8_t *out, uint64_t out_bytes,
+                                   const int64_t *out_offsets_host, int32_t *status, void *workspace, uint64_t workspace_bytes);
 
 /* ---- progressive JPEG files decoded on the device (standard_jpeg_decode_many(..., progressive=True)) ----------------------------------
  * SOF2 files with Huffman coding, under the frame rules of aej_jpegdec_parse_host (8-bit, 1 or 3 components, 4:4:4 / 4:2:2 / 4:2:0 /
@@ -508,7 +523,10 @@ AEJ_API int aej_jpegdec_batch_scaled(aej_ctx *ctx, const aej_jpegdec_desc *descs
  *   one launch per dependency level decodes every restart segment of every scan of that level, one thread per segment (DC refinement:
  *   one thread per MCU), into the file's coefficients; the baseline path's IDCT and colour kernels finish.  A bad scan marks its file
  *   and never reads or writes outside its own bytes and its file's coefficients.  Workspace: aej_jpegprog_workspace_bytes.
- * aej_jpegprog_batch_scaled / aej_jpegprog_workspace_bytes_scaled: with scales_host [n], as aej_jpegdec_batch_scaled. */
+ * aej_jpegprog_batch_scaled / aej_jpegprog_workspace_bytes_scaled: with scales_host [n], as aej_jpegdec_batch_scaled.
+ * aej_jpegprog_batch_mode / aej_jpegprog_workspace_bytes_mode: with scales_host [n] and components_host [n] (either may be NULL), as
+ *   aej_jpegdec_batch_mode: the progressive decoder finishes with the baseline path's reconstruction, the luma kernel included.
+ *   (Additions to ABI 3: no existing signature, struct or behaviour changed.) */
 typedef struct aej_jpegprog_frame {
     int32_t width, height;
     int32_t ncomp;             /* 1 or 3 */
@@ -544,6 +562,12 @@ AEJ_API int aej_jpegprog_batch_scaled(aej_ctx *ctx, const aej_jpegprog_frame *fr
                                       const int *scales_host, const uint8_t *data, uint64_t data_bytes, const int64_t *data_offsets_host,
                                       uint8_t *out, uint64_t out_bytes, const int64_t *out_offsets_host, int32_t *status, void *workspace,
                                       uint64_t workspace_bytes);
+AEJ_API uint64_t aej_jpegprog_workspace_bytes_mode(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
+                                                   const int *scales_host, const int *components_host);
+AEJ_API int aej_jpegprog_batch_mode(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
+                                    const int *scales_host, const int *components_host, const uint8_t *data, uint64_t data_bytes,
+                                    const int64_t *data_offsets_host, uint8_t *out, uint64_t out_bytes, const int64_t *out_offsets_host,
+                                    int32_t *status, void *workspace, uint64_t workspace_bytes);
 
 /* ---- images of mixed sizes and qualities encoded in one call (standard_jpeg_encode_many) -------------------------------------------------
  * The files of aej_jfif_encode_batch_opt / _prog -- Pillow's Image.save(buf, "JPEG", quality, subsampling, optimize, progressive), byte
@@ -816,7 +840,7 @@ AEJ_API int aej_jfif_transform_batch_cut(aej_ctx *ctx, const aej_jpegdec_desc *d
                                          int64_t *lengths, uint64_t *total_host, int32_t *status, int32_t *n_groups_host, void *workspace,
                                          uint64_t workspace_bytes);
 
-/* ---- Pillow's resize, reduce and thumbnail for packed 8-bit RGB images (resize_many, standard_jpeg_thumbnail_many) ------------------
+/* ---- Pillow's resize, reduce and thumbnail for packed 8-bit RGB (_ch entries: and mode-"L") images (resize_many, standard_jpeg_thumbnail_many) ------------------
  * Image.resize with the convolution filters, Image.reduce and the reducing_gap step of resize, bit for bit, for many images of
  * different sizes in one call (csrc/resample.hip).  An image is uint8 [h][w][3], packed.  Per image, in this order:
  *   1. reduce (only when reduce_x > 1 or reduce_y > 1): the region reduce_box = x0, y0, x1, y1 of the source is cut into reduce_x x
@@ -841,7 +865,14 @@ AEJ_API int aej_jfif_transform_batch_cut(aej_ctx *ctx, const aej_jpegdec_desc *d
  *   vertical: each one grid over every image that needs it) and one upload of the descriptors and tap tables, then waits for the
  *   upload; nothing is copied back.  Every descriptor is checked before any device work: AEJ_ERR_ARG naming the image for an unknown
  *   filter, a size below 1 or above 65535, a reduce factor below 1, an empty box or one outside the image, an image outside src_bytes
- *   / dst_bytes; AEJ_ERR_UNSUPPORTED naming the image for the tall one.  Workspace: aej_resample_workspace_bytes with the same descriptors (0 for descriptors the call refuses). */
+ *   / dst_bytes; AEJ_ERR_UNSUPPORTED naming the image for the tall one.  Workspace: aej_resample_workspace_bytes with the same descriptors (0 for descriptors the call refuses).
+ * aej_resample_batch_ch / aej_resample_workspace_bytes_ch: the same calls with channels_host [n], each 3 or 1 (anything else:
+ *   AEJ_ERR_ARG naming the image, 0 bytes; NULL: every image 3): image i is uint8 [h][w][channels], packed -- 1 is Pillow's mode "L",
+ *   the same reduce and passes on one channel (Pillow's mode-"L" resize equals one channel of its RGB resize of three copies).  The
+ *   descriptor is unchanged: its offsets are bytes.  Exactly dst_w * dst_h * channels bytes and no other byte of dst are written.
+ *   Images of either count form launches of their own: at most six kernels for a mixed call, and with every count 3 the calls are
+ *   aej_resample_batch and aej_resample_workspace_bytes byte for byte, launches included.  (Additions to ABI 3: no existing signature,
+ *   struct or behaviour changed.) */
 enum { AEJ_RESAMPLE_LANCZOS = 1, AEJ_RESAMPLE_BILINEAR = 2, AEJ_RESAMPLE_BICUBIC = 3, AEJ_RESAMPLE_BOX = 4, AEJ_RESAMPLE_HAMMING = 5 }; /* Pillow's integers */
 typedef struct aej_resample_desc {
     int64_t src_offset, dst_offset;
@@ -857,6 +888,9 @@ AEJ_API int aej_resample_taps_host(int in_size, float in0, float in1, int out_si
 AEJ_API uint64_t aej_resample_workspace_bytes(aej_ctx *ctx, const aej_resample_desc *descs_host, int n);
 AEJ_API int aej_resample_batch(aej_ctx *ctx, const aej_resample_desc *descs_host, int n, const uint8_t *src, uint64_t src_bytes, uint8_t *dst,
                                uint64_t dst_bytes, void *workspace, uint64_t workspace_bytes);
+AEJ_API uint64_t aej_resample_workspace_bytes_ch(aej_ctx *ctx, const aej_resample_desc *descs_host, int n, const int *channels_host);
+AEJ_API int aej_resample_batch_ch(aej_ctx *ctx, const aej_resample_desc *descs_host, int n, const int *channels_host, const uint8_t *src,
+                                  uint64_t src_bytes, uint8_t *dst, uint64_t dst_bytes, void *workspace, uint64_t workspace_bytes);
 
 #ifdef __cplusplus
 }

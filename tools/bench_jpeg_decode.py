@@ -3,7 +3,7 @@ markers -- Pillow's default, decoded by the self-synchronising subsequences -- a
 decoding them on a thread pool and uploading its pixels.
 
     python tools/bench_jpeg_decode.py [--batch 64] [--repeats 3] [--threads 16] [--subseq-bits N] [--progressive] [--scale S]
-                                      [--transcoded] [--no-pillow] [--out FILE]
+                                      [--mode RGB|L] [--transcoded] [--no-pillow] [--out FILE]
 
 --progressive writes the same files with progressive=True and decodes them with standard_jpeg_decode_many(..., progressive=True)
 (csrc/jpegprog.hip: one thread per restart segment and dependency level, so the files without restart markers are a serial decode
@@ -11,6 +11,9 @@ per scan and the restart-per-row files show what the kernels do when the format 
 
 --scale 2 / 4 / 8 decodes at that fraction of the size on both sides: standard_jpeg_decode_many(..., scale=S) (csrc/jpegdec.hip
 k_jd_scaled) against Pillow after im.draft("RGB", (W // S, H // S)); the gigapixels per second still count the files' full-size pixels.
+
+--mode L decodes to the luma plane alone on both sides: standard_jpeg_decode_many(..., mode="L") (csrc/jpegdec.hip k_jd_luma), uint8
+[h, w] tensors, against Pillow after im.draft("L", (W // S, H // S)) -- not convert("L").
 
 --transcoded adds a third case: the files without restart markers put through standard_jpeg_transcode_many(...,
 restart_marker_rows=1) (progressive output with --progressive) -- the lossless way to make an archive cheap to decode -- with the time
@@ -52,6 +55,7 @@ def main():
     ap.add_argument("--subseq-bits", type=int, default=0, help="jpegdec_subseq_bits (0: the library's default)")
     ap.add_argument("--progressive", action="store_true", help="progressive files through csrc/jpegprog.hip")
     ap.add_argument("--scale", type=int, default=1, choices=(1, 2, 4, 8), help="decode at 1 / scale of the size (Pillow: Image.draft)")
+    ap.add_argument("--mode", default="RGB", choices=("RGB", "L"), help="L: the luma plane alone (Pillow: Image.draft('L', ...))")
     ap.add_argument("--transcoded", action="store_true", help="also: the no-restart files transcoded with restart_marker_rows=1")
     ap.add_argument("--no-pillow", action="store_true")
     ap.add_argument("--out")
@@ -65,6 +69,8 @@ def main():
            "pillow_threads": a.threads, "progressive": a.progressive, "cases": {}}
     if a.scale != 1:
         res["scale"] = a.scale
+    if a.mode != "RGB":
+        res["mode"] = a.mode
     pool = ThreadPoolExecutor(a.threads)
 
     def save(i, opts):
@@ -74,12 +80,14 @@ def main():
 
     def pil_load(f):
         im = Image.open(io.BytesIO(f))
-        if a.scale != 1:
-            im.draft("RGB", (W // a.scale, H // a.scale))
-        return np.asarray(im.convert("RGB"))
+        if a.scale != 1 or a.mode == "L":
+            im.draft(a.mode, (W // a.scale, H // a.scale))
+        return np.asarray(im if a.mode == "L" else im.convert("RGB"))
 
     def decode(files):
         how = dict(scale=a.scale) if a.scale != 1 else {}
+        if a.mode != "RGB":
+            how["mode"] = a.mode
         return A.standard_jpeg_decode_many(files, progressive=True, **how) if a.progressive else A.standard_jpeg_decode_many(files, **how)
 
     plain, extra = None, {}

@@ -1,12 +1,14 @@
 """JPEG thumbnail timing: 64 x 4K Pillow files (quality 75, 4:2:0) to thumbnails of (256, 256) and (1024, 1024), bicubic, three ways:
 
-    python tools/bench_jpeg_thumbnail.py [--batch 64] [--repeats 3] [--threads 16] [--out FILE]
+    python tools/bench_jpeg_thumbnail.py [--batch 64] [--repeats 3] [--threads 16] [--mode RGB|L] [--out FILE]
 
 "gpu" is standard_jpeg_thumbnail_many: header parsing and the plan on the host, the scaled decode, then csrc/resample.hip on the
 decoder's output; it ends with device uint8 [h, w, 3] tensors and reads nothing back but the decoder's status words.
 "decode_host_resize" is the route without it: standard_jpeg_decode_many(scale=s) with thumbnail_plan's scale, a copy of the pixels to
 the host, Pillow's Image.resize with the box and reducing_gap on --threads threads, one upload of the results.
 "pillow" is Image.open(buf).thumbnail(size) per file on --threads threads, then one upload of the results.
+--mode L: every route in one channel -- standard_jpeg_thumbnail_many(..., mode="L") and standard_jpeg_decode_many(..., mode="L") end with
+uint8 [h, w] tensors, and Pillow is the thumbnail of the file's one draft("L", ...) call (pil_thumbnail below), not convert("L").
 Every time is a host clock around work that ends in a device synchronise, after one warm-up; the median of --repeats is reported.  The
 GPU's pixels are checked against Pillow's for every file before timing.  Prints one JSON line (and writes it to --out).
 
@@ -56,6 +58,20 @@ def save_files(x, pool):
     return list(pool.map(save, range(len(x))))
 
 
+def pil_thumbnail(f, size, mode, gap=2.0):
+    """Pillow's thumbnail of one file.  mode "L": the one it makes when the file's one draft() call asks for mode "L" (thumbnail()'s own
+    draft does nothing after a first one): the draft at thumbnail()'s requested size, then thumbnail()'s resize over the box it returns"""
+    im = Image.open(io.BytesIO(f))
+    if mode != "L":
+        im.thumbnail(size, BICUBIC, reducing_gap=gap)
+        return np.asarray(im.convert("RGB"))
+    plan = A.thumbnail_plan(im.size[0], im.size[1], size, gap)
+    res = im.draft("L", (int(size[0] * gap), int(size[1] * gap)) if plan is not None else None)
+    if plan is not None and im.size != tuple(plan[2]):
+        im = im.resize(tuple(plan[2]), BICUBIC, box=res[1], reducing_gap=gap)
+    return np.asarray(im)
+
+
 def trace_calls(a):
     """the calls of the kernel-trace run: the first of each kind also warms the workspace up and is left out of the summary"""
     pool = ThreadPoolExecutor(a.threads)
@@ -69,14 +85,14 @@ def trace_calls(a):
 
     for size in SIZES:
         scale = A.thumbnail_plan(W, H, size)[0]
-        for fn in (lambda: A.standard_jpeg_thumbnail_many(files, size), lambda: A.standard_jpeg_decode_many(files, scale=scale)):
+        for fn in (lambda: A.standard_jpeg_thumbnail_many(files, size, **a.how), lambda: A.standard_jpeg_decode_many(files, scale=scale, **a.how)):
             for _ in range(a.trace_calls):
                 mark()
                 out = fn()
                 torch.cuda.synchronize()
                 del out
     mark()
-    print(json.dumps({"batch": a.batch, "calls_per_kind": a.trace_calls, "sizes": [list(s) for s in SIZES]}))
+    print(json.dumps({"batch": a.batch, "calls_per_kind": a.trace_calls, "sizes": [list(s) for s in SIZES], "mode": a.mode}))
 
 
 def short(name):
@@ -166,10 +182,12 @@ def main():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--mode", default="RGB", choices=("RGB", "L"), help="L: one-channel thumbnails of the luma plane (Pillow: Image.draft('L', ...))")
     ap.add_argument("--out")
     ap.add_argument("--trace-calls", type=int, default=0, help="the run to put under rocprofv3: this many calls of each kind per size")
     ap.add_argument("--trace-summary", help="the directory rocprofv3 wrote such a run's trace to (with --trace-calls as in that run)")
     a = ap.parse_args()
+    a.how = {} if a.mode == "RGB" else {"mode": a.mode}      # RGB: the calls without the keyword
     if a.trace_summary:
         a.trace_calls = a.trace_calls or 4
         return trace_summary(a)
@@ -179,24 +197,22 @@ def main():
     pool = ThreadPoolExecutor(a.threads)
     files = save_files(images(a.batch), pool)
     res = {"batch": a.batch, "H": H, "W": W, "quality": 75, "filter": "bicubic", "reducing_gap": 2.0, "pillow_threads": a.threads,
-           "file_mb": sum(len(f) for f in files) / 1e6, "cases": {}}
+           "file_mb": sum(len(f) for f in files) / 1e6, "mode": a.mode, "cases": {}}
     for size in SIZES:
         plan = A.thumbnail_plan(W, H, size)
         scale, factors, final, box = plan
 
         def pil_thumb(f):
-            im = Image.open(io.BytesIO(f))
-            im.thumbnail(size, BICUBIC)
-            return np.asarray(im.convert("RGB"))
+            return pil_thumbnail(f, size, a.mode)
 
         def gpu():
-            return A.standard_jpeg_thumbnail_many(files, size)
+            return A.standard_jpeg_thumbnail_many(files, size, **a.how)
 
         def pillow():
             return torch.from_numpy(np.stack(list(pool.map(pil_thumb, files)))).to("cuda:0")
 
         def decode_host_resize():
-            dec = A.standard_jpeg_decode_many(files, scale=scale)
+            dec = A.standard_jpeg_decode_many(files, scale=scale, **a.how)
             host = [d.cpu().numpy() for d in dec]
             out = pool.map(lambda p: np.asarray(Image.fromarray(p).resize(final, BICUBIC, box=box, reducing_gap=2.0)), host)
             return torch.from_numpy(np.stack(list(out))).to("cuda:0")
