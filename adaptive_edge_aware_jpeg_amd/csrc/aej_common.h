@@ -64,6 +64,8 @@ struct Tuning {
     int sobel_lds = 0;             // "sobel_lds": 1 = the LDS-tiled Sobel / NMS kernel of rounds 1-2 for every shape
     int dct_multi = 1;             // "dct_multi": 1 = calls of at most 8 Mpx run the DCTs of sizes 4 .. 64 as one launch (0: one launch per size)
     int sobel_xcd = 1;             // "sobel_xcd": 1 = each XCD works on a contiguous range of the register Sobel kernel's tiles (0: round-robin, rounds 3-4)
+    int qt_chunks = 1;             // "qt_chunks": 1 = min block 4 runs the quadtree's chunk-run kernels (in-plane chunks only, several per wave; 0: one wave per chunk of the root square)
+    int qt_chunk_run = 0;          // "qt_chunk_run": chunks per wave of those kernels, 0 = automatic (1 .. 16 by the call's in-plane chunks: about 4096 waves)
 };
 
 // natural (row-major) index of zigzag positions 0 .. 63 of an 8 x 8 block: the one place the order is written down

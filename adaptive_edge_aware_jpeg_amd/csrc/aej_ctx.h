@@ -73,6 +73,7 @@ struct aej_ctx {
     int chain_hook = 0;                // run_canny_chain publishes chain_event after the blur (2) / Sobel (3) stage of the part being enqueued
     hipEvent_t chain_event = nullptr;
     aej::Tuning tune;                  // aej_set_option: kernel / launch-shape choices (nothing in the library reads the environment)
+    int qt_chunk_launches = 0;         // aej_get_option "qt_chunk_launches": quadtree stages the chunk-run kernels have served (aej_set_option resets it)
     int jd_subseq_bits = 2048;         // aej_set_option "jpegdec_subseq_bits": subsequence length of aej_jpegdec_batch's Huffman decode
     long long jd_sync_rounds = 0;      // sync rounds of the last aej_jpegdec_batch
     struct aej_pending *pending = nullptr;     // the call between aej_encode_batch_begin and aej_encode_batch_end

@@ -72,9 +72,21 @@ struct QtBuffers {
 };
 void launch_qt_cells(hipStream_t st, const Geom &g, const QtGeom &q, const unsigned long long *edge_bits, const QtBuffers &qb);
 void launch_pack_edge_bits(hipStream_t st, const Geom &g, const unsigned char *edge, unsigned long long *bits);
-void launch_qt_count(hipStream_t st, const Geom &g, const QtGeom &q, const QtBuffers &qb);
-void launch_qt_scan(hipStream_t st, const Geom &g, const QtGeom &q, const QtBuffers &qb);
-void launch_qt_emit(hipStream_t st, const Geom &g, const QtGeom &q, const QtBuffers &qb);
+// The chunk-run kernel set (Tuning::qt_chunks; min block 4, at least 16 cells per root side): its count and emit grids cover the chunks
+// whose origin lies inside the plane, a wave taking `run` consecutive ones of the sequence (image, layer, chunk row, chunk column).
+struct QtRuns {
+    int ncx0, ncx1, ncx2;   // chunk columns of layers 0 .. 2 that lie (partly) inside the plane
+    int ncy0, ncy1, ncy2;   // chunk rows
+    int nin0, nin1, nin2;   // ncx * ncy
+    int per_image, total;   // in-plane chunks of one image / of the call
+    int run;                // chunks per wave
+};
+bool qt_chunk_runs(const Geom &g, const QtGeom &q, const Tuning &t, QtRuns &r);      // false: the general kernels serve this call
+bool qt_needs_upper(const Geom &g, const QtGeom &q);      // k_qt_upper runs, and QtBuffers::pyr has to be zero in front of it
+// runs: what qt_chunk_runs() gave for this call, or null for the general kernels (decided once per call, by run_quadtree)
+void launch_qt_count(hipStream_t st, const Geom &g, const QtGeom &q, const QtBuffers &qb, const QtRuns *runs);      // (the chunk-run count kernel clears qb.overflow)
+void launch_qt_scan(hipStream_t st, const Geom &g, const QtGeom &q, const QtBuffers &qb, const QtRuns *runs);
+void launch_qt_emit(hipStream_t st, const Geom &g, const QtGeom &q, const QtBuffers &qb, const QtRuns *runs);
 
 // dct.hip
 constexpr int kBigBlocks = 128;      // workgroups (and scratch slots of 256 KiB) of the 256 x 256 kernels

@@ -367,6 +367,9 @@ const OptionDef kOptions[] = {
     { "sobel_lds", &aej::Tuning::sobel_lds, nullptr, 0, 1, true },
     { "sobel_xcd", &aej::Tuning::sobel_xcd, nullptr, 0, 1, true },
     { "dct_multi", &aej::Tuning::dct_multi, nullptr, 0, 1, true },
+    { "qt_chunks", &aej::Tuning::qt_chunks, nullptr, 0, 1, true },
+    { "qt_chunk_run", &aej::Tuning::qt_chunk_run, nullptr, 0, 16, true },
+    { "qt_chunk_launches", nullptr, &aej_ctx::qt_chunk_launches, 0, 0x7fffffff, false },
     { "sub_chain", nullptr, &aej_ctx::sub_chain, -1, 3, false },
     { "jpegdec_subseq_bits", nullptr, &aej_ctx::jd_subseq_bits, 32, 1 << 20, false },
 };

@@ -175,13 +175,18 @@ static int clear_canny_ws(aej_ctx *ctx, const CannyWs &w)
 static int run_quadtree(aej_ctx *ctx, const Geom &g, const QtGeom &q, QtWs &w, const unsigned long long *edge_bits)
 {
     hipStream_t st = ctx->stream;
+    // The fill clears the upper pyramid and the overflow flag.  The pyramid is only read when k_qt_upper runs, and the chunk-run count
+    // kernel clears the flag itself: a call that needs neither (the codec's 4 .. 64 blocks) has no fill in front of its quadtree.
+    QtRuns runs_of_call;
+    const QtRuns *runs = qt_chunk_runs(g, q, ctx->tune, runs_of_call) ? &runs_of_call : nullptr;      // which kernel set serves the call: decided here, once
     if (ctx->capturing) launch_zero(st, w.zero_begin, (size_t)(w.zero_end - w.zero_begin));
-    else AEJ_HIP_CHECK(hipMemsetAsync(w.zero_begin, 0, (size_t)(w.zero_end - w.zero_begin), st));
+    else if (qt_needs_upper(g, q) || !runs) AEJ_HIP_CHECK(hipMemsetAsync(w.zero_begin, 0, (size_t)(w.zero_end - w.zero_begin), st));
     w.qb.edge_bits = edge_bits;
     launch_qt_cells(st, g, q, edge_bits, w.qb);
-    launch_qt_count(st, g, q, w.qb);
-    launch_qt_scan(st, g, q, w.qb);
-    launch_qt_emit(st, g, q, w.qb);
+    launch_qt_count(st, g, q, w.qb, runs);
+    launch_qt_scan(st, g, q, w.qb, runs);
+    launch_qt_emit(st, g, q, w.qb, runs);
+    if (runs) ctx->qt_chunk_launches++;
     AEJ_HIP_CHECK(hipGetLastError());
     return 0;
 }

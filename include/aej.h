@@ -126,6 +126,11 @@ AEJ_API int aej_get_schedule_host(aej_ctx *ctx, int batch, int H, int W, int32_t
  *   "sobel_lds"             0 | 1 (0)          1: the LDS-tiled Sobel / NMS kernel for every shape (default: register kernel when w % 4 == 0)
  *   "dct_multi"             0 | 1 (1)          1: calls of at most 8 Mpx run the DCTs of block sizes 4 .. 64 as ONE launch (latency), 0: one launch per size
  *   "sobel_xcd"             0 | 1 (1)          1: each XCD gets a contiguous range of the register Sobel kernel's tiles (0: round-robin)
+ *   "qt_chunks"             0 | 1 (1)          1: with min block 4 the quadtree's count / emit kernels cover the in-plane chunks only, several per
+ *                                              wave, and count from ballot masks (0: one wave per chunk of the Morton root square)
+ *   "qt_chunk_run"          0..16 (0)          chunks per wave of those kernels; 0 = automatic (1 .. 16, sized for about 4096 waves per call)
+ *   "qt_chunk_launches"     counter            quadtree stages the chunk-run kernels have served on this context (read it with
+ *                                              aej_get_option; setting it, usually to 0, restarts the count)
  *   "sub_chain"             -1..3 (-1)         which stage of the previously enqueued part a part's colour stage waits for: 0 none, 1 colour,
  *                                              2 blur, 3 Sobel; -1 = 1
  *   "jpegdec_subseq_bits"   32..1048576 (2048) bits per subsequence of aej_jpegdec_batch's self-synchronising Huffman decode */
