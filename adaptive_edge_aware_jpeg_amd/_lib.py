@@ -257,6 +257,13 @@ SIGNATURES = {
     "aej_jpegdec_batch_scaled": (_I, [_P, _P, _I, _P, _P, _U64, _P, _P, _U64, _P, _P, _P, _U64]),
     "aej_jpegdec_workspace_bytes_mode": (_U64, [_P, _P, _I, _P, _P]),
     "aej_jpegdec_batch_mode": (_I, [_P, _P, _I, _P, _P, _P, _U64, _P, _P, _U64, _P, _P, _P, _U64]),
+    "aej_jpegdec_workspace_bytes_box": (_U64, [_P, _P, _I, _P, _P, _P]),
+    "aej_jpegdec_batch_box": (_I, [_P, _P, _I, _P, _P, _P, _P, _U64, _P, _P, _U64, _P, _P, _P, _U64]),
+    "aej_jpegdec_box_window_host": (_I, [_P, _P, _P]),
+    "aej_jpegprog_box_window_host": (_I, [_P, _P, _P]),
+    "aej_jpegdec_box_stats": (_I, [_P, _P]),
+    "aej_jpegprog_workspace_bytes_box": (_U64, [_P, _P, _P, _I, _P, _P, _P]),
+    "aej_jpegprog_batch_box": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _U64, _P, _P, _U64, _P, _P, _P, _U64]),
     "aej_jpegprog_parse_host": (_I, [_P, _U64, _P, _P, _I, _P, _I]),
     "aej_jpegprog_workspace_bytes": (_U64, [_P, _P, _P, _I]),
     "aej_jpegprog_batch": (_I, [_P, _P, _P, _I, _P, _U64, _P, _P, _U64, _P, _P, _P, _U64]),

@@ -76,6 +76,7 @@ struct aej_ctx {
     int qt_chunk_launches = 0;         // aej_get_option "qt_chunk_launches": quadtree stages the chunk-run kernels have served (aej_set_option resets it)
     int jd_subseq_bits = 2048;         // aej_set_option "jpegdec_subseq_bits": subsequence length of aej_jpegdec_batch's Huffman decode
     long long jd_sync_rounds = 0;      // sync rounds of the last aej_jpegdec_batch
+    long long jd_box_stats[3] = { 0, 0, 0 };      // aej_jpegdec_box_stats: restart segments, those decoded, coefficient blocks stored of the last aej_jpegdec_batch_box with a box
     struct aej_pending *pending = nullptr;     // the call between aej_encode_batch_begin and aej_encode_batch_end
     // optional stage timing (aej_set_profiling): events on ctx->stream around each stage of aej_encode_batch
     bool profiling = false;

@@ -329,7 +329,7 @@ int jfifprog_scan_device(hipStream_t st, const short *coefs_host, long long n, i
 #include "jpegdec_core.h"
 
 namespace aej {
-struct JdBufSizes { long long chunks, segs, slots, blocks, clean, planes, px, grp[3], grp440[3], grpl[4]; };      // totals over the files of one call (grp, grp440, grpl: JdFile::grp_base, ::grp440_base, ::grpl_base)
+struct JdBufSizes { long long chunks, segs, slots, blocks, clean, planes, px, grp[3], grp440[3], grpl[4], grpb; };      // totals over the files of one call (grp, grp440, grpl, grpb: JdFile::grp_base, ::grp440_base, ::grpl_base, ::grpb_base)
 struct JdBufs {
     JdFile *files; aej_jpegdec_desc *descs; int *last_change;      // one upload: files, descriptors, the "last round that changed" word
     int *cnt; long long *pre, *clean_len; JdSeg *segs; unsigned char *clean; JdSlots sl; short *coef; unsigned char *planes;
@@ -354,10 +354,21 @@ void jpeg_stream_layout(long long len, int n_segments, int S, JdFile &F, JdBufSi
 // one file's coefficient blocks and, decoded at scale 1 << shift, its sample planes and pixels (shift 0) or its workgroups of the
 // scaled kernel (1..3), or, with kJdLuma added to shift, its workgroups of the luma kernel (d's frame fields): F's reconstruction
 // fields, z's totals
-void jpeg_recon_layout(const aej_jpegdec_desc &d, int shift, JdFile &F, JdBufSizes &z);
+// box (NULL, or the whole image: none): left, top, right, bottom inside the image (jpeg_box_inside), full size only -- the file's
+// workgroups of k_jd_box and no sample planes; window_coef: only the coefficients of the window's MCU rows are stored (baseline files)
+void jpeg_recon_layout(const aej_jpegdec_desc &d, int shift, JdFile &F, JdBufSizes &z, const int *box = nullptr, bool window_coef = true);
+template <class D>                     // D: aej_jpegdec_desc or aej_jpegprog_frame
+bool jpeg_box_whole(const D &d, const int *box) { return !box || (box[0] == 0 && box[1] == 0 && box[2] == d.width && box[3] == d.height); }
+template <class D>
+bool jpeg_box_inside(const D &d, const int *box)
+{
+    return 0 <= box[0] && box[0] < box[2] && box[2] <= d.width && 0 <= box[1] && box[1] < box[3] && box[3] <= d.height;
+}
 inline int jpeg_scale_shift(int scale) { return scale == 1 ? 0 : scale == 2 ? 1 : scale == 4 ? 2 : scale == 8 ? 3 : -1; }      // -1: not a scale
 // shifts: log2 of every file's scale (+ kJdLuma for a file that leaves as its luma plane), or NULL for all at full size, RGB
-void jpegdec_layout(const aej_jpegdec_desc *descs, int n, int S, std::vector<JdFile> &files, JdBufSizes &z, const int *shifts = nullptr);
+// boxes: NULL or [n][4], jpeg_recon_layout's box of every file
+void jpegdec_layout(const aej_jpegdec_desc *descs, int n, int S, std::vector<JdFile> &files, JdBufSizes &z, const int *shifts = nullptr,
+                    const int *boxes = nullptr);
 unsigned long long jpegdec_carve(void *base, int n, const JdBufSizes &z, JdBufs &w);
 hipError_t launch_jpegdec_begin(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, const void *blob_host, unsigned long long blob_bytes,
                                 const unsigned char *scans, int S, int *status);
@@ -391,7 +402,8 @@ inline void jp_scan_units(const aej_jpegprog_frame &f, int ncomp, int comp0, int
 }
 int jpegprog_parse(const unsigned char *data, unsigned long long n, aej_jpegprog_frame &f, std::vector<aej_jpegprog_scan> &scans,
                    std::string &msg, bool allow440 = false);                                                           // jpegparse.hip
-bool jpegprog_layout(const aej_jpegprog_frame *frames, const aej_jpegprog_scan *scans, int n, JpLayout &y, const int *shifts = nullptr);
+bool jpegprog_layout(const aej_jpegprog_frame *frames, const aej_jpegprog_scan *scans, int n, JpLayout &y, const int *shifts = nullptr,
+                     const int *boxes = nullptr);
 unsigned long long jpegprog_blob(const JpLayout &y, std::vector<unsigned char> *out);
 unsigned long long jpegprog_carve(void *base, const JpLayout &y, JpBufs &w);
 hipError_t launch_jpegprog_entropy(hipStream_t st, const JpLayout &y, const JpBufs &w, const void *blob_host, unsigned long long blob_bytes,

@@ -272,13 +272,74 @@ static int check_scales(aej_ctx *ctx, const char *fn, const int *scales_host, in
     return fail(ctx, AEJ_ERR_ARG, "%s: file %d: scale %d (1, 2, 4 or 8)", fn, bad, scales_host[bad]);
 }
 
-static uint64_t jpegdec_workspace(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host, const int *components_host = nullptr)
+// the boxes of a _box call ([n][4] left, top, right, bottom; NULL: none): every one inside its image (*unsupported false), and none but the
+// whole image on a file that is not decoded at full size (*unsupported true); *bad: the file.  D: aej_jpegdec_desc or aej_jpegprog_frame
+template <class D>
+static bool boxes_ok(const D *frames, int n, const int32_t *boxes_host, const std::vector<int> &shifts, int *bad, bool *unsupported)
+{
+    for (int i = 0; boxes_host && i < n; i++) {
+        const int32_t *b = boxes_host + 4 * i;
+        *bad = i;
+        *unsupported = false;
+        if (!jpeg_box_inside(frames[i], b)) return false;
+        *unsupported = true;
+        if (!jpeg_box_whole(frames[i], b) && (shifts[i] & (kJdLuma - 1))) return false;
+    }
+    return true;
+}
+template <class D>
+static int check_boxes(aej_ctx *ctx, const char *fn, const D *frames, int n, const int32_t *boxes_host, const std::vector<int> &shifts)
+{
+    int bad = 0;
+    bool unsupported = false;
+    if (boxes_ok(frames, n, boxes_host, shifts, &bad, &unsupported)) return 0;
+    const int32_t *b = boxes_host + 4 * bad;
+    if (unsupported) return fail(ctx, AEJ_ERR_UNSUPPORTED, "%s: file %d: a box at scale 2, 4 or 8 is not built", fn, bad);
+    return fail(ctx, AEJ_ERR_ARG, "%s: file %d: box (%d, %d, %d, %d) is empty or leaves the %d x %d image", fn, bad, b[0], b[1], b[2], b[3],
+                frames[bad].width, frames[bad].height);
+}
+
+// jd_box_window behind the two public entries
+static int box_window_host(int width, int height, int hs, int vs, int ncomp, const int32_t *box4_host, int32_t *window4_out_host)
+{
+    if (!box4_host || !window4_out_host || width < 1 || height < 1 || (ncomp != 1 && ncomp != 3)) return AEJ_ERR_ARG;
+    if (ncomp == 3 && ((hs != 1 && hs != 2) || (vs != 1 && vs != 2))) return AEJ_ERR_ARG;
+    if (!(0 <= box4_host[0] && box4_host[0] < box4_host[2] && box4_host[2] <= width && 0 <= box4_host[1] && box4_host[1] < box4_host[3] && box4_host[3] <= height))
+        return AEJ_ERR_ARG;
+    jd_box_window(width, height, hs, vs, ncomp, false, box4_host, window4_out_host);
+    return 0;
+}
+
+extern "C" int aej_jpegdec_box_window_host(const aej_jpegdec_desc *desc_host, const int32_t *box4_host, int32_t *window4_out_host)
+{
+    if (!desc_host) return AEJ_ERR_ARG;
+    return box_window_host(desc_host->width, desc_host->height, desc_host->hs, desc_host->vs, desc_host->ncomp, box4_host, window4_out_host);
+}
+
+extern "C" int aej_jpegprog_box_window_host(const aej_jpegprog_frame *frame_host, const int32_t *box4_host, int32_t *window4_out_host)
+{
+    if (!frame_host) return AEJ_ERR_ARG;
+    return box_window_host(frame_host->width, frame_host->height, frame_host->hs, frame_host->vs, frame_host->ncomp, box4_host, window4_out_host);
+}
+
+extern "C" int aej_jpegdec_box_stats(aej_ctx *ctx, int64_t *out3_host)
+{
+    if (!ctx || !out3_host) return AEJ_ERR_ARG;
+    for (int v = 0; v < 3; v++) out3_host[v] = ctx->jd_box_stats[v];
+    return 0;
+}
+
+static uint64_t jpegdec_workspace(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host, const int *components_host = nullptr,
+                                  const int32_t *boxes_host = nullptr)
 {
     std::vector<int> shifts;
+    int bad = 0;
+    bool unsupported = false;
     if (!ctx || !jpegdec_descs_ok(descs_host, n) || !scale_shifts(scales_host, n, shifts, nullptr, components_host)) return 0;
+    if (!boxes_ok(descs_host, n, boxes_host, shifts, &bad, &unsupported)) return 0;
     std::vector<JdFile> files;
     JdBufSizes z;
-    jpegdec_layout(descs_host, n, ctx->jd_subseq_bits, files, z, shifts.data());
+    jpegdec_layout(descs_host, n, ctx->jd_subseq_bits, files, z, shifts.data(), boxes_host);
     JdBufs w;
     return jpegdec_carve(nullptr, n, z, w);
 }
@@ -297,6 +358,12 @@ extern "C" uint64_t aej_jpegdec_workspace_bytes_mode(aej_ctx *ctx, const aej_jpe
                                                      const int *components_host)
 {
     return jpegdec_workspace(ctx, descs_host, n, scales_host, components_host);
+}
+
+extern "C" uint64_t aej_jpegdec_workspace_bytes_box(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host,
+                                                    const int *components_host, const int32_t *boxes_host)
+{
+    return jpegdec_workspace(ctx, descs_host, n, scales_host, components_host, boxes_host);
 }
 
 // the entropy decode of n baseline files up to the fixed point of the sync rounds: everything of aej_jpegdec_batch before the
@@ -336,17 +403,30 @@ static int jpegdec_decode(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *
 static int jpegdec_batch(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs_host, int n, const int *scales_host, const int *components_host,
                          const uint8_t *scans,
                          uint64_t scans_bytes, const int64_t *scan_offsets_host, uint8_t *out, uint64_t out_bytes, const int64_t *out_offsets_host,
-                         int32_t *status, void *workspace, uint64_t workspace_bytes)
+                         int32_t *status, void *workspace, uint64_t workspace_bytes, const int32_t *boxes_host = nullptr)
 {
     AEJ_TRY(enter(ctx, fn));
     if (!jpegdec_descs_ok(descs_host, n)) return fail(ctx, AEJ_ERR_ARG, "%s: no files, or a descriptor aej_jpegdec_parse_host did not write", fn);
     if (!scans || !scan_offsets_host || !out || !out_offsets_host || !status || !workspace) return null_buffer(ctx, fn);
     std::vector<int> shifts;
     AEJ_TRY(check_scales(ctx, fn, scales_host, n, shifts, components_host));
+    AEJ_TRY(check_boxes(ctx, fn, descs_host, n, boxes_host, shifts));
     const int S = ctx->jd_subseq_bits;
     std::vector<JdFile> files;
     JdBufSizes z;
-    jpegdec_layout(descs_host, n, S, files, z, shifts.data());
+    jpegdec_layout(descs_host, n, S, files, z, shifts.data(), boxes_host);
+    if (z.grpb > 0) {                                        // aej_jpegdec_box_stats: from the descriptors and the windows alone
+        long long total = 0, decoded = 0;
+        for (int i = 0; i < n; i++) {
+            const aej_jpegdec_desc &d = descs_host[i];
+            total += d.n_segments;
+            if (!(files[i].shift & kJdBox)) { decoded += d.n_segments; continue; }
+            const long long mcus = (long long)d.mcux * d.mcuy, ri = d.restart_interval ? d.restart_interval : mcus;
+            const long long lo = (long long)files[i].win[1] * d.mcux, hi = (long long)files[i].win[3] * d.mcux;      // the window's MCUs: segment g holds [g * ri, g * ri + ri)
+            decoded += std::min<long long>((hi + ri - 1) / ri, d.n_segments) - lo / ri;
+        }
+        ctx->jd_box_stats[0] = total; ctx->jd_box_stats[1] = decoded; ctx->jd_box_stats[2] = z.blocks;
+    }
     for (int i = 0; i < n; i++) {                            // file by file, scan before image, as the errors were always reported
         const aej_jpegdec_desc &d = descs_host[i];
         AEJ_TRY(jpegdec_scan_offset(ctx, fn, d, i, scans_bytes, scan_offsets_host[i], files[i]));
@@ -383,6 +463,15 @@ extern "C" int aej_jpegdec_batch_mode(aej_ctx *ctx, const aej_jpegdec_desc *desc
 {
     return jpegdec_batch(ctx, __func__, descs_host, n, scales_host, components_host, scans, scans_bytes, scan_offsets_host, out, out_bytes,
                          out_offsets_host, status, workspace, workspace_bytes);
+}
+
+extern "C" int aej_jpegdec_batch_box(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host, const int *components_host,
+                                     const int32_t *boxes_host, const uint8_t *scans, uint64_t scans_bytes, const int64_t *scan_offsets_host,
+                                     uint8_t *out, uint64_t out_bytes, const int64_t *out_offsets_host, int32_t *status, void *workspace,
+                                     uint64_t workspace_bytes)
+{
+    return jpegdec_batch(ctx, __func__, descs_host, n, scales_host, components_host, scans, scans_bytes, scan_offsets_host, out, out_bytes,
+                         out_offsets_host, status, workspace, workspace_bytes, boxes_host);
 }
 
 extern "C" int aej_test_jpegdec_idct_host(const int16_t *coef_host, const uint16_t *qt_host, int size, uint8_t *out_host)
@@ -427,11 +516,15 @@ extern "C" int aej_jpegprog_parse_host_440(const uint8_t *data_host, uint64_t nb
 }
 
 static uint64_t jpegprog_workspace(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n, const int *scales_host,
-                                   const int *components_host = nullptr)
+                                   const int *components_host = nullptr, const int32_t *boxes_host = nullptr)
 {
     JpLayout y;
     std::vector<int> shifts;
-    if (!ctx || !scale_shifts(scales_host, n, shifts, nullptr, components_host) || !jpegprog_layout(frames_host, scans_host, n, y, shifts.data())) return 0;
+    int bad = 0;
+    bool unsupported = false;
+    if (!ctx || !scale_shifts(scales_host, n, shifts, nullptr, components_host)) return 0;
+    if (boxes_host && (!frames_host || !boxes_ok(frames_host, n, boxes_host, shifts, &bad, &unsupported))) return 0;
+    if (!jpegprog_layout(frames_host, scans_host, n, y, shifts.data(), boxes_host)) return 0;
     JpBufs w;
     return jpegprog_carve(nullptr, y, w);
 }
@@ -453,18 +546,28 @@ extern "C" uint64_t aej_jpegprog_workspace_bytes_mode(aej_ctx *ctx, const aej_jp
     return jpegprog_workspace(ctx, frames_host, scans_host, n, scales_host, components_host);
 }
 
+extern "C" uint64_t aej_jpegprog_workspace_bytes_box(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
+                                                     const int *scales_host, const int *components_host, const int32_t *boxes_host)
+{
+    return jpegprog_workspace(ctx, frames_host, scans_host, n, scales_host, components_host, boxes_host);
+}
+
 // levels [0, n_levels) of the entropy stage, then either the reconstruction into `out` or (tests) a copy of the coefficients
 static int jpegprog_run(aej_ctx *ctx, const char *fn, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
                         const int *scales_host, const uint8_t *data, uint64_t data_bytes, const int64_t *data_offsets_host, int n_levels, uint8_t *out, uint64_t out_bytes,
                         const int64_t *out_offsets_host, int16_t *coef_out, uint64_t coef_blocks, int32_t *status, void *workspace,
-                        uint64_t workspace_bytes, const int *components_host = nullptr)
+                        uint64_t workspace_bytes, const int *components_host = nullptr, const int32_t *boxes_host = nullptr)
 {
     if (!ctx) return AEJ_ERR_ARG;
     AEJ_TRY(refuse_in_flight(ctx, fn));
     JpLayout y;
     std::vector<int> shifts;
     AEJ_TRY(check_scales(ctx, fn, scales_host, n, shifts, components_host));
-    if (!jpegprog_layout(frames_host, scans_host, n, y, shifts.data()))
+    if (boxes_host) {                                        // the frames' sizes are read: the checks jpegprog_layout starts with, first
+        if (!frames_host || n < 1) return fail(ctx, AEJ_ERR_ARG, "%s: no files, or descriptors aej_jpegprog_parse_host did not write", fn);
+        AEJ_TRY(check_boxes(ctx, fn, frames_host, n, boxes_host, shifts));
+    }
+    if (!jpegprog_layout(frames_host, scans_host, n, y, shifts.data(), boxes_host))
         return fail(ctx, AEJ_ERR_ARG, "%s: no files, or descriptors aej_jpegprog_parse_host did not write", fn);
     if (!data || !data_offsets_host || !status || !workspace || (!out && !coef_out) || (out && !out_offsets_host))
         return null_buffer(ctx, fn);
@@ -512,6 +615,16 @@ extern "C" int aej_jpegprog_batch_mode(aej_ctx *ctx, const aej_jpegprog_frame *f
     if (!out) return ctx ? null_buffer(ctx, __func__) : AEJ_ERR_ARG;
     return jpegprog_run(ctx, __func__, frames_host, scans_host, n, scales_host, data, data_bytes, data_offsets_host, 1 << 30, out, out_bytes,
                         out_offsets_host, nullptr, 0, status, workspace, workspace_bytes, components_host);
+}
+
+extern "C" int aej_jpegprog_batch_box(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
+                                      const int *scales_host, const int *components_host, const int32_t *boxes_host, const uint8_t *data,
+                                      uint64_t data_bytes, const int64_t *data_offsets_host, uint8_t *out, uint64_t out_bytes,
+                                      const int64_t *out_offsets_host, int32_t *status, void *workspace, uint64_t workspace_bytes)
+{
+    if (!out) return ctx ? null_buffer(ctx, __func__) : AEJ_ERR_ARG;
+    return jpegprog_run(ctx, __func__, frames_host, scans_host, n, scales_host, data, data_bytes, data_offsets_host, 1 << 30, out, out_bytes,
+                        out_offsets_host, nullptr, 0, status, workspace, workspace_bytes, components_host, boxes_host);
 }
 
 extern "C" int aej_test_jpegprog_coefs(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,

@@ -26,6 +26,11 @@
 //                   and below the run (a vertical halo).  A kernel of its own, so that k_jd_scaled compiles as it did without it
 //   k_jd_luma       files that leave as their luma plane alone, [oh][ow] (libjpeg's out_color_space = JCS_GRAYSCALE; a one-component
 //                   file's samples), at scale 1, 2, 4 or 8, in the place of all of the above: k_jd_scaled's plan, luma blocks only
+//   k_jd_box        files of which a box is decoded (box= of the Python call), in the place of k_jd_idct / k_jd_rgb / k_jd_luma: one workgroup
+//                   per tile of the box -- IDCTs of the tile's luma blocks and of its chroma blocks plus a ring of neighbour blocks into
+//                   LDS, then jd_chroma / jd_rgb on the LDS planes, and only the box's pixels stored.  No sample planes.  In a call with
+//                   such a file k_jd_init / k_jd_sync / k_jd_write run as their <true> instantiation: a restart segment of a boxed file
+//                   that holds no MCU of the window's MCU rows is an idle slot to them, and only those rows' coefficients are stored
 // Bounds: every index derives from the host-computed JdFile layout; a file's reads stay inside its scan and its clean stream, decode loops
 // are bounded by their subsequence's bits, and coefficient writes by the segment's block count.
 #include <string.h>
@@ -194,6 +199,8 @@ struct JdSlotPos {
     long long j;                          // subsequence within the segment; -1: idle slot
 };
 
+// kBox: the slots of a boxed file's segment [first_mcu, first_mcu + n_mcu) that does not meet the window's MCU rows are idle
+template <bool kBox>
 __device__ __forceinline__ JdSlotPos jd_slot(const JdFile *files, const aej_jpegdec_desc *descs, int n, const JdSeg *segs, long long t)
 {
     JdSlotPos p;
@@ -206,6 +213,10 @@ __device__ __forceinline__ JdSlotPos jd_slot(const JdFile *files, const aej_jpeg
     p.seg = sg + g;
     p.j = s - p.seg->slot_base;
     if (s >= F.n_slots || p.j < 0 || p.j >= p.seg->n_sub) p.j = -1;
+    if (kBox && (F.shift & kJdBox)) {
+        const long long mcux = descs[p.f].mcux, first = p.seg->first_mcu;
+        if (first >= F.win[3] * mcux || first + p.seg->n_mcu <= F.win[1] * mcux) p.j = -1;
+    }
     return p;
 }
 
@@ -227,13 +238,14 @@ __device__ __forceinline__ unsigned long long jd_decode_slot(const aej_jpegdec_d
     return jd_pack(pos, k, z, rc != kJdRunStop);
 }
 
+template <bool kBox>
 __global__ __launch_bounds__(kJdThreads) void k_jd_init(const JdFile *__restrict__ files, const aej_jpegdec_desc *__restrict__ descs, int n,
                                                         long long n_slots, const JdSeg *__restrict__ segs, const unsigned char *__restrict__ clean,
                                                         JdSlots sl, int S, int *__restrict__ last_change)
 {
     const long long t = (long long)blockIdx.x * kJdThreads + threadIdx.x;
     if (t >= n_slots) return;
-    const JdSlotPos p = jd_slot(files, descs, n, segs, t);
+    const JdSlotPos p = jd_slot<kBox>(files, descs, n, segs, t);
     int out[4] = { 0, 0, 0, 0 };
     unsigned long long entry = jd_pack(0, 0, 0, 1), exit = entry;
     if (p.j >= 0) {
@@ -247,6 +259,7 @@ __global__ __launch_bounds__(kJdThreads) void k_jd_init(const JdFile *__restrict
     sl.first[t] = p.j == 0;
 }
 
+template <bool kBox>
 __global__ __launch_bounds__(kJdThreads) void k_jd_sync(const JdFile *__restrict__ files, const aej_jpegdec_desc *__restrict__ descs, int n,
                                                         long long n_slots, const JdSeg *__restrict__ segs, const unsigned char *__restrict__ clean,
                                                         JdSlots sl, int S, int round, int *__restrict__ last_change)
@@ -254,7 +267,7 @@ __global__ __launch_bounds__(kJdThreads) void k_jd_sync(const JdFile *__restrict
     if (__hip_atomic_load(last_change, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < round - 1) return;      // converged
     const long long t = (long long)blockIdx.x * kJdThreads + threadIdx.x;
     if (t >= n_slots) return;
-    const JdSlotPos p = jd_slot(files, descs, n, segs, t);
+    const JdSlotPos p = jd_slot<kBox>(files, descs, n, segs, t);
     if (p.j <= 0) return;
     const unsigned long long prev = __hip_atomic_load(sl.state + t - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const unsigned long long entry = jd_err(prev) ? jd_guess(*p.seg, p.j, S) : prev;
@@ -309,13 +322,14 @@ __global__ __launch_bounds__(kJdScanThreads) void k_jd_scan_slots(const JdFile *
     }
 }
 
+template <bool kBox>
 __global__ __launch_bounds__(kJdThreads) void k_jd_write(const JdFile *__restrict__ files, const aej_jpegdec_desc *__restrict__ descs, int n,
                                                          long long n_slots, const JdSeg *__restrict__ segs, const unsigned char *__restrict__ clean,
                                                          JdSlots sl, int S, short *__restrict__ coef, int *__restrict__ status)
 {
     const long long t = (long long)blockIdx.x * kJdThreads + threadIdx.x;
     if (t >= n_slots) return;
-    const JdSlotPos p = jd_slot(files, descs, n, segs, t);
+    const JdSlotPos p = jd_slot<kBox>(files, descs, n, segs, t);
     if (p.j < 0) return;
     const JdSeg &sg = *p.seg;
     const aej_jpegdec_desc &d = descs[p.f];
@@ -332,7 +346,23 @@ __global__ __launch_bounds__(kJdThreads) void k_jd_write(const JdFile *__restric
     int pred[3] = { sl.dc_pre[t * 3], sl.dc_pre[t * 3 + 1], sl.dc_pre[t * 3 + 2] };
     long long next = sl.blk_pre[t];
     short *c = coef + (F.blk_base + (long long)sg.first_mcu * d.blocks_per_mcu) * 64;
-    const int rc = jd_run<true>(d, br, pos, k, z, stop, seg_end, nstart, dc, c, next, seg_blocks, pred);
+    int rc;
+    if (kBox && (F.shift & kJdBox)) {                 // blocks [lo, hi) of the segment lie in the stored MCU rows [win[1], win[3]); c: its block 0, were it stored
+        const long long first = (long long)sg.first_mcu * d.blocks_per_mcu, row = (long long)d.mcux * d.blocks_per_mcu;
+        const long long lo = max(0LL, F.win[1] * row - first), hi = min(seg_blocks, F.win[3] * row - first);
+        c = coef + (F.blk_base + first - F.row0 * row) * 64;
+        rc = jd_run<true, true>(d, br, pos, k, z, stop, seg_end, nstart, dc, c, next, hi, pred, lo);
+        const long long cur = z == 0 ? next : next - 1;
+        if (rc == kJdRunDone || cur >= hi) return;   // nothing the window needs is left in this slot
+        if (rc == kJdRunStop) {
+            if (p.j + 1 == sg.n_sub) jd_fail(status, p.f, AEJ_JPEGDEC_TRUNCATED);
+            return;
+        }
+        jd_fail(status, p.f, rc == kJdRunOutOfBits ? AEJ_JPEGDEC_TRUNCATED : rc == kJdRunBadCode ? AEJ_JPEGDEC_BAD_CODE
+                             : rc == kJdRunPast63 ? AEJ_JPEGDEC_RUN_PAST_63 : AEJ_JPEGDEC_BAD_DC);
+        return;
+    }
+    rc = jd_run<true>(d, br, pos, k, z, stop, seg_end, nstart, dc, c, next, seg_blocks, pred);
     const long long cur = z == 0 ? next : next - 1;      // the block being decoded (or the next one) when the loop stopped
     if (rc == kJdRunDone) return;
     if (rc == kJdRunStop) {
@@ -596,6 +626,83 @@ __global__ __launch_bounds__(kJdThreads) void k_jd_luma(const JdFile *__restrict
     }
 }
 
+// Boxed reconstruction, coefficients -> the box's pixels in one kernel, for every layout (4:4:4, 4:2:2, 4:2:0, 4:4:0, one component) and
+// both outputs: RGB (a one-component file: R = G = B), or the luma plane alone where the file's shift carries kJdLuma.  Workgroup
+// `blockIdx.x` is tile g - grpb_base of its file: tiles of kJdBoxW x kJdBoxH pixels -- TX x TY whole MCUs -- in row-major order over the
+// window win = (mx0, my0, mx1, my1), the grid anchored at the window's origin.  The tile's luma blocks go through the 8 x 8 IDCT into
+// sy; its chroma blocks go into scb / scr together with a ring of one MCU on every side that jd_chroma up-samples across (columns
+// when hs == 2 and the file's chroma is more than 2 wide, rows when vs == 2 and the chroma is not replicated), the ring clipped to the
+// window: by jd_box_window every sample a pixel of the box reads lies in the window, so the clip drops nothing that is read.  The
+// pixels of the tile that lie in the box then run jd_box_chroma -- jd_chroma's arithmetic, indexed so that the FILE's sample (row,
+// column) addresses the LDS plane, hence the file's own edge rules -- and jd_rgb, and are stored.  Every return in front of the
+// barrier depends on the workgroup alone.
+// LDS: three planes of kJdBoxH rows x kJdBoxW columns, 12 KiB.  The chroma plane holds (TY + 2) x (TX + 2) blocks at most where a
+// direction is up-sampled -- TX = 8 (80 columns), TY = 2 (32 rows) there -- and TY x TX blocks (32 x 128 at most) where it is not.
+// Bounds: MCU rows [cy0, cy1) and [ty0, ty1) lie in [win[1], win[3]), which the stored rows [row0, row0 + n_blocks / (mcux * bpm))
+// contain, and MCU columns in [win[0], win[2]) <= mcux, so block indices stay inside the file's stored coefficients; LDS rows and
+// columns stay below (cy1 - cy0) * 8 <= kJdBoxH and (cx1 - cx0) * 8 <= kJdBoxW; a store goes to pixel (y, x) with t <= y < b and
+// l <= x < r only, at out_off + ((y - t) * (r - l) + (x - l)) * channels, inside the box's image.
+__global__ __launch_bounds__(kJdThreads) void k_jd_box(const JdFile *__restrict__ files, const aej_jpegdec_desc *__restrict__ descs, int n,
+                                                       const short *__restrict__ coef, unsigned char *__restrict__ out)
+{
+    __shared__ unsigned char sy[kJdBoxH * kJdBoxW], scb[kJdBoxH * kJdBoxW], scr[kJdBoxH * kJdBoxW];
+    int lo = 0, hi = n - 1;                           // the last file whose first workgroup is <= blockIdx.x
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (files[mid].grpb_base <= (long long)blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+    const JdFile &F = files[lo];
+    const aej_jpegdec_desc &d = descs[lo];
+    if (!(F.shift & kJdBox)) return;                  // never: the host gives these workgroups to boxed files alone
+    const bool three = d.ncomp == 3, color = three && !(F.shift & kJdLuma);
+    const int hs = three ? d.hs : 1, vs = three ? d.vs : 1, nl = hs * vs, bpm = d.blocks_per_mcu;
+    if (hs > 2 || vs > 2) return;                     // never: the parsers admit these factors alone
+    const int TX = kJdBoxW / (8 * hs), TY = kJdBoxH / (8 * vs);
+    const int ntx = (F.win[2] - F.win[0] + TX - 1) / TX, g = (int)(blockIdx.x - F.grpb_base);
+    const int tx0 = F.win[0] + (g % ntx) * TX, ty0 = F.win[1] + (g / ntx) * TY;
+    if (ty0 >= F.win[3]) return;                      // never: the host gives a file ntx * nty workgroups
+    const int tx1 = min(tx0 + TX, F.win[2]), ty1 = min(ty0 + TY, F.win[3]);
+    const int wc = (d.width + hs - 1) / hs, hc = (d.height + vs - 1) / vs;
+    const int rx = color && hs == 2 && wc > 2, ry = color && vs == 2 && !(hs == 2 && wc <= 2);      // the ring, in MCUs
+    const int cx0 = max(tx0 - rx, F.win[0]), cx1 = min(tx1 + rx, F.win[2]), cy0 = max(ty0 - ry, F.win[1]), cy1 = min(ty1 + ry, F.win[3]);
+    const int nY = (tx1 - tx0) * (ty1 - ty0) * nl, ncx = cx1 - cx0, nC = color ? 2 * ncx * (cy1 - cy0) : 0;
+    for (int i = threadIdx.x; i < nY + nC; i += kJdThreads) {
+        int mx, my, k, c;
+        unsigned char *dst;
+        if (i < nY) {
+            const int mcu = i / nl, ky = (i % nl) / hs, kx = (i % nl) % hs;
+            my = ty0 + mcu / (tx1 - tx0); mx = tx0 + mcu % (tx1 - tx0); k = i % nl; c = 0;
+            dst = sy + (((my - ty0) * vs + ky) * 8) * kJdBoxW + ((mx - tx0) * hs + kx) * 8;
+        } else {
+            const int j = (i - nY) >> 1;
+            c = 1 + ((i - nY) & 1); k = nl + c - 1;
+            my = cy0 + j / ncx; mx = cx0 + j % ncx;
+            dst = (c == 1 ? scb : scr) + ((my - cy0) * 8) * kJdBoxW + (mx - cx0) * 8;
+        }
+        const short *cf = coef + (F.blk_base + ((long long)(my - F.row0) * d.mcux + mx) * bpm + k) * 64;
+        jd_idct_block(cf, d.qt[c], dst, kJdBoxW);         // inlined, as in k_jd_idct and k_jd_luma<0>: 164 VGPRs, occupancy 3; through jd_idct_block_call
+                                                          // 248, occupancy 2, and k_jd_scaled<1>, which shares that function, no longer compiles as it did
+    }
+    __syncthreads();
+    const int l = F.box[0], t = F.box[1], bw = F.box[2] - l;
+    const int px0 = max(l, tx0 * 8 * hs), px1 = min(F.box[2], tx1 * 8 * hs), py0 = max(t, ty0 * 8 * vs), py1 = min(F.box[3], ty1 * 8 * vs);
+    const int ncols = px1 - px0, npx = ncols > 0 && py1 > py0 ? ncols * (py1 - py0) : 0;
+    unsigned char *img = out + F.out_off;
+    // the file's chroma sample (row, column) is at pcb[row * kJdBoxW + column]: only formed for rows and columns of [cy0, cy1) x [cx0, cx1)
+    const long long coff = (long long)cy0 * 8 * kJdBoxW + cx0 * 8;
+    for (int p = threadIdx.x; p < npx; p += kJdThreads) {
+        const int y = py0 + p / ncols, x = px0 + p % ncols;
+        const int Y = sy[(y - ty0 * 8 * vs) * kJdBoxW + (x - tx0 * 8 * hs)];
+        const long long o = (long long)(y - t) * bw + (x - l);
+        if (!color) {
+            if (F.shift & kJdLuma) img[o] = (unsigned char)Y;
+            else { unsigned char *q = img + o * 3; q[0] = q[1] = q[2] = (unsigned char)Y; }
+            continue;
+        }
+        jd_rgb(Y, jd_box_chroma(scb, coff, hs, vs, wc, hc, y, x), jd_box_chroma(scr, coff, hs, vs, wc, hc, y, x), img + o * 3);
+    }
+}
+
 // ---- host: descriptor checks, layout and launch sequence -----------------------------------------------------------------------------------
 bool jpegdec_descs_ok(const aej_jpegdec_desc *d, int n)
 {
@@ -624,12 +731,22 @@ void jpeg_stream_layout(long long len, int n_segments, int S, JdFile &F, JdBufSi
     z.slots += F.n_slots;
 }
 
-void jpeg_recon_layout(const aej_jpegdec_desc &d, int shift, JdFile &F, JdBufSizes &z)
+void jpeg_recon_layout(const aej_jpegdec_desc &d, int shift, JdFile &F, JdBufSizes &z, const int *box, bool window_coef)
 {
+    const bool luma = (shift & kJdLuma) != 0, boxed = !jpeg_box_whole(d, box);
     F.blk_base = z.blocks;
     F.n_blocks = (long long)d.mcux * d.mcuy * d.blocks_per_mcu;
+    F.row0 = 0;
+    F.grpb_base = z.grpb;
+    if (boxed) {                                      // full size only (the callers refuse a box at another scale)
+        for (int v = 0; v < 4; v++) F.box[v] = box[v];
+        jd_box_window(d.width, d.height, d.hs, d.vs, d.ncomp, luma, box, F.win);
+        if (window_coef) {                            // the window's MCU rows alone, at full width
+            F.row0 = F.win[1];
+            F.n_blocks = (long long)d.mcux * (F.win[3] - F.win[1]) * d.blocks_per_mcu;
+        }
+    }
     z.blocks += F.n_blocks;
-    const bool luma = (shift & kJdLuma) != 0;
     F.shift = shift;
     shift &= kJdLuma - 1;
     F.ow = (d.width + (1 << shift) - 1) >> shift; F.oh = (d.height + (1 << shift) - 1) >> shift;
@@ -637,6 +754,14 @@ void jpeg_recon_layout(const aej_jpegdec_desc &d, int shift, JdFile &F, JdBufSiz
     for (int s = 0; s < 4; s++) F.grpl_base[s] = z.grpl[s];
     F.plane_off = z.planes;
     F.px_base = z.px;
+    if (boxed) {                                      // no sample planes, no pixels of k_jd_rgb's, no workgroups but k_jd_box's
+        const int hs = d.ncomp == 3 ? d.hs : 1, vs = d.ncomp == 3 ? d.vs : 1, TX = kJdBoxW / (8 * hs), TY = kJdBoxH / (8 * vs);
+        F.shift |= kJdBox;
+        F.ow = box[2] - box[0]; F.oh = box[3] - box[1];
+        F.pw0 = F.ph0 = F.pw1 = F.ph1 = 0;
+        z.grpb += (long long)((F.win[2] - F.win[0] + TX - 1) / TX) * ((F.win[3] - F.win[1] + TY - 1) / TY);
+        return;
+    }
     if (luma) {                                       // at every scale: no sample planes, no pixels of k_jd_rgb's, workgroups of k_jd_luma<shift>
         F.pw0 = F.ph0 = F.pw1 = F.ph1 = 0;
         z.grpl[shift] += (long long)d.mcuy * ((d.mcux + kJdRun - 1) / kJdRun);
@@ -654,13 +779,13 @@ void jpeg_recon_layout(const aej_jpegdec_desc &d, int shift, JdFile &F, JdBufSiz
     z.px += (long long)d.width * d.height;
 }
 
-void jpegdec_layout(const aej_jpegdec_desc *descs, int n, int S, std::vector<JdFile> &files, JdBufSizes &z, const int *shifts)
+void jpegdec_layout(const aej_jpegdec_desc *descs, int n, int S, std::vector<JdFile> &files, JdBufSizes &z, const int *shifts, const int *boxes)
 {
     files.assign(n, JdFile{});
     z = JdBufSizes{};
     for (int i = 0; i < n; i++) {
         jpeg_stream_layout(descs[i].scan_length, descs[i].n_segments, S, files[i], z);
-        jpeg_recon_layout(descs[i], shifts ? shifts[i] : 0, files[i], z);
+        jpeg_recon_layout(descs[i], shifts ? shifts[i] : 0, files[i], z, boxes ? boxes + 4 * i : nullptr);
     }
 }
 
@@ -695,8 +820,8 @@ hipError_t launch_jpegdec_begin(hipStream_t st, int n, const JdBufSizes &z, cons
     hipError_t e = hipMemcpyAsync(w.files, blob_host, blob_bytes, hipMemcpyHostToDevice, st);
     if (e != hipSuccess) return e;
     if ((e = launch_jpegdec_unstuff(st, n, z, w, scans, S, status)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_jd_init, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.slots, w.segs, w.clean, w.sl, S,
-                       w.last_change);
+    hipLaunchKernelGGL(z.grpb > 0 ? k_jd_init<true> : k_jd_init<false>, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.slots,
+                       w.segs, w.clean, w.sl, S, w.last_change);
     return hipGetLastError();
 }
 
@@ -718,8 +843,8 @@ hipError_t launch_jpegdec_unstuff(hipStream_t st, int n, const JdBufSizes &z, co
 hipError_t launch_jpegdec_sync(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, int S, int first_round, int rounds)
 {
     for (int r = first_round; r < first_round + rounds; r++)
-        hipLaunchKernelGGL(k_jd_sync, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.slots, w.segs, w.clean, w.sl, S, r,
-                           w.last_change);
+        hipLaunchKernelGGL(z.grpb > 0 ? k_jd_sync<true> : k_jd_sync<false>, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.slots,
+                           w.segs, w.clean, w.sl, S, r, w.last_change);
     return hipGetLastError();
 }
 
@@ -729,8 +854,8 @@ hipError_t launch_jpegdec_write(hipStream_t st, int n, const JdBufSizes &z, cons
     hipError_t e = hipMemsetAsync(w.coef, 0, (size_t)z.blocks * 128, st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_jd_scan_slots, dim3(n), dim3(kJdScanThreads), 0, st, w.files, w.sl);
-    hipLaunchKernelGGL(k_jd_write, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.slots, w.segs, w.clean, w.sl, S, w.coef,
-                       status);
+    hipLaunchKernelGGL(z.grpb > 0 ? k_jd_write<true> : k_jd_write<false>, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.slots,
+                       w.segs, w.clean, w.sl, S, w.coef, status);
     return hipGetLastError();
 }
 
@@ -741,7 +866,7 @@ hipError_t launch_jpegdec_finish(hipStream_t st, int n, const JdBufSizes &z, con
     return launch_jpegdec_recon(st, n, z, w, out);
 }
 
-// the files of a call that decode at scale 2, 4, 8, and the luma-only ones at every scale: one launch per kernel and scale present
+// the files of a call that decode at scale 2, 4, 8, the luma-only ones at every scale and the boxed ones: one launch per kernel and scale present
 // (JdFile::shift and ::grp_base / ::grp440_base / ::grpl_base pick a file's kernel and workgroups; the layout inside the kernel follows
 // the file's sampling factors)
 static hipError_t launch_jpegdec_recon_scaled(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, unsigned char *out)
@@ -756,6 +881,7 @@ static hipError_t launch_jpegdec_recon_scaled(hipStream_t st, int n, const JdBuf
     if (z.grpl[1] > 0) hipLaunchKernelGGL(k_jd_luma<1>, dim3((unsigned)z.grpl[1]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
     if (z.grpl[2] > 0) hipLaunchKernelGGL(k_jd_luma<2>, dim3((unsigned)z.grpl[2]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
     if (z.grpl[3] > 0) hipLaunchKernelGGL(k_jd_luma<3>, dim3((unsigned)z.grpl[3]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
+    if (z.grpb > 0) hipLaunchKernelGGL(k_jd_box, dim3((unsigned)z.grpb), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
     return hipGetLastError();
 }
 

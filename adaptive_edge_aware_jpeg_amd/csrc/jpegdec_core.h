@@ -13,6 +13,8 @@ namespace aej {
 constexpr int kJdChunk = 64;           // bytes per un-stuffing chunk
 constexpr int kJdSyncBatch = 4;        // sync rounds launched between two read-backs of the "changed" word
 constexpr int kJdLuma = 4;             // added to log2 of a file's scale: the luma plane alone, [oh][ow] (JdFile::shift)
+constexpr int kJdBox = 8;              // added to a full-size file's shift: only a box of it is reconstructed (k_jd_box; JdFile::box, ::win)
+constexpr int kJdBoxW = 128, kJdBoxH = 32;      // pixels of one tile of k_jd_box: a whole number of MCUs of every layout
 
 // per-file layout of one aej_jpegdec_batch (host-computed, uploaded with the descriptors)
 struct JdFile {
@@ -32,6 +34,11 @@ struct JdFile {
     long long grp_base[3];             // [shift - 1]: first workgroup of the file in k_jd_scaled<shift>'s grid (kJdRun MCUs of one MCU row each)
     long long grp440_base[3];          // the same in k_jd_scaled_h1v2<shift>'s grid, where the three-component 1 x 2 (4:4:0) files go
     long long grpl_base[4];            // [log2 scale]: the same in k_jd_luma's grid, where the luma-only files of every layout go
+    long long grpb_base;               // first workgroup of the file in k_jd_box's grid (one tile of kJdBoxW x kJdBoxH pixels each)
+    int box[4];                        // a boxed file (shift & kJdBox): left, top, right, bottom in pixels of the image; ow, oh are the box's
+    int win[4];                        // its MCU window mx0, my0, mx1, my1 (jd_box_window): the MCUs whose blocks the box's pixels read
+    int row0;                          // first MCU row whose coefficients are stored (win[1] for a baseline file, 0 for a progressive
+                                       // one): block b of MCU (my, mx) is blk_base + ((my - row0) * mcux + mx) * blocks_per_mcu + b
 };
 
 // one restart segment: written by the un-stuffing scatter (start) and k_jd_segments (the rest)
@@ -101,9 +108,12 @@ enum { kJdRunStop = 0, kJdRunOutOfBits = 1, kJdRunBadCode = 2, kJdRunPast63 = 3,
 // Decode symbols from state (pos, k, z) while pos < stop; no symbol may end past seg_end.  Counts the blocks started and sums their
 // DC differences per component.  kWrite: also stores the coefficients (natural order) of blocks [0, seg_blocks) of the segment into
 // coef (its block 0), with DC predictors pred[], `next` being the index of the next block to start; stops once every block is done.
-template <bool kWrite>
+// kWin (a boxed file): only blocks [win_lo, seg_blocks) of the segment are stored -- seg_blocks being where the file's coefficient window
+// ends in the segment -- while the DC predictions are still tracked through the blocks before win_lo; kJdRunDone once block
+// seg_blocks - 1 is complete.  coef + b * 64 is only formed for win_lo <= b < seg_blocks.
+template <bool kWrite, bool kWin = false>
 AEJ_HD inline int jd_run(const aej_jpegdec_desc &d, JdBits &br, long long &pos, int &k, int &z, long long stop, long long seg_end,
-                         int &nstart, int dc[3], short *coef, long long &next, long long seg_blocks, int pred[3])
+                         int &nstart, int dc[3], short *coef, long long &next, long long seg_blocks, int pred[3], long long win_lo = 0)
 {
     const int bpm = d.blocks_per_mcu;
     while (pos < stop) {
@@ -127,7 +137,7 @@ AEJ_HD inline int jd_run(const aej_jpegdec_desc &d, JdBits &br, long long &pos, 
             dc[c] += v;
             if (kWrite) {
                 pred[c] += v;
-                coef[next * 64] = (short)pred[c];
+                if (!kWin || next >= win_lo) coef[next * 64] = (short)pred[c];
                 next++;
             }
             z = 1;
@@ -138,7 +148,7 @@ AEJ_HD inline int jd_run(const aej_jpegdec_desc &d, JdBits &br, long long &pos, 
                 z += r;
                 if (kWrite) {
                     const long long cur = next - 1;
-                    if (cur >= 0 && cur < seg_blocks) coef[cur * 64 + jd_natural(z)] = (short)v;
+                    if (cur >= (kWin ? win_lo : 0) && cur < seg_blocks) coef[cur * 64 + jd_natural(z)] = (short)v;
                 }
                 z++;
             } else if (r == 15) {
@@ -314,6 +324,64 @@ AEJ_HD inline int jd_chroma(const unsigned char *p, long long stride, int hs, in
     const int cs = 3 * n0[j] + n1[j];
     if ((x & 1) == 0) return j == 0 ? (4 * cs + 8) >> 4 : (3 * cs + 3 * n0[j - 1] + n1[j - 1] + 8) >> 4;
     return j == wc - 1 ? (4 * cs + 7) >> 4 : (3 * cs + 3 * n0[j + 1] + n1[j + 1] + 7) >> 4;
+}
+
+// jd_chroma for k_jd_box: the same arithmetic on a part of the plane held in LDS, kJdBoxW samples a row, where the file's chroma
+// sample (row, column) is p[row * kJdBoxW + column - off] (off: the index the part's first sample would have in the whole plane)
+AEJ_HD inline int jd_box_chroma(const unsigned char *p, long long off, int hs, int vs, int wc, int hc, int y, int x)
+{
+    const long long W = kJdBoxW;
+    if (hs == 1) {
+        if (vs == 1) return p[y * W + x - off];
+        return jd_h1v2(p[(y >> 1) * W + x - off], p[jd_h1v2_far(y, hc) * W + x - off], y);
+    }
+    const int j = x >> 1;
+    if (wc <= 2) return p[(vs == 2 ? y >> 1 : y) * W + j - off];
+    // index arithmetic, not pointers: a row's first samples of the whole plane may lie before the part.  Only the neighbour that
+    // the pixel's parity selects is read: the other one may lie outside the part.
+    const long long r0 = (vs == 2 ? y >> 1 : y) * W - off;
+    if (vs == 1) {
+        if ((x & 1) == 0) return j == 0 ? p[r0] : (3 * p[r0 + j] + p[r0 + j - 1] + 1) >> 2;
+        return j == wc - 1 ? p[r0 + j] : (3 * p[r0 + j] + p[r0 + j + 1] + 2) >> 2;
+    }
+    const long long r1 = jd_h1v2_far(y, hc) * W - off;
+    const int cs = 3 * p[r0 + j] + p[r1 + j];
+    if ((x & 1) == 0) return j == 0 ? (4 * cs + 8) >> 4 : (3 * cs + 3 * p[r0 + j - 1] + p[r1 + j - 1] + 8) >> 4;
+    return j == wc - 1 ? (4 * cs + 7) >> 4 : (3 * cs + 3 * p[r0 + j + 1] + p[r1 + j + 1] + 7) >> 4;
+}
+
+// The MCU window of a box (l, t, r, b; 0 <= l < r <= width, 0 <= t < b <= height): win = mx0, my0, mx1, my1, the bounding rectangle
+// of the MCUs that hold the luma samples of the box's pixels and, unless luma_only or the file has one component, the chroma samples
+// jd_chroma reads for them -- the co-sited one and its neighbour in each up-sampled direction, after jd_chroma's edge rules for the
+// FILE's wc and hc.  The sample indices are monotonic in x and in y, so the two pixels at either end of a range decide.
+AEJ_HD inline void jd_box_window(int width, int height, int hs, int vs, int ncomp, bool luma_only, const int *box, int *win)
+{
+    if (ncomp != 3) hs = vs = 1;
+    const int l = box[0], t = box[1], r = box[2], b = box[3];
+    win[0] = l / (8 * hs); win[2] = (r - 1) / (8 * hs) + 1;      // the luma samples: the pixels themselves
+    win[1] = t / (8 * vs); win[3] = (b - 1) / (8 * vs) + 1;
+    if (ncomp != 3 || luma_only) return;
+    const int wc = (width + hs - 1) / hs, hc = (height + vs - 1) / vs;
+    int j0 = l, j1 = r - 1, i0 = t, i1 = b - 1;       // chroma sample ranges
+    const bool rep = hs == 2 && wc <= 2;              // plain replication: the co-sited sample alone, in both directions
+    if (hs == 2) {
+        j0 = l >> 1; j1 = (r - 1) >> 1;
+        if (!rep) {
+            if ((l & 1) == 0 && j0 > 0) j0--;
+            if (((r - 1) & 1) && j1 < wc - 1) j1++;
+        }
+    }
+    if (vs == 2) {
+        i0 = t >> 1; i1 = (b - 1) >> 1;
+        if (!rep) {
+            if ((t & 1) == 0 && i0 > 0) i0--;
+            if (((b - 1) & 1) && i1 < hc - 1) i1++;
+        }
+    }
+    if (j0 / 8 < win[0]) win[0] = j0 / 8;
+    if (j1 / 8 + 1 > win[2]) win[2] = j1 / 8 + 1;
+    if (i0 / 8 < win[1]) win[1] = i0 / 8;
+    if (i1 / 8 + 1 > win[3]) win[3] = i1 / 8 + 1;
 }
 
 AEJ_HD inline void jd_rgb(int Y, int cb, int cr, unsigned char *o)

@@ -69,7 +69,7 @@ __global__ __launch_bounds__(256) void k_jp_status(const JpScan *__restrict__ sc
 
 // ---- host: validation, layout, launch sequence -----------------------------------------------------------------------------------------
 // Everything the kernels index with is recomputed or checked here; the dependency levels are derived again rather than trusted.
-bool jpegprog_layout(const aej_jpegprog_frame *frames, const aej_jpegprog_scan *scans_in, int n, JpLayout &y, const int *shifts)
+bool jpegprog_layout(const aej_jpegprog_frame *frames, const aej_jpegprog_scan *scans_in, int n, JpLayout &y, const int *shifts, const int *boxes)
 {
     y = JpLayout{};
     if (!frames || !scans_in || n < 1) return false;
@@ -86,7 +86,7 @@ bool jpegprog_layout(const aej_jpegprog_frame *frames, const aej_jpegprog_scan *
         d.width = f.width; d.height = f.height; d.ncomp = f.ncomp; d.hs = f.hs; d.vs = f.vs; d.mcux = f.mcux; d.mcuy = f.mcuy;
         d.blocks_per_mcu = f.blocks_per_mcu; d.n_segments = 1; d.sof = f.sof; d.precision16 = f.precision16;
         memcpy(d.qt, f.qt, sizeof d.qt);
-        jpeg_recon_layout(d, shifts ? shifts[i] : 0, y.ffiles[i], y.fz);
+        jpeg_recon_layout(d, shifts ? shifts[i] : 0, y.ffiles[i], y.fz, boxes ? boxes + 4 * i : nullptr, false);      // a boxed file: all coefficients, k_jd_box
         int cell_level[3][64];
         for (int c = 0; c < 3; c++) for (int k = 0; k < 64; k++) cell_level[c][k] = -1;
         for (int j = 0; j < f.n_scans; j++) {

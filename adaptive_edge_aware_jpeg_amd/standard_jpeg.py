@@ -358,9 +358,9 @@ def _stage(ctx, views, pieces):
     return dev, off
 
 
-def _decode_baseline(ctx, idx, parsed, views, out, out_off, scales=None, comps=None):
-    """aej_jpegdec_batch (scales None), aej_jpegdec_batch_scaled or (comps: 3 or 1 per file) aej_jpegdec_batch_mode over the files idx
-    -> their status words (device int32)"""
+def _decode_baseline(ctx, idx, parsed, views, out, out_off, scales=None, comps=None, boxes=None):
+    """aej_jpegdec_batch (scales None), aej_jpegdec_batch_scaled, (comps: 3 or 1 per file) aej_jpegdec_batch_mode or (boxes: int32
+    [n, 4]) aej_jpegdec_batch_box over the files idx -> their status words (device int32)"""
     from ._lib import JpegDecDesc
     t, lib, n = ctx.torch, ctx.lib, len(idx)
     descs = (JpegDecDesc * n)(*[parsed[i] for i in idx])
@@ -375,6 +375,10 @@ def _decode_baseline(ctx, idx, parsed, views, out, out_off, scales=None, comps=N
         cc = np.ascontiguousarray(comps[idx], np.int32)
         how = (sc[0].ctypes.data if sc else None, cc.ctypes.data)
         nbytes, batch = lib.aej_jpegdec_workspace_bytes_mode, lib.aej_jpegdec_batch_mode
+    if boxes is not None:
+        bb = np.ascontiguousarray(boxes[idx], np.int32)
+        how = (sc[0].ctypes.data if sc else None, cc.ctypes.data if comps is not None else None, bb.ctypes.data)
+        nbytes, batch = lib.aej_jpegdec_workspace_bytes_box, lib.aej_jpegdec_batch_box
     nws = int(nbytes(ctx.handle, ctypes.addressof(descs), n, *how))
     if nws == 0:
         raise ValueError("descriptors the library refuses")
@@ -385,9 +389,9 @@ def _decode_baseline(ctx, idx, parsed, views, out, out_off, scales=None, comps=N
     return status
 
 
-def _decode_progressive(ctx, idx, parsed, views, out, out_off, scales=None, comps=None):
-    """aej_jpegprog_batch (scales None), aej_jpegprog_batch_scaled or (comps) aej_jpegprog_batch_mode over the files idx -> their status
-    words (device int32)"""
+def _decode_progressive(ctx, idx, parsed, views, out, out_off, scales=None, comps=None, boxes=None):
+    """aej_jpegprog_batch (scales None), aej_jpegprog_batch_scaled, (comps) aej_jpegprog_batch_mode or (boxes) aej_jpegprog_batch_box
+    over the files idx -> their status words (device int32)"""
     from ._lib import JpegProgFrame, JpegProgScan
     t, lib, n = ctx.torch, ctx.lib, len(idx)
     frames = (JpegProgFrame * n)(*[parsed[i][0] for i in idx])
@@ -404,6 +408,10 @@ def _decode_progressive(ctx, idx, parsed, views, out, out_off, scales=None, comp
         cc = np.ascontiguousarray(comps[idx], np.int32)
         how = (sc[0].ctypes.data if sc else None, cc.ctypes.data)
         nbytes, batch = lib.aej_jpegprog_workspace_bytes_mode, lib.aej_jpegprog_batch_mode
+    if boxes is not None:
+        bb = np.ascontiguousarray(boxes[idx], np.int32)
+        how = (sc[0].ctypes.data if sc else None, cc.ctypes.data if comps is not None else None, bb.ctypes.data)
+        nbytes, batch = lib.aej_jpegprog_workspace_bytes_box, lib.aej_jpegprog_batch_box
     nws = int(nbytes(ctx.handle, ctypes.addressof(frames), ctypes.addressof(scans), n, *how))
     if nws == 0:
         raise ValueError("descriptors the library refuses")
@@ -451,6 +459,87 @@ def _check_modes(mode, n, what="file"):
     return [one(m, f"{what} {i}") for i, m in enumerate(mode)]
 
 
+def _check_decode_box(b, who):
+    """one box -> (left, top, right, bottom) of ints; TypeError for anything that is not a list / tuple of four integers"""
+    if not isinstance(b, (list, tuple)) or len(b) != 4:
+        raise TypeError(f"{who}: box {b!r}: (left, top, right, bottom) required")
+    for v in b:
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"{who}: box {tuple(b)!r}: four integers required")
+    return tuple(int(v) for v in b)
+
+
+def _check_boxes(box, n):
+    """box= of standard_jpeg_decode_many -> None, or a list of n of None / (left, top, right, bottom).  One box for every file, or a
+    list / tuple with one entry per file, each a box or None (told apart by an entry that is None, a list or a tuple).  TypeError for a
+    value or an entry that is not a box of four integers (a bool, a float, a tuple of another length); ValueError for a sequence of
+    another length than files.  Whether a box fits its image is checked once the header is parsed (_box_in_image)."""
+    if box is None:
+        return None
+    if not isinstance(box, (list, tuple)):
+        raise TypeError(f"box {box!r}: (left, top, right, bottom), or a list of one such tuple or None per file, required")
+    if len(box) == 0 or any(b is None or isinstance(b, (list, tuple)) for b in box):
+        if len(box) != n:
+            raise ValueError(f"box: {len(box)} entries for {n} files")
+        return [None if b is None else _check_decode_box(b, f"file {i}") for i, b in enumerate(box)]
+    return [_check_decode_box(box, "every file")] * n
+
+
+def _box_in_image(box, width, height, index):
+    """ValueError naming the file unless 0 <= left < right <= width and 0 <= top < bottom <= height"""
+    l, t, r, b = box
+    if not (0 <= l < r <= width and 0 <= t < b <= height):
+        raise ValueError(f"file {index}: box {box!r} is empty, inverted or leaves the {width} x {height} image (nothing is padded)")
+
+
+def decode_box_window(width: int, height: int, hs: int, vs: int, ncomp: int, box, luma: bool = False):
+    """The MCU window of a boxed decode (host only): (mx0, my0, mx1, my1), the half-open rectangle of MCUs -- 8 hs x 8 vs pixels each,
+    8 x 8 for a one-component file -- whose blocks the pixels of box = (left, top, right, bottom) read in a width x height file with
+    luma sampling factors hs x vs (1 x 1, 2 x 1, 2 x 2, 1 x 2) and ncomp components.  That is the MCUs of the luma samples of those
+    pixels and, per chroma component of a three-component file, of the samples libjpeg's up-sampling reads for them: the co-sited one
+    plus one neighbour in each up-sampled direction (h2v2: the far row and columns j +- 1; h2v1: columns; h1v2: rows), after the edge
+    rules of the FILE's chroma plane (no neighbour past its first or last sample; a plane at most 2 wide is replicated: no neighbour
+    at all).  The bounding rectangle is exact.  luma=True: the window of a mode "L" decode, the luma samples' alone.  The C twin is
+    aej_jpegdec_box_window_host.  ValueError for a box that is empty or leaves the image, TypeError for one that is not four integers."""
+    box = _check_decode_box(box, "decode_box_window")
+    width, height, hs, vs, ncomp = int(width), int(height), int(hs), int(vs), int(ncomp)
+    if width < 1 or height < 1 or ncomp not in (1, 3) or (ncomp == 3 and (hs not in (1, 2) or vs not in (1, 2))):
+        raise ValueError(f"decode_box_window: a {width} x {height} file of {ncomp} components sampled {hs} x {vs}")
+    _box_in_image(box, width, height, 0)
+    if ncomp == 1:
+        hs = vs = 1
+    l, t, r, b = box
+    mx0, mx1, my0, my1 = l // (8 * hs), (r - 1) // (8 * hs) + 1, t // (8 * vs), (b - 1) // (8 * vs) + 1
+    if ncomp == 3 and not luma:
+        wc, hc = -(-width // hs), -(-height // vs)
+        fancy = not (hs == 2 and wc <= 2)
+
+        def span(a0, a1, f, nc):                     # first and last chroma sample read for luma samples a0 .. a1 of one axis
+            if f == 1:
+                return a0, a1
+            j0, j1 = a0 >> 1, a1 >> 1
+            if fancy:
+                j0 -= 1 if a0 % 2 == 0 and j0 > 0 else 0
+                j1 += 1 if a1 % 2 == 1 and j1 < nc - 1 else 0
+            return j0, j1
+
+        j0, j1 = span(l, r - 1, hs, wc)
+        i0, i1 = span(t, b - 1, vs, hc)
+        mx0, mx1, my0, my1 = min(mx0, j0 // 8), max(mx1, j1 // 8 + 1), min(my0, i0 // 8), max(my1, i1 // 8 + 1)
+    return mx0, my0, mx1, my1
+
+
+def decode_box_stats(device: int = 0):
+    """(segments_total, segments_decoded, coef_blocks) of the last standard_jpeg_decode_many with a box on this device's current
+    stream that had baseline files (aej_jpegdec_box_stats), summed over those files: their restart segments, the ones that were
+    Huffman-decoded (those holding an MCU of the window's MCU rows; every one of a file without a box) and the coefficient blocks
+    stored.  Computed on the host from the headers and the windows: nothing is read back."""
+    ctx = get_context(device)
+    out = (ctypes.c_int64 * 3)()
+    ctx.check(ctx.lib.aej_jpegdec_box_stats(ctx.handle, ctypes.addressof(out)))
+    return int(out[0]), int(out[1]), int(out[2])
+
+
 def _views(out, out_off, shapes, comps):
     """the images of a packed decode: [h, w, 3], or [h, w] where comps says 1"""
     return [out[int(o):int(o) + h * w * c].view(*((h, w, 3) if c == 3 else (h, w))) for o, (h, w), c in zip(out_off, shapes, comps)]
@@ -467,7 +556,7 @@ def draft_scale(width: int, height: int, size) -> int:
     return next((s for s in (8, 4, 2) if s <= ratio), 1)
 
 
-def standard_jpeg_decode_many(files, device: int = 0, progressive: bool = False, scale=1, layout_440: bool = False, mode="RGB") -> list:
+def standard_jpeg_decode_many(files, device: int = 0, progressive: bool = False, scale=1, layout_440: bool = False, mode="RGB", box=None) -> list:
     """Decode JPEG files on the device: -> list of uint8 [H_i, W_i, 3] tensors (views into one packed allocation), in input
     order, on the context of the current stream; element i equals ``np.asarray(Image.open(io.BytesIO(files[i])).convert("RGB"))``.
     scale: 1, 2, 4 or 8, or a sequence of one such value per file (ValueError naming the value otherwise; a bool is refused): file i
@@ -493,26 +582,47 @@ def standard_jpeg_decode_many(files, device: int = 0, progressive: bool = False,
     -- [h, w] for a one-component file, [h, w, 3] for a colour one.  The images stay views into one packed allocation (h * w bytes of an
     L image, h * w * 3 of an RGB one).  A string that is not one of the three, or a sequence of another length than files, raises
     ValueError (naming the file of a bad entry); a value that is neither a string nor a list / tuple TypeError -- before any device
-    work, like every keyword here."""
+    work, like every keyword here.
+    box: None (the default: the call as it always was -- the same library entries, the same launches), one (left, top, right, bottom)
+    for every file, or a list with one entry per file, each such a tuple or None (the whole image).  Pillow's crop() coordinates, in
+    pixels of the decoded image, 0 <= left < right <= W_i and 0 <= top < bottom <= H_i.  Element i is then uint8 [bottom - top,
+    right - left, 3] -- [bottom - top, right - left] where mode makes it one-channel -- and equals ``np.asarray(Image.open(f)
+    .convert("RGB").crop(box))`` (for "L": the ``draft("L", None)`` image cropped), i.e. ``[top:bottom, left:right]`` of what the call
+    returns without box=: a box edge inside the picture is filtered with its real neighbours from outside the box.  Only what the box
+    needs is done (csrc/jpegdec.hip, ``k_jd_box``; ``decode_box_window`` is the MCU window, ``decode_box_stats`` what the last call
+    skipped): of a baseline file only the restart segments that hold MCUs of the window's MCU rows are Huffman-decoded and only those
+    rows' coefficients are stored; one kernel reconstructs the box's tiles from the coefficients, with no sample planes.  A progressive
+    file keeps its whole entropy decode and gets the boxed reconstruction.  Works with progressive=True, layout_440=True and every
+    mode; boxed and unboxed files, every kind and layout mix in one call.  Refusals, before any device work: a box that is empty,
+    inverted or leaves the image ValueError naming the file (Pillow would pad with black; that is not built); a bool, a float or a
+    tuple of another length TypeError; a list of another length than files ValueError; a box on a file whose scale is not 1
+    NotImplementedError ("a box at scale 2, 4 or 8 is not built").  ERRORS IN SKIPPED DATA: a boxed decode reports scan errors only
+    for the data it reads -- a malformed restart segment that the box does not need is not noticed, where the call without box=
+    raises."""
     files = list(files)
     if not files:
         raise ValueError("standard_jpeg_decode_many needs at least one file")
     modes = _check_modes(mode, len(files))
     _, out, out_off, shapes, comps = _decode_files(files, device, progressive, _check_scales(scale, len(files)),
-                                                   layout_440=_check_bool("layout_440", layout_440), modes=modes)
+                                                   layout_440=_check_bool("layout_440", layout_440), modes=modes,
+                                                   boxes=_check_boxes(box, len(files)))
     return _views(out, out_off, shapes, comps)
 
 
-def _decode_files(files, device, progressive, scales, choose=None, layout_440=False, modes=None):
+def _decode_files(files, device, progressive, scales, choose=None, layout_440=False, modes=None, boxes=None):
     """The decode of standard_jpeg_decode_many -> (context, the packed uint8 output, int64 offsets, [(h, w)], [3 or 1: the channels of
     each image]).  scales: int32 [n]; with `choose`, file i's scale is choose(i, width, height) instead, asked once its header
-    is parsed and before any device work.  modes: _check_modes' list (None: every file "RGB")."""
+    is parsed and before any device work.  modes: _check_modes' list (None: every file "RGB").  boxes: _check_boxes' list (None: no
+    file has one); the shape of a boxed file is its box's."""
     n = len(files)
     parsed, views, base_idx, prog_idx, shapes, comps = [], [], [], [], [], []
+    box_arr, prog_set = None, set()
     for i, is_prog, d, mv in _parse_sources(files, progressive, layout_440=layout_440):
         parsed.append(d)
         views.append(mv)
         (prog_idx if is_prog else base_idx).append(i)
+        if is_prog:
+            prog_set.add(i)
         frame = d[0] if is_prog else d
         m = "RGB" if modes is None else modes[i]
         comps.append(1 if m == "L" or (m == "auto" and frame.ncomp == 1) else 3)
@@ -520,6 +630,20 @@ def _decode_files(files, device, progressive, scales, choose=None, layout_440=Fa
             scales[i] = choose(i, frame.width, frame.height)
         s = int(scales[i])
         shapes.append((-(-frame.height // s), -(-frame.width // s)))
+        if boxes is not None and boxes[i] is not None:
+            _box_in_image(boxes[i], frame.width, frame.height, i)
+            if boxes[i] == (0, 0, frame.width, frame.height):
+                continue                                 # the whole image: no box
+            if s != 1:
+                raise NotImplementedError(f"file {i}: a box at scale 2, 4 or 8 is not built")
+            box_arr = np.zeros((n, 4), np.int32) if box_arr is None else box_arr
+            box_arr[i] = boxes[i]
+            shapes[-1] = (boxes[i][3] - boxes[i][1], boxes[i][2] - boxes[i][0])
+    if box_arr is not None:                          # the entries with boxes: every other file's is its whole image
+        for i in range(n):
+            if not box_arr[i].any():
+                frame = parsed[i][0] if i in prog_set else parsed[i]
+                box_arr[i] = (0, 0, frame.width, frame.height)
     if (scales == 1).all():
         scales = None                                # the unscaled entries, as before
     comps_arr = None if all(c == 3 for c in comps) else np.array(comps, np.int32)      # every image RGB: the entries without components, as before
@@ -534,7 +658,8 @@ def _decode_files(files, device, progressive, scales, choose=None, layout_440=Fa
     st = np.zeros(n, np.int64)
     for idx, run in ((base_idx, _decode_baseline), (prog_idx, _decode_progressive)):
         if idx:
-            st[idx] = run(ctx, idx, parsed, views, out, out_off, scales, comps_arr).cpu().numpy()      # the one read-back of the per-file status words
+            extra = () if box_arr is None else (box_arr,)      # no box: the entries without boxes, as before
+            st[idx] = run(ctx, idx, parsed, views, out, out_off, scales, comps_arr, *extra).cpu().numpy()      # the one read-back of the per-file status words
     _raise_status((int(i), int(st[i])) for i in np.flatnonzero(st))
     return ctx, out, out_off, shapes, comps
 

@@ -461,7 +461,25 @@ AEJ_API int aej_jfif_recon_batch_prog(aej_ctx *ctx, int batch, int H, int W, int
  *   the reconstruction of a luma file is one kernel at every scale, full size included -- the IDCTs of its luma blocks into LDS, then
  *   whole-dword row stores -- that never reads a chroma block, so such a file adds no sample planes to the workspace: that of a call
  *   never exceeds the same call's with every count 3.  With every count 3 both calls are the _scaled ones byte for byte, launches
- *   included.  (Additions to ABI 3: no existing signature, struct or behaviour changed.) */
+ *   included.  (Additions to ABI 3: no existing signature, struct or behaviour changed.)
+ * aej_jpegdec_batch_box / aej_jpegdec_workspace_bytes_box: the _mode calls with boxes_host [n][4] as well -- left, top, right, bottom in
+ *   pixels of the full-size image, Pillow's crop() box, 0 <= left < right <= width and 0 <= top < bottom <= height (anything else:
+ *   AEJ_ERR_ARG naming the file, 0 bytes; nothing is padded).  Image i is then [bottom - top][right - left][components]: exactly the
+ *   pixels [top, bottom) x [left, right) of what the _mode call gives.  A NULL boxes_host, or a box that is the whole image, is the
+ *   _mode call for that file: the same layout, the same launches.  A box on a file whose scale is not 1 is AEJ_ERR_UNSUPPORTED ("a box
+ *   at scale 2, 4 or 8 is not built").  Both refusals come before any device work and leave out untouched.  A boxed file is
+ *   reconstructed by one kernel, coefficients to the box's pixels, and has no sample planes; of a boxed BASELINE file only the
+ *   coefficients of the MCU rows of its window are stored, and a restart segment that holds no MCU of those rows is not Huffman-decoded
+ *   (un-stuffing, segment finding and the restart-marker count check still cover the whole scan): status reports errors of the data that
+ *   is read alone, so a malformed segment the box does not need goes unnoticed.
+ * aej_jpegdec_box_window_host: HOST only.  window4_out_host gets mx0, my0, mx1, my1: the half-open rectangle of MCUs whose blocks the
+ *   pixels of box4_host (left, top, right, bottom) of an RGB decode read -- the luma samples of those pixels and, per chroma component,
+ *   the co-sited sample plus the one neighbour in each direction that libjpeg's fancy up-sampling filters across, after the edge rules
+ *   of the FILE's chroma width and height (a plane at most 2 samples wide is replicated).  AEJ_ERR_ARG for a box outside the image.
+ *   (A luma decode reads the luma samples' MCUs alone.)  aej_jpegprog_box_window_host: the same from a progressive file's frame.
+ * aej_jpegdec_box_stats: out3_host gets, for the last aej_jpegdec_batch_box of the context in which a file had a box: the restart
+ *   segments of its files, those that were Huffman-decoded, and the coefficient blocks stored -- computed on the host from the
+ *   descriptors and the windows, nothing is read back.  (Additions to ABI 3: no existing signature, struct or behaviour changed.) */
 enum {
     AEJ_JPEGDEC_OK = 0, AEJ_JPEGDEC_TRUNCATED = 1 /* the scan ends before the last MCU */, AEJ_JPEGDEC_BAD_CODE = 2 /* not in the table */,
     AEJ_JPEGDEC_RUN_PAST_63 = 3 /* an AC run beyond the block */, AEJ_JPEGDEC_BAD_DC = 4 /* DC category above 11 */,
@@ -504,6 +522,14 @@ AEJ_API uint64_t aej_jpegdec_workspace_bytes_mode(aej_ctx *ctx, const aej_jpegde
 AEJ_API int aej_jpegdec_batch_mode(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host, const int *components_host,
                                    const uint8_t *scans, uint64_t scans_bytes, const int64_t *scan_offsets_host, uint8_t *out, uint64_t out_bytes,
                                    const int64_t *out_offsets_host, int32_t *status, void *workspace, uint64_t workspace_bytes);
+AEJ_API uint64_t aej_jpegdec_workspace_bytes_box(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host,
+                                                 const int *components_host, const int32_t *boxes_host);
+AEJ_API int aej_jpegdec_batch_box(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host, const int *components_host,
+                                  const int32_t *boxes_host, const uint8_t *scans, uint64_t scans_bytes, const int64_t *scan_offsets_host,
+                                  uint8_t *out, uint64_t out_bytes, const int64_t *out_offsets_host, int32_t *status, void *workspace,
+                                  uint64_t workspace_bytes);
+AEJ_API int aej_jpegdec_box_window_host(const aej_jpegdec_desc *desc_host, const int32_t *box4_host, int32_t *window4_out_host);
+AEJ_API int aej_jpegdec_box_stats(aej_ctx *ctx, int64_t *out3_host);
 
 /* ---- progressive JPEG files decoded on the device (standard_jpeg_decode_many(..., progressive=True)) ----------------------------------
  * SOF2 files with Huffman coding, under the frame rules of aej_jpegdec_parse_host (8-bit, 1 or 3 components, 4:4:4 / 4:2:2 / 4:2:0 /
@@ -531,6 +557,10 @@ AEJ_API int aej_jpegdec_batch_mode(aej_ctx *ctx, const aej_jpegdec_desc *descs_h
  * aej_jpegprog_batch_scaled / aej_jpegprog_workspace_bytes_scaled: with scales_host [n], as aej_jpegdec_batch_scaled.
  * aej_jpegprog_batch_mode / aej_jpegprog_workspace_bytes_mode: with scales_host [n] and components_host [n] (either may be NULL), as
  *   aej_jpegdec_batch_mode: the progressive decoder finishes with the baseline path's reconstruction, the luma kernel included.
+ *   (Additions to ABI 3: no existing signature, struct or behaviour changed.)
+ * aej_jpegprog_batch_box / aej_jpegprog_workspace_bytes_box: with boxes_host [n][4] as well, as aej_jpegdec_batch_box (the same
+ *   refusals): a boxed file finishes in the baseline path's boxed reconstruction kernel and has no sample planes.  Its entropy decode
+ *   and its coefficients stay whole: every scan is decoded, so every scan's errors are reported.
  *   (Additions to ABI 3: no existing signature, struct or behaviour changed.) */
 typedef struct aej_jpegprog_frame {
     int32_t width, height;
@@ -573,6 +603,13 @@ AEJ_API int aej_jpegprog_batch_mode(aej_ctx *ctx, const aej_jpegprog_frame *fram
                                     const int *scales_host, const int *components_host, const uint8_t *data, uint64_t data_bytes,
                                     const int64_t *data_offsets_host, uint8_t *out, uint64_t out_bytes, const int64_t *out_offsets_host,
                                     int32_t *status, void *workspace, uint64_t workspace_bytes);
+AEJ_API uint64_t aej_jpegprog_workspace_bytes_box(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
+                                                  const int *scales_host, const int *components_host, const int32_t *boxes_host);
+AEJ_API int aej_jpegprog_batch_box(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
+                                   const int *scales_host, const int *components_host, const int32_t *boxes_host, const uint8_t *data,
+                                   uint64_t data_bytes, const int64_t *data_offsets_host, uint8_t *out, uint64_t out_bytes,
+                                   const int64_t *out_offsets_host, int32_t *status, void *workspace, uint64_t workspace_bytes);
+AEJ_API int aej_jpegprog_box_window_host(const aej_jpegprog_frame *frame_host, const int32_t *box4_host, int32_t *window4_out_host);
 
 /* ---- images of mixed sizes and qualities encoded in one call (standard_jpeg_encode_many) -------------------------------------------------
  * The files of aej_jfif_encode_batch_opt / _prog -- Pillow's Image.save(buf, "JPEG", quality, subsampling, optimize, progressive), byte
