@@ -151,6 +151,16 @@ class JpegDecDesc(ctypes.Structure):
                 ("scan_offset", ctypes.c_int64), ("scan_length", ctypes.c_int64)]
 
 
+class JpegAdobe(ctypes.Structure):
+    """aej_jpeg_adobe (include/aej.h): the colour model of a file (JPEG_COLOURS) and, of a four-component one, component 3's sampling
+    factors and tables -- what the _adobe parsers write beside the descriptor"""
+    _fields_ = [("colour", ctypes.c_int32), ("h3", ctypes.c_int32), ("v3", ctypes.c_int32), ("tq3", ctypes.c_int32),
+                ("qt3", ctypes.c_uint16 * 64), ("dc3", JpegDecHuff), ("ac3", JpegDecHuff)]
+
+
+JPEG_COLOURS = ("YCbCr", "RGB", "CMYK", "YCCK")      # AEJ_JPEG_*: aej_jpeg_adobe.colour ("YCbCr" also for a one-component file)
+
+
 class JpegProgFrame(ctypes.Structure):
     """aej_jpegprog_frame (include/aej.h): the frame of a progressive file"""
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("ncomp", ctypes.c_int32), ("hs", ctypes.c_int32), ("vs", ctypes.c_int32),
@@ -264,6 +274,12 @@ SIGNATURES = {
     "aej_jpegdec_box_stats": (_I, [_P, _P]),
     "aej_jpegprog_workspace_bytes_box": (_U64, [_P, _P, _P, _I, _P, _P, _P]),
     "aej_jpegprog_batch_box": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _U64, _P, _P, _U64, _P, _P, _P, _U64]),
+    "aej_jpegdec_parse_host_adobe": (_I, [_P, _U64, _P, _P, _P, _I, _I]),
+    "aej_jpegprog_parse_host_adobe": (_I, [_P, _U64, _P, _P, _I, _P, _P, _I, _I]),
+    "aej_jpegdec_workspace_bytes_adobe": (_U64, [_P, _P, _I, _P, _P, _P, _P]),
+    "aej_jpegdec_batch_adobe": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _U64, _P, _P, _U64, _P, _P, _P, _U64]),
+    "aej_jpegprog_workspace_bytes_adobe": (_U64, [_P, _P, _P, _I, _P, _P, _P, _P]),
+    "aej_jpegprog_batch_adobe": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _U64, _P, _P, _U64, _P, _P, _P, _U64]),
     "aej_jpegprog_parse_host": (_I, [_P, _U64, _P, _P, _I, _P, _I]),
     "aej_jpegprog_workspace_bytes": (_U64, [_P, _P, _P, _I]),
     "aej_jpegprog_batch": (_I, [_P, _P, _P, _I, _P, _U64, _P, _P, _U64, _P, _P, _P, _U64]),
@@ -315,6 +331,7 @@ SIGNATURES = {
     "aej_resample_batch_ch": (_I, [_P, _P, _I, _P, _P, _U64, _P, _U64, _P, _U64]),
     "aej_test_jpegprog_coefs": (_I, [_P, _P, _P, _I, _P, _U64, _P, _I, _P, _U64, _P, _P, _U64]),             # include/aej_testing.h (tests only)
     "aej_test_jpegprog_coefs_host": (_I, [_P, _P, _P, _U64, _I, _P, _U64]),                                 # include/aej_testing.h (tests only)
+    "aej_test_jpeg_adobe_pixels_host": (_I, [_P, _I64, _I, _I, _P]),                                        # include/aej_testing.h (tests only)
     "aej_test_jpegdec_idct_host": (_I, [_P, _P, _I, _P]),                                                   # include/aej_testing.h (tests only)
 }
 

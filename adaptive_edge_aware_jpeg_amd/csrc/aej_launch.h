@@ -329,15 +329,18 @@ int jfifprog_scan_device(hipStream_t st, const short *coefs_host, long long n, i
 #include "jpegdec_core.h"
 
 namespace aej {
-struct JdBufSizes { long long chunks, segs, slots, blocks, clean, planes, px, grp[3], grp440[3], grpl[4], grpb; };      // totals over the files of one call (grp, grp440, grpl, grpb: JdFile::grp_base, ::grp440_base, ::grpl_base, ::grpb_base)
+struct JdBufSizes { long long chunks, segs, slots, blocks, clean, planes, px, grp[3], grp440[3], grpl[4], grpb, grpa, uniform; };      // totals over the files of one call (grp, grp440, grpl, grpb: JdFile::grp_base, ::grp440_base, ::grpl_base, ::grpb_base; grpa: ::grpa_base, the workgroups of k_jd_adobe -- non-zero exactly when the call has a four-component or RGB-coded file; uniform: the baseline ones among them with JdFile::uniform)
 struct JdBufs {
     JdFile *files; aej_jpegdec_desc *descs; int *last_change;      // one upload: files, descriptors, the "last round that changed" word
+    aej_jpeg_adobe *adobe;                                         // and, in a call with z.grpa > 0 alone, the files' aej_jpeg_adobe behind that word (else NULL)
     int *cnt; long long *pre, *clean_len; JdSeg *segs; unsigned char *clean; JdSlots sl; short *coef; unsigned char *planes;
 };
 struct JdHuffSrc { bool defined = false; unsigned char bits[17] = {}; unsigned char vals[256] = {}; int count = 0; };      // one DHT table
 bool jd_build_huff(const JdHuffSrc &s, aej_jpegdec_huff &h);                                                              // jpegparse.hip
 // allow440 (both parsers): luma sampled 1 x 2 over 1 x 1 chroma is accepted beside 4:4:4, 4:2:2 and 4:2:0
-int jpegdec_parse(const unsigned char *data, unsigned long long n, aej_jpegdec_desc &d, std::string &msg, bool allow440 = false);      // jpegparse.hip
+// adobe (both parsers; not NULL: the _adobe entries): four-component and RGB-coded files are accepted too, *adobe says what the file is
+int jpegdec_parse(const unsigned char *data, unsigned long long n, aej_jpegdec_desc &d, std::string &msg, bool allow440 = false,
+                  aej_jpeg_adobe *adobe = nullptr);                                                                    // jpegparse.hip
 // did one of the parsers write this frame?  D: aej_jpegdec_desc or aej_jpegprog_frame -- what the layouts below size buffers from
 template <class D>
 bool jpeg_frame_ok(const D &e)
@@ -348,7 +351,21 @@ bool jpeg_frame_ok(const D &e)
     if (e.mcux != (e.width + 8 * e.hs - 1) / (8 * e.hs) || e.mcuy != (e.height + 8 * e.vs - 1) / (8 * e.vs)) return false;
     return e.blocks_per_mcu == (e.ncomp == 1 ? 1 : e.hs * e.vs + 2);
 }
-bool jpegdec_descs_ok(const aej_jpegdec_desc *descs, int n);      // n >= 1 descriptors aej_jpegdec_parse_host wrote
+inline bool jpeg_adobe_new(const aej_jpeg_adobe *x) { return x && x->colour != AEJ_JPEG_YCBCR; }      // a file only the _adobe entries take
+// the same with the file's aej_jpeg_adobe (NULL: none): a four-component frame is one the _adobe parsers wrote
+template <class D>
+bool jpeg_frame_ok(const D &e, const aej_jpeg_adobe *x)
+{
+    if (!x || x->colour == AEJ_JPEG_YCBCR) return jpeg_frame_ok(e);
+    if (x->colour == AEJ_JPEG_RGB) return e.ncomp == 3 && jpeg_frame_ok(e);
+    if ((x->colour != AEJ_JPEG_CMYK && x->colour != AEJ_JPEG_YCCK) || e.ncomp != 4) return false;
+    if (!((e.hs == 1 || e.hs == 2) && (e.vs == 1 || e.vs == 2))) return false;
+    if (!((x->h3 == e.hs && x->v3 == e.vs) || (x->h3 == 1 && x->v3 == 1))) return false;
+    if (e.width < 1 || e.height < 1 || e.width > 65535 || e.height > 65535) return false;
+    if (e.mcux != (e.width + 8 * e.hs - 1) / (8 * e.hs) || e.mcuy != (e.height + 8 * e.vs - 1) / (8 * e.vs)) return false;
+    return e.blocks_per_mcu == e.hs * e.vs + 2 + x->h3 * x->v3;
+}
+bool jpegdec_descs_ok(const aej_jpegdec_desc *descs, int n, const aej_jpeg_adobe *adobe = nullptr);      // n >= 1 descriptors aej_jpegdec_parse_host wrote (adobe: [n] or NULL)
 // one un-stuffing stream of len stuffed bytes and n_segments restart segments, subsequences of S bits: F's stream fields, z's totals
 void jpeg_stream_layout(long long len, int n_segments, int S, JdFile &F, JdBufSizes &z);
 // one file's coefficient blocks and, decoded at scale 1 << shift, its sample planes and pixels (shift 0) or its workgroups of the
@@ -356,7 +373,10 @@ void jpeg_stream_layout(long long len, int n_segments, int S, JdFile &F, JdBufSi
 // fields, z's totals
 // box (NULL, or the whole image: none): left, top, right, bottom inside the image (jpeg_box_inside), full size only -- the file's
 // workgroups of k_jd_box and no sample planes; window_coef: only the coefficients of the window's MCU rows are stored (baseline files)
-void jpeg_recon_layout(const aej_jpegdec_desc &d, int shift, JdFile &F, JdBufSizes &z, const int *box = nullptr, bool window_coef = true);
+// x (NULL: none): the file's aej_jpeg_adobe; with another colour than YCbCr the file gets kJdAdobe in its shift, four sample planes and
+// its workgroups of k_jd_adobe (shift: 0, or kJdCmyk for four-channel output; the callers refuse a scale, luma or a box for such a file)
+void jpeg_recon_layout(const aej_jpegdec_desc &d, int shift, JdFile &F, JdBufSizes &z, const int *box = nullptr, bool window_coef = true,
+                       const aej_jpeg_adobe *x = nullptr);
 template <class D>                     // D: aej_jpegdec_desc or aej_jpegprog_frame
 bool jpeg_box_whole(const D &d, const int *box) { return !box || (box[0] == 0 && box[1] == 0 && box[2] == d.width && box[3] == d.height); }
 template <class D>
@@ -368,7 +388,7 @@ inline int jpeg_scale_shift(int scale) { return scale == 1 ? 0 : scale == 2 ? 1 
 // shifts: log2 of every file's scale (+ kJdLuma for a file that leaves as its luma plane), or NULL for all at full size, RGB
 // boxes: NULL or [n][4], jpeg_recon_layout's box of every file
 void jpegdec_layout(const aej_jpegdec_desc *descs, int n, int S, std::vector<JdFile> &files, JdBufSizes &z, const int *shifts = nullptr,
-                    const int *boxes = nullptr);
+                    const int *boxes = nullptr, const aej_jpeg_adobe *adobe = nullptr);
 unsigned long long jpegdec_carve(void *base, int n, const JdBufSizes &z, JdBufs &w);
 hipError_t launch_jpegdec_begin(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, const void *blob_host, unsigned long long blob_bytes,
                                 const unsigned char *scans, int S, int *status);
@@ -388,6 +408,7 @@ struct JpLayout {                      // host-computed layout of one aej_jpegpr
     std::vector<JdFile> sfiles, ffiles;                // one un-stuffing stream per scan; one reconstruction entry per file
     std::vector<aej_jpegdec_desc> sdescs, fdescs;      // per scan: segments, unit counts, Huffman tables; per file: what k_jd_idct / k_jd_rgb read
     std::vector<JpScan> scans;
+    std::vector<aej_jpeg_adobe> fadobe;                // per file, in a call with a four-component or RGB-coded file alone (fz.grpa > 0); else empty
     std::vector<int> src;                              // scans[t] is the caller's scan src[t]
     std::vector<JpItem> items;
     std::vector<long long> level_items;                // items of level l: [level_items[l], level_items[l + 1])
@@ -395,15 +416,17 @@ struct JpLayout {                      // host-computed layout of one aej_jpegpr
     int n_levels = 0;
 };
 struct JpBufs { void *blob; JdBufs s, f; JpScan *scans; JpItem *items; int *sstatus; };
-inline void jp_scan_units(const aej_jpegprog_frame &f, int ncomp, int comp0, int &ux, int &uy)      // the units a progressive scan walks
+// the units a progressive scan walks (x: the file's aej_jpeg_adobe or NULL -- component 3 sampled as component 0 has its block grid)
+inline void jp_scan_units(const aej_jpegprog_frame &f, int ncomp, int comp0, int &ux, int &uy, const aej_jpeg_adobe *x = nullptr)
 {
-    if (ncomp > 1 || f.ncomp == 1 || comp0 > 0) { ux = f.mcux; uy = f.mcuy; }      // chroma is sampled 1x1: its block grid is the MCU grid
+    const bool full3 = comp0 == 3 && x && x->h3 == f.hs && x->v3 == f.vs;
+    if (ncomp > 1 || f.ncomp == 1 || (comp0 > 0 && !full3)) { ux = f.mcux; uy = f.mcuy; }      // chroma is sampled 1x1: its block grid is the MCU grid
     else { ux = (f.width + 7) / 8; uy = (f.height + 7) / 8; }
 }
 int jpegprog_parse(const unsigned char *data, unsigned long long n, aej_jpegprog_frame &f, std::vector<aej_jpegprog_scan> &scans,
-                   std::string &msg, bool allow440 = false);                                                           // jpegparse.hip
+                   std::string &msg, bool allow440 = false, aej_jpeg_adobe *adobe = nullptr);                          // jpegparse.hip
 bool jpegprog_layout(const aej_jpegprog_frame *frames, const aej_jpegprog_scan *scans, int n, JpLayout &y, const int *shifts = nullptr,
-                     const int *boxes = nullptr);
+                     const int *boxes = nullptr, const aej_jpeg_adobe *adobe = nullptr);
 unsigned long long jpegprog_blob(const JpLayout &y, std::vector<unsigned char> *out);
 unsigned long long jpegprog_carve(void *base, const JpLayout &y, JpBufs &w);
 hipError_t launch_jpegprog_entropy(hipStream_t st, const JpLayout &y, const JpBufs &w, const void *blob_host, unsigned long long blob_bytes,

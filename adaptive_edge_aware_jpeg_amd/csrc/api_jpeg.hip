@@ -197,11 +197,12 @@ extern "C" int aej_test_jfif_prog_scan(aej_ctx *ctx, const int16_t *coefs_host, 
 }
 
 // ---- baseline JPEG files decoded on the device (jpegdec.hip; the marker walk: jpegparse.hip) --------------------------------------------------------------------------
-static int jd_parse_host(const uint8_t *data_host, uint64_t nbytes, aej_jpegdec_desc *desc_host, char *msg, int msg_capacity, int layout_440)
+static int jd_parse_host(const uint8_t *data_host, uint64_t nbytes, aej_jpegdec_desc *desc_host, char *msg, int msg_capacity, int layout_440,
+                         aej_jpeg_adobe *adobe_host = nullptr)
 {
     if (!desc_host || (layout_440 != 0 && layout_440 != 1)) return AEJ_ERR_ARG;
     std::string m;
-    const int rc = jpegdec_parse(data_host, nbytes, *desc_host, m, layout_440 != 0);
+    const int rc = jpegdec_parse(data_host, nbytes, *desc_host, m, layout_440 != 0, adobe_host);
     copy_msg(m, msg, msg_capacity);
     return rc;
 }
@@ -215,6 +216,13 @@ extern "C" int aej_jpegdec_parse_host_440(const uint8_t *data_host, uint64_t nby
                                           int layout_440)
 {
     return jd_parse_host(data_host, nbytes, desc_host, msg, msg_capacity, layout_440);
+}
+
+extern "C" int aej_jpegdec_parse_host_adobe(const uint8_t *data_host, uint64_t nbytes, aej_jpegdec_desc *desc_host, aej_jpeg_adobe *adobe_host,
+                                            char *msg, int msg_capacity, int layout_440)
+{
+    if (!adobe_host) return AEJ_ERR_ARG;
+    return jd_parse_host(data_host, nbytes, desc_host, msg, msg_capacity, layout_440, adobe_host);
 }
 
 // ---- what a call's offsets must satisfy (shared by the decoders and the transcoder) -------------------------------------------------------
@@ -242,7 +250,7 @@ static int jpegprog_scan_offsets(aej_ctx *ctx, const char *fn, JpLayout &y, uint
 // the image of file i (RGB, or its luma plane: file.shift) checked against the output and entered into the layout
 static int image_offset(aej_ctx *ctx, const char *fn, int i, uint64_t out_bytes, long long oo, JdFile &file)
 {
-    const long long bytes = (long long)file.ow * file.oh * ((file.shift & kJdLuma) ? 1 : 3);
+    const long long bytes = (long long)file.ow * file.oh * ((file.shift & kJdCmyk) ? 4 : (file.shift & kJdLuma) ? 1 : 3);
     if (!inside(oo, bytes, out_bytes)) return fail(ctx, AEJ_ERR_ARG, "%s: file %d: image outside the output", fn, i);
     file.out_off = oo;
     return 0;
@@ -299,6 +307,51 @@ static int check_boxes(aej_ctx *ctx, const char *fn, const D *frames, int n, con
                 frames[bad].width, frames[bad].height);
 }
 
+// The _adobe entries: components_host may say 4 (Pillow's mode "CMYK" image) for a four-component file.  comps3 gets the counts with 3 in
+// the place of every 4, for scale_shifts; after it adobe_shifts adds kJdCmyk to those files' shifts.  False (*bad: the file): a 4 on a file
+// that does not have four components.
+template <class D>
+static bool adobe_components(const D *frames, int n, const int *components_host, const aej_jpeg_adobe *adobe_host, std::vector<int> &comps3, int *bad)
+{
+    comps3.clear();
+    if (!components_host) return true;
+    comps3.assign(components_host, components_host + n);
+    for (int i = 0; i < n; i++)
+        if (components_host[i] == 4) {
+            *bad = i;
+            if (!frames || frames[i].ncomp != 4 || !adobe_host || !jpeg_adobe_new(adobe_host + i)) return false;
+            comps3[i] = 3;
+        }
+    return true;
+}
+static void adobe_shifts(int n, const int *components_host, std::vector<int> &shifts)
+{
+    for (int i = 0; components_host && i < n; i++) if (components_host[i] == 4) shifts[i] |= kJdCmyk;
+}
+// what is not built for a four-component or RGB-coded file: 0, or 1 luma, 2 a scale, 3 a box (*bad: the file)
+template <class D>
+static int adobe_unbuilt(const D *frames, int n, const aej_jpeg_adobe *adobe_host, const std::vector<int> &shifts, const int32_t *boxes_host, int *bad)
+{
+    for (int i = 0; adobe_host && i < n; i++) {
+        if (!jpeg_adobe_new(adobe_host + i)) continue;
+        *bad = i;
+        if (shifts[i] & kJdLuma) return 1;
+        if (shifts[i] & (kJdLuma - 1)) return 2;
+        if (boxes_host && !jpeg_box_whole(frames[i], boxes_host + 4 * i)) return 3;
+    }
+    return 0;
+}
+template <class D>
+static int check_adobe(aej_ctx *ctx, const char *fn, const D *frames, int n, const aej_jpeg_adobe *adobe_host, const std::vector<int> &shifts,
+                       const int32_t *boxes_host)
+{
+    int bad = 0;
+    const int what = adobe_unbuilt(frames, n, adobe_host, shifts, boxes_host, &bad);
+    if (!what) return 0;
+    return fail(ctx, AEJ_ERR_UNSUPPORTED, "%s: file %d: %s of a four-component / RGB-coded file is not built", fn, bad,
+                what == 1 ? "luma output" : what == 2 ? "a scale other than 1" : "a box");
+}
+
 // jd_box_window behind the two public entries
 static int box_window_host(int width, int height, int hs, int vs, int ncomp, const int32_t *box4_host, int32_t *window4_out_host)
 {
@@ -330,16 +383,26 @@ extern "C" int aej_jpegdec_box_stats(aej_ctx *ctx, int64_t *out3_host)
 }
 
 static uint64_t jpegdec_workspace(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host, const int *components_host = nullptr,
-                                  const int32_t *boxes_host = nullptr)
+                                  const int32_t *boxes_host = nullptr, const aej_jpeg_adobe *adobe_host = nullptr)
 {
-    std::vector<int> shifts;
+    std::vector<int> shifts, comps3;
     int bad = 0;
     bool unsupported = false;
-    if (!ctx || !jpegdec_descs_ok(descs_host, n) || !scale_shifts(scales_host, n, shifts, nullptr, components_host)) return 0;
+    if (!ctx || !jpegdec_descs_ok(descs_host, n, adobe_host)) return 0;
+    const int *components4 = components_host;         // with the 4s
+    if (adobe_host) {
+        if (!adobe_components(descs_host, n, components_host, adobe_host, comps3, &bad)) return 0;
+        if (components_host) components_host = comps3.data();
+    }
+    if (!scale_shifts(scales_host, n, shifts, nullptr, components_host)) return 0;
     if (!boxes_ok(descs_host, n, boxes_host, shifts, &bad, &unsupported)) return 0;
+    if (adobe_host) {
+        if (adobe_unbuilt(descs_host, n, adobe_host, shifts, boxes_host, &bad)) return 0;
+        adobe_shifts(n, components4, shifts);
+    }
     std::vector<JdFile> files;
     JdBufSizes z;
-    jpegdec_layout(descs_host, n, ctx->jd_subseq_bits, files, z, shifts.data(), boxes_host);
+    jpegdec_layout(descs_host, n, ctx->jd_subseq_bits, files, z, shifts.data(), boxes_host, adobe_host);
     JdBufs w;
     return jpegdec_carve(nullptr, n, z, w);
 }
@@ -366,10 +429,16 @@ extern "C" uint64_t aej_jpegdec_workspace_bytes_box(aej_ctx *ctx, const aej_jpeg
     return jpegdec_workspace(ctx, descs_host, n, scales_host, components_host, boxes_host);
 }
 
+extern "C" uint64_t aej_jpegdec_workspace_bytes_adobe(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host,
+                                                      const int *components_host, const int32_t *boxes_host, const aej_jpeg_adobe *adobe_host)
+{
+    return jpegdec_workspace(ctx, descs_host, n, scales_host, components_host, boxes_host, adobe_host);
+}
+
 // the entropy decode of n baseline files up to the fixed point of the sync rounds: everything of aej_jpegdec_batch before the
 // coefficient write (`files` carries the scan offsets; the caller has carved `w`)
 static int jpegdec_decode(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs_host, int n, const std::vector<JdFile> &files, const JdBufSizes &z,
-                          const JdBufs &w, const uint8_t *scans, int32_t *status)
+                          const JdBufs &w, const uint8_t *scans, int32_t *status, const aej_jpeg_adobe *adobe_host = nullptr)
 {
     const int S = ctx->jd_subseq_bits;
     // one upload: files, descriptors, the "last round that changed" word (-1)
@@ -381,6 +450,8 @@ static int jpegdec_decode(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *
     long long max_slots = 0;
     for (const JdFile &f : files) max_slots = std::max(max_slots, f.n_slots);
     AEJ_TRY(bind_device(ctx));
+    if (z.grpa > 0)                                   // a call with a four-component or RGB-coded file: the kernels of such a call read these
+        AEJ_HIP_CHECK(hipMemcpyAsync(w.adobe, adobe_host, sizeof(aej_jpeg_adobe) * n, hipMemcpyHostToDevice, ctx->stream));
     AEJ_HIP_CHECK(launch_jpegdec_begin(ctx->stream, n, z, w, blob.data(), blob.size(), scans, S, status));
     // sync rounds: kJdSyncBatch launches, then one word read back; more only while the last launched round still changed something.
     // Each round settles at least the first unsettled subsequence of every segment, so max_slots rounds always suffice.
@@ -403,18 +474,31 @@ static int jpegdec_decode(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *
 static int jpegdec_batch(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs_host, int n, const int *scales_host, const int *components_host,
                          const uint8_t *scans,
                          uint64_t scans_bytes, const int64_t *scan_offsets_host, uint8_t *out, uint64_t out_bytes, const int64_t *out_offsets_host,
-                         int32_t *status, void *workspace, uint64_t workspace_bytes, const int32_t *boxes_host = nullptr)
+                         int32_t *status, void *workspace, uint64_t workspace_bytes, const int32_t *boxes_host = nullptr,
+                         const aej_jpeg_adobe *adobe_host = nullptr)
 {
     AEJ_TRY(enter(ctx, fn));
-    if (!jpegdec_descs_ok(descs_host, n)) return fail(ctx, AEJ_ERR_ARG, "%s: no files, or a descriptor aej_jpegdec_parse_host did not write", fn);
+    if (!jpegdec_descs_ok(descs_host, n, adobe_host))
+        return fail(ctx, AEJ_ERR_ARG, "%s: no files, or a descriptor aej_jpegdec_parse_host did not write", fn);
     if (!scans || !scan_offsets_host || !out || !out_offsets_host || !status || !workspace) return null_buffer(ctx, fn);
-    std::vector<int> shifts;
+    std::vector<int> shifts, comps3;
+    const int *components4 = components_host;         // with the 4s of the _adobe entry
+    if (adobe_host) {
+        int bad = 0;
+        if (!adobe_components(descs_host, n, components_host, adobe_host, comps3, &bad))
+            return fail(ctx, AEJ_ERR_ARG, "%s: file %d: 4 output components for a file that does not have four", fn, bad);
+        if (components_host) components_host = comps3.data();
+    }
     AEJ_TRY(check_scales(ctx, fn, scales_host, n, shifts, components_host));
     AEJ_TRY(check_boxes(ctx, fn, descs_host, n, boxes_host, shifts));
+    if (adobe_host) {
+        AEJ_TRY(check_adobe(ctx, fn, descs_host, n, adobe_host, shifts, boxes_host));
+        adobe_shifts(n, components4, shifts);
+    }
     const int S = ctx->jd_subseq_bits;
     std::vector<JdFile> files;
     JdBufSizes z;
-    jpegdec_layout(descs_host, n, S, files, z, shifts.data(), boxes_host);
+    jpegdec_layout(descs_host, n, S, files, z, shifts.data(), boxes_host, adobe_host);
     if (z.grpb > 0) {                                        // aej_jpegdec_box_stats: from the descriptors and the windows alone
         long long total = 0, decoded = 0;
         for (int i = 0; i < n; i++) {
@@ -435,7 +519,7 @@ static int jpegdec_batch(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *d
     JdBufs w;
     const unsigned long long need = jpegdec_carve(workspace, n, z, w);
     AEJ_TRY(check_workspace(ctx, need, workspace_bytes));
-    AEJ_TRY(jpegdec_decode(ctx, fn, descs_host, n, files, z, w, scans, status));
+    AEJ_TRY(jpegdec_decode(ctx, fn, descs_host, n, files, z, w, scans, status, adobe_host));
     AEJ_HIP_CHECK(launch_jpegdec_finish(ctx->stream, n, z, w, S, out, status));
     return 0;
 }
@@ -474,6 +558,28 @@ extern "C" int aej_jpegdec_batch_box(aej_ctx *ctx, const aej_jpegdec_desc *descs
                          out_offsets_host, status, workspace, workspace_bytes, boxes_host);
 }
 
+extern "C" int aej_jpegdec_batch_adobe(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host, const int *components_host,
+                                       const int32_t *boxes_host, const aej_jpeg_adobe *adobe_host, const uint8_t *scans, uint64_t scans_bytes,
+                                       const int64_t *scan_offsets_host, uint8_t *out, uint64_t out_bytes, const int64_t *out_offsets_host,
+                                       int32_t *status, void *workspace, uint64_t workspace_bytes)
+{
+    return jpegdec_batch(ctx, __func__, descs_host, n, scales_host, components_host, scans, scans_bytes, scan_offsets_host, out, out_bytes,
+                         out_offsets_host, status, workspace, workspace_bytes, boxes_host, adobe_host);
+}
+
+// the host twins of the per-pixel colour rules of k_jd_adobe (jpegdec_core.h), for the tests: n pixels of four samples -> n pixels of
+// `components` (3 or 4) channels under `colour` (AEJ_JPEG_RGB, _CMYK, _YCCK)
+extern "C" int aej_test_jpeg_adobe_pixels_host(const uint8_t *samples4_host, int64_t n, int colour, int components, uint8_t *out_host)
+{
+    if (!samples4_host || !out_host || n < 0 || colour < AEJ_JPEG_RGB || colour > AEJ_JPEG_YCCK || (components != 3 && components != 4)) return AEJ_ERR_ARG;
+    if (components == 4 && colour == AEJ_JPEG_RGB) return AEJ_ERR_ARG;
+    for (int64_t i = 0; i < n; i++) {
+        const int s[4] = { samples4_host[4 * i], samples4_host[4 * i + 1], samples4_host[4 * i + 2], samples4_host[4 * i + 3] };
+        jd_adobe_pixel(colour, components == 4, s, out_host + i * components);
+    }
+    return 0;
+}
+
 extern "C" int aej_test_jpegdec_idct_host(const int16_t *coef_host, const uint16_t *qt_host, int size, uint8_t *out_host)
 {
     if (!coef_host || !qt_host || !out_host || (size != 1 && size != 2 && size != 4)) return AEJ_ERR_ARG;
@@ -489,12 +595,12 @@ extern "C" int64_t aej_jpegdec_sync_rounds(aej_ctx *ctx)
 
 // ---- progressive JPEG files decoded on the device (jpegprog.hip) ----------------------------------------------------------------------
 static int jp_parse_host(const uint8_t *data_host, uint64_t nbytes, aej_jpegprog_frame *frame_host, aej_jpegprog_scan *scans_host, int scan_capacity,
-                         char *msg, int msg_capacity, int layout_440)
+                         char *msg, int msg_capacity, int layout_440, aej_jpeg_adobe *adobe_host = nullptr)
 {
     if (!frame_host || (layout_440 != 0 && layout_440 != 1)) return AEJ_ERR_ARG;
     std::string m;
     std::vector<aej_jpegprog_scan> scans;
-    int rc = jpegprog_parse(data_host, nbytes, *frame_host, scans, m, layout_440 != 0);
+    int rc = jpegprog_parse(data_host, nbytes, *frame_host, scans, m, layout_440 != 0, adobe_host);
     if (rc == 0 && scans_host) {
         if (scan_capacity < (int)scans.size()) { rc = AEJ_ERR_CAPACITY; m = "scan capacity below the file's " + std::to_string(scans.size()) + " scans"; }
         else memcpy(scans_host, scans.data(), sizeof(aej_jpegprog_scan) * scans.size());
@@ -515,16 +621,32 @@ extern "C" int aej_jpegprog_parse_host_440(const uint8_t *data_host, uint64_t nb
     return jp_parse_host(data_host, nbytes, frame_host, scans_host, scan_capacity, msg, msg_capacity, layout_440);
 }
 
+extern "C" int aej_jpegprog_parse_host_adobe(const uint8_t *data_host, uint64_t nbytes, aej_jpegprog_frame *frame_host, aej_jpegprog_scan *scans_host,
+                                             int scan_capacity, aej_jpeg_adobe *adobe_host, char *msg, int msg_capacity, int layout_440)
+{
+    if (!adobe_host) return AEJ_ERR_ARG;
+    return jp_parse_host(data_host, nbytes, frame_host, scans_host, scan_capacity, msg, msg_capacity, layout_440, adobe_host);
+}
+
 static uint64_t jpegprog_workspace(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n, const int *scales_host,
-                                   const int *components_host = nullptr, const int32_t *boxes_host = nullptr)
+                                   const int *components_host = nullptr, const int32_t *boxes_host = nullptr, const aej_jpeg_adobe *adobe_host = nullptr)
 {
     JpLayout y;
-    std::vector<int> shifts;
+    std::vector<int> shifts, comps3;
     int bad = 0;
     bool unsupported = false;
+    const int *components4 = components_host;         // with the 4s
+    if (adobe_host) {
+        if (!frames_host || n < 1 || !adobe_components(frames_host, n, components_host, adobe_host, comps3, &bad)) return 0;
+        if (components_host) components_host = comps3.data();
+    }
     if (!ctx || !scale_shifts(scales_host, n, shifts, nullptr, components_host)) return 0;
     if (boxes_host && (!frames_host || !boxes_ok(frames_host, n, boxes_host, shifts, &bad, &unsupported))) return 0;
-    if (!jpegprog_layout(frames_host, scans_host, n, y, shifts.data(), boxes_host)) return 0;
+    if (adobe_host) {
+        if (adobe_unbuilt(frames_host, n, adobe_host, shifts, boxes_host, &bad)) return 0;
+        adobe_shifts(n, components4, shifts);
+    }
+    if (!jpegprog_layout(frames_host, scans_host, n, y, shifts.data(), boxes_host, adobe_host)) return 0;
     JpBufs w;
     return jpegprog_carve(nullptr, y, w);
 }
@@ -552,22 +674,42 @@ extern "C" uint64_t aej_jpegprog_workspace_bytes_box(aej_ctx *ctx, const aej_jpe
     return jpegprog_workspace(ctx, frames_host, scans_host, n, scales_host, components_host, boxes_host);
 }
 
+extern "C" uint64_t aej_jpegprog_workspace_bytes_adobe(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
+                                                       const int *scales_host, const int *components_host, const int32_t *boxes_host,
+                                                       const aej_jpeg_adobe *adobe_host)
+{
+    return jpegprog_workspace(ctx, frames_host, scans_host, n, scales_host, components_host, boxes_host, adobe_host);
+}
+
 // levels [0, n_levels) of the entropy stage, then either the reconstruction into `out` or (tests) a copy of the coefficients
 static int jpegprog_run(aej_ctx *ctx, const char *fn, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
                         const int *scales_host, const uint8_t *data, uint64_t data_bytes, const int64_t *data_offsets_host, int n_levels, uint8_t *out, uint64_t out_bytes,
                         const int64_t *out_offsets_host, int16_t *coef_out, uint64_t coef_blocks, int32_t *status, void *workspace,
-                        uint64_t workspace_bytes, const int *components_host = nullptr, const int32_t *boxes_host = nullptr)
+                        uint64_t workspace_bytes, const int *components_host = nullptr, const int32_t *boxes_host = nullptr,
+                        const aej_jpeg_adobe *adobe_host = nullptr)
 {
     if (!ctx) return AEJ_ERR_ARG;
     AEJ_TRY(refuse_in_flight(ctx, fn));
     JpLayout y;
-    std::vector<int> shifts;
+    std::vector<int> shifts, comps3;
+    const int *components4 = components_host;         // with the 4s of the _adobe entry
+    if (adobe_host) {
+        int bad = 0;
+        if (!frames_host || n < 1) return fail(ctx, AEJ_ERR_ARG, "%s: no files, or descriptors aej_jpegprog_parse_host did not write", fn);
+        if (!adobe_components(frames_host, n, components_host, adobe_host, comps3, &bad))
+            return fail(ctx, AEJ_ERR_ARG, "%s: file %d: 4 output components for a file that does not have four", fn, bad);
+        if (components_host) components_host = comps3.data();
+    }
     AEJ_TRY(check_scales(ctx, fn, scales_host, n, shifts, components_host));
     if (boxes_host) {                                        // the frames' sizes are read: the checks jpegprog_layout starts with, first
         if (!frames_host || n < 1) return fail(ctx, AEJ_ERR_ARG, "%s: no files, or descriptors aej_jpegprog_parse_host did not write", fn);
         AEJ_TRY(check_boxes(ctx, fn, frames_host, n, boxes_host, shifts));
     }
-    if (!jpegprog_layout(frames_host, scans_host, n, y, shifts.data(), boxes_host))
+    if (adobe_host) {
+        AEJ_TRY(check_adobe(ctx, fn, frames_host, n, adobe_host, shifts, boxes_host));
+        adobe_shifts(n, components4, shifts);
+    }
+    if (!jpegprog_layout(frames_host, scans_host, n, y, shifts.data(), boxes_host, adobe_host))
         return fail(ctx, AEJ_ERR_ARG, "%s: no files, or descriptors aej_jpegprog_parse_host did not write", fn);
     if (!data || !data_offsets_host || !status || !workspace || (!out && !coef_out) || (out && !out_offsets_host))
         return null_buffer(ctx, fn);
@@ -625,6 +767,17 @@ extern "C" int aej_jpegprog_batch_box(aej_ctx *ctx, const aej_jpegprog_frame *fr
     if (!out) return ctx ? null_buffer(ctx, __func__) : AEJ_ERR_ARG;
     return jpegprog_run(ctx, __func__, frames_host, scans_host, n, scales_host, data, data_bytes, data_offsets_host, 1 << 30, out, out_bytes,
                         out_offsets_host, nullptr, 0, status, workspace, workspace_bytes, components_host, boxes_host);
+}
+
+extern "C" int aej_jpegprog_batch_adobe(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
+                                        const int *scales_host, const int *components_host, const int32_t *boxes_host,
+                                        const aej_jpeg_adobe *adobe_host, const uint8_t *data, uint64_t data_bytes, const int64_t *data_offsets_host,
+                                        uint8_t *out, uint64_t out_bytes, const int64_t *out_offsets_host, int32_t *status, void *workspace,
+                                        uint64_t workspace_bytes)
+{
+    if (!out) return ctx ? null_buffer(ctx, __func__) : AEJ_ERR_ARG;
+    return jpegprog_run(ctx, __func__, frames_host, scans_host, n, scales_host, data, data_bytes, data_offsets_host, 1 << 30, out, out_bytes,
+                        out_offsets_host, nullptr, 0, status, workspace, workspace_bytes, components_host, boxes_host, adobe_host);
 }
 
 extern "C" int aej_test_jpegprog_coefs(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,

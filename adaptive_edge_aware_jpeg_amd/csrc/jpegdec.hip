@@ -31,6 +31,13 @@
 //                   LDS, then jd_chroma / jd_rgb on the LDS planes, and only the box's pixels stored.  No sample planes.  In a call with
 //                   such a file k_jd_init / k_jd_sync / k_jd_write run as their <true> instantiation: a restart segment of a boxed file
 //                   that holds no MCU of the window's MCU rows is an idle slot to them, and only those rows' coefficients are stored
+//   k_jd_init4 / k_jd_sync4 / k_jd_scan_slots4 / k_jd_write4   the slot kernels of a call that has a four-component (CMYK, YCCK) or RGB-coded
+//                   file (aej_jpegdec_batch_adobe), for all of its files: a fourth DC sum and prefix per slot, a 4-bit block slot in the packed
+//                   state, component 3 under the tables of the file's aej_jpeg_adobe; k_jd_fix4 between two k_jd_scan_slots4 for the files
+//                   whose components share one table pair (JdFile::uniform), where the block slot comes from the block counts
+//   k_jd_idct4      k_jd_idct for those files: four sample planes
+//   k_jd_adobe      those files in the place of k_jd_rgb: four pixels per thread -- every sub-sampled plane, K included, up-sampled by
+//                   jd_chroma's rules, the colour model's rule (jd_adobe_pixel), whole-dword stores of 3 or 4 channels
 // Bounds: every index derives from the host-computed JdFile layout; a file's reads stay inside its scan and its clean stream, decode loops
 // are bounded by their subsequence's bits, and coefficient writes by the segment's block count.
 #include <string.h>
@@ -220,22 +227,52 @@ __device__ __forceinline__ JdSlotPos jd_slot(const JdFile *files, const aej_jpeg
     return p;
 }
 
-__device__ __forceinline__ unsigned long long jd_guess(const JdSeg &sg, long long j, int S) { return jd_pack(sg.start * 8 + j * S, 0, 0, 0); }
+template <bool kFour = false>
+__device__ __forceinline__ unsigned long long jd_guess(const JdSeg &sg, long long j, int S) { return jd_pack<kFour>(sg.start * 8 + j * S, 0, 0, 0); }
 
-// one sync-mode decode of slot (seg, j) from `entry`; returns the exit state
+// one sync-mode decode of slot (seg, j) from `entry`; returns the exit state.  out: blocks started and the DC sums (kFour: of four
+// components; x: the file's aej_jpeg_adobe)
+template <bool kFour = false>
 __device__ __forceinline__ unsigned long long jd_decode_slot(const aej_jpegdec_desc &d, const unsigned char *clean, const JdSeg &sg, long long j, int S,
-                                                             unsigned long long entry, int out[4])
+                                                             unsigned long long entry, int *out, const aej_jpeg_adobe *x = nullptr, int k_given = -1)
 {
+    constexpr int kNc = kFour ? 4 : 3;
     JdBits br(clean);
-    long long pos = jd_pos(entry);
-    int k = jd_k(entry), z = jd_z(entry);
+    long long pos = jd_pos<kFour>(entry);
+    int k = kFour && k_given >= 0 ? k_given : jd_k<kFour>(entry), z = jd_z(entry);
     const long long seg_end = (sg.start + sg.nbytes) * 8;
     const long long stop = j + 1 == sg.n_sub ? seg_end : sg.start * 8 + (j + 1) * S;
-    int nstart = 0, dc[3] = { 0, 0, 0 }, pred[3];
+    int nstart = 0, dc[kNc] = {}, pred[kNc];
     long long next = 0;
-    const int rc = jd_run<false>(d, br, pos, k, z, stop, seg_end, nstart, dc, nullptr, next, 0, pred);
-    out[0] = nstart; out[1] = dc[0]; out[2] = dc[1]; out[3] = dc[2];
-    return jd_pack(pos, k, z, rc != kJdRunStop);
+    const int rc = jd_run<false, false, kFour>(d, br, pos, k, z, stop, seg_end, nstart, dc, nullptr, next, 0, pred, 0, x);
+    out[0] = nstart;
+    for (int v = 0; v < kNc; v++) out[v + 1] = dc[v];
+    return jd_pack<kFour>(pos, k, z, rc != kJdRunStop);
+}
+
+// The three slot kernels as functions of <kBox, kFour>: k_jd_init / k_jd_sync / k_jd_write <kBox> are their <kBox, false> forms; the
+// <true, true> forms are k_jd_init4 / k_jd_sync4 / k_jd_write4, which a call with a four-component or RGB-coded file runs for all of
+// its files (kFour: jd_pack's 4-bit block slot, a fourth DC sum per slot, component 3 under the tables of adobe[file]).
+template <bool kBox, bool kFour>
+__device__ __forceinline__ void jd_init_slot(const JdFile *__restrict__ files, const aej_jpegdec_desc *__restrict__ descs, int n,
+                                             long long n_slots, const JdSeg *__restrict__ segs, const unsigned char *__restrict__ clean,
+                                             JdSlots sl, int S, int *__restrict__ last_change, const aej_jpeg_adobe *__restrict__ adobe)
+{
+    constexpr int kNv = kFour ? 5 : 4;
+    const long long t = (long long)blockIdx.x * kJdThreads + threadIdx.x;
+    if (t >= n_slots) return;
+    const JdSlotPos p = jd_slot<kBox>(files, descs, n, segs, t);
+    int out[kNv] = {};
+    unsigned long long entry = jd_pack<kFour>(0, 0, 0, 1), exit = entry;
+    if (p.j >= 0) {
+        entry = jd_guess<kFour>(*p.seg, p.j, S);
+        exit = jd_decode_slot<kFour>(descs[p.f], clean + files[p.f].clean_off, *p.seg, p.j, S, entry, out, kFour ? adobe + p.f : nullptr);
+        if (p.j > 0) atomicMax(last_change, 0);
+    }
+    sl.state[t] = exit;
+    sl.used[t] = entry;
+    for (int v = 0; v < kNv; v++) sl.cnt[t * kNv + v] = out[v];
+    sl.first[t] = p.j == 0;
 }
 
 template <bool kBox>
@@ -243,20 +280,41 @@ __global__ __launch_bounds__(kJdThreads) void k_jd_init(const JdFile *__restrict
                                                         long long n_slots, const JdSeg *__restrict__ segs, const unsigned char *__restrict__ clean,
                                                         JdSlots sl, int S, int *__restrict__ last_change)
 {
+    jd_init_slot<kBox, false>(files, descs, n, n_slots, segs, clean, sl, S, last_change, nullptr);
+}
+
+__global__ __launch_bounds__(kJdThreads) void k_jd_init4(const JdFile *__restrict__ files, const aej_jpegdec_desc *__restrict__ descs, int n,
+                                                         long long n_slots, const JdSeg *__restrict__ segs, const unsigned char *__restrict__ clean,
+                                                         JdSlots sl, int S, int *__restrict__ last_change, const aej_jpeg_adobe *__restrict__ adobe)
+{
+    jd_init_slot<true, true>(files, descs, n, n_slots, segs, clean, sl, S, last_change, adobe);
+}
+
+template <bool kBox, bool kFour>
+__device__ __forceinline__ void jd_sync_slot(const JdFile *__restrict__ files, const aej_jpegdec_desc *__restrict__ descs, int n,
+                                             long long n_slots, const JdSeg *__restrict__ segs, const unsigned char *__restrict__ clean,
+                                             JdSlots sl, int S, int round, int *__restrict__ last_change, const aej_jpeg_adobe *__restrict__ adobe)
+{
+    constexpr int kNv = kFour ? 5 : 4;
+    if (__hip_atomic_load(last_change, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < round - 1) return;      // converged
     const long long t = (long long)blockIdx.x * kJdThreads + threadIdx.x;
     if (t >= n_slots) return;
     const JdSlotPos p = jd_slot<kBox>(files, descs, n, segs, t);
-    int out[4] = { 0, 0, 0, 0 };
-    unsigned long long entry = jd_pack(0, 0, 0, 1), exit = entry;
-    if (p.j >= 0) {
-        entry = jd_guess(*p.seg, p.j, S);
-        exit = jd_decode_slot(descs[p.f], clean + files[p.f].clean_off, *p.seg, p.j, S, entry, out);
-        if (p.j > 0) atomicMax(last_change, 0);
-    }
-    sl.state[t] = exit;
+    if (p.j <= 0) return;
+    const unsigned long long prev = __hip_atomic_load(sl.state + t - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    unsigned long long entry = jd_err<kFour>(prev) ? jd_guess<kFour>(*p.seg, p.j, S) : prev;
+    if (kFour && files[p.f].uniform) entry &= ~(15ULL << 6);      // one table for all components: the decode does not depend on the block slot, and
+                                                                 // nothing in the bits would ever correct a wrong one -- slot 0 here, k_jd_fix4 later
+    if (entry == sl.used[t]) return;
+    int out[kNv];
+    const unsigned long long exit = jd_decode_slot<kFour>(descs[p.f], clean + files[p.f].clean_off, *p.seg, p.j, S, entry, out, kFour ? adobe + p.f : nullptr);
     sl.used[t] = entry;
-    for (int v = 0; v < 4; v++) sl.cnt[t * 4 + v] = out[v];
-    sl.first[t] = p.j == 0;
+    bool changed = exit != sl.state[t];
+    for (int v = 0; v < kNv; v++) changed |= out[v] != sl.cnt[t * kNv + v];
+    if (!changed) return;
+    for (int v = 0; v < kNv; v++) sl.cnt[t * kNv + v] = out[v];
+    __hip_atomic_store(sl.state + t, exit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    atomicMax(last_change, round);
 }
 
 template <bool kBox>
@@ -264,69 +322,104 @@ __global__ __launch_bounds__(kJdThreads) void k_jd_sync(const JdFile *__restrict
                                                         long long n_slots, const JdSeg *__restrict__ segs, const unsigned char *__restrict__ clean,
                                                         JdSlots sl, int S, int round, int *__restrict__ last_change)
 {
-    if (__hip_atomic_load(last_change, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < round - 1) return;      // converged
-    const long long t = (long long)blockIdx.x * kJdThreads + threadIdx.x;
-    if (t >= n_slots) return;
-    const JdSlotPos p = jd_slot<kBox>(files, descs, n, segs, t);
-    if (p.j <= 0) return;
-    const unsigned long long prev = __hip_atomic_load(sl.state + t - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned long long entry = jd_err(prev) ? jd_guess(*p.seg, p.j, S) : prev;
-    if (entry == sl.used[t]) return;
-    int out[4];
-    const unsigned long long exit = jd_decode_slot(descs[p.f], clean + files[p.f].clean_off, *p.seg, p.j, S, entry, out);
-    sl.used[t] = entry;
-    bool changed = exit != sl.state[t];
-    for (int v = 0; v < 4; v++) changed |= out[v] != sl.cnt[t * 4 + v];
-    if (!changed) return;
-    for (int v = 0; v < 4; v++) sl.cnt[t * 4 + v] = out[v];
-    __hip_atomic_store(sl.state + t, exit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    atomicMax(last_change, round);
+    jd_sync_slot<kBox, false>(files, descs, n, n_slots, segs, clean, sl, S, round, last_change, nullptr);
 }
 
-// segmented exclusive scan over a file's slots (reset where a segment starts): blocks started and the three DC sums
-__global__ __launch_bounds__(kJdScanThreads) void k_jd_scan_slots(const JdFile *__restrict__ files, JdSlots sl)
+__global__ __launch_bounds__(kJdThreads) void k_jd_sync4(const JdFile *__restrict__ files, const aej_jpegdec_desc *__restrict__ descs, int n,
+                                                         long long n_slots, const JdSeg *__restrict__ segs, const unsigned char *__restrict__ clean,
+                                                         JdSlots sl, int S, int round, int *__restrict__ last_change,
+                                                         const aej_jpeg_adobe *__restrict__ adobe)
 {
-    __shared__ long long sh[4][kJdScanThreads];
-    __shared__ int shf[kJdScanThreads];
+    jd_sync_slot<true, true>(files, descs, n, n_slots, segs, clean, sl, S, round, last_change, adobe);
+}
+
+// segmented exclusive scan over a file's slots (reset where a segment starts): blocks started and the three DC sums (kFour: four)
+template <bool kFour>
+__device__ __forceinline__ void jd_scan_slots(const JdFile *__restrict__ files, JdSlots sl, long long (*sh)[kJdScanThreads], int *shf)
+{
+    constexpr int kNv = kFour ? 5 : 4;
     const JdFile &F = files[blockIdx.x];
     const long long m = F.n_slots, per = (m + kJdScanThreads - 1) / kJdScanThreads;
     const long long lo = min(m, threadIdx.x * per), hi = min(m, lo + per);
     const long long b = F.slot_base;
-    long long a[4] = { 0, 0, 0, 0 };
+    long long a[kNv] = {};
     int fl = 0;
     for (long long i = lo; i < hi; i++) {
-        if (sl.first[b + i]) { fl = 1; for (int v = 0; v < 4; v++) a[v] = 0; }
-        for (int v = 0; v < 4; v++) a[v] += sl.cnt[(b + i) * 4 + v];
+        if (sl.first[b + i]) { fl = 1; for (int v = 0; v < kNv; v++) a[v] = 0; }
+        for (int v = 0; v < kNv; v++) a[v] += sl.cnt[(b + i) * kNv + v];
     }
-    for (int v = 0; v < 4; v++) sh[v][threadIdx.x] = a[v];
+    for (int v = 0; v < kNv; v++) sh[v][threadIdx.x] = a[v];
     shf[threadIdx.x] = fl;
     __syncthreads();
     for (int off = 1; off < kJdScanThreads; off <<= 1) {      // (flag, sum) pairs: a later reset discards what came before
-        long long t[4];
+        long long t[kNv];
         int tf = 0;
-        if (threadIdx.x >= off) { for (int v = 0; v < 4; v++) t[v] = sh[v][threadIdx.x - off]; tf = shf[threadIdx.x - off]; }
+        if (threadIdx.x >= off) { for (int v = 0; v < kNv; v++) t[v] = sh[v][threadIdx.x - off]; tf = shf[threadIdx.x - off]; }
         __syncthreads();
         if (threadIdx.x >= off && !shf[threadIdx.x]) {
-            for (int v = 0; v < 4; v++) sh[v][threadIdx.x] += t[v];
+            for (int v = 0; v < kNv; v++) sh[v][threadIdx.x] += t[v];
             shf[threadIdx.x] = tf;
         }
         __syncthreads();
     }
-    long long run[4] = { 0, 0, 0, 0 };
-    if (threadIdx.x > 0) for (int v = 0; v < 4; v++) run[v] = sh[v][threadIdx.x - 1];
+    long long run[kNv] = {};
+    if (threadIdx.x > 0) for (int v = 0; v < kNv; v++) run[v] = sh[v][threadIdx.x - 1];
     for (long long i = lo; i < hi; i++) {
-        if (sl.first[b + i]) for (int v = 0; v < 4; v++) run[v] = 0;
+        if (sl.first[b + i]) for (int v = 0; v < kNv; v++) run[v] = 0;
         sl.blk_pre[b + i] = run[0];
-        for (int v = 0; v < 3; v++) sl.dc_pre[(b + i) * 3 + v] = (int)run[v + 1];
-        for (int v = 0; v < 4; v++) run[v] += sl.cnt[(b + i) * 4 + v];
+        for (int v = 0; v < kNv - 1; v++) sl.dc_pre[(b + i) * (kNv - 1) + v] = (int)run[v + 1];
+        for (int v = 0; v < kNv; v++) run[v] += sl.cnt[(b + i) * kNv + v];
     }
 }
 
-template <bool kBox>
-__global__ __launch_bounds__(kJdThreads) void k_jd_write(const JdFile *__restrict__ files, const aej_jpegdec_desc *__restrict__ descs, int n,
-                                                         long long n_slots, const JdSeg *__restrict__ segs, const unsigned char *__restrict__ clean,
-                                                         JdSlots sl, int S, short *__restrict__ coef, int *__restrict__ status)
+// the block slot of a uniform file's slot t at its entry, from the blocks started before it in the segment (which begins an MCU): the
+// block in progress when z != 0, else the next one
+__device__ __forceinline__ int jd_slot_k(long long blk_pre, int z, int bpm)
 {
+    const long long cur = z == 0 ? blk_pre : blk_pre - 1;
+    return (int)((cur > 0 ? cur : 0) % bpm);
+}
+
+// After the first k_jd_scan_slots4 of a kFour call, for the slots of uniform files alone: the decode once more, now from the right block
+// slot, so that every DC difference is summed under its own component; a second k_jd_scan_slots4 then gives the DC prefixes.  (The
+// blocks started, the exit position and the zigzag index do not depend on the slot and stay as the sync rounds left them.)
+__global__ __launch_bounds__(kJdThreads) void k_jd_fix4(const JdFile *__restrict__ files, const aej_jpegdec_desc *__restrict__ descs, int n,
+                                                        long long n_slots, const JdSeg *__restrict__ segs, const unsigned char *__restrict__ clean,
+                                                        JdSlots sl, int S, const aej_jpeg_adobe *__restrict__ adobe)
+{
+    const long long t = (long long)blockIdx.x * kJdThreads + threadIdx.x;
+    if (t >= n_slots) return;
+    const JdSlotPos p = jd_slot<true>(files, descs, n, segs, t);
+    if (p.j < 0 || !files[p.f].uniform) return;
+    unsigned long long entry = jd_guess<true>(*p.seg, p.j, S);
+    if (p.j > 0 && !jd_err<true>(sl.state[t - 1])) entry = sl.state[t - 1];
+    int out[5];
+    jd_decode_slot<true>(descs[p.f], clean + files[p.f].clean_off, *p.seg, p.j, S, entry, out, adobe + p.f,
+                         jd_slot_k(sl.blk_pre[t], jd_z(entry), descs[p.f].blocks_per_mcu));
+    for (int v = 1; v < 5; v++) sl.cnt[t * 5 + v] = out[v];
+}
+
+__global__ __launch_bounds__(kJdScanThreads) void k_jd_scan_slots(const JdFile *__restrict__ files, JdSlots sl)
+{
+    __shared__ long long sh[4][kJdScanThreads];
+    __shared__ int shf[kJdScanThreads];
+    jd_scan_slots<false>(files, sl, sh, shf);
+}
+
+__global__ __launch_bounds__(kJdScanThreads) void k_jd_scan_slots4(const JdFile *__restrict__ files, JdSlots sl)
+{
+    __shared__ long long sh[5][kJdScanThreads];
+    __shared__ int shf[kJdScanThreads];
+    jd_scan_slots<true>(files, sl, sh, shf);
+}
+
+template <bool kBox, bool kFour>
+__device__ __forceinline__ void jd_write_slot(const JdFile *__restrict__ files, const aej_jpegdec_desc *__restrict__ descs, int n,
+                                              long long n_slots, const JdSeg *__restrict__ segs, const unsigned char *__restrict__ clean,
+                                              JdSlots sl, int S, short *__restrict__ coef, int *__restrict__ status,
+                                              const aej_jpeg_adobe *__restrict__ adobe)
+{
+    constexpr int kNc = kFour ? 4 : 3;
     const long long t = (long long)blockIdx.x * kJdThreads + threadIdx.x;
     if (t >= n_slots) return;
     const JdSlotPos p = jd_slot<kBox>(files, descs, n, segs, t);
@@ -334,24 +427,27 @@ __global__ __launch_bounds__(kJdThreads) void k_jd_write(const JdFile *__restric
     const JdSeg &sg = *p.seg;
     const aej_jpegdec_desc &d = descs[p.f];
     const JdFile &F = files[p.f];
-    unsigned long long entry = jd_guess(sg, p.j, S);
-    if (p.j > 0 && !jd_err(sl.state[t - 1])) entry = sl.state[t - 1];
+    const aej_jpeg_adobe *x = kFour ? adobe + p.f : nullptr;
+    unsigned long long entry = jd_guess<kFour>(sg, p.j, S);
+    if (p.j > 0 && !jd_err<kFour>(sl.state[t - 1])) entry = sl.state[t - 1];
     JdBits br(clean + F.clean_off);
-    long long pos = jd_pos(entry);
-    int k = jd_k(entry), z = jd_z(entry);
+    long long pos = jd_pos<kFour>(entry);
+    int k = jd_k<kFour>(entry), z = jd_z(entry);
     const long long seg_end = (sg.start + sg.nbytes) * 8;
     const long long stop = p.j + 1 == sg.n_sub ? seg_end : sg.start * 8 + (p.j + 1) * S;
     const long long seg_blocks = (long long)sg.n_mcu * d.blocks_per_mcu;
-    int nstart = 0, dc[3] = { 0, 0, 0 };
-    int pred[3] = { sl.dc_pre[t * 3], sl.dc_pre[t * 3 + 1], sl.dc_pre[t * 3 + 2] };
+    int nstart = 0, dc[kNc] = {};
+    int pred[kNc];
+    for (int v = 0; v < kNc; v++) pred[v] = sl.dc_pre[t * kNc + v];
     long long next = sl.blk_pre[t];
+    if (kFour && F.uniform) k = jd_slot_k(next, z, d.blocks_per_mcu);
     short *c = coef + (F.blk_base + (long long)sg.first_mcu * d.blocks_per_mcu) * 64;
     int rc;
     if (kBox && (F.shift & kJdBox)) {                 // blocks [lo, hi) of the segment lie in the stored MCU rows [win[1], win[3]); c: its block 0, were it stored
         const long long first = (long long)sg.first_mcu * d.blocks_per_mcu, row = (long long)d.mcux * d.blocks_per_mcu;
         const long long lo = max(0LL, F.win[1] * row - first), hi = min(seg_blocks, F.win[3] * row - first);
         c = coef + (F.blk_base + first - F.row0 * row) * 64;
-        rc = jd_run<true, true>(d, br, pos, k, z, stop, seg_end, nstart, dc, c, next, hi, pred, lo);
+        rc = jd_run<true, true, kFour>(d, br, pos, k, z, stop, seg_end, nstart, dc, c, next, hi, pred, lo, x);
         const long long cur = z == 0 ? next : next - 1;
         if (rc == kJdRunDone || cur >= hi) return;   // nothing the window needs is left in this slot
         if (rc == kJdRunStop) {
@@ -362,7 +458,7 @@ __global__ __launch_bounds__(kJdThreads) void k_jd_write(const JdFile *__restric
                              : rc == kJdRunPast63 ? AEJ_JPEGDEC_RUN_PAST_63 : AEJ_JPEGDEC_BAD_DC);
         return;
     }
-    rc = jd_run<true>(d, br, pos, k, z, stop, seg_end, nstart, dc, c, next, seg_blocks, pred);
+    rc = jd_run<true, false, kFour>(d, br, pos, k, z, stop, seg_end, nstart, dc, c, next, seg_blocks, pred, 0, x);
     const long long cur = z == 0 ? next : next - 1;      // the block being decoded (or the next one) when the loop stopped
     if (rc == kJdRunDone) return;
     if (rc == kJdRunStop) {
@@ -374,30 +470,141 @@ __global__ __launch_bounds__(kJdThreads) void k_jd_write(const JdFile *__restric
                          : rc == kJdRunPast63 ? AEJ_JPEGDEC_RUN_PAST_63 : AEJ_JPEGDEC_BAD_DC);
 }
 
+template <bool kBox>
+__global__ __launch_bounds__(kJdThreads) void k_jd_write(const JdFile *__restrict__ files, const aej_jpegdec_desc *__restrict__ descs, int n,
+                                                         long long n_slots, const JdSeg *__restrict__ segs, const unsigned char *__restrict__ clean,
+                                                         JdSlots sl, int S, short *__restrict__ coef, int *__restrict__ status)
+{
+    jd_write_slot<kBox, false>(files, descs, n, n_slots, segs, clean, sl, S, coef, status, nullptr);
+}
+
+__global__ __launch_bounds__(kJdThreads) void k_jd_write4(const JdFile *__restrict__ files, const aej_jpegdec_desc *__restrict__ descs, int n,
+                                                          long long n_slots, const JdSeg *__restrict__ segs, const unsigned char *__restrict__ clean,
+                                                          JdSlots sl, int S, short *__restrict__ coef, int *__restrict__ status,
+                                                          const aej_jpeg_adobe *__restrict__ adobe)
+{
+    jd_write_slot<true, true>(files, descs, n, n_slots, segs, clean, sl, S, coef, status, adobe);
+}
+
 // ---- reconstruction --------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kJdThreads) void k_jd_idct(const JdFile *__restrict__ files, const aej_jpegdec_desc *__restrict__ descs, int n,
-                                                        long long n_blocks, const short *__restrict__ coef, unsigned char *__restrict__ planes)
+// kAdobe: k_jd_idct4, for the files with kJdAdobe in their shift alone (which k_jd_idct leaves alone, as it does every file with a shift):
+// component 3's blocks follow the MCU's others and go to a fourth plane behind the three, pw3 x ph3, under adobe[file]'s table
+template <bool kAdobe>
+__device__ __forceinline__ void jd_idct_thread(const JdFile *__restrict__ files, const aej_jpegdec_desc *__restrict__ descs, int n,
+                                               long long n_blocks, const short *__restrict__ coef, unsigned char *__restrict__ planes,
+                                               const aej_jpeg_adobe *__restrict__ adobe)
 {
     const long long idx = (long long)blockIdx.x * kJdThreads + threadIdx.x;
     if (idx >= n_blocks) return;
     const int f = jd_find_file<&JdFile::blk_base>(files, n, idx);
     const JdFile &F = files[f];
-    if (F.shift) return;                              // a scaled file: k_jd_scaled reads its coefficients
+    if (kAdobe ? !(F.shift & kJdAdobe) : F.shift != 0) return;      // a scaled file: k_jd_scaled reads its coefficients
     const aej_jpegdec_desc &d = descs[f];
     const long long b = idx - F.blk_base, mcu = b / d.blocks_per_mcu;
     const int k = (int)(b % d.blocks_per_mcu), my = (int)(mcu / d.mcux), mx = (int)(mcu % d.mcux);
-    const int c = jd_comp(d, k);
+    const int c = kAdobe ? jd_comp4(d, k) : jd_comp(d, k);
     unsigned char *pl = planes + F.plane_off;
     long long stride, y0, x0;
+    const uint16_t *qt = kAdobe ? d.qt[c < 3 ? c : 0] : d.qt[c];
     if (c == 0) {
         const int by = d.ncomp == 1 ? my : my * d.vs + k / d.hs, bx = d.ncomp == 1 ? mx : mx * d.hs + k % d.hs;
         if (by >= (d.height + 7) / 8 || bx >= (d.width + 7) / 8) return;     // dummy block of an edge MCU
         stride = F.pw0; y0 = by * 8; x0 = bx * 8;
+    } else if (kAdobe && c == 3) {
+        const aej_jpeg_adobe &x = adobe[f];
+        const int kk = k - d.hs * d.vs - 2;
+        const bool full = x.h3 == d.hs && x.v3 == d.vs;                   // sampled as component 0: its block grid, its dummy blocks
+        const int by = full ? my * d.vs + kk / d.hs : my, bx = full ? mx * d.hs + kk % d.hs : mx;
+        if (full && (by >= (d.height + 7) / 8 || bx >= (d.width + 7) / 8)) return;
+        pl += (long long)F.pw0 * F.ph0 + 2LL * F.pw1 * F.ph1;
+        stride = F.pw3; y0 = by * 8; x0 = bx * 8;
+        qt = x.qt3;
     } else {
         pl += (long long)F.pw0 * F.ph0 + (long long)(c - 1) * F.pw1 * F.ph1;
         stride = F.pw1; y0 = my * 8; x0 = mx * 8;
     }
-    jd_idct_block(coef + idx * 64, d.qt[c], pl + y0 * stride + x0, stride);
+    jd_idct_block(coef + idx * 64, qt, pl + y0 * stride + x0, stride);
+}
+
+__global__ __launch_bounds__(kJdThreads) void k_jd_idct(const JdFile *__restrict__ files, const aej_jpegdec_desc *__restrict__ descs, int n,
+                                                        long long n_blocks, const short *__restrict__ coef, unsigned char *__restrict__ planes)
+{
+    jd_idct_thread<false>(files, descs, n, n_blocks, coef, planes, nullptr);
+}
+
+__global__ __launch_bounds__(kJdThreads) void k_jd_idct4(const JdFile *__restrict__ files, const aej_jpegdec_desc *__restrict__ descs, int n,
+                                                         long long n_blocks, const short *__restrict__ coef, unsigned char *__restrict__ planes,
+                                                         const aej_jpeg_adobe *__restrict__ adobe)
+{
+    jd_idct_thread<true>(files, descs, n, n_blocks, coef, planes, adobe);
+}
+
+// kJdAdobePx consecutive pixels [r0, r1) of a file with kJdAdobe, kCh output channels: the samples of every plane up-sampled by
+// jd_chroma's rules (component 3 sampled as component 0 is read as it is), the colour model's rule, and the bytes stored -- a whole
+// group whose first byte is dword-aligned as kCh dwords, anything else byte by byte
+template <int kCh>
+__device__ __forceinline__ void jd_adobe_group(const JdFile &F, const aej_jpegdec_desc &d, int colour, bool full3, const unsigned char *pl,
+                                               unsigned char *img, long long r0, long long r1)
+{
+    const unsigned char *p1 = pl + (long long)F.pw0 * F.ph0, *p2 = p1 + (long long)F.pw1 * F.ph1, *p3 = p2 + (long long)F.pw1 * F.ph1;
+    const int wc = (d.width + d.hs - 1) / d.hs, hc = (d.height + d.vs - 1) / d.vs;
+    unsigned w[kCh] = {};
+#pragma unroll
+    for (int i = 0; i < kJdAdobePx; i++) {
+        const long long r = r0 + i;
+        if (r >= r1) break;
+        const int y = (int)(r / d.width), x = (int)(r % d.width);
+        int s[4];
+        s[0] = pl[(long long)y * F.pw0 + x];
+        s[1] = jd_chroma(p1, F.pw1, d.hs, d.vs, wc, hc, y, x);
+        s[2] = jd_chroma(p2, F.pw1, d.hs, d.vs, wc, hc, y, x);
+        s[3] = d.ncomp != 4 ? 0 : full3 ? p3[(long long)y * F.pw3 + x] : jd_chroma(p3, F.pw3, d.hs, d.vs, wc, hc, y, x);
+        unsigned char o[4];
+        jd_adobe_pixel(colour, kCh == 4, s, o);
+#pragma unroll
+        for (int c = 0; c < kCh; c++) w[(i * kCh + c) >> 2] |= (unsigned)o[c] << (8 * ((i * kCh + c) & 3));
+    }
+    unsigned char *gp = img + r0 * kCh;
+    if (r1 - r0 == kJdAdobePx && ((uintptr_t)gp & 3) == 0) {
+#pragma unroll
+        for (int c = 0; c < kCh; c++) reinterpret_cast<unsigned *>(gp)[c] = w[c];
+    } else {
+        const int nb = (int)(r1 - r0) * kCh;
+#pragma unroll
+        for (int b = 0; b < kJdAdobePx * kCh; b++) if (b < nb) gp[b] = (unsigned char)(w[b >> 2] >> (8 * (b & 3)));
+    }
+}
+
+// The files with another colour model than YCbCr (JdFile::shift & kJdAdobe; aej_jpeg_adobe::colour RGB, CMYK, YCCK), sample planes ->
+// pixels, in the place of k_jd_rgb.  Workgroup `blockIdx.x` is workgroup g - grpa_base of its file, so the file, its colour model and
+// its output form are the same for the whole workgroup: no lane diverges on them.  Thread t of the file takes the kJdAdobePx
+// consecutive pixels (row-major over the image) from 4 t - lead on, lead in 0..3 chosen so that the group's first output byte is
+// dword-aligned whatever the image's offset in the packed output (three channels; with four the groups start at pixel 0 and are
+// aligned when the image is).  Bounds: only pixels r in [0, width * height) are read and stored, at img + r * channels; the plane
+// reads are jd_chroma's, inside the real samples of each plane.
+__global__ __launch_bounds__(kJdThreads) void k_jd_adobe(const JdFile *__restrict__ files, const aej_jpegdec_desc *__restrict__ descs,
+                                                         const aej_jpeg_adobe *__restrict__ adobe, int n, const unsigned char *__restrict__ planes,
+                                                         unsigned char *__restrict__ out)
+{
+    int lo = 0, hi = n - 1;                           // the last file whose first workgroup is <= blockIdx.x
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (files[mid].grpa_base <= (long long)blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+    const JdFile &F = files[lo];
+    const aej_jpegdec_desc &d = descs[lo];
+    if (!(F.shift & kJdAdobe) || d.hs > 2 || d.vs > 2) return;      // never: the host gives these workgroups to such files alone
+    const int colour = adobe[lo].colour;
+    const bool full3 = adobe[lo].h3 == d.hs && adobe[lo].v3 == d.vs, four = (F.shift & kJdCmyk) != 0;
+    const long long npx = (long long)d.width * d.height;
+    unsigned char *img = out + F.out_off;
+    const int lead = four ? 0 : (4 - (int)((uintptr_t)img & 3)) & 3;      // pixel r of an RGB image starts at a + 3 r = a - r (mod 4)
+    const long long first = (((long long)blockIdx.x - F.grpa_base) * kJdThreads + threadIdx.x) * kJdAdobePx - lead;
+    const long long r0 = max(first, 0LL), r1 = min(first + kJdAdobePx, npx);
+    if (r0 >= r1) return;
+    const unsigned char *pl = planes + F.plane_off;
+    if (four) jd_adobe_group<4>(F, d, colour, full3, pl, img, r0, r1);
+    else jd_adobe_group<3>(F, d, colour, full3, pl, img, r0, r1);
 }
 
 __global__ __launch_bounds__(kJdThreads) void k_jd_rgb(const JdFile *__restrict__ files, const aej_jpegdec_desc *__restrict__ descs, int n,
@@ -704,12 +911,12 @@ __global__ __launch_bounds__(kJdThreads) void k_jd_box(const JdFile *__restrict_
 }
 
 // ---- host: descriptor checks, layout and launch sequence -----------------------------------------------------------------------------------
-bool jpegdec_descs_ok(const aej_jpegdec_desc *d, int n)
+bool jpegdec_descs_ok(const aej_jpegdec_desc *d, int n, const aej_jpeg_adobe *adobe)
 {
     if (!d || n < 1) return false;
     for (int i = 0; i < n; i++) {
         const aej_jpegdec_desc &e = d[i];
-        if (!jpeg_frame_ok(e) || e.scan_length < 0 || e.restart_interval < 0) return false;
+        if (!jpeg_frame_ok(e, adobe ? adobe + i : nullptr) || e.scan_length < 0 || e.restart_interval < 0) return false;
         const long long mcus = (long long)e.mcux * e.mcuy;
         if (e.n_segments != (e.restart_interval ? (mcus + e.restart_interval - 1) / e.restart_interval : 1)) return false;
     }
@@ -731,7 +938,7 @@ void jpeg_stream_layout(long long len, int n_segments, int S, JdFile &F, JdBufSi
     z.slots += F.n_slots;
 }
 
-void jpeg_recon_layout(const aej_jpegdec_desc &d, int shift, JdFile &F, JdBufSizes &z, const int *box, bool window_coef)
+void jpeg_recon_layout(const aej_jpegdec_desc &d, int shift, JdFile &F, JdBufSizes &z, const int *box, bool window_coef, const aej_jpeg_adobe *x)
 {
     const bool luma = (shift & kJdLuma) != 0, boxed = !jpeg_box_whole(d, box);
     F.blk_base = z.blocks;
@@ -754,6 +961,18 @@ void jpeg_recon_layout(const aej_jpegdec_desc &d, int shift, JdFile &F, JdBufSiz
     for (int s = 0; s < 4; s++) F.grpl_base[s] = z.grpl[s];
     F.plane_off = z.planes;
     F.px_base = z.px;
+    F.grpa_base = z.grpa;
+    F.pw3 = F.ph3 = 0;
+    if (jpeg_adobe_new(x)) {                          // four sample planes (three for an RGB-coded file), no pixels of k_jd_rgb's: workgroups of k_jd_adobe
+        F.shift |= kJdAdobe;
+        F.pw0 = d.mcux * 8 * d.hs; F.ph0 = d.mcuy * 8 * d.vs;
+        F.pw1 = d.mcux * 8; F.ph1 = d.mcuy * 8;
+        if (d.ncomp == 4) { F.pw3 = d.mcux * 8 * x->h3; F.ph3 = d.mcuy * 8 * x->v3; }
+        z.planes += align_up((long long)F.pw0 * F.ph0 + 2LL * F.pw1 * F.ph1 + (long long)F.pw3 * F.ph3, 256);
+        const long long groups = ((long long)d.width * d.height + kJdAdobePx - 1) / kJdAdobePx + 1;      // one more: the lead group
+        z.grpa += (groups + kJdThreads - 1) / kJdThreads;
+        return;
+    }
     if (boxed) {                                      // no sample planes, no pixels of k_jd_rgb's, no workgroups but k_jd_box's
         const int hs = d.ncomp == 3 ? d.hs : 1, vs = d.ncomp == 3 ? d.vs : 1, TX = kJdBoxW / (8 * hs), TY = kJdBoxH / (8 * vs);
         F.shift |= kJdBox;
@@ -779,13 +998,22 @@ void jpeg_recon_layout(const aej_jpegdec_desc &d, int shift, JdFile &F, JdBufSiz
     z.px += (long long)d.width * d.height;
 }
 
-void jpegdec_layout(const aej_jpegdec_desc *descs, int n, int S, std::vector<JdFile> &files, JdBufSizes &z, const int *shifts, const int *boxes)
+void jpegdec_layout(const aej_jpegdec_desc *descs, int n, int S, std::vector<JdFile> &files, JdBufSizes &z, const int *shifts, const int *boxes,
+                    const aej_jpeg_adobe *adobe)
 {
     files.assign(n, JdFile{});
     z = JdBufSizes{};
     for (int i = 0; i < n; i++) {
         jpeg_stream_layout(descs[i].scan_length, descs[i].n_segments, S, files[i], z);
-        jpeg_recon_layout(descs[i], shifts ? shifts[i] : 0, files[i], z, boxes ? boxes + 4 * i : nullptr);
+        jpeg_recon_layout(descs[i], shifts ? shifts[i] : 0, files[i], z, boxes ? boxes + 4 * i : nullptr, true, adobe ? adobe + i : nullptr);
+        if (adobe && jpeg_adobe_new(adobe + i)) {     // one DC and one AC table for every component?
+            const aej_jpegdec_desc &d = descs[i];
+            bool same = !memcmp(&d.dc[1], &d.dc[0], sizeof d.dc[0]) && !memcmp(&d.dc[2], &d.dc[0], sizeof d.dc[0]) &&
+                        !memcmp(&d.ac[1], &d.ac[0], sizeof d.ac[0]) && !memcmp(&d.ac[2], &d.ac[0], sizeof d.ac[0]);
+            if (d.ncomp == 4) same = same && !memcmp(&adobe[i].dc3, &d.dc[0], sizeof d.dc[0]) && !memcmp(&adobe[i].ac3, &d.ac[0], sizeof d.ac[0]);
+            files[i].uniform = same;
+            z.uniform += same;
+        }
     }
 }
 
@@ -795,6 +1023,8 @@ unsigned long long jpegdec_carve(void *base, int n, const JdBufSizes &z, JdBufs 
     w.files = (JdFile *)c.take<char>(sizeof(JdFile) * n + sizeof(aej_jpegdec_desc) * n + 16);      // one upload: see JdBufs
     w.descs = base ? (aej_jpegdec_desc *)((char *)w.files + sizeof(JdFile) * n) : nullptr;
     w.last_change = base ? (int *)((char *)w.descs + sizeof(aej_jpegdec_desc) * n) : nullptr;
+    const bool four = z.grpa > 0;                     // a four-component or RGB-coded file: their aej_jpeg_adobe (a second upload), a fourth DC sum per slot
+    w.adobe = four ? c.take<aej_jpeg_adobe>(n) : nullptr;
     w.cnt = c.take<int>(z.chunks * 3);
     w.pre = c.take<long long>(z.chunks * 3);
     w.clean_len = c.take<long long>(n);
@@ -802,10 +1032,10 @@ unsigned long long jpegdec_carve(void *base, int n, const JdBufSizes &z, JdBufs 
     w.clean = c.take<unsigned char>(z.clean);
     w.sl.state = c.take<unsigned long long>(z.slots);
     w.sl.used = c.take<unsigned long long>(z.slots);
-    w.sl.cnt = c.take<int>(z.slots * 4);
+    w.sl.cnt = c.take<int>(z.slots * (four ? 5 : 4));
     w.sl.first = c.take<unsigned char>(z.slots);
     w.sl.blk_pre = c.take<long long>(z.slots);
-    w.sl.dc_pre = c.take<int>(z.slots * 3);
+    w.sl.dc_pre = c.take<int>(z.slots * (four ? 4 : 3));
     w.coef = c.take<short>(z.blocks * 64);
     w.planes = c.take<unsigned char>(z.planes);
     return c.bytes();
@@ -820,8 +1050,13 @@ hipError_t launch_jpegdec_begin(hipStream_t st, int n, const JdBufSizes &z, cons
     hipError_t e = hipMemcpyAsync(w.files, blob_host, blob_bytes, hipMemcpyHostToDevice, st);
     if (e != hipSuccess) return e;
     if ((e = launch_jpegdec_unstuff(st, n, z, w, scans, S, status)) != hipSuccess) return e;
-    hipLaunchKernelGGL(z.grpb > 0 ? k_jd_init<true> : k_jd_init<false>, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.slots,
-                       w.segs, w.clean, w.sl, S, w.last_change);
+    if (z.grpa > 0) {
+        hipLaunchKernelGGL(k_jd_init4, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.slots, w.segs, w.clean, w.sl, S,
+                           w.last_change, w.adobe);
+    } else {
+        hipLaunchKernelGGL(z.grpb > 0 ? k_jd_init<true> : k_jd_init<false>, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n,
+                           z.slots, w.segs, w.clean, w.sl, S, w.last_change);
+    }
     return hipGetLastError();
 }
 
@@ -842,9 +1077,14 @@ hipError_t launch_jpegdec_unstuff(hipStream_t st, int n, const JdBufSizes &z, co
 
 hipError_t launch_jpegdec_sync(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, int S, int first_round, int rounds)
 {
-    for (int r = first_round; r < first_round + rounds; r++)
-        hipLaunchKernelGGL(z.grpb > 0 ? k_jd_sync<true> : k_jd_sync<false>, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.slots,
-                           w.segs, w.clean, w.sl, S, r, w.last_change);
+    for (int r = first_round; r < first_round + rounds; r++) {
+        if (z.grpa > 0)
+            hipLaunchKernelGGL(k_jd_sync4, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.slots, w.segs, w.clean, w.sl, S, r,
+                               w.last_change, w.adobe);
+        else
+            hipLaunchKernelGGL(z.grpb > 0 ? k_jd_sync<true> : k_jd_sync<false>, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n,
+                               z.slots, w.segs, w.clean, w.sl, S, r, w.last_change);
+    }
     return hipGetLastError();
 }
 
@@ -853,6 +1093,16 @@ hipError_t launch_jpegdec_write(hipStream_t st, int n, const JdBufSizes &z, cons
 {
     hipError_t e = hipMemsetAsync(w.coef, 0, (size_t)z.blocks * 128, st);
     if (e != hipSuccess) return e;
+    if (z.grpa > 0) {
+        hipLaunchKernelGGL(k_jd_scan_slots4, dim3(n), dim3(kJdScanThreads), 0, st, w.files, w.sl);
+        if (z.uniform > 0) {                          // files whose bits do not tell the block slot: DC sums again under the slots the block counts give
+            hipLaunchKernelGGL(k_jd_fix4, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.slots, w.segs, w.clean, w.sl, S, w.adobe);
+            hipLaunchKernelGGL(k_jd_scan_slots4, dim3(n), dim3(kJdScanThreads), 0, st, w.files, w.sl);
+        }
+        hipLaunchKernelGGL(k_jd_write4, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.slots, w.segs, w.clean, w.sl, S, w.coef,
+                           status, w.adobe);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(k_jd_scan_slots, dim3(n), dim3(kJdScanThreads), 0, st, w.files, w.sl);
     hipLaunchKernelGGL(z.grpb > 0 ? k_jd_write<true> : k_jd_write<false>, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.slots,
                        w.segs, w.clean, w.sl, S, w.coef, status);
@@ -882,6 +1132,10 @@ static hipError_t launch_jpegdec_recon_scaled(hipStream_t st, int n, const JdBuf
     if (z.grpl[2] > 0) hipLaunchKernelGGL(k_jd_luma<2>, dim3((unsigned)z.grpl[2]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
     if (z.grpl[3] > 0) hipLaunchKernelGGL(k_jd_luma<3>, dim3((unsigned)z.grpl[3]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
     if (z.grpb > 0) hipLaunchKernelGGL(k_jd_box, dim3((unsigned)z.grpb), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
+    if (z.grpa > 0) {                                 // the four-component and RGB-coded files: four sample planes, then their pixels
+        hipLaunchKernelGGL(k_jd_idct4, dim3(jd_grid(z.blocks)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.blocks, w.coef, w.planes, w.adobe);
+        hipLaunchKernelGGL(k_jd_adobe, dim3((unsigned)z.grpa), dim3(kJdThreads), 0, st, w.files, w.descs, w.adobe, n, w.planes, out);
+    }
     return hipGetLastError();
 }
 

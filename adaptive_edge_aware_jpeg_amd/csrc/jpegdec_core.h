@@ -14,6 +14,9 @@ constexpr int kJdChunk = 64;           // bytes per un-stuffing chunk
 constexpr int kJdSyncBatch = 4;        // sync rounds launched between two read-backs of the "changed" word
 constexpr int kJdLuma = 4;             // added to log2 of a file's scale: the luma plane alone, [oh][ow] (JdFile::shift)
 constexpr int kJdBox = 8;              // added to a full-size file's shift: only a box of it is reconstructed (k_jd_box; JdFile::box, ::win)
+constexpr int kJdAdobe = 16;           // a four-component or RGB-coded file (aej_jpeg_adobe::colour): k_jd_idct<true> and k_jd_adobe alone reconstruct it
+constexpr int kJdCmyk = 32;            // with kJdAdobe: the image leaves with four channels (Pillow's mode "CMYK"), not as RGB
+constexpr int kJdAdobePx = 4;          // pixels one thread of k_jd_adobe reconstructs: 12 or 16 output bytes, whole dwords
 constexpr int kJdBoxW = 128, kJdBoxH = 32;      // pixels of one tile of k_jd_box: a whole number of MCUs of every layout
 
 // per-file layout of one aej_jpegdec_batch (host-computed, uploaded with the descriptors)
@@ -39,6 +42,11 @@ struct JdFile {
     int win[4];                        // its MCU window mx0, my0, mx1, my1 (jd_box_window): the MCUs whose blocks the box's pixels read
     int row0;                          // first MCU row whose coefficients are stored (win[1] for a baseline file, 0 for a progressive
                                        // one): block b of MCU (my, mx) is blk_base + ((my - row0) * mcux + mx) * blocks_per_mcu + b
+    long long grpa_base;               // first workgroup of the file in k_jd_adobe's grid (shift & kJdAdobe)
+    int pw3, ph3;                      // such a file's fourth plane (whole MCUs; behind the three others), 0 x 0 for three components
+    int uniform;                       // such a baseline file whose components all decode under one DC and one AC table (what libjpeg writes
+                                       // for CMYK and RGB): its bits say nothing about the block slot, which the kFour kernels then take from
+                                       // the block counts instead of the predecessor's state (k_jd_sync4, k_jd_fix4, k_jd_write4)
 };
 
 // one restart segment: written by the un-stuffing scatter (start) and k_jd_segments (the rest)
@@ -51,22 +59,26 @@ struct JdSeg {
 
 struct JdSlots {
     unsigned long long *state, *used;     // exit state; the entry state it was decoded from
-    int *cnt;                             // [slot][4]: blocks started, DC sums of components 0..2
+    int *cnt;                             // [slot][4]: blocks started, DC sums of components 0..2 (a kFour call: [slot][5], components 0..3)
     unsigned char *first;                 // the slot starts a segment
     long long *blk_pre;                   // exclusive prefix of blocks started within the segment
-    int *dc_pre;                          // [slot][3]
+    int *dc_pre;                          // [slot][3] (a kFour call: [slot][4])
 };
 
 // decoder state at a symbol boundary, packed in one 64-bit word (so that a successor reads it whole):
 // bits 0..5 zigzag index, 6..8 block slot in the MCU, 9 "no state" (the decode that would produce it stopped on an error), 10.. bit offset
+// kFour (a call with a four-component file, whose MCU has up to 10 blocks): the block slot takes bits 6..9, the others move up one
+template <bool kFour = false>
 AEJ_HD inline unsigned long long jd_pack(long long pos, int k, int z, int err)
 {
-    return ((unsigned long long)pos << 10) | ((unsigned long long)(err & 1) << 9) | ((unsigned long long)(k & 7) << 6) | (unsigned long long)(z & 63);
+    constexpr int kb = kFour ? 4 : 3;
+    return ((unsigned long long)pos << (7 + kb)) | ((unsigned long long)(err & 1) << (6 + kb)) | ((unsigned long long)(k & ((1 << kb) - 1)) << 6) |
+           (unsigned long long)(z & 63);
 }
-AEJ_HD inline long long jd_pos(unsigned long long s) { return (long long)(s >> 10); }
-AEJ_HD inline int jd_k(unsigned long long s) { return (int)((s >> 6) & 7); }
+template <bool kFour = false> AEJ_HD inline long long jd_pos(unsigned long long s) { return (long long)(s >> (kFour ? 11 : 10)); }
+template <bool kFour = false> AEJ_HD inline int jd_k(unsigned long long s) { return (int)((s >> 6) & (kFour ? 15 : 7)); }
 AEJ_HD inline int jd_z(unsigned long long s) { return (int)(s & 63); }
-AEJ_HD inline int jd_err(unsigned long long s) { return (int)((s >> 9) & 1); }
+template <bool kFour = false> AEJ_HD inline int jd_err(unsigned long long s) { return (int)((s >> (kFour ? 10 : 9)) & 1); }
 
 // big-endian bit window over a 4-byte-aligned byte stream
 struct JdBits {
@@ -103,6 +115,9 @@ AEJ_HD inline int jd_natural(int z) { return kZigzag8.natural[z]; }
 
 AEJ_HD inline int jd_comp(const aej_jpegdec_desc &d, int k) { return d.ncomp == 1 ? 0 : (k < d.hs * d.vs ? 0 : k - d.hs * d.vs + 1); }
 
+// the same in a kFour call, for every file of it: component 3's blocks follow the MCU's others (one component: hs = vs = 1, k = 0)
+AEJ_HD inline int jd_comp4(const aej_jpegdec_desc &d, int k) { const int n0 = d.hs * d.vs; return k < n0 ? 0 : k - n0 < 2 ? k - n0 + 1 : 3; }
+
 enum { kJdRunStop = 0, kJdRunOutOfBits = 1, kJdRunBadCode = 2, kJdRunPast63 = 3, kJdRunBadDc = 4, kJdRunDone = 5 };
 
 // Decode symbols from state (pos, k, z) while pos < stop; no symbol may end past seg_end.  Counts the blocks started and sums their
@@ -111,15 +126,19 @@ enum { kJdRunStop = 0, kJdRunOutOfBits = 1, kJdRunBadCode = 2, kJdRunPast63 = 3,
 // kWin (a boxed file): only blocks [win_lo, seg_blocks) of the segment are stored -- seg_blocks being where the file's coefficient window
 // ends in the segment -- while the DC predictions are still tracked through the blocks before win_lo; kJdRunDone once block
 // seg_blocks - 1 is complete.  coef + b * 64 is only formed for win_lo <= b < seg_blocks.
-template <bool kWrite, bool kWin = false>
+// dc and pred have one entry per component the call can meet: three, or with kFour (a call with a four-component file) four, and
+// component 3 then decodes under x's tables (x: the file's
+// aej_jpeg_adobe, only read for a block of component 3).
+template <bool kWrite, bool kWin = false, bool kFour = false>
 AEJ_HD inline int jd_run(const aej_jpegdec_desc &d, JdBits &br, long long &pos, int &k, int &z, long long stop, long long seg_end,
-                         int &nstart, int dc[3], short *coef, long long &next, long long seg_blocks, int pred[3], long long win_lo = 0)
+                         int &nstart, int *dc, short *coef, long long &next, long long seg_blocks, int *pred, long long win_lo = 0,
+                         const aej_jpeg_adobe *x = nullptr)
 {
     const int bpm = d.blocks_per_mcu;
     while (pos < stop) {
         if (kWrite && z == 0 && next >= seg_blocks) return kJdRunDone;
-        const int c = jd_comp(d, k);
-        const aej_jpegdec_huff &h = z == 0 ? d.dc[c] : d.ac[c];
+        const int c = kFour ? jd_comp4(d, k) : jd_comp(d, k);
+        const aej_jpegdec_huff &h = kFour && c == 3 ? (z == 0 ? x->dc3 : x->ac3) : z == 0 ? d.dc[c] : d.ac[c];
         const unsigned win = br.peek32(pos);
         int len, sym;
         if (!jd_huff(h, win, len, sym)) return kJdRunBadCode;
@@ -393,6 +412,40 @@ AEJ_HD inline void jd_rgb(int Y, int cb, int cr, unsigned char *o)
     o[0] = (unsigned char)(R < 0 ? 0 : R > 255 ? 255 : R);
     o[1] = (unsigned char)(G < 0 ? 0 : G > 255 ? 255 : G);
     o[2] = (unsigned char)(B < 0 ? 0 : B > 255 ? 255 : B);
+}
+
+// ---- the colour models that are not YCbCr (aej_jpeg_adobe::colour), per pixel, as Pillow returns them -------------------------------------
+// s: the pixel's four samples after up-sampling -> Pillow's mode "CMYK" pixel.  CMYK: Pillow unpacks every four-component file as
+// "CMYK;I", 255 - sample.  YCCK: libjpeg's ycck_cmyk_convert (255 - R, 255 - G, 255 - B of its YCbCr -> RGB, K as it is) and then that
+// inversion: R, G, B and 255 - K.
+AEJ_HD inline void jd_cmyk_pixel(const int *s, unsigned char *o)
+{
+    for (int c = 0; c < 4; c++) o[c] = (unsigned char)(255 - s[c]);
+}
+AEJ_HD inline void jd_ycck_pixel(const int *s, unsigned char *o)
+{
+    jd_rgb(s[0], s[1], s[2], o);
+    o[3] = (unsigned char)(255 - s[3]);
+}
+// Pillow's MULDIV255 and its cmyk2rgb (Convert.c): a mode "CMYK" pixel -> RGB, in integers
+AEJ_HD inline int jd_muldiv255(int a, int b) { const int t = a * b + 128; return ((t >> 8) + t) >> 8; }
+AEJ_HD inline void jd_cmyk_rgb(const unsigned char *cmyk, unsigned char *o)
+{
+    const int nk = 255 - cmyk[3];
+    for (int c = 0; c < 3; c++) {
+        const int v = nk - jd_muldiv255(cmyk[c], nk);
+        o[c] = (unsigned char)(v < 0 ? 0 : v > 255 ? 255 : v);
+    }
+}
+// one pixel of a file with colour AEJ_JPEG_RGB / _CMYK / _YCCK from its samples s[0..3] (three components: s[3] unused): o gets 4
+// channels when cmyk_out (four-component files alone), else 3
+AEJ_HD inline void jd_adobe_pixel(int colour, bool cmyk_out, const int *s, unsigned char *o)
+{
+    if (colour == AEJ_JPEG_RGB) { o[0] = (unsigned char)s[0]; o[1] = (unsigned char)s[1]; o[2] = (unsigned char)s[2]; return; }
+    unsigned char p[4];
+    if (colour == AEJ_JPEG_YCCK) jd_ycck_pixel(s, p); else jd_cmyk_pixel(s, p);
+    if (cmyk_out) { o[0] = p[0]; o[1] = p[1]; o[2] = p[2]; o[3] = p[3]; }
+    else jd_cmyk_rgb(p, o);
 }
 
 // un-stuffing: what byte p of a scan is (the neighbours decide: a run of 0xFF followed by 0x00 is one data 0xFF)

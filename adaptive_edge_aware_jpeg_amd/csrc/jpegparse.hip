@@ -57,8 +57,8 @@ namespace {
 enum { kJpgSegment, kJpgEOI, kJpgEndOfFile, kJpgStrayBytes, kJpgEndInMarker };      // JpgParse::next; a refusal is its negative AEJ_ERR_*
 
 struct JpScript {                      // what the scans so far have done to each (component, coefficient) cell; -1: nothing yet
-    int coef_al[3][64], cell_level[3][64];
-    bool qlatched[3] = {};
+    int coef_al[4][64], cell_level[4][64];
+    bool qlatched[4] = {};
     JpScript() { memset(coef_al, -1, sizeof coef_al); memset(cell_level, -1, sizeof cell_level); }
 };
 
@@ -83,6 +83,8 @@ struct JpgParse {
     bool sof = false;
     int nf = 0;                        // components the frame header lists
     bool allow440 = false;             // the caller takes luma sampled 1 x 2 over 1 x 1 chroma (4:4:0) too: the _440 entries
+    bool allow_adobe = false;          // the caller takes four components and RGB-coded files too (the _adobe entries): x says what the file is
+    aej_jpeg_adobe x = {};
 
     JpgParse(const unsigned char *data, unsigned long long bytes, std::string &m_) : b(data), n(bytes), msg(m_) {}
     int bad(const std::string &t) { msg = t; return (int)AEJ_ERR_ARG; }
@@ -125,7 +127,7 @@ struct JpgParse {
         if (len != 6u + 3u * nf) return bad("SOF length does not match its component count");
         if (f.height == 0) return unsup("DNL (height defined after the scan)");
         if (f.width == 0) return bad("zero image width");
-        if (nf != 1 && nf != 3) return unsup(std::to_string(nf) + " components (only 1 or 3)");
+        if (nf != 1 && nf != 3 && !(allow_adobe && nf == 4)) return unsup(std::to_string(nf) + " components (only 1 or 3)");
         for (int i = 0; i < nf; i++) {
             f.comp_id[i] = s[6 + 3 * i];
             f.comp_h[i] = s[7 + 3 * i] >> 4;
@@ -226,13 +228,26 @@ struct JpgParse {
         }
     }
 
-    // three components are YCbCr unless the file says RGB
+    // three components are YCbCr unless the file says RGB; four (allow_adobe alone) are CMYK unless APP14 says YCCK: libjpeg's
+    // default_decompress_parms.  With allow_adobe the two RGB refusals become x.colour.
     int colour_rule()
     {
+        if (nf == 4) {
+            if (adobe && adobe_transform != 0 && adobe_transform != 2)
+                return unsup("Adobe APP14 transform " + std::to_string(adobe_transform) + " in a four-component file (libjpeg reads it as YCCK with a warning)");
+            x.colour = adobe && adobe_transform == 2 ? AEJ_JPEG_YCCK : AEJ_JPEG_CMYK;
+            return 0;
+        }
         if (nf != 3) return 0;
         const bool rgb_ids = f.comp_id[0] == 'R' && f.comp_id[1] == 'G' && f.comp_id[2] == 'B';
-        if (!jfif && adobe && adobe_transform == 0) return unsup("Adobe APP14 transform 0 (RGB colour)");
-        if (!jfif && !adobe && rgb_ids) return unsup("component ids 'R','G','B' without JFIF (RGB colour)");
+        if (!jfif && adobe && adobe_transform == 0) {
+            if (!allow_adobe) return unsup("Adobe APP14 transform 0 (RGB colour)");
+            x.colour = AEJ_JPEG_RGB;
+        }
+        if (!jfif && !adobe && rgb_ids) {
+            if (!allow_adobe) return unsup("component ids 'R','G','B' without JFIF (RGB colour)");
+            x.colour = AEJ_JPEG_RGB;
+        }
         return 0;
     }
 
@@ -240,14 +255,17 @@ struct JpgParse {
     // the MCU grid
     int sampling()
     {
-        if (nf == 3) {
-            const int h0 = f.comp_h[0], v0 = f.comp_v[0];
+        if (nf == 3 || nf == 4) {
+            const int h0 = f.comp_h[0], v0 = f.comp_v[0], h3 = f.comp_h[3], v3 = f.comp_v[3];
             if (f.comp_h[1] != 1 || f.comp_v[1] != 1 || f.comp_h[2] != 1 || f.comp_v[2] != 1 ||
-                !((h0 == 1 && v0 == 1) || (h0 == 2 && v0 == 1) || (h0 == 2 && v0 == 2) || (allow440 && h0 == 1 && v0 == 2)))
+                !((h0 == 1 && v0 == 1) || (h0 == 2 && v0 == 1) || (h0 == 2 && v0 == 2) || (allow440 && h0 == 1 && v0 == 2)) ||
+                (nf == 4 && !((h3 == h0 && v3 == v0) || (h3 == 1 && v3 == 1))))      // component 3: component 0's factors, or 1 x 1
                 return unsup("sampling factors " + std::to_string(h0) + "x" + std::to_string(v0) + "," + std::to_string(f.comp_h[1]) + "x" +
-                             std::to_string(f.comp_v[1]) + "," + std::to_string(f.comp_h[2]) + "x" + std::to_string(f.comp_v[2]));
+                             std::to_string(f.comp_v[1]) + "," + std::to_string(f.comp_h[2]) + "x" + std::to_string(f.comp_v[2]) +
+                             (nf == 4 ? "," + std::to_string(h3) + "x" + std::to_string(v3) : std::string()));
             f.hs = h0; f.vs = v0;
             f.blocks_per_mcu = h0 * v0 + 2;
+            if (nf == 4) { x.h3 = h3; x.v3 = v3; x.tq3 = f.comp_tq[3]; f.blocks_per_mcu += h3 * v3; }
         } else {
             f.hs = f.vs = 1;
             f.blocks_per_mcu = 1;
@@ -258,9 +276,9 @@ struct JpgParse {
     }
 
     int undefined_qt(int c) { return bad("undefined quantisation table " + std::to_string(f.comp_tq[c])); }
-    void latch_qt(int c)               // component c takes the table its frame entry names, as it stands now
+    void latch_qt(int c)               // component c takes the table its frame entry names, as it stands now (component 3: in x)
     {
-        memcpy(f.qt[c], qt[f.comp_tq[c]], sizeof f.qt[c]);
+        memcpy(c == 3 ? x.qt3 : f.qt[c], qt[f.comp_tq[c]], sizeof f.qt[0]);
         f.precision16 |= q16[f.comp_tq[c]];
     }
 
@@ -297,8 +315,8 @@ struct JpgParse {
             if (!qdef[f.comp_tq[i]]) return undefined_qt(i);
             if (td > 3 || ta > 3 || !huff[0][td].defined || !huff[1][ta].defined) return bad("undefined Huffman table");
             latch_qt(i);
-            jd_build_huff(huff[0][td], d.dc[i]);
-            jd_build_huff(huff[1][ta], d.ac[i]);
+            jd_build_huff(huff[0][td], i == 3 ? x.dc3 : d.dc[i]);
+            jd_build_huff(huff[1][ta], i == 3 ? x.ac3 : d.ac[i]);
         }
         const long long mcus = (long long)f.mcux * f.mcuy;
         d.restart_interval = ri;
@@ -360,7 +378,7 @@ struct JpgParse {
             }
             if (sc.ss == 0 && sc.ah == 0) {
                 if (!huff[0][sc.td[i]].defined) return bad(at + "undefined Huffman table");
-                jd_build_huff(huff[0][sc.td[i]], sc.dc[i]);
+                jd_build_huff(huff[0][sc.td[i]], i == 3 ? x.dc3 : sc.dc[i]);
             }
             if (sc.ss > 0) {
                 if (!huff[1][sc.ta[i]].defined) return bad(at + "undefined Huffman table");
@@ -372,7 +390,7 @@ struct JpgParse {
         sc.level = level;
         f.n_levels = std::max(f.n_levels, level + 1);
         sc.restart_interval = ri;
-        jp_scan_units(f, ns, sc.comp[0], sc.units_x, sc.units_y);
+        jp_scan_units(f, ns, sc.comp[0], sc.units_x, sc.units_y, &x);
         const long long units = (long long)sc.units_x * sc.units_y;
         sc.n_segments = ri ? (int)((units + ri - 1) / ri) : 1;
         unsigned long long q = end;
@@ -420,24 +438,28 @@ struct JpgParse {
 
 }  // namespace
 
-int jpegdec_parse(const unsigned char *b, unsigned long long n, aej_jpegdec_desc &d, std::string &msg, bool allow440)
+int jpegdec_parse(const unsigned char *b, unsigned long long n, aej_jpegdec_desc &d, std::string &msg, bool allow440, aej_jpeg_adobe *adobe)
 {
     memset(&d, 0, sizeof d);
     JpgParse P(b, n, msg);
     P.allow440 = allow440;
+    P.allow_adobe = adobe != nullptr;
     const int rc = P.baseline(d);
     P.store(d);
+    if (adobe) *adobe = P.x;
     return rc;
 }
 
 int jpegprog_parse(const unsigned char *b, unsigned long long n, aej_jpegprog_frame &f, std::vector<aej_jpegprog_scan> &scans, std::string &msg,
-                   bool allow440)
+                   bool allow440, aej_jpeg_adobe *adobe)
 {
     scans.clear();
     JpgParse P(b, n, msg);
     P.allow440 = allow440;
+    P.allow_adobe = adobe != nullptr;
     const int rc = P.progressive(scans);
     f = P.f;
+    if (adobe) *adobe = P.x;
     return rc;
 }
 

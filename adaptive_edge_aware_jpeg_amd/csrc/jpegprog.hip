@@ -23,18 +23,25 @@ namespace aej {
 
 constexpr int kJpUnstuffS = 1 << 20;      // the un-stuffing kernels size subsequence slots nobody uses here; one per MiB keeps them few
 
-__global__ __launch_bounds__(kJpItem) void k_jp_level(const JpScan *__restrict__ scans, const JdFile *__restrict__ sfiles,
-                                                      const aej_jpegdec_desc *__restrict__ sdescs, const JpItem *__restrict__ items,
-                                                      const JdSeg *__restrict__ segs, const unsigned char *__restrict__ clean,
-                                                      short *__restrict__ coef, int *__restrict__ sstatus)
+// kFour: k_jp_level4, which a call with a four-component or RGB-coded file runs for all of its files: a fourth table slot in LDS for an
+// interleaved DC scan of four components (fadobe[file].dc3), a fourth DC predictor, component 3's blocks in jp_slot
+template <bool kFour>
+__device__ __forceinline__ void jp_level(const JpScan *__restrict__ scans, const JdFile *__restrict__ sfiles,
+                                         const aej_jpegdec_desc *__restrict__ sdescs, const JpItem *__restrict__ items,
+                                         const JdSeg *__restrict__ segs, const unsigned char *__restrict__ clean,
+                                         short *__restrict__ coef, int *__restrict__ sstatus, aej_jpegdec_huff *tab,
+                                         const aej_jpeg_adobe *__restrict__ fadobe)
 {
-    __shared__ aej_jpegdec_huff tab[3];
     const JpItem it = items[blockIdx.x];
     const JpScan sc = scans[it.scan];
     const int ntab = sc.kind == kJpDcFirst ? min(sc.ncomp, 3) : sc.kind == kJpDcRefine ? 0 : 1;
     const unsigned *src = reinterpret_cast<const unsigned *>(sc.kind == kJpDcFirst ? sdescs[it.scan].dc : sdescs[it.scan].ac);
     unsigned *dst = reinterpret_cast<unsigned *>(tab);
     for (int i = threadIdx.x; i < ntab * (int)(sizeof(aej_jpegdec_huff) / 4); i += kJpItem) dst[i] = src[i];
+    if (kFour && sc.kind == kJpDcFirst && sc.ncomp == 4) {
+        const unsigned *src3 = reinterpret_cast<const unsigned *>(&fadobe[sc.file].dc3);
+        for (int i = threadIdx.x; i < (int)(sizeof(aej_jpegdec_huff) / 4); i += kJpItem) dst[3 * (sizeof(aej_jpegdec_huff) / 4) + i] = src3[i];
+    }
     __syncthreads();
     const unsigned char *cl = clean + sfiles[it.scan].clean_off;
     short *c = coef + sc.blk_base * 64;
@@ -45,7 +52,7 @@ __global__ __launch_bounds__(kJpItem) void k_jp_level(const JpScan *__restrict__
         if (u >= units) return;
         const long long g = sc.restart_interval ? u / sc.restart_interval : 0;
         if (g >= sc.n_segments) return;
-        rc = jp_dc_refine_unit(sc, cl, segs[sc.seg_base + g], u, c);
+        rc = jp_dc_refine_unit<kFour>(sc, cl, segs[sc.seg_base + g], u, c);
     } else {
         const long long g = (long long)it.first + threadIdx.x;
         if (g >= sc.n_segments) return;
@@ -53,10 +60,28 @@ __global__ __launch_bounds__(kJpItem) void k_jp_level(const JpScan *__restrict__
         const long long u0 = min((long long)sg.first_mcu, units);
         const int nu = (int)min((long long)sg.n_mcu, units - u0);
         JpBits b(cl, sg.start * 8, (sg.start + sg.nbytes) * 8);
-        rc = sc.kind == kJpDcFirst ? jp_dc_first(sc, tab, b, u0, nu, c)
-           : sc.kind == kJpAcFirst ? jp_ac_first(sc, tab[0], b, u0, nu, c) : jp_ac_refine(sc, tab[0], b, u0, nu, c);
+        rc = sc.kind == kJpDcFirst ? jp_dc_first<kFour>(sc, tab, b, u0, nu, c)
+           : sc.kind == kJpAcFirst ? jp_ac_first<kFour>(sc, tab[0], b, u0, nu, c) : jp_ac_refine<kFour>(sc, tab[0], b, u0, nu, c);
     }
     if (rc != kJdRunStop) atomicCAS(sstatus + it.scan, 0, jp_status(rc));
+}
+
+__global__ __launch_bounds__(kJpItem) void k_jp_level(const JpScan *__restrict__ scans, const JdFile *__restrict__ sfiles,
+                                                      const aej_jpegdec_desc *__restrict__ sdescs, const JpItem *__restrict__ items,
+                                                      const JdSeg *__restrict__ segs, const unsigned char *__restrict__ clean,
+                                                      short *__restrict__ coef, int *__restrict__ sstatus)
+{
+    __shared__ aej_jpegdec_huff tab[3];
+    jp_level<false>(scans, sfiles, sdescs, items, segs, clean, coef, sstatus, tab, nullptr);
+}
+
+__global__ __launch_bounds__(kJpItem) void k_jp_level4(const JpScan *__restrict__ scans, const JdFile *__restrict__ sfiles,
+                                                       const aej_jpegdec_desc *__restrict__ sdescs, const JpItem *__restrict__ items,
+                                                       const JdSeg *__restrict__ segs, const unsigned char *__restrict__ clean,
+                                                       short *__restrict__ coef, int *__restrict__ sstatus, const aej_jpeg_adobe *__restrict__ fadobe)
+{
+    __shared__ aej_jpegdec_huff tab[4];
+    jp_level<true>(scans, sfiles, sdescs, items, segs, clean, coef, sstatus, tab, fadobe);
 }
 
 __global__ __launch_bounds__(256) void k_jp_status(const JpScan *__restrict__ scans, int ns, const int *__restrict__ sstatus, int *__restrict__ status)
@@ -69,7 +94,8 @@ __global__ __launch_bounds__(256) void k_jp_status(const JpScan *__restrict__ sc
 
 // ---- host: validation, layout, launch sequence -----------------------------------------------------------------------------------------
 // Everything the kernels index with is recomputed or checked here; the dependency levels are derived again rather than trusted.
-bool jpegprog_layout(const aej_jpegprog_frame *frames, const aej_jpegprog_scan *scans_in, int n, JpLayout &y, const int *shifts, const int *boxes)
+bool jpegprog_layout(const aej_jpegprog_frame *frames, const aej_jpegprog_scan *scans_in, int n, JpLayout &y, const int *shifts, const int *boxes,
+                     const aej_jpeg_adobe *adobe)
 {
     y = JpLayout{};
     if (!frames || !scans_in || n < 1) return false;
@@ -80,15 +106,16 @@ bool jpegprog_layout(const aej_jpegprog_frame *frames, const aej_jpegprog_scan *
     long long s0 = 0;
     for (int i = 0; i < n; i++) {
         const aej_jpegprog_frame &f = frames[i];
-        if (!jpeg_frame_ok(f) || f.n_scans < 1 || f.n_scans > 4096) return false;
+        const aej_jpeg_adobe *x = adobe ? adobe + i : nullptr;
+        if (!jpeg_frame_ok(f, x) || f.n_scans < 1 || f.n_scans > 4096) return false;
         aej_jpegdec_desc &d = y.fdescs[i];
         memset(&d, 0, sizeof d);
         d.width = f.width; d.height = f.height; d.ncomp = f.ncomp; d.hs = f.hs; d.vs = f.vs; d.mcux = f.mcux; d.mcuy = f.mcuy;
         d.blocks_per_mcu = f.blocks_per_mcu; d.n_segments = 1; d.sof = f.sof; d.precision16 = f.precision16;
         memcpy(d.qt, f.qt, sizeof d.qt);
-        jpeg_recon_layout(d, shifts ? shifts[i] : 0, y.ffiles[i], y.fz, boxes ? boxes + 4 * i : nullptr, false);      // a boxed file: all coefficients, k_jd_box
-        int cell_level[3][64];
-        for (int c = 0; c < 3; c++) for (int k = 0; k < 64; k++) cell_level[c][k] = -1;
+        jpeg_recon_layout(d, shifts ? shifts[i] : 0, y.ffiles[i], y.fz, boxes ? boxes + 4 * i : nullptr, false, x);      // a boxed file: all coefficients, k_jd_box
+        int cell_level[4][64];
+        for (int c = 0; c < 4; c++) for (int k = 0; k < 64; k++) cell_level[c][k] = -1;
         for (int j = 0; j < f.n_scans; j++) {
             const aej_jpegprog_scan &s = scans_in[s0 + j];
             if (s.ncomp < 1 || s.ncomp > f.ncomp || (s.ncomp > 1 && s.ncomp != f.ncomp)) return false;
@@ -97,7 +124,7 @@ bool jpegprog_layout(const aej_jpegprog_frame *frames, const aej_jpegprog_scan *
             if (s.ss < 0 || s.ss > s.se || s.se > 63 || (s.ss == 0 && s.se != 0) || (s.ss > 0 && s.ncomp != 1)) return false;
             if (s.al < 0 || s.al > 13 || s.ah < 0 || s.ah > 14 || s.restart_interval < 0 || s.data_length < 0) return false;
             int ux, uy;
-            jp_scan_units(f, s.ncomp, s.comp[0], ux, uy);
+            jp_scan_units(f, s.ncomp, s.comp[0], ux, uy, x);
             const long long units = (long long)ux * uy;
             if (s.units_x != ux || s.units_y != uy) return false;
             if (s.n_segments != (s.restart_interval ? (units + s.restart_interval - 1) / s.restart_interval : 1)) return false;
@@ -140,11 +167,13 @@ bool jpegprog_layout(const aej_jpegprog_frame *frames, const aej_jpegprog_scan *
         o.restart_interval = s.restart_interval; o.n_segments = s.n_segments;
         o.seg_base = F.seg_base;
         o.blk_base = y.ffiles[o.file].blk_base; o.n_blocks = y.ffiles[o.file].n_blocks;
+        o.h3 = adobe && f.ncomp == 4 ? adobe[o.file].h3 : 0; o.v3 = adobe && f.ncomp == 4 ? adobe[o.file].v3 : 0;
         const long long work = o.kind == kJpDcRefine ? (long long)s.units_x * s.units_y : s.n_segments;
         for (long long first = 0; first < work; first += kJpItem) y.items.push_back(JpItem{ t, (int)first });
         y.level_items[o.level + 1] = (long long)y.items.size();
     }
     for (int l = 1; l <= y.n_levels; l++) y.level_items[l] = std::max(y.level_items[l], y.level_items[l - 1]);
+    if (y.fz.grpa > 0) y.fadobe.assign(adobe, adobe + n);      // a call with a four-component or RGB-coded file: uploaded with the rest
     return true;
 }
 
@@ -160,6 +189,8 @@ unsigned long long jpegprog_carve(void *base, const JpLayout &y, JpBufs &w)
     w.items = b.take<JpItem>(y.items.size());
     w.f.files = b.take<JdFile>(nf);
     w.f.descs = b.take<aej_jpegdec_desc>(nf);
+    w.f.adobe = y.fadobe.empty() ? nullptr : b.take<aej_jpeg_adobe>(nf);
+    w.s.adobe = nullptr;
     w.s.cnt = c.take<int>(y.sz.chunks * 3);
     w.s.pre = c.take<long long>(y.sz.chunks * 3);
     w.s.clean_len = c.take<long long>(ns);
@@ -185,6 +216,7 @@ unsigned long long jpegprog_blob(const JpLayout &y, std::vector<unsigned char> *
     put(y.items.data(), sizeof(JpItem) * y.items.size());
     put(y.ffiles.data(), sizeof(JdFile) * y.ffiles.size());
     put(y.fdescs.data(), sizeof(aej_jpegdec_desc) * y.fdescs.size());
+    if (!y.fadobe.empty()) put(y.fadobe.data(), sizeof(aej_jpeg_adobe) * y.fadobe.size());
     return off;
 }
 
@@ -200,7 +232,10 @@ hipError_t launch_jpegprog_entropy(hipStream_t st, const JpLayout &y, const JpBu
     if ((e = launch_jpegdec_unstuff(st, ns, y.sz, w.s, data, kJpUnstuffS, w.sstatus)) != hipSuccess) return e;
     for (int l = 0; l < std::min(n_levels, y.n_levels); l++) {
         const long long lo = y.level_items[l], hi = y.level_items[l + 1];
-        if (hi > lo)
+        if (hi > lo && y.fz.grpa > 0)
+            hipLaunchKernelGGL(k_jp_level4, dim3((unsigned)(hi - lo)), dim3(kJpItem), 0, st, w.scans, w.s.files, w.s.descs, w.items + lo, w.s.segs,
+                               w.s.clean, w.f.coef, w.sstatus, w.f.adobe);
+        else if (hi > lo)
             hipLaunchKernelGGL(k_jp_level, dim3((unsigned)(hi - lo)), dim3(kJpItem), 0, st, w.scans, w.s.files, w.s.descs, w.items + lo, w.s.segs,
                                w.s.clean, w.f.coef, w.sstatus);
     }

@@ -20,6 +20,7 @@ struct JpScan {
     int restart_interval, n_segments;
     long long seg_base;                // first restart segment (global index)
     long long blk_base, n_blocks;      // the file's coefficient blocks, MCU order
+    int h3, v3;                        // component 3's sampling factors (aej_jpeg_adobe), 0 unless the file has four components
 };
 
 struct JpItem { int scan, first; };    // a workgroup's share of a level: kJpItem segments (units) of one scan from `first` on
@@ -27,6 +28,9 @@ struct JpItem { int scan, first; };    // a workgroup's share of a level: kJpIte
 AEJ_HD inline int jp_blocks_per_unit(const JpScan &s) { return s.ncomp > 1 ? s.bpm : 1; }
 
 // block `k` of unit `u` of the scan -> its index among the file's blocks (MCU order, the layout k_jd_idct reads); -1 outside the file
+// kFour (here and below: a call with a four-component file): component 3 sampled as component 0 walks its own block grid, and its
+// blocks follow the MCU's others
+template <bool kFour = false>
 AEJ_HD inline long long jp_slot(const JpScan &s, long long u, int k)
 {
     long long b;
@@ -35,6 +39,8 @@ AEJ_HD inline long long jp_slot(const JpScan &s, long long u, int k)
     } else {
         const long long by = u / s.units_x, bx = u % s.units_x;
         if (s.comp0 == 0) b = ((by / s.vs) * s.mcux + bx / s.hs) * s.bpm + (by % s.vs) * s.hs + bx % s.hs;
+        else if (kFour && s.comp0 == 3 && s.h3 == s.hs && s.v3 == s.vs)
+            b = ((by / s.vs) * s.mcux + bx / s.hs) * s.bpm + s.hs * s.vs + 2 + (by % s.vs) * s.hs + bx % s.hs;
         else b = (by * s.mcux + bx) * s.bpm + s.hs * s.vs + s.comp0 - 1;
     }
     return b >= 0 && b < s.n_blocks ? b : -1;
@@ -72,31 +78,34 @@ struct JpBits {
 AEJ_HD inline int jp_extend(unsigned bits, int sz) { return sz == 0 ? 0 : bits < (1u << (sz - 1)) ? (int)bits - (1 << sz) + 1 : (int)bits; }
 
 // DC first scan (G.1.2.1): units [u0, u0 + nu) of the scan from one restart segment; tab[i]: the table of the scan's component i
+template <bool kFour = false>
 AEJ_HD inline int jp_dc_first(const JpScan &s, const aej_jpegdec_huff *tab, JpBits &b, long long u0, int nu, short *coef)
 {
-    int pred[3] = { 0, 0, 0 };
+    int pred[kFour ? 4 : 3] = {};
     const int bpu = jp_blocks_per_unit(s);
     for (int u = 0; u < nu; u++)
         for (int k = 0; k < bpu; k++) {
-            const int ci = s.ncomp > 1 ? (k < s.hs * s.vs ? 0 : k - s.hs * s.vs + 1) : 0;
+            int ci = s.ncomp > 1 ? (k < s.hs * s.vs ? 0 : k - s.hs * s.vs + 1) : 0;
+            if (kFour && ci > 3) ci = 3;
             int sym;
             unsigned bits;
             const int rc = b.symbol(tab[ci], sym, bits, [](int v) { return v > 11 ? -1 : v; });
             if (rc != kJdRunStop) return rc;
             pred[ci] += jp_extend(bits, sym);
-            const long long slot = jp_slot(s, u0 + u, k);
+            const long long slot = jp_slot<kFour>(s, u0 + u, k);
             if (slot >= 0) coef[slot * 64] = (short)(pred[ci] * (1 << s.al));
         }
     return kJdRunStop;
 }
 
 // AC first scan (G.1.2.2): one component, band ss..se, EOB runs across blocks
+template <bool kFour = false>
 AEJ_HD inline int jp_ac_first(const JpScan &s, const aej_jpegdec_huff &tab, JpBits &b, long long u0, int nu, short *coef)
 {
     int eobrun = 0;
     for (int u = 0; u < nu; u++) {
         if (eobrun > 0) { eobrun--; continue; }
-        const long long slot = jp_slot(s, u0 + u, 0);
+        const long long slot = jp_slot<kFour>(s, u0 + u, 0);
         for (int k = s.ss; k <= s.se; k++) {
             int sym;
             unsigned bits;
@@ -136,12 +145,13 @@ AEJ_HD inline void jp_correct(short *c, int al)       // a set correction bit: o
 }
 
 // AC refinement scan (G.1.2.3): correction bits of the coefficients already non-zero interleaved with new +-1 coefficients
+template <bool kFour = false>
 AEJ_HD inline int jp_ac_refine(const JpScan &s, const aej_jpegdec_huff &tab, JpBits &b, long long u0, int nu, short *coef)
 {
     int eobrun = 0;
     const int p1 = 1 << s.al;
     for (int u = 0; u < nu; u++) {
-        const long long slot = jp_slot(s, u0 + u, 0);
+        const long long slot = jp_slot<kFour>(s, u0 + u, 0);
         if (slot < 0) return kJdRunOutOfBits;                  // cannot happen with the host's geometry; never touch another file
         short *blk = coef + slot * 64;
         const unsigned long long nz = jp_nonzero_mask(blk, s.ss, s.se);
@@ -186,6 +196,7 @@ AEJ_HD inline int jp_ac_refine(const JpScan &s, const aej_jpegdec_huff &tab, JpB
 }
 
 // DC refinement (G.1.2.1): block i of a restart segment is bit i of it
+template <bool kFour = false>
 AEJ_HD inline int jp_dc_refine_unit(const JpScan &s, const unsigned char *clean, const JdSeg &sg, long long u, short *coef)
 {
     const int bpu = jp_blocks_per_unit(s);
@@ -196,7 +207,7 @@ AEJ_HD inline int jp_dc_refine_unit(const JpScan &s, const unsigned char *clean,
         const long long bit = local * bpu + k;
         if (bit >= sg.nbytes * 8) return kJdRunOutOfBits;
         const long long pos = sg.start * 8 + bit;
-        const long long slot = jp_slot(s, u, k);
+        const long long slot = jp_slot<kFour>(s, u, k);
         if (((js_bswap(w[pos >> 5]) >> (31 - (int)(pos & 31))) & 1) && slot >= 0) coef[slot * 64] |= (short)(1 << s.al);
     }
     return kJdRunStop;

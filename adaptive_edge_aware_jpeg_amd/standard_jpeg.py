@@ -286,53 +286,66 @@ def _raise_status(bad):
         raise ValueError(f"file {i}: {JPEGDEC_STATUS[code] if 0 <= code < len(JPEGDEC_STATUS) else f'status {code}'}")
 
 
-def parse_header(data, index: int = 0, layout_440: bool = False):
+def parse_header(data, index: int = 0, layout_440: bool = False, adobe: bool = False):
     """aej_jpegdec_parse_host: the JpegDecDesc of one file's markers (host only).  Raises NotImplementedError for a valid file outside
     the supported set and ValueError for a malformed header, both naming the file index.  layout_440=True (aej_jpegdec_parse_host_440)
     also takes a three-component file whose luma is sampled 1 x 2 over 1 x 1 chroma (4:4:0: hs = 1, vs = 2); without it such a file is
-    refused as before."""
-    from ._lib import JpegDecDesc, load_library
+    refused as before.  adobe=True (aej_jpegdec_parse_host_adobe) also takes four-component (CMYK, YCCK) and RGB-coded files, refused
+    as before without it; the descriptor then carries two more attributes: ``adobe``, the file's JpegAdobe (component 3's factors and
+    tables), and ``colour``, one of "YCbCr", "RGB", "CMYK", "YCCK"."""
+    from ._lib import JPEG_COLOURS, JpegAdobe, JpegDecDesc, load_library
     buf, n = _buffer(data)
     d, msg = JpegDecDesc(), ctypes.create_string_buffer(256)
     head = (ctypes.addressof(buf), n, ctypes.addressof(d), ctypes.addressof(msg), 256)
     lib = load_library()
+    if _check_bool("adobe", adobe):
+        x = JpegAdobe()
+        _refuse(lib.aej_jpegdec_parse_host_adobe(*head[:3], ctypes.addressof(x), *head[3:], int(_check_bool("layout_440", layout_440))), msg, index)
+        d.adobe, d.colour = x, JPEG_COLOURS[x.colour]
+        return d
     _refuse(lib.aej_jpegdec_parse_host_440(*head, 1) if _check_bool("layout_440", layout_440) else lib.aej_jpegdec_parse_host(*head), msg, index)
     return d
 
 
-def parse_scans(data, index: int = 0, layout_440: bool = False):
+def parse_scans(data, index: int = 0, layout_440: bool = False, adobe: bool = False):
     """aej_jpegprog_parse_host: (JpegProgFrame, [JpegProgScan, ...]) of one progressive (SOF2) file, every marker SOI .. EOI walked on
     the host.  Raises ValueError for a malformed file or a scan script that violates T.81 G.1.1.1 and NotImplementedError for a valid
     file outside the supported set (an incomplete progression, arithmetic coding, a file that is not progressive, ...), both naming the
-    file index.  layout_440: as parse_header (aej_jpegprog_parse_host_440)."""
-    from ._lib import JpegProgFrame, JpegProgScan, load_library
+    file index.  layout_440: as parse_header (aej_jpegprog_parse_host_440).  adobe: as parse_header (aej_jpegprog_parse_host_adobe);
+    the frame then carries ``adobe`` and ``colour``."""
+    from ._lib import JPEG_COLOURS, JpegAdobe, JpegProgFrame, JpegProgScan, load_library
     lib = load_library()
     buf, n = _buffer(data)
     frame, msg = JpegProgFrame(), ctypes.create_string_buffer(256)
-    if _check_bool("layout_440", layout_440):
+    if _check_bool("adobe", adobe):
+        x, l440 = JpegAdobe(), int(_check_bool("layout_440", layout_440))
+        parse = lambda d, m, f, sc, cap, ms, mc: lib.aej_jpegprog_parse_host_adobe(d, m, f, sc, cap, ctypes.addressof(x), ms, mc, l440)  # noqa: E731
+    elif _check_bool("layout_440", layout_440):
         parse = lambda *a: lib.aej_jpegprog_parse_host_440(*a, 1)  # noqa: E731
     else:
         parse = lib.aej_jpegprog_parse_host
     _refuse(parse(ctypes.addressof(buf), n, ctypes.addressof(frame), None, 0, ctypes.addressof(msg), 256), msg, index)
     scans = (JpegProgScan * max(frame.n_scans, 1))()
     _refuse(parse(ctypes.addressof(buf), n, ctypes.addressof(frame), ctypes.addressof(scans), frame.n_scans, ctypes.addressof(msg), 256), msg, index)
+    if adobe:
+        frame.adobe, frame.colour = x, JPEG_COLOURS[x.colour]
     return frame, list(scans)
 
 
-def _parse_sources(files, progressive=True, transcoder=False, start=0, grey=False, layout_440=False):
+def _parse_sources(files, progressive=True, transcoder=False, start=0, grey=False, layout_440=False, adobe=False):
     """Parse every file once, telling baseline from progressive: yields (i, is_progressive, JpegDecDesc | (JpegProgFrame, scans), view)
     file by file, i counting from start.  progressive=False refuses progressive files the way standard_jpeg_decode_many does without
     its keyword; transcoder=True refuses what the transcoder does not take, which without grey=True includes one-component files.
-    layout_440=True: the parsers' keyword of that name, for every file.  Every refusal names the file."""
+    layout_440=True, adobe=True: the parsers' keywords of those names, for every file.  Every refusal names the file."""
     for i, f in enumerate(files, start):
         try:
-            d, is_prog = parse_header(f, i, layout_440), False
+            d, is_prog = parse_header(f, i, layout_440, adobe), False
         except NotImplementedError as e:
             if "progressive JPEG (SOF2)" not in str(e):
                 raise
             if not progressive:
                 raise NotImplementedError(f"{e}; pass progressive=True to standard_jpeg_decode_many") from None
-            d, is_prog = parse_scans(f, i, layout_440), True
+            d, is_prog = parse_scans(f, i, layout_440, adobe), True
         frame = d[0] if is_prog else d
         if transcoder and frame.ncomp != 3 and not (grey and frame.ncomp == 1):
             raise NotImplementedError(f"file {i}: a single-component (grey) file: the transcoder takes three-component files unless grey=True is passed")
@@ -358,9 +371,19 @@ def _stage(ctx, views, pieces):
     return dev, off
 
 
+def _adobe_array(frames):
+    """the JpegAdobe [n] of a call's frames when one of them is a four-component or RGB-coded file (the _adobe entries), else None"""
+    from ._lib import JpegAdobe
+    xs = [getattr(f, "adobe", None) for f in frames]
+    if not any(x is not None and x.colour != 0 for x in xs):
+        return None
+    return (JpegAdobe * len(xs))(*[x if x is not None else JpegAdobe() for x in xs])
+
+
 def _decode_baseline(ctx, idx, parsed, views, out, out_off, scales=None, comps=None, boxes=None):
     """aej_jpegdec_batch (scales None), aej_jpegdec_batch_scaled, (comps: 3 or 1 per file) aej_jpegdec_batch_mode or (boxes: int32
-    [n, 4]) aej_jpegdec_batch_box over the files idx -> their status words (device int32)"""
+    [n, 4]) aej_jpegdec_batch_box over the files idx -> their status words (device int32).  With a four-component or RGB-coded file
+    among them (adobe=True alone parses one): aej_jpegdec_batch_adobe, comps 4 for a file that leaves in mode "CMYK"."""
     from ._lib import JpegDecDesc
     t, lib, n = ctx.torch, ctx.lib, len(idx)
     descs = (JpegDecDesc * n)(*[parsed[i] for i in idx])
@@ -379,6 +402,11 @@ def _decode_baseline(ctx, idx, parsed, views, out, out_off, scales=None, comps=N
         bb = np.ascontiguousarray(boxes[idx], np.int32)
         how = (sc[0].ctypes.data if sc else None, cc.ctypes.data if comps is not None else None, bb.ctypes.data)
         nbytes, batch = lib.aej_jpegdec_workspace_bytes_box, lib.aej_jpegdec_batch_box
+    xs = _adobe_array([parsed[i] for i in idx])
+    if xs is not None:
+        how = (sc[0].ctypes.data if sc else None, cc.ctypes.data if comps is not None else None, bb.ctypes.data if boxes is not None else None,
+               ctypes.addressof(xs))
+        nbytes, batch = lib.aej_jpegdec_workspace_bytes_adobe, lib.aej_jpegdec_batch_adobe
     nws = int(nbytes(ctx.handle, ctypes.addressof(descs), n, *how))
     if nws == 0:
         raise ValueError("descriptors the library refuses")
@@ -412,6 +440,11 @@ def _decode_progressive(ctx, idx, parsed, views, out, out_off, scales=None, comp
         bb = np.ascontiguousarray(boxes[idx], np.int32)
         how = (sc[0].ctypes.data if sc else None, cc.ctypes.data if comps is not None else None, bb.ctypes.data)
         nbytes, batch = lib.aej_jpegprog_workspace_bytes_box, lib.aej_jpegprog_batch_box
+    xs = _adobe_array([parsed[i][0] for i in idx])        # a four-component or RGB-coded file among them: the _adobe entries
+    if xs is not None:
+        how = (sc[0].ctypes.data if sc else None, cc.ctypes.data if comps is not None else None, bb.ctypes.data if boxes is not None else None,
+               ctypes.addressof(xs))
+        nbytes, batch = lib.aej_jpegprog_workspace_bytes_adobe, lib.aej_jpegprog_batch_adobe
     nws = int(nbytes(ctx.handle, ctypes.addressof(frames), ctypes.addressof(scans), n, *how))
     if nws == 0:
         raise ValueError("descriptors the library refuses")
@@ -541,8 +574,8 @@ def decode_box_stats(device: int = 0):
 
 
 def _views(out, out_off, shapes, comps):
-    """the images of a packed decode: [h, w, 3], or [h, w] where comps says 1"""
-    return [out[int(o):int(o) + h * w * c].view(*((h, w, 3) if c == 3 else (h, w))) for o, (h, w), c in zip(out_off, shapes, comps)]
+    """the images of a packed decode: [h, w, 3], [h, w] where comps says 1, or [h, w, 4] where it says 4"""
+    return [out[int(o):int(o) + h * w * c].view(*((h, w) if c == 1 else (h, w, c))) for o, (h, w), c in zip(out_off, shapes, comps)]
 
 
 def draft_scale(width: int, height: int, size) -> int:
@@ -556,7 +589,8 @@ def draft_scale(width: int, height: int, size) -> int:
     return next((s for s in (8, 4, 2) if s <= ratio), 1)
 
 
-def standard_jpeg_decode_many(files, device: int = 0, progressive: bool = False, scale=1, layout_440: bool = False, mode="RGB", box=None) -> list:
+def standard_jpeg_decode_many(files, device: int = 0, progressive: bool = False, scale=1, layout_440: bool = False, mode="RGB", box=None,
+                              adobe: bool = False) -> list:
     """Decode JPEG files on the device: -> list of uint8 [H_i, W_i, 3] tensors (views into one packed allocation), in input
     order, on the context of the current stream; element i equals ``np.asarray(Image.open(io.BytesIO(files[i])).convert("RGB"))``.
     scale: 1, 2, 4 or 8, or a sequence of one such value per file (ValueError naming the value otherwise; a bool is refused): file i
@@ -598,26 +632,39 @@ def standard_jpeg_decode_many(files, device: int = 0, progressive: bool = False,
     tuple of another length TypeError; a list of another length than files ValueError; a box on a file whose scale is not 1
     NotImplementedError ("a box at scale 2, 4 or 8 is not built").  ERRORS IN SKIPPED DATA: a boxed decode reports scan errors only
     for the data it reads -- a malformed restart segment that the box does not need is not noticed, where the call without box=
-    raises."""
+    raises.
+    adobe=True (TypeError for a value that is not a bool; without it every call is as it always was, every refusal included) also
+    takes the files libjpeg reads under another colour model, baseline or -- with progressive=True -- progressive, mixed freely with
+    the others: four components as CMYK (no Adobe APP14 marker, or one with transform 0) or YCCK (transform 2; any other transform
+    NotImplementedError), and three components coded as RGB (no JFIF marker, and APP14 transform 0 or the component ids 'R','G','B':
+    what ``save(..., keep_rgb=True)`` writes).  Components 1 and 2 sampled 1 x 1, component 0 as for YCbCr files, component 3 as
+    component 0 (Photoshop: K at full resolution, up to 10 blocks per MCU) or 1 x 1 (Pillow's subsampling=1 / 2: K is up-sampled with
+    the chroma, by the same rules).  mode="auto" gives such a file in Pillow's own mode: uint8 [H, W, 4] equal to
+    ``np.asarray(Image.open(f))`` (mode "CMYK": 255 - sample; for YCCK libjpeg's YCbCr -> RGB of components 0..2 and 255 - K) for
+    four components, [H, W, 3] (the samples) for an RGB-coded one.  mode="RGB" gives [H, W, 3] for every file: of a four-component one
+    Pillow's ``.convert("RGB")`` of that CMYK image, in its integer arithmetic.  Not built, NotImplementedError naming the file before
+    any device work: mode="L", a scale other than 1 or a box for one of these files ("... of a four-component / RGB-coded file is
+    not built").  The thumbnail, transcode, transform and encode calls have no such keyword and refuse these files as before."""
     files = list(files)
     if not files:
         raise ValueError("standard_jpeg_decode_many needs at least one file")
     modes = _check_modes(mode, len(files))
     _, out, out_off, shapes, comps = _decode_files(files, device, progressive, _check_scales(scale, len(files)),
                                                    layout_440=_check_bool("layout_440", layout_440), modes=modes,
-                                                   boxes=_check_boxes(box, len(files)))
+                                                   boxes=_check_boxes(box, len(files)), adobe=_check_bool("adobe", adobe))
     return _views(out, out_off, shapes, comps)
 
 
-def _decode_files(files, device, progressive, scales, choose=None, layout_440=False, modes=None, boxes=None):
+def _decode_files(files, device, progressive, scales, choose=None, layout_440=False, modes=None, boxes=None, adobe=False):
     """The decode of standard_jpeg_decode_many -> (context, the packed uint8 output, int64 offsets, [(h, w)], [3 or 1: the channels of
     each image]).  scales: int32 [n]; with `choose`, file i's scale is choose(i, width, height) instead, asked once its header
     is parsed and before any device work.  modes: _check_modes' list (None: every file "RGB").  boxes: _check_boxes' list (None: no
-    file has one); the shape of a boxed file is its box's."""
+    file has one); the shape of a boxed file is its box's.  adobe: the parsers' keyword; a four-component file that leaves in mode
+    "CMYK" has 4 channels."""
     n = len(files)
     parsed, views, base_idx, prog_idx, shapes, comps = [], [], [], [], [], []
     box_arr, prog_set = None, set()
-    for i, is_prog, d, mv in _parse_sources(files, progressive, layout_440=layout_440):
+    for i, is_prog, d, mv in _parse_sources(files, progressive, layout_440=layout_440, adobe=adobe):
         parsed.append(d)
         views.append(mv)
         (prog_idx if is_prog else base_idx).append(i)
@@ -625,10 +672,15 @@ def _decode_files(files, device, progressive, scales, choose=None, layout_440=Fa
             prog_set.add(i)
         frame = d[0] if is_prog else d
         m = "RGB" if modes is None else modes[i]
-        comps.append(1 if m == "L" or (m == "auto" and frame.ncomp == 1) else 3)
+        comps.append(1 if m == "L" or (m == "auto" and frame.ncomp == 1) else 4 if m == "auto" and frame.ncomp == 4 else 3)
         if choose is not None:
             scales[i] = choose(i, frame.width, frame.height)
         s = int(scales[i])
+        if adobe and frame.colour != "YCbCr":            # the new kinds: full size, whole, in colour
+            whole = boxes is None or boxes[i] is None or boxes[i] == (0, 0, frame.width, frame.height)
+            what = "mode 'L'" if m == "L" else "a scale other than 1" if s != 1 else None if whole else "a box"
+            if what:
+                raise NotImplementedError(f"file {i}: {what} of a four-component / RGB-coded file is not built")
         shapes.append((-(-frame.height // s), -(-frame.width // s)))
         if boxes is not None and boxes[i] is not None:
             _box_in_image(boxes[i], frame.width, frame.height, i)

@@ -611,6 +611,57 @@ AEJ_API int aej_jpegprog_batch_box(aej_ctx *ctx, const aej_jpegprog_frame *frame
                                    const int64_t *out_offsets_host, int32_t *status, void *workspace, uint64_t workspace_bytes);
 AEJ_API int aej_jpegprog_box_window_host(const aej_jpegprog_frame *frame_host, const int32_t *box4_host, int32_t *window4_out_host);
 
+/* ---- CMYK, YCCK and RGB-coded files (standard_jpeg_decode_many(..., adobe=True)) -------------------------------------------------------
+ * The files libjpeg reads with another colour model than YCbCr or grey: four components -- CMYK without an Adobe APP14 marker or with
+ * transform 0, YCCK with transform 2 (any other transform: AEJ_ERR_UNSUPPORTED; libjpeg takes it as YCCK with a warning) -- and three
+ * components coded as RGB (no JFIF marker, and APP14 transform 0 or the component ids 'R','G','B').  The parsers above refuse them; the
+ * _adobe parsers take them and fill one aej_jpeg_adobe per file beside the descriptor, which keeps its three tables: the fourth
+ * component's sampling factors and tables travel in the aej_jpeg_adobe.  A file of the kinds the parsers above take gets colour =
+ * AEJ_JPEG_YCBCR and zeros.  Sampling: components 1 and 2 are 1 x 1, component 0 as for three components (hs, vs), component 3 either
+ * component 0's factors (blocks_per_mcu = 2 hs vs + 2: 10 for 2 x 2) or 1 x 1 (blocks_per_mcu = hs vs + 3); a sub-sampled component 3
+ * is up-sampled as the chroma planes are.  desc->ncomp is 4 for a four-component file, which the entries without _adobe refuse.
+ *
+ * aej_jpegdec_parse_host_adobe / aej_jpegprog_parse_host_adobe: the _440 parsers with adobe_host (one struct, not NULL) as well.
+ * aej_jpegdec_batch_adobe / aej_jpegdec_workspace_bytes_adobe, aej_jpegprog_batch_adobe / aej_jpegprog_workspace_bytes_adobe: the _box
+ *   calls with adobe_host [n] as well.  NULL, or every colour AEJ_JPEG_YCBCR: the _box call byte for byte, launches included.  For a file
+ *   with another colour, components_host[i] (NULL: 3) is 3 -- image i is [height][width][3]: the samples of an RGB-coded file; of a
+ *   four-component one Pillow's CMYK -> RGB of the image below, clip8(nk - MULDIV255(c, nk)) per channel with nk = 255 - K -- or 4
+ *   (four-component files only): [height][width][4], Pillow's mode "CMYK" image: 255 - sample for CMYK; for YCCK libjpeg's YCbCr -> RGB
+ *   of samples 0..2 and 255 - sample 3.  Refused with AEJ_ERR_UNSUPPORTED naming the file, before any device work and leaving out
+ *   untouched: such a file with components 1, with a scale other than 1 or with a box that is not its whole image ("... of a
+ *   four-component / RGB-coded file is not built").  components 4 on any other file is AEJ_ERR_ARG.  A call with such a file runs the
+ *   four-component instantiations of the entropy kernels (a fourth DC predictor, a 4-bit block slot) and reconstructs these files
+ *   with kernels of their own; every other file of the call is reconstructed as before.  A file whose components all decode under one
+ *   DC and one AC table (what libjpeg writes for CMYK and RGB) says nothing about the block slot in its bits; the slot is then taken
+ *   from the block counts, at the price of one more counting pass.
+ *   (Additions to ABI 3: no existing signature, struct or behaviour changed.) */
+enum { AEJ_JPEG_YCBCR = 0, AEJ_JPEG_RGB = 1, AEJ_JPEG_CMYK = 2, AEJ_JPEG_YCCK = 3 };
+typedef struct aej_jpeg_adobe {
+    int32_t colour;            /* AEJ_JPEG_*: YCbCr (or grey), RGB, CMYK, YCCK */
+    int32_t h3, v3;            /* sampling factors of component 3; 0 unless the file has four components */
+    int32_t tq3;               /* its quantisation table index in the frame header */
+    uint16_t qt3[64];          /* its quantisation table, natural order */
+    aej_jpegdec_huff dc3, ac3; /* its Huffman tables: a baseline file's scan; of a progressive file dc3 alone, from the interleaved DC scan */
+} aej_jpeg_adobe;
+AEJ_API int aej_jpegdec_parse_host_adobe(const uint8_t *data_host, uint64_t nbytes, aej_jpegdec_desc *desc_host, aej_jpeg_adobe *adobe_host,
+                                         char *msg, int msg_capacity, int layout_440);
+AEJ_API int aej_jpegprog_parse_host_adobe(const uint8_t *data_host, uint64_t nbytes, aej_jpegprog_frame *frame_host, aej_jpegprog_scan *scans_host,
+                                          int scan_capacity, aej_jpeg_adobe *adobe_host, char *msg, int msg_capacity, int layout_440);
+AEJ_API uint64_t aej_jpegdec_workspace_bytes_adobe(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host,
+                                                   const int *components_host, const int32_t *boxes_host, const aej_jpeg_adobe *adobe_host);
+AEJ_API int aej_jpegdec_batch_adobe(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host, const int *components_host,
+                                    const int32_t *boxes_host, const aej_jpeg_adobe *adobe_host, const uint8_t *scans, uint64_t scans_bytes,
+                                    const int64_t *scan_offsets_host, uint8_t *out, uint64_t out_bytes, const int64_t *out_offsets_host,
+                                    int32_t *status, void *workspace, uint64_t workspace_bytes);
+AEJ_API uint64_t aej_jpegprog_workspace_bytes_adobe(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
+                                                    const int *scales_host, const int *components_host, const int32_t *boxes_host,
+                                                    const aej_jpeg_adobe *adobe_host);
+AEJ_API int aej_jpegprog_batch_adobe(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
+                                     const int *scales_host, const int *components_host, const int32_t *boxes_host,
+                                     const aej_jpeg_adobe *adobe_host, const uint8_t *data, uint64_t data_bytes, const int64_t *data_offsets_host,
+                                     uint8_t *out, uint64_t out_bytes, const int64_t *out_offsets_host, int32_t *status, void *workspace,
+                                     uint64_t workspace_bytes);
+
 /* ---- images of mixed sizes and qualities encoded in one call (standard_jpeg_encode_many) -------------------------------------------------
  * The files of aej_jfif_encode_batch_opt / _prog -- Pillow's Image.save(buf, "JPEG", quality, subsampling, optimize, progressive), byte
  * for byte -- for n images that each have their own size and quality.  One kernel covers every 8 x 8 block of every image (colour, edge

@@ -43,6 +43,12 @@ AEJ_API int aej_test_jfif_prog_scan(aej_ctx *ctx, const int16_t *coefs_host, int
  * samples, row after row -- computed by the function of csrc/jpegdec_core.h that the kernel calls (jd_idct_sized). */
 AEJ_API int aej_test_jpegdec_idct_host(const int16_t *coef_host, const uint16_t *qt_host, int size, uint8_t *out_host);
 
+/* The per-pixel colour rules of the four-component / RGB-coded reconstruction (aej_jpegdec_batch_adobe), HOST only: samples4_host [n][4]
+ * up-sampled samples of one pixel each, colour AEJ_JPEG_RGB, _CMYK or _YCCK, components 3 or 4 (4: not with _RGB) -> out_host
+ * [n][components], computed by the functions of csrc/jpegdec_core.h that the kernel calls (jd_adobe_pixel: jd_cmyk_pixel, jd_ycck_pixel,
+ * jd_cmyk_rgb).  AEJ_ERR_ARG for anything else. */
+AEJ_API int aej_test_jpeg_adobe_pixels_host(const uint8_t *samples4_host, int64_t n, int colour, int components, uint8_t *out_host);
+
 #ifdef __cplusplus
 }
 #endif
