@@ -25,8 +25,8 @@ from .lpips import LpipsWeights  # noqa: E402
 from .quadtree import QuadNode, QuadTree  # noqa: E402
 from .settings import JpegCompressionSettings  # noqa: E402
 from .resample import resize_many  # noqa: E402
-from .standard_jpeg import (decode_box_stats, decode_box_window, draft_scale, encode_groups, exif_orientation, standard_jpeg_batch, standard_jpeg_decode_many,  # noqa: E402
-                            standard_jpeg_encode_many, standard_jpeg_many, standard_jpeg_thumbnail_jpeg_many, standard_jpeg_thumbnail_many, standard_jpeg_transcode_many, standard_jpeg_transform_many, thumbnail_plan,
+from .standard_jpeg import (decode_box_stats, decode_box_window, draft_scale, encode_groups, exif_orientation, resized_crop_plan, standard_jpeg_batch, standard_jpeg_decode_many,  # noqa: E402
+                            standard_jpeg_encode_many, standard_jpeg_many, standard_jpeg_resized_crop_many, standard_jpeg_thumbnail_jpeg_many, standard_jpeg_thumbnail_many, standard_jpeg_transcode_many, standard_jpeg_transform_many, thumbnail_plan,
                             transform_crop_box, transform_prefix)
 from .sweep import SweepResult, reference_grid, sweep  # noqa: E402
 
@@ -35,4 +35,5 @@ __all__ = ["Jpeg", "JpegCompressionSettings", "EncodedBatch", "Image", "Evaluati
            "sweep", "reference_grid", "SweepResult", "LpipsWeights", "standard_jpeg_many", "standard_jpeg_batch",
            "standard_jpeg_decode_many", "standard_jpeg_transcode_many", "standard_jpeg_transform_many", "exif_orientation", "draft_scale",
            "resize_many", "standard_jpeg_thumbnail_many", "thumbnail_plan", "standard_jpeg_encode_many", "standard_jpeg_thumbnail_jpeg_many",
-           "encode_groups", "transform_prefix", "transform_crop_box", "decode_box_window", "decode_box_stats"]
+           "encode_groups", "transform_prefix", "transform_crop_box", "decode_box_window", "decode_box_stats", "resized_crop_plan",
+           "standard_jpeg_resized_crop_many"]

@@ -272,6 +272,12 @@ SIGNATURES = {
     "aej_jpegdec_box_window_host": (_I, [_P, _P, _P]),
     "aej_jpegprog_box_window_host": (_I, [_P, _P, _P]),
     "aej_jpegdec_box_stats": (_I, [_P, _P]),
+    "aej_jpegdec_workspace_bytes_sbox": (_U64, [_P, _P, _I, _P, _P, _P]),
+    "aej_jpegdec_batch_sbox": (_I, [_P, _P, _I, _P, _P, _P, _P, _U64, _P, _P, _U64, _P, _P, _P, _U64]),
+    "aej_jpegdec_sbox_window_host": (_I, [_P, _I, _P, _P]),
+    "aej_jpegprog_sbox_window_host": (_I, [_P, _I, _P, _P]),
+    "aej_jpegprog_workspace_bytes_sbox": (_U64, [_P, _P, _P, _I, _P, _P, _P]),
+    "aej_jpegprog_batch_sbox": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _U64, _P, _P, _U64, _P, _P, _P, _U64]),
     "aej_jpegprog_workspace_bytes_box": (_U64, [_P, _P, _P, _I, _P, _P, _P]),
     "aej_jpegprog_batch_box": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _U64, _P, _P, _U64, _P, _P, _P, _U64]),
     "aej_jpegdec_parse_host_adobe": (_I, [_P, _U64, _P, _P, _P, _I, _I]),
@@ -329,6 +335,8 @@ SIGNATURES = {
     "aej_resample_batch": (_I, [_P, _P, _I, _P, _U64, _P, _U64, _P, _U64]),
     "aej_resample_workspace_bytes_ch": (_U64, [_P, _P, _I, _P]),
     "aej_resample_batch_ch": (_I, [_P, _P, _I, _P, _P, _U64, _P, _U64, _P, _U64]),
+    "aej_resample_workspace_bytes_win": (_U64, [_P, _P, _I, _P, _P]),
+    "aej_resample_batch_win": (_I, [_P, _P, _I, _P, _P, _P, _U64, _P, _U64, _P, _U64]),
     "aej_test_jpegprog_coefs": (_I, [_P, _P, _P, _I, _P, _U64, _P, _I, _P, _U64, _P, _P, _U64]),             # include/aej_testing.h (tests only)
     "aej_test_jpegprog_coefs_host": (_I, [_P, _P, _P, _U64, _I, _P, _U64]),                                 # include/aej_testing.h (tests only)
     "aej_test_jpeg_adobe_pixels_host": (_I, [_P, _I64, _I, _I, _P]),                                        # include/aej_testing.h (tests only)

@@ -329,7 +329,7 @@ int jfifprog_scan_device(hipStream_t st, const short *coefs_host, long long n, i
 #include "jpegdec_core.h"
 
 namespace aej {
-struct JdBufSizes { long long chunks, segs, slots, blocks, clean, planes, px, grp[3], grp440[3], grpl[4], grpb, grpa, uniform; };      // totals over the files of one call (grp, grp440, grpl, grpb: JdFile::grp_base, ::grp440_base, ::grpl_base, ::grpb_base; grpa: ::grpa_base, the workgroups of k_jd_adobe -- non-zero exactly when the call has a four-component or RGB-coded file; uniform: the baseline ones among them with JdFile::uniform)
+struct JdBufSizes { long long chunks, segs, slots, blocks, clean, planes, px, grp[3], grp440[3], grpl[4], grpb, grpa, uniform, grps[3]; };      // totals over the files of one call (grp, grp440, grpl, grpb, grps: JdFile::grp_base, ::grp440_base, ::grpl_base, ::grpb_base, ::grps_base; grpa: ::grpa_base, the workgroups of k_jd_adobe -- non-zero exactly when the call has a four-component or RGB-coded file; uniform: the baseline ones among them with JdFile::uniform)
 struct JdBufs {
     JdFile *files; aej_jpegdec_desc *descs; int *last_change;      // one upload: files, descriptors, the "last round that changed" word
     aej_jpeg_adobe *adobe;                                         // and, in a call with z.grpa > 0 alone, the files' aej_jpeg_adobe behind that word (else NULL)
@@ -373,6 +373,8 @@ void jpeg_stream_layout(long long len, int n_segments, int S, JdFile &F, JdBufSi
 // fields, z's totals
 // box (NULL, or the whole image: none): left, top, right, bottom inside the image (jpeg_box_inside), full size only -- the file's
 // workgroups of k_jd_box and no sample planes; window_coef: only the coefficients of the window's MCU rows are stored (baseline files)
+// kJdSbox in shift (the _sbox entries, scale 2, 4, 8): box is in pixels of the scaled image, inside it and not the whole of it -- the
+// file's workgroups of k_jd_sbox<log2 scale>, the same coefficient window
 // x (NULL: none): the file's aej_jpeg_adobe; with another colour than YCbCr the file gets kJdAdobe in its shift, four sample planes and
 // its workgroups of k_jd_adobe (shift: 0, or kJdCmyk for four-channel output; the callers refuse a scale, luma or a box for such a file)
 void jpeg_recon_layout(const aej_jpegdec_desc &d, int shift, JdFile &F, JdBufSizes &z, const int *box = nullptr, bool window_coef = true,
@@ -565,6 +567,7 @@ struct RsImage {                       // host: the stages of one image and wher
     int ch;                            // bytes per pixel: 3, or 1
     RsReduce r; RsConv h, v;
     long long src_offset, dst_offset, src_bytes, dst_bytes, r_src, tmp_a, tmp_b, h_table, v_table;
+    long long win_shift;               // a windowed source without a reduce: bytes from its first stored pixel to pixel (0, 0) of the virtual image (<= 0)
 };
 struct RsPlan {
     std::vector<RsImage> images;
@@ -578,7 +581,8 @@ int rs_ksize(float in0, float in1, int out_size, int filter);
 void rs_taps(int in_size, float in0, float in1, int out_size, int filter, int ksize, int *bounds, int *taps);
 void rs_bounds_of_row(int in_size, float in0, float in1, int out_size, int filter, int xx, int *bounds);
 const char *rs_check(const aej_resample_desc &d, int *code);
-int resample_plan(const aej_resample_desc *descs, int n, bool fill, RsPlan &plan, const char **why, int *code, const int *channels = nullptr);
+int resample_plan(const aej_resample_desc *descs, int n, bool fill, RsPlan &plan, const char **why, int *code, const int *channels = nullptr,
+                  const int *windows = nullptr);
 unsigned long long resample_carve(void *base, const RsPlan &plan, RsBufs &w);
 void resample_blob(const RsPlan &plan, const RsBufs &w, const unsigned char *src, unsigned char *dst, std::vector<unsigned char> &blob);
 hipError_t launch_resample(hipStream_t st, const RsPlan &plan, const RsBufs &w, const void *blob_host, unsigned long long blob_bytes);

@@ -282,13 +282,19 @@ static int check_scales(aej_ctx *ctx, const char *fn, const int *scales_host, in
 
 // the boxes of a _box call ([n][4] left, top, right, bottom; NULL: none): every one inside its image (*unsupported false), and none but the
 // whole image on a file that is not decoded at full size (*unsupported true); *bad: the file.  D: aej_jpegdec_desc or aej_jpegprog_frame
+// sbox (the _sbox entries): a box is in pixels of the file's image at its scale, ceil(width / s) x ceil(height / s), and only has to lie in that
 template <class D>
-static bool boxes_ok(const D *frames, int n, const int32_t *boxes_host, const std::vector<int> &shifts, int *bad, bool *unsupported)
+static bool boxes_ok(const D *frames, int n, const int32_t *boxes_host, const std::vector<int> &shifts, int *bad, bool *unsupported, bool sbox = false)
 {
     for (int i = 0; boxes_host && i < n; i++) {
         const int32_t *b = boxes_host + 4 * i;
         *bad = i;
         *unsupported = false;
+        if (sbox) {
+            const int sh = shifts[i] & (kJdLuma - 1), ow = (frames[i].width + (1 << sh) - 1) >> sh, oh = (frames[i].height + (1 << sh) - 1) >> sh;
+            if (!(0 <= b[0] && b[0] < b[2] && b[2] <= ow && 0 <= b[1] && b[1] < b[3] && b[3] <= oh)) return false;
+            continue;
+        }
         if (!jpeg_box_inside(frames[i], b)) return false;
         *unsupported = true;
         if (!jpeg_box_whole(frames[i], b) && (shifts[i] & (kJdLuma - 1))) return false;
@@ -296,15 +302,27 @@ static bool boxes_ok(const D *frames, int n, const int32_t *boxes_host, const st
     return true;
 }
 template <class D>
-static int check_boxes(aej_ctx *ctx, const char *fn, const D *frames, int n, const int32_t *boxes_host, const std::vector<int> &shifts)
+static int check_boxes(aej_ctx *ctx, const char *fn, const D *frames, int n, const int32_t *boxes_host, const std::vector<int> &shifts, bool sbox = false)
 {
     int bad = 0;
     bool unsupported = false;
-    if (boxes_ok(frames, n, boxes_host, shifts, &bad, &unsupported)) return 0;
+    if (boxes_ok(frames, n, boxes_host, shifts, &bad, &unsupported, sbox)) return 0;
     const int32_t *b = boxes_host + 4 * bad;
     if (unsupported) return fail(ctx, AEJ_ERR_UNSUPPORTED, "%s: file %d: a box at scale 2, 4 or 8 is not built", fn, bad);
+    const int sh = sbox ? shifts[bad] & (kJdLuma - 1) : 0;
     return fail(ctx, AEJ_ERR_ARG, "%s: file %d: box (%d, %d, %d, %d) is empty or leaves the %d x %d image", fn, bad, b[0], b[1], b[2], b[3],
-                frames[bad].width, frames[bad].height);
+                (frames[bad].width + (1 << sh) - 1) >> sh, (frames[bad].height + (1 << sh) - 1) >> sh);
+}
+// after boxes_ok of an _sbox call: kJdSbox on the files at scale 2, 4, 8 whose box is not their whole scaled image (jpeg_recon_layout); the
+// others are the _box call's -- at scale 1 the box is in full-size pixels, and the whole scaled image is no box
+template <class D>
+static void sbox_shifts(const D *frames, int n, const int32_t *boxes_host, std::vector<int> &shifts)
+{
+    for (int i = 0; boxes_host && i < n; i++) {
+        const int32_t *b = boxes_host + 4 * i;
+        const int sh = shifts[i] & (kJdLuma - 1), ow = (frames[i].width + (1 << sh) - 1) >> sh, oh = (frames[i].height + (1 << sh) - 1) >> sh;
+        if (sh && !(b[0] == 0 && b[1] == 0 && b[2] == ow && b[3] == oh)) shifts[i] |= kJdSbox;
+    }
 }
 
 // The _adobe entries: components_host may say 4 (Pillow's mode "CMYK" image) for a four-component file.  comps3 gets the counts with 3 in
@@ -363,6 +381,31 @@ static int box_window_host(int width, int height, int hs, int vs, int ncomp, con
     return 0;
 }
 
+// jd_sbox_window behind its two public entries: the box in pixels of the image at `scale`
+static int sbox_window_host(int width, int height, int hs, int vs, int ncomp, int scale, const int32_t *box4_host, int32_t *window4_out_host)
+{
+    const int sh = jpeg_scale_shift(scale);
+    if (sh < 0 || !box4_host || !window4_out_host || width < 1 || height < 1 || (ncomp != 1 && ncomp != 3)) return AEJ_ERR_ARG;
+    if (ncomp == 3 && ((hs != 1 && hs != 2) || (vs != 1 && vs != 2))) return AEJ_ERR_ARG;
+    const int ow = (width + scale - 1) >> sh, oh = (height + scale - 1) >> sh;
+    if (!(0 <= box4_host[0] && box4_host[0] < box4_host[2] && box4_host[2] <= ow && 0 <= box4_host[1] && box4_host[1] < box4_host[3] && box4_host[3] <= oh))
+        return AEJ_ERR_ARG;
+    jd_sbox_window(width, height, hs, vs, ncomp, false, sh, box4_host, window4_out_host);
+    return 0;
+}
+
+extern "C" int aej_jpegdec_sbox_window_host(const aej_jpegdec_desc *desc_host, int scale, const int32_t *box4_host, int32_t *window4_out_host)
+{
+    if (!desc_host) return AEJ_ERR_ARG;
+    return sbox_window_host(desc_host->width, desc_host->height, desc_host->hs, desc_host->vs, desc_host->ncomp, scale, box4_host, window4_out_host);
+}
+
+extern "C" int aej_jpegprog_sbox_window_host(const aej_jpegprog_frame *frame_host, int scale, const int32_t *box4_host, int32_t *window4_out_host)
+{
+    if (!frame_host) return AEJ_ERR_ARG;
+    return sbox_window_host(frame_host->width, frame_host->height, frame_host->hs, frame_host->vs, frame_host->ncomp, scale, box4_host, window4_out_host);
+}
+
 extern "C" int aej_jpegdec_box_window_host(const aej_jpegdec_desc *desc_host, const int32_t *box4_host, int32_t *window4_out_host)
 {
     if (!desc_host) return AEJ_ERR_ARG;
@@ -383,7 +426,7 @@ extern "C" int aej_jpegdec_box_stats(aej_ctx *ctx, int64_t *out3_host)
 }
 
 static uint64_t jpegdec_workspace(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host, const int *components_host = nullptr,
-                                  const int32_t *boxes_host = nullptr, const aej_jpeg_adobe *adobe_host = nullptr)
+                                  const int32_t *boxes_host = nullptr, const aej_jpeg_adobe *adobe_host = nullptr, bool sbox = false)
 {
     std::vector<int> shifts, comps3;
     int bad = 0;
@@ -395,7 +438,8 @@ static uint64_t jpegdec_workspace(aej_ctx *ctx, const aej_jpegdec_desc *descs_ho
         if (components_host) components_host = comps3.data();
     }
     if (!scale_shifts(scales_host, n, shifts, nullptr, components_host)) return 0;
-    if (!boxes_ok(descs_host, n, boxes_host, shifts, &bad, &unsupported)) return 0;
+    if (!boxes_ok(descs_host, n, boxes_host, shifts, &bad, &unsupported, sbox)) return 0;
+    if (sbox) sbox_shifts(descs_host, n, boxes_host, shifts);
     if (adobe_host) {
         if (adobe_unbuilt(descs_host, n, adobe_host, shifts, boxes_host, &bad)) return 0;
         adobe_shifts(n, components4, shifts);
@@ -427,6 +471,12 @@ extern "C" uint64_t aej_jpegdec_workspace_bytes_box(aej_ctx *ctx, const aej_jpeg
                                                     const int *components_host, const int32_t *boxes_host)
 {
     return jpegdec_workspace(ctx, descs_host, n, scales_host, components_host, boxes_host);
+}
+
+extern "C" uint64_t aej_jpegdec_workspace_bytes_sbox(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host,
+                                                     const int *components_host, const int32_t *boxes_host)
+{
+    return jpegdec_workspace(ctx, descs_host, n, scales_host, components_host, boxes_host, nullptr, true);
 }
 
 extern "C" uint64_t aej_jpegdec_workspace_bytes_adobe(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host,
@@ -475,7 +525,7 @@ static int jpegdec_batch(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *d
                          const uint8_t *scans,
                          uint64_t scans_bytes, const int64_t *scan_offsets_host, uint8_t *out, uint64_t out_bytes, const int64_t *out_offsets_host,
                          int32_t *status, void *workspace, uint64_t workspace_bytes, const int32_t *boxes_host = nullptr,
-                         const aej_jpeg_adobe *adobe_host = nullptr)
+                         const aej_jpeg_adobe *adobe_host = nullptr, bool sbox = false)
 {
     AEJ_TRY(enter(ctx, fn));
     if (!jpegdec_descs_ok(descs_host, n, adobe_host))
@@ -490,7 +540,8 @@ static int jpegdec_batch(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *d
         if (components_host) components_host = comps3.data();
     }
     AEJ_TRY(check_scales(ctx, fn, scales_host, n, shifts, components_host));
-    AEJ_TRY(check_boxes(ctx, fn, descs_host, n, boxes_host, shifts));
+    AEJ_TRY(check_boxes(ctx, fn, descs_host, n, boxes_host, shifts, sbox));
+    if (sbox) sbox_shifts(descs_host, n, boxes_host, shifts);
     if (adobe_host) {
         AEJ_TRY(check_adobe(ctx, fn, descs_host, n, adobe_host, shifts, boxes_host));
         adobe_shifts(n, components4, shifts);
@@ -499,7 +550,7 @@ static int jpegdec_batch(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *d
     std::vector<JdFile> files;
     JdBufSizes z;
     jpegdec_layout(descs_host, n, S, files, z, shifts.data(), boxes_host, adobe_host);
-    if (z.grpb > 0) {                                        // aej_jpegdec_box_stats: from the descriptors and the windows alone
+    if (z.grpb > 0 || z.grps[0] > 0 || z.grps[1] > 0 || z.grps[2] > 0) {      // aej_jpegdec_box_stats: from the descriptors and the windows alone
         long long total = 0, decoded = 0;
         for (int i = 0; i < n; i++) {
             const aej_jpegdec_desc &d = descs_host[i];
@@ -556,6 +607,15 @@ extern "C" int aej_jpegdec_batch_box(aej_ctx *ctx, const aej_jpegdec_desc *descs
 {
     return jpegdec_batch(ctx, __func__, descs_host, n, scales_host, components_host, scans, scans_bytes, scan_offsets_host, out, out_bytes,
                          out_offsets_host, status, workspace, workspace_bytes, boxes_host);
+}
+
+extern "C" int aej_jpegdec_batch_sbox(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host, const int *components_host,
+                                      const int32_t *boxes_host, const uint8_t *scans, uint64_t scans_bytes, const int64_t *scan_offsets_host,
+                                      uint8_t *out, uint64_t out_bytes, const int64_t *out_offsets_host, int32_t *status, void *workspace,
+                                      uint64_t workspace_bytes)
+{
+    return jpegdec_batch(ctx, __func__, descs_host, n, scales_host, components_host, scans, scans_bytes, scan_offsets_host, out, out_bytes,
+                         out_offsets_host, status, workspace, workspace_bytes, boxes_host, nullptr, true);
 }
 
 extern "C" int aej_jpegdec_batch_adobe(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host, const int *components_host,
@@ -629,7 +689,8 @@ extern "C" int aej_jpegprog_parse_host_adobe(const uint8_t *data_host, uint64_t 
 }
 
 static uint64_t jpegprog_workspace(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n, const int *scales_host,
-                                   const int *components_host = nullptr, const int32_t *boxes_host = nullptr, const aej_jpeg_adobe *adobe_host = nullptr)
+                                   const int *components_host = nullptr, const int32_t *boxes_host = nullptr, const aej_jpeg_adobe *adobe_host = nullptr,
+                                   bool sbox = false)
 {
     JpLayout y;
     std::vector<int> shifts, comps3;
@@ -641,7 +702,8 @@ static uint64_t jpegprog_workspace(aej_ctx *ctx, const aej_jpegprog_frame *frame
         if (components_host) components_host = comps3.data();
     }
     if (!ctx || !scale_shifts(scales_host, n, shifts, nullptr, components_host)) return 0;
-    if (boxes_host && (!frames_host || !boxes_ok(frames_host, n, boxes_host, shifts, &bad, &unsupported))) return 0;
+    if (boxes_host && (!frames_host || !boxes_ok(frames_host, n, boxes_host, shifts, &bad, &unsupported, sbox))) return 0;
+    if (sbox && boxes_host) sbox_shifts(frames_host, n, boxes_host, shifts);
     if (adobe_host) {
         if (adobe_unbuilt(frames_host, n, adobe_host, shifts, boxes_host, &bad)) return 0;
         adobe_shifts(n, components4, shifts);
@@ -674,6 +736,12 @@ extern "C" uint64_t aej_jpegprog_workspace_bytes_box(aej_ctx *ctx, const aej_jpe
     return jpegprog_workspace(ctx, frames_host, scans_host, n, scales_host, components_host, boxes_host);
 }
 
+extern "C" uint64_t aej_jpegprog_workspace_bytes_sbox(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
+                                                      const int *scales_host, const int *components_host, const int32_t *boxes_host)
+{
+    return jpegprog_workspace(ctx, frames_host, scans_host, n, scales_host, components_host, boxes_host, nullptr, true);
+}
+
 extern "C" uint64_t aej_jpegprog_workspace_bytes_adobe(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
                                                        const int *scales_host, const int *components_host, const int32_t *boxes_host,
                                                        const aej_jpeg_adobe *adobe_host)
@@ -686,7 +754,7 @@ static int jpegprog_run(aej_ctx *ctx, const char *fn, const aej_jpegprog_frame *
                         const int *scales_host, const uint8_t *data, uint64_t data_bytes, const int64_t *data_offsets_host, int n_levels, uint8_t *out, uint64_t out_bytes,
                         const int64_t *out_offsets_host, int16_t *coef_out, uint64_t coef_blocks, int32_t *status, void *workspace,
                         uint64_t workspace_bytes, const int *components_host = nullptr, const int32_t *boxes_host = nullptr,
-                        const aej_jpeg_adobe *adobe_host = nullptr)
+                        const aej_jpeg_adobe *adobe_host = nullptr, bool sbox = false)
 {
     if (!ctx) return AEJ_ERR_ARG;
     AEJ_TRY(refuse_in_flight(ctx, fn));
@@ -703,7 +771,8 @@ static int jpegprog_run(aej_ctx *ctx, const char *fn, const aej_jpegprog_frame *
     AEJ_TRY(check_scales(ctx, fn, scales_host, n, shifts, components_host));
     if (boxes_host) {                                        // the frames' sizes are read: the checks jpegprog_layout starts with, first
         if (!frames_host || n < 1) return fail(ctx, AEJ_ERR_ARG, "%s: no files, or descriptors aej_jpegprog_parse_host did not write", fn);
-        AEJ_TRY(check_boxes(ctx, fn, frames_host, n, boxes_host, shifts));
+        AEJ_TRY(check_boxes(ctx, fn, frames_host, n, boxes_host, shifts, sbox));
+        if (sbox) sbox_shifts(frames_host, n, boxes_host, shifts);
     }
     if (adobe_host) {
         AEJ_TRY(check_adobe(ctx, fn, frames_host, n, adobe_host, shifts, boxes_host));
@@ -767,6 +836,16 @@ extern "C" int aej_jpegprog_batch_box(aej_ctx *ctx, const aej_jpegprog_frame *fr
     if (!out) return ctx ? null_buffer(ctx, __func__) : AEJ_ERR_ARG;
     return jpegprog_run(ctx, __func__, frames_host, scans_host, n, scales_host, data, data_bytes, data_offsets_host, 1 << 30, out, out_bytes,
                         out_offsets_host, nullptr, 0, status, workspace, workspace_bytes, components_host, boxes_host);
+}
+
+extern "C" int aej_jpegprog_batch_sbox(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
+                                       const int *scales_host, const int *components_host, const int32_t *boxes_host, const uint8_t *data,
+                                       uint64_t data_bytes, const int64_t *data_offsets_host, uint8_t *out, uint64_t out_bytes,
+                                       const int64_t *out_offsets_host, int32_t *status, void *workspace, uint64_t workspace_bytes)
+{
+    if (!out) return ctx ? null_buffer(ctx, __func__) : AEJ_ERR_ARG;
+    return jpegprog_run(ctx, __func__, frames_host, scans_host, n, scales_host, data, data_bytes, data_offsets_host, 1 << 30, out, out_bytes,
+                        out_offsets_host, nullptr, 0, status, workspace, workspace_bytes, components_host, boxes_host, nullptr, true);
 }
 
 extern "C" int aej_jpegprog_batch_adobe(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,

@@ -16,22 +16,23 @@ extern "C" int aej_resample_taps_host(int in_size, float in0, float in1, int out
 }
 
 // the plan of a call, or the refusal of its first bad descriptor (fn NULL: quietly, for the size query)
-static int resample_layout(aej_ctx *ctx, const char *fn, const aej_resample_desc *descs_host, int n, bool fill, RsPlan &plan, const int *channels_host)
+static int resample_layout(aej_ctx *ctx, const char *fn, const aej_resample_desc *descs_host, int n, bool fill, RsPlan &plan, const int *channels_host,
+                           const int32_t *windows_host = nullptr)
 {
     if (n < 1) return fn ? fail(ctx, AEJ_ERR_ARG, "%s: no images", fn) : AEJ_ERR_ARG;
     const char *why = nullptr;
     int code = AEJ_ERR_ARG;
-    const int bad = resample_plan(descs_host, n, fill, plan, &why, &code, channels_host);
+    const int bad = resample_plan(descs_host, n, fill, plan, &why, &code, channels_host, windows_host);
     if (bad >= 0) return fn ? fail(ctx, code, "%s: image %d: %s", fn, bad, why) : code;
     for (int s = 0; s < 6; s++)
         if (plan.tiles[s / 3][s % 3] > 0x7fffffffLL) return fn ? fail(ctx, AEJ_ERR_UNSUPPORTED, "%s: more than 2^31 workgroups in one launch", fn) : AEJ_ERR_UNSUPPORTED;
     return 0;
 }
 
-static uint64_t resample_workspace(aej_ctx *ctx, const aej_resample_desc *descs_host, int n, const int *channels_host)
+static uint64_t resample_workspace(aej_ctx *ctx, const aej_resample_desc *descs_host, int n, const int *channels_host, const int32_t *windows_host = nullptr)
 {
     RsPlan plan;
-    if (!ctx || !descs_host || resample_layout(ctx, nullptr, descs_host, n, false, plan, channels_host)) return 0;
+    if (!ctx || !descs_host || resample_layout(ctx, nullptr, descs_host, n, false, plan, channels_host, windows_host)) return 0;
     RsBufs w;
     return resample_carve(nullptr, plan, w);
 }
@@ -46,14 +47,21 @@ extern "C" uint64_t aej_resample_workspace_bytes_ch(aej_ctx *ctx, const aej_resa
     return resample_workspace(ctx, descs_host, n, channels_host);
 }
 
-// aej_resample_batch (channels_host NULL: every image three channels) and aej_resample_batch_ch
+extern "C" uint64_t aej_resample_workspace_bytes_win(aej_ctx *ctx, const aej_resample_desc *descs_host, int n, const int *channels_host,
+                                                     const int32_t *windows_host)
+{
+    return resample_workspace(ctx, descs_host, n, channels_host, windows_host);
+}
+
+// aej_resample_batch (channels_host NULL: every image three channels), aej_resample_batch_ch and aej_resample_batch_win (windows_host)
 static int resample_batch(aej_ctx *ctx, const char *fn, const aej_resample_desc *descs_host, int n, const int *channels_host, const uint8_t *src,
-                          uint64_t src_bytes, uint8_t *dst, uint64_t dst_bytes, void *workspace, uint64_t workspace_bytes)
+                          uint64_t src_bytes, uint8_t *dst, uint64_t dst_bytes, void *workspace, uint64_t workspace_bytes,
+                          const int32_t *windows_host = nullptr)
 {
     AEJ_TRY(enter(ctx, fn));
     if (!descs_host || !src || !dst || !workspace) return null_buffer(ctx, fn);
     RsPlan plan;
-    AEJ_TRY(resample_layout(ctx, fn, descs_host, n, true, plan, channels_host));
+    AEJ_TRY(resample_layout(ctx, fn, descs_host, n, true, plan, channels_host, windows_host));
     for (int i = 0; i < n; i++) {
         const RsImage &im = plan.images[i];
         if ((uint64_t)im.src_offset + (uint64_t)im.src_bytes > src_bytes) return fail(ctx, AEJ_ERR_ARG, "%s: image %d: source outside the input", fn, i);
@@ -79,4 +87,11 @@ extern "C" int aej_resample_batch_ch(aej_ctx *ctx, const aej_resample_desc *desc
                                      uint64_t src_bytes, uint8_t *dst, uint64_t dst_bytes, void *workspace, uint64_t workspace_bytes)
 {
     return resample_batch(ctx, __func__, descs_host, n, channels_host, src, src_bytes, dst, dst_bytes, workspace, workspace_bytes);
+}
+
+extern "C" int aej_resample_batch_win(aej_ctx *ctx, const aej_resample_desc *descs_host, int n, const int *channels_host, const int32_t *windows_host,
+                                      const uint8_t *src, uint64_t src_bytes, uint8_t *dst, uint64_t dst_bytes, void *workspace,
+                                      uint64_t workspace_bytes)
+{
+    return resample_batch(ctx, __func__, descs_host, n, channels_host, src, src_bytes, dst, dst_bytes, workspace, workspace_bytes, windows_host);
 }

@@ -31,6 +31,10 @@
 //                   LDS, then jd_chroma / jd_rgb on the LDS planes, and only the box's pixels stored.  No sample planes.  In a call with
 //                   such a file k_jd_init / k_jd_sync / k_jd_write run as their <true> instantiation: a restart segment of a boxed file
 //                   that holds no MCU of the window's MCU rows is an idle slot to them, and only those rows' coefficients are stored
+//   k_jd_sbox       files of which a box of the SCALED image is decoded (scaled_box= of the Python call, the _sbox entries) at scale 2, 4 or 8,
+//                   in the place of k_jd_scaled / k_jd_scaled_h1v2 / k_jd_luma: k_jd_box's plan at m = 8 >> shift samples per block side, with
+//                   the reduced IDCTs and libjpeg's up-sampling rules at that scale.  The segment skip and the coefficient window of the
+//                   boxed files carry over unchanged (they work in MCUs)
 //   k_jd_init4 / k_jd_sync4 / k_jd_scan_slots4 / k_jd_write4   the slot kernels of a call that has a four-component (CMYK, YCCK) or RGB-coded
 //                   file (aej_jpegdec_batch_adobe), for all of its files: a fourth DC sum and prefix per slot, a 4-bit block slot in the packed
 //                   state, component 3 under the tables of the file's aej_jpeg_adobe; k_jd_fix4 between two k_jd_scan_slots4 for the files
@@ -910,6 +914,111 @@ __global__ __launch_bounds__(kJdThreads) void k_jd_box(const JdFile *__restrict_
     }
 }
 
+// The 8 x 8 block behind a call, for k_jd_sbox<1> alone (the 2m x 2m chroma IDCT of a 4:2:0 file at scale 2): a function of its own, not
+// jd_idct_block_call, because sharing that one changes how k_jd_scaled<1> compiles (the trap k_jd_luma<0> and k_jd_box met)
+__device__ __attribute__((noinline)) void jd_idct_block_sbox(const short *c, const uint16_t *qt, unsigned char *dst)
+{
+    jd_idct_block(c, qt, dst, kJdBoxW);
+}
+
+// one block at IDCT size kN (1, 2, 4 or 8) into an LDS plane of k_jd_sbox, kJdBoxW samples a row
+template <int kN>
+__device__ __forceinline__ void jd_sbox_idct(const short *c, const uint16_t *qt, unsigned char *dst)
+{
+    if constexpr (kN == 8) jd_idct_block_sbox(c, qt, dst);
+    else if constexpr (kN == 4) jd_idct4_block(c, qt, dst, kJdBoxW);
+    else if constexpr (kN == 2) jd_idct2_block(c, qt, dst, kJdBoxW);
+    else dst[0] = jd_range_limit(jd_descale((long long)((int)c[0] * (int)qt[0]), 3));
+}
+
+// Boxed reconstruction at scale 1 << kShift (kShift 1, 2, 3), coefficients -> the pixels of a box of the SCALED image in one kernel, for
+// every layout and both outputs, as k_jd_box does at full size.  m = 8 >> kShift samples per luma block side, so an MCU covers
+// hs * m x vs * m scaled pixels.  Workgroup `blockIdx.x` is tile g - grps_base[kShift - 1] of its file: tiles of kJdBoxW x kJdBoxH
+// scaled pixels -- TX = 128 / (hs * m) by TY = 32 / (vs * m) whole MCUs, for hs, vs in 1, 2 and m in 4, 2, 1 -- in row-major order over
+// the window win = (mx0, my0, mx1, my1) of jd_sbox_window, the grid anchored at the window's origin.  The tile's luma blocks go through
+// the m x m IDCT into sy; its chroma blocks go at nc = jd_chroma_idct_size(hs, vs, m) into scb / scr: 2m for 4:2:0 (the chroma comes
+// out at luma resolution), m otherwise, and then with a ring of one MCU on either side in the one direction libjpeg up-samples at that
+// scale -- columns for 4:2:2 at scales 2 and 4 when the scaled chroma is more than 2 wide (h2v1 fancy), rows for 4:4:0 at scales 2 and 4
+// (h1v2 fancy); replication (scale 8, narrow 4:2:2) has no ring -- the ring clipped to the window: by jd_sbox_window every sample a
+// pixel of the box reads lies in the window.  The pixels of the tile that lie in the box then run jd_sbox_chroma and jd_rgb (or leave
+// as luma where the file's shift carries kJdLuma; a one-component file: R = G = B) and are stored, byte by byte: a box's rows start at
+// any byte.  Every return in front of the barrier depends on the workgroup alone.  At scale 8 a tile is up to 4096 one-coefficient luma
+// blocks, so the IDCT loop makes several passes per thread.
+// LDS: three planes of kJdBoxH rows x kJdBoxW columns, 12 KiB.  Luma: TY * vs * m = 32 rows, TX * hs * m = 128 columns.  Chroma:
+// 4:4:4 / grey and 4:2:0 TY * nc = 32 rows x TX * nc = 128 columns; 4:2:2 32 rows x (TX + 2) * m = 64 + 2m <= 72 columns; 4:4:0
+// (TY + 2) * m = 16 + 2m <= 24 rows x 128 columns.
+// Bounds: MCU rows [cy0, cy1) and [ty0, ty1) lie in [win[1], win[3]), which the stored rows [row0, row0 + n_blocks / (mcux * bpm))
+// contain, and MCU columns in [win[0], win[2]) <= mcux, so block indices stay inside the file's stored coefficients; LDS rows and
+// columns stay below the figures above; a store goes to scaled pixel (y, x) with t <= y < b and l <= x < r only, at
+// out_off + ((y - t) * (r - l) + (x - l)) * channels, inside the box's image.
+template <int kShift>
+__global__ __launch_bounds__(kJdThreads) void k_jd_sbox(const JdFile *__restrict__ files, const aej_jpegdec_desc *__restrict__ descs, int n,
+                                                        const short *__restrict__ coef, unsigned char *__restrict__ out)
+{
+    constexpr int m = 8 >> kShift;
+    __shared__ unsigned char sy[kJdBoxH * kJdBoxW], scb[kJdBoxH * kJdBoxW], scr[kJdBoxH * kJdBoxW];
+    int lo = 0, hi = n - 1;                           // the last file whose first workgroup is <= blockIdx.x
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (files[mid].grps_base[kShift - 1] <= (long long)blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+    const JdFile &F = files[lo];
+    const aej_jpegdec_desc &d = descs[lo];
+    if (!(F.shift & kJdSbox) || (F.shift & (kJdLuma - 1)) != kShift) return;      // never: the host gives these workgroups to such files alone
+    const bool three = d.ncomp == 3, color = three && !(F.shift & kJdLuma);
+    const int hs = three ? d.hs : 1, vs = three ? d.vs : 1, nl = hs * vs, bpm = d.blocks_per_mcu;
+    if (hs > 2 || vs > 2) return;                     // never: the parsers admit these factors alone
+    const int TX = kJdBoxW / (hs * m), TY = kJdBoxH / (vs * m);
+    const int ntx = (F.win[2] - F.win[0] + TX - 1) / TX, g = (int)(blockIdx.x - F.grps_base[kShift - 1]);
+    const int tx0 = F.win[0] + (g % ntx) * TX, ty0 = F.win[1] + (g / ntx) * TY;
+    if (ty0 >= F.win[3]) return;                      // never: the host gives a file ntx * nty workgroups
+    const int tx1 = min(tx0 + TX, F.win[2]), ty1 = min(ty0 + TY, F.win[3]);
+    const bool wide = hs == 2 && vs == 2;             // 4:2:0: the chroma IDCT is 2m
+    const int nc = wide ? 2 * m : m;                  // jd_chroma_idct_size(hs, vs, m) for these factors
+    const int sw = (d.width + (1 << kShift) - 1) >> kShift, sh = (d.height + (1 << kShift) - 1) >> kShift;      // the scaled image
+    const int wc = (sw + 1) >> 1, hc = (sh + 1) >> 1; // the real chroma width (4:2:2) and height (4:4:0) at this scale
+    const bool h2v1 = color && hs == 2 && vs == 1, h1v2 = color && hs == 1 && vs == 2;
+    const bool fancy = kShift < 3 && ((h2v1 && wc > 2) || h1v2);      // libjpeg: no fancy up-sampling beside a 1 x 1 IDCT, nor for <= 2 samples a row
+    const int rx = h2v1 && fancy, ry = h1v2 && fancy; // the ring, in MCUs
+    const int cx0 = max(tx0 - rx, F.win[0]), cx1 = min(tx1 + rx, F.win[2]), cy0 = max(ty0 - ry, F.win[1]), cy1 = min(ty1 + ry, F.win[3]);
+    const int ntw = tx1 - tx0, nY = ntw * (ty1 - ty0) * nl, ncx = cx1 - cx0, nC = color ? 2 * ncx * (cy1 - cy0) : 0;
+    for (int i = threadIdx.x; i < nY + nC; i += kJdThreads) {
+        int mx, my, k, c;
+        unsigned char *dst;
+        if (i < nY) {
+            const int mcu = i / nl, ky = (i % nl) / hs, kx = (i % nl) % hs;
+            my = ty0 + mcu / ntw; mx = tx0 + mcu % ntw; k = i % nl; c = 0;
+            dst = sy + (((my - ty0) * vs + ky) * m) * kJdBoxW + ((mx - tx0) * hs + kx) * m;
+        } else {
+            const int j = (i - nY) >> 1;
+            c = 1 + ((i - nY) & 1); k = nl + c - 1;
+            my = cy0 + j / ncx; mx = cx0 + j % ncx;
+            dst = (c == 1 ? scb : scr) + ((my - cy0) * nc) * kJdBoxW + (mx - cx0) * nc;
+        }
+        const short *cf = coef + (F.blk_base + ((long long)(my - F.row0) * d.mcux + mx) * bpm + k) * 64;
+        if (c != 0 && wide) jd_sbox_idct<2 * m>(cf, d.qt[c], dst);
+        else jd_sbox_idct<m>(cf, d.qt[c], dst);
+    }
+    __syncthreads();
+    const int l = F.box[0], t = F.box[1], bw = F.box[2] - l;
+    const int px0 = max(l, tx0 * hs * m), px1 = min(F.box[2], tx1 * hs * m), py0 = max(t, ty0 * vs * m), py1 = min(F.box[3], ty1 * vs * m);
+    const int ncols = px1 - px0, npx = ncols > 0 && py1 > py0 ? ncols * (py1 - py0) : 0;
+    unsigned char *img = out + F.out_off;
+    // the file's scaled chroma sample (row, column) is at pcb[row * kJdBoxW + column]: only formed for rows and columns of [cy0, cy1) x [cx0, cx1)
+    const long long coff = (long long)cy0 * nc * kJdBoxW + cx0 * nc;
+    for (int p = threadIdx.x; p < npx; p += kJdThreads) {
+        const int y = py0 + p / ncols, x = px0 + p % ncols;
+        const int Y = sy[(y - ty0 * vs * m) * kJdBoxW + (x - tx0 * hs * m)];
+        const long long o = (long long)(y - t) * bw + (x - l);
+        if (!color) {
+            if (F.shift & kJdLuma) img[o] = (unsigned char)Y;
+            else { unsigned char *q = img + o * 3; q[0] = q[1] = q[2] = (unsigned char)Y; }
+            continue;
+        }
+        jd_rgb(Y, jd_sbox_chroma(scb, coff, h2v1, h1v2, fancy, wc, hc, y, x), jd_sbox_chroma(scr, coff, h2v1, h1v2, fancy, wc, hc, y, x), img + o * 3);
+    }
+}
+
 // ---- host: descriptor checks, layout and launch sequence -----------------------------------------------------------------------------------
 bool jpegdec_descs_ok(const aej_jpegdec_desc *d, int n, const aej_jpeg_adobe *adobe)
 {
@@ -940,14 +1049,17 @@ void jpeg_stream_layout(long long len, int n_segments, int S, JdFile &F, JdBufSi
 
 void jpeg_recon_layout(const aej_jpegdec_desc &d, int shift, JdFile &F, JdBufSizes &z, const int *box, bool window_coef, const aej_jpeg_adobe *x)
 {
-    const bool luma = (shift & kJdLuma) != 0, boxed = !jpeg_box_whole(d, box);
+    // a box: of the full-size image (the callers refuse one at another scale), or -- kJdSbox in shift, set by the _sbox entries for a box
+    // that is not the whole scaled image -- of the image at scale 2, 4 or 8
+    const bool luma = (shift & kJdLuma) != 0, sbox = (shift & kJdSbox) != 0, boxed = sbox || ((shift & (kJdLuma - 1)) == 0 && !jpeg_box_whole(d, box));
     F.blk_base = z.blocks;
     F.n_blocks = (long long)d.mcux * d.mcuy * d.blocks_per_mcu;
     F.row0 = 0;
     F.grpb_base = z.grpb;
-    if (boxed) {                                      // full size only (the callers refuse a box at another scale)
+    for (int s = 0; s < 3; s++) F.grps_base[s] = z.grps[s];
+    if (boxed) {
         for (int v = 0; v < 4; v++) F.box[v] = box[v];
-        jd_box_window(d.width, d.height, d.hs, d.vs, d.ncomp, luma, box, F.win);
+        jd_sbox_window(d.width, d.height, d.hs, d.vs, d.ncomp, luma, shift & (kJdLuma - 1), box, F.win);      // shift 0: jd_box_window
         if (window_coef) {                            // the window's MCU rows alone, at full width
             F.row0 = F.win[1];
             F.n_blocks = (long long)d.mcux * (F.win[3] - F.win[1]) * d.blocks_per_mcu;
@@ -974,11 +1086,12 @@ void jpeg_recon_layout(const aej_jpegdec_desc &d, int shift, JdFile &F, JdBufSiz
         return;
     }
     if (boxed) {                                      // no sample planes, no pixels of k_jd_rgb's, no workgroups but k_jd_box's
-        const int hs = d.ncomp == 3 ? d.hs : 1, vs = d.ncomp == 3 ? d.vs : 1, TX = kJdBoxW / (8 * hs), TY = kJdBoxH / (8 * vs);
+        const int m = 8 >> shift;                     // samples per luma block side: 8, or with kJdSbox 4, 2, 1
+        const int hs = d.ncomp == 3 ? d.hs : 1, vs = d.ncomp == 3 ? d.vs : 1, TX = kJdBoxW / (m * hs), TY = kJdBoxH / (m * vs);
         F.shift |= kJdBox;
         F.ow = box[2] - box[0]; F.oh = box[3] - box[1];
         F.pw0 = F.ph0 = F.pw1 = F.ph1 = 0;
-        z.grpb += (long long)((F.win[2] - F.win[0] + TX - 1) / TX) * ((F.win[3] - F.win[1] + TY - 1) / TY);
+        (sbox ? z.grps[shift - 1] : z.grpb) += (long long)((F.win[2] - F.win[0] + TX - 1) / TX) * ((F.win[3] - F.win[1] + TY - 1) / TY);
         return;
     }
     if (luma) {                                       // at every scale: no sample planes, no pixels of k_jd_rgb's, workgroups of k_jd_luma<shift>
@@ -1042,6 +1155,8 @@ unsigned long long jpegdec_carve(void *base, int n, const JdBufSizes &z, JdBufs 
 }
 
 static unsigned jd_grid(long long n) { return (unsigned)((n + kJdThreads - 1) / kJdThreads); }
+// a call with a boxed file, at full size or at a scale: the <true> slot kernels
+static bool jd_any_box(const JdBufSizes &z) { return z.grpb > 0 || z.grps[0] > 0 || z.grps[1] > 0 || z.grps[2] > 0; }
 
 // everything up to the first read-back: upload, un-stuffing, segments, first guesses
 hipError_t launch_jpegdec_begin(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, const void *blob_host, unsigned long long blob_bytes,
@@ -1054,7 +1169,7 @@ hipError_t launch_jpegdec_begin(hipStream_t st, int n, const JdBufSizes &z, cons
         hipLaunchKernelGGL(k_jd_init4, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.slots, w.segs, w.clean, w.sl, S,
                            w.last_change, w.adobe);
     } else {
-        hipLaunchKernelGGL(z.grpb > 0 ? k_jd_init<true> : k_jd_init<false>, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n,
+        hipLaunchKernelGGL(jd_any_box(z) ? k_jd_init<true> : k_jd_init<false>, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n,
                            z.slots, w.segs, w.clean, w.sl, S, w.last_change);
     }
     return hipGetLastError();
@@ -1082,7 +1197,7 @@ hipError_t launch_jpegdec_sync(hipStream_t st, int n, const JdBufSizes &z, const
             hipLaunchKernelGGL(k_jd_sync4, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.slots, w.segs, w.clean, w.sl, S, r,
                                w.last_change, w.adobe);
         else
-            hipLaunchKernelGGL(z.grpb > 0 ? k_jd_sync<true> : k_jd_sync<false>, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n,
+            hipLaunchKernelGGL(jd_any_box(z) ? k_jd_sync<true> : k_jd_sync<false>, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n,
                                z.slots, w.segs, w.clean, w.sl, S, r, w.last_change);
     }
     return hipGetLastError();
@@ -1104,7 +1219,7 @@ hipError_t launch_jpegdec_write(hipStream_t st, int n, const JdBufSizes &z, cons
         return hipGetLastError();
     }
     hipLaunchKernelGGL(k_jd_scan_slots, dim3(n), dim3(kJdScanThreads), 0, st, w.files, w.sl);
-    hipLaunchKernelGGL(z.grpb > 0 ? k_jd_write<true> : k_jd_write<false>, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.slots,
+    hipLaunchKernelGGL(jd_any_box(z) ? k_jd_write<true> : k_jd_write<false>, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.slots,
                        w.segs, w.clean, w.sl, S, w.coef, status);
     return hipGetLastError();
 }
@@ -1132,6 +1247,9 @@ static hipError_t launch_jpegdec_recon_scaled(hipStream_t st, int n, const JdBuf
     if (z.grpl[2] > 0) hipLaunchKernelGGL(k_jd_luma<2>, dim3((unsigned)z.grpl[2]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
     if (z.grpl[3] > 0) hipLaunchKernelGGL(k_jd_luma<3>, dim3((unsigned)z.grpl[3]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
     if (z.grpb > 0) hipLaunchKernelGGL(k_jd_box, dim3((unsigned)z.grpb), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
+    if (z.grps[0] > 0) hipLaunchKernelGGL(k_jd_sbox<1>, dim3((unsigned)z.grps[0]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
+    if (z.grps[1] > 0) hipLaunchKernelGGL(k_jd_sbox<2>, dim3((unsigned)z.grps[1]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
+    if (z.grps[2] > 0) hipLaunchKernelGGL(k_jd_sbox<3>, dim3((unsigned)z.grps[2]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
     if (z.grpa > 0) {                                 // the four-component and RGB-coded files: four sample planes, then their pixels
         hipLaunchKernelGGL(k_jd_idct4, dim3(jd_grid(z.blocks)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.blocks, w.coef, w.planes, w.adobe);
         hipLaunchKernelGGL(k_jd_adobe, dim3((unsigned)z.grpa), dim3(kJdThreads), 0, st, w.files, w.descs, w.adobe, n, w.planes, out);

@@ -18,6 +18,8 @@ constexpr int kJdAdobe = 16;           // a four-component or RGB-coded file (ae
 constexpr int kJdCmyk = 32;            // with kJdAdobe: the image leaves with four channels (Pillow's mode "CMYK"), not as RGB
 constexpr int kJdAdobePx = 4;          // pixels one thread of k_jd_adobe reconstructs: 12 or 16 output bytes, whole dwords
 constexpr int kJdBoxW = 128, kJdBoxH = 32;      // pixels of one tile of k_jd_box: a whole number of MCUs of every layout
+constexpr int kJdSbox = 64;            // with kJdBox, on a file decoded at scale 2, 4 or 8: the box is in pixels of the scaled image (k_jd_sbox;
+                                       // tiles of kJdBoxW x kJdBoxH scaled pixels, a whole number of the scaled MCUs of every layout too)
 
 // per-file layout of one aej_jpegdec_batch (host-computed, uploaded with the descriptors)
 struct JdFile {
@@ -43,6 +45,8 @@ struct JdFile {
     int row0;                          // first MCU row whose coefficients are stored (win[1] for a baseline file, 0 for a progressive
                                        // one): block b of MCU (my, mx) is blk_base + ((my - row0) * mcux + mx) * blocks_per_mcu + b
     long long grpa_base;               // first workgroup of the file in k_jd_adobe's grid (shift & kJdAdobe)
+    long long grps_base[3];            // [log2 scale - 1]: first workgroup of the file in k_jd_sbox<log2 scale>'s grid (shift & kJdSbox): box and
+                                       // win are then in pixels and MCUs of the scaled image (jd_sbox_window), ow, oh the box's
     int pw3, ph3;                      // such a file's fourth plane (whole MCUs; behind the three others), 0 x 0 for three components
     int uniform;                       // such a baseline file whose components all decode under one DC and one AC table (what libjpeg writes
                                        // for CMYK and RGB): its bits say nothing about the block slot, which the kFour kernels then take from
@@ -401,6 +405,61 @@ AEJ_HD inline void jd_box_window(int width, int height, int hs, int vs, int ncom
     if (j1 / 8 + 1 > win[2]) win[2] = j1 / 8 + 1;
     if (i0 / 8 < win[1]) win[1] = i0 / 8;
     if (i1 / 8 + 1 > win[3]) win[3] = i1 / 8 + 1;
+}
+
+// jd_box_window for a box (l, t, r, b) in pixels of the image scaled by 1 << shift, ow = ceil(width >> shift) by oh (shift 0: jd_box_window
+// itself).  With m = 8 >> shift an MCU covers hs * m x vs * m scaled pixels.  The chroma follows libjpeg at that scale
+// (jd_chroma_idct_size; k_jd_scaled, k_jd_scaled_h1v2): 4:4:4 and 4:2:0 chroma comes out of its IDCT at luma resolution, so a pixel
+// reads its own MCU alone; 4:2:2 chroma (m wide per MCU) is up-sampled h2v1 fancy at scales 2 and 4 when the scaled chroma width
+// (ow + 1) >> 1 exceeds 2 -- one neighbour column after the edge clamps -- and replicated otherwise; 4:4:0 chroma is up-sampled h1v2
+// fancy at scales 2 and 4 -- one neighbour row after the clamps, at any width -- and replicated at scale 8.  Exact, as jd_box_window.
+AEJ_HD inline void jd_sbox_window(int width, int height, int hs, int vs, int ncomp, bool luma_only, int shift, const int *box, int *win)
+{
+    if (shift == 0) { jd_box_window(width, height, hs, vs, ncomp, luma_only, box, win); return; }
+    if (ncomp != 3) hs = vs = 1;
+    const int m = 8 >> shift, l = box[0], t = box[1], r = box[2], b = box[3];
+    win[0] = l / (hs * m); win[2] = (r - 1) / (hs * m) + 1;      // the luma samples: the pixels themselves
+    win[1] = t / (vs * m); win[3] = (b - 1) / (vs * m) + 1;
+    if (ncomp != 3 || luma_only || hs == vs || shift == 3) return;      // no chroma, chroma at luma resolution, or replication: the pixel's own MCU
+    const int ow = (width + (1 << shift) - 1) >> shift, oh = (height + (1 << shift) - 1) >> shift;
+    if (hs == 2) {                                    // h2v1: chroma sample j lies in MCU column j / m
+        const int wc = (ow + 1) >> 1;
+        if (wc <= 2) return;
+        int j0 = l >> 1, j1 = (r - 1) >> 1;
+        if ((l & 1) == 0 && j0 > 0) j0--;
+        if (((r - 1) & 1) && j1 < wc - 1) j1++;
+        if (j0 / m < win[0]) win[0] = j0 / m;
+        if (j1 / m + 1 > win[2]) win[2] = j1 / m + 1;
+    } else {                                          // h1v2: chroma row i lies in MCU row i / m
+        const int hc = (oh + 1) >> 1;
+        int i0 = t >> 1, i1 = (b - 1) >> 1;
+        if ((t & 1) == 0 && i0 > 0) i0--;
+        if (((b - 1) & 1) && i1 < hc - 1) i1++;
+        if (i0 / m < win[1]) win[1] = i0 / m;
+        if (i1 / m + 1 > win[3]) win[3] = i1 / m + 1;
+    }
+}
+
+// the chroma sample of scaled pixel (y, x) for k_jd_sbox, from a part of the scaled chroma plane held in LDS, kJdBoxW samples a row,
+// where the file's scaled chroma sample (row, column) is p[row * kJdBoxW + column - off]: k_jd_scaled's h2v1 rule (fancy: jd_h2v1, of
+// which only the neighbour the pixel's parity selects is read -- the other may lie outside the part), k_jd_scaled_h1v2's h1v2 rule,
+// or the sample at the pixel's own place (4:4:4, 4:2:0).  wc, hc: the scaled chroma plane's real width and height
+AEJ_HD inline int jd_sbox_chroma(const unsigned char *p, long long off, bool h2v1, bool h1v2, bool fancy, int wc, int hc, int y, int x)
+{
+    const long long W = kJdBoxW;
+    if (h2v1) {
+        const int j = x >> 1;
+        const long long r0 = y * W - off;
+        const int cur = p[r0 + j];
+        if (!fancy) return cur;
+        if ((x & 1) == 0) return j == 0 ? cur : (3 * cur + p[r0 + j - 1] + 1) >> 2;
+        return j == wc - 1 ? cur : (3 * cur + p[r0 + j + 1] + 2) >> 2;
+    }
+    if (h1v2) {
+        const int cur = p[(y >> 1) * W + x - off];
+        return fancy ? jd_h1v2(cur, p[jd_h1v2_far(y, hc) * W + x - off], y) : cur;
+    }
+    return p[y * W + x - off];
 }
 
 AEJ_HD inline void jd_rgb(int Y, int cb, int cr, unsigned char *o)

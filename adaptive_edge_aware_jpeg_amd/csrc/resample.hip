@@ -272,13 +272,41 @@ static long long rs_table(RsPlan &plan, std::vector<RsTableKey> &keys, std::vect
 // fill = false: sizes only (aej_resample_workspace_bytes); the bounds of the vertical tables are needed either way (they size the
 // horizontal pass), so those are computed on the side.  channels (may be NULL: every image 3): 3 or 1 per image, the bytes of a pixel;
 // the images of either count form launches of their own (RsPlan::count, ::tiles).  -> -1, or the first descriptor refused (*why, *code)
-int resample_plan(const aej_resample_desc *descs, int n, bool fill, RsPlan &plan, const char **why, int *code, const int *channels)
+// windows (may be NULL: none; the _win entries): [n][4] x0, y0, vw, vh -- the stored source of image i, src_w x src_h, is the rectangle
+// [y0, y0 + src_h) x [x0, x0 + src_w) of a virtual image vw x vh in whose coordinates box and reduce_box are.  Everything is planned
+// from the virtual size -- the tables are those of the whole image, rs_taps never sees a shifted origin -- and only the first stage's
+// base pointer (RsImage::win_shift, which may point before the stored bytes: no byte outside them is read) and pitch move.  Refused
+// here, on the host: a window outside its virtual image, and a tap with a non-zero count or a reduce box that reaches outside the
+// stored rectangle.
+static bool rs_axis_inside(int in_size, float in0, float in1, int out_size, int f, int lo, int hi)
+{
+    for (int xx = 0; xx < out_size; xx++) {
+        int b[2];
+        rs_bounds_of_row(in_size, in0, in1, out_size, f, xx, b);
+        if (b[1] > 0 && (b[0] < lo || b[0] + b[1] > hi)) return false;
+    }
+    return true;
+}
+
+int resample_plan(const aej_resample_desc *descs, int n, bool fill, RsPlan &plan, const char **why, int *code, const int *channels, const int *windows)
 {
     plan = RsPlan{};
     std::vector<RsTableKey> keys;
     std::vector<long long> where;
     for (int i = 0; i < n; i++) {
-        const aej_resample_desc &d = descs[i];
+        aej_resample_desc d = descs[i];
+        const int sw = d.src_w, sh = d.src_h;        // the stored rectangle: its pitch and rows
+        int wx0 = 0, wy0 = 0;
+        if (windows) {
+            const int *q = windows + 4 * i;
+            *code = AEJ_ERR_ARG;
+            if (sw < 1 || sh < 1 || q[0] < 0 || q[1] < 0 || q[2] < 1 || q[3] < 1 || q[2] > 65535 || q[3] > 65535 || (long long)q[0] + sw > q[2] ||
+                (long long)q[1] + sh > q[3]) {
+                *why = "a window (x0, y0, vw, vh) that does not hold the stored src_w x src_h rectangle";
+                return i;
+            }
+            wx0 = q[0]; wy0 = q[1]; d.src_w = q[2]; d.src_h = q[3];      // planned as the whole virtual image
+        }
         if ((*why = rs_check(d, code)) != nullptr) return i;
         const int ch = channels ? channels[i] : 3;
         if (ch != 1 && ch != 3) { *why = "a channel count other than 1 or 3"; *code = AEJ_ERR_ARG; return i; }
@@ -290,10 +318,14 @@ int resample_plan(const aej_resample_desc *descs, int n, bool fill, RsPlan &plan
         if (im.reduce) {
             const int *r = d.reduce_box;
             RsReduce &e = im.r;
-            e.bw = r[2] - r[0]; e.bh = r[3] - r[1]; e.fx = d.reduce_x; e.fy = d.reduce_y; e.in_w = d.src_w;
+            e.bw = r[2] - r[0]; e.bh = r[3] - r[1]; e.fx = d.reduce_x; e.fy = d.reduce_y; e.in_w = sw;
+            if (windows && (r[0] < wx0 || r[1] < wy0 || r[2] > wx0 + sw || r[3] > wy0 + sh)) {
+                *why = "a reduce box that reaches outside the stored window"; *code = AEJ_ERR_ARG;
+                return i;
+            }
             e.out_w = w = (e.bw + e.fx - 1) / e.fx;
             e.out_h = h = (e.bh + e.fy - 1) / e.fy;
-            im.r_src = d.src_offset + ((long long)r[1] * d.src_w + r[0]) * ch;
+            im.r_src = d.src_offset + ((long long)(r[1] - wy0) * sw + (r[0] - wx0)) * ch;
             e.tile_base = tiles[0];
             tiles[0] += rs_tiles((long long)w * h);
             im.tmp_a = plan.tmp_bytes;
@@ -304,6 +336,14 @@ int resample_plan(const aej_resample_desc *descs, int n, bool fill, RsPlan &plan
         im.vertical = d.dst_h != h || b[1] != 0 || b[3] != (float)d.dst_h;
         const bool copy = !im.reduce && !im.horizontal && !im.vertical;
         int first = 0, last = h;
+        if (windows && !im.reduce) {                  // the first stage reads the stored rectangle: every tap inside it
+            const bool cols = im.horizontal ? rs_axis_inside(w, b[0], b[2], d.dst_w, d.filter, wx0, wx0 + sw) : wx0 == 0 && sw == w;
+            const bool rows = im.vertical ? rs_axis_inside(h, b[1], b[3], d.dst_h, d.filter, wy0, wy0 + sh) : wy0 == 0 && sh == h;
+            if (!cols || !rows) {
+                *why = "a tap that reaches outside the stored window"; *code = AEJ_ERR_ARG;
+                return i;
+            }
+        }
         if (im.vertical || copy) {
             RsConv &e = im.v;
             e.ksize = copy ? 1 : rs_ksize(b[1], b[3], d.dst_h, d.filter);
@@ -318,6 +358,7 @@ int resample_plan(const aej_resample_desc *descs, int n, bool fill, RsPlan &plan
             }
             e.shift = first;
             e.in_w = e.out_w = d.dst_w; e.out_h = d.dst_h;
+            if (windows && !im.reduce && !im.horizontal) e.in_w = sw;      // reads the stored rectangle itself
             e.tile_base = tiles[2];
             tiles[2] += rs_tiles((long long)e.out_w * e.out_h);
         }
@@ -326,7 +367,7 @@ int resample_plan(const aej_resample_desc *descs, int n, bool fill, RsPlan &plan
             e.ksize = rs_ksize(b[0], b[2], d.dst_w, d.filter);
             const RsTableKey key{1, w, d.dst_w, d.filter, b[0], b[2]};
             im.h_table = rs_table(plan, keys, where, key, e.ksize, false, fill);
-            e.in_w = w; e.out_w = d.dst_w; e.out_h = last - first; e.shift = first;
+            e.in_w = windows && !im.reduce ? sw : w; e.out_w = d.dst_w; e.out_h = last - first; e.shift = first;
             e.tile_base = tiles[1];
             tiles[1] += rs_tiles((long long)e.out_w * e.out_h);
             if (im.vertical) {
@@ -335,7 +376,8 @@ int resample_plan(const aej_resample_desc *descs, int n, bool fill, RsPlan &plan
             }
         }
         im.src_offset = d.src_offset; im.dst_offset = d.dst_offset;
-        im.src_bytes = (long long)d.src_w * d.src_h * ch; im.dst_bytes = (long long)d.dst_w * d.dst_h * ch;
+        im.win_shift = windows && !im.reduce ? -((long long)wy0 * sw + wx0) * ch : 0;
+        im.src_bytes = (long long)sw * sh * ch; im.dst_bytes = (long long)d.dst_w * d.dst_h * ch;
         int *count = plan.count[ch == 1];
         count[0] += im.reduce; count[1] += im.horizontal; count[2] += im.vertical || copy;
         plan.images.push_back(im);
@@ -373,7 +415,7 @@ void resample_blob(const RsPlan &plan, const RsBufs &w, const unsigned char *src
     const int *ints = (const int *)(w.blob + entries);
     if (plan.n_ints) memcpy(blob.data() + entries, plan.ints.data(), 4 * plan.n_ints);
     for (const RsImage &im : plan.images) {
-        const unsigned char *in = src + im.src_offset;
+        const unsigned char *in = src + im.src_offset + im.win_shift;      // pixel (0, 0) of the virtual image, were it stored
         unsigned char *out = dst + im.dst_offset;
         const bool copy = !im.reduce && !im.horizontal && !im.vertical;
         RsReduce *&r = rr[im.ch == 1];

@@ -99,6 +99,23 @@ def _safe_box(size_img, size, f, box):
             min(size_img[0], math.ceil(box[2] + fsup * sx)), min(size_img[1], math.ceil(box[3] + fsup * sy)))
 
 
+def _tap_hull(in_size, in0, in1, out_size, f):
+    """(first, end) source indices one axis of a resize reads: the first tap of output 0 to the end of the last output's taps -- the
+    window arithmetic of aej_resample_taps_host's bounds (rs_window, csrc/resample.hip: float32 box edges and their float32
+    difference, the rest in double) for those two outputs alone, without the tables"""
+    a, b = np.float32(in0), np.float32(in1)
+    scale = float(b - a) / out_size
+    support = _SUPPORT[f] * (1.0 if scale < 1.0 else scale)
+
+    def window(xx):
+        center = float(a) + (xx + 0.5) * scale
+        lo, hi = max(int(center - support + 0.5), 0), min(int(center + support + 0.5), in_size)
+        return lo, max(hi - lo, 0)
+
+    first, (lo, cnt) = window(0)[0], window(out_size - 1)
+    return first, lo + cnt
+
+
 def reduce_factors(box, size, gap):
     """the integer factors Image.resize reduces by first under reducing_gap=gap"""
     if gap is None:
@@ -139,10 +156,11 @@ def _steps(what, W, H, size, box, f, gap):
     return step
 
 
-def _run(ctx, src, src_bytes, src_off, steps, f, channels=None):
+def _run(ctx, src, src_bytes, src_off, steps, f, channels=None, windows=None, packed=False):
     """aej_resample_batch over the images at src + src_off[i] -> list of uint8 [h, w, 3] views into one packed allocation.
     f: one filter per image.  channels (None: every image 3): 3 or 1 per image; with a 1 among them the call is aej_resample_batch_ch
-    and that image's view is [h, w]."""
+    and that image's view is [h, w].  windows (int32 [n, 4] x0, y0, vw, vh; None: none): aej_resample_batch_win -- step i's src is the
+    stored rectangle at (x0, y0) of a virtual vw x vh image in whose coordinates its boxes are.  packed: -> the packed allocation itself."""
     from ._lib import ResampleDesc
     t, lib, n = ctx.torch, ctx.lib, len(steps)
     descs = (ResampleDesc * n)()
@@ -164,10 +182,15 @@ def _run(ctx, src, src_bytes, src_off, steps, f, channels=None):
     if any(c != 3 for c in ch):                      # every image RGB: the entries without channels, as before
         cc = np.array(ch, np.int32)
         how, sfx = (cc.ctypes.data,), "_ch"
+    if windows is not None:
+        cc, ww = np.array(ch, np.int32), np.ascontiguousarray(windows, np.int32)
+        how, sfx = (cc.ctypes.data, ww.ctypes.data), "_win"
     nws = int(getattr(lib, "aej_resample_workspace_bytes" + sfx)(ctx.handle, ctypes.addressof(descs), n, *how))
     ws = ctx.workspace(max(nws, 256))
     ctx.check(getattr(lib, "aej_resample_batch" + sfx)(ctx.handle, ctypes.addressof(descs), n, *how, ctypes.c_void_p(src), ctypes.c_uint64(src_bytes),
                                                        out.data_ptr(), ctypes.c_uint64(pos), ws.data_ptr(), ctypes.c_uint64(ws.numel())))
+    if packed:
+        return out
     return [out[o:o + s["dst"][0] * s["dst"][1] * c].view(*((s["dst"][1], s["dst"][0]) + ((3,) if c == 3 else ())))
             for o, s, c in zip(dst_off, steps, ch)]
 

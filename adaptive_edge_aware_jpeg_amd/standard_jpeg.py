@@ -50,6 +50,7 @@ and every requested quality reuses them (csrc/jfif.hip, ``aej_jfif_*`` in includ
 taken as ``rint(x * 255)`` -- the exact inverse of ``Image.load``'s ``uint8 / 255``.
 """
 import ctypes
+import math
 from typing import List, Sequence, Tuple
 
 import numpy as np
@@ -380,7 +381,7 @@ def _adobe_array(frames):
     return (JpegAdobe * len(xs))(*[x if x is not None else JpegAdobe() for x in xs])
 
 
-def _decode_baseline(ctx, idx, parsed, views, out, out_off, scales=None, comps=None, boxes=None):
+def _decode_baseline(ctx, idx, parsed, views, out, out_off, scales=None, comps=None, boxes=None, sbox=False):
     """aej_jpegdec_batch (scales None), aej_jpegdec_batch_scaled, (comps: 3 or 1 per file) aej_jpegdec_batch_mode or (boxes: int32
     [n, 4]) aej_jpegdec_batch_box over the files idx -> their status words (device int32).  With a four-component or RGB-coded file
     among them (adobe=True alone parses one): aej_jpegdec_batch_adobe, comps 4 for a file that leaves in mode "CMYK"."""
@@ -402,6 +403,8 @@ def _decode_baseline(ctx, idx, parsed, views, out, out_off, scales=None, comps=N
         bb = np.ascontiguousarray(boxes[idx], np.int32)
         how = (sc[0].ctypes.data if sc else None, cc.ctypes.data if comps is not None else None, bb.ctypes.data)
         nbytes, batch = lib.aej_jpegdec_workspace_bytes_box, lib.aej_jpegdec_batch_box
+        if sbox:                                         # the boxes are in pixels of each file's scaled image
+            nbytes, batch = lib.aej_jpegdec_workspace_bytes_sbox, lib.aej_jpegdec_batch_sbox
     xs = _adobe_array([parsed[i] for i in idx])
     if xs is not None:
         how = (sc[0].ctypes.data if sc else None, cc.ctypes.data if comps is not None else None, bb.ctypes.data if boxes is not None else None,
@@ -417,7 +420,7 @@ def _decode_baseline(ctx, idx, parsed, views, out, out_off, scales=None, comps=N
     return status
 
 
-def _decode_progressive(ctx, idx, parsed, views, out, out_off, scales=None, comps=None, boxes=None):
+def _decode_progressive(ctx, idx, parsed, views, out, out_off, scales=None, comps=None, boxes=None, sbox=False):
     """aej_jpegprog_batch (scales None), aej_jpegprog_batch_scaled, (comps) aej_jpegprog_batch_mode or (boxes) aej_jpegprog_batch_box
     over the files idx -> their status words (device int32)"""
     from ._lib import JpegProgFrame, JpegProgScan
@@ -440,6 +443,8 @@ def _decode_progressive(ctx, idx, parsed, views, out, out_off, scales=None, comp
         bb = np.ascontiguousarray(boxes[idx], np.int32)
         how = (sc[0].ctypes.data if sc else None, cc.ctypes.data if comps is not None else None, bb.ctypes.data)
         nbytes, batch = lib.aej_jpegprog_workspace_bytes_box, lib.aej_jpegprog_batch_box
+        if sbox:
+            nbytes, batch = lib.aej_jpegprog_workspace_bytes_sbox, lib.aej_jpegprog_batch_sbox
     xs = _adobe_array([parsed[i][0] for i in idx])        # a four-component or RGB-coded file among them: the _adobe entries
     if xs is not None:
         how = (sc[0].ctypes.data if sc else None, cc.ctypes.data if comps is not None else None, bb.ctypes.data if boxes is not None else None,
@@ -525,7 +530,7 @@ def _box_in_image(box, width, height, index):
         raise ValueError(f"file {index}: box {box!r} is empty, inverted or leaves the {width} x {height} image (nothing is padded)")
 
 
-def decode_box_window(width: int, height: int, hs: int, vs: int, ncomp: int, box, luma: bool = False):
+def decode_box_window(width: int, height: int, hs: int, vs: int, ncomp: int, box, luma: bool = False, scale: int = 1):
     """The MCU window of a boxed decode (host only): (mx0, my0, mx1, my1), the half-open rectangle of MCUs -- 8 hs x 8 vs pixels each,
     8 x 8 for a one-component file -- whose blocks the pixels of box = (left, top, right, bottom) read in a width x height file with
     luma sampling factors hs x vs (1 x 1, 2 x 1, 2 x 2, 1 x 2) and ncomp components.  That is the MCUs of the luma samples of those
@@ -533,11 +538,36 @@ def decode_box_window(width: int, height: int, hs: int, vs: int, ncomp: int, box
     plus one neighbour in each up-sampled direction (h2v2: the far row and columns j +- 1; h2v1: columns; h1v2: rows), after the edge
     rules of the FILE's chroma plane (no neighbour past its first or last sample; a plane at most 2 wide is replicated: no neighbour
     at all).  The bounding rectangle is exact.  luma=True: the window of a mode "L" decode, the luma samples' alone.  The C twin is
-    aej_jpegdec_box_window_host.  ValueError for a box that is empty or leaves the image, TypeError for one that is not four integers."""
+    aej_jpegdec_box_window_host.  ValueError for a box that is empty or leaves the image, TypeError for one that is not four integers.
+    scale (1, 2, 4 or 8; 1: all of the above): the window of scaled_box=, a box in pixels of the image decoded at that scale,
+    ceil(width / scale) x ceil(height / scale), whose MCUs cover 8 hs / scale x 8 vs / scale scaled pixels.  The chroma follows libjpeg
+    at that scale: 4:4:4 and 4:2:0 chroma comes out of its inverse DCT at luma resolution (the pixel's own MCU alone); 4:2:2 chroma is
+    up-sampled h2v1 fancy at scales 2 and 4 when the scaled chroma plane is more than 2 wide (one neighbour column after the clamps)
+    and replicated otherwise; 4:4:0 chroma is up-sampled h1v2 fancy at scales 2 and 4 (one neighbour row) and replicated at scale 8.
+    The C twin is aej_jpegdec_sbox_window_host."""
     box = _check_decode_box(box, "decode_box_window")
     width, height, hs, vs, ncomp = int(width), int(height), int(hs), int(vs), int(ncomp)
     if width < 1 or height < 1 or ncomp not in (1, 3) or (ncomp == 3 and (hs not in (1, 2) or vs not in (1, 2))):
         raise ValueError(f"decode_box_window: a {width} x {height} file of {ncomp} components sampled {hs} x {vs}")
+    scale = _check_scale(scale)
+    if scale != 1:
+        ow, oh, m = -(-width // scale), -(-height // scale), 8 // scale
+        _box_in_image(box, ow, oh, 0)
+        if ncomp == 1:
+            hs = vs = 1
+        l, t, r, b = box
+        mx0, mx1, my0, my1 = l // (hs * m), (r - 1) // (hs * m) + 1, t // (vs * m), (b - 1) // (vs * m) + 1
+        if ncomp == 3 and not luma and hs != vs and scale != 8:
+            def reach(a0, a1, nc):                   # first and last chroma sample the fancy filter reads for luma samples a0 .. a1
+                j0, j1 = a0 >> 1, a1 >> 1
+                return j0 - (1 if a0 % 2 == 0 and j0 > 0 else 0), j1 + (1 if a1 % 2 == 1 and j1 < nc - 1 else 0)
+            if hs == 2 and (ow + 1) // 2 > 2:
+                j0, j1 = reach(l, r - 1, (ow + 1) // 2)
+                mx0, mx1 = min(mx0, j0 // m), max(mx1, j1 // m + 1)
+            elif vs == 2:
+                i0, i1 = reach(t, b - 1, (oh + 1) // 2)
+                my0, my1 = min(my0, i0 // m), max(my1, i1 // m + 1)
+        return mx0, my0, mx1, my1
     _box_in_image(box, width, height, 0)
     if ncomp == 1:
         hs = vs = 1
@@ -563,7 +593,8 @@ def decode_box_window(width: int, height: int, hs: int, vs: int, ncomp: int, box
 
 
 def decode_box_stats(device: int = 0):
-    """(segments_total, segments_decoded, coef_blocks) of the last standard_jpeg_decode_many with a box on this device's current
+    """(segments_total, segments_decoded, coef_blocks) of the last standard_jpeg_decode_many with a box or a scaled_box (or
+    standard_jpeg_resized_crop_many, whose decode is one) on this device's current
     stream that had baseline files (aej_jpegdec_box_stats), summed over those files: their restart segments, the ones that were
     Huffman-decoded (those holding an MCU of the window's MCU rows; every one of a file without a box) and the coefficient blocks
     stored.  Computed on the host from the headers and the windows: nothing is read back."""
@@ -590,7 +621,7 @@ def draft_scale(width: int, height: int, size) -> int:
 
 
 def standard_jpeg_decode_many(files, device: int = 0, progressive: bool = False, scale=1, layout_440: bool = False, mode="RGB", box=None,
-                              adobe: bool = False) -> list:
+                              adobe: bool = False, scaled_box=None) -> list:
     """Decode JPEG files on the device: -> list of uint8 [H_i, W_i, 3] tensors (views into one packed allocation), in input
     order, on the context of the current stream; element i equals ``np.asarray(Image.open(io.BytesIO(files[i])).convert("RGB"))``.
     scale: 1, 2, 4 or 8, or a sequence of one such value per file (ValueError naming the value otherwise; a bool is refused): file i
@@ -644,26 +675,40 @@ def standard_jpeg_decode_many(files, device: int = 0, progressive: bool = False,
     four components, [H, W, 3] (the samples) for an RGB-coded one.  mode="RGB" gives [H, W, 3] for every file: of a four-component one
     Pillow's ``.convert("RGB")`` of that CMYK image, in its integer arithmetic.  Not built, NotImplementedError naming the file before
     any device work: mode="L", a scale other than 1 or a box for one of these files ("... of a four-component / RGB-coded file is
-    not built").  The thumbnail, transcode, transform and encode calls have no such keyword and refuse these files as before."""
+    not built").  The thumbnail, transcode, transform and encode calls have no such keyword and refuse these files as before.
+    scaled_box: box= in pixels of each file's SCALED image, [ceil(H_i / s_i), ceil(W_i / s_i)] -- Pillow's crop() box of the drafted
+    image -- so that it works at scale 2, 4 and 8: one box for every file, or one box or None per file.  Element i equals
+    ``[top:bottom, left:right]`` of the same call without the keyword.  Only the box's tiles are reconstructed, from the reduced inverse
+    DCTs (csrc/jpegdec.hip, ``k_jd_sbox``; ``decode_box_window(..., scale=s)`` is the MCU window), and the restart-segment skip and the
+    coefficient window of box= apply to baseline files as they do there.  At scale 1 it is box=.  The checks and error words are
+    those of box=, against the scaled image's size; giving both box= and scaled_box= raises ValueError; box= at scale 2, 4 or 8 still
+    raises NotImplementedError."""
     files = list(files)
     if not files:
         raise ValueError("standard_jpeg_decode_many needs at least one file")
     modes = _check_modes(mode, len(files))
+    if box is not None and scaled_box is not None:
+        raise ValueError("box= and scaled_box= are both given: one of them (box= is in full-size pixels, scaled_box= in pixels of the scaled image)")
     _, out, out_off, shapes, comps = _decode_files(files, device, progressive, _check_scales(scale, len(files)),
                                                    layout_440=_check_bool("layout_440", layout_440), modes=modes,
-                                                   boxes=_check_boxes(box, len(files)), adobe=_check_bool("adobe", adobe))
+                                                   boxes=_check_boxes(box, len(files)), adobe=_check_bool("adobe", adobe),
+                                                   sboxes=_check_boxes(scaled_box, len(files)))
     return _views(out, out_off, shapes, comps)
 
 
-def _decode_files(files, device, progressive, scales, choose=None, layout_440=False, modes=None, boxes=None, adobe=False):
+def _decode_files(files, device, progressive, scales, choose=None, layout_440=False, modes=None, boxes=None, adobe=False, sboxes=None):
     """The decode of standard_jpeg_decode_many -> (context, the packed uint8 output, int64 offsets, [(h, w)], [3 or 1: the channels of
     each image]).  scales: int32 [n]; with `choose`, file i's scale is choose(i, width, height) instead, asked once its header
     is parsed and before any device work.  modes: _check_modes' list (None: every file "RGB").  boxes: _check_boxes' list (None: no
     file has one); the shape of a boxed file is its box's.  adobe: the parsers' keyword; a four-component file that leaves in mode
-    "CMYK" has 4 channels."""
+    "CMYK" has 4 channels.  sboxes (not together with boxes): the same list with every box in pixels of its file's scaled image; an
+    entry may be set by `choose`, which is asked first."""
     n = len(files)
     parsed, views, base_idx, prog_idx, shapes, comps = [], [], [], [], [], []
     box_arr, prog_set = None, set()
+    sbox = sboxes is not None
+    if sbox:
+        boxes = sboxes
     for i, is_prog, d, mv in _parse_sources(files, progressive, layout_440=layout_440, adobe=adobe):
         parsed.append(d)
         views.append(mv)
@@ -677,16 +722,17 @@ def _decode_files(files, device, progressive, scales, choose=None, layout_440=Fa
             scales[i] = choose(i, frame.width, frame.height)
         s = int(scales[i])
         if adobe and frame.colour != "YCbCr":            # the new kinds: full size, whole, in colour
-            whole = boxes is None or boxes[i] is None or boxes[i] == (0, 0, frame.width, frame.height)
+            whole = boxes is None or boxes[i] is None or boxes[i] == ((0, 0, -(-frame.width // s), -(-frame.height // s)) if sbox else (0, 0, frame.width, frame.height))
             what = "mode 'L'" if m == "L" else "a scale other than 1" if s != 1 else None if whole else "a box"
             if what:
                 raise NotImplementedError(f"file {i}: {what} of a four-component / RGB-coded file is not built")
         shapes.append((-(-frame.height // s), -(-frame.width // s)))
         if boxes is not None and boxes[i] is not None:
-            _box_in_image(boxes[i], frame.width, frame.height, i)
-            if boxes[i] == (0, 0, frame.width, frame.height):
+            bw, bh = (shapes[-1][1], shapes[-1][0]) if sbox else (frame.width, frame.height)      # the image the box is a box of
+            _box_in_image(boxes[i], bw, bh, i)
+            if boxes[i] == (0, 0, bw, bh):
                 continue                                 # the whole image: no box
-            if s != 1:
+            if s != 1 and not sbox:
                 raise NotImplementedError(f"file {i}: a box at scale 2, 4 or 8 is not built")
             box_arr = np.zeros((n, 4), np.int32) if box_arr is None else box_arr
             box_arr[i] = boxes[i]
@@ -695,7 +741,8 @@ def _decode_files(files, device, progressive, scales, choose=None, layout_440=Fa
         for i in range(n):
             if not box_arr[i].any():
                 frame = parsed[i][0] if i in prog_set else parsed[i]
-                box_arr[i] = (0, 0, frame.width, frame.height)
+                s = int(scales[i]) if sbox else 1
+                box_arr[i] = (0, 0, -(-frame.width // s), -(-frame.height // s))
     if (scales == 1).all():
         scales = None                                # the unscaled entries, as before
     comps_arr = None if all(c == 3 for c in comps) else np.array(comps, np.int32)      # every image RGB: the entries without components, as before
@@ -710,7 +757,7 @@ def _decode_files(files, device, progressive, scales, choose=None, layout_440=Fa
     st = np.zeros(n, np.int64)
     for idx, run in ((base_idx, _decode_baseline), (prog_idx, _decode_progressive)):
         if idx:
-            extra = () if box_arr is None else (box_arr,)      # no box: the entries without boxes, as before
+            extra = () if box_arr is None else (box_arr, True) if sbox else (box_arr,)      # no box: the entries without boxes, as before
             st[idx] = run(ctx, idx, parsed, views, out, out_off, scales, comps_arr, *extra).cpu().numpy()      # the one read-back of the per-file status words
     _raise_status((int(i), int(st[i])) for i in np.flatnonzero(st))
     return ctx, out, out_off, shapes, comps
@@ -757,6 +804,104 @@ def thumbnail_plan(width: int, height: int, size, reducing_gap=2.0):
     if (-(-width // s), -(-height // s)) == final:
         return s, (1, 1), final, box
     return s, reduce_factors(box, final, gap), final, box
+
+
+def _check_crop_box(b, who):
+    """one crop box of the resized-crop calls -> (l, t, r, b) of numbers; TypeError for anything that is not a list / tuple of four
+    finite numbers (a bool is none)"""
+    from .resample import _is_number
+    if not isinstance(b, (list, tuple)) or len(b) != 4:
+        raise TypeError(f"{who}: box {b!r}: (left, top, right, bottom) required")
+    if not all(_is_number(v) and math.isfinite(v) for v in b):
+        raise TypeError(f"{who}: box {tuple(b)!r}: four finite numbers required")
+    return tuple(v.item() if isinstance(v, np.generic) else v for v in b)
+
+
+def resized_crop_plan(width: int, height: int, box, size, resample="bilinear", reducing_gap=None, what: str = "resized_crop_plan"):
+    """What standard_jpeg_resized_crop_many does with one width x height file (host only).  box = (l, t, r, b) in full-size pixels,
+    fractions allowed, 0 <= l < r <= width and 0 <= t < b <= height (ValueError otherwise; TypeError for anything but four numbers);
+    size = (w, h).  -> dict with
+    scale: 1 when reducing_gap is None, otherwise the largest of 8, 4, 2, 1 that does not exceed ``min(int(r - l) // int(w * g),
+        int(b - t) // int(h * g))`` (1 when a divisor is 0) -- thumbnail_plan's rule with the box's size in the place of the image's;
+    box: (l / s, t / s, r / s, b / s), the box resize() is given on the image decoded at that scale, ceil(width / s) x ceil(height / s);
+    factors, reduce_box: the whole factors resize() reduces by first under reducing_gap and the region it reduces ((1, 1): none);
+    window: (x0, y0, x1, y1), the integer rectangle of the scaled image that is read: the reduce box where there is a reduce, else
+        per axis from the first tap of the first output pixel to the end of the last output pixel's taps (resample_taps' bounds);
+    step: resize_many's own description of the resize (box in the coordinates the reduce leaves)."""
+    from . import resample as RS
+    f, gap, (w, h) = RS._check_filter(resample, what), RS._check_gap(reducing_gap, what), RS._check_size(size, what)
+    l, t, r, b = box = _check_crop_box(box, what)
+    width, height = int(width), int(height)
+    if width < 1 or height < 1:
+        raise ValueError(f"{what}: a {width} x {height} file: positive sizes required")
+    if not (0 <= l < r <= width and 0 <= t < b <= height):
+        raise ValueError(f"{what}: box {box!r} is empty, inverted or leaves the {width} x {height} image (nothing is padded)")
+    s = 1
+    if gap is not None:
+        dw, dh = int(w * gap), int(h * gap)
+        ratio = min(int(r - l) // dw, int(b - t) // dh) if dw > 0 and dh > 0 else 0
+        s = next((v for v in (8, 4, 2) if v <= ratio), 1)
+    ow, oh = -(-width // s), -(-height // s)
+    sbox = (l / s, t / s, r / s, b / s)
+    step = RS._steps(what, ow, oh, (w, h), sbox, f, gap)
+    if step["factors"] != (1, 1):
+        window = tuple(int(v) for v in step["reduce_box"])
+    else:
+        (x0, x1), (y0, y1) = RS._tap_hull(ow, step["box"][0], step["box"][2], w, f), RS._tap_hull(oh, step["box"][1], step["box"][3], h, f)
+        window = (x0, y0, x1, y1)
+    return dict(scale=s, box=sbox, factors=step["factors"], reduce_box=step["reduce_box"], window=window, step=step)
+
+
+def standard_jpeg_resized_crop_many(files, box, size, resample="bilinear", reducing_gap=None, progressive: bool = False,
+                                    layout_440: bool = False, mode: str = "RGB", device: int = 0):
+    """Decode a box of each JPEG file and resize it to one size, on the device -- RandomResizedCrop's decode, a tile pyramid's, a region
+    preview's: -> ONE uint8 tensor [N, h, w, 3] ([N, h, w] under mode="L").  box: one (l, t, r, b) for every file or a list of one per
+    file, in full-size pixels, fractions allowed, inside the image (nothing is padded).  size: one (w, h).  resample: one of the five
+    filters of resize_many ("nearest" is not built).  Per file (resized_crop_plan): the scale s_i the reducing_gap allows for the
+    box's size (1 without one), then element i equals ``resize_many([standard_jpeg_decode_many([f_i], scale=s_i, ...)[0]], size,
+    resample, box=box_i / s_i, reducing_gap=reducing_gap)[0]`` -- in Pillow's words the image drafted at scale s_i, then
+    ``.convert("RGB").resize(size, F, box=box_i / s_i, reducing_gap=g)``; with the defaults ``Image.open(f).convert("RGB")
+    .resize(size, F, box=box)``.  Only the window of the scaled image that the resize reads is ever reconstructed: one decode with
+    scaled_box= each file's plan window, then one resample that reads those windows in place under the whole image's tap tables
+    (``aej_resample_batch_win``; at most three launches).  Nothing is read back except the decoder's status words.
+    progressive / layout_440: as standard_jpeg_decode_many.  mode: "RGB" or "L" (the luma plane, as there); "auto" is refused
+    (ValueError): one tensor has one channel count.  TypeError for a box that is not four numbers, ValueError naming the file for a
+    list of another length than files or a box outside its image, before any device work."""
+    from . import resample as RS
+    layout_440 = _check_bool("layout_440", layout_440)
+    files = list(files)
+    n = len(files)
+    if n < 1:
+        raise ValueError("standard_jpeg_resized_crop_many needs at least one file")
+    if not isinstance(mode, str):
+        raise TypeError(f"mode {mode!r}: 'RGB' or 'L' required")
+    if mode not in ("RGB", "L"):
+        raise ValueError(f"mode {mode!r}: 'RGB' or 'L' required" + (" ('auto' would mix channel counts in the one tensor returned)" if mode == "auto" else ""))
+    f, gap = RS._check_filter(resample, "every file"), RS._check_gap(reducing_gap, "every file")
+    w, h = RS._check_size(size, "standard_jpeg_resized_crop_many")
+    if not isinstance(box, (list, tuple)):
+        raise TypeError(f"box {box!r}: (left, top, right, bottom), or a list of one such tuple per file, required")
+    if len(box) > 0 and all(isinstance(b, (list, tuple)) for b in box):
+        if len(box) != n:
+            raise ValueError(f"box: {len(box)} entries for {n} files")
+        boxes = [_check_crop_box(b, f"file {i}") for i, b in enumerate(box)]
+    else:
+        boxes = [_check_crop_box(box, "every file")] * n
+    plans, sboxes = [None] * n, [None] * n
+
+    def choose(i, width, height):
+        plans[i] = p = resized_crop_plan(width, height, boxes[i], (w, h), f, gap, f"file {i}")
+        sboxes[i] = p["window"]
+        return p["scale"]
+
+    ctx, out, out_off, shapes, comps = _decode_files(files, device, progressive, np.ones(n, np.int32), choose, layout_440, [mode] * n, sboxes=sboxes)
+    steps, windows = [], np.zeros((n, 4), np.int32)
+    for i, p in enumerate(plans):
+        x0, y0, x1, y1 = p["window"]
+        steps.append(dict(p["step"], src=(x1 - x0, y1 - y0)))      # the stored rectangle; the virtual image is the whole scaled one
+        windows[i] = (x0, y0) + p["step"]["src"]
+    res = RS._run(ctx, out.data_ptr(), out.numel(), out_off, steps, [f] * n, comps, windows=windows, packed=True)
+    return res.view(*((n, h, w) + ((3,) if mode == "RGB" else ())))
 
 
 def standard_jpeg_thumbnail_many(files, size, resample="bicubic", reducing_gap=2.0, progressive: bool = False, device: int = 0,

@@ -479,7 +479,23 @@ AEJ_API int aej_jfif_recon_batch_prog(aej_ctx *ctx, int batch, int H, int W, int
  *   (A luma decode reads the luma samples' MCUs alone.)  aej_jpegprog_box_window_host: the same from a progressive file's frame.
  * aej_jpegdec_box_stats: out3_host gets, for the last aej_jpegdec_batch_box of the context in which a file had a box: the restart
  *   segments of its files, those that were Huffman-decoded, and the coefficient blocks stored -- computed on the host from the
- *   descriptors and the windows, nothing is read back.  (Additions to ABI 3: no existing signature, struct or behaviour changed.) */
+ *   descriptors and the windows, nothing is read back.  (Additions to ABI 3: no existing signature, struct or behaviour changed.)
+ * aej_jpegdec_batch_sbox / aej_jpegdec_workspace_bytes_sbox: the _box calls with one difference: boxes_host[i] is in pixels of the SCALED
+ *   image of file i, ow = ceil(width / scale) by oh = ceil(height / scale) -- Pillow's crop() box of the drafted image, 0 <= left <
+ *   right <= ow and 0 <= top < bottom <= oh (anything else: AEJ_ERR_ARG naming the file, 0 bytes, out untouched).  Image i is exactly
+ *   [top, bottom) x [left, right) of what the _mode call gives at that scale.  At scale 1 the call is the _box call byte for byte,
+ *   launches included; a NULL boxes_host, or a box that is the whole scaled image, is the _mode call for that file.  A file with such
+ *   a box at scale 2, 4 or 8 is reconstructed by one kernel from the reduced inverse DCTs of the box's tiles alone, under libjpeg's
+ *   up-sampling rules at that scale, and of a BASELINE file only the restart segments and the coefficient rows of the window are
+ *   decoded and stored, as in the _box call (aej_jpegdec_box_stats reports these calls too).  The _box entries still refuse a box at
+ *   scale 2, 4 or 8.
+ * aej_jpegdec_sbox_window_host: HOST only.  aej_jpegdec_box_window_host for a box in pixels of the image at `scale` (1, 2, 4 or 8): the
+ *   MCUs -- hs * 8 / scale by vs * 8 / scale scaled pixels each -- whose blocks the box's pixels read.  4:4:4, one-component and 4:2:0
+ *   files: the pixel's own MCU (the 4:2:0 chroma IDCT is twice the luma's, so nothing is up-sampled).  4:2:2: one neighbour column after
+ *   the edge clamps at scales 2 and 4 when the scaled chroma width (ow + 1) / 2 exceeds 2 (h2v1 fancy), none otherwise (replication).
+ *   4:4:0: one neighbour row after the clamps at scales 2 and 4 (h1v2 fancy), none at scale 8.  AEJ_ERR_ARG for a box outside the scaled
+ *   image or a scale that is none.  aej_jpegprog_sbox_window_host: the same from a progressive file's frame.
+ *   (Additions to ABI 3: no existing signature, struct or behaviour changed.) */
 enum {
     AEJ_JPEGDEC_OK = 0, AEJ_JPEGDEC_TRUNCATED = 1 /* the scan ends before the last MCU */, AEJ_JPEGDEC_BAD_CODE = 2 /* not in the table */,
     AEJ_JPEGDEC_RUN_PAST_63 = 3 /* an AC run beyond the block */, AEJ_JPEGDEC_BAD_DC = 4 /* DC category above 11 */,
@@ -530,6 +546,13 @@ AEJ_API int aej_jpegdec_batch_box(aej_ctx *ctx, const aej_jpegdec_desc *descs_ho
                                   uint64_t workspace_bytes);
 AEJ_API int aej_jpegdec_box_window_host(const aej_jpegdec_desc *desc_host, const int32_t *box4_host, int32_t *window4_out_host);
 AEJ_API int aej_jpegdec_box_stats(aej_ctx *ctx, int64_t *out3_host);
+AEJ_API uint64_t aej_jpegdec_workspace_bytes_sbox(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host,
+                                                  const int *components_host, const int32_t *boxes_host);
+AEJ_API int aej_jpegdec_batch_sbox(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host, const int *components_host,
+                                   const int32_t *boxes_host, const uint8_t *scans, uint64_t scans_bytes, const int64_t *scan_offsets_host,
+                                   uint8_t *out, uint64_t out_bytes, const int64_t *out_offsets_host, int32_t *status, void *workspace,
+                                   uint64_t workspace_bytes);
+AEJ_API int aej_jpegdec_sbox_window_host(const aej_jpegdec_desc *desc_host, int scale, const int32_t *box4_host, int32_t *window4_out_host);
 
 /* ---- progressive JPEG files decoded on the device (standard_jpeg_decode_many(..., progressive=True)) ----------------------------------
  * SOF2 files with Huffman coding, under the frame rules of aej_jpegdec_parse_host (8-bit, 1 or 3 components, 4:4:4 / 4:2:2 / 4:2:0 /
@@ -610,6 +633,16 @@ AEJ_API int aej_jpegprog_batch_box(aej_ctx *ctx, const aej_jpegprog_frame *frame
                                    uint64_t data_bytes, const int64_t *data_offsets_host, uint8_t *out, uint64_t out_bytes,
                                    const int64_t *out_offsets_host, int32_t *status, void *workspace, uint64_t workspace_bytes);
 AEJ_API int aej_jpegprog_box_window_host(const aej_jpegprog_frame *frame_host, const int32_t *box4_host, int32_t *window4_out_host);
+/* aej_jpegprog_batch_sbox / aej_jpegprog_workspace_bytes_sbox, aej_jpegprog_sbox_window_host: the _box entries with the boxes in pixels
+ * of each file's SCALED image, as aej_jpegdec_batch_sbox (the same refusals; scale 1: the _box call byte for byte).  The entropy decode
+ * stays whole.  (Additions to ABI 3: no existing signature, struct or behaviour changed.) */
+AEJ_API uint64_t aej_jpegprog_workspace_bytes_sbox(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
+                                                   const int *scales_host, const int *components_host, const int32_t *boxes_host);
+AEJ_API int aej_jpegprog_batch_sbox(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
+                                    const int *scales_host, const int *components_host, const int32_t *boxes_host, const uint8_t *data,
+                                    uint64_t data_bytes, const int64_t *data_offsets_host, uint8_t *out, uint64_t out_bytes,
+                                    const int64_t *out_offsets_host, int32_t *status, void *workspace, uint64_t workspace_bytes);
+AEJ_API int aej_jpegprog_sbox_window_host(const aej_jpegprog_frame *frame_host, int scale, const int32_t *box4_host, int32_t *window4_out_host);
 
 /* ---- CMYK, YCCK and RGB-coded files (standard_jpeg_decode_many(..., adobe=True)) -------------------------------------------------------
  * The files libjpeg reads with another colour model than YCbCr or grey: four components -- CMYK without an Adobe APP14 marker or with
@@ -965,7 +998,15 @@ AEJ_API int aej_jfif_transform_batch_cut(aej_ctx *ctx, const aej_jpegdec_desc *d
  *   descriptor is unchanged: its offsets are bytes.  Exactly dst_w * dst_h * channels bytes and no other byte of dst are written.
  *   Images of either count form launches of their own: at most six kernels for a mixed call, and with every count 3 the calls are
  *   aej_resample_batch and aej_resample_workspace_bytes byte for byte, launches included.  (Additions to ABI 3: no existing signature,
- *   struct or behaviour changed.) */
+ *   struct or behaviour changed.)
+ * aej_resample_batch_win / aej_resample_workspace_bytes_win: the _ch calls with windows_host [n][4] = x0, y0, vw, vh as well.  The stored
+ *   source of image i -- src_w x src_h at src_offset, packed -- is the rectangle [y0, y0 + src_h) x [x0, x0 + src_w) of a virtual image
+ *   vw x vh, and box and reduce_box are in the virtual image's coordinates.  The tap tables are computed from the virtual size, so they
+ *   are bit for bit the whole image's, and the result is the _ch call's on the whole image as long as nothing outside the rectangle is
+ *   read: that is checked per descriptor on the host before any device work -- a tap with a non-zero count, or the reduce box, that
+ *   reaches outside the stored rectangle, or a rectangle outside its virtual image: AEJ_ERR_ARG naming the image, 0 bytes, dst
+ *   untouched.  Only the base pointer and the pitch of the first stage move; the kernels are the same.  NULL windows_host: the _ch call
+ *   byte for byte.  (Additions to ABI 3: no existing signature, struct or behaviour changed.) */
 enum { AEJ_RESAMPLE_LANCZOS = 1, AEJ_RESAMPLE_BILINEAR = 2, AEJ_RESAMPLE_BICUBIC = 3, AEJ_RESAMPLE_BOX = 4, AEJ_RESAMPLE_HAMMING = 5 }; /* Pillow's integers */
 typedef struct aej_resample_desc {
     int64_t src_offset, dst_offset;
@@ -984,6 +1025,11 @@ AEJ_API int aej_resample_batch(aej_ctx *ctx, const aej_resample_desc *descs_host
 AEJ_API uint64_t aej_resample_workspace_bytes_ch(aej_ctx *ctx, const aej_resample_desc *descs_host, int n, const int *channels_host);
 AEJ_API int aej_resample_batch_ch(aej_ctx *ctx, const aej_resample_desc *descs_host, int n, const int *channels_host, const uint8_t *src,
                                   uint64_t src_bytes, uint8_t *dst, uint64_t dst_bytes, void *workspace, uint64_t workspace_bytes);
+AEJ_API uint64_t aej_resample_workspace_bytes_win(aej_ctx *ctx, const aej_resample_desc *descs_host, int n, const int *channels_host,
+                                                  const int32_t *windows_host);
+AEJ_API int aej_resample_batch_win(aej_ctx *ctx, const aej_resample_desc *descs_host, int n, const int *channels_host, const int32_t *windows_host,
+                                   const uint8_t *src, uint64_t src_bytes, uint8_t *dst, uint64_t dst_bytes, void *workspace,
+                                   uint64_t workspace_bytes);
 
 #ifdef __cplusplus
 }
