@@ -186,6 +186,19 @@ class ResampleDesc(ctypes.Structure):
                 ("reduce_x", ctypes.c_int32), ("reduce_y", ctypes.c_int32), ("reduce_box", ctypes.c_int32 * 4), ("reserved", ctypes.c_int32)]
 
 
+class PngDesc(ctypes.Structure):
+    """aej_png_desc (include/aej.h): what aej_png_parse_host reads from a file's chunks"""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("bit_depth", ctypes.c_int32), ("colour_type", ctypes.c_int32),
+                ("channels", ctypes.c_int32), ("row_bytes", ctypes.c_int32), ("interlace", ctypes.c_int32), ("n_idat", ctypes.c_int32),
+                ("palette_len", ctypes.c_int32), ("has_trns", ctypes.c_int32), ("idat_bytes", ctypes.c_int64),
+                ("palette", ctypes.c_uint8 * 768), ("mode_chars", ctypes.c_char * 8)]
+
+    @property
+    def mode(self) -> str:
+        """Pillow's mode of the opened file"""
+        return self.mode_chars.decode()
+
+
 SIGNATURES = {
     "aej_abi_version": (_I, []),
     "aej_create": (_P, [_I, _P]),
@@ -337,6 +350,9 @@ SIGNATURES = {
     "aej_resample_batch_ch": (_I, [_P, _P, _I, _P, _P, _U64, _P, _U64, _P, _U64]),
     "aej_resample_workspace_bytes_win": (_U64, [_P, _P, _I, _P, _P]),
     "aej_resample_batch_win": (_I, [_P, _P, _I, _P, _P, _P, _U64, _P, _U64, _P, _U64]),
+    "aej_png_parse_host": (_I, [_P, _U64, _P, _P, _I, _P, _I]),
+    "aej_png_workspace_bytes": (_U64, [_P, _P, _I]),
+    "aej_png_unfilter_batch": (_I, [_P, _P, _I, _P, _U64, _P, _P, _P, _P, _P, _P, _U64, _P, _P, _P, _U64]),
     "aej_test_jpegprog_coefs": (_I, [_P, _P, _P, _I, _P, _U64, _P, _I, _P, _U64, _P, _P, _U64]),             # include/aej_testing.h (tests only)
     "aej_test_jpegprog_coefs_host": (_I, [_P, _P, _P, _U64, _I, _P, _U64]),                                 # include/aej_testing.h (tests only)
     "aej_test_jpeg_adobe_pixels_host": (_I, [_P, _I64, _I, _I, _P]),                                        # include/aej_testing.h (tests only)
@@ -350,6 +366,8 @@ INFLATE_STATUS = ["ok", "bad zlib header", "bad block type", "bad code lengths",
 JPEGDEC_STATUS = ["ok", "truncated scan (it ends before the last MCU)", "bad Huffman code", "coefficient run past 63",
                   "DC category above 11", "restart marker out of sequence, missing or unexpected",
                   "coefficient out of range for an 8-bit JPEG (AC beyond +-1023 or DC outside -1024..1023)"]
+PNG_STATUS = ["ok", "the zlib stream of its IDAT chunks does not inflate", "inflated size is not height x (1 + row bytes)",
+              "a filter byte above 4"]
 HEADER_STATUS = ["ok", "more leaves than the layer holds", "leaf size outside the block-size range of the header",
                  "quadtree header does not tile the layer", "coefficient count does not match the quadtree header", "bad layer descriptor"]
 

@@ -588,3 +588,24 @@ void resample_blob(const RsPlan &plan, const RsBufs &w, const unsigned char *src
 hipError_t launch_resample(hipStream_t st, const RsPlan &plan, const RsBufs &w, const void *blob_host, unsigned long long blob_bytes);
 
 }  // namespace aej
+
+// png.hip: the scanline un-filter of PNG files and their expansion to the output layout (aej_png_unfilter_batch), one workgroup per file
+namespace aej {
+
+constexpr int kPngGroup = 64;          // files per launch: their table travels in the kernel's arguments, so nothing is uploaded
+struct PngFile {
+    long long in_off;                  // its filtered scanlines in `inflated`: H x (1 + rb) bytes, a multiple of 4
+    long long out_off;                 // its image in `out`
+    long long carry_off;               // its carried scanline in the workspace (png_carry_bytes), a multiple of 256
+    int W, H, rb;                      // pixels per row, rows, bytes per row without the filter byte
+    unsigned char bpp;                 // the filters' distance to the byte "to the left": bytes per whole pixel, 1 for the packed depths
+    unsigned char depth, ct;           // bit depth (1, 2, 4, 8), colour type (0, 2, 3, 4, 6)
+    unsigned char oc;                  // bytes per pixel of the image written: 1 .. 4
+};
+struct PngGroup { PngFile f[kPngGroup]; };
+long long png_carry_bytes(int rb, int bpp);
+// files first .. first + count of the call (count <= kPngGroup); the per-file arrays are the whole call's
+void launch_png_unfilter(hipStream_t st, const PngGroup &grp, int first, int count, const unsigned char *inflated, const long long *inflate_out_bytes,
+                         const int *inflate_status, const unsigned char *palettes, unsigned char *out, unsigned char *carry, int *status);
+
+}  // namespace aej

@@ -1,0 +1,204 @@
+// api_png.hip -- the PNG entries of the C ABI (include/aej.h): the host chunk walk (aej_png_parse_host) and the launch of the scanline
+// un-filter and layout conversion of csrc/png.hip (aej_png_unfilter_batch).  Host code only.
+#include "aej_ctx.h"
+
+using namespace aej;
+
+namespace {
+
+constexpr int kPngMaxSide = 1 << 24;     // keeps every in-row index of the kernel inside an int (row bytes <= 2^26)
+
+uint32_t be32(const uint8_t *p) { return (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | p[3]; }
+
+// CRC-32 of ISO 3309 as the PNG specification's annex D computes it, over a chunk's type and data
+uint32_t png_crc(const uint8_t *p, size_t n)
+{
+    static uint32_t table[256];
+    static std::once_flag once;
+    std::call_once(once, [] {
+        for (uint32_t i = 0; i < 256; i++) {
+            uint32_t c = i;
+            for (int k = 0; k < 8; k++) c = c & 1 ? 0xedb88320u ^ (c >> 1) : c >> 1;
+            table[i] = c;
+        }
+    });
+    uint32_t c = 0xffffffffu;
+    for (size_t i = 0; i < n; i++) c = table[(c ^ p[i]) & 255] ^ (c >> 8);
+    return c ^ 0xffffffffu;
+}
+
+int refuse(int code, const std::string &m, char *msg, int cap)
+{
+    copy_msg(m, msg, cap);
+    return code;
+}
+
+// samples per pixel of a colour type, 0 for a value that is none
+int png_channels(int ct) { return ct == 0 || ct == 3 ? 1 : ct == 2 ? 3 : ct == 4 ? 2 : ct == 6 ? 4 : 0; }
+
+bool png_desc_ok(const aej_png_desc &d)
+{
+    const int ch = png_channels(d.colour_type);
+    if (!ch || d.channels != ch || d.interlace != 0) return false;
+    if (d.width < 1 || d.height < 1 || d.width > kPngMaxSide || d.height > kPngMaxSide) return false;
+    const bool packed = d.bit_depth == 1 || d.bit_depth == 2 || d.bit_depth == 4;
+    if (!(d.bit_depth == 8 || (packed && (d.colour_type == 0 || d.colour_type == 3)))) return false;
+    if (d.row_bytes != (int)(((long long)d.width * ch * d.bit_depth + 7) / 8)) return false;
+    return d.palette_len >= 0 && d.palette_len <= 256 && (d.colour_type != 3 || d.palette_len > 0);
+}
+
+int png_bpp(const aej_png_desc &d) { return d.bit_depth == 8 ? d.channels : 1; }
+
+int png_out_channels(const aej_png_desc &d, int layout)
+{
+    if (layout == AEJ_PNG_RGB || d.colour_type == 3) return 3;
+    return d.channels;
+}
+
+}  // namespace
+
+extern "C" int aej_png_parse_host(const uint8_t *data_host, uint64_t nbytes, aej_png_desc *desc_host, int64_t *spans_host, int span_capacity,
+                                  char *msg, int msg_capacity)
+{
+    if (!data_host || !desc_host || span_capacity < 0) return refuse(AEJ_ERR_ARG, "NULL buffer", msg, msg_capacity);
+    aej_png_desc &d = *desc_host;
+    memset(&d, 0, sizeof d);
+    static const uint8_t kSig[8] = { 0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a };
+    if (nbytes < 8 || memcmp(data_host, kSig, 8) != 0) return refuse(AEJ_ERR_ARG, "not a PNG file: bad signature", msg, msg_capacity);
+    uint64_t pos = 8;
+    bool have_ihdr = false, have_plte = false, ended = false;
+    while (!ended && pos < nbytes) {
+        if (nbytes - pos < 12) return refuse(AEJ_ERR_ARG, "truncated file: a chunk header runs past the end", msg, msg_capacity);
+        const uint64_t len = be32(data_host + pos);
+        const uint8_t *type = data_host + pos + 4;
+        const std::string name(reinterpret_cast<const char *>(type), 4);
+        if (len > nbytes - pos - 12) return refuse(AEJ_ERR_ARG, "truncated file: the length of chunk " + name + " runs past the end", msg, msg_capacity);
+        const uint8_t *body = type + 4;
+        auto named = [&](const char *t) { return memcmp(type, t, 4) == 0; };
+        auto crc_ok = [&] { return png_crc(type, 4 + (size_t)len) == be32(body + len); };
+        if (!have_ihdr) {
+            if (!named("IHDR") || len != 13) return refuse(AEJ_ERR_ARG, "missing IHDR: the first chunk is " + name, msg, msg_capacity);
+            if (!crc_ok()) return refuse(AEJ_ERR_ARG, "bad CRC on IHDR", msg, msg_capacity);
+            have_ihdr = true;
+            const uint32_t w = be32(body), h = be32(body + 4);
+            d.bit_depth = body[8];
+            d.colour_type = body[9];
+            d.interlace = body[12];
+            d.channels = png_channels(d.colour_type);
+            if (w == 0 || h == 0) return refuse(AEJ_ERR_ARG, "zero width or height", msg, msg_capacity);
+            if (w > 0x7fffffffu || h > 0x7fffffffu) return refuse(AEJ_ERR_ARG, "width or height above 2^31 - 1", msg, msg_capacity);
+            d.width = (int32_t)w;
+            d.height = (int32_t)h;
+            const int bd = d.bit_depth;
+            const bool depth_known = bd == 1 || bd == 2 || bd == 4 || bd == 8 || bd == 16;
+            const bool depth_allowed = depth_known && (d.colour_type == 0 || (d.colour_type == 3 && bd != 16) || ((d.colour_type == 2 || d.colour_type == 4 || d.colour_type == 6) && bd >= 8));
+            if (!d.channels || !depth_allowed)
+                return refuse(AEJ_ERR_ARG, "colour type " + std::to_string(d.colour_type) + " with bit depth " + std::to_string(bd) + " is not a PNG image type", msg, msg_capacity);
+            if (body[10] != 0 || body[11] != 0 || body[12] > 1) return refuse(AEJ_ERR_ARG, "unknown compression, filter or interlace method", msg, msg_capacity);
+            const char *mode = d.colour_type == 0 ? (bd == 1 ? "1" : "L") : d.colour_type == 2 ? "RGB" : d.colour_type == 3 ? "P" : d.colour_type == 4 ? "LA" : "RGBA";
+            snprintf(d.mode, sizeof d.mode, "%s", mode);
+            if (bd == 16) return refuse(AEJ_ERR_UNSUPPORTED, "16-bit samples are not built", msg, msg_capacity);
+            if (d.interlace) return refuse(AEJ_ERR_UNSUPPORTED, "Adam7 interlace is not built", msg, msg_capacity);
+            if (d.width > kPngMaxSide || d.height > kPngMaxSide) return refuse(AEJ_ERR_UNSUPPORTED, "a side above 2^24 pixels is not built", msg, msg_capacity);
+            d.row_bytes = (int32_t)(((long long)d.width * d.channels * bd + 7) / 8);
+        } else if (named("IHDR")) {
+            return refuse(AEJ_ERR_ARG, "a second IHDR", msg, msg_capacity);
+        } else if (named("PLTE")) {
+            if (!crc_ok()) return refuse(AEJ_ERR_ARG, "bad CRC on PLTE", msg, msg_capacity);
+            if (have_plte || len == 0 || len % 3 != 0 || len > 768) return refuse(AEJ_ERR_ARG, "a PLTE chunk that is repeated, empty, longer than 256 entries or no multiple of 3", msg, msg_capacity);
+            have_plte = true;
+            d.palette_len = (int32_t)(len / 3);
+            memcpy(d.palette, body, (size_t)len);
+        } else if (named("tRNS")) {
+            if (!crc_ok()) return refuse(AEJ_ERR_ARG, "bad CRC on tRNS", msg, msg_capacity);
+            d.has_trns = 1;
+        } else if (named("IDAT")) {
+            if (d.colour_type == 3 && !have_plte) return refuse(AEJ_ERR_ARG, "missing PLTE before the first IDAT", msg, msg_capacity);
+            if (d.n_idat == INT32_MAX) return refuse(AEJ_ERR_ARG, "too many IDAT chunks", msg, msg_capacity);
+            if (spans_host && d.n_idat < span_capacity) {
+                spans_host[2 * (int64_t)d.n_idat] = (int64_t)(pos + 8);
+                spans_host[2 * (int64_t)d.n_idat + 1] = (int64_t)len;
+            }
+            d.n_idat++;
+            d.idat_bytes += (int64_t)len;
+        } else if (named("IEND")) {
+            ended = true;
+        } else if (named("acTL") || named("fcTL") || named("fdAT")) {
+            return refuse(AEJ_ERR_UNSUPPORTED, "APNG frames (chunk " + name + ") are not built", msg, msg_capacity);
+        } else if (!(type[0] & 0x20)) {
+            return refuse(AEJ_ERR_UNSUPPORTED, "unknown critical chunk " + name, msg, msg_capacity);
+        }
+        pos += 12 + len;
+    }
+    if (!have_ihdr) return refuse(AEJ_ERR_ARG, "missing IHDR", msg, msg_capacity);
+    if (d.colour_type == 3 && !have_plte) return refuse(AEJ_ERR_ARG, "missing PLTE", msg, msg_capacity);
+    if (d.n_idat == 0) return refuse(AEJ_ERR_ARG, "missing IDAT", msg, msg_capacity);
+    if (spans_host && d.n_idat > span_capacity) return refuse(AEJ_ERR_CAPACITY, "more IDAT chunks than the span list holds", msg, msg_capacity);
+    copy_msg("", msg, msg_capacity);
+    return 0;
+}
+
+extern "C" uint64_t aej_png_workspace_bytes(aej_ctx *ctx, const aej_png_desc *descs_host, int n)
+{
+    if (!ctx || !descs_host || n < 1) return 0;
+    unsigned long long total = 0;
+    for (int i = 0; i < n; i++) {
+        if (!png_desc_ok(descs_host[i])) return 0;
+        total += (unsigned long long)png_carry_bytes(descs_host[i].row_bytes, png_bpp(descs_host[i]));
+    }
+    return total;
+}
+
+extern "C" int aej_png_unfilter_batch(aej_ctx *ctx, const aej_png_desc *descs_host, int n, const uint8_t *inflated, uint64_t inflated_bytes,
+                                      const int64_t *in_offsets_host, const int64_t *inflate_out_bytes, const int32_t *inflate_status,
+                                      const uint8_t *palettes, const int32_t *layouts_host, uint8_t *out, uint64_t out_bytes,
+                                      const int64_t *out_offsets_host, int32_t *status, void *workspace, uint64_t workspace_bytes)
+{
+    const char *fn = __func__;
+    AEJ_TRY(enter(ctx, fn));
+    if (n < 1 || !descs_host) return fail(ctx, AEJ_ERR_ARG, "%s: no files", fn);
+    if (!inflated || !in_offsets_host || !out || !out_offsets_host || !status || !workspace) return null_buffer(ctx, fn);
+    if ((inflate_out_bytes == nullptr) != (inflate_status == nullptr))
+        return fail(ctx, AEJ_ERR_ARG, "%s: inflate_out_bytes and inflate_status go together", fn);
+    if (reinterpret_cast<uintptr_t>(inflated) & 3 || reinterpret_cast<uintptr_t>(palettes) & 3 || reinterpret_cast<uintptr_t>(workspace) & 3)
+        return fail(ctx, AEJ_ERR_ARG, "%s: inflated, palettes and workspace must be 4-byte aligned", fn);
+    std::vector<PngFile> files(n);
+    unsigned long long carry = 0;
+    for (int i = 0; i < n; i++) {
+        const aej_png_desc &d = descs_host[i];
+        if (!png_desc_ok(d)) return fail(ctx, AEJ_ERR_ARG, "%s: file %d: a descriptor aej_png_parse_host did not write", fn, i);
+        const int layout = layouts_host ? layouts_host[i] : AEJ_PNG_RGB;
+        if (layout != AEJ_PNG_RGB && layout != AEJ_PNG_AUTO) return fail(ctx, AEJ_ERR_ARG, "%s: file %d: layout %d", fn, i, layout);
+        if (d.colour_type == 3 && !palettes) return fail(ctx, AEJ_ERR_ARG, "%s: file %d: a palette file and no palettes", fn, i);
+        PngFile &f = files[i];
+        f.W = d.width;
+        f.H = d.height;
+        f.rb = d.row_bytes;
+        f.bpp = (unsigned char)png_bpp(d);
+        f.depth = (unsigned char)d.bit_depth;
+        f.ct = (unsigned char)d.colour_type;
+        f.oc = (unsigned char)png_out_channels(d, layout);
+        const unsigned long long raw = (unsigned long long)d.height * (1ull + (unsigned long long)d.row_bytes);      // < 2^51
+        const unsigned long long image = (unsigned long long)d.height * (unsigned long long)d.width * f.oc;
+        const long long io = in_offsets_host[i], oo = out_offsets_host[i];
+        if (io < 0 || (io & 3) || (unsigned long long)io > inflated_bytes || ((raw + 3) & ~3ull) > inflated_bytes - (unsigned long long)io)
+            return fail(ctx, AEJ_ERR_ARG, "%s: file %d: scanlines outside the inflated buffer (whole dwords), or an offset that is no multiple of 4", fn, i);
+        if (oo < 0 || (unsigned long long)oo > out_bytes || image > out_bytes - (unsigned long long)oo)
+            return fail(ctx, AEJ_ERR_ARG, "%s: file %d: image outside the output", fn, i);
+        f.in_off = io;
+        f.out_off = oo;
+        f.carry_off = (long long)carry;
+        carry += (unsigned long long)png_carry_bytes(d.row_bytes, f.bpp);
+    }
+    AEJ_TRY(check_workspace(ctx, carry, workspace_bytes));
+    AEJ_TRY(bind_device(ctx));
+    for (int first = 0; first < n; first += kPngGroup) {
+        PngGroup grp{};
+        const int count = std::min(kPngGroup, n - first);
+        std::copy(files.begin() + first, files.begin() + first + count, grp.f);
+        launch_png_unfilter(ctx->stream, grp, first, count, inflated, reinterpret_cast<const long long *>(inflate_out_bytes), inflate_status,
+                            palettes, out, static_cast<unsigned char *>(workspace), status);
+        AEJ_HIP_CHECK(hipGetLastError());
+    }
+    return 0;
+}

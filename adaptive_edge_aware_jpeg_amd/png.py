@@ -1,0 +1,216 @@
+"""PNG files decoded on the GPU, pixel-identical to Pillow (``png_decode_many``), and the host chunk walk (``png_parse_header``).
+
+The host reads only the chunk framing (``aej_png_parse_host``).  The zlib stream of every file -- its IDAT chunks joined -- is inflated
+by ``aej_inflate_batch`` (csrc/inflate.hip, one wave per file) or, as the A / B partner, by ``zlib.decompress`` on a thread pool; the
+scanline un-filter and the expansion of grey, palette and alpha layouts run on the device either way (csrc/png.hip)."""
+import ctypes
+import zlib
+from concurrent.futures import ThreadPoolExecutor
+from typing import List, Optional
+
+import numpy as np
+
+from ._lib import get_context
+from .jpeg import usable_cpus
+from .standard_jpeg import _buffer, _refuse
+
+MODES = ("RGB", "auto")      # AEJ_PNG_RGB, AEJ_PNG_AUTO
+MAX_HOST_WORKERS = 16
+
+
+def png_parse_header(data, index: int = 0):
+    """aej_png_parse_host: the PngDesc of one file's chunks (host only, no device needed).  Attributes: ``width``, ``height``,
+    ``bit_depth``, ``colour_type``, ``channels`` (samples per pixel in the file), ``row_bytes`` (a scanline without its filter byte),
+    ``mode`` (Pillow's mode of the opened file: "1", "L", "P", "RGB", "LA", "RGBA"), ``n_idat`` and ``idat_bytes`` (number and total data
+    bytes of the IDAT chunks, empty ones included), ``palette_len`` (entries of PLTE), ``has_trns``, and ``idat_spans``: an int64 array
+    [n_idat, 2] of (offset in the file, length) of each IDAT chunk's data.  Raises NotImplementedError for a valid file outside the
+    supported set (16-bit samples, Adam7 interlace, APNG frames) and ValueError for a malformed one (bad signature, missing IHDR, PLTE or
+    IDAT, a bad CRC on IHDR, PLTE or tRNS, zero width or height, a chunk length that runs past the file), both naming the file index."""
+    from ._lib import AEJ_ERR_CAPACITY, PngDesc, load_library
+    lib = load_library()
+    buf, n = _buffer(data)
+    d, msg = PngDesc(), ctypes.create_string_buffer(256)
+    spans = np.zeros((8, 2), np.int64)
+    rc = lib.aej_png_parse_host(ctypes.addressof(buf), n, ctypes.addressof(d), spans.ctypes.data, len(spans), ctypes.addressof(msg), 256)
+    if rc == AEJ_ERR_CAPACITY:                           # more IDAT chunks than the first guess: the count is known now
+        spans = np.zeros((d.n_idat, 2), np.int64)
+        rc = lib.aej_png_parse_host(ctypes.addressof(buf), n, ctypes.addressof(d), spans.ctypes.data, len(spans), ctypes.addressof(msg), 256)
+    _refuse(rc, msg, index)
+    d.idat_spans = spans[:d.n_idat]
+    return d
+
+
+def _check_modes(mode, n):
+    try:
+        modes = [mode] * n if isinstance(mode, str) else list(mode)
+    except TypeError:
+        raise ValueError(f"mode: {mode!r} is neither one of {MODES} nor a sequence of them") from None
+    if len(modes) != n:
+        raise ValueError(f"mode: {len(modes)} values for {n} files")
+    for i, m in enumerate(modes):
+        if m not in MODES:
+            raise ValueError(f"mode of file {i}: {m!r} is not one of {MODES}")
+    return modes
+
+
+def _out_channels(d, mode) -> int:
+    return 3 if mode == "RGB" or d.colour_type == 3 else d.channels
+
+
+def _inflate_on_host(ctx, streams, raw, in_off, sizes, workers):
+    """inflate="host": zlib.decompress of every file's stream on a thread pool, each result through a page-locked buffer into its slot of
+    ``raw``.  Raises ValueError naming the file for a stream zlib refuses or that inflates to another size than the header's."""
+    t = ctx.torch
+    chunk = 256 << 20
+    buf = getattr(ctx, "_png_pinned", None)
+    need = min(chunk, max(max(sizes), 1 << 20))
+    if buf is None or buf.numel() < need:
+        buf = ctx._png_pinned = t.empty(need, dtype=t.uint8, pin_memory=True)
+    cap = buf.numel()
+    hb = buf.numpy()
+    used = 0
+
+    def one(s):
+        try:
+            return zlib.decompress(s)
+        except zlib.error as e:
+            return e
+
+    with ThreadPoolExecutor(max_workers=min(workers or usable_cpus(), MAX_HOST_WORKERS)) as ex:
+        for i, data in enumerate(ex.map(one, streams)):
+            if isinstance(data, zlib.error):
+                raise ValueError(f"file {i}: the zlib stream of its IDAT chunks does not inflate ({data})")
+            if len(data) != sizes[i]:
+                raise ValueError(f"file {i}: inflated size {len(data)} is not height x (1 + row bytes) = {sizes[i]}")
+            done = 0
+            while done < sizes[i]:
+                if used == cap:                          # the buffer is full: wait for its copies before refilling it
+                    t.cuda.current_stream(ctx.device).synchronize()
+                    used = 0
+                k = min(sizes[i] - done, cap - used)
+                hb[used:used + k] = np.frombuffer(data, np.uint8, k, done)
+                raw[in_off[i] + done:in_off[i] + done + k].copy_(buf[used:used + k], non_blocking=True)
+                used += k
+                done += k
+    t.cuda.current_stream(ctx.device).synchronize()      # the buffer is reused by the next call
+
+
+def png_decode_many(files, mode="RGB", inflate: str = "gpu", device: int = 0, workers: Optional[int] = None) -> List:
+    """Decode PNG files (bytes-like, of mixed sizes and kinds) on the GPU -> a list of device uint8 tensors, one per file, in file order.
+
+    ``mode`` is one value for all files or one per file.  "RGB": [H, W, 3], equal to ``np.asarray(Image.open(f).convert("RGB"))`` --
+    alpha is dropped (not composited), tRNS is ignored, grey is replicated, palette indices go through PLTE and an index past the
+    palette's end reads black.  "auto": the layout of Pillow's own mode -- colour type 0 gives [H, W] (bit depth 1 becomes 0 / 255, depth
+    2 is multiplied by 85, depth 4 by 17: what Pillow's modes "1" and "L" convert to), colour type 4 [H, W, 2], 2 [H, W, 3], 6 [H, W, 4];
+    colour type 3 gives [H, W, 3] through the palette, the one place where "auto" is ``convert("RGB")`` and not Pillow's mode "P".  Any
+    other mode raises ValueError.
+
+    Supported: non-interlaced files of colour type 0 (1, 2, 4, 8 bits), 2 (8), 3 (1, 2, 4, 8), 4 (8) and 6 (8), any number of IDAT chunks
+    (empty ones and ones that split the zlib header included); unknown ancillary chunks are skipped; no gamma, ICC or sRGB handling, as
+    Pillow applies none on open.  16-bit samples, Adam7 interlace and APNG frames raise NotImplementedError("file i: ..."); a malformed
+    file (``png_parse_header``) raises ValueError("file i: ..."), both before any device work.
+
+    ``inflate="gpu"`` (default): the joined IDAT bytes of all files cross in one page-locked copy and ``aej_inflate_batch`` decodes them,
+    one wave per file.  ``inflate="host"``: ``zlib.decompress`` per file on a thread pool (``workers``, at most 16) and the filtered
+    scanlines are uploaded.  With either, the un-filter and the layout conversion run on the device and nothing is read back but the
+    status words, once per call: a stream that does not inflate, an inflated size other than H x (1 + row bytes) and a filter byte above
+    4 raise ValueError naming the file (the first such file of the call); the other files of the call are not affected.
+
+    DEPARTURE FROM PILLOW: IDAT chunk CRCs are not checked; the Adler-32 of the inflated data is, on the device (by zlib with
+    ``inflate="host"``).  A file whose only damage is an IDAT CRC therefore decodes here, where Pillow raises."""
+    if inflate not in ("gpu", "host"):
+        raise ValueError("inflate must be 'gpu' or 'host'")
+    files = list(files)
+    n = len(files)
+    modes = _check_modes(mode, n)
+    if n == 0:
+        return []
+    parsed = [png_parse_header(f, i) for i, f in enumerate(files)]
+    return _decode_parsed(get_context(device), parsed, [memoryview(f).cast("B") for f in files], modes, inflate, workers)
+
+
+def _decode_parsed(ctx, parsed, views, modes, inflate, workers, events=None):
+    """png_decode_many after the host parse.  events (tools/profiling/bench_png_decode.py): a dict that gets torch events around the two
+    enqueues, "inflate" (inflate="gpu" alone) and "unfilter": (start, end) each."""
+    from ._lib import INFLATE_STATUS, PNG_STATUS, PngDesc
+    t, lib, n = ctx.torch, ctx.lib, len(parsed)
+
+    def mark(name, at):
+        if events is not None:
+            events.setdefault(name, [t.cuda.Event(enable_timing=True), t.cuda.Event(enable_timing=True)])[at].record()
+
+    def align(v, a=4):
+        return (v + a - 1) // a * a
+
+    sizes = [d.height * (1 + d.row_bytes) for d in parsed]
+    in_off, out_off, shapes = np.zeros(n, np.int64), np.zeros(n, np.int64), []
+    ipos = opos = 0
+    for i, d in enumerate(parsed):
+        in_off[i], out_off[i] = ipos, opos
+        ipos += align(sizes[i])
+        c = _out_channels(d, modes[i])
+        shapes.append((d.height, d.width) if c == 1 and modes[i] == "auto" else (d.height, d.width, c))
+        opos += d.height * d.width * c
+    raw = ctx.empty((ipos,), t.uint8)
+    out = ctx.empty((opos,), t.uint8)
+    stat = ctx.empty((2, n), t.int32)
+
+    # one page-locked staging buffer, one host-to-device copy: the palettes, the stream descriptors and (inflate="gpu") the streams
+    off_pal = 0
+    off_sd = off_pal + align(n * 768, 16)
+    pos = off_sd + align(n * 32, 16)
+    st_off = []
+    if inflate == "gpu":
+        for d in parsed:
+            st_off.append(pos)
+            pos = align(pos + d.idat_bytes)
+    total = align(pos, 16)
+    host = ctx.pinned(total)[:total].numpy()
+    sd = host[off_sd:off_sd + n * 32].view(np.int64).reshape(n, 4)
+    streams = []
+    for i, d in enumerate(parsed):
+        host[off_pal + 768 * i:off_pal + 768 * (i + 1)] = np.frombuffer(d.palette, np.uint8)
+        pieces = [views[i][o:o + k] for o, k in d.idat_spans if k]
+        if inflate == "gpu":
+            p = st_off[i]
+            for piece in pieces:
+                host[p:p + len(piece)] = np.frombuffer(piece, np.uint8)
+                p += len(piece)
+            sd[i] = (st_off[i], d.idat_bytes, in_off[i], sizes[i])
+        else:
+            streams.append(b"".join(pieces))
+    if inflate == "host":
+        _inflate_on_host(ctx, streams, raw, in_off, sizes, workers)
+    dev = ctx.empty((total,), t.uint8)
+    dev.copy_(ctx.pinned(total)[:total], non_blocking=True)
+    base = dev.data_ptr()
+    if inflate == "gpu":
+        inflated = ctx.empty((n,), t.int64)
+        mark("inflate", 0)
+        ctx.check(lib.aej_inflate_batch(ctx.handle, base, base + off_sd, n, raw.data_ptr(), ctypes.c_uint64(raw.numel()), inflated.data_ptr(),
+                                        stat[0].data_ptr()))
+        mark("inflate", 1)
+        vouch = (inflated.data_ptr(), stat[0].data_ptr())
+    else:
+        stat[0].zero_()
+        vouch = (None, None)
+    descs = (PngDesc * n)(*parsed)
+    layouts = np.array([MODES.index(m) for m in modes], np.int32)
+    nws = int(lib.aej_png_workspace_bytes(ctx.handle, ctypes.addressof(descs), n))
+    if nws == 0:
+        raise ValueError("descriptors the library refuses")
+    ws = ctx.workspace(nws)
+    mark("unfilter", 0)
+    ctx.check(lib.aej_png_unfilter_batch(ctx.handle, ctypes.addressof(descs), n, raw.data_ptr(), ctypes.c_uint64(raw.numel()), in_off.ctypes.data,
+                                         *vouch, base + off_pal, layouts.ctypes.data, out.data_ptr(), ctypes.c_uint64(out.numel()),
+                                         out_off.ctypes.data, stat[1].data_ptr(), ws.data_ptr(), ctypes.c_uint64(nws)))
+    mark("unfilter", 1)
+    s = stat.cpu().numpy()                               # the one read-back; it also ends the staging buffer's use
+    for i in range(n):
+        if s[0, i]:
+            code = int(s[0, i])
+            raise ValueError(f"file {i}: {PNG_STATUS[1]} ({INFLATE_STATUS[code] if 0 <= code < len(INFLATE_STATUS) else f'status {code}'})")
+        if s[1, i]:
+            code = int(s[1, i])
+            raise ValueError(f"file {i}: {PNG_STATUS[code] if 0 <= code < len(PNG_STATUS) else f'status {code}'}")
+    return [out[int(out_off[i]):int(out_off[i]) + int(np.prod(shapes[i]))].view(shapes[i]) for i in range(n)]

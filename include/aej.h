@@ -1031,6 +1031,54 @@ AEJ_API int aej_resample_batch_win(aej_ctx *ctx, const aej_resample_desc *descs_
                                    const uint8_t *src, uint64_t src_bytes, uint8_t *dst, uint64_t dst_bytes, void *workspace,
                                    uint64_t workspace_bytes);
 
+/* ---- PNG files decoded on the device (png_decode_many) ------------------------------------------------------------------------------
+ * Pixel-identical to PIL.Image.open(file).convert("RGB"), or to the image in Pillow's own mode, for non-interlaced files of colour type
+ * 0 (grey: 1, 2, 4, 8 bits), 2 (RGB: 8), 3 (palette: 1, 2, 4, 8), 4 (grey + alpha: 8) and 6 (RGBA: 8).  The zlib stream of a file -- its
+ * IDAT chunks joined -- is inflated by aej_inflate_batch (or by the host); the scanline un-filter and the expansion to the output layout
+ * run in csrc/png.hip.  IDAT chunk CRCs are not checked (the Adler-32 of the inflated data is, on the device).  No gamma, ICC or sRGB
+ * handling, as Pillow applies none on open.
+ *
+ * aej_png_parse_host: HOST only, needs no context.  Walks the chunks of one file into *desc (all zero before) and the IDAT spans:
+ *   spans_host [span_capacity][2] int64 = { offset of the chunk's data in the file, its length }, empty chunks included.  spans_host
+ *   may be NULL (a count query: desc->n_idat and idat_bytes are still filled); with span_capacity < n_idat: AEJ_ERR_CAPACITY.  Returns 0;
+ *   AEJ_ERR_UNSUPPORTED for a valid file outside the supported set (16-bit samples, Adam7 interlace, APNG: an acTL or fdAT chunk, an
+ *   unknown critical chunk, a side above 2^24); AEJ_ERR_ARG for a malformed file (bad signature, missing IHDR / PLTE / IDAT, a bad CRC
+ *   on IHDR, PLTE or tRNS, zero width or height, a bit depth the colour type does not allow, a chunk length that runs past the file).
+ *   msg (may be NULL) gets the reason.  Unknown ancillary chunks are skipped; tRNS is noted and otherwise ignored.
+ * aej_png_workspace_bytes: the workspace of aej_png_unfilter_batch (one carried scanline per file); 0 for bad descriptors.
+ * aej_png_unfilter_batch: n files.  Only enqueues on the context's stream: no synchronisation, no read-back.  inflated: device bytes,
+ *   the filtered scanlines of file i -- height x (1 + row_bytes) bytes -- at in_offsets_host[i], a multiple of 4, and with its length
+ *   rounded up to 4 inside inflated_bytes (whole dwords are read).  inflate_out_bytes / inflate_status: the device arrays
+ *   aej_inflate_batch wrote for the n streams, or both NULL for scanlines the host inflated (and whose sizes it has checked).
+ *   palettes: device [n][768], the desc's palette of each file (NULL when no file has colour type 3).  layouts_host[i] (NULL: all RGB):
+ *   AEJ_PNG_RGB -- [height][width][3]: alpha dropped, grey replicated, indices through the palette (one past its end reads black) -- or
+ *   AEJ_PNG_AUTO -- colour type 0: [height][width] (1 bit -> 0 / 255, 2 bits x 85, 4 bits x 17), 4: [..][2], 2: [..][3], 6: [..][4],
+ *   3: [..][3] through the palette.  Image i is written at out_offsets_host[i]; nothing else of out is touched.  status: device [n]
+ *   int32, AEJ_PNG_*; a file whose status is not OK leaves its image partly written or untouched, the other files are not affected. */
+enum { AEJ_PNG_OK = 0, AEJ_PNG_INFLATE_FAILED = 1, AEJ_PNG_SIZE_MISMATCH = 2 /* inflated bytes != height * (1 + row_bytes) */,
+       AEJ_PNG_BAD_FILTER = 3 /* a filter byte above 4 */ };
+enum { AEJ_PNG_RGB = 0, AEJ_PNG_AUTO = 1 };
+typedef struct aej_png_desc {
+    int32_t width, height;
+    int32_t bit_depth, colour_type;
+    int32_t channels;              /* samples per pixel in the file: 1, 3, 1, 2, 4 for colour type 0, 2, 3, 4, 6 */
+    int32_t row_bytes;             /* ceil(width * channels * bit_depth / 8): a scanline without its filter byte */
+    int32_t interlace;
+    int32_t n_idat;                /* IDAT chunks, empty ones included */
+    int32_t palette_len;           /* entries of PLTE (0: none) */
+    int32_t has_trns;
+    int64_t idat_bytes;            /* their data bytes together: the length of the zlib stream */
+    uint8_t palette[768];          /* PLTE, zero past palette_len */
+    char mode[8];                  /* Pillow's mode of the opened file: "1", "L", "P", "RGB", "LA", "RGBA" */
+} aej_png_desc;
+AEJ_API int aej_png_parse_host(const uint8_t *data_host, uint64_t nbytes, aej_png_desc *desc_host, int64_t *spans_host, int span_capacity,
+                               char *msg, int msg_capacity);
+AEJ_API uint64_t aej_png_workspace_bytes(aej_ctx *ctx, const aej_png_desc *descs_host, int n);
+AEJ_API int aej_png_unfilter_batch(aej_ctx *ctx, const aej_png_desc *descs_host, int n, const uint8_t *inflated, uint64_t inflated_bytes,
+                                   const int64_t *in_offsets_host, const int64_t *inflate_out_bytes, const int32_t *inflate_status,
+                                   const uint8_t *palettes, const int32_t *layouts_host, uint8_t *out, uint64_t out_bytes,
+                                   const int64_t *out_offsets_host, int32_t *status, void *workspace, uint64_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif
