@@ -357,6 +357,7 @@ SIGNATURES = {
     "aej_test_jpegprog_coefs_host": (_I, [_P, _P, _P, _U64, _I, _P, _U64]),                                 # include/aej_testing.h (tests only)
     "aej_test_jpeg_adobe_pixels_host": (_I, [_P, _I64, _I, _I, _P]),                                        # include/aej_testing.h (tests only)
     "aej_test_jpegdec_idct_host": (_I, [_P, _P, _I, _P]),                                                   # include/aej_testing.h (tests only)
+    "aej_test_jpegdec_coefs_host": (_I, [_P, _P, _U64, _P, _U64]),                                          # include/aej_testing.h (tests only)
 }
 
 # status values of aej_inflate_batch / aej_decode_headers (include/aej.h AEJ_INFLATE_* / AEJ_HEADER_*)

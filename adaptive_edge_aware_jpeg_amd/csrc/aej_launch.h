@@ -329,10 +329,10 @@ int jfifprog_scan_device(hipStream_t st, const short *coefs_host, long long n, i
 #include "jpegdec_core.h"
 
 namespace aej {
-struct JdBufSizes { long long chunks, segs, slots, blocks, clean, planes, px, grp[3], grp440[3], grpl[4], grpb, grpa, uniform, grps[3]; };      // totals over the files of one call (grp, grp440, grpl, grpb, grps: JdFile::grp_base, ::grp440_base, ::grpl_base, ::grpb_base, ::grps_base; grpa: ::grpa_base, the workgroups of k_jd_adobe -- non-zero exactly when the call has a four-component or RGB-coded file; uniform: the baseline ones among them with JdFile::uniform)
+struct JdBufSizes { long long chunks, segs, slots, blocks, clean, planes, px, grp[3], grp440[3], grpl[4], grpb, grpa, uniform, grps[3]; };      // totals over the files of one call (grp, grp440, grpl, grpb, grps: JdFile::grp_base, ::grp440_base, ::grpl_base, ::grpb_base, ::grps_base; grpa: ::grpa_base, the workgroups of k_jd_adobe -- non-zero exactly when the call has a four-component or RGB-coded file; uniform: the files with JdFile::uniform, three-component YCbCr ones included -- a call with one runs the kFour slot kernels too)
 struct JdBufs {
     JdFile *files; aej_jpegdec_desc *descs; int *last_change;      // one upload: files, descriptors, the "last round that changed" word
-    aej_jpeg_adobe *adobe;                                         // and, in a call with z.grpa > 0 alone, the files' aej_jpeg_adobe behind that word (else NULL)
+    aej_jpeg_adobe *adobe;                                         // and, in a call that runs the kFour slot kernels (z.grpa > 0 or z.uniform > 0), room for the files' aej_jpeg_adobe (uploaded when z.grpa > 0; else NULL)
     int *cnt; long long *pre, *clean_len; JdSeg *segs; unsigned char *clean; JdSlots sl; short *coef; unsigned char *planes;
 };
 struct JdHuffSrc { bool defined = false; unsigned char bits[17] = {}; unsigned char vals[256] = {}; int count = 0; };      // one DHT table
@@ -396,6 +396,7 @@ hipError_t launch_jpegdec_begin(hipStream_t st, int n, const JdBufSizes &z, cons
                                 const unsigned char *scans, int S, int *status);
 hipError_t launch_jpegdec_unstuff(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, const unsigned char *scans, int S, int *status);
 hipError_t launch_jpegdec_recon(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, unsigned char *out);
+int jpegdec_coefs_host(const aej_jpegdec_desc &d, const unsigned char *file, unsigned long long nbytes, short *coef, unsigned long long coef_blocks);
 hipError_t launch_jpegdec_sync(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, int S, int first_round, int rounds);
 hipError_t launch_jpegdec_write(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, int S, int *status);      // finish without the reconstruction
 hipError_t launch_jpegdec_finish(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, int S, unsigned char *out, int *status);

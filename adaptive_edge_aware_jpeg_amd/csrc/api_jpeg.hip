@@ -500,8 +500,11 @@ static int jpegdec_decode(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *
     long long max_slots = 0;
     for (const JdFile &f : files) max_slots = std::max(max_slots, f.n_slots);
     AEJ_TRY(bind_device(ctx));
-    if (z.grpa > 0)                                   // a call with a four-component or RGB-coded file: the kernels of such a call read these
+    if (z.grpa > 0) {                                 // a call with a four-component or RGB-coded file: the kernels of such a call read these
         AEJ_HIP_CHECK(hipMemcpyAsync(w.adobe, adobe_host, sizeof(aej_jpeg_adobe) * n, hipMemcpyHostToDevice, ctx->stream));
+    } else if (w.adobe) {                             // the kFour slot kernels for a uniform three-component file alone: no file has a component 3
+        AEJ_HIP_CHECK(hipMemsetAsync(w.adobe, 0, sizeof(aej_jpeg_adobe) * n, ctx->stream));      // (jd_comp4), so nothing reads these; zeros all the same
+    }
     AEJ_HIP_CHECK(launch_jpegdec_begin(ctx->stream, n, z, w, blob.data(), blob.size(), scans, S, status));
     // sync rounds: kJdSyncBatch launches, then one word read back; more only while the last launched round still changed something.
     // Each round settles at least the first unsettled subsequence of every segment, so max_slots rounds always suffice.
@@ -645,6 +648,13 @@ extern "C" int aej_test_jpegdec_idct_host(const int16_t *coef_host, const uint16
     if (!coef_host || !qt_host || !out_host || (size != 1 && size != 2 && size != 4)) return AEJ_ERR_ARG;
     jd_idct_sized(coef_host, qt_host, size, out_host, size);
     return 0;
+}
+
+extern "C" int aej_test_jpegdec_coefs_host(const aej_jpegdec_desc *desc_host, const uint8_t *file_host, uint64_t nbytes, int16_t *coef_out_host,
+                                           uint64_t coef_blocks)
+{
+    if (!desc_host || !file_host || !coef_out_host) return AEJ_ERR_ARG;
+    return jpegdec_coefs_host(*desc_host, file_host, nbytes, coef_out_host, coef_blocks);
 }
 
 extern "C" int64_t aej_jpegdec_sync_rounds(aej_ctx *ctx)

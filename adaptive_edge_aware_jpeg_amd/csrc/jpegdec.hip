@@ -36,7 +36,7 @@
 //                   the reduced IDCTs and libjpeg's up-sampling rules at that scale.  The segment skip and the coefficient window of the
 //                   boxed files carry over unchanged (they work in MCUs)
 //   k_jd_init4 / k_jd_sync4 / k_jd_scan_slots4 / k_jd_write4   the slot kernels of a call that has a four-component (CMYK, YCCK) or RGB-coded
-//                   file (aej_jpegdec_batch_adobe), for all of its files: a fourth DC sum and prefix per slot, a 4-bit block slot in the packed
+//                   file (aej_jpegdec_batch_adobe), or a YCbCr file whose three components share one table pair (jd_four), for all of its files: a fourth DC sum and prefix per slot, a 4-bit block slot in the packed
 //                   state, component 3 under the tables of the file's aej_jpeg_adobe; k_jd_fix4 between two k_jd_scan_slots4 for the files
 //                   whose components share one table pair (JdFile::uniform), where the block slot comes from the block counts
 //   k_jd_idct4      k_jd_idct for those files: four sample planes
@@ -1119,7 +1119,7 @@ void jpegdec_layout(const aej_jpegdec_desc *descs, int n, int S, std::vector<JdF
     for (int i = 0; i < n; i++) {
         jpeg_stream_layout(descs[i].scan_length, descs[i].n_segments, S, files[i], z);
         jpeg_recon_layout(descs[i], shifts ? shifts[i] : 0, files[i], z, boxes ? boxes + 4 * i : nullptr, true, adobe ? adobe + i : nullptr);
-        if (adobe && jpeg_adobe_new(adobe + i)) {     // one DC and one AC table for every component?
+        if (descs[i].ncomp == 3 || (adobe && jpeg_adobe_new(adobe + i))) {      // one DC and one AC table for every component?
             const aej_jpegdec_desc &d = descs[i];
             bool same = !memcmp(&d.dc[1], &d.dc[0], sizeof d.dc[0]) && !memcmp(&d.dc[2], &d.dc[0], sizeof d.dc[0]) &&
                         !memcmp(&d.ac[1], &d.ac[0], sizeof d.ac[0]) && !memcmp(&d.ac[2], &d.ac[0], sizeof d.ac[0]);
@@ -1130,13 +1130,18 @@ void jpegdec_layout(const aej_jpegdec_desc *descs, int n, int S, std::vector<JdF
     }
 }
 
+// The kFour slot kernels run for a call with a four-component or RGB-coded file, and for one with a file whose components all decode
+// under one table pair (JdFile::uniform) -- a three-component one too: a flat page saved with optimised tables is such a file, and the
+// plain kernels would need one sync round per subsequence for it, since no bit ever corrects a wrong block slot.
+static bool jd_four(const JdBufSizes &z) { return z.grpa > 0 || z.uniform > 0; }
+
 unsigned long long jpegdec_carve(void *base, int n, const JdBufSizes &z, JdBufs &w)
 {
     Carver c(base);
     w.files = (JdFile *)c.take<char>(sizeof(JdFile) * n + sizeof(aej_jpegdec_desc) * n + 16);      // one upload: see JdBufs
     w.descs = base ? (aej_jpegdec_desc *)((char *)w.files + sizeof(JdFile) * n) : nullptr;
     w.last_change = base ? (int *)((char *)w.descs + sizeof(aej_jpegdec_desc) * n) : nullptr;
-    const bool four = z.grpa > 0;                     // a four-component or RGB-coded file: their aej_jpeg_adobe (a second upload), a fourth DC sum per slot
+    const bool four = jd_four(z);                     // the kFour slot kernels: the files' aej_jpeg_adobe (a second upload, when the call has any), a fourth DC sum per slot
     w.adobe = four ? c.take<aej_jpeg_adobe>(n) : nullptr;
     w.cnt = c.take<int>(z.chunks * 3);
     w.pre = c.take<long long>(z.chunks * 3);
@@ -1165,7 +1170,7 @@ hipError_t launch_jpegdec_begin(hipStream_t st, int n, const JdBufSizes &z, cons
     hipError_t e = hipMemcpyAsync(w.files, blob_host, blob_bytes, hipMemcpyHostToDevice, st);
     if (e != hipSuccess) return e;
     if ((e = launch_jpegdec_unstuff(st, n, z, w, scans, S, status)) != hipSuccess) return e;
-    if (z.grpa > 0) {
+    if (jd_four(z)) {
         hipLaunchKernelGGL(k_jd_init4, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.slots, w.segs, w.clean, w.sl, S,
                            w.last_change, w.adobe);
     } else {
@@ -1193,7 +1198,7 @@ hipError_t launch_jpegdec_unstuff(hipStream_t st, int n, const JdBufSizes &z, co
 hipError_t launch_jpegdec_sync(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, int S, int first_round, int rounds)
 {
     for (int r = first_round; r < first_round + rounds; r++) {
-        if (z.grpa > 0)
+        if (jd_four(z))
             hipLaunchKernelGGL(k_jd_sync4, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.slots, w.segs, w.clean, w.sl, S, r,
                                w.last_change, w.adobe);
         else
@@ -1208,7 +1213,7 @@ hipError_t launch_jpegdec_write(hipStream_t st, int n, const JdBufSizes &z, cons
 {
     hipError_t e = hipMemsetAsync(w.coef, 0, (size_t)z.blocks * 128, st);
     if (e != hipSuccess) return e;
-    if (z.grpa > 0) {
+    if (jd_four(z)) {
         hipLaunchKernelGGL(k_jd_scan_slots4, dim3(n), dim3(kJdScanThreads), 0, st, w.files, w.sl);
         if (z.uniform > 0) {                          // files whose bits do not tell the block slot: DC sums again under the slots the block counts give
             hipLaunchKernelGGL(k_jd_fix4, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.slots, w.segs, w.clean, w.sl, S, w.adobe);
@@ -1265,6 +1270,56 @@ hipError_t launch_jpegdec_recon(hipStream_t st, int n, const JdBufSizes &z, cons
         hipLaunchKernelGGL(k_jd_rgb, dim3(jd_grid(z.px)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.px, w.planes, out);
     }
     return launch_jpegdec_recon_scaled(st, n, z, w, out);
+}
+
+// ---- host: the entropy decode stepped through on the CPU (aej_test_jpegdec_coefs_host) ------------------------------------------------------
+// One or three components.  Un-stuffs as k_jd_count / k_jd_scatter do (jd_byte_class, RSTn numbers checked), then one jd_run<true> per
+// restart segment from its first bit to its last: what the sync rounds' fixed point and k_jd_write give, without subsequences.
+int jpegdec_coefs_host(const aej_jpegdec_desc &d, const unsigned char *file, unsigned long long nbytes, short *coef, unsigned long long coef_blocks)
+{
+    if ((d.ncomp != 1 && d.ncomp != 3) || d.blocks_per_mcu < 1 || d.blocks_per_mcu > 6 || d.mcux < 1 || d.mcuy < 1 || d.n_segments < 1) return AEJ_ERR_ARG;
+    if (d.scan_offset < 0 || d.scan_length < 0 || (unsigned long long)d.scan_offset + (unsigned long long)d.scan_length > nbytes) return AEJ_ERR_ARG;
+    const long long total = (long long)d.mcux * d.mcuy, blocks = total * d.blocks_per_mcu;
+    if ((unsigned long long)blocks > coef_blocks) return AEJ_ERR_CAPACITY;
+    memset(coef, 0, (size_t)blocks * 128);
+    const unsigned char *s = file + d.scan_offset;
+    std::vector<unsigned> words((size_t)(d.scan_length / 4 + 8), 0u);
+    unsigned char *clean = reinterpret_cast<unsigned char *>(words.data());
+    std::vector<JdSeg> segs(1, JdSeg{});
+    long long o = 0;
+    for (long long p = 0; p < d.scan_length; p++) {
+        const int c = jd_byte_class(s, d.scan_length, p);
+        if (c == kJdByteEnd) break;
+        if (c == kJdByteData) clean[o++] = s[p];
+        else if (c == kJdByteRst) {
+            if ((s[p] & 7) != (int)((segs.size() - 1) & 7)) return AEJ_JPEGDEC_BAD_RESTART;
+            JdSeg g{};
+            g.start = o;
+            segs.push_back(g);
+        }
+    }
+    if ((long long)segs.size() != d.n_segments) return AEJ_JPEGDEC_BAD_RESTART;
+    const long long ri = d.restart_interval ? d.restart_interval : total;
+    for (size_t g = 0; g < segs.size(); g++) {
+        JdSeg &sg = segs[g];
+        sg.nbytes = (g + 1 < segs.size() ? segs[g + 1].start : o) - sg.start;
+        sg.first_mcu = (int)std::min((long long)g * ri, total);
+        sg.n_mcu = (int)std::min(ri, total - sg.first_mcu);
+        JdBits br(clean);
+        long long pos = sg.start * 8, next = 0;
+        const long long seg_end = (sg.start + sg.nbytes) * 8, seg_blocks = (long long)sg.n_mcu * d.blocks_per_mcu;
+        int k = 0, z = 0, nstart = 0, dc[3] = {}, pred[3] = {};
+        const int rc = jd_run<true>(d, br, pos, k, z, seg_end, seg_end, nstart, dc, coef + (long long)sg.first_mcu * d.blocks_per_mcu * 64, next,
+                                    seg_blocks, pred);
+        if (rc == kJdRunDone) continue;
+        if (rc == kJdRunStop) {
+            if ((z == 0 ? next : next - 1) < seg_blocks) return AEJ_JPEGDEC_TRUNCATED;
+            continue;
+        }
+        return rc == kJdRunOutOfBits ? AEJ_JPEGDEC_TRUNCATED : rc == kJdRunBadCode ? AEJ_JPEGDEC_BAD_CODE
+             : rc == kJdRunPast63 ? AEJ_JPEGDEC_RUN_PAST_63 : AEJ_JPEGDEC_BAD_DC;
+    }
+    return 0;
 }
 
 }  // namespace aej

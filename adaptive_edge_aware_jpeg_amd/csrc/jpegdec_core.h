@@ -48,9 +48,10 @@ struct JdFile {
     long long grps_base[3];            // [log2 scale - 1]: first workgroup of the file in k_jd_sbox<log2 scale>'s grid (shift & kJdSbox): box and
                                        // win are then in pixels and MCUs of the scaled image (jd_sbox_window), ow, oh the box's
     int pw3, ph3;                      // such a file's fourth plane (whole MCUs; behind the three others), 0 x 0 for three components
-    int uniform;                       // such a baseline file whose components all decode under one DC and one AC table (what libjpeg writes
-                                       // for CMYK and RGB): its bits say nothing about the block slot, which the kFour kernels then take from
-                                       // the block counts instead of the predecessor's state (k_jd_sync4, k_jd_fix4, k_jd_write4)
+    int uniform;                       // a baseline file of three or four components that all decode under one DC and one AC table (what
+                                       // libjpeg writes for CMYK and RGB, and what optimised tables of a flat YCbCr picture can be): its bits
+                                       // say nothing about the block slot, which the kFour kernels -- run for every call with such a file --
+                                       // take from the block counts instead of the predecessor's state (k_jd_sync4, k_jd_fix4, k_jd_write4)
 };
 
 // one restart segment: written by the un-stuffing scatter (start) and k_jd_segments (the rest)
@@ -103,6 +104,8 @@ struct JdBits {
     }
 };
 
+// The "& 255" below is defensive only and no test can tell it from its absence: a code that no entry of the 9-bit table matches and that is
+// <= maxcode[l] is, by the canonical order of the codes, one of length l's own, so valoff[l] + code is its index in vals, 0 .. 255.
 AEJ_HD inline bool jd_huff(const aej_jpegdec_huff &h, unsigned win, int &len, int &sym)
 {
     const unsigned e = h.lut[win >> 23];
@@ -212,7 +215,10 @@ AEJ_HD inline void jd_idct8(long long *d, int s)
     d[3 * s] = jd_descale(t13 + t0, n); d[4 * s] = jd_descale(t13 - t0, n);
 }
 
-AEJ_HD inline unsigned char jd_range_limit(long long x)      // libjpeg's masked table: wraps as the decoder's does
+// libjpeg's masked range-limit table (the C code's: jidctint.c after prepare_range_limit_table), which wraps modulo 1024.  Pillow runs
+// libjpeg-turbo's SIMD inverse DCT, which saturates instead; the two agree while x stays in [-512, 511], which every block of real
+// 8-bit samples does (the JPEG decode section, has the measured boundary).  Outside it this follows the C code, not Pillow.
+AEJ_HD inline unsigned char jd_range_limit(long long x)
 {
     const int m = (int)(x & 1023);
     return (unsigned char)(m < 128 ? m + 128 : m < 512 ? 255 : m < 896 ? 0 : m - 896);

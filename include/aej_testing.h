@@ -43,6 +43,14 @@ AEJ_API int aej_test_jfif_prog_scan(aej_ctx *ctx, const int16_t *coefs_host, int
  * samples, row after row -- computed by the function of csrc/jpegdec_core.h that the kernel calls (jd_idct_sized). */
 AEJ_API int aej_test_jpegdec_idct_host(const int16_t *coef_host, const uint16_t *qt_host, int size, uint8_t *out_host);
 
+/* The baseline entropy decode of one file, HOST only, for coefficient-level comparison with tests/scaled_decode_reference.py: desc_host as
+ * aej_jpegdec_parse_host wrote it for file_host (one or three components).  The scan is un-stuffed with the byte classifier the kernels
+ * use (jd_byte_class), and each restart segment is then decoded from its first bit to its last by the per-thread routine of
+ * csrc/jpegdec_core.h (jd_run, jd_huff).  coef_out_host gets int16 [mcux * mcuy * blocks_per_mcu][64], natural order, blocks in MCU order
+ * (coef_blocks: its capacity in blocks).  Returns the first AEJ_JPEGDEC_* status met (0 = none) or an AEJ_ERR_*. */
+AEJ_API int aej_test_jpegdec_coefs_host(const aej_jpegdec_desc *desc_host, const uint8_t *file_host, uint64_t nbytes, int16_t *coef_out_host,
+                                        uint64_t coef_blocks);
+
 /* The per-pixel colour rules of the four-component / RGB-coded reconstruction (aej_jpegdec_batch_adobe), HOST only: samples4_host [n][4]
  * up-sampled samples of one pixel each, colour AEJ_JPEG_RGB, _CMYK or _YCCK, components 3 or 4 (4: not with _RGB) -> out_host
  * [n][components], computed by the functions of csrc/jpegdec_core.h that the kernel calls (jd_adobe_pixel: jd_cmyk_pixel, jd_ycck_pixel,

@@ -4,7 +4,11 @@ Pillow cannot write the layout (subsampling="4:4:0" raises), but a Pillow 4:2:2 
 of its frame header goes from 0x21 to 0x12 and its height and width fields are swapped: both layouts have Y, Y, Cb, Cr per MCU, the same
 number of MCUs (ceil(W / 16) x ceil(H / 8) becomes ceil(H / 8) x ceil(W / 16)) and the same number of real blocks per component in the
 non-interleaved scans of a progressive file, so every scan -- its restart intervals too -- decodes to the end.  The picture is another
-one, which does not matter: Pillow's decode of the patched file is the reference."""
+one, which does not matter: Pillow's decode of the patched file is the reference.
+
+There is no up-sampling rule here.  The NumPy model of the layout's reconstruction -- libjpeg's h1v2 "fancy" filter, replication at scale
+8 -- is tests/scaled_decode_reference.upsample_h1v2 and the 4:4:0 branch of its decode(), checked against pil_decode-style Pillow
+decodes of written 4:4:0 files at every scale (tests/test_jpeg_streams_host.py)."""
 import io
 import struct
 

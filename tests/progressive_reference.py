@@ -58,9 +58,7 @@ def walk(data):
             ns = body[0]
             ids = [c["id"] for c in frame["comps"]]
             comps = [(ids.index(body[1 + 2 * i]), body[2 + 2 * i] >> 4, body[2 + 2 * i] & 15) for i in range(ns)]
-            q = p
-            while not (data[q] == 0xFF and data[q + 1] != 0 and not 0xD0 <= data[q + 1] <= 0xD7 and data[q + 1] != 0xFF):
-                q += 1
+            q = _scan_end(data, p)
             scans.append(dict(comps=comps, ss=body[1 + 2 * ns], se=body[2 + 2 * ns], ah=body[3 + 2 * ns] >> 4, al=body[3 + 2 * ns] & 15,
                               ri=ri, dc={k: v for k, v in tables[0].items()}, ac={k: v for k, v in tables[1].items()},
                               start=p, end=q, dht=dht_since, qts={c[0]: qts.get(frame["comps"][c[0]]["tq"]) for c in comps}))
@@ -69,11 +67,31 @@ def walk(data):
     return frame, scans
 
 
+def _ff_run(data, i):
+    """data[i] is 0xFF: (offset of the byte after the run of 0xFF that starts there, that byte; None at the end of the data)"""
+    while i < len(data) and data[i] == 0xFF:
+        i += 1
+    return i, (data[i] if i < len(data) else None)
+
+
+def _scan_end(data, p):
+    """offset of the marker that ends the entropy-coded data starting at p, by libjpeg's rule: a run of 0xFF followed by 0x00 is one
+    data 0xFF, followed by RSTn one restart marker, followed by anything else the end of the scan (the run's first byte is returned)"""
+    while True:
+        if data[p] != 0xFF:
+            p += 1
+            continue
+        q, c = _ff_run(data, p)
+        if c is None or not (c == 0 or 0xD0 <= c <= 0xD7):
+            return p
+        p = q + 1
+
+
 class _Bits:
-    """MSB-first reader over one restart interval's bytes (stuffing removed)"""
+    """MSB-first reader over one restart interval's bytes (stuffing removed by _intervals)"""
 
     def __init__(self, raw):
-        self.b, self.pos = raw.replace(b"\xff\x00", b"\xff"), 0
+        self.b, self.pos = raw, 0
 
     def bit(self):
         assert self.pos < 8 * len(self.b), "ran out of bits"
@@ -114,15 +132,25 @@ def _extend(v, t):
 
 
 def _intervals(data, scan):
-    raw, out, i, last = data[scan["start"]:scan["end"]], [], 0, 0
-    while i + 1 < len(raw):
-        if raw[i] == 0xFF and 0xD0 <= raw[i + 1] <= 0xD7:
-            out.append(raw[last:i])
-            last = i + 2
-            i += 2
+    """the scan's restart intervals, un-stuffed, by the rule of _scan_end.  Bytes between an interval's last needed bit and the next
+    marker stay at its end, where the decode of a known number of units never looks: libjpeg drops them too (with a warning)"""
+    raw, out, cur, i = data[scan["start"]:scan["end"]], [], bytearray(), 0
+    while i < len(raw):
+        if raw[i] != 0xFF:
+            cur.append(raw[i])
+            i += 1
+            continue
+        i, c = _ff_run(raw, i)
+        if c is None:                                              # fill bytes in front of the marker that ends the scan
+            break
+        if c == 0:
+            cur.append(0xFF)
         else:
-            i += 2 if raw[i] == 0xFF else 1
-    out.append(raw[last:])
+            assert 0xD0 <= c <= 0xD7
+            out.append(bytes(cur))
+            cur = bytearray()
+        i += 1
+    out.append(bytes(cur))
     return out
 
 

@@ -8,7 +8,9 @@ arrays, written from libjpeg's rules (jidctred.c, jdmaster.c, jdsample.c), not f
   * 4:2:2 chroma is up-sampled with the h2v1 "fancy" filter at scales 2 and 4 (plain replication for a plane at most 2 samples wide)
     and with plain replication at scale 8, where the smallest IDCT is 1 x 1 and libjpeg switches fancy up-sampling off.
 
-    rgb = decode(data, scale)                   # uint8 [ceil(H / s)][ceil(W / s)][3]
+    rgb = decode(data, scale)                   # uint8 [ceil(H / s)][ceil(W / s)][3]; every layout the library takes, 4:4:0 included
+    luma = decode(data, scale, "L")             # uint8 [ceil(H / s)][ceil(W / s)]: the luma plane, what Pillow's draft("L", ...) gives
+    rgb = decode(data, 1, simd=True)            # the 8 x 8 IDCT as libjpeg-turbo's SIMD code computes it outside the range of real samples
     samples = idct_reduced(coef, qt, n)         # [..., 8, 8] quantised coefficients -> [..., n, n] samples, n in (1, 2, 4)
 
 Coefficients come from tests/progressive_reference.py (progressive files) or from the sequential Huffman decode below (baseline
@@ -94,12 +96,71 @@ def baseline_coefficients(data):
     return coef
 
 
+# ---- the 8 x 8 inverse DCT as libjpeg-turbo's x86 SIMD code computes it (jidctint-sse2 / -avx2: the published algorithm of jidctint.c on
+# 16-bit lanes).  Inside the range real samples give it equals jfif_reference.idct; outside it differs in three places: the dequantised
+# products and the 16-bit sums (in0 +- in4, the odd part's z3 and z4) wrap at 16 bits, each pass's results are packed to int16 with
+# saturation, and the last step is a saturating pack to int8 plus 128 -- not the masked table of the C code.
+def _wrap16(x):
+    return ((x + 32768) & 65535) - 32768
+
+
+def _wrap32(x):
+    return ((x + (1 << 31)) & ((1 << 32) - 1)) - (1 << 31)
+
+
+def _simd_pass(d, n):
+    """one pass over axis -1 of int16-valued [..., 8] -> int16-valued [..., 8]"""
+    F = J.F
+    t2 = d[..., 2] * F["f0541"] + d[..., 6] * (F["f0541"] - F["f1847"])
+    t3 = d[..., 2] * (F["f0541"] + F["f0765"]) + d[..., 6] * F["f0541"]
+    t0, t1 = _wrap16(d[..., 0] + d[..., 4]) << 13, _wrap16(d[..., 0] - d[..., 4]) << 13
+    t10, t13, t11, t12 = t0 + t3, t0 - t3, t1 + t2, t1 - t2
+    d7, d5, d3, d1 = d[..., 7], d[..., 5], d[..., 3], d[..., 1]
+    z3, z4 = _wrap16(d7 + d3), _wrap16(d5 + d1)
+    z3, z4 = z3 * (F["f1175"] - F["f1961"]) + z4 * F["f1175"], z3 * F["f1175"] + z4 * (F["f1175"] - F["f0390"])
+    o0 = d7 * (F["f0298"] - F["f0899"]) - d1 * F["f0899"] + z3
+    o3 = -d7 * F["f0899"] + d1 * (F["f1501"] - F["f0899"]) + z4
+    o1 = d5 * (F["f2053"] - F["f2562"]) - d3 * F["f2562"] + z4
+    o2 = -d5 * F["f2562"] + d3 * (F["f3072"] - F["f2562"]) + z3
+    out = np.empty_like(d)
+    for k, (a, b) in enumerate(((t10, o3), (t11, o2), (t12, o1), (t13, o0))):
+        a, b = _wrap32(a), _wrap32(b)
+        out[..., k] = np.clip(_wrap32(_wrap32(a + b) + (1 << (n - 1))) >> n, -32768, 32767)
+        out[..., 7 - k] = np.clip(_wrap32(_wrap32(a - b) + (1 << (n - 1))) >> n, -32768, 32767)
+    return out
+
+
+def idct_simd(coef, qt):
+    """[..., 8, 8] quantised coefficients (natural order) and 64 quantisers -> [..., 8, 8] samples"""
+    coef = np.asarray(coef, np.int64)
+    d = _wrap16(coef * np.asarray(qt, np.int64).reshape(8, 8))
+    ws = np.swapaxes(_simd_pass(np.swapaxes(d, -1, -2), 11), -1, -2)
+    flat = (coef[..., 1:, :] == 0).all((-1, -2))                    # no AC term below row 0: every row is the first, shifted left in 16 bits
+    ws = np.where(flat[..., None, None], _wrap16(d[..., :1, :] << 2) + np.zeros_like(d), ws)
+    return np.clip(_simd_pass(ws, 18), -128, 127) + 128
+
+
 _COEF = {}
 
 
-def decode(data, scale):
-    """uint8 [ceil(H / scale)][ceil(W / scale)][3] of a baseline or complete progressive file"""
-    assert scale in (1, 2, 4, 8)
+def upsample_h1v2(c, H):
+    """libjpeg's h1v2 "fancy" up-sampling of ceil(H / 2) real chroma rows -> [H] rows: 3/4 of the nearer row and 1/4 of the further,
+    the edge rows standing in for the rows outside.  No narrow-plane exception (jdsample.c has none for this layout)."""
+    h = -(-H // 2)
+    c = c[:h]
+    above = np.concatenate([c[:1], c[:-1]])
+    below = np.concatenate([c[1:], c[-1:]])
+    out = np.empty((2 * h, c.shape[1]), np.int64)
+    out[0::2] = (3 * c + above + 1) >> 2
+    out[1::2] = (3 * c + below + 2) >> 2
+    return out[:H]
+
+
+def decode(data, scale=1, mode="RGB", simd=False):
+    """uint8 [ceil(H / scale)][ceil(W / scale)][3] of a baseline or complete progressive file of any layout the library takes (4:4:4,
+    4:2:2, 4:2:0, 4:4:0, grey); mode "L": [ceil(H / scale)][ceil(W / scale)], the luma plane (a grey file's samples).  simd (full size
+    only): the 8 x 8 inverse DCT with the semantics of libjpeg-turbo's SIMD code (idct_simd), which matters only outside the range of real samples"""
+    assert scale in (1, 2, 4, 8) and mode in ("RGB", "L") and not (simd and scale != 1)
     data = bytes(data)
     frame, scans = P.walk(data)
     if data not in _COEF:                                          # the slow part, shared by the scales of one file
@@ -116,16 +177,25 @@ def decode(data, scale):
     planes = []
     for c, g in enumerate(geo):
         n = idct_size(g["h"], g["v"], hmax, vmax, m)
-        b = idct_reduced(coef[c].reshape(g["ah"], g["aw"], 8, 8), qts[c], n)
+        blocks = coef[c].reshape(g["ah"], g["aw"], 8, 8)
+        b = idct_simd(blocks, qts[c]) if simd else idct_reduced(blocks, qts[c], n)
         p = b.swapaxes(1, 2).reshape(g["ah"] * n, g["aw"] * n)
         planes.append(p[:-(-H * g["v"] * n // (vmax * 8)), :-(-W * g["h"] * n // (hmax * 8))])      # the component's real size
     y = planes[0]
     oh, ow = y.shape
     assert (oh, ow) == (-(-H // scale), -(-W // scale))
+    if mode == "L":
+        return y.astype(np.uint8)
     if len(planes) == 1:
         return np.stack([y, y, y], -1).astype(np.uint8)
     cb, cr = planes[1], planes[2]
-    if (hmax, vmax) == (2, 2) and scale == 1:                      # full size: h2v2 fancy, as tests/jfif_reference.py has it
+    if (hmax, vmax) == (1, 2):                                     # 4:4:0: h1v2 fancy, replication at scale 8 (the smallest IDCT is 1 x 1)
+        assert cb.shape == (-(-oh // 2), ow)
+        if scale == 8:
+            cb, cr = np.repeat(cb, 2, 0)[:oh], np.repeat(cr, 2, 0)[:oh]
+        else:
+            cb, cr = upsample_h1v2(cb, oh), upsample_h1v2(cr, oh)
+    elif (hmax, vmax) == (2, 2) and scale == 1:                      # full size: h2v2 fancy, as tests/jfif_reference.py has it
         cb, cr = J._upsample(cb, H, W), J._upsample(cr, H, W)
     elif cb.shape != y.shape:                                      # 4:2:2: the one layout still up-sampled below full size
         assert (hmax, vmax) == (2, 1) and cb.shape == (oh, -(-ow // 2))
