@@ -387,10 +387,11 @@ bool jpeg_box_inside(const D &d, const int *box)
     return 0 <= box[0] && box[0] < box[2] && box[2] <= d.width && 0 <= box[1] && box[1] < box[3] && box[3] <= d.height;
 }
 inline int jpeg_scale_shift(int scale) { return scale == 1 ? 0 : scale == 2 ? 1 : scale == 4 ? 2 : scale == 8 ? 3 : -1; }      // -1: not a scale
-// shifts: log2 of every file's scale (+ kJdLuma for a file that leaves as its luma plane), or NULL for all at full size, RGB
-// boxes: NULL or [n][4], jpeg_recon_layout's box of every file
-void jpegdec_layout(const aej_jpegdec_desc *descs, int n, int S, std::vector<JdFile> &files, JdBufSizes &z, const int *shifts = nullptr,
-                    const int *boxes = nullptr, const aej_jpeg_adobe *adobe = nullptr);
+// What the options of a decoder call resolve to (api_jpeg.hip: jd_resolve; {}: no options).  shifts: jpeg_recon_layout's shift of every
+// file -- log2 of its scale, + kJdLuma for one that leaves as its luma plane, + kJdSbox, + kJdCmyk -- or empty for all at full size,
+// RGB; boxes: NULL or [n][4], jpeg_recon_layout's box of every file; adobe: NULL or [n], its aej_jpeg_adobe
+struct JdResolved { std::vector<int> shifts; const int *boxes = nullptr; const aej_jpeg_adobe *adobe = nullptr; };
+void jpegdec_layout(const aej_jpegdec_desc *descs, int n, int S, std::vector<JdFile> &files, JdBufSizes &z, const JdResolved &r);
 unsigned long long jpegdec_carve(void *base, int n, const JdBufSizes &z, JdBufs &w);
 hipError_t launch_jpegdec_begin(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, const void *blob_host, unsigned long long blob_bytes,
                                 const unsigned char *scans, int S, int *status);
@@ -428,8 +429,7 @@ inline void jp_scan_units(const aej_jpegprog_frame &f, int ncomp, int comp0, int
 }
 int jpegprog_parse(const unsigned char *data, unsigned long long n, aej_jpegprog_frame &f, std::vector<aej_jpegprog_scan> &scans,
                    std::string &msg, bool allow440 = false, aej_jpeg_adobe *adobe = nullptr);                          // jpegparse.hip
-bool jpegprog_layout(const aej_jpegprog_frame *frames, const aej_jpegprog_scan *scans, int n, JpLayout &y, const int *shifts = nullptr,
-                     const int *boxes = nullptr, const aej_jpeg_adobe *adobe = nullptr);
+bool jpegprog_layout(const aej_jpegprog_frame *frames, const aej_jpegprog_scan *scans, int n, JpLayout &y, const JdResolved &r);
 unsigned long long jpegprog_blob(const JpLayout &y, std::vector<unsigned char> *out);
 unsigned long long jpegprog_carve(void *base, const JpLayout &y, JpBufs &w);
 hipError_t launch_jpegprog_entropy(hipStream_t st, const JpLayout &y, const JpBufs &w, const void *blob_host, unsigned long long blob_bytes,

@@ -198,7 +198,7 @@ extern "C" int aej_test_jfif_prog_scan(aej_ctx *ctx, const int16_t *coefs_host, 
 
 // ---- baseline JPEG files decoded on the device (jpegdec.hip; the marker walk: jpegparse.hip) --------------------------------------------------------------------------
 static int jd_parse_host(const uint8_t *data_host, uint64_t nbytes, aej_jpegdec_desc *desc_host, char *msg, int msg_capacity, int layout_440,
-                         aej_jpeg_adobe *adobe_host = nullptr)
+                         aej_jpeg_adobe *adobe_host)
 {
     if (!desc_host || (layout_440 != 0 && layout_440 != 1)) return AEJ_ERR_ARG;
     std::string m;
@@ -209,13 +209,13 @@ static int jd_parse_host(const uint8_t *data_host, uint64_t nbytes, aej_jpegdec_
 
 extern "C" int aej_jpegdec_parse_host(const uint8_t *data_host, uint64_t nbytes, aej_jpegdec_desc *desc_host, char *msg, int msg_capacity)
 {
-    return jd_parse_host(data_host, nbytes, desc_host, msg, msg_capacity, 0);
+    return jd_parse_host(data_host, nbytes, desc_host, msg, msg_capacity, 0, nullptr);
 }
 
 extern "C" int aej_jpegdec_parse_host_440(const uint8_t *data_host, uint64_t nbytes, aej_jpegdec_desc *desc_host, char *msg, int msg_capacity,
                                           int layout_440)
 {
-    return jd_parse_host(data_host, nbytes, desc_host, msg, msg_capacity, layout_440);
+    return jd_parse_host(data_host, nbytes, desc_host, msg, msg_capacity, layout_440, nullptr);
 }
 
 extern "C" int aej_jpegdec_parse_host_adobe(const uint8_t *data_host, uint64_t nbytes, aej_jpegdec_desc *desc_host, aej_jpeg_adobe *adobe_host,
@@ -256,118 +256,68 @@ static int image_offset(aej_ctx *ctx, const char *fn, int i, uint64_t out_bytes,
     return 0;
 }
 
-// the scales of a scaled call (NULL: every file at full size) -> log2 of each; a value that is not 1, 2, 4 or 8 is the caller's error
-// components_host (the _mode entries; NULL: every file as RGB): 3, or 1 for a file that leaves as its luma plane (kJdLuma added to its
-// shift); anything else is the caller's error too (*bad_comp says which of the two it was)
-static bool scale_shifts(const int *scales_host, int n, std::vector<int> &shifts, int *bad = nullptr, const int *components_host = nullptr,
-                         bool *bad_comp = nullptr)
+// ---- the options of a decoder call: one set, resolved by one routine for the size query and the call alike ------------------------------
+// scales (NULL: every file at full size): 1, 2, 4 or 8 per file.  components (NULL: every file as RGB): 3, 1 for a file that leaves as
+// its luma plane, or -- with adobe alone -- 4 for a four-component file that leaves as Pillow's mode "CMYK" image.  boxes (NULL: none):
+// [n][4] left, top, right, bottom, in pixels of the full-size image, where only the whole image is taken at scale 2, 4 or 8, or (sbox) in
+// pixels of the file's image at its scale, ceil(width / s) x ceil(height / s).  adobe (NULL: none): what the _adobe parsers wrote.
+struct JdOptions { const int *scales, *components; const int32_t *boxes; const aej_jpeg_adobe *adobe; bool sbox; };
+enum { kJdrOk, kJdrNoFrames, kJdrFour, kJdrComponents, kJdrScale, kJdrBox, kJdrBoxScaled, kJdrAdobeLuma, kJdrAdobeScale, kJdrAdobeBox };
+struct JdRefusal { int kind = kJdrOk, file = 0, v[6] = {}; };      // v: the offending value, or the box and the size of its image
+
+// -> what jpegdec_layout / jpegprog_layout take, or the first thing refused, in the order the entries always reported them.  The frames are
+// read only for boxes and adobe (aej_jpegprog_*: they are checked only later, by jpegprog_layout).  D: aej_jpegdec_desc or aej_jpegprog_frame
+template <class D>
+static JdRefusal jd_resolve(const D *frames, int n, const JdOptions &o, JdResolved &r)
 {
+    std::vector<int> &shifts = r.shifts;
+    const bool no_frames = !frames || n < 1;
+    r.boxes = o.boxes; r.adobe = o.adobe;
     shifts.assign(n > 0 ? n : 0, 0);
-    for (int i = 0; scales_host && i < n; i++)
-        if ((shifts[i] = jpeg_scale_shift(scales_host[i])) < 0) { if (bad) *bad = i; return false; }
-    for (int i = 0; components_host && i < n; i++) {
-        if (components_host[i] == 1) shifts[i] |= kJdLuma;
-        else if (components_host[i] != 3) { if (bad) *bad = i; if (bad_comp) *bad_comp = true; return false; }
+    if (o.adobe && no_frames) return { kJdrNoFrames };
+    for (int i = 0; o.adobe && o.components && i < n; i++)
+        if (o.components[i] == 4 && (frames[i].ncomp != 4 || !jpeg_adobe_new(o.adobe + i))) return { kJdrFour, i };
+    for (int i = 0; o.scales && i < n; i++)
+        if ((shifts[i] = jpeg_scale_shift(o.scales[i])) < 0) return { kJdrScale, i, { o.scales[i] } };
+    for (int i = 0; o.components && i < n; i++) {
+        if (o.components[i] == 1) shifts[i] |= kJdLuma;
+        else if (o.components[i] != 3 && !(o.components[i] == 4 && o.adobe)) return { kJdrComponents, i, { o.components[i] } };
     }
-    return true;
-}
-static int check_scales(aej_ctx *ctx, const char *fn, const int *scales_host, int n, std::vector<int> &shifts, const int *components_host = nullptr)
-{
-    int bad = 0;
-    bool bad_comp = false;
-    if (scale_shifts(scales_host, n, shifts, &bad, components_host, &bad_comp)) return 0;
-    if (bad_comp) return fail(ctx, AEJ_ERR_ARG, "%s: file %d: %d output components (3: RGB, 1: luma)", fn, bad, components_host[bad]);
-    return fail(ctx, AEJ_ERR_ARG, "%s: file %d: scale %d (1, 2, 4 or 8)", fn, bad, scales_host[bad]);
+    if (o.boxes && no_frames) return { kJdrNoFrames };
+    for (int i = 0; o.boxes && i < n; i++) {
+        const int32_t *b = o.boxes + 4 * i;
+        const int sh = shifts[i] & (kJdLuma - 1), s = o.sbox ? sh : 0, ow = (frames[i].width + (1 << s) - 1) >> s, oh = (frames[i].height + (1 << s) - 1) >> s;
+        if (!(0 <= b[0] && b[0] < b[2] && b[2] <= ow && 0 <= b[1] && b[1] < b[3] && b[3] <= oh)) return { kJdrBox, i, { b[0], b[1], b[2], b[3], ow, oh } };
+        if (!sh || (b[0] == 0 && b[1] == 0 && b[2] == ow && b[3] == oh)) continue;      // at scale 1 the two kinds of box coincide, and the whole image is no box
+        if (!o.sbox) return { kJdrBoxScaled, i };
+        shifts[i] |= kJdSbox;                                // k_jd_sbox (jpeg_recon_layout)
+    }
+    for (int i = 0; o.adobe && i < n; i++) {                 // a four-component or RGB-coded file: full size, whole, in colour
+        if (!jpeg_adobe_new(o.adobe + i)) continue;
+        if (shifts[i] & kJdLuma) return { kJdrAdobeLuma, i };
+        if (shifts[i] & (kJdLuma - 1)) return { kJdrAdobeScale, i };
+        if (o.boxes && !jpeg_box_whole(frames[i], o.boxes + 4 * i)) return { kJdrAdobeBox, i };
+        if (o.components && o.components[i] == 4) shifts[i] |= kJdCmyk;
+    }
+    return {};
 }
 
-// the boxes of a _box call ([n][4] left, top, right, bottom; NULL: none): every one inside its image (*unsupported false), and none but the
-// whole image on a file that is not decoded at full size (*unsupported true); *bad: the file.  D: aej_jpegdec_desc or aej_jpegprog_frame
-// sbox (the _sbox entries): a box is in pixels of the file's image at its scale, ceil(width / s) x ceil(height / s), and only has to lie in that
-template <class D>
-static bool boxes_ok(const D *frames, int n, const int32_t *boxes_host, const std::vector<int> &shifts, int *bad, bool *unsupported, bool sbox = false)
+// a refusal in the entry's words (0: none).  The size queries do not come here: they answer 0 and leave the context's last error alone
+static int jd_refuse(aej_ctx *ctx, const char *fn, const JdRefusal &r)
 {
-    for (int i = 0; boxes_host && i < n; i++) {
-        const int32_t *b = boxes_host + 4 * i;
-        *bad = i;
-        *unsupported = false;
-        if (sbox) {
-            const int sh = shifts[i] & (kJdLuma - 1), ow = (frames[i].width + (1 << sh) - 1) >> sh, oh = (frames[i].height + (1 << sh) - 1) >> sh;
-            if (!(0 <= b[0] && b[0] < b[2] && b[2] <= ow && 0 <= b[1] && b[1] < b[3] && b[3] <= oh)) return false;
-            continue;
-        }
-        if (!jpeg_box_inside(frames[i], b)) return false;
-        *unsupported = true;
-        if (!jpeg_box_whole(frames[i], b) && (shifts[i] & (kJdLuma - 1))) return false;
+    const int i = r.file, *v = r.v;
+    switch (r.kind) {
+    case kJdrOk: return 0;
+    case kJdrNoFrames: return fail(ctx, AEJ_ERR_ARG, "%s: no files, or descriptors aej_jpegprog_parse_host did not write", fn);
+    case kJdrFour: return fail(ctx, AEJ_ERR_ARG, "%s: file %d: 4 output components for a file that does not have four", fn, i);
+    case kJdrComponents: return fail(ctx, AEJ_ERR_ARG, "%s: file %d: %d output components (3: RGB, 1: luma)", fn, i, v[0]);
+    case kJdrScale: return fail(ctx, AEJ_ERR_ARG, "%s: file %d: scale %d (1, 2, 4 or 8)", fn, i, v[0]);
+    case kJdrBox:
+        return fail(ctx, AEJ_ERR_ARG, "%s: file %d: box (%d, %d, %d, %d) is empty or leaves the %d x %d image", fn, i, v[0], v[1], v[2], v[3], v[4], v[5]);
+    case kJdrBoxScaled: return fail(ctx, AEJ_ERR_UNSUPPORTED, "%s: file %d: a box at scale 2, 4 or 8 is not built", fn, i);
     }
-    return true;
-}
-template <class D>
-static int check_boxes(aej_ctx *ctx, const char *fn, const D *frames, int n, const int32_t *boxes_host, const std::vector<int> &shifts, bool sbox = false)
-{
-    int bad = 0;
-    bool unsupported = false;
-    if (boxes_ok(frames, n, boxes_host, shifts, &bad, &unsupported, sbox)) return 0;
-    const int32_t *b = boxes_host + 4 * bad;
-    if (unsupported) return fail(ctx, AEJ_ERR_UNSUPPORTED, "%s: file %d: a box at scale 2, 4 or 8 is not built", fn, bad);
-    const int sh = sbox ? shifts[bad] & (kJdLuma - 1) : 0;
-    return fail(ctx, AEJ_ERR_ARG, "%s: file %d: box (%d, %d, %d, %d) is empty or leaves the %d x %d image", fn, bad, b[0], b[1], b[2], b[3],
-                (frames[bad].width + (1 << sh) - 1) >> sh, (frames[bad].height + (1 << sh) - 1) >> sh);
-}
-// after boxes_ok of an _sbox call: kJdSbox on the files at scale 2, 4, 8 whose box is not their whole scaled image (jpeg_recon_layout); the
-// others are the _box call's -- at scale 1 the box is in full-size pixels, and the whole scaled image is no box
-template <class D>
-static void sbox_shifts(const D *frames, int n, const int32_t *boxes_host, std::vector<int> &shifts)
-{
-    for (int i = 0; boxes_host && i < n; i++) {
-        const int32_t *b = boxes_host + 4 * i;
-        const int sh = shifts[i] & (kJdLuma - 1), ow = (frames[i].width + (1 << sh) - 1) >> sh, oh = (frames[i].height + (1 << sh) - 1) >> sh;
-        if (sh && !(b[0] == 0 && b[1] == 0 && b[2] == ow && b[3] == oh)) shifts[i] |= kJdSbox;
-    }
-}
-
-// The _adobe entries: components_host may say 4 (Pillow's mode "CMYK" image) for a four-component file.  comps3 gets the counts with 3 in
-// the place of every 4, for scale_shifts; after it adobe_shifts adds kJdCmyk to those files' shifts.  False (*bad: the file): a 4 on a file
-// that does not have four components.
-template <class D>
-static bool adobe_components(const D *frames, int n, const int *components_host, const aej_jpeg_adobe *adobe_host, std::vector<int> &comps3, int *bad)
-{
-    comps3.clear();
-    if (!components_host) return true;
-    comps3.assign(components_host, components_host + n);
-    for (int i = 0; i < n; i++)
-        if (components_host[i] == 4) {
-            *bad = i;
-            if (!frames || frames[i].ncomp != 4 || !adobe_host || !jpeg_adobe_new(adobe_host + i)) return false;
-            comps3[i] = 3;
-        }
-    return true;
-}
-static void adobe_shifts(int n, const int *components_host, std::vector<int> &shifts)
-{
-    for (int i = 0; components_host && i < n; i++) if (components_host[i] == 4) shifts[i] |= kJdCmyk;
-}
-// what is not built for a four-component or RGB-coded file: 0, or 1 luma, 2 a scale, 3 a box (*bad: the file)
-template <class D>
-static int adobe_unbuilt(const D *frames, int n, const aej_jpeg_adobe *adobe_host, const std::vector<int> &shifts, const int32_t *boxes_host, int *bad)
-{
-    for (int i = 0; adobe_host && i < n; i++) {
-        if (!jpeg_adobe_new(adobe_host + i)) continue;
-        *bad = i;
-        if (shifts[i] & kJdLuma) return 1;
-        if (shifts[i] & (kJdLuma - 1)) return 2;
-        if (boxes_host && !jpeg_box_whole(frames[i], boxes_host + 4 * i)) return 3;
-    }
-    return 0;
-}
-template <class D>
-static int check_adobe(aej_ctx *ctx, const char *fn, const D *frames, int n, const aej_jpeg_adobe *adobe_host, const std::vector<int> &shifts,
-                       const int32_t *boxes_host)
-{
-    int bad = 0;
-    const int what = adobe_unbuilt(frames, n, adobe_host, shifts, boxes_host, &bad);
-    if (!what) return 0;
-    return fail(ctx, AEJ_ERR_UNSUPPORTED, "%s: file %d: %s of a four-component / RGB-coded file is not built", fn, bad,
-                what == 1 ? "luma output" : what == 2 ? "a scale other than 1" : "a box");
+    return fail(ctx, AEJ_ERR_UNSUPPORTED, "%s: file %d: %s of a four-component / RGB-coded file is not built", fn, i,
+                r.kind == kJdrAdobeLuma ? "luma output" : r.kind == kJdrAdobeScale ? "a scale other than 1" : "a box");
 }
 
 // jd_box_window behind the two public entries
@@ -425,70 +375,55 @@ extern "C" int aej_jpegdec_box_stats(aej_ctx *ctx, int64_t *out3_host)
     return 0;
 }
 
-static uint64_t jpegdec_workspace(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host, const int *components_host = nullptr,
-                                  const int32_t *boxes_host = nullptr, const aej_jpeg_adobe *adobe_host = nullptr, bool sbox = false)
+static uint64_t jpegdec_workspace(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const JdOptions &o)
 {
-    std::vector<int> shifts, comps3;
-    int bad = 0;
-    bool unsupported = false;
-    if (!ctx || !jpegdec_descs_ok(descs_host, n, adobe_host)) return 0;
-    const int *components4 = components_host;         // with the 4s
-    if (adobe_host) {
-        if (!adobe_components(descs_host, n, components_host, adobe_host, comps3, &bad)) return 0;
-        if (components_host) components_host = comps3.data();
-    }
-    if (!scale_shifts(scales_host, n, shifts, nullptr, components_host)) return 0;
-    if (!boxes_ok(descs_host, n, boxes_host, shifts, &bad, &unsupported, sbox)) return 0;
-    if (sbox) sbox_shifts(descs_host, n, boxes_host, shifts);
-    if (adobe_host) {
-        if (adobe_unbuilt(descs_host, n, adobe_host, shifts, boxes_host, &bad)) return 0;
-        adobe_shifts(n, components4, shifts);
-    }
+    JdResolved r;
+    if (!ctx || !jpegdec_descs_ok(descs_host, n, o.adobe) || jd_resolve(descs_host, n, o, r).kind) return 0;
     std::vector<JdFile> files;
     JdBufSizes z;
-    jpegdec_layout(descs_host, n, ctx->jd_subseq_bits, files, z, shifts.data(), boxes_host, adobe_host);
+    jpegdec_layout(descs_host, n, ctx->jd_subseq_bits, files, z, r);
     JdBufs w;
     return jpegdec_carve(nullptr, n, z, w);
 }
 
 extern "C" uint64_t aej_jpegdec_workspace_bytes(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n)
 {
-    return jpegdec_workspace(ctx, descs_host, n, nullptr);
+    return jpegdec_workspace(ctx, descs_host, n, {});
 }
 
 extern "C" uint64_t aej_jpegdec_workspace_bytes_scaled(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host)
 {
-    return scales_host ? jpegdec_workspace(ctx, descs_host, n, scales_host) : 0;
+    return scales_host ? jpegdec_workspace(ctx, descs_host, n, { scales_host }) : 0;
 }
 
 extern "C" uint64_t aej_jpegdec_workspace_bytes_mode(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host,
                                                      const int *components_host)
 {
-    return jpegdec_workspace(ctx, descs_host, n, scales_host, components_host);
+    return jpegdec_workspace(ctx, descs_host, n, { scales_host, components_host });
 }
 
 extern "C" uint64_t aej_jpegdec_workspace_bytes_box(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host,
                                                     const int *components_host, const int32_t *boxes_host)
 {
-    return jpegdec_workspace(ctx, descs_host, n, scales_host, components_host, boxes_host);
+    return jpegdec_workspace(ctx, descs_host, n, { scales_host, components_host, boxes_host });
 }
 
 extern "C" uint64_t aej_jpegdec_workspace_bytes_sbox(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host,
                                                      const int *components_host, const int32_t *boxes_host)
 {
-    return jpegdec_workspace(ctx, descs_host, n, scales_host, components_host, boxes_host, nullptr, true);
+    return jpegdec_workspace(ctx, descs_host, n, { scales_host, components_host, boxes_host, nullptr, true });
 }
 
 extern "C" uint64_t aej_jpegdec_workspace_bytes_adobe(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host,
                                                       const int *components_host, const int32_t *boxes_host, const aej_jpeg_adobe *adobe_host)
 {
-    return jpegdec_workspace(ctx, descs_host, n, scales_host, components_host, boxes_host, adobe_host);
+    return jpegdec_workspace(ctx, descs_host, n, { scales_host, components_host, boxes_host, adobe_host });
 }
 
 // the entropy decode of n baseline files up to the fixed point of the sync rounds: everything of aej_jpegdec_batch before the
 // coefficient write (`files` carries the scan offsets; the caller has carved `w`)
 static int jpegdec_decode(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs_host, int n, const std::vector<JdFile> &files, const JdBufSizes &z,
-                          const JdBufs &w, const uint8_t *scans, int32_t *status, const aej_jpeg_adobe *adobe_host = nullptr)
+                          const JdBufs &w, const uint8_t *scans, int32_t *status, const aej_jpeg_adobe *adobe_host)
 {
     const int S = ctx->jd_subseq_bits;
     // one upload: files, descriptors, the "last round that changed" word (-1)
@@ -523,36 +458,21 @@ static int jpegdec_decode(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *
     return 0;
 }
 
-// aej_jpegdec_batch (scales_host NULL: every file at full size), aej_jpegdec_batch_scaled and aej_jpegdec_batch_mode (components_host)
-static int jpegdec_batch(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs_host, int n, const int *scales_host, const int *components_host,
-                         const uint8_t *scans,
+// every aej_jpegdec_batch* entry: descriptors, then null buffers, then the options, then offsets, then the workspace
+static int jpegdec_batch(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs_host, int n, const JdOptions &o, const uint8_t *scans,
                          uint64_t scans_bytes, const int64_t *scan_offsets_host, uint8_t *out, uint64_t out_bytes, const int64_t *out_offsets_host,
-                         int32_t *status, void *workspace, uint64_t workspace_bytes, const int32_t *boxes_host = nullptr,
-                         const aej_jpeg_adobe *adobe_host = nullptr, bool sbox = false)
+                         int32_t *status, void *workspace, uint64_t workspace_bytes)
 {
     AEJ_TRY(enter(ctx, fn));
-    if (!jpegdec_descs_ok(descs_host, n, adobe_host))
+    if (!jpegdec_descs_ok(descs_host, n, o.adobe))
         return fail(ctx, AEJ_ERR_ARG, "%s: no files, or a descriptor aej_jpegdec_parse_host did not write", fn);
     if (!scans || !scan_offsets_host || !out || !out_offsets_host || !status || !workspace) return null_buffer(ctx, fn);
-    std::vector<int> shifts, comps3;
-    const int *components4 = components_host;         // with the 4s of the _adobe entry
-    if (adobe_host) {
-        int bad = 0;
-        if (!adobe_components(descs_host, n, components_host, adobe_host, comps3, &bad))
-            return fail(ctx, AEJ_ERR_ARG, "%s: file %d: 4 output components for a file that does not have four", fn, bad);
-        if (components_host) components_host = comps3.data();
-    }
-    AEJ_TRY(check_scales(ctx, fn, scales_host, n, shifts, components_host));
-    AEJ_TRY(check_boxes(ctx, fn, descs_host, n, boxes_host, shifts, sbox));
-    if (sbox) sbox_shifts(descs_host, n, boxes_host, shifts);
-    if (adobe_host) {
-        AEJ_TRY(check_adobe(ctx, fn, descs_host, n, adobe_host, shifts, boxes_host));
-        adobe_shifts(n, components4, shifts);
-    }
+    JdResolved r;
+    AEJ_TRY(jd_refuse(ctx, fn, jd_resolve(descs_host, n, o, r)));
     const int S = ctx->jd_subseq_bits;
     std::vector<JdFile> files;
     JdBufSizes z;
-    jpegdec_layout(descs_host, n, S, files, z, shifts.data(), boxes_host, adobe_host);
+    jpegdec_layout(descs_host, n, S, files, z, r);
     if (z.grpb > 0 || z.grps[0] > 0 || z.grps[1] > 0 || z.grps[2] > 0) {      // aej_jpegdec_box_stats: from the descriptors and the windows alone
         long long total = 0, decoded = 0;
         for (int i = 0; i < n; i++) {
@@ -573,7 +493,7 @@ static int jpegdec_batch(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *d
     JdBufs w;
     const unsigned long long need = jpegdec_carve(workspace, n, z, w);
     AEJ_TRY(check_workspace(ctx, need, workspace_bytes));
-    AEJ_TRY(jpegdec_decode(ctx, fn, descs_host, n, files, z, w, scans, status, adobe_host));
+    AEJ_TRY(jpegdec_decode(ctx, fn, descs_host, n, files, z, w, scans, status, o.adobe));
     AEJ_HIP_CHECK(launch_jpegdec_finish(ctx->stream, n, z, w, S, out, status));
     return 0;
 }
@@ -582,8 +502,7 @@ extern "C" int aej_jpegdec_batch(aej_ctx *ctx, const aej_jpegdec_desc *descs_hos
                                  const int64_t *scan_offsets_host, uint8_t *out, uint64_t out_bytes, const int64_t *out_offsets_host,
                                  int32_t *status, void *workspace, uint64_t workspace_bytes)
 {
-    return jpegdec_batch(ctx, __func__, descs_host, n, nullptr, nullptr, scans, scans_bytes, scan_offsets_host, out, out_bytes, out_offsets_host, status,
-                         workspace, workspace_bytes);
+    return jpegdec_batch(ctx, __func__, descs_host, n, {}, scans, scans_bytes, scan_offsets_host, out, out_bytes, out_offsets_host, status, workspace, workspace_bytes);
 }
 
 extern "C" int aej_jpegdec_batch_scaled(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host, const uint8_t *scans,
@@ -591,16 +510,14 @@ extern "C" int aej_jpegdec_batch_scaled(aej_ctx *ctx, const aej_jpegdec_desc *de
                                         const int64_t *out_offsets_host, int32_t *status, void *workspace, uint64_t workspace_bytes)
 {
     if (!scales_host) return ctx ? null_buffer(ctx, __func__) : AEJ_ERR_ARG;
-    return jpegdec_batch(ctx, __func__, descs_host, n, scales_host, nullptr, scans, scans_bytes, scan_offsets_host, out, out_bytes, out_offsets_host,
-                         status, workspace, workspace_bytes);
+    return jpegdec_batch(ctx, __func__, descs_host, n, { scales_host }, scans, scans_bytes, scan_offsets_host, out, out_bytes, out_offsets_host, status, workspace, workspace_bytes);
 }
 
 extern "C" int aej_jpegdec_batch_mode(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host, const int *components_host,
                                       const uint8_t *scans, uint64_t scans_bytes, const int64_t *scan_offsets_host, uint8_t *out, uint64_t out_bytes,
                                       const int64_t *out_offsets_host, int32_t *status, void *workspace, uint64_t workspace_bytes)
 {
-    return jpegdec_batch(ctx, __func__, descs_host, n, scales_host, components_host, scans, scans_bytes, scan_offsets_host, out, out_bytes,
-                         out_offsets_host, status, workspace, workspace_bytes);
+    return jpegdec_batch(ctx, __func__, descs_host, n, { scales_host, components_host }, scans, scans_bytes, scan_offsets_host, out, out_bytes, out_offsets_host, status, workspace, workspace_bytes);
 }
 
 extern "C" int aej_jpegdec_batch_box(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host, const int *components_host,
@@ -608,8 +525,8 @@ extern "C" int aej_jpegdec_batch_box(aej_ctx *ctx, const aej_jpegdec_desc *descs
                                      uint8_t *out, uint64_t out_bytes, const int64_t *out_offsets_host, int32_t *status, void *workspace,
                                      uint64_t workspace_bytes)
 {
-    return jpegdec_batch(ctx, __func__, descs_host, n, scales_host, components_host, scans, scans_bytes, scan_offsets_host, out, out_bytes,
-                         out_offsets_host, status, workspace, workspace_bytes, boxes_host);
+    return jpegdec_batch(ctx, __func__, descs_host, n, { scales_host, components_host, boxes_host },
+                         scans, scans_bytes, scan_offsets_host, out, out_bytes, out_offsets_host, status, workspace, workspace_bytes);
 }
 
 extern "C" int aej_jpegdec_batch_sbox(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host, const int *components_host,
@@ -617,8 +534,8 @@ extern "C" int aej_jpegdec_batch_sbox(aej_ctx *ctx, const aej_jpegdec_desc *desc
                                       uint8_t *out, uint64_t out_bytes, const int64_t *out_offsets_host, int32_t *status, void *workspace,
                                       uint64_t workspace_bytes)
 {
-    return jpegdec_batch(ctx, __func__, descs_host, n, scales_host, components_host, scans, scans_bytes, scan_offsets_host, out, out_bytes,
-                         out_offsets_host, status, workspace, workspace_bytes, boxes_host, nullptr, true);
+    return jpegdec_batch(ctx, __func__, descs_host, n, { scales_host, components_host, boxes_host, nullptr, true },
+                         scans, scans_bytes, scan_offsets_host, out, out_bytes, out_offsets_host, status, workspace, workspace_bytes);
 }
 
 extern "C" int aej_jpegdec_batch_adobe(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n, const int *scales_host, const int *components_host,
@@ -626,8 +543,8 @@ extern "C" int aej_jpegdec_batch_adobe(aej_ctx *ctx, const aej_jpegdec_desc *des
                                        const int64_t *scan_offsets_host, uint8_t *out, uint64_t out_bytes, const int64_t *out_offsets_host,
                                        int32_t *status, void *workspace, uint64_t workspace_bytes)
 {
-    return jpegdec_batch(ctx, __func__, descs_host, n, scales_host, components_host, scans, scans_bytes, scan_offsets_host, out, out_bytes,
-                         out_offsets_host, status, workspace, workspace_bytes, boxes_host, adobe_host);
+    return jpegdec_batch(ctx, __func__, descs_host, n, { scales_host, components_host, boxes_host, adobe_host },
+                         scans, scans_bytes, scan_offsets_host, out, out_bytes, out_offsets_host, status, workspace, workspace_bytes);
 }
 
 // the host twins of the per-pixel colour rules of k_jd_adobe (jpegdec_core.h), for the tests: n pixels of four samples -> n pixels of
@@ -665,7 +582,7 @@ extern "C" int64_t aej_jpegdec_sync_rounds(aej_ctx *ctx)
 
 // ---- progressive JPEG files decoded on the device (jpegprog.hip) ----------------------------------------------------------------------
 static int jp_parse_host(const uint8_t *data_host, uint64_t nbytes, aej_jpegprog_frame *frame_host, aej_jpegprog_scan *scans_host, int scan_capacity,
-                         char *msg, int msg_capacity, int layout_440, aej_jpeg_adobe *adobe_host = nullptr)
+                         char *msg, int msg_capacity, int layout_440, aej_jpeg_adobe *adobe_host)
 {
     if (!frame_host || (layout_440 != 0 && layout_440 != 1)) return AEJ_ERR_ARG;
     std::string m;
@@ -682,13 +599,13 @@ static int jp_parse_host(const uint8_t *data_host, uint64_t nbytes, aej_jpegprog
 extern "C" int aej_jpegprog_parse_host(const uint8_t *data_host, uint64_t nbytes, aej_jpegprog_frame *frame_host, aej_jpegprog_scan *scans_host,
                                        int scan_capacity, char *msg, int msg_capacity)
 {
-    return jp_parse_host(data_host, nbytes, frame_host, scans_host, scan_capacity, msg, msg_capacity, 0);
+    return jp_parse_host(data_host, nbytes, frame_host, scans_host, scan_capacity, msg, msg_capacity, 0, nullptr);
 }
 
 extern "C" int aej_jpegprog_parse_host_440(const uint8_t *data_host, uint64_t nbytes, aej_jpegprog_frame *frame_host, aej_jpegprog_scan *scans_host,
                                            int scan_capacity, char *msg, int msg_capacity, int layout_440)
 {
-    return jp_parse_host(data_host, nbytes, frame_host, scans_host, scan_capacity, msg, msg_capacity, layout_440);
+    return jp_parse_host(data_host, nbytes, frame_host, scans_host, scan_capacity, msg, msg_capacity, layout_440, nullptr);
 }
 
 extern "C" int aej_jpegprog_parse_host_adobe(const uint8_t *data_host, uint64_t nbytes, aej_jpegprog_frame *frame_host, aej_jpegprog_scan *scans_host,
@@ -698,97 +615,64 @@ extern "C" int aej_jpegprog_parse_host_adobe(const uint8_t *data_host, uint64_t 
     return jp_parse_host(data_host, nbytes, frame_host, scans_host, scan_capacity, msg, msg_capacity, layout_440, adobe_host);
 }
 
-static uint64_t jpegprog_workspace(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n, const int *scales_host,
-                                   const int *components_host = nullptr, const int32_t *boxes_host = nullptr, const aej_jpeg_adobe *adobe_host = nullptr,
-                                   bool sbox = false)
+static uint64_t jpegprog_workspace(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n, const JdOptions &o)
 {
     JpLayout y;
-    std::vector<int> shifts, comps3;
-    int bad = 0;
-    bool unsupported = false;
-    const int *components4 = components_host;         // with the 4s
-    if (adobe_host) {
-        if (!frames_host || n < 1 || !adobe_components(frames_host, n, components_host, adobe_host, comps3, &bad)) return 0;
-        if (components_host) components_host = comps3.data();
-    }
-    if (!ctx || !scale_shifts(scales_host, n, shifts, nullptr, components_host)) return 0;
-    if (boxes_host && (!frames_host || !boxes_ok(frames_host, n, boxes_host, shifts, &bad, &unsupported, sbox))) return 0;
-    if (sbox && boxes_host) sbox_shifts(frames_host, n, boxes_host, shifts);
-    if (adobe_host) {
-        if (adobe_unbuilt(frames_host, n, adobe_host, shifts, boxes_host, &bad)) return 0;
-        adobe_shifts(n, components4, shifts);
-    }
-    if (!jpegprog_layout(frames_host, scans_host, n, y, shifts.data(), boxes_host, adobe_host)) return 0;
+    JdResolved r;
+    if (!ctx || jd_resolve(frames_host, n, o, r).kind || !jpegprog_layout(frames_host, scans_host, n, y, r)) return 0;
     JpBufs w;
     return jpegprog_carve(nullptr, y, w);
 }
 
 extern "C" uint64_t aej_jpegprog_workspace_bytes(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n)
 {
-    return jpegprog_workspace(ctx, frames_host, scans_host, n, nullptr);
+    return jpegprog_workspace(ctx, frames_host, scans_host, n, {});
 }
 
 extern "C" uint64_t aej_jpegprog_workspace_bytes_scaled(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
                                                         const int *scales_host)
 {
-    return scales_host ? jpegprog_workspace(ctx, frames_host, scans_host, n, scales_host) : 0;
+    return scales_host ? jpegprog_workspace(ctx, frames_host, scans_host, n, { scales_host }) : 0;
 }
 
 extern "C" uint64_t aej_jpegprog_workspace_bytes_mode(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
                                                       const int *scales_host, const int *components_host)
 {
-    return jpegprog_workspace(ctx, frames_host, scans_host, n, scales_host, components_host);
+    return jpegprog_workspace(ctx, frames_host, scans_host, n, { scales_host, components_host });
 }
 
 extern "C" uint64_t aej_jpegprog_workspace_bytes_box(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
                                                      const int *scales_host, const int *components_host, const int32_t *boxes_host)
 {
-    return jpegprog_workspace(ctx, frames_host, scans_host, n, scales_host, components_host, boxes_host);
+    return jpegprog_workspace(ctx, frames_host, scans_host, n, { scales_host, components_host, boxes_host });
 }
 
 extern "C" uint64_t aej_jpegprog_workspace_bytes_sbox(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
                                                       const int *scales_host, const int *components_host, const int32_t *boxes_host)
 {
-    return jpegprog_workspace(ctx, frames_host, scans_host, n, scales_host, components_host, boxes_host, nullptr, true);
+    return jpegprog_workspace(ctx, frames_host, scans_host, n, { scales_host, components_host, boxes_host, nullptr, true });
 }
 
 extern "C" uint64_t aej_jpegprog_workspace_bytes_adobe(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
                                                        const int *scales_host, const int *components_host, const int32_t *boxes_host,
                                                        const aej_jpeg_adobe *adobe_host)
 {
-    return jpegprog_workspace(ctx, frames_host, scans_host, n, scales_host, components_host, boxes_host, adobe_host);
+    return jpegprog_workspace(ctx, frames_host, scans_host, n, { scales_host, components_host, boxes_host, adobe_host });
 }
 
-// levels [0, n_levels) of the entropy stage, then either the reconstruction into `out` or (tests) a copy of the coefficients
+// levels [0, n_levels) of the entropy stage, then either the reconstruction into `out` or (tests) a copy of the coefficients.  The
+// options first, then the descriptors (jpegprog_layout), then null buffers, then offsets, then the workspace
 static int jpegprog_run(aej_ctx *ctx, const char *fn, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
-                        const int *scales_host, const uint8_t *data, uint64_t data_bytes, const int64_t *data_offsets_host, int n_levels, uint8_t *out, uint64_t out_bytes,
-                        const int64_t *out_offsets_host, int16_t *coef_out, uint64_t coef_blocks, int32_t *status, void *workspace,
-                        uint64_t workspace_bytes, const int *components_host = nullptr, const int32_t *boxes_host = nullptr,
-                        const aej_jpeg_adobe *adobe_host = nullptr, bool sbox = false)
+                        const JdOptions &o, const uint8_t *data, uint64_t data_bytes, const int64_t *data_offsets_host, int n_levels, uint8_t *out,
+                        uint64_t out_bytes, const int64_t *out_offsets_host, int16_t *coef_out, uint64_t coef_blocks, int32_t *status, void *workspace,
+                        uint64_t workspace_bytes)
 {
     if (!ctx) return AEJ_ERR_ARG;
     AEJ_TRY(refuse_in_flight(ctx, fn));
     JpLayout y;
-    std::vector<int> shifts, comps3;
-    const int *components4 = components_host;         // with the 4s of the _adobe entry
-    if (adobe_host) {
-        int bad = 0;
-        if (!frames_host || n < 1) return fail(ctx, AEJ_ERR_ARG, "%s: no files, or descriptors aej_jpegprog_parse_host did not write", fn);
-        if (!adobe_components(frames_host, n, components_host, adobe_host, comps3, &bad))
-            return fail(ctx, AEJ_ERR_ARG, "%s: file %d: 4 output components for a file that does not have four", fn, bad);
-        if (components_host) components_host = comps3.data();
-    }
-    AEJ_TRY(check_scales(ctx, fn, scales_host, n, shifts, components_host));
-    if (boxes_host) {                                        // the frames' sizes are read: the checks jpegprog_layout starts with, first
-        if (!frames_host || n < 1) return fail(ctx, AEJ_ERR_ARG, "%s: no files, or descriptors aej_jpegprog_parse_host did not write", fn);
-        AEJ_TRY(check_boxes(ctx, fn, frames_host, n, boxes_host, shifts, sbox));
-        if (sbox) sbox_shifts(frames_host, n, boxes_host, shifts);
-    }
-    if (adobe_host) {
-        AEJ_TRY(check_adobe(ctx, fn, frames_host, n, adobe_host, shifts, boxes_host));
-        adobe_shifts(n, components4, shifts);
-    }
-    if (!jpegprog_layout(frames_host, scans_host, n, y, shifts.data(), boxes_host, adobe_host))
+    JdResolved r;
+    AEJ_TRY(jd_refuse(ctx, fn, jd_resolve(frames_host, n, o, r)));
+    if (!jpegprog_layout(frames_host, scans_host, n, y, r))
         return fail(ctx, AEJ_ERR_ARG, "%s: no files, or descriptors aej_jpegprog_parse_host did not write", fn);
     if (!data || !data_offsets_host || !status || !workspace || (!out && !coef_out) || (out && !out_offsets_host))
         return null_buffer(ctx, fn);
@@ -814,7 +698,7 @@ extern "C" int aej_jpegprog_batch(aej_ctx *ctx, const aej_jpegprog_frame *frames
                                   const int64_t *out_offsets_host, int32_t *status, void *workspace, uint64_t workspace_bytes)
 {
     if (!out) return ctx ? null_buffer(ctx, __func__) : AEJ_ERR_ARG;
-    return jpegprog_run(ctx, __func__, frames_host, scans_host, n, nullptr, data, data_bytes, data_offsets_host, 1 << 30, out, out_bytes,
+    return jpegprog_run(ctx, __func__, frames_host, scans_host, n, {}, data, data_bytes, data_offsets_host, 1 << 30, out, out_bytes,
                         out_offsets_host, nullptr, 0, status, workspace, workspace_bytes);
 }
 
@@ -824,7 +708,7 @@ extern "C" int aej_jpegprog_batch_scaled(aej_ctx *ctx, const aej_jpegprog_frame 
                                          uint64_t workspace_bytes)
 {
     if (!out || !scales_host) return ctx ? null_buffer(ctx, __func__) : AEJ_ERR_ARG;
-    return jpegprog_run(ctx, __func__, frames_host, scans_host, n, scales_host, data, data_bytes, data_offsets_host, 1 << 30, out, out_bytes,
+    return jpegprog_run(ctx, __func__, frames_host, scans_host, n, { scales_host }, data, data_bytes, data_offsets_host, 1 << 30, out, out_bytes,
                         out_offsets_host, nullptr, 0, status, workspace, workspace_bytes);
 }
 
@@ -834,8 +718,8 @@ extern "C" int aej_jpegprog_batch_mode(aej_ctx *ctx, const aej_jpegprog_frame *f
                                        int32_t *status, void *workspace, uint64_t workspace_bytes)
 {
     if (!out) return ctx ? null_buffer(ctx, __func__) : AEJ_ERR_ARG;
-    return jpegprog_run(ctx, __func__, frames_host, scans_host, n, scales_host, data, data_bytes, data_offsets_host, 1 << 30, out, out_bytes,
-                        out_offsets_host, nullptr, 0, status, workspace, workspace_bytes, components_host);
+    return jpegprog_run(ctx, __func__, frames_host, scans_host, n, { scales_host, components_host }, data, data_bytes, data_offsets_host, 1 << 30, out, out_bytes,
+                        out_offsets_host, nullptr, 0, status, workspace, workspace_bytes);
 }
 
 extern "C" int aej_jpegprog_batch_box(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
@@ -844,8 +728,8 @@ extern "C" int aej_jpegprog_batch_box(aej_ctx *ctx, const aej_jpegprog_frame *fr
                                       const int64_t *out_offsets_host, int32_t *status, void *workspace, uint64_t workspace_bytes)
 {
     if (!out) return ctx ? null_buffer(ctx, __func__) : AEJ_ERR_ARG;
-    return jpegprog_run(ctx, __func__, frames_host, scans_host, n, scales_host, data, data_bytes, data_offsets_host, 1 << 30, out, out_bytes,
-                        out_offsets_host, nullptr, 0, status, workspace, workspace_bytes, components_host, boxes_host);
+    return jpegprog_run(ctx, __func__, frames_host, scans_host, n, { scales_host, components_host, boxes_host }, data, data_bytes, data_offsets_host, 1 << 30, out, out_bytes,
+                        out_offsets_host, nullptr, 0, status, workspace, workspace_bytes);
 }
 
 extern "C" int aej_jpegprog_batch_sbox(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
@@ -854,8 +738,8 @@ extern "C" int aej_jpegprog_batch_sbox(aej_ctx *ctx, const aej_jpegprog_frame *f
                                        const int64_t *out_offsets_host, int32_t *status, void *workspace, uint64_t workspace_bytes)
 {
     if (!out) return ctx ? null_buffer(ctx, __func__) : AEJ_ERR_ARG;
-    return jpegprog_run(ctx, __func__, frames_host, scans_host, n, scales_host, data, data_bytes, data_offsets_host, 1 << 30, out, out_bytes,
-                        out_offsets_host, nullptr, 0, status, workspace, workspace_bytes, components_host, boxes_host, nullptr, true);
+    return jpegprog_run(ctx, __func__, frames_host, scans_host, n, { scales_host, components_host, boxes_host, nullptr, true }, data, data_bytes, data_offsets_host, 1 << 30, out, out_bytes,
+                        out_offsets_host, nullptr, 0, status, workspace, workspace_bytes);
 }
 
 extern "C" int aej_jpegprog_batch_adobe(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
@@ -865,8 +749,8 @@ extern "C" int aej_jpegprog_batch_adobe(aej_ctx *ctx, const aej_jpegprog_frame *
                                         uint64_t workspace_bytes)
 {
     if (!out) return ctx ? null_buffer(ctx, __func__) : AEJ_ERR_ARG;
-    return jpegprog_run(ctx, __func__, frames_host, scans_host, n, scales_host, data, data_bytes, data_offsets_host, 1 << 30, out, out_bytes,
-                        out_offsets_host, nullptr, 0, status, workspace, workspace_bytes, components_host, boxes_host, adobe_host);
+    return jpegprog_run(ctx, __func__, frames_host, scans_host, n, { scales_host, components_host, boxes_host, adobe_host }, data, data_bytes, data_offsets_host, 1 << 30, out, out_bytes,
+                        out_offsets_host, nullptr, 0, status, workspace, workspace_bytes);
 }
 
 extern "C" int aej_test_jpegprog_coefs(aej_ctx *ctx, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *scans_host, int n,
@@ -874,7 +758,7 @@ extern "C" int aej_test_jpegprog_coefs(aej_ctx *ctx, const aej_jpegprog_frame *f
                                        int16_t *coef_out, uint64_t coef_blocks, int32_t *status, void *workspace, uint64_t workspace_bytes)
 {
     if (!coef_out) return ctx ? null_buffer(ctx, __func__) : AEJ_ERR_ARG;
-    return jpegprog_run(ctx, __func__, frames_host, scans_host, n, nullptr, data, data_bytes, data_offsets_host, n_levels, nullptr, 0, nullptr, coef_out,
+    return jpegprog_run(ctx, __func__, frames_host, scans_host, n, {}, data, data_bytes, data_offsets_host, n_levels, nullptr, 0, nullptr, coef_out,
                         coef_blocks, status, workspace, workspace_bytes);
 }
 
@@ -906,44 +790,48 @@ struct JtCall {
 };
 static bool rst_ok(int blocks, int rows) { return blocks >= 0 && blocks <= kJrMaxInterval && rows >= 0 && rows <= kJrMaxInterval; }
 
+// The options of a transcode / transform call, as the entries state them ({}: the plain transcode).  xf: one transform code per file
+// (NULL: kJxNone for every file; need_xf: the entry refuses that).  boxes: NULL, or jx_geom's crop box of every file (right == 0: none).
+// The one-file host routines take the same set: xf and boxes point at that file's code and box.
+struct JtOptions { const int32_t *xf; int trim, rst_blocks, rst_rows, allow440; const int32_t *boxes; int drop; bool need_xf; };
+
 static int jt_layout(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs, int n_base, const aej_jpegprog_frame *frames,
-                     const aej_jpegprog_scan *pscans, int n_prog, const uint16_t *density, int progressive, const int32_t *xf, int trim, int rst_blocks,
-                     int rst_rows, JtCall &c, int allow440 = 0, const int32_t *boxes = nullptr, int drop = 0)
+                     const aej_jpegprog_scan *pscans, int n_prog, const uint16_t *density, int progressive, const JtOptions &o, JtCall &c)
 {
-    if (allow440 != 0 && allow440 != 1) return fail(ctx, AEJ_ERR_ARG, "%s: layout_440 %d (0 or 1)", fn, allow440);
-    if (drop != 0 && drop != 1) return fail(ctx, AEJ_ERR_ARG, "%s: drop_chroma %d (0 or 1)", fn, drop);
-    if (trim != 0 && trim != 1) return fail(ctx, AEJ_ERR_ARG, "%s: trim %d (0 or 1)", fn, trim);
-    if (!rst_ok(rst_blocks, rst_rows)) return fail(ctx, AEJ_ERR_ARG, "%s: restart_blocks %d, restart_rows %d (0 .. 65535)", fn, rst_blocks, rst_rows);
+    if (o.allow440 != 0 && o.allow440 != 1) return fail(ctx, AEJ_ERR_ARG, "%s: layout_440 %d (0 or 1)", fn, o.allow440);
+    if (o.drop != 0 && o.drop != 1) return fail(ctx, AEJ_ERR_ARG, "%s: drop_chroma %d (0 or 1)", fn, o.drop);
+    if (o.trim != 0 && o.trim != 1) return fail(ctx, AEJ_ERR_ARG, "%s: trim %d (0 or 1)", fn, o.trim);
+    if (!rst_ok(o.rst_blocks, o.rst_rows)) return fail(ctx, AEJ_ERR_ARG, "%s: restart_blocks %d, restart_rows %d (0 .. 65535)", fn, o.rst_blocks, o.rst_rows);
     if (n_base < 0 || n_prog < 0 || n_base + n_prog < 1 || (long long)n_base + n_prog > 65535 || (progressive != 0 && progressive != 1))
         return fail(ctx, AEJ_ERR_ARG, "%s: 1 .. 65535 files and progressive 0 or 1 required", fn);
     if (n_base && !jpegdec_descs_ok(descs, n_base)) return fail(ctx, AEJ_ERR_ARG, "%s: a descriptor aej_jpegdec_parse_host did not write", fn);
-    if (n_prog && !jpegprog_layout(frames, pscans, n_prog, c.y)) return fail(ctx, AEJ_ERR_ARG, "%s: descriptors aej_jpegprog_parse_host did not write", fn);
+    if (n_prog && !jpegprog_layout(frames, pscans, n_prog, c.y, {})) return fail(ctx, AEJ_ERR_ARG, "%s: descriptors aej_jpegprog_parse_host did not write", fn);
     const int n = n_base + n_prog;
     c.src.assign(n, JtSource{});
     std::vector<long long> nblk(n);
-    if (n_base) jpegdec_layout(descs, n_base, ctx->jd_subseq_bits, c.files, c.z);
+    if (n_base) jpegdec_layout(descs, n_base, ctx->jd_subseq_bits, c.files, c.z, {});
     c.z.planes = c.z.px = 0;                                 // no reconstruction: no sample planes
     c.y.fz.planes = c.y.fz.px = 0;
     for (int i = 0; i < n; i++) {
         const bool ok = i < n_base ? jt_source_ok(descs[i]) : jt_source_ok(frames[i - n_base]);
         if (!ok) return fail(ctx, AEJ_ERR_UNSUPPORTED, "%s: file %d: three components or one, with 8-bit quantisation tables, required", fn, i);
         if (i < n_base) jfiftrans_source(descs[i], c.src[i]); else jfiftrans_source(frames[i - n_base], c.src[i]);
-        if (!allow440 && c.src[i].ncomp == 3 && c.src[i].hs == 1 && c.src[i].vs == 2)
+        if (!o.allow440 && c.src[i].ncomp == 3 && c.src[i].hs == 1 && c.src[i].vs == 2)
             return fail(ctx, AEJ_ERR_UNSUPPORTED, "%s: file %d: a 4:4:0 file, which the entries with layout_440 take", fn, i);
         nblk[i] = i < n_base ? c.files[i].n_blocks : c.y.ffiles[i - n_base].n_blocks;
         if (density) { c.src[i].units = density[3 * i] & 255; c.src[i].xdensity = density[3 * i + 1]; c.src[i].ydensity = density[3 * i + 2]; }
     }
     int why = kJxOk;
-    const int bad = jfiftrans_plan(c.src, nblk, progressive != 0, xf, trim, c.plan, &why, rst_blocks, rst_rows, allow440 != 0, boxes, drop != 0);
+    const int bad = jfiftrans_plan(c.src, nblk, progressive != 0, o.xf, o.trim, c.plan, &why, o.rst_blocks, o.rst_rows, o.allow440 != 0, o.boxes, o.drop != 0);
     if (bad < 0) return 0;
     if (why == kJxCropRange)
-        return fail(ctx, AEJ_ERR_ARG, "%s: file %d: crop box (%d, %d, %d, %d) does not lie inside the transformed image", fn, bad, boxes[4 * bad],
-                    boxes[4 * bad + 1], boxes[4 * bad + 2], boxes[4 * bad + 3]);
+        return fail(ctx, AEJ_ERR_ARG, "%s: file %d: crop box (%d, %d, %d, %d) does not lie inside the transformed image", fn, bad, o.boxes[4 * bad],
+                    o.boxes[4 * bad + 1], o.boxes[4 * bad + 2], o.boxes[4 * bad + 3]);
     if (why == kJxLayout)
         return fail(ctx, AEJ_ERR_UNSUPPORTED, "%s: file %d: a transposing transform of a 4:2:2 file would be a 4:4:0 file, which is not built", fn, bad);      // (the entries with layout_440 write it)
     if (why == kJxNotPerfect)
         return fail(ctx, AEJ_ERR_ARG, "%s: file %d: transform %d mirrors an axis that is not a whole number of MCUs (trim = 1 drops the partial ones)", fn,
-                    bad, xf ? xf[bad] : 0);
+                    bad, o.xf ? o.xf[bad] : 0);
     if (why == kJxTrimsToZero) return fail(ctx, AEJ_ERR_ARG, "%s: file %d: nothing is left of the mirrored axis after the trim", fn, bad);
     return fail(ctx, AEJ_ERR_ARG, "%s: file %d: a transform code outside 0 .. 7, or descriptors whose sampling or block counts do not fit", fn, bad);
 }
@@ -962,17 +850,17 @@ static JtWorkspace jt_carve(void *workspace, int n_base, int n_prog, JtCall &c)
 }
 
 static int jt_headers(const aej_jpegdec_desc *desc_host, const aej_jpegprog_frame *frame_host, const uint16_t *density3_host, int progressive,
-                      int transform, int trim, uint8_t *out_host, int capacity, int allow440 = 0, const int32_t *box = nullptr, int drop = 0)
+                      const JtOptions &o, uint8_t *out_host, int capacity)
 {
-    if ((allow440 != 0 && allow440 != 1) || (drop != 0 && drop != 1)) return AEJ_ERR_ARG;
-    if ((!desc_host) == (!frame_host) || !out_host || capacity < 0 || (progressive != 0 && progressive != 1) || (trim != 0 && trim != 1)) return AEJ_ERR_ARG;
+    if ((o.allow440 != 0 && o.allow440 != 1) || (o.drop != 0 && o.drop != 1)) return AEJ_ERR_ARG;
+    if ((!desc_host) == (!frame_host) || !out_host || capacity < 0 || (progressive != 0 && progressive != 1) || (o.trim != 0 && o.trim != 1)) return AEJ_ERR_ARG;
     if (!(desc_host ? jt_source_ok(*desc_host) : jt_source_ok(*frame_host))) return AEJ_ERR_UNSUPPORTED;
     JtSource s;
     if (desc_host) jfiftrans_source(*desc_host, s); else jfiftrans_source(*frame_host, s);
     if (density3_host) { s.units = density3_host[0] & 255; s.xdensity = density3_host[1]; s.ydensity = density3_host[2]; }
     JxGeom x;
-    if (!allow440 && s.ncomp == 3 && s.hs == 1 && s.vs == 2) return AEJ_ERR_UNSUPPORTED;
-    const int rc = jx_geom(s.height, s.width, s.hs, s.vs, transform, trim, x, s.ncomp, allow440 != 0, box, drop != 0);
+    if (!o.allow440 && s.ncomp == 3 && s.hs == 1 && s.vs == 2) return AEJ_ERR_UNSUPPORTED;
+    const int rc = jx_geom(s.height, s.width, s.hs, s.vs, o.xf ? *o.xf : kJxNone, o.trim, x, s.ncomp, o.allow440 != 0, o.boxes, o.drop != 0);
     if (rc != kJxOk) return rc == kJxLayout ? AEJ_ERR_UNSUPPORTED : AEJ_ERR_ARG;
     const int n = jfiftrans_prefix_host(jfiftrans_transformed(s, x), progressive != 0, out_host, capacity);
     return n < 0 ? AEJ_ERR_CAPACITY : n;
@@ -981,34 +869,35 @@ static int jt_headers(const aej_jpegdec_desc *desc_host, const aej_jpegprog_fram
 extern "C" int aej_jfif_transcode_headers_host(const aej_jpegdec_desc *desc_host, const aej_jpegprog_frame *frame_host, const uint16_t *density3_host,
                                                int progressive, uint8_t *out_host, int capacity)
 {
-    return jt_headers(desc_host, frame_host, density3_host, progressive, kJxNone, 0, out_host, capacity);
+    return jt_headers(desc_host, frame_host, density3_host, progressive, {}, out_host, capacity);
 }
 
 extern "C" int aej_jfif_transform_headers_host(const aej_jpegdec_desc *desc_host, const aej_jpegprog_frame *frame_host, const uint16_t *density3_host,
                                                int progressive, int transform, int trim, uint8_t *out_host, int capacity)
 {
-    return jt_headers(desc_host, frame_host, density3_host, progressive, transform, trim, out_host, capacity);
+    return jt_headers(desc_host, frame_host, density3_host, progressive, { &transform, trim }, out_host, capacity);
 }
 
 extern "C" int aej_jfif_transform_headers_host_440(const aej_jpegdec_desc *desc_host, const aej_jpegprog_frame *frame_host, const uint16_t *density3_host,
                                                    int progressive, int transform, int trim, int layout_440, uint8_t *out_host, int capacity)
 {
-    return jt_headers(desc_host, frame_host, density3_host, progressive, transform, trim, out_host, capacity, layout_440);
+    return jt_headers(desc_host, frame_host, density3_host, progressive, { &transform, trim, 0, 0, layout_440 }, out_host, capacity);
 }
 
 extern "C" int aej_jfif_transform_headers_host_cut(const aej_jpegdec_desc *desc_host, const aej_jpegprog_frame *frame_host, const uint16_t *density3_host,
                                                    int progressive, int transform, int trim, int layout_440, const int32_t *box4_host, int drop_chroma,
                                                    uint8_t *out_host, int capacity)
 {
-    return jt_headers(desc_host, frame_host, density3_host, progressive, transform, trim, out_host, capacity, layout_440, box4_host, drop_chroma);
+    return jt_headers(desc_host, frame_host, density3_host, progressive, { &transform, trim, 0, 0, layout_440, box4_host, drop_chroma }, out_host, capacity);
 }
 
-static int jt_geometry_host(int H, int W, int hs, int vs, int transform, int trim, int32_t *out4_host, int allow440, int nc = 3,
-                            const int32_t *box = nullptr, int drop = 0, int32_t *corner2 = nullptr)
+// out4_host (may be NULL): the output's height, width and sampling factors; corner2 (may be NULL): the crop's corner in output pixels
+static int jt_geometry_host(int H, int W, int hs, int vs, int nc, const JtOptions &o, int32_t *out4_host, int32_t *corner2)
 {
     JxGeom x;
-    if ((allow440 != 0 && allow440 != 1) || (drop != 0 && drop != 1)) return AEJ_ERR_ARG;
-    const int rc = jx_geom(H, W, hs, vs, transform, trim != 0, x, nc, allow440 != 0, box, drop != 0);
+    const int trim = o.trim;
+    if ((o.allow440 != 0 && o.allow440 != 1) || (o.drop != 0 && o.drop != 1)) return AEJ_ERR_ARG;
+    const int rc = jx_geom(H, W, hs, vs, *o.xf, trim != 0, x, nc, o.allow440 != 0, o.boxes, o.drop != 0);
     if ((trim != 0 && trim != 1) || rc == kJxBadArg) return AEJ_ERR_ARG;
     if (rc == kJxLayout) return AEJ_ERR_UNSUPPORTED;
     if (rc == kJxCropRange) return AEJ_JFIF_TRANSFORM_CROP_RANGE;
@@ -1022,29 +911,28 @@ extern "C" int aej_jfif_transform_geometry_host_cut(int H, int W, int hs, int vs
                                                     const int32_t *box4_host, int drop_chroma, int32_t *out6_host)
 {
     int32_t o[6] = { 0, 0, 0, 0, 0, 0 };
-    const int rc = jt_geometry_host(H, W, hs, vs, transform, trim, o, layout_440, components, box4_host, drop_chroma, o + 4);
+    const int rc = jt_geometry_host(H, W, hs, vs, components, { &transform, trim, 0, 0, layout_440, box4_host, drop_chroma }, o, o + 4);
     if (rc == 0 && out6_host) memcpy(out6_host, o, sizeof o);
     return rc;
 }
 
 extern "C" int aej_jfif_transform_geometry_host(int H, int W, int hs, int vs, int transform, int trim, int32_t *out4_host)
 {
-    return jt_geometry_host(H, W, hs, vs, transform, trim, out4_host, 0);
+    return jt_geometry_host(H, W, hs, vs, 3, { &transform, trim }, out4_host, nullptr);
 }
 
 extern "C" int aej_jfif_transform_geometry_host_440(int H, int W, int hs, int vs, int transform, int trim, int layout_440, int32_t *out4_host)
 {
-    return jt_geometry_host(H, W, hs, vs, transform, trim, out4_host, layout_440);
+    return jt_geometry_host(H, W, hs, vs, 3, { &transform, trim, 0, 0, layout_440 }, out4_host, nullptr);
 }
 
-static int64_t jt_coefs_host(int H, int W, int hs, int vs, int nc, int transform, int trim, const int16_t *src_host, int64_t src_blocks,
-                             int16_t *dst_host, int64_t dst_blocks, int allow440 = 0, const int32_t *box = nullptr, int drop = 0, bool cut_entry = false)
+static int64_t jt_coefs_host(int H, int W, int hs, int vs, int nc, const JtOptions &o, const int16_t *src_host, int64_t src_blocks, int16_t *dst_host,
+                             int64_t dst_blocks)
 {
     JxGeom x;
-    const int rc = cut_entry ? jt_geometry_host(H, W, hs, vs, transform, trim, nullptr, allow440, nc, box, drop)
-                             : jt_geometry_host(H, W, hs, vs, transform, trim, nullptr, allow440);
+    const int rc = jt_geometry_host(H, W, hs, vs, nc, o, nullptr, nullptr);
     if (rc) return rc;
-    jx_geom(H, W, hs, vs, transform, trim, x, nc, allow440 != 0, box, drop != 0);
+    jx_geom(H, W, hs, vs, *o.xf, o.trim, x, nc, o.allow440 != 0, o.boxes, o.drop != 0);
     if (!src_host && !dst_host) return x.n_out;              // a size query
     if (!src_host || !dst_host || src_blocks != x.n_src) return AEJ_ERR_ARG;
     if (dst_blocks < x.n_out) return AEJ_ERR_CAPACITY;
@@ -1055,42 +943,40 @@ static int64_t jt_coefs_host(int H, int W, int hs, int vs, int nc, int transform
 extern "C" int64_t aej_jfif_transform_coefs_host(int H, int W, int hs, int vs, int transform, int trim, const int16_t *src_host, int64_t src_blocks,
                                                  int16_t *dst_host, int64_t dst_blocks)
 {
-    return jt_coefs_host(H, W, hs, vs, 3, transform, trim, src_host, src_blocks, dst_host, dst_blocks);
+    return jt_coefs_host(H, W, hs, vs, 3, { &transform, trim }, src_host, src_blocks, dst_host, dst_blocks);
 }
 
 extern "C" int64_t aej_jfif_transform_coefs_host_440(int H, int W, int hs, int vs, int transform, int trim, int layout_440, const int16_t *src_host,
                                                      int64_t src_blocks, int16_t *dst_host, int64_t dst_blocks)
 {
-    return jt_coefs_host(H, W, hs, vs, 3, transform, trim, src_host, src_blocks, dst_host, dst_blocks, layout_440);
+    return jt_coefs_host(H, W, hs, vs, 3, { &transform, trim, 0, 0, layout_440 }, src_host, src_blocks, dst_host, dst_blocks);
 }
 
 extern "C" int64_t aej_jfif_transform_coefs_host_cut(int H, int W, int hs, int vs, int components, int transform, int trim, int layout_440,
                                                      const int32_t *box4_host, int drop_chroma, const int16_t *src_host, int64_t src_blocks,
                                                      int16_t *dst_host, int64_t dst_blocks)
 {
-    const int64_t rc = jt_coefs_host(H, W, hs, vs, components, transform, trim, src_host, src_blocks, dst_host, dst_blocks, layout_440, box4_host,
-                                     drop_chroma, true);
-    const bool refused = jt_geometry_host(H, W, hs, vs, transform, trim, nullptr, layout_440, components, box4_host, drop_chroma) > 0;
+    const JtOptions o{ &transform, trim, 0, 0, layout_440, box4_host, drop_chroma };
+    const int64_t rc = jt_coefs_host(H, W, hs, vs, components, o, src_host, src_blocks, dst_host, dst_blocks);
+    const bool refused = jt_geometry_host(H, W, hs, vs, components, o, nullptr, nullptr) > 0;
     return refused ? AEJ_ERR_ARG : rc;                        // a cropped file can have 1, 2 or 3 blocks: no positive refusal codes here
 }
 
 extern "C" int64_t aej_jfif_transform_coefs_grey_host(int H, int W, int transform, int trim, const int16_t *src_host, int64_t src_blocks,
                                                       int16_t *dst_host, int64_t dst_blocks)
 {
-    const int64_t rc = jt_coefs_host(H, W, 1, 1, 1, transform, trim, src_host, src_blocks, dst_host, dst_blocks);
+    const int64_t rc = jt_coefs_host(H, W, 1, 1, 1, { &transform, trim }, src_host, src_blocks, dst_host, dst_blocks);
     const bool refused = aej_jfif_transform_geometry_host(H, W, 1, 1, transform, trim, nullptr) > 0;
     return refused ? AEJ_ERR_ARG : rc;                        // a one-component file can have 1 or 2 blocks: no positive refusal codes here
 }
 
-static uint64_t jt_workspace_bytes(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs_host, int n_base, const aej_jpegprog_frame *frames_host,
-                                   const aej_jpegprog_scan *pscans_host, int n_prog, int progressive, const int32_t *xf, int trim, int rst_blocks,
-                                   int rst_rows, int allow440 = 0, const int32_t *boxes = nullptr, int drop = 0)
+static uint64_t jt_workspace_bytes(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base, const aej_jpegprog_frame *frames_host,
+                                   const aej_jpegprog_scan *pscans_host, int n_prog, int progressive, const JtOptions &o)
 {
-    if (!ctx || (n_base > 0 && !descs_host) || (n_prog > 0 && (!frames_host || !pscans_host))) return 0;
+    if (!ctx || (o.need_xf && !o.xf) || (n_base > 0 && !descs_host) || (n_prog > 0 && (!frames_host || !pscans_host))) return 0;
     JtCall c;
     const std::string keep = ctx->err;
-    const int rc = jt_layout(ctx, fn, descs_host, n_base, frames_host, pscans_host, n_prog, nullptr, progressive, xf, trim, rst_blocks, rst_rows, c, allow440,
-                             boxes, drop);
+    const int rc = jt_layout(ctx, "", descs_host, n_base, frames_host, pscans_host, n_prog, nullptr, progressive, o, c);
     ctx->err = keep;                                         // a size query leaves the context's last error alone
     return rc ? 0 : jt_carve(nullptr, n_base, n_prog, c).bytes;
 }
@@ -1099,14 +985,14 @@ extern "C" uint64_t aej_jfif_transcode_workspace_bytes_rst(aej_ctx *ctx, const a
                                                            const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *pscans_host, int n_prog,
                                                            int progressive, int restart_blocks, int restart_rows)
 {
-    return jt_workspace_bytes(ctx, __func__, descs_host, n_base, frames_host, pscans_host, n_prog, progressive, nullptr, 0, restart_blocks, restart_rows);
+    return jt_workspace_bytes(ctx, descs_host, n_base, frames_host, pscans_host, n_prog, progressive, { nullptr, 0, restart_blocks, restart_rows });
 }
 
 extern "C" uint64_t aej_jfif_transcode_workspace_bytes(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base,
                                                        const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *pscans_host, int n_prog,
                                                        int progressive)
 {
-    return jt_workspace_bytes(ctx, __func__, descs_host, n_base, frames_host, pscans_host, n_prog, progressive, nullptr, 0, 0, 0);
+    return jt_workspace_bytes(ctx, descs_host, n_base, frames_host, pscans_host, n_prog, progressive, {});
 }
 
 extern "C" uint64_t aej_jfif_transform_workspace_bytes_rst(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base,
@@ -1114,9 +1000,7 @@ extern "C" uint64_t aej_jfif_transform_workspace_bytes_rst(aej_ctx *ctx, const a
                                                            int progressive, const int32_t *transforms_host, int trim, int restart_blocks,
                                                            int restart_rows)
 {
-    if (!transforms_host) return 0;
-    return jt_workspace_bytes(ctx, __func__, descs_host, n_base, frames_host, pscans_host, n_prog, progressive, transforms_host, trim, restart_blocks,
-                              restart_rows);
+    return jt_workspace_bytes(ctx, descs_host, n_base, frames_host, pscans_host, n_prog, progressive, { transforms_host, trim, restart_blocks, restart_rows, 0, nullptr, 0, true });
 }
 
 extern "C" uint64_t aej_jfif_transform_workspace_bytes_440(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base,
@@ -1124,8 +1008,7 @@ extern "C" uint64_t aej_jfif_transform_workspace_bytes_440(aej_ctx *ctx, const a
                                                            int progressive, const int32_t *transforms_host, int trim, int restart_blocks,
                                                            int restart_rows, int layout_440)
 {
-    return jt_workspace_bytes(ctx, __func__, descs_host, n_base, frames_host, pscans_host, n_prog, progressive, transforms_host, trim, restart_blocks,
-                              restart_rows, layout_440);
+    return jt_workspace_bytes(ctx, descs_host, n_base, frames_host, pscans_host, n_prog, progressive, { transforms_host, trim, restart_blocks, restart_rows, layout_440 });
 }
 
 extern "C" uint64_t aej_jfif_transform_workspace_bytes_cut(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base,
@@ -1133,31 +1016,29 @@ extern "C" uint64_t aej_jfif_transform_workspace_bytes_cut(aej_ctx *ctx, const a
                                                            int progressive, const int32_t *transforms_host, int trim, int restart_blocks,
                                                            int restart_rows, int layout_440, const int32_t *boxes4_host, int drop_chroma)
 {
-    return jt_workspace_bytes(ctx, __func__, descs_host, n_base, frames_host, pscans_host, n_prog, progressive, transforms_host, trim, restart_blocks,
-                              restart_rows, layout_440, boxes4_host, drop_chroma);
+    return jt_workspace_bytes(ctx, descs_host, n_base, frames_host, pscans_host, n_prog, progressive, { transforms_host, trim, restart_blocks, restart_rows, layout_440, boxes4_host, drop_chroma });
 }
 
 extern "C" uint64_t aej_jfif_transform_workspace_bytes(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base,
                                                        const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *pscans_host, int n_prog,
                                                        int progressive, const int32_t *transforms_host, int trim)
 {
-    return aej_jfif_transform_workspace_bytes_rst(ctx, descs_host, n_base, frames_host, pscans_host, n_prog, progressive, transforms_host, trim, 0, 0);
+    return jt_workspace_bytes(ctx, descs_host, n_base, frames_host, pscans_host, n_prog, progressive, { transforms_host, trim, 0, 0, 0, nullptr, 0, true });
 }
 
 static int jt_batch(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs_host, int n_base, const uint8_t *scans, uint64_t scans_bytes,
                     const int64_t *scan_offsets_host, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *pscans_host, int n_prog,
                     const uint8_t *data, uint64_t data_bytes, const int64_t *data_offsets_host, const uint16_t *density_host, int progressive,
-                    const int32_t *xf, int trim, int rst_blocks, int rst_rows, uint8_t *out, uint64_t out_capacity, int64_t *offsets,
-                    int64_t *lengths, uint64_t *total_host, int32_t *status, int32_t *n_groups_host, void *workspace, uint64_t workspace_bytes,
-                    int allow440 = 0, const int32_t *boxes = nullptr, int drop = 0)
+                    const JtOptions &o, uint8_t *out, uint64_t out_capacity, int64_t *offsets, int64_t *lengths, uint64_t *total_host, int32_t *status,
+                    int32_t *n_groups_host, void *workspace, uint64_t workspace_bytes)
 {
     AEJ_TRY(enter(ctx, fn));
+    if (o.need_xf && !o.xf) return null_buffer(ctx, fn);
     if ((n_base > 0 && (!descs_host || !scans || !scan_offsets_host)) || (n_prog > 0 && (!frames_host || !pscans_host || !data || !data_offsets_host)) ||
         !offsets || !lengths || !total_host || !status || !workspace)
         return null_buffer(ctx, fn);
     JtCall c;
-    AEJ_TRY(jt_layout(ctx, fn, descs_host, n_base, frames_host, pscans_host, n_prog, density_host, progressive, xf, trim, rst_blocks, rst_rows, c, allow440,
-                      boxes, drop));
+    AEJ_TRY(jt_layout(ctx, fn, descs_host, n_base, frames_host, pscans_host, n_prog, density_host, progressive, o, c));
     for (int i = 0; i < n_base; i++) AEJ_TRY(jpegdec_scan_offset(ctx, fn, descs_host[i], i, scans_bytes, scan_offsets_host[i], c.files[i]));
     AEJ_TRY(jpegprog_scan_offsets(ctx, fn, c.y, data_bytes, data_offsets_host));
     const JtWorkspace ws = jt_carve(workspace, n_base, n_prog, c);
@@ -1171,7 +1052,7 @@ static int jt_batch(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs_
     if (n_groups_host) *n_groups_host = (int32_t)c.plan.groups.size();
     std::vector<unsigned char> blob;
     if (n_base) {
-        AEJ_TRY(jpegdec_decode(ctx, fn, descs_host, n_base, c.files, c.z, ws.wb, scans, status));
+        AEJ_TRY(jpegdec_decode(ctx, fn, descs_host, n_base, c.files, c.z, ws.wb, scans, status, nullptr));
         AEJ_HIP_CHECK(launch_jpegdec_write(ctx->stream, n_base, c.z, ws.wb, ctx->jd_subseq_bits, status));
     } else {
         AEJ_TRY(bind_device(ctx));
@@ -1198,8 +1079,8 @@ extern "C" int aej_jfif_transcode_batch_rst(aej_ctx *ctx, const aej_jpegdec_desc
                                             uint64_t *total_host, int32_t *status, int32_t *n_groups_host, void *workspace, uint64_t workspace_bytes)
 {
     return jt_batch(ctx, __func__, descs_host, n_base, scans, scans_bytes, scan_offsets_host, frames_host, pscans_host, n_prog, data, data_bytes,
-                    data_offsets_host, density_host, progressive, nullptr, 0, restart_blocks, restart_rows, out, out_capacity, offsets, lengths,
-                    total_host, status, n_groups_host, workspace, workspace_bytes);
+                    data_offsets_host, density_host, progressive, { nullptr, 0, restart_blocks, restart_rows }, out, out_capacity, offsets, lengths, total_host, status, n_groups_host,
+                    workspace, workspace_bytes);
 }
 
 extern "C" int aej_jfif_transcode_batch(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base, const uint8_t *scans, uint64_t scans_bytes,
@@ -1210,21 +1091,8 @@ extern "C" int aej_jfif_transcode_batch(aej_ctx *ctx, const aej_jpegdec_desc *de
                                         int32_t *n_groups_host, void *workspace, uint64_t workspace_bytes)
 {
     return jt_batch(ctx, __func__, descs_host, n_base, scans, scans_bytes, scan_offsets_host, frames_host, pscans_host, n_prog, data, data_bytes,
-                    data_offsets_host, density_host, progressive, nullptr, 0, 0, 0, out, out_capacity, offsets, lengths, total_host, status,
-                    n_groups_host, workspace, workspace_bytes);
-}
-
-static int jx_batch(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *descs_host, int n_base, const uint8_t *scans, uint64_t scans_bytes,
-                    const int64_t *scan_offsets_host, const aej_jpegprog_frame *frames_host, const aej_jpegprog_scan *pscans_host, int n_prog,
-                    const uint8_t *data, uint64_t data_bytes, const int64_t *data_offsets_host, const uint16_t *density_host, int progressive,
-                    const int32_t *transforms_host, int trim, int rst_blocks, int rst_rows, uint8_t *out, uint64_t out_capacity, int64_t *offsets,
-                    int64_t *lengths, uint64_t *total_host, int32_t *status, int32_t *n_groups_host, void *workspace, uint64_t workspace_bytes)
-{
-    AEJ_TRY(enter(ctx, fn));
-    if (!transforms_host) return null_buffer(ctx, fn);
-    return jt_batch(ctx, fn, descs_host, n_base, scans, scans_bytes, scan_offsets_host, frames_host, pscans_host, n_prog, data, data_bytes,
-                    data_offsets_host, density_host, progressive, transforms_host, trim, rst_blocks, rst_rows, out, out_capacity, offsets, lengths,
-                    total_host, status, n_groups_host, workspace, workspace_bytes);
+                    data_offsets_host, density_host, progressive, {}, out, out_capacity, offsets, lengths, total_host, status, n_groups_host,
+                    workspace, workspace_bytes);
 }
 
 extern "C" int aej_jfif_transform_batch_rst(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base, const uint8_t *scans, uint64_t scans_bytes,
@@ -1235,9 +1103,9 @@ extern "C" int aej_jfif_transform_batch_rst(aej_ctx *ctx, const aej_jpegdec_desc
                                             uint64_t out_capacity, int64_t *offsets, int64_t *lengths, uint64_t *total_host, int32_t *status,
                                             int32_t *n_groups_host, void *workspace, uint64_t workspace_bytes)
 {
-    return jx_batch(ctx, __func__, descs_host, n_base, scans, scans_bytes, scan_offsets_host, frames_host, pscans_host, n_prog, data, data_bytes,
-                    data_offsets_host, density_host, progressive, transforms_host, trim, restart_blocks, restart_rows, out, out_capacity, offsets,
-                    lengths, total_host, status, n_groups_host, workspace, workspace_bytes);
+    return jt_batch(ctx, __func__, descs_host, n_base, scans, scans_bytes, scan_offsets_host, frames_host, pscans_host, n_prog, data, data_bytes,
+                    data_offsets_host, density_host, progressive, { transforms_host, trim, restart_blocks, restart_rows, 0, nullptr, 0, true }, out, out_capacity, offsets, lengths, total_host, status, n_groups_host,
+                    workspace, workspace_bytes);
 }
 
 extern "C" int aej_jfif_transform_batch_440(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base, const uint8_t *scans, uint64_t scans_bytes,
@@ -1249,8 +1117,8 @@ extern "C" int aej_jfif_transform_batch_440(aej_ctx *ctx, const aej_jpegdec_desc
                                             int32_t *status, int32_t *n_groups_host, void *workspace, uint64_t workspace_bytes)
 {
     return jt_batch(ctx, __func__, descs_host, n_base, scans, scans_bytes, scan_offsets_host, frames_host, pscans_host, n_prog, data, data_bytes,
-                    data_offsets_host, density_host, progressive, transforms_host, trim, restart_blocks, restart_rows, out, out_capacity, offsets,
-                    lengths, total_host, status, n_groups_host, workspace, workspace_bytes, layout_440);
+                    data_offsets_host, density_host, progressive, { transforms_host, trim, restart_blocks, restart_rows, layout_440 }, out, out_capacity, offsets, lengths, total_host, status, n_groups_host,
+                    workspace, workspace_bytes);
 }
 
 extern "C" int aej_jfif_transform_batch_cut(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base, const uint8_t *scans, uint64_t scans_bytes,
@@ -1263,8 +1131,8 @@ extern "C" int aej_jfif_transform_batch_cut(aej_ctx *ctx, const aej_jpegdec_desc
                                             uint64_t workspace_bytes)
 {
     return jt_batch(ctx, __func__, descs_host, n_base, scans, scans_bytes, scan_offsets_host, frames_host, pscans_host, n_prog, data, data_bytes,
-                    data_offsets_host, density_host, progressive, transforms_host, trim, restart_blocks, restart_rows, out, out_capacity, offsets,
-                    lengths, total_host, status, n_groups_host, workspace, workspace_bytes, layout_440, boxes4_host, drop_chroma);
+                    data_offsets_host, density_host, progressive, { transforms_host, trim, restart_blocks, restart_rows, layout_440, boxes4_host, drop_chroma }, out, out_capacity, offsets, lengths, total_host, status, n_groups_host,
+                    workspace, workspace_bytes);
 }
 
 extern "C" int aej_jfif_transform_batch(aej_ctx *ctx, const aej_jpegdec_desc *descs_host, int n_base, const uint8_t *scans, uint64_t scans_bytes,
@@ -1275,9 +1143,9 @@ extern "C" int aej_jfif_transform_batch(aej_ctx *ctx, const aej_jpegdec_desc *de
                                         int64_t *lengths, uint64_t *total_host, int32_t *status, int32_t *n_groups_host, void *workspace,
                                         uint64_t workspace_bytes)
 {
-    return jx_batch(ctx, __func__, descs_host, n_base, scans, scans_bytes, scan_offsets_host, frames_host, pscans_host, n_prog, data, data_bytes,
-                    data_offsets_host, density_host, progressive, transforms_host, trim, 0, 0, out, out_capacity, offsets, lengths, total_host,
-                    status, n_groups_host, workspace, workspace_bytes);
+    return jt_batch(ctx, __func__, descs_host, n_base, scans, scans_bytes, scan_offsets_host, frames_host, pscans_host, n_prog, data, data_bytes,
+                    data_offsets_host, density_host, progressive, { transforms_host, trim, 0, 0, 0, nullptr, 0, true }, out, out_capacity, offsets, lengths, total_host, status, n_groups_host,
+                    workspace, workspace_bytes);
 }
 
 // ---- images of mixed sizes and qualities in one call (jfifmany.hip): the ragged front end, then the transcoder's chains --------------------

@@ -1111,14 +1111,14 @@ void jpeg_recon_layout(const aej_jpegdec_desc &d, int shift, JdFile &F, JdBufSiz
     z.px += (long long)d.width * d.height;
 }
 
-void jpegdec_layout(const aej_jpegdec_desc *descs, int n, int S, std::vector<JdFile> &files, JdBufSizes &z, const int *shifts, const int *boxes,
-                    const aej_jpeg_adobe *adobe)
+void jpegdec_layout(const aej_jpegdec_desc *descs, int n, int S, std::vector<JdFile> &files, JdBufSizes &z, const JdResolved &r)
 {
+    const aej_jpeg_adobe *adobe = r.adobe;
     files.assign(n, JdFile{});
     z = JdBufSizes{};
     for (int i = 0; i < n; i++) {
         jpeg_stream_layout(descs[i].scan_length, descs[i].n_segments, S, files[i], z);
-        jpeg_recon_layout(descs[i], shifts ? shifts[i] : 0, files[i], z, boxes ? boxes + 4 * i : nullptr, true, adobe ? adobe + i : nullptr);
+        jpeg_recon_layout(descs[i], r.shifts.empty() ? 0 : r.shifts[i], files[i], z, r.boxes ? r.boxes + 4 * i : nullptr, true, adobe ? adobe + i : nullptr);
         if (descs[i].ncomp == 3 || (adobe && jpeg_adobe_new(adobe + i))) {      // one DC and one AC table for every component?
             const aej_jpegdec_desc &d = descs[i];
             bool same = !memcmp(&d.dc[1], &d.dc[0], sizeof d.dc[0]) && !memcmp(&d.dc[2], &d.dc[0], sizeof d.dc[0]) &&

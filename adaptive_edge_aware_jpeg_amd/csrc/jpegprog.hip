@@ -94,9 +94,9 @@ __global__ __launch_bounds__(256) void k_jp_status(const JpScan *__restrict__ sc
 
 // ---- host: validation, layout, launch sequence -----------------------------------------------------------------------------------------
 // Everything the kernels index with is recomputed or checked here; the dependency levels are derived again rather than trusted.
-bool jpegprog_layout(const aej_jpegprog_frame *frames, const aej_jpegprog_scan *scans_in, int n, JpLayout &y, const int *shifts, const int *boxes,
-                     const aej_jpeg_adobe *adobe)
+bool jpegprog_layout(const aej_jpegprog_frame *frames, const aej_jpegprog_scan *scans_in, int n, JpLayout &y, const JdResolved &r)
 {
+    const aej_jpeg_adobe *adobe = r.adobe;
     y = JpLayout{};
     if (!frames || !scans_in || n < 1) return false;
     y.ffiles.assign(n, JdFile{});
@@ -113,7 +113,7 @@ bool jpegprog_layout(const aej_jpegprog_frame *frames, const aej_jpegprog_scan *
         d.width = f.width; d.height = f.height; d.ncomp = f.ncomp; d.hs = f.hs; d.vs = f.vs; d.mcux = f.mcux; d.mcuy = f.mcuy;
         d.blocks_per_mcu = f.blocks_per_mcu; d.n_segments = 1; d.sof = f.sof; d.precision16 = f.precision16;
         memcpy(d.qt, f.qt, sizeof d.qt);
-        jpeg_recon_layout(d, shifts ? shifts[i] : 0, y.ffiles[i], y.fz, boxes ? boxes + 4 * i : nullptr, false, x);      // a boxed file: all coefficients, k_jd_box (kJdSbox in its shift: k_jd_sbox)
+        jpeg_recon_layout(d, r.shifts.empty() ? 0 : r.shifts[i], y.ffiles[i], y.fz, r.boxes ? r.boxes + 4 * i : nullptr, false, x);      // a boxed file: all coefficients, k_jd_box (kJdSbox in its shift: k_jd_sbox)
         int cell_level[4][64];
         for (int c = 0; c < 4; c++) for (int k = 0; k < 64; k++) cell_level[c][k] = -1;
         for (int j = 0; j < f.n_scans; j++) {
@@ -253,7 +253,7 @@ int jpegprog_coefs_host(const aej_jpegprog_frame &frame, const aej_jpegprog_scan
                         int n_levels, short *coef, unsigned long long coef_blocks)
 {
     JpLayout y;
-    if (!jpegprog_layout(&frame, scans_in, 1, y)) return AEJ_ERR_ARG;
+    if (!jpegprog_layout(&frame, scans_in, 1, y, {})) return AEJ_ERR_ARG;
     if ((unsigned long long)y.fz.blocks > coef_blocks) return AEJ_ERR_CAPACITY;
     memset(coef, 0, (size_t)y.fz.blocks * 128);
     for (size_t t = 0; t < y.scans.size(); t++) {

@@ -381,35 +381,31 @@ def _adobe_array(frames):
     return (JpegAdobe * len(xs))(*[x if x is not None else JpegAdobe() for x in xs])
 
 
+def _decode_entries(lib, family, idx, scales, comps, boxes, sbox, xs):
+    """The C entries of one decoder family ("jpegdec" | "jpegprog") for a call's options -> (the size query, the batch entry, their
+    leading option arguments, the arrays those point into, to be kept until the call returns).  The entry is the narrowest that takes
+    every option given: none, _scaled (scales), _mode (comps: 3, 1 or 4 per file), _box or -- sbox: the boxes are in pixels of each file's
+    scaled image -- _sbox (boxes: int32 [n, 4]), _adobe (xs: _adobe_array's); an option not given goes as NULL."""
+    arrays = [None if a is None else np.ascontiguousarray(a[idx], np.int32) for a in (scales, comps, boxes)]
+    args = [None if a is None else a.ctypes.data for a in arrays] + [None if xs is None else ctypes.addressof(xs)]
+    given = max(k + 1 if a is not None else 0 for k, a in enumerate(args))
+    # _adobe wins over _sbox: its files are refused at any scale but 1, where a scaled box is the full-size box (another file's at 2, 4, 8: refused)
+    sfx = ("", "_scaled", "_mode", "_sbox" if sbox else "_box", "_adobe")[given]
+    return getattr(lib, f"aej_{family}_workspace_bytes{sfx}"), getattr(lib, f"aej_{family}_batch{sfx}"), tuple(args[:given]), arrays
+
+
 def _decode_baseline(ctx, idx, parsed, views, out, out_off, scales=None, comps=None, boxes=None, sbox=False):
-    """aej_jpegdec_batch (scales None), aej_jpegdec_batch_scaled, (comps: 3 or 1 per file) aej_jpegdec_batch_mode or (boxes: int32
-    [n, 4]) aej_jpegdec_batch_box over the files idx -> their status words (device int32).  With a four-component or RGB-coded file
-    among them (adobe=True alone parses one): aej_jpegdec_batch_adobe, comps 4 for a file that leaves in mode "CMYK"."""
+    """the aej_jpegdec_batch* entry for the options given (_decode_entries) over the files idx -> their status words (device int32).
+    With a four-component or RGB-coded file among them (adobe=True alone parses one): aej_jpegdec_batch_adobe, comps 4 for a file that
+    leaves in mode "CMYK"."""
     from ._lib import JpegDecDesc
-    t, lib, n = ctx.torch, ctx.lib, len(idx)
+    t, n = ctx.torch, len(idx)
     descs = (JpegDecDesc * n)(*[parsed[i] for i in idx])
     scans, scan_off = _stage(ctx, views, [(i, parsed[i].scan_offset, parsed[i].scan_length) for i in idx])
     oo = np.ascontiguousarray(out_off[idx])
     status = ctx.empty((n,), t.int32)
-    sc = () if scales is None else (np.ascontiguousarray(scales[idx], np.int32),)
-    how = () if scales is None else (sc[0].ctypes.data,)
-    nbytes, batch = ((lib.aej_jpegdec_workspace_bytes, lib.aej_jpegdec_batch) if scales is None else
-                     (lib.aej_jpegdec_workspace_bytes_scaled, lib.aej_jpegdec_batch_scaled))
-    if comps is not None:
-        cc = np.ascontiguousarray(comps[idx], np.int32)
-        how = (sc[0].ctypes.data if sc else None, cc.ctypes.data)
-        nbytes, batch = lib.aej_jpegdec_workspace_bytes_mode, lib.aej_jpegdec_batch_mode
-    if boxes is not None:
-        bb = np.ascontiguousarray(boxes[idx], np.int32)
-        how = (sc[0].ctypes.data if sc else None, cc.ctypes.data if comps is not None else None, bb.ctypes.data)
-        nbytes, batch = lib.aej_jpegdec_workspace_bytes_box, lib.aej_jpegdec_batch_box
-        if sbox:                                         # the boxes are in pixels of each file's scaled image
-            nbytes, batch = lib.aej_jpegdec_workspace_bytes_sbox, lib.aej_jpegdec_batch_sbox
     xs = _adobe_array([parsed[i] for i in idx])
-    if xs is not None:
-        how = (sc[0].ctypes.data if sc else None, cc.ctypes.data if comps is not None else None, bb.ctypes.data if boxes is not None else None,
-               ctypes.addressof(xs))
-        nbytes, batch = lib.aej_jpegdec_workspace_bytes_adobe, lib.aej_jpegdec_batch_adobe
+    nbytes, batch, how, keep = _decode_entries(ctx.lib, "jpegdec", idx, scales, comps, boxes, sbox, xs)
     nws = int(nbytes(ctx.handle, ctypes.addressof(descs), n, *how))
     if nws == 0:
         raise ValueError("descriptors the library refuses")
@@ -421,35 +417,17 @@ def _decode_baseline(ctx, idx, parsed, views, out, out_off, scales=None, comps=N
 
 
 def _decode_progressive(ctx, idx, parsed, views, out, out_off, scales=None, comps=None, boxes=None, sbox=False):
-    """aej_jpegprog_batch (scales None), aej_jpegprog_batch_scaled, (comps) aej_jpegprog_batch_mode or (boxes) aej_jpegprog_batch_box
-    over the files idx -> their status words (device int32)"""
+    """the same through the aej_jpegprog_batch* entries -> the files' status words (device int32)"""
     from ._lib import JpegProgFrame, JpegProgScan
-    t, lib, n = ctx.torch, ctx.lib, len(idx)
+    t, n = ctx.torch, len(idx)
     frames = (JpegProgFrame * n)(*[parsed[i][0] for i in idx])
     flat = [(i, s) for i in idx for s in parsed[i][1]]
     scans = (JpegProgScan * len(flat))(*[s for _, s in flat])
     data, data_off = _stage(ctx, views, [(i, s.data_offset, s.data_length) for i, s in flat])
     oo = np.ascontiguousarray(out_off[idx])
     status = ctx.empty((n,), t.int32)
-    sc = () if scales is None else (np.ascontiguousarray(scales[idx], np.int32),)
-    how = () if scales is None else (sc[0].ctypes.data,)
-    nbytes, batch = ((lib.aej_jpegprog_workspace_bytes, lib.aej_jpegprog_batch) if scales is None else
-                     (lib.aej_jpegprog_workspace_bytes_scaled, lib.aej_jpegprog_batch_scaled))
-    if comps is not None:
-        cc = np.ascontiguousarray(comps[idx], np.int32)
-        how = (sc[0].ctypes.data if sc else None, cc.ctypes.data)
-        nbytes, batch = lib.aej_jpegprog_workspace_bytes_mode, lib.aej_jpegprog_batch_mode
-    if boxes is not None:
-        bb = np.ascontiguousarray(boxes[idx], np.int32)
-        how = (sc[0].ctypes.data if sc else None, cc.ctypes.data if comps is not None else None, bb.ctypes.data)
-        nbytes, batch = lib.aej_jpegprog_workspace_bytes_box, lib.aej_jpegprog_batch_box
-        if sbox:
-            nbytes, batch = lib.aej_jpegprog_workspace_bytes_sbox, lib.aej_jpegprog_batch_sbox
     xs = _adobe_array([parsed[i][0] for i in idx])        # a four-component or RGB-coded file among them: the _adobe entries
-    if xs is not None:
-        how = (sc[0].ctypes.data if sc else None, cc.ctypes.data if comps is not None else None, bb.ctypes.data if boxes is not None else None,
-               ctypes.addressof(xs))
-        nbytes, batch = lib.aej_jpegprog_workspace_bytes_adobe, lib.aej_jpegprog_batch_adobe
+    nbytes, batch, how, keep = _decode_entries(ctx.lib, "jpegprog", idx, scales, comps, boxes, sbox, xs)
     nws = int(nbytes(ctx.handle, ctypes.addressof(frames), ctypes.addressof(scans), n, *how))
     if nws == 0:
         raise ValueError("descriptors the library refuses")
