@@ -1,5 +1,4 @@
 """GPU: Jpeg.decompress_many (aej_inflate_batch + aej_decode_headers) against Jpeg.decompress, the oracle and zlib."""
-import ctypes
 import hashlib
 import json
 import os
@@ -9,13 +8,13 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from inflate_helpers import BitWriter, rebuild, run_inflate, zhdr
 
 pytestmark = pytest.mark.gpu
 
 FIXTURES = sorted(f[:-5] for f in os.listdir(GOLDEN) if f.endswith(".ajpg"))
 ROUNDTRIP = [("YCbCr", 256, 384, (4, 64)), ("OKLAB", 250, 332, (4, 128)), ("ICtCp", 128, 256, (4, 32)), ("ICaCb", 96, 128, (4, 16)),
              ("JzAzBz", 120, 200, (8, 64)), ("YCoCg", 101, 67, (4, 32)), ("YCoCg-R", 33, 35, (2, 16)), ("YCbCr", 1080, 1920, (4, 64))]
-GUARD = 0xA5
 
 
 @pytest.fixture(scope="module")
@@ -97,42 +96,6 @@ def test_mixed_headers_and_empty(A):
 
 
 # ---------------------------------------------------------------------------------------------------------------- inflate alone
-def run_inflate(A, ctx, streams, caps=None):
-    """-> (outputs, statuses, guards intact) for streams decoded in ONE aej_inflate_batch launch into a guarded buffer."""
-    import torch
-    n = len(streams)
-    in_off, pos = [], 0
-    for s in streams:
-        in_off.append(pos)
-        pos += (len(s) + 3) // 4 * 4
-    src = np.zeros(max(pos, 4), np.uint8)
-    for o, s in zip(in_off, streams):
-        src[o:o + len(s)] = np.frombuffer(s, np.uint8)
-    caps = caps or [len(zlib.decompress(s)) if ok else 1 << 16 for s, ok in zip(streams, [True] * n)]
-    out_off, pos = [], 0
-    for c in caps:
-        out_off.append(pos)
-        pos += (c + 3) // 4 * 4 + 256              # guard bytes after every slot
-    dst = torch.full((pos,), GUARD, dtype=torch.uint8, device="cuda")
-    desc = np.array([[in_off[i], len(streams[i]), out_off[i], caps[i]] for i in range(n)], np.int64)
-    d_src, d_desc = torch.from_numpy(src).cuda(), torch.from_numpy(desc).cuda()
-    out_bytes = torch.zeros(n, dtype=torch.int64, device="cuda")
-    status = torch.full((n,), -1, dtype=torch.int32, device="cuda")
-    ctx.check(ctx.lib.aej_inflate_batch(ctx.handle, d_src.data_ptr(), d_desc.data_ptr(), n, dst.data_ptr(), ctypes.c_uint64(pos),
-                                        out_bytes.data_ptr(), status.data_ptr()))
-    host = dst.cpu().numpy()
-    nb, st = out_bytes.cpu().numpy(), status.cpu().numpy()
-    outs, guards = [], True
-    for i in range(n):
-        outs.append(host[out_off[i]:out_off[i] + nb[i]].tobytes())
-        end = out_off[i] + nb[i] if st[i] == 0 else out_off[i] + caps[i]
-        nxt = out_off[i + 1] if i + 1 < n else pos
-        guards &= bool(np.all(host[max(end, out_off[i] + caps[i]):nxt] == GUARD))
-        if st[i] == 0:
-            guards &= bool(np.all(host[end:out_off[i] + caps[i]] == GUARD))
-    return outs, st, guards
-
-
 def good_streams():
     rng = np.random.default_rng(7)
     raw = [rng.integers(0, 256, 5000, dtype=np.uint8).tobytes(), b"",
@@ -168,27 +131,6 @@ def test_inflate_gpu_deflate_multi_megabyte_block(A, oracle, ctx):
     assert guards and not st.any()
     for s, o in zip(streams, outs):
         assert o == zlib.decompress(s)
-
-
-class BitWriter:
-    def __init__(self):
-        self.bits = []
-
-    def put(self, v, n):                 # LSB first
-        self.bits += [(v >> i) & 1 for i in range(n)]
-
-    def code(self, v, n):                # Huffman codes MSB first
-        self.bits += [(v >> (n - 1 - i)) & 1 for i in range(n)]
-
-    def bytes(self):
-        b = self.bits + [0] * (-len(self.bits) % 8)
-        return bytes(sum(b[i + j] << j for j in range(8)) for i in range(0, len(b), 8))
-
-
-def zhdr(cmf=0x78, fdict=0):
-    flg = fdict << 5
-    flg |= (31 - (cmf * 256 + flg) % 31) % 31
-    return bytes([cmf, flg])
 
 
 def corrupt_cases():
@@ -228,13 +170,6 @@ def test_inflate_corruption_statuses(A, ctx):
 
 
 # ---------------------------------------------------------------------------------------------------------------- corrupt files
-def rebuild(meta_bytes, layers):
-    out = [meta_bytes]
-    for bits_len, root, packed, stream in layers:
-        out += [bits_len.to_bytes(4, "big"), root.to_bytes(4, "big"), packed, len(stream).to_bytes(4, "big"), stream]
-    return b"".join(out)
-
-
 def mutations(data):
     from adaptive_edge_aware_jpeg_amd.jpeg import parse_container
     mlen = int.from_bytes(data[:4], "big")
