@@ -41,6 +41,8 @@ class Trace:
         self.matches = []            # (distance, length, output position of its first byte)
         self.lit_code_bits = set()   # lengths of the literal / length codes actually read
         self.dist_code_bits = set()  # lengths of the distance codes actually read
+        self.lit_counts = [0] * 286  # how often each literal / length symbol was read (256: once per coded block)
+        self.dist_counts = [0] * 30  # how often each distance symbol was read
 
     def crossing(self):
         """the repeat symbols with a run that starts among the literal lengths and ends among the distance lengths"""
@@ -197,6 +199,7 @@ def _run(src, out, tr):
             if s is None or s > 285:
                 raise _Stop(BAD_SYMBOL)
             tr.lit_code_bits.add(n)
+            tr.lit_counts[s] += 1
             if s < 256:
                 out.append(s)
                 continue
@@ -209,6 +212,7 @@ def _run(src, out, tr):
             if d is None or d > 29:
                 raise _Stop(BAD_SYMBOL)
             tr.dist_code_bits.add(n)
+            tr.dist_counts[d] += 1
             base, extra = _DIST[d]
             f = src.bits(extra)
             distance = base + f
