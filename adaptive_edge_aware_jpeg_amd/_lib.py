@@ -356,6 +356,7 @@ SIGNATURES = {
     "aej_test_jpegprog_coefs": (_I, [_P, _P, _P, _I, _P, _U64, _P, _I, _P, _U64, _P, _P, _U64]),             # include/aej_testing.h (tests only)
     "aej_test_jpegprog_coefs_host": (_I, [_P, _P, _P, _U64, _I, _P, _U64]),                                 # include/aej_testing.h (tests only)
     "aej_test_jpeg_adobe_pixels_host": (_I, [_P, _I64, _I, _I, _P]),                                        # include/aej_testing.h (tests only)
+    "aej_test_jpeg_upsample_host": (_I, [_P, _I64, _I64, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),          # include/aej_testing.h (tests only)
     "aej_test_jpegdec_idct_host": (_I, [_P, _P, _I, _P]),                                                   # include/aej_testing.h (tests only)
     "aej_test_jpegdec_coefs_host": (_I, [_P, _P, _U64, _P, _U64]),                                          # include/aej_testing.h (tests only)
 }

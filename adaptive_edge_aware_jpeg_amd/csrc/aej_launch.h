@@ -329,7 +329,8 @@ int jfifprog_scan_device(hipStream_t st, const short *coefs_host, long long n, i
 #include "jpegdec_core.h"
 
 namespace aej {
-struct JdBufSizes { long long chunks, segs, slots, blocks, clean, planes, px, grp[3], grp440[3], grpl[4], grpb, grpa, uniform, grps[3]; };      // totals over the files of one call (grp, grp440, grpl, grpb, grps: JdFile::grp_base, ::grp440_base, ::grpl_base, ::grpb_base, ::grps_base; grpa: ::grpa_base, the workgroups of k_jd_adobe -- non-zero exactly when the call has a four-component or RGB-coded file; uniform: the files with JdFile::uniform, three-component YCbCr ones included -- a call with one runs the kFour slot kernels too)
+struct JdBufSizes { long long chunks, segs, slots, blocks, clean, planes, px, grp[3], grp440[3], grpl[4], grpa, uniform, grps[4]; };      // totals over the files of one call (grp, grp440, grpl, grps: JdFile::grp_base, ::grp440_base, ::grpl_base, ::grps_base; grpa: ::grpa_base, the workgroups of k_jd_adobe -- non-zero exactly when the call has a four-component or RGB-coded file; uniform: the files with JdFile::uniform, three-component YCbCr ones included -- a call with one runs the kFour slot kernels too)
+inline bool jpeg_any_box(const JdBufSizes &z) { return z.grps[0] > 0 || z.grps[1] > 0 || z.grps[2] > 0 || z.grps[3] > 0; }      // a call with a boxed file, at full size or at a scale: the <true> slot kernels, aej_jpegdec_box_stats
 struct JdBufs {
     JdFile *files; aej_jpegdec_desc *descs; int *last_change;      // one upload: files, descriptors, the "last round that changed" word
     aej_jpeg_adobe *adobe;                                         // and, in a call that runs the kFour slot kernels (z.grpa > 0 or z.uniform > 0), room for the files' aej_jpeg_adobe (uploaded when z.grpa > 0; else NULL)
@@ -372,7 +373,7 @@ void jpeg_stream_layout(long long len, int n_segments, int S, JdFile &F, JdBufSi
 // scaled kernel (1..3), or, with kJdLuma added to shift, its workgroups of the luma kernel (d's frame fields): F's reconstruction
 // fields, z's totals
 // box (NULL, or the whole image: none): left, top, right, bottom inside the image (jpeg_box_inside), full size only -- the file's
-// workgroups of k_jd_box and no sample planes; window_coef: only the coefficients of the window's MCU rows are stored (baseline files)
+// workgroups of k_jd_sbox<0> and no sample planes; window_coef: only the coefficients of the window's MCU rows are stored (baseline files)
 // kJdSbox in shift (the _sbox entries, scale 2, 4, 8): box is in pixels of the scaled image, inside it and not the whole of it -- the
 // file's workgroups of k_jd_sbox<log2 scale>, the same coefficient window
 // x (NULL: none): the file's aej_jpeg_adobe; with another colour than YCbCr the file gets kJdAdobe in its shift, four sample planes and

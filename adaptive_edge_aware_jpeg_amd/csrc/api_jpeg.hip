@@ -290,7 +290,7 @@ static JdRefusal jd_resolve(const D *frames, int n, const JdOptions &o, JdResolv
         if (!(0 <= b[0] && b[0] < b[2] && b[2] <= ow && 0 <= b[1] && b[1] < b[3] && b[3] <= oh)) return { kJdrBox, i, { b[0], b[1], b[2], b[3], ow, oh } };
         if (!sh || (b[0] == 0 && b[1] == 0 && b[2] == ow && b[3] == oh)) continue;      // at scale 1 the two kinds of box coincide, and the whole image is no box
         if (!o.sbox) return { kJdrBoxScaled, i };
-        shifts[i] |= kJdSbox;                                // k_jd_sbox (jpeg_recon_layout)
+        shifts[i] |= kJdSbox;                                // a box of the scaled image (jpeg_recon_layout)
     }
     for (int i = 0; o.adobe && i < n; i++) {                 // a four-component or RGB-coded file: full size, whole, in colour
         if (!jpeg_adobe_new(o.adobe + i)) continue;
@@ -320,18 +320,7 @@ static int jd_refuse(aej_ctx *ctx, const char *fn, const JdRefusal &r)
                 r.kind == kJdrAdobeLuma ? "luma output" : r.kind == kJdrAdobeScale ? "a scale other than 1" : "a box");
 }
 
-// jd_box_window behind the two public entries
-static int box_window_host(int width, int height, int hs, int vs, int ncomp, const int32_t *box4_host, int32_t *window4_out_host)
-{
-    if (!box4_host || !window4_out_host || width < 1 || height < 1 || (ncomp != 1 && ncomp != 3)) return AEJ_ERR_ARG;
-    if (ncomp == 3 && ((hs != 1 && hs != 2) || (vs != 1 && vs != 2))) return AEJ_ERR_ARG;
-    if (!(0 <= box4_host[0] && box4_host[0] < box4_host[2] && box4_host[2] <= width && 0 <= box4_host[1] && box4_host[1] < box4_host[3] && box4_host[3] <= height))
-        return AEJ_ERR_ARG;
-    jd_box_window(width, height, hs, vs, ncomp, false, box4_host, window4_out_host);
-    return 0;
-}
-
-// jd_sbox_window behind its two public entries: the box in pixels of the image at `scale`
+// jd_sbox_window behind its four public entries: the box in pixels of the image at `scale` (the _box_ entries: 1)
 static int sbox_window_host(int width, int height, int hs, int vs, int ncomp, int scale, const int32_t *box4_host, int32_t *window4_out_host)
 {
     const int sh = jpeg_scale_shift(scale);
@@ -359,13 +348,13 @@ extern "C" int aej_jpegprog_sbox_window_host(const aej_jpegprog_frame *frame_hos
 extern "C" int aej_jpegdec_box_window_host(const aej_jpegdec_desc *desc_host, const int32_t *box4_host, int32_t *window4_out_host)
 {
     if (!desc_host) return AEJ_ERR_ARG;
-    return box_window_host(desc_host->width, desc_host->height, desc_host->hs, desc_host->vs, desc_host->ncomp, box4_host, window4_out_host);
+    return sbox_window_host(desc_host->width, desc_host->height, desc_host->hs, desc_host->vs, desc_host->ncomp, 1, box4_host, window4_out_host);
 }
 
 extern "C" int aej_jpegprog_box_window_host(const aej_jpegprog_frame *frame_host, const int32_t *box4_host, int32_t *window4_out_host)
 {
     if (!frame_host) return AEJ_ERR_ARG;
-    return box_window_host(frame_host->width, frame_host->height, frame_host->hs, frame_host->vs, frame_host->ncomp, box4_host, window4_out_host);
+    return sbox_window_host(frame_host->width, frame_host->height, frame_host->hs, frame_host->vs, frame_host->ncomp, 1, box4_host, window4_out_host);
 }
 
 extern "C" int aej_jpegdec_box_stats(aej_ctx *ctx, int64_t *out3_host)
@@ -473,7 +462,7 @@ static int jpegdec_batch(aej_ctx *ctx, const char *fn, const aej_jpegdec_desc *d
     std::vector<JdFile> files;
     JdBufSizes z;
     jpegdec_layout(descs_host, n, S, files, z, r);
-    if (z.grpb > 0 || z.grps[0] > 0 || z.grps[1] > 0 || z.grps[2] > 0) {      // aej_jpegdec_box_stats: from the descriptors and the windows alone
+    if (jpeg_any_box(z)) {                                   // aej_jpegdec_box_stats: from the descriptors and the windows alone
         long long total = 0, decoded = 0;
         for (int i = 0; i < n; i++) {
             const aej_jpegdec_desc &d = descs_host[i];
@@ -557,6 +546,18 @@ extern "C" int aej_test_jpeg_adobe_pixels_host(const uint8_t *samples4_host, int
         const int s[4] = { samples4_host[4 * i], samples4_host[4 * i + 1], samples4_host[4 * i + 2], samples4_host[4 * i + 3] };
         jd_adobe_pixel(colour, components == 4, s, out_host + i * components);
     }
+    return 0;
+}
+
+// the host twin of the chroma up-sampling rule (jd_up_chroma, jpegdec_core.h), for the tests: the rule's samples for the output pixels
+// [y0, y1) x [x0, x1), row after row
+extern "C" int aej_test_jpeg_upsample_host(const uint8_t *part_host, int64_t stride, int64_t off, int uh, int uv, int fancy, int wc, int hc,
+                                           int x0, int y0, int x1, int y1, uint8_t *out_host)
+{
+    if (!part_host || !out_host || (uh != 1 && uh != 2) || (uv != 1 && uv != 2) || (uh == 2 && uv == 2 && !fancy)) return AEJ_ERR_ARG;
+    if (wc < 1 || hc < 1 || x0 < 0 || x0 > x1 || x1 > uh * wc || y0 < 0 || y0 > y1 || y1 > uv * hc) return AEJ_ERR_ARG;
+    for (int y = y0; y < y1; y++)
+        for (int x = x0; x < x1; x++) *out_host++ = (uint8_t)jd_up_chroma(part_host, stride, off, uh, uv, fancy != 0, wc, hc, y, x);
     return 0;
 }
 

@@ -15,26 +15,24 @@
 //   k_jd_write      one thread per slot: the decode again, now storing coefficients and DC values (prefix + own differences); errors of
 //                   blocks the segment needs, and a segment that ends before its last block, go to the file's status
 //   k_jd_idct       one thread per real block: dequantise, islow IDCT, range limit -> sample planes
-//   k_jd_rgb        one thread per pixel: up-sampling (h2v2 / h2v1 fancy, replication when the chroma is <= 2 wide; h1v2 fancy for a
-//                   4:4:0 file, at any width) and YCbCr -> RGB
+//   k_jd_rgb        one thread per pixel: up-sampling (jd_chroma: the one rule of jpegdec_core.h, jd_up_chroma, at full size) and
+//                   YCbCr -> RGB
 //   k_jd_scaled     files decoded at scale 2, 4 or 8 (Pillow's draft()) in the place of the two above: one workgroup per run of kJdRun
 //                   MCUs of one MCU row -- reduced IDCTs into LDS, colour into LDS, then the run's output rows stored as whole dwords.
 //                   No sample planes: 4:2:0 chroma comes out of a twice-as-large IDCT at luma resolution, and the one neighbour sample
-//                   the h2v1 filter of a 4:2:2 file needs on either side comes from the chroma blocks of the two adjacent MCUs
+//                   jd_up_chroma reads for a 4:2:2 file on either side comes from the chroma blocks of the two adjacent MCUs
 //   k_jd_scaled_h1v2 the same for 4:4:0 files (luma 1 x 2), whose chroma IDCT stays at the luma block's size at every scale and is
 //                   up-sampled vertically: the neighbour rows the h1v2 filter needs come from the chroma blocks of the MCU rows above
 //                   and below the run (a vertical halo).  A kernel of its own, so that k_jd_scaled compiles as it did without it
 //   k_jd_luma       files that leave as their luma plane alone, [oh][ow] (libjpeg's out_color_space = JCS_GRAYSCALE; a one-component
 //                   file's samples), at scale 1, 2, 4 or 8, in the place of all of the above: k_jd_scaled's plan, luma blocks only
-//   k_jd_box        files of which a box is decoded (box= of the Python call), in the place of k_jd_idct / k_jd_rgb / k_jd_luma: one workgroup
-//                   per tile of the box -- IDCTs of the tile's luma blocks and of its chroma blocks plus a ring of neighbour blocks into
-//                   LDS, then jd_chroma / jd_rgb on the LDS planes, and only the box's pixels stored.  No sample planes.  In a call with
-//                   such a file k_jd_init / k_jd_sync / k_jd_write run as their <true> instantiation: a restart segment of a boxed file
-//                   that holds no MCU of the window's MCU rows is an idle slot to them, and only those rows' coefficients are stored
-//   k_jd_sbox       files of which a box of the SCALED image is decoded (scaled_box= of the Python call, the _sbox entries) at scale 2, 4 or 8,
-//                   in the place of k_jd_scaled / k_jd_scaled_h1v2 / k_jd_luma: k_jd_box's plan at m = 8 >> shift samples per block side, with
-//                   the reduced IDCTs and libjpeg's up-sampling rules at that scale.  The segment skip and the coefficient window of the
-//                   boxed files carry over unchanged (they work in MCUs)
+//   k_jd_sbox       files of which a box is decoded, in the place of every reconstruction kernel above: of the full-size image (box= of the
+//                   Python call, the _box entries; <0>) or of the image at scale 2, 4 or 8 (scaled_box=, the _sbox entries; <1..3>).  One
+//                   workgroup per tile of the box -- IDCTs, at m = 8 >> shift samples per block side, of the tile's luma blocks and of its
+//                   chroma blocks plus a ring of neighbour blocks into LDS, then jd_up_chroma / jd_rgb on the LDS planes, and only the
+//                   box's pixels stored.  No sample planes.  In a call with such a file k_jd_init / k_jd_sync / k_jd_write run as their
+//                   <true> instantiation: a restart segment of a boxed file that holds no MCU of the window's MCU rows is an idle slot
+//                   to them, and only those rows' coefficients are stored (both work in MCUs, whatever the scale)
 //   k_jd_init4 / k_jd_sync4 / k_jd_scan_slots4 / k_jd_write4   the slot kernels of a call that has a four-component (CMYK, YCCK) or RGB-coded
 //                   file (aej_jpegdec_batch_adobe), or a YCbCr file whose three components share one table pair (jd_four), for all of its files: a fourth DC sum and prefix per slot, a 4-bit block slot in the packed
 //                   state, component 3 under the tables of the file's aej_jpeg_adobe; k_jd_fix4 between two k_jd_scan_slots4 for the files
@@ -58,16 +56,50 @@ constexpr int kJdThreads = 256;
 constexpr int kJdScanThreads = 1024;
 constexpr int kJdRun = 64;                 // MCUs of one MCU row that a workgroup of k_jd_scaled reconstructs
 
-// index i of the last element with (base array member) <= t, over n files
-template <long long JdFile::*M>
-__device__ __forceinline__ int jd_find_file(const JdFile *f, int n, long long t)
+// index i of the last of n files with base(file) <= t
+template <class Base>
+__device__ __forceinline__ int jd_find_last(const JdFile *f, int n, long long t, Base base)
 {
     int lo = 0, hi = n - 1;
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
-        if (f[mid].*M <= t) lo = mid; else hi = mid - 1;
+        if (base(f[mid]) <= t) lo = mid; else hi = mid - 1;
     }
     return lo;
+}
+
+// the same where the base is a member
+template <long long JdFile::*M>
+__device__ __forceinline__ int jd_find_file(const JdFile *f, int n, long long t)
+{
+    return jd_find_last(f, n, t, [](const JdFile &F) { return F.*M; });
+}
+
+// the file whose workgroups contain `blockIdx.x`, in the grid of the kernel whose first workgroup of a file is M[k] (an array member)
+template <class A>
+__device__ __forceinline__ int jd_group_file(const JdFile *f, int n, A JdFile::*M, int k)
+{
+    return jd_find_last(f, n, (long long)blockIdx.x, [=](const JdFile &F) { return (F.*M)[k]; });
+}
+
+// Rows 0 .. nrows - 1 of nbytes bytes each leave LDS for global memory, row r to gp0 + r * pitch: whole dwords inside a row, single
+// bytes at its unaligned ends, so only the row's own bytes are written.  kPlaced: the row sits in LDS as it does in its dwords -- at
+// lds + r * stride + (its address & 3), lds and stride dword-aligned -- and a dword is one LDS read; else the row starts at
+// lds + r * stride, wherever that is, and a dword is put together from four bytes.
+template <bool kPlaced>
+__device__ __forceinline__ void jd_store_rows(unsigned char *gp0, int pitch, const unsigned char *lds, int stride, int nrows, int nbytes)
+{
+    const int nslots = (nbytes + 6) / 4;              // dwords a row can touch: up to 3 bytes of shift
+    for (int p = threadIdx.x; p < nrows * nslots; p += kJdThreads) {
+        const int r = p / nslots, k = p % nslots;
+        unsigned char *gp = gp0 + (long long)r * pitch;
+        const int a = (int)((uintptr_t)gp & 3), b0 = max(4 * k, a), b1 = min(4 * k + 4, a + nbytes);
+        const unsigned char *s = lds + r * stride - (kPlaced ? 0 : a);      // s[b]: the byte at place b of the row's dwords (read for a <= b < a + nbytes only)
+        if (b1 - b0 != 4) { for (int b = b0; b < b1; b++) gp[b - a] = s[b]; continue; }      // the ends of a row: its own bytes only
+        unsigned *g = reinterpret_cast<unsigned *>(gp + (4 * k - a));
+        if (kPlaced) *g = *reinterpret_cast<const unsigned *>(s + 4 * k);
+        else *g = (unsigned)s[4 * k] | ((unsigned)s[4 * k + 1] << 8) | ((unsigned)s[4 * k + 2] << 16) | ((unsigned)s[4 * k + 3] << 24);
+    }
 }
 
 __device__ __forceinline__ int jd_find_seg(const JdSeg *s, int n, long long t)      // last segment whose slot_base <= t
@@ -544,7 +576,7 @@ __global__ __launch_bounds__(kJdThreads) void k_jd_idct4(const JdFile *__restric
 }
 
 // kJdAdobePx consecutive pixels [r0, r1) of a file with kJdAdobe, kCh output channels: the samples of every plane up-sampled by
-// jd_chroma's rules (component 3 sampled as component 0 is read as it is), the colour model's rule, and the bytes stored -- a whole
+// jd_chroma (component 3 sampled as component 0 is read as it is), the colour model's rule, and the bytes stored -- a whole
 // group whose first byte is dword-aligned as kCh dwords, anything else byte by byte
 template <int kCh>
 __device__ __forceinline__ void jd_adobe_group(const JdFile &F, const aej_jpegdec_desc &d, int colour, bool full3, const unsigned char *pl,
@@ -590,11 +622,7 @@ __global__ __launch_bounds__(kJdThreads) void k_jd_adobe(const JdFile *__restric
                                                          const aej_jpeg_adobe *__restrict__ adobe, int n, const unsigned char *__restrict__ planes,
                                                          unsigned char *__restrict__ out)
 {
-    int lo = 0, hi = n - 1;                           // the last file whose first workgroup is <= blockIdx.x
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (files[mid].grpa_base <= (long long)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
+    const int lo = jd_find_file<&JdFile::grpa_base>(files, n, blockIdx.x);
     const JdFile &F = files[lo];
     const aej_jpegdec_desc &d = descs[lo];
     if (!(F.shift & kJdAdobe) || d.hs > 2 || d.vs > 2) return;      // never: the host gives these workgroups to such files alone
@@ -634,7 +662,9 @@ __global__ __launch_bounds__(kJdThreads) void k_jd_rgb(const JdFile *__restrict_
 // g - grp_base of its file: MCUs [g0, g0 + ng) of MCU row my.  m = 8 >> kShift samples per luma block side.
 // LDS: three sample planes of 2m rows x kJdRun * 2m columns (the widest run: two luma blocks per MCU side) and the run's RGB rows.
 // Bounds: block indices stay below the file's mcux * mcuy * blocks_per_mcu; LDS columns below ng * hs * m <= kCols for luma and
-// (ng + 2) * nc <= kCols for chroma; only bytes of pixels (y < oh, x < ow) of the file's own image are stored.
+// (ng + 2) * nc <= kCols for chroma -- jd_up_chroma reads chroma column j of the pixel's own MCU and, for a 4:2:2 file, j - 1 or j + 1
+// where the FILE has it: a column of MCUs [c0, c1), since a run's neighbour MCU is in them wherever the image has one; only bytes of
+// pixels (y < oh, x < ow) of the file's own image are stored.
 template <int kShift>
 __global__ __launch_bounds__(kJdThreads) void k_jd_scaled(const JdFile *__restrict__ files, const aej_jpegdec_desc *__restrict__ descs, int n,
                                                           const short *__restrict__ coef, unsigned char *__restrict__ out)
@@ -642,11 +672,7 @@ __global__ __launch_bounds__(kJdThreads) void k_jd_scaled(const JdFile *__restri
     constexpr int m = 8 >> kShift, kRows = 2 * m, kCols = kJdRun * 2 * m, kRgbStride = kCols * 3 + 4;
     __shared__ unsigned char sy[kRows * kCols], scb[kRows * kCols], scr[kRows * kCols];
     __shared__ __align__(4) unsigned char srgb[kRows * kRgbStride];
-    int lo = 0, hi = n - 1;                           // the last file whose first workgroup is <= blockIdx.x
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (files[mid].grp_base[kShift - 1] <= (long long)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
+    const int lo = jd_group_file(files, n, &JdFile::grp_base, kShift - 1);
     const JdFile &F = files[lo];
     const aej_jpegdec_desc &d = descs[lo];
     const int per_row = (d.mcux + kJdRun - 1) / kJdRun, g = (int)(blockIdx.x - F.grp_base[kShift - 1]);
@@ -654,8 +680,8 @@ __global__ __launch_bounds__(kJdThreads) void k_jd_scaled(const JdFile *__restri
     const bool color = d.ncomp == 3;
     const int hs = d.hs, vs = d.vs, nl = color ? hs * vs : 1, nc = jd_chroma_idct_size(hs, vs, m);
     const bool h2v1 = color && hs == 2 && vs == 1;    // the one layout whose chroma is still up-sampled
-    const int wc = (F.ow + 1) >> 1;                   // its real chroma width
-    const bool fancy = h2v1 && kShift < 3 && wc > 2;  // libjpeg: no fancy up-sampling beside a 1 x 1 IDCT, nor for <= 2 samples
+    const int uh = h2v1 ? 2 : 1, wc = (F.ow + 1) >> 1;      // its real chroma width
+    const bool fancy = h2v1 && kShift < 3 && wc > 2;  // jd_up_chroma: no fancy up-sampling beside a 1 x 1 IDCT, nor for <= 2 samples
     const int c0 = fancy && g0 > 0 ? g0 - 1 : g0, c1 = fancy && g0 + ng < d.mcux ? g0 + ng + 1 : g0 + ng;      // MCUs whose chroma is needed
     const int nY = ng * nl, nC = color ? (c1 - c0) * 2 : 0;
     const int bw = (d.width + 7) / 8, bh = (d.height + 7) / 8;
@@ -686,53 +712,33 @@ __global__ __launch_bounds__(kJdThreads) void k_jd_scaled(const JdFile *__restri
         unsigned char *o = srgb + r * kRgbStride + a + 3 * x;
         const int Y = sy[r * kCols + x];
         if (!color) { o[0] = o[1] = o[2] = (unsigned char)Y; continue; }
-        const unsigned char *rb = scb + r * kCols, *rr = scr + r * kCols;
-        int cb, cr;
-        if (h2v1) {
-            const int j = (x0 + x) >> 1, l = j - c0 * nc, ll = max(l - 1, 0), lr = min(l + 1, (c1 - c0) * nc - 1);
-            cb = fancy ? jd_h2v1(rb[l], rb[ll], rb[lr], x0 + x, j, wc) : rb[l];
-            cr = fancy ? jd_h2v1(rr[l], rr[ll], rr[lr], x0 + x, j, wc) : rr[l];
-        } else {
-            cb = rb[x]; cr = rr[x];
-        }
-        jd_rgb(Y, cb, cr, o);
+        // the file's chroma sample of column j is at column j - c0 * nc of the LDS rows, whose row r is the pixel's own (uv = 1)
+        jd_rgb(Y, jd_up_chroma(scb, kCols, c0 * nc, uh, 1, fancy, wc, 0, r, x0 + x), jd_up_chroma(scr, kCols, c0 * nc, uh, 1, fancy, wc, 0, r, x0 + x), o);
     }
     __syncthreads();
-    const int nslots = (nbytes + 6) / 4;              // dwords a row can touch: up to 3 bytes of shift
-    for (int p = threadIdx.x; p < nrows * nslots; p += kJdThreads) {
-        const int r = p / nslots, k = p % nslots;
-        unsigned char *gp = img + ((long long)(y0 + r) * F.ow + x0) * 3;
-        const int a = (int)((uintptr_t)gp & 3), b0 = max(4 * k, a), b1 = min(4 * k + 4, a + nbytes);
-        const unsigned char *s = srgb + r * kRgbStride;
-        if (b1 - b0 == 4) *reinterpret_cast<unsigned *>(gp + (4 * k - a)) = *reinterpret_cast<const unsigned *>(s + 4 * k);
-        else for (int b = b0; b < b1; b++) gp[b - a] = s[b];      // the ends of a row: its own bytes only
-    }
+    jd_store_rows<true>(img + ((long long)y0 * F.ow + x0) * 3, F.ow * 3, srgb, kRgbStride, nrows, nbytes);
 }
 
 // Scaled reconstruction of three-component files whose luma is sampled 1 x 2 (4:4:0): k_jd_scaled's plan -- workgroup `blockIdx.x` is run
 // g - grp440_base of its file, MCUs [g0, g0 + ng) of MCU row my -- with the MCU m columns by 2m rows of output.  jd_chroma_idct_size gives
-// this layout an m x m chroma IDCT at every scale, so the chroma is always up-sampled vertically: h1v2 fancy at scales 2 and 4
-// (jd_h1v2), replication beside the 1 x 1 IDCT of scale 8, as libjpeg does.  The filter reads the chroma row above the run's first and
+// this layout an m x m chroma IDCT at every scale, so the chroma is always up-sampled vertically (jd_up_chroma, uv = 2): h1v2 fancy at
+// scales 2 and 4, replication beside the 1 x 1 IDCT of scale 8.  The filter reads the chroma row above the run's first and
 // below its last: the vertical halo.  The chroma blocks of MCU rows my - 1 and my + 1, where the image has them, are reconstructed here
 // a second time (the horizontal halo of k_jd_scaled does the same with its two neighbour MCUs), whole, into row sets of their own.
 // LDS: luma 2m rows x kJdRun * m columns; per chroma plane three sets of m rows (above, own, below; one set of one row at scale 8);
 // the run's RGB rows.  Bounds: a neighbour MCU row is only addressed when 0 <= row < mcuy, so block indices stay below the file's
-// mcux * mcuy * 4; LDS rows of chroma stay in [m - 1, 2m] of 3m (far row of jd_h1v2_far is one off the run's own rows at most, and
+// mcux * mcuy * 4; LDS rows of chroma stay in [m - 1, 2m] of 3m (the neighbour row, jd_up_far, is one off the run's own rows at most, and
 // off them only where that MCU row exists); only bytes of pixels (y < oh, x < ow) of the file's own image are stored.
 template <int kShift>
 __global__ __launch_bounds__(kJdThreads) void k_jd_scaled_h1v2(const JdFile *__restrict__ files, const aej_jpegdec_desc *__restrict__ descs, int n,
                                                                const short *__restrict__ coef, unsigned char *__restrict__ out)
 {
     constexpr int m = 8 >> kShift, kCols = kJdRun * m, kRgbStride = kCols * 3 + 4;
-    constexpr bool kFancy = kShift < 3;               // libjpeg: no fancy up-sampling beside a 1 x 1 IDCT
+    constexpr bool kFancy = kShift < 3;               // no fancy up-sampling beside a 1 x 1 IDCT
     constexpr int kSets = kFancy ? 3 : 1;
     __shared__ unsigned char sy[2 * m * kCols], scb[kSets * m * kCols], scr[kSets * m * kCols];
     __shared__ __align__(4) unsigned char srgb[2 * m * kRgbStride];
-    int lo = 0, hi = n - 1;                           // the last file whose first workgroup is <= blockIdx.x
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (files[mid].grp440_base[kShift - 1] <= (long long)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
+    const int lo = jd_group_file(files, n, &JdFile::grp440_base, kShift - 1);
     const JdFile &F = files[lo];
     const aej_jpegdec_desc &d = descs[lo];
     const int per_row = (d.mcux + kJdRun - 1) / kJdRun, g = (int)(blockIdx.x - F.grp440_base[kShift - 1]);
@@ -762,30 +768,17 @@ __global__ __launch_bounds__(kJdThreads) void k_jd_scaled_h1v2(const JdFile *__r
     const int y0 = my * 2 * m, x0 = g0 * m;
     const int nrows = min(2 * m, F.oh - y0), ncols = min(ng * m, F.ow - x0), nbytes = ncols * 3;
     unsigned char *img = out + F.out_off;
+    // the file's chroma row i is row i - (first row of the sets) of the LDS rows: the sets start at the MCU row above the run's, or, the
+    // one set of scale 8, at the run's own.  No column is up-sampled, so the rule is given the run's columns as they lie in LDS
+    const int coff = (kFancy ? my - 1 : my) * m * kCols;
     for (int p = threadIdx.x; p < nrows * ncols; p += kJdThreads) {
         const int r = p / ncols, x = p % ncols;
         const int a = (int)((uintptr_t)(img + ((long long)(y0 + r) * F.ow + x0) * 3) & 3);      // the row sits in LDS as it does in its dwords
         unsigned char *o = srgb + r * kRgbStride + a + 3 * x;
-        int cb, cr;
-        if (kFancy) {
-            const int y = y0 + r, base = (my - 1) * m, lc = (y >> 1) - base, lf = jd_h1v2_far(y, hc) - base;      // rows of the three sets
-            cb = jd_h1v2(scb[lc * kCols + x], scb[lf * kCols + x], y);
-            cr = jd_h1v2(scr[lc * kCols + x], scr[lf * kCols + x], y);
-        } else {
-            cb = scb[x]; cr = scr[x];
-        }
-        jd_rgb(sy[r * kCols + x], cb, cr, o);
+        jd_rgb(sy[r * kCols + x], jd_up_chroma(scb, kCols, coff, 1, 2, kFancy, 0, hc, y0 + r, x), jd_up_chroma(scr, kCols, coff, 1, 2, kFancy, 0, hc, y0 + r, x), o);
     }
     __syncthreads();
-    const int nslots = (nbytes + 6) / 4;              // dwords a row can touch: up to 3 bytes of shift
-    for (int p = threadIdx.x; p < nrows * nslots; p += kJdThreads) {
-        const int r = p / nslots, k = p % nslots;
-        unsigned char *gp = img + ((long long)(y0 + r) * F.ow + x0) * 3;
-        const int a = (int)((uintptr_t)gp & 3), b0 = max(4 * k, a), b1 = min(4 * k + 4, a + nbytes);
-        const unsigned char *s = srgb + r * kRgbStride;
-        if (b1 - b0 == 4) *reinterpret_cast<unsigned *>(gp + (4 * k - a)) = *reinterpret_cast<const unsigned *>(s + 4 * k);
-        else for (int b = b0; b < b1; b++) gp[b - a] = s[b];      // the ends of a row: its own bytes only
-    }
+    jd_store_rows<true>(img + ((long long)y0 * F.ow + x0) * 3, F.ow * 3, srgb, kRgbStride, nrows, nbytes);
 }
 
 // Luma-only reconstruction, coefficients -> [oh][ow] in one kernel, at every scale 1 << kShift (0: full size) and for every layout: the
@@ -800,11 +793,7 @@ __global__ __launch_bounds__(kJdThreads) void k_jd_luma(const JdFile *__restrict
 {
     constexpr int m = 8 >> kShift, kRows = 2 * m, kCols = kJdRun * 2 * m;
     __shared__ unsigned char sy[kRows * kCols];
-    int lo = 0, hi = n - 1;                           // the last file whose first workgroup is <= blockIdx.x
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (files[mid].grpl_base[kShift] <= (long long)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
+    const int lo = jd_group_file(files, n, &JdFile::grpl_base, kShift);
     const JdFile &F = files[lo];
     const aej_jpegdec_desc &d = descs[lo];
     const int per_row = (d.mcux + kJdRun - 1) / kJdRun, g = (int)(blockIdx.x - F.grpl_base[kShift]);
@@ -824,104 +813,17 @@ __global__ __launch_bounds__(kJdThreads) void k_jd_luma(const JdFile *__restrict
     const int y0 = my * vs * m, x0 = g0 * hs * m;
     const int nrows = min(vs * m, F.oh - y0), nbytes = min(ng * hs * m, F.ow - x0);
     unsigned char *img = out + F.out_off;
-    const int nslots = (nbytes + 6) / 4;              // dwords a row can touch: up to 3 bytes of shift
-    for (int p = threadIdx.x; p < nrows * nslots; p += kJdThreads) {
-        const int r = p / nslots, k = p % nslots;
-        unsigned char *gp = img + (long long)(y0 + r) * F.ow + x0;
-        const int a = (int)((uintptr_t)gp & 3), b0 = max(4 * k, a), b1 = min(4 * k + 4, a + nbytes);
-        const unsigned char *s = sy + r * kCols - a;  // s[b]: the byte at place b of the row's dwords (read for a <= b < a + nbytes only)
-        if (b1 - b0 == 4)
-            *reinterpret_cast<unsigned *>(gp + (4 * k - a)) = (unsigned)s[4 * k] | ((unsigned)s[4 * k + 1] << 8) | ((unsigned)s[4 * k + 2] << 16) |
-                                                              ((unsigned)s[4 * k + 3] << 24);
-        else for (int b = b0; b < b1; b++) gp[b - a] = s[b];      // the ends of a row: its own bytes only
-    }
-}
-
-// Boxed reconstruction, coefficients -> the box's pixels in one kernel, for every layout (4:4:4, 4:2:2, 4:2:0, 4:4:0, one component) and
-// both outputs: RGB (a one-component file: R = G = B), or the luma plane alone where the file's shift carries kJdLuma.  Workgroup
-// `blockIdx.x` is tile g - grpb_base of its file: tiles of kJdBoxW x kJdBoxH pixels -- TX x TY whole MCUs -- in row-major order over the
-// window win = (mx0, my0, mx1, my1), the grid anchored at the window's origin.  The tile's luma blocks go through the 8 x 8 IDCT into
-// sy; its chroma blocks go into scb / scr together with a ring of one MCU on every side that jd_chroma up-samples across (columns
-// when hs == 2 and the file's chroma is more than 2 wide, rows when vs == 2 and the chroma is not replicated), the ring clipped to the
-// window: by jd_box_window every sample a pixel of the box reads lies in the window, so the clip drops nothing that is read.  The
-// pixels of the tile that lie in the box then run jd_box_chroma -- jd_chroma's arithmetic, indexed so that the FILE's sample (row,
-// column) addresses the LDS plane, hence the file's own edge rules -- and jd_rgb, and are stored.  Every return in front of the
-// barrier depends on the workgroup alone.
-// LDS: three planes of kJdBoxH rows x kJdBoxW columns, 12 KiB.  The chroma plane holds (TY + 2) x (TX + 2) blocks at most where a
-// direction is up-sampled -- TX = 8 (80 columns), TY = 2 (32 rows) there -- and TY x TX blocks (32 x 128 at most) where it is not.
-// Bounds: MCU rows [cy0, cy1) and [ty0, ty1) lie in [win[1], win[3]), which the stored rows [row0, row0 + n_blocks / (mcux * bpm))
-// contain, and MCU columns in [win[0], win[2]) <= mcux, so block indices stay inside the file's stored coefficients; LDS rows and
-// columns stay below (cy1 - cy0) * 8 <= kJdBoxH and (cx1 - cx0) * 8 <= kJdBoxW; a store goes to pixel (y, x) with t <= y < b and
-// l <= x < r only, at out_off + ((y - t) * (r - l) + (x - l)) * channels, inside the box's image.
-__global__ __launch_bounds__(kJdThreads) void k_jd_box(const JdFile *__restrict__ files, const aej_jpegdec_desc *__restrict__ descs, int n,
-                                                       const short *__restrict__ coef, unsigned char *__restrict__ out)
-{
-    __shared__ unsigned char sy[kJdBoxH * kJdBoxW], scb[kJdBoxH * kJdBoxW], scr[kJdBoxH * kJdBoxW];
-    int lo = 0, hi = n - 1;                           // the last file whose first workgroup is <= blockIdx.x
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (files[mid].grpb_base <= (long long)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    const JdFile &F = files[lo];
-    const aej_jpegdec_desc &d = descs[lo];
-    if (!(F.shift & kJdBox)) return;                  // never: the host gives these workgroups to boxed files alone
-    const bool three = d.ncomp == 3, color = three && !(F.shift & kJdLuma);
-    const int hs = three ? d.hs : 1, vs = three ? d.vs : 1, nl = hs * vs, bpm = d.blocks_per_mcu;
-    if (hs > 2 || vs > 2) return;                     // never: the parsers admit these factors alone
-    const int TX = kJdBoxW / (8 * hs), TY = kJdBoxH / (8 * vs);
-    const int ntx = (F.win[2] - F.win[0] + TX - 1) / TX, g = (int)(blockIdx.x - F.grpb_base);
-    const int tx0 = F.win[0] + (g % ntx) * TX, ty0 = F.win[1] + (g / ntx) * TY;
-    if (ty0 >= F.win[3]) return;                      // never: the host gives a file ntx * nty workgroups
-    const int tx1 = min(tx0 + TX, F.win[2]), ty1 = min(ty0 + TY, F.win[3]);
-    const int wc = (d.width + hs - 1) / hs, hc = (d.height + vs - 1) / vs;
-    const int rx = color && hs == 2 && wc > 2, ry = color && vs == 2 && !(hs == 2 && wc <= 2);      // the ring, in MCUs
-    const int cx0 = max(tx0 - rx, F.win[0]), cx1 = min(tx1 + rx, F.win[2]), cy0 = max(ty0 - ry, F.win[1]), cy1 = min(ty1 + ry, F.win[3]);
-    const int nY = (tx1 - tx0) * (ty1 - ty0) * nl, ncx = cx1 - cx0, nC = color ? 2 * ncx * (cy1 - cy0) : 0;
-    for (int i = threadIdx.x; i < nY + nC; i += kJdThreads) {
-        int mx, my, k, c;
-        unsigned char *dst;
-        if (i < nY) {
-            const int mcu = i / nl, ky = (i % nl) / hs, kx = (i % nl) % hs;
-            my = ty0 + mcu / (tx1 - tx0); mx = tx0 + mcu % (tx1 - tx0); k = i % nl; c = 0;
-            dst = sy + (((my - ty0) * vs + ky) * 8) * kJdBoxW + ((mx - tx0) * hs + kx) * 8;
-        } else {
-            const int j = (i - nY) >> 1;
-            c = 1 + ((i - nY) & 1); k = nl + c - 1;
-            my = cy0 + j / ncx; mx = cx0 + j % ncx;
-            dst = (c == 1 ? scb : scr) + ((my - cy0) * 8) * kJdBoxW + (mx - cx0) * 8;
-        }
-        const short *cf = coef + (F.blk_base + ((long long)(my - F.row0) * d.mcux + mx) * bpm + k) * 64;
-        jd_idct_block(cf, d.qt[c], dst, kJdBoxW);         // inlined, as in k_jd_idct and k_jd_luma<0>: 164 VGPRs, occupancy 3; through jd_idct_block_call
-                                                          // 248, occupancy 2, and k_jd_scaled<1>, which shares that function, no longer compiles as it did
-    }
-    __syncthreads();
-    const int l = F.box[0], t = F.box[1], bw = F.box[2] - l;
-    const int px0 = max(l, tx0 * 8 * hs), px1 = min(F.box[2], tx1 * 8 * hs), py0 = max(t, ty0 * 8 * vs), py1 = min(F.box[3], ty1 * 8 * vs);
-    const int ncols = px1 - px0, npx = ncols > 0 && py1 > py0 ? ncols * (py1 - py0) : 0;
-    unsigned char *img = out + F.out_off;
-    // the file's chroma sample (row, column) is at pcb[row * kJdBoxW + column]: only formed for rows and columns of [cy0, cy1) x [cx0, cx1)
-    const long long coff = (long long)cy0 * 8 * kJdBoxW + cx0 * 8;
-    for (int p = threadIdx.x; p < npx; p += kJdThreads) {
-        const int y = py0 + p / ncols, x = px0 + p % ncols;
-        const int Y = sy[(y - ty0 * 8 * vs) * kJdBoxW + (x - tx0 * 8 * hs)];
-        const long long o = (long long)(y - t) * bw + (x - l);
-        if (!color) {
-            if (F.shift & kJdLuma) img[o] = (unsigned char)Y;
-            else { unsigned char *q = img + o * 3; q[0] = q[1] = q[2] = (unsigned char)Y; }
-            continue;
-        }
-        jd_rgb(Y, jd_box_chroma(scb, coff, hs, vs, wc, hc, y, x), jd_box_chroma(scr, coff, hs, vs, wc, hc, y, x), img + o * 3);
-    }
+    jd_store_rows<false>(img + (long long)y0 * F.ow + x0, F.ow, sy, kCols, nrows, nbytes);
 }
 
 // The 8 x 8 block behind a call, for k_jd_sbox<1> alone (the 2m x 2m chroma IDCT of a 4:2:0 file at scale 2): a function of its own, not
-// jd_idct_block_call, because sharing that one changes how k_jd_scaled<1> compiles (the trap k_jd_luma<0> and k_jd_box met)
+// jd_idct_block_call, because sharing that one changes how k_jd_scaled<1> compiles (the trap k_jd_luma<0> met)
 __device__ __attribute__((noinline)) void jd_idct_block_sbox(const short *c, const uint16_t *qt, unsigned char *dst)
 {
     jd_idct_block(c, qt, dst, kJdBoxW);
 }
 
-// one block at IDCT size kN (1, 2, 4 or 8) into an LDS plane of k_jd_sbox, kJdBoxW samples a row
+// one block at IDCT size kN (1, 2, 4 or 8) into an LDS plane of k_jd_sbox<1..3>, kJdBoxW samples a row
 template <int kN>
 __device__ __forceinline__ void jd_sbox_idct(const short *c, const uint16_t *qt, unsigned char *dst)
 {
@@ -931,55 +833,55 @@ __device__ __forceinline__ void jd_sbox_idct(const short *c, const uint16_t *qt,
     else dst[0] = jd_range_limit(jd_descale((long long)((int)c[0] * (int)qt[0]), 3));
 }
 
-// Boxed reconstruction at scale 1 << kShift (kShift 1, 2, 3), coefficients -> the pixels of a box of the SCALED image in one kernel, for
-// every layout and both outputs, as k_jd_box does at full size.  m = 8 >> kShift samples per luma block side, so an MCU covers
-// hs * m x vs * m scaled pixels.  Workgroup `blockIdx.x` is tile g - grps_base[kShift - 1] of its file: tiles of kJdBoxW x kJdBoxH
-// scaled pixels -- TX = 128 / (hs * m) by TY = 32 / (vs * m) whole MCUs, for hs, vs in 1, 2 and m in 4, 2, 1 -- in row-major order over
-// the window win = (mx0, my0, mx1, my1) of jd_sbox_window, the grid anchored at the window's origin.  The tile's luma blocks go through
-// the m x m IDCT into sy; its chroma blocks go at nc = jd_chroma_idct_size(hs, vs, m) into scb / scr: 2m for 4:2:0 (the chroma comes
-// out at luma resolution), m otherwise, and then with a ring of one MCU on either side in the one direction libjpeg up-samples at that
-// scale -- columns for 4:2:2 at scales 2 and 4 when the scaled chroma is more than 2 wide (h2v1 fancy), rows for 4:4:0 at scales 2 and 4
-// (h1v2 fancy); replication (scale 8, narrow 4:2:2) has no ring -- the ring clipped to the window: by jd_sbox_window every sample a
-// pixel of the box reads lies in the window.  The pixels of the tile that lie in the box then run jd_sbox_chroma and jd_rgb (or leave
-// as luma where the file's shift carries kJdLuma; a one-component file: R = G = B) and are stored, byte by byte: a box's rows start at
-// any byte.  Every return in front of the barrier depends on the workgroup alone.  At scale 8 a tile is up to 4096 one-coefficient luma
-// blocks, so the IDCT loop makes several passes per thread.
-// LDS: three planes of kJdBoxH rows x kJdBoxW columns, 12 KiB.  Luma: TY * vs * m = 32 rows, TX * hs * m = 128 columns.  Chroma:
-// 4:4:4 / grey and 4:2:0 TY * nc = 32 rows x TX * nc = 128 columns; 4:2:2 32 rows x (TX + 2) * m = 64 + 2m <= 72 columns; 4:4:0
-// (TY + 2) * m = 16 + 2m <= 24 rows x 128 columns.
+// Boxed reconstruction at scale 1 << kShift (kShift 0: full size), coefficients -> the pixels of a box of the image at that scale in one
+// kernel, for every layout (4:4:4, 4:2:2, 4:2:0, 4:4:0, one component) and both outputs: RGB (a one-component file: R = G = B), or the
+// luma plane alone where the file's shift carries kJdLuma.  m = 8 >> kShift samples per luma block side, so an MCU covers hs * m x vs * m
+// pixels.  Workgroup `blockIdx.x` is tile g - grps_base[kShift] of its file: tiles of kJdBoxW x kJdBoxH pixels -- TX = 128 / (hs * m) by
+// TY = 32 / (vs * m) whole MCUs, for hs, vs in 1, 2 and m in 8, 4, 2, 1 -- in row-major order over the window win = (mx0, my0, mx1, my1)
+// of jd_sbox_window, the grid anchored at the window's origin.  The tile's luma blocks go through the m x m IDCT into sy; its chroma
+// blocks go at nc (jd_up_plan: 2m for 4:2:0 at a scale, where the chroma comes out at luma resolution; m otherwise) into scb / scr,
+// with a ring of one MCU on either side in every direction that is still up-sampled by 2 and not replicated (jd_up_chroma: columns where
+// uh = 2, rows where uv = 2, neither beside a 1 x 1 IDCT nor where uh = 2 meets a plane at most two samples wide), the ring clipped to the
+// window: by jd_sbox_window every sample a pixel of the box reads lies in the window, so the clip drops nothing that is read.  The
+// pixels of the tile that lie in the box then run jd_up_chroma -- indexed so that the FILE's sample (row, column) addresses the LDS
+// plane, hence the file's own edge rules -- and jd_rgb, and are stored, byte by byte: a box's rows start at any byte.  Every return in
+// front of the barrier depends on the workgroup alone.  At scale 8 a tile is up to 4096 one-coefficient luma blocks, so the IDCT loop
+// makes several passes per thread.  The 8 x 8 IDCT of kShift 0 is inlined, as in k_jd_idct and k_jd_luma<0>: 164 VGPRs, occupancy 3;
+// through jd_idct_block_call 248, occupancy 2, and k_jd_scaled<1>, which shares that function, no longer compiles as it did.
+// LDS: three planes of kJdBoxH rows x kJdBoxW columns, 12 KiB.  Luma: TY * vs * m = 32 rows, TX * hs * m = 128 columns.  Chroma, in
+// samples: (TY + 2 ry) * nc rows x (TX + 2 rx) * nc columns with rx, ry in 0, 1 the ring, and nc = hs * m / uh = vs * m / uv, so
+// TX * nc = 128 / uh and TY * nc = 32 / uv.  No ring (uh = uv = 1, or replication): at most 32 x 128.  uh = 2: 64 + 2 nc <= 80 columns;
+// uv = 2: 16 + 2 nc <= 32 rows (nc <= 8).
 // Bounds: MCU rows [cy0, cy1) and [ty0, ty1) lie in [win[1], win[3]), which the stored rows [row0, row0 + n_blocks / (mcux * bpm))
 // contain, and MCU columns in [win[0], win[2]) <= mcux, so block indices stay inside the file's stored coefficients; LDS rows and
-// columns stay below the figures above; a store goes to scaled pixel (y, x) with t <= y < b and l <= x < r only, at
-// out_off + ((y - t) * (r - l) + (x - l)) * channels, inside the box's image.
+// columns stay below (cy1 - cy0) * nc and (cx1 - cx0) * nc, the figures above; jd_up_chroma reads samples of MCUs [cy0, cy1) x
+// [cx0, cx1) only (the pixel's own MCU and, through the ring, the clamped neighbour's, which the window holds); a store goes to pixel
+// (y, x) with t <= y < b and l <= x < r only, at out_off + ((y - t) * (r - l) + (x - l)) * channels, inside the box's image.
 template <int kShift>
 __global__ __launch_bounds__(kJdThreads) void k_jd_sbox(const JdFile *__restrict__ files, const aej_jpegdec_desc *__restrict__ descs, int n,
                                                         const short *__restrict__ coef, unsigned char *__restrict__ out)
 {
     constexpr int m = 8 >> kShift;
     __shared__ unsigned char sy[kJdBoxH * kJdBoxW], scb[kJdBoxH * kJdBoxW], scr[kJdBoxH * kJdBoxW];
-    int lo = 0, hi = n - 1;                           // the last file whose first workgroup is <= blockIdx.x
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (files[mid].grps_base[kShift - 1] <= (long long)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
+    const int lo = jd_group_file(files, n, &JdFile::grps_base, kShift);
     const JdFile &F = files[lo];
     const aej_jpegdec_desc &d = descs[lo];
-    if (!(F.shift & kJdSbox) || (F.shift & (kJdLuma - 1)) != kShift) return;      // never: the host gives these workgroups to such files alone
+    if (!(F.shift & kJdBox) || (F.shift & (kJdLuma - 1)) != kShift) return;      // never: the host gives these workgroups to such files alone
     const bool three = d.ncomp == 3, color = three && !(F.shift & kJdLuma);
     const int hs = three ? d.hs : 1, vs = three ? d.vs : 1, nl = hs * vs, bpm = d.blocks_per_mcu;
     if (hs > 2 || vs > 2) return;                     // never: the parsers admit these factors alone
     const int TX = kJdBoxW / (hs * m), TY = kJdBoxH / (vs * m);
-    const int ntx = (F.win[2] - F.win[0] + TX - 1) / TX, g = (int)(blockIdx.x - F.grps_base[kShift - 1]);
+    const int ntx = (F.win[2] - F.win[0] + TX - 1) / TX, g = (int)(blockIdx.x - F.grps_base[kShift]);
     const int tx0 = F.win[0] + (g % ntx) * TX, ty0 = F.win[1] + (g / ntx) * TY;
     if (ty0 >= F.win[3]) return;                      // never: the host gives a file ntx * nty workgroups
     const int tx1 = min(tx0 + TX, F.win[2]), ty1 = min(ty0 + TY, F.win[3]);
-    const bool wide = hs == 2 && vs == 2;             // 4:2:0: the chroma IDCT is 2m
-    const int nc = wide ? 2 * m : m;                  // jd_chroma_idct_size(hs, vs, m) for these factors
-    const int sw = (d.width + (1 << kShift) - 1) >> kShift, sh = (d.height + (1 << kShift) - 1) >> kShift;      // the scaled image
-    const int wc = (sw + 1) >> 1, hc = (sh + 1) >> 1; // the real chroma width (4:2:2) and height (4:4:0) at this scale
-    const bool h2v1 = color && hs == 2 && vs == 1, h1v2 = color && hs == 1 && vs == 2;
-    const bool fancy = kShift < 3 && ((h2v1 && wc > 2) || h1v2);      // libjpeg: no fancy up-sampling beside a 1 x 1 IDCT, nor for <= 2 samples a row
-    const int rx = h2v1 && fancy, ry = h1v2 && fancy; // the ring, in MCUs
+    const bool wide = kShift > 0 && hs == 2 && vs == 2;      // 4:2:0 at a scale: the chroma IDCT is 2m
+    const int nc = wide ? 2 * m : m, uh = wide ? 1 : hs, uv = wide ? 1 : vs;      // jd_up_plan for these factors
+    const int sw = (d.width + (1 << kShift) - 1) >> kShift, sh = (d.height + (1 << kShift) - 1) >> kShift;      // the image at this scale
+    const int wc = uh == 2 ? (sw + 1) >> 1 : sw, hc = uv == 2 ? (sh + 1) >> 1 : sh;
+    constexpr bool fancy = kShift < 3;                // no fancy up-sampling beside a 1 x 1 IDCT
+    const bool ring = color && !jd_up_replicates(uh, fancy, wc);
+    const int rx = ring && uh == 2, ry = ring && uv == 2;      // the ring, in MCUs
     const int cx0 = max(tx0 - rx, F.win[0]), cx1 = min(tx1 + rx, F.win[2]), cy0 = max(ty0 - ry, F.win[1]), cy1 = min(ty1 + ry, F.win[3]);
     const int ntw = tx1 - tx0, nY = ntw * (ty1 - ty0) * nl, ncx = cx1 - cx0, nC = color ? 2 * ncx * (cy1 - cy0) : 0;
     for (int i = threadIdx.x; i < nY + nC; i += kJdThreads) {
@@ -996,7 +898,8 @@ __global__ __launch_bounds__(kJdThreads) void k_jd_sbox(const JdFile *__restrict
             dst = (c == 1 ? scb : scr) + ((my - cy0) * nc) * kJdBoxW + (mx - cx0) * nc;
         }
         const short *cf = coef + (F.blk_base + ((long long)(my - F.row0) * d.mcux + mx) * bpm + k) * 64;
-        if (c != 0 && wide) jd_sbox_idct<2 * m>(cf, d.qt[c], dst);
+        if constexpr (kShift == 0) jd_idct_block(cf, d.qt[c], dst, kJdBoxW);
+        else if (c != 0 && wide) jd_sbox_idct<2 * m>(cf, d.qt[c], dst);
         else jd_sbox_idct<m>(cf, d.qt[c], dst);
     }
     __syncthreads();
@@ -1004,7 +907,7 @@ __global__ __launch_bounds__(kJdThreads) void k_jd_sbox(const JdFile *__restrict
     const int px0 = max(l, tx0 * hs * m), px1 = min(F.box[2], tx1 * hs * m), py0 = max(t, ty0 * vs * m), py1 = min(F.box[3], ty1 * vs * m);
     const int ncols = px1 - px0, npx = ncols > 0 && py1 > py0 ? ncols * (py1 - py0) : 0;
     unsigned char *img = out + F.out_off;
-    // the file's scaled chroma sample (row, column) is at pcb[row * kJdBoxW + column]: only formed for rows and columns of [cy0, cy1) x [cx0, cx1)
+    // the file's chroma sample (row, column) is at scb[row * kJdBoxW + column - coff]: only formed for rows and columns of [cy0, cy1) x [cx0, cx1)
     const long long coff = (long long)cy0 * nc * kJdBoxW + cx0 * nc;
     for (int p = threadIdx.x; p < npx; p += kJdThreads) {
         const int y = py0 + p / ncols, x = px0 + p % ncols;
@@ -1015,7 +918,7 @@ __global__ __launch_bounds__(kJdThreads) void k_jd_sbox(const JdFile *__restrict
             else { unsigned char *q = img + o * 3; q[0] = q[1] = q[2] = (unsigned char)Y; }
             continue;
         }
-        jd_rgb(Y, jd_sbox_chroma(scb, coff, h2v1, h1v2, fancy, wc, hc, y, x), jd_sbox_chroma(scr, coff, h2v1, h1v2, fancy, wc, hc, y, x), img + o * 3);
+        jd_rgb(Y, jd_up_chroma(scb, kJdBoxW, coff, uh, uv, fancy, wc, hc, y, x), jd_up_chroma(scr, kJdBoxW, coff, uh, uv, fancy, wc, hc, y, x), img + o * 3);
     }
 }
 
@@ -1051,15 +954,14 @@ void jpeg_recon_layout(const aej_jpegdec_desc &d, int shift, JdFile &F, JdBufSiz
 {
     // a box: of the full-size image (the callers refuse one at another scale), or -- kJdSbox in shift, set by the _sbox entries for a box
     // that is not the whole scaled image -- of the image at scale 2, 4 or 8
-    const bool luma = (shift & kJdLuma) != 0, sbox = (shift & kJdSbox) != 0, boxed = sbox || ((shift & (kJdLuma - 1)) == 0 && !jpeg_box_whole(d, box));
+    const bool luma = (shift & kJdLuma) != 0, boxed = (shift & kJdSbox) != 0 || ((shift & (kJdLuma - 1)) == 0 && !jpeg_box_whole(d, box));
     F.blk_base = z.blocks;
     F.n_blocks = (long long)d.mcux * d.mcuy * d.blocks_per_mcu;
     F.row0 = 0;
-    F.grpb_base = z.grpb;
-    for (int s = 0; s < 3; s++) F.grps_base[s] = z.grps[s];
+    for (int s = 0; s < 4; s++) F.grps_base[s] = z.grps[s];
     if (boxed) {
         for (int v = 0; v < 4; v++) F.box[v] = box[v];
-        jd_sbox_window(d.width, d.height, d.hs, d.vs, d.ncomp, luma, shift & (kJdLuma - 1), box, F.win);      // shift 0: jd_box_window
+        jd_sbox_window(d.width, d.height, d.hs, d.vs, d.ncomp, luma, shift & (kJdLuma - 1), box, F.win);
         if (window_coef) {                            // the window's MCU rows alone, at full width
             F.row0 = F.win[1];
             F.n_blocks = (long long)d.mcux * (F.win[3] - F.win[1]) * d.blocks_per_mcu;
@@ -1085,13 +987,13 @@ void jpeg_recon_layout(const aej_jpegdec_desc &d, int shift, JdFile &F, JdBufSiz
         z.grpa += (groups + kJdThreads - 1) / kJdThreads;
         return;
     }
-    if (boxed) {                                      // no sample planes, no pixels of k_jd_rgb's, no workgroups but k_jd_box's
+    if (boxed) {                                      // no sample planes, no pixels of k_jd_rgb's, no workgroups but k_jd_sbox<shift>'s
         const int m = 8 >> shift;                     // samples per luma block side: 8, or with kJdSbox 4, 2, 1
         const int hs = d.ncomp == 3 ? d.hs : 1, vs = d.ncomp == 3 ? d.vs : 1, TX = kJdBoxW / (m * hs), TY = kJdBoxH / (m * vs);
         F.shift |= kJdBox;
         F.ow = box[2] - box[0]; F.oh = box[3] - box[1];
         F.pw0 = F.ph0 = F.pw1 = F.ph1 = 0;
-        (sbox ? z.grps[shift - 1] : z.grpb) += (long long)((F.win[2] - F.win[0] + TX - 1) / TX) * ((F.win[3] - F.win[1] + TY - 1) / TY);
+        z.grps[shift] += (long long)((F.win[2] - F.win[0] + TX - 1) / TX) * ((F.win[3] - F.win[1] + TY - 1) / TY);
         return;
     }
     if (luma) {                                       // at every scale: no sample planes, no pixels of k_jd_rgb's, workgroups of k_jd_luma<shift>
@@ -1160,8 +1062,6 @@ unsigned long long jpegdec_carve(void *base, int n, const JdBufSizes &z, JdBufs 
 }
 
 static unsigned jd_grid(long long n) { return (unsigned)((n + kJdThreads - 1) / kJdThreads); }
-// a call with a boxed file, at full size or at a scale: the <true> slot kernels
-static bool jd_any_box(const JdBufSizes &z) { return z.grpb > 0 || z.grps[0] > 0 || z.grps[1] > 0 || z.grps[2] > 0; }
 
 // everything up to the first read-back: upload, un-stuffing, segments, first guesses
 hipError_t launch_jpegdec_begin(hipStream_t st, int n, const JdBufSizes &z, const JdBufs &w, const void *blob_host, unsigned long long blob_bytes,
@@ -1174,7 +1074,7 @@ hipError_t launch_jpegdec_begin(hipStream_t st, int n, const JdBufSizes &z, cons
         hipLaunchKernelGGL(k_jd_init4, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.slots, w.segs, w.clean, w.sl, S,
                            w.last_change, w.adobe);
     } else {
-        hipLaunchKernelGGL(jd_any_box(z) ? k_jd_init<true> : k_jd_init<false>, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n,
+        hipLaunchKernelGGL(jpeg_any_box(z) ? k_jd_init<true> : k_jd_init<false>, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n,
                            z.slots, w.segs, w.clean, w.sl, S, w.last_change);
     }
     return hipGetLastError();
@@ -1202,7 +1102,7 @@ hipError_t launch_jpegdec_sync(hipStream_t st, int n, const JdBufSizes &z, const
             hipLaunchKernelGGL(k_jd_sync4, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.slots, w.segs, w.clean, w.sl, S, r,
                                w.last_change, w.adobe);
         else
-            hipLaunchKernelGGL(jd_any_box(z) ? k_jd_sync<true> : k_jd_sync<false>, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n,
+            hipLaunchKernelGGL(jpeg_any_box(z) ? k_jd_sync<true> : k_jd_sync<false>, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n,
                                z.slots, w.segs, w.clean, w.sl, S, r, w.last_change);
     }
     return hipGetLastError();
@@ -1224,7 +1124,7 @@ hipError_t launch_jpegdec_write(hipStream_t st, int n, const JdBufSizes &z, cons
         return hipGetLastError();
     }
     hipLaunchKernelGGL(k_jd_scan_slots, dim3(n), dim3(kJdScanThreads), 0, st, w.files, w.sl);
-    hipLaunchKernelGGL(jd_any_box(z) ? k_jd_write<true> : k_jd_write<false>, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.slots,
+    hipLaunchKernelGGL(jpeg_any_box(z) ? k_jd_write<true> : k_jd_write<false>, dim3(jd_grid(z.slots)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.slots,
                        w.segs, w.clean, w.sl, S, w.coef, status);
     return hipGetLastError();
 }
@@ -1251,10 +1151,10 @@ static hipError_t launch_jpegdec_recon_scaled(hipStream_t st, int n, const JdBuf
     if (z.grpl[1] > 0) hipLaunchKernelGGL(k_jd_luma<1>, dim3((unsigned)z.grpl[1]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
     if (z.grpl[2] > 0) hipLaunchKernelGGL(k_jd_luma<2>, dim3((unsigned)z.grpl[2]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
     if (z.grpl[3] > 0) hipLaunchKernelGGL(k_jd_luma<3>, dim3((unsigned)z.grpl[3]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
-    if (z.grpb > 0) hipLaunchKernelGGL(k_jd_box, dim3((unsigned)z.grpb), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
-    if (z.grps[0] > 0) hipLaunchKernelGGL(k_jd_sbox<1>, dim3((unsigned)z.grps[0]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
-    if (z.grps[1] > 0) hipLaunchKernelGGL(k_jd_sbox<2>, dim3((unsigned)z.grps[1]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
-    if (z.grps[2] > 0) hipLaunchKernelGGL(k_jd_sbox<3>, dim3((unsigned)z.grps[2]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
+    if (z.grps[0] > 0) hipLaunchKernelGGL(k_jd_sbox<0>, dim3((unsigned)z.grps[0]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
+    if (z.grps[1] > 0) hipLaunchKernelGGL(k_jd_sbox<1>, dim3((unsigned)z.grps[1]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
+    if (z.grps[2] > 0) hipLaunchKernelGGL(k_jd_sbox<2>, dim3((unsigned)z.grps[2]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
+    if (z.grps[3] > 0) hipLaunchKernelGGL(k_jd_sbox<3>, dim3((unsigned)z.grps[3]), dim3(kJdThreads), 0, st, w.files, w.descs, n, w.coef, out);
     if (z.grpa > 0) {                                 // the four-component and RGB-coded files: four sample planes, then their pixels
         hipLaunchKernelGGL(k_jd_idct4, dim3(jd_grid(z.blocks)), dim3(kJdThreads), 0, st, w.files, w.descs, n, z.blocks, w.coef, w.planes, w.adobe);
         hipLaunchKernelGGL(k_jd_adobe, dim3((unsigned)z.grpa), dim3(kJdThreads), 0, st, w.files, w.descs, w.adobe, n, w.planes, out);

@@ -13,13 +13,12 @@ namespace aej {
 constexpr int kJdChunk = 64;           // bytes per un-stuffing chunk
 constexpr int kJdSyncBatch = 4;        // sync rounds launched between two read-backs of the "changed" word
 constexpr int kJdLuma = 4;             // added to log2 of a file's scale: the luma plane alone, [oh][ow] (JdFile::shift)
-constexpr int kJdBox = 8;              // added to a full-size file's shift: only a box of it is reconstructed (k_jd_box; JdFile::box, ::win)
+constexpr int kJdBox = 8;              // added to a file's shift: only a box of it is reconstructed (k_jd_sbox; JdFile::box, ::win)
 constexpr int kJdAdobe = 16;           // a four-component or RGB-coded file (aej_jpeg_adobe::colour): k_jd_idct<true> and k_jd_adobe alone reconstruct it
 constexpr int kJdCmyk = 32;            // with kJdAdobe: the image leaves with four channels (Pillow's mode "CMYK"), not as RGB
 constexpr int kJdAdobePx = 4;          // pixels one thread of k_jd_adobe reconstructs: 12 or 16 output bytes, whole dwords
-constexpr int kJdBoxW = 128, kJdBoxH = 32;      // pixels of one tile of k_jd_box: a whole number of MCUs of every layout
-constexpr int kJdSbox = 64;            // with kJdBox, on a file decoded at scale 2, 4 or 8: the box is in pixels of the scaled image (k_jd_sbox;
-                                       // tiles of kJdBoxW x kJdBoxH scaled pixels, a whole number of the scaled MCUs of every layout too)
+constexpr int kJdBoxW = 128, kJdBoxH = 32;      // pixels of one tile of k_jd_sbox: a whole number of MCUs of every layout at every scale
+constexpr int kJdSbox = 64;            // with kJdBox, on a file decoded at scale 2, 4 or 8: the box is in pixels of the scaled image
 
 // per-file layout of one aej_jpegdec_batch (host-computed, uploaded with the descriptors)
 struct JdFile {
@@ -39,14 +38,13 @@ struct JdFile {
     long long grp_base[3];             // [shift - 1]: first workgroup of the file in k_jd_scaled<shift>'s grid (kJdRun MCUs of one MCU row each)
     long long grp440_base[3];          // the same in k_jd_scaled_h1v2<shift>'s grid, where the three-component 1 x 2 (4:4:0) files go
     long long grpl_base[4];            // [log2 scale]: the same in k_jd_luma's grid, where the luma-only files of every layout go
-    long long grpb_base;               // first workgroup of the file in k_jd_box's grid (one tile of kJdBoxW x kJdBoxH pixels each)
     int box[4];                        // a boxed file (shift & kJdBox): left, top, right, bottom in pixels of the image; ow, oh are the box's
-    int win[4];                        // its MCU window mx0, my0, mx1, my1 (jd_box_window): the MCUs whose blocks the box's pixels read
+    int win[4];                        // its MCU window mx0, my0, mx1, my1 (jd_sbox_window): the MCUs whose blocks the box's pixels read
     int row0;                          // first MCU row whose coefficients are stored (win[1] for a baseline file, 0 for a progressive
                                        // one): block b of MCU (my, mx) is blk_base + ((my - row0) * mcux + mx) * blocks_per_mcu + b
     long long grpa_base;               // first workgroup of the file in k_jd_adobe's grid (shift & kJdAdobe)
-    long long grps_base[3];            // [log2 scale - 1]: first workgroup of the file in k_jd_sbox<log2 scale>'s grid (shift & kJdSbox): box and
-                                       // win are then in pixels and MCUs of the scaled image (jd_sbox_window), ow, oh the box's
+    long long grps_base[4];            // [log2 scale]: first workgroup of the file in k_jd_sbox<log2 scale>'s grid (shift & kJdBox; one tile of
+                                       // kJdBoxW x kJdBoxH pixels each): box and win are in pixels and MCUs of the image at that scale, ow, oh the box's
     int pw3, ph3;                      // such a file's fourth plane (whole MCUs; behind the three others), 0 x 0 for three components
     int uniform;                       // a baseline file of three or four components that all decode under one DC and one AC table (what
                                        // libjpeg writes for CMYK and RGB, and what optimised tables of a flat YCbCr picture can be): its bits
@@ -321,151 +319,105 @@ AEJ_HD inline int jd_chroma_idct_size(int hs, int vs, int m)
     return n;
 }
 
-// libjpeg's h2v1 "fancy" up-sampling of chroma sample j (of wc) with its neighbours, for output column x: jd_chroma's vs == 1 rule
-AEJ_HD inline int jd_h2v1(int cur, int left, int right, int x, int j, int wc)
+// ---- chroma up-sampling: libjpeg's rule, stated here once ----------------------------------------------------------------------------------
+// A chroma component comes out of its IDCT (jd_chroma_idct_size) at 1 / uh of the output's width and 1 / uv of its height, uh and uv in
+// 1, 2, and jdsample.c brings it to the output's size.  Along an axis with factor 1 the pixel reads the sample at its own place.  Along
+// one with factor 2, pixel x reads sample x >> 1, and
+//   plain replication   nothing else: beside a 1 x 1 IDCT (scale 8; `fancy` false -- jdmaster.c's use_merged_upsample / do_fancy test on
+//                       the IDCT size), and in both directions where a column is up-sampled over a plane at most two samples wide;
+//   "fancy"             3/4 of it and 1/4 of the neighbour the pixel lies nearer to -- x >> 1 - 1 for an even x, x >> 1 + 1 for an odd
+//                       one -- with bias 1 (even) or 2 (odd) before >> 2: h2v1 along a row, h1v2 down a column.  h2v2 runs the vertical
+//                       filter unrounded on both columns first (3 * near row + far row), then the horizontal one on those sums with bias
+//                       8 (even) or 7 (odd) before >> 4.
+// At the plane's edges the missing neighbour is the edge sample itself: (3 s + s + 1) >> 2 = (3 s + s + 2) >> 2 = s, which libjpeg writes
+// as special cases of the first and last column (h2v1, h2v2: s, (4 cs + 8) >> 4, (4 cs + 7) >> 4) and as the edge row standing in for
+// rows -1 and hc (h1v2, h2v2).  jd_up_far is that clamped neighbour, over the plane's REAL samples.
+
+// the neighbour sample that output coordinate x of an axis up-sampled by 2 reads beside sample x >> 1, of n real samples
+AEJ_HD inline int jd_up_far(int x, int n) { const int j = x >> 1; return (x & 1) ? (j + 1 < n ? j + 1 : n - 1) : (j > 0 ? j - 1 : 0); }
+
+// What is still to up-sample after the chroma IDCT of a file decoded at scale 1 << shift: m = 8 >> shift luma samples per block side, the
+// chroma IDCT size nc, the factors uh, uv that remain (2 x 2 luma at a scale: the chroma comes out of a 2m IDCT at luma resolution), fancy,
+// and the real sample counts wc x hc of the chroma plane at that scale.  hs, vs: the luma factors, 1 x 1 for a file without chroma.
+struct JdUp { int m, nc, uh, uv; bool fancy; int wc, hc; };
+AEJ_HD inline JdUp jd_up_plan(int width, int height, int hs, int vs, int shift)
 {
-    if ((x & 1) == 0) return j == 0 ? cur : (3 * cur + left + 1) >> 2;
-    return j == wc - 1 ? cur : (3 * cur + right + 2) >> 2;
+    JdUp u;
+    u.m = 8 >> shift;
+    u.nc = jd_chroma_idct_size(hs, vs, u.m);
+    u.uh = hs * u.m / u.nc; u.uv = vs * u.m / u.nc;
+    u.fancy = u.nc > 1;
+    u.wc = (((width + (1 << shift) - 1) >> shift) + u.uh - 1) / u.uh;
+    u.hc = (((height + (1 << shift) - 1) >> shift) + u.uv - 1) / u.uv;
+    return u;
+}
+// plain replication in both directions?
+AEJ_HD inline bool jd_up_replicates(int uh, bool fancy, int wc) { return !fancy || (uh == 2 && wc <= 2); }
+
+// The chroma sample of output pixel (y, x), from a plane or a part of one with row stride W in which the file's sample (row, column) is
+// p[row * W + column - off] (off: the index the part's first sample would have in the whole plane; 0 for a whole plane).  uh, uv, fancy,
+// wc, hc as above; uh = uv = 2 without fancy does not occur.  Index arithmetic, not row pointers: a row's first samples may lie before
+// the part.  Only the neighbour that the pixel's parity selects is read, a row clamped to the FILE's plane and a column not at all at
+// the FILE's edges: the other one may lie outside the part (the boxed kernel and the halos of the scaled kernels hold exactly what
+// jd_up_span says).  How the tests are spelt decides registers in k_jd_rgb: `fancy` first, on its own.
+AEJ_HD inline int jd_up_chroma(const unsigned char *p, long long W, long long off, int uh, int uv, bool fancy, int wc, int hc, int y, int x)
+{
+    if (!fancy) return p[(uv == 2 ? y >> 1 : y) * W + (uh == 2 ? x >> 1 : x) - off];
+    if (uh == 1) {
+        if (uv == 1) return p[y * W + x - off];
+        return (3 * p[(y >> 1) * W + x - off] + p[jd_up_far(y, hc) * W + x - off] + 1 + (y & 1)) >> 2;    // h1v2
+    }
+    const int j = x >> 1;
+    if (wc <= 2) return p[(uv == 2 ? y >> 1 : y) * W + j - off];
+    const int odd = x & 1, jn = odd ? j + 1 : j - 1;  // the nearer neighbour column
+    const bool edge = odd ? j == wc - 1 : j == 0;     // it does not exist: the sample stands in for it, and it is not read
+    if (uv == 1) {                                                                                        // h2v1
+        const long long r0 = y * W - off;
+        return edge ? p[r0 + j] : (3 * p[r0 + j] + p[r0 + jn] + 1 + odd) >> 2;
+    }
+    const long long r0 = (y >> 1) * W - off, r1 = jd_up_far(y, hc) * W - off;                             // h2v2
+    const int cs = 3 * p[r0 + j] + p[r1 + j];
+    return (3 * cs + (edge ? cs : 3 * p[r0 + jn] + p[r1 + jn]) + 8 - odd) >> 4;
 }
 
-// libjpeg's h1v2 "fancy" up-sampling for output row y: `cur` is the sample of chroma row y >> 1, `far` that of the row above it (y even)
-// or below it (y odd), the edge rows standing in for rows -1 and hc.  No narrow-plane exception: jdsample.c has none for this layout.
-AEJ_HD inline int jd_h1v2(int cur, int far, int y) { return (3 * cur + far + ((y & 1) ? 2 : 1)) >> 2; }
-// the row `far` is: of hc chroma rows
-AEJ_HD inline int jd_h1v2_far(int y, int hc) { const int cy = y >> 1; return (y & 1) ? (cy + 1 < hc ? cy + 1 : hc - 1) : (cy > 0 ? cy - 1 : 0); }
-
-// chroma sample for output pixel (y, x) from a plane of wc x hc real samples (row stride `stride`); hs, vs: luma sampling factors
+// full size, a whole plane of wc x hc real samples (row stride `stride`); hs, vs: the luma sampling factors
 AEJ_HD inline int jd_chroma(const unsigned char *p, long long stride, int hs, int vs, int wc, int hc, int y, int x)
 {
-    if (hs == 1) {
-        if (vs == 1) return p[(long long)y * stride + x];                    // 4:4:4
-        return jd_h1v2(p[(long long)(y >> 1) * stride + x], p[(long long)jd_h1v2_far(y, hc) * stride + x], y);      // 4:4:0: h1v2 fancy
-    }
-    const int j = x >> 1;
-    if (wc <= 2) return p[(long long)(vs == 2 ? y >> 1 : y) * stride + j];  // plain replication
-    if (vs == 1) {                                                          // h2v1 fancy
-        const unsigned char *r = p + (long long)y * stride;
-        if ((x & 1) == 0) return j == 0 ? r[0] : (3 * r[j] + r[j - 1] + 1) >> 2;
-        return j == wc - 1 ? r[j] : (3 * r[j] + r[j + 1] + 2) >> 2;
-    }
-    const int cy = y >> 1, far = (y & 1) ? (cy + 1 < hc ? cy + 1 : hc - 1) : (cy > 0 ? cy - 1 : 0);   // h2v2 fancy
-    const unsigned char *n0 = p + (long long)cy * stride, *n1 = p + (long long)far * stride;
-    const int cs = 3 * n0[j] + n1[j];
-    if ((x & 1) == 0) return j == 0 ? (4 * cs + 8) >> 4 : (3 * cs + 3 * n0[j - 1] + n1[j - 1] + 8) >> 4;
-    return j == wc - 1 ? (4 * cs + 7) >> 4 : (3 * cs + 3 * n0[j + 1] + n1[j + 1] + 7) >> 4;
+    return jd_up_chroma(p, stride, 0, hs, vs, true, wc, hc, y, x);
 }
 
-// jd_chroma for k_jd_box: the same arithmetic on a part of the plane held in LDS, kJdBoxW samples a row, where the file's chroma
-// sample (row, column) is p[row * kJdBoxW + column - off] (off: the index the part's first sample would have in the whole plane)
-AEJ_HD inline int jd_box_chroma(const unsigned char *p, long long off, int hs, int vs, int wc, int hc, int y, int x)
+// the samples s0..s1 that output coordinates a..b of one axis read (factor u, n real samples): the indices are monotonic in the
+// coordinate, so the two ends decide
+AEJ_HD inline void jd_up_span(int a, int b, int u, bool rep, int n, int &s0, int &s1)
 {
-    const long long W = kJdBoxW;
-    if (hs == 1) {
-        if (vs == 1) return p[y * W + x - off];
-        return jd_h1v2(p[(y >> 1) * W + x - off], p[jd_h1v2_far(y, hc) * W + x - off], y);
-    }
-    const int j = x >> 1;
-    if (wc <= 2) return p[(vs == 2 ? y >> 1 : y) * W + j - off];
-    // index arithmetic, not pointers: a row's first samples of the whole plane may lie before the part.  Only the neighbour that
-    // the pixel's parity selects is read: the other one may lie outside the part.
-    const long long r0 = (vs == 2 ? y >> 1 : y) * W - off;
-    if (vs == 1) {
-        if ((x & 1) == 0) return j == 0 ? p[r0] : (3 * p[r0 + j] + p[r0 + j - 1] + 1) >> 2;
-        return j == wc - 1 ? p[r0 + j] : (3 * p[r0 + j] + p[r0 + j + 1] + 2) >> 2;
-    }
-    const long long r1 = jd_h1v2_far(y, hc) * W - off;
-    const int cs = 3 * p[r0 + j] + p[r1 + j];
-    if ((x & 1) == 0) return j == 0 ? (4 * cs + 8) >> 4 : (3 * cs + 3 * p[r0 + j - 1] + p[r1 + j - 1] + 8) >> 4;
-    return j == wc - 1 ? (4 * cs + 7) >> 4 : (3 * cs + 3 * p[r0 + j + 1] + p[r1 + j + 1] + 7) >> 4;
+    s0 = a; s1 = b;
+    if (u != 2) return;
+    s0 = a >> 1; s1 = b >> 1;
+    if (rep) return;
+    if (jd_up_far(a, n) < s0) s0 = jd_up_far(a, n);
+    if (jd_up_far(b, n) > s1) s1 = jd_up_far(b, n);
 }
 
-// The MCU window of a box (l, t, r, b; 0 <= l < r <= width, 0 <= t < b <= height): win = mx0, my0, mx1, my1, the bounding rectangle
-// of the MCUs that hold the luma samples of the box's pixels and, unless luma_only or the file has one component, the chroma samples
-// jd_chroma reads for them -- the co-sited one and its neighbour in each up-sampled direction, after jd_chroma's edge rules for the
-// FILE's wc and hc.  The sample indices are monotonic in x and in y, so the two pixels at either end of a range decide.
-AEJ_HD inline void jd_box_window(int width, int height, int hs, int vs, int ncomp, bool luma_only, const int *box, int *win)
-{
-    if (ncomp != 3) hs = vs = 1;
-    const int l = box[0], t = box[1], r = box[2], b = box[3];
-    win[0] = l / (8 * hs); win[2] = (r - 1) / (8 * hs) + 1;      // the luma samples: the pixels themselves
-    win[1] = t / (8 * vs); win[3] = (b - 1) / (8 * vs) + 1;
-    if (ncomp != 3 || luma_only) return;
-    const int wc = (width + hs - 1) / hs, hc = (height + vs - 1) / vs;
-    int j0 = l, j1 = r - 1, i0 = t, i1 = b - 1;       // chroma sample ranges
-    const bool rep = hs == 2 && wc <= 2;              // plain replication: the co-sited sample alone, in both directions
-    if (hs == 2) {
-        j0 = l >> 1; j1 = (r - 1) >> 1;
-        if (!rep) {
-            if ((l & 1) == 0 && j0 > 0) j0--;
-            if (((r - 1) & 1) && j1 < wc - 1) j1++;
-        }
-    }
-    if (vs == 2) {
-        i0 = t >> 1; i1 = (b - 1) >> 1;
-        if (!rep) {
-            if ((t & 1) == 0 && i0 > 0) i0--;
-            if (((b - 1) & 1) && i1 < hc - 1) i1++;
-        }
-    }
-    if (j0 / 8 < win[0]) win[0] = j0 / 8;
-    if (j1 / 8 + 1 > win[2]) win[2] = j1 / 8 + 1;
-    if (i0 / 8 < win[1]) win[1] = i0 / 8;
-    if (i1 / 8 + 1 > win[3]) win[3] = i1 / 8 + 1;
-}
-
-// jd_box_window for a box (l, t, r, b) in pixels of the image scaled by 1 << shift, ow = ceil(width >> shift) by oh (shift 0: jd_box_window
-// itself).  With m = 8 >> shift an MCU covers hs * m x vs * m scaled pixels.  The chroma follows libjpeg at that scale
-// (jd_chroma_idct_size; k_jd_scaled, k_jd_scaled_h1v2): 4:4:4 and 4:2:0 chroma comes out of its IDCT at luma resolution, so a pixel
-// reads its own MCU alone; 4:2:2 chroma (m wide per MCU) is up-sampled h2v1 fancy at scales 2 and 4 when the scaled chroma width
-// (ow + 1) >> 1 exceeds 2 -- one neighbour column after the edge clamps -- and replicated otherwise; 4:4:0 chroma is up-sampled h1v2
-// fancy at scales 2 and 4 -- one neighbour row after the clamps, at any width -- and replicated at scale 8.  Exact, as jd_box_window.
+// The MCU window of a box (l, t, r, b; 0 <= l < r, 0 <= t < b) in pixels of the image scaled by 1 << shift (0: full size), ceil(width >>
+// shift) by ceil(height >> shift): win = mx0, my0, mx1, my1, the bounding rectangle of the MCUs that hold the luma samples of the box's
+// pixels -- an MCU covers hs * m x vs * m of them -- and, unless luma_only or the file has one component, the chroma samples jd_up_chroma
+// reads for them under the file's jd_up_plan (jd_up_span; chroma sample (i, j) lies in MCU (i / nc, j / nc)).  Exact.
 AEJ_HD inline void jd_sbox_window(int width, int height, int hs, int vs, int ncomp, bool luma_only, int shift, const int *box, int *win)
 {
-    if (shift == 0) { jd_box_window(width, height, hs, vs, ncomp, luma_only, box, win); return; }
     if (ncomp != 3) hs = vs = 1;
-    const int m = 8 >> shift, l = box[0], t = box[1], r = box[2], b = box[3];
-    win[0] = l / (hs * m); win[2] = (r - 1) / (hs * m) + 1;      // the luma samples: the pixels themselves
-    win[1] = t / (vs * m); win[3] = (b - 1) / (vs * m) + 1;
-    if (ncomp != 3 || luma_only || hs == vs || shift == 3) return;      // no chroma, chroma at luma resolution, or replication: the pixel's own MCU
-    const int ow = (width + (1 << shift) - 1) >> shift, oh = (height + (1 << shift) - 1) >> shift;
-    if (hs == 2) {                                    // h2v1: chroma sample j lies in MCU column j / m
-        const int wc = (ow + 1) >> 1;
-        if (wc <= 2) return;
-        int j0 = l >> 1, j1 = (r - 1) >> 1;
-        if ((l & 1) == 0 && j0 > 0) j0--;
-        if (((r - 1) & 1) && j1 < wc - 1) j1++;
-        if (j0 / m < win[0]) win[0] = j0 / m;
-        if (j1 / m + 1 > win[2]) win[2] = j1 / m + 1;
-    } else {                                          // h1v2: chroma row i lies in MCU row i / m
-        const int hc = (oh + 1) >> 1;
-        int i0 = t >> 1, i1 = (b - 1) >> 1;
-        if ((t & 1) == 0 && i0 > 0) i0--;
-        if (((b - 1) & 1) && i1 < hc - 1) i1++;
-        if (i0 / m < win[1]) win[1] = i0 / m;
-        if (i1 / m + 1 > win[3]) win[3] = i1 / m + 1;
-    }
-}
-
-// the chroma sample of scaled pixel (y, x) for k_jd_sbox, from a part of the scaled chroma plane held in LDS, kJdBoxW samples a row,
-// where the file's scaled chroma sample (row, column) is p[row * kJdBoxW + column - off]: k_jd_scaled's h2v1 rule (fancy: jd_h2v1, of
-// which only the neighbour the pixel's parity selects is read -- the other may lie outside the part), k_jd_scaled_h1v2's h1v2 rule,
-// or the sample at the pixel's own place (4:4:4, 4:2:0).  wc, hc: the scaled chroma plane's real width and height
-AEJ_HD inline int jd_sbox_chroma(const unsigned char *p, long long off, bool h2v1, bool h1v2, bool fancy, int wc, int hc, int y, int x)
-{
-    const long long W = kJdBoxW;
-    if (h2v1) {
-        const int j = x >> 1;
-        const long long r0 = y * W - off;
-        const int cur = p[r0 + j];
-        if (!fancy) return cur;
-        if ((x & 1) == 0) return j == 0 ? cur : (3 * cur + p[r0 + j - 1] + 1) >> 2;
-        return j == wc - 1 ? cur : (3 * cur + p[r0 + j + 1] + 2) >> 2;
-    }
-    if (h1v2) {
-        const int cur = p[(y >> 1) * W + x - off];
-        return fancy ? jd_h1v2(cur, p[jd_h1v2_far(y, hc) * W + x - off], y) : cur;
-    }
-    return p[y * W + x - off];
+    const JdUp u = jd_up_plan(width, height, hs, vs, shift);
+    const int l = box[0], t = box[1], r = box[2], b = box[3];
+    win[0] = l / (hs * u.m); win[2] = (r - 1) / (hs * u.m) + 1;      // the luma samples: the pixels themselves
+    win[1] = t / (vs * u.m); win[3] = (b - 1) / (vs * u.m) + 1;
+    if (ncomp != 3 || luma_only) return;
+    const bool rep = jd_up_replicates(u.uh, u.fancy, u.wc);
+    int j0, j1, i0, i1;
+    jd_up_span(l, r - 1, u.uh, rep, u.wc, j0, j1);
+    jd_up_span(t, b - 1, u.uv, rep, u.hc, i0, i1);
+    if (j0 / u.nc < win[0]) win[0] = j0 / u.nc;
+    if (j1 / u.nc + 1 > win[2]) win[2] = j1 / u.nc + 1;
+    if (i0 / u.nc < win[1]) win[1] = i0 / u.nc;
+    if (i1 / u.nc + 1 > win[3]) win[3] = i1 / u.nc + 1;
 }
 
 AEJ_HD inline void jd_rgb(int Y, int cb, int cr, unsigned char *o)

@@ -113,7 +113,7 @@ bool jpegprog_layout(const aej_jpegprog_frame *frames, const aej_jpegprog_scan *
         d.width = f.width; d.height = f.height; d.ncomp = f.ncomp; d.hs = f.hs; d.vs = f.vs; d.mcux = f.mcux; d.mcuy = f.mcuy;
         d.blocks_per_mcu = f.blocks_per_mcu; d.n_segments = 1; d.sof = f.sof; d.precision16 = f.precision16;
         memcpy(d.qt, f.qt, sizeof d.qt);
-        jpeg_recon_layout(d, r.shifts.empty() ? 0 : r.shifts[i], y.ffiles[i], y.fz, r.boxes ? r.boxes + 4 * i : nullptr, false, x);      // a boxed file: all coefficients, k_jd_box (kJdSbox in its shift: k_jd_sbox)
+        jpeg_recon_layout(d, r.shifts.empty() ? 0 : r.shifts[i], y.ffiles[i], y.fz, r.boxes ? r.boxes + 4 * i : nullptr, false, x);      // a boxed file: all coefficients, k_jd_sbox
         int cell_level[4][64];
         for (int c = 0; c < 4; c++) for (int k = 0; k < 64; k++) cell_level[c][k] = -1;
         for (int j = 0; j < f.n_scans; j++) {

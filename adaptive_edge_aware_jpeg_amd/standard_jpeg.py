@@ -632,7 +632,7 @@ def standard_jpeg_decode_many(files, device: int = 0, progressive: bool = False,
     right - left, 3] -- [bottom - top, right - left] where mode makes it one-channel -- and equals ``np.asarray(Image.open(f)
     .convert("RGB").crop(box))`` (for "L": the ``draft("L", None)`` image cropped), i.e. ``[top:bottom, left:right]`` of what the call
     returns without box=: a box edge inside the picture is filtered with its real neighbours from outside the box.  Only what the box
-    needs is done (csrc/jpegdec.hip, ``k_jd_box``; ``decode_box_window`` is the MCU window, ``decode_box_stats`` what the last call
+    needs is done (csrc/jpegdec.hip, ``k_jd_sbox<0>``; ``decode_box_window`` is the MCU window, ``decode_box_stats`` what the last call
     skipped): of a baseline file only the restart segments that hold MCUs of the window's MCU rows are Huffman-decoded and only those
     rows' coefficients are stored; one kernel reconstructs the box's tiles from the coefficients, with no sample planes.  A progressive
     file keeps its whole entropy decode and gets the boxed reconstruction.  Works with progressive=True, layout_440=True and every

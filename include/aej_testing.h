@@ -43,6 +43,16 @@ AEJ_API int aej_test_jfif_prog_scan(aej_ctx *ctx, const int16_t *coefs_host, int
  * samples, row after row -- computed by the function of csrc/jpegdec_core.h that the kernel calls (jd_idct_sized). */
 AEJ_API int aej_test_jpegdec_idct_host(const int16_t *coef_host, const uint16_t *qt_host, int size, uint8_t *out_host);
 
+/* The chroma up-sampling rule of every JPEG reconstruction kernel (jd_up_chroma of csrc/jpegdec_core.h, the function the kernels call),
+ * HOST only.  part_host: a chroma plane or a part of one with row stride `stride`, in which the plane's sample (row, column) is
+ * part_host[row * stride + column - off]; wc x hc: the plane's real samples; uh, uv in 1, 2: the factors to up-sample by; fancy: 0 beside
+ * a 1 x 1 IDCT (plain replication).  out_host gets the samples of the output pixels [y0, y1) x [x0, x1) of the uv * hc x uh * wc
+ * up-sampled plane, row after row.  Only the samples the rule reads for those pixels are read: the part has to hold no others.
+ * AEJ_ERR_ARG for a null pointer, a factor other than 1 and 2, uh = uv = 2 without fancy (no decoder uses it), or a rectangle that is
+ * not inside the up-sampled plane. */
+AEJ_API int aej_test_jpeg_upsample_host(const uint8_t *part_host, int64_t stride, int64_t off, int uh, int uv, int fancy, int wc, int hc,
+                                        int x0, int y0, int x1, int y1, uint8_t *out_host);
+
 /* The baseline entropy decode of one file, HOST only, for coefficient-level comparison with tests/scaled_decode_reference.py: desc_host as
  * aej_jpegdec_parse_host wrote it for file_host (one or three components).  The scan is un-stuffed with the byte classifier the kernels
  * use (jd_byte_class), and each restart segment is then decoded from its first bit to its last by the per-thread routine of
