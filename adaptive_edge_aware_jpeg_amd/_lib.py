@@ -272,6 +272,7 @@ SIGNATURES = {
     "aej_jfif_recon_batch_prog": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _U64]),
     "aej_test_jfif_prog_scan_host": (_I, [_P, ctypes.c_int64, _I, _I, _I, _I, _P, _U64, _P, _P, _P]),        # include/aej_testing.h (tests only)
     "aej_test_jfif_prog_scan": (_I, [_P, _P, ctypes.c_int64, _I, _I, _I, _I, _P, _U64, _P, _P, _P]),         # include/aej_testing.h (tests only)
+    "aej_test_jfif_seq_scan_host": (_I, [_P, ctypes.c_int64, _I, _I, _I, _I, _I, _P, _P, _U64, _P]),            # include/aej_testing.h (tests only)
     "aej_jpegdec_parse_host": (_I, [_P, _U64, _P, _P, _I]),
     "aej_jpegdec_workspace_bytes": (_U64, [_P, _P, _I]),
     "aej_jpegdec_batch": (_I, [_P, _P, _I, _P, _U64, _P, _P, _U64, _P, _P, _P, _U64]),

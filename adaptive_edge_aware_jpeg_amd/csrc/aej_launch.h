@@ -257,6 +257,11 @@ void jfif_params_host(int q, int H, int W, JfifParams &p, int ss = 2, int ncomp 
 constexpr int jfif_sof_bytes(int ncomp) { return 10 + 3 * ncomp; }      // a frame header, marker and length included
 constexpr int jfif_sos_bytes(int ncomp) { return 8 + 2 * ncomp; }       // a scan header of every component
 int jfif_huffman_host(const long long *counts, unsigned char *bits, unsigned char *huffval);
+// the baseline scan of n_mcu MCUs of given coefficients (int16 [n_mcu * blocks per MCU][64], zigzag and MCU order) on the host: the
+// symbol counts [4][257] in table order and the stuffed scan bytes with their RSTn markers.  -> 0, or AEJ_ERR_ARG / AEJ_ERR_CAPACITY
+// (out_len is set)
+int jfif_seq_scan_host(const short *coefs, long long n_mcu, int hs, int vs, int ncomp, int R, int optimize, long long *hist, unsigned char *out,
+                       unsigned long long cap, unsigned long long *out_len);
 hipError_t launch_jfif_encode(hipStream_t st, const JfifGeom &g, const JfifBufs &w, const JfifParams *par_host, const unsigned char *rgb,
                               unsigned char *out, unsigned long long cap, long long *lengths, long long *offsets);
 hipError_t launch_jfif_recon(hipStream_t st, const JfifGeom &g, const JfifBufs &w, unsigned char *rgb_out);

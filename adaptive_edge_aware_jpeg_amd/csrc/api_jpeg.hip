@@ -180,6 +180,16 @@ extern "C" int aej_test_jfif_prog_scan_host(const int16_t *coefs_host, int64_t n
     return rc;
 }
 
+extern "C" int aej_test_jfif_seq_scan_host(const int16_t *coefs_host, int64_t n_mcu, int hs, int vs, int ncomp, int restart_interval, int optimize,
+                                           int64_t *hist_host, uint8_t *out_host, uint64_t capacity, uint64_t *out_len_host)
+{
+    if (!out_len_host) return AEJ_ERR_ARG;
+    unsigned long long len = 0;
+    const int rc = jfif_seq_scan_host(coefs_host, n_mcu, hs, vs, ncomp, restart_interval, optimize, (long long *)hist_host, out_host, capacity, &len);
+    *out_len_host = len;
+    return rc;
+}
+
 extern "C" int aej_test_jfif_prog_scan(aej_ctx *ctx, const int16_t *coefs_host, int64_t n_blocks, int Ss, int Se, int Ah, int Al, uint8_t *out_host,
                                        uint64_t capacity, uint64_t *out_len_host, int64_t *counts_host, int64_t *cuts_host)
 {

@@ -33,6 +33,11 @@
 //                   decoder's islow IDCT pass and masked range limit (jd_idct8, jd_range_limit) -> uint8 sample planes
 //   k_jfif_rgb      one thread per output pixel: h2v2 / h2v1 fancy up-sampling (plain replication when the chroma is <= 2 wide, as
 //                   libjpeg-turbo does; none at 4:4:4) and the fixed-point YCbCr -> RGB -- jd_chroma, jd_rgb of jpegdec_core.h
+// What a block gives the scan is written once, in jfif_prog_core.h: je_block_seq (the DC difference, the run-length walk of Annex F.1.2
+// with its ZRL and EOB symbols) into a sink -- a histogram (k_jfif_hist), a bit count (k_jfif_quant, whose coefficient source quantises
+// as the walk reads; k_jfif_count) or the bit writer (k_jfif_emit) -- and je_dc_pred, the DC predictor with its restart rule.  A block's
+// place in its restart interval and the stuffing copy with markers are jfif_restart_core.h's (jr_place, jr_stuff_chunk), shared with
+// jfifprog.hip.  jfif_seq_scan_host (aej_test_jfif_seq_scan_host) steps through all of these on the CPU.
 // The bit writer (JeBits), magnitude category, predecessor block, 0xFF counting / stuffing loops and the prefix-sum kernel are
 // jfif_stream_core.h's, the zigzag tables aej_common.h's (kZigzag8, k_zigzag8): one copy for every coder and decoder.
 // Bounds: every index derives from JfifGeom; a stream's words stay inside its stride (the per-block bound kJfifBlockWords holds for every
@@ -43,9 +48,12 @@
 #include "aej_launch.h"
 #include "jfif_arith.h"
 #include "jfif_huff_core.h"
+#include "jfif_prog_core.h"
 #include "jfif_restart_core.h"
 #include "jfif_stream_core.h"
 #include "jpegdec_core.h"
+
+#include <vector>
 
 namespace aej {
 
@@ -98,7 +106,7 @@ __constant__ unsigned k_ac_chroma[256] = {
 
 // ---- arithmetic shared by the stages ----------------------------------------------------------------------------------------------
 // jf_y, jf_c, jf_h2v1, jf_h2v2, jf_descale, jf_fdct8, jf_quant: jfif_arith.h (shared with jfifmany.hip); js_nbits, js_prev, JeBits,
-// js_stuff_*, k_js_scan: jfif_stream_core.h (shared with jfifprog.hip); jd_idct8, jd_range_limit, jd_chroma, jd_rgb: jpegdec_core.h
+// js_stuff_*, k_js_scan: jfif_stream_core.h, je_block_seq, je_dc_pred and the sinks: jfif_prog_core.h (shared with jfifprog.hip); jd_idct8, jd_range_limit, jd_chroma, jd_rgb: jpegdec_core.h
 
 // MCU geometry: block k (0 .. HS * VS - 1 luma in raster order, then Cb, Cr) of MCU m; luma blocks outside ceil(H/8) x ceil(W/8) are
 // dummies (right edge when HS = 2, bottom edge when VS = 2)
@@ -187,6 +195,22 @@ __device__ __forceinline__ JfCodes jf_file_codes(const unsigned *codes, long lon
     return JfCodes{ t, t + 256 };
 }
 
+// k_jfif_quant's coefficient sources for je_block_seq, which reads every index once, in increasing order: JfQuantSrc quantises
+// coefficient i of the block d (FDCT output, natural order) with qt[i] as it is read and stores it to o[i]; a dummy block has no AC
+struct JfQuantSrc {
+    const int *d, *qt;
+    short *o;
+    __device__ __forceinline__ int operator[](int i) const
+    {
+        const int v = jf_quant(d[k_zigzag8.natural[i]], qt[i]);
+        o[i] = (short)v;
+        return v;
+    }
+};
+struct JfNoAc {
+    __device__ __forceinline__ int operator[](int) const { return 0; }
+};
+
 // (a) quantise every block of every (quality, image) and count its Huffman bits
 template <int HS, int VS>
 __global__ __launch_bounds__(kJfThreads) void k_jfif_quant(JfifGeom g, const JfifParams *__restrict__ par, const int *__restrict__ dct,
@@ -204,31 +228,21 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_quant(JfifGeom g, const Jfi
     short *o = coef + idx * 64;
     const int dc = jf_qdc<HS, VS>(g, img, p, m, k);
     const long long pb = js_prev(NL, BPM, m, k);
-    const int diff = dc - (pb < 0 ? 0 : jf_qdc<HS, VS>(g, img, p, pb / BPM, (int)(pb % BPM)));
-    const int dcat = js_nbits(diff);
-    int bits = (int)(hc.dc[dcat] & 255) + dcat;
+    const int pred = pb < 0 ? 0 : jf_qdc<HS, VS>(g, img, p, pb / BPM, (int)(pb % BPM));      // (this chain has no restart intervals)
+    JeLen sink{ nullptr, 0 };
     o[0] = (short)dc;
     if (!jf_real<HS, VS>(g, m, k)) {
         for (int i = 1; i < 64; i++) o[i] = 0;
-        lens[idx] = bits + (int)(hc.ac[0] & 255);
+        je_block_seq(dc, pred, JfNoAc{}, hc.dc, hc.ac, sink);
+        lens[idx] = sink.total;
         return;
     }
-    const int *d = img + blk * 64;
-    int run = 0;
-    for (int i = 1; i < 64; i++) {
-        const int v = jf_quant(d[k_zigzag8.natural[i]], qt[i]);
-        o[i] = (short)v;
-        if (v == 0) { run++; continue; }
-        const int cat = js_nbits(v);
-        bits += (run >> 4) * (int)(hc.ac[0xF0] & 255) + (int)(hc.ac[((run & 15) << 4) | cat] & 255) + cat;
-        run = 0;
-    }
-    if (run) bits += (int)(hc.ac[0] & 255);
-    lens[idx] = bits;
+    je_block_seq(dc, pred, JfQuantSrc{ img + blk * 64, qt, o }, hc.dc, hc.ac, sink);
+    lens[idx] = sink.total;
 }
 
 // ---- optimize: the file's own Huffman tables -----------------------------------------------------------------------------------------
-// (a1) the symbols k_jfif_emit will write for every block, dummies included: DC categories, (run << 4) | size, ZRL per 16 zeros, EOB.
+// (a1) the symbols k_jfif_emit will write for every block, dummies included (je_block_seq into a histogram).
 // grid (blocks of one segment, segment); counts are private to a wave in LDS, then one 64-bit add per non-zero bin.
 template <int HS, int VS, int NC>
 __global__ __launch_bounds__(kJfThreads) void k_jfif_hist(JfifGeom g, const short *__restrict__ coef, unsigned long long *__restrict__ hist)
@@ -242,18 +256,9 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_hist(JfifGeom g, const shor
         const long long m = blk / BPM;
         const int k = (int)(blk % BPM);
         unsigned(*h)[kJhSymbols] = cnt[threadIdx.x / 64] + (k >= NL ? 2 : 0);      // [0] DC, [1] AC of the block's component class
-        const short *c = coef + (seg * g.nblk + blk) * 64;
-        const long long pb = js_prev(NL, BPM, m, k);
-        atomicAdd(&h[0][js_nbits(c[0] - (pb < 0 || jr_resets(m, pb, BPM, g.R) ? 0 : coef[(seg * g.nblk + pb) * 64]))], 1u);
-        int run = 0;
-        for (int i = 1; i < 64; i++) {
-            const int v = c[i];
-            if (v == 0) { run++; continue; }
-            if (run > 15) atomicAdd(&h[1][0xF0], (unsigned)(run >> 4));
-            atomicAdd(&h[1][((run & 15) << 4) | js_nbits(v)], 1u);
-            run = 0;
-        }
-        if (run) atomicAdd(&h[1][0], 1u);
+        const short *base = coef + seg * g.nblk * 64, *c = base + blk * 64;
+        JeHist<unsigned> sink{ nullptr };
+        je_block_seq(c[0], je_dc_pred(base, NL, BPM, m, k, g.R), c, h[0], h[1], sink);
     }
     __syncthreads();
     for (int i = threadIdx.x; i < kTables * kJhSymbols; i += kJfThreads) {
@@ -341,19 +346,10 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_count(JfifGeom g, const sho
     const long long seg = idx / g.nblk, blk = idx % g.nblk, m = blk / BPM;
     const int k = (int)(blk % BPM);
     const JfCodes hc = jf_file_codes(codes, seg, k >= NL);
-    const short *c = coef + idx * 64;
-    const long long pb = js_prev(NL, BPM, m, k);
-    const int dcat = js_nbits(c[0] - (pb < 0 || jr_resets(m, pb, BPM, g.R) ? 0 : coef[(seg * g.nblk + pb) * 64]));
-    int bits = (int)(hc.dc[dcat] & 255) + dcat, run = 0;
-    for (int i = 1; i < 64; i++) {
-        const int v = c[i];
-        if (v == 0) { run++; continue; }
-        const int cat = js_nbits(v);
-        bits += (run >> 4) * (int)(hc.ac[0xF0] & 255) + (int)(hc.ac[((run & 15) << 4) | cat] & 255) + cat;
-        run = 0;
-    }
-    if (run) bits += (int)(hc.ac[0] & 255);
-    lens[idx] = bits;
+    const short *base = coef + seg * g.nblk * 64, *c = base + blk * 64;
+    JeLen sink{ nullptr, 0 };
+    je_block_seq(c[0], je_dc_pred(base, NL, BPM, m, k, g.R), c, hc.dc, hc.ac, sink);
+    lens[idx] = sink.total;
 }
 
 // (b) k_js_scan (jfif_stream_core.h): a segment's n + 1 prefix sums of its blocks' bits (boff) and later of its chunks' 0xFF counts (ffpre)
@@ -400,42 +396,16 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_emit(JfifGeom g, const shor
     const long long seg = idx / g.nblk, blk = idx % g.nblk, m = blk / BPM;
     const int k = (int)(blk % BPM);
     const JfCodes hc = kOpt ? jf_file_codes(codes, seg, k >= NL) : jf_codes(k >= NL);
-    const short *c = coef + idx * 64;
-    const long long pb = js_prev(NL, BPM, m, k);
-    long long pos = (long long)boff[idx + seg], end_bits = 0;                                   // n + 1 entries per segment
-    bool last = blk == g.nblk - 1, reset = pb < 0;
-    if (g.R) {                                               // uniform: the block's place inside its byte-aligned interval
-        const unsigned long long *b = boff + seg * (g.nblk + 1);
-        const long long per = (long long)g.R * BPM, iv = blk / per, lo = iv * per, hi = min(lo + per, g.nblk);
-        pos = 8 * (long long)ivoff[seg * (g.niv + 1) + iv] + (long long)(b[blk] - b[lo]);
-        end_bits = (long long)(b[hi] - b[lo]);
-        last = blk == hi - 1;
-        reset = reset || jr_resets(m, pb, BPM, g.R);
-    } else if (last) {
-        end_bits = jf_bits(g, boff, seg);
-    }
-    JeBits bw(stream + seg * g.stream_words, pos, g.stream_words);
-    const int diff = c[0] - (reset ? 0 : coef[(seg * g.nblk + pb) * 64]);
-    const int dcat = js_nbits(diff);
-    bw.put(hc.dc[dcat] >> 8, (int)(hc.dc[dcat] & 255));
-    if (dcat) bw.put((unsigned)(diff < 0 ? diff - 1 : diff) & ((1u << dcat) - 1), dcat);
-    int run = 0;
-    for (int i = 1; i < 64; i++) {
-        const int v = c[i];
-        if (v == 0) { run++; continue; }
-        for (; run > 15; run -= 16) bw.put(hc.ac[0xF0] >> 8, (int)(hc.ac[0xF0] & 255));
-        const int cat = js_nbits(v);
-        const unsigned e = hc.ac[(run << 4) | cat];
-        bw.put(e >> 8, (int)(e & 255));
-        bw.put((unsigned)(v < 0 ? v - 1 : v) & ((1u << cat) - 1), cat);
-        run = 0;
-    }
-    if (run) bw.put(hc.ac[0] >> 8, (int)(hc.ac[0] & 255));
-    if (last) {                                              // pad the last byte (of every restart interval) with 1-bits
-        const int pad = (int)((8 - (end_bits & 7)) & 7);
-        if (pad) bw.put((1u << pad) - 1, pad);
-    }
-    bw.finish();
+    const short *base = coef + seg * g.nblk * 64, *c = base + blk * 64;
+    const unsigned long long *b = boff + seg * (g.nblk + 1);                                    // n + 1 entries per segment
+    const int dc = c[0], pred = je_dc_pred(base, NL, BPM, m, k, g.R);                           // (loaded beside the offsets, not behind them)
+    JrPlace at{ (long long)b[blk], 0, blk == g.nblk - 1 };
+    if (g.R) at = jr_place(blk, (long long)g.R * BPM, g.nblk, b, ivoff + seg * (g.niv + 1));   // uniform: inside its byte-aligned interval
+    else if (at.last) at.total = jf_bits(g, boff, seg);
+    JeEmit sink{ nullptr, JeBits(stream + seg * g.stream_words, at.pos, g.stream_words) };
+    je_block_seq(dc, pred, c, hc.dc, hc.ac, sink);
+    if (at.last) sink.bw.pad_ones(at.total);                 // the last byte (of every restart interval) is padded with 1-bits
+    sink.bw.finish();
 }
 
 // 0xFF bytes per 64-byte chunk of each stream's data
@@ -494,13 +464,8 @@ __global__ __launch_bounds__(kJfThreads) void k_jfif_scatter(JfifGeom g, const J
     const unsigned char *src = reinterpret_cast<const unsigned char *>(stream + seg * g.stream_words);
     if (lo >= hi) return;
     unsigned char *dst = file + hdr_len + lo + (long long)ffpre[idx + seg];                         // n + 1 entries per segment
-    if (g.R) {                                               // uniform: the markers before this chunk shift it, those inside it are written here
-        const unsigned long long *starts = ivoff + seg * (g.niv + 1);
-        const long long k = jr_first_from(starts, g.niv, lo);
-        jr_stuff_copy(dst + 2 * (k - 1), src, lo, hi, starts, g.niv, k);
-    } else {
-        js_stuff_copy(dst, src, lo, hi);
-    }
+    // uniform: with restarts the markers before this chunk shift it, those inside it are written here
+    jr_stuff_chunk(dst, src, lo, hi, g.R ? ivoff + seg * (g.niv + 1) : nullptr, g.R ? g.niv : 0);
 }
 
 // ---- reconstruction ----------------------------------------------------------------------------------------------------------------
@@ -675,6 +640,74 @@ int jfif_huffman_host(const long long *counts, unsigned char *bits, unsigned cha
     }
     if (!any || counts[256] < 0) return -1;
     return jh_build(w, bits, huffval);
+}
+
+// the testing entry aej_test_jfif_seq_scan_host: the baseline scan of n_mcu MCUs of given coefficients, by the text the kernels run --
+// je_block_seq and je_dc_pred into the three sinks, jh_build / jh_codes, jr_place, JeBits::pad_ones, jr_stuff_chunk -- stage after stage
+// as jf_entropy launches them
+int jfif_seq_scan_host(const short *coefs, long long n_mcu, int hs, int vs, int ncomp, int R, int optimize, long long *hist, unsigned char *out,
+                       unsigned long long cap, unsigned long long *out_len)
+{
+    if (!coefs || !hist || !out || !out_len || n_mcu < 1 || n_mcu > (1LL << 20) || (ncomp != 1 && ncomp != 3) || (optimize != 0 && optimize != 1)) return AEJ_ERR_ARG;
+    if (ncomp == 1) hs = vs = 1;
+    if (!((hs == 1 || hs == 2) && (vs == 1 || vs == 2)) || R < 0 || R > kJrMaxInterval || (R > 0 && !optimize)) return AEJ_ERR_ARG;
+    const int NL = hs * vs, BPM = NL + ncomp - 1, ntab = ncomp == 1 ? 2 : 4;
+    const long long n = n_mcu * BPM;
+    for (long long i = 0; i < n * 64; i++)
+        if (coefs[i] > kJeMaxCoef || coefs[i] < -kJeMaxCoef) return AEJ_ERR_ARG;
+    std::vector<unsigned> codes(4 * 256, 0);
+    // block i as the kernels code it, under tables of `stride` entries each: DC luma, AC luma, DC chroma, AC chroma
+    auto block = [&](long long i, auto *tabs, int stride, auto &sink) {
+        const int k = (int)(i % BPM);
+        const short *c = coefs + i * 64;
+        tabs += (k >= NL ? 2 : 0) * stride;
+        je_block_seq(c[0], je_dc_pred(coefs, NL, BPM, i / BPM, k, R), c, tabs, tabs + stride, sink);
+    };
+    // k_jfif_hist
+    for (int i = 0; i < 4 * kJhSymbols; i++) hist[i] = 0;
+    for (long long i = 0; i < n; i++) {
+        JeHist<unsigned long long> sink{ nullptr };
+        block(i, reinterpret_cast<unsigned long long *>(hist), kJhSymbols, sink);      // (the counts are not negative)
+    }
+    // k_jfif_tables, or the Annex K tables
+    const unsigned char *annexk[4] = { kDht_dc_luma, kDht_ac_luma, kDht_dc_chroma, kDht_ac_chroma };
+    for (int t = 0; t < ntab; t++) {
+        unsigned char bits[16], vals[256];
+        if (optimize) {
+            JhWork w;
+            for (int i = 0; i < 256; i++) w.freq[i] = hist[t * kJhSymbols + i];
+            jh_build(w, bits, vals);
+        }
+        jh_codes(optimize ? bits : annexk[t], optimize ? vals : annexk[t] + 16, codes.data() + t * 256);
+    }
+    // k_jfif_count, k_js_scan (bits, then the intervals' bytes)
+    std::vector<unsigned long long> P(n + 1, 0), starts;
+    for (long long i = 0; i < n; i++) {
+        JeLen sink{ nullptr, 0 };
+        block(i, codes.data(), 256, sink);
+        P[i + 1] = P[i] + sink.total;
+    }
+    const long long per = (long long)R * BPM, niv = R ? jr_count(n_mcu, R) : 0;
+    starts.assign(niv + 1, 0);
+    for (long long v = 0; v < niv; v++) starts[v + 1] = starts[v] + ((P[std::min((v + 1) * per, n)] - P[v * per] + 7) >> 3);
+    const long long nbytes = R ? (long long)starts[niv] : (long long)((P[n] + 7) >> 3), limit = (nbytes + 3) / 4 + 1;
+    // k_jfif_emit
+    std::vector<unsigned> words(limit, 0);
+    for (long long i = 0; i < n; i++) {
+        JrPlace at{ (long long)P[i], (long long)P[n], i == n - 1 };
+        if (R) at = jr_place(i, per, n, P.data(), starts.data());
+        JeEmit sink{ nullptr, JeBits(words.data(), at.pos, limit) };
+        block(i, codes.data(), 256, sink);
+        if (at.last) sink.bw.pad_ones(at.total);
+        sink.bw.finish();
+    }
+    // k_jfif_ffcount, k_jfif_layout, k_jfif_scatter
+    const unsigned char *src = reinterpret_cast<const unsigned char *>(words.data());
+    const unsigned long long o = (unsigned long long)(nbytes + js_stuff_count(src, 0, nbytes) + (R ? 2 * (niv - 1) : 0));
+    *out_len = o;
+    if (o > cap) return AEJ_ERR_CAPACITY;
+    jr_stuff_chunk(out, src, 0, nbytes, starts.data(), niv);
+    return 0;
 }
 
 void jfif_quant_tables(int q, int luma[64], int chroma[64])

@@ -1,7 +1,12 @@
-// jfif_prog_core.h -- the Annex G (progressive) entropy coder as libjpeg's jcphuff.c runs it, written once as host + device functions so
-// that aej_test_jfif_prog_scan_host steps through the text the kernels of jfifprog.hip run.
+// jfif_prog_core.h -- what one block gives a Huffman-coded JPEG scan, written once as host + device functions: the sequential block
+// of Annex F.1.2 (je_block_seq: every baseline writer of jfif.hip -- histogram, bit count, the quantiser's Annex K count, emitter) and
+// the Annex G (progressive) coder as libjpeg's jcphuff.c runs it (jfifprog.hip).  A sequential block is the progressive pieces at
+// Al = 0 -- je_dc_first, je_ac_first over 1 .. 63, the EOB symbol -- so both coders and both host testing entries
+// (aej_test_jfif_seq_scan_host, aej_test_jfif_prog_scan_host) step through one text.  The sinks a block is coded into (nothing, a
+// histogram, a bit count, the bit writer) and the DC predictor with its restart rule (je_dc_pred) are here too.
 //
-// libjpeg codes a scan serially: an end-of-band run (EOBRUN) and the correction bits deferred behind it (BE) pass from block to block.
+// libjpeg codes a progressive scan serially: an end-of-band run (EOBRUN) and the correction bits deferred behind it (BE) pass from block
+// to block.
 // Here a block is coded on its own (je_dc_*, je_ac_first, je_ac_refine report what it emits to a sink and what it leaves pending), and
 // the state between blocks is a partition of the scan into pieces:
 //   a block "joins" when it ends with zeros or deferred bits pending (r > 0 || BR > 0); a block that emits no symbol always joins;
@@ -13,6 +18,7 @@
 #pragma once
 #include <stdint.h>
 
+#include "jfif_restart_core.h"
 #include "jfif_stream_core.h"
 
 namespace aej {
@@ -35,7 +41,8 @@ AEJ_HD inline int je_block_bound(int Ss, int Se, int Ah)
     return (Ah ? 17 : 27) * (Se - Ss + 1) + 30;
 }
 
-// A sink takes sym(s): one Huffman symbol; bits(v, n): n <= 16 raw bits; many(v, n): n <= 63 raw bits, the first one highest.
+// A sink takes sym(s, n = 1): the Huffman symbol s, n >= 0 times in a row (the ZRLs of a zero run); bits(v, n): n <= 16 raw bits; many(v, n): n <= 63 raw bits, the first one highest.  Its
+// member `codes` is the table its symbols index (code words, or a histogram's counters): the caller points it at the DC or the AC table.
 template <class Sink>
 AEJ_HD inline void je_dc_first(int cur, int prev, int Al, Sink &s)      // prev: the component's block before in scan order (0 at the start)
 {
@@ -46,8 +53,10 @@ AEJ_HD inline void je_dc_first(int cur, int prev, int Al, Sink &s)      // prev:
 template <class Sink>
 AEJ_HD inline void je_dc_refine(int cur, int Al, Sink &s) { s.bits((unsigned)(cur >> Al) & 1u, 1); }
 
-template <class Sink>
-AEJ_HD inline JeBlock je_ac_first(const short *c, int Ss, int Se, int Al, Sink &s)
+// c: anything indexable that yields the coefficients (a const short *, or a source that computes them): every index Ss .. Se is read
+// exactly once, in increasing order, so a source may do its work -- quantise, store -- inside operator[]
+template <class Src, class Sink>
+AEJ_HD inline JeBlock je_ac_first(Src c, int Ss, int Se, int Al, Sink &s)
 {
     JeBlock b = { 0, 0, 0, 0 };
     int r = 0;
@@ -55,7 +64,8 @@ AEJ_HD inline JeBlock je_ac_first(const short *c, int Ss, int Se, int Al, Sink &
         const int v = c[k], t = (v < 0 ? -v : v) >> Al;
         if (t == 0) { r++; continue; }
         b.e = 1;                                             // here libjpeg flushes the run before: it ended with the block before
-        for (; r > 15; r -= 16) s.sym(0xF0);
+        s.sym(0xF0, r >> 4);                                 // the run's ZRLs in one call, often none: a length sink multiplies, no branch, no loop
+        r &= 15;
         const int n = js_nbits(t);
         s.sym((r << 4) | n);
         s.bits((unsigned)(v < 0 ? ~t : t) & ((1u << n) - 1), n);
@@ -108,6 +118,27 @@ AEJ_HD inline void je_eobrun(int run, Sink &s)              // the EOBn symbol o
     if (n) s.bits((unsigned)run & ((1u << n) - 1), n);
 }
 
+// One block of a sequential scan (Annex F.1.2: baseline, and the optimised files' own tables): the DC difference against `pred`, the
+// run-length walk over coefficients 1 .. 63 of c (read as je_ac_first reads them; c[0] is not read), EOB if zeros are pending.
+// dc_codes / ac_codes: the block's two tables, as the sink's `codes`.
+template <class Src, class Tab, class Sink>
+AEJ_HD inline void je_block_seq(int dc, int pred, Src c, Tab dc_codes, Tab ac_codes, Sink &s)
+{
+    s.codes = dc_codes;
+    je_dc_first(dc, pred, 0, s);
+    s.codes = ac_codes;
+    if (je_ac_first(c, 1, 63, 0, s).r) s.sym(0x00);
+}
+
+// the DC predictor of block k of MCU m in an interleaved scan (NL luma blocks of BPM per MCU, restart interval R, 0: none) over the
+// coefficients `coef` of the scan's blocks in MCU order: the DC of the component's block before, 0 at the start of the scan and of
+// every restart interval
+AEJ_HD inline int je_dc_pred(const short *coef, int NL, int BPM, long long m, int k, int R)
+{
+    const long long pb = js_prev(NL, BPM, m, k);
+    return pb < 0 || jr_resets(m, pb, BPM, R) ? 0 : coef[pb * 64];
+}
+
 // ---- the partition -------------------------------------------------------------------------------------------------------------------
 // value of one block of an AC scan for the prefix sum: a break (the block does not continue the chain of the block before: it is the
 // first of the scan, it emits, or the block before left nothing pending) and its pending correction bits
@@ -153,21 +184,40 @@ AEJ_HD inline long long je_piece_end(const unsigned long long *P, long long p, l
 
 // ---- sinks.  codes: (code << 8) | length per symbol (jh_codes); JeEmit writes through JeBits (jfif_stream_core.h)
 struct JeNull {
-    AEJ_HD inline void sym(int) {}
+    AEJ_HD inline void sym(int, int = 1) {}
+    AEJ_HD inline void bits(unsigned, int) {}
+    AEJ_HD inline void many(unsigned long long, int) {}
+};
+// symbol counts: T unsigned in LDS on the device (counted atomically: a wave shares one), unsigned long long on the host
+template <class T>
+struct JeHist {
+    T *codes;
+    AEJ_HD inline void sym(int s, int n = 1)
+    {
+        if (n == 0) return;
+#if defined(__HIP_DEVICE_COMPILE__)
+        atomicAdd(codes + s, (T)n);
+#else
+        codes[s] += (T)n;
+#endif
+    }
     AEJ_HD inline void bits(unsigned, int) {}
     AEJ_HD inline void many(unsigned long long, int) {}
 };
 struct JeLen {
     const unsigned *codes;
     int total;
-    AEJ_HD inline void sym(int s) { total += (int)(codes[s] & 255); }
+    AEJ_HD inline void sym(int s, int n = 1) { total += n * (int)(codes[s] & 255); }
     AEJ_HD inline void bits(unsigned, int n) { total += n; }
     AEJ_HD inline void many(unsigned long long, int n) { total += n; }
 };
 struct JeEmit {
     const unsigned *codes;
     JeBits bw;
-    AEJ_HD inline void sym(int s) { bw.put(codes[s] >> 8, (int)(codes[s] & 255)); }
+    AEJ_HD inline void sym(int s, int n = 1)
+    {
+        for (; n > 0; n--) bw.put(codes[s] >> 8, (int)(codes[s] & 255));
+    }
     AEJ_HD inline void bits(unsigned v, int n) { bw.put(v, n); }
     AEJ_HD inline void many(unsigned long long v, int n)
     {

@@ -6,13 +6,13 @@
 // last one shorter; before the first MCU of interval k >= 1 the coder flushes what is pending, pads the byte with 1-bits, writes the
 // marker FF D0 + ((k - 1) & 7) and sets every DC predictor to 0.  The writers here keep every interval byte-aligned in the unstuffed
 // stream (its bytes are ceil(bits / 8), the last block pads) and never store a marker there: a prefix sum over the intervals' byte
-// lengths gives their starts, and the scatter that stuffs 0xFF bytes inserts each marker before its interval's first byte.
+// lengths gives their starts, and the scatter that stuffs 0xFF bytes inserts each marker before its interval's first byte.  Where an
+// item (a block of a scan) lands in such a stream (jr_place) and the stuffing copy of a chunk of it (jr_stuff_chunk) are here as well:
+// both chains' emit and scatter kernels and the host entry aej_test_jfif_seq_scan_host call them.
 #pragma once
 #include <stdint.h>
 
-#ifndef AEJ_HD
-#define AEJ_HD __host__ __device__
-#endif
+#include "jfif_stream_core.h"
 
 namespace aej {
 
@@ -72,6 +72,32 @@ AEJ_HD inline void jr_stuff_copy(unsigned char *dst, const unsigned char *src, l
         *dst++ = v;
         if (v == 0xFF) *dst++ = 0;
     }
+}
+
+// the bytes [lo, hi) of a scan's unstuffed stream with a 0x00 after every 0xFF, and with the scan's markers if it has intervals (niv > 0;
+// starts as above); dst is where byte lo goes once the 0x00 bytes before it are counted -- the marker bytes before it are counted here
+AEJ_HD inline void jr_stuff_chunk(unsigned char *dst, const unsigned char *src, long long lo, long long hi, const unsigned long long *starts,
+                                  long long niv)
+{
+    if (niv == 0) {
+        js_stuff_copy(dst, src, lo, hi);
+        return;
+    }
+    const long long k = jr_first_from(starts, niv, lo);
+    jr_stuff_copy(dst + 2 * (k - 1), src, lo, hi, starts, niv, k);
+}
+
+// Item i of a scan of n items whose restart intervals hold `per` items each (the last one fewer).  P: the scan's n + 1 exclusive prefix
+// sums of the items' bits, starts: the byte starts of its intervals (both may be windows of longer sums: only differences are used)
+// -> the item's bit position in the scan's stream of byte-aligned intervals, the bits of its interval, whether it is the interval's last
+struct JrPlace {
+    long long pos, total;
+    bool last;
+};
+AEJ_HD inline JrPlace jr_place(long long i, long long per, long long n, const unsigned long long *P, const unsigned long long *starts)
+{
+    const long long iv = i / per, lo = iv * per, hi = lo + per < n ? lo + per : n;
+    return JrPlace{ 8 * (long long)(starts[iv] - starts[0]) + (long long)(P[i] - P[lo]), (long long)(P[hi] - P[lo]), i == hi - 1 };
 }
 
 }  // namespace aej

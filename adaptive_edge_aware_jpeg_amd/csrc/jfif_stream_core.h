@@ -2,8 +2,11 @@
 // the big-endian bit writer, 0xFF counting and stuffing of a byte range, the predecessor of a block in an interleaved scan, and the
 // segmented prefix-sum kernel.  jfif.hip (baseline, optimised), jfifprog.hip (progressive) and through them the ragged encoder, the
 // transcoder and the transforms write their streams with these; the decoders' bit windows take js_bswap.  Host + device where the host
-// testing entries step through the same text (aej_test_jfif_prog_scan_host).  Every piece must stay bit-exact with libjpeg-turbo: the
-// Pillow byte-for-byte suites (tests/test_gpu_jfif*.py) pin all callers at once.
+// testing entries step through the same text (aej_test_jfif_seq_scan_host, aej_test_jfif_prog_scan_host).  Every piece must stay
+// bit-exact with libjpeg-turbo: the Pillow byte-for-byte suites (tests/test_gpu_jfif*.py) pin all callers at once.
+// Who includes what: jfif_restart_core.h (restart index rules, an item's place in its interval, the stuffing copy with markers) includes
+// this file; jfif_prog_core.h (the block coders je_block_seq / je_dc_* / je_ac_*, their sinks, the DC predictor) includes both; jfif.hip
+// and jfifprog.hip include all three, api_jpeg.hip this file and jfif_restart_core.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -79,6 +82,11 @@ struct JeBits {
             word((unsigned)(acc >> n));
             acc &= (1ull << n) - 1;
         }
+    }
+    AEJ_HD inline void pad_ones(long long total_bits)       // after the last bit of a byte-aligned run of total_bits bits: 1-bits up to its last byte's end
+    {
+        const int pad = (int)((8 - (total_bits & 7)) & 7);
+        put((1u << pad) - 1, pad);
     }
     AEJ_HD inline void finish()
     {

@@ -56,19 +56,12 @@ __host__ __device__ inline long long jfp_coef_block(const JfpGeom &g, const JfpS
     const long long by = i / g.ybx, bx = i % g.ybx;
     return ((by / g.vs) * g.mcux + bx / g.hs) * BPM + (by % g.vs) * g.hs + bx % g.hs;
 }
-// interleaved scans: the block of the same component before block i in scan order (-1 at the start) and whether i is chroma
-__host__ __device__ inline long long jfp_prev(const JfpGeom &g, long long i, bool *chroma)
+// DC first scans (interleaved): the predictor of item i (je_dc_pred) and whether i is chroma
+__device__ __forceinline__ int jfp_dc_pred(const JfpGeom &g, const JfpScan &s, const short *base, long long i, bool *chroma)
 {
     const int NL = g.hs * g.vs, BPM = NL + g.nchroma, k = (int)(i % BPM);
     *chroma = k >= NL;
-    return js_prev(NL, BPM, i / BPM, k);
-}
-// DC first scans: the predictor of item i -- the component's block before it in scan order, 0 at the start of the scan and of a restart interval
-__device__ __forceinline__ int jfp_dc_pred(const JfpGeom &g, const JfpScan &s, const short *base, long long i, bool *chroma)
-{
-    const long long pb = jfp_prev(g, i, chroma);
-    const int BPM = g.hs * g.vs + g.nchroma;
-    return pb < 0 || jr_resets(i / BPM, pb, BPM, s.R) ? 0 : base[pb * 64];
+    return je_dc_pred(base, NL, BPM, i / BPM, k, s.R);
 }
 // the value of item idx in the partition's prefix sums (je_pack), from the flags k_jfp_facts left
 __device__ __forceinline__ unsigned long long jfp_value(const unsigned short *flags, long long idx)
@@ -143,13 +136,6 @@ __global__ __launch_bounds__(kJfpThreads) void k_jfp_cuts(JfpGeom g, const unsig
     }
 }
 
-struct JfpHistSink {
-    unsigned *h;
-    __device__ __forceinline__ void sym(int s) { atomicAdd(h + s, 1u); }
-    __device__ __forceinline__ void bits(unsigned, int) {}
-    __device__ __forceinline__ void many(unsigned long long, int) {}
-};
-
 __global__ __launch_bounds__(kJfpThreads) void k_jfp_hist(JfpGeom g, const short *__restrict__ coef, const int *__restrict__ plen,
                                                           unsigned long long *__restrict__ hist)
 {
@@ -165,10 +151,10 @@ __global__ __launch_bounds__(kJfpThreads) void k_jfp_hist(JfpGeom g, const short
         if (s.Ss == 0) {
             bool chroma;
             const int pred = jfp_dc_pred(g, s, base, i, &chroma);
-            JfpHistSink sink{ cnt[threadIdx.x / 64][chroma ? 1 : 0] };
+            JeHist<unsigned> sink{ cnt[threadIdx.x / 64][chroma ? 1 : 0] };
             je_dc_first(base[i * 64], pred, s.Al, sink);
         } else {
-            JfpHistSink sink{ cnt[threadIdx.x / 64][0] };
+            JeHist<unsigned> sink{ cnt[threadIdx.x / 64][0] };
             const short *c = base + jfp_coef_block(g, s, i) * 64;
             if (s.Ah) je_ac_refine(c, s.Ss, s.Se, s.Al, sink); else je_ac_first(c, s.Ss, s.Se, s.Al, sink);
             const int run = plen[seg * g.T + s.ioff + i];
@@ -304,21 +290,11 @@ __global__ __launch_bounds__(kJfpThreads) void k_jfp_emit(JfpGeom g, const short
     jfp_stage_codes(g, s, seg, codes, lc);
     if (i >= s.n) return;
     const unsigned long long *p = pre + seg * (g.T + 1) + s.ioff;
-    long long pos = (long long)(p[i] - p[0]), total = (long long)(p[s.n] - p[0]);
-    bool last = i == s.n - 1;
-    if (s.R) {                                               // uniform: the item's place inside its byte-aligned restart interval
-        const unsigned long long *v = ivpre + seg * (g.NIV + 1) + s.ivoff;
-        const long long iv = i / s.per, lo = iv * s.per, hi = min(lo + s.per, s.n);
-        pos = 8 * (long long)(v[iv] - v[0]) + (long long)(p[i] - p[lo]);
-        total = (long long)(p[hi] - p[lo]);
-        last = i == hi - 1;
-    }
-    JeEmit sink{ nullptr, JeBits(stream + seg * g.stream_words + s.woff, pos, s.wcap) };
+    JrPlace at{ (long long)(p[i] - p[0]), (long long)(p[s.n] - p[0]), i == s.n - 1 };
+    if (s.R) at = jr_place(i, s.per, s.n, p, ivpre + seg * (g.NIV + 1) + s.ivoff);      // uniform: inside its byte-aligned restart interval
+    JeEmit sink{ nullptr, JeBits(stream + seg * g.stream_words + s.woff, at.pos, s.wcap) };
     jfp_item(g, s, seg, i, coef, plen, lc, sink);
-    if (last) {                                              // pad the last byte of the scan (of every restart interval) with 1-bits
-        const int pad = (int)((8 - (total & 7)) & 7);
-        if (pad) sink.bw.put((1u << pad) - 1, pad);
-    }
+    if (at.last) sink.bw.pad_ones(at.total);                 // the last byte of the scan (of every restart interval) is padded with 1-bits
     sink.bw.finish();
 }
 
@@ -412,13 +388,8 @@ __global__ __launch_bounds__(kJfpThreads) void k_jfp_scatter(JfpGeom g, const Jf
     const unsigned long long *ff = ffpre + seg * (g.n_chunks + 1);
     const unsigned char *src = reinterpret_cast<const unsigned char *>(stream + seg * g.stream_words + s.woff);
     unsigned char *dst = file + at + hl + lo + (long long)(ff[ch] - ff[s.coff]);
-    if (s.R) {                                               // uniform: the markers before this chunk shift it, those inside it are written here
-        const unsigned long long *starts = ivpre + seg * (g.NIV + 1) + s.ivoff;
-        const long long k = jr_first_from(starts, s.niv, lo);
-        jr_stuff_copy(dst + 2 * (k - 1), src, lo, hi, starts, s.niv, k);
-    } else {
-        js_stuff_copy(dst, src, lo, hi);
-    }
+    // uniform: with restarts the markers before this chunk shift it, those inside it are written here
+    jr_stuff_chunk(dst, src, lo, hi, s.R ? ivpre + seg * (g.NIV + 1) + s.ivoff : nullptr, s.R ? s.niv : 0);
 }
 
 // restarts: k_js_scan's input for the intervals' starts -- interval i of the launch (file after file, scan after scan inside a file),
@@ -627,13 +598,6 @@ static bool jfp_scan_args(const short *coefs, long long n, int Ss, int Se, int A
     return true;
 }
 
-struct JfpCountSink {
-    long long *h;
-    void sym(int s) { h[s]++; }
-    void bits(unsigned, int) {}
-    void many(unsigned long long, int) {}
-};
-
 int jfifprog_scan_host(const short *coefs, long long n, int Ss, int Se, int Ah, int Al, unsigned char *out, unsigned long long cap,
                        unsigned long long *out_len, long long *counts, long long *cuts)
 {
@@ -641,7 +605,7 @@ int jfifprog_scan_host(const short *coefs, long long n, int Ss, int Se, int Ah, 
     for (int i = 0; i < kJhSymbols; i++) counts[i] = 0;
     cuts[0] = cuts[1] = 0;
     std::vector<int> plen(n, 0);
-    JfpCountSink cs{ counts };
+    JeHist<unsigned long long> cs{ reinterpret_cast<unsigned long long *>(counts) };      // (the counts are not negative)
     auto block = [&](long long i, auto &sink) {              // item i as the kernels code it
         const short *c = coefs + i * 64;
         if (Ss == 0) {
@@ -694,10 +658,7 @@ int jfifprog_scan_host(const short *coefs, long long n, int Ss, int Se, int Ah, 
     for (long long i = 0; i < n; i++) {
         JeEmit em{ codes, JeBits(words.data(), pos[i], limit) };
         block(i, em);
-        if (i == n - 1) {
-            const int pad = (int)((8 - (pos[n] & 7)) & 7);
-            if (pad) em.bw.put((1u << pad) - 1, pad);
-        }
+        if (i == n - 1) em.bw.pad_ones(pos[n]);
         em.bw.finish();
     }
     const unsigned char *src = reinterpret_cast<const unsigned char *>(words.data());

@@ -38,6 +38,19 @@ AEJ_API int aej_test_jfif_prog_scan_host(const int16_t *coefs_host, int64_t n_bl
 AEJ_API int aej_test_jfif_prog_scan(aej_ctx *ctx, const int16_t *coefs_host, int64_t n_blocks, int Ss, int Se, int Ah, int Al, uint8_t *out_host,
                                     uint64_t capacity, uint64_t *out_len_host, int64_t *counts_host, int64_t *cuts_host);
 
+/* The baseline (sequential, interleaved) scan of given quantised coefficients, HOST only: the per-block coder, DC predictor, interval
+ * placement, padding and stuffing of csrc/jfif_prog_core.h, jfif_restart_core.h and jfif_stream_core.h -- the text the kernels of
+ * csrc/jfif.hip run -- stepped through on the CPU.  coefs_host: int16 [n_mcu * blocks per MCU][64], zigzag order, blocks in MCU order
+ * (hs * vs luma blocks in raster order, then Cb, Cr), |value| <= 2047 -- the layout aej_jfif_many_coefs_host returns.  hs, vs: the luma
+ * sampling factors, 1 or 2 each (1 x 2 is 4:4:0); ncomp 3, or 1 (grey: one block per MCU).  restart_interval: MCUs per restart
+ * interval, 0 for none (an interval requires optimize, as in the encoders).  optimize 0: the Annex K tables; 1: the optimal tables of
+ * the scan's own symbols.  hist_host gets the symbol counts [4][257] (DC luma, AC luma, DC chroma, AC chroma; grey: the first two),
+ * out_host the entropy-coded segment -- padded with 1-bits, 0xFF stuffed, RSTn markers included, without EOI -- and *out_len_host its
+ * length.  AEJ_ERR_ARG for a null pointer, a coefficient out of range, a bad layout or interval; AEJ_ERR_CAPACITY (with *out_len_host
+ * set) when capacity is too small.  (Addition: the ABI version stays 3.) */
+AEJ_API int aej_test_jfif_seq_scan_host(const int16_t *coefs_host, int64_t n_mcu, int hs, int vs, int ncomp, int restart_interval, int optimize,
+                                        int64_t *hist_host, uint8_t *out_host, uint64_t capacity, uint64_t *out_len_host);
+
 /* One block through the reduced inverse DCT of a scaled decode (aej_jpegdec_batch_scaled), HOST only: coef_host [64] quantised
  * coefficients and qt_host [64] quantisers, both in natural order; size 1, 2 or 4 (AEJ_ERR_ARG otherwise); out_host gets size x size
  * samples, row after row -- computed by the function of csrc/jpegdec_core.h that the kernel calls (jd_idct_sized). */
