@@ -241,6 +241,10 @@ SIGNATURES = {
     "aej_deflate_histogram": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _U64]),
     "aej_deflate_batch": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _P, _U64, _P, _P, _U64]),
     "aej_deflate_build_tables": (_I, [_P, _P, _P]),
+    "aej_deflate_bytes_workspace_bytes": (_U64, [_P, _I]),
+    "aej_deflate_bytes_histogram": (_I, [_P, _P, _U64, _P, _I, _P, _P, _U64]),
+    "aej_deflate_bytes_build_tables": (_I, [_P, _I, _P]),
+    "aej_deflate_bytes_batch": (_I, [_P, _P, _U64, _P, _I, _P, _I, _P, _U64, _P, _P, _U64]),
     "aej_pack_u8_levels_host": (_I, [_P, _I64, _P, _I]),
     "aej_decode_workspace_bytes": (_U64, [_P, _I, _I, _I]),
     "aej_decode_batch": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _U64]),
@@ -354,6 +358,8 @@ SIGNATURES = {
     "aej_png_parse_host": (_I, [_P, _U64, _P, _P, _I, _P, _I]),
     "aej_png_workspace_bytes": (_U64, [_P, _P, _I]),
     "aej_png_unfilter_batch": (_I, [_P, _P, _I, _P, _U64, _P, _P, _P, _P, _P, _P, _U64, _P, _P, _P, _U64]),
+    "aej_png_filter_bytes": (_U64, [_I, _I, _I]),
+    "aej_png_filter_batch": (_I, [_P, _P, _I, _I, _P, _U64]),
     "aej_test_jpegprog_coefs": (_I, [_P, _P, _P, _I, _P, _U64, _P, _I, _P, _U64, _P, _P, _U64]),             # include/aej_testing.h (tests only)
     "aej_test_jpegprog_coefs_host": (_I, [_P, _P, _P, _U64, _I, _P, _U64]),                                 # include/aej_testing.h (tests only)
     "aej_test_jpeg_adobe_pixels_host": (_I, [_P, _I64, _I, _I, _P]),                                        # include/aej_testing.h (tests only)

@@ -144,6 +144,21 @@ void launch_deflate_parse(hipStream_t st, const int *coeffs, const long long *co
 void launch_deflate(hipStream_t st, const int *coeffs, const long long *counts, int batch, long long coeff_stride, const long long *coeff_off,
                     const long long *coeff_cap, const unsigned *tables /* [3][448] or null */, int reuse_parse, unsigned char *out,
                     unsigned long long stream_stride, long long *sizes, void *workspace);
+// the same stage on byte streams of mixed lengths (aej_deflate_bytes_*: png_encode_many's filtered scanlines), one zlib stream per file
+constexpr int kBzGroup = 32;           // files per launch: their table travels in the kernel's arguments
+struct BzFile {
+    long long in_off, n_bytes;         // the stream in `in`: in_off a multiple of 4, whole dwords readable
+    long long out_off, out_cap;        // its slot in `out`: both multiples of 4
+    int chunk0;                        // its first chunk among the call's: the sum of deflate_bytes_chunks() of the files before it
+    int bpp, stride;                   // the distances always tried: a pixel and a scanline (1 + row bytes)
+    int pad;
+};
+struct BzGroup { BzFile f[kBzGroup]; };
+long long deflate_bytes_chunks(long long n_bytes);
+unsigned long long deflate_bytes_workspace_bytes(long long chunks, int n);
+void launch_deflate_bytes_parse(hipStream_t st, const unsigned char *in, const BzFile *files, int n, int *hist /* device [n][320] */, void *workspace);
+void launch_deflate_bytes(hipStream_t st, const unsigned char *in, const BzFile *files, int n, const unsigned *tables /* device [n][448] or null */,
+                          unsigned char *out, long long *sizes /* device [n] */, void *workspace);
 
 // inflate.hip -- zlib streams (RFC 1950 / 1951), one wave per stream.  desc: device [n][4] int64 = in_off, in_len, out_off, out_cap (bytes)
 void launch_inflate(hipStream_t st, const unsigned char *src, const long long *desc, int n, unsigned char *dst, long long dst_bytes,
@@ -614,5 +629,15 @@ long long png_carry_bytes(int rb, int bpp);
 // files first .. first + count of the call (count <= kPngGroup); the per-file arrays are the whole call's
 void launch_png_unfilter(hipStream_t st, const PngGroup &grp, int first, int count, const unsigned char *inflated, const long long *inflate_out_bytes,
                          const int *inflate_status, const unsigned char *palettes, unsigned char *out, unsigned char *carry, int *status);
+// the scanline filter of png_encode_many (aej_png_filter_batch): one wave per row, kPngGroup images per launch
+struct PngEncImage {
+    const unsigned char *src;          // H rows of rb bytes, contiguous (any alignment)
+    long long dst_off;                 // its scanline stream in `out`: H x (1 + rb) bytes
+    int rb, H;                         // bytes per row, rows
+    int row0;                          // its first row among the launch's rows
+    int bpp;                           // bytes per pixel: 1 .. 4
+};
+struct PngEncGroup { PngEncImage f[kPngGroup]; };
+void launch_png_filter(hipStream_t st, const PngEncGroup &grp, int count, int rows, int optimize, unsigned char *out);
 
 }  // namespace aej

@@ -331,3 +331,95 @@ extern "C" int aej_deflate_batch(aej_ctx *ctx, const int32_t *coeffs, const int6
                    streams, stream_stride, reinterpret_cast<long long *>(sizes), workspace);
     return deflate_finish(ctx, workspace, stream_stride);
 }
+
+// ---- the deflate of byte streams (csrc/deflate.hip, k_bz_*).  descs_host: [n][6] int64 = offset in `in`, bytes, bytes per pixel, bytes
+// per scanline, offset in `out`, bytes of the slot in `out` (the last two are read by aej_deflate_bytes_batch alone)
+namespace {
+constexpr long long kBzMaxBytes = 1ll << 40;
+int bz_files(aej_ctx *ctx, const char *fn, const int64_t *descs, int n, uint64_t in_bytes, bool with_out, uint64_t out_bytes, std::vector<BzFile> &files)
+{
+    if (n < 1 || !descs) return fail(ctx, AEJ_ERR_ARG, "%s: no streams", fn);
+    files.resize((size_t)n);
+    long long chunks = 0;
+    for (int i = 0; i < n; i++) {
+        const int64_t *d = descs + 6 * (int64_t)i;
+        BzFile &f = files[(size_t)i];
+        if (d[1] < 1 || d[1] > kBzMaxBytes) return fail(ctx, AEJ_ERR_ARG, "%s: stream %d: %lld bytes (1 .. 2^40)", fn, i, (long long)d[1]);
+        const unsigned long long whole = ((unsigned long long)d[1] + 3ull) & ~3ull;
+        if (d[0] < 0 || (d[0] & 3) || (unsigned long long)d[0] > in_bytes || whole > in_bytes - (unsigned long long)d[0])
+            return fail(ctx, AEJ_ERR_ARG, "%s: stream %d: outside the input (whole dwords), or an offset that is no multiple of 4", fn, i);
+        if (d[2] < 1 || d[2] > 4 || d[3] < 1 || d[3] > (1 << 26)) return fail(ctx, AEJ_ERR_ARG, "%s: stream %d: bytes per pixel %lld, per scanline %lld", fn, i, (long long)d[2], (long long)d[3]);
+        f.in_off = d[0]; f.n_bytes = d[1]; f.bpp = (int)d[2]; f.stride = (int)d[3]; f.out_off = 0; f.out_cap = 0; f.pad = 0;
+        if (with_out) {
+            if (d[4] < 0 || (d[4] & 3) || d[5] < 16 || (d[5] & 3) || (unsigned long long)d[4] > out_bytes || (unsigned long long)d[5] > out_bytes - (unsigned long long)d[4])
+                return fail(ctx, AEJ_ERR_ARG, "%s: stream %d: a slot outside the output, below 16 bytes, or no multiple of 4", fn, i);
+            f.out_off = d[4]; f.out_cap = d[5];
+        }
+        f.chunk0 = (int)chunks;
+        chunks += deflate_bytes_chunks(d[1]);
+        if (chunks > INT32_MAX) return fail(ctx, AEJ_ERR_ARG, "%s: more than 2^31 chunks in one call", fn);
+    }
+    return 0;
+}
+int bz_finish(aej_ctx *ctx, const char *fn, void *workspace)
+{
+    AEJ_HIP_CHECK(hipGetLastError());
+    AEJ_HIP_CHECK(hipMemcpyAsync(ctx->h_flag, workspace, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    AEJ_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (*ctx->h_flag) return fail(ctx, AEJ_ERR_CAPACITY, "%s: a deflate stream does not fit its slot (aej_deflate_stream_bound gives a safe size)", fn);
+    return 0;
+}
+}  // namespace
+
+extern "C" uint64_t aej_deflate_bytes_workspace_bytes(const int64_t *descs_host, int n)
+{
+    if (!descs_host || n < 1) return 0;
+    long long chunks = 0;
+    for (int i = 0; i < n; i++) {
+        const long long b = descs_host[6 * (int64_t)i + 1];
+        if (b < 1 || b > kBzMaxBytes) return 0;
+        chunks += deflate_bytes_chunks(b);
+        if (chunks > INT32_MAX) return 0;
+    }
+    return deflate_bytes_workspace_bytes(chunks, n);
+}
+
+extern "C" int aej_deflate_bytes_build_tables(const int32_t *hist_host, int n, uint32_t *tables_host)
+{
+    if (!hist_host || !tables_host || n < 1) return AEJ_ERR_ARG;
+    for (int i = 0; i < n; i++)
+        if (deflate_build_table_host(hist_host + (int64_t)i * AEJ_DEFLATE_HIST_BINS, 0, tables_host + (int64_t)i * AEJ_DEFLATE_TABLE_WORDS)) return AEJ_ERR_CAPACITY;
+    return 0;
+}
+
+extern "C" int aej_deflate_bytes_histogram(aej_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const int64_t *descs_host, int n, int32_t *hist, void *workspace,
+                                           uint64_t workspace_bytes)
+{
+    const char *fn = __func__;
+    AEJ_TRY(enter(ctx, fn));
+    if (!in || !hist || !workspace) return null_buffer(ctx, fn);
+    if ((reinterpret_cast<uintptr_t>(in) & 3) || (reinterpret_cast<uintptr_t>(workspace) & 255)) return fail(ctx, AEJ_ERR_ARG, "%s: in must be 4-byte and workspace 256-byte aligned", fn);
+    std::vector<BzFile> files;
+    AEJ_TRY(bz_files(ctx, fn, descs_host, n, in_bytes, false, 0, files));
+    AEJ_TRY(check_workspace(ctx, aej_deflate_bytes_workspace_bytes(descs_host, n), workspace_bytes));
+    AEJ_TRY(bind_device(ctx));
+    launch_deflate_bytes_parse(ctx->stream, in, files.data(), n, hist, workspace);
+    return bz_finish(ctx, fn, workspace);
+}
+
+extern "C" int aej_deflate_bytes_batch(aej_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const int64_t *descs_host, int n, const uint32_t *tables, int reuse_parse,
+                                       uint8_t *out, uint64_t out_bytes, int64_t *sizes, void *workspace, uint64_t workspace_bytes)
+{
+    const char *fn = __func__;
+    AEJ_TRY(enter(ctx, fn));
+    if (!in || !out || !sizes || !workspace) return null_buffer(ctx, fn);
+    if ((reinterpret_cast<uintptr_t>(in) & 3) || (reinterpret_cast<uintptr_t>(out) & 3) || (reinterpret_cast<uintptr_t>(workspace) & 255))
+        return fail(ctx, AEJ_ERR_ARG, "%s: in and out must be 4-byte and workspace 256-byte aligned", fn);
+    std::vector<BzFile> files;
+    AEJ_TRY(bz_files(ctx, fn, descs_host, n, in_bytes, true, out_bytes, files));
+    AEJ_TRY(check_workspace(ctx, aej_deflate_bytes_workspace_bytes(descs_host, n), workspace_bytes));
+    AEJ_TRY(bind_device(ctx));
+    if (!reuse_parse) launch_deflate_bytes_parse(ctx->stream, in, files.data(), n, nullptr, workspace);
+    launch_deflate_bytes(ctx->stream, in, files.data(), n, tables, out, reinterpret_cast<long long *>(sizes), workspace);
+    return bz_finish(ctx, fn, workspace);
+}

@@ -1,5 +1,5 @@
 // api_png.hip -- the PNG entries of the C ABI (include/aej.h): the host chunk walk (aej_png_parse_host) and the launch of the scanline
-// un-filter and layout conversion of csrc/png.hip (aej_png_unfilter_batch).  Host code only.
+// un-filter and layout conversion of csrc/png.hip (aej_png_unfilter_batch), and of its scanline filter (aej_png_filter_batch).  Host code only.
 #include "aej_ctx.h"
 
 using namespace aej;
@@ -199,6 +199,60 @@ extern "C" int aej_png_unfilter_batch(aej_ctx *ctx, const aej_png_desc *descs_ho
         launch_png_unfilter(ctx->stream, grp, first, count, inflated, reinterpret_cast<const long long *>(inflate_out_bytes), inflate_status,
                             palettes, out, static_cast<unsigned char *>(workspace), status);
         AEJ_HIP_CHECK(hipGetLastError());
+    }
+    return 0;
+}
+
+namespace {
+constexpr int kPngEncMaxRowBytes = 1 << 24;      // a row's cost sum (at most 128 per byte) stays inside an int
+bool png_enc_shape_ok(long long height, long long row_bytes, long long bpp)
+{
+    return height >= 1 && height <= kPngMaxSide && bpp >= 1 && bpp <= 4 && row_bytes >= bpp && row_bytes <= kPngEncMaxRowBytes && row_bytes % bpp == 0;
+}
+}  // namespace
+
+extern "C" uint64_t aej_png_filter_bytes(int height, int row_bytes, int bpp)
+{
+    return png_enc_shape_ok(height, row_bytes, bpp) ? (uint64_t)height * (1ull + (uint64_t)row_bytes) : 0;
+}
+
+extern "C" int aej_png_filter_batch(aej_ctx *ctx, const int64_t *descs_host, int n, int optimize, uint8_t *out, uint64_t out_bytes)
+{
+    const char *fn = __func__;
+    AEJ_TRY(enter(ctx, fn));
+    if (n < 1 || !descs_host) return fail(ctx, AEJ_ERR_ARG, "%s: no images", fn);
+    if (!out) return null_buffer(ctx, fn);
+    if (reinterpret_cast<uintptr_t>(out) & 3) return fail(ctx, AEJ_ERR_ARG, "%s: out must be 4-byte aligned", fn);
+    for (int i = 0; i < n; i++) {
+        const int64_t *d = descs_host + 5 * (int64_t)i;      // source pointer, height, row bytes, bytes per pixel, offset in out
+        if (!d[0]) return fail(ctx, AEJ_ERR_ARG, "%s: image %d: NULL source", fn, i);
+        if (!png_enc_shape_ok(d[1], d[2], d[3]))
+            return fail(ctx, AEJ_ERR_ARG, "%s: image %d: height %lld, row bytes %lld, bytes per pixel %lld (1 .. 2^24 rows of 1 .. 2^24 bytes, whole pixels of 1 .. 4 bytes)",
+                        fn, i, (long long)d[1], (long long)d[2], (long long)d[3]);
+        const unsigned long long need = (unsigned long long)d[1] * (1ull + (unsigned long long)d[2]);
+        if (d[4] < 0 || (unsigned long long)d[4] > out_bytes || need > out_bytes - (unsigned long long)d[4])
+            return fail(ctx, AEJ_ERR_ARG, "%s: image %d: scanlines outside the output", fn, i);
+    }
+    AEJ_TRY(bind_device(ctx));
+    for (int first = 0; first < n;) {
+        PngEncGroup grp{};
+        int count = 0;
+        long long rows = 0;
+        for (; count < kPngGroup && first + count < n; count++) {
+            const int64_t *d = descs_host + 5 * (int64_t)(first + count);
+            if (rows + d[1] > INT32_MAX) break;              // (count >= 1: a height is at most 2^24)
+            PngEncImage &f = grp.f[count];
+            f.src = reinterpret_cast<const unsigned char *>(static_cast<uintptr_t>(d[0]));
+            f.H = (int)d[1];
+            f.rb = (int)d[2];
+            f.bpp = (int)d[3];
+            f.dst_off = d[4];
+            f.row0 = (int)rows;
+            rows += d[1];
+        }
+        launch_png_filter(ctx->stream, grp, count, (int)rows, optimize ? 1 : 0, out);
+        AEJ_HIP_CHECK(hipGetLastError());
+        first += count;
     }
     return 0;
 }

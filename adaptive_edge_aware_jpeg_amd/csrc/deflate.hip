@@ -25,6 +25,9 @@
 //   k_lz_scan    per stream: which code, the bit offset of every chunk, zlib header, Adler-32, stream size.
 //   k_lz_emit    the chunks' bit strings, assembled in LDS and written at their BIT offset (boundary words by atomicOr).
 // Everything is deterministic: the same input gives the same bytes.
+//
+// Further down, the same four passes on BYTE streams of mixed lengths (k_bz_*, aej_deflate_bytes_*): the filtered scanlines of
+// png_encode_many, where a match may start at any byte.  The scan, the sort, the bit sinks and the symbol arithmetic are shared.
 #include "aej_common.h"
 #include "aej_launch.h"
 #include <string.h>
@@ -138,6 +141,51 @@ __device__ __forceinline__ void lz_stage(const unsigned *src, long long c0, int 
     if (threadIdx.x < 4) sIn[kLzChunkDw + threadIdx.x] = 0u;
 }
 
+// Bitonic sort of N keys in LDS by the kLzThreads threads of the workgroup (both parse kernels); ends with a barrier.
+template <int N>
+__device__ __forceinline__ void lz_sort_keys(unsigned *keys, int tid)
+{
+    // A thread owns eight consecutive keys: the passes of strides 4, 2, 1 of a stage exchange keys inside such a group and run
+    // in registers (one LDS round trip and one barrier instead of three of each); the wider strides go through the LDS, a pass each.
+    static_assert(N % (8 * kLzThreads) == 0 && (N & (N - 1)) == 0, "groups of eight keys, a whole number per thread");
+    auto local_passes = [&](int k, int jmax, int g) {                      // strides jmax, jmax / 2, ... 1 (jmax <= 4) of stage k, keys 8 g .. 8 g + 7
+        unsigned v[8];
+        const uint4 lo = *reinterpret_cast<const uint4 *>(&keys[8 * g]), hi = *reinterpret_cast<const uint4 *>(&keys[8 * g + 4]);
+        v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w; v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
+#pragma unroll
+        for (int j = 4; j > 0; j >>= 1) {
+            if (j <= jmax) {
+#pragma unroll
+                for (int e = 0; e < 8; e++) {
+                    if ((e & j) == 0) {
+                        const bool up = ((8 * g + e) & k) == 0;
+                        const unsigned a = v[e], c2 = v[e | j];
+                        const bool sw = (a > c2) == up;
+                        v[e] = sw ? c2 : a; v[e | j] = sw ? a : c2;
+                    }
+                }
+            }
+        }
+        *reinterpret_cast<uint4 *>(&keys[8 * g]) = make_uint4(v[0], v[1], v[2], v[3]);
+        *reinterpret_cast<uint4 *>(&keys[8 * g + 4]) = make_uint4(v[4], v[5], v[6], v[7]);
+    };
+    for (int k = 2; k <= N; k <<= 1) {
+        int j = k >> 1;
+        for (; j > 4; j >>= 1) {
+            for (int t = tid; t < N / 2; t += kLzThreads) {
+                const int i = 2 * t - (t & (j - 1));           // the lower index of pair t for stride j
+                const int p = i + j;
+                const unsigned a = keys[i], bkey = keys[p];
+                const bool up = (i & k) == 0;
+                if ((a > bkey) == up) { keys[i] = bkey; keys[p] = a; }
+            }
+            __syncthreads();
+        }
+        for (int g = tid; g < N / 8; g += kLzThreads) local_passes(k, j, g);
+        __syncthreads();
+    }
+}
+
 struct LzLds {
     unsigned in[kLzChunkDw + 4];
     unsigned keys[kLzChunkDw];           // sort keys (hash << 13 | position); afterwards the DP's cost rows
@@ -172,45 +220,7 @@ __global__ __launch_bounds__(kLzThreads) void k_lz_parse(LzStreams S)
     for (int i = tid; i < kLzChunkDw; i += kLzThreads)
         L.keys[i] = i < len ? (lz_hash(L.in[i], L.in[i + 1]) << 13) | (unsigned)i : 0xffffffffu;
     __syncthreads();
-    // Bitonic sort.  A thread owns eight consecutive keys: the passes of strides 4, 2, 1 of a stage exchange keys inside such a group and run
-    // in registers (one LDS round trip and one barrier instead of three of each); the wider strides go through the LDS, a pass each.
-    static_assert(kLzChunkDw == 8 * kLzThreads, "eight keys per thread");
-    auto local_passes = [&](int k, int jmax) {                             // strides jmax, jmax / 2, ... 1 (jmax <= 4) of stage k
-        unsigned v[8];
-        const uint4 lo = *reinterpret_cast<const uint4 *>(&L.keys[8 * tid]), hi = *reinterpret_cast<const uint4 *>(&L.keys[8 * tid + 4]);
-        v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w; v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
-#pragma unroll
-        for (int j = 4; j > 0; j >>= 1) {
-            if (j <= jmax) {
-#pragma unroll
-                for (int e = 0; e < 8; e++) {
-                    if ((e & j) == 0) {
-                        const bool up = ((8 * tid + e) & k) == 0;
-                        const unsigned a = v[e], c2 = v[e | j];
-                        const bool sw = (a > c2) == up;
-                        v[e] = sw ? c2 : a; v[e | j] = sw ? a : c2;
-                    }
-                }
-            }
-        }
-        *reinterpret_cast<uint4 *>(&L.keys[8 * tid]) = make_uint4(v[0], v[1], v[2], v[3]);
-        *reinterpret_cast<uint4 *>(&L.keys[8 * tid + 4]) = make_uint4(v[4], v[5], v[6], v[7]);
-    };
-    for (int k = 2; k <= kLzChunkDw; k <<= 1) {
-        int j = k >> 1;
-        for (; j > 4; j >>= 1) {
-            for (int t = tid; t < kLzChunkDw / 2; t += kLzThreads) {
-                const int i = 2 * t - (t & (j - 1));           // the lower index of pair t for stride j
-                const int p = i + j;
-                const unsigned a = L.keys[i], bkey = L.keys[p];
-                const bool up = (i & k) == 0;
-                if ((a > bkey) == up) { L.keys[i] = bkey; L.keys[p] = a; }
-            }
-            __syncthreads();
-        }
-        local_passes(k, j);
-        __syncthreads();
-    }
+    lz_sort_keys<kLzChunkDw>(L.keys, tid);
     // ---- (2a) the kLzNear nearest positions.  A wave per sub-block, a lane per position: bit j of eq[d] (a ballot) says "coefficient j equals
     // the one d before it", so the run of matches behind a position is a shift and a count-trailing-ones -- no walk (inside a run of zeros
     // every walk would be as long as the rest of the sub-block).  Distances ascend, so at equal length the nearer one stays.
@@ -556,17 +566,24 @@ __global__ __launch_bounds__(kLzSubs) void k_lz_sizes(LzStreams S)
 }
 
 // Pass 3 (one workgroup per stream): which code, bit offsets of the chunks, zlib header, Adler-32, the stream's size.
-__global__ __launch_bounds__(256) void k_lz_scan(LzStreams S)
+// The workspace arrays of the chunks (LzStreams / BzStreams) and what the scan says about each stream.
+struct LzScanArrays {
+    const unsigned *chunk_bits, *chunk_adler;
+    const unsigned char *chunk_missing;
+    unsigned long long *chunk_pos;
+    unsigned char *stream_fixed;
+    long long *sizes;
+    int *error;
+};
+// Stream s: its chunks are g0 .. g0 + nchunks of the arrays, of chunk_bytes input bytes each (n_bytes in all); tab = its dynamic code or
+// null; out = its slot of `cap` bytes (4-byte aligned, a multiple of 4).  Called by all 256 threads of the workgroup.
+__device__ __forceinline__ void lz_scan_stream(const LzScanArrays &S, int s, long long g0, int nchunks, long long n_bytes, int chunk_bytes, const unsigned *tab,
+                                               unsigned char *out, unsigned long long cap)
 {
     __shared__ unsigned long long sCarry, sTot[2];
     __shared__ unsigned long long sWave[4];
     __shared__ int sMissing, sFixed;
-    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-    const int b = s / 3, l = s - 3 * b;
-    long long n_dw;
-    (void)lz_stream_of(S, s, n_dw);
-    const int nchunks = (int)((n_dw + kLzChunkDw - 1) / kLzChunkDw);
-    const long long g0 = (long long)b * S.chunk_off[3] + S.chunk_off[l];
+    const int tid = threadIdx.x, lane = tid & 63;
     // totals under both codes, any missing symbol
     unsigned long long tf = 0, td = 0;
     int miss = 0;
@@ -577,7 +594,6 @@ __global__ __launch_bounds__(256) void k_lz_scan(LzStreams S)
     if (miss) sMissing = 1;
     if (lane == 0) { atomicAdd(&sTot[0], tf); atomicAdd(&sTot[1], td); }
     __syncthreads();
-    const unsigned *tab = S.tables ? S.tables + l * kDefTableWords : nullptr;
     if (tid == 0) {
         // block header + tokens + end of block
         const unsigned long long bits_fixed = 3ull + sTot[0] + 7ull;
@@ -605,11 +621,10 @@ __global__ __launch_bounds__(256) void k_lz_scan(LzStreams S)
         if (tid == 255) sCarry = carry + wbase + inc;
         __syncthreads();
     }
-    unsigned char *out = S.out + (unsigned long long)s * S.stream_stride;
     const unsigned long long end_bits = sCarry + (sFixed ? 7ull : (unsigned long long)(tab[256] >> 16));      // ... + end of block
     const unsigned long long body_end = (end_bits + 7ull) / 8ull;
     const unsigned long long total = body_end + 4ull;
-    if (total > S.stream_stride) { if (tid == 0) { S.sizes[s] = (long long)total; atomicMax(S.error, 1); } return; }
+    if (total > cap) { if (tid == 0) { S.sizes[s] = (long long)total; atomicMax(S.error, 1); } return; }
     // The emit pass stores a chunk's inner words and ORs its first and last word into the stream (they are shared with the neighbours, the
     // block header and the end-of-block code): zero exactly those words, and everything from the last chunk's end to the Adler-32.
     unsigned *ow = reinterpret_cast<unsigned *>(out);
@@ -641,9 +656,8 @@ __global__ __launch_bounds__(256) void k_lz_scan(LzStreams S)
         }
         unsigned A = 1, Bs = 0;
         const unsigned *ad = S.chunk_adler + g0 * 2;
-        const long long n_bytes = 4 * n_dw;
         for (int i = 0; i < nchunks; i++) {
-            const long long len = (long long)(i + 1) * kLzChunkBytes <= n_bytes ? kLzChunkBytes : n_bytes - (long long)i * kLzChunkBytes;
+            const long long len = (long long)(i + 1) * chunk_bytes <= n_bytes ? chunk_bytes : n_bytes - (long long)i * chunk_bytes;
             Bs = (unsigned)((Bs + (unsigned long long)(len % kAdlerMod) * A + ad[2 * i + 1]) % kAdlerMod);
             A = (A + ad[2 * i]) % kAdlerMod;
         }
@@ -651,6 +665,17 @@ __global__ __launch_bounds__(256) void k_lz_scan(LzStreams S)
         out[body_end] = (unsigned char)(adler >> 24); out[body_end + 1] = (unsigned char)(adler >> 16);
         out[body_end + 2] = (unsigned char)(adler >> 8); out[body_end + 3] = (unsigned char)adler;
     }
+}
+
+__global__ __launch_bounds__(256) void k_lz_scan(LzStreams S)
+{
+    const int s = blockIdx.x;
+    const int b = s / 3, l = s - 3 * b;
+    long long n_dw;
+    (void)lz_stream_of(S, s, n_dw);
+    const LzScanArrays A{ S.chunk_bits, S.chunk_adler, S.chunk_missing, S.chunk_pos, S.stream_fixed, S.sizes, S.error };
+    lz_scan_stream(A, s, (long long)b * S.chunk_off[3] + S.chunk_off[l], (int)((n_dw + kLzChunkDw - 1) / kLzChunkDw), 4 * n_dw, kLzChunkBytes,
+                   S.tables ? S.tables + l * kDefTableWords : nullptr, S.out + (unsigned long long)s * S.stream_stride, S.stream_stride);
 }
 
 // Pass 4: the chunks' bit strings, assembled in LDS and ORed into the stream at their bit offset.
@@ -703,6 +728,315 @@ __global__ __launch_bounds__(kLzSubs) void k_lz_emit(LzStreams S)
     const unsigned nwords = (total + 31u) / 32u;
     unsigned *dst = reinterpret_cast<unsigned *>(S.out + (unsigned long long)s * S.stream_stride) + (pos >> 5);
     // the first and the last word are shared with the neighbouring chunks (and the block header / end of block): OR; the rest are this chunk's alone
+    for (unsigned i = tid; i < nwords; i += kLzSubs) {
+        const unsigned v = sOut[i];
+        if (i == 0 || i == nwords - 1) { if (v) atomicOr(&dst[i], v); }
+        else dst[i] = v;
+    }
+}
+
+// ---- the deflate of byte streams (aej_deflate_bytes_*: the filtered scanlines of png_encode_many) ---------------------------------------
+// The same four passes on BYTE positions.  A chunk is kBzChunk = 8192 bytes of one file's stream, so that the sub-block count and the
+// sizes / scan / emit arithmetic are the ones above (128 sub-blocks of 64, one thread each); the sort takes the chunk's positions and
+// the 8192 before them (16384 keys: measured against 8192 in EXPERIMENTS.md; 32768 keys do not fit the LDS).  A chunk's matches may
+// start up to kBzHist bytes before it: the parse stages that history in LDS with the chunk, because the distances that pay in filtered
+// scanlines are the pixel (bpp, 2 bpp) and the scanline (1 + row bytes, a pixel either side of it, and its multiples), and a scanline
+// of a large image is longer than a chunk.
+//   k_bz_parse   (1) positions sorted by (hash of the next three bytes, position): the predecessors with the same hash are the chain,
+//                nearest first.  (2) A thread per position tries the kBzNear fixed distances and up to kBzRows whole scanlines (into the
+//                history as well) and up to kBzDepth chain entries (inside the chunk and the kBzSortHist bytes before it), and keeps
+//                the match with the best saving under the static cost model.  (3) A thread per 64-byte sub-block chooses literals or
+//                matches by dynamic programming (matches are clipped to the sub-block) and writes one token word per position:
+//                0 = literal, L | D << 8 = match of L >= 3 bytes at distance D.
+//   k_bz_sizes, k_bz_scan, k_bz_emit: as above, per file; the scan is the same routine (lz_scan_stream).
+constexpr int kBzChunk = kLzChunkDw;                // byte positions per chunk
+constexpr int kBzSub = kLzSubDw;                    // bytes per sub-block
+constexpr int kBzHist = 24576;                      // bytes before the chunk a match may start in: chunk + history = one deflate window
+#ifndef AEJ_BZ_SORT_HIST
+#define AEJ_BZ_SORT_HIST 8192                       // (a build-time choice so that both values can be timed: EXPERIMENTS.md)
+#endif
+constexpr int kBzSortHist = AEJ_BZ_SORT_HIST;       // history positions that are hashed and sorted with the chunk's, so that chains reach them: 0 or 8192
+constexpr int kBzSort = kBzChunk + kBzSortHist;     // sorted positions per workgroup (a key each in LDS: 16384 is the most that fits beside the bytes)
+constexpr int kBzPosBits = kBzSort == 8192 ? 13 : 14;
+static_assert(kBzSort == 8192 || kBzSort == 16384, "the sort takes a power of two; 32768 keys alone are 128 KiB of LDS");
+constexpr int kBzDepth = 16;                        // chain entries tried per position
+constexpr int kBzNear = 5;                          // fixed distances always tried ...
+constexpr int kBzRows = 16;                         // ... and this many whole scanlines
+constexpr int kBzPad = 16;
+static_assert(kBzHist + kBzChunk <= 32768, "distances stay inside deflate's window");
+static_assert(kBzSub <= 255, "a match length fits the token's low byte");
+
+struct BzStreams {
+    BzGroup grp;                  // the files of this launch: blockIdx.y
+    int first;                    // index of grp.f[0] in the call: hist, tables, sizes and stream_fixed are the whole call's
+    const unsigned char *in;
+    unsigned char *out;
+    unsigned *tokens;             // [chunks][kBzChunk]
+    unsigned *chunk_bits, *chunk_adler;
+    unsigned char *chunk_missing;
+    unsigned short *sub_bits;     // [chunks][kLzSubs][2]
+    unsigned long long *chunk_pos;
+    unsigned char *stream_fixed;  // [n]
+    const unsigned *tables;       // [n][kDefTableWords] or null
+    long long *sizes;             // [n]
+    int *hist;                    // [n][kDefHistBins] (parse only; may be null)
+    int *error;
+};
+
+struct BzLds {
+    unsigned char in[kBzHist + kBzChunk + kBzPad];      // the history, then the chunk (zeros beyond its end)
+    unsigned keys[kBzSort];              // sort keys (hash << kBzPosBits | position, history first); afterwards the DP's cost rows
+    unsigned res[kBzChunk];              // best match of the position: L | D << 8; bit 31: the DP takes it
+    int hist[kDefHistBins];
+};
+static_assert(sizeof(BzLds) <= 160 * 1024, "one workgroup per CU");
+
+// static bit-cost model in eighths of a bit: filtered scanlines are small residuals around 0 (mod 256)
+__device__ __forceinline__ int bz_lit_cost(unsigned b)
+{
+    const unsigned v = b < 128u ? b : 256u - b;
+    return v == 0u ? 24 : v < 3u ? 40 : v < 9u ? 52 : v < 33u ? 64 : 80;
+}
+__device__ __forceinline__ int bz_match_cost(int L, int D) { return lz_len_cost(L) + lz_dist_cost(D); }
+
+// the chunk's bytes as the sizes and emit passes need them: whole dwords of the stream (in_off and c0 are multiples of 4), zeros beyond len
+__device__ __forceinline__ void bz_stage_chunk(const unsigned char *src, int len, unsigned *dst, int nthreads)
+{
+    for (int i = threadIdx.x * 4; i < kBzChunk; i += nthreads * 4) {
+        unsigned v = 0u;
+        if (i < len) v = *reinterpret_cast<const unsigned *>(src + i);
+        if (i + 4 > len && i < len) v &= (1u << (8 * (len - i))) - 1u;
+        dst[i >> 2] = v;
+    }
+}
+
+__global__ __launch_bounds__(kLzThreads) void k_bz_parse(BzStreams S)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lz_smem[];
+    BzLds &L = *reinterpret_cast<BzLds *>(lz_smem);
+    const BzFile f = S.grp.f[blockIdx.y];
+    const int c = blockIdx.x, tid = threadIdx.x;
+    const long long c0 = (long long)c * kBzChunk;
+    if (c0 >= f.n_bytes) return;
+    const int len = (int)(f.n_bytes - c0 < kBzChunk ? f.n_bytes - c0 : kBzChunk);
+    const int h0 = (int)(c0 < kBzHist ? c0 : kBzHist);                     // history bytes there are: a multiple of 4
+    {
+        const unsigned char *src = S.in + f.in_off + c0;
+        unsigned *dst = reinterpret_cast<unsigned *>(L.in);
+        for (int i = -h0 + 4 * tid; i < kBzChunk + kBzPad; i += 4 * kLzThreads) {
+            unsigned v = 0u;
+            if (i < len) v = *reinterpret_cast<const unsigned *>(src + i);
+            if (i + 4 > len && i < len) v &= (1u << (8 * (len - i))) - 1u;
+            dst[(kBzHist + i) >> 2] = v;
+        }
+    }
+    for (int i = tid; i < kDefHistBins; i += kLzThreads) L.hist[i] = 0;
+    __syncthreads();
+    const unsigned char *in = L.in + kBzHist;                              // in[i]: byte i of the chunk; in[-d]: history
+    for (int p = tid; p < kBzSort; p += kLzThreads) {                      // sorted position p is byte p - kBzSortHist of the chunk
+        const int i = p - kBzSortHist;
+        const unsigned v = (unsigned)in[i] | ((unsigned)in[i + 1] << 8) | ((unsigned)in[i + 2] << 16);
+        L.keys[p] = i >= -h0 && i + 2 < len ? (((v * 2654435761u) >> kBzPosBits) << kBzPosBits) | (unsigned)p : 0xffffffffu;      // (a match needs three bytes)
+        if (i >= 0) L.res[i] = 0u;
+    }
+    __syncthreads();
+    lz_sort_keys<kBzSort>(L.keys, tid);
+    // ---- (2) the best match of every position
+    const int stride = f.stride;
+    const int near[kBzNear] = { 1, f.bpp, 2 * f.bpp, stride - f.bpp, stride + f.bpp };
+    for (int ks = tid; ks < kBzSort; ks += kLzThreads) {
+        const unsigned key = L.keys[ks];
+        if (key == 0xffffffffu) continue;
+        const int i = (int)(key & (unsigned)(kBzSort - 1)) - kBzSortHist;
+        if (i < 0) continue;                                               // a history position: a source only
+        int maxl = len - i;
+        const int to_sub_end = kBzSub - (i & (kBzSub - 1));
+        maxl = maxl < to_sub_end ? maxl : to_sub_end;
+        if (maxl < 3) continue;
+        int best = 0, bd = 0, bscore = 0;
+        auto consider = [&](int d) {
+            const unsigned char *p = in + i, *q = p - d;
+            if (p[0] != q[0] || p[1] != q[1] || p[2] != q[2]) return;
+            int m = 3;
+            while (m < maxl && p[m] == q[m]) m++;
+            const int sc = 56 * m - bz_match_cost(m, d);                   // what the match saves against literals of 7 bits
+            if (sc > bscore) { bscore = sc; best = m; bd = d; }
+        };
+#pragma unroll
+        for (int k = 0; k < kBzNear; k++) {
+            const int d = near[k];
+            if (d >= 1 && d <= i + h0 && d <= 32768 && best < maxl) consider(d);
+        }
+        // the same column of the rows above, as far up as the history goes: what repeats down an image (tiles, glyphs, dithering)
+        for (int k = 1, d = stride; k <= kBzRows && d <= i + h0 && d <= 32768 && best < maxl; k++, d += stride) consider(d);
+        const unsigned h = key >> kBzPosBits;
+        for (int t = 1; t <= kBzDepth && ks - t >= 0 && best < maxl; t++) {
+            const unsigned k2 = L.keys[ks - t];
+            if ((k2 >> kBzPosBits) != h) break;
+            consider(i + kBzSortHist - (int)(k2 & (unsigned)(kBzSort - 1)));      // (same hash: sorted by position, so the distance is positive)
+        }
+        if (best >= 3) L.res[i] = (unsigned)best | ((unsigned)bd << 8);
+    }
+    __syncthreads();
+    // ---- (3) parse: one thread per sub-block, backward dynamic programming over the static costs, then the tokens front to back
+    unsigned short *cost = reinterpret_cast<unsigned short *>(L.keys);     // [kLzSubs][kBzSub + 2]
+    if (tid < kLzSubs) {
+        const int s0 = tid * kBzSub;
+        const int sn = len - s0 < kBzSub ? len - s0 : kBzSub;
+        if (sn > 0) {
+            unsigned short *cs = cost + tid * (kBzSub + 2);
+            cs[sn] = 0;
+            for (int j = sn - 1; j >= 0; j--) {
+                const unsigned r = L.res[s0 + j];
+                const int Lm = (int)(r & 255u);
+                int bestc = bz_lit_cost(in[s0 + j]) + cs[j + 1];
+                bool take = false;
+                if (Lm >= 3 && j + Lm <= sn) {
+                    const int cm = bz_match_cost(Lm, (int)((r >> 8) & 0xffffu)) + cs[j + Lm];
+                    if (cm < bestc) { bestc = cm; take = true; }
+                }
+                cs[j] = (unsigned short)bestc;
+                L.res[s0 + j] = (r & 0x7fffffffu) | (take ? 0x80000000u : 0u);
+            }
+            unsigned *tok = S.tokens + ((long long)f.chunk0 + c) * kBzChunk + s0;
+            for (int j = 0; j < sn;) {
+                const unsigned r = L.res[s0 + j];
+                if (r >> 31) {
+                    const int Lm = (int)(r & 255u), d = (int)((r >> 8) & 0xffffu);
+                    tok[j] = r & 0x00ffffffu;
+                    int eb; unsigned ex;
+                    atomicAdd(&L.hist[lz_len_sym(Lm, eb, ex)], 1);
+                    atomicAdd(&L.hist[kDefLitLen + lz_dist_sym(d, eb, ex)], 1);
+                    j += Lm;
+                } else {
+                    tok[j] = 0u;
+                    atomicAdd(&L.hist[in[s0 + j]], 1);
+                    j++;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (S.hist) {
+        int *gh = S.hist + (long long)(S.first + blockIdx.y) * kDefHistBins;
+        for (int i = tid; i < kDefHistBins; i += kLzThreads) if (L.hist[i]) atomicAdd(&gh[i], L.hist[i]);
+        if (tid == 0 && c0 + len >= f.n_bytes) atomicAdd(&gh[256], 1);     // the stream's end-of-block symbol
+    }
+}
+
+// the tokens of one sub-block of bytes, front to back
+template <typename V>
+__device__ __forceinline__ void bz_walk(const unsigned *tok, const unsigned char *in, int sn, V &&visit)
+{
+    for (int j = 0; j < sn;) {
+        const unsigned t = tok[j];
+        const int Lm = (int)(t & 255u), d = (int)((t >> 8) & 0xffffu);
+        if (Lm >= 3 && Lm <= sn - j && d >= 1 && d <= 32768) { visit.match(Lm, d); j += Lm; }      // (anything else in a corrupt workspace reads as a literal)
+        else { visit.lit(in[j]); j++; }
+    }
+}
+
+__device__ __forceinline__ const unsigned *bz_load_table(const BzStreams &S, int file, unsigned *sTab)
+{
+    if (!S.tables) return nullptr;
+    const unsigned *t = S.tables + (long long)file * kDefTableWords;
+    for (int i = threadIdx.x; i < kDefTabHdr; i += blockDim.x) sTab[i] = t[i];
+    return sTab;
+}
+
+__global__ __launch_bounds__(kLzSubs) void k_bz_sizes(BzStreams S)
+{
+    __shared__ unsigned sIn[kBzChunk / 4];
+    __shared__ unsigned sTab[kDefTabHdr];
+    __shared__ unsigned sRed[5][kLzSubs / 64];
+    const BzFile f = S.grp.f[blockIdx.y];
+    const int c = blockIdx.x, tid = threadIdx.x;
+    const long long c0 = (long long)c * kBzChunk;
+    if (c0 >= f.n_bytes) return;
+    const long long g = (long long)f.chunk0 + c;
+    const int len = (int)(f.n_bytes - c0 < kBzChunk ? f.n_bytes - c0 : kBzChunk);
+    bz_stage_chunk(S.in + f.in_off + c0, len, sIn, kLzSubs);
+    const unsigned *tab = bz_load_table(S, S.first + blockIdx.y, sTab);
+    __syncthreads();
+    const unsigned char *in = reinterpret_cast<const unsigned char *>(sIn);
+    const int s0 = tid * kBzSub;
+    const int sn = len - s0 < kBzSub ? (len - s0 > 0 ? len - s0 : 0) : kBzSub;
+    LzCountBits cnt;
+    cnt.tab = tab;
+    unsigned a = 0, m = 0;
+    if (sn > 0) {
+        bz_walk(S.tokens + g * kBzChunk + s0, in + s0, sn, cnt);
+        for (int i = 0; i < sn; i++) { a += in[s0 + i]; m += (unsigned)i * in[s0 + i]; }
+    }
+    S.sub_bits[(g * kLzSubs + tid) * 2] = (unsigned short)cnt.fixed;
+    S.sub_bits[(g * kLzSubs + tid) * 2 + 1] = (unsigned short)cnt.dyn;
+    // sum of (len - i) * byte over the chunk = sum over sub-blocks of [(len - s0) * a - m]
+    const unsigned long long wsum = sn > 0 ? (unsigned long long)(len - s0) * a - m : 0ull;
+    unsigned vf = (unsigned)cnt.fixed, vd = (unsigned)cnt.dyn, va = a, vw = (unsigned)(wsum % kAdlerMod), vm = cnt.missing ? 1u : 0u;
+    for (int o = 32; o > 0; o >>= 1) { vf += __shfl_down(vf, o); vd += __shfl_down(vd, o); va += __shfl_down(va, o); vw += __shfl_down(vw, o); vm += __shfl_down(vm, o); }
+    if ((tid & 63) == 0) { sRed[0][tid >> 6] = vf; sRed[1][tid >> 6] = vd; sRed[2][tid >> 6] = va; sRed[3][tid >> 6] = vw; sRed[4][tid >> 6] = vm; }
+    __syncthreads();
+    if (tid == 0) {
+        unsigned tf = 0, td = 0, ta = 0, tw = 0, tm = 0;
+        for (int k = 0; k < kLzSubs / 64; k++) { tf += sRed[0][k]; td += sRed[1][k]; ta += sRed[2][k]; tw += sRed[3][k]; tm += sRed[4][k]; }
+        S.chunk_bits[g * 2] = tf;
+        S.chunk_bits[g * 2 + 1] = td;
+        S.chunk_missing[g] = tm ? 1 : 0;
+        S.chunk_adler[g * 2] = ta % kAdlerMod;
+        S.chunk_adler[g * 2 + 1] = tw % kAdlerMod;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_bz_scan(BzStreams S)
+{
+    const BzFile f = S.grp.f[blockIdx.x];
+    const int s = S.first + blockIdx.x;
+    const LzScanArrays A{ S.chunk_bits, S.chunk_adler, S.chunk_missing, S.chunk_pos, S.stream_fixed, S.sizes, S.error };
+    lz_scan_stream(A, s, f.chunk0, (int)((f.n_bytes + kBzChunk - 1) / kBzChunk), f.n_bytes, kBzChunk,
+                   S.tables ? S.tables + (long long)s * kDefTableWords : nullptr, S.out + f.out_off, (unsigned long long)f.out_cap);
+}
+
+constexpr int kBzOutWords = kBzChunk * 16 / 32 + 8;               // the worst a dynamic code can do: a match of three bytes in 15 + 5 + 15 + 13 bits
+__global__ __launch_bounds__(kLzSubs) void k_bz_emit(BzStreams S)
+{
+    __shared__ unsigned sIn[kBzChunk / 4];
+    __shared__ unsigned sOut[kBzOutWords];
+    __shared__ unsigned sTab[kDefTabHdr];
+    __shared__ unsigned sWaveBits[kLzSubs / 64];
+    const BzFile f = S.grp.f[blockIdx.y];
+    const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int s = S.first + blockIdx.y;
+    const long long c0 = (long long)c * kBzChunk;
+    if (c0 >= f.n_bytes || *S.error) return;
+    const long long g = (long long)f.chunk0 + c;
+    const int len = (int)(f.n_bytes - c0 < kBzChunk ? f.n_bytes - c0 : kBzChunk);
+    bz_stage_chunk(S.in + f.in_off + c0, len, sIn, kLzSubs);
+    const int fixed = S.stream_fixed[s];
+    const unsigned *tab = fixed ? nullptr : bz_load_table(S, s, sTab);
+    for (int i = tid; i < kBzOutWords; i += kLzSubs) sOut[i] = 0u;
+    const unsigned long long pos = S.chunk_pos[g];                   // bit offset of this chunk's tokens in the stream
+    const unsigned mine = S.sub_bits[(g * kLzSubs + tid) * 2 + (fixed ? 0 : 1)];
+    unsigned inc = mine;
+    for (int o = 1; o < 64; o <<= 1) { const unsigned t = __shfl_up(inc, o); if (lane >= o) inc += t; }
+    if (lane == 63) sWaveBits[tid >> 6] = inc;
+    __syncthreads();
+    unsigned off = (unsigned)(pos & 31ull) + inc - mine;
+    for (int k = 0; k < (tid >> 6); k++) off += sWaveBits[k];
+    const unsigned char *in = reinterpret_cast<const unsigned char *>(sIn);
+    const int s0 = tid * kBzSub;
+    const int sn = len - s0 < kBzSub ? (len - s0 > 0 ? len - s0 : 0) : kBzSub;
+    if (sn > 0) {
+        BitSink sink;
+        sink.start(sOut, off);
+        LzEmitBits v{ sink, tab };
+        bz_walk(S.tokens + g * kBzChunk + s0, in + s0, sn, v);
+        sink.finish();
+    }
+    __syncthreads();
+    unsigned total = (unsigned)(pos & 31ull);
+    for (int k = 0; k < kLzSubs / 64; k++) total += sWaveBits[k];
+    const unsigned nwords = (total + 31u) / 32u;
+    unsigned *dst = reinterpret_cast<unsigned *>(S.out + f.out_off) + (pos >> 5);
     for (unsigned i = tid; i < nwords; i += kLzSubs) {
         const unsigned v = sOut[i];
         if (i == 0 || i == nwords - 1) { if (v) atomicOr(&dst[i], v); }
@@ -942,6 +1276,74 @@ void launch_deflate(hipStream_t st, const int *coeffs, const long long *counts, 
     if (S.chunk_off[3] > 0) hipLaunchKernelGGL(k_lz_sizes, dim3(S.chunk_off[3], batch), dim3(kLzSubs), 0, st, S);
     hipLaunchKernelGGL(k_lz_scan, dim3(batch * 3), dim3(256), 0, st, S);
     if (S.chunk_off[3] > 0) hipLaunchKernelGGL(k_lz_emit, dim3(S.chunk_off[3], batch), dim3(kLzSubs), emit_lds, st, S);
+}
+
+// ---- the byte-stream deflate's host side ----
+static long long bz_total_chunks(const BzFile *files, int n) { return n > 0 ? files[n - 1].chunk0 + (files[n - 1].n_bytes + kBzChunk - 1) / kBzChunk : 0; }
+
+long long deflate_bytes_chunks(long long n_bytes) { return (n_bytes + kBzChunk - 1) / kBzChunk; }
+
+unsigned long long deflate_bytes_workspace_bytes(long long chunks, int n)
+{
+    const unsigned long long c = (unsigned long long)chunks;
+    return 256 + al256(c * kBzChunk * sizeof(unsigned)) + al256(c * 2 * sizeof(unsigned)) * 2 + al256(c) + al256(c * kLzSubs * 2 * sizeof(unsigned short)) +
+           al256(c * sizeof(unsigned long long)) + al256((unsigned long long)n);
+}
+
+static BzStreams bz_args(const unsigned char *in, const BzFile *files, int n, void *workspace)
+{
+    BzStreams S;
+    memset(&S, 0, sizeof S);
+    S.in = in;
+    const unsigned long long c = (unsigned long long)bz_total_chunks(files, n);
+    char *w = static_cast<char *>(workspace);
+    S.error = reinterpret_cast<int *>(w); w += 256;
+    S.tokens = reinterpret_cast<unsigned *>(w); w += al256(c * kBzChunk * sizeof(unsigned));
+    S.chunk_bits = reinterpret_cast<unsigned *>(w); w += al256(c * 2 * sizeof(unsigned));
+    S.chunk_adler = reinterpret_cast<unsigned *>(w); w += al256(c * 2 * sizeof(unsigned));
+    S.chunk_missing = reinterpret_cast<unsigned char *>(w); w += al256(c);
+    S.sub_bits = reinterpret_cast<unsigned short *>(w); w += al256(c * kLzSubs * 2 * sizeof(unsigned short));
+    S.chunk_pos = reinterpret_cast<unsigned long long *>(w); w += al256(c * sizeof(unsigned long long));
+    S.stream_fixed = reinterpret_cast<unsigned char *>(w);
+    return S;
+}
+
+// the launch of one kernel over the call's files, kBzGroup at a time (their table travels in the kernel's arguments)
+template <typename K>
+static void bz_for_groups(BzStreams &S, const BzFile *files, int n, K &&launch)
+{
+    for (int first = 0; first < n; first += kBzGroup) {
+        const int count = std::min(kBzGroup, n - first);
+        long long most = 0;
+        for (int i = 0; i < count; i++) { S.grp.f[i] = files[first + i]; most = std::max(most, deflate_bytes_chunks(files[first + i].n_bytes)); }
+        S.first = first;
+        launch(S, count, (unsigned)most);
+    }
+}
+
+void launch_deflate_bytes_parse(hipStream_t st, const unsigned char *in, const BzFile *files, int n, int *hist, void *workspace)
+{
+    BzStreams S = bz_args(in, files, n, workspace);
+    S.hist = hist;
+    static bool attr = false;
+    if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bz_parse), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(BzLds)); attr = true; }
+    (void)hipMemsetAsync(S.error, 0, 256, st);
+    if (hist) (void)hipMemsetAsync(hist, 0, (size_t)n * kDefHistBins * sizeof(int), st);
+    bz_for_groups(S, files, n, [&](const BzStreams &G, int count, unsigned most) {
+        if (most) hipLaunchKernelGGL(k_bz_parse, dim3(most, count), dim3(kLzThreads), sizeof(BzLds), st, G);
+    });
+}
+
+void launch_deflate_bytes(hipStream_t st, const unsigned char *in, const BzFile *files, int n, const unsigned *tables, unsigned char *out, long long *sizes,
+                          void *workspace)
+{
+    BzStreams S = bz_args(in, files, n, workspace);
+    S.tables = tables; S.out = out; S.sizes = sizes;
+    bz_for_groups(S, files, n, [&](const BzStreams &G, int count, unsigned most) {
+        if (most) hipLaunchKernelGGL(k_bz_sizes, dim3(most, count), dim3(kLzSubs), 0, st, G);
+        hipLaunchKernelGGL(k_bz_scan, dim3(count), dim3(256), 0, st, G);
+        if (most) hipLaunchKernelGGL(k_bz_emit, dim3(most, count), dim3(kLzSubs), 0, st, G);
+    });
 }
 
 }  // namespace aej

@@ -1,5 +1,5 @@
 // png.hip -- the PNG half of png_decode_many after the inflate: the scanline un-filter (PNG specification, section 9) and the expansion of
-// grey, palette and alpha layouts to the image the caller asked for.
+// grey, palette and alpha layouts to the image the caller asked for; and, further down, the scanline filter of png_encode_many.
 //
 // One workgroup per file, and in it one wave64 that un-filters.  Un-filtering is a recurrence -- Sub, Average and Paeth need the byte
 // `bpp` to the left, Up, Average and Paeth the row above, Paeth the byte above-left as well -- so the rows of a file are not independent,
@@ -222,6 +222,134 @@ __global__ __launch_bounds__(kWaves * 64) void png_unfilter_kernel(PngGroup grp,
     if (threadIdx.x == 0) status[index] = st;
 }
 
+// ---- the scanline filter of png_encode_many (aej_png_filter_batch) -------------------------------------------------------------------
+// Encoding has no recurrence: a row is filtered against the RAW row above, so rows are independent.  One wave64 per row, kEncWaves rows
+// per workgroup, all rows of up to kPngGroup images in one launch: a wave finds its image by a search over the group's first-row table.
+// The wave makes two passes over its row, 256 bytes a step, a dword per lane.  Pass 1 forms the cost sum (v < 128 ? v : 256 - v) of the
+// five filters' bytes in registers, reduces them across the wave and applies Pillow's rule (None; if its cost is not 0: Up, Sub, Average
+// only with optimize, Paeth, each only if strictly cheaper).  Pass 2 recomputes the chosen filter and stores it behind the filter byte.
+// "left" and "up-left" never come from memory: they are the lane's own dword and its neighbour's (the last lane's of the step before
+// for lane 0, zero at the row's start -- the a = c = 0 columns), shifted by bpp bytes.
+// SOURCE: H rows of rb bytes each, contiguous, any alignment (the caller makes a strided tensor contiguous first).  The lanes' dwords
+// are aligned in the DESTINATION (rows are 1 + rb apart, so no alignment holds for both); the source is read as aligned dwords and a
+// funnel shift, and only dwords that overlap the image are loaded.  A dword of the destination that is not wholly the row's is stored
+// by bytes.  rb <= 2^24 keeps a cost sum inside an int; the entry refuses more.
+constexpr int kEncWaves = 4;
+
+// the four bytes at address p; aligned dwords that do not overlap [lo, hi) are not loaded and read as 0
+__device__ inline unsigned load4_within(uintptr_t p, uintptr_t lo, uintptr_t hi)
+{
+    const uintptr_t a = p & ~(uintptr_t)3;
+    const int sh = (int)(p & 3) * 8;
+    unsigned v0 = 0u, v1 = 0u;
+    if (a + 4 > lo && a < hi) v0 = *reinterpret_cast<const unsigned *>(a);
+    if (sh && a + 8 > lo && a + 4 < hi) v1 = *reinterpret_cast<const unsigned *>(a + 4);
+    return sh ? (v0 >> sh) | (v1 << (32 - sh)) : v0;
+}
+
+// filter type ft of byte x with a = left, b = up, c = up-left (PNG specification 9.2)
+__device__ inline unsigned filter_byte(int ft, int x, int a, int b, int c)
+{
+    const int pa = abs(b - c), pb = abs(a - c), pc = abs(a + b - 2 * c);
+    const int paeth = (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
+    const int pred = ft == 1 ? a : ft == 2 ? b : ft == 3 ? (a + b) >> 1 : ft == 4 ? paeth : 0;
+    return (unsigned)(x - pred) & 255u;
+}
+
+__global__ __launch_bounds__(kEncWaves * 64) void png_filter_kernel(PngEncGroup grp, int count, int rows, int optimize, unsigned char *out)
+{
+    const int lane = threadIdx.x & 63;
+    const int r = (int)blockIdx.x * kEncWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (r >= rows) return;
+    int lo = 0, hi = count - 1;                                  // the last image whose first row is not beyond r
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (grp.f[mid].row0 <= r) lo = mid; else hi = mid - 1;
+    }
+    const PngEncImage f = grp.f[lo];
+    const int y = r - f.row0, rb = f.rb, bpp = f.bpp;
+    if (y < 0 || y >= f.H) return;
+    const uintptr_t img_lo = reinterpret_cast<uintptr_t>(f.src), img_hi = img_lo + (size_t)f.H * (size_t)rb;
+    const uintptr_t row = img_lo + (size_t)y * (size_t)rb;
+    unsigned char *dst = out + f.dst_off + (long long)y * (rb + 1);         // the filter byte, then byte q of the row at dst[1 + q]
+    const int q_first = -1 - (int)(reinterpret_cast<uintptr_t>(dst) & 3);   // row position of the first byte of dst's first dword (-1: the filter byte)
+
+    // bytes q0 .. q0 + 3 of the row and of the row above; zero outside [0, rb) and above the first row
+    auto load = [&](int q0, unsigned &x, unsigned &b) {
+        x = 0u; b = 0u;
+        if (q0 + 4 > 0 && q0 < rb) {
+            unsigned mask = 0xffffffffu;
+            if (q0 < 0) mask &= 0xffffffffu << (8 * -q0);
+            if (q0 + 4 > rb) mask &= 0xffffffffu >> (8 * (q0 + 4 - rb));
+            x = load4_within(row + (intptr_t)q0, img_lo, img_hi) & mask;
+            if (y > 0) b = load4_within(row - (size_t)rb + (intptr_t)q0, img_lo, img_hi) & mask;
+        }
+    };
+    // the dword bpp bytes to the left of `own`, whose left neighbour dword is `prev`
+    auto left_of = [&](unsigned own, unsigned prev) {
+        return bpp == 4 ? prev : (unsigned)(((unsigned long long)own << 32 | prev) >> (32 - 8 * bpp));
+    };
+
+    int cost[5] = { 0, 0, 0, 0, 0 };
+    unsigned cx = 0u, cb = 0u;                                              // the last lane's dwords of the step before
+    for (int base = q_first; base < rb; base += 256) {
+        const int q0 = base + 4 * lane;
+        unsigned x, b;
+        load(q0, x, b);
+        unsigned xp = __shfl_up(x, 1), bp = __shfl_up(b, 1);
+        if (lane == 0) { xp = cx; bp = cb; }
+        cx = (unsigned)__builtin_amdgcn_readlane((int)x, 63);
+        cb = (unsigned)__builtin_amdgcn_readlane((int)b, 63);
+        const unsigned a = left_of(x, xp), c = left_of(b, bp);
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            if (q0 + j < 0 || q0 + j >= rb) continue;
+            const int X = (x >> (8 * j)) & 255, A = (a >> (8 * j)) & 255, B = (b >> (8 * j)) & 255, C = (c >> (8 * j)) & 255;
+#pragma unroll
+            for (int ft = 0; ft < 5; ft++) {
+                const int v = (int)filter_byte(ft, X, A, B, C);
+                cost[ft] += v < 128 ? v : 256 - v;
+            }
+        }
+    }
+#pragma unroll
+    for (int ft = 0; ft < 5; ft++)
+        for (int o = 32; o > 0; o >>= 1) cost[ft] += __shfl_xor(cost[ft], o);
+    int ft = 0, best = cost[0];
+    if (best != 0) {
+        if (cost[2] < best) { best = cost[2]; ft = 2; }
+        if (cost[1] < best) { best = cost[1]; ft = 1; }
+        if (optimize && cost[3] < best) { best = cost[3]; ft = 3; }
+        if (cost[4] < best) { best = cost[4]; ft = 4; }
+    }
+    ft = __builtin_amdgcn_readfirstlane(ft);
+
+    cx = 0u; cb = 0u;
+    for (int base = q_first; base < rb; base += 256) {
+        const int q0 = base + 4 * lane;
+        unsigned x, b;
+        load(q0, x, b);
+        unsigned xp = __shfl_up(x, 1), bp = __shfl_up(b, 1);
+        if (lane == 0) { xp = cx; bp = cb; }
+        cx = (unsigned)__builtin_amdgcn_readlane((int)x, 63);
+        cb = (unsigned)__builtin_amdgcn_readlane((int)b, 63);
+        const unsigned a = left_of(x, xp), c = left_of(b, bp);
+        unsigned word = 0u;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const unsigned v = q0 + j == -1 ? (unsigned)ft
+                                            : filter_byte(ft, (x >> (8 * j)) & 255, (a >> (8 * j)) & 255, (b >> (8 * j)) & 255, (c >> (8 * j)) & 255);
+            word |= v << (8 * j);
+        }
+        if (q0 >= -1 && q0 + 4 <= rb) *reinterpret_cast<unsigned *>(dst + 1 + q0) = word;
+        else {
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+                if (q0 + j >= -1 && q0 + j < rb) dst[1 + q0 + j] = (unsigned char)(word >> (8 * j));
+        }
+    }
+}
+
 }  // namespace
 
 long long png_carry_bytes(int rb, int bpp) { return carry_bytes_of(rb, bpp); }
@@ -232,6 +360,12 @@ void launch_png_unfilter(hipStream_t st, const PngGroup &grp, int first, int cou
     if (count > 0)
         hipLaunchKernelGGL(png_unfilter_kernel, dim3(count), dim3(kWaves * 64), 0, st, grp, first, count, inflated, inflate_out_bytes, inflate_status, palettes,
                            out, carry, status);
+}
+
+void launch_png_filter(hipStream_t st, const PngEncGroup &grp, int count, int rows, int optimize, unsigned char *out)
+{
+    if (count > 0 && rows > 0)
+        hipLaunchKernelGGL(png_filter_kernel, dim3((rows + kEncWaves - 1) / kEncWaves), dim3(kEncWaves * 64), 0, st, grp, count, rows, optimize, out);
 }
 
 }  // namespace aej

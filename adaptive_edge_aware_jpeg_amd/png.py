@@ -1,9 +1,11 @@
-"""PNG files decoded on the GPU, pixel-identical to Pillow (``png_decode_many``), and the host chunk walk (``png_parse_header``).
+"""PNG files decoded on the GPU, pixel-identical to Pillow (``png_decode_many``), the host chunk walk (``png_parse_header``), and PNG
+files written on the GPU with Pillow's scanline filtering (``png_encode_many``, at the end of this module).
 
 The host reads only the chunk framing (``aej_png_parse_host``).  The zlib stream of every file -- its IDAT chunks joined -- is inflated
 by ``aej_inflate_batch`` (csrc/inflate.hip, one wave per file) or, as the A / B partner, by ``zlib.decompress`` on a thread pool; the
 scanline un-filter and the expansion of grey, palette and alpha layouts run on the device either way (csrc/png.hip)."""
 import ctypes
+import struct
 import zlib
 from concurrent.futures import ThreadPoolExecutor
 from typing import List, Optional
@@ -214,3 +216,196 @@ def _decode_parsed(ctx, parsed, views, modes, inflate, workers, events=None):
             code = int(s[1, i])
             raise ValueError(f"file {i}: {PNG_STATUS[code] if 0 <= code < len(PNG_STATUS) else f'status {code}'}")
     return [out[int(out_off[i]):int(out_off[i]) + int(np.prod(shapes[i]))].view(shapes[i]) for i in range(n)]
+
+
+# ---- encode -------------------------------------------------------------------------------------------------------------------------
+ENCODE_MODES = ("auto", "L", "LA", "RGB", "RGBA")
+_MODE_OF_CHANNELS = {1: "L", 2: "LA", 3: "RGB", 4: "RGBA"}
+_COLOUR_TYPE = {1: 0, 2: 4, 3: 2, 4: 6}
+_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+IDAT_BYTES = 65536           # Pillow cuts the zlib stream into IDAT chunks of this size
+MAX_ENCODE_SIDE = 1 << 24    # rows, and bytes per row, of one image (aej_png_filter_bytes)
+
+
+def _is_tensor(x):
+    return type(x).__module__.split(".")[0] == "torch" and hasattr(x, "data_ptr")
+
+
+def _check_images(images, mode, optimize, compress_level, entropy, workers):
+    """The host-side validation of png_encode_many (no device is touched): -> [(image, H, W, bytes per pixel)]."""
+    if entropy not in ("gpu", "host"):
+        raise ValueError("entropy must be 'gpu' or 'host'")
+    if mode not in ENCODE_MODES:
+        raise ValueError(f"mode: {mode!r} is not one of {ENCODE_MODES}")
+    if not isinstance(optimize, (bool, np.bool_)):
+        raise ValueError(f"optimize: {optimize!r} is not a bool")
+    if isinstance(compress_level, bool) or not isinstance(compress_level, (int, np.integer)) or not 0 <= compress_level <= 9:
+        raise ValueError(f"compress_level: {compress_level!r} is not an integer in 0 .. 9")
+    if workers is not None and (isinstance(workers, bool) or not isinstance(workers, (int, np.integer)) or workers < 1):
+        raise ValueError(f"workers: {workers!r} is neither None nor a positive integer")
+    if isinstance(images, np.ndarray) or _is_tensor(images):
+        raise ValueError("images: a list of images is expected, not one array (mixed sizes have no common array)")
+    items = []
+    for i, x in enumerate(list(images)):
+        if not (isinstance(x, np.ndarray) or _is_tensor(x)):
+            raise ValueError(f"image {i}: {type(x).__name__} is neither a numpy array nor a torch tensor")
+        if str(x.dtype).split(".")[-1] != "uint8":
+            raise ValueError(f"image {i}: dtype {x.dtype} is not uint8")
+        shape = tuple(int(v) for v in x.shape)
+        if len(shape) not in (2, 3):
+            raise ValueError(f"image {i}: shape {shape} is neither [H, W] nor [H, W, C]")
+        if len(shape) == 3 and shape[2] not in (2, 3, 4):
+            raise ValueError(f"image {i}: {shape[2]} channels; the layouts are [H, W] (L), [H, W, 2] (LA), [H, W, 3] (RGB) and [H, W, 4] (RGBA)")
+        bpp = 1 if len(shape) == 2 else shape[2]
+        if mode != "auto" and _MODE_OF_CHANNELS[bpp] != mode:
+            raise ValueError(f"image {i}: shape {shape} is mode {_MODE_OF_CHANNELS[bpp]}, not the mode {mode!r} asked for")
+        if shape[0] < 1 or shape[1] < 1:
+            raise ValueError(f"image {i}: shape {shape} has no pixels")
+        if shape[0] > MAX_ENCODE_SIDE or shape[1] * bpp > MAX_ENCODE_SIDE:
+            raise NotImplementedError(f"image {i}: shape {shape}: more than 2^24 rows or bytes per row are not built")
+        items.append((x, shape[0], shape[1], bpp))
+    return items
+
+
+def _chunk(name, body):
+    return struct.pack(">I", len(body)) + name + bytes(body) + struct.pack(">I", zlib.crc32(body, zlib.crc32(name)))
+
+
+def _frame(H, W, bpp, stream):
+    """The file Pillow writes around a zlib stream: signature, IHDR, IDAT chunks of 65536 bytes, IEND."""
+    stream = memoryview(stream)
+    parts = [_SIGNATURE, _chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, _COLOUR_TYPE[bpp], 0, 0, 0))]
+    parts += [_chunk(b"IDAT", stream[k:k + IDAT_BYTES]) for k in range(0, len(stream), IDAT_BYTES)]
+    parts.append(_chunk(b"IEND", b""))
+    return b"".join(parts)
+
+
+def _align4(v):
+    return (v + 3) // 4 * 4
+
+
+def _filter_on_device(ctx, items, optimize, events=None):
+    """aej_png_filter_batch over all images -> (device uint8 buffer, offsets, sizes) of their scanline streams (offsets are multiples of
+    4).  Images that are not on the device cross in one page-locked copy; a tensor that is not contiguous is made so first."""
+    t, lib, n = ctx.torch, ctx.lib, len(items)
+    sizes = [H * (1 + W * bpp) for _, H, W, bpp in items]
+    offs, pos = [], 0
+    for k in sizes:
+        offs.append(pos)
+        pos = _align4(pos + k)
+    raw = ctx.empty((pos + 4,), t.uint8)
+    up_off, up = {}, 0
+    for i, (x, H, W, bpp) in enumerate(items):
+        if not (_is_tensor(x) and x.is_cuda):
+            up_off[i] = up
+            up = _align4(up + H * W * bpp)
+    keep, ptrs = [], [0] * n
+    if up:
+        stage = ctx.pinned(up)
+        hb = stage[:up].numpy()
+        for i, o in up_off.items():
+            x, H, W, bpp = items[i]
+            a = x.numpy() if _is_tensor(x) else x
+            hb[o:o + H * W * bpp] = np.ascontiguousarray(a).reshape(-1)
+        dev = ctx.empty((up,), t.uint8)
+        dev.copy_(stage[:up], non_blocking=True)
+        keep.append(dev)
+        for i, o in up_off.items():
+            ptrs[i] = dev.data_ptr() + o
+    for i, (x, H, W, bpp) in enumerate(items):
+        if i not in up_off:
+            x = x.to(ctx.device).contiguous()
+            keep.append(x)
+            ptrs[i] = x.data_ptr()
+    descs = np.array([(ptrs[i], H, W * bpp, bpp, offs[i]) for i, (_, H, W, bpp) in enumerate(items)], np.int64).reshape(n, 5)
+    if events is not None:
+        events["filter"] = [t.cuda.Event(enable_timing=True), t.cuda.Event(enable_timing=True)]
+        events["filter"][0].record()
+    ctx.check(lib.aej_png_filter_batch(ctx.handle, descs.ctypes.data, n, 1 if optimize else 0, raw.data_ptr(), ctypes.c_uint64(raw.numel())))
+    if events is not None:
+        events["filter"][1].record()
+    return raw, offs, sizes, keep
+
+
+def _deflate_on_device(ctx, raw, items, offs, sizes):
+    """aej_deflate_bytes_*: -> (page-locked uint8 numpy view of the streams back to back, their sizes)."""
+    from ._lib import AejError
+    t, lib, n = ctx.torch, ctx.lib, len(items)
+    caps = [_align4(int(lib.aej_deflate_stream_bound(ctypes.c_uint64(k)))) for k in sizes]
+    out_off = np.concatenate([[0], np.cumsum(caps)]).astype(np.int64)
+    descs = np.array([(offs[i], sizes[i], bpp, 1 + W * bpp, out_off[i], caps[i]) for i, (_, H, W, bpp) in enumerate(items)], np.int64).reshape(n, 6)
+    nws = int(lib.aej_deflate_bytes_workspace_bytes(descs.ctypes.data, n))
+    if nws == 0:
+        raise ValueError("stream sizes the library refuses")
+    ws = ctx.workspace(nws)
+    out = ctx.empty((int(out_off[n]),), t.uint8)
+    hist = ctx.empty((n, 320), t.int32)
+    dsizes = ctx.empty((n,), t.int64)
+    common = (ctx.handle, raw.data_ptr(), ctypes.c_uint64(raw.numel()), descs.ctypes.data, n)
+    ctx.check(lib.aej_deflate_bytes_histogram(*common, hist.data_ptr(), ws.data_ptr(), ctypes.c_uint64(nws)))
+    h = np.ascontiguousarray(hist.cpu().numpy())
+    tab = np.zeros((n, 448), np.uint32)
+    if lib.aej_deflate_bytes_build_tables(h.ctypes.data, n, tab.ctypes.data):
+        raise AejError("aej_deflate_bytes_build_tables failed")
+    tabs = t.from_numpy(tab.view(np.int32)).to(ctx.device)
+    ctx.check(lib.aej_deflate_bytes_batch(*common, tabs.data_ptr(), 1, out.data_ptr(), ctypes.c_uint64(out.numel()), dsizes.data_ptr(),
+                                          ws.data_ptr(), ctypes.c_uint64(nws)))
+    got = [int(v) for v in dsizes.cpu().numpy()]
+    packed = t.cat([out[int(out_off[i]):int(out_off[i]) + got[i]] for i in range(n)])      # compacted on the device: one copy of what was written
+    host = ctx.pinned(packed.numel())[:packed.numel()]
+    host.copy_(packed)
+    return host.numpy(), got
+
+
+def png_encode_many(images, mode="auto", optimize: bool = False, compress_level: int = 6, entropy: str = "gpu", device: int = 0,
+                    workers: Optional[int] = None) -> List[bytes]:
+    """Write PNG files on the GPU -> a list of ``bytes``, one file per image, in order.  The scanline filtering is Pillow's, so the
+    filter bytes and the filtered scanlines (``zlib.decompress`` of the joined IDAT chunks) equal those of
+    ``Image.fromarray(x).save(f, "PNG", optimize=optimize)`` byte for byte, and the files decode to the input pixels.
+
+    ``images``: uint8 device tensors, host tensors or numpy arrays, of mixed sizes and kinds: [H, W] (L), [H, W, 2] (LA), [H, W, 3]
+    (RGB), [H, W, 4] (RGBA) -- the layouts ``png_decode_many(mode="auto")`` returns.  ``mode="auto"`` takes each image's own layout;
+    "L", "LA", "RGB" or "RGBA" insist on that one.  A tensor that is not contiguous is accepted and made contiguous first (the filter
+    kernel reads whole rows back to back).  Wrong dtype, rank, channel count, an image without pixels and bad option values raise
+    ValueError("image i: ...") on the host before any device work; more than 2^24 rows or bytes per row raise NotImplementedError.
+    Files carry IHDR, IDAT and IEND only: no palette, 16-bit, interlace, pnginfo, ICC or dpi.
+
+    ``optimize`` is Pillow's: the Average filter joins the candidates (and, with ``entropy="host"``, zlib runs at level 9).
+
+    ``entropy="gpu"`` (default): the scanlines are deflated on the device (csrc/deflate.hip, matches at byte positions, one deflate
+    block per file under the file's own Huffman code) and only the finished streams are read back; the host adds the chunk framing.
+    The files are larger than Pillow's (README) and ``compress_level`` is IGNORED: there is one effort level.  The same input gives the
+    same bytes, alone or in a batch.  ``entropy="host"``: the scanlines are read back once and
+    ``zlib.compressobj(compress_level, DEFLATED, 15, 9, Z_FILTERED)`` runs on a thread pool (``workers``, at most 16): the file equals
+    Pillow's byte for byte."""
+    items = _check_images(images, mode, optimize, compress_level, entropy, workers)
+    if not items:
+        return []
+    return _encode_checked(get_context(device), items, bool(optimize), int(compress_level), entropy, workers)
+
+
+def _encode_checked(ctx, items, optimize, compress_level, entropy, workers, events=None):
+    raw, offs, sizes, keep = _filter_on_device(ctx, items, optimize, events)
+    pool = ThreadPoolExecutor(max_workers=min(workers or MAX_HOST_WORKERS, MAX_HOST_WORKERS))
+    try:
+        if entropy == "host":
+            host = ctx.pinned(raw.numel())[:raw.numel()]
+            host.copy_(raw)                                  # the one read-back (it also ends the use of the inputs)
+            hb = host.numpy()
+            level = 9 if optimize else compress_level
+
+            def one(i):
+                z = zlib.compressobj(level, zlib.DEFLATED, 15, 9, zlib.Z_FILTERED)
+                stream = z.compress(hb[offs[i]:offs[i] + sizes[i]]) + z.flush()
+                return _frame(items[i][1], items[i][2], items[i][3], stream)
+        else:
+            hb, got = _deflate_on_device(ctx, raw, items, offs, sizes)
+            starts = np.concatenate([[0], np.cumsum(got)])
+
+            def one(i):
+                return _frame(items[i][1], items[i][2], items[i][3], hb[int(starts[i]):int(starts[i]) + got[i]])
+        files = list(pool.map(one, range(len(items))))
+    finally:
+        pool.shutdown()
+    del keep
+    return files

@@ -289,6 +289,26 @@ AEJ_API int aej_deflate_build_tables(const int32_t *hist_host, const int32_t *co
 AEJ_API int aej_deflate_batch(aej_ctx *ctx, const int32_t *coeffs, const int64_t *counts, int batch, int H, int W, const uint32_t *tables, int reuse_parse,
                               uint8_t *streams, uint64_t stream_stride, int64_t *sizes, void *workspace, uint64_t workspace_bytes);
 
+/* The same stage on BYTE streams of mixed lengths, one zlib stream per file (png_encode_many(entropy="gpu"): the filtered scanlines).
+ * Matches start at any byte position, in chunks of 8192 positions with up to 24576 bytes of history; the distances always tried are
+ * 1, bpp, 2 bpp, stride -+ bpp and up to 16 multiples of the stride, the rest comes from exact hash chains over the chunk and the 8192 bytes before it.  One deflate block
+ * per stream: the file's dynamic code (aej_deflate_bytes_build_tables over its histogram) or the fixed code when that is smaller.
+ * descs_host: [n][6] int64 = offset of the stream in `in` (a multiple of 4; whole dwords are read, so the length rounded up to 4 must
+ *   lie inside in_bytes), its bytes (1 .. 2^40), bytes per pixel (1 .. 4), bytes per scanline (stride, 1 .. 2^26), offset and size of
+ *   its slot in `out` (multiples of 4, at least 16 bytes; read by aej_deflate_bytes_batch only).
+ * aej_deflate_bytes_workspace_bytes: 0 for lengths outside the range.  aej_deflate_bytes_histogram: parse; hist = device
+ *   [n][AEJ_DEFLATE_HIST_BINS].  aej_deflate_bytes_build_tables (host only): tables_host [n][AEJ_DEFLATE_TABLE_WORDS] with codes for the
+ *   symbols that occur.  aej_deflate_bytes_batch: tables = device [n][AEJ_DEFLATE_TABLE_WORDS] or NULL; reuse_parse as above; the
+ *   stream of file i goes to its slot, its length to sizes[i] (device int64).  aej_deflate_stream_bound(bytes) is always enough for a
+ *   slot; a stream that does not fit returns AEJ_ERR_CAPACITY and is not written.  `in`, `out` 4-byte, workspace 256-byte aligned.
+ *   Both device calls synchronise the context's stream.  The same input gives the same bytes. */
+AEJ_API uint64_t aej_deflate_bytes_workspace_bytes(const int64_t *descs_host, int n);
+AEJ_API int aej_deflate_bytes_histogram(aej_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const int64_t *descs_host, int n, int32_t *hist, void *workspace,
+                                        uint64_t workspace_bytes);
+AEJ_API int aej_deflate_bytes_build_tables(const int32_t *hist_host, int n, uint32_t *tables_host);
+AEJ_API int aej_deflate_bytes_batch(aej_ctx *ctx, const uint8_t *in, uint64_t in_bytes, const int64_t *descs_host, int n, const uint32_t *tables, int reuse_parse,
+                                    uint8_t *out, uint64_t out_bytes, int64_t *sizes, void *workspace, uint64_t workspace_bytes);
+
 /* HOST-only helper (no context, no device work) for the 8-bit ingest of HOST images (src/image/image.py:80 makes every
  * loaded image `uint8.astype(float32) / 255.0`): if every one of the n float32 values at rgb_host is bit for bit float32(k) / 255.0f for
  * some k in 0..255, the levels k are written to u8_host and 1 is returned -- the caller then uploads 3 B per pixel instead of 12 and
@@ -1078,6 +1098,20 @@ AEJ_API int aej_png_unfilter_batch(aej_ctx *ctx, const aej_png_desc *descs_host,
                                    const int64_t *in_offsets_host, const int64_t *inflate_out_bytes, const int32_t *inflate_status,
                                    const uint8_t *palettes, const int32_t *layouts_host, uint8_t *out, uint64_t out_bytes,
                                    const int64_t *out_offsets_host, int32_t *status, void *workspace, uint64_t workspace_bytes);
+
+/* ---- PNG encode: the scanline filter of png_encode_many (csrc/png.hip), Pillow's choice rule ----
+ * Every row gets the filter Pillow's writer picks (not libpng's heuristic): cost(f) = sum of (v < 128 ? v : 256 - v) over the row's
+ * filtered bytes v, the row above the first row all zeros; None (0) to start with and kept if its cost is 0, otherwise Up (2), Sub (1),
+ * Average (3, only when optimize != 0) and Paeth (4) are tried in that order and taken only when strictly cheaper.
+ * aej_png_filter_bytes: height x (1 + row_bytes), the bytes of one image's scanline stream; 0 for a shape the filter refuses (height
+ *   outside 1 .. 2^24, bpp outside 1 .. 4, row_bytes outside bpp .. 2^24 or no multiple of bpp).
+ * aej_png_filter_batch: descs_host = [n][5] int64: the image's DEVICE pointer, its height, row bytes, bytes per pixel, and the offset of
+ *   its scanline stream in `out` (device, 4-byte aligned; the offsets need no alignment).  An image is `height` rows of `row_bytes`
+ *   bytes, CONTIGUOUS, at any address; the call refuses a NULL pointer, a shape as above and a stream outside out_bytes with
+ *   AEJ_ERR_ARG.  Rows are independent (a row is filtered against the raw row above): one wave per row, all rows of 64 images a launch.
+ *   Only enqueues on the context's stream. */
+AEJ_API uint64_t aej_png_filter_bytes(int height, int row_bytes, int bpp);
+AEJ_API int aej_png_filter_batch(aej_ctx *ctx, const int64_t *descs_host, int n, int optimize, uint8_t *out, uint64_t out_bytes);
 
 #ifdef __cplusplus
 }

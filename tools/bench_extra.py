@@ -5,6 +5,7 @@ zlib level-9 streams of the container on host threads (src/jpeg/jpeg.py:588-590)
 Diagnostic companion of bench.py (same synthetic 4K images); prints one JSON object.  GPU only.
 
     python tools/bench_extra.py [--batch 32] [--steps 5] [--e2e-images 16]
+    python tools/bench_extra.py --mode png-encode [--png-images 64] [--steps 5] [--data natural]
 """
 import argparse
 import json
@@ -111,18 +112,97 @@ def end_to_end(torch, bench, A, codec, args, dev, H, W):
     return res
 
 
+def png_encode(torch, bench, A, args, dev, H, W):
+    """--mode png-encode: `png_encode_many` of --png-images RGB images of 4K with both entropy settings, against the download and Pillow's
+    `save` on 16 threads; file sizes against Pillow's levels 1 and 6; the filter kernel's rate against a device copy of the same bytes.
+    Every time is the median of --steps runs after one warm-up, with the range."""
+    import io
+    import statistics
+    from concurrent.futures import ThreadPoolExecutor
+    from PIL import Image as PILImage
+    from adaptive_edge_aware_jpeg_amd import png as P
+    from benchlib.data import to_u8
+    n = args.png_images
+    make = bench.synth_batch if args.data == "synthetic" else bench.natural_batch
+    imgs = []
+    for b0 in range(0, n, 8):
+        imgs += list(to_u8(torch, make(torch, min(8, n - b0), H, W, 4242 + b0, dev)))
+    torch.cuda.synchronize()
+    raw_bytes = n * H * W * 3
+
+    def runs(fn):
+        fn()
+        ts = []
+        for _ in range(args.steps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fn()
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+        return out, {"median_s": round(statistics.median(ts), 4), "min_s": round(min(ts), 4), "max_s": round(max(ts), 4),
+                     "MP/s": round(n * H * W / 1e6 / statistics.median(ts), 1)}
+
+    def pillow(level):
+        host = [x.cpu().numpy() for x in imgs]               # the download is part of what a caller without the GPU writer pays
+
+        def one(a):
+            buf = io.BytesIO()
+            PILImage.fromarray(a).save(buf, "PNG", compress_level=level)
+            return buf.getvalue()
+        with ThreadPoolExecutor(max_workers=16) as ex:
+            return list(ex.map(one, host))
+
+    res = {"images": n, "data": args.data, "shape": [H, W, 3], "steps": args.steps}
+    gpu, res["entropy_gpu"] = runs(lambda: A.png_encode_many(imgs))
+    host, res["entropy_host_level6"] = runs(lambda: A.png_encode_many(imgs, entropy="host"))
+    _, res["entropy_host_level1"] = runs(lambda: A.png_encode_many(imgs, entropy="host", compress_level=1))
+    p6, res["pillow_16_threads_level6"] = runs(lambda: pillow(6))
+    p1, res["pillow_16_threads_level1"] = runs(lambda: pillow(1))
+    assert host == p6
+    back = A.png_decode_many(gpu[:2], mode="auto")
+    assert all(torch.equal(a, b) for a, b in zip(imgs, back))
+    size = lambda fs: sum(len(f) for f in fs)
+    res["bytes"] = {"raw": raw_bytes, "entropy_gpu": size(gpu), "pillow_level6": size(p6), "pillow_level1": size(p1),
+                    "gpu_over_level1": round(size(gpu) / size(p1), 4), "gpu_over_level6": round(size(gpu) / size(p6), 4)}
+    # the filter kernel alone, and a device copy of as many bytes
+    ctx = A._lib.get_context(0)
+    items = P._check_images(imgs, "auto", False, 6, "gpu", None)
+    ms, cp = [], []
+    src = torch.cat([x.reshape(-1) for x in imgs])
+    dst = torch.empty_like(src)
+    for _ in range(args.steps + 1):
+        ev = {}
+        P._filter_on_device(ctx, items, False, ev)
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        dst.copy_(src)
+        b.record()
+        torch.cuda.synchronize()
+        ms.append(ev["filter"][0].elapsed_time(ev["filter"][1]))
+        cp.append(a.elapsed_time(b))
+    ms, cp = statistics.median(ms[1:]), statistics.median(cp[1:])
+    res["filter_kernel"] = {"ms": round(ms, 3), "GB/s_read_plus_written": round((2 * raw_bytes + n * H) / ms / 1e6, 1),
+                            "device_copy_ms": round(cp, 3), "device_copy_GB/s_read_plus_written": round(2 * raw_bytes / cp / 1e6, 1)}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--e2e-images", type=int, default=16, help="images of the end-to-end compress_many measurement (zlib-9 of ~50 MB per 4K image: seconds of host time)")
     ap.add_argument("--data", choices=["synthetic", "natural"], default="synthetic")
+    ap.add_argument("--mode", choices=["all", "png-encode"], default="all", help="png-encode: only the PNG writer's measurement (png_encode)")
+    ap.add_argument("--png-images", type=int, default=64)
     args = ap.parse_args()
     import torch
     import bench
     import adaptive_edge_aware_jpeg_amd as A
     B, H, W = args.batch, 2160, 3840
     dev = torch.device("cuda", 0)
+    if args.mode == "png-encode":
+        print(json.dumps({"png_encode": png_encode(torch, bench, A, args, dev, H, W)}))
+        return
     x = bench.synth_batch(torch, B, H, W, 20250718, dev)
     x8 = (x * 255.0).round().to(torch.uint8)
     codec = A.Jpeg(A.JpegCompressionSettings("YCbCr", (40, 80), (4, 64)))
