@@ -186,6 +186,19 @@ class ResampleDesc(ctypes.Structure):
                 ("reduce_x", ctypes.c_int32), ("reduce_y", ctypes.c_int32), ("reduce_box", ctypes.c_int32 * 4), ("reserved", ctypes.c_int32)]
 
 
+class FilterDesc(ctypes.Structure):
+    """aej_filter_desc (include/aej.h): one image of aej_filter_batch"""
+    _fields_ = [("src_offset", ctypes.c_int64), ("dst_offset", ctypes.c_int64), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("channels", ctypes.c_int32), ("kind", ctypes.c_int32), ("xradius", ctypes.c_float), ("yradius", ctypes.c_float),
+                ("percent", ctypes.c_int32), ("threshold", ctypes.c_int32)]
+
+
+class FilterPlan(ctypes.Structure):
+    """aej_filter_plan (include/aej.h): what aej_filter_plan_host makes of a filter, per axis (x, y)"""
+    _fields_ = [("passes", ctypes.c_int32), ("box", ctypes.c_float * 2), ("r", ctypes.c_int32 * 2), ("ww", ctypes.c_uint32 * 2),
+                ("fw", ctypes.c_uint32 * 2)]
+
+
 class PngDesc(ctypes.Structure):
     """aej_png_desc (include/aej.h): what aej_png_parse_host reads from a file's chunks"""
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("bit_depth", ctypes.c_int32), ("colour_type", ctypes.c_int32),
@@ -360,6 +373,10 @@ SIGNATURES = {
     "aej_png_unfilter_batch": (_I, [_P, _P, _I, _P, _U64, _P, _P, _P, _P, _P, _P, _U64, _P, _P, _P, _U64]),
     "aej_png_filter_bytes": (_U64, [_I, _I, _I]),
     "aej_png_filter_batch": (_I, [_P, _P, _I, _I, _P, _U64]),
+    "aej_filter_plan_host": (_I, [_I, ctypes.c_float, ctypes.c_float, _P]),
+    "aej_filter_geometry_host": (_I, [_P]),
+    "aej_filter_workspace_bytes": (_U64, [_P, _P, _I, _I]),
+    "aej_filter_batch": (_I, [_P, _P, _I, _I, _P, _U64, _P, _U64, _P, _U64]),
     "aej_test_jpegprog_coefs": (_I, [_P, _P, _P, _I, _P, _U64, _P, _I, _P, _U64, _P, _P, _U64]),             # include/aej_testing.h (tests only)
     "aej_test_jpegprog_coefs_host": (_I, [_P, _P, _P, _U64, _I, _P, _U64]),                                 # include/aej_testing.h (tests only)
     "aej_test_jpeg_adobe_pixels_host": (_I, [_P, _I64, _I, _I, _P]),                                        # include/aej_testing.h (tests only)

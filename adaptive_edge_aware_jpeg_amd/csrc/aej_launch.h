@@ -611,6 +611,48 @@ hipError_t launch_resample(hipStream_t st, const RsPlan &plan, const RsBufs &w, 
 
 }  // namespace aej
 
+// filter.hip: Pillow's BoxBlur / GaussianBlur / UnsharpMask on packed 8-bit images of 1 to 4 channels (aej_filter_*)
+namespace aej {
+constexpr int kFtThreads = 512;        // k_filter_tile: eight waves, two workgroups a CU at its largest tile
+constexpr int kFtTileW = 64, kFtTileH = 32;      // output pixels of a fused tile
+constexpr int kFtHalo = 16;            // the most passes * (r + 1) may be on an axis of the fused kernel: 4-channel tiles then take 56 KiB of LDS
+constexpr int kFtSeg = 8;              // samples one lane slides its window over in the fused kernel
+constexpr int kFtPassThreads = 256;    // k_filter_rows, k_filter_cols
+constexpr int kFtRowSpan = 512;        // pixels of a row one k_filter_rows workgroup writes
+constexpr int kFtColBand = 128;        // rows one k_filter_cols lane walks down
+constexpr int kFtColBytes = 4 * kFtPassThreads;      // byte columns of a k_filter_cols workgroup: a lane owns 4
+constexpr int kFtMaxRadius = 1024;
+struct FtEntry {                       // one image of one launch (device pointers set by filter_blob)
+    const unsigned char *in, *orig;    // orig: the unfiltered image where this launch applies the unsharp epilogue, else NULL
+    unsigned char *out;
+    long long tile_base;               // the first workgroup of this image in its launch
+    int w, h;                          // k_filter_tile, k_filter_rows: pixels; k_filter_cols: w is the bytes of a row
+    int nx, ny, hx, hy;                // k_filter_tile: passes per axis (0: none) and the halo passes * (r + 1)
+    int rx, ry;                        // the rows kernel reads the x fields, the columns kernel the y fields
+    unsigned wwx, fwx, wwy, fwy;
+    int percent, threshold;
+};
+struct FtStage {                       // host: an entry and where its pointers come from (0 src, 1 dst, 2 the workspace's buffers)
+    FtEntry e;
+    int in_base, out_base;
+    long long in_off, out_off, orig_off;      // orig_off < 0: no epilogue
+};
+struct FtLaunch { int kernel, ch, first, count; long long tiles; unsigned lds; };      // kernel: 0 tile, 1 rows, 2 columns
+struct FtPlan {
+    std::vector<FtStage> stages;       // launch by launch
+    std::vector<FtLaunch> launches;
+    std::vector<long long> src_offset, dst_offset, bytes;      // per image
+    long long tmp_bytes = 0;
+};
+struct FtBufs { unsigned char *blob, *tmp; };
+int filter_weights(int kind, float xradius, float yradius, aej_filter_plan &p);      // aej_filter_plan_host
+int filter_plan(const aej_filter_desc *descs, int n, int path, FtPlan &plan, int *bad, const char **why);
+unsigned long long filter_carve(void *base, const FtPlan &plan, FtBufs &w);
+void filter_blob(const FtPlan &plan, const FtBufs &w, const unsigned char *src, unsigned char *dst, std::vector<FtEntry> &blob);
+hipError_t launch_filter(hipStream_t st, const FtPlan &plan, const FtBufs &w, const FtEntry *blob_host);
+
+}  // namespace aej
+
 // png.hip: the scanline un-filter of PNG files and their expansion to the output layout (aej_png_unfilter_batch), one workgroup per file
 namespace aej {
 

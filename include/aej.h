@@ -1113,6 +1113,59 @@ AEJ_API int aej_png_unfilter_batch(aej_ctx *ctx, const aej_png_desc *descs_host,
 AEJ_API uint64_t aej_png_filter_bytes(int height, int row_bytes, int bpp);
 AEJ_API int aej_png_filter_batch(aej_ctx *ctx, const int64_t *descs_host, int n, int optimize, uint8_t *out, uint64_t out_bytes);
 
+/* ---- Pillow's BoxBlur, GaussianBlur and UnsharpMask for packed 8-bit images of 1 to 4 channels (filter_many, csrc/filter.hip) --------
+ * Image.filter with ImageFilter.BoxBlur / GaussianBlur / UnsharpMask, bit for bit, for many images of different sizes, channel counts
+ * and filters in one call.  An image is uint8 [h][w][channels], packed; channels are filtered independently (no alpha
+ * pre-multiplication).  The three filters are one family: `passes` runs of one extended box blur per axis, then an optional integer
+ * epilogue, all in uint32 on uint8 samples with a defined rounding after every pass.
+ *   box radius of a Gaussian radius (float32 steps, the square root and the floor in double), passes = 3:
+ *     sigma2 = radius * radius / 3;  L = sqrt(12 sigma2 + 1);  l = floor((L - 1) / 2);
+ *     a = (2 l + 1) (l (l + 1) - 3 sigma2) / (6 (sigma2 - (l + 1) (l + 1)));  box = l + a
+ *   weights of one float32 box radius fr:  r = (int)fr;  ww = (uint32)(2^24 / (fr * 2 + 1)) (a float32 division);
+ *     fw = (uint32)(2^24 - (2 r + 1) ww) / 2
+ *   one pass along a line p of N samples, indices clamped to [0, N - 1]:
+ *     out(x) = (ww * sum(p[x - r .. x + r]) + fw * (p[x - r - 1] + p[x + r + 1]) + 2^23) >> 24
+ *   a filter with box radii (bx, by): if bx != 0, `passes` horizontal passes, each on the uint8 output of the one before; then, if
+ *     by != 0, `passes` vertical ones; both 0: a copy.  AEJ_FILTER_BOX: passes = 1 and the radii as given; AEJ_FILTER_GAUSSIAN:
+ *     passes = 3 and the mapping above per axis; AEJ_FILTER_UNSHARP: the Gaussian, then per sample diff = in - blur and
+ *     out = clip(in + diff * percent / 100, 0, 255) (C division) where |diff| > threshold, in elsewhere.
+ *
+ * aej_filter_plan_host: HOST only, needs no context: the passes and, per axis (x, y), the float32 box radius and r, ww, fw of a
+ *   filter -- the one place where the mapping and the weights are computed; the batch entry uses it.  AEJ_ERR_ARG for an unknown kind
+ *   and a radius that is negative or not finite; AEJ_ERR_UNSUPPORTED for a box radius whose integer part exceeds 1024.
+ * aej_filter_geometry_host: HOST only: out[0..5] = the fused kernel's tile width and height in pixels and its largest halo (the most
+ *   passes * (r + 1) may be on an axis), the pixels of a row kernel's span, the rows of a column kernel's band and the byte columns
+ *   of a column kernel's workgroup.
+ * aej_filter_batch: n images.  src / dst: device bytes; image i is read at src + src_offset and written at dst + dst_offset, exactly
+ *   width * height * channels bytes and no other byte of dst; src and dst must not overlap.  path: AEJ_FILTER_AUTO (per image: the
+ *   fused kernel where its halo allows), AEJ_FILTER_FUSED (AEJ_ERR_ARG naming the image whose filter is beyond the halo) or
+ *   AEJ_FILTER_PASSES.  Fused: one launch per channel count present, one read and one write of the image.  Passes: one launch per
+ *   pass over every image that needs it -- at most 2 * passes launches per channel count present -- through two buffers per image in
+ *   the workspace.  One upload of the entries, then the call waits for it; nothing is copied back.  Every descriptor is checked
+ *   before any device work: AEJ_ERR_ARG naming the image for a size below 1 or above 65535, a channel count outside 1 .. 4, an
+ *   unknown kind, a bad radius, an image outside src_bytes / dst_bytes; AEJ_ERR_UNSUPPORTED naming it for a box radius above 1024 and
+ *   |percent| above 1000000.  Workspace: aej_filter_workspace_bytes with the same descriptors and path (0 for ones the call refuses). */
+enum { AEJ_FILTER_BOX = 0, AEJ_FILTER_GAUSSIAN = 1, AEJ_FILTER_UNSHARP = 2 };
+enum { AEJ_FILTER_AUTO = 0, AEJ_FILTER_FUSED = 1, AEJ_FILTER_PASSES = 2 };
+typedef struct aej_filter_desc {
+    int64_t src_offset, dst_offset;
+    int32_t width, height, channels;
+    int32_t kind;                  /* AEJ_FILTER_* */
+    float xradius, yradius;        /* the filter's radii as given (AEJ_FILTER_UNSHARP: both its one radius) */
+    int32_t percent, threshold;    /* read only for AEJ_FILTER_UNSHARP */
+} aej_filter_desc;
+typedef struct aej_filter_plan {
+    int32_t passes;
+    float box[2];                  /* x, y */
+    int32_t r[2];
+    uint32_t ww[2], fw[2];
+} aej_filter_plan;
+AEJ_API int aej_filter_plan_host(int kind, float xradius, float yradius, aej_filter_plan *out);
+AEJ_API int aej_filter_geometry_host(int32_t *out);
+AEJ_API uint64_t aej_filter_workspace_bytes(aej_ctx *ctx, const aej_filter_desc *descs_host, int n, int path);
+AEJ_API int aej_filter_batch(aej_ctx *ctx, const aej_filter_desc *descs_host, int n, int path, const uint8_t *src, uint64_t src_bytes,
+                             uint8_t *dst, uint64_t dst_bytes, void *workspace, uint64_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif
