@@ -21,6 +21,8 @@ import math
 
 import numpy as np
 
+from ._images import gather_u8, is_int, is_number, one_or_each, packed_views
+
 KINDS = {"BoxBlur": 0, "GaussianBlur": 1, "UnsharpMask": 2}      # AEJ_FILTER_*
 PATHS = {"auto": 0, "fused": 1, "passes": 2}                     # AEJ_FILTER_AUTO / _FUSED / _PASSES
 MAX_BOX_RADIUS = 1024
@@ -51,14 +53,6 @@ class UnsharpMask:
         self.radius = radius
         self.percent = percent
         self.threshold = threshold
-
-
-def _is_number(v):
-    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
-
-
-def _is_int(v):
-    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
 
 
 def filter_plan(kind, xradius, yradius):
@@ -97,10 +91,10 @@ def _check_filter(f, what):
         raise ValueError(f"{what}: filter {f!r}: a BoxBlur, GaussianBlur or UnsharpMask (or an object with that name and its parameters) required")
     radius = f.radius
     if name != "UnsharpMask" and isinstance(radius, (tuple, list)):
-        if len(radius) != 2 or not all(_is_number(v) for v in radius):
+        if len(radius) != 2 or not all(is_number(v) for v in radius):
             raise ValueError(f"{what}: {name} radius {radius!r}: a number or an (x, y) pair of numbers required")
         xy = (float(radius[0]), float(radius[1]))
-    elif _is_number(radius):
+    elif is_number(radius):
         xy = (float(radius), float(radius))
     else:
         raise ValueError(f"{what}: {name} radius {radius!r}: a number{'' if name == 'UnsharpMask' else ' or an (x, y) pair of numbers'} required")
@@ -112,7 +106,7 @@ def _check_filter(f, what):
     if name == "UnsharpMask":
         percent, threshold = getattr(f, "percent", None), getattr(f, "threshold", None)
         for k, v in (("percent", percent), ("threshold", threshold)):
-            if not _is_int(v):
+            if not is_int(v):
                 raise TypeError(f"{what}: UnsharpMask {k} {v!r}: an int required (no bools), as in Pillow")
         percent, threshold = int(percent), int(threshold)
         if abs(percent) > MAX_PERCENT:
@@ -126,14 +120,6 @@ def _check_filter(f, what):
     except NotImplementedError:
         raise NotImplementedError(f"{what}: {name} radius {radius!r}: a box radius above {MAX_BOX_RADIUS} is not built") from None
     return KINDS[name], xy[0], xy[1], percent, threshold, plan
-
-
-def _check_filters(filter, n):
-    if isinstance(filter, (list, tuple)):
-        if len(filter) != n:
-            raise ValueError(f"filter: {len(filter)} entries for {n} images")
-        return [_check_filter(f, f"image {i}") for i, f in enumerate(filter)]
-    return [_check_filter(filter, "every image")] * n
 
 
 def filter_many(images, filter, device: int = 0, _path: str = "auto") -> list:
@@ -154,7 +140,7 @@ def filter_many(images, filter, device: int = 0, _path: str = "auto") -> list:
         raise ValueError("filter_many needs at least one image")
     if not isinstance(_path, str) or _path not in PATHS:
         raise ValueError(f"_path {_path!r}: 'auto', 'fused' or 'passes' required")
-    filters = _check_filters(filter, n)
+    filters = one_or_each(filter, n, _check_filter, "filter", "image")
     if _path == "fused":
         limit = filter_geometry()["max_halo"]
         for i, f in enumerate(filters):
@@ -170,49 +156,27 @@ def filter_many(images, filter, device: int = 0, _path: str = "auto") -> list:
         if max(shape[:2]) > 65535:
             raise ValueError(f"image {i}: sizes up to 65535 a side")
         shapes.append(shape)
-    nbytes = [int(np.prod(s)) for s in shapes]
     ctx = get_context(device)
     t, lib = ctx.torch, ctx.lib
     # the sources: device tensors are read where they are; NumPy arrays and host tensors cross in one pinned copy
-    host = [i for i, a in enumerate(images) if not (isinstance(a, t.Tensor) and a.is_cuda)]
-    keep = {}
-    if host:
-        off, pos = {}, 0
-        for i in host:
-            off[i] = pos
-            pos += nbytes[i]
-        stage = ctx.pinned(pos)
-        for i in host:
-            a = images[i].numpy() if isinstance(images[i], t.Tensor) else images[i]
-            stage.numpy()[off[i]:off[i] + nbytes[i]] = np.ascontiguousarray(a).reshape(-1)
-        up = ctx.empty((pos,), t.uint8)
-        up.copy_(stage[:pos], non_blocking=True)
-        for i in host:
-            keep[i] = up[off[i]:off[i] + nbytes[i]]
-    for i, a in enumerate(images):
-        if i not in keep:
-            keep[i] = a.to(device=ctx.device).contiguous()
-    ptrs = [keep[i].data_ptr() for i in range(n)]
-    base = min(ptrs)
-    end = max(p + nb for p, nb in zip(ptrs, nbytes))
+    src = gather_u8(ctx, images)
+    base, span, src_off = src.span()
     descs = (FilterDesc * n)()
     pos = 0
     for i, (shape, f) in enumerate(zip(shapes, filters)):
         d = descs[i]
-        d.src_offset, d.dst_offset = ptrs[i] - base, pos
+        d.src_offset, d.dst_offset = src_off[i], pos
         d.height, d.width, d.channels = shape[0], shape[1], shape[2] if len(shape) == 3 else 1
         d.kind, d.xradius, d.yradius, d.percent, d.threshold = f[:5]
-        pos += nbytes[i]
+        pos += src.nbytes[i]
     out = ctx.empty((pos,), t.uint8)
     path = PATHS[_path]
     ws = ctx.workspace(max(int(lib.aej_filter_workspace_bytes(ctx.handle, ctypes.addressof(descs), n, path)), 256))
-    ctx.check(lib.aej_filter_batch(ctx.handle, ctypes.addressof(descs), n, path, ctypes.c_void_p(base), ctypes.c_uint64(end - base),
+    ctx.check(lib.aej_filter_batch(ctx.handle, ctypes.addressof(descs), n, path, ctypes.c_void_p(base), ctypes.c_uint64(span),
                                    out.data_ptr(), ctypes.c_uint64(pos), ws.data_ptr(), ctypes.c_uint64(ws.numel())))
-    res = []
-    for i, shape in enumerate(shapes):
-        o = out[descs[i].dst_offset:descs[i].dst_offset + nbytes[i]].view(*shape)
-        com = getattr(images[i], "jpeg_comment", None)
+    res = packed_views(out, [d.dst_offset for d in descs], shapes)
+    for o, a in zip(res, images):
+        com = getattr(a, "jpeg_comment", None)
         if com is not None:
             o.jpeg_comment = com
-        res.append(o)
     return res

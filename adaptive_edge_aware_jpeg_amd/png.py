@@ -12,6 +12,7 @@ from typing import List, Optional
 
 import numpy as np
 
+from ._images import gather_u8, is_int, is_tensor, packed_views, stage_layout
 from ._lib import get_context
 from .jpeg import usable_cpus
 from .standard_jpeg import _buffer, _refuse
@@ -215,7 +216,7 @@ def _decode_parsed(ctx, parsed, views, modes, inflate, workers, events=None):
         if s[1, i]:
             code = int(s[1, i])
             raise ValueError(f"file {i}: {PNG_STATUS[code] if 0 <= code < len(PNG_STATUS) else f'status {code}'}")
-    return [out[int(out_off[i]):int(out_off[i]) + int(np.prod(shapes[i]))].view(shapes[i]) for i in range(n)]
+    return packed_views(out, out_off, shapes)
 
 
 # ---- encode -------------------------------------------------------------------------------------------------------------------------
@@ -227,10 +228,6 @@ IDAT_BYTES = 65536           # Pillow cuts the zlib stream into IDAT chunks of t
 MAX_ENCODE_SIDE = 1 << 24    # rows, and bytes per row, of one image (aej_png_filter_bytes)
 
 
-def _is_tensor(x):
-    return type(x).__module__.split(".")[0] == "torch" and hasattr(x, "data_ptr")
-
-
 def _check_images(images, mode, optimize, compress_level, entropy, workers):
     """The host-side validation of png_encode_many (no device is touched): -> [(image, H, W, bytes per pixel)]."""
     if entropy not in ("gpu", "host"):
@@ -239,15 +236,15 @@ def _check_images(images, mode, optimize, compress_level, entropy, workers):
         raise ValueError(f"mode: {mode!r} is not one of {ENCODE_MODES}")
     if not isinstance(optimize, (bool, np.bool_)):
         raise ValueError(f"optimize: {optimize!r} is not a bool")
-    if isinstance(compress_level, bool) or not isinstance(compress_level, (int, np.integer)) or not 0 <= compress_level <= 9:
+    if not is_int(compress_level) or not 0 <= compress_level <= 9:
         raise ValueError(f"compress_level: {compress_level!r} is not an integer in 0 .. 9")
-    if workers is not None and (isinstance(workers, bool) or not isinstance(workers, (int, np.integer)) or workers < 1):
+    if workers is not None and (not is_int(workers) or workers < 1):
         raise ValueError(f"workers: {workers!r} is neither None nor a positive integer")
-    if isinstance(images, np.ndarray) or _is_tensor(images):
+    if isinstance(images, np.ndarray) or is_tensor(images):
         raise ValueError("images: a list of images is expected, not one array (mixed sizes have no common array)")
     items = []
     for i, x in enumerate(list(images)):
-        if not (isinstance(x, np.ndarray) or _is_tensor(x)):
+        if not (isinstance(x, np.ndarray) or is_tensor(x)):
             raise ValueError(f"image {i}: {type(x).__name__} is neither a numpy array nor a torch tensor")
         if str(x.dtype).split(".")[-1] != "uint8":
             raise ValueError(f"image {i}: dtype {x.dtype} is not uint8")
@@ -289,42 +286,17 @@ def _filter_on_device(ctx, items, optimize, events=None):
     4).  Images that are not on the device cross in one page-locked copy; a tensor that is not contiguous is made so first."""
     t, lib, n = ctx.torch, ctx.lib, len(items)
     sizes = [H * (1 + W * bpp) for _, H, W, bpp in items]
-    offs, pos = [], 0
-    for k in sizes:
-        offs.append(pos)
-        pos = _align4(pos + k)
+    offs, pos = stage_layout(sizes, [True] * n, align=4)
     raw = ctx.empty((pos + 4,), t.uint8)
-    up_off, up = {}, 0
-    for i, (x, H, W, bpp) in enumerate(items):
-        if not (_is_tensor(x) and x.is_cuda):
-            up_off[i] = up
-            up = _align4(up + H * W * bpp)
-    keep, ptrs = [], [0] * n
-    if up:
-        stage = ctx.pinned(up)
-        hb = stage[:up].numpy()
-        for i, o in up_off.items():
-            x, H, W, bpp = items[i]
-            a = x.numpy() if _is_tensor(x) else x
-            hb[o:o + H * W * bpp] = np.ascontiguousarray(a).reshape(-1)
-        dev = ctx.empty((up,), t.uint8)
-        dev.copy_(stage[:up], non_blocking=True)
-        keep.append(dev)
-        for i, o in up_off.items():
-            ptrs[i] = dev.data_ptr() + o
-    for i, (x, H, W, bpp) in enumerate(items):
-        if i not in up_off:
-            x = x.to(ctx.device).contiguous()
-            keep.append(x)
-            ptrs[i] = x.data_ptr()
-    descs = np.array([(ptrs[i], H, W * bpp, bpp, offs[i]) for i, (_, H, W, bpp) in enumerate(items)], np.int64).reshape(n, 5)
+    src = gather_u8(ctx, [x for x, _, _, _ in items], align=4)       # (the caller's read-back ends the staging buffer's use)
+    descs = np.array([(src.ptrs[i], H, W * bpp, bpp, offs[i]) for i, (_, H, W, bpp) in enumerate(items)], np.int64).reshape(n, 5)
     if events is not None:
         events["filter"] = [t.cuda.Event(enable_timing=True), t.cuda.Event(enable_timing=True)]
         events["filter"][0].record()
     ctx.check(lib.aej_png_filter_batch(ctx.handle, descs.ctypes.data, n, 1 if optimize else 0, raw.data_ptr(), ctypes.c_uint64(raw.numel())))
     if events is not None:
         events["filter"][1].record()
-    return raw, offs, sizes, keep
+    return raw, offs, sizes, src.keep
 
 
 def _deflate_on_device(ctx, raw, items, offs, sizes):

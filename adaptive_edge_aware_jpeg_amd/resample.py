@@ -22,6 +22,7 @@ import math
 
 import numpy as np
 
+from ._images import gather_u8, is_int, is_number, one_or_each, packed_views
 from ._lib import get_context
 
 FILTERS = {"box": 4, "bilinear": 2, "hamming": 5, "bicubic": 3, "lanczos": 1}      # Pillow's Image.Resampling integers
@@ -35,7 +36,7 @@ def _check_filter(resample, what="resample") -> int:
             raise NotImplementedError(f"{what}: resample 'nearest': Pillow takes another path for it, which is not built")
         if resample in FILTERS:
             return FILTERS[resample]
-    elif isinstance(resample, (int, np.integer)) and not isinstance(resample, (bool, np.bool_)):
+    elif is_int(resample):
         if int(resample) == 0:
             raise NotImplementedError(f"{what}: resample 0 (nearest): Pillow takes another path for it, which is not built")
         if int(resample) in _SUPPORT:
@@ -43,32 +44,18 @@ def _check_filter(resample, what="resample") -> int:
     raise ValueError(f"{what}: resample {resample!r}: 'box', 'bilinear', 'hamming', 'bicubic', 'lanczos' or Pillow's 4, 2, 5, 3, 1 required")
 
 
-def _check_filters(resample, n, what):
-    """one filter, or a list / tuple of one per image -> list of n of Pillow's integers.  A refusal names the image (`what` and its
-    index) whose entry it is, or "every `what`" for the one filter all of them share."""
-    if isinstance(resample, (list, tuple)):
-        if len(resample) != n:
-            raise ValueError(f"resample: {len(resample)} entries for {n} {what}s")
-        return [_check_filter(r, f"{what} {i}") for i, r in enumerate(resample)]
-    return [_check_filter(resample, f"every {what}")] * n
-
-
 def _check_gap(gap, what="reducing_gap"):
     """reducing_gap, which all images of a call share: `what` says so in a refusal ("every image")"""
     if gap is None:
         return None
-    if isinstance(gap, (bool, np.bool_)) or not isinstance(gap, (int, float, np.integer, np.floating)) or not gap >= 1.0:
+    if not is_number(gap) or not gap >= 1.0:
         raise ValueError(f"{what}: reducing_gap must be 1.0 or greater (got {gap!r})")
     return float(gap)
 
 
-def _is_number(v):
-    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
-
-
 def _check_size(size, what, integers=True):
     """one (w, h): positive integers (or, for a thumbnail request, positive numbers whose floor is at least 1)"""
-    ok = not isinstance(size, (str, bytes)) and hasattr(size, "__len__") and len(size) == 2 and all(_is_number(v) for v in size)
+    ok = not isinstance(size, (str, bytes)) and hasattr(size, "__len__") and len(size) == 2 and all(is_number(v) for v in size)
     if ok and integers:
         ok = all(int(v) == v and v >= 1 for v in size)
     elif ok:
@@ -84,7 +71,7 @@ def _per_item(value, n, width, name, what):
         return [None] * n
     if isinstance(value, (str, bytes)) or not hasattr(value, "__len__"):
         raise ValueError(f"{name} {value!r}: {width} numbers, or one such entry per {what}, required")
-    if len(value) == width and all(_is_number(v) or isinstance(v, (bool, np.bool_)) for v in value):
+    if len(value) == width and all(is_number(v) or isinstance(v, (bool, np.bool_)) for v in value):
         return [tuple(value)] * n
     if len(value) != n:
         raise ValueError(f"{name}: {len(value)} entries for {n} {what}s")
@@ -131,7 +118,7 @@ def _steps(what, W, H, size, box, f, gap):
     if box is None:
         box = whole
     else:
-        if len(box) != 4 or not all(_is_number(v) and math.isfinite(v) for v in box):
+        if len(box) != 4 or not all(is_number(v) and math.isfinite(v) for v in box):
             raise ValueError(f"{what}: box {box!r}: four numbers (x0, y0, x1, y1) required")
         b = [float(np.float32(v)) for v in box]       # as Pillow's C code sees it
         if b[0] < 0 or b[1] < 0:
@@ -191,8 +178,7 @@ def _run(ctx, src, src_bytes, src_off, steps, f, channels=None, windows=None, pa
                                                        out.data_ptr(), ctypes.c_uint64(pos), ws.data_ptr(), ctypes.c_uint64(ws.numel())))
     if packed:
         return out
-    return [out[o:o + s["dst"][0] * s["dst"][1] * c].view(*((s["dst"][1], s["dst"][0]) + ((3,) if c == 3 else ())))
-            for o, s, c in zip(dst_off, steps, ch)]
+    return packed_views(out, dst_off, [(s["dst"][1], s["dst"][0]) + ((3,) if c == 3 else ()) for s, c in zip(steps, ch)])
 
 
 def resample_taps(in_size: int, in0: float, in1: float, out_size: int, resample="bicubic"):
@@ -210,7 +196,7 @@ def resample_taps(in_size: int, in0: float, in1: float, out_size: int, resample=
 
 
 def resize_many(images, size, resample="bicubic", box=None, reducing_gap=None, device: int = 0, mode: str = "RGB") -> list:
-    """Resize uint8 [H_i, W_i, 3] (RGB) and, with mode=, [H_i, W_i] (mode "L") images (device tensors or NumPy arrays, of mixed sizes) on
+    """Resize uint8 [H_i, W_i, 3] (RGB) and, with mode=, [H_i, W_i] (mode "L") images (device tensors, host tensors or NumPy arrays, of mixed sizes) on
     the device: -> list of uint8 [h_i, w_i, 3] / [h_i, w_i] tensors -- output i has the rank of input i --, views into one packed
     allocation; element i equals ``np.asarray(Image.fromarray(a_i).resize(size_i, F, box=box_i, reducing_gap=reducing_gap))``.
     mode, as standard_jpeg_encode_many's: "RGB" (the default: the call as it always was, every image [H, W, 3], an [H, W] image refused
@@ -226,10 +212,10 @@ def resize_many(images, size, resample="bicubic", box=None, reducing_gap=None, d
     n = len(images)
     if n < 1:
         raise ValueError("resize_many needs at least one image")
-    f, gap = _check_filters(resample, n, "image"), _check_gap(reducing_gap, "every image")
+    f, gap = one_or_each(resample, n, _check_filter, "resample", "image"), _check_gap(reducing_gap, "every image")
     if not isinstance(mode, str) or mode not in ("RGB", "L", "auto"):
         raise ValueError(f"mode {mode!r}: 'RGB', 'L' or 'auto' required")
-    if not isinstance(size, (str, bytes)) and hasattr(size, "__len__") and len(size) == 2 and all(_is_number(v) or isinstance(v, (bool, np.bool_)) for v in size):
+    if not isinstance(size, (str, bytes)) and hasattr(size, "__len__") and len(size) == 2 and all(is_number(v) or isinstance(v, (bool, np.bool_)) for v in size):
         sizes = [_check_size(size, "resize_many")] * n
     else:
         if isinstance(size, (str, bytes)) or not hasattr(size, "__len__") or len(size) != n:
@@ -249,29 +235,8 @@ def resize_many(images, size, resample="bicubic", box=None, reducing_gap=None, d
             raise ValueError(f"image {i}: sizes up to 65535 a side")
         steps.append(_steps(f"image {i}", shape[1], shape[0], sizes[i], boxes[i], f[i], gap))
         shapes.append(shape)
-    nbytes = [int(np.prod(s)) for s in shapes]
     ctx = get_context(device)
-    t = ctx.torch
-    # the sources: device tensors are read where they are; NumPy arrays cross in one pinned copy
-    host = [i for i, a in enumerate(images) if not isinstance(a, t.Tensor)]
-    keep = {}
-    if host:
-        off, pos = {}, 0
-        for i in host:
-            off[i] = pos
-            pos += nbytes[i]
-        stage = ctx.pinned(pos)
-        for i in host:
-            nb = nbytes[i]
-            stage.numpy()[off[i]:off[i] + nb] = np.ascontiguousarray(images[i]).reshape(-1)
-        up = ctx.empty((pos,), t.uint8)
-        up.copy_(stage[:pos], non_blocking=True)
-        for i in host:
-            keep[i] = up[off[i]:off[i] + nbytes[i]]
-    for i, a in enumerate(images):
-        if i not in keep:
-            keep[i] = a.to(device=ctx.device).contiguous()
-    ptrs = [keep[i].data_ptr() for i in range(n)]
-    base = min(ptrs)
-    end = max(p + nb for p, nb in zip(ptrs, nbytes))
-    return _run(ctx, base, end - base, [p - base for p in ptrs], steps, f, [3 if len(s) == 3 else 1 for s in shapes])
+    # the sources: device tensors are read where they are; NumPy arrays and host tensors cross in one pinned copy
+    src = gather_u8(ctx, images)              # (held until _run's entry has synchronised)
+    base, span, src_off = src.span()
+    return _run(ctx, base, span, src_off, steps, f, [3 if len(s) == 3 else 1 for s in shapes])

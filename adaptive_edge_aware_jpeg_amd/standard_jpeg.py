@@ -55,6 +55,7 @@ from typing import List, Sequence, Tuple
 
 import numpy as np
 
+from ._images import gather_u8, is_int, is_number, is_tensor, one_or_each, packed_views
 from ._lib import get_context
 
 HEADER_CAPACITY = 1024       # SOI .. SOS are 623 bytes with the Annex K Huffman tables; optimised tables are never longer
@@ -75,7 +76,7 @@ def _check_subsampling(s) -> int:
     """"4:4:4" / "4:2:2" / "4:2:0" or Pillow's 0 / 1 / 2 -> 0 / 1 / 2"""
     if isinstance(s, str) and s in SUBSAMPLING:
         return SUBSAMPLING[s]
-    if isinstance(s, (int, np.integer)) and not isinstance(s, (bool, np.bool_)) and 0 <= int(s) <= 2:
+    if is_int(s) and 0 <= int(s) <= 2:
         return int(s)
     raise ValueError(f"subsampling {s!r}: '4:4:4', '4:2:2', '4:2:0' or 0, 1, 2 required")
 
@@ -442,7 +443,7 @@ SCALES = (1, 2, 4, 8)
 
 
 def _check_scale(s) -> int:
-    if isinstance(s, (bool, np.bool_)) or not isinstance(s, (int, np.integer)) or int(s) not in SCALES:
+    if not is_int(s) or int(s) not in SCALES:
         raise ValueError(f"scale {s!r}: 1, 2, 4 or 8 required")
     return int(s)
 
@@ -480,7 +481,7 @@ def _check_decode_box(b, who):
     if not isinstance(b, (list, tuple)) or len(b) != 4:
         raise TypeError(f"{who}: box {b!r}: (left, top, right, bottom) required")
     for v in b:
-        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+        if not is_int(v):
             raise TypeError(f"{who}: box {tuple(b)!r}: four integers required")
     return tuple(int(v) for v in b)
 
@@ -584,7 +585,7 @@ def decode_box_stats(device: int = 0):
 
 def _views(out, out_off, shapes, comps):
     """the images of a packed decode: [h, w, 3], [h, w] where comps says 1, or [h, w, 4] where it says 4"""
-    return [out[int(o):int(o) + h * w * c].view(*((h, w) if c == 1 else (h, w, c))) for o, (h, w), c in zip(out_off, shapes, comps)]
+    return packed_views(out, out_off, [(h, w) if c == 1 else (h, w, c) for (h, w), c in zip(shapes, comps)])
 
 
 def draft_scale(width: int, height: int, size) -> int:
@@ -787,10 +788,9 @@ def thumbnail_plan(width: int, height: int, size, reducing_gap=2.0):
 def _check_crop_box(b, who):
     """one crop box of the resized-crop calls -> (l, t, r, b) of numbers; TypeError for anything that is not a list / tuple of four
     finite numbers (a bool is none)"""
-    from .resample import _is_number
     if not isinstance(b, (list, tuple)) or len(b) != 4:
         raise TypeError(f"{who}: box {b!r}: (left, top, right, bottom) required")
-    if not all(_is_number(v) and math.isfinite(v) for v in b):
+    if not all(is_number(v) and math.isfinite(v) for v in b):
         raise TypeError(f"{who}: box {tuple(b)!r}: four finite numbers required")
     return tuple(v.item() if isinstance(v, np.generic) else v for v in b)
 
@@ -907,7 +907,7 @@ def standard_jpeg_thumbnail_many(files, size, resample="bicubic", reducing_gap=2
     if n < 1:
         raise ValueError("standard_jpeg_thumbnail_many needs at least one file")
     modes = _check_modes(mode, n)
-    f, gap = RS._check_filters(resample, n, "file"), RS._check_gap(reducing_gap, "every file")
+    f, gap = one_or_each(resample, n, RS._check_filter, "resample", "file"), RS._check_gap(reducing_gap, "every file")
     if not isinstance(size, (str, bytes)) and hasattr(size, "__len__") and len(size) == 2 and not any(hasattr(v, "__len__") for v in size):
         sizes = [RS._check_size(size, "standard_jpeg_thumbnail_many", integers=False)] * n
     else:
@@ -1110,7 +1110,7 @@ def _check_box(box, i):
     if box is None:
         return None
     ok = not isinstance(box, (str, bytes)) and hasattr(box, "__len__") and len(box) == 4 and \
-        all(isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) for v in box)
+        all(is_int(v) for v in box)
     if not ok:
         raise ValueError(f"file {i}: crop {box!r}: (left, upper, right, lower) as four ints, or None, required")
     return tuple(int(v) for v in box)
@@ -1471,7 +1471,7 @@ def _check_images(images, mode="RGB"):
         raise ValueError(f"{len(images)} images: at most 65535 in one call")
     out = []
     for i, x in enumerate(images):
-        is_torch = type(x).__module__.split(".")[0] == "torch" and hasattr(x, "data_ptr")      # (no import: torch may not see a device yet)
+        is_torch = is_tensor(x)
         if not is_torch:
             x = np.asarray(x)
         dt = str(x.dtype)
@@ -1491,35 +1491,36 @@ def _check_images(images, mode="RGB"):
 
 
 def _packed_source(ctx, imgs):
-    """-> (a device uint8 tensor that keeps the pixels alive, its address, its bytes, int64 offsets of the images in it).  Device uint8
-    tensors that are contiguous views of one allocation on this device are used where they lie; anything else is packed into a new buffer."""
+    """-> (what keeps the pixels alive on the device, the source's address, its bytes, int64 offsets of the images in it).  Device uint8
+    tensors that are contiguous views of one allocation on this device are used where they lie; anything else is packed into a new buffer
+    (images that are all on the host by _images.gather_u8, whose staging contract aej_jfif_many_encode's synchronise meets)."""
     t, n = ctx.torch, len(imgs)
     if all(is_t and not is_f and x.is_cuda and x.device == ctx.device and x.is_contiguous() for x, is_t, is_f in imgs):
         st = imgs[0][0].untyped_storage()
         if all(x.untyped_storage().data_ptr() == st.data_ptr() for x, _, _ in imgs):
             off = np.array([x.data_ptr() - st.data_ptr() for x, _, _ in imgs], np.int64)
             return [x for x, _, _ in imgs], st.data_ptr(), st.nbytes(), off
-    sizes = np.array([int(np.prod(x.shape)) for x, _, _ in imgs], np.int64)      # 3 H W, or H W of a grey image
-    off = np.concatenate(([0], np.cumsum(sizes)[:-1])).astype(np.int64)
-    total = int(sizes.sum())
-    buf = ctx.empty((total,), t.uint8)
     if not any(is_t for _, is_t, _ in imgs):                 # every image on the host: one pinned copy
-        stage = ctx.pinned(total)
-        host = stage.numpy()
+        arrays = []
         for i, (x, _, is_f) in enumerate(imgs):
             if is_f:
                 if not (x.min() >= 0.0 and x.max() <= 1.0):
                     raise ValueError(f"image {i}: float32 images must lie in [0, 1]")
                 x = np.rint(x * np.float32(255)).astype(np.uint8)
-            host[off[i]:off[i] + sizes[i]] = x.reshape(-1)
-        buf.copy_(stage[:total], non_blocking=True)
-    else:
-        for i, (x, _, _) in enumerate(imgs):
-            try:
-                u8 = _to_u8(ctx, x) if x.ndim == 3 else _values_u8(ctx, x)
-            except ValueError as e:
-                raise ValueError(f"image {i}: {e}") from None
-            buf[int(off[i]):int(off[i] + sizes[i])].copy_(u8.reshape(-1))
+            arrays.append(x)
+        src = gather_u8(ctx, arrays)
+        base, total, off = src.span()
+        return src.keep, base, total, np.array(off, np.int64)
+    sizes = np.array([int(np.prod(x.shape)) for x, _, _ in imgs], np.int64)      # 3 H W, or H W of a grey image
+    off = np.concatenate(([0], np.cumsum(sizes)[:-1])).astype(np.int64)
+    total = int(sizes.sum())
+    buf = ctx.empty((total,), t.uint8)
+    for i, (x, _, _) in enumerate(imgs):
+        try:
+            u8 = _to_u8(ctx, x) if x.ndim == 3 else _values_u8(ctx, x)
+        except ValueError as e:
+            raise ValueError(f"image {i}: {e}") from None
+        buf[int(off[i]):int(off[i] + sizes[i])].copy_(u8.reshape(-1))
     return buf, buf.data_ptr(), total, off
 
 
