@@ -125,6 +125,17 @@ AEJ_HD inline int jd_comp4(const aej_jpegdec_desc &d, int k) { const int n0 = d.
 
 enum { kJdRunStop = 0, kJdRunOutOfBits = 1, kJdRunBadCode = 2, kJdRunPast63 = 3, kJdRunBadDc = 4, kJdRunDone = 5 };
 
+// One Huffman symbol from the 32-bit window at a position that has `avail` (>= 1) bits left in its restart segment.  The window's bits
+// from `avail` on are whatever follows the segment in memory -- the next segment, or bytes nobody wrote -- and must decide nothing: a code
+// of at most `avail` bits is found whatever they hold (the table is a prefix code, shorter lengths are tried first); everything else --
+// a match longer than `avail`, or no match while fewer than 16 bits are left -- is a segment that ends inside a code.  Without this rule a
+// truncated file was "truncated scan" or "bad Huffman code" (or "DC category above 11") depending on the bytes behind its data.
+AEJ_HD inline int jd_symbol(const aej_jpegdec_huff &h, unsigned win, long long avail, int &len, int &sym)
+{
+    if (!jd_huff(h, win, len, sym)) return avail < 16 ? kJdRunOutOfBits : kJdRunBadCode;
+    return len > avail ? kJdRunOutOfBits : kJdRunStop;
+}
+
 // Decode symbols from state (pos, k, z) while pos < stop; no symbol may end past seg_end.  Counts the blocks started and sums their
 // DC differences per component.  kWrite: also stores the coefficients (natural order) of blocks [0, seg_blocks) of the segment into
 // coef (its block 0), with DC predictors pred[], `next` being the index of the next block to start; stops once every block is done.
@@ -146,7 +157,8 @@ AEJ_HD inline int jd_run(const aej_jpegdec_desc &d, JdBits &br, long long &pos, 
         const aej_jpegdec_huff &h = kFour && c == 3 ? (z == 0 ? x->dc3 : x->ac3) : z == 0 ? d.dc[c] : d.ac[c];
         const unsigned win = br.peek32(pos);
         int len, sym;
-        if (!jd_huff(h, win, len, sym)) return kJdRunBadCode;
+        const int rc = jd_symbol(h, win, seg_end - pos, len, sym);
+        if (rc != kJdRunStop) return rc;
         const int sz = z == 0 ? sym : (sym & 15);
         if (z == 0 && sym > 11) return kJdRunBadDc;
         if (pos + len + sz > seg_end) return kJdRunOutOfBits;

@@ -65,7 +65,8 @@ struct JpBits {
         if (pos >= end) return kJdRunOutOfBits;
         const unsigned win = br.peek32(pos);
         int len;
-        if (!jd_huff(h, win, len, sym)) return kJdRunBadCode;
+        const int rc = jd_symbol(h, win, end - pos, len, sym);      // (the bits behind `end` decide nothing: jpegdec_core.h)
+        if (rc != kJdRunStop) return rc;
         const int nb = extra(sym);
         if (nb < 0) return kJdRunBadDc;
         if (pos + len + nb > end) return kJdRunOutOfBits;

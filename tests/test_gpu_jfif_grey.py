@@ -364,7 +364,8 @@ def _abi_call(ctx, rows, src, src_bytes, out, cap, ss=2, opt=0, prog=0):
     descs = (JfifManyDesc * n)(*[JfifManyDesc(*r) for r in rows])
     nws = int(lib.aej_jfif_many_workspace_bytes(ctx.handle, ctypes.addressof(descs), n, ss, opt, prog))
     ws = torch.empty(max(nws, 256), dtype=torch.uint8, device="cuda")
-    offsets, lengths = torch.zeros(n, dtype=torch.int64, device="cuda"), torch.zeros(n, dtype=torch.int64, device="cuda")
+    # outputs the entry writes: they start as 0xA5 bytes, not as zeros it could lean on
+    offsets, lengths = (torch.full((8 * n,), 0xA5, dtype=torch.uint8, device="cuda").view(torch.int64) for _ in range(2))
     total, groups = ctypes.c_uint64(), ctypes.c_int32()
     rc = lib.aej_jfif_many_encode(ctx.handle, ctypes.addressof(descs), n, src.data_ptr(), ctypes.c_uint64(src_bytes), ss, opt, prog,
                                   out.data_ptr() if out is not None else None, ctypes.c_uint64(cap), offsets.data_ptr(), lengths.data_ptr(),

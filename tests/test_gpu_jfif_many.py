@@ -118,7 +118,7 @@ def test_input_forms_give_the_same_bytes(A, images, encoded):
     assert enc([(d.float() / 255) if k % 2 else d for k, d in enumerate(dev)]) == want        # float and uint8 tensors mixed
     strided = []
     for x in images:                                                 # every second row / column of a larger tensor
-        big = torch.zeros((2 * x.shape[0], 2 * x.shape[1], 3), dtype=torch.uint8, device="cuda")
+        big = torch.full((2 * x.shape[0], 2 * x.shape[1], 3), 0xA5, dtype=torch.uint8, device="cuda")      # what lies between the strides is not the image
         big[::2, ::2] = torch.from_numpy(x).cuda()
         strided.append(big[::2, ::2])
     assert not strided[-1].is_contiguous() and enc(strided) == want
@@ -168,7 +168,8 @@ def _abi_call(ctx, rows, src, src_bytes, out, cap, ss=2, opt=0, prog=0):
     descs = (JfifManyDesc * n)(*[JfifManyDesc(o, w, h, q, 0) for o, w, h, q in rows])
     nws = int(lib.aej_jfif_many_workspace_bytes(ctx.handle, ctypes.addressof(descs), n, ss, opt, prog))
     ws = torch.empty(max(nws, 256), dtype=torch.uint8, device="cuda")
-    offsets, lengths = torch.zeros(n, dtype=torch.int64, device="cuda"), torch.zeros(n, dtype=torch.int64, device="cuda")
+    # outputs the entry writes: they start as 0xA5 bytes, not as zeros it could lean on
+    offsets, lengths = (torch.full((8 * n,), 0xA5, dtype=torch.uint8, device="cuda").view(torch.int64) for _ in range(2))
     total, groups = ctypes.c_uint64(), ctypes.c_int32()
     rc = lib.aej_jfif_many_encode(ctx.handle, ctypes.addressof(descs), n, src.data_ptr(), ctypes.c_uint64(src_bytes), ss, opt, prog,
                                   out.data_ptr() if out is not None else None, ctypes.c_uint64(cap), offsets.data_ptr(), lengths.data_ptr(),

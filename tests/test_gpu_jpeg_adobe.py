@@ -190,7 +190,7 @@ def _c_call(A, data, scale, box, comps, out):
     scan = torch.frombuffer(bytearray(data[d.scan_offset:d.scan_offset + d.scan_length]), dtype=torch.uint8).cuda()
     sc, bx, cc = (ctypes.c_int * 1)(scale), (ctypes.c_int32 * 4)(*box), (ctypes.c_int * 1)(comps)
     so, oo = (ctypes.c_int64 * 1)(0), (ctypes.c_int64 * 1)(0)
-    status = torch.zeros(1, dtype=torch.int32, device="cuda")
+    status = torch.full((1,), -0x5A5A5A5B, dtype=torch.int32, device="cuda")      # 0xA5 bytes: the entry clears its status words itself
     full = (ctypes.c_int * 1)(4 if d.ncomp == 4 else 3)
     nws = int(lib.aej_jpegdec_workspace_bytes_adobe(ctx.handle, ctypes.addressof(descs), 1, None, ctypes.addressof(full), None, ctypes.addressof(xs)))
     assert nws > 0
@@ -248,7 +248,7 @@ def test_null_array_is_the_box_call(A):
     outs = []
     for extra, fn in (((), lib.aej_jpegdec_batch_box), ((None,), lib.aej_jpegdec_batch_adobe), ((ctypes.addressof(xs),), lib.aej_jpegdec_batch_adobe)):
         out = torch.full((n * 83 * 61 * 3,), 7, dtype=torch.uint8, device="cuda")
-        status = torch.zeros(n, dtype=torch.int32, device="cuda")
+        status = torch.full((n,), -0x5A5A5A5B, dtype=torch.int32, device="cuda")      # 0xA5 bytes: the entry clears its status words itself
         assert fn(*head, *extra, scans.data_ptr(), ctypes.c_uint64(scans.numel()), ctypes.addressof(so), out.data_ptr(), ctypes.c_uint64(out.numel()),
                   ctypes.addressof(oo), status.data_ptr(), ws.data_ptr(), ctypes.c_uint64(nws)) == 0
         torch.cuda.synchronize()

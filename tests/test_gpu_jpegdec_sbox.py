@@ -240,7 +240,7 @@ def _c_decode(A, entry, data, scale, box, out):
     scan = torch.frombuffer(bytearray(data[d.scan_offset:d.scan_offset + d.scan_length]), dtype=torch.uint8).cuda()
     sc, bx = (ctypes.c_int * 1)(scale), (ctypes.c_int32 * 4)(*box)
     so, oo = (ctypes.c_int64 * 1)(0), (ctypes.c_int64 * 1)(0)
-    status = torch.zeros(1, dtype=torch.int32, device="cuda")
+    status = torch.full((1,), -0x5A5A5A5B, dtype=torch.int32, device="cuda")      # 0xA5 bytes: the entry clears its status words itself
     nws = int(lib.aej_jpegdec_workspace_bytes_mode(ctx.handle, ctypes.addressof(descs), 1, None, None))
     ws = torch.empty(nws, dtype=torch.uint8, device="cuda")
     return getattr(lib, entry)(ctx.handle, ctypes.addressof(descs), 1, ctypes.addressof(sc), None, ctypes.addressof(bx), scan.data_ptr(),

@@ -156,8 +156,9 @@ def test_c_entry(A):
     pal = np.stack([np.frombuffer(bytes(d.palette), np.uint8) for d in descs])
     dev = lambda a: torch.from_numpy(a).cuda()  # noqa: E731
     d_src, d_table, d_pal = dev(src), dev(table), dev(pal)
-    raw = torch.zeros(int(in_off[1]) + (sizes[1] + 3) // 4 * 4, dtype=torch.uint8, device="cuda")
-    inflated = torch.zeros(2, dtype=torch.int64, device="cuda")
+    # what the two entries write (scanlines, inflated sizes) and their scratch start as 0xA5 bytes, not as zeros they could lean on
+    raw = torch.full((int(in_off[1]) + (sizes[1] + 3) // 4 * 4,), 0xA5, dtype=torch.uint8, device="cuda")
+    inflated = torch.full((16,), 0xA5, dtype=torch.uint8, device="cuda").view(torch.int64)
     ist = torch.full((2,), -1, dtype=torch.int32, device="cuda")
     status = torch.full((2,), -1, dtype=torch.int32, device="cuda")
     want = [R.expected(names[0], "RGB"), R.expected(names[1], "auto")]
@@ -167,7 +168,7 @@ def test_c_entry(A):
                                     inflated.data_ptr(), ist.data_ptr()))
     nws = int(lib.aej_png_workspace_bytes(ctx.handle, ctypes.addressof(descs), 2))
     assert nws > 0 and nws % 256 == 0
-    ws = torch.zeros(nws, dtype=torch.uint8, device="cuda")
+    ws = torch.full((nws,), 0xA5, dtype=torch.uint8, device="cuda")
     ctx.check(lib.aej_png_unfilter_batch(ctx.handle, ctypes.addressof(descs), 2, raw.data_ptr(), ctypes.c_uint64(raw.numel()), in_off.ctypes.data,
                                          inflated.data_ptr(), ist.data_ptr(), d_pal.data_ptr(), layouts.ctypes.data, out.data_ptr(),
                                          ctypes.c_uint64(out.numel()), out_off.ctypes.data, status.data_ptr(), ws.data_ptr(), ctypes.c_uint64(nws)))
