@@ -8,7 +8,7 @@ pixel-identical to Pillow), ``resize_many`` (``Image.resize``) and ``standard_jp
 both pixel-identical to Pillow too; ``standard_jpeg_encode_many`` encodes images of mixed sizes and qualities in one call and
 ``standard_jpeg_thumbnail_jpeg_many`` goes from JPEG files to their JPEG thumbnails on the device; ``png_decode_many`` decodes PNG files
 on the device, pixel-identical to Pillow, and ``png_encode_many`` writes them there with Pillow's scanline filtering; ``filter_many`` is ``Image.filter`` with Pillow's ``BoxBlur``,
-``GaussianBlur`` and ``UnsharpMask``, pixel-identical as well.  The arithmetic runs in hand-written HIP kernels behind the
+``GaussianBlur`` and ``UnsharpMask``, its ``Kernel`` (``SHARPEN`` and the other built-ins), rank (``MedianFilter`` ...) and mode filters, pixel-identical as well.  The arithmetic runs in hand-written HIP kernels behind the
 C ABI of ``libaejpeg_hip.so`` (include/aej.h); there is no CPU fallback.
 """
 from ._lib import _look_at_hw_queues, configure_hw_queues, hw_queues, set_hw_queues
@@ -21,7 +21,8 @@ _look_at_hw_queues()
 from .color import apply_normalization, convert, get_color_spaces  # noqa: E402
 from .edge_detection import EdgeDetection  # noqa: E402
 from .evaluation_metrics import EvaluationMetrics  # noqa: E402
-from .filters import BoxBlur, GaussianBlur, UnsharpMask, filter_many  # noqa: E402
+from .filters import (BLUR, CONTOUR, DETAIL, EDGE_ENHANCE, EDGE_ENHANCE_MORE, EMBOSS, FIND_EDGES, SHARPEN, SMOOTH, SMOOTH_MORE, BoxBlur, GaussianBlur, Kernel,  # noqa: E402
+                      MaxFilter, MedianFilter, MinFilter, ModeFilter, RankFilter, UnsharpMask, filter_many)
 from .image import Image  # noqa: E402
 from .jpeg import EncodedBatch, Jpeg  # noqa: E402
 from .lpips import LpipsWeights  # noqa: E402
@@ -41,4 +42,5 @@ __all__ = ["Jpeg", "JpegCompressionSettings", "EncodedBatch", "Image", "Evaluati
            "resize_many", "standard_jpeg_thumbnail_many", "thumbnail_plan", "standard_jpeg_encode_many", "standard_jpeg_thumbnail_jpeg_many",
            "encode_groups", "transform_prefix", "transform_crop_box", "decode_box_window", "decode_box_stats", "resized_crop_plan",
            "standard_jpeg_resized_crop_many", "png_decode_many", "png_parse_header", "png_encode_many",
-           "BoxBlur", "GaussianBlur", "UnsharpMask", "filter_many"]
+           "BoxBlur", "GaussianBlur", "UnsharpMask", "filter_many", "Kernel", "RankFilter", "MedianFilter", "MinFilter", "MaxFilter", "ModeFilter",
+           "BLUR", "CONTOUR", "DETAIL", "EDGE_ENHANCE", "EDGE_ENHANCE_MORE", "EMBOSS", "FIND_EDGES", "SHARPEN", "SMOOTH", "SMOOTH_MORE"]

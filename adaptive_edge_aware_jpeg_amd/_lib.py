@@ -199,6 +199,13 @@ class FilterPlan(ctypes.Structure):
                 ("fw", ctypes.c_uint32 * 2)]
 
 
+class WindowDesc(ctypes.Structure):
+    """aej_window_desc (include/aej.h): one image of aej_window_batch"""
+    _fields_ = [("src_offset", ctypes.c_int64), ("dst_offset", ctypes.c_int64), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("channels", ctypes.c_int32), ("kind", ctypes.c_int32), ("size", ctypes.c_int32), ("rank", ctypes.c_int32),
+                ("scale", ctypes.c_float), ("offset", ctypes.c_float), ("kernel", ctypes.c_float * 25), ("reserved", ctypes.c_int32)]
+
+
 class PngDesc(ctypes.Structure):
     """aej_png_desc (include/aej.h): what aej_png_parse_host reads from a file's chunks"""
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("bit_depth", ctypes.c_int32), ("colour_type", ctypes.c_int32),
@@ -377,6 +384,9 @@ SIGNATURES = {
     "aej_filter_geometry_host": (_I, [_P]),
     "aej_filter_workspace_bytes": (_U64, [_P, _P, _I, _I]),
     "aej_filter_batch": (_I, [_P, _P, _I, _I, _P, _U64, _P, _U64, _P, _U64]),
+    "aej_window_geometry_host": (_I, [_P]),
+    "aej_window_workspace_bytes": (_U64, [_P, _P, _I]),
+    "aej_window_batch": (_I, [_P, _P, _I, _P, _U64, _P, _U64, _P, _U64]),
     "aej_test_jpegprog_coefs": (_I, [_P, _P, _P, _I, _P, _U64, _P, _I, _P, _U64, _P, _P, _U64]),             # include/aej_testing.h (tests only)
     "aej_test_jpegprog_coefs_host": (_I, [_P, _P, _P, _U64, _I, _P, _U64]),                                 # include/aej_testing.h (tests only)
     "aej_test_jpeg_adobe_pixels_host": (_I, [_P, _I64, _I, _I, _P]),                                        # include/aej_testing.h (tests only)

@@ -653,6 +653,33 @@ hipError_t launch_filter(hipStream_t st, const FtPlan &plan, const FtBufs &w, co
 
 }  // namespace aej
 
+// window.hip: Pillow's Kernel, rank and mode filters on packed 8-bit images of 1 to 4 channels (aej_window_*)
+namespace aej {
+constexpr int kWnThreads = 512;        // eight waves: a lane produces 4 adjacent bytes of a tile row at a time
+constexpr int kWnTileW = 64, kWnTileH = 32;      // output pixels of a tile
+constexpr int kWnKernelHalo = 2, kWnRankHalo = 7, kWnModeHalo = 3;      // the largest r of each kind: a 4-channel rank-15 tile takes 14 KiB of LDS
+struct WnEntry {                       // one image of one launch (device pointers set by window_blob)
+    const unsigned char *in;
+    unsigned char *out;
+    long long tile_base;               // the first workgroup of this image in its launch
+    int w, h;                          // pixels
+    int r, rank;                       // the halo size / 2; the rank kernel's rank
+    float ss0;                         // Kernel: offset + 0.5f
+    float q[25];                       // Kernel: kernel[i] / scale
+};
+struct WnLaunch { int kind, ch, size, first, count; long long tiles; unsigned lds; };      // size: the Kernel's (3 or 5), else 0
+struct WnPlan {
+    std::vector<WnEntry> entries;      // launch by launch; in / out hold nothing yet
+    std::vector<int> image;            // the image of each entry
+    std::vector<WnLaunch> launches;
+    std::vector<long long> src_offset, dst_offset, bytes;      // per image
+};
+int window_plan(const aej_window_desc *descs, int n, WnPlan &plan, int *bad, const char **why);
+void window_blob(const WnPlan &plan, const unsigned char *src, unsigned char *dst, std::vector<WnEntry> &blob);
+hipError_t launch_window(hipStream_t st, const WnPlan &plan, unsigned char *blob_dev, const WnEntry *blob_host);
+
+}  // namespace aej
+
 // png.hip: the scanline un-filter of PNG files and their expansion to the output layout (aej_png_unfilter_batch), one workgroup per file
 namespace aej {
 

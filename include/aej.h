@@ -1166,6 +1166,52 @@ AEJ_API uint64_t aej_filter_workspace_bytes(aej_ctx *ctx, const aej_filter_desc 
 AEJ_API int aej_filter_batch(aej_ctx *ctx, const aej_filter_desc *descs_host, int n, int path, const uint8_t *src, uint64_t src_bytes,
                              uint8_t *dst, uint64_t dst_bytes, void *workspace, uint64_t workspace_bytes);
 
+/* ---- Pillow's Kernel, rank and mode filters for packed 8-bit images of 1 to 4 channels (filter_many, csrc/window.hip) ----------------
+ * Image.filter with ImageFilter.Kernel (and the ten built-ins, which are Kernels), RankFilter / MedianFilter / MinFilter / MaxFilter
+ * and ModeFilter, bit for bit, for many images of different sizes, channel counts and filters in one call.  An image is uint8
+ * [h][w][channels], packed; channels are filtered independently.  Three families, each with its own border rule:
+ *   AEJ_WINDOW_KERNEL, size k = 3 or 5, r = k / 2: all in float32, every operation rounded (no fused multiply-add, no re-association):
+ *     q[i] = kernel[i] / scale;  ss0 = offset + 0.5f -- both once, on the host, in the library;
+ *     for r <= x < w - r and r <= y < h - r:  ss = ss0;  for j = 0 .. k - 1:
+ *       ss = ss + (((q[j k] p[y + r - j][x - r] + q[j k + 1] p[y + r - j][x - r + 1]) + ...) + q[j k + k - 1] p[y + r - j][x + r])
+ *     -- kernel row 0 meets the image row BELOW the sample (a vertical flip, no horizontal one), the products of a row are added left
+ *     to right and the row's sum is added to ss --;  out = 0 if ss <= 0, 255 if ss >= 255, else ss truncated.
+ *     Samples within r of an edge are copies of the source; an image with w < k or h < k is a copy.
+ *   AEJ_WINDOW_RANK, size odd, 0 <= rank < size^2: out = the rank-th smallest (from 0) of the size x size window centred on the sample,
+ *     window positions clamped to the image (edge replication); every sample is computed.  Min is rank 0, Max rank size^2 - 1, Median
+ *     rank size^2 / 2.
+ *   AEJ_WINDOW_MODE, r = size / 2 (an even size acts as size + 1): over the window [y - r, y + r] x [x - r, x + r] clipped to the image
+ *     (positions outside do not vote) the most frequent value, the smallest one on a tie; out = that value if it occurs MORE THAN
+ *     TWICE, else the sample itself.
+ *
+ * aej_window_geometry_host: HOST only: out[0..4] = the tile width and height in pixels and the largest halo (r) of a Kernel, a rank
+ *   and a mode filter.
+ * aej_window_batch: n images.  src / dst: device bytes; image i is read at src + src_offset and written at dst + dst_offset, exactly
+ *   width * height * channels bytes and no other byte of dst; src and dst must not overlap.  One launch per kind (and Kernel size) and
+ *   channel count present, one read and one write of the image: a workgroup stages a tile and its halo in LDS.  One upload of the
+ *   entries, then the call waits for it; nothing is copied back.  Every descriptor is checked before any device work: AEJ_ERR_ARG
+ *   naming the image for a size below 1 or above 65535, a channel count outside 1 .. 4, an unknown kind, a Kernel size other than 3
+ *   or 5, a kernel value, scale, offset or quotient that is not finite, a scale of 0, a rank size that is even or below 1, a rank
+ *   outside [0, size^2), a mode size below 1, an image outside src_bytes / dst_bytes; AEJ_ERR_UNSUPPORTED naming it for a rank size
+ *   above 15, a mode size above 7 and a |kernel[i] / scale| or |offset| above 2^100 (below that no partial sum overflows float32, so
+ *   no NaN reaches the clip).  Workspace: aej_window_workspace_bytes with the same descriptors (0 for ones the call refuses): the
+ *   entries only. */
+enum { AEJ_WINDOW_KERNEL = 0, AEJ_WINDOW_RANK = 1, AEJ_WINDOW_MODE = 2 };
+typedef struct aej_window_desc {
+    int64_t src_offset, dst_offset;
+    int32_t width, height, channels;
+    int32_t kind;                  /* AEJ_WINDOW_* */
+    int32_t size;                  /* AEJ_WINDOW_KERNEL: 3 or 5; _RANK: odd, 1 .. 15; _MODE: 1 .. 7 */
+    int32_t rank;                  /* read only for AEJ_WINDOW_RANK */
+    float scale, offset;           /* read only for AEJ_WINDOW_KERNEL, as given */
+    float kernel[25];              /* the first size * size values, row by row, as given */
+    int32_t reserved;
+} aej_window_desc;
+AEJ_API int aej_window_geometry_host(int32_t *out);
+AEJ_API uint64_t aej_window_workspace_bytes(aej_ctx *ctx, const aej_window_desc *descs_host, int n);
+AEJ_API int aej_window_batch(aej_ctx *ctx, const aej_window_desc *descs_host, int n, const uint8_t *src, uint64_t src_bytes,
+                             uint8_t *dst, uint64_t dst_bytes, void *workspace, uint64_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif
