@@ -23,6 +23,7 @@ from .edge_detection import EdgeDetection  # noqa: E402
 from .evaluation_metrics import EvaluationMetrics  # noqa: E402
 from .filters import (BLUR, CONTOUR, DETAIL, EDGE_ENHANCE, EDGE_ENHANCE_MORE, EMBOSS, FIND_EDGES, SHARPEN, SMOOTH, SMOOTH_MORE, BoxBlur, GaussianBlur, Kernel,  # noqa: E402
                       MaxFilter, MedianFilter, MinFilter, ModeFilter, RankFilter, UnsharpMask, filter_many)
+from .geometry import rotate_many, transform_many, transform_plan, transpose_many  # noqa: E402
 from .image import Image  # noqa: E402
 from .jpeg import EncodedBatch, Jpeg  # noqa: E402
 from .lpips import LpipsWeights  # noqa: E402
@@ -43,4 +44,5 @@ __all__ = ["Jpeg", "JpegCompressionSettings", "EncodedBatch", "Image", "Evaluati
            "encode_groups", "transform_prefix", "transform_crop_box", "decode_box_window", "decode_box_stats", "resized_crop_plan",
            "standard_jpeg_resized_crop_many", "png_decode_many", "png_parse_header", "png_encode_many",
            "BoxBlur", "GaussianBlur", "UnsharpMask", "filter_many", "Kernel", "RankFilter", "MedianFilter", "MinFilter", "MaxFilter", "ModeFilter",
-           "BLUR", "CONTOUR", "DETAIL", "EDGE_ENHANCE", "EDGE_ENHANCE_MORE", "EMBOSS", "FIND_EDGES", "SHARPEN", "SMOOTH", "SMOOTH_MORE"]
+           "BLUR", "CONTOUR", "DETAIL", "EDGE_ENHANCE", "EDGE_ENHANCE_MORE", "EMBOSS", "FIND_EDGES", "SHARPEN", "SMOOTH", "SMOOTH_MORE",
+           "transform_many", "rotate_many", "transpose_many", "transform_plan"]

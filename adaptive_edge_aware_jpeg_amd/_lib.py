@@ -206,6 +206,19 @@ class WindowDesc(ctypes.Structure):
                 ("scale", ctypes.c_float), ("offset", ctypes.c_float), ("kernel", ctypes.c_float * 25), ("reserved", ctypes.c_int32)]
 
 
+class WarpDesc(ctypes.Structure):
+    """aej_warp_desc (include/aej.h): one image of aej_warp_batch"""
+    _fields_ = [("src_offset", ctypes.c_int64), ("dst_offset", ctypes.c_int64), ("src_w", ctypes.c_int32), ("src_h", ctypes.c_int32),
+                ("dst_w", ctypes.c_int32), ("dst_h", ctypes.c_int32), ("channels", ctypes.c_int32), ("path", ctypes.c_int32),
+                ("method", ctypes.c_int32), ("filter", ctypes.c_int32), ("coef", ctypes.c_double * 8), ("fill", ctypes.c_uint8 * 4),
+                ("premultiply", ctypes.c_int32), ("reserved", ctypes.c_int32 * 2)]
+
+
+class WarpPlan(ctypes.Structure):
+    """aej_warp_plan (include/aej.h): what aej_warp_plan_host makes of one descriptor"""
+    _fields_ = [("path", ctypes.c_int32), ("premultiply", ctypes.c_int32), ("fixed", ctypes.c_int64 * 6)]
+
+
 class PngDesc(ctypes.Structure):
     """aej_png_desc (include/aej.h): what aej_png_parse_host reads from a file's chunks"""
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("bit_depth", ctypes.c_int32), ("colour_type", ctypes.c_int32),
@@ -387,6 +400,10 @@ SIGNATURES = {
     "aej_window_geometry_host": (_I, [_P]),
     "aej_window_workspace_bytes": (_U64, [_P, _P, _I]),
     "aej_window_batch": (_I, [_P, _P, _I, _P, _U64, _P, _U64, _P, _U64]),
+    "aej_warp_geometry_host": (_I, [_P]),
+    "aej_warp_plan_host": (_I, [_P, _P, _P, _I64]),
+    "aej_warp_workspace_bytes": (_U64, [_P, _P, _I]),
+    "aej_warp_batch": (_I, [_P, _P, _I, _P, _U64, _P, _U64, _P, _U64]),
     "aej_test_jpegprog_coefs": (_I, [_P, _P, _P, _I, _P, _U64, _P, _I, _P, _U64, _P, _P, _U64]),             # include/aej_testing.h (tests only)
     "aej_test_jpegprog_coefs_host": (_I, [_P, _P, _P, _U64, _I, _P, _U64]),                                 # include/aej_testing.h (tests only)
     "aej_test_jpeg_adobe_pixels_host": (_I, [_P, _I64, _I, _I, _P]),                                        # include/aej_testing.h (tests only)

@@ -680,6 +680,41 @@ hipError_t launch_window(hipStream_t st, const WnPlan &plan, unsigned char *blob
 
 }  // namespace aej
 
+// warp.hip: Pillow's Image.transform and Image.transpose on packed 8-bit images of 1 to 4 channels (aej_warp_*)
+namespace aej {
+constexpr int kWpThreads = 256;
+constexpr int kWpTileW = 32, kWpTileH = 8;       // k_warp: output pixels of a workgroup, one per lane
+constexpr int kWpFlipBytes = 1024, kWpFlipRows = 4;      // k_flip: bytes of an output row (4 per lane) and rows of a workgroup
+constexpr int kWpSwapTile = 32;                  // k_transpose: a square tile of output pixels, staged in LDS
+constexpr int kWpMaxSide = 32767;
+struct WpEntry {                       // one image of one launch (device pointers set by warp_blob)
+    const unsigned char *in;
+    unsigned char *out;
+    const int *tab;                    // AEJ_WARP_TABLES: xtab[dw], ytab[dh]
+    long long tile_base;               // the first workgroup of this image in its launch
+    long long fx[6];                   // AEJ_WARP_FIXED: A0 .. A5
+    double a[8];
+    int sw, sh, dw, dh;                // pixels
+    int method;                        // AEJ_WARP_TRANSPOSE: Pillow's method
+    int premul;
+    unsigned char fill[4];
+    int tab_at;                        // host: its tables in WpPlan::tables (ints), -1: none
+};
+struct WpLaunch { int kernel, ch, filter, path, first, count; long long tiles; };      // kernel: 0 k_warp, 1 k_flip, 2 k_transpose
+struct WpPlan {
+    std::vector<WpEntry> entries;      // launch by launch; in / out / tab hold nothing yet
+    std::vector<int> image;            // the image of each entry
+    std::vector<WpLaunch> launches;
+    std::vector<int> tables;           // every AEJ_WARP_TABLES image's two tables
+    std::vector<long long> src_offset, dst_offset, src_bytes, dst_bytes;      // per image
+};
+int warp_resolve(const aej_warp_desc &d, aej_warp_plan &p, std::vector<int> *tables, const char **why);      // aej_warp_plan_host
+int warp_plan(const aej_warp_desc *descs, int n, WpPlan &plan, int *bad, const char **why);
+void warp_blob(const WpPlan &plan, const unsigned char *src, unsigned char *dst, const int *tables_dev, std::vector<WpEntry> &blob);
+hipError_t launch_warp(hipStream_t st, const WpPlan &plan, unsigned char *blob_dev, const WpEntry *blob_host, int *tables_dev);
+
+}  // namespace aej
+
 // png.hip: the scanline un-filter of PNG files and their expansion to the output layout (aej_png_unfilter_batch), one workgroup per file
 namespace aej {
 

@@ -1212,6 +1212,78 @@ AEJ_API uint64_t aej_window_workspace_bytes(aej_ctx *ctx, const aej_window_desc 
 AEJ_API int aej_window_batch(aej_ctx *ctx, const aej_window_desc *descs_host, int n, const uint8_t *src, uint64_t src_bytes,
                              uint8_t *dst, uint64_t dst_bytes, void *workspace, uint64_t workspace_bytes);
 
+/* ---- Pillow's Image.transform, rotate and transpose for packed 8-bit images of 1 to 4 channels (geometry.py, csrc/warp.hip) ---------
+ * Image.transform with AFFINE, PERSPECTIVE and QUAD under NEAREST, BILINEAR and BICUBIC, and Image.transpose with its seven methods,
+ * bit for bit, for many images of different sizes, channel counts, paths and filters in one call.  An image is uint8
+ * [h][w][channels], packed.  EXTENT and Image.rotate are AFFINE by the time they get here (geometry.py restates Image.py).
+ *
+ * All arithmetic is IEEE float64, every operation rounded, nothing fused or re-associated.  For output pixel (x, y), xin = x + 0.5,
+ * yin = y + 0.5, coef = a:
+ *   AEJ_WARP_AFFINE       xx = (a0 xin + a1 yin) + a2;  yy = (a3 xin + a4 yin) + a5
+ *   AEJ_WARP_PERSPECTIVE  the same numerators, each divided by (a6 xin + a7 yin) + 1
+ *   AEJ_WARP_QUAD         xx = ((a0 + a1 xin) + a2 yin) + (a3 xin) yin;  yy = ((a4 + a5 xin) + a6 yin) + (a7 xin) yin
+ * AEJ_WARP_NEAREST under PERSPECTIVE and QUAD: the source pixel (trunc xx, trunc yy) if 0 <= xx < W and 0 <= yy < H, else outside.
+ * AEJ_WARP_NEAREST under AFFINE never evaluates the above; the library resolves the image to one of two integer paths, as Pillow does:
+ *   AEJ_WARP_TABLES (a1 == 0 and a3 == 0): xo = a2 + a0 0.5; for x = 0 .. w - 1 in turn: xtab[x] = xo < 0 ? -1 : trunc xo; xo += a0 --
+ *     a running sum, built on the host -- and ytab likewise from a5 and a4; the source pixel is (xtab[x], ytab[y]) if in range.
+ *   AEJ_WARP_FIXED (else), 16.16 fixed point with FIX(v) = floor(v 65536 + 0.5):  A0 = FIX(a0), A1 = FIX(a1), A3 = FIX(a3), A4 = FIX(a4),
+ *     A2 = FIX((a2 + a0 0.5) + a1 0.5), A5 = FIX((a5 + a3 0.5) + a4 0.5);  xi = (A2 + x A0 + y A1) >> 16, yi = (A5 + x A3 + y A4) >> 16
+ *     in int64; the source pixel is (xi, yi) if in range.  Pillow takes this path only while |x a0 + y a1 + a2| < 32768 and
+ *     |x a3 + y a4 + a5| < 32768 at (0, 0), (w, 0), (0, h), (w, h); beyond that (and for a constant outside int32) the image is
+ *     refused with AEJ_ERR_UNSUPPORTED: Pillow's float64 running-sum fallback is not built.  With sides up to 32767 the guard keeps
+ *     Pillow's int32 sums and these int64 sums on the same side of every range test.
+ * AEJ_WARP_BILINEAR: outside unless 0 <= xx < W and 0 <= yy < H.  xx -= 0.5, yy -= 0.5, x = floor xx, y = floor yy, dx = xx - x,
+ *   dy = yy - y; columns x, x + 1 clamped to the image, row y clamped:  v1 = p[x0] + (p[x1] - p[x0]) dx on row y; v2 the same on row
+ *   y + 1 if that row exists, else v2 = v1;  v = v1 + (v2 - v1) dy, truncated.
+ * AEJ_WARP_BICUBIC: the same test, x, y, dx, dy; x -= 1, y -= 1; columns x .. x + 3 clamped; cub(v1, v2, v3, v4, d) = p1 + d (p2 + d (p3 +
+ *   d p4)) with p1 = v2, p2 = -v1 + v3, p3 = ((2 (v1 - v2)) + v3) - v4, p4 = ((-v1 + v2) - v3) + v4.  Row y clamped; each of rows y + 1,
+ *   y + 2, y + 3 is evaluated if it exists and else repeats the value of the row before it; cub over the four with dy; 0 if v <= 0,
+ *   255 if v >= 255, else truncated.
+ * A coordinate that is NaN (undefined in Pillow) makes the pixel an outside one.  Outside pixels take `fill`.
+ * premultiply (read for 2 and 4 channels under BILINEAR and BICUBIC only; the last channel is alpha): a sample c becomes
+ *   ((t >> 8) + t) >> 8 with t = c alpha + 128 as it is loaded, and the result (the fill as given included) is un-premultiplied as it
+ *   is stored: unchanged for alpha 0 and 255, else min(255, 255 c / alpha) in integers.
+ * AEJ_WARP_TRANSPOSE: `method` is Pillow's Image.Transpose value (0 FLIP_LEFT_RIGHT, 1 FLIP_TOP_BOTTOM, 2 ROTATE_90, 3 ROTATE_180,
+ *   4 ROTATE_270, 5 TRANSPOSE, 6 TRANSVERSE); dst_w x dst_h must be the source's size for 0, 1, 3 and its transpose for the others.
+ *
+ * aej_warp_geometry_host: HOST only: out[0..5] = the warp kernel's tile width and height in pixels, the mirrored copy's tile in bytes
+ *   of a row and rows, the transposing kernel's tile width and height in pixels.
+ * aej_warp_plan_host: HOST only, no device and no context: what the library makes of ONE descriptor (offsets not read):
+ *   out->path the resolved path, out->premultiply whether alpha is premultiplied, out->fixed A0 .. A5 for AEJ_WARP_FIXED; for
+ *   AEJ_WARP_TABLES tables[0 .. dst_w) = xtab and tables[dst_w .. dst_w + dst_h) = ytab (tables_len >= dst_w + dst_h, else
+ *   AEJ_ERR_CAPACITY; tables may be NULL for the other paths).  Returns the code aej_warp_batch would refuse the descriptor with.
+ * aej_warp_batch: n images.  src / dst: device bytes; image i is read at src + src_offset (src_w src_h channels bytes) and written at
+ *   dst + dst_offset, exactly dst_w dst_h channels bytes and no other byte of dst; no source image may overlap dst.  One launch per
+ *   (channels, filter, path) present; one thread per output pixel, a workgroup owns a 32 x 8 output tile; one upload of the entries
+ *   and tables, then the call waits for it; nothing is copied back.  Every descriptor is checked before any device work: AEJ_ERR_ARG
+ *   naming the image for a size below 1 or above 32767, a channel count outside 1 .. 4, a path that is not one of TRANSPOSE, AFFINE,
+ *   PERSPECTIVE, QUAD (TABLES and FIXED are what the library resolves AFFINE to, not inputs), an unknown filter or transpose method,
+ *   a coefficient that is not finite, a transposed size that does not fit, an image outside src_bytes / dst_bytes;
+ *   AEJ_ERR_UNSUPPORTED naming it for an AFFINE under NEAREST beyond the fixed-point guard.  Workspace: aej_warp_workspace_bytes with
+ *   the same descriptors (0 for ones the call refuses): the entries and the tables. */
+enum { AEJ_WARP_TRANSPOSE = 0, AEJ_WARP_TABLES = 1, AEJ_WARP_FIXED = 2, AEJ_WARP_AFFINE = 3, AEJ_WARP_PERSPECTIVE = 4, AEJ_WARP_QUAD = 5 };
+enum { AEJ_WARP_NEAREST = 0, AEJ_WARP_BILINEAR = 2, AEJ_WARP_BICUBIC = 3 };      /* Pillow's Image.Resampling values */
+typedef struct aej_warp_desc {
+    int64_t src_offset, dst_offset;
+    int32_t src_w, src_h, dst_w, dst_h, channels;
+    int32_t path;                  /* AEJ_WARP_TRANSPOSE, _AFFINE, _PERSPECTIVE or _QUAD */
+    int32_t method;                /* AEJ_WARP_TRANSPOSE: Pillow's Image.Transpose value */
+    int32_t filter;                /* AEJ_WARP_NEAREST, _BILINEAR, _BICUBIC (not read for AEJ_WARP_TRANSPOSE) */
+    double coef[8];                /* AFFINE: 6, PERSPECTIVE: 8, QUAD: the 8 of its bilinear form */
+    uint8_t fill[4];               /* the outside pixel, one byte per channel */
+    int32_t premultiply;           /* 0 or 1 */
+    int32_t reserved[2];
+} aej_warp_desc;
+typedef struct aej_warp_plan {
+    int32_t path, premultiply;
+    int64_t fixed[6];              /* A0 .. A5 */
+} aej_warp_plan;
+AEJ_API int aej_warp_geometry_host(int32_t *out);
+AEJ_API int aej_warp_plan_host(const aej_warp_desc *desc, aej_warp_plan *out, int32_t *tables, int64_t tables_len);
+AEJ_API uint64_t aej_warp_workspace_bytes(aej_ctx *ctx, const aej_warp_desc *descs_host, int n);
+AEJ_API int aej_warp_batch(aej_ctx *ctx, const aej_warp_desc *descs_host, int n, const uint8_t *src, uint64_t src_bytes, uint8_t *dst,
+                           uint64_t dst_bytes, void *workspace, uint64_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif
