@@ -17,6 +17,7 @@
 #include "../../include/aej_testing.h"
 #include "aej_common.h"
 #include "aej_launch.h"
+#include "aej_sched.h"
 
 struct aej_pending;
 constexpr int kFlagWords = 16;       // [0] quadtree overflow flag, [1] entries that went through the hysteresis work queue (diagnostic)
@@ -62,6 +63,12 @@ struct aej_ctx {
     static constexpr int kMaxSub = 8;
     int dct_crowded = 0;               // this call runs as sub-batches or beside other calls: DCT kernels that share CUs (aej_launch.h DctArgs::crowded)
     hipStream_t sub_stream[kMaxSub] = {};
+    // stream priorities (aej_sched.h): with fewer than 8 hardware queues the part streams are created with priorities, so that the
+    // runtime serves them from one queue pool per level instead of the one pool the caller's streams have filled already
+    int stream_priorities = 1;         // aej_set_option "stream_priorities": 0 never, 1 automatic (hw_queues < 8), 2 always (A / B)
+    int stream_priority_pattern = aej::kDefaultPriorityPattern;      // aej_set_option "stream_priority_pattern": the levels dealt (aej_sched.h)
+    int sub_stream_key = 0;            // what the existing part streams were created under: 0 no priorities, 1 + pattern otherwise
+    int n_priority_streams = 0;        // aej_get_option "priority_streams": part streams this context holds that were created with a priority
     hipEvent_t sub_color_done[kMaxSub] = {}, sub_in = nullptr;
     int *sub_flag[kMaxSub] = {};       // pinned read-back words per sub-batch (layout of h_flag)
     long long n_split_calls = 0;

@@ -350,6 +350,9 @@ extern "C" int64_t aej_get_split_calls(aej_ctx *ctx) { return ctx ? (int64_t)ctx
 extern "C" int aej_set_hw_queues(aej_ctx *ctx, int n)
 {
     if (!ctx || n < 1) return AEJ_ERR_ARG;
+    if (aej::priorities_refused(ctx->stream_priorities, ctx->stream_priority_pattern, n))
+        return fail(ctx, AEJ_ERR_ARG, "aej_set_hw_queues: %d queues on each of %d priority levels (stream_priorities = 2) are more than the %d a process may hold",
+                    n, aej::priority_levels(ctx->stream_priority_pattern), aej::kMaxProcessQueues);
     ctx->hw_queues = n;
     return 0;
 }
@@ -371,6 +374,9 @@ const OptionDef kOptions[] = {
     { "qt_chunk_run", &aej::Tuning::qt_chunk_run, nullptr, 0, 16, true },
     { "qt_chunk_launches", nullptr, &aej_ctx::qt_chunk_launches, 0, 0x7fffffff, false },
     { "sub_chain", nullptr, &aej_ctx::sub_chain, -1, 3, false },
+    { "stream_priorities", nullptr, &aej_ctx::stream_priorities, 0, 2, false },
+    { "stream_priority_pattern", nullptr, &aej_ctx::stream_priority_pattern, 0, aej::kPriorityPatterns - 1, false },
+    { "priority_streams", nullptr, &aej_ctx::n_priority_streams, 0, 0, false },
     { "jpegdec_subseq_bits", nullptr, &aej_ctx::jd_subseq_bits, 32, 1 << 20, false },
 };
 const OptionDef *find_option(const char *name)
@@ -388,6 +394,15 @@ extern "C" int aej_set_option(aej_ctx *ctx, const char *name, int64_t value)
     if (!o) return fail(ctx, AEJ_ERR_ARG, "aej_set_option: unknown option '%s'", name ? name : "(null)");
     if (value < o->lo || value > o->hi || (o->field == &aej::Tuning::dct64_kernel && value != 0 && value != 1 && value != 4))
         return fail(ctx, AEJ_ERR_ARG, "aej_set_option: %s = %lld outside its range [%lld, %lld]", name, (long long)value, o->lo, o->hi);
+    if (o->ctx_field == &aej_ctx::n_priority_streams) return fail(ctx, AEJ_ERR_ARG, "aej_set_option: %s is read-only", name);
+    if (o->ctx_field == &aej_ctx::stream_priorities || o->ctx_field == &aej_ctx::stream_priority_pattern) {
+        // "always" is refused where it would take the process past the queues it may hold (aej_sched.h)
+        const int mode = o->ctx_field == &aej_ctx::stream_priorities ? (int)value : ctx->stream_priorities;
+        const int pattern = o->ctx_field == &aej_ctx::stream_priority_pattern ? (int)value : ctx->stream_priority_pattern;
+        if (aej::priorities_refused(mode, pattern, ctx->hw_queues))
+            return fail(ctx, AEJ_ERR_ARG, "aej_set_option: %s = %lld: %d queues on each of %d priority levels are more than the %d a process may hold", name,
+                        (long long)value, ctx->hw_queues, aej::priority_levels(pattern), aej::kMaxProcessQueues);
+    }
     if (o->field) ctx->tune.*(o->field) = (int)value;
     else ctx->*(o->ctx_field) = (int)value;
     if (o->drops_graphs) drop_graphs(ctx);      // a captured graph holds the launches the old value chose

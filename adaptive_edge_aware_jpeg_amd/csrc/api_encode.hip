@@ -39,6 +39,8 @@ static void collect_marks(aej_ctx *ctx)
 static std::mutex g_chain_mutex;
 static hipEvent_t g_last_color_done[kMaxDevices] = {};      // per device; owned by the context that recorded it
 static int g_calls_in_flight[kMaxDevices] = {};             // per device: calls between aej_encode_batch_begin and _end (guarded by g_chain_mutex)
+static unsigned long long g_priority_streams_dealt = 0;     // part streams the process has created with a priority (guarded by g_chain_mutex): the
+                                                            // levels are dealt in creation order, so that parts which run together spread over them
 
 void drop_graphs(aej_ctx *ctx)
 {
@@ -459,7 +461,10 @@ static int sub_batches(const aej_ctx *ctx, const Geom &g, int hw_queues, bool as
             n = (px >= (384LL << 20) && g.B >= 16) ? 4 : (px >= (64LL << 20) && g.B >= 8) ? 2 : 1;
         } else {
             // HIP's default of 4 hardware queues: streams start to share queues (two streams on one queue run one after the other), so
-            // two sub-batches, and only for a call that has the device to itself (with 4 queues: 4 sub-batches 8.4 ms, 2: 8.1 ms)
+            // two sub-batches, and only for a call that has the device to itself (with 4 queues: 4 sub-batches 8.4 ms, 2: 8.1 ms).
+            // Stream priorities (ensure_sub_streams) give those two streams queues of their own; the count stays at two, because a
+            // context that had made four would keep two idle streams on the queues that the parts of other contexts then have to
+            // share (profiles/stream_priorities_ab.txt: 5.96 against 5.62 ms per pipelined step).
             bool alone;
             { std::lock_guard<std::mutex> lock(g_chain_mutex); alone = g_calls_in_flight[ctx->device] == 0; }
             n = (alone && px >= (64LL << 20) && g.B >= 8) ? 2 : 1;
@@ -542,6 +547,47 @@ static int enqueue_part(aej_ctx *ctx, EncodePart &p, const QtGeom &q, const void
     return enqueue_readback(ctx, p.w);      // one read-back for the whole part
 }
 
+// (the streams are idle: no call of the context is in flight; aej_destroy frees whatever is left)
+static void destroy_sub_streams(aej_ctx *ctx)
+{
+    for (int i = 0; i < aej_ctx::kMaxSub; i++)
+        if (ctx->sub_stream[i]) { (void)hipStreamDestroy(ctx->sub_stream[i]); ctx->sub_stream[i] = nullptr; }
+    ctx->n_priority_streams = 0;
+}
+
+// The part streams of a call cut into nsub.  Those that are missing are all created here, in one go: streams that run together are
+// created together (EXPERIMENTS.md R5-8, R5-9).  With fewer than 8 hardware queues (aej_sched.h priorities_in_use) they are created with
+// priorities, dealt process-wide in creation order, and the runtime serves each level from a queue pool of its own; with 8 or more
+// they are created as they always were.  Streams made under another setting of the option are replaced (they are idle: no call of
+// this context is in flight).
+static int ensure_sub_streams(aej_ctx *ctx, int nsub)
+{
+    const bool prio = priorities_in_use(ctx->stream_priorities, ctx->hw_queues);
+    const int key = prio ? 1 + ctx->stream_priority_pattern : 0;
+    if (key != ctx->sub_stream_key) destroy_sub_streams(ctx);
+    ctx->sub_stream_key = key;
+    int value_of[3] = { 0, 0, 0 };      // PriorityLevel -> the runtime's number (normal is 0, a smaller number is a higher priority)
+    if (prio) {
+        int least = 0, greatest = 0;
+        AEJ_HIP_CHECK(hipDeviceGetStreamPriorityRange(&least, &greatest));
+        value_of[kPrioHigh] = greatest;
+        value_of[kPrioLow] = least;
+    }
+    std::lock_guard<std::mutex> lock(g_chain_mutex);
+    for (int i = 0; i < nsub; i++) {
+        if (ctx->sub_stream[i]) continue;
+        if (prio) {
+            const int level = priority_level_of(ctx->stream_priority_pattern, g_priority_streams_dealt);
+            AEJ_HIP_CHECK(hipStreamCreateWithPriority(&ctx->sub_stream[i], hipStreamNonBlocking, value_of[level]));
+            g_priority_streams_dealt++;
+            ctx->n_priority_streams++;
+        } else {
+            AEJ_HIP_CHECK(hipStreamCreateWithFlags(&ctx->sub_stream[i], hipStreamNonBlocking));
+        }
+    }
+    return 0;
+}
+
 static int encode_begin_impl(aej_ctx *ctx, const void *rgb, bool in_u8, int batch, int H, int W, int32_t *coeffs, int32_t *leaves,
                              uint8_t *states, int64_t *counts, float *dct_f32, void *workspace, uint64_t workspace_bytes, bool &started)
 {
@@ -605,12 +651,10 @@ static int encode_begin_impl(aej_ctx *ctx, const void *rgb, bool in_u8, int batc
     if (slice * (unsigned long long)nsub > workspace_bytes)
         return fail(ctx, AEJ_ERR_CAPACITY, "workspace too small for %d sub-batches: need %llu bytes, got %llu", nsub, slice * (unsigned long long)nsub,
                     (unsigned long long)workspace_bytes);
+    AEJ_TRY(ensure_sub_streams(ctx, nsub));
     for (int i = 0; i < nsub; i++) {
         if (!ctx->sub_color_done[i]) AEJ_HIP_CHECK(hipEventCreateWithFlags(&ctx->sub_color_done[i], hipEventDisableTiming));
-        if (!ctx->sub_stream[i]) {
-            AEJ_HIP_CHECK(hipStreamCreateWithFlags(&ctx->sub_stream[i], hipStreamNonBlocking));
-            AEJ_HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&ctx->sub_flag[i]), kFlagWords * sizeof(int), hipHostMallocDefault));
-        }
+        if (!ctx->sub_flag[i]) AEJ_HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&ctx->sub_flag[i]), kFlagWords * sizeof(int), hipHostMallocDefault));
     }
     if (!ctx->sub_in) AEJ_HIP_CHECK(hipEventCreateWithFlags(&ctx->sub_in, hipEventDisableTiming));
     AEJ_HIP_CHECK(hipEventRecord(ctx->sub_in, user));          // inputs produced on the caller's stream are complete before any sub-batch reads them
@@ -907,7 +951,7 @@ extern "C" int aej_get_schedule_host(aej_ctx *ctx, int batch, int H, int W, int3
     const int n = sub_batches(ctx, g, ctx->hw_queues), n_wide = sub_batches(ctx, g, 16);
     out_host[0] = ctx->hw_queues;
     out_host[1] = n;
-    out_host[2] = (ctx->hw_queues < 8 && n_wide > n) ? 1 : 0;
-    out_host[3] = 0;
+    out_host[2] = (ctx->hw_queues < kWideScheduleQueues && n_wide > n) ? 1 : 0;
+    out_host[3] = effective_hw_queues(ctx->stream_priorities, ctx->stream_priority_pattern, ctx->hw_queues);      // queues the part streams spread over
     return 0;
 }

@@ -110,7 +110,10 @@ AEJ_API int aej_set_sub_batches(aej_ctx *ctx, int n);
  * read it -- so the HOST states it: aej_create assumes 4 (the conservative schedule) and the Python package passes what it knows
  * (adaptive_edge_aware_jpeg_amd/_lib.py: the variable's value when the package was imported before the first HIP call, 4 otherwise).
  * aej_get_schedule_host: out_host[4] = { hardware queues assumed, sub-batches the automatic mode would use for (batch, H, W) right now,
- * 1 when fewer than 8 queues force the two-sub-batch schedule for a call the 4-sub-batch one would serve better, reserved }. */
+ * 1 when fewer than 8 queues force the two-sub-batch schedule for a call the 4-sub-batch one would serve better, the queues the
+ * sub-batch streams spread over: the first word times the stream-priority levels in use ("stream_priorities" below), the first word
+ * itself when no stream gets a priority }.  aej_set_hw_queues refuses (AEJ_ERR_ARG) a count that "stream_priorities" = 2 would take
+ * past 32 queues. */
 AEJ_API int aej_set_hw_queues(aej_ctx *ctx, int n);
 AEJ_API int aej_get_schedule_host(aej_ctx *ctx, int batch, int H, int W, int32_t *out_host);
 /* Tuning and A / B options of one context.  The library reads NO environment variable: whatever changes which kernel or launch shape
@@ -133,6 +136,16 @@ AEJ_API int aej_get_schedule_host(aej_ctx *ctx, int batch, int H, int W, int32_t
  *                                              aej_get_option; setting it, usually to 0, restarts the count)
  *   "sub_chain"             -1..3 (-1)         which stage of the previously enqueued part a part's colour stage waits for: 0 none, 1 colour,
  *                                              2 blur, 3 Sobel; -1 = 1
+ *   "stream_priorities"     0 | 1 | 2 (1)      sub-batch streams created with stream priorities: the HIP runtime keeps one pool of hardware
+ *                                              queues per priority level, each up to GPU_MAX_HW_QUEUES, so the sub-batch streams get queues
+ *                                              beside the ones the caller's streams share.  0: never; 1: when the host states fewer than 8
+ *                                              hardware queues (with 8 or more nothing changes); 2: always (A / B runs; refused when queues x
+ *                                              levels would pass the 32 queues a process may hold).  Streams made under another value are
+ *                                              replaced by the next split call.  The caller's stream and the graph stream are never touched.
+ *   "stream_priority_pattern" 0..3 (3)         the levels dealt to those streams, process-wide in creation order: 0 normal / high,
+ *                                              1 normal / low, 2 normal / high / low, 3 high / low (the measured best; a sub-batch at the
+ *                                              normal level beside one at another ran slower than no priorities at all)
+ *   "priority_streams"      counter            sub-batch streams this context holds that were created with a priority (read-only)
  *   "jpegdec_subseq_bits"   32..1048576 (2048) bits per subsequence of aej_jpegdec_batch's self-synchronising Huffman decode */
 AEJ_API int aej_set_option(aej_ctx *ctx, const char *name, int64_t value);
 AEJ_API int aej_get_option(aej_ctx *ctx, const char *name, int64_t *value_host);
