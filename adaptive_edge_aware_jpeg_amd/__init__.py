@@ -8,7 +8,9 @@ pixel-identical to Pillow), ``resize_many`` (``Image.resize``) and ``standard_jp
 both pixel-identical to Pillow too; ``standard_jpeg_encode_many`` encodes images of mixed sizes and qualities in one call and
 ``standard_jpeg_thumbnail_jpeg_many`` goes from JPEG files to their JPEG thumbnails on the device; ``png_decode_many`` decodes PNG files
 on the device, pixel-identical to Pillow, and ``png_encode_many`` writes them there with Pillow's scanline filtering; ``filter_many`` is ``Image.filter`` with Pillow's ``BoxBlur``,
-``GaussianBlur`` and ``UnsharpMask``, its ``Kernel`` (``SHARPEN`` and the other built-ins), rank (``MedianFilter`` ...) and mode filters, pixel-identical as well.  The arithmetic runs in hand-written HIP kernels behind the
+``GaussianBlur`` and ``UnsharpMask``, its ``Kernel`` (``SHARPEN`` and the other built-ins), rank (``MedianFilter`` ...) and mode filters, pixel-identical as well;
+``adjust_many`` is ``ImageEnhance`` (``Brightness``, ``Contrast``, ``Color``, ``Sharpness``) and the point operations of ``ImageOps`` (``AutoContrast``, ``Equalize``,
+``Posterize``, ``Solarize``, ``Invert``, ``Grayscale``) and ``Image.point``, one op or a chain per image, and ``histogram_many`` is ``Image.histogram``.  The arithmetic runs in hand-written HIP kernels behind the
 C ABI of ``libaejpeg_hip.so`` (include/aej.h); there is no CPU fallback.
 """
 from ._lib import _look_at_hw_queues, configure_hw_queues, hw_queues, set_hw_queues
@@ -18,6 +20,8 @@ from ._lib import _look_at_hw_queues, configure_hw_queues, hw_queues, set_hw_que
 # is the explicit opt-in, `hw_queues()` reports what the library schedules for, `set_hw_queues(n)` states it (policy: _lib.py).
 _look_at_hw_queues()
 
+from .adjust import (AutoContrast, Brightness, Color, Colorize, Contrast, Equalize, Grayscale, Hue, Invert, Point, Posterize, Sharpness, Solarize,  # noqa: E402
+                     adjust_many, adjust_plan, histogram_many)
 from .color import apply_normalization, convert, get_color_spaces  # noqa: E402
 from .edge_detection import EdgeDetection  # noqa: E402
 from .evaluation_metrics import EvaluationMetrics  # noqa: E402
@@ -45,4 +49,6 @@ __all__ = ["Jpeg", "JpegCompressionSettings", "EncodedBatch", "Image", "Evaluati
            "standard_jpeg_resized_crop_many", "png_decode_many", "png_parse_header", "png_encode_many",
            "BoxBlur", "GaussianBlur", "UnsharpMask", "filter_many", "Kernel", "RankFilter", "MedianFilter", "MinFilter", "MaxFilter", "ModeFilter",
            "BLUR", "CONTOUR", "DETAIL", "EDGE_ENHANCE", "EDGE_ENHANCE_MORE", "EMBOSS", "FIND_EDGES", "SHARPEN", "SMOOTH", "SMOOTH_MORE",
-           "transform_many", "rotate_many", "transpose_many", "transform_plan"]
+           "transform_many", "rotate_many", "transpose_many", "transform_plan",
+           "adjust_many", "histogram_many", "adjust_plan", "Brightness", "Contrast", "Color", "Sharpness", "AutoContrast", "Equalize", "Posterize",
+           "Solarize", "Invert", "Grayscale", "Point", "Colorize", "Hue"]

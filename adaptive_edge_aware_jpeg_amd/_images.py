@@ -1,4 +1,4 @@
-"""The intake the image-list calls share (``filter_many``, ``resize_many``, ``png_encode_many``, ``standard_jpeg_encode_many``): the
+"""The intake the image-list calls share (``filter_many``, ``adjust_many``, ``resize_many``, ``png_encode_many``, ``standard_jpeg_encode_many``): the
 argument predicates, "one value or one per image", and the staging of a list of uint8 images of mixed sizes, part on the host and part
 on the device, into device memory with one upload.  Imports without torch and without a device."""
 import math

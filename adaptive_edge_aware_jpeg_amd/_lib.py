@@ -219,6 +219,24 @@ class WarpPlan(ctypes.Structure):
     _fields_ = [("path", ctypes.c_int32), ("premultiply", ctypes.c_int32), ("fixed", ctypes.c_int64 * 6)]
 
 
+class AdjustOp(ctypes.Structure):
+    """aej_adjust_op (include/aej.h): one op of a chain"""
+    _fields_ = [("kind", ctypes.c_int32), ("table", ctypes.c_int32), ("factor", ctypes.c_float), ("preserve_tone", ctypes.c_int32),
+                ("cutoff", ctypes.c_double * 2), ("ignore", ctypes.c_uint32 * 8)]
+
+
+class AdjustDesc(ctypes.Structure):
+    """aej_adjust_desc (include/aej.h): one image of aej_adjust_batch and aej_histogram_batch"""
+    _fields_ = [("src_offset", ctypes.c_int64), ("dst_offset", ctypes.c_int64), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("channels", ctypes.c_int32), ("n_ops", ctypes.c_int32), ("ops", AdjustOp * 8)]
+
+
+class AdjustPlan(ctypes.Structure):
+    """aej_adjust_plan (include/aej.h): what aej_adjust_plan_host makes of one descriptor"""
+    _fields_ = [("out_channels", ctypes.c_int32), ("n_segments", ctypes.c_int32), ("n_passes", ctypes.c_int32), ("n_smooths", ctypes.c_int32),
+                ("n_launches", ctypes.c_int32), ("segment_first", ctypes.c_int32 * 8), ("reserved", ctypes.c_int32 * 3)]
+
+
 class PngDesc(ctypes.Structure):
     """aej_png_desc (include/aej.h): what aej_png_parse_host reads from a file's chunks"""
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("bit_depth", ctypes.c_int32), ("colour_type", ctypes.c_int32),
@@ -404,6 +422,11 @@ SIGNATURES = {
     "aej_warp_plan_host": (_I, [_P, _P, _P, _I64]),
     "aej_warp_workspace_bytes": (_U64, [_P, _P, _I]),
     "aej_warp_batch": (_I, [_P, _P, _I, _P, _U64, _P, _U64, _P, _U64]),
+    "aej_adjust_geometry_host": (_I, [_P]),
+    "aej_adjust_plan_host": (_I, [_P, _P]),
+    "aej_adjust_workspace_bytes": (_U64, [_P, _P, _I]),
+    "aej_adjust_batch": (_I, [_P, _P, _I, _P, _I, _P, _U64, _P, _U64, _P, _U64]),
+    "aej_histogram_batch": (_I, [_P, _P, _I, _P, _U64, _P, _U64, _P, _U64]),
     "aej_test_jpegprog_coefs": (_I, [_P, _P, _P, _I, _P, _U64, _P, _I, _P, _U64, _P, _P, _U64]),             # include/aej_testing.h (tests only)
     "aej_test_jpegprog_coefs_host": (_I, [_P, _P, _P, _U64, _I, _P, _U64]),                                 # include/aej_testing.h (tests only)
     "aej_test_jpeg_adobe_pixels_host": (_I, [_P, _I64, _I, _I, _P]),                                        # include/aej_testing.h (tests only)

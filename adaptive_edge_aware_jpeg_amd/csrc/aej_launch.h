@@ -715,6 +715,56 @@ hipError_t launch_warp(hipStream_t st, const WpPlan &plan, unsigned char *blob_d
 
 }  // namespace aej
 
+// adjust.hip: Pillow's ImageEnhance, ImageOps point operations and Image.histogram on packed 8-bit images of 1 to 4 channels (aej_adjust_*)
+namespace aej {
+constexpr int kAdThreads = 256;
+constexpr int kAdChunk = 4096;         // pixels of one image a workgroup takes at a time: in groups of 16 bytes a lane (12 for 3 channels)
+constexpr int kAdMaxGrid = 16384;      // workgroups of a launch; the chunks beyond are reached by striding
+constexpr int kAdMaxSide = 32767;
+constexpr int kAdHistWords = 1024;     // counters of one histogram pass of one image: up to 4 bands x 256
+constexpr int kAdWiden = -1;           // AdLutEntry::kind of aej_histogram_batch's widening
+struct AdStep { int kind, slot; float factor; int pad; };
+struct AdEntry {                       // one image of one histogram or apply launch
+    const unsigned char *in;           // the segment's input, cin bytes a pixel
+    const unsigned char *deg;          // filter(SMOOTH) of `in`: read when step 0 is AEJ_ADJUST_SHARPNESS
+    unsigned char *out;                // apply: what the steps leave, 1 byte a pixel after a GRAYSCALE, else cin
+    unsigned *hist;                    // histogram: `bins` counters of this pass
+    const unsigned char *tables;       // the image's AEJ_ADJUST_MAX_OPS tables, one per op of its chain
+    long long chunk_base;              // the first chunk of this image in its launch
+    long long npix;
+    int n_steps, luma, bins, pad;      // luma: the histogram is of L alone
+    AdStep step[AEJ_ADJUST_MAX_OPS];
+};
+struct AdLutEntry {                    // one image of one table launch (k_adjust_luts)
+    const unsigned *hist;
+    unsigned char *table;              // the op's table; CONTRAST: byte 0 is the mean
+    long long *wide;                   // kAdWiden: the int64 counts
+    long long npix;
+    int kind, bands, copies, pad;      // bands histograms -> bands tables, or one table written `copies` times (preserve_tone)
+    double cutoff[2];
+    unsigned ignore[8];
+};
+struct AdLaunch { int kernel, cin, gray, first, count, round; long long chunks; };      // kernel: 0 k_adjust_hist, 1 k_adjust_luts, 2 k_adjust_apply, 3 SMOOTH round
+struct AdSmooth { WnPlan plan; std::vector<WnEntry> blob; unsigned char *blob_dev; };
+struct AdPlan {
+    std::vector<AdEntry> entries;      // launch by launch, device pointers set (null when only measured)
+    std::vector<AdLutEntry> luts;
+    std::vector<AdLaunch> launches;
+    std::vector<AdSmooth> smooths;
+    std::vector<unsigned char> tables; // per image AEJ_ADJUST_MAX_OPS tables, the AEJ_ADJUST_LUT ones filled
+    std::vector<long long> src_offset, dst_offset, src_bytes, dst_bytes;      // per image (dst in the output's own elements)
+    unsigned char *entries_dev, *luts_dev, *tables_dev;
+    unsigned *hists_dev;
+    long long n_hists;
+    unsigned long long bytes;          // the workspace
+};
+int adjust_resolve(const aej_adjust_desc &d, int n_tables, aej_adjust_plan &p, const char **why);      // aej_adjust_plan_host
+int adjust_plan(const aej_adjust_desc *descs, int n, const unsigned char *tables_host, int n_tables, bool histogram, void *workspace,
+                const unsigned char *src, unsigned char *dst, AdPlan &plan, int *bad, const char **why);
+hipError_t launch_adjust(hipStream_t st, const AdPlan &plan);
+
+}  // namespace aej
+
 // png.hip: the scanline un-filter of PNG files and their expansion to the output layout (aej_png_unfilter_batch), one workgroup per file
 namespace aej {
 

@@ -1297,6 +1297,85 @@ AEJ_API uint64_t aej_warp_workspace_bytes(aej_ctx *ctx, const aej_warp_desc *des
 AEJ_API int aej_warp_batch(aej_ctx *ctx, const aej_warp_desc *descs_host, int n, const uint8_t *src, uint64_t src_bytes, uint8_t *dst,
                            uint64_t dst_bytes, void *workspace, uint64_t workspace_bytes);
 
+/* ---- Pillow's ImageEnhance, ImageOps point operations, Image.point and Image.histogram for packed 8-bit images (adjust.py, csrc/adjust.hip)
+ * A chain of up to 8 ops per image, bit for bit, for many images of different sizes, channel counts and chains in one call.  An image
+ * is uint8 [h][w][channels], packed: 1 L, 2 LA, 3 RGB, 4 RGBA; the last band of 2 and 4 channels is alpha.
+ *
+ * L of a pixel: band 0 for 1 and 2 channels, else (r 19595 + g 38470 + b 7471 + 0x8000) >> 16; alpha is ignored.
+ * The enhancers are Image.blend(degenerate, image, factor), a = factor as float32, all float32, the product and the sum rounded
+ * separately (no fused multiply-add):  t = float(d) + a float(s - d);  for 0 <= a <= 1 out = t truncated, otherwise
+ * out = 0 if t <= 0, 255 if t >= 255, else t truncated.  The alpha band of every degenerate is the image's own, so alpha is unchanged.
+ *   AEJ_ADJUST_BRIGHTNESS  d = 0
+ *   AEJ_ADJUST_CONTRAST    d = int(sum_i(i h[i]) / pixels + 0.5) in float64, h the histogram of L (the sum is an exact integer)
+ *   AEJ_ADJUST_COLOR       d = L in every colour band; an image of 1 or 2 channels is unchanged
+ *   AEJ_ADJUST_SHARPNESS   d = filter(SMOOTH): the AEJ_WINDOW_KERNEL (1 1 1, 1 5 1, 1 1 1) / 13 of every band; samples within 1 of an
+ *                          edge are copies of the image
+ * The table ops map every band b through table[b][v]:
+ *   AEJ_ADJUST_AUTOCONTRAST  ImageOps.autocontrast, loop for loop, per band from that band's histogram, or with preserve_tone one table
+ *     from the histogram of L for all bands: bins with their bit in `ignore` are zeroed; n = the sum of the bins;
+ *     cut = int(n cutoff[0] // 100) (float64 floor division as Python's) is taken off the low end bin by bin, int(n cutoff[1] // 100)
+ *     off the high end; lo and hi = the first and last non-zero bin (255 and 0 if there is none); the identity if hi <= lo, else
+ *     scale = 255.0 / (hi - lo), offset = -lo scale, table[i] = int(i scale + offset) clipped to 0 .. 255, in float64.
+ *   AEJ_ADJUST_EQUALIZE  ImageOps.equalize per band: over the NON-ZERO bins, step = (their sum - the last of them) / 255 in integers;
+ *     the identity with one non-zero bin or step 0; else n = step / 2 and for i = 0 .. 255: table[i] = min(n / step, 255), n += h[i].
+ *   AEJ_ADJUST_LUT  table number `table` of the call's tables_host: 4 bands x 256 bytes (posterize, solarize, invert, Image.point).
+ *   Both histogram ops take 1 and 3 channels only, as Pillow's _lut.
+ * AEJ_ADJUST_GRAYSCALE  convert("L"): one channel, L; the ops after it see a 1-channel image.
+ *
+ * One chain runs as segments.  Every step rounds to uint8 as Pillow's intermediate image would, so a segment is evaluated per pixel in
+ * registers: the source is read once and the result written once.  A CONTRAST, AUTOCONTRAST or EQUALIZE adds one histogram launch,
+ * which re-evaluates the steps of its segment before it, and one table launch; no intermediate image is written for it.  A SHARPNESS
+ * that is not the first op starts a new segment whose input is the previous segment's output in the workspace; every SHARPNESS adds
+ * one SMOOTH launch (window.hip) of its segment's input into the workspace.  launches = 2 passes + smooths + segments.
+ *
+ * aej_adjust_geometry_host: HOST only: out[0..3] = the pixels of a chunk (one workgroup's share of an image in the histogram and apply
+ *   kernels), the threads of a workgroup, the largest grid (beyond it workgroups stride) and the bytes of a table.
+ * aej_adjust_plan_host: HOST only, no device and no context: what the library makes of ONE descriptor (offsets and table numbers not
+ *   read).  Returns the code aej_adjust_batch would refuse the descriptor with.
+ * aej_adjust_batch: n images.  src / dst: device bytes; image i is read at src + src_offset (width height channels bytes) and written
+ *   at dst + dst_offset, exactly width height out_channels bytes and no other byte of dst; no source image may overlap dst.
+ *   tables_host: n_tables tables of 1024 bytes on the HOST (may be NULL when n_tables is 0).  Each launch is one grid over every
+ *   image (of one channel count) that needs it.  The call zeroes its histograms itself, uploads its entries and tables once, runs on
+ *   the context's stream and waits once at the end; nothing is read back in between.  Every descriptor is checked before any device
+ *   work: AEJ_ERR_ARG naming the image for a size below 1 or above 32767, a channel count outside 1 .. 4, n_ops outside 1 .. 8, an
+ *   unknown op, a factor that is not finite, a cutoff that is negative or not finite, a table number outside tables_host, a
+ *   histogram op where the image has 2 or 4 channels, an image outside src_bytes / dst_bytes.  Workspace:
+ *   aej_adjust_workspace_bytes with the same descriptors (0 for ones the call refuses): entries, tables, histograms and the planes.
+ * aej_histogram_batch: Image.histogram() of n images (descriptors with n_ops = 0; dst_offset counts int64 elements): image i gets
+ *   channels x 256 int64 counts at hist + dst_offset, band by band.  The counts are kept as uint32 (32767^2 fits) and widened on
+ *   the device.  Same checks, same workspace query (descriptors with n_ops = 0 size this call). */
+enum { AEJ_ADJUST_BRIGHTNESS = 0, AEJ_ADJUST_CONTRAST = 1, AEJ_ADJUST_COLOR = 2, AEJ_ADJUST_SHARPNESS = 3, AEJ_ADJUST_AUTOCONTRAST = 4,
+       AEJ_ADJUST_EQUALIZE = 5, AEJ_ADJUST_LUT = 6, AEJ_ADJUST_GRAYSCALE = 7 };
+#define AEJ_ADJUST_MAX_OPS 8
+#define AEJ_ADJUST_TABLE_BYTES 1024
+typedef struct aej_adjust_op {
+    int32_t kind;                  /* AEJ_ADJUST_* */
+    int32_t table;                 /* AEJ_ADJUST_LUT: its table in tables_host */
+    float factor;                  /* the enhancers */
+    int32_t preserve_tone;         /* AEJ_ADJUST_AUTOCONTRAST: 0 or 1 */
+    double cutoff[2];              /* AEJ_ADJUST_AUTOCONTRAST: per cent off the low and the high end */
+    uint32_t ignore[8];            /* AEJ_ADJUST_AUTOCONTRAST: bit v of the 256 set: bin v is zeroed */
+} aej_adjust_op;
+typedef struct aej_adjust_desc {
+    int64_t src_offset, dst_offset;
+    int32_t width, height, channels;
+    int32_t n_ops;                 /* 1 .. 8; 0 for aej_histogram_batch */
+    aej_adjust_op ops[AEJ_ADJUST_MAX_OPS];
+} aej_adjust_desc;
+typedef struct aej_adjust_plan {
+    int32_t out_channels, n_segments, n_passes, n_smooths, n_launches;
+    int32_t segment_first[AEJ_ADJUST_MAX_OPS];      /* the first op of each segment */
+    int32_t reserved[3];
+} aej_adjust_plan;
+AEJ_API int aej_adjust_geometry_host(int32_t *out);
+AEJ_API int aej_adjust_plan_host(const aej_adjust_desc *desc, aej_adjust_plan *out);
+AEJ_API uint64_t aej_adjust_workspace_bytes(aej_ctx *ctx, const aej_adjust_desc *descs_host, int n);
+AEJ_API int aej_adjust_batch(aej_ctx *ctx, const aej_adjust_desc *descs_host, int n, const uint8_t *tables_host, int n_tables,
+                             const uint8_t *src, uint64_t src_bytes, uint8_t *dst, uint64_t dst_bytes, void *workspace,
+                             uint64_t workspace_bytes);
+AEJ_API int aej_histogram_batch(aej_ctx *ctx, const aej_adjust_desc *descs_host, int n, const uint8_t *src, uint64_t src_bytes,
+                                int64_t *hist, uint64_t hist_elements, void *workspace, uint64_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif
