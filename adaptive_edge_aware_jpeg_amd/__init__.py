@@ -10,7 +10,9 @@ both pixel-identical to Pillow too; ``standard_jpeg_encode_many`` encodes images
 on the device, pixel-identical to Pillow, and ``png_encode_many`` writes them there with Pillow's scanline filtering; ``filter_many`` is ``Image.filter`` with Pillow's ``BoxBlur``,
 ``GaussianBlur`` and ``UnsharpMask``, its ``Kernel`` (``SHARPEN`` and the other built-ins), rank (``MedianFilter`` ...) and mode filters, pixel-identical as well;
 ``adjust_many`` is ``ImageEnhance`` (``Brightness``, ``Contrast``, ``Color``, ``Sharpness``) and the point operations of ``ImageOps`` (``AutoContrast``, ``Equalize``,
-``Posterize``, ``Solarize``, ``Invert``, ``Grayscale``) and ``Image.point``, one op or a chain per image, and ``histogram_many`` is ``Image.histogram``.  The arithmetic runs in hand-written HIP kernels behind the
+``Posterize``, ``Solarize``, ``Invert``, ``Grayscale``) and ``Image.point``, one op or a chain per image, and ``histogram_many`` is ``Image.histogram``;
+``paste_many``, ``alpha_composite_many``, ``blend_many``, ``composite_many`` and ``chop_many`` are ``Image.paste`` (with every mask Pillow takes), ``Image.alpha_composite``,
+``Image.blend``, ``Image.composite`` and ``ImageChops`` for lists of image pairs.  The arithmetic runs in hand-written HIP kernels behind the
 C ABI of ``libaejpeg_hip.so`` (include/aej.h); there is no CPU fallback.
 """
 from ._lib import _look_at_hw_queues, configure_hw_queues, hw_queues, set_hw_queues
@@ -23,6 +25,7 @@ _look_at_hw_queues()
 from .adjust import (AutoContrast, Brightness, Color, Colorize, Contrast, Equalize, Grayscale, Hue, Invert, Point, Posterize, Sharpness, Solarize,  # noqa: E402
                      adjust_many, adjust_plan, histogram_many)
 from .color import apply_normalization, convert, get_color_spaces  # noqa: E402
+from .compose import ChopAdd, ChopSubtract, alpha_composite_many, blend_many, chop_many, compose_plan, composite_many, paste_many  # noqa: E402
 from .edge_detection import EdgeDetection  # noqa: E402
 from .evaluation_metrics import EvaluationMetrics  # noqa: E402
 from .filters import (BLUR, CONTOUR, DETAIL, EDGE_ENHANCE, EDGE_ENHANCE_MORE, EMBOSS, FIND_EDGES, SHARPEN, SMOOTH, SMOOTH_MORE, BoxBlur, GaussianBlur, Kernel,  # noqa: E402
@@ -51,4 +54,5 @@ __all__ = ["Jpeg", "JpegCompressionSettings", "EncodedBatch", "Image", "Evaluati
            "BLUR", "CONTOUR", "DETAIL", "EDGE_ENHANCE", "EDGE_ENHANCE_MORE", "EMBOSS", "FIND_EDGES", "SHARPEN", "SMOOTH", "SMOOTH_MORE",
            "transform_many", "rotate_many", "transpose_many", "transform_plan",
            "adjust_many", "histogram_many", "adjust_plan", "Brightness", "Contrast", "Color", "Sharpness", "AutoContrast", "Equalize", "Posterize",
-           "Solarize", "Invert", "Grayscale", "Point", "Colorize", "Hue"]
+           "Solarize", "Invert", "Grayscale", "Point", "Colorize", "Hue",
+           "paste_many", "alpha_composite_many", "blend_many", "composite_many", "chop_many", "compose_plan", "ChopAdd", "ChopSubtract"]

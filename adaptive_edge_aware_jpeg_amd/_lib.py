@@ -237,6 +237,22 @@ class AdjustPlan(ctypes.Structure):
                 ("n_launches", ctypes.c_int32), ("segment_first", ctypes.c_int32 * 8), ("reserved", ctypes.c_int32 * 3)]
 
 
+class ComposeDesc(ctypes.Structure):
+    """aej_compose_desc (include/aej.h): one element of aej_compose_batch"""
+    _fields_ = [("base_offset", ctypes.c_int64), ("over_offset", ctypes.c_int64), ("mask_offset", ctypes.c_int64), ("dst_offset", ctypes.c_int64),
+                ("kind", ctypes.c_int32), ("op", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("channels", ctypes.c_int32),
+                ("over_width", ctypes.c_int32), ("over_height", ctypes.c_int32), ("over_channels", ctypes.c_int32),
+                ("mask_width", ctypes.c_int32), ("mask_height", ctypes.c_int32), ("mask_channels", ctypes.c_int32), ("mask_kind", ctypes.c_int32),
+                ("x", ctypes.c_int32), ("y", ctypes.c_int32), ("box", ctypes.c_int32 * 4), ("alpha", ctypes.c_float), ("scale", ctypes.c_float),
+                ("offset", ctypes.c_float), ("colour", ctypes.c_uint8 * 4), ("reserved", ctypes.c_int32 * 2)]
+
+
+class ComposePlan(ctypes.Structure):
+    """aej_compose_plan (include/aej.h): what aej_compose_plan_host makes of one descriptor"""
+    _fields_ = [("out_width", ctypes.c_int32), ("out_height", ctypes.c_int32), ("out_channels", ctypes.c_int32), ("region", ctypes.c_int32 * 4),
+                ("reads_overlay", ctypes.c_int32), ("reads_mask", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
+
+
 class PngDesc(ctypes.Structure):
     """aej_png_desc (include/aej.h): what aej_png_parse_host reads from a file's chunks"""
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("bit_depth", ctypes.c_int32), ("colour_type", ctypes.c_int32),
@@ -427,6 +443,10 @@ SIGNATURES = {
     "aej_adjust_workspace_bytes": (_U64, [_P, _P, _I]),
     "aej_adjust_batch": (_I, [_P, _P, _I, _P, _I, _P, _U64, _P, _U64, _P, _U64]),
     "aej_histogram_batch": (_I, [_P, _P, _I, _P, _U64, _P, _U64, _P, _U64]),
+    "aej_compose_geometry_host": (_I, [_P]),
+    "aej_compose_plan_host": (_I, [_P, _P]),
+    "aej_compose_workspace_bytes": (_U64, [_P, _P, _I]),
+    "aej_compose_batch": (_I, [_P, _P, _I, _P, _U64, _P, _U64, _P, _U64]),
     "aej_test_jpegprog_coefs": (_I, [_P, _P, _P, _I, _P, _U64, _P, _I, _P, _U64, _P, _P, _U64]),             # include/aej_testing.h (tests only)
     "aej_test_jpegprog_coefs_host": (_I, [_P, _P, _P, _U64, _I, _P, _U64]),                                 # include/aej_testing.h (tests only)
     "aej_test_jpeg_adobe_pixels_host": (_I, [_P, _I64, _I, _I, _P]),                                        # include/aej_testing.h (tests only)

@@ -39,14 +39,6 @@ __device__ __forceinline__ const AdEntry &ad_entry(const AdEntry *__restrict__ e
 
 __device__ __forceinline__ int ad_luma(int r, int g, int b) { return (r * 19595 + g * 38470 + b * 7471 + 0x8000) >> 16; }
 
-// Image.blend's sample: the product and the sum are rounded separately
-__device__ __forceinline__ int ad_blend(int d, int s, float a, bool inside)
-{
-    const float t = __fadd_rn((float)d, __fmul_rn(a, (float)(s - d)));
-    if (inside) return (int)t;
-    return t <= 0.f ? 0 : t >= 255.f ? 255 : (int)t;
-}
-
 // kP pixels from pixel q on (q < npix): one vector access when all kP exist, else byte by byte (the missing ones are 0)
 template <int kC, int kP>
 __device__ __forceinline__ void ad_load(const unsigned char *__restrict__ p, long long q, long long npix, int (&px)[kP][kC])

@@ -758,10 +758,53 @@ struct AdPlan {
     long long n_hists;
     unsigned long long bytes;          // the workspace
 };
+// Image.blend's sample (the enhancers of adjust.hip, AEJ_COMPOSE_BLEND of compose.hip): the product and the sum are rounded separately
+__device__ __forceinline__ int ad_blend(int d, int s, float a, bool inside)
+{
+    const float t = __fadd_rn((float)d, __fmul_rn(a, (float)(s - d)));
+    if (inside) return (int)t;
+    return t <= 0.f ? 0 : t >= 255.f ? 255 : (int)t;
+}
 int adjust_resolve(const aej_adjust_desc &d, int n_tables, aej_adjust_plan &p, const char **why);      // aej_adjust_plan_host
 int adjust_plan(const aej_adjust_desc *descs, int n, const unsigned char *tables_host, int n_tables, bool histogram, void *workspace,
                 const unsigned char *src, unsigned char *dst, AdPlan &plan, int *bad, const char **why);
 hipError_t launch_adjust(hipStream_t st, const AdPlan &plan);
+
+}  // namespace aej
+
+// compose.hip: Pillow's paste, alpha_composite, blend, composite and ImageChops on packed 8-bit images of 1 to 4 channels (aej_compose_*)
+namespace aej {
+constexpr int kCpThreads = 256;
+constexpr int kCpChunk = 4096;         // pixels of one output image a workgroup takes at a time, in k_adjust_apply's lane groups
+constexpr int kCpMaxGrid = 16384;      // workgroups of a launch; the chunks beyond are reached by striding
+constexpr int kCpMaxSide = 32767;
+struct CpEntry {                       // one element of one launch
+    const unsigned char *base;         // bw pixels a row, the output's channels a pixel
+    const unsigned char *over;         // ow pixels a row, oc bytes a pixel; null: `colour`
+    const unsigned char *mask;         // ow pixels a row, mc bytes a pixel; null unless mkind is AEJ_COMPOSE_MASK_BIT or _BYTE
+    unsigned char *out;                // W x H pixels
+    long long chunk_base;              // the first chunk of this element in its launch
+    int npix, W, bw, pad;              // npix = W x the output's rows (below 2^30)
+    int ox, oy, ow;                    // the overlay's pixel (0, 0) in the output, its row
+    int rx0, ry0, rx1, ry1;            // the region, clipped: every pixel in it has an overlay (and mask) pixel
+    int kind, op, mkind, oc, mc;
+    float alpha, scale, offset;
+    unsigned char colour[4];
+};
+struct CpLaunch { int channels, first, count; long long chunks; };
+struct CpPlan {
+    std::vector<CpEntry> entries;      // launch by launch, device pointers set (null when only measured)
+    std::vector<CpLaunch> launches;
+    std::vector<long long> dst_offset, dst_bytes;      // per element
+    struct Read { int element; long long offset, bytes; };
+    std::vector<Read> reads;           // every source the call reads
+    unsigned char *entries_dev;
+    unsigned long long bytes;          // the workspace
+};
+int compose_resolve(const aej_compose_desc &d, aej_compose_plan &p, const char **why);      // aej_compose_plan_host
+int compose_plan(const aej_compose_desc *descs, int n, void *workspace, const unsigned char *src, unsigned char *dst, CpPlan &plan, int *bad,
+                 const char **why);
+hipError_t launch_compose(hipStream_t st, const CpPlan &plan);
 
 }  // namespace aej
 

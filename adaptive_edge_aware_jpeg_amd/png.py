@@ -102,7 +102,7 @@ def png_decode_many(files, mode="RGB", inflate: str = "gpu", device: int = 0, wo
     """Decode PNG files (bytes-like, of mixed sizes and kinds) on the GPU -> a list of device uint8 tensors, one per file, in file order.
 
     ``mode`` is one value for all files or one per file.  "RGB": [H, W, 3], equal to ``np.asarray(Image.open(f).convert("RGB"))`` --
-    alpha is dropped (not composited), tRNS is ignored, grey is replicated, palette indices go through PLTE and an index past the
+    alpha is dropped (not composited: ``alpha_composite_many`` over a background does that from mode="auto"), tRNS is ignored, grey is replicated, palette indices go through PLTE and an index past the
     palette's end reads black.  "auto": the layout of Pillow's own mode -- colour type 0 gives [H, W] (bit depth 1 becomes 0 / 255, depth
     2 is multiplied by 85, depth 4 by 17: what Pillow's modes "1" and "L" convert to), colour type 4 [H, W, 2], 2 [H, W, 3], 6 [H, W, 4];
     colour type 3 gives [H, W, 3] through the palette, the one place where "auto" is ``convert("RGB")`` and not Pillow's mode "P".  Any

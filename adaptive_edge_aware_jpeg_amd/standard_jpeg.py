@@ -1156,7 +1156,8 @@ def _cut_geometry(i, frame, name, trim, layout_440, box, drop):
     if not (0 <= box[0] < box[2] <= w and 0 <= box[1] < box[3] <= h):
         raise ValueError(f"file {i}: crop {box} does not lie inside the {w} x {h} image that {name}{' with trim=True' if trim else ''} leaves: "
                          f"0 <= left < right <= {w} and 0 <= upper < lower <= {h} required (boxes are not clamped)")
-    rc = entry(ctypes.addressof((ctypes.c_int32 * 4)(*box)))
+    cut = (ctypes.c_int32 * 4)(*box)                # (held by a name: an unnamed array is freed as soon as addressof returns, before the entry reads it)
+    rc = entry(ctypes.addressof(cut))
     if rc:
         raise ValueError(f"file {i}: the library refuses the crop {box} ({rc})")
     return tuple(out)

@@ -1376,6 +1376,86 @@ AEJ_API int aej_adjust_batch(aej_ctx *ctx, const aej_adjust_desc *descs_host, in
 AEJ_API int aej_histogram_batch(aej_ctx *ctx, const aej_adjust_desc *descs_host, int n, const uint8_t *src, uint64_t src_bytes,
                                 int64_t *hist, uint64_t hist_elements, void *workspace, uint64_t workspace_bytes);
 
+/* ---- Pillow's two-image operations for packed 8-bit images (compose.py, csrc/compose.hip): Image.paste, Image.alpha_composite,
+ * Image.blend, Image.composite and ImageChops, bit for bit, for many elements of different sizes and channel counts in one call.
+ * An element has a BASE (uint8 [h][w][channels], packed: 1 L, 2 LA, 3 RGB, 4 RGBA), an OVERLAY of over_channels channels (0: the
+ * constant `colour`) whose pixel (0, 0) lies at pixel (x, y) of the base -- x and y may be negative --, and a MASK that lies where the
+ * overlay lies.  The output is out_w x out_h x channels: the base's size, except for AEJ_COMPOSE_CHOP, where it is the common top-left
+ * rectangle (the minimum of each side).  The REGION is the intersection of the output, of the overlay's rectangle at (x, y) and of
+ * box[] = left, top, right, bottom in the overlay's own coordinates, moved to (x, y) as well.  Outside the region the output is the
+ * base; inside, with d the base's, s the overlay's and m the mask's sample at the same place, all integer divisions truncating:
+ *
+ * AEJ_COMPOSE_PASTE (Image.paste; Image.composite(im1, im2, mask) is the paste of im1 over im2)  per band.  An overlay with one
+ *   channel more than the base (4 over 3, 2 over 1) loses its last band.  By mask_kind:
+ *   AEJ_COMPOSE_MASK_NONE     out = s
+ *   AEJ_COMPOSE_MASK_BIT      Pillow's mode "1": out = m != 0 ? s : d
+ *   AEJ_COMPOSE_MASK_BYTE     m = the LAST band of the mask's mask_channels (L, or the alpha of LA and RGBA):
+ *                             t = d (255 - m) + s m + 128;  out = ((t >> 8) + t) >> 8  -- ONE division of the sum, not one per product.
+ *                             Pillow's fill: a COLOUR through a 1-channel mask into a base of 2 or 4 channels takes m = 255 in the
+ *                             bands before the last wherever m != 0 and the base's last band is 0; a colour takes no 2-channel mask
+ *   AEJ_COMPOSE_MASK_OVERLAY  the same with m = the last band of the overlay's own pixel (paste(im, at, im)); no mask is read
+ * AEJ_COMPOSE_ALPHA  Image.alpha_composite, 2 or 4 channels on both sides, sa and da the two last bands:  sa == 0: out = d.  Otherwise
+ *   outa = sa 255 + da (255 - sa);  c1 = sa 255 255 128 / outa;  c2 = 255 128 - c1;  div255(t) = ((t >> 8) + t) >> 8;
+ *   colour bands: out = div255(s c1 + d c2 + (0x80 << 7)) >> 7;  last band: out = div255(outa + 0x80).
+ * AEJ_COMPOSE_BLEND  Image.blend(base, overlay, alpha) on every band, the last included: the float32 form of the enhancers above,
+ *   t = float(d) + alpha float(s - d), the product and the sum rounded separately; 0 <= alpha <= 1: t truncated, otherwise clipped
+ *   to 0 .. 255 and then truncated.
+ * AEJ_COMPOSE_CHOP  ImageChops.<op>(base, overlay) on every band, a = d, b = s.  CLIPPED to 0 .. 255:
+ *   AEJ_CHOP_ADD       int(float(a + b) / scale + float(offset)), float32, the quotient and the sum rounded separately, truncated
+ *   AEJ_CHOP_SUBTRACT  the same with a - b
+ *   AEJ_CHOP_MULTIPLY  a b / 255          AEJ_CHOP_SCREEN  255 - (255 - a) (255 - b) / 255
+ *   AEJ_CHOP_LIGHTER   max(a, b)          AEJ_CHOP_DARKER  min(a, b)          AEJ_CHOP_DIFFERENCE  |a - b|
+ *   and WRAPPED to a byte (& 255):
+ *   AEJ_CHOP_ADD_MODULO  a + b            AEJ_CHOP_SUBTRACT_MODULO  a - b
+ *   AEJ_CHOP_HARD_LIGHT  b < 128 ? a b / 127 : 255 - (255 - b) (255 - a) / 127
+ *   AEJ_CHOP_OVERLAY     a < 128 ? a b / 127 : 255 - (255 - a) (255 - b) / 127
+ *   AEJ_CHOP_SOFT_LIGHT  ((255 - a) (a b)) / 65536 + (a (255 - (255 - a) (255 - b) / 255)) / 255
+ *
+ * aej_compose_geometry_host: HOST only: out[0..2] = the pixels of a chunk (one workgroup's share of an output image), the threads of a
+ *   workgroup, the largest grid (beyond it workgroups stride).
+ * aej_compose_plan_host: HOST only, no device and no context: what the library makes of ONE descriptor (offsets not read): the output's
+ *   size and the clipped region.  Returns the code aej_compose_batch would refuse the descriptor with.
+ * aej_compose_batch: n elements.  src / dst: device bytes; element i reads its base at src + base_offset, its overlay at src +
+ *   over_offset (unless over_channels is 0), its mask at src + mask_offset (AEJ_COMPOSE_MASK_BIT and _BYTE only), and writes exactly
+ *   out_w out_h channels bytes at dst + dst_offset and no other byte of dst; several elements may name the same source bytes; no
+ *   source may overlap dst.  One launch per channel count of the call, each one grid over every element of that count.  The call
+ *   uploads its entries once, runs on the context's stream and waits once at the end.  Every descriptor is checked before any device
+ *   work: AEJ_ERR_ARG naming the element for a size below 1 or above 32767, a channel count outside 1 .. 4, an unknown kind, op or
+ *   mask kind, a pair of channel counts that is not built, a mask whose size is not the overlay's, AEJ_COMPOSE_MASK_OVERLAY with an
+ *   overlay of 1 or 3 channels, an alpha, scale or offset that is not finite, a scale of 0, a source outside src_bytes, an image
+ *   outside dst_bytes.  Workspace: aej_compose_workspace_bytes with the same descriptors (0 for ones the call refuses). */
+enum { AEJ_COMPOSE_PASTE = 0, AEJ_COMPOSE_ALPHA = 1, AEJ_COMPOSE_BLEND = 2, AEJ_COMPOSE_CHOP = 3 };
+enum { AEJ_COMPOSE_MASK_NONE = 0, AEJ_COMPOSE_MASK_BIT = 1, AEJ_COMPOSE_MASK_BYTE = 2, AEJ_COMPOSE_MASK_OVERLAY = 3 };
+enum { AEJ_CHOP_ADD = 0, AEJ_CHOP_SUBTRACT = 1, AEJ_CHOP_ADD_MODULO = 2, AEJ_CHOP_SUBTRACT_MODULO = 3, AEJ_CHOP_MULTIPLY = 4,
+       AEJ_CHOP_SCREEN = 5, AEJ_CHOP_LIGHTER = 6, AEJ_CHOP_DARKER = 7, AEJ_CHOP_DIFFERENCE = 8, AEJ_CHOP_SOFT_LIGHT = 9,
+       AEJ_CHOP_HARD_LIGHT = 10, AEJ_CHOP_OVERLAY = 11 };
+typedef struct aej_compose_desc {
+    int64_t base_offset, over_offset, mask_offset, dst_offset;
+    int32_t kind;                  /* AEJ_COMPOSE_* */
+    int32_t op;                    /* AEJ_COMPOSE_CHOP: AEJ_CHOP_* */
+    int32_t width, height, channels;               /* the base */
+    int32_t over_width, over_height, over_channels;      /* the overlay; over_channels 0: `colour`, and the size is the region's */
+    int32_t mask_width, mask_height, mask_channels;      /* the mask: AEJ_COMPOSE_MASK_BIT (1 channel, bytes 0 / not 0) and _BYTE */
+    int32_t mask_kind;             /* AEJ_COMPOSE_MASK_* */
+    int32_t x, y;                  /* where pixel (0, 0) of the overlay lies in the base */
+    int32_t box[4];                /* left, top, right, bottom: the part of the overlay that is used, in its own coordinates */
+    float alpha;                   /* AEJ_COMPOSE_BLEND */
+    float scale, offset;           /* AEJ_CHOP_ADD and AEJ_CHOP_SUBTRACT */
+    uint8_t colour[4];
+    int32_t reserved[2];
+} aej_compose_desc;
+typedef struct aej_compose_plan {
+    int32_t out_width, out_height, out_channels;
+    int32_t region[4];             /* left, top, right, bottom in the output; all 0 when nothing of the overlay is inside */
+    int32_t reads_overlay, reads_mask;
+    int32_t reserved[3];
+} aej_compose_plan;
+AEJ_API int aej_compose_geometry_host(int32_t *out);
+AEJ_API int aej_compose_plan_host(const aej_compose_desc *desc, aej_compose_plan *out);
+AEJ_API uint64_t aej_compose_workspace_bytes(aej_ctx *ctx, const aej_compose_desc *descs_host, int n);
+AEJ_API int aej_compose_batch(aej_ctx *ctx, const aej_compose_desc *descs_host, int n, const uint8_t *src, uint64_t src_bytes, uint8_t *dst,
+                              uint64_t dst_bytes, void *workspace, uint64_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif
