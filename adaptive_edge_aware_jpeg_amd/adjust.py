@@ -30,9 +30,9 @@ import math
 
 import numpy as np
 
-from ._images import gather_u8, is_int, is_number, one_or_each, packed_views
+from ._images import (gather_u8, image_shape, intake, is_int, is_number, one_or_each, packed_out, packed_results, packed_shape,
+                      refuse_pil_and_bool, run_entry)
 
-MAX_SIDE = 32767
 MAX_OPS = 8
 TABLE_BYTES = 1024
 KINDS = ("brightness", "contrast", "color", "sharpness", "autocontrast", "equalize", "lut", "grayscale")      # AEJ_ADJUST_* (include/aej.h)
@@ -143,25 +143,9 @@ _ONLY_L_RGB = ("autocontrast", "equalize", "posterize", "solarize", "invert")   
 
 
 # ---- argument checks (host only) ---------------------------------------------------------------------------------------------------
-def _shapes(images):
-    shapes = []
-    for i, a in enumerate(images):
-        mode = getattr(a, "mode", None)
-        if isinstance(mode, str) and hasattr(a, "getbands"):
-            if mode in ("P", "1"):
-                raise NotImplementedError(f"image {i}: images of mode {mode!r} are not built")
-            raise TypeError(f"image {i}: a uint8 array or tensor required, got a PIL image")
-        shape, dt = tuple(getattr(a, "shape", ())), str(getattr(a, "dtype", None))
-        if dt in ("bool", "torch.bool"):
-            raise NotImplementedError(f"image {i}: images of mode '1' (bool) are not built")
-        if not (len(shape) == 2 or (len(shape) == 3 and shape[2] in (2, 3, 4))) or shape[0] < 1 or shape[1] < 1:
-            raise ValueError(f"image {i}: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape {shape}")
-        if dt not in ("uint8", "torch.uint8"):
-            raise TypeError(f"image {i}: uint8 required, got {dt}")
-        if max(shape[:2]) > MAX_SIDE:
-            raise ValueError(f"image {i}: sizes up to {MAX_SIDE} a side")
-        shapes.append(tuple(int(v) for v in shape))
-    return shapes
+def _image(a, who):
+    refuse_pil_and_bool(a, who)
+    return image_shape(a, who)
 
 
 def _check_chain(v, who):
@@ -245,7 +229,7 @@ def _describe(chain, C, who, tables):
 
 def _fill(d, shape, ops):
     from ._lib import AdjustDesc  # noqa: F401
-    d.width, d.height, d.channels, d.n_ops = shape[1], shape[0], shape[2] if len(shape) == 3 else 1, len(ops)
+    d.height, d.width, d.channels, d.n_ops = *shape, len(ops)
     for k, o in enumerate(ops):
         p = d.ops[k]
         p.kind, p.table, p.factor, p.preserve_tone = o["kind"], o["table"], o["factor"], o["preserve_tone"]
@@ -282,7 +266,7 @@ def adjust_plan(channels, ops):
     chain = _check_chain(ops, who)
     described, out_c = _describe(chain, int(channels), who, {})
     d, p = AdjustDesc(), AdjustPlan()
-    _fill(d, (1, 1, int(channels)) if channels > 1 else (1, 1), described)
+    _fill(d, (1, 1, int(channels)), described)
     rc = load_library().aej_adjust_plan_host(ctypes.addressof(d), ctypes.addressof(p))
     if rc:
         raise ValueError(f"{who}: the chain was refused (code {rc})")
@@ -290,13 +274,6 @@ def adjust_plan(channels, ops):
     names = [op.name for op in chain]
     return dict(segments=[names[a:b] for a, b in zip(firsts, firsts[1:])], passes=int(p.n_passes), launches=int(p.n_launches),
                 out_channels=int(p.out_channels))
-
-
-def _intake(images, name):
-    images = list(images)
-    if len(images) < 1:
-        raise ValueError(f"{name} needs at least one image")
-    return images, _shapes(images)
 
 
 def adjust_many(images, ops, device: int = 0) -> list:
@@ -314,48 +291,37 @@ def adjust_many(images, ops, device: int = 0) -> list:
     255, a cutoff that is negative or not finite, bits outside 0 to 8; TypeError for a dtype other than uint8 and for something that
     is not an op; NotImplementedError for ``mask=``, images of mode "P" and "1", ``Colorize`` and ``Hue``."""
     from ._lib import AdjustDesc, get_context
-    images, shapes = _intake(images, "adjust_many")
+    images, shapes = intake(images, "adjust_many", _image)
     n = len(images)
     chains = _each_chain(ops, n)
     tables, jobs, seen = {}, [], {}
-    for i in range(n):
-        C = shapes[i][2] if len(shapes[i]) == 3 else 1
+    for i, (h, w, C) in enumerate(shapes):
         key = (id(chains[i]), C)                              # one chain for all images is described once per channel count
         if key not in seen:
             seen[key] = _describe(chains[i], C, f"image {i}", tables)
         described, out_c = seen[key]
-        jobs.append((described, shapes[i][:2] + ((out_c,) if out_c > 1 else ())))
+        jobs.append((described, packed_shape(h, w, out_c)))
     ctx = get_context(device)
-    t, lib = ctx.torch, ctx.lib
     src = gather_u8(ctx, images)
     base, span, src_off = src.span()
+    out_shapes = [j[1] for j in jobs]
+    out, offsets = packed_out(ctx, out_shapes)
     descs = (AdjustDesc * n)()
-    offsets, pos = [], 0
     filled = {}
-    for i, (described, out_shape) in enumerate(jobs):
-        key = (id(described), len(shapes[i]) == 3 and shapes[i][2])
+    for i, (described, _) in enumerate(jobs):
+        key = (id(described), shapes[i][2])
         if key in filled:
             ctypes.memmove(ctypes.addressof(descs[i]), ctypes.addressof(descs[filled[key]]), ctypes.sizeof(AdjustDesc))
-            descs[i].width, descs[i].height = shapes[i][1], shapes[i][0]
+            descs[i].height, descs[i].width = shapes[i][:2]
         else:
             _fill(descs[i], shapes[i], described)
             filled[key] = i
-        descs[i].src_offset, descs[i].dst_offset = src_off[i], pos
-        offsets.append(pos)
-        pos += int(math.prod(out_shape))
+        descs[i].src_offset, descs[i].dst_offset = src_off[i], offsets[i]
     blob = b"".join(tables)                                   # (dicts keep insertion order: table k is the k-th key)
     host_tables = (ctypes.c_uint8 * max(len(blob), 1)).from_buffer_copy(blob or b"\0")
-    out = ctx.empty((pos,), t.uint8)
-    ws = ctx.workspace(max(int(lib.aej_adjust_workspace_bytes(ctx.handle, ctypes.addressof(descs), n)), 256))
-    ctx.check(lib.aej_adjust_batch(ctx.handle, ctypes.addressof(descs), n, ctypes.addressof(host_tables), len(tables), ctypes.c_void_p(base),
-                                   ctypes.c_uint64(span), out.data_ptr(), ctypes.c_uint64(pos), ws.data_ptr(),
-                                   ctypes.c_uint64(ws.numel())))      # synchronises: src's staging is free again
-    res = packed_views(out, offsets, [j[1] for j in jobs])
-    for o, a in zip(res, images):
-        com = getattr(a, "jpeg_comment", None)
-        if com is not None:
-            o.jpeg_comment = com
-    return res
+    run_entry(ctx, ctx.lib.aej_adjust_workspace_bytes, ctx.lib.aej_adjust_batch, descs, n, base, span, out,
+              args=(ctypes.addressof(host_tables), len(tables)), query_args=())      # synchronises: src's staging is free again
+    return packed_results(out, offsets, out_shapes, images)
 
 
 def histogram_many(images, device: int = 0) -> list:
@@ -363,21 +329,16 @@ def histogram_many(images, device: int = 0) -> list:
     by band, views into one packed allocation in input order.  Counted on the device as uint32 (32767 x 32767 fits) and widened
     there.  The image checks are adjust_many's."""
     from ._lib import AdjustDesc, get_context
-    images, shapes = _intake(images, "histogram_many")
+    images, shapes = intake(images, "histogram_many", _image)
     n = len(images)
     ctx = get_context(device)
-    t, lib = ctx.torch, ctx.lib
     src = gather_u8(ctx, images)
     base, span, src_off = src.span()
+    out_shapes = [(256 * c,) for _, _, c in shapes]
+    out, offsets = packed_out(ctx, out_shapes, ctx.torch.int64)
     descs = (AdjustDesc * n)()
-    offsets, pos = [], 0
     for i, s in enumerate(shapes):
         _fill(descs[i], s, [])
-        descs[i].src_offset, descs[i].dst_offset = src_off[i], pos
-        offsets.append(pos)
-        pos += 256 * descs[i].channels
-    out = ctx.empty((pos,), t.int64)
-    ws = ctx.workspace(max(int(lib.aej_adjust_workspace_bytes(ctx.handle, ctypes.addressof(descs), n)), 256))
-    ctx.check(lib.aej_histogram_batch(ctx.handle, ctypes.addressof(descs), n, ctypes.c_void_p(base), ctypes.c_uint64(span), out.data_ptr(),
-                                      ctypes.c_uint64(pos), ws.data_ptr(), ctypes.c_uint64(ws.numel())))      # synchronises: src's staging is free again
-    return packed_views(out, offsets, [(256 * descs[i].channels,) for i in range(n)])
+        descs[i].src_offset, descs[i].dst_offset = src_off[i], offsets[i]
+    run_entry(ctx, ctx.lib.aej_adjust_workspace_bytes, ctx.lib.aej_histogram_batch, descs, n, base, span, out)      # synchronises: src's staging is free again
+    return packed_results(out, offsets, out_shapes)

@@ -23,9 +23,9 @@ import math
 
 import numpy as np
 
-from ._images import gather_u8, is_int, is_number, packed_views
+from ._images import (MAX_SIDE, gather_u8, image_list, image_shape, is_int, is_number, is_pil, packed_out, packed_results, packed_shape,
+                      refuse_pil_and_bool, run_entry)
 
-MAX_SIDE = 32767
 KINDS = ("paste", "alpha_composite", "blend", "chop")          # AEJ_COMPOSE_* (include/aej.h); "composite" is a paste
 MASK_KINDS = ("none", "bit", "byte", "overlay")                # AEJ_COMPOSE_MASK_*
 CHOPS = ("add", "subtract", "add_modulo", "subtract_modulo", "multiply", "screen", "lighter", "darker", "difference", "soft_light",
@@ -66,23 +66,13 @@ def _is_image(a):
 
 def _shape(a, who, what="image"):
     """a uint8 image -> (h, w, channels)"""
-    mode = getattr(a, "mode", None)
-    if isinstance(mode, str) and hasattr(a, "getbands"):
-        if mode in ("P", "1"):
-            raise NotImplementedError(f"{who}: {what}s of mode {mode!r} are not built")
-        raise TypeError(f"{who}: {what}: a uint8 array or tensor required, got a PIL image")
-    if not _is_image(a):
+    if not _is_image(a) and not is_pil(a):
         raise TypeError(f"{who}: {what}: a uint8 array or tensor required, got {type(a).__name__}")
-    shape, dt = tuple(a.shape), _dtype(a)
-    if dt == "bool":
-        raise NotImplementedError(f"{who}: {what}s of mode '1' (bool) are not built")
-    if not (len(shape) == 2 or (len(shape) == 3 and shape[2] in (2, 3, 4))) or shape[0] < 1 or shape[1] < 1:
-        raise ValueError(f"{who}: {what}: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape {shape}")
-    if dt != "uint8":
-        raise TypeError(f"{who}: {what}: uint8 required, got {dt}")
-    if max(shape[:2]) > MAX_SIDE:
-        raise ValueError(f"{who}: {what}: sizes up to {MAX_SIDE} a side")
-    return int(shape[0]), int(shape[1]), int(shape[2]) if len(shape) == 3 else 1
+    refuse_pil_and_bool(a, who, what, f"{who}: {what}")
+    try:
+        return image_shape(a, f"{who}: {what}")
+    except TypeError:                                  # (this module names a tensor's dtype without its "torch.")
+        raise TypeError(f"{who}: {what}: uint8 required, got {_dtype(a)}") from None
 
 
 def _mask_shape(m, who):
@@ -112,13 +102,6 @@ def _each(value, n, name, single):
             raise ValueError(f"{name}: {len(value)} entries for {n} images")
         return value
     return [value] * n
-
-
-def _intake(images, name):
-    images = list(images)
-    if len(images) < 1:
-        raise ValueError(f"{name} needs at least one image")
-    return images
 
 
 def _element(kind, base, who, **kw):
@@ -337,7 +320,7 @@ def _run(elements, firsts, device):
     from ._lib import ComposeDesc, get_context
     n = len(elements)
     ctx = get_context(device)
-    t, lib = ctx.torch, ctx.lib
+    lib = ctx.lib
     objs, where = [], {}
     for e in elements:
         for k in ("base", "over", "mask"):
@@ -347,29 +330,20 @@ def _run(elements, firsts, device):
     src = gather_u8(ctx, objs)
     base, span, src_off = src.span()
     descs = (ComposeDesc * n)()
-    offsets, shapes, pos = [], [], 0
+    shapes = []
     for i, e in enumerate(elements):
         d = descs[i]
         _fill(d, e)
         d.base_offset = src_off[where[id(e["base"])]]
         d.over_offset = src_off[where[id(e["over"])]] if e["over"] is not None else 0
         d.mask_offset = src_off[where[id(e["mask"])]] if e["mask"] is not None else 0
-        d.dst_offset = pos
         p = _resolve(lib, d, f"image {i}")
-        shape = (int(p.out_height), int(p.out_width)) + ((int(p.out_channels),) if p.out_channels > 1 else ())
-        offsets.append(pos)
-        shapes.append(shape)
-        pos += int(math.prod(shape))
-    out = ctx.empty((pos,), t.uint8)
-    ws = ctx.workspace(max(int(lib.aej_compose_workspace_bytes(ctx.handle, ctypes.addressof(descs), n)), 256))
-    ctx.check(lib.aej_compose_batch(ctx.handle, ctypes.addressof(descs), n, ctypes.c_void_p(base), ctypes.c_uint64(span), out.data_ptr(),
-                                    ctypes.c_uint64(pos), ws.data_ptr(), ctypes.c_uint64(ws.numel())))      # synchronises: src's staging is free again
-    res = packed_views(out, offsets, shapes)
-    for o, a in zip(res, firsts):
-        com = getattr(a, "jpeg_comment", None)
-        if com is not None:
-            o.jpeg_comment = com
-    return res
+        shapes.append(packed_shape(int(p.out_height), int(p.out_width), int(p.out_channels)))
+    out, offsets = packed_out(ctx, shapes)
+    for d, o in zip(descs, offsets):
+        d.dst_offset = o
+    run_entry(ctx, lib.aej_compose_workspace_bytes, lib.aej_compose_batch, descs, n, base, span, out)      # synchronises: src's staging is free again
+    return packed_results(out, offsets, shapes, firsts)
 
 
 def _is_box(v):
@@ -391,7 +365,7 @@ def paste_many(bases, overlays, at=(0, 0), mask=None, device: int = 0) -> list:
     ("images do not match"), "alpha" with an overlay of 1 or 3 channels or a colour, a colour that does not fit the base's mode or
     has neither a mask nor a 4-tuple `at` of at least one pixel.  TypeError: a dtype other than uint8.  NotImplementedError: every
     other pair of modes, naming both."""
-    bases = _intake(bases, "paste_many")
+    bases = image_list(bases, "paste_many")
     n = len(bases)
     ov = _each(overlays, n, "overlays", lambda v: False)
     ats = _each(at, n, "at", _is_box)
@@ -407,7 +381,7 @@ def alpha_composite_many(bases, overlays, dest=(0, 0), source=(0, 0), device: in
     the base is dropped, as in Pillow.  ValueError, with Pillow's words: "Source must be a sequence of length 2 or 4", "Destination
     must be a sequence of length 2", "Source must be non-negative", "Coordinate 'right' is less than 'left'", "Coordinate 'lower' is
     less than 'upper'", "image has wrong mode" for anything but 2 and 4 channels, "images do not match" for 2 against 4."""
-    bases = _intake(bases, "alpha_composite_many")
+    bases = image_list(bases, "alpha_composite_many")
     n = len(bases)
     ov = _each(overlays, n, "overlays", lambda v: False)
     dests = _each(dest, n, "dest", _is_box)
@@ -419,7 +393,7 @@ def blend_many(images1, images2, alpha, device: int = 0) -> list:
     """``Image.blend(im1, im2, alpha)``: im1 + alpha (im2 - im1) in float32 on every band, alpha included.  images2: one image for all
     or a list; alpha: one number or a list.  Values outside 0 to 1 extrapolate and clip, as Pillow's.  ValueError: images of one
     element whose sizes or channel counts differ ("images do not match"), an alpha whose float32 value is not finite."""
-    images1 = _intake(images1, "blend_many")
+    images1 = image_list(images1, "blend_many")
     n = len(images1)
     second = _each(images2, n, "images2", lambda v: False)
     alphas = _each(alpha, n, "alpha", lambda v: False)
@@ -431,7 +405,7 @@ def composite_many(images1, images2, masks, device: int = 0) -> list:
     as paste_many's (a bool array, uint8 [h, w], or the last band of [h, w, 2] and [h, w, 4]); images2 and masks: one for all or a
     list.  The two images and the mask of one element must have EQUAL sizes and the images equal channel counts (ValueError "images
     do not match"); Pillow tolerates a second image larger than the first and the mask, this call does not."""
-    images1 = _intake(images1, "composite_many")
+    images1 = image_list(images1, "composite_many")
     n = len(images1)
     second = _each(images2, n, "images2", lambda v: False)
     ms = _each(masks, n, "masks", lambda v: False)
@@ -446,7 +420,7 @@ def chop_many(images1, images2, op, device: int = 0) -> list:
     side, as Pillow's.  Every band is treated alike, alpha included.  ValueError: an unknown op, a scale that is 0 or not finite,
     an offset that is not an int, a scale and offset that take the result out of the int range.  NotImplementedError:
     "logical_and", "logical_or", "logical_xor", "offset" and "invert"."""
-    images1 = _intake(images1, "chop_many")
+    images1 = image_list(images1, "chop_many")
     n = len(images1)
     second = _each(images2, n, "images2", lambda v: False)
     ops = _each(op, n, "op", lambda v: False)

@@ -27,16 +27,6 @@ namespace aej {
 
 template <int kC> struct AdLane { static constexpr int pix = kC == 1 ? 16 : kC == 2 ? 8 : 4; };
 
-__device__ __forceinline__ const AdEntry &ad_entry(const AdEntry *__restrict__ e, int n, long long chunk)
-{
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (e[mid].chunk_base <= chunk) lo = mid; else hi = mid - 1;
-    }
-    return e[lo];
-}
-
 __device__ __forceinline__ int ad_luma(int r, int g, int b) { return (r * 19595 + g * 38470 + b * 7471 + 0x8000) >> 16; }
 
 // kP pixels from pixel q on (q < npix): one vector access when all kP exist, else byte by byte (the missing ones are 0)
@@ -135,7 +125,7 @@ __global__ __launch_bounds__(kAdThreads) void k_adjust_hist(const AdEntry *__res
     __shared__ __align__(16) unsigned char tab[AEJ_ADJUST_MAX_OPS * AEJ_ADJUST_TABLE_BYTES];
     unsigned *mine = wh[threadIdx.x >> 6];
     for (long long chunk = blockIdx.x; chunk < chunks; chunk += gridDim.x) {
-        const AdEntry &e = ad_entry(entries, n, chunk);
+        const AdEntry &e = chunk_entry(entries, n, chunk);
         ad_stage(e, tab);
         for (int i = threadIdx.x; i < kWaves * kC * 256; i += kAdThreads) (&wh[0][0])[i] = 0u;
         __syncthreads();
@@ -181,7 +171,7 @@ __global__ __launch_bounds__(kAdThreads) void k_adjust_apply(const AdEntry *__re
     constexpr int kP = AdLane<kC>::pix, kOut = kGray ? 1 : kC;
     __shared__ __align__(16) unsigned char tab[AEJ_ADJUST_MAX_OPS * AEJ_ADJUST_TABLE_BYTES];
     for (long long chunk = blockIdx.x; chunk < chunks; chunk += gridDim.x) {
-        const AdEntry &e = ad_entry(entries, n, chunk);
+        const AdEntry &e = chunk_entry(entries, n, chunk);
         ad_stage(e, tab);
         __syncthreads();
         const long long p0 = (chunk - e.chunk_base) * kAdChunk;
@@ -379,10 +369,8 @@ int adjust_plan(const aej_adjust_desc *descs, int n, const unsigned char *tables
         const int code = ad_chain(descs[i], n_tables, histogram, ap[i], chain[i], why);
         if (code) return code;
         const long long npix = (long long)descs[i].width * descs[i].height;
-        plan.src_offset.push_back(descs[i].src_offset);
-        plan.dst_offset.push_back(descs[i].dst_offset);
-        plan.src_bytes.push_back(npix * descs[i].channels);
-        plan.dst_bytes.push_back(histogram ? (long long)descs[i].channels * 256 : npix * ap[i].out_channels);
+        plan.spans.reads.push_back({ i, descs[i].src_offset, npix * descs[i].channels });
+        plan.spans.writes.push_back({ i, descs[i].dst_offset, histogram ? (long long)descs[i].channels * 256 : npix * ap[i].out_channels });
         max_seg = std::max(max_seg, chain[i].n_seg);
         n_hists += ap[i].n_passes;
     }
@@ -401,9 +389,9 @@ int adjust_plan(const aej_adjust_desc *descs, int n, const unsigned char *tables
     plan.hists_dev = cv.take<unsigned>(n_hists * kAdHistWords);
     plan.n_hists = n_hists;
     for (int i = 0; i < n && !histogram; i++) {
-        if (chain[i].n_seg >= 2) plane0[i] = cv.take<unsigned char>(plan.src_bytes[i]);
-        if (chain[i].n_seg >= 3) plane1[i] = cv.take<unsigned char>(plan.src_bytes[i]);
-        if (ap[i].n_smooths) smooth[i] = cv.take<unsigned char>(plan.src_bytes[i]);
+        if (chain[i].n_seg >= 2) plane0[i] = cv.take<unsigned char>(plan.spans.reads[i].bytes);
+        if (chain[i].n_seg >= 3) plane1[i] = cv.take<unsigned char>(plan.spans.reads[i].bytes);
+        if (ap[i].n_smooths) smooth[i] = cv.take<unsigned char>(plan.spans.reads[i].bytes);
     }
     if (!histogram) {
         plan.tables.assign((size_t)n * AEJ_ADJUST_MAX_OPS * AEJ_ADJUST_TABLE_BYTES, 0);

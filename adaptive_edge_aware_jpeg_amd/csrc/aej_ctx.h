@@ -159,6 +159,27 @@ inline int null_buffer(aej_ctx *ctx, const char *fn = nullptr)
 {
     return fn ? aej::fail(ctx, AEJ_ERR_ARG, "%s: NULL buffer", fn) : aej::fail(ctx, AEJ_ERR_ARG, "NULL buffer");
 }
+// the span check of a packed-image entry (aej_spans.h) as its refusal: what the call reads lies in the input, what it writes in the
+// output of dst_elements elements of dst_unit bytes, and no source meets the output
+inline int check_spans(aej_ctx *ctx, const char *fn, const aej::Spans &spans, const void *src, uint64_t src_bytes, const void *dst,
+                       uint64_t dst_elements, uint64_t dst_unit = 1)
+{
+    static const char *const what[] = { nullptr, "source outside the input", "image outside the output", "source inside the output" };
+    const aej::SpanVerdict v = aej::span_fault(spans, (uintptr_t)src, src_bytes, (uintptr_t)dst, dst_elements, dst_unit);
+    return v.fault ? aej::fail(ctx, AEJ_ERR_ARG, "%s: image %d: %s", fn, v.image, what[v.fault]) : 0;
+}
+// the plan of a packed-image call, or the refusal of its first bad descriptor (fn NULL: quietly, for the size query).
+// plan(&bad, &why) is the entry's own plan function: -> 0, or its error code with `why` and, where one image is at fault, `bad`
+template <class Plan>
+inline int plan_or_refuse(aej_ctx *ctx, const char *fn, int n, Plan plan)
+{
+    if (n < 1) return fn ? aej::fail(ctx, AEJ_ERR_ARG, "%s: no images", fn) : AEJ_ERR_ARG;
+    const char *why = nullptr;
+    int bad = -1;
+    const int code = plan(&bad, &why);
+    if (!code || !fn) return code;
+    return bad >= 0 ? aej::fail(ctx, code, "%s: image %d: %s", fn, bad, why) : aej::fail(ctx, code, "%s: %s", fn, why);
+}
 // a parser's message into the caller's buffer (truncated, always terminated)
 inline void copy_msg(const std::string &m, char *msg, int msg_capacity)
 {

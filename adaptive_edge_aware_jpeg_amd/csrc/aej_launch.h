@@ -1,8 +1,37 @@
 // aej_launch.h -- host-side launch functions exported by the .hip translation units.
 #pragma once
 #include "aej_common.h"
+#include "aej_spans.h"
 
 namespace aej {
+
+// DEVICE: index of the last of n entries with base(entry) <= t (entries sorted by base, entry 0 at or below every t asked for): how a
+// workgroup, wave or lane of a grid laid over many images finds its own
+template <class E, class T, class Base>
+__device__ __forceinline__ int find_last(const E *f, int n, T t, Base base)
+{
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (base(f[mid]) <= t) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+// the same for the tile kernels: the entry whose workgroups (from its tile_base on) contain blockIdx.x.  (`Here` reads blockIdx.x
+// in the comparison, where the loops this replaces read it: handing find_last its value instead changes the code the compiler emits
+// for the kernels of filter.hip, window.hip and warp.hip -- EXPERIMENTS.md, "One binary search on the device")
+template <class E>
+__device__ __forceinline__ const E &tile_entry(const E *__restrict__ e, int n)
+{
+    struct Here { __device__ __forceinline__ operator long long() const { return (long long)blockIdx.x; } };
+    return e[find_last(e, n, Here(), [](const E &x) { return x.tile_base; })];
+}
+// and for the chunk kernels: the entry whose chunks (from its chunk_base on) contain `chunk`
+template <class E>
+__device__ __forceinline__ const E &chunk_entry(const E *__restrict__ e, int n, long long chunk)
+{
+    return e[find_last(e, n, chunk, [](const E &x) { return x.chunk_base; })];
+}
 
 // color.hip
 int launch_color_convert(hipStream_t st, int space, const float *rgb, float *out, long long n);
@@ -588,11 +617,12 @@ struct RsImage {                       // host: the stages of one image and wher
     bool reduce, horizontal, vertical;
     int ch;                            // bytes per pixel: 3, or 1
     RsReduce r; RsConv h, v;
-    long long src_offset, dst_offset, src_bytes, dst_bytes, r_src, tmp_a, tmp_b, h_table, v_table;
+    long long r_src, tmp_a, tmp_b, h_table, v_table;
     long long win_shift;               // a windowed source without a reduce: bytes from its first stored pixel to pixel (0, 0) of the virtual image (<= 0)
 };
 struct RsPlan {
     std::vector<RsImage> images;
+    Spans spans;                       // per image: its stored source rectangle, its output
     std::vector<int> ints;             // the tables (filled on request)
     long long n_ints = 0, tmp_bytes = 0, tiles[2][3] = {{0, 0, 0}, {0, 0, 0}};      // [0]: the three-channel images, [1]: the one-channel ones
     int count[2][3] = {{0, 0, 0}, {0, 0, 0}};      // images in the reduce / horizontal / vertical launch of either
@@ -641,7 +671,7 @@ struct FtLaunch { int kernel, ch, first, count; long long tiles; unsigned lds; }
 struct FtPlan {
     std::vector<FtStage> stages;       // launch by launch
     std::vector<FtLaunch> launches;
-    std::vector<long long> src_offset, dst_offset, bytes;      // per image
+    Spans spans;                       // per image: its source, its output
     long long tmp_bytes = 0;
 };
 struct FtBufs { unsigned char *blob, *tmp; };
@@ -672,7 +702,7 @@ struct WnPlan {
     std::vector<WnEntry> entries;      // launch by launch; in / out hold nothing yet
     std::vector<int> image;            // the image of each entry
     std::vector<WnLaunch> launches;
-    std::vector<long long> src_offset, dst_offset, bytes;      // per image
+    Spans spans;                       // per image: its source, its output
 };
 int window_plan(const aej_window_desc *descs, int n, WnPlan &plan, int *bad, const char **why);
 void window_blob(const WnPlan &plan, const unsigned char *src, unsigned char *dst, std::vector<WnEntry> &blob);
@@ -706,7 +736,7 @@ struct WpPlan {
     std::vector<int> image;            // the image of each entry
     std::vector<WpLaunch> launches;
     std::vector<int> tables;           // every AEJ_WARP_TABLES image's two tables
-    std::vector<long long> src_offset, dst_offset, src_bytes, dst_bytes;      // per image
+    Spans spans;                       // per image: its source, its output
 };
 int warp_resolve(const aej_warp_desc &d, aej_warp_plan &p, std::vector<int> *tables, const char **why);      // aej_warp_plan_host
 int warp_plan(const aej_warp_desc *descs, int n, WpPlan &plan, int *bad, const char **why);
@@ -752,7 +782,7 @@ struct AdPlan {
     std::vector<AdLaunch> launches;
     std::vector<AdSmooth> smooths;
     std::vector<unsigned char> tables; // per image AEJ_ADJUST_MAX_OPS tables, the AEJ_ADJUST_LUT ones filled
-    std::vector<long long> src_offset, dst_offset, src_bytes, dst_bytes;      // per image (dst in the output's own elements)
+    Spans spans;                       // per image: its source, its output (in the output's own elements)
     unsigned char *entries_dev, *luts_dev, *tables_dev;
     unsigned *hists_dev;
     long long n_hists;
@@ -795,9 +825,7 @@ struct CpLaunch { int channels, first, count; long long chunks; };
 struct CpPlan {
     std::vector<CpEntry> entries;      // launch by launch, device pointers set (null when only measured)
     std::vector<CpLaunch> launches;
-    std::vector<long long> dst_offset, dst_bytes;      // per element
-    struct Read { int element; long long offset, bytes; };
-    std::vector<Read> reads;           // every source the call reads
+    Spans spans;                       // per element: every source it reads (base, overlay, mask), its output
     unsigned char *entries_dev;
     unsigned long long bytes;          // the workspace
 };

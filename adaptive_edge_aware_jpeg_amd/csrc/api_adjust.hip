@@ -19,16 +19,12 @@ extern "C" int aej_adjust_plan_host(const aej_adjust_desc *desc, aej_adjust_plan
     return adjust_resolve(*desc, -1, *out, &why);
 }
 
-// the plan of a call, or the refusal of its first bad descriptor (fn NULL: quietly, for the size query)
 static int adjust_layout(aej_ctx *ctx, const char *fn, const aej_adjust_desc *descs_host, int n, const uint8_t *tables_host, int n_tables,
                          bool histogram, void *workspace, const uint8_t *src, uint8_t *dst, AdPlan &plan)
 {
-    if (n < 1) return fn ? fail(ctx, AEJ_ERR_ARG, "%s: no images", fn) : AEJ_ERR_ARG;
-    const char *why = nullptr;
-    int bad = -1;
-    const int code = adjust_plan(descs_host, n, tables_host, n_tables, histogram, workspace, src, dst, plan, &bad, &why);
-    if (!code || !fn) return code;
-    return bad >= 0 ? fail(ctx, code, "%s: image %d: %s", fn, bad, why) : fail(ctx, code, "%s: %s", fn, why);
+    return plan_or_refuse(ctx, fn, n, [&](int *bad, const char **why) {
+        return adjust_plan(descs_host, n, tables_host, n_tables, histogram, workspace, src, dst, plan, bad, why);
+    });
 }
 
 extern "C" uint64_t aej_adjust_workspace_bytes(aej_ctx *ctx, const aej_adjust_desc *descs_host, int n)
@@ -47,13 +43,7 @@ static int adjust_run(aej_ctx *ctx, const char *fn, const aej_adjust_desc *descs
 {
     AdPlan plan;
     AEJ_TRY(adjust_layout(ctx, fn, descs_host, n, tables_host, n_tables, histogram, nullptr, nullptr, nullptr, plan));      // the checks and the size
-    const uint64_t unit = histogram ? sizeof(int64_t) : 1;
-    for (int i = 0; i < n; i++) {
-        if ((uint64_t)plan.src_offset[i] + (uint64_t)plan.src_bytes[i] > src_bytes) return fail(ctx, AEJ_ERR_ARG, "%s: image %d: source outside the input", fn, i);
-        if ((uint64_t)plan.dst_offset[i] + (uint64_t)plan.dst_bytes[i] > dst_elements) return fail(ctx, AEJ_ERR_ARG, "%s: image %d: image outside the output", fn, i);
-        const uintptr_t a = (uintptr_t)src + (uintptr_t)plan.src_offset[i], d = (uintptr_t)dst;
-        if (a < d + dst_elements * unit && d < a + (uintptr_t)plan.src_bytes[i]) return fail(ctx, AEJ_ERR_ARG, "%s: image %d: source inside the output", fn, i);
-    }
+    AEJ_TRY(check_spans(ctx, fn, plan.spans, src, src_bytes, dst, dst_elements, histogram ? sizeof(int64_t) : 1));
     AEJ_TRY(check_workspace(ctx, plan.bytes, workspace_bytes));
     AEJ_TRY(adjust_layout(ctx, fn, descs_host, n, tables_host, n_tables, histogram, workspace, src, dst, plan));             // the same plan, with its pointers
     AEJ_TRY(bind_device(ctx));

@@ -17,15 +17,9 @@ extern "C" int aej_filter_geometry_host(int32_t *out)
     return 0;
 }
 
-// the plan of a call, or the refusal of its first bad descriptor (fn NULL: quietly, for the size query)
 static int filter_layout(aej_ctx *ctx, const char *fn, const aej_filter_desc *descs_host, int n, int path, FtPlan &plan)
 {
-    if (n < 1) return fn ? fail(ctx, AEJ_ERR_ARG, "%s: no images", fn) : AEJ_ERR_ARG;
-    const char *why = nullptr;
-    int bad = -1;
-    const int code = filter_plan(descs_host, n, path, plan, &bad, &why);
-    if (!code || !fn) return code;
-    return bad >= 0 ? fail(ctx, code, "%s: image %d: %s", fn, bad, why) : fail(ctx, code, "%s: %s", fn, why);
+    return plan_or_refuse(ctx, fn, n, [&](int *bad, const char **why) { return filter_plan(descs_host, n, path, plan, bad, why); });
 }
 
 extern "C" uint64_t aej_filter_workspace_bytes(aej_ctx *ctx, const aej_filter_desc *descs_host, int n, int path)
@@ -44,13 +38,7 @@ extern "C" int aej_filter_batch(aej_ctx *ctx, const aej_filter_desc *descs_host,
     if (!descs_host || !src || !dst || !workspace) return null_buffer(ctx, fn);
     FtPlan plan;
     AEJ_TRY(filter_layout(ctx, fn, descs_host, n, path, plan));
-    for (int i = 0; i < n; i++) {
-        if ((uint64_t)plan.src_offset[i] + (uint64_t)plan.bytes[i] > src_bytes) return fail(ctx, AEJ_ERR_ARG, "%s: image %d: source outside the input", fn, i);
-        if ((uint64_t)plan.dst_offset[i] + (uint64_t)plan.bytes[i] > dst_bytes) return fail(ctx, AEJ_ERR_ARG, "%s: image %d: image outside the output", fn, i);
-        // (src_bytes may span memory between separate images, the output among it: what must not meet the output is each image)
-        const uintptr_t a = (uintptr_t)src + (uintptr_t)plan.src_offset[i], d = (uintptr_t)dst;
-        if (a < d + dst_bytes && d < a + (uintptr_t)plan.bytes[i]) return fail(ctx, AEJ_ERR_ARG, "%s: image %d: source inside the output", fn, i);
-    }
+    AEJ_TRY(check_spans(ctx, fn, plan.spans, src, src_bytes, dst, dst_bytes));
     FtBufs w;
     AEJ_TRY(check_workspace(ctx, filter_carve(workspace, plan, w), workspace_bytes));
     std::vector<FtEntry> blob;

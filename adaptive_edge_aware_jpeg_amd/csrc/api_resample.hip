@@ -19,11 +19,11 @@ extern "C" int aej_resample_taps_host(int in_size, float in0, float in1, int out
 static int resample_layout(aej_ctx *ctx, const char *fn, const aej_resample_desc *descs_host, int n, bool fill, RsPlan &plan, const int *channels_host,
                            const int32_t *windows_host = nullptr)
 {
-    if (n < 1) return fn ? fail(ctx, AEJ_ERR_ARG, "%s: no images", fn) : AEJ_ERR_ARG;
-    const char *why = nullptr;
-    int code = AEJ_ERR_ARG;
-    const int bad = resample_plan(descs_host, n, fill, plan, &why, &code, channels_host, windows_host);
-    if (bad >= 0) return fn ? fail(ctx, code, "%s: image %d: %s", fn, bad, why) : code;
+    AEJ_TRY(plan_or_refuse(ctx, fn, n, [&](int *bad, const char **why) {
+        int code = AEJ_ERR_ARG;
+        *bad = resample_plan(descs_host, n, fill, plan, why, &code, channels_host, windows_host);      // (the image at fault, or -1)
+        return *bad >= 0 ? code : 0;
+    }));
     for (int s = 0; s < 6; s++)
         if (plan.tiles[s / 3][s % 3] > 0x7fffffffLL) return fn ? fail(ctx, AEJ_ERR_UNSUPPORTED, "%s: more than 2^31 workgroups in one launch", fn) : AEJ_ERR_UNSUPPORTED;
     return 0;
@@ -62,11 +62,7 @@ static int resample_batch(aej_ctx *ctx, const char *fn, const aej_resample_desc 
     if (!descs_host || !src || !dst || !workspace) return null_buffer(ctx, fn);
     RsPlan plan;
     AEJ_TRY(resample_layout(ctx, fn, descs_host, n, true, plan, channels_host, windows_host));
-    for (int i = 0; i < n; i++) {
-        const RsImage &im = plan.images[i];
-        if ((uint64_t)im.src_offset + (uint64_t)im.src_bytes > src_bytes) return fail(ctx, AEJ_ERR_ARG, "%s: image %d: source outside the input", fn, i);
-        if ((uint64_t)im.dst_offset + (uint64_t)im.dst_bytes > dst_bytes) return fail(ctx, AEJ_ERR_ARG, "%s: image %d: image outside the output", fn, i);
-    }
+    AEJ_TRY(check_spans(ctx, fn, plan.spans, src, src_bytes, dst, dst_bytes));
     RsBufs w;
     AEJ_TRY(check_workspace(ctx, resample_carve(workspace, plan, w), workspace_bytes));
     std::vector<unsigned char> blob;

@@ -23,15 +23,9 @@ extern "C" int aej_warp_plan_host(const aej_warp_desc *desc, aej_warp_plan *out,
     return 0;
 }
 
-// the plan of a call, or the refusal of its first bad descriptor (fn NULL: quietly, for the size query)
 static int warp_layout(aej_ctx *ctx, const char *fn, const aej_warp_desc *descs_host, int n, WpPlan &plan)
 {
-    if (n < 1) return fn ? fail(ctx, AEJ_ERR_ARG, "%s: no images", fn) : AEJ_ERR_ARG;
-    const char *why = nullptr;
-    int bad = -1;
-    const int code = warp_plan(descs_host, n, plan, &bad, &why);
-    if (!code || !fn) return code;
-    return bad >= 0 ? fail(ctx, code, "%s: image %d: %s", fn, bad, why) : fail(ctx, code, "%s: %s", fn, why);
+    return plan_or_refuse(ctx, fn, n, [&](int *bad, const char **why) { return warp_plan(descs_host, n, plan, bad, why); });
 }
 
 static unsigned long long warp_carve(void *base, const WpPlan &plan, unsigned char *&blob, int *&tables)
@@ -59,13 +53,7 @@ extern "C" int aej_warp_batch(aej_ctx *ctx, const aej_warp_desc *descs_host, int
     if (!descs_host || !src || !dst || !workspace) return null_buffer(ctx, fn);
     WpPlan plan;
     AEJ_TRY(warp_layout(ctx, fn, descs_host, n, plan));
-    for (int i = 0; i < n; i++) {
-        if ((uint64_t)plan.src_offset[i] + (uint64_t)plan.src_bytes[i] > src_bytes) return fail(ctx, AEJ_ERR_ARG, "%s: image %d: source outside the input", fn, i);
-        if ((uint64_t)plan.dst_offset[i] + (uint64_t)plan.dst_bytes[i] > dst_bytes) return fail(ctx, AEJ_ERR_ARG, "%s: image %d: image outside the output", fn, i);
-        // (src_bytes may span memory between separate images, the output among it: what must not meet the output is each image)
-        const uintptr_t a = (uintptr_t)src + (uintptr_t)plan.src_offset[i], d = (uintptr_t)dst;
-        if (a < d + dst_bytes && d < a + (uintptr_t)plan.src_bytes[i]) return fail(ctx, AEJ_ERR_ARG, "%s: image %d: source inside the output", fn, i);
-    }
+    AEJ_TRY(check_spans(ctx, fn, plan.spans, src, src_bytes, dst, dst_bytes));
     unsigned char *blob_dev;
     int *tables_dev;
     AEJ_TRY(check_workspace(ctx, warp_carve(workspace, plan, blob_dev, tables_dev), workspace_bytes));

@@ -28,16 +28,6 @@ namespace aej {
 
 template <int kC> struct CpLane { static constexpr int pix = kC == 1 ? 16 : kC == 2 ? 8 : 4; };
 
-__device__ __forceinline__ const CpEntry &cp_entry(const CpEntry *__restrict__ e, int n, long long chunk)
-{
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (e[mid].chunk_base <= chunk) lo = mid; else hi = mid - 1;
-    }
-    return e[lo];
-}
-
 // kBytes adjacent bytes by one vector access
 template <int kBytes> struct CpWords {
     unsigned w[kBytes / 4];
@@ -136,7 +126,7 @@ __global__ __launch_bounds__(kCpThreads) void k_compose(const CpEntry *__restric
     constexpr int kP = CpLane<kC>::pix;
     constexpr int kWide = kC == 1 || kC == 3 ? kC + 1 : kC;    // the overlay with one band more: 2 over 1, 4 over 3
     for (long long chunk = blockIdx.x; chunk < chunks; chunk += gridDim.x) {
-        const CpEntry &e = cp_entry(entries, n, chunk);
+        const CpEntry &e = chunk_entry(entries, n, chunk);
         const int p0 = (int)(chunk - e.chunk_base) * kCpChunk;
         const bool masked = e.mkind == AEJ_COMPOSE_MASK_BIT || e.mkind == AEJ_COMPOSE_MASK_BYTE;
         for (int j = 0; j < kCpChunk / (kCpThreads * kP); j++) {
@@ -309,11 +299,10 @@ int compose_plan(const aej_compose_desc *descs, int n, void *workspace, const un
         if (code) return code;
         const aej_compose_desc &d = descs[i];
         const bool masked = d.mask_kind == AEJ_COMPOSE_MASK_BIT || d.mask_kind == AEJ_COMPOSE_MASK_BYTE;
-        plan.dst_offset.push_back(d.dst_offset);
-        plan.dst_bytes.push_back((long long)cp[i].out_width * cp[i].out_height * d.channels);
-        plan.reads.push_back({ i, d.base_offset, (long long)d.width * d.height * d.channels });
-        if (d.over_channels > 0) plan.reads.push_back({ i, d.over_offset, (long long)d.over_width * d.over_height * d.over_channels });
-        if (masked) plan.reads.push_back({ i, d.mask_offset, (long long)d.mask_width * d.mask_height * d.mask_channels });
+        plan.spans.writes.push_back({ i, d.dst_offset, (long long)cp[i].out_width * cp[i].out_height * d.channels });
+        plan.spans.reads.push_back({ i, d.base_offset, (long long)d.width * d.height * d.channels });
+        if (d.over_channels > 0) plan.spans.reads.push_back({ i, d.over_offset, (long long)d.over_width * d.over_height * d.over_channels });
+        if (masked) plan.spans.reads.push_back({ i, d.mask_offset, (long long)d.mask_width * d.mask_height * d.mask_channels });
     }
     *bad = -1;
     Carver cv(workspace);

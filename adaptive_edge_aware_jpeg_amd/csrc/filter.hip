@@ -56,16 +56,6 @@ int filter_weights(int kind, float xradius, float yradius, aej_filter_plan &p)
 }
 
 // ---- device: what the three kernels share ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ const FtEntry &ft_entry(const FtEntry *__restrict__ e, int n)
-{
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (e[mid].tile_base <= (long long)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    return e[lo];
-}
-
 // Every factor is below 2^24 -- acc <= 255 * 2049, far <= 510, fw < 2^23, and ww < 2^24 for every radius but one so small that
 // 2^24 / (2 fr + 1) rounds to 2^24, which filter_plan replaces (see kFtUnitWeight) --, so the products are the full-rate 24-bit ones.
 __device__ __forceinline__ unsigned ft_box(unsigned acc, unsigned far, unsigned ww, unsigned fw)
@@ -122,7 +112,7 @@ template <int kC>
 __global__ __launch_bounds__(kFtThreads) void k_filter_tile(const FtEntry *__restrict__ entries, int n)
 {
     extern __shared__ __align__(16) unsigned char ft_lds[];
-    const FtEntry &e = ft_entry(entries, n);
+    const FtEntry &e = tile_entry(entries, n);
     const int tiles_x = (e.w + kFtTileW - 1) / kFtTileW, local = (int)((long long)blockIdx.x - e.tile_base);
     const int X0 = (local % tiles_x) * kFtTileW, Y0 = (local / tiles_x) * kFtTileH;
     const int hx = e.hx, hy = e.hy, RW = kFtTileW + 2 * hx, RH = kFtTileH + 2 * hy;
@@ -228,7 +218,7 @@ template <int kC>
 __global__ __launch_bounds__(kFtPassThreads) void k_filter_rows(const FtEntry *__restrict__ entries, int n)
 {
     extern __shared__ __align__(16) unsigned char ft_lds[];
-    const FtEntry &e = ft_entry(entries, n);
+    const FtEntry &e = tile_entry(entries, n);
     const int spans = (e.w + kFtRowSpan - 1) / kFtRowSpan;
     const long long local = (long long)blockIdx.x - e.tile_base;
     const int y = (int)(local / spans), x0 = (int)(local - (long long)y * spans) * kFtRowSpan;
@@ -287,7 +277,7 @@ __global__ __launch_bounds__(kFtPassThreads) void k_filter_rows(const FtEntry *_
 // first row is summed over the rows it really covers, the clamped ones counted, not read.
 __global__ __launch_bounds__(kFtPassThreads) void k_filter_cols(const FtEntry *__restrict__ entries, int n)
 {
-    const FtEntry &e = ft_entry(entries, n);
+    const FtEntry &e = tile_entry(entries, n);
     const int groups = (e.w + kFtColBytes - 1) / kFtColBytes;
     const long long local = (long long)blockIdx.x - e.tile_base;
     const int band = (int)(local / groups), b0 = ((int)(local - (long long)band * groups) * kFtPassThreads + (int)threadIdx.x) * 4;
@@ -364,9 +354,8 @@ int filter_plan(const aej_filter_desc *descs, int n, int path, FtPlan &plan, int
         im.fused = path != AEJ_FILTER_PASSES && fits;
         im.stages = std::max(1, im.nx + im.ny);      // (no pass at all: one identity pass copies)
         const long long bytes = (long long)d.width * d.height * d.channels;
-        plan.src_offset.push_back(d.src_offset);
-        plan.dst_offset.push_back(d.dst_offset);
-        plan.bytes.push_back(bytes);
+        plan.spans.reads.push_back({ i, d.src_offset, bytes });
+        plan.spans.writes.push_back({ i, d.dst_offset, bytes });
         im.tmp = plan.tmp_bytes;
         if (!im.fused) plan.tmp_bytes += align_up(bytes, 256) * std::min(2, im.stages - 1);
     }
@@ -407,7 +396,7 @@ int filter_plan(const aej_filter_desc *descs, int n, int path, FtPlan &plan, int
     // stage s of an image reads the source (s = 0) or buffer (s - 1) & 1 and writes the destination (the last) or buffer s & 1
     auto route = [&](FtStage &s, int i, int stage) {
         const Image &im = images[i];
-        const long long buf = align_up(plan.bytes[i], 256);
+        const long long buf = align_up(plan.spans.writes[i].bytes, 256);
         if (stage > 0) { s.in_base = 2; s.in_off = im.tmp + ((stage - 1) & 1) * buf; }
         if (stage < im.stages - 1) { s.out_base = 2; s.out_off = im.tmp + (stage & 1) * buf; s.orig_off = -1; }
     };

@@ -33,12 +33,7 @@ constexpr int kJmThreads = 256, kJmBlocks = kJmThreads / 8, kJmStride = 9;
 
 __device__ __forceinline__ int jm_find_image(const JmImage *f, int n, long long t)      // last image whose blk_base <= t (jt_find_file)
 {
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (f[mid].blk_base <= t) lo = mid; else hi = mid - 1;
-    }
-    return lo;
+    return find_last(f, n, t, [](const JmImage &I) { return I.blk_base; });
 }
 
 template <int HS, int VS>

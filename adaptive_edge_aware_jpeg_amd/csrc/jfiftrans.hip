@@ -56,12 +56,7 @@ constexpr int kJtThreads = 256;
 
 __device__ __forceinline__ int jt_find_file(const JtFile *f, int n, long long t)      // last file whose src_base <= t (jd_find_file)
 {
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (f[mid].src_base <= t) lo = mid; else hi = mid - 1;
-    }
-    return lo;
+    return find_last(f, n, t, [](const JtFile &F) { return F.src_base; });
 }
 
 __global__ __launch_bounds__(kJtThreads) void k_jt_bridge(const JtFile *__restrict__ files, int n, long long n_blocks, int *__restrict__ status)

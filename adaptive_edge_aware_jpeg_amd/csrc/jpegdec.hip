@@ -56,30 +56,18 @@ constexpr int kJdThreads = 256;
 constexpr int kJdScanThreads = 1024;
 constexpr int kJdRun = 64;                 // MCUs of one MCU row that a workgroup of k_jd_scaled reconstructs
 
-// index i of the last of n files with base(file) <= t
-template <class Base>
-__device__ __forceinline__ int jd_find_last(const JdFile *f, int n, long long t, Base base)
-{
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (base(f[mid]) <= t) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
-// the same where the base is a member
+// index i of the last of n files whose member M is <= t (find_last, aej_launch.h)
 template <long long JdFile::*M>
 __device__ __forceinline__ int jd_find_file(const JdFile *f, int n, long long t)
 {
-    return jd_find_last(f, n, t, [](const JdFile &F) { return F.*M; });
+    return find_last(f, n, t, [](const JdFile &F) { return F.*M; });
 }
 
 // the file whose workgroups contain `blockIdx.x`, in the grid of the kernel whose first workgroup of a file is M[k] (an array member)
 template <class A>
 __device__ __forceinline__ int jd_group_file(const JdFile *f, int n, A JdFile::*M, int k)
 {
-    return jd_find_last(f, n, (long long)blockIdx.x, [=](const JdFile &F) { return (F.*M)[k]; });
+    return find_last(f, n, (long long)blockIdx.x, [=](const JdFile &F) { return (F.*M)[k]; });
 }
 
 // Rows 0 .. nrows - 1 of nbytes bytes each leave LDS for global memory, row r to gp0 + r * pitch: whole dwords inside a row, single
@@ -104,12 +92,7 @@ __device__ __forceinline__ void jd_store_rows(unsigned char *gp0, int pitch, con
 
 __device__ __forceinline__ int jd_find_seg(const JdSeg *s, int n, long long t)      // last segment whose slot_base <= t
 {
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (s[mid].slot_base <= t) lo = mid; else hi = mid - 1;
-    }
-    return lo;
+    return find_last(s, n, t, [](const JdSeg &S) { return S.slot_base; });
 }
 
 __device__ __forceinline__ void jd_fail(int *status, int f, int code) { atomicCAS(status + f, 0, code); }

@@ -111,18 +111,6 @@ void rs_taps(int in_size, float in0, float in1, int out_size, int f, int ksize, 
 }
 
 // ---- kernels ------------------------------------------------------------------------------------------------------------------------------
-// the entry of a stage whose workgroups contain blockIdx.x (entries sorted by tile_base, entry 0 at 0)
-template <class E>
-__device__ __forceinline__ const E &rs_entry(const E *__restrict__ e, int n)
-{
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (e[mid].tile_base <= (long long)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    return e[lo];
-}
-
 __device__ __forceinline__ unsigned char rs_clip(int acc)
 {
     return (unsigned char)min(max(acc >> kRsBits, 0), 255);      // an arithmetic shift, as Pillow's clip8
@@ -133,7 +121,7 @@ __device__ __forceinline__ unsigned char rs_clip(int acc)
 template <int kC>
 __global__ __launch_bounds__(kRsThreads) void k_rs_reduce(const RsReduce *__restrict__ entries, int n)
 {
-    const RsReduce &e = rs_entry(entries, n);
+    const RsReduce &e = tile_entry(entries, n);
     const long long p = ((long long)blockIdx.x - e.tile_base) * kRsThreads + threadIdx.x;
     if (p >= (long long)e.out_w * e.out_h) return;
     const int y = (int)(p / e.out_w), x = (int)(p - (long long)y * e.out_w);
@@ -161,7 +149,7 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_reduce(const RsReduce *__rest
 template <int kC>
 __global__ __launch_bounds__(kRsThreads) void k_rs_horizontal(const RsConv *__restrict__ entries, int n)
 {
-    const RsConv &e = rs_entry(entries, n);
+    const RsConv &e = tile_entry(entries, n);
     const long long p = ((long long)blockIdx.x - e.tile_base) * kRsThreads + threadIdx.x;
     if (p >= (long long)e.out_w * e.out_h) return;
     const int y = (int)(p / e.out_w), xx = (int)(p - (long long)y * e.out_w);
@@ -185,7 +173,7 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_horizontal(const RsConv *__re
 template <int kC>
 __global__ __launch_bounds__(kRsThreads) void k_rs_vertical(const RsConv *__restrict__ entries, int n)
 {
-    const RsConv &e = rs_entry(entries, n);
+    const RsConv &e = tile_entry(entries, n);
     const long long p = ((long long)blockIdx.x - e.tile_base) * kRsThreads + threadIdx.x;
     if (p >= (long long)e.out_w * e.out_h) return;
     const int yy = (int)(p / e.out_w), x = (int)(p - (long long)yy * e.out_w);
@@ -375,9 +363,9 @@ int resample_plan(const aej_resample_desc *descs, int n, bool fill, RsPlan &plan
                 plan.tmp_bytes += align_up((long long)e.out_w * e.out_h * ch, 256);
             }
         }
-        im.src_offset = d.src_offset; im.dst_offset = d.dst_offset;
         im.win_shift = windows && !im.reduce ? -((long long)wy0 * sw + wx0) * ch : 0;
-        im.src_bytes = (long long)sw * sh * ch; im.dst_bytes = (long long)d.dst_w * d.dst_h * ch;
+        plan.spans.reads.push_back({ i, d.src_offset, (long long)sw * sh * ch });
+        plan.spans.writes.push_back({ i, d.dst_offset, (long long)d.dst_w * d.dst_h * ch });
         int *count = plan.count[ch == 1];
         count[0] += im.reduce; count[1] += im.horizontal; count[2] += im.vertical || copy;
         plan.images.push_back(im);
@@ -414,9 +402,10 @@ void resample_blob(const RsPlan &plan, const RsBufs &w, const unsigned char *src
     vv[0] = hh[1] + plan.count[1][1]; vv[1] = vv[0] + plan.count[0][2];
     const int *ints = (const int *)(w.blob + entries);
     if (plan.n_ints) memcpy(blob.data() + entries, plan.ints.data(), 4 * plan.n_ints);
-    for (const RsImage &im : plan.images) {
-        const unsigned char *in = src + im.src_offset + im.win_shift;      // pixel (0, 0) of the virtual image, were it stored
-        unsigned char *out = dst + im.dst_offset;
+    for (size_t i = 0; i < plan.images.size(); i++) {
+        const RsImage &im = plan.images[i];
+        const unsigned char *in = src + plan.spans.reads[i].offset + im.win_shift;      // pixel (0, 0) of the virtual image, were it stored
+        unsigned char *out = dst + plan.spans.writes[i].offset;
         const bool copy = !im.reduce && !im.horizontal && !im.vertical;
         RsReduce *&r = rr[im.ch == 1];
         RsConv *&h = hh[im.ch == 1], *&v = vv[im.ch == 1];

@@ -22,16 +22,6 @@
 
 namespace aej {
 
-__device__ __forceinline__ const WpEntry &wp_entry(const WpEntry *__restrict__ e, int n)
-{
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (e[mid].tile_base <= (long long)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    return e[lo];
-}
-
 // nb (1 .. 4) bytes at any address, as the low bytes of a word
 __device__ __forceinline__ unsigned wp_load4(const unsigned char *p, int nb)
 {
@@ -119,7 +109,7 @@ __device__ __forceinline__ void wp_row(const WpEntry &e, int x0, int y, double d
 template <int kC, int kF, int kPath>
 __global__ __launch_bounds__(kWpThreads) void k_warp(const WpEntry *__restrict__ entries, int n)
 {
-    const WpEntry &e = wp_entry(entries, n);
+    const WpEntry &e = tile_entry(entries, n);
     const int tiles_x = (e.dw + kWpTileW - 1) / kWpTileW, local = (int)((long long)blockIdx.x - e.tile_base);
     const int x = (local % tiles_x) * kWpTileW + (int)(threadIdx.x % kWpTileW);
     const int y = (local / tiles_x) * kWpTileH + (int)(threadIdx.x / kWpTileW);
@@ -208,7 +198,7 @@ __global__ __launch_bounds__(kWpThreads) void k_warp(const WpEntry *__restrict__
 template <int kC>
 __global__ __launch_bounds__(kWpThreads) void k_flip(const WpEntry *__restrict__ entries, int n)
 {
-    const WpEntry &e = wp_entry(entries, n);
+    const WpEntry &e = tile_entry(entries, n);
     const int rb = e.dw * kC, tiles_x = (rb + kWpFlipBytes - 1) / kWpFlipBytes, local = (int)((long long)blockIdx.x - e.tile_base);
     const int b0 = (local % tiles_x) * kWpFlipBytes + (int)threadIdx.x * 4, y0 = (local / tiles_x) * kWpFlipRows;
     if (b0 >= rb) return;
@@ -238,7 +228,7 @@ __global__ __launch_bounds__(kWpThreads) void k_transpose(const WpEntry *__restr
 {
     constexpr int kPitch = kWpSwapTile * kC + 4;
     __shared__ unsigned char lds[kWpSwapTile * kPitch];
-    const WpEntry &e = wp_entry(entries, n);
+    const WpEntry &e = tile_entry(entries, n);
     const int tiles_x = (e.dw + kWpSwapTile - 1) / kWpSwapTile, local = (int)((long long)blockIdx.x - e.tile_base);
     const int X0 = (local % tiles_x) * kWpSwapTile, Y0 = (local / tiles_x) * kWpSwapTile;
     const int tw = min(kWpSwapTile, e.dw - X0), th = min(kWpSwapTile, e.dh - Y0);
@@ -358,10 +348,8 @@ int warp_plan(const aej_warp_desc *descs, int n, WpPlan &plan, int *bad, const c
             key[i] = { (d.method == 0 || d.method == 1 || d.method == 3) ? 1 : 2, d.channels, 0, 0 };
         else
             key[i] = { 0, d.channels, d.filter, p.path };
-        plan.src_offset.push_back(d.src_offset);
-        plan.dst_offset.push_back(d.dst_offset);
-        plan.src_bytes.push_back((long long)d.src_w * d.src_h * d.channels);
-        plan.dst_bytes.push_back((long long)d.dst_w * d.dst_h * d.channels);
+        plan.spans.reads.push_back({ i, d.src_offset, (long long)d.src_w * d.src_h * d.channels });
+        plan.spans.writes.push_back({ i, d.dst_offset, (long long)d.dst_w * d.dst_h * d.channels });
     }
     *bad = -1;
     std::vector<char> done(n, 0);
@@ -390,8 +378,8 @@ void warp_blob(const WpPlan &plan, const unsigned char *src, unsigned char *dst,
 {
     blob = plan.entries;
     for (size_t k = 0; k < blob.size(); k++) {
-        blob[k].in = src + plan.src_offset[plan.image[k]];
-        blob[k].out = dst + plan.dst_offset[plan.image[k]];
+        blob[k].in = src + plan.spans.reads[plan.image[k]].offset;
+        blob[k].out = dst + plan.spans.writes[plan.image[k]].offset;
         blob[k].tab = blob[k].tab_at >= 0 ? tables_dev + blob[k].tab_at : nullptr;
     }
 }

@@ -24,16 +24,6 @@
 
 namespace aej {
 
-__device__ __forceinline__ const WnEntry &wn_entry(const WnEntry *__restrict__ e, int n)
-{
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (e[mid].tile_base <= (long long)blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    return e[lo];
-}
-
 // nb (1 .. 4) bytes at any address, as the low bytes of a word; the address of a row of a packed image has no alignment
 __device__ __forceinline__ unsigned wn_load4(const unsigned char *p, int nb)
 {
@@ -106,7 +96,7 @@ template <int kC, int kK>
 __global__ __launch_bounds__(kWnThreads) void k_window_conv(const WnEntry *__restrict__ entries, int n)
 {
     extern __shared__ __align__(16) unsigned char wn_lds_buf[];
-    const WnEntry &e = wn_entry(entries, n);
+    const WnEntry &e = tile_entry(entries, n);
     constexpr int r = kK / 2, M = (r * kC + 3) / 4, ND = 2 * M + 1;
     constexpr int pad = (4 - (r * kC) % 4) % 4, pitch = (pad + (kWnTileW + 2 * r) * kC + 3) & ~3, tile_off = pad + r * kC;
     const WnTile t = wn_tile(e);
@@ -161,7 +151,7 @@ template <int kC>
 __global__ __launch_bounds__(kWnThreads) void k_window_rank(const WnEntry *__restrict__ entries, int n)
 {
     extern __shared__ __align__(16) unsigned char wn_lds_buf[];
-    const WnEntry &e = wn_entry(entries, n);
+    const WnEntry &e = tile_entry(entries, n);
     const int r = e.r, rank = e.rank, pad = wn_pad(r, kC), pitch = wn_pitch(r, kC);
     const WnTile t = wn_tile(e);
     wn_stage<kC>(e, t, r, wn_lds_buf, pad, pitch);
@@ -192,7 +182,7 @@ template <int kC>
 __global__ __launch_bounds__(kWnThreads) void k_window_mode(const WnEntry *__restrict__ entries, int n)
 {
     extern __shared__ __align__(16) unsigned char wn_lds_buf[];
-    const WnEntry &e = wn_entry(entries, n);
+    const WnEntry &e = tile_entry(entries, n);
     const int r = e.r, pad = wn_pad(r, kC), pitch = wn_pitch(r, kC);
     const WnTile t = wn_tile(e);
     wn_stage<kC>(e, t, r, wn_lds_buf, pad, pitch);
@@ -266,9 +256,9 @@ int window_plan(const aej_window_desc *descs, int n, WnPlan &plan, int *bad, con
             *why = "unknown filter kind";
             return AEJ_ERR_ARG;
         }
-        plan.src_offset.push_back(d.src_offset);
-        plan.dst_offset.push_back(d.dst_offset);
-        plan.bytes.push_back((long long)d.width * d.height * d.channels);
+        const long long bytes = (long long)d.width * d.height * d.channels;
+        plan.spans.reads.push_back({ i, d.src_offset, bytes });
+        plan.spans.writes.push_back({ i, d.dst_offset, bytes });
     }
     *bad = -1;
     static const int kinds[4][2] = { { AEJ_WINDOW_KERNEL, 3 }, { AEJ_WINDOW_KERNEL, 5 }, { AEJ_WINDOW_RANK, 0 }, { AEJ_WINDOW_MODE, 0 } };
@@ -296,8 +286,8 @@ void window_blob(const WnPlan &plan, const unsigned char *src, unsigned char *ds
 {
     blob = plan.entries;
     for (size_t k = 0; k < blob.size(); k++) {
-        blob[k].in = src + plan.src_offset[plan.image[k]];
-        blob[k].out = dst + plan.dst_offset[plan.image[k]];
+        blob[k].in = src + plan.spans.reads[plan.image[k]].offset;
+        blob[k].out = dst + plan.spans.writes[plan.image[k]].offset;
     }
 }
 

@@ -33,7 +33,7 @@ import math
 
 import numpy as np
 
-from ._images import gather_u8, is_int, is_number, one_or_each, packed_views
+from ._images import gather_u8, image_list, image_shape, is_int, is_number, one_or_each, packed_out, packed_results, packed_shape, run_entry
 
 KINDS = {"BoxBlur": 0, "GaussianBlur": 1, "UnsharpMask": 2}      # AEJ_FILTER_*
 PATHS = {"auto": 0, "fused": 1, "passes": 2}                     # AEJ_FILTER_AUTO / _FUSED / _PASSES
@@ -370,10 +370,8 @@ def filter_many(images, filter, device: int = 0, _path: str = "auto") -> list:
     2^100.  _path ("auto", "fused", "passes") picks the blurs' kernel path for tests and A/B runs; "fused" raises ValueError for a
     blur beyond its halo; images with a window filter ignore it."""
     from ._lib import FilterDesc, WindowDesc, get_context
-    images = list(images)
+    images = image_list(images, "filter_many")
     n = len(images)
-    if n < 1:
-        raise ValueError("filter_many needs at least one image")
     if not isinstance(_path, str) or _path not in PATHS:
         raise ValueError(f"_path {_path!r}: 'auto', 'fused' or 'passes' required")
     filters = one_or_each(filter, n, _check_filter, "filter", "image")
@@ -382,18 +380,9 @@ def filter_many(images, filter, device: int = 0, _path: str = "auto") -> list:
         for i, f in enumerate(filters):
             if f[0] != "window" and max(_halo(f[5])) > limit:
                 raise ValueError(f"image {i}: _path 'fused': the filter needs a halo of {max(_halo(f[5]))}, the fused kernel takes {limit}")
-    shapes = []
-    for i, a in enumerate(images):
-        shape, dt = tuple(getattr(a, "shape", ())), str(getattr(a, "dtype", None))
-        if not (len(shape) == 2 or (len(shape) == 3 and shape[2] in (2, 3, 4))) or shape[0] < 1 or shape[1] < 1:
-            raise ValueError(f"image {i}: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape {shape}")
-        if dt not in ("uint8", "torch.uint8"):
-            raise TypeError(f"image {i}: uint8 required, got {dt}")
-        if max(shape[:2]) > 65535:
-            raise ValueError(f"image {i}: sizes up to 65535 a side")
-        shapes.append(shape)
+    shapes = [image_shape(a, f"image {i}", 65535) for i, a in enumerate(images)]      # (after the filters: a call with both wrong names the filter)
     ctx = get_context(device)
-    t, lib = ctx.torch, ctx.lib
+    lib = ctx.lib
     # the sources: device tensors are read where they are; NumPy arrays and host tensors cross in one pinned copy
     src = gather_u8(ctx, images)
     base, span, src_off = src.span()
@@ -401,8 +390,10 @@ def filter_many(images, filter, device: int = 0, _path: str = "auto") -> list:
     window = [f[0] == "window" for f in filters]
     nw = sum(window)
     descs, wdescs = (FilterDesc * max(n - nw, 1))(), (WindowDesc * max(nw, 1))()
-    offsets, pos, kb, kw = [], 0, 0, 0
-    for i, (shape, f) in enumerate(zip(shapes, filters)):
+    out_shapes = [packed_shape(*s) for s in shapes]
+    out, offsets = packed_out(ctx, out_shapes)
+    kb, kw = 0, 0
+    for i, f in enumerate(filters):
         if window[i]:
             d, kw = wdescs[kw], kw + 1
             d.kind, d.size, d.rank, d.scale, d.offset = f[1:6]
@@ -410,23 +401,10 @@ def filter_many(images, filter, device: int = 0, _path: str = "auto") -> list:
         else:
             d, kb = descs[kb], kb + 1
             d.kind, d.xradius, d.yradius, d.percent, d.threshold = f[:5]
-        d.src_offset, d.dst_offset = src_off[i], pos
-        d.height, d.width, d.channels = shape[0], shape[1], shape[2] if len(shape) == 3 else 1
-        offsets.append(pos)
-        pos += src.nbytes[i]
-    out = ctx.empty((pos,), t.uint8)
+        d.src_offset, d.dst_offset = src_off[i], offsets[i]
+        d.height, d.width, d.channels = shapes[i]
     if n > nw:
-        path = PATHS[_path]
-        ws = ctx.workspace(max(int(lib.aej_filter_workspace_bytes(ctx.handle, ctypes.addressof(descs), n - nw, path)), 256))
-        ctx.check(lib.aej_filter_batch(ctx.handle, ctypes.addressof(descs), n - nw, path, ctypes.c_void_p(base), ctypes.c_uint64(span),
-                                       out.data_ptr(), ctypes.c_uint64(pos), ws.data_ptr(), ctypes.c_uint64(ws.numel())))
+        run_entry(ctx, lib.aej_filter_workspace_bytes, lib.aej_filter_batch, descs, n - nw, base, span, out, args=(PATHS[_path],))
     if nw:
-        ws = ctx.workspace(max(int(lib.aej_window_workspace_bytes(ctx.handle, ctypes.addressof(wdescs), nw)), 256))
-        ctx.check(lib.aej_window_batch(ctx.handle, ctypes.addressof(wdescs), nw, ctypes.c_void_p(base), ctypes.c_uint64(span),
-                                       out.data_ptr(), ctypes.c_uint64(pos), ws.data_ptr(), ctypes.c_uint64(ws.numel())))
-    res = packed_views(out, offsets, shapes)
-    for o, a in zip(res, images):
-        com = getattr(a, "jpeg_comment", None)
-        if com is not None:
-            o.jpeg_comment = com
-    return res
+        run_entry(ctx, lib.aej_window_workspace_bytes, lib.aej_window_batch, wdescs, nw, base, span, out)      # (either synchronises: src's staging is free again)
+    return packed_results(out, offsets, out_shapes, images)

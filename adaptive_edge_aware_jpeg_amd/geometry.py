@@ -19,9 +19,8 @@ import math
 
 import numpy as np
 
-from ._images import gather_u8, is_int, is_number, one_or_each, packed_views
+from ._images import MAX_SIDE, gather_u8, intake, is_int, is_number, one_or_each, packed_out, packed_results, packed_shape, run_entry
 
-MAX_SIDE = 32767
 RESAMPLE = {"nearest": 0, "lanczos": 1, "bilinear": 2, "bicubic": 3, "box": 4, "hamming": 5}      # Pillow's Image.Resampling
 TRANSFORMS = ("affine", "extent", "perspective", "quad", "mesh")                                 # Pillow's Image.Transform, by value
 TRANSPOSES = ("flip_left_right", "flip_top_bottom", "rotate_90", "rotate_180", "rotate_270", "transpose", "transverse")      # Image.Transpose
@@ -142,20 +141,6 @@ def _scalar(v):
     return not isinstance(v, (list, tuple))
 
 
-def _shapes(images):
-    shapes = []
-    for i, a in enumerate(images):
-        shape, dt = tuple(getattr(a, "shape", ())), str(getattr(a, "dtype", None))
-        if not (len(shape) == 2 or (len(shape) == 3 and shape[2] in (2, 3, 4))) or shape[0] < 1 or shape[1] < 1:
-            raise ValueError(f"image {i}: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape {shape}")
-        if dt not in ("uint8", "torch.uint8"):
-            raise TypeError(f"image {i}: uint8 required, got {dt}")
-        if max(shape[:2]) > MAX_SIDE:
-            raise ValueError(f"image {i}: sizes up to {MAX_SIDE} a side")
-        shapes.append(tuple(int(v) for v in shape))
-    return shapes
-
-
 def _fill_bytes(fill, channels, who):
     """what ``Image.new`` puts into every pixel: an int fills the first channel and leaves the others 0, alpha included"""
     if fill is None:
@@ -230,8 +215,7 @@ def _rotate(W, H, angle, expand, center, translate):
 def _job(shape, size, path, coef, resample, fill, premultiply, who, method=0):
     """the descriptor fields of one image, resolved by the library's host plan (aej_warp_plan_host): -> dict"""
     from ._lib import WarpDesc, WarpPlan, load_library
-    H, W = shape[:2]
-    C = shape[2] if len(shape) == 3 else 1
+    H, W, C = shape
     w, h = size
     if not (1 <= w <= MAX_SIDE and 1 <= h <= MAX_SIDE):
         raise ValueError(f"{who}: an output of {w} x {h}: sizes from 1 to {MAX_SIDE} a side")
@@ -250,7 +234,7 @@ def _job(shape, size, path, coef, resample, fill, premultiply, who, method=0):
                                   f"of the output): Pillow's float64 fallback is not built")
     if rc:
         raise ValueError(f"{who}: the transform was refused (code {rc})")
-    return dict(desc=d, plan=p, tables=tables, out_shape=(h, w) + tuple(shape[2:]))
+    return dict(desc=d, plan=p, tables=tables, out_shape=packed_shape(h, w, C))
 
 
 def transform_plan(W, H, size, method, data, resample="nearest", channels=3, premultiply=True):
@@ -266,8 +250,7 @@ def transform_plan(W, H, size, method, data, resample="nearest", channels=3, pre
     who = "transform_plan"
     size, method, data, resample = _check_size(size, who), _check_method(method, who), _check_data(data, who), _check_resample(resample, who)
     path, coef = _coefficients(method, data, size[0], size[1], who)
-    shape = (int(H), int(W)) + ((int(channels),) if channels > 1 else ())
-    j = _job(shape, size, path, coef, resample, None, premultiply, who)
+    j = _job((int(H), int(W), int(channels)), size, path, coef, resample, None, premultiply, who)
     p, w = j["plan"], size[0]
     tab = np.frombuffer(j["tables"], np.int32).copy()
     tables = PATHS[p.path] == "tables"
@@ -284,38 +267,21 @@ def warp_geometry():
     return dict(zip(("tile_w", "tile_h", "flip_bytes", "flip_rows", "swap_w", "swap_h"), (int(v) for v in g)))
 
 
-def _run(images, shapes, jobs, device):
+def _run(images, jobs, device):
     """the device part of the three calls: one gather, one packed output, one aej_warp_batch"""
     from ._lib import WarpDesc, get_context
     n = len(images)
     ctx = get_context(device)
-    t, lib = ctx.torch, ctx.lib
     src = gather_u8(ctx, images)
     base, span, src_off = src.span()
+    shapes = [j["out_shape"] for j in jobs]
+    out, offsets = packed_out(ctx, shapes)
     descs = (WarpDesc * n)()
-    offsets, pos = [], 0
     for i, j in enumerate(jobs):
         ctypes.memmove(ctypes.addressof(descs[i]), ctypes.addressof(j["desc"]), ctypes.sizeof(WarpDesc))
-        descs[i].src_offset, descs[i].dst_offset = src_off[i], pos
-        offsets.append(pos)
-        pos += int(math.prod(j["out_shape"]))
-    out = ctx.empty((pos,), t.uint8)
-    ws = ctx.workspace(max(int(lib.aej_warp_workspace_bytes(ctx.handle, ctypes.addressof(descs), n)), 256))
-    ctx.check(lib.aej_warp_batch(ctx.handle, ctypes.addressof(descs), n, ctypes.c_void_p(base), ctypes.c_uint64(span), out.data_ptr(),
-                                 ctypes.c_uint64(pos), ws.data_ptr(), ctypes.c_uint64(ws.numel())))      # synchronises: src's staging is free again
-    res = packed_views(out, offsets, [j["out_shape"] for j in jobs])
-    for o, a in zip(res, images):
-        com = getattr(a, "jpeg_comment", None)
-        if com is not None:
-            o.jpeg_comment = com
-    return res
-
-
-def _intake(images, name):
-    images = list(images)
-    if len(images) < 1:
-        raise ValueError(f"{name} needs at least one image")
-    return images, _shapes(images)
+        descs[i].src_offset, descs[i].dst_offset = src_off[i], offsets[i]
+    run_entry(ctx, ctx.lib.aej_warp_workspace_bytes, ctx.lib.aej_warp_batch, descs, n, base, span, out)      # synchronises: src's staging is free again
+    return packed_results(out, offsets, shapes, images)
 
 
 def transform_many(images, size, method, data, resample="nearest", fillcolor=None, premultiply=True, device: int = 0) -> list:
@@ -336,7 +302,7 @@ def transform_many(images, size, method, data, resample="nearest", fillcolor=Non
     of range or of another length than the channels; TypeError for a dtype other than uint8; NotImplementedError for "mesh", an
     ``ImageTransformHandler`` and an affine transform under "nearest" whose coordinates reach 32768 at a corner of the output
     (Pillow's float64 fallback is not built)."""
-    images, shapes = _intake(images, "transform_many")
+    images, shapes = intake(images, "transform_many")
     n = len(images)
     sizes = _each(size, n, _check_size, "size", lambda v: _flat(v) and len(v) == 2)
     methods = _each(method, n, _check_method, "method", _scalar)
@@ -349,7 +315,7 @@ def transform_many(images, size, method, data, resample="nearest", fillcolor=Non
         who = f"image {i}"
         path, coef = _coefficients(methods[i], datas[i], sizes[i][0], sizes[i][1], who)
         jobs.append(_job(shapes[i], sizes[i], path, coef, filters[i], fills[i], pre, who))
-    return _run(images, shapes, jobs, device)
+    return _run(images, jobs, device)
 
 
 def rotate_many(images, angle, resample="nearest", expand=False, center=None, translate=None, fillcolor=None, premultiply=True,
@@ -361,7 +327,7 @@ def rotate_many(images, angle, resample="nearest", expand=False, center=None, tr
     ``round(sin, 15)`` about the centre (default (w / 2, h / 2)), expand sizes the output by ``ceil(max) - floor(min)`` of the
     transformed corners, and the result is an AFFINE transform.  Every argument is one for all images or one per image.  The checks,
     the refusals and premultiply are transform_many's; ValueError also for an angle, center or translate that is not finite."""
-    images, shapes = _intake(images, "rotate_many")
+    images, shapes = intake(images, "rotate_many")
     n = len(images)
     angles = _each(angle, n, _check_angle, "angle", _scalar)
     filters = _each(resample, n, _check_resample, "resample", _scalar)
@@ -381,7 +347,7 @@ def rotate_many(images, angle, resample="nearest", expand=False, center=None, tr
             jobs.append(_job(shapes[i], (H, W) if plan[1] != 3 else (W, H), "transpose", [0.0] * 8, 0, None, pre, who, method=plan[1]))
         else:
             jobs.append(_job(shapes[i], plan[1], "affine", [float(v) for v in plan[2]] + [0.0, 0.0], filters[i], fills[i], pre, who))
-    return _run(images, shapes, jobs, device)
+    return _run(images, jobs, device)
 
 
 def transpose_many(images, method, device: int = 0) -> list:
@@ -389,7 +355,7 @@ def transpose_many(images, method, device: int = 0) -> list:
     .transpose(method_i))``.  method: one for all images or one per image, any of Pillow's seven ``Image.Transpose`` methods by name
     ("FLIP_LEFT_RIGHT", "FLIP_TOP_BOTTOM", "ROTATE_90", "ROTATE_180", "ROTATE_270", "TRANSPOSE", "TRANSVERSE"; any case) or value
     (0 .. 6).  The flips and ROTATE_180 are mirrored copies, the five others go through an LDS tile.  ValueError for an unknown method."""
-    images, shapes = _intake(images, "transpose_many")
+    images, shapes = intake(images, "transpose_many")
     n = len(images)
     methods = _each(method, n, _check_transpose, "method", _scalar)
     jobs = []
@@ -397,4 +363,4 @@ def transpose_many(images, method, device: int = 0) -> list:
         H, W = shapes[i][:2]
         swap = methods[i] in (2, 4, 5, 6)
         jobs.append(_job(shapes[i], (H, W) if swap else (W, H), "transpose", [0.0] * 8, 0, None, False, f"image {i}", method=methods[i]))
-    return _run(images, shapes, jobs, device)
+    return _run(images, jobs, device)

@@ -22,7 +22,7 @@ import math
 
 import numpy as np
 
-from ._images import gather_u8, is_int, is_number, one_or_each, packed_views
+from ._images import gather_u8, image_list, is_int, is_number, one_or_each, packed_views, run_entry
 from ._lib import get_context
 
 FILTERS = {"box": 4, "bilinear": 2, "hamming": 5, "bicubic": 3, "lanczos": 1}      # Pillow's Image.Resampling integers
@@ -172,10 +172,7 @@ def _run(ctx, src, src_bytes, src_off, steps, f, channels=None, windows=None, pa
     if windows is not None:
         cc, ww = np.array(ch, np.int32), np.ascontiguousarray(windows, np.int32)
         how, sfx = (cc.ctypes.data, ww.ctypes.data), "_win"
-    nws = int(getattr(lib, "aej_resample_workspace_bytes" + sfx)(ctx.handle, ctypes.addressof(descs), n, *how))
-    ws = ctx.workspace(max(nws, 256))
-    ctx.check(getattr(lib, "aej_resample_batch" + sfx)(ctx.handle, ctypes.addressof(descs), n, *how, ctypes.c_void_p(src), ctypes.c_uint64(src_bytes),
-                                                       out.data_ptr(), ctypes.c_uint64(pos), ws.data_ptr(), ctypes.c_uint64(ws.numel())))
+    run_entry(ctx, getattr(lib, "aej_resample_workspace_bytes" + sfx), getattr(lib, "aej_resample_batch" + sfx), descs, n, src, src_bytes, out, args=how)
     if packed:
         return out
     return packed_views(out, dst_off, [(s["dst"][1], s["dst"][0]) + ((3,) if c == 3 else ()) for s, c in zip(steps, ch)])
@@ -208,10 +205,8 @@ def resize_many(images, size, resample="bicubic", box=None, reducing_gap=None, d
     many times the size are first reduced by whole factors, as Pillow does.  Up-scaling is the same path.  Every argument is checked
     on the host before any device work and a refusal names the image; an image more than 100 times as tall as wide that is made
     shorter raises NotImplementedError."""
-    images = list(images)
+    images = image_list(images, "resize_many")
     n = len(images)
-    if n < 1:
-        raise ValueError("resize_many needs at least one image")
     f, gap = one_or_each(resample, n, _check_filter, "resample", "image"), _check_gap(reducing_gap, "every image")
     if not isinstance(mode, str) or mode not in ("RGB", "L", "auto"):
         raise ValueError(f"mode {mode!r}: 'RGB', 'L' or 'auto' required")

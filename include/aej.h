@@ -1024,7 +1024,9 @@ AEJ_API int aej_jfif_transform_batch_cut(aej_ctx *ctx, const aej_jpegdec_desc *d
  *   vertical: each one grid over every image that needs it) and one upload of the descriptors and tap tables, then waits for the
  *   upload; nothing is copied back.  Every descriptor is checked before any device work: AEJ_ERR_ARG naming the image for an unknown
  *   filter, a size below 1 or above 65535, a reduce factor below 1, an empty box or one outside the image, an image outside src_bytes
- *   / dst_bytes; AEJ_ERR_UNSUPPORTED naming the image for the tall one.  Workspace: aej_resample_workspace_bytes with the same descriptors (0 for descriptors the call refuses).
+ *   / dst_bytes, a source image that overlaps dst ("source inside the output": no source image may overlap the dst_bytes at dst,
+ *   as for aej_filter_batch and the entries after it; the _ch and _win calls alike.  Such a call read pixels it was overwriting; it
+ *   is refused since the entries share one span check); AEJ_ERR_UNSUPPORTED naming the image for the tall one.  Workspace: aej_resample_workspace_bytes with the same descriptors (0 for descriptors the call refuses).
  * aej_resample_batch_ch / aej_resample_workspace_bytes_ch: the same calls with channels_host [n], each 3 or 1 (anything else:
  *   AEJ_ERR_ARG naming the image, 0 bytes; NULL: every image 3): image i is uint8 [h][w][channels], packed -- 1 is Pillow's mode "L",
  *   the same reduce and passes on one channel (Pillow's mode-"L" resize equals one channel of its RGB resize of three copies).  The

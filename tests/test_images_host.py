@@ -110,3 +110,265 @@ def test_stage_layout_values():
     assert I.stage_layout([1, 3, 4, 5], [True] * 4) == ([0, 1, 4, 8], 13)
     assert I.stage_layout([1, 3, 4, 5], [True] * 4, 4) == ([0, 4, 8, 12], 20)
     assert I.stage_layout([1, 3, 4, 5], [True, False, True, True], align=4) == ([0, None, 4, 8], 16)
+
+
+# ---- the refusals of the packed-image calls' intake ------------------------------------------------------------------------------------
+# Every call, every place an image goes (the list, and for the two-image calls the second image and the mask), every fault below; the
+# other arguments are good.  All of them are refused on the host, before a context exists.
+def _view(shape, dtype=np.uint8):
+    return np.broadcast_to(np.zeros((), dtype), shape)      # costs no memory
+
+
+FAULTS = {"shape (4,)": lambda limit: _view((4,)),
+          "shape (4, 5, 1)": lambda limit: _view((4, 5, 1)),
+          "shape (4, 5, 5)": lambda limit: _view((4, 5, 5)),
+          "shape (2, 2, 3, 1)": lambda limit: _view((2, 2, 3, 1)),
+          "shape (0, 5, 3)": lambda limit: _view((0, 5, 3)),
+          "shape (4, 0)": lambda limit: _view((4, 0)),
+          "int16": lambda limit: _view((4, 5, 3), np.int16),
+          "float32": lambda limit: _view((4, 5, 3), np.float32),
+          "bool": lambda limit: _view((4, 5, 3), np.bool_),
+          "a side above the limit": lambda limit: _view((1, limit + 1))}
+
+
+def _calls():
+    """name -> (call(images, second, mask), side limit, channels of a good image, the places besides the list)"""
+    import adaptive_edge_aware_jpeg_amd as A
+    from adaptive_edge_aware_jpeg_amd import adjust, compose, filters, geometry
+    return {"filter_many": (lambda im, s, m: filters.filter_many(im, filters.MedianFilter(3)), 65535, 3, ()),
+            "transform_many": (lambda im, s, m: geometry.transform_many(im, (3, 2), "affine", (1, 0, 0, 0, 1, 0)), 32767, 3, ()),
+            "rotate_many": (lambda im, s, m: geometry.rotate_many(im, 30), 32767, 3, ()),
+            "transpose_many": (lambda im, s, m: geometry.transpose_many(im, "rotate_90"), 32767, 3, ()),
+            "adjust_many": (lambda im, s, m: adjust.adjust_many(im, adjust.Brightness(1.2)), 32767, 3, ()),
+            "histogram_many": (lambda im, s, m: adjust.histogram_many(im), 32767, 3, ()),
+            "paste_many": (lambda im, s, m: compose.paste_many(im, s, (0, 0), m), 32767, 3, ("second", "mask")),
+            "alpha_composite_many": (lambda im, s, m: compose.alpha_composite_many(im, s), 32767, 4, ("second",)),
+            "blend_many": (lambda im, s, m: compose.blend_many(im, s, 0.5), 32767, 3, ("second",)),
+            "composite_many": (lambda im, s, m: compose.composite_many(im, s, m), 32767, 3, ("second", "mask")),
+            "chop_many": (lambda im, s, m: compose.chop_many(im, s, "add"), 32767, 3, ("second",))}
+
+
+def _refusal(call, *args):
+    try:
+        call(*args)
+    except Exception as e:      # noqa: BLE001 (the table says which)
+        return type(e).__name__, str(e)
+    return None
+
+
+def intake_refusals():
+    """-> {"call / place / fault": (exception type name, message) or None}, in the table's order"""
+    got = {}
+    for name, (call, limit, channels, places) in _calls().items():
+        good, good_mask = _view((4, 5, channels)), _view((4, 5))
+        got[f"{name} / images / an empty list"] = _refusal(call, [], good, good_mask)
+        for fault, make in FAULTS.items():
+            got[f"{name} / images / {fault}"] = _refusal(call, [good, make(limit)], good, good_mask)
+            if "second" in places:
+                got[f"{name} / second / {fault}"] = _refusal(call, [good, good], [good, make(limit)], good_mask)
+            if "mask" in places:
+                got[f"{name} / mask / {fault}"] = _refusal(call, [good, good], good, [good_mask, make(limit)])
+    return got
+
+
+# recorded at the commit before _images.py took the intake over: the exception type and the whole message of every row
+INTAKE_REFUSALS = {
+    'filter_many / images / an empty list': ('ValueError', 'filter_many needs at least one image'),
+    'filter_many / images / shape (4,)': ('ValueError', 'image 1: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4,)'),
+    'filter_many / images / shape (4, 5, 1)': ('ValueError', 'image 1: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 5, 1)'),
+    'filter_many / images / shape (4, 5, 5)': ('ValueError', 'image 1: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 5, 5)'),
+    'filter_many / images / shape (2, 2, 3, 1)': ('ValueError', 'image 1: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (2, 2, 3, 1)'),
+    'filter_many / images / shape (0, 5, 3)': ('ValueError', 'image 1: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (0, 5, 3)'),
+    'filter_many / images / shape (4, 0)': ('ValueError', 'image 1: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 0)'),
+    'filter_many / images / int16': ('TypeError', 'image 1: uint8 required, got int16'),
+    'filter_many / images / float32': ('TypeError', 'image 1: uint8 required, got float32'),
+    'filter_many / images / bool': ('TypeError', 'image 1: uint8 required, got bool'),
+    'filter_many / images / a side above the limit': ('ValueError', 'image 1: sizes up to 65535 a side'),
+    'transform_many / images / an empty list': ('ValueError', 'transform_many needs at least one image'),
+    'transform_many / images / shape (4,)': ('ValueError', 'image 1: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4,)'),
+    'transform_many / images / shape (4, 5, 1)': ('ValueError', 'image 1: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 5, 1)'),
+    'transform_many / images / shape (4, 5, 5)': ('ValueError', 'image 1: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 5, 5)'),
+    'transform_many / images / shape (2, 2, 3, 1)': ('ValueError', 'image 1: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (2, 2, 3, 1)'),
+    'transform_many / images / shape (0, 5, 3)': ('ValueError', 'image 1: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (0, 5, 3)'),
+    'transform_many / images / shape (4, 0)': ('ValueError', 'image 1: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 0)'),
+    'transform_many / images / int16': ('TypeError', 'image 1: uint8 required, got int16'),
+    'transform_many / images / float32': ('TypeError', 'image 1: uint8 required, got float32'),
+    'transform_many / images / bool': ('TypeError', 'image 1: uint8 required, got bool'),
+    'transform_many / images / a side above the limit': ('ValueError', 'image 1: sizes up to 32767 a side'),
+    'rotate_many / images / an empty list': ('ValueError', 'rotate_many needs at least one image'),
+    'rotate_many / images / shape (4,)': ('ValueError', 'image 1: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4,)'),
+    'rotate_many / images / shape (4, 5, 1)': ('ValueError', 'image 1: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 5, 1)'),
+    'rotate_many / images / shape (4, 5, 5)': ('ValueError', 'image 1: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 5, 5)'),
+    'rotate_many / images / shape (2, 2, 3, 1)': ('ValueError', 'image 1: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (2, 2, 3, 1)'),
+    'rotate_many / images / shape (0, 5, 3)': ('ValueError', 'image 1: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (0, 5, 3)'),
+    'rotate_many / images / shape (4, 0)': ('ValueError', 'image 1: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 0)'),
+    'rotate_many / images / int16': ('TypeError', 'image 1: uint8 required, got int16'),
+    'rotate_many / images / float32': ('TypeError', 'image 1: uint8 required, got float32'),
+    'rotate_many / images / bool': ('TypeError', 'image 1: uint8 required, got bool'),
+    'rotate_many / images / a side above the limit': ('ValueError', 'image 1: sizes up to 32767 a side'),
+    'transpose_many / images / an empty list': ('ValueError', 'transpose_many needs at least one image'),
+    'transpose_many / images / shape (4,)': ('ValueError', 'image 1: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4,)'),
+    'transpose_many / images / shape (4, 5, 1)': ('ValueError', 'image 1: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 5, 1)'),
+    'transpose_many / images / shape (4, 5, 5)': ('ValueError', 'image 1: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 5, 5)'),
+    'transpose_many / images / shape (2, 2, 3, 1)': ('ValueError', 'image 1: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (2, 2, 3, 1)'),
+    'transpose_many / images / shape (0, 5, 3)': ('ValueError', 'image 1: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (0, 5, 3)'),
+    'transpose_many / images / shape (4, 0)': ('ValueError', 'image 1: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 0)'),
+    'transpose_many / images / int16': ('TypeError', 'image 1: uint8 required, got int16'),
+    'transpose_many / images / float32': ('TypeError', 'image 1: uint8 required, got float32'),
+    'transpose_many / images / bool': ('TypeError', 'image 1: uint8 required, got bool'),
+    'transpose_many / images / a side above the limit': ('ValueError', 'image 1: sizes up to 32767 a side'),
+    'adjust_many / images / an empty list': ('ValueError', 'adjust_many needs at least one image'),
+    'adjust_many / images / shape (4,)': ('ValueError', 'image 1: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4,)'),
+    'adjust_many / images / shape (4, 5, 1)': ('ValueError', 'image 1: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 5, 1)'),
+    'adjust_many / images / shape (4, 5, 5)': ('ValueError', 'image 1: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 5, 5)'),
+    'adjust_many / images / shape (2, 2, 3, 1)': ('ValueError', 'image 1: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (2, 2, 3, 1)'),
+    'adjust_many / images / shape (0, 5, 3)': ('ValueError', 'image 1: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (0, 5, 3)'),
+    'adjust_many / images / shape (4, 0)': ('ValueError', 'image 1: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 0)'),
+    'adjust_many / images / int16': ('TypeError', 'image 1: uint8 required, got int16'),
+    'adjust_many / images / float32': ('TypeError', 'image 1: uint8 required, got float32'),
+    'adjust_many / images / bool': ('NotImplementedError', "image 1: images of mode '1' (bool) are not built"),
+    'adjust_many / images / a side above the limit': ('ValueError', 'image 1: sizes up to 32767 a side'),
+    'histogram_many / images / an empty list': ('ValueError', 'histogram_many needs at least one image'),
+    'histogram_many / images / shape (4,)': ('ValueError', 'image 1: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4,)'),
+    'histogram_many / images / shape (4, 5, 1)': ('ValueError', 'image 1: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 5, 1)'),
+    'histogram_many / images / shape (4, 5, 5)': ('ValueError', 'image 1: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 5, 5)'),
+    'histogram_many / images / shape (2, 2, 3, 1)': ('ValueError', 'image 1: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (2, 2, 3, 1)'),
+    'histogram_many / images / shape (0, 5, 3)': ('ValueError', 'image 1: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (0, 5, 3)'),
+    'histogram_many / images / shape (4, 0)': ('ValueError', 'image 1: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 0)'),
+    'histogram_many / images / int16': ('TypeError', 'image 1: uint8 required, got int16'),
+    'histogram_many / images / float32': ('TypeError', 'image 1: uint8 required, got float32'),
+    'histogram_many / images / bool': ('NotImplementedError', "image 1: images of mode '1' (bool) are not built"),
+    'histogram_many / images / a side above the limit': ('ValueError', 'image 1: sizes up to 32767 a side'),
+    'paste_many / images / an empty list': ('ValueError', 'paste_many needs at least one image'),
+    'paste_many / images / shape (4,)': ('ValueError', 'image 1: image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4,)'),
+    'paste_many / second / shape (4,)': ('ValueError', 'image 1: overlay: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4,)'),
+    'paste_many / mask / shape (4,)': ('ValueError', 'image 1: mask: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4,)'),
+    'paste_many / images / shape (4, 5, 1)': ('ValueError', 'image 1: image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 5, 1)'),
+    'paste_many / second / shape (4, 5, 1)': ('ValueError', 'image 1: overlay: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 5, 1)'),
+    'paste_many / mask / shape (4, 5, 1)': ('ValueError', 'image 1: mask: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 5, 1)'),
+    'paste_many / images / shape (4, 5, 5)': ('ValueError', 'image 1: image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 5, 5)'),
+    'paste_many / second / shape (4, 5, 5)': ('ValueError', 'image 1: overlay: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 5, 5)'),
+    'paste_many / mask / shape (4, 5, 5)': ('ValueError', 'image 1: mask: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 5, 5)'),
+    'paste_many / images / shape (2, 2, 3, 1)': ('ValueError', 'image 1: image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (2, 2, 3, 1)'),
+    'paste_many / second / shape (2, 2, 3, 1)': ('ValueError', 'image 1: overlay: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (2, 2, 3, 1)'),
+    'paste_many / mask / shape (2, 2, 3, 1)': ('ValueError', 'image 1: mask: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (2, 2, 3, 1)'),
+    'paste_many / images / shape (0, 5, 3)': ('ValueError', 'image 1: image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (0, 5, 3)'),
+    'paste_many / second / shape (0, 5, 3)': ('ValueError', 'image 1: overlay: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (0, 5, 3)'),
+    'paste_many / mask / shape (0, 5, 3)': ('ValueError', 'image 1: mask: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (0, 5, 3)'),
+    'paste_many / images / shape (4, 0)': ('ValueError', 'image 1: image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 0)'),
+    'paste_many / second / shape (4, 0)': ('ValueError', 'image 1: overlay: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 0)'),
+    'paste_many / mask / shape (4, 0)': ('ValueError', 'image 1: mask: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 0)'),
+    'paste_many / images / int16': ('TypeError', 'image 1: image: uint8 required, got int16'),
+    'paste_many / second / int16': ('TypeError', 'image 1: overlay: uint8 required, got int16'),
+    'paste_many / mask / int16': ('TypeError', 'image 1: mask: uint8 required, got int16'),
+    'paste_many / images / float32': ('TypeError', 'image 1: image: uint8 required, got float32'),
+    'paste_many / second / float32': ('TypeError', 'image 1: overlay: uint8 required, got float32'),
+    'paste_many / mask / float32': ('TypeError', 'image 1: mask: uint8 required, got float32'),
+    'paste_many / images / bool': ('NotImplementedError', "image 1: images of mode '1' (bool) are not built"),
+    'paste_many / second / bool': ('NotImplementedError', "image 1: overlays of mode '1' (bool) are not built"),
+    'paste_many / mask / bool': ('ValueError', 'image 1: mask: a bool mask is [h, w] with sizes from 1 to 32767, got shape (4, 5, 3)'),
+    'paste_many / images / a side above the limit': ('ValueError', 'image 1: image: sizes up to 32767 a side'),
+    'paste_many / second / a side above the limit': ('ValueError', 'image 1: overlay: sizes up to 32767 a side'),
+    'paste_many / mask / a side above the limit': ('ValueError', 'image 1: mask: sizes up to 32767 a side'),
+    'alpha_composite_many / images / an empty list': ('ValueError', 'alpha_composite_many needs at least one image'),
+    'alpha_composite_many / images / shape (4,)': ('ValueError', 'image 1: image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4,)'),
+    'alpha_composite_many / second / shape (4,)': ('ValueError', 'image 1: overlay: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4,)'),
+    'alpha_composite_many / images / shape (4, 5, 1)': ('ValueError', 'image 1: image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 5, 1)'),
+    'alpha_composite_many / second / shape (4, 5, 1)': ('ValueError', 'image 1: overlay: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 5, 1)'),
+    'alpha_composite_many / images / shape (4, 5, 5)': ('ValueError', 'image 1: image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 5, 5)'),
+    'alpha_composite_many / second / shape (4, 5, 5)': ('ValueError', 'image 1: overlay: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 5, 5)'),
+    'alpha_composite_many / images / shape (2, 2, 3, 1)': ('ValueError', 'image 1: image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (2, 2, 3, 1)'),
+    'alpha_composite_many / second / shape (2, 2, 3, 1)': ('ValueError', 'image 1: overlay: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (2, 2, 3, 1)'),
+    'alpha_composite_many / images / shape (0, 5, 3)': ('ValueError', 'image 1: image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (0, 5, 3)'),
+    'alpha_composite_many / second / shape (0, 5, 3)': ('ValueError', 'image 1: overlay: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (0, 5, 3)'),
+    'alpha_composite_many / images / shape (4, 0)': ('ValueError', 'image 1: image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 0)'),
+    'alpha_composite_many / second / shape (4, 0)': ('ValueError', 'image 1: overlay: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 0)'),
+    'alpha_composite_many / images / int16': ('TypeError', 'image 1: image: uint8 required, got int16'),
+    'alpha_composite_many / second / int16': ('TypeError', 'image 1: overlay: uint8 required, got int16'),
+    'alpha_composite_many / images / float32': ('TypeError', 'image 1: image: uint8 required, got float32'),
+    'alpha_composite_many / second / float32': ('TypeError', 'image 1: overlay: uint8 required, got float32'),
+    'alpha_composite_many / images / bool': ('NotImplementedError', "image 1: images of mode '1' (bool) are not built"),
+    'alpha_composite_many / second / bool': ('NotImplementedError', "image 1: overlays of mode '1' (bool) are not built"),
+    'alpha_composite_many / images / a side above the limit': ('ValueError', 'image 1: image: sizes up to 32767 a side'),
+    'alpha_composite_many / second / a side above the limit': ('ValueError', 'image 1: overlay: sizes up to 32767 a side'),
+    'blend_many / images / an empty list': ('ValueError', 'blend_many needs at least one image'),
+    'blend_many / images / shape (4,)': ('ValueError', 'image 1: image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4,)'),
+    'blend_many / second / shape (4,)': ('ValueError', 'image 1: second image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4,)'),
+    'blend_many / images / shape (4, 5, 1)': ('ValueError', 'image 1: image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 5, 1)'),
+    'blend_many / second / shape (4, 5, 1)': ('ValueError', 'image 1: second image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 5, 1)'),
+    'blend_many / images / shape (4, 5, 5)': ('ValueError', 'image 1: image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 5, 5)'),
+    'blend_many / second / shape (4, 5, 5)': ('ValueError', 'image 1: second image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 5, 5)'),
+    'blend_many / images / shape (2, 2, 3, 1)': ('ValueError', 'image 1: image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (2, 2, 3, 1)'),
+    'blend_many / second / shape (2, 2, 3, 1)': ('ValueError', 'image 1: second image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (2, 2, 3, 1)'),
+    'blend_many / images / shape (0, 5, 3)': ('ValueError', 'image 1: image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (0, 5, 3)'),
+    'blend_many / second / shape (0, 5, 3)': ('ValueError', 'image 1: second image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (0, 5, 3)'),
+    'blend_many / images / shape (4, 0)': ('ValueError', 'image 1: image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 0)'),
+    'blend_many / second / shape (4, 0)': ('ValueError', 'image 1: second image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 0)'),
+    'blend_many / images / int16': ('TypeError', 'image 1: image: uint8 required, got int16'),
+    'blend_many / second / int16': ('TypeError', 'image 1: second image: uint8 required, got int16'),
+    'blend_many / images / float32': ('TypeError', 'image 1: image: uint8 required, got float32'),
+    'blend_many / second / float32': ('TypeError', 'image 1: second image: uint8 required, got float32'),
+    'blend_many / images / bool': ('NotImplementedError', "image 1: images of mode '1' (bool) are not built"),
+    'blend_many / second / bool': ('NotImplementedError', "image 1: second images of mode '1' (bool) are not built"),
+    'blend_many / images / a side above the limit': ('ValueError', 'image 1: image: sizes up to 32767 a side'),
+    'blend_many / second / a side above the limit': ('ValueError', 'image 1: second image: sizes up to 32767 a side'),
+    'composite_many / images / an empty list': ('ValueError', 'composite_many needs at least one image'),
+    'composite_many / images / shape (4,)': ('ValueError', 'image 1: image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4,)'),
+    'composite_many / second / shape (4,)': ('ValueError', 'image 1: second image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4,)'),
+    'composite_many / mask / shape (4,)': ('ValueError', 'image 1: mask: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4,)'),
+    'composite_many / images / shape (4, 5, 1)': ('ValueError', 'image 1: image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 5, 1)'),
+    'composite_many / second / shape (4, 5, 1)': ('ValueError', 'image 1: second image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 5, 1)'),
+    'composite_many / mask / shape (4, 5, 1)': ('ValueError', 'image 1: mask: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 5, 1)'),
+    'composite_many / images / shape (4, 5, 5)': ('ValueError', 'image 1: image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 5, 5)'),
+    'composite_many / second / shape (4, 5, 5)': ('ValueError', 'image 1: second image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 5, 5)'),
+    'composite_many / mask / shape (4, 5, 5)': ('ValueError', 'image 1: mask: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 5, 5)'),
+    'composite_many / images / shape (2, 2, 3, 1)': ('ValueError', 'image 1: image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (2, 2, 3, 1)'),
+    'composite_many / second / shape (2, 2, 3, 1)': ('ValueError', 'image 1: second image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (2, 2, 3, 1)'),
+    'composite_many / mask / shape (2, 2, 3, 1)': ('ValueError', 'image 1: mask: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (2, 2, 3, 1)'),
+    'composite_many / images / shape (0, 5, 3)': ('ValueError', 'image 1: image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (0, 5, 3)'),
+    'composite_many / second / shape (0, 5, 3)': ('ValueError', 'image 1: second image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (0, 5, 3)'),
+    'composite_many / mask / shape (0, 5, 3)': ('ValueError', 'image 1: mask: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (0, 5, 3)'),
+    'composite_many / images / shape (4, 0)': ('ValueError', 'image 1: image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 0)'),
+    'composite_many / second / shape (4, 0)': ('ValueError', 'image 1: second image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 0)'),
+    'composite_many / mask / shape (4, 0)': ('ValueError', 'image 1: mask: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 0)'),
+    'composite_many / images / int16': ('TypeError', 'image 1: image: uint8 required, got int16'),
+    'composite_many / second / int16': ('TypeError', 'image 1: second image: uint8 required, got int16'),
+    'composite_many / mask / int16': ('TypeError', 'image 1: mask: uint8 required, got int16'),
+    'composite_many / images / float32': ('TypeError', 'image 1: image: uint8 required, got float32'),
+    'composite_many / second / float32': ('TypeError', 'image 1: second image: uint8 required, got float32'),
+    'composite_many / mask / float32': ('TypeError', 'image 1: mask: uint8 required, got float32'),
+    'composite_many / images / bool': ('NotImplementedError', "image 1: images of mode '1' (bool) are not built"),
+    'composite_many / second / bool': ('NotImplementedError', "image 1: second images of mode '1' (bool) are not built"),
+    'composite_many / mask / bool': ('ValueError', 'image 1: mask: a bool mask is [h, w] with sizes from 1 to 32767, got shape (4, 5, 3)'),
+    'composite_many / images / a side above the limit': ('ValueError', 'image 1: image: sizes up to 32767 a side'),
+    'composite_many / second / a side above the limit': ('ValueError', 'image 1: second image: sizes up to 32767 a side'),
+    'composite_many / mask / a side above the limit': ('ValueError', 'image 1: mask: sizes up to 32767 a side'),
+    'chop_many / images / an empty list': ('ValueError', 'chop_many needs at least one image'),
+    'chop_many / images / shape (4,)': ('ValueError', 'image 1: image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4,)'),
+    'chop_many / second / shape (4,)': ('ValueError', 'image 1: second image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4,)'),
+    'chop_many / images / shape (4, 5, 1)': ('ValueError', 'image 1: image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 5, 1)'),
+    'chop_many / second / shape (4, 5, 1)': ('ValueError', 'image 1: second image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 5, 1)'),
+    'chop_many / images / shape (4, 5, 5)': ('ValueError', 'image 1: image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 5, 5)'),
+    'chop_many / second / shape (4, 5, 5)': ('ValueError', 'image 1: second image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 5, 5)'),
+    'chop_many / images / shape (2, 2, 3, 1)': ('ValueError', 'image 1: image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (2, 2, 3, 1)'),
+    'chop_many / second / shape (2, 2, 3, 1)': ('ValueError', 'image 1: second image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (2, 2, 3, 1)'),
+    'chop_many / images / shape (0, 5, 3)': ('ValueError', 'image 1: image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (0, 5, 3)'),
+    'chop_many / second / shape (0, 5, 3)': ('ValueError', 'image 1: second image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (0, 5, 3)'),
+    'chop_many / images / shape (4, 0)': ('ValueError', 'image 1: image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 0)'),
+    'chop_many / second / shape (4, 0)': ('ValueError', 'image 1: second image: uint8 [H, W], [H, W, 2], [H, W, 3] or [H, W, 4] with at least one pixel required, got shape (4, 0)'),
+    'chop_many / images / int16': ('TypeError', 'image 1: image: uint8 required, got int16'),
+    'chop_many / second / int16': ('TypeError', 'image 1: second image: uint8 required, got int16'),
+    'chop_many / images / float32': ('TypeError', 'image 1: image: uint8 required, got float32'),
+    'chop_many / second / float32': ('TypeError', 'image 1: second image: uint8 required, got float32'),
+    'chop_many / images / bool': ('NotImplementedError', "image 1: images of mode '1' (bool) are not built"),
+    'chop_many / second / bool': ('NotImplementedError', "image 1: second images of mode '1' (bool) are not built"),
+    'chop_many / images / a side above the limit': ('ValueError', 'image 1: image: sizes up to 32767 a side'),
+    'chop_many / second / a side above the limit': ('ValueError', 'image 1: second image: sizes up to 32767 a side'),
+}
+
+
+def test_intake_refusals_are_the_recorded_ones():
+    got = intake_refusals()
+    assert list(got) == list(INTAKE_REFUSALS)
+    wrong = {k: (got[k], INTAKE_REFUSALS[k]) for k in got if got[k] != INTAKE_REFUSALS[k]}
+    assert not wrong, wrong
