@@ -144,10 +144,11 @@ def _steps(what, W, H, size, box, f, gap):
 
 
 def _run(ctx, src, src_bytes, src_off, steps, f, channels=None, windows=None, packed=False):
-    """aej_resample_batch over the images at src + src_off[i] -> list of uint8 [h, w, 3] views into one packed allocation.
-    f: one filter per image.  channels (None: every image 3): 3 or 1 per image; with a 1 among them the call is aej_resample_batch_ch
-    and that image's view is [h, w].  windows (int32 [n, 4] x0, y0, vw, vh; None: none): aej_resample_batch_win -- step i's src is the
-    stored rectangle at (x0, y0) of a virtual vw x vh image in whose coordinates its boxes are.  packed: -> the packed allocation itself."""
+    """aej_resample_batch_win over the images at src + src_off[i] -> list of uint8 [h, w, 3] views into one packed allocation.
+    f: one filter per image.  channels (None: every image 3): 3 or 1 per image; an image with 1 comes back as [h, w].  windows (int32
+    [n, 4] x0, y0, vw, vh; None: none): step i's src is the stored rectangle at (x0, y0) of a virtual vw x vh image in whose
+    coordinates its boxes are.  The entry takes NULL channels when every image has 3 and NULL windows when there are none, and is then
+    aej_resample_batch_ch / aej_resample_batch (include/aej.h).  packed: -> the packed allocation itself."""
     from ._lib import ResampleDesc
     t, lib, n = ctx.torch, ctx.lib, len(steps)
     descs = (ResampleDesc * n)()
@@ -165,14 +166,10 @@ def _run(ctx, src, src_bytes, src_off, steps, f, channels=None, windows=None, pa
         dst_off.append(pos)
         pos += d.dst_w * d.dst_h * ch[i]
     out = ctx.empty((pos,), t.uint8)
-    how, sfx = (), ""
-    if any(c != 3 for c in ch):                      # every image RGB: the entries without channels, as before
-        cc = np.array(ch, np.int32)
-        how, sfx = (cc.ctypes.data,), "_ch"
-    if windows is not None:
-        cc, ww = np.array(ch, np.int32), np.ascontiguousarray(windows, np.int32)
-        how, sfx = (cc.ctypes.data, ww.ctypes.data), "_win"
-    run_entry(ctx, getattr(lib, "aej_resample_workspace_bytes" + sfx), getattr(lib, "aej_resample_batch" + sfx), descs, n, src, src_bytes, out, args=how)
+    cc = np.array(ch, np.int32) if any(c != 3 for c in ch) else None
+    ww = None if windows is None else np.ascontiguousarray(windows, np.int32)
+    run_entry(ctx, lib.aej_resample_workspace_bytes_win, lib.aej_resample_batch_win, descs, n, src, src_bytes, out,
+              args=(None if cc is None else cc.ctypes.data, None if ww is None else ww.ctypes.data))
     if packed:
         return out
     return packed_views(out, dst_off, [(s["dst"][1], s["dst"][0]) + ((3,) if c == 3 else ()) for s, c in zip(steps, ch)])

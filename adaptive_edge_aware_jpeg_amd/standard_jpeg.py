@@ -10,8 +10,9 @@ coefficients, and so the decoded pixels, are those of the baseline file.  The de
 complete progressive file -- on the device, pixel-identical to ``Image.open(file).convert("RGB")`` (csrc/jpegdec.hip, ``aej_jpegdec_*``;
 csrc/jpegprog.hip, ``aej_jpegprog_*``).  With ``scale=2``, ``4`` or ``8`` (one value, or one per file) a file is decoded at that fraction of
 its size straight from its coefficients, through libjpeg's reduced inverse DCTs: the ``[ceil(H / s), ceil(W / s), 3]`` pixels Pillow
-returns once ``Image.draft()`` has chosen scale ``s`` -- what ``Image.thumbnail()`` starts from (``aej_jpegdec_batch_scaled``,
-``aej_jpegprog_batch_scaled``; one fused kernel, csrc/jpegdec.hip ``k_jd_scaled``).  ``draft_scale`` is ``draft()``'s choice of that
+returns once ``Image.draft()`` has chosen scale ``s`` -- what ``Image.thumbnail()`` starts from (the ``scales_host`` of
+``aej_jpegdec_batch_adobe`` / ``aej_jpegprog_batch_adobe``, the one decoder entry per kind that every keyword here goes through; one
+fused kernel, csrc/jpegdec.hip ``k_jd_scaled``).  ``draft_scale`` is ``draft()``'s choice of that
 scale for a requested size.
 
 ``standard_jpeg_thumbnail_many`` finishes that line: ``Image.thumbnail`` on JPEG files, on the device, pixel-identical to Pillow -- the
@@ -23,23 +24,23 @@ file size, on the host.  ``resize_many`` (resample.py) is ``Image.resize`` itsel
 ``mode="L"`` / ``"auto"`` (one value, or one per file) on the decode and on both thumbnail calls is Pillow's mode "L" on the pixel side:
 a one-component file comes back as ``[h, w]``, and under ``"L"`` so does a colour file, as its luma plane alone -- what Pillow gives after
 ``im.draft("L", size)`` makes libjpeg set ``out_color_space = JCS_GRAYSCALE``: no chroma IDCT, no up-sampling, no colour conversion, and
-not ``convert("L")``, from which it differs by several levels (``aej_jpegdec_batch_mode``, ``aej_jpegprog_batch_mode``; one kernel at
+not ``convert("L")``, from which it differs by several levels (the same entries' ``components_host``; one kernel at
 every scale, csrc/jpegdec.hip ``k_jd_luma``).  ``resize_many(mode="L" / "auto")`` takes ``[H, W]`` images, alone or beside ``[H, W, 3]`` ones
-(``aej_resample_batch_ch``), and ``standard_jpeg_thumbnail_jpeg_many(mode="auto")`` writes a grey source's thumbnail as the
+(the ``channels_host`` of ``aej_resample_batch_win``), and ``standard_jpeg_thumbnail_jpeg_many(mode="auto")`` writes a grey source's thumbnail as the
 one-component file Pillow saves.  ``"RGB"``, the default, is every call as it always was.
 
 ``standard_jpeg_transcode_many`` joins the two without touching a pixel: it Huffman-decodes existing files to their quantised
 coefficients on the device and entropy-codes the same coefficients again, as a baseline file under the file's own optimal Huffman
-tables or as the ten-scan progressive file (csrc/jfiftrans.hip, ``aej_jfif_transcode_*``) -- what ``jpegtran -optimize`` and
-``jpegtran -progressive`` do.  The output keeps the source's quantisation tables, component ids, sampling and JFIF density, drops its
+tables or as the ten-scan progressive file (csrc/jfiftrans.hip; ``aej_jfif_transform_*_cut`` with no transform, crop or chroma
+drop) -- what ``jpegtran -optimize`` and ``jpegtran -progressive`` do.  The output keeps the source's quantisation tables, component ids, sampling and JFIF density, drops its
 restart markers, and with ``keep_metadata=True`` carries its APP1..APP13, APP15 and COM segments over (spliced on the host).  A
 Pillow file transcoded this way equals Pillow's own ``optimize=True`` / ``progressive=True`` file of the same pixels byte for byte.
 ``standard_jpeg_transform_many`` is the same call with a lossless flip, rotation or transposition of every file on the way, by name or
-from the EXIF Orientation tag (``jpegtran -flip / -rotate / -transpose``, ``exiftran -a``; ``aej_jfif_transform_*``).  Both take
+from the EXIF Orientation tag (``jpegtran -flip / -rotate / -transpose``, ``exiftran -a``; ``aej_jfif_transform_*_cut``).  Both take
 one-component (grey) files too when ``grey=True`` is passed.
 
 ``standard_jpeg_encode_many`` is the encoder for images of mixed sizes, each with its own quality, in one call: one front-end kernel over
-every block of every image, then one entropy chain per distinct size (csrc/jfifmany.hip, ``aej_jfif_many_*``); the files are those
+every block of every image, then one entropy chain per distinct size (csrc/jfifmany.hip, ``aej_jfif_many_*_rst``); the files are those
 ``standard_jpeg_many`` writes for each image alone; with ``mode="L"`` / ``"auto"`` it also writes the one-component files Pillow saves
 for mode-"L" images, from ``[H, W]`` planes.  ``standard_jpeg_thumbnail_jpeg_many`` puts it behind
 ``standard_jpeg_thumbnail_many``: JPEG bytes in, smaller JPEG bytes out, the pixels never leaving the device.
@@ -174,6 +175,27 @@ def _values_u8(ctx, x):
     return t.round(xf * t.full((), 255.0, dtype=t.float32, device=ctx.device)).to(t.uint8)
 
 
+def _sized_call(ctx, call, cap, total, offsets, lengths):
+    """The capacity retry of the entries that write files: call(out, cap) with `out` a device uint8 buffer of the guessed capacity `cap`
+    (None for cap 0: the sizes alone); on AEJ_ERR_CAPACITY with the entry's `total` above cap once more with exactly that many bytes; then
+    ctx.check.  -> (out, the files' offsets in it, their lengths), the two on the host as int64 arrays"""
+    from ._lib import AEJ_ERR_CAPACITY
+    out = ctx.empty((cap,), ctx.torch.uint8) if cap else None
+    rc = call(out, cap)
+    if rc == AEJ_ERR_CAPACITY and total.value > cap:
+        cap = int(total.value)
+        out = ctx.empty((cap,), ctx.torch.uint8)
+        rc = call(out, cap)
+    ctx.check(rc)
+    return out, offsets.cpu().numpy(), lengths.cpu().numpy()
+
+
+def _file_bytes(out, offsets, lengths) -> List[bytes]:
+    """_sized_call's result read back in one copy -> the files, in the order of `offsets`"""
+    blob = out[:int((offsets + lengths).max())].cpu().numpy().tobytes()
+    return [blob[o:o + n] for o, n in zip(offsets.tolist(), lengths.tolist())]
+
+
 class _Encoded:
     """One aej_jfif_encode_batch: the workspace (it holds the coefficients the reconstruction reads), lengths [Q, B], optional bytes."""
 
@@ -193,30 +215,23 @@ class _Encoded:
         q = np.array(self.qualities, np.int32)
         offsets, lengths = ctx.empty((Q * B,), t.int64), ctx.empty((Q * B,), t.int64)
         total = ctypes.c_uint64()
-        out, cap = None, 0
+        cap = 0
         if want_bytes:
             hdr = PROGRESSIVE_HEADER_CAPACITY if prog else HEADER_CAPACITY
             cap = Q * B * (hdr + H * W * 3 // (4 if ss == 2 else 2))      # most files are far smaller; a miss costs one more call
-            out = ctx.empty((cap,), t.uint8)
         encode = lib.aej_jfif_encode_batch_prog if prog else lib.aej_jfif_encode_batch_opt
-        args = lambda o, c: (ctx.handle, x_u8.data_ptr(), B, H, W, Q, q.ctypes.data, ss, *(() if prog else (opt,)),  # noqa: E731
-                             o.data_ptr() if o is not None else None,
-                             ctypes.c_uint64(c), offsets.data_ptr(), lengths.data_ptr(), ctypes.addressof(total), self.ws.data_ptr(),
-                             ctypes.c_uint64(nbytes))
-        rc = encode(*args(out, cap))
-        if rc == -4 and out is not None and total.value > cap:        # AEJ_ERR_CAPACITY: run again with the exact size
-            cap = int(total.value)
-            out = ctx.empty((cap,), t.uint8)
-            rc = encode(*args(out, cap))
-        ctx.check(rc)
-        self.lengths = lengths.cpu().numpy().reshape(Q, B)
-        self.offsets = offsets.cpu().numpy().reshape(Q, B)
-        self.out = out
+        call = lambda o, c: encode(ctx.handle, x_u8.data_ptr(), B, H, W, Q, q.ctypes.data, ss, *(() if prog else (opt,)),  # noqa: E731
+                                   o.data_ptr() if o is not None else None,
+                                   ctypes.c_uint64(c), offsets.data_ptr(), lengths.data_ptr(), ctypes.addressof(total), self.ws.data_ptr(),
+                                   ctypes.c_uint64(nbytes))
+        self.out, host_off, host_len = _sized_call(ctx, call, cap, total, offsets, lengths)
+        self.lengths, self.offsets = host_len.reshape(Q, B), host_off.reshape(Q, B)
 
     def files(self) -> List[List[bytes]]:
         """[quality][image] bytes"""
-        blob = self.out[:int(self.lengths.sum())].cpu().numpy().tobytes()
-        return [[blob[o:o + n] for o, n in zip(orow, nrow)] for orow, nrow in zip(self.offsets.tolist(), self.lengths.tolist())]
+        B = self.B
+        flat = _file_bytes(self.out, self.offsets.reshape(-1), self.lengths.reshape(-1))
+        return [flat[k:k + B] for k in range(0, len(flat), B)]
 
     def decoded(self):
         """device uint8 [Q, B, H, W, 3]: what Pillow's decoder returns for every file"""
@@ -289,43 +304,43 @@ def _raise_status(bad):
 
 
 def parse_header(data, index: int = 0, layout_440: bool = False, adobe: bool = False):
-    """aej_jpegdec_parse_host: the JpegDecDesc of one file's markers (host only).  Raises NotImplementedError for a valid file outside
-    the supported set and ValueError for a malformed header, both naming the file index.  layout_440=True (aej_jpegdec_parse_host_440)
-    also takes a three-component file whose luma is sampled 1 x 2 over 1 x 1 chroma (4:4:0: hs = 1, vs = 2); without it such a file is
-    refused as before.  adobe=True (aej_jpegdec_parse_host_adobe) also takes four-component (CMYK, YCCK) and RGB-coded files, refused
-    as before without it; the descriptor then carries two more attributes: ``adobe``, the file's JpegAdobe (component 3's factors and
-    tables), and ``colour``, one of "YCbCr", "RGB", "CMYK", "YCCK"."""
+    """aej_jpegdec_parse_host_440: the JpegDecDesc of one file's markers (host only).  Raises NotImplementedError for a valid file
+    outside the supported set and ValueError for a malformed header, both naming the file index.  layout_440=True (the entry's
+    layout_440 = 1) also takes a three-component file whose luma is sampled 1 x 2 over 1 x 1 chroma (4:4:0: hs = 1, vs = 2); without it
+    such a file is refused.  adobe=True (aej_jpegdec_parse_host_adobe, whose parser accepts files the other refuses) also takes
+    four-component (CMYK, YCCK) and RGB-coded files, refused without it; the descriptor then carries two more attributes: ``adobe``,
+    the file's JpegAdobe (component 3's factors and tables), and ``colour``, one of "YCbCr", "RGB", "CMYK", "YCCK"."""
     from ._lib import JPEG_COLOURS, JpegAdobe, JpegDecDesc, load_library
     buf, n = _buffer(data)
     d, msg = JpegDecDesc(), ctypes.create_string_buffer(256)
     head = (ctypes.addressof(buf), n, ctypes.addressof(d), ctypes.addressof(msg), 256)
     lib = load_library()
-    if _check_bool("adobe", adobe):
+    adobe, l440 = _check_bool("adobe", adobe), int(_check_bool("layout_440", layout_440))
+    if adobe:
         x = JpegAdobe()
-        _refuse(lib.aej_jpegdec_parse_host_adobe(*head[:3], ctypes.addressof(x), *head[3:], int(_check_bool("layout_440", layout_440))), msg, index)
+        _refuse(lib.aej_jpegdec_parse_host_adobe(*head[:3], ctypes.addressof(x), *head[3:], l440), msg, index)
         d.adobe, d.colour = x, JPEG_COLOURS[x.colour]
         return d
-    _refuse(lib.aej_jpegdec_parse_host_440(*head, 1) if _check_bool("layout_440", layout_440) else lib.aej_jpegdec_parse_host(*head), msg, index)
+    _refuse(lib.aej_jpegdec_parse_host_440(*head, l440), msg, index)
     return d
 
 
 def parse_scans(data, index: int = 0, layout_440: bool = False, adobe: bool = False):
-    """aej_jpegprog_parse_host: (JpegProgFrame, [JpegProgScan, ...]) of one progressive (SOF2) file, every marker SOI .. EOI walked on
-    the host.  Raises ValueError for a malformed file or a scan script that violates T.81 G.1.1.1 and NotImplementedError for a valid
+    """aej_jpegprog_parse_host_440: (JpegProgFrame, [JpegProgScan, ...]) of one progressive (SOF2) file, every marker SOI .. EOI walked
+    on the host.  Raises ValueError for a malformed file or a scan script that violates T.81 G.1.1.1 and NotImplementedError for a valid
     file outside the supported set (an incomplete progression, arithmetic coding, a file that is not progressive, ...), both naming the
-    file index.  layout_440: as parse_header (aej_jpegprog_parse_host_440).  adobe: as parse_header (aej_jpegprog_parse_host_adobe);
-    the frame then carries ``adobe`` and ``colour``."""
+    file index.  layout_440: as parse_header (the entry's layout_440).  adobe: as parse_header (aej_jpegprog_parse_host_adobe); the
+    frame then carries ``adobe`` and ``colour``."""
     from ._lib import JPEG_COLOURS, JpegAdobe, JpegProgFrame, JpegProgScan, load_library
     lib = load_library()
     buf, n = _buffer(data)
     frame, msg = JpegProgFrame(), ctypes.create_string_buffer(256)
-    if _check_bool("adobe", adobe):
-        x, l440 = JpegAdobe(), int(_check_bool("layout_440", layout_440))
+    adobe, l440 = _check_bool("adobe", adobe), int(_check_bool("layout_440", layout_440))
+    if adobe:
+        x = JpegAdobe()
         parse = lambda d, m, f, sc, cap, ms, mc: lib.aej_jpegprog_parse_host_adobe(d, m, f, sc, cap, ctypes.addressof(x), ms, mc, l440)  # noqa: E731
-    elif _check_bool("layout_440", layout_440):
-        parse = lambda *a: lib.aej_jpegprog_parse_host_440(*a, 1)  # noqa: E731
     else:
-        parse = lib.aej_jpegprog_parse_host
+        parse = lambda *a: lib.aej_jpegprog_parse_host_440(*a, l440)  # noqa: E731
     _refuse(parse(ctypes.addressof(buf), n, ctypes.addressof(frame), None, 0, ctypes.addressof(msg), 256), msg, index)
     scans = (JpegProgScan * max(frame.n_scans, 1))()
     _refuse(parse(ctypes.addressof(buf), n, ctypes.addressof(frame), ctypes.addressof(scans), frame.n_scans, ctypes.addressof(msg), 256), msg, index)
@@ -335,8 +350,9 @@ def parse_scans(data, index: int = 0, layout_440: bool = False, adobe: bool = Fa
 
 
 def _parse_sources(files, progressive=True, transcoder=False, start=0, grey=False, layout_440=False, adobe=False):
-    """Parse every file once, telling baseline from progressive: yields (i, is_progressive, JpegDecDesc | (JpegProgFrame, scans), view)
-    file by file, i counting from start.  progressive=False refuses progressive files the way standard_jpeg_decode_many does without
+    """Parse every file once, telling baseline from progressive: yields (i, is_progressive, JpegDecDesc | (JpegProgFrame, scans), the
+    frame -- that descriptor, or that JpegProgFrame --, view) file by file, i counting from start.  progressive=False refuses
+    progressive files the way standard_jpeg_decode_many does without
     its keyword; transcoder=True refuses what the transcoder does not take, which without grey=True includes one-component files.
     layout_440=True, adobe=True: the parsers' keywords of those names, for every file.  Every refusal names the file."""
     for i, f in enumerate(files, start):
@@ -353,7 +369,41 @@ def _parse_sources(files, progressive=True, transcoder=False, start=0, grey=Fals
             raise NotImplementedError(f"file {i}: a single-component (grey) file: the transcoder takes three-component files unless grey=True is passed")
         if transcoder and frame.precision16:
             raise NotImplementedError(f"file {i}: a 16-bit quantisation table: the transcoder writes 8-bit tables")
-        yield i, is_prog, d, memoryview(f).cast("B")
+        yield i, is_prog, d, frame, memoryview(f).cast("B")
+
+
+class _Sources:
+    """The parsed files of one call, marshalled once for the decoders and the transcoder: parsed[i] is file i's JpegDecDesc or
+    (JpegProgFrame, scans), frames[i] its frame either way, views[i] its bytes; base_idx and prog_idx are the baseline and the
+    progressive files, each in file order."""
+
+    def __init__(self):
+        self.parsed, self.frames, self.views, self.base_idx, self.prog_idx = [], [], [], [], []
+
+    def parse(self, files, *args, **kw):
+        """_parse_sources(files, ...) with every file entered here before it is yielded as (i, frame, view): what the caller checks
+        between two files is reported before the next file's header is"""
+        for i, is_prog, d, frame, mv in _parse_sources(files, *args, **kw):
+            self.parsed.append(d)
+            self.frames.append(frame)
+            self.views.append(mv)
+            (self.prog_idx if is_prog else self.base_idx).append(i)
+            yield i, frame, mv
+
+    def baseline(self, idx):
+        """-> (JpegDecDesc [n], n, the staging pieces (file, scan offset, scan length)) of the baseline files idx"""
+        from ._lib import JpegDecDesc
+        descs = (JpegDecDesc * max(len(idx), 1))(*[self.parsed[i] for i in idx])
+        return descs, len(idx), [(i, self.parsed[i].scan_offset, self.parsed[i].scan_length) for i in idx]
+
+    def progressive(self, idx):
+        """-> (JpegProgFrame [n], the files' JpegProgScan in one flat array, n, the staging pieces (file, data offset, data length) of
+        those scans) of the progressive files idx"""
+        from ._lib import JpegProgFrame, JpegProgScan
+        flat = [(i, s) for i in idx for s in self.parsed[i][1]]
+        frames = (JpegProgFrame * max(len(idx), 1))(*[self.frames[i] for i in idx])
+        scans = (JpegProgScan * max(len(flat), 1))(*[s for _, s in flat])
+        return frames, scans, len(idx), [(i, s.data_offset, s.data_length) for i, s in flat]
 
 
 def _stage(ctx, views, pieces):
@@ -382,60 +432,37 @@ def _adobe_array(frames):
     return (JpegAdobe * len(xs))(*[x if x is not None else JpegAdobe() for x in xs])
 
 
-def _decode_entries(lib, family, idx, scales, comps, boxes, sbox, xs):
-    """The C entries of one decoder family ("jpegdec" | "jpegprog") for a call's options -> (the size query, the batch entry, their
-    leading option arguments, the arrays those point into, to be kept until the call returns).  The entry is the narrowest that takes
-    every option given: none, _scaled (scales), _mode (comps: 3, 1 or 4 per file), _box or -- sbox: the boxes are in pixels of each file's
-    scaled image -- _sbox (boxes: int32 [n, 4]), _adobe (xs: _adobe_array's); an option not given goes as NULL."""
+def _decode_kind(ctx, src, prog, out, out_off, scales=None, comps=None, boxes=None, sbox=False):
+    """aej_jpegdec_batch_adobe over the call's baseline files or (prog) aej_jpegprog_batch_adobe over its progressive ones -> their
+    status words (device int32).  The package binds the widest entry: an option that no file of the call uses goes as NULL -- scales
+    (int32 [n]), comps (3, 1 or, for a four-component file that leaves in mode "CMYK", 4 per file), boxes (int32 [n, 4]), the JpegAdobe
+    array (_adobe_array) -- and the entry is then the narrower one byte for byte, launches included (include/aej.h).  sbox: the boxes are
+    in pixels of each file's scaled image, which is the _sbox entries' reading of the same arguments."""
+    idx = src.prog_idx if prog else src.base_idx
+    if prog:
+        frames, pscans, n, pieces = src.progressive(idx)
+        lead = (ctx.handle, ctypes.addressof(frames), ctypes.addressof(pscans), n)
+    else:
+        descs, n, pieces = src.baseline(idx)
+        lead = (ctx.handle, ctypes.addressof(descs), n)
+    data, data_off = _stage(ctx, src.views, pieces)
+    oo = np.ascontiguousarray(out_off[idx])
+    status = ctx.empty((n,), ctx.torch.int32)
     arrays = [None if a is None else np.ascontiguousarray(a[idx], np.int32) for a in (scales, comps, boxes)]
-    args = [None if a is None else a.ctypes.data for a in arrays] + [None if xs is None else ctypes.addressof(xs)]
-    given = max(k + 1 if a is not None else 0 for k, a in enumerate(args))
+    how = [None if a is None else a.ctypes.data for a in arrays]
+    xs = _adobe_array([src.frames[i] for i in idx])
     # _adobe wins over _sbox: its files are refused at any scale but 1, where a scaled box is the full-size box (another file's at 2, 4, 8: refused)
-    sfx = ("", "_scaled", "_mode", "_sbox" if sbox else "_box", "_adobe")[given]
-    return getattr(lib, f"aej_{family}_workspace_bytes{sfx}"), getattr(lib, f"aej_{family}_batch{sfx}"), tuple(args[:given]), arrays
-
-
-def _decode_baseline(ctx, idx, parsed, views, out, out_off, scales=None, comps=None, boxes=None, sbox=False):
-    """the aej_jpegdec_batch* entry for the options given (_decode_entries) over the files idx -> their status words (device int32).
-    With a four-component or RGB-coded file among them (adobe=True alone parses one): aej_jpegdec_batch_adobe, comps 4 for a file that
-    leaves in mode "CMYK"."""
-    from ._lib import JpegDecDesc
-    t, n = ctx.torch, len(idx)
-    descs = (JpegDecDesc * n)(*[parsed[i] for i in idx])
-    scans, scan_off = _stage(ctx, views, [(i, parsed[i].scan_offset, parsed[i].scan_length) for i in idx])
-    oo = np.ascontiguousarray(out_off[idx])
-    status = ctx.empty((n,), t.int32)
-    xs = _adobe_array([parsed[i] for i in idx])
-    nbytes, batch, how, keep = _decode_entries(ctx.lib, "jpegdec", idx, scales, comps, boxes, sbox, xs)
-    nws = int(nbytes(ctx.handle, ctypes.addressof(descs), n, *how))
+    sfx = "_sbox" if sbox and xs is None else "_adobe"
+    if sfx == "_adobe":
+        how.append(None if xs is None else ctypes.addressof(xs))
+    family = "aej_jpegprog_" if prog else "aej_jpegdec_"
+    nws = int(getattr(ctx.lib, family + "workspace_bytes" + sfx)(*lead, *how))
     if nws == 0:
         raise ValueError("descriptors the library refuses")
     ws = ctx.workspace(nws)
-    ctx.check(batch(ctx.handle, ctypes.addressof(descs), n, *how, scans.data_ptr(), ctypes.c_uint64(scans.numel()),
-                    scan_off.ctypes.data, out.data_ptr(), ctypes.c_uint64(out.numel()), oo.ctypes.data,
-                    status.data_ptr(), ws.data_ptr(), ctypes.c_uint64(nws)))
-    return status
-
-
-def _decode_progressive(ctx, idx, parsed, views, out, out_off, scales=None, comps=None, boxes=None, sbox=False):
-    """the same through the aej_jpegprog_batch* entries -> the files' status words (device int32)"""
-    from ._lib import JpegProgFrame, JpegProgScan
-    t, n = ctx.torch, len(idx)
-    frames = (JpegProgFrame * n)(*[parsed[i][0] for i in idx])
-    flat = [(i, s) for i in idx for s in parsed[i][1]]
-    scans = (JpegProgScan * len(flat))(*[s for _, s in flat])
-    data, data_off = _stage(ctx, views, [(i, s.data_offset, s.data_length) for i, s in flat])
-    oo = np.ascontiguousarray(out_off[idx])
-    status = ctx.empty((n,), t.int32)
-    xs = _adobe_array([parsed[i][0] for i in idx])        # a four-component or RGB-coded file among them: the _adobe entries
-    nbytes, batch, how, keep = _decode_entries(ctx.lib, "jpegprog", idx, scales, comps, boxes, sbox, xs)
-    nws = int(nbytes(ctx.handle, ctypes.addressof(frames), ctypes.addressof(scans), n, *how))
-    if nws == 0:
-        raise ValueError("descriptors the library refuses")
-    ws = ctx.workspace(nws)
-    ctx.check(batch(ctx.handle, ctypes.addressof(frames), ctypes.addressof(scans), n, *how, data.data_ptr(),
-                    ctypes.c_uint64(data.numel()), data_off.ctypes.data, out.data_ptr(), ctypes.c_uint64(out.numel()),
-                    oo.ctypes.data, status.data_ptr(), ws.data_ptr(), ctypes.c_uint64(nws)))
+    ctx.check(getattr(ctx.lib, family + "batch" + sfx)(*lead, *how, data.data_ptr(), ctypes.c_uint64(data.numel()), data_off.ctypes.data,
+                                                       out.data_ptr(), ctypes.c_uint64(out.numel()), oo.ctypes.data, status.data_ptr(),
+                                                       ws.data_ptr(), ctypes.c_uint64(nws)))
     return status
 
 
@@ -627,7 +654,7 @@ def standard_jpeg_decode_many(files, device: int = 0, progressive: bool = False,
     L image, h * w * 3 of an RGB one).  A string that is not one of the three, or a sequence of another length than files, raises
     ValueError (naming the file of a bad entry); a value that is neither a string nor a list / tuple TypeError -- before any device
     work, like every keyword here.
-    box: None (the default: the call as it always was -- the same library entries, the same launches), one (left, top, right, bottom)
+    box: None (the default: the call as it always was -- NULL boxes, the same launches), one (left, top, right, bottom)
     for every file, or a list with one entry per file, each such a tuple or None (the whole image).  Pillow's crop() coordinates, in
     pixels of the decoded image, 0 <= left < right <= W_i and 0 <= top < bottom <= H_i.  Element i is then uint8 [bottom - top,
     right - left, 3] -- [bottom - top, right - left] where mode makes it one-channel -- and equals ``np.asarray(Image.open(f)
@@ -683,18 +710,11 @@ def _decode_files(files, device, progressive, scales, choose=None, layout_440=Fa
     "CMYK" has 4 channels.  sboxes (not together with boxes): the same list with every box in pixels of its file's scaled image; an
     entry may be set by `choose`, which is asked first."""
     n = len(files)
-    parsed, views, base_idx, prog_idx, shapes, comps = [], [], [], [], [], []
-    box_arr, prog_set = None, set()
+    src, shapes, comps, box_arr = _Sources(), [], [], None
     sbox = sboxes is not None
     if sbox:
         boxes = sboxes
-    for i, is_prog, d, mv in _parse_sources(files, progressive, layout_440=layout_440, adobe=adobe):
-        parsed.append(d)
-        views.append(mv)
-        (prog_idx if is_prog else base_idx).append(i)
-        if is_prog:
-            prog_set.add(i)
-        frame = d[0] if is_prog else d
+    for i, frame, _ in src.parse(files, progressive, layout_440=layout_440, adobe=adobe):
         m = "RGB" if modes is None else modes[i]
         comps.append(1 if m == "L" or (m == "auto" and frame.ncomp == 1) else 4 if m == "auto" and frame.ncomp == 4 else 3)
         if choose is not None:
@@ -716,15 +736,14 @@ def _decode_files(files, device, progressive, scales, choose=None, layout_440=Fa
             box_arr = np.zeros((n, 4), np.int32) if box_arr is None else box_arr
             box_arr[i] = boxes[i]
             shapes[-1] = (boxes[i][3] - boxes[i][1], boxes[i][2] - boxes[i][0])
-    if box_arr is not None:                          # the entries with boxes: every other file's is its whole image
-        for i in range(n):
+    if box_arr is not None:                          # a call with boxes: every other file's is its whole image
+        for i, frame in enumerate(src.frames):
             if not box_arr[i].any():
-                frame = parsed[i][0] if i in prog_set else parsed[i]
                 s = int(scales[i]) if sbox else 1
                 box_arr[i] = (0, 0, -(-frame.width // s), -(-frame.height // s))
     if (scales == 1).all():
-        scales = None                                # the unscaled entries, as before
-    comps_arr = None if all(c == 3 for c in comps) else np.array(comps, np.int32)      # every image RGB: the entries without components, as before
+        scales = None                                # every file at full size: NULL
+    comps_arr = None if all(c == 3 for c in comps) else np.array(comps, np.int32)      # every image RGB: NULL
     ctx = get_context(device)
     t = ctx.torch
     out_off = np.zeros(n, np.int64)
@@ -734,10 +753,10 @@ def _decode_files(files, device, progressive, scales, choose=None, layout_440=Fa
         opos += h * w * comps[i]
     out = ctx.empty((max(opos, 1),), t.uint8)
     st = np.zeros(n, np.int64)
-    for idx, run in ((base_idx, _decode_baseline), (prog_idx, _decode_progressive)):
+    for idx, prog in ((src.base_idx, False), (src.prog_idx, True)):      # one staging copy and one entry per kind
         if idx:
-            extra = () if box_arr is None else (box_arr, True) if sbox else (box_arr,)      # no box: the entries without boxes, as before
-            st[idx] = run(ctx, idx, parsed, views, out, out_off, scales, comps_arr, *extra).cpu().numpy()      # the one read-back of the per-file status words
+            st[idx] = _decode_kind(ctx, src, prog, out, out_off, scales, comps_arr, box_arr,
+                                   sbox and box_arr is not None).cpu().numpy()      # the one read-back of the per-file status words
     _raise_status((int(i), int(st[i])) for i in np.flatnonzero(st))
     return ctx, out, out_off, shapes, comps
 
@@ -999,34 +1018,30 @@ def metadata_segments(data, index: int = 0) -> bytes:
     return b"".join(bytes(mv[a:b]) for m, a, b in marker_segments(mv, index) if _is_metadata(m))
 
 
-def _prefix(data, index, transform, trim, headers, grey=False, layout_440=False, cut=None):
-    """transcode_prefix (transform None) and transform_prefix: headers(lib, frame pointers and density, output buffer and capacity)
-    calls the caller's own ABI entry.  cut: None, or (crop box or None, drop_chroma) -- the refusals of _cut_geometry then"""
+def _prefix(data, index, progressive, transform, trim, grey, layout_440, box=None, drop=False):
+    """transcode_prefix (the transform "none", whose geometry refuses no file the parsers took) and transform_prefix, both through
+    aej_jfif_transform_headers_host_cut; box (or None) and drop: transform_prefix's crop and drop_chroma"""
     from ._lib import load_library
-    (_, is_prog, d, mv), = _parse_sources([data], transcoder=True, start=index, grey=_check_bool("grey", grey), layout_440=layout_440)
-    frame = d[0] if is_prog else d
-    if cut is not None:
-        _cut_geometry(index, frame, _check_transform(transform, index), trim, layout_440, cut[0], cut[1])
-    elif transform is not None:
-        _transform_geometry(index, frame.height, frame.width, frame.hs, frame.vs, _check_transform(transform, index), trim, layout_440)
+    (_, is_prog, _, frame, mv), = _parse_sources([data], transcoder=True, start=index, grey=_check_bool("grey", grey), layout_440=layout_440)
+    _transform_geometry(index, frame, _check_transform(transform, index), trim, layout_440, box, drop)
     dens = (ctypes.c_uint16 * 3)(*_jfif_density(mv, marker_segments(mv, index)))
     buf = (ctypes.c_uint8 * 512)()
-    n = headers(load_library(), (None if is_prog else ctypes.addressof(frame), ctypes.addressof(frame) if is_prog else None, ctypes.addressof(dens)),
-                (ctypes.addressof(buf), 512))
+    b4 = None if box is None else (ctypes.c_int32 * 4)(*box)
+    n = load_library().aej_jfif_transform_headers_host_cut(
+        None if is_prog else ctypes.addressof(frame), ctypes.addressof(frame) if is_prog else None, ctypes.addressof(dens), int(progressive),
+        TRANSFORMS.index(transform), int(trim), int(layout_440), None if b4 is None else ctypes.addressof(b4), int(drop),
+        ctypes.addressof(buf), 512)
     if n < 0:
         raise ValueError(f"file {index}: the library refuses its descriptor ({n})")
     return bytes(buf[:n])
 
 
 def transcode_prefix(data, progressive: bool = False, index: int = 0, grey: bool = False, layout_440: bool = False) -> bytes:
-    """The bytes SOI .. end of SOF0 / SOF2 that standard_jpeg_transcode_many writes for one file (aej_jfif_transcode_headers_host,
-    host only): JFIF APP0 with the source's density, its quantisation tables, its frame header.  grey, layout_440: as
-    standard_jpeg_transcode_many (with layout_440 the entry is aej_jfif_transform_headers_host_440 with the code 0)."""
+    """The bytes SOI .. end of SOF0 / SOF2 that standard_jpeg_transcode_many writes for one file (aej_jfif_transform_headers_host_cut
+    with the code 0, no crop and no chroma drop, host only): JFIF APP0 with the source's density, its quantisation tables, its frame
+    header.  grey, layout_440: as standard_jpeg_transcode_many."""
     progressive = _check_bool("progressive", progressive)
-    if _check_bool("layout_440", layout_440):
-        return _prefix(data, index, None, False, lambda lib, src, dst: lib.aej_jfif_transform_headers_host_440(*src, int(progressive), 0, 0, 1, *dst),
-                       grey, True)
-    return _prefix(data, index, None, False, lambda lib, src, dst: lib.aej_jfif_transcode_headers_host(*src, int(progressive), *dst), grey)
+    return _prefix(data, index, progressive, "none", False, grey, _check_bool("layout_440", layout_440))
 
 
 def splice_metadata(out: bytes, meta: bytes) -> bytes:
@@ -1085,26 +1100,6 @@ def exif_orientation(data, index: int = 0) -> int:
     return at[0] if at and 1 <= at[0] <= 8 else 1
 
 
-def _transform_geometry(i, height, width, hs, vs, name, trim, layout_440=False):
-    """-> the output's (height, width, hs, vs); the refusals of a transform, naming the file, before any device work"""
-    from ._lib import load_library
-    if name in _TRANSPOSING and hs != vs and not layout_440:
-        raise NotImplementedError(f"file {i}: {name} of a 4:2:2 file would be a 4:4:0 file, which neither the coders nor the decoders here have")
-    out = (ctypes.c_int32 * 4)()
-    if layout_440:
-        rc = load_library().aej_jfif_transform_geometry_host_440(height, width, hs, vs, TRANSFORMS.index(name), int(trim), 1, ctypes.addressof(out))
-    else:
-        rc = load_library().aej_jfif_transform_geometry_host(height, width, hs, vs, TRANSFORMS.index(name), int(trim), ctypes.addressof(out))
-    if rc == 1:
-        raise ValueError(f"file {i}: {name} of a {width} x {height} file mirrors an axis that is not a whole number of its {8 * hs} x {8 * vs} MCUs; "
-                         "trim=True drops the partial MCUs at that edge first")
-    if rc == 2:
-        raise ValueError(f"file {i}: {name} with trim=True leaves nothing of a {width} x {height} file with {8 * hs} x {8 * vs} MCUs")
-    if rc:
-        raise ValueError(f"file {i}: the library refuses the transform ({rc})")
-    return tuple(out)
-
-
 def _check_box(box, i):
     """one crop entry -> None or four ints; bool, float and anything that is not four values are refused, naming the file"""
     if box is None:
@@ -1130,9 +1125,10 @@ def _check_crop(crop, n):
     return [_check_box(e, i) for i, e in enumerate(entries)]
 
 
-def _cut_geometry(i, frame, name, trim, layout_440, box, drop):
-    """_transform_geometry with a crop box (or None) and drop_chroma (aej_jfif_transform_geometry_host_cut) -> the output's (height,
-    width, hs, vs) and the crop's aligned corner (L, U); every refusal names the file and comes before any device work"""
+def _transform_geometry(i, frame, name, trim, layout_440, box=None, drop=False):
+    """The geometry of one file's transform, with its crop box (or None) and drop_chroma (aej_jfif_transform_geometry_host_cut) -> the
+    output's (height, width, hs, vs) and the crop's aligned corner (L, U); every refusal names the file and comes before any device
+    work.  The frame's own component count goes to the entry: a parsed one-component frame carries hs = vs = 1."""
     from ._lib import load_library
     nc = 1 if frame.ncomp == 1 else 3
     one = drop or nc == 1                           # a one-component output: 8 x 8 MCUs, no layout
@@ -1175,8 +1171,8 @@ def transform_crop_box(data, transform, crop, trim: bool = False, index: int = 0
     box = _check_box(crop, index)
     if box is None:
         raise ValueError(f"file {index}: crop None: a box required")
-    (_, is_prog, d, _), = _parse_sources([data], transcoder=True, start=index, grey=grey, layout_440=layout_440)
-    g = _cut_geometry(index, d[0] if is_prog else d, _check_transform(transform, index), trim, layout_440, box, drop_chroma)
+    (_, _, _, frame, _), = _parse_sources([data], transcoder=True, start=index, grey=grey, layout_440=layout_440)
+    g = _transform_geometry(index, frame, _check_transform(transform, index), trim, layout_440, box, drop_chroma)
     return (g[4], g[5], box[2], box[3])
 
 
@@ -1190,24 +1186,14 @@ def _check_transform(name, i):
 def transform_prefix(data, transform, progressive: bool = False, trim: bool = False, index: int = 0, grey: bool = False,
                      layout_440: bool = False, crop=None, drop_chroma: bool = False) -> bytes:
     """The bytes SOI .. end of SOF0 / SOF2 that standard_jpeg_transform_many writes for one file under one transform name
-    (aej_jfif_transform_headers_host, host only): transcode_prefix with the output's size and sampling and, for a transposing
-    transform, every quantisation table transposed.  grey, layout_440: as standard_jpeg_transform_many (with layout_440 the entry is
-    aej_jfif_transform_headers_host_440: a transposed 4:2:2 frame carries the sampling byte 0x12).  crop (one box, or None),
-    drop_chroma: as standard_jpeg_transform_many (aej_jfif_transform_headers_host_cut): the cropped size; for a dropped chroma one DQT
-    and the one-component frame header."""
+    (aej_jfif_transform_headers_host_cut, host only): transcode_prefix with the output's size and sampling and, for a transposing
+    transform, every quantisation table transposed.  grey, layout_440: as standard_jpeg_transform_many (with layout_440 a transposed
+    4:2:2 frame carries the sampling byte 0x12).  crop (one box, or None), drop_chroma: as standard_jpeg_transform_many: the cropped
+    size; for a dropped chroma one DQT and the one-component frame header."""
     progressive, trim = _check_bool("progressive", progressive), _check_bool("trim", trim)
     box = _check_box(crop, index)
-    if _check_bool("drop_chroma", drop_chroma) or box is not None:
-        layout_440 = _check_bool("layout_440", layout_440)
-        b4 = (ctypes.c_int32 * 4)(*(box or (0, 0, 0, 0)))
-        return _prefix(data, index, transform, trim, lambda lib, src, dst: lib.aej_jfif_transform_headers_host_cut(
-            *src, int(progressive), TRANSFORMS.index(transform), int(trim), int(layout_440), ctypes.addressof(b4), int(drop_chroma), *dst),
-            grey, layout_440, (box, drop_chroma))
-    if _check_bool("layout_440", layout_440):
-        return _prefix(data, index, transform, trim, lambda lib, src, dst: lib.aej_jfif_transform_headers_host_440(
-            *src, int(progressive), TRANSFORMS.index(transform), int(trim), 1, *dst), grey, True)
-    return _prefix(data, index, transform, trim, lambda lib, src, dst: lib.aej_jfif_transform_headers_host(
-        *src, int(progressive), TRANSFORMS.index(transform), int(trim), *dst), grey)
+    drop_chroma, layout_440 = _check_bool("drop_chroma", drop_chroma), _check_bool("layout_440", layout_440)
+    return _prefix(data, index, progressive, transform, trim, grey, layout_440, box, drop_chroma)
 
 
 def standard_jpeg_transform_many(files, transform, progressive: bool = False, trim: bool = False, device: int = 0,
@@ -1283,9 +1269,7 @@ def standard_jpeg_transform_many(files, transform, progressive: bool = False, tr
         if len(names) != n:
             raise ValueError(f"file {min(len(names), n)}: {len(names)} transforms for {n} files")
         names = [_check_transform(t, i) for i, t in enumerate(names)]
-    if drop_chroma or any(b is not None for b in boxes):
-        return _transcode_many(files, progressive, device, keep_metadata, names, trim, names is None, grey, rst, layout_440, (boxes, drop_chroma))
-    return _transcode_many(files, progressive, device, keep_metadata, names, trim, names is None, grey, rst, layout_440)
+    return _transcode_many(files, progressive, device, keep_metadata, names, trim, names is None, grey, rst, layout_440, boxes, drop_chroma)
 
 
 def standard_jpeg_transcode_many(files, progressive: bool = False, device: int = 0, keep_metadata: bool = False, grey: bool = False,
@@ -1328,101 +1312,62 @@ def standard_jpeg_transcode_many(files, progressive: bool = False, device: int =
     return _transcode_many(files, progressive, device, keep_metadata, None, False, False, grey, rst, layout_440)
 
 
-def _transcode_many(files, progressive, device, keep_metadata, names, trim, exif, grey=False, rst=(0, 0), layout_440=False, cut=None):
-    """the transcode (names None and not exif) and the transform: names[i] is file i's transform, exif takes it from the file; rst:
-    (restart_marker_blocks, restart_marker_rows) -- (0, 0) goes through the entries without restart arguments; layout_440: the one pair
-    of _440 entries serves transcode and transform, with the restart arguments always; cut: None, or ([n] crop boxes or None,
-    drop_chroma) -- the pair of _cut entries then, which take layout_440 as a value"""
+def _transcode_many(files, progressive, device, keep_metadata, names, trim, exif, grey=False, rst=(0, 0), layout_440=False, boxes=None,
+                    drop=False):
+    """the transcode (names None and not exif) and the transform, both through the aej_jfif_transform_*_cut entries: names[i] is file
+    i's transform, exif takes it from the file; rst: (restart_marker_blocks, restart_marker_rows); boxes: None, or [n] crop boxes or
+    None; drop: drop_chroma.  What no file of the call uses goes as the entry's neutral value -- NULL transforms when every file is
+    "none", NULL boxes when no file has one, 0 for the rest -- which is the narrower entry byte for byte (include/aej.h)."""
     global _last_transcode_groups
-    from ._lib import JpegDecDesc, JpegProgFrame, JpegProgScan
     n = len(files)
     names = ["none"] * n if names is None else names
-    views, parsed, base_idx, prog_idx, density, meta = [], [None] * n, [], [], [None] * n, [b""] * n
-    for i, is_prog, d, mv in _parse_sources(files, transcoder=True, grey=grey, layout_440=layout_440):
-        parsed[i] = d
-        (prog_idx if is_prog else base_idx).append(i)
-        views.append(mv)
+    boxes = [None] * n if boxes is None else boxes
+    src, density, meta = _Sources(), [None] * n, [b""] * n
+    for i, frame, mv in src.parse(files, transcoder=True, grey=grey, layout_440=layout_440):
         segs = marker_segments(mv, i)
         density[i] = _jfif_density(mv, segs)
         at = _exif_orientation_at(mv, segs) if exif else None
         if at and 1 <= at[0] <= 8:
             names[i] = _EXIF_TRANSFORM[at[0]]
-        if cut is not None:
-            _cut_geometry(i, parsed[i][0] if is_prog else parsed[i], names[i], trim, layout_440, cut[0][i], cut[1])
-        elif names[i] != "none":
-            frame = parsed[i][0] if is_prog else parsed[i]
-            _transform_geometry(i, frame.height, frame.width, frame.hs, frame.vs, names[i], trim, layout_440)
+        _transform_geometry(i, frame, names[i], trim, layout_440, boxes[i], drop)
         if keep_metadata:
             meta[i] = metadata_segments(mv, i)
             if at and 1 < at[0] <= 8:                # the tag's value becomes 1, in the TIFF block's byte order; nothing else changes
                 k = sum(min(b, at[1]) - a for m, a, b in segs if a < at[1] and _is_metadata(m))      # its place among the carried bytes
                 meta[i] = meta[i][:k] + (1).to_bytes(2, at[2]) + meta[i][k + 2:]
-    order = base_idx + prog_idx                     # the call's file order: baseline sources first
-    nb, npg = len(base_idx), len(prog_idx)
+    order = src.base_idx + src.prog_idx             # the call's file order: baseline sources first
     ctx = get_context(device)
     t, lib = ctx.torch, ctx.lib
-    descs = (JpegDecDesc * max(nb, 1))(*[parsed[i] for i in base_idx])
-    frames = (JpegProgFrame * max(npg, 1))(*[parsed[i][0] for i in prog_idx])
-    flat = [(i, s) for i in prog_idx for s in parsed[i][1]]
-    pscans = (JpegProgScan * max(len(flat), 1))(*[s for _, s in flat])
+    descs, nb, base_pieces = src.baseline(src.base_idx)
+    frames, pscans, npg, prog_pieces = src.progressive(src.prog_idx)
     # one staging copy for both kinds (the pinned buffer behind _stage is only valid until its next use)
-    scans, off = _stage(ctx, views, [(i, parsed[i].scan_offset, parsed[i].scan_length) for i in base_idx] +
-                        [(i, s.data_offset, s.data_length) for i, s in flat])
-    data, scan_off, data_off = scans, np.ascontiguousarray(off[:max(nb, 1)]), np.ascontiguousarray(off[nb:nb + max(len(flat), 1)])
+    scans, off = _stage(ctx, src.views, base_pieces + prog_pieces)
+    data, scan_off, data_off = scans, np.ascontiguousarray(off[:max(nb, 1)]), np.ascontiguousarray(off[nb:nb + max(len(prog_pieces), 1)])
     dens = np.ascontiguousarray(np.array([density[i] for i in order], np.uint16))
     codes = np.ascontiguousarray(np.array([TRANSFORMS.index(names[i]) for i in order], np.int32))
-    plain = not codes.any()                         # every file "none": the transcoder's own entries
-    rst440 = (int(rst[0]), int(rst[1]), 1)
-    rst = tuple(rst) if any(rst) else ()            # the _rst entries' two extra arguments
-    sfx = "_rst" if rst else ""
-    if cut is not None:
-        boxes = np.ascontiguousarray(np.array([cut[0][i] or (0, 0, 0, 0) for i in order], np.int32))      # right == 0: no crop
-        cut_args = (int(rst440[0]), int(rst440[1]), int(layout_440), boxes.ctypes.data, int(cut[1]))
-        nws = int(lib.aej_jfif_transform_workspace_bytes_cut(ctx.handle, ctypes.addressof(descs), nb, ctypes.addressof(frames), ctypes.addressof(pscans),
-                                                             npg, int(progressive), codes.ctypes.data, int(trim), *cut_args))
-    elif layout_440:
-        nws = int(lib.aej_jfif_transform_workspace_bytes_440(ctx.handle, ctypes.addressof(descs), nb, ctypes.addressof(frames), ctypes.addressof(pscans),
-                                                             npg, int(progressive), codes.ctypes.data, int(trim), *rst440))
-    elif plain:
-        nws = int(getattr(lib, "aej_jfif_transcode_workspace_bytes" + sfx)(ctx.handle, ctypes.addressof(descs), nb, ctypes.addressof(frames),
-                                                                          ctypes.addressof(pscans), npg, int(progressive), *rst))
-    else:
-        nws = int(getattr(lib, "aej_jfif_transform_workspace_bytes" + sfx)(ctx.handle, ctypes.addressof(descs), nb, ctypes.addressof(frames),
-                                                                          ctypes.addressof(pscans), npg, int(progressive), codes.ctypes.data,
-                                                                          int(trim), *rst))
+    box_arr = np.ascontiguousarray(np.array([boxes[i] or (0, 0, 0, 0) for i in order], np.int32))      # right == 0: no crop
+    how = (int(progressive), codes.ctypes.data if codes.any() else None, int(trim), int(rst[0]), int(rst[1]), int(layout_440),
+           box_arr.ctypes.data if box_arr.any() else None, int(drop))
+    nws = int(lib.aej_jfif_transform_workspace_bytes_cut(ctx.handle, ctypes.addressof(descs), nb, ctypes.addressof(frames), ctypes.addressof(pscans),
+                                                         npg, *how))
     if nws == 0:
         raise ValueError("descriptors the library refuses")
     ws = ctx.workspace(nws)
     status, offsets, lengths = ctx.empty((n,), t.int32), ctx.empty((n,), t.int64), ctx.empty((n,), t.int64)
     total, groups = ctypes.c_uint64(), ctypes.c_int32()
-    cap = sum(len(v) for v in views) * 5 // 4 + (PROGRESSIVE_HEADER_CAPACITY if progressive else HEADER_CAPACITY) * n      # (a miss costs one more call)
-    out = ctx.empty((cap,), t.uint8)
-    head = (ctx.handle, ctypes.addressof(descs), nb, scans.data_ptr(), ctypes.c_uint64(scans.numel()), scan_off.ctypes.data, ctypes.addressof(frames),
-            ctypes.addressof(pscans), npg, data.data_ptr(), ctypes.c_uint64(data.numel()), data_off.ctypes.data, dens.ctypes.data, int(progressive))
-    tail = (offsets.data_ptr(), lengths.data_ptr(), ctypes.addressof(total), status.data_ptr(), ctypes.addressof(groups), ws.data_ptr(),
-            ctypes.c_uint64(nws))
-    if cut is not None:
-        call = lambda o, c: lib.aej_jfif_transform_batch_cut(*head, codes.ctypes.data, int(trim), *cut_args, o.data_ptr(), ctypes.c_uint64(c), *tail)  # noqa: E731
-    elif layout_440:
-        call = lambda o, c: lib.aej_jfif_transform_batch_440(*head, codes.ctypes.data, int(trim), *rst440, o.data_ptr(), ctypes.c_uint64(c), *tail)  # noqa: E731
-    elif plain:
-        call = lambda o, c: getattr(lib, "aej_jfif_transcode_batch" + sfx)(*head, *rst, o.data_ptr(), ctypes.c_uint64(c), *tail)  # noqa: E731
-    else:
-        call = lambda o, c: getattr(lib, "aej_jfif_transform_batch" + sfx)(*head, codes.ctypes.data, int(trim), *rst, o.data_ptr(),  # noqa: E731
-                                                                          ctypes.c_uint64(c), *tail)
-    rc = call(out, cap)
-    if rc == -4 and total.value > cap:             # AEJ_ERR_CAPACITY: run again with the exact size
-        cap = int(total.value)
-        out = ctx.empty((cap,), t.uint8)
-        rc = call(out, cap)
-    ctx.check(rc)
+    cap = sum(len(v) for v in src.views) * 5 // 4 + (PROGRESSIVE_HEADER_CAPACITY if progressive else HEADER_CAPACITY) * n      # (a miss costs one more call)
+    call = lambda o, c: lib.aej_jfif_transform_batch_cut(  # noqa: E731
+        ctx.handle, ctypes.addressof(descs), nb, scans.data_ptr(), ctypes.c_uint64(scans.numel()), scan_off.ctypes.data, ctypes.addressof(frames),
+        ctypes.addressof(pscans), npg, data.data_ptr(), ctypes.c_uint64(data.numel()), data_off.ctypes.data, dens.ctypes.data, *how,
+        o.data_ptr(), ctypes.c_uint64(c), offsets.data_ptr(), lengths.data_ptr(), ctypes.addressof(total), status.data_ptr(),
+        ctypes.addressof(groups), ws.data_ptr(), ctypes.c_uint64(nws))
+    sized = _sized_call(ctx, call, cap, total, offsets, lengths)
     _last_transcode_groups = int(groups.value)
     st = status.cpu().numpy()                       # the one read-back of the per-file status words
     _raise_status(sorted((order[int(k)], int(st[k])) for k in np.flatnonzero(st)))
-    blob = out[:int(total.value)].cpu().numpy().tobytes()
     res = [None] * n
-    for k, (o, m) in enumerate(zip(offsets.cpu().tolist(), lengths.cpu().tolist())):
-        res[order[k]] = splice_metadata(blob[o:o + m], meta[order[k]])
+    for k, f in enumerate(_file_bytes(*sized)):
+        res[order[k]] = splice_metadata(f, meta[order[k]])
     return res
 
 
@@ -1526,14 +1471,14 @@ def _packed_source(ctx, imgs):
 
 
 def _encode_many(ctx, imgs, qualities, ss, opt, prog, rst=(0, 0)):
+    """aej_jfif_many_encode_rst over the checked images (_check_images' list); rst: (restart_marker_blocks, restart_marker_rows), (0, 0)
+    being aej_jfif_many_encode"""
     global _last_encode_groups
-    rst = tuple(rst) if any(rst) else ()            # (0, 0) goes through the entries without restart arguments
-    sfx = "_rst" if rst else ""
     from ._lib import JfifManyDesc
     t, lib, n = ctx.torch, ctx.lib, len(imgs)
     keep, src, src_bytes, off = _packed_source(ctx, imgs)
     descs = (JfifManyDesc * n)(*[JfifManyDesc(int(off[i]), int(x.shape[1]), int(x.shape[0]), qualities[i], 1 if x.ndim == 2 else 3) for i, (x, _, _) in enumerate(imgs)])
-    nws = int(getattr(lib, "aej_jfif_many_workspace_bytes" + sfx)(ctx.handle, ctypes.addressof(descs), n, ss, int(opt), int(prog), *rst))
+    nws = int(lib.aej_jfif_many_workspace_bytes_rst(ctx.handle, ctypes.addressof(descs), n, ss, int(opt), int(prog), int(rst[0]), int(rst[1])))
     if nws == 0:
         raise ValueError("descriptors the library refuses")
     ws = ctx.workspace(nws)
@@ -1541,19 +1486,13 @@ def _encode_many(ctx, imgs, qualities, ss, opt, prog, rst=(0, 0)):
     total, groups = ctypes.c_uint64(), ctypes.c_int32()
     hdr = PROGRESSIVE_HEADER_CAPACITY if prog else HEADER_CAPACITY
     cap = sum(hdr + x.shape[0] * x.shape[1] * 3 // (4 if ss == 2 else 2) for x, _, _ in imgs)      # most files are far smaller; a miss costs one more call
-    out = ctx.empty((cap,), t.uint8)
-    call = lambda o, c: getattr(lib, "aej_jfif_many_encode" + sfx)(ctx.handle, ctypes.addressof(descs), n, src, ctypes.c_uint64(src_bytes), ss,  # noqa: E731
-                                                 int(opt), int(prog), *rst, o.data_ptr(), ctypes.c_uint64(c), offsets.data_ptr(), lengths.data_ptr(), ctypes.addressof(total),
-                                                 ctypes.addressof(groups), ws.data_ptr(), ctypes.c_uint64(nws))
-    rc = call(out, cap)
-    if rc == -4 and total.value > cap:                       # AEJ_ERR_CAPACITY: run again with the exact size
-        cap = int(total.value)
-        out = ctx.empty((cap,), t.uint8)
-        rc = call(out, cap)
-    ctx.check(rc)                                            # (`keep` has held the pixels until here)
+    call = lambda o, c: lib.aej_jfif_many_encode_rst(  # noqa: E731
+        ctx.handle, ctypes.addressof(descs), n, src, ctypes.c_uint64(src_bytes), ss, int(opt), int(prog), int(rst[0]), int(rst[1]), o.data_ptr(),
+        ctypes.c_uint64(c), offsets.data_ptr(), lengths.data_ptr(), ctypes.addressof(total), ctypes.addressof(groups), ws.data_ptr(),
+        ctypes.c_uint64(nws))
+    sized = _sized_call(ctx, call, cap, total, offsets, lengths)      # (`keep` has held the pixels until here)
     _last_encode_groups = int(groups.value)
-    blob = out[:int(total.value)].cpu().numpy().tobytes()
-    res = [blob[o:o + m] for o, m in zip(offsets.cpu().tolist(), lengths.cpu().tolist())]
+    res = _file_bytes(*sized)
     for i, (x, _, _) in enumerate(imgs):             # a comment the image carries: one COM segment after the JFIF APP0, where libjpeg puts it
         com = getattr(x, "jpeg_comment", None)
         if com is not None:

@@ -189,7 +189,10 @@ class _HostContext:
         raise AssertionError("no workspace is made for a size of 0")
 
 
-def test_zero_zero_reaches_the_entries_of_before_with_their_arguments(monkeypatch):
+def test_zero_zero_reaches_the_wide_entries_with_neutral_arguments(monkeypatch):
+    """The package binds the widest entry of each operation ("What the JPEG file calls share"): the defaults and an explicit
+    (0, 0) are one and the same call, whose restart arguments are 0, 0 -- by include/aej.h the entry without them -- and a setting
+    changes those two arguments and nothing else.  tests/test_gpu_jpeg_wide_entries.py holds the library to that equivalence."""
     ctx = _HostContext()
     monkeypatch.setattr(S, "get_context", lambda device=0: ctx)
     x = _image(32, 48)                                                # whole MCUs: rot180 is allowed
@@ -205,15 +208,22 @@ def test_zero_zero_reaches_the_entries_of_before_with_their_arguments(monkeypatc
     enc = lambda **kw: A.standard_jpeg_encode_many([x], **kw)  # noqa: E731
     tra = lambda **kw: A.standard_jpeg_transcode_many([jpg], **kw)  # noqa: E731
     tfm = lambda **kw: A.standard_jpeg_transform_many([jpg], "rot180", **kw)  # noqa: E731
-    for call, name in ((enc, "aej_jfif_many_workspace_bytes"), (tra, "aej_jfif_transcode_workspace_bytes"),
-                       (tfm, "aej_jfif_transform_workspace_bytes")):
-        plain, zero = entry(call), entry(call, restart_marker_blocks=0, restart_marker_rows=0)
-        assert plain[0] == zero[0] == name and len(plain[1]) == len(zero[1]) == len(SIGNATURES[name][1])
-        assert plain[1][2:] == zero[1][2:] or name != "aej_jfif_many_workspace_bytes"       # (the descriptors' address differs per call)
-        both = entry(call, restart_marker_blocks=3, restart_marker_rows=2)
-        assert both[0] == name + "_rst" and len(both[1]) == len(SIGNATURES[name + "_rst"][1]) and both[1][-2:] == (3, 2)
-        assert both[1][:len(plain[1])][-1] == plain[1][-1]                                   # the arguments before them are the same call's
-        assert entry(call, restart_marker_rows=1)[1][-2:] == (0, 1)
+    ADDR = "an address"                                               # of host arrays, new with every call; NULL stays None
+
+    def shape(args, blocks, rows):
+        return tuple(ADDR if isinstance(a, int) and a > 65535 else a for a in args) == tuple(blocks if a == "blocks" else rows if a == "rows" else a
+                                                                                            for a in want)
+
+    many = ("aej_jfif_many_workspace_bytes_rst", (None, ADDR, 1, 2, 0, 0, "blocks", "rows"))      # ctx, descs, n, 4:2:0, optimize, progressive
+    # ctx, descs, n_base, frames, scans, n_prog, progressive, transforms, trim, restart_blocks, restart_rows, layout_440, boxes, drop_chroma
+    cut = "aej_jfif_transform_workspace_bytes_cut"
+    for call, (name, want) in ((enc, many), (tra, (cut, (None, ADDR, 1, ADDR, ADDR, 0, 0, None, 0, "blocks", "rows", 0, None, 0))),
+                               (tfm, (cut, (None, ADDR, 1, ADDR, ADDR, 0, 0, ADDR, 0, "blocks", "rows", 0, None, 0)))):
+        assert len(want) == len(SIGNATURES[name][1])
+        for kw, blocks, rows in (({}, 0, 0), (dict(restart_marker_blocks=0, restart_marker_rows=0), 0, 0),
+                                 (dict(restart_marker_blocks=3, restart_marker_rows=2), 3, 2), (dict(restart_marker_rows=1), 0, 1)):
+            got = entry(call, **kw)
+            assert got[0] == name and shape(got[1], blocks, rows), (name, kw, got)
 
 
 def test_abi_symbols_and_refusals(lib):
