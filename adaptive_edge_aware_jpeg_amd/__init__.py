@@ -34,7 +34,7 @@ from .geometry import rotate_many, transform_many, transform_plan, transpose_man
 from .image import Image  # noqa: E402
 from .jpeg import EncodedBatch, Jpeg  # noqa: E402
 from .lpips import LpipsWeights  # noqa: E402
-from .png import png_decode_many, png_encode_many, png_parse_header  # noqa: E402
+from .png import png_adam7_passes, png_decode_many, png_encode_many, png_parse_header  # noqa: E402
 from .quadtree import QuadNode, QuadTree  # noqa: E402
 from .settings import JpegCompressionSettings  # noqa: E402
 from .resample import resize_many  # noqa: E402
@@ -49,7 +49,7 @@ __all__ = ["Jpeg", "JpegCompressionSettings", "EncodedBatch", "Image", "Evaluati
            "standard_jpeg_decode_many", "standard_jpeg_transcode_many", "standard_jpeg_transform_many", "exif_orientation", "draft_scale",
            "resize_many", "standard_jpeg_thumbnail_many", "thumbnail_plan", "standard_jpeg_encode_many", "standard_jpeg_thumbnail_jpeg_many",
            "encode_groups", "transform_prefix", "transform_crop_box", "decode_box_window", "decode_box_stats", "resized_crop_plan",
-           "standard_jpeg_resized_crop_many", "png_decode_many", "png_parse_header", "png_encode_many",
+           "standard_jpeg_resized_crop_many", "png_decode_many", "png_parse_header", "png_adam7_passes", "png_encode_many",
            "BoxBlur", "GaussianBlur", "UnsharpMask", "filter_many", "Kernel", "RankFilter", "MedianFilter", "MinFilter", "MaxFilter", "ModeFilter",
            "BLUR", "CONTOUR", "DETAIL", "EDGE_ENHANCE", "EDGE_ENHANCE_MORE", "EMBOSS", "FIND_EDGES", "SHARPEN", "SMOOTH", "SMOOTH_MORE",
            "transform_many", "rotate_many", "transpose_many", "transform_plan",

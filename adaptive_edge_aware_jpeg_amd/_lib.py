@@ -265,6 +265,12 @@ class PngDesc(ctypes.Structure):
         """Pillow's mode of the opened file"""
         return self.mode_chars.decode()
 
+    @property
+    def raw_bytes(self) -> int:
+        """aej_png_raw_bytes: the inflated size the file must have -- height x (1 + row_bytes), or for an interlaced file the sum over
+        its non-empty passes of h_p x (1 + row_bytes_p)"""
+        return int(load_library().aej_png_raw_bytes(ctypes.addressof(self)))
+
 
 SIGNATURES = {
     "aej_abi_version": (_I, []),
@@ -423,6 +429,9 @@ SIGNATURES = {
     "aej_resample_workspace_bytes_win": (_U64, [_P, _P, _I, _P, _P]),
     "aej_resample_batch_win": (_I, [_P, _P, _I, _P, _P, _P, _U64, _P, _U64, _P, _U64]),
     "aej_png_parse_host": (_I, [_P, _U64, _P, _P, _I, _P, _I]),
+    "aej_png_parse_host_accept": (_I, [_P, _U64, ctypes.c_uint32, _P, _P, _I, _P, _I]),
+    "aej_png_raw_bytes": (_U64, [_P]),
+    "aej_png_adam7_passes_host": (_I, [_I, _I, _P]),
     "aej_png_workspace_bytes": (_U64, [_P, _P, _I]),
     "aej_png_unfilter_batch": (_I, [_P, _P, _I, _P, _U64, _P, _P, _P, _P, _P, _P, _U64, _P, _P, _P, _U64]),
     "aej_png_filter_bytes": (_U64, [_I, _I, _I]),

@@ -836,24 +836,59 @@ hipError_t launch_compose(hipStream_t st, const CpPlan &plan);
 
 }  // namespace aej
 
-// png.hip: the scanline un-filter of PNG files and their expansion to the output layout (aej_png_unfilter_batch), one workgroup per file
+// png.hip: the scanline un-filter of PNG files and their expansion to the output layout (aej_png_unfilter_batch), one workgroup per work
+// item: a non-interlaced file, or one non-empty Adam7 pass of an interlaced one (the kernel finds a pass's geometry from its file's)
 namespace aej {
 
 constexpr int kPngGroup = 64;          // files per launch: their table travels in the kernel's arguments, so nothing is uploaded
 struct PngFile {
-    long long in_off;                  // its filtered scanlines in `inflated`: H x (1 + rb) bytes, a multiple of 4
-    long long out_off;                 // its image in `out`
-    long long carry_off;               // its carried scanline in the workspace (png_carry_bytes), a multiple of 256
+    long long in_off;                  // its filtered scanlines in `inflated`, at a multiple of 4: H x (1 + rb) bytes, or its passes back to back
+    long long out_off;                 // its image in `out`; of an interlaced file its pass images in the workspace (PngAdam7File::img_off)
+    long long carry_off;               // its carried scanline in the workspace (png_carry_bytes), a multiple of 256; an interlaced file's: one
+                                       // per non-empty pass, back to back
+    long long raw_bytes;               // the inflated size the file must have (of an interlaced file: all its passes)
     int W, H, rb;                      // pixels per row, rows, bytes per row without the filter byte
-    unsigned char bpp;                 // the filters' distance to the byte "to the left": bytes per whole pixel, 1 for the packed depths
-    unsigned char depth, ct;           // bit depth (1, 2, 4, 8), colour type (0, 2, 3, 4, 6)
+    int item;                          // -1, or for an interlaced file: the status word of its pass p is int item + p of the workspace
+    unsigned char bpp;                 // the filters' distance to the byte "to the left": bytes per whole pixel (1 .. 8), 1 for the packed depths
+    unsigned char depth, ct;           // bit depth (1, 2, 4, 8, 16), colour type (0, 2, 3, 4, 6)
     unsigned char oc;                  // bytes per pixel of the image written: 1 .. 4
 };
 struct PngGroup { PngFile f[kPngGroup]; };
 long long png_carry_bytes(int rb, int bpp);
 // files first .. first + count of the call (count <= kPngGroup); the per-file arrays are the whole call's
 void launch_png_unfilter(hipStream_t st, const PngGroup &grp, int first, int count, const unsigned char *inflated, const long long *inflate_out_bytes,
-                         const int *inflate_status, const unsigned char *palettes, unsigned char *out, unsigned char *carry, int *status);
+                         const int *inflate_status, const unsigned char *palettes, unsigned char *out, unsigned char *workspace, int *status);
+
+// Adam7 (PNG specification, section 8.2): pass p = 0 .. 6 holds the pixels (x0 + i dx, y0 + j dy) of the image
+struct Adam7Pass { int x0, y0, sx, sy, w, h; };      // dx = 1 << sx, dy = 1 << sy; w x h pixels, either 0 for an empty pass
+__host__ __device__ inline Adam7Pass adam7_pass(int W, int H, int p)
+{
+    Adam7Pass a;
+    a.x0 = (0x0402010 >> (4 * (6 - p))) & 15;        // 0 4 0 2 0 1 0
+    a.y0 = (0x0040201 >> (4 * (6 - p))) & 15;        // 0 0 4 0 2 0 1
+    a.sx = (0x3322110 >> (4 * (6 - p))) & 15;        // 8 8 4 4 2 2 1
+    a.sy = (0x3332211 >> (4 * (6 - p))) & 15;        // 8 8 8 4 4 2 2
+    a.w = W > a.x0 ? (W - a.x0 + (1 << a.sx) - 1) >> a.sx : 0;
+    a.h = H > a.y0 ? (H - a.y0 + (1 << a.sy) - 1) >> a.sy : 0;
+    if (a.w == 0 || a.h == 0) a.w = a.h = 0;
+    return a;
+}
+// the pass that holds pixel (x, y)
+__host__ __device__ inline int adam7_pass_of(int x, int y)
+{
+    return y & 1 ? 6 : x & 1 ? 5 : y & 2 ? 4 : x & 2 ? 3 : y & 4 ? 2 : x & 4 ? 1 : 0;
+}
+// the interleave of the pass images of interlaced files into their images (png_adam7_interleave_kernel), kPngGroup files per launch
+struct PngAdam7File {
+    long long out_off;                 // its image in `out`
+    long long img_off;                 // its pass images in the workspace, a multiple of 4: pass p behind pass p - 1, each w x h x oc rounded up to 4
+    int W, H, oc;
+    int file;                          // its status word in `status`: the largest of its passes'
+    int item;                          // the status word of its pass p is int item + p of the workspace
+};
+struct PngAdam7Group { PngAdam7File f[kPngGroup]; };
+void launch_png_adam7_interleave(hipStream_t st, const PngAdam7Group &grp, int count, int max_height, const unsigned char *workspace,
+                                 unsigned char *out, int *status);
 // the scanline filter of png_encode_many (aej_png_filter_batch): one wave per row, kPngGroup images per launch
 struct PngEncImage {
     const unsigned char *src;          // H rows of rb bytes, contiguous (any alignment)

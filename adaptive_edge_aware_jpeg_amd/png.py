@@ -3,7 +3,12 @@ files written on the GPU with Pillow's scanline filtering (``png_encode_many``, 
 
 The host reads only the chunk framing (``aej_png_parse_host``).  The zlib stream of every file -- its IDAT chunks joined -- is inflated
 by ``aej_inflate_batch`` (csrc/inflate.hip, one wave per file) or, as the A / B partner, by ``zlib.decompress`` on a thread pool; the
-scanline un-filter and the expansion of grey, palette and alpha layouts run on the device either way (csrc/png.hip)."""
+scanline un-filter and the expansion of grey, palette and alpha layouts run on the device either way (csrc/png.hip).
+
+Adam7-interlaced files (``interlaced=True``) and 16-bit files (``depth16=True``) are opt-in keywords of both calls; without them such a
+file is refused as it always was.  Neither touches the inflate: an interlaced file is seven smaller un-filter problems (the work item
+of the un-filter kernel is a pass, ``png_adam7_passes``) whose packed pass images a second kernel interleaves, and a 16-bit file is the
+same walk with units of 2, 4, 6 or 8 bytes."""
 import ctypes
 import struct
 import zlib
@@ -19,25 +24,61 @@ from .standard_jpeg import _buffer, _refuse
 
 MODES = ("RGB", "auto")      # AEJ_PNG_RGB, AEJ_PNG_AUTO
 MAX_HOST_WORKERS = 16
+ACCEPT_ADAM7, ACCEPT_16BIT = 1, 2      # AEJ_PNG_ACCEPT_*
+_HINTS = (("Adam7 interlace is not built", "interlaced=True"), ("16-bit samples are not built", "depth16=True"))
 
 
-def png_parse_header(data, index: int = 0):
+def _accept(interlaced, depth16) -> int:
+    for name, v in (("interlaced", interlaced), ("depth16", depth16)):
+        if not isinstance(v, (bool, np.bool_)):
+            raise TypeError(f"{name}: {v!r} is not a bool")
+    return (ACCEPT_ADAM7 if interlaced else 0) | (ACCEPT_16BIT if depth16 else 0)
+
+
+def png_adam7_passes(width: int, height: int):
+    """The seven Adam7 passes of a ``width`` x ``height`` image (PNG specification, section 8.2; aej_png_adam7_passes_host, host only):
+    a list of ``(x0, y0, dx, dy, w_p, h_p)`` -- pass p holds the pixels ``(x0 + i dx, y0 + j dy)``, ``w_p`` x ``h_p`` of them, both 0
+    for a pass without pixels (such a pass has no bytes in the file, not even filter bytes).  Each non-empty pass is one work item of the
+    un-filter kernel.  ValueError for a side that is no positive integer."""
+    from ._lib import load_library
+    if not is_int(width) or not is_int(height) or width < 1 or height < 1 or width >= 1 << 31 or height >= 1 << 31:
+        raise ValueError(f"width and height must be positive integers, not {width!r} and {height!r}")
+    t = np.zeros((7, 6), np.int32)
+    if load_library().aej_png_adam7_passes_host(int(width), int(height), t.ctypes.data):
+        raise ValueError(f"width {width} and height {height} are refused")
+    return [tuple(int(v) for v in row) for row in t]
+
+
+def png_parse_header(data, index: int = 0, interlaced: bool = False, depth16: bool = False):
     """aej_png_parse_host: the PngDesc of one file's chunks (host only, no device needed).  Attributes: ``width``, ``height``,
     ``bit_depth``, ``colour_type``, ``channels`` (samples per pixel in the file), ``row_bytes`` (a scanline without its filter byte),
     ``mode`` (Pillow's mode of the opened file: "1", "L", "P", "RGB", "LA", "RGBA"), ``n_idat`` and ``idat_bytes`` (number and total data
-    bytes of the IDAT chunks, empty ones included), ``palette_len`` (entries of PLTE), ``has_trns``, and ``idat_spans``: an int64 array
-    [n_idat, 2] of (offset in the file, length) of each IDAT chunk's data.  Raises NotImplementedError for a valid file outside the
-    supported set (16-bit samples, Adam7 interlace, APNG frames) and ValueError for a malformed one (bad signature, missing IHDR, PLTE or
+    bytes of the IDAT chunks, empty ones included), ``palette_len`` (entries of PLTE), ``has_trns``, ``interlace``, ``raw_bytes`` (the
+    inflated size the file must have: height x (1 + row_bytes), or for an interlaced file the sum over its non-empty passes of
+    h_p x (1 + row_bytes_p)) and ``idat_spans``: an int64 array [n_idat, 2] of (offset in the file, length) of each IDAT chunk's data.
+    ``interlaced=True`` takes Adam7 files (``interlace`` is 1, ``row_bytes`` stays the full-width scanline), ``depth16=True`` files of bit
+    depth 16 (``mode`` is Pillow's: "I;16" for colour type 0, "RGB" for 2, "RGBA" for 4 and for 6); a value that is not a bool raises
+    TypeError.  Raises NotImplementedError for a valid file outside the supported set (without its keyword 16-bit samples and Adam7
+    interlace, the message naming the keyword; APNG frames) and ValueError for a malformed one (bad signature, missing IHDR, PLTE or
     IDAT, a bad CRC on IHDR, PLTE or tRNS, zero width or height, a chunk length that runs past the file), both naming the file index."""
-    from ._lib import AEJ_ERR_CAPACITY, PngDesc, load_library
+    from ._lib import AEJ_ERR_CAPACITY, AEJ_ERR_UNSUPPORTED, PngDesc, load_library
+    accept = _accept(interlaced, depth16)
     lib = load_library()
     buf, n = _buffer(data)
     d, msg = PngDesc(), ctypes.create_string_buffer(256)
     spans = np.zeros((8, 2), np.int64)
-    rc = lib.aej_png_parse_host(ctypes.addressof(buf), n, ctypes.addressof(d), spans.ctypes.data, len(spans), ctypes.addressof(msg), 256)
+
+    def parse():
+        return lib.aej_png_parse_host_accept(ctypes.addressof(buf), n, accept, ctypes.addressof(d), spans.ctypes.data, len(spans), ctypes.addressof(msg), 256)
+
+    rc = parse()
     if rc == AEJ_ERR_CAPACITY:                           # more IDAT chunks than the first guess: the count is known now
         spans = np.zeros((d.n_idat, 2), np.int64)
-        rc = lib.aej_png_parse_host(ctypes.addressof(buf), n, ctypes.addressof(d), spans.ctypes.data, len(spans), ctypes.addressof(msg), 256)
+        rc = parse()
+    if rc == AEJ_ERR_UNSUPPORTED:
+        for text, keyword in _HINTS:
+            if msg.value.decode() == text:
+                raise NotImplementedError(f"file {index}: {text}; pass {keyword} to png_decode_many or png_parse_header")
     _refuse(rc, msg, index)
     d.idat_spans = spans[:d.n_idat]
     return d
@@ -57,10 +98,15 @@ def _check_modes(mode, n):
 
 
 def _out_channels(d, mode) -> int:
-    return 3 if mode == "RGB" or d.colour_type == 3 else d.channels
+    """bytes per pixel of the image written (png_out_channels of csrc/api_png.hip)"""
+    if mode == "RGB" or d.colour_type == 3:
+        return 3
+    if d.bit_depth == 16:
+        return {0: 2, 2: 3, 4: 4, 6: 4}[d.colour_type]
+    return d.channels
 
 
-def _inflate_on_host(ctx, streams, raw, in_off, sizes, workers):
+def _inflate_on_host(ctx, streams, raw, in_off, sizes, interlaced, workers):
     """inflate="host": zlib.decompress of every file's stream on a thread pool, each result through a page-locked buffer into its slot of
     ``raw``.  Raises ValueError naming the file for a stream zlib refuses or that inflates to another size than the header's."""
     t = ctx.torch
@@ -84,7 +130,8 @@ def _inflate_on_host(ctx, streams, raw, in_off, sizes, workers):
             if isinstance(data, zlib.error):
                 raise ValueError(f"file {i}: the zlib stream of its IDAT chunks does not inflate ({data})")
             if len(data) != sizes[i]:
-                raise ValueError(f"file {i}: inflated size {len(data)} is not height x (1 + row bytes) = {sizes[i]}")
+                raise ValueError(f"file {i}: inflated size {len(data)} is not height x (1 + row bytes) = {sizes[i]}" if not interlaced[i] else
+                                 f"file {i}: inflated size {len(data)} is not the sum of its passes' height x (1 + row bytes) = {sizes[i]}")
             done = 0
             while done < sizes[i]:
                 if used == cap:                          # the buffer is full: wait for its copies before refilling it
@@ -98,7 +145,8 @@ def _inflate_on_host(ctx, streams, raw, in_off, sizes, workers):
     t.cuda.current_stream(ctx.device).synchronize()      # the buffer is reused by the next call
 
 
-def png_decode_many(files, mode="RGB", inflate: str = "gpu", device: int = 0, workers: Optional[int] = None) -> List:
+def png_decode_many(files, mode="RGB", inflate: str = "gpu", device: int = 0, workers: Optional[int] = None, interlaced: bool = False,
+                    depth16: bool = False) -> List:
     """Decode PNG files (bytes-like, of mixed sizes and kinds) on the GPU -> a list of device uint8 tensors, one per file, in file order.
 
     ``mode`` is one value for all files or one per file.  "RGB": [H, W, 3], equal to ``np.asarray(Image.open(f).convert("RGB"))`` --
@@ -110,25 +158,37 @@ def png_decode_many(files, mode="RGB", inflate: str = "gpu", device: int = 0, wo
 
     Supported: non-interlaced files of colour type 0 (1, 2, 4, 8 bits), 2 (8), 3 (1, 2, 4, 8), 4 (8) and 6 (8), any number of IDAT chunks
     (empty ones and ones that split the zlib header included); unknown ancillary chunks are skipped; no gamma, ICC or sRGB handling, as
-    Pillow applies none on open.  16-bit samples, Adam7 interlace and APNG frames raise NotImplementedError("file i: ..."); a malformed
-    file (``png_parse_header``) raises ValueError("file i: ..."), both before any device work.
+    Pillow applies none on open.  Without their keywords 16-bit samples and Adam7 interlace raise NotImplementedError("file i: ...",
+    naming the keyword), as APNG frames always do; a malformed file (``png_parse_header``) raises ValueError("file i: ..."), both
+    before any device work.
+
+    ``interlaced=True`` also takes Adam7-interlaced files of every supported kind, mixed freely with the others: such a file gives, in
+    either mode, exactly what the non-interlaced file of the same samples gives.  ``depth16=True`` also takes files of bit depth 16
+    (colour types 0, 2, 4, 6), interlaced or not.  Pillow keeps the HIGH BYTE of a 16-bit sample, except for grey: "RGB" gives the high
+    bytes of R, G, B (colour types 2, 6) or of the grey sample three times (4), but for colour type 0 the sample CLIPPED to 255 --
+    ``min(v, 255)`` three times, not a shift: that is what Pillow's ``convert("RGB")`` of its mode "I;16" does, however odd.  "auto":
+    colour type 2 gives uint8 [H, W, 3], 4 and 6 uint8 [H, W, 4] (Pillow opens 16-bit grey + alpha as "RGBA": grey, grey, grey, alpha),
+    and colour type 0 a ``torch.uint16`` [H, W] tensor of the whole samples in host byte order (mode "I;16"), equal to
+    ``np.asarray(Image.open(f))`` -- a view of the same packed allocation as the other images, its offset rounded up to 2 bytes.  A
+    value of either keyword that is not a bool raises TypeError.
 
     ``inflate="gpu"`` (default): the joined IDAT bytes of all files cross in one page-locked copy and ``aej_inflate_batch`` decodes them,
     one wave per file.  ``inflate="host"``: ``zlib.decompress`` per file on a thread pool (``workers``, at most 16) and the filtered
     scanlines are uploaded.  With either, the un-filter and the layout conversion run on the device and nothing is read back but the
-    status words, once per call: a stream that does not inflate, an inflated size other than H x (1 + row bytes) and a filter byte above
-    4 raise ValueError naming the file (the first such file of the call); the other files of the call are not affected.
+    status words, once per call: a stream that does not inflate, an inflated size other than H x (1 + row bytes) (of an interlaced file:
+    other than the sum of that over its non-empty passes) and a filter byte above 4 raise ValueError naming the file (the first such file of the call); the other files of the call are not affected.
 
     DEPARTURE FROM PILLOW: IDAT chunk CRCs are not checked; the Adler-32 of the inflated data is, on the device (by zlib with
     ``inflate="host"``).  A file whose only damage is an IDAT CRC therefore decodes here, where Pillow raises."""
     if inflate not in ("gpu", "host"):
         raise ValueError("inflate must be 'gpu' or 'host'")
+    _accept(interlaced, depth16)
     files = list(files)
     n = len(files)
     modes = _check_modes(mode, n)
     if n == 0:
         return []
-    parsed = [png_parse_header(f, i) for i, f in enumerate(files)]
+    parsed = [png_parse_header(f, i, interlaced, depth16) for i, f in enumerate(files)]
     return _decode_parsed(get_context(device), parsed, [memoryview(f).cast("B") for f in files], modes, inflate, workers)
 
 
@@ -145,14 +205,17 @@ def _decode_parsed(ctx, parsed, views, modes, inflate, workers, events=None):
     def align(v, a=4):
         return (v + a - 1) // a * a
 
-    sizes = [d.height * (1 + d.row_bytes) for d in parsed]
-    in_off, out_off, shapes = np.zeros(n, np.int64), np.zeros(n, np.int64), []
+    sizes = [d.raw_bytes for d in parsed]
+    in_off, out_off, shapes, wide = np.zeros(n, np.int64), np.zeros(n, np.int64), [], []
     ipos = opos = 0
     for i, d in enumerate(parsed):
         in_off[i], out_off[i] = ipos, opos
         ipos += align(sizes[i])
         c = _out_channels(d, modes[i])
-        shapes.append((d.height, d.width) if c == 1 and modes[i] == "auto" else (d.height, d.width, c))
+        wide.append(d.bit_depth == 16 and d.colour_type == 0 and modes[i] == "auto")      # "I;16": two bytes a pixel, one uint16
+        if wide[i]:
+            out_off[i] = opos = align(opos, 2)
+        shapes.append((d.height, d.width) if modes[i] == "auto" and (c == 1 or wide[i]) else (d.height, d.width, c))
         opos += d.height * d.width * c
     raw = ctx.empty((ipos,), t.uint8)
     out = ctx.empty((opos,), t.uint8)
@@ -183,7 +246,7 @@ def _decode_parsed(ctx, parsed, views, modes, inflate, workers, events=None):
         else:
             streams.append(b"".join(pieces))
     if inflate == "host":
-        _inflate_on_host(ctx, streams, raw, in_off, sizes, workers)
+        _inflate_on_host(ctx, streams, raw, in_off, sizes, [d.interlace for d in parsed], workers)
     dev = ctx.empty((total,), t.uint8)
     dev.copy_(ctx.pinned(total)[:total], non_blocking=True)
     base = dev.data_ptr()
@@ -216,7 +279,10 @@ def _decode_parsed(ctx, parsed, views, modes, inflate, workers, events=None):
         if s[1, i]:
             code = int(s[1, i])
             raise ValueError(f"file {i}: {PNG_STATUS[code] if 0 <= code < len(PNG_STATUS) else f'status {code}'}")
-    return packed_views(out, out_off, shapes)
+    if not any(wide):
+        return packed_views(out, out_off, shapes)
+    return [out[int(o):int(o) + 2 * s[0] * s[1]].view(t.uint16).view(*s) if w else packed_views(out, [o], [s])[0]
+            for o, s, w in zip(out_off, shapes, wide)]
 
 
 # ---- encode -------------------------------------------------------------------------------------------------------------------------

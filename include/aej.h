@@ -1067,8 +1067,9 @@ AEJ_API int aej_resample_batch_win(aej_ctx *ctx, const aej_resample_desc *descs_
                                    uint64_t workspace_bytes);
 
 /* ---- PNG files decoded on the device (png_decode_many) ------------------------------------------------------------------------------
- * Pixel-identical to PIL.Image.open(file).convert("RGB"), or to the image in Pillow's own mode, for non-interlaced files of colour type
- * 0 (grey: 1, 2, 4, 8 bits), 2 (RGB: 8), 3 (palette: 1, 2, 4, 8), 4 (grey + alpha: 8) and 6 (RGBA: 8).  The zlib stream of a file -- its
+ * Pixel-identical to PIL.Image.open(file).convert("RGB"), or to the image in Pillow's own mode, for files of colour type
+ * 0 (grey: 1, 2, 4, 8, 16 bits), 2 (RGB: 8, 16), 3 (palette: 1, 2, 4, 8), 4 (grey + alpha: 8, 16) and 6 (RGBA: 8, 16), Adam7-interlaced
+ * or not (a parser hands out 16-bit and interlaced descriptors only when asked: aej_png_parse_host_accept).  The zlib stream of a file -- its
  * IDAT chunks joined -- is inflated by aej_inflate_batch (or by the host); the scanline un-filter and the expansion to the output layout
  * run in csrc/png.hip.  IDAT chunk CRCs are not checked (the Adler-32 of the inflated data is, on the device).  No gamma, ICC or sRGB
  * handling, as Pillow applies none on open.
@@ -1080,19 +1081,32 @@ AEJ_API int aej_resample_batch_win(aej_ctx *ctx, const aej_resample_desc *descs_
  *   unknown critical chunk, a side above 2^24); AEJ_ERR_ARG for a malformed file (bad signature, missing IHDR / PLTE / IDAT, a bad CRC
  *   on IHDR, PLTE or tRNS, zero width or height, a bit depth the colour type does not allow, a chunk length that runs past the file).
  *   msg (may be NULL) gets the reason.  Unknown ancillary chunks are skipped; tRNS is noted and otherwise ignored.
- * aej_png_workspace_bytes: the workspace of aej_png_unfilter_batch (one carried scanline per file); 0 for bad descriptors.
+ * aej_png_parse_host_accept: the same walk with a word of AEJ_PNG_ACCEPT_* flags (any other bit: AEJ_ERR_ARG); aej_png_parse_host is
+ *   this entry with 0.  AEJ_PNG_ACCEPT_ADAM7 takes interlaced files (desc->interlace = 1; row_bytes stays the full-width scanline),
+ *   AEJ_PNG_ACCEPT_16BIT files of bit depth 16 (mode "I;16" for colour type 0, "RGB" for 2, "RGBA" for 4 and 6, as Pillow opens them).
+ * aej_png_raw_bytes: the inflated size a file of this descriptor must have: height x (1 + row_bytes), or for an interlaced file the sum
+ *   over its non-empty passes of h_p x (1 + row_bytes_p) -- a pass without pixels has no bytes, not even filter bytes.  0 for a bad one.
+ * aej_png_adam7_passes_host: passes_host [7][6] int32 = { x0, y0, dx, dy, w_p, h_p } of the seven passes of a width x height image
+ *   (pass p holds the pixels (x0 + i dx, y0 + j dy); w_p = h_p = 0 for an empty pass).  AEJ_ERR_ARG for a side below 1.
+ * aej_png_workspace_bytes: the workspace of aej_png_unfilter_batch (one carried scanline per file; for an interlaced file one per
+ *   non-empty pass, its pass images and eight status words); 0 for bad descriptors.
  * aej_png_unfilter_batch: n files.  Only enqueues on the context's stream: no synchronisation, no read-back.  inflated: device bytes,
- *   the filtered scanlines of file i -- height x (1 + row_bytes) bytes -- at in_offsets_host[i], a multiple of 4, and with its length
+ *   the filtered scanlines of file i -- aej_png_raw_bytes of them -- at in_offsets_host[i], a multiple of 4, and with its length
  *   rounded up to 4 inside inflated_bytes (whole dwords are read).  inflate_out_bytes / inflate_status: the device arrays
  *   aej_inflate_batch wrote for the n streams, or both NULL for scanlines the host inflated (and whose sizes it has checked).
  *   palettes: device [n][768], the desc's palette of each file (NULL when no file has colour type 3).  layouts_host[i] (NULL: all RGB):
  *   AEJ_PNG_RGB -- [height][width][3]: alpha dropped, grey replicated, indices through the palette (one past its end reads black) -- or
  *   AEJ_PNG_AUTO -- colour type 0: [height][width] (1 bit -> 0 / 255, 2 bits x 85, 4 bits x 17), 4: [..][2], 2: [..][3], 6: [..][4],
- *   3: [..][3] through the palette.  Image i is written at out_offsets_host[i]; nothing else of out is touched.  status: device [n]
+ *   3: [..][3] through the palette; at bit depth 16 colour type 0: [height][width] uint16 in host byte order (Pillow's "I;16"; an even
+ *   offset is the caller's business), 2: [..][3], 4 and 6: [..][4], the high byte of every sample (grey + alpha as Pillow's RGBA: the
+ *   grey three times).  Under AEJ_PNG_RGB a 16-bit sample gives its high byte, but a 16-bit GREY sample is CLIPPED: min(sample, 255),
+ *   which is what Pillow's convert("RGB") of an "I;16" image does.  An interlaced file gives the image of the non-interlaced file with
+ *   the same samples: each pass is un-filtered into the workspace and a second kernel interleaves them.  Image i is written at out_offsets_host[i]; nothing else of out is touched.  status: device [n]
  *   int32, AEJ_PNG_*; a file whose status is not OK leaves its image partly written or untouched, the other files are not affected. */
-enum { AEJ_PNG_OK = 0, AEJ_PNG_INFLATE_FAILED = 1, AEJ_PNG_SIZE_MISMATCH = 2 /* inflated bytes != height * (1 + row_bytes) */,
+enum { AEJ_PNG_OK = 0, AEJ_PNG_INFLATE_FAILED = 1, AEJ_PNG_SIZE_MISMATCH = 2 /* inflated bytes != height * (1 + row_bytes), or != aej_png_raw_bytes */,
        AEJ_PNG_BAD_FILTER = 3 /* a filter byte above 4 */ };
 enum { AEJ_PNG_RGB = 0, AEJ_PNG_AUTO = 1 };
+enum { AEJ_PNG_ACCEPT_ADAM7 = 1, AEJ_PNG_ACCEPT_16BIT = 2 };
 typedef struct aej_png_desc {
     int32_t width, height;
     int32_t bit_depth, colour_type;
@@ -1104,10 +1118,14 @@ typedef struct aej_png_desc {
     int32_t has_trns;
     int64_t idat_bytes;            /* their data bytes together: the length of the zlib stream */
     uint8_t palette[768];          /* PLTE, zero past palette_len */
-    char mode[8];                  /* Pillow's mode of the opened file: "1", "L", "P", "RGB", "LA", "RGBA" */
+    char mode[8];                  /* Pillow's mode of the opened file: "1", "L", "P", "RGB", "LA", "RGBA", "I;16" */
 } aej_png_desc;
 AEJ_API int aej_png_parse_host(const uint8_t *data_host, uint64_t nbytes, aej_png_desc *desc_host, int64_t *spans_host, int span_capacity,
                                char *msg, int msg_capacity);
+AEJ_API int aej_png_parse_host_accept(const uint8_t *data_host, uint64_t nbytes, uint32_t accept, aej_png_desc *desc_host, int64_t *spans_host,
+                                      int span_capacity, char *msg, int msg_capacity);
+AEJ_API uint64_t aej_png_raw_bytes(const aej_png_desc *desc_host);
+AEJ_API int aej_png_adam7_passes_host(int width, int height, int32_t *passes_host);
 AEJ_API uint64_t aej_png_workspace_bytes(aej_ctx *ctx, const aej_png_desc *descs_host, int n);
 AEJ_API int aej_png_unfilter_batch(aej_ctx *ctx, const aej_png_desc *descs_host, int n, const uint8_t *inflated, uint64_t inflated_bytes,
                                    const int64_t *in_offsets_host, const int64_t *inflate_out_bytes, const int32_t *inflate_status,
