@@ -12,7 +12,8 @@ on the device, pixel-identical to Pillow, and ``png_encode_many`` writes them th
 ``adjust_many`` is ``ImageEnhance`` (``Brightness``, ``Contrast``, ``Color``, ``Sharpness``) and the point operations of ``ImageOps`` (``AutoContrast``, ``Equalize``,
 ``Posterize``, ``Solarize``, ``Invert``, ``Grayscale``) and ``Image.point``, one op or a chain per image, and ``histogram_many`` is ``Image.histogram``;
 ``paste_many``, ``alpha_composite_many``, ``blend_many``, ``composite_many`` and ``chop_many`` are ``Image.paste`` (with every mask Pillow takes), ``Image.alpha_composite``,
-``Image.blend``, ``Image.composite`` and ``ImageChops`` for lists of image pairs.  The arithmetic runs in hand-written HIP kernels behind the
+``Image.blend``, ``Image.composite`` and ``ImageChops`` for lists of image pairs; ``convert_many`` is ``Image.convert`` between "L", "LA", "RGB", "RGBA", "YCbCr",
+"HSV" and "CMYK" (and ``convert(mode, matrix)``), ``hue_many`` torchvision's ``adjust_hue`` and ``colorize_many`` ``ImageOps.colorize``.  The arithmetic runs in hand-written HIP kernels behind the
 C ABI of ``libaejpeg_hip.so`` (include/aej.h); there is no CPU fallback.
 """
 from ._lib import _look_at_hw_queues, configure_hw_queues, hw_queues, set_hw_queues
@@ -24,6 +25,8 @@ _look_at_hw_queues()
 
 from .adjust import (AutoContrast, Brightness, Color, Colorize, Contrast, Equalize, Grayscale, Hue, Invert, Point, Posterize, Sharpness, Solarize,  # noqa: E402
                      adjust_many, adjust_plan, histogram_many)
+# (the submodule convert.py is imported BEFORE the function of the same name: the package attribute `convert` stays the function)
+from .convert import colorize_many, convert_many, convert_plan, hue_many  # noqa: E402
 from .color import apply_normalization, convert, get_color_spaces  # noqa: E402
 from .compose import ChopAdd, ChopSubtract, alpha_composite_many, blend_many, chop_many, compose_plan, composite_many, paste_many  # noqa: E402
 from .edge_detection import EdgeDetection  # noqa: E402
@@ -55,4 +58,5 @@ __all__ = ["Jpeg", "JpegCompressionSettings", "EncodedBatch", "Image", "Evaluati
            "transform_many", "rotate_many", "transpose_many", "transform_plan",
            "adjust_many", "histogram_many", "adjust_plan", "Brightness", "Contrast", "Color", "Sharpness", "AutoContrast", "Equalize", "Posterize",
            "Solarize", "Invert", "Grayscale", "Point", "Colorize", "Hue",
-           "paste_many", "alpha_composite_many", "blend_many", "composite_many", "chop_many", "compose_plan", "ChopAdd", "ChopSubtract"]
+           "paste_many", "alpha_composite_many", "blend_many", "composite_many", "chop_many", "compose_plan", "ChopAdd", "ChopSubtract",
+           "convert_many", "hue_many", "colorize_many", "convert_plan"]

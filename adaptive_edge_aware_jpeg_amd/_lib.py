@@ -253,6 +253,19 @@ class ComposePlan(ctypes.Structure):
                 ("reads_overlay", ctypes.c_int32), ("reads_mask", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
 
 
+class ConvertDesc(ctypes.Structure):
+    """aej_convert_desc (include/aej.h): one image of aej_convert_batch"""
+    _fields_ = [("src_offset", ctypes.c_int64), ("dst_offset", ctypes.c_int64), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("channels", ctypes.c_int32), ("source_mode", ctypes.c_int32), ("target_mode", ctypes.c_int32), ("kind", ctypes.c_int32),
+                ("hue_shift", ctypes.c_int32), ("table", ctypes.c_int32), ("matrix", ctypes.c_float * 12), ("reserved", ctypes.c_int32 * 2)]
+
+
+class ConvertPlan(ctypes.Structure):
+    """aej_convert_plan (include/aej.h): what aej_convert_plan_host makes of one descriptor"""
+    _fields_ = [("out_channels", ctypes.c_int32), ("n_steps", ctypes.c_int32), ("step_from", ctypes.c_int32 * 2), ("step_to", ctypes.c_int32 * 2),
+                ("reserved", ctypes.c_int32 * 2)]
+
+
 class PngDesc(ctypes.Structure):
     """aej_png_desc (include/aej.h): what aej_png_parse_host reads from a file's chunks"""
     _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("bit_depth", ctypes.c_int32), ("colour_type", ctypes.c_int32),
@@ -456,6 +469,10 @@ SIGNATURES = {
     "aej_compose_plan_host": (_I, [_P, _P]),
     "aej_compose_workspace_bytes": (_U64, [_P, _P, _I]),
     "aej_compose_batch": (_I, [_P, _P, _I, _P, _U64, _P, _U64, _P, _U64]),
+    "aej_convert_geometry_host": (_I, [_P]),
+    "aej_convert_plan_host": (_I, [_P, _P]),
+    "aej_convert_workspace_bytes": (_U64, [_P, _P, _I]),
+    "aej_convert_batch": (_I, [_P, _P, _I, _P, _I, _P, _U64, _P, _U64, _P, _U64]),
     "aej_test_jpegprog_coefs": (_I, [_P, _P, _P, _I, _P, _U64, _P, _I, _P, _U64, _P, _P, _U64]),             # include/aej_testing.h (tests only)
     "aej_test_jpegprog_coefs_host": (_I, [_P, _P, _P, _U64, _I, _P, _U64]),                                 # include/aej_testing.h (tests only)
     "aej_test_jpeg_adobe_pixels_host": (_I, [_P, _I64, _I, _I, _P]),                                        # include/aej_testing.h (tests only)

@@ -24,7 +24,7 @@ from histograms counted there.  A chain is evaluated per pixel in registers; onl
 write an intermediate image (to its workspace).
 
 Not built, refused by name with NotImplementedError: ``mask=`` arguments, images of mode "P" and "1", ``ImageOps.colorize``
-(``Colorize``) and hue adjustment (``Hue``)."""
+(``Colorize``) and hue adjustment (``Hue``) as ops of a chain -- ``colorize_many`` and ``hue_many`` (convert.py) are calls of their own."""
 import ctypes
 import math
 
@@ -124,7 +124,7 @@ class Point(_Op):
 
 
 class Colorize(_Op):
-    """``ImageOps.colorize``: not built"""
+    """``ImageOps.colorize``: not built as an op of a chain; ``colorize_many`` (convert.py) is the call"""
     name = "colorize"
 
     def __init__(self, *args, **kwargs):
@@ -132,7 +132,7 @@ class Colorize(_Op):
 
 
 class Hue(_Op):
-    """hue adjustment (``convert("HSV")``): not built"""
+    """hue adjustment (``convert("HSV")``): not built as an op of a chain; ``hue_many`` (convert.py) is the call"""
     name = "hue"
 
     def __init__(self, *args, **kwargs):
@@ -191,7 +191,7 @@ def _describe(chain, C, who, tables):
     ops = []
     for op in chain:
         if op.name in ("colorize", "hue"):
-            raise NotImplementedError(f"{who}: {type(op).__name__} is not built")
+            raise NotImplementedError(f"{who}: {type(op).__name__} is not built as an op of adjust_many: {op.name}_many (convert.py) is the call")
         if getattr(op, "mask", None) is not None:
             raise NotImplementedError(f"{who}: {type(op).__name__}: mask= is not built")
         if op.name in _ONLY_L_RGB and C not in (1, 3):

@@ -836,6 +836,38 @@ hipError_t launch_compose(hipStream_t st, const CpPlan &plan);
 
 }  // namespace aej
 
+// convert.hip: Pillow's Image.convert between its 8-bit modes, hue adjustment and ImageOps.colorize on packed 8-bit images (aej_convert_*)
+namespace aej {
+constexpr int kCvThreads = 256;
+constexpr int kCvChunk = 4096;         // pixels of one image a workgroup takes at a time, in k_adjust_apply's lane groups
+constexpr int kCvMaxGrid = 16384;      // workgroups of a launch; the chunks beyond are reached by striding
+constexpr int kCvMaxSide = 32767;
+struct CvEntry {                       // one image of one launch
+    const unsigned char *in;           // cin bytes a pixel
+    unsigned char *out;                // cout bytes a pixel
+    const unsigned char *table;        // AEJ_CONVERT_TABLE: its 768 bytes
+    long long chunk_base;              // the first chunk of this image in its launch
+    long long npix;
+    int kind, n_steps, hue, ycc;       // ycc: a step reads the YCbCr tables
+    int from[2], to[2];                // AEJ_MODE_* of each step
+    float m[12];
+};
+struct CvLaunch { int cin, cout, first, count; long long chunks; };
+struct CvPlan {
+    std::vector<CvEntry> entries;      // launch by launch, device pointers set (null when only measured)
+    std::vector<CvLaunch> launches;
+    std::vector<unsigned char> tables; // the call's tables, as tables_host has them
+    Spans spans;                       // per image: its source, its output
+    unsigned char *entries_dev, *tables_dev;
+    unsigned long long bytes;          // the workspace
+};
+int convert_resolve(const aej_convert_desc &d, int n_tables, aej_convert_plan &p, const char **why);      // aej_convert_plan_host
+int convert_plan(const aej_convert_desc *descs, int n, const unsigned char *tables_host, int n_tables, void *workspace,
+                 const unsigned char *src, unsigned char *dst, CvPlan &plan, int *bad, const char **why);
+hipError_t launch_convert(hipStream_t st, const CvPlan &plan);
+
+}  // namespace aej
+
 // png.hip: the scanline un-filter of PNG files and their expansion to the output layout (aej_png_unfilter_batch), one workgroup per work
 // item: a non-interlaced file, or one non-empty Adam7 pass of an interlaced one (the kernel finds a pass's geometry from its file's)
 namespace aej {

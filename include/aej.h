@@ -1476,6 +1476,79 @@ AEJ_API uint64_t aej_compose_workspace_bytes(aej_ctx *ctx, const aej_compose_des
 AEJ_API int aej_compose_batch(aej_ctx *ctx, const aej_compose_desc *descs_host, int n, const uint8_t *src, uint64_t src_bytes, uint8_t *dst,
                               uint64_t dst_bytes, void *workspace, uint64_t workspace_bytes);
 
+/* ---- Pillow's Image.convert between its 8-bit modes, hue adjustment and ImageOps.colorize for packed 8-bit images (convert.py,
+ * csrc/convert.hip), bit for bit, for many images of different sizes, channel counts and conversions in one call.  An image is uint8
+ * [h][w][channels], packed; source_mode says what its channels MEAN (AEJ_MODE_*: L 1 band, LA 2, RGB, YCbCr and HSV 3, RGBA and CMYK 4).
+ *
+ * The route.  Image.convert (Pillow 12.2) has a direct converter for: L, LA, RGB and RGBA -> every mode; YCbCr -> L, LA, RGB;
+ * HSV -> RGB; CMYK -> RGB, RGBA, HSV; and a mode to itself (a copy).  Any other pair goes through the source's base mode -- RGB for
+ * YCbCr, HSV and CMYK -- in two steps, the image between them being 8-bit: CMYK -> L is CMYK -> RGB -> L, YCbCr -> HSV goes through RGB.
+ * Both steps run per pixel in registers.  `>>` is an arithmetic shift, clip8 clamps to 0 .. 255, (int) and (float) are C casts.
+ *
+ * One step.  A source with grey meaning (L, LA, and YCbCr when the target is L or LA: its Y) gives g; any other gives r, g, b:
+ *   CMYK -> r, g, b   per band c with k:  nk = 255 - k;  t = c nk + 128;  clip8(nk - (((t >> 8) + t) >> 8))
+ *   YCbCr -> r, g, b  U(coef)[i] = (int)(coef (i - 128) 64 + 0.5) in float64:  r = clip8(y + (U(1.402)[cr] >> 6));
+ *                     g = clip8(y + ((U(-.34414)[cb] + U(-.71414)[cr]) >> 6));  b = clip8(y + (U(1.772)[cb] >> 6))
+ *   HSV -> r, g, b    s == 0: grey v.  Else in float64:  x = h 6.0 / 255.0;  i = floor(x);  f = (float)(x - i);  fs = (float)(s / 255.0);
+ *                     p = round(v (1.0 - fs));  q = round(v (1.0 - fs f));  t = round(v (1.0 - fs (1.0 - f))), C's round, each clip8;
+ *                     i mod 6 selects (v,t,p), (q,v,p), (p,v,t), (p,q,v), (t,p,v), (v,p,q)
+ * and the target takes it:
+ *   L      g, or (r 19595 + g 38470 + b 7471 + 0x8000) >> 16          LA    the same and alpha
+ *   RGB    g, g, g or r, g, b                                          RGBA  the same and alpha
+ *   YCbCr  (g, 128, 128), or with T(coef)[i] = (int)(coef i 64 + 0.5) in float64:  Y = (T(.299)[r] + T(.587)[g] + T(.114)[b]) >> 6;
+ *          Cb = clip8(((T(-.16874)[r] + T(-.33126)[g] + T(.5)[b]) >> 6) + 128);  Cr = clip8(((T(.5)[r] + T(-.41869)[g] + T(-.08131)[b]) >> 6) + 128)
+ *   HSV    (0, 0, g), or:  v = max;  max == min: h = s = 0.  Else in float32:  cr = (float)(max - min);  s = cr / (float)max;
+ *          rc = (float)(max - r) / cr, gc and bc likewise;  h = bc - gc if r is the max, else 2.0 + rc - bc if g is, else 4.0 + gc - rc,
+ *          evaluated in float64 from those float32 values and rounded to float32 once;  h = (float)fmod((double)h / 6.0 + 1.0, 1.0);
+ *          H = clip8((int)((double)h 255.0));  S = clip8((int)((double)s 255.0))
+ *   CMYK   (0, 0, 0, 255 - g), or (255 - r, 255 - g, 255 - b, 0)
+ * Alpha is the source's where it has one (LA, RGBA), else 255.
+ *
+ * AEJ_CONVERT_MODE    the route from source_mode to target_mode.
+ * AEJ_CONVERT_MATRIX  im.convert("L", matrix4) / im.convert("RGB", matrix12): source_mode RGB, target L (matrix[0..3]) or RGB (a row of
+ *                     four per band).  Per band in float32, left to right, each product and sum rounded:
+ *                     v = ((m0 r + m1 g) + m2 b) + m3 + 0.5f;  v <= 0: 0;  v >= 255: 255;  else v truncated.
+ * AEJ_CONVERT_HUE     source_mode RGB or RGBA, target the same: RGB -> HSV, H = (H + hue_shift) & 255, HSV -> RGB; alpha is kept.
+ * AEJ_CONVERT_TABLE   ImageOps.colorize: source_mode L, target RGB: band b = table[b 256 + L] of table number `table` of tables_host
+ *                     (768 bytes each: red, green, blue).
+ *
+ * aej_convert_geometry_host: HOST only: out[0..2] = the pixels of a chunk (one workgroup's share of an image), the threads of a
+ *   workgroup, the largest grid (beyond it workgroups stride).
+ * aej_convert_plan_host: HOST only, no device and no context: the route of ONE descriptor (offsets and table numbers not read).
+ *   Returns the code aej_convert_batch would refuse the descriptor with.
+ * aej_convert_batch: n images.  src / dst: device bytes; image i is read at src + src_offset (width height channels bytes) and written
+ *   at dst + dst_offset, exactly width height out_channels bytes and no other byte of dst; no source image may overlap dst.
+ *   tables_host: n_tables tables of 768 bytes on the HOST (may be NULL when n_tables is 0).  One launch per pair of channel counts of
+ *   the call, each one grid over every image of that pair.  The call uploads its entries and tables once, runs on the context's stream
+ *   and waits once at the end.  Every descriptor is checked before any device work: AEJ_ERR_ARG naming the image for a size below 1 or
+ *   above 32767, an unknown mode or kind, a source_mode whose bands are not `channels`, a MATRIX, HUE or TABLE on modes other than the
+ *   ones above, a matrix entry that is not finite, a hue_shift outside 0 .. 255, a table number outside tables_host, an image outside
+ *   src_bytes / dst_bytes.  Workspace: aej_convert_workspace_bytes with the same descriptors (0 for ones the call refuses). */
+enum { AEJ_MODE_L = 0, AEJ_MODE_LA = 1, AEJ_MODE_RGB = 2, AEJ_MODE_RGBA = 3, AEJ_MODE_YCBCR = 4, AEJ_MODE_HSV = 5, AEJ_MODE_CMYK = 6 };
+enum { AEJ_CONVERT_MODE = 0, AEJ_CONVERT_MATRIX = 1, AEJ_CONVERT_HUE = 2, AEJ_CONVERT_TABLE = 3 };
+#define AEJ_CONVERT_TABLE_BYTES 768
+typedef struct aej_convert_desc {
+    int64_t src_offset, dst_offset;
+    int32_t width, height, channels;
+    int32_t source_mode, target_mode;      /* AEJ_MODE_* */
+    int32_t kind;                  /* AEJ_CONVERT_* */
+    int32_t hue_shift;             /* AEJ_CONVERT_HUE: 0 .. 255, added to H modulo 256 */
+    int32_t table;                 /* AEJ_CONVERT_TABLE: its table in tables_host */
+    float matrix[12];              /* AEJ_CONVERT_MATRIX */
+    int32_t reserved[2];
+} aej_convert_desc;
+typedef struct aej_convert_plan {
+    int32_t out_channels, n_steps; /* n_steps: 1 or 2 conversions (AEJ_CONVERT_HUE: 2; MATRIX and TABLE: 1) */
+    int32_t step_from[2], step_to[2];      /* AEJ_MODE_* of each */
+    int32_t reserved[2];
+} aej_convert_plan;
+AEJ_API int aej_convert_geometry_host(int32_t *out);
+AEJ_API int aej_convert_plan_host(const aej_convert_desc *desc, aej_convert_plan *out);
+AEJ_API uint64_t aej_convert_workspace_bytes(aej_ctx *ctx, const aej_convert_desc *descs_host, int n);
+AEJ_API int aej_convert_batch(aej_ctx *ctx, const aej_convert_desc *descs_host, int n, const uint8_t *tables_host, int n_tables,
+                              const uint8_t *src, uint64_t src_bytes, uint8_t *dst, uint64_t dst_bytes, void *workspace,
+                              uint64_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif
