@@ -129,6 +129,11 @@ struct Carver {
 // ---- api.hip: constant tables and geometry ---------------------------------------------------------------------------------------
 extern const double kMid[7][3], kScale[7][3];
 int check_encode_args(aej_ctx *ctx, int batch, int H, int W);
+// The largest image or plane the codec takes: 2^29 pixels (H x W of one image; sides at most 65535).  Up to there pixel and element
+// indices fit `int` and the byte offsets of a float32 plane `unsigned` (the kernels' 32-bit quantities: LeafWork::coef, the leaves'
+// coefficient offsets, the strip kernel's plane offsets); only the float32 RGB input, 12 bytes a pixel, needs 64-bit addressing.
+constexpr long long kMaxImagePixels = 1ll << 29;
+int check_image_size(aej_ctx *ctx, const char *what, int H, int W);      // AEJ_ERR_UNSUPPORTED above either limit (make_geom and the stage entries)
 int make_geom(aej_ctx *ctx, int space, int B, int H, int W, aej::Geom &g);
 void make_plane_geom(int H, int W, aej::Geom &g);
 int make_qtgeom(aej_ctx *ctx, const aej::Geom &g, int bmin, int bmax, aej::QtGeom &q, bool allow_small_root = false);

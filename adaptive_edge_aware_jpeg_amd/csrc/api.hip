@@ -63,10 +63,19 @@ static void fill_clahe_geom(Geom &g)
     }
 }
 
+int check_image_size(aej_ctx *ctx, const char *what, int H, int W)
+{
+    if (H > 65535 || W > 65535) return fail(ctx, AEJ_ERR_UNSUPPORTED, "%s %dx%d: sides above 65535 pixels are not built (leaf origins travel as 16-bit pairs, LeafWork)", what, H, W);
+    if ((long long)H * W > kMaxImagePixels)
+        return fail(ctx, AEJ_ERR_UNSUPPORTED, "%s %dx%d: more than 2^29 = %lld pixels in one image are not built (element indices and plane byte offsets are 32-bit)",
+                    what, H, W, kMaxImagePixels);
+    return 0;
+}
+
 int make_geom(aej_ctx *ctx, int space, int B, int H, int W, Geom &g)
 {
     memset(&g, 0, sizeof g);
-    if (H > 65535 || W > 65535) return fail(ctx, AEJ_ERR_UNSUPPORTED, "image %dx%d: sides above 65535 pixels are not built (leaf origins travel as 16-bit pairs, LeafWork)", H, W);
+    AEJ_TRY(check_image_size(ctx, "image", H, W));
     g.B = B; g.nl = 3; g.H = H; g.W = W;
     long long off = 0;
     for (int l = 0; l < 3; l++) {

@@ -804,6 +804,7 @@ extern "C" int aej_canny(aej_ctx *ctx, const float *plane, int H, int W, uint8_t
 {
     AEJ_TRY(enter(ctx, __func__));
     if (H < 1 || W < 1) return fail(ctx, AEJ_ERR_ARG, "Input array must be a 2D.");
+    AEJ_TRY(check_image_size(ctx, "plane", H, W));
     if (!plane || !edge || !workspace) return null_buffer(ctx);
     if (workspace_bytes < aej_canny_workspace_bytes(H, W)) return fail(ctx, AEJ_ERR_CAPACITY, "workspace too small");
     AEJ_TRY(bind_device(ctx));
@@ -870,6 +871,7 @@ extern "C" int aej_quadtree(aej_ctx *ctx, const uint8_t *edge, int H, int W, int
 {
     AEJ_TRY(enter(ctx, __func__));
     if (H < 1 || W < 1) return fail(ctx, AEJ_ERR_ARG, "Input array must be a 2D with a single channel.");
+    AEJ_TRY(check_image_size(ctx, "edge map", H, W));
     if (!edge || !leaves || !states || !counts || !workspace) return null_buffer(ctx);
     AEJ_TRY(bind_device(ctx));
     Geom g;
@@ -897,7 +899,7 @@ extern "C" int aej_dct_quant_zigzag(aej_ctx *ctx, const float *norm, int H, int 
     AEJ_TRY(enter(ctx, __func__));
     if (!ctx->has_settings) return fail(ctx, AEJ_ERR_STATE, "aej_set_settings has not been called");
     if (H < 1 || W < 1 || layer < 0 || layer > 2 || n_leaves < 0) return fail(ctx, AEJ_ERR_ARG, "bad argument");
-    if (H > 65535 || W > 65535) return fail(ctx, AEJ_ERR_UNSUPPORTED, "plane %dx%d: sides above 65535 pixels are not built", H, W);
+    AEJ_TRY(check_image_size(ctx, "plane", H, W));
     if (n_leaves == 0) return 0;
     if (!norm || !leaves || !coeffs) return null_buffer(ctx);
     AEJ_TRY(bind_device(ctx));

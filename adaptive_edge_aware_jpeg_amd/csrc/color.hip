@@ -463,7 +463,9 @@ __global__ __launch_bounds__(256) void k_color_planes_strip(const IN *__restrict
         const int tx0 = x0 / g.ctw[0];                 // CLAHE tile column of the strip's first pixel
         const int xedge = (tx0 + 1) * g.ctw[0];        // the one vertical tile edge the strip can meet
         const bool straddle = xedge < x0 + 128 && xedge < g.W;
-        const IN *img = rgb + (long long)b * g.H * g.W * 3;
+        // the strip's first row goes into the base pointer (scalar, 64-bit): a float32 image of 2^29 pixels is 6 GiB, and the per-lane
+        // 32-bit byte offset then spans the strip's own rows only (at most 64 rows of 65535 pixels of 12 bytes: < 2^26)
+        const IN *img = rgb + ((long long)b * g.H + y0) * g.W * 3;
         const long long ibase = (long long)b * g.pstride;
         {
             // (per-thread values are re-derived per strip from a copy of the thread id the compiler cannot see through: hoisted out of
@@ -480,7 +482,7 @@ __global__ __launch_bounds__(256) void k_color_planes_strip(const IN *__restrict
                 unsigned char *u80 = planes_u8 + ibase + g.poff[0];
                 float *normc[2] = { planes_norm + ibase + poff1, planes_norm + ibase + poff2 }, *rawc[2] = { planes_raw + ibase + poff1, planes_raw + ibase + poff2 };
                 unsigned char *u8c[2] = { planes_u8 + ibase + poff1, planes_u8 + ibase + poff2 };
-                unsigned ioff = (unsigned)(ya * g.W + px) * (3u * (unsigned)sizeof(IN));      // byte offset inside the image: < 2^32
+                unsigned ioff = (unsigned)((ya - y0) * g.W + px) * (3u * (unsigned)sizeof(IN));      // byte offset inside the strip's rows: < 2^26
                 unsigned o_l = (unsigned)(ya * g.w[0] + px);
                 unsigned o_c = RH == 2 ? (unsigned)((ya >> 1) * g.w[1] + (px >> 1)) : (unsigned)(ya * g.w[1] + (px >> 2));
                 // element offsets of the NORMALISED planes (what the DCT kernels read): the same as o_l / o_c when those planes are row-major;
