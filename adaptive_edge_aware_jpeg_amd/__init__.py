@@ -8,7 +8,7 @@ pixel-identical to Pillow), ``resize_many`` (``Image.resize``) and ``standard_jp
 both pixel-identical to Pillow too; ``standard_jpeg_encode_many`` encodes images of mixed sizes and qualities in one call and
 ``standard_jpeg_thumbnail_jpeg_many`` goes from JPEG files to their JPEG thumbnails on the device; ``png_decode_many`` decodes PNG files
 on the device, pixel-identical to Pillow, and ``png_encode_many`` writes them there with Pillow's scanline filtering; ``filter_many`` is ``Image.filter`` with Pillow's ``BoxBlur``,
-``GaussianBlur`` and ``UnsharpMask``, its ``Kernel`` (``SHARPEN`` and the other built-ins), rank (``MedianFilter`` ...) and mode filters, pixel-identical as well;
+``GaussianBlur`` and ``UnsharpMask``, its ``Kernel`` (``SHARPEN`` and the other built-ins), rank (``MedianFilter`` ...) and mode filters and its ``Color3DLUT``, pixel-identical as well;
 ``adjust_many`` is ``ImageEnhance`` (``Brightness``, ``Contrast``, ``Color``, ``Sharpness``) and the point operations of ``ImageOps`` (``AutoContrast``, ``Equalize``,
 ``Posterize``, ``Solarize``, ``Invert``, ``Grayscale``) and ``Image.point``, one op or a chain per image, and ``histogram_many`` is ``Image.histogram``;
 ``paste_many``, ``alpha_composite_many``, ``blend_many``, ``composite_many`` and ``chop_many`` are ``Image.paste`` (with every mask Pillow takes), ``Image.alpha_composite``,
@@ -31,8 +31,8 @@ from .color import apply_normalization, convert, get_color_spaces  # noqa: E402
 from .compose import ChopAdd, ChopSubtract, alpha_composite_many, blend_many, chop_many, compose_plan, composite_many, paste_many  # noqa: E402
 from .edge_detection import EdgeDetection  # noqa: E402
 from .evaluation_metrics import EvaluationMetrics  # noqa: E402
-from .filters import (BLUR, CONTOUR, DETAIL, EDGE_ENHANCE, EDGE_ENHANCE_MORE, EMBOSS, FIND_EDGES, SHARPEN, SMOOTH, SMOOTH_MORE, BoxBlur, GaussianBlur, Kernel,  # noqa: E402
-                      MaxFilter, MedianFilter, MinFilter, ModeFilter, RankFilter, UnsharpMask, filter_many)
+from .filters import (BLUR, CONTOUR, DETAIL, EDGE_ENHANCE, EDGE_ENHANCE_MORE, EMBOSS, FIND_EDGES, SHARPEN, SMOOTH, SMOOTH_MORE, BoxBlur, Color3DLUT, GaussianBlur, Kernel,  # noqa: E402
+                      MaxFilter, MedianFilter, MinFilter, ModeFilter, RankFilter, UnsharpMask, filter_many, lut3d_plan)
 from .geometry import rotate_many, transform_many, transform_plan, transpose_many  # noqa: E402
 from .image import Image  # noqa: E402
 from .jpeg import EncodedBatch, Jpeg  # noqa: E402
@@ -53,7 +53,7 @@ __all__ = ["Jpeg", "JpegCompressionSettings", "EncodedBatch", "Image", "Evaluati
            "resize_many", "standard_jpeg_thumbnail_many", "thumbnail_plan", "standard_jpeg_encode_many", "standard_jpeg_thumbnail_jpeg_many",
            "encode_groups", "transform_prefix", "transform_crop_box", "decode_box_window", "decode_box_stats", "resized_crop_plan",
            "standard_jpeg_resized_crop_many", "png_decode_many", "png_parse_header", "png_adam7_passes", "png_encode_many",
-           "BoxBlur", "GaussianBlur", "UnsharpMask", "filter_many", "Kernel", "RankFilter", "MedianFilter", "MinFilter", "MaxFilter", "ModeFilter",
+           "BoxBlur", "GaussianBlur", "UnsharpMask", "filter_many", "Kernel", "RankFilter", "MedianFilter", "MinFilter", "MaxFilter", "ModeFilter", "Color3DLUT", "lut3d_plan",
            "BLUR", "CONTOUR", "DETAIL", "EDGE_ENHANCE", "EDGE_ENHANCE_MORE", "EMBOSS", "FIND_EDGES", "SHARPEN", "SMOOTH", "SMOOTH_MORE",
            "transform_many", "rotate_many", "transpose_many", "transform_plan",
            "adjust_many", "histogram_many", "adjust_plan", "Brightness", "Contrast", "Color", "Sharpness", "AutoContrast", "Equalize", "Posterize",

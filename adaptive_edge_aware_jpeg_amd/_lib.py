@@ -206,6 +206,13 @@ class WindowDesc(ctypes.Structure):
                 ("scale", ctypes.c_float), ("offset", ctypes.c_float), ("kernel", ctypes.c_float * 25), ("reserved", ctypes.c_int32)]
 
 
+class Lut3dDesc(ctypes.Structure):
+    """aej_lut3d_desc (include/aej.h): one image of aej_lut3d_batch"""
+    _fields_ = [("src_offset", ctypes.c_int64), ("dst_offset", ctypes.c_int64), ("height", ctypes.c_int32), ("width", ctypes.c_int32),
+                ("channels_in", ctypes.c_int32), ("channels_out", ctypes.c_int32), ("table_channels", ctypes.c_int32),
+                ("size", ctypes.c_int32 * 3), ("table", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class WarpDesc(ctypes.Structure):
     """aej_warp_desc (include/aej.h): one image of aej_warp_batch"""
     _fields_ = [("src_offset", ctypes.c_int64), ("dst_offset", ctypes.c_int64), ("src_w", ctypes.c_int32), ("src_h", ctypes.c_int32),
@@ -456,6 +463,10 @@ SIGNATURES = {
     "aej_window_geometry_host": (_I, [_P]),
     "aej_window_workspace_bytes": (_U64, [_P, _P, _I]),
     "aej_window_batch": (_I, [_P, _P, _I, _P, _U64, _P, _U64, _P, _U64]),
+    "aej_lut3d_prepare_host": (_I, [_P, _I64, _P]),
+    "aej_lut3d_geometry_host": (_I, [_P]),
+    "aej_lut3d_workspace_bytes": (_U64, [_P, _P, _I]),
+    "aej_lut3d_batch": (_I, [_P, _P, _I, _P, _P, _I, _P, _U64, _P, _U64, _P, _U64]),
     "aej_warp_geometry_host": (_I, [_P]),
     "aej_warp_plan_host": (_I, [_P, _P, _P, _I64]),
     "aej_warp_workspace_bytes": (_U64, [_P, _P, _I]),

@@ -710,6 +710,39 @@ hipError_t launch_window(hipStream_t st, const WnPlan &plan, unsigned char *blob
 
 }  // namespace aej
 
+// lut3d.hip: Pillow's Color3DLUT on packed 8-bit images of 3 and 4 channels (aej_lut3d_*)
+namespace aej {
+constexpr int kLtThreads = 512;        // eight waves
+constexpr int kLtRun = 4;              // adjacent pixels a lane takes at a time: 3 or 4 dwords in, 3 or 4 out
+constexpr int kLtTile = 2 * kLtThreads * kLtRun;      // pixels of a workgroup
+struct LtEntry {                       // one image of one launch (device pointers set by lut3d_blob)
+    const unsigned char *in;
+    unsigned char *out;
+    const uint2 *table;                // its table, every entry four INT16 (a 3-channel entry padded)
+    long long tile_base;               // the first workgroup of this image in its launch
+    long long npix;
+    unsigned scale[3];                 // (s_d - 1) / 255 in 18 fraction bits
+    int s1, s12;                       // the steps of axis 2 and axis 3, in entries
+    int entries;                       // s1 * s2 * s3
+    int pad;
+};
+struct LtLaunch { int ci, tc, co, first, count; long long tiles; };
+struct LtPlan {
+    std::vector<LtEntry> entries;      // launch by launch; in / out / table hold nothing yet
+    std::vector<int> image;            // the image of each entry
+    std::vector<LtLaunch> launches;
+    std::vector<long long> table_at;   // per table: its first entry in the padded upload; one more: the end
+    std::vector<int> table_tc;         // per table: its channels (0: no image uses it)
+    Spans spans;                       // per image: its source, its output
+};
+int lut3d_plan(const aej_lut3d_desc *descs, int n, const long long *table_offsets, int n_tables, LtPlan &plan, int *bad, const char **why);
+int lut3d_prepare(const float *table, long long n, short *out);      // aej_lut3d_prepare_host
+void lut3d_blob(const LtPlan &plan, const aej_lut3d_desc *descs, const short *tables_host, const long long *table_offsets, const unsigned char *src,
+                unsigned char *dst, const uint2 *tables_dev, std::vector<LtEntry> &blob, std::vector<short> &padded);
+hipError_t launch_lut3d(hipStream_t st, const LtPlan &plan, unsigned char *blob_dev, const LtEntry *blob_host, uint2 *tables_dev, const short *padded);
+
+}  // namespace aej
+
 // warp.hip: Pillow's Image.transform and Image.transpose on packed 8-bit images of 1 to 4 channels (aej_warp_*)
 namespace aej {
 constexpr int kWpThreads = 256;

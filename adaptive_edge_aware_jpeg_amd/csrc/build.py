@@ -8,7 +8,7 @@ import sys
 from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = ["api.hip", "api_encode.hip", "api_decode.hip", "api_metrics.hip", "api_jpeg.hip", "api_resample.hip", "api_png.hip", "api_filter.hip", "api_window.hip", "api_warp.hip", "api_adjust.hip", "api_compose.hip", "api_convert.hip", "color.hip", "canny.hip", "quadtree.hip", "dct.hip", "decode.hip", "metrics.hip", "deflate.hip", "inflate.hip", "headers.hip", "requant.hip", "lpips.hip", "jfif.hip", "jpegdec.hip", "jpegprog.hip", "jpegparse.hip", "jfifprog.hip", "jfiftrans.hip", "jfifmany.hip", "resample.hip", "png.hip", "filter.hip", "window.hip", "warp.hip", "adjust.hip", "compose.hip", "convert.hip"]
+SOURCES = ["api.hip", "api_encode.hip", "api_decode.hip", "api_metrics.hip", "api_jpeg.hip", "api_resample.hip", "api_png.hip", "api_filter.hip", "api_window.hip", "api_lut3d.hip", "api_warp.hip", "api_adjust.hip", "api_compose.hip", "api_convert.hip", "color.hip", "canny.hip", "quadtree.hip", "dct.hip", "decode.hip", "metrics.hip", "deflate.hip", "inflate.hip", "headers.hip", "requant.hip", "lpips.hip", "jfif.hip", "jpegdec.hip", "jpegprog.hip", "jpegparse.hip", "jfifprog.hip", "jfiftrans.hip", "jfifmany.hip", "resample.hip", "png.hip", "filter.hip", "window.hip", "lut3d.hip", "warp.hip", "adjust.hip", "compose.hip", "convert.hip"]
 HEADERS = ["aej_common.h", "aej_launch.h", "aej_ctx.h", "aej_spans.h", "aej_sched.h", "aej_devmath.h", "inv_constants.h", "pow_tables.h", "aej_mfma.h", "aej_bigblock.h", "aej_quant.h", "jpegdec_core.h", "jpegprog_core.h", "jfif_huff_core.h", "jfif_prog_core.h", "jfif_restart_core.h", "jfif_stream_core.h", "jfif_transform_core.h", "jfif_arith.h", "jfif_many_core.h", os.path.join("..", "..", "include", "aej.h"),
            os.path.join("..", "..", "include", "aej_testing.h")]
 LIB = os.path.join(HERE, "..", "libaejpeg_hip.so")

@@ -19,14 +19,20 @@ LDS: ``Kernel`` -- and the ten built-ins ``SHARPEN``, ``SMOOTH``, ``SMOOTH_MORE`
 ``EDGE_ENHANCE_MORE``, ``EMBOSS``, ``FIND_EDGES``, which are Kernels -- is a 3 x 3 or 5 x 5 float32 convolution in exactly Pillow's
 order of operations (kernel row 0 meets the row below the sample; samples within r of an edge are copies); ``RankFilter``,
 ``MedianFilter``, ``MinFilter`` and ``MaxFilter`` pick the rank-th smallest of a window clamped to the image; ``ModeFilter`` takes the
-most frequent value of a window clipped to the image if it occurs more than twice.  With them ``filter_many`` takes every
-``PIL.ImageFilter`` filter except ``Color3DLUT``, blurs and window filters mixed freely in one call.
+most frequent value of a window clipped to the image if it occurs more than twice.
+
+``Color3DLUT`` is the one filter that works on a pixel, not on its neighbourhood (csrc/lut3d.hip, ``aej_lut3d_*``): the R, G and B
+bytes of an [H, W, 3] or [H, W, 4] image are the coordinates in a table of size 2 .. 65 per axis and 3 or 4 channels, whose eight
+entries around the point are interpolated in integers (include/aej.h has the rule); the output has the channels of the filter's
+``target_mode`` where it names one, else the input's.  The floats of a table become INT16 once per call and distinct table object
+(``aej_lut3d_prepare_host``).  With it ``filter_many`` takes every ``PIL.ImageFilter`` filter, blurs, window filters and tables mixed
+freely in one call.
 
 Departures from Pillow: a negative radius is refused for all three blurs (Pillow refuses it for BoxBlur only and returns garbage for
 the other two); a Kernel scale of 0 -- ``scale=None`` over a zero-sum kernel included -- is refused (Pillow divides by zero and returns
 zeros); a mode size below 1 is refused (Pillow accepts it).  Not built (NotImplementedError): a box radius above 1024, ``|percent|``
-above 1,000,000, a rank size above 15, a mode size above 7 and a ``|kernel[i] / scale|`` or ``|offset|`` above 2^100.  There is no
-CPU fallback.
+above 1,000,000, a rank size above 15, a mode size above 7 and a ``|kernel[i] / scale|`` or ``|offset|`` above 2^100.  A table with a
+NaN is refused (Pillow's result for one is undefined).  There is no CPU fallback.
 """
 import ctypes
 import math
@@ -42,6 +48,7 @@ MAX_PERCENT = 1000000
 MAX_RANK_SIZE = 15
 MAX_MODE_SIZE = 7
 MAX_KERNEL_VALUE = 2.0 ** 100                                    # of |kernel[i] / scale| and |offset|: no partial sum overflows float32
+MODE_BANDS = {"RGB": 3, "YCbCr": 3, "HSV": 3, "LAB": 3, "RGBA": 4, "RGBX": 4, "CMYK": 4, "RGBa": 4}      # the 8-bit modes a Color3DLUT may target
 
 
 class BoxBlur:
@@ -188,6 +195,95 @@ class ModeFilter:
         self.size = size
 
 
+class Color3DLUT:
+    """``PIL.ImageFilter.Color3DLUT``: a table of ``channels`` (3 or 4) values per point of a size[0] x size[1] x size[2] grid over the
+    colour cube (2 .. 65 points an axis), the first axis -- R -- changing fastest; 0.0 is the lowest output value, 1.0 the highest.
+    table: ``channels * size**3`` numbers, or ``size**3`` tuples of ``channels``, or a NumPy array of shape (n * channels,),
+    (n, channels) or (size[2], size[1], size[0], channels).  target_mode: the mode of the result where it differs from the image's
+    (``filter_many`` reads its number of bands).  The checks and their messages are Pillow's."""
+    name = "Color 3D LUT"
+
+    def __init__(self, size, table, channels=3, target_mode=None, _copy_table=True):
+        if channels not in (3, 4):
+            raise ValueError("Only 3 or 4 output channels are supported")
+        self.size = size = self._check_size(size)
+        self.channels = channels
+        self.mode = target_mode
+        items = size[0] * size[1] * size[2]
+        wrong_size = False
+        if isinstance(table, np.ndarray):
+            if table.shape in ((items * channels,), (items, channels), (size[2], size[1], size[0], channels)):
+                table = (table.copy() if _copy_table else table).reshape(items * channels)
+            else:
+                wrong_size = True
+        else:
+            if _copy_table:
+                table = list(table)
+            if table and isinstance(table[0], (list, tuple)):
+                flat = []
+                for pixel in table:
+                    if len(pixel) != channels:
+                        raise ValueError(f"The elements of the table should have a length of {channels}.")
+                    flat.extend(pixel)
+                table = flat
+        if wrong_size or len(table) != items * channels:
+            raise ValueError("The table should have either channels * size**3 float items or size**3 items of channels-sized tuples with floats. "
+                             f"Table should be: {channels}x{size[0]}x{size[1]}x{size[2]}. Actual length: {len(table)}")
+        self.table = table
+
+    @staticmethod
+    def _check_size(size):
+        try:
+            _, _, _ = size
+        except ValueError as e:
+            raise ValueError("Size should be either an integer or a tuple of three integers.") from e
+        except TypeError:
+            size = (size, size, size)
+        size = tuple(int(x) for x in size)
+        if not all(2 <= s <= 65 for s in size):
+            raise ValueError("Size should be in [2, 65] range.")
+        return size
+
+    @classmethod
+    def generate(cls, size, callback, channels=3, target_mode=None):
+        """the table of ``callback(r, g, b)`` -> ``channels`` values at every grid point, the coordinates from 0.0 to 1.0; b is the
+        outermost loop, r the innermost"""
+        s1, s2, s3 = cls._check_size(size)
+        if channels not in (3, 4):
+            raise ValueError("Only 3 or 4 output channels are supported")
+        table = [0] * (s1 * s2 * s3 * channels)
+        at = 0
+        for b in range(s3):
+            for g in range(s2):
+                for r in range(s1):
+                    table[at:at + channels] = callback(r / (s1 - 1), g / (s2 - 1), b / (s3 - 1))
+                    at += channels
+        return cls((s1, s2, s3), table, channels=channels, target_mode=target_mode, _copy_table=False)
+
+    def transform(self, callback, with_normals=False, channels=None, target_mode=None):
+        """a new table of ``callback(*values)`` -- ``callback(r, g, b, *values)`` with_normals -- at every grid point; channels: those
+        of the new table where they change"""
+        if channels not in (None, 3, 4):
+            raise ValueError("Only 3 or 4 output channels are supported")
+        ch_in, ch_out = self.channels, channels or self.channels
+        s1, s2, s3 = self.size
+        table = [0] * (s1 * s2 * s3 * ch_out)
+        at_in = at_out = 0
+        for b in range(s3):
+            for g in range(s2):
+                for r in range(s1):
+                    values = self.table[at_in:at_in + ch_in]
+                    values = callback(r / (s1 - 1), g / (s2 - 1), b / (s3 - 1), *values) if with_normals else callback(*values)
+                    table[at_out:at_out + ch_out] = values
+                    at_in += ch_in
+                    at_out += ch_out
+        return type(self)(self.size, table, channels=ch_out, target_mode=target_mode or self.mode, _copy_table=False)
+
+    def __repr__(self):
+        mode = f" target_mode={self.mode}" if self.mode else ""
+        return "<{} from {} size={:d}x{:d}x{:d} channels={:d}{}>".format(type(self).__name__, type(self.table).__name__, *self.size, self.channels, mode)
+
+
 def filter_plan(kind, xradius, yradius):
     """aej_filter_plan_host (host only, no device): -> dict(passes, box=(x, y), r=(x, y), ww=(x, y), fw=(x, y)), the passes of a
     filter kind ("BoxBlur", "GaussianBlur", "UnsharpMask") and per axis the float32 box radius and the integer weights of a pass.
@@ -219,6 +315,77 @@ def window_geometry():
     g = (ctypes.c_int32 * 5)()
     load_library().aej_window_geometry_host(ctypes.addressof(g))
     return dict(zip(("tile_w", "tile_h", "kernel_halo", "rank_halo", "mode_halo"), (int(v) for v in g)))
+
+
+def lut3d_geometry():
+    """aej_lut3d_geometry_host (host only): -> dict(threads, run, tile): the lanes of a workgroup, the adjacent pixels a lane takes at
+    a time and the pixels of a workgroup."""
+    from ._lib import load_library
+    g = (ctypes.c_int32 * 3)()
+    load_library().aej_lut3d_geometry_host(ctypes.addressof(g))
+    return dict(zip(("threads", "run", "tile"), (int(v) for v in g)))
+
+
+def _check_lut(f, what, cache=None):
+    """an object with ``table``, ``channels`` and ``size`` -> ("lut", size, channels, bands of its target mode or None, its table as
+    INT16).  cache: {id(object): (object, result)} of one call, so that an object given for many images is prepared once and is one
+    table of the call."""
+    if cache is not None and id(f) in cache:
+        return cache[id(f)][1]
+    from ._lib import load_library
+    channels, size, mode = f.channels, f.size, getattr(f, "mode", None)
+    if not is_int(channels) or channels not in (3, 4):
+        raise ValueError(f"{what}: Color3DLUT channels {channels!r}: 3 or 4 required")
+    if is_int(size):
+        size = (size,) * 3
+    if not isinstance(size, (tuple, list)) or len(size) != 3 or not all(is_int(v) and 2 <= v <= 65 for v in size):
+        raise ValueError(f"{what}: Color3DLUT size {size!r}: an int or three ints in [2, 65] required")
+    size = tuple(int(v) for v in size)
+    if mode is not None and (not isinstance(mode, str) or mode not in MODE_BANDS):
+        raise ValueError(f"{what}: Color3DLUT target mode {mode!r}: one of {', '.join(MODE_BANDS)} (8-bit, 3 or 4 bands) or None required")
+    try:
+        table = np.asarray(f.table)
+        if table.dtype.kind not in "fiub":
+            raise TypeError
+        with np.errstate(over="ignore"):
+            table = np.ascontiguousarray(table, np.float32).reshape(-1)      # as Pillow reads every item: a C float
+    except (TypeError, ValueError):
+        raise TypeError(f"{what}: Color3DLUT table: numbers required") from None
+    items = size[0] * size[1] * size[2] * int(channels)
+    if table.size != items:
+        raise ValueError(f"{what}: Color3DLUT table of {table.size} values: {channels}x{size[0]}x{size[1]}x{size[2]} = {items} required")
+    if np.isnan(table).any():
+        raise ValueError(f"{what}: Color3DLUT table holds a NaN")
+    prepared = np.empty(items, np.int16)
+    if load_library().aej_lut3d_prepare_host(table.ctypes.data, items, prepared.ctypes.data):
+        raise ValueError(f"{what}: Color3DLUT table refused")
+    res = ("lut", size, int(channels), None if mode is None else MODE_BANDS[mode], prepared)
+    if cache is not None:
+        cache[id(f)] = (f, res)                        # (holds the object: its id stays its own for the call)
+    return res
+
+
+def _lut_channels_out(channels_in, lut, who):
+    """Pillow's rule by bands alone: the output has the bands of the target mode, else the source's"""
+    _, _, tc, bands, _ = lut
+    if channels_in not in (3, 4):
+        raise ValueError(f"{who}: Color3DLUT takes [H, W, 3] and [H, W, 4] images, got {channels_in} channel{'s' if channels_in > 1 else ''} "
+                         f"(Pillow: image has wrong mode)")
+    co = bands or channels_in
+    if tc == 4 and co == 3:
+        raise ValueError(f"{who}: Color3DLUT with a 4-channel table needs a 4-band result, the {'target mode' if bands else 'image'} has 3 (as Pillow)")
+    if co == 4 and tc == 3 and channels_in == 3:
+        raise ValueError(f"{who}: Color3DLUT with a 3-channel table on a 3-channel image cannot fill a 4-band target mode (as Pillow)")
+    return co
+
+
+def lut3d_plan(channels_in, lut):
+    """What ``filter_many`` does with a Color3DLUT on an image of channels_in channels (host only, no device): -> (channels of the
+    output, bytes of the table as staged on the device -- 8 an entry --, the kernel path: "global", the only one, which reads the
+    table through the caches).  The refusals are ``filter_many``'s, naming "the image"."""
+    res = _check_lut(lut, "the image")
+    co = _lut_channels_out(channels_in, res, "the image")
+    return co, 8 * res[1][0] * res[1][1] * res[1][2], "global"
 
 
 def _f32(v):
@@ -300,15 +467,18 @@ def _halo(plan):
     return tuple(plan["passes"] * (plan["r"][a] + 1) if plan["box"][a] != 0 else 0 for a in (0, 1))
 
 
-def _check_filter(f, what):
+def _check_filter(f, what, luts=None):
     """one filter object -> (kind, xradius, yradius, percent, threshold, plan) for a blur, ("window", kind, size, rank, scale, offset,
-    kernel) for a window filter.  `what` names the image (or "every image") in a refusal.  A class -- ``ImageFilter.SHARPEN`` is one --
-    or any other callable is called for its instance; the filters are told by their attributes, as Pillow's own objects carry them."""
+    kernel) for a window filter, ("lut", ...) for a Color3DLUT (_check_lut, with its cache `luts`).  `what` names the image (or "every
+    image") in a refusal.  A class -- ``ImageFilter.SHARPEN`` is one -- or any other callable is called for its instance; the filters
+    are told by their attributes, as Pillow's own objects carry them."""
     if callable(f):
         try:
             f = f()
         except Exception as e:
             raise ValueError(f"{what}: filter {f!r}: calling it for a filter object failed: {e}") from None
+    if hasattr(f, "table") and hasattr(f, "channels") and hasattr(f, "size"):
+        return _check_lut(f, what, luts)
     name = getattr(f, "name", None)
     if hasattr(f, "filterargs"):
         return _check_kernel(f, what)
@@ -354,47 +524,62 @@ def _check_filter(f, what):
 
 def filter_many(images, filter, device: int = 0, _path: str = "auto") -> list:
     """Filter uint8 [H_i, W_i], [H_i, W_i, 2], [H_i, W_i, 3] and [H_i, W_i, 4] images (Pillow's L, LA, RGB and RGBA; device tensors,
-    host tensors or NumPy arrays, of mixed sizes) on the device: -> list of uint8 device tensors with the shapes of the inputs, views
-    into one packed allocation that never alias an input; element i equals ``np.asarray(Image.fromarray(a_i).filter(F_i))``.
-    filter: one filter for all images, or a list of one per image, blurs and window filters mixed freely: BoxBlur, GaussianBlur,
-    UnsharpMask, Kernel and the ten built-ins (SHARPEN ...), RankFilter, MedianFilter, MinFilter, MaxFilter, ModeFilter.
-    ``PIL.ImageFilter``'s own objects are taken as well -- any object with a blur's ``name`` and ``radius`` (``percent``, ``threshold``),
-    with ``filterargs``, with ``size`` and ``rank``, or named "Mode" with a ``size`` --, and so is a class or another callable that
-    returns one: ``ImageFilter.SHARPEN`` is a class.  An input tensor's ``jpeg_comment`` goes to its output, as Pillow's ``filter``
-    keeps ``im.info``.  Every argument is checked on the host before any device work and a refusal names the image: ValueError for a
-    wrong shape, a side above 65535, a filter list of another length, an unknown filter, a radius that is negative or not finite, a
-    kernel size other than (3, 3) and (5, 5), a kernel of the wrong length or with non-numbers, a kernel value, scale, offset or
-    quotient not finite in float32, a scale of 0, a rank size that is even or below 1, a rank outside [0, size^2), a mode size below
-    1; TypeError for a dtype other than uint8 and a percent, threshold, size or rank that is not an int; NotImplementedError for a box
-    radius above 1024, |percent| above 1,000,000, a rank size above 15, a mode size above 7 and a |kernel / scale| or |offset| above
-    2^100.  _path ("auto", "fused", "passes") picks the blurs' kernel path for tests and A/B runs; "fused" raises ValueError for a
-    blur beyond its halo; images with a window filter ignore it."""
-    from ._lib import FilterDesc, WindowDesc, get_context
+    host tensors or NumPy arrays, of mixed sizes) on the device: -> list of uint8 device tensors with the shapes of the inputs -- but
+    for an image under a Color3DLUT whose target mode has another number of bands, which is [H_i, W_i, bands] --, views into one
+    packed allocation that never alias an input; element i equals ``np.asarray(Image.fromarray(a_i).filter(F_i))``.
+    filter: one filter for all images, or a list of one per image, blurs, window filters and tables mixed freely: BoxBlur,
+    GaussianBlur, UnsharpMask, Kernel and the ten built-ins (SHARPEN ...), RankFilter, MedianFilter, MinFilter, MaxFilter, ModeFilter,
+    Color3DLUT.  ``PIL.ImageFilter``'s own objects are taken as well -- any object with ``table``, ``channels`` and ``size`` (and
+    ``mode``), with a blur's ``name`` and ``radius`` (``percent``, ``threshold``), with ``filterargs``, with ``size`` and ``rank``, or
+    named "Mode" with a ``size`` --, and so is a class or another callable that returns one: ``ImageFilter.SHARPEN`` is a class.  A
+    Color3DLUT takes [H, W, 3] and [H, W, 4] images; its output has the bands of its target mode (RGB, YCbCr, HSV, LAB: 3; RGBA, RGBX,
+    CMYK, RGBa: 4), else the input's: a 3-channel table drops the alpha of a 4-channel image for a 3-band target and copies it
+    otherwise, a 4-channel table writes all four bytes.  One table object given for many images is prepared and uploaded once.
+    An input tensor's ``jpeg_comment`` goes to its output, as Pillow's ``filter`` keeps ``im.info``.  Every argument is checked on the
+    host before any device work and a refusal names the image: ValueError for a wrong shape, a side above 65535, a filter list of
+    another length, an unknown filter, a radius that is negative or not finite, a kernel size other than (3, 3) and (5, 5), a kernel
+    of the wrong length or with non-numbers, a kernel value, scale, offset or quotient not finite in float32, a scale of 0, a rank
+    size that is even or below 1, a rank outside [0, size^2), a mode size below 1, a table size outside [2, 65], table channels other
+    than 3 and 4, a table of the wrong length or with a NaN, a target mode that is not one of the eight, an image of 1 or 2 channels
+    under a table, a 4-channel table for a 3-band result, a 3-channel table on a 3-channel image for a 4-band result; TypeError for a
+    dtype other than uint8, a percent, threshold, size or rank that is not an int and a table with non-numbers; NotImplementedError
+    for a box radius above 1024, |percent| above 1,000,000, a rank size above 15, a mode size above 7 and a |kernel / scale| or
+    |offset| above 2^100.  _path ("auto", "fused", "passes") picks the blurs' kernel path for tests and A/B runs; "fused" raises
+    ValueError for a blur beyond its halo; images with a window filter or a table ignore it."""
+    from ._lib import FilterDesc, Lut3dDesc, WindowDesc, get_context
     images = image_list(images, "filter_many")
     n = len(images)
     if not isinstance(_path, str) or _path not in PATHS:
         raise ValueError(f"_path {_path!r}: 'auto', 'fused' or 'passes' required")
-    filters = one_or_each(filter, n, _check_filter, "filter", "image")
+    luts = {}
+    filters = one_or_each(filter, n, lambda f, what: _check_filter(f, what, luts), "filter", "image")
     if _path == "fused":
         limit = filter_geometry()["max_halo"]
         for i, f in enumerate(filters):
-            if f[0] != "window" and max(_halo(f[5])) > limit:
+            if f[0] not in ("window", "lut") and max(_halo(f[5])) > limit:
                 raise ValueError(f"image {i}: _path 'fused': the filter needs a halo of {max(_halo(f[5]))}, the fused kernel takes {limit}")
     shapes = [image_shape(a, f"image {i}", 65535) for i, a in enumerate(images)]      # (after the filters: a call with both wrong names the filter)
+    out_shapes = [packed_shape(h, w, _lut_channels_out(c, f, f"image {i}") if f[0] == "lut" else c) for i, ((h, w, c), f) in enumerate(zip(shapes, filters))]
     ctx = get_context(device)
     lib = ctx.lib
     # the sources: device tensors are read where they are; NumPy arrays and host tensors cross in one pinned copy
     src = gather_u8(ctx, images)
     base, span, src_off = src.span()
-    # one packed output in input order; the blurs' entry and the window filters' entry each write their own images' bytes into it
-    window = [f[0] == "window" for f in filters]
-    nw = sum(window)
-    descs, wdescs = (FilterDesc * max(n - nw, 1))(), (WindowDesc * max(nw, 1))()
-    out_shapes = [packed_shape(*s) for s in shapes]
+    # one packed output in input order; the blurs' entry, the window filters' entry and the tables' entry each write their own images' bytes into it
+    nw, nl = sum(f[0] == "window" for f in filters), sum(f[0] == "lut" for f in filters)
+    descs, wdescs, ldescs = (FilterDesc * max(n - nw - nl, 1))(), (WindowDesc * max(nw, 1))(), (Lut3dDesc * max(nl, 1))()
     out, offsets = packed_out(ctx, out_shapes)
-    kb, kw = 0, 0
+    kb, kw, kl = 0, 0, 0
+    tables = {}                                        # the call's distinct tables by identity: id -> (index, INT16 array)
     for i, f in enumerate(filters):
-        if window[i]:
+        if f[0] == "lut":
+            d, kl = ldescs[kl], kl + 1
+            d.size[:], d.table_channels, d.channels_out = f[1], f[2], out_shapes[i][2]
+            d.table = tables.setdefault(id(f[4]), (len(tables), f[4]))[0]
+            d.src_offset, d.dst_offset = src_off[i], offsets[i]
+            d.height, d.width, d.channels_in = shapes[i]
+            continue
+        if f[0] == "window":
             d, kw = wdescs[kw], kw + 1
             d.kind, d.size, d.rank, d.scale, d.offset = f[1:6]
             d.kernel[:len(f[6])] = f[6]
@@ -403,8 +588,14 @@ def filter_many(images, filter, device: int = 0, _path: str = "auto") -> list:
             d.kind, d.xradius, d.yradius, d.percent, d.threshold = f[:5]
         d.src_offset, d.dst_offset = src_off[i], offsets[i]
         d.height, d.width, d.channels = shapes[i]
-    if n > nw:
-        run_entry(ctx, lib.aej_filter_workspace_bytes, lib.aej_filter_batch, descs, n - nw, base, span, out, args=(PATHS[_path],))
+    if n > nw + nl:
+        run_entry(ctx, lib.aej_filter_workspace_bytes, lib.aej_filter_batch, descs, n - nw - nl, base, span, out, args=(PATHS[_path],))
     if nw:
-        run_entry(ctx, lib.aej_window_workspace_bytes, lib.aej_window_batch, wdescs, nw, base, span, out)      # (either synchronises: src's staging is free again)
+        run_entry(ctx, lib.aej_window_workspace_bytes, lib.aej_window_batch, wdescs, nw, base, span, out)      # (each synchronises: src's staging is free again)
+    if nl:
+        flat = [t for _, t in tables.values()]
+        table_offsets = np.cumsum([0] + [t.size for t in flat], dtype=np.int64)
+        every = np.ascontiguousarray(np.concatenate(flat) if len(flat) > 1 else flat[0])
+        run_entry(ctx, lib.aej_lut3d_workspace_bytes, lib.aej_lut3d_batch, ldescs, nl, base, span, out,
+                  args=(every.ctypes.data, table_offsets.ctypes.data, len(flat)), query_args=())
     return packed_results(out, offsets, out_shapes, images)

@@ -1247,6 +1247,57 @@ AEJ_API uint64_t aej_window_workspace_bytes(aej_ctx *ctx, const aej_window_desc 
 AEJ_API int aej_window_batch(aej_ctx *ctx, const aej_window_desc *descs_host, int n, const uint8_t *src, uint64_t src_bytes,
                              uint8_t *dst, uint64_t dst_bytes, void *workspace, uint64_t workspace_bytes);
 
+/* ---- Pillow's Color3DLUT for packed 8-bit images of 3 and 4 channels (filter_many, csrc/lut3d.hip) ------------------------------------
+ * Image.filter with ImageFilter.Color3DLUT, bit for bit, for many images of different sizes, channel counts and tables in one call.  An
+ * image is uint8 [h][w][channels_in], packed; its first three bytes are the coordinates in the table, R on axis 1, G on axis 2, B on
+ * axis 3.  A table is INT16 [s3][s2][s1][table_channels] (axis 1 fastest), made from the floats by aej_lut3d_prepare_host.
+ *
+ * aej_lut3d_prepare_host: HOST only, the one place the float -> INT16 rule lives: n floats -> n INT16.  With K = 255 << 6 = 16320:
+ *     v >= (32767 - 0.5) / K -> 32767;  v <= (-32768 + 0.5) / K -> -32768 (both compared in double: +-inf clamp);  otherwise
+ *     p = v * K rounded to FLOAT32, then (int16)(p - 0.5) for v < 0, else (int16)(p + 0.5), the +-0.5 added in double and the
+ *     conversion truncating toward zero.  AEJ_ERR_ARG for a NaN (Pillow's result for one is undefined) and for a NULL pointer.
+ *
+ * Per pixel, with s1, s2, s3 = size and tc = table_channels, all in integers:
+ *     scale_d = (uint32)((s_d - 1) / 255.0 * (1 << 18))          -- once per image, on the host, in double, truncated
+ *     i_d     = byte_d * scale_d;   cell_d = i_d >> 18;   shift_d = (i_d & 0x3FFFF) >> 3          -- shift_d in 0 .. 32767
+ *     base    = tc * (cell_1 + cell_2 * s1 + cell_3 * s1 * s2)
+ *     lerp(a, b, s) = (a * (32768 - s) + b * s) >> 15            -- int32, arithmetic shift, per channel
+ *   along axis 1 four times (the corner pairs at base, base + s1 tc, base + s1 s2 tc, base + (s1 s2 + s1) tc, each with the entry tc
+ *   further on) by shift_1, then along axis 2 twice by shift_2, then along axis 3 by shift_3;  out = clamp((v + 32) >> 6, 0, 255).
+ *   255 divides no s_d - 1 in 1 .. 64, so 255 * scale_d < (s_d - 1) << 18 and cell_d <= s_d - 2: the further corner is always in the
+ *   table.  |a| <= 2^15 and the two weights sum to 2^15, so no product or sum leaves int32.
+ *   (channels_in, table_channels, channels_out): (3, 3, 3); (4, 3, 3) drops the fourth byte; (4, 3, 4) copies the source's fourth byte;
+ *   (3, 4, 4) and (4, 4, 4) take the fourth byte from the table.  (., 4, 3) and (3, 3, 4) are refused, as Pillow refuses them.
+ *
+ * aej_lut3d_geometry_host: HOST only: out[0..2] = the lanes of a workgroup, the adjacent pixels a lane takes at a time and the pixels
+ *   of a workgroup's tile.  (There is no LDS path for small tables: it was measured and not kept, EXPERIMENTS.md.)
+ * aej_lut3d_batch: n images.  src / dst: device bytes; image i is read at src + src_offset (width * height * channels_in bytes) and
+ *   written at dst + dst_offset, exactly width * height * channels_out bytes and no other byte of dst; src and dst must not overlap.
+ *   tables_host: the call's n_tables distinct tables back to back, table t at INT16 elements [table_offsets[t], table_offsets[t + 1])
+ *   (table_offsets has n_tables + 1 entries); a descriptor names its table by index, below n_tables and below n (a call has no use for more tables than
+ *   images; the size query, which is not told n_tables, relies on it), and the images of one table share its upload.
+ *   One launch per (channels_in, table_channels, channels_out) present, one read and one write of the image, the table read through
+ *   the caches; a lane takes four adjacent pixels in dwords, whatever the alignment of the image.
+ *   One upload of the entries and the tables (every entry padded to four INT16), then the call waits for it; nothing is copied back.
+ *   Every descriptor is checked before any device work: AEJ_ERR_ARG naming the image for a side below 1 or above 65535, a size outside
+ *   [2, 65], channel counts other than the five combinations above, a table index outside [0, n_tables), a table whose length is not
+ *   s1 * s2 * s3 * table_channels, an image outside src_bytes / dst_bytes.  Workspace: aej_lut3d_workspace_bytes with the same
+ *   descriptors (0 for ones the call refuses): the entries and the padded tables. */
+typedef struct aej_lut3d_desc {
+    int64_t src_offset, dst_offset;
+    int32_t height, width;
+    int32_t channels_in, channels_out, table_channels;      /* 3 or 4 each */
+    int32_t size[3];               /* s1, s2, s3: 2 .. 65 */
+    int32_t table;                 /* the image's table among the call's distinct tables */
+    int32_t reserved;
+} aej_lut3d_desc;
+AEJ_API int aej_lut3d_prepare_host(const float *table, int64_t n, int16_t *out);
+AEJ_API int aej_lut3d_geometry_host(int32_t *out);
+AEJ_API uint64_t aej_lut3d_workspace_bytes(aej_ctx *ctx, const aej_lut3d_desc *descs_host, int n);
+AEJ_API int aej_lut3d_batch(aej_ctx *ctx, const aej_lut3d_desc *descs_host, int n, const int16_t *tables_host,
+                            const int64_t *table_offsets, int n_tables, const uint8_t *src, uint64_t src_bytes, uint8_t *dst,
+                            uint64_t dst_bytes, void *workspace, uint64_t workspace_bytes);
+
 /* ---- Pillow's Image.transform, rotate and transpose for packed 8-bit images of 1 to 4 channels (geometry.py, csrc/warp.hip) ---------
  * Image.transform with AFFINE, PERSPECTIVE and QUAD under NEAREST, BILINEAR and BICUBIC, and Image.transpose with its seven methods,
  * bit for bit, for many images of different sizes, channel counts, paths and filters in one call.  An image is uint8
